@@ -5,7 +5,12 @@ A "step" is one pass of the hot path (fused dequant + IDCT + chroma upsample + Y
 batch of F synthetic 8K (7680x4320) 4:2:0 baseline frames whose int16 coefficient planes are already
 resident in HBM; pixels are written to HBM.  value = decoded Mpixels/s over all ranks.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--size 8k|4k] [--workload both|headline|batch4k]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--size 8k|4k] [--dump-outputs DIR] [--full [--workload both|headline|batch4k]]
+
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  --dump-outputs DIR then writes what the last
+timed step computed as DIR/pixels.npy (float32, a fixed seeded sample of the output bytes; the inputs are seeded too, so two builds
+can be compared output for output).  --full adds everything else: the check against the oracle, the side measurements below,
+the CPU baselines and the profiler passes.
 
 N > 1: one rank per GPU, RCCL barriers and scalar reductions only (frames are independent, nothing is exchanged).  Started
 either by the driver through torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) or plainly as
@@ -14,7 +19,7 @@ either by the driver through torch.distributed.run (RANK / LOCAL_RANK / WORLD_SI
 for than devices visible, or a WORLD_SIZE that contradicts --gpus, is an error -- never a silent run on fewer GPUs.
 Rank 0 prints ONE JSON line.
 
-Beside the headline the same line carries
+With --full, beside the headline the same line carries
   "batch4k"        BASELINE config 4 as written: 256 distinct 4K 4:2:0 Q85 DRI=8 streams in host memory, image-sharded
                    over the ranks (strong scaling), bytes -> pixels in HBM, each rank on its share of the host cores;
   "roofline_dense" the headline launch on content that defeats the sparse shortcuts (every coefficient non-zero) and on
@@ -64,6 +69,23 @@ def verify_against_oracle(frames):
         got = px.cpu().numpy().reshape(-1)
         ok = ok and got.size == exp.size and bool(np.array_equal(got, exp.reshape(-1)))
     return ok
+
+
+DUMP_SAMPLES = 8 << 20  # float32 values: 32 MB, under the 64 MB an output dump may take
+DUMP_SEED = 5150
+
+
+def dump_outputs(out, directory):
+    """--dump-outputs: `out` (the device tensor the last timed step wrote) -> directory/pixels.npy, float32 values of its bytes at
+    DUMP_SAMPLES positions drawn with DUMP_SEED, in ascending order (every byte when they fit): the same positions for the same
+    arguments, so that the files of two builds compare element for element."""
+    flat = out.reshape(-1)
+    n = flat.numel()
+    if n > DUMP_SAMPLES:
+        idx = torch.randint(0, n, (DUMP_SAMPLES,), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+        flat = flat[idx.to(flat.device)]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "pixels.npy"), flat.to(torch.float32).cpu().numpy())
 
 
 def cpu_baseline(jpeg_bytes, width, height):
@@ -726,8 +748,13 @@ def main():
     ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 --pmc child passes (roofline.traffic = null)")
     ap.add_argument("--no-dense", action="store_true", help="skip roofline_dense")
     ap.add_argument("--no-xt", action="store_true", help="skip xt_profile_c (BASELINE config 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the check against the oracle, the side measurements, the CPU baselines and the profiler passes "
+                         "(the --no-* switches and --workload select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed to DIR/pixels.npy (float32, a fixed seeded sample)")
     ap.add_argument("--workload", default="both", choices=["both", "headline", "batch4k"],
-                    help="headline = the 8K kernel benchmark only; batch4k adds BASELINE config 4 (256 x 4K streams -> pixels, sharded)")
+                    help="with --full: headline = the 8K kernel benchmark only; batch4k adds BASELINE config 4 (256 x 4K streams -> pixels, sharded)")
     ap.add_argument("--batch-frames", type=int, default=256, help="frames of the config 4 batch (256 as written)")
     ap.add_argument("--batch-steps", type=int, default=5)
     ap.add_argument("--traffic-child", default="", help=argparse.SUPPRESS)
@@ -742,6 +769,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     if not launched and not args.traffic_child and not args.emulate_world_child and \
             (args.launcher == "always" or (args.launcher == "auto" and args.gpus > 1)):
@@ -832,9 +861,11 @@ def main():
         kernel_ms = float(t[0])
     assert total_pixels == W * H * F * args.steps * world
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(out, args.dump_outputs)
     # what the timed launches wrote, against the oracle (rank 0's frames; after the timed region, never part of it)
     verified = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             verified = verify_against_oracle([(out[i], jpegs[i % 2]) for i in sorted({0, 1, F - 1})])
         except Exception as e:  # noqa: BLE001 -- reported, never hidden
@@ -864,17 +895,18 @@ def main():
     result["launch"] = {"launched_by": "torch.distributed.run" if launched else "single process", "world": world,
                         "collectives": dist.get_backend() if dist else None, "visible_devices": torch.cuda.device_count()}
     result["verified_note"] = ("frames 0, 1 and F-1 of the output the timed launches wrote, downloaded after the timed region and compared byte for byte "
-                               "with oracle.decode() of their streams (oracle/: the checker, never on the measured path)")
+                               "with oracle.decode() of their streams (oracle/: the checker, never on the measured path)" if args.full else
+                               "not checked: the check against the oracle runs with --full")
 
-    if rank == 0 and world == 1 and not args.no_traffic:
+    if args.full and rank == 0 and world == 1 and not args.no_traffic:
         tb, tnote = measure_traffic(info, host_planes, api.kernel_name(info), F)
         result["roofline"]["traffic"] = tb
         result["roofline"]["traffic_note"] = tnote
     else:
-        result["roofline"]["traffic_note"] = "not measured in this run (N > 1 or --no-traffic)"
+        result["roofline"]["traffic_note"] = "not measured in this run (N > 1, --no-traffic or no --full)"
     # what HBM gives this launch's traffic without the arithmetic (a side measurement: never fails the line)
     mb = os.path.join(ROOT, "tools", "microbench", "stream_ceiling")
-    if rank == 0 and world == 1 and not args.no_traffic and args.subsampling == "420" and os.path.exists(mb):
+    if args.full and rank == 0 and world == 1 and not args.no_traffic and args.subsampling == "420" and os.path.exists(mb):
         try:
             torch.cuda.synchronize()
             t = json.loads(subprocess.run([mb, "--brief"], capture_output=True, text=True, timeout=120).stdout.strip().splitlines()[-1])
@@ -887,7 +919,7 @@ def main():
                         "16-byte-per-lane copy of the same 3 + 3 bytes per pixel; fractions of the same 8 TB/s"}
         except Exception as e:  # noqa: BLE001
             result["roofline"]["traffic_only"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_dense and args.subsampling == "420":
+    if args.full and rank == 0 and world == 1 and not args.no_dense and args.subsampling == "420":
         try:
             result["roofline_dense"] = dense_roofline(info, F, W, H, stream, max(5, args.steps // 2))
         except Exception as e:  # noqa: BLE001
@@ -898,7 +930,7 @@ def main():
             result["roofline_reference_encoded"] = {"error": repr(e)}
 
     # config 4 comes before the single-rank side measurements: with N > 1 every rank takes part in it, and nobody waits for rank 0
-    if args.workload in ("both", "batch4k"):
+    if args.full and args.workload in ("both", "batch4k"):
         del coef, out
         torch.cuda.empty_cache()
         try:
@@ -906,7 +938,7 @@ def main():
             result["batch4k"] = b4
         except Exception as e:  # noqa: BLE001 -- all ranks take the same path: a failure here is symmetric
             result["batch4k"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         # whole decode of one frame through the decoder object: host Huffman (all cores) + streaming H2D +
         # kernel + D2H into host memory.  PCIe/host inclusive -- reported beside, never as `value`.
         user = np.empty((H, W, 3), np.uint8)
@@ -924,14 +956,14 @@ def main():
                                 "phases_ms": {k: round(v * 1e3, 2) for k, v in tm.items()},
                                 "note": "one frame, PCIe and host inclusive: bytes -> host Huffman (restart-interval parallel) -> "
                                         "pinned H2D (streamed) -> kernel -> D2H -> copy into the caller's interleaved bitmap"}
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         # the drop-in boundary from a client's seat: class JPEG through its hooks, one request and the reference CLI's stripe loop
         client = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libjpeg_amd", "bin", "stripe_loop")
         try:
             result["end_to_end"]["drop_in_client"] = drop_in_client(client, jpegs[0], 6) if os.path.exists(client) else {"skipped": "libjpeg_amd/bin/stripe_loop is not built"}
         except Exception as e:  # noqa: BLE001 -- a side measurement never costs the headline number
             result["end_to_end"]["drop_in_client"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         # the same, pipelined over a batch of frames (config 4's end-to-end shape): two decoder objects / streams
         from libjpeg_amd import pipeline
 
@@ -945,7 +977,7 @@ def main():
         result["end_to_end"]["pipelined"] = {"value": round(W * H * nb / dt / 1e6, 1), "unit": "Mpixels/s", "frames": nb,
                                              "ms_per_frame": round(dt / nb * 1e3, 2), "depth": 2,
                                              "note": "two decoder objects / streams, D2H straight into pinned frames; bound by the ~200 MB per 8K frame that cross PCIe"}
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         # the same with the entropy decoding on the device (restart intervals in parallel, csrc/huffman.hip): only the
         # compressed bytes go up.  One frame to host memory, one frame left in HBM, and the two-deep pipeline.
         ts, tr = [], []
@@ -1039,7 +1071,7 @@ def main():
             "restart_interval_mcus": 8, "stream_bytes": len(jpegs[0]),
             "note": "bytes -> header parse + restart marker search on the host -> H2D of the compressed stream -> "
                     "huffman_scan_kernel (one lane per restart interval) -> fused kernel -> D2H of the pixels"}
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         # progressive frames with restart markers: every scan on the device since round 6 (huffman_prog_kernel), host decoder beside it
         try:
             pdata = synth.synth_jpeg(W, H, seed=1234 + 17 * rank, quality=85, subsampling=args.subsampling, restart_mcus=8, progressive=True)
@@ -1063,7 +1095,7 @@ def main():
                         "marker search on the host, every scan one restart interval per lane (DC / AC first passes with EOB runs, refinement passes)"}
         except Exception as e:  # noqa: BLE001 -- a side measurement never costs the headline number
             result["end_to_end"]["progressive"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_end_to_end:
+    if args.full and rank == 0 and world == 1 and not args.no_end_to_end:
         # encoder direction of the block pipeline: forward kernels on frames resident in HBM, and one picture
         # from host memory to a baseline stream (upload, kernels, download of the coefficients, entropy coder on the host)
         try:
@@ -1108,12 +1140,12 @@ def main():
                                            "encoder's tables and coefficients (mijpeg_encode_image)"}}
         except Exception as e:  # a side measurement never costs the headline number
             result["end_to_end"]["encoder_direction"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_xt:
+    if args.full and rank == 0 and world == 1 and not args.no_xt:
         try:
             result["xt_profile_c"] = xt_profile_c(local_rank, stream, not args.no_cpu_baseline)
         except Exception as e:  # noqa: BLE001 -- a side measurement never costs the headline number
             result["xt_profile_c"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             result["cpu_baseline"] = cpu_baseline(jpegs[0], W, H)
             if isinstance(result.get("batch4k"), dict) and result["batch4k"].get("cpu_baseline"):
@@ -1147,10 +1179,11 @@ def main():
                    "progressive_read_ms_host": pick(result, "end_to_end", "progressive", "read_ms_host"),
                    "progressive_read_ms_device": pick(result, "end_to_end", "progressive", "read_ms_prefer_gpu"),
                    "dense_frac": pick(result, "roofline_dense", "dense", "frac"), "reference_encoded_frac": pick(result, "roofline_reference_encoded", "frac")}
-        for k, v in summary.items():
-            if k != "verified":
-                result["config"]["side_" + k] = v
-        result["summary"] = summary
+        if args.full:
+            for k, v in summary.items():
+                if k != "verified":
+                    result["config"]["side_" + k] = v
+            result["summary"] = summary
         print(json.dumps(result))
     if dist:
         dist.barrier()

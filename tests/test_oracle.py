@@ -3,15 +3,32 @@
 1. every committed fixture in tests/golden (pixels produced by the reference binary, see
    tests/golden/make_golden.py) must be reproduced bit-exactly;
 2. when oracle/_ref/jpeg is available (build container), fresh random streams are decoded by both
-   and compared live.
+   and compared live; elsewhere the same cases run on the streams and reference outputs that
+   tests/golden/make_live_reference.py stored under tests/golden/live_reference/.
 These run on CPU (-m "not gpu")."""
 import hashlib
+import json
+import os
 
 import numpy as np
 import pytest
 
-from conftest import BIG_CASES, MANIFEST, P12_CASES, SMALL_CASES, XT_CASES, big_jpeg, golden_jpeg, golden_pixels
+from conftest import BIG_CASES, GOLDEN_DIR, MANIFEST, P12_CASES, SMALL_CASES, XT_CASES, big_jpeg, golden_jpeg, golden_pixels
 from libjpeg_amd import synth
+
+LIVE_DIR = os.path.join(GOLDEN_DIR, "live_reference")
+
+
+def stored_live_case(key):
+    """-> (stream, manifest entry) of a live case as tests/golden/make_live_reference.py stored it with the reference built."""
+    with open(os.path.join(LIVE_DIR, "manifest.json")) as f:
+        ent = json.load(f)[key]
+    with open(os.path.join(LIVE_DIR, key + ".jpg"), "rb") as f:
+        return f.read(), ent
+
+
+def sha256_of(a, dtype):
+    return hashlib.sha256(np.ascontiguousarray(a, dtype).tobytes()).hexdigest()
 
 
 @pytest.mark.parametrize("name", SMALL_CASES)
@@ -58,14 +75,24 @@ def test_oracle_12bit_matches_reference_golden(oracle, name):
     assert hashlib.sha256(np.ascontiguousarray(out, "<u2").tobytes()).hexdigest() == ent["pixels_sha256"]
 
 
+LIVE_XT = [(97, 61, []), (160, 112, ["-s", "1x1,2x2,2x2"]), (48, 80, ["-q", "40", "-Q", "50"])]
+
+
+def live_xt_stream(oracle, w, h, extra):
+    return oracle.reference_encode_hdr(synth.synth_hdr(w, h, w) * 3.0, ["-r", "-q", "85", "-Q", "90", "-h", "-profile", "c", "-r12"] + extra)
+
+
 def test_oracle_xt_vs_live_reference(oracle):
-    if not oracle.have_reference():
-        pytest.skip("oracle/_ref/jpeg not built (needs /root/reference)")
-    for w, h, extra in [(97, 61, []), (160, 112, ["-s", "1x1,2x2,2x2"]), (48, 80, ["-q", "40", "-Q", "50"])]:
-        data = oracle.reference_encode_hdr(synth.synth_hdr(w, h, w) * 3.0, ["-r", "-q", "85", "-Q", "90", "-h", "-profile", "c", "-r12"] + extra)
-        codes, _ = oracle.decode_xt(data)
-        ref = oracle.reference_decode_hdr(data)
-        assert np.array_equal(oracle.half_codes_to_float(codes).view(np.uint32), ref.view(np.uint32))
+    for w, h, extra in LIVE_XT:
+        if oracle.have_reference():
+            data = live_xt_stream(oracle, w, h, extra)
+            codes, _ = oracle.decode_xt(data)
+            ref = oracle.reference_decode_hdr(data)
+            assert np.array_equal(oracle.half_codes_to_float(codes).view(np.uint32), ref.view(np.uint32))
+        else:
+            data, ent = stored_live_case(f"xt_{w}x{h}")
+            codes, _ = oracle.decode_xt(data)
+            assert sha256_of(oracle.half_codes_to_float(codes), "<f4") == ent["pixels_sha256"]
 
 
 def test_scan_order_and_quant_natural_order(oracle):
@@ -129,13 +156,18 @@ def _live_cases():
 
 @pytest.mark.parametrize("w,h,q,sub,dri,seed", list(_live_cases()))
 def test_oracle_vs_live_reference(oracle, w, h, q, sub, dri, seed):
-    if not oracle.have_reference():
-        pytest.skip("oracle/_ref/jpeg not built (needs /root/reference)")
-    data = synth.encode_jpeg(synth.synth_image(w, h, seed), q, sub, dri)
-    assert np.array_equal(oracle.decode(data), oracle.reference_decode(data))
+    if oracle.have_reference():
+        data = synth.encode_jpeg(synth.synth_image(w, h, seed), q, sub, dri)
+        assert np.array_equal(oracle.decode(data), oracle.reference_decode(data))
+    else:
+        data, ent = stored_live_case(f"decode_{seed}")
+        assert sha256_of(oracle.decode(data), np.uint8) == ent["pixels_sha256"]
 
 
-@pytest.mark.parametrize("w,h,sub,dri,scale", [(200, 120, "420", 8, 16), (97, 61, "444", 0, 16), (129, 71, "422", 3, 9), (64, 48, "420", 0, 40), (33, 200, "420", 1, 3)])
+LIVE_12BIT = [(200, 120, "420", 8, 16), (97, 61, "444", 0, 16), (129, 71, "422", 3, 9), (64, 48, "420", 0, 40), (33, 200, "420", 1, 3)]
+
+
+@pytest.mark.parametrize("w,h,sub,dri,scale", LIVE_12BIT)
 def test_oracle_vs_live_reference_12bit(oracle, w, h, sub, dri, scale):
     """12-bit streams made by synth.to_12bit (SOF1, P = 12, 16-bit quantiser entries over an 8-bit stream's entropy coded
     data): the restatement against the reference binary -- these streams are the 12-bit content of the GPU parity tests and of
@@ -146,10 +178,12 @@ def test_oracle_vs_live_reference_12bit(oracle, w, h, sub, dri, scale):
     assert px.dtype == np.uint16 and px.shape == (h, w, 3) and px.max() <= 4095
     if scale == 16:
         assert np.abs(px.astype(int) - 16 * oracle.decode(j8).astype(int)).max() <= 24
-    if not oracle.have_reference():
-        pytest.skip("oracle/_ref/jpeg not built (needs /root/reference)")
-    rpx, rerr = oracle.reference_decode_status(data)
-    assert rerr == 0 and np.array_equal(np.asarray(rpx).reshape(px.shape), px)
+    if oracle.have_reference():
+        rpx, rerr = oracle.reference_decode_status(data)
+        assert rerr == 0 and np.array_equal(np.asarray(rpx).reshape(px.shape), px)
+    else:
+        data, ent = stored_live_case(f"decode12_{w}x{h}")
+        assert sha256_of(oracle.decode16(data), "<u2") == ent["pixels_sha256"]
 
 
 # ------------------------------------------------------------------------------------------------------
@@ -177,16 +211,24 @@ def test_forward_matches_the_reference_encoders_golden_files(oracle, name):
         assert np.array_equal(_covered(info, mine, c), _covered(info, ref, c)), (name, c)
 
 
-@pytest.mark.parametrize("w,h,args,seed", [(512, 512, ["-bl", "-q", "75"], 1234), (640, 360, ["-bl", "-q", "97", "-s", "1x1,2x2,2x2"], 5),
-                                           (333, 211, ["-bl", "-q", "40", "-s", "1x1,2x1,2x1"], 6), (70, 40, ["-bl", "-q", "90"], 7)])
-def test_forward_matches_the_live_reference_encoder(oracle, w, h, args, seed):
-    if not oracle.have_reference():
-        pytest.skip("needs oracle/_ref/jpeg")
+LIVE_FORWARD = [(512, 512, ["-bl", "-q", "75"], 1234), (640, 360, ["-bl", "-q", "97", "-s", "1x1,2x2,2x2"], 5),
+                (333, 211, ["-bl", "-q", "40", "-s", "1x1,2x1,2x1"], 6), (70, 40, ["-bl", "-q", "90"], 7)]
+
+
+def live_forward_image(w, h, seed):
     rng = np.random.default_rng(seed)
     img = synth.synth_image(w, h, seed) if seed != 6 else rng.integers(0, 256, (h, w, 3)).astype(np.uint8)
     if seed == 7:
         img = np.ascontiguousarray(img[..., :1])
-    info, ref = oracle.decode_coefficients(oracle.reference_encode(img.squeeze(), args))
+    return img
+
+
+@pytest.mark.parametrize("w,h,args,seed", LIVE_FORWARD)
+def test_forward_matches_the_live_reference_encoder(oracle, w, h, args, seed):
+    img = live_forward_image(w, h, seed)
+    # the reference encoder's stream: live, or as make_live_reference.py stored it
+    stream = oracle.reference_encode(img.squeeze(), args) if oracle.have_reference() else stored_live_case(f"forward_{seed}")[0]
+    info, ref = oracle.decode_coefficients(stream)
     mine = oracle.forward(info, img, 1)
     for c in range(info.ncomp):
         assert np.array_equal(_covered(info, mine, c), _covered(info, ref, c)), c

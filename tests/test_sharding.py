@@ -124,13 +124,24 @@ def test_host_threads_are_divided_among_the_ranks():
 
 
 def test_bind_to_gpu_node_is_a_hint_that_never_fails():
-    """Without a GPU (or without sysfs topology) nothing happens and nothing is raised; the affinity stays what it was."""
+    """Without a GPU (or without sysfs topology) nothing happens and nothing is raised; the affinity stays what it was.  Where a
+    GPU is visible the process is either left as it was or bound to a part of the CPUs it had, as many as the result says."""
     import os
+
+    import torch
 
     from libjpeg_amd import sharding
     before = os.sched_getaffinity(0)
-    assert sharding.bind_to_gpu_node(0) is None
-    assert os.sched_getaffinity(0) == before
+    try:
+        got = sharding.bind_to_gpu_node(0)
+        after = os.sched_getaffinity(0)
+        if got is None or not torch.cuda.is_available():
+            assert got is None
+            assert after == before
+        else:
+            assert after < before and got["cpus"] == len(after)
+    finally:
+        os.sched_setaffinity(0, before)
 
 
 def test_batch_schedule_covers_every_frame_once():
@@ -175,7 +186,7 @@ def test_bench_through_its_own_launcher_over_rccl():
     and the reductions run on the device over RCCL; the line says so, and every rank's frames are checked against the oracle."""
     import json
 
-    r = _bench("--gpus", "1", "--launcher", "always", "--workload", "batch4k", "--batch-frames", "32", "--batch-steps", "2", "--frames", "8",
+    r = _bench("--gpus", "1", "--launcher", "always", "--full", "--workload", "batch4k", "--batch-frames", "32", "--batch-steps", "2", "--frames", "8",
                "--steps", "2", "--warmup", "1", "--settle-ms", "0", "--no-traffic", "--no-dense", "--no-xt", "--no-end-to-end", "--no-cpu-baseline",
                "--emulate-world", "0", env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -186,3 +197,42 @@ def test_bench_through_its_own_launcher_over_rccl():
     b = res["batch4k"]
     assert b["verified"] is True and b["per_rank_verified"] == [True] and b["n_gpus"] == 1 and b["frames"] == 32
     assert len(b["per_rank_ms"]) == 1 and b["per_rank_host_threads"] == [b["host_threads_per_rank"]]
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_and_dumps_what_the_last_one_wrote(tmp_path):
+    """A plain run is the headline alone: exactly --steps timed steps, ms_per_step on the line, no side measurement.  --dump-outputs
+    writes a seeded sample of the pixels the last step left in HBM: the same file on every run, and the oracle's pixels at the same
+    positions."""
+    import importlib.util
+    import json
+
+    import numpy as np
+    import torch
+
+    from libjpeg_amd import synth
+    from oracle import oracle as O
+
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    frames, (W, H) = 4, bench.SIZES["8k"]
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--frames", str(frames), "--settle-ms", "0", "--dump-outputs", str(d))
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert r.returncode == 0 and len(lines) == 1, (r.stdout[-600:], r.stderr[-1200:])
+        res = json.loads(lines[0])
+        assert res["steps"] == 3 and res["ms_per_step"] > 0 and res["unit"] == "Mpixels/s" and res["higher_is_better"] is True
+        assert not {"batch4k", "end_to_end", "xt_profile_c", "cpu_baseline", "roofline_dense", "summary"} & set(res)
+        px = np.load(d / "pixels.npy")
+        assert px.dtype == np.float32 and px.shape == (bench.DUMP_SAMPLES,) and px.nbytes <= 64 << 20
+        dumps.append(px)
+    assert np.array_equal(dumps[0], dumps[1])
+    frame_bytes = H * W * 3
+    idx = torch.randint(0, frames * frame_bytes, (bench.DUMP_SAMPLES,), generator=torch.Generator().manual_seed(bench.DUMP_SEED)).sort().values.numpy()
+    exp = [O.decode(synth.synth_jpeg(W, H, seed=1234 + i, quality=85, subsampling="420", restart_mcus=8)).reshape(-1) for i in range(2)]
+    f, pos = idx // frame_bytes, idx % frame_bytes
+    want = np.where(f % 2 == 0, exp[0][pos], exp[1][pos]).astype(np.float32)
+    assert np.array_equal(dumps[0], want)

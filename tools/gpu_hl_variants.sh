@@ -12,7 +12,7 @@ for v in $NAMES; do
   MIJPEG_LIBRARY=$ROOT/tools/ab/libmijpeg_$v.so timeout 600 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "$K" > $O/parity_$v.log 2>&1
   echo "parity $v: $(tail -1 $O/parity_$v.log)"
 done
-HL="--workload headline --no-cpu-baseline --no-end-to-end --no-traffic --no-xt --steps 20 --warmup 3"
+HL="--full --workload headline --no-cpu-baseline --no-end-to-end --no-traffic --no-xt --steps 20 --warmup 3"
 for rep in $(seq 1 $REPS); do
   for v in $NAMES; do
     MIJPEG_LIBRARY=$ROOT/tools/ab/libmijpeg_$v.so timeout 300 python bench.py $HL > $O/hl_${v}_$rep.json 2> $O/hl_${v}_$rep.err

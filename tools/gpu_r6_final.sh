@@ -7,7 +7,7 @@ O=gpurun_out/r6final
 bash tools/gpu_profile.sh r06 > $O/profile.log 2>&1; tail -30 $O/profile.log
 cd "$ROOT"
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-( time timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err ); echo "bench exit $?"; tail -c 900 $O/bench.json; echo
+( time timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err ); echo "bench exit $?"; tail -c 900 $O/bench.json; echo
 timeout 2400 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1; echo "pytest exit $?"; tail -3 $O/pytest_gpu.log
 timeout 200 python tools/multiscan_probe.py make /tmp/ms > /dev/null 2>&1
 MIJPEG_TRACE_SUBMIT=1 MIJPEG_READ_TIMES=1 timeout 200 python tools/multiscan_probe.py run /tmp/ms 6 > $O/multiscan_probe.txt 2>&1; grep "ran on" $O/multiscan_probe.txt

@@ -12,7 +12,7 @@ for round in 1 2 3; do
   for v in "" "$V"; do
     if [ -n "$v" ]; then export MIJPEG_LIBRARY=$ROOT/tools/ab/libmijpeg_$v.so; else unset MIJPEG_LIBRARY; fi
     echo -n "round $round ${v:-default}: " >> $O
-    python bench.py --no-xt --no-end-to-end --no-cpu-baseline --workload headline 2>/dev/null | grep -o "\"ms_per_step\": [0-9.]*\|\"kernel_frac\": [0-9.]*\|\"dense_frac[^}]*\|\"verified\": [a-z]*" | tr "\n" " " >> $O; echo >> $O
+    python bench.py --full --no-xt --no-end-to-end --no-cpu-baseline --workload headline 2>/dev/null | grep -o "\"ms_per_step\": [0-9.]*\|\"kernel_frac\": [0-9.]*\|\"dense_frac[^}]*\|\"verified\": [a-z]*" | tr "\n" " " >> $O; echo >> $O
   done
 done
 unset MIJPEG_LIBRARY
