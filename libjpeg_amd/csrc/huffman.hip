@@ -835,11 +835,21 @@ __device__ __forceinline__ int prog_block_refine(DevBits &br, const HuffDevTable
 
 // LDS: [max_tables tables | zigzag order][per wave: L block slots | L rings | L block numbers | L lists of free positions]
 constexpr int PROG_ZZ_BYTES = 80;
+// Bytes of one wave's staging area, rounded up to 16 so that every wave's slots and rings keep the 16-byte alignment of their
+// 128-bit LDS accesses (a lane takes 340 bytes for int16, 468 for int32: with 1 or 2 lanes a wave the plain sum is only 4- or
+// 8-byte aligned; from 4 lanes on it is a multiple of 16 already).  The kernel and launch_huffman_prog's LDS size both use it.
+__host__ __device__ constexpr int prog_wave_bytes(int lanes, int slot)
+{
+  return (lanes * (slot + RING_PITCH + 16 + PROG_ZLIST_PITCH) + 15) & ~15;
+}
+static_assert(prog_wave_bytes(1, 128) % 16 == 0 && prog_wave_bytes(2, 128) % 16 == 0 && prog_wave_bytes(1, 256) % 16 == 0 &&
+              prog_wave_bytes(2, 256) % 16 == 0, "wave staging areas start 16-byte aligned");
+static_assert(prog_wave_bytes(4, 128) == 4 * (128 + RING_PITCH + 16 + PROG_ZLIST_PITCH) &&
+              prog_wave_bytes(4, 256) == 4 * (256 + RING_PITCH + 16 + PROG_ZLIST_PITCH), "from 4 lanes on the layout is unchanged");
 template <class T> __global__ __launch_bounds__(256) void huffman_prog_kernel(const ProgArgs a)
 {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds_raw[];
   constexpr int SLOT = 64 * (int)sizeof(T), CH = SLOT / 16;
-  constexpr int LANE_BYTES = SLOT + RING_PITCH + 16 + PROG_ZLIST_PITCH;
   const int table_bytes = a.max_tables * (int)sizeof(HuffDevTable) + PROG_ZZ_BYTES;
   const uint8_t *zz = lds_raw + table_bytes - PROG_ZZ_BYTES; // (a look-up per coefficient, at a position that differs from lane to lane: LDS, not memory)
   const HuffDevTable *tabs = reinterpret_cast<const HuffDevTable *>(lds_raw);
@@ -847,14 +857,15 @@ template <class T> __global__ __launch_bounds__(256) void huffman_prog_kernel(co
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const ProgGroup grp = a.groups[blockIdx.x];
   const ProgScanDev sc = a.scans[grp.scan]; // uniform
-  uint8_t *stage = lds_raw + table_bytes + wv * (L * LANE_BYTES);
+  const int wave_bytes = prog_wave_bytes(L, SLOT);
+  uint8_t *stage = lds_raw + table_bytes + wv * wave_bytes;
   uint8_t *rings = stage + L * SLOT;
   uint32_t *blkno = reinterpret_cast<uint32_t *>(stage + L * (SLOT + RING_PITCH));
   uint16_t *zlist = reinterpret_cast<uint16_t *>(stage + L * (SLOT + RING_PITCH + 16) + (lane & (L - 1)) * PROG_ZLIST_PITCH);
   {
     const uint32_t *src = reinterpret_cast<const uint32_t *>(a.tables + sc.table_off);
     uint32_t *dst = reinterpret_cast<uint32_t *>(lds_raw);
-    const int words = sc.ntables * (int)sizeof(HuffDevTable) / 4, first = table_bytes / 4, rest = nwaves * L * LANE_BYTES / 4;
+    const int words = sc.ntables * (int)sizeof(HuffDevTable) / 4, first = table_bytes / 4, rest = nwaves * wave_bytes / 4;
     for (int i = threadIdx.x; i < words; i += blockDim.x) dst[i] = src[i];
     for (int i = threadIdx.x; i < rest; i += blockDim.x) dst[first + i] = 0;
     if (threadIdx.x < PROG_ZZ_BYTES / 4) dst[first - PROG_ZZ_BYTES / 4 + threadIdx.x] = reinterpret_cast<const uint32_t *>(prog_zigzag)[threadIdx.x];
@@ -969,7 +980,7 @@ int launch_huffman_prog(const ProgArgs &a, hipStream_t stream)
 {
   if (a.n_groups <= 0) return 0;
   const size_t slot = a.wide ? 256 : 128;
-  const size_t lds = (size_t)a.max_tables * sizeof(HuffDevTable) + PROG_ZZ_BYTES + (size_t)a.waves_per_group * a.lanes * (slot + RING_PITCH + 16 + PROG_ZLIST_PITCH);
+  const size_t lds = (size_t)a.max_tables * sizeof(HuffDevTable) + PROG_ZZ_BYTES + (size_t)a.waves_per_group * prog_wave_bytes(a.lanes, (int)slot);
   if (a.wide) hipLaunchKernelGGL(huffman_prog_kernel<int32_t>, dim3(a.n_groups), dim3(64 * a.waves_per_group), lds, stream, a);
   else hipLaunchKernelGGL(huffman_prog_kernel<int16_t>, dim3(a.n_groups), dim3(64 * a.waves_per_group), lds, stream, a);
   return (int)hipGetLastError();
