@@ -1876,6 +1876,19 @@ try {
 // Aggregation over the images of a decoded batch: what one reconstruction launch for all of them needs to know.
 static int finish_batch(mijpeg_decoder *d);
 
+// The range gates of the kernel selection (plan_reconstruct): a kernel or flavour is admitted where mijpeg_info::range_max
+// (sum |c| q of a block) is below its gate
+constexpr int32_t GATE_DOT2 = 1477;          // fused420p_kernel's second pass on v_dot2 (idct_columns_dot2: sum |c| q <= 1476)
+constexpr int32_t GATE_PACKED = 2047;        // chroma filtered as int16 pairs (packed 4:2:0, 4:2:2, 4:4:0)
+constexpr int32_t GATE_INT16_SAMPLES = 7600; // int16 sample planes of the kernel pair; int16 luma of fusedxtw420_kernel<true>
+constexpr int32_t GATE_FUSED8 = 8190;        // chroma of the 8-bit fused 4:2:2 / 4:4:0 / 4:1:1 / 4:4:4 kernels, fused1_kernel
+constexpr int32_t GATE_XT_LEGACY = 16384;    // legacy frame of the JPEG XT kernels (fused, and the merge's 32-bit colour stage)
+constexpr int32_t GATE_12_CHROMA = 45056;    // 12-bit fused kernels: chroma (every component of fused_tile_kernel's fast12)
+constexpr int32_t GATE_12_LUMA = 49152;      // 12-bit fused kernels: luma
+constexpr int32_t GATE_XT_RESIDUAL = 65536;  // residual frame of the fused JPEG XT kernels
+constexpr int32_t RANGE_GATES[] = { // (ascending)
+    GATE_DOT2, GATE_PACKED, GATE_INT16_SAMPLES, GATE_FUSED8, GATE_XT_LEGACY, GATE_12_CHROMA, GATE_12_LUMA, GATE_XT_RESIDUAL};
+
 // What the last finished batch of shared tables reported, for the speculative launch of the next one (MIJPEG_FLAG_SPECULATIVE):
 // frame geometry, tables, and the range check that selected its kernel.  Process-wide: the decoder objects of a pipeline work
 // on chunks of the same material.
@@ -1890,12 +1903,11 @@ SpecHint *spec_hint()
   static SpecHint *h = new SpecHint;
   return h;
 }
-// the gates of the kernel selection (use_* above): an assumed range just below the next gate selects the kernel the hint's
-// batch ran on and holds for every batch that stays below that gate
+// an assumed range just below the next gate selects the kernel the hint's batch ran on and holds for every batch that stays
+// below that gate
 int32_t next_gate_below(int32_t range)
 {
-  static const int32_t gates[] = {1477, 2047, 7600, 8190, 16384, 45056, 49152, 65536}; // (1477: use_dot2_pass's range_max <= 1476)
-  for (int32_t g : gates)
+  for (int32_t g : RANGE_GATES)
     if (range < g) return g - 1;
   return -1;
 }
@@ -2292,34 +2304,13 @@ try {
 // ------------------------------------------------------------------------------------------------
 // stateless batch launch
 // ------------------------------------------------------------------------------------------------
-static bool is_420(const mijpeg_info &f)
+static Sampling sampling_of(const mijpeg_info &f)
 {
-  return f.components == 3 && f.hsamp[0] == 2 && f.vsamp[0] == 2 && f.hsamp[1] == 1 && f.vsamp[1] == 1 &&
-         f.hsamp[2] == 1 && f.vsamp[2] == 1;
-}
-
-static bool is_444(const mijpeg_info &f)
-{
-  return f.components == 3 && f.hsamp[0] == 1 && f.vsamp[0] == 1 && f.hsamp[1] == 1 && f.vsamp[1] == 1 && f.hsamp[2] == 1 &&
-         f.vsamp[2] == 1;
-}
-
-static bool is_422(const mijpeg_info &f)
-{
-  return f.components == 3 && f.hsamp[0] == 2 && f.vsamp[0] == 1 && f.hsamp[1] == 1 && f.vsamp[1] == 1 && f.hsamp[2] == 1 &&
-         f.vsamp[2] == 1;
-}
-
-static bool is_411(const mijpeg_info &f)
-{
-  return f.components == 3 && f.hsamp[0] == 4 && f.vsamp[0] == 1 && f.hsamp[1] == 1 && f.vsamp[1] == 1 && f.hsamp[2] == 1 &&
-         f.vsamp[2] == 1;
-}
-
-static bool is_440(const mijpeg_info &f)
-{
-  return f.components == 3 && f.hsamp[0] == 1 && f.vsamp[0] == 2 && f.hsamp[1] == 1 && f.vsamp[1] == 1 && f.hsamp[2] == 1 &&
-         f.vsamp[2] == 1;
+  if (f.components == 1) return Sampling::GREY;
+  if (f.components != 3 || f.hsamp[1] != 1 || f.vsamp[1] != 1 || f.hsamp[2] != 1 || f.vsamp[2] != 1) return Sampling::OTHER;
+  const int h = f.hsamp[0], v = f.vsamp[0];
+  return h == 2 && v == 2 ? Sampling::S420 : h == 2 && v == 1 ? Sampling::S422 : h == 1 && v == 2 ? Sampling::S440
+         : h == 4 && v == 1 ? Sampling::S411 : h == 1 && v == 1 ? Sampling::S444 : Sampling::OTHER;
 }
 
 // The fused kernels address inside a frame with 32-bit byte offsets (planes and pixels; frames are 64 bits apart): frames
@@ -2333,7 +2324,7 @@ static bool is_440(const mijpeg_info &f)
 static bool dnl_row_missing(const mijpeg_info &f)
 {
   if (!f.dnl) return false;
-  for (int c = 0; c < f.components; c++) {
+  for (int c = 0; c < f.components && c < MIJPEG_MAX_COMPONENTS; c++) {
     const int ch = (f.height + f.suby[c] - 1) / f.suby[c];
     if (f.suby[c] > 1 && (ch & 7) == 0 && f.rows[c] <= (ch >> 3)) return true;
   }
@@ -2359,145 +2350,32 @@ static bool fits32(const mijpeg_batch *b)
   return (uint64_t)f.height * rs + line <= lim;
 }
 
-static bool fast_ok(const mijpeg_batch *b)
+// every delta << 4 a signed 16-bit operand (the fast transforms)
+static bool deltas_fit16(const mijpeg_info &f)
 {
-  // fast arithmetic: range check passed (host decoder) and every delta << 4 fits a signed 16-bit operand
-  const mijpeg_info &f = b->info;
-  if (!f.fast_arith || (b->flags & MIJPEG_FLAG_FORCE_SAFE)) return false;
-  for (int c = 0; c < f.components; c++)
-    for (int i = 0; i < 64; i++)
-      if (f.quant[f.quant_index[c]][i] > 2047) return false;
-  return true;
-}
-
-// fused 4:4:4 keeps the chroma samples as packed int16: needs |sample| <= 4 * range_max < 32768
-static bool use_fused444(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  return is_444(f) && f.ycbcr && !f.xt && f.precision == 8 && !(b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM)) && fast_ok(b) &&
-         f.range_max[1] < 8190 && f.range_max[2] < 8190 && fits32(b);
-}
-
-static bool use_fused420(const mijpeg_batch *b)
-{
-  return is_420(b->info) && b->info.ycbcr && !b->info.xt && b->info.precision == 8 &&
-         !(b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM)) && fits32(b);
-}
-
-// 12-bit 4:2:0 frames (SOF1, P = 12) inside the ranges the 12-bit flavour of the fused kernel is exact for: every delta << 4 a
-// signed 16-bit operand; sum |c| q < 49152 bounds every butterfly intermediate by 1573 * 16 * 49152 < 2^31 (first pass;
-// the second pass sees at most 22.2 * range_max per column) and every multiplicand by 2^23; chroma sum |c| q < 45056 bounds
-// the chroma samples (times 16) by 4.02 * 45056 + 2 < 181 200 (|basis| <= 1/4 per coefficient, the 9-bit constants and the
-// roundings add < 0.5 %), whose products with the colour constants (11485; 2819 + 5850; 14516 taken as 4 * 3629) fit 32 bits
-static bool use_fused420_12(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F420_12") != nullptr; // A-B comparisons
-  if (off || !is_420(f) || !f.ycbcr || f.xt || f.precision != 12 ||
-      (b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM | MIJPEG_FLAG_FORCE_SAFE)) || !fits32(b))
-    return false;
-  if (f.range_max[0] <= 0 || f.range_max[0] >= 49152 || f.range_max[1] >= 45056 || f.range_max[2] >= 45056) return false;
-  for (int c = 0; c < 3; c++)
-    for (int i = 0; i < 64; i++)
-      if (f.quant[f.quant_index[c]][i] > 2047) return false;
-  return true;
-}
-
-// The 12-bit kernels' colour stage in one 32-bit sum per channel (colour12<true>, kernels.hip): the luma sample times 16 is at most
-// 4.02 * range_max[0] + 2 in magnitude, a chroma sample behind the upsampling filters 4.02 * range_max[c] + 4 (the bounds of
-// use_fused420_12; the filters are convex combinations plus a rounding), so (|y'| + 32776) * 8192 + 14516 |c| -- 14516 is the largest
-// weight a channel puts on chroma, 2819 + 5850 the green one's -- stays below 2^31 where this holds.  Monotone in every range: a
-// speculative launch that assumed larger ranges and selected the flavour holds for the smaller ones.  MIJPEG_NO_NARROW12: A-B runs.
-static bool narrow12_colour(const mijpeg_info &f)
-{
-  static const bool off = getenv("MIJPEG_NO_NARROW12") != nullptr;
-  if (off || f.precision != 12 || f.components != 3) return false;
-  const int64_t ry = f.range_max[0], rc = std::max(f.range_max[1], f.range_max[2]);
-  if (ry <= 0 || rc < 0) return false;
-  const int64_t sum = ((402 * ry + 99) / 100 + 2 + 32776) * 8192 + 14516 * ((402 * rc + 99) / 100 + 4);
-  return sum < ((int64_t)1 << 31);
-}
-
-// 12-bit 4:4:4 frames: the same bounds (no filter between the transforms and the colour stage)
-static bool use_fused444_12(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F444_12") != nullptr; // A-B comparisons
-  if (off || !is_444(f) || !f.ycbcr || f.xt || f.precision != 12 ||
-      (b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM | MIJPEG_FLAG_FORCE_SAFE)) || !fits32(b))
-    return false;
-  if (f.range_max[0] <= 0 || f.range_max[0] >= 49152 || f.range_max[1] >= 45056 || f.range_max[2] >= 45056) return false;
-  for (int c = 0; c < 3; c++)
-    for (int i = 0; i < 64; i++)
-      if (f.quant[f.quant_index[c]][i] > 2047) return false;
-  return true;
-}
-
-// 12-bit 4:2:2 frames: the same bounds again (the horizontal filter weighs samples below 2^18 with 4 in total)
-static bool use_fused422_12(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F422_12") != nullptr; // A-B comparisons
-  if (off || !is_422(f) || !f.ycbcr || f.xt || f.precision != 12 ||
-      (b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM | MIJPEG_FLAG_FORCE_SAFE)) || !fits32(b))
-    return false;
-  if (f.range_max[0] <= 0 || f.range_max[0] >= 49152 || f.range_max[1] >= 45056 || f.range_max[2] >= 45056) return false;
-  for (int c = 0; c < 3; c++)
-    for (int i = 0; i < 64; i++)
-      if (f.quant[f.quant_index[c]][i] > 2047) return false;
-  return true;
-}
-
-// 12-bit single-component frames: the butterflies' bound alone
-static bool use_fused1_12(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F1_12") != nullptr; // A-B comparisons
-  if (off || f.components != 1 || f.xt || f.precision != 12 || (b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_FORCE_SAFE)) || !fits32(b)) return false;
-  if (f.range_max[0] <= 0 || f.range_max[0] >= 49152) return false;
-  for (int i = 0; i < 64; i++)
-    if (f.quant[f.quant_index[0]][i] > 2047) return false;
-  return true;
-}
-
-// 12-bit frames of the other layouts (fused_tile_kernel): the same bounds, the chroma one for every component -- 32-bit
-// butterflies and colour products as in use_fused420_12; the upsampling filters weigh two samples (< 2^18 each with the level
-// shift) with at most 8 in total, far inside the 24-bit operands and 32-bit sums of the kernel's fast flavour
-static bool tile_fast12(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_TILE_FAST12") != nullptr; // A-B comparisons
-  if (off || f.xt || f.precision != 12 || f.coef_wide || (b->flags & MIJPEG_FLAG_FORCE_SAFE) || f.range_max[0] <= 0) return false;
+  if (f.components > MIJPEG_MAX_COMPONENTS) return false;
   for (int c = 0; c < f.components; c++) {
-    if (f.range_max[c] >= 45056) return false;
+    if ((unsigned)f.quant_index[c] >= 4) return false;
     for (int i = 0; i < 64; i++)
       if (f.quant[f.quant_index[c]][i] > 2047) return false;
   }
   return true;
 }
 
-// the packed flavour filters (Cb, Cr) pairs in 16 bits: every chroma sample * 16 is bounded by 4 * range_max, and the
-// filter sums a + 3 b + r by four times that
-static bool use_fused420p(const mijpeg_batch *b)
+// The 12-bit kernels' colour stage in one 32-bit sum per channel (colour12<true>, kernels.hip): the luma sample times 16 is at most
+// 4.02 * range_max[0] + 2 in magnitude, a chroma sample behind the upsampling filters 4.02 * range_max[c] + 4 (the bounds of
+// the 12-bit gate of plan_reconstruct; the filters are convex combinations plus a rounding), so (|y'| + 32776) * 8192 + 14516 |c| --
+// 14516 is the largest weight a channel puts on chroma, 2819 + 5850 the green one's -- stays below 2^31 where this holds.  Monotone
+// in every range: a speculative launch that assumed larger ranges and selected the flavour holds for the smaller ones.
+static bool narrow12_colour(const mijpeg_info &f)
 {
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F420P") != nullptr; // tuning / A-B comparisons
-  return !off && use_fused420(b) && fast_ok(b) && f.range_max[1] < 2047 && f.range_max[2] < 2047;
+  if (f.precision != 12 || f.components != 3) return false;
+  const int64_t ry = f.range_max[0], rc = std::max(f.range_max[1], f.range_max[2]);
+  if (ry <= 0 || rc < 0) return false;
+  const int64_t sum = ((402 * ry + 99) / 100 + 2 + 32776) * 8192 + 14516 * ((402 * rc + 99) / 100 + 4);
+  return sum < ((int64_t)1 << 31);
 }
 
-// ... and where the first-pass results of every transform fit 16 bits the second pass runs on v_dot2 as well (idct_columns_dot2 in
-// kernels.hip has the bound: sum |c| q <= 1476 per block).  MIJPEG_FLAG_FORCE_DOT2 (testing): whatever the range check says.
-static bool use_dot2_pass(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_DOT2") != nullptr; // A-B comparisons
-  if (off || b->quant_dev) return false;
-  if (b->flags & MIJPEG_FLAG_FORCE_DOT2) return true;
-  return f.range_max[0] <= 1476 && f.range_max[1] <= 1476 && f.range_max[2] <= 1476;
-}
-
-// JPEG XT profile C in the shape the fused kernel covers: 8-bit 4:2:0 legacy frame and 12-bit 4:4:4 residual frame without
-// hidden bits, L transformation on, both frames within the range the fast transforms are exact for
 // JPEG XT: the L transformation in force for this launch.  A request without colour transformation (the command line's -c)
 // replaces the STANDARD YCbCr transformation by the identity and leaves everything else of the merge alone
 // (colortrafo/colortransformerfactory.cpp:231-232: `if (ltrafo == YCbCr && disabletorgb) ltrafo = Identity`)
@@ -2507,18 +2385,11 @@ static bool xt_ltrafo_ycbcr(const mijpeg_batch *b)
   return x.ltrafo_ycbcr && !((b->flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM) && x.ltrafo_standard);
 }
 
-static bool use_fusedxt(const mijpeg_batch *b)
+// JPEG XT profile C in the shape the fused kernels cover (the legacy frame's part is plan_reconstruct's): 12-bit 4:4:4
+// residual frame of the legacy frame's size, L transformation on, the residual frame within the range the fast transforms
+// are exact for
+static bool fused_xt_shape(const mijpeg_batch *b)
 {
-  const mijpeg_info &f = b->info;
-  if (!f.xt || !b->xt || !is_420(f) || f.precision != 8 || (b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_FORCE_SAFE)) || !fits32(b)) return false;
-  // the legacy frame's range check (fast_arith itself is never set for XT frames: the generic kernels run SAFE on them)
-  for (int c = 0; c < 3; c++) {
-    if (f.range_max[c] >= 16384) return false;
-    for (int i = 0; i < 64; i++)
-      if (f.quant[f.quant_index[c]][i] > 2047) return false;
-  }
-  static const bool off = getenv("MIJPEG_NO_FUSEDXT") != nullptr; // A-B comparisons
-  if (off) return false;
   const mijpeg_xt_params &x = *b->xt;
   const mijpeg_info &r = x.residual;
   if (x.general) return false; // free-form matrices, table gathers, DCT bypass: xt_merge_general_kernel
@@ -2528,90 +2399,120 @@ static bool use_fusedxt(const mijpeg_batch *b)
   if (x.hidden_bits || x.residual_hidden_bits < 0 || x.residual_hidden_bits > 4 || (x.residual_wide != 0) != (x.residual_hidden_bits > 0) ||
       x.ltable_entries != 256 || !xt_ltrafo_ycbcr(b) || r.precision != 12 || r.components != 3 || x.out_max != 65535 || x.out_shift != 32768)
     return false;
-  static const bool no_wide = getenv("MIJPEG_NO_FUSEDXTW") != nullptr; // A-B comparisons
-  if (x.residual_hidden_bits && no_wide) return false;
-  for (int c = 0; c < 3; c++) {
-    if (r.subx[c] != 1 || r.suby[c] != 1 || r.blocks_w[c] != r.blocks_w[0] || r.blocks_h[c] != r.blocks_h[0] || r.range_max[c] >= 65536) return false;
-    for (int i = 0; i < 64; i++)
-      if (r.quant[r.quant_index[c]][i] > 2047) return false;
+  for (int c = 0; c < 3; c++)
+    if (r.subx[c] != 1 || r.suby[c] != 1 || r.blocks_w[c] != r.blocks_w[0] || r.blocks_h[c] != r.blocks_h[0] || r.range_max[c] >= GATE_XT_RESIDUAL)
+      return false;
+  return deltas_fit16(r) && r.width == b->info.width && r.height == b->info.height;
+}
+
+// Which kernel reconstructs a batch, and in which flavour: the one place that decides it (mijpeg_kernel_name,
+// mijpeg_workspace_bytes and launch_reconstruct_ex each ask once).  Safe on any batch description, a JPEG XT frame without
+// its parameter block and a batch without strides included.  (A rectangle request needs MIJPEG_FLAG_FORCE_GENERIC, which
+// alone rules out the fused, flat and tile kernels.)
+static ReconPlan plan_reconstruct(const mijpeg_batch *b)
+{
+  const mijpeg_info &f = b->info;
+  const int32_t *r = f.range_max;
+  const bool generic = b->flags & MIJPEG_FLAG_FORCE_GENERIC, safe = b->flags & MIJPEG_FLAG_FORCE_SAFE;
+  const bool ycc = f.ycbcr && !(b->flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM); // (the fused three-component kernels transform colour)
+  const bool deltas16 = deltas_fit16(f); // (false for more components than a frame can have)
+  const auto chroma_below = [&](int32_t gate) { return r[1] < gate && r[2] < gate; };
+  ReconPlan p{};
+  p.sampling = sampling_of(f);
+  p.fast = f.fast_arith && !safe && !f.coef_wide && deltas16;
+  const auto plan = [&](Recon k) { p.kernel = k; return p; };
+  if (f.xt) {
+    // (fast_arith itself is never set for XT frames: the generic kernels run SAFE on them; the fused ones check the range here)
+    if (b->xt && p.sampling == Sampling::S420 && f.precision == 8 && !generic && !safe && deltas16 && r[0] < GATE_XT_LEGACY &&
+        chroma_below(GATE_XT_LEGACY) && fits32(b) && fused_xt_shape(b))
+      return plan(b->xt->residual_hidden_bits ? Recon::FUSEDXTW420 : Recon::FUSEDXT420);
+    if (f.coef_wide) return plan(Recon::PAIR_LONG);
+    if (f.components == 1) return plan(Recon::XT_MERGE1);
+    return plan(b->xt && b->xt->general ? Recon::XT_MERGE_GENERAL : Recon::XT_MERGE);
   }
-  return r.width == f.width && r.height == f.height;
+  if (f.coef_wide) return plan(Recon::PAIR_LONG); // int32 coefficients (damaged stream)
+  const bool fits = f.components >= 1 && f.components <= MIJPEG_MAX_COMPONENTS && fits32(b); // (no missing DNL row either)
+  if (fits && !generic && f.precision == 8) {
+    // single components: samples travel as packed int16
+    if (p.sampling == Sampling::GREY && p.fast && r[0] < GATE_FUSED8) return plan(Recon::FUSED1);
+    // 4:2:0 in any range; the packed flavour filters (Cb, Cr) pairs in 16 bits: every chroma sample * 16 is bounded by
+    // 4 * range_max, and the filter sums a + 3 b + r by four times that.  Where the first-pass results of every transform fit
+    // 16 bits its second pass runs on v_dot2 as well (MIJPEG_FLAG_FORCE_DOT2, for testing: whatever the range check says).
+    if (p.sampling == Sampling::S420 && ycc) {
+      if (!p.fast || !chroma_below(GATE_PACKED)) return plan(Recon::FUSED420);
+      p.dot2 = !b->quant_dev && ((b->flags & MIJPEG_FLAG_FORCE_DOT2) || (r[0] < GATE_DOT2 && chroma_below(GATE_DOT2)));
+      return plan(Recon::FUSED420P);
+    }
+    // 4:2:2, 4:4:0 (what a losslessly rotated 4:2:2 picture is), 4:1:1, 4:4:4: chroma samples travel through LDS as int16 pairs
+    // (4 * range_max < 32768); 4:2:2 and 4:4:0 filter on the pairs below the packed gate, on 32-bit values between the two
+    if (p.sampling != Sampling::GREY && p.sampling != Sampling::OTHER && ycc && p.fast && chroma_below(GATE_FUSED8)) {
+      const Sampling s = p.sampling;
+      p.wide = (s == Sampling::S422 || s == Sampling::S440) && !chroma_below(GATE_PACKED);
+      return plan(s == Sampling::S422 ? Recon::FUSED422 : s == Sampling::S440 ? Recon::FUSED440 : s == Sampling::S411 ? Recon::FUSED411 : Recon::FUSED444);
+    }
+  }
+  // 12 bit (SOF1, P = 12): 4:2:0, 4:2:2, 4:4:4 and single components inside the ranges the 12-bit flavours are exact for: every
+  // delta << 4 a signed 16-bit operand; sum |c| q < 49152 bounds every butterfly intermediate by 1573 * 16 * 49152 < 2^31 (first
+  // pass; the second pass sees at most 22.2 * range_max per column) and every multiplicand by 2^23; chroma sum |c| q < 45056 bounds
+  // the chroma samples (times 16) by 4.02 * 45056 + 2 < 181 200 (|basis| <= 1/4 per coefficient, the 9-bit constants and the
+  // roundings add < 0.5 %), whose products with the colour constants (11485; 2819 + 5850; 14516 taken as 4 * 3629) fit 32 bits.
+  // (The horizontal filter of 4:2:2 weighs samples below 2^18 with 4 in total.)
+  if (fits && !generic && f.precision == 12 && !safe && deltas16 && r[0] > 0 && r[0] < GATE_12_LUMA) {
+    if (p.sampling == Sampling::GREY) return plan(Recon::FUSED1_12);
+    const Sampling s = p.sampling;
+    if ((s == Sampling::S420 || s == Sampling::S422 || s == Sampling::S444) && ycc && chroma_below(GATE_12_CHROMA)) {
+      p.narrow12 = narrow12_colour(f);
+      return plan(s == Sampling::S420 ? Recon::FUSED420_12 : s == Sampling::S422 ? Recon::FUSED422_12 : Recon::FUSED444_12);
+    }
+  }
+  // every component 1 x 1, three or four of them, 8 bit, no colour transformation, fast arithmetic: fused_flat_kernel
+  // (CMYK; RGB stored as such -- Adobe transform 0, a merging specification with the identity L transformation, the caller's
+  // MIJPEG_FLAG_NO_COLOR_TRANSFORM on a 4:4:4 frame)
+  bool flat = f.precision == 8 && !b->quant_dev && !generic && (f.components == 4 || (f.components == 3 && !ycc)) && p.fast && fits;
+  for (int c = 0; c < f.components && flat; c++)
+    flat = f.subx[c] == 1 && f.suby[c] == 1 && f.blocks_w[c] == f.blocks_w[0] && f.blocks_h[c] == f.blocks_h[0];
+  if (flat) return plan(Recon::FLAT);
+  // plain JPEG frames of any layout go through LDS in one pass (fused_tile_kernel); the pair with its sample planes in HBM
+  // stays for per-frame tables in device memory, MIJPEG_FLAG_FORCE_GENERIC (rectangle requests) and missing DNL rows
+  if (b->quant_dev || generic || dnl_row_missing(f)) return plan(Recon::PAIR);
+  // 12-bit frames of the tile kernel: the bounds of the 12-bit gate above, the chroma one for every component (the upsampling
+  // filters weigh two samples, < 2^18 each with the level shift, with at most 8 in total: far inside the fast flavour's 24-bit
+  // operands and 32-bit sums)
+  p.fast12 = f.precision == 12 && !safe && deltas16 && r[0] > 0;
+  for (int c = 0; c < f.components && p.fast12; c++) p.fast12 = r[c] < GATE_12_CHROMA;
+  return plan(Recon::TILE);
 }
 
-// single-component frames (and single components without upsampling): samples travel as packed int16
-static bool use_fused1(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F1") != nullptr; // A-B comparisons
-  return !off && f.components == 1 && !f.xt && f.precision == 8 && !(b->flags & MIJPEG_FLAG_FORCE_GENERIC) && fast_ok(b) && f.range_max[0] < 8190 &&
-         fits32(b);
-}
-
-// fused 4:2:2 / 4:4:0: chroma samples travel through LDS as int16 pairs (range_max < 8190, the fused 4:4:4 kernel's bound);
-// below the packed 4:2:0 flavour's bound (2047) the filter runs on the pairs, between the two on unpacked 32-bit values
-static bool chroma_packed(const mijpeg_info &f) { return f.range_max[1] < 2047 && f.range_max[2] < 2047; }
-static bool use_fused422(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F422") != nullptr; // A-B comparisons
-  return !off && is_422(f) && f.ycbcr && !f.xt && f.precision == 8 && !(b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM)) && fast_ok(b) &&
-         f.range_max[1] < 8190 && f.range_max[2] < 8190 && fits32(b);
-}
-
-// fused 4:1:1: int16 pairs in LDS, 32-bit four-fold filter
-static bool use_fused411(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F411") != nullptr; // A-B comparisons
-  return !off && is_411(f) && f.ycbcr && !f.xt && f.precision == 8 && !(b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM)) && fast_ok(b) &&
-         f.range_max[1] < 8190 && f.range_max[2] < 8190 && fits32(b);
-}
-
-// fused 4:4:0 (what a losslessly rotated 4:2:2 picture is): the vertical half of the packed filter, same bound
-static bool use_fused440(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_F440") != nullptr; // A-B comparisons
-  return !off && is_440(f) && f.ycbcr && !f.xt && f.precision == 8 && !(b->flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM)) && fast_ok(b) &&
-         f.range_max[1] < 8190 && f.range_max[2] < 8190 && fits32(b);
-}
-
-// every component 1 x 1, three or four of them, 8 bit, no colour transformation, fast arithmetic: fused_flat_kernel
-// (CMYK; RGB stored as such -- Adobe transform 0, a merging specification with the identity L transformation, the caller's
-// MIJPEG_FLAG_NO_COLOR_TRANSFORM on a 4:4:4 frame)
-static bool use_fused_flat(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  static const bool off = getenv("MIJPEG_NO_FUSED_FLAT") != nullptr; // A-B measurements
-  if (off || f.xt || f.precision != 8 || f.coef_wide || b->quant_dev || (f.components != 3 && f.components != 4)) return false;
-  if (b->flags & MIJPEG_FLAG_FORCE_GENERIC) return false;
-  if (f.components == 3 && f.ycbcr && !(b->flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM)) return false;
-  for (int c = 0; c < f.components; c++)
-    if (f.subx[c] != 1 || f.suby[c] != 1 || f.blocks_w[c] != f.blocks_w[0] || f.blocks_h[c] != f.blocks_h[0]) return false;
-  return fast_ok(b) && fits32(b) && !dnl_row_missing(f);
-}
+// per Recon: the name, and that of the flavour (ReconPlan::wide, ReconPlan::narrow12) where the kernel has one
+static const char *const RECON_NAMES[][2] = {
+    {"fused420p_kernel", nullptr},
+    {"fused420_kernel", nullptr},
+    {"fused422_kernel", "fused422_kernel<wide>"},
+    {"fused440_kernel", "fused440_kernel<wide>"},
+    {"fused411_kernel", nullptr},
+    {"fused444_kernel", nullptr},
+    {"fused1_kernel", nullptr},
+    {"fused420_kernel<12>", "fused420_kernel<12>/narrow"},
+    {"fused422_12_kernel", "fused422_12_kernel/narrow"},
+    {"fused444_12_kernel", "fused444_12_kernel/narrow"},
+    {"fused1_kernel<12>", nullptr},
+    {"fusedxt420_kernel", nullptr},
+    {"fusedxtw420_kernel", nullptr},
+    {"fused_flat_kernel", nullptr},
+    {"fused_tile_kernel", nullptr},
+    {"idct_planes_kernel+upsample_color_kernel", nullptr},
+    {"idct_planes_long_kernel+upsample_color_kernel", nullptr},
+    {"idct_planes_kernel+xt_merge_kernel", nullptr},
+    {"idct_planes_kernel+xt_merge_general_kernel", nullptr},
+    {"idct_planes_kernel+xt_merge1_kernel", nullptr},
+};
+static_assert(sizeof(RECON_NAMES) / sizeof(RECON_NAMES[0]) == (size_t)Recon::XT_MERGE1 + 1, "one name per kernel");
 
 const char *mijpeg_kernel_name(const mijpeg_batch *b)
 try {
   if (!b) return "";
-  if (use_fusedxt(b)) return b->xt->residual_hidden_bits ? "fusedxtw420_kernel" : "fusedxt420_kernel";
-  if (use_fused420p(b)) return "fused420p_kernel";
-  if (use_fused422(b)) return chroma_packed(b->info) ? "fused422_kernel" : "fused422_kernel<wide>";
-  if (use_fused440(b)) return chroma_packed(b->info) ? "fused440_kernel" : "fused440_kernel<wide>";
-  if (use_fused411(b)) return "fused411_kernel";
-  if (use_fused1(b)) return "fused1_kernel";
-  if (use_fused420_12(b)) return narrow12_colour(b->info) ? "fused420_kernel<12>/narrow" : "fused420_kernel<12>";
-  if (use_fused1_12(b)) return "fused1_kernel<12>";
-  if (use_fused444_12(b)) return narrow12_colour(b->info) ? "fused444_12_kernel/narrow" : "fused444_12_kernel";
-  if (use_fused422_12(b)) return narrow12_colour(b->info) ? "fused422_12_kernel/narrow" : "fused422_12_kernel";
-  if (b->info.coef_wide) return "idct_planes_long_kernel+upsample_color_kernel";
-  if (use_fused420(b)) return "fused420_kernel";
-  if (use_fused444(b)) return "fused444_kernel";
-  if (b->info.xt && b->info.components == 1) return "idct_planes_kernel+xt_merge1_kernel";
-  if (b->info.xt) return b->xt && b->xt->general ? "idct_planes_kernel+xt_merge_general_kernel" : "idct_planes_kernel+xt_merge_kernel";
-  if (use_fused_flat(b)) return "fused_flat_kernel";
-  if (b->quant_dev || (b->flags & MIJPEG_FLAG_FORCE_GENERIC) || getenv("MIJPEG_NO_FUSED_TILE") || dnl_row_missing(b->info)) return "idct_planes_kernel+upsample_color_kernel";
-  return "fused_tile_kernel";
+  const ReconPlan p = plan_reconstruct(b);
+  return RECON_NAMES[(int)p.kernel][p.wide || p.narrow12 ? 1 : 0];
 } catch (...) { (void)boundary_catch(nullptr, "mijpeg_kernel_name"); return nullptr; }
 
 static const size_t LUT_BYTES = 3 * 4096 * sizeof(int32_t);
@@ -2631,14 +2532,21 @@ static size_t xt_table_bytes(const mijpeg_batch *b)
 // per-frame tables (quant_dev) are expanded to the transforms' operands (deltas << 4, int32) in the workspace
 static size_t expanded_tables_bytes(const mijpeg_batch *b) { return b->quant_dev ? (size_t)b->frames * 4 * 64 * sizeof(int32_t) : 0; }
 
-size_t mijpeg_workspace_bytes(const mijpeg_batch *b)
-try {
-  if (!b) return 0;
-  if (use_fused420(b) || use_fused444(b) || use_fused422(b) || use_fused440(b) || use_fused411(b) || use_fused1(b) || use_fused420_12(b) || use_fused1_12(b) || use_fused444_12(b) || use_fused422_12(b)) return expanded_tables_bytes(b);
-  if (use_fusedxt(b)) return LUT_BYTES;
+static bool is_fused_xt(Recon k) { return k == Recon::FUSEDXT420 || k == Recon::FUSEDXTW420; }
+
+static size_t workspace_need(const mijpeg_batch *b, const ReconPlan &p)
+{
+  if (is_fused_xt(p.kernel)) return LUT_BYTES;
+  if (p.kernel < Recon::FUSEDXT420) return expanded_tables_bytes(b);
   // [LUT_BYTES: L lookup tables (JPEG XT, up to 3 x 4096 entries)] [per frame: int32 sample planes, one sample per
   // coefficient: coef_count of them, fewer when the residual planes hold 32-bit coefficients] [expanded per-frame tables]
+  // [JPEG XT tables]
   return LUT_BYTES + (size_t)b->info.coef_count * sizeof(int32_t) * (size_t)b->frames + expanded_tables_bytes(b) + xt_table_bytes(b);
+}
+
+size_t mijpeg_workspace_bytes(const mijpeg_batch *b)
+try {
+  return b ? workspace_need(b, plan_reconstruct(b)) : 0;
 } catch (...) { (void)boundary_catch(nullptr, "mijpeg_workspace_bytes"); return 0; }
 
 // What a rectangle request that does not show the plain picture adds to a launch (request_model.hpp; GenericArgs::rowmap ...)
@@ -2665,21 +2573,18 @@ static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const Requ
   if ((f.precision != 8 && f.precision != 12) || f.components < 1 || f.components > 4) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED;
   if (f.xt && (!b->xt || (f.components != 3 && f.components != 1))) return MIJPEG_ERR_MISSING_PARAMETER; // (one component: grey scale with a residual)
   if (f.coef_wide && (f.xt || b->quant_dev)) return MIJPEG_ERR_INVALID_PARAMETER; // int32 planes: single plain JPEG frames only
-  const bool fast = fast_ok(b) && !f.coef_wide;
+  const ReconPlan p = plan_reconstruct(b);
+  const size_t need = workspace_need(b, p);
+  if (need && (!b->workspace || b->workspace_bytes < need)) return MIJPEG_ERR_MISSING_PARAMETER;
   hipStream_t s = (hipStream_t)stream;
   int rc;
-  const bool f444 = use_fused444(b), fxt = use_fusedxt(b), f422 = use_fused422(b), f440 = use_fused440(b), f411 = use_fused411(b), f1 = use_fused1(b);
-  const bool f420_12 = use_fused420_12(b), f1_12 = use_fused1_12(b), f444_12 = use_fused444_12(b), f422_12 = use_fused422_12(b);
-  if (fxt && (!b->workspace || b->workspace_bytes < LUT_BYTES)) return MIJPEG_ERR_MISSING_PARAMETER;
   const int32_t *qdev = nullptr;
   if (b->quant_dev) {
-    const size_t need = mijpeg_workspace_bytes(b);
-    if (!b->workspace || b->workspace_bytes < need) return MIJPEG_ERR_MISSING_PARAMETER;
     int32_t *dst = (int32_t *)((char *)b->workspace + (need - expanded_tables_bytes(b) - xt_table_bytes(b)));
     if (launch_expand_deltas(b->quant_dev, dst, b->frames, s)) return MIJPEG_ERR_DEVICE;
     qdev = dst;
   }
-  if (use_fused420(b) || f444 || fxt || f422 || f440 || f411 || f1 || f420_12 || f1_12 || f444_12 || f422_12) {
+  if (p.kernel <= Recon::FUSEDXTW420) {
     FusedXtArgs xa;
     memset(&xa, 0, sizeof(xa));
     Fused420Args &a = xa.base;
@@ -2697,19 +2602,20 @@ static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const Requ
     a.bh_y = f.blocks_h[0];
     a.bw_c = f.blocks_w[1];
     a.bh_c = f.blocks_h[1];
-    a.cw = f440 ? f.width : f411 ? (f.width + 3) / 4 : (f.width + 1) / 2;
-    a.ch = (f422 || f411 || f422_12) ? f.height : (f.height + 1) / 2;
+    const bool full_height = p.sampling == Sampling::S422 || p.sampling == Sampling::S411; // (chroma subsampled horizontally only)
+    a.cw = p.sampling == Sampling::S440 ? f.width : p.sampling == Sampling::S411 ? (f.width + 3) / 4 : (f.width + 1) / 2;
+    a.ch = full_height ? f.height : (f.height + 1) / 2;
     // DNL frames: the reference's upsamplers never learnt the height (upsampling/upsamplerbase.cpp:61-75), their line buffers
     // have no bottom edge: below the last chroma line comes what the block rows hold (the padding of the last one, then the
     // MCU row the first scan created behind the picture: the store has it, include/mijpeg.h) instead of that line again
-    if (f.dnl && !(f422 || f411 || f422_12) && f.components > 1) a.ch = a.bh_c * 8;
+    if (f.dnl && !full_height && f.components > 1) a.ch = a.bh_c * 8;
     a.tiles_x = (f.width + 127) / 128;
     a.tiles_y = (f.height + 127) / 128;
     a.frames = b->frames;
     for (int c = 0; c < 3; c++)
       fill_deltas(a.q[c], f.quant[f.quant_index[c]]);
     a.qdev = qdev;
-    if (fxt) {
+    if (is_fused_xt(p.kernel)) {
       const mijpeg_xt_params &x = *b->xt;
       const mijpeg_info &r = x.residual;
       for (int c = 0; c < 3; c++) {
@@ -2727,12 +2633,10 @@ static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const Requ
       xa.ext.out_shift = x.out_shift;
       xa.ext.rprecision = r.precision + x.residual_hidden_bits;
       // (the two-wave flavour of the hidden-bit kernel keeps the luma block as int16: sample * 16 + 2056 with |sample * 16| <= 4 sum |c| q)
-      xa.luma_fits16 = f.range_max[0] < 7600 ? 1 : 0;
-      rc = launch_fusedxt420(xa, s);
-    } else
-      rc = f420_12 ? launch_fused420_12(a, narrow12_colour(f), s) : f444_12 ? launch_fused444_12(a, narrow12_colour(f), s) : f422_12 ? launch_fused422_12(a, narrow12_colour(f), s) : f1_12 ? launch_fused1_12(a, s) : f1 ? launch_fused1(a, s) : f444 ? launch_fused444(a, s) : f422 ? launch_fused422(a, !chroma_packed(f), s) : f440 ? launch_fused440(a, !chroma_packed(f), s) : f411 ? launch_fused411(a, s) : use_fused420p(b) ? launch_fused420p(a, use_dot2_pass(b), s) : launch_fused420(a, fast, s);
+      xa.luma_fits16 = f.range_max[0] < GATE_INT16_SAMPLES ? 1 : 0;
+    }
+    rc = launch_fused(p, xa, s);
   } else {
-    if (!b->workspace || b->workspace_bytes < mijpeg_workspace_bytes(b)) return MIJPEG_ERR_MISSING_PARAMETER;
     GenericArgs a;
     memset(&a, 0, sizeof(a));
     a.coef = b->coef_dev;
@@ -2776,10 +2680,9 @@ static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const Requ
     for (int c = 0; c < f.components; c++) plane(c, f, c, lprec);
     if (f.coef_wide) { a.wide_first = 0; a.wide_count = f.components; a.wide_long = 1; }
     // int16 sample planes between the two kernels: |sample * 16| <= 2048 (level shift) + 4 * range_max must fit 16 bits
-    static const bool int32_planes = getenv("MIJPEG_GENERIC_INT32") != nullptr; // A-B comparisons
-    a.narrow = fast && !f.xt && f.precision == 8 && !f.coef_wide && !int32_planes;
+    a.narrow = p.fast && !f.xt && f.precision == 8;
     for (int c = 0; c < f.components && a.narrow; c++)
-      if (f.range_max[c] >= 7600) a.narrow = 0;
+      if (f.range_max[c] >= GATE_INT16_SAMPLES) a.narrow = 0;
     a.maxval = (1 << lprec) - 1;
     a.dcshift = (1 << (lprec - 1)) << 4;
     if (f.xt) {
@@ -2816,7 +2719,7 @@ static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const Requ
       a.xt_rct = x.rct;
       a.xt_noclamp = x.clamp ? 0 : 1;
       a.xt_rbits = x.residual.components ? xrbits : 4;
-      a.legacy32 = lprec == 8 && f.range_max[0] < 16384 && f.range_max[1] < 16384 && f.range_max[2] < 16384 &&
+      a.legacy32 = lprec == 8 && f.range_max[0] < GATE_XT_LEGACY && f.range_max[1] < GATE_XT_LEGACY && f.range_max[2] < GATE_XT_LEGACY &&
                    !(b->flags & MIJPEG_FLAG_FORCE_SAFE);
       a.ltable = (const int32_t *)b->workspace;
       for (int c = 0; c < 3; c++)
@@ -2832,7 +2735,7 @@ static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const Requ
         memcpy(a.lmat, x.lmat, sizeof(a.lmat));
         memcpy(a.rmat, x.rmat, sizeof(a.rmat));
         memcpy(a.cmat, x.cmat, sizeof(a.cmat));
-        char *tp = (char *)b->workspace + (mijpeg_workspace_bytes(b) - xt_table_bytes(b));
+        char *tp = (char *)b->workspace + (need - xt_table_bytes(b));
         for (int c = 0; c < 3; c++) {
           // only the highest-frequency delta is used, with the colour bits folded in (residualblockhelper.cpp:351-364)
           // (m_usQuantization is a UWORD: deltas >= 4096 wrap; shifted where the path has more than one fractional bit)
@@ -2871,13 +2774,8 @@ static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const Requ
       }
       if (!f.xt) a.ycbcr = rx->ycc; // the colour transformer the first request built (colortransformerfactory.cpp:220-221)
     }
-    // plain JPEG frames of any layout go through LDS in one pass (fused_tile_kernel); the pair with its sample planes in HBM
-    // stays for JPEG XT, int32 coefficient planes, per-frame tables in device memory, rectangle requests and MIJPEG_FLAG_FORCE_GENERIC
-    static const bool no_tile = getenv("MIJPEG_NO_FUSED_TILE") != nullptr; // A-B measurements
-    const bool tile = !rx && !f.xt && !f.coef_wide && !qdev && !(b->flags & MIJPEG_FLAG_FORCE_GENERIC) && !no_tile && !dnl_row_missing(f);
-    rc = !rx && use_fused_flat(b) ? launch_fused_flat(a, s) : -1;
-    if (rc == -1) rc = tile ? launch_fused_tile(a, fast || tile_fast12(b), s) : -1;
-    if (rc == -1) rc = launch_generic(a, fast, s);
+    rc = p.kernel == Recon::FLAT ? launch_fused_flat(a, s) : p.kernel == Recon::TILE ? launch_fused_tile(a, p.fast || p.fast12, s) : -1;
+    if (rc == -1) rc = launch_generic(a, p.fast, s); // (also where no tile of fused_tile_kernel fits LDS)
   }
   return rc ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
 }

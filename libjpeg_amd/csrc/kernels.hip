@@ -1186,7 +1186,7 @@ __device__ __forceinline__ unsigned tap_sum_pk(unsigned a, unsigned w)
 }
 
 // D2: the second pass of every transform on v_dot2 (idct_columns_dot2; admitted by the host where sum |c| q <= 1476 in all three
-// components: use_dot2_pass in capi.cpp)
+// components: plan_reconstruct in capi.cpp)
 template <int MINW, bool QDEV, bool D2 = false>
 __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fused420Args a)
 {
@@ -1611,7 +1611,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(const Fuse
 // 12-bit flavour of the 4:2:2 kernel (SOF1, P = 12; 16-bit samples out, 4 B in + 6 B out per pixel): the same tile, the chroma
 // samples as 32-bit values in two LDS planes (a 12-bit chroma sample times 16 does not fit 16 bits: 72 KB + the fetch staging
 // = half a CU's LDS, two workgroups per CU), fused420_kernel<.., 12>'s colour stage behind the horizontal filter.  Gates:
-// use_fused422_12 (capi.cpp), the 12-bit 4:2:0 kernel's.
+// plan_reconstruct's 12-bit gate (capi.cpp), the 12-bit 4:2:0 kernel's.
 template <bool QDEV, bool N12>
 __global__ __launch_bounds__(F420_THREADS, 2) void fused422_12_kernel(const Fused420Args a)
 {
@@ -2162,7 +2162,7 @@ __global__ __launch_bounds__(F420_THREADS, FXT_MINW) void fusedxt420_kernel(cons
 #endif
 
   for (int i = tid; i < 3 * 256; i += F420_THREADS) ltab[i] = x.ltable[i] - x.out_shift; // the merge subtracts it anyway
-  f420_chroma_to_lds<true, false, true>(a, coef, cplane, stage, lane, wave, tx, ty); // (the legacy frame passed the 16384 range check: use_fusedxt)
+  f420_chroma_to_lds<true, false, true>(a, coef, cplane, stage, lane, wave, tx, ty); // (the legacy frame passed the 16384 range check: plan_reconstruct)
   __syncthreads();
   f420_chroma_edges(a, cplane, tid, tx, ty);
 
@@ -2386,7 +2386,7 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
   const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
 
   for (int i = tid; i < 3 * 256; i += F420_THREADS) ltab[i] = (ltab_t)(x.ltable[i] - x.out_shift);
-  f420_chroma_to_lds<true, false, true>(a, coef, cplane, stage, lane, wave, tx, ty); // (the legacy frame passed the 16384 range check: use_fusedxt)
+  f420_chroma_to_lds<true, false, true>(a, coef, cplane, stage, lane, wave, tx, ty); // (the legacy frame passed the 16384 range check: plan_reconstruct)
   __syncthreads();
   f420_chroma_edges(a, cplane, tid, tx, ty);
 
@@ -2739,7 +2739,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(const Fuse
 // 12-bit flavour (SOF1, P = 12; 16-bit samples out, 6 B in + 6 B out per pixel): the same decomposition with the chroma blocks kept as
 // 32-bit values (64 + 64 VGPRs: a 12-bit chroma sample times 16 does not fit 16 bits), two waves per SIMD.  The colour stage is
 // fused420_kernel<.., 12>'s: (y' + 32776 + (c L >> 13)) >> 4 clamped to [0, 4095], exact under the host's range gates
-// (use_fused444_12: the 12-bit 4:2:0 kernel's bounds; there is no filter between transform and colour stage here).
+// (plan_reconstruct: the 12-bit 4:2:0 kernel's bounds; there is no filter between transform and colour stage here).
 template <bool QDEV, bool N12>
 __global__ __launch_bounds__(F420_THREADS, 2) void fused444_12_kernel(const Fused420Args a)
 {
@@ -3668,7 +3668,7 @@ __global__ __launch_bounds__(256, TILE_MINW) void fused_tile_kernel(const Generi
             if (FAST) {
               // the reference's 64-bit sum (y 8192 + c' L + 65536) >> 17 with c' = c - level shift in 32 bits: c' L = q 2^13 + r,
               // 0 <= r < 2^13, gives ((y + 8 + q) 2^13 + r) >> 17 = (y + 8 + q) >> 4 exactly (fused420_kernel<12> has the proof;
-              // FAST bounds the chroma samples times 16 by 181 200, see use_fused420_12 in capi.cpp: the products stay inside
+              // FAST bounds the chroma samples times 16 by 181 200, see plan_reconstruct in capi.cpp: the products stay inside
               // 32 bits, the operands inside 24)
               const int yk = s[0][x] + 8, cb = s[NC > 1 ? 1 : 0][x] - a.dcshift, cr = s[NC > 2 ? 2 : 0][x] - a.dcshift;
               const int r = (yk + (__mul24(cr, L_CR_R) >> 13)) >> 4;
@@ -4167,149 +4167,53 @@ static Fused420Args with_tile_magic(const Fused420Args &a0)
 #ifndef F420_12_MINW
 #define F420_12_MINW 2
 #endif
-int launch_fused420(const Fused420Args &a0, bool fast, hipStream_t stream)
+// The steps every fused launch shares: tile magic, the grid in the kernel's tile order, nothing to launch on an empty grid,
+// the error check
+template <int ORDER = MIJ_TILE_ORDER, typename... Extra>
+static int launch_tiles(void (*kernel)(Fused420Args, Extra...), const Fused420Args &a0, hipStream_t stream, const Extra &...extra)
 {
   const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
+  const unsigned total = workgroups_for_tiles<ORDER>((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
   if (total == 0) return 0;
-  // two workgroups per CU for both flavours (132 / 194 VGPRs)
-  if (a.qdev) {
-    if (!fast) hipLaunchKernelGGL((fused420_kernel<false, 2, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((fused420_kernel<true, F420_FAST_MINW, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  } else if (!fast) hipLaunchKernelGGL((fused420_kernel<false, 2, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused420_kernel<true, F420_FAST_MINW, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
+  hipLaunchKernelGGL(kernel, dim3(total), dim3(F420_THREADS), 0, stream, a, extra...);
   return (int)hipGetLastError();
 }
 
-int launch_fused420_12(const Fused420Args &a0, bool narrow, hipStream_t stream)
+int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t s)
 {
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles<1>((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (total == 0) return 0;
-  if (a.qdev) {
-    if (narrow) hipLaunchKernelGGL((fused420_kernel<true, F420_12_MINW, true, 12, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((fused420_kernel<true, F420_12_MINW, true, 12, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  } else if (narrow) hipLaunchKernelGGL((fused420_kernel<true, F420_12_MINW, false, 12, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused420_kernel<true, F420_12_MINW, false, 12, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  return (int)hipGetLastError();
-}
-
-int launch_fused420p(const Fused420Args &a0, bool dot2, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (total == 0) return 0;
-  // four workgroups per CU (127 VGPRs with the luma prefetch, 27 KB LDS); the per-frame-table build three (133 VGPRs)
-  if (a.qdev) hipLaunchKernelGGL((fused420p_kernel<3, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else if (dot2) hipLaunchKernelGGL((fused420p_kernel<F420P_MINW, false, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused420p_kernel<F420P_MINW, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  return (int)hipGetLastError();
-}
-
-int launch_fusedxt420(const FusedXtArgs &x0, hipStream_t stream)
-{
-  FusedXtArgs x = x0;
-  x.base = with_tile_magic(x0.base);
-  const unsigned total = workgroups_for_tiles<XT_TILE_ORDER>((unsigned)x.base.tiles_x, (unsigned)x.base.tiles_y * (unsigned)x.base.frames);
-  if (x.ext.rprecision > 12) {
-    static const bool one_wave = getenv("MIJPEG_XTW_ONE_WAVE") != nullptr; // A-B comparisons
-    if (x.luma_fits16 && x.ext.is_float && !one_wave) hipLaunchKernelGGL(fusedxtw420_kernel<true>, dim3(total), dim3(F420_THREADS), 0, stream, x.base, x.ext);
-    else hipLaunchKernelGGL(fusedxtw420_kernel<false>, dim3(total), dim3(F420_THREADS), 0, stream, x.base, x.ext);
+  const Fused420Args &a = x.base;
+  const bool q = a.qdev != nullptr;
+  switch (p.kernel) {
+  case Recon::FUSED420: // two workgroups per CU for both flavours (132 / 194 VGPRs)
+    if (p.fast) return launch_tiles(q ? fused420_kernel<true, F420_FAST_MINW, true> : fused420_kernel<true, F420_FAST_MINW, false>, a, s);
+    return launch_tiles(q ? fused420_kernel<false, 2, true> : fused420_kernel<false, 2, false>, a, s);
+  case Recon::FUSED420P: // four workgroups per CU (127 VGPRs with the luma prefetch, 27 KB LDS); the per-frame-table build three (133 VGPRs)
+    return launch_tiles(q ? fused420p_kernel<3, true> : p.dot2 ? fused420p_kernel<F420P_MINW, false, true> : fused420p_kernel<F420P_MINW, false>, a, s);
+  case Recon::FUSED422:
+    if (p.wide) return launch_tiles(q ? fused422_kernel<3, true, true> : fused422_kernel<3, false, true>, a, s);
+    return launch_tiles(q ? fused422_kernel<3, true, false> : fused422_kernel<3, false, false>, a, s);
+  case Recon::FUSED440:
+    if (p.wide) return launch_tiles(q ? fused440_kernel<3, true, true> : fused440_kernel<3, false, true>, a, s);
+    return launch_tiles(q ? fused440_kernel<3, true, false> : fused440_kernel<3, false, false>, a, s);
+  case Recon::FUSED411: return launch_tiles(q ? fused411_kernel<3, true> : fused411_kernel<3, false>, a, s);
+  case Recon::FUSED444: // 168 VGPRs -> three waves per SIMD: 5 % faster than the unconstrained 171-register build
+    return launch_tiles(q ? fused444_kernel<2, true> : fused444_kernel<3, false>, a, s);
+  case Recon::FUSED1: return launch_tiles<1>(q ? fused1_kernel<true, 8> : fused1_kernel<false, 8>, a, s);
+  case Recon::FUSED420_12:
+    if (p.narrow12) return launch_tiles<1>(q ? fused420_kernel<true, F420_12_MINW, true, 12, true> : fused420_kernel<true, F420_12_MINW, false, 12, true>, a, s);
+    return launch_tiles<1>(q ? fused420_kernel<true, F420_12_MINW, true, 12, false> : fused420_kernel<true, F420_12_MINW, false, 12, false>, a, s);
+  case Recon::FUSED422_12:
+    if (p.narrow12) return launch_tiles(q ? fused422_12_kernel<true, true> : fused422_12_kernel<false, true>, a, s);
+    return launch_tiles(q ? fused422_12_kernel<true, false> : fused422_12_kernel<false, false>, a, s);
+  case Recon::FUSED444_12:
+    if (p.narrow12) return launch_tiles(q ? fused444_12_kernel<true, true> : fused444_12_kernel<false, true>, a, s);
+    return launch_tiles(q ? fused444_12_kernel<true, false> : fused444_12_kernel<false, false>, a, s);
+  case Recon::FUSED1_12: return launch_tiles<1>(q ? fused1_kernel<true, 12> : fused1_kernel<false, 12>, a, s);
+  case Recon::FUSEDXT420: return launch_tiles<XT_TILE_ORDER>(fusedxt420_kernel, a, s, x.ext);
+  case Recon::FUSEDXTW420:
+    return launch_tiles<XT_TILE_ORDER>(x.luma_fits16 && x.ext.is_float ? fusedxtw420_kernel<true> : fusedxtw420_kernel<false>, a, s, x.ext);
+  default: return -1; // (not a kernel of this launcher)
   }
-  else hipLaunchKernelGGL(fusedxt420_kernel, dim3(total), dim3(F420_THREADS), 0, stream, x.base, x.ext);
-  return (int)hipGetLastError();
-}
-
-int launch_fused422(const Fused420Args &a0, bool wide, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (wide) {
-    if (a.qdev) hipLaunchKernelGGL((fused422_kernel<3, true, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((fused422_kernel<3, false, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  } else {
-    if (a.qdev) hipLaunchKernelGGL((fused422_kernel<3, true, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((fused422_kernel<3, false, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  }
-  return (int)hipGetLastError();
-}
-
-int launch_fused411(const Fused420Args &a0, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (a.qdev) hipLaunchKernelGGL((fused411_kernel<3, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused411_kernel<3, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  return (int)hipGetLastError();
-}
-
-int launch_fused1(const Fused420Args &a0, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles<1>((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (a.qdev) hipLaunchKernelGGL((fused1_kernel<true, 8>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused1_kernel<false, 8>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  return (int)hipGetLastError();
-}
-
-int launch_fused1_12(const Fused420Args &a0, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles<1>((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (a.qdev) hipLaunchKernelGGL((fused1_kernel<true, 12>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused1_kernel<false, 12>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  return (int)hipGetLastError();
-}
-
-int launch_fused440(const Fused420Args &a0, bool wide, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (wide) {
-    if (a.qdev) hipLaunchKernelGGL((fused440_kernel<3, true, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((fused440_kernel<3, false, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  } else {
-    if (a.qdev) hipLaunchKernelGGL((fused440_kernel<3, true, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((fused440_kernel<3, false, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  }
-  return (int)hipGetLastError();
-}
-
-int launch_fused444(const Fused420Args &a0, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (total == 0) return 0;
-  // 168 VGPRs -> three waves per SIMD: 5 % faster than the unconstrained 171-register build
-  if (a.qdev) hipLaunchKernelGGL((fused444_kernel<2, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused444_kernel<3, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  return (int)hipGetLastError();
-}
-
-int launch_fused422_12(const Fused420Args &a0, bool narrow, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (total == 0) return 0;
-  if (a.qdev) {
-    if (narrow) hipLaunchKernelGGL((fused422_12_kernel<true, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((fused422_12_kernel<true, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  } else if (narrow) hipLaunchKernelGGL((fused422_12_kernel<false, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused422_12_kernel<false, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  return (int)hipGetLastError();
-}
-
-int launch_fused444_12(const Fused420Args &a0, bool narrow, hipStream_t stream)
-{
-  const Fused420Args a = with_tile_magic(a0);
-  const unsigned total = workgroups_for_tiles((unsigned)a.tiles_x, (unsigned)a.tiles_y * (unsigned)a.frames);
-  if (total == 0) return 0;
-  if (a.qdev) {
-    if (narrow) hipLaunchKernelGGL((fused444_12_kernel<true, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-    else hipLaunchKernelGGL((fused444_12_kernel<true, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  } else if (narrow) hipLaunchKernelGGL((fused444_12_kernel<false, true>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  else hipLaunchKernelGGL((fused444_12_kernel<false, false>), dim3(total), dim3(F420_THREADS), 0, stream, a);
-  return (int)hipGetLastError();
 }
 
 // per-frame tables as the client hands them over (u16 deltas, [frames][4][64]) -> the operands of the transforms (<< 4, int32)
@@ -4334,11 +4238,10 @@ static size_t fused_tile_geometry(GenericArgs &a, bool narrow)
   int hmax = 1, vmax = 1;
   for (int c = 0; c < a.ncomp; c++) { hmax = max(hmax, a.subx[c]); vmax = max(vmax, a.suby[c]); }
   const int mw = 8 * hmax, mh = 8 * vmax;
-  static const int env_w = getenv("MIJPEG_TILE_W") ? atoi(getenv("MIJPEG_TILE_W")) : 0, env_h = getenv("MIJPEG_TILE_H") ? atoi(getenv("MIJPEG_TILE_H")) : 0; // A-B measurements
   // a subsampled direction pays a block row / column of halo on each side of the tile: twice the extent there halves its share
   // (1x4 frames: 327 -> 479 Gpixel/s with 128 lines instead of 64)
-  const int want_w[3] = {env_w ? env_w : hmax > 1 ? 128 : 64, 64, 32};
-  int want_h[4] = {env_h ? env_h : vmax > 1 ? 128 : 64, 64, 48, 32};
+  const int want_w[3] = {hmax > 1 ? 128 : 64, 64, 32};
+  int want_h[4] = {vmax > 1 ? 128 : 64, 64, 48, 32};
   if (want_h[0] == 64) { want_h[1] = 48; want_h[2] = 32; want_h[3] = 16; }
   auto plane_bytes = [&](int tw, int th) {
     size_t samples = 0;
@@ -4359,7 +4262,7 @@ static size_t fused_tile_geometry(GenericArgs &a, bool narrow)
       const int tw = mw * max(1, want_w[iw] / mw);
       int th = mh * max(1, want_h[ih] / mh);
       if (plane_bytes(tw, th) + staging > two) continue;
-      if (plane_bytes(tw, th) + staging > three && ih + 1 < 4 && !env_h) {
+      if (plane_bytes(tw, th) + staging > three && ih + 1 < 4) {
         const int th2 = mh * max(1, want_h[ih + 1] / mh);
         if (th2 * 4 >= th * 3 && plane_bytes(tw, th2) + staging <= three) th = th2;
       }

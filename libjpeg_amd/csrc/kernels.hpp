@@ -117,18 +117,30 @@ struct GenericArgs {
   int32_t tile_w, tile_h, tiles_x, tiles_y;
 };
 
-int launch_fused420(const Fused420Args &a, bool fast, hipStream_t stream);
-int launch_fused1_12(const Fused420Args &a, hipStream_t stream);   // 12-bit single component frames inside the range gate
-int launch_fused420_12(const Fused420Args &a, bool narrow, hipStream_t stream); // 12-bit frames inside the range gates, 16-bit samples out; narrow: the colour sums fit 32 bits (colour12)
-int launch_fused420p(const Fused420Args &a, bool dot2, hipStream_t stream); // FAST only, chroma samples within int16 filter range; dot2: the second pass in 16 bits too (range_max <= 1476)
-int launch_fused444(const Fused420Args &a, hipStream_t stream); // same argument block; all planes bw_y x bh_y
-int launch_fused422_12(const Fused420Args &a, bool narrow, hipStream_t stream); // 12-bit 4:2:2 frames inside the range gates
-int launch_fused444_12(const Fused420Args &a, bool narrow, hipStream_t stream); // 12-bit 4:4:4 frames inside the range gates, 16-bit samples out
-int launch_fused1(const Fused420Args &a, hipStream_t stream);   // single component: plane off_y, bw_y x bh_y blocks, one byte per pixel
-int launch_fused440(const Fused420Args &a, bool wide, hipStream_t stream);
-int launch_fused411(const Fused420Args &a, hipStream_t stream); // same argument block; chroma planes bw_c x bh_y, cw = ceil(W/4), ch = H // same argument block; chroma planes bw_y x bh_c, cw = W, ch = ceil(H/2)
-int launch_fused422(const Fused420Args &a, bool wide, hipStream_t stream); // wide: 32-bit filters for chroma ranges between the packed gate and 8190 // same argument block; chroma planes bw_c x bh_y, cw = ceil(W/2), ch = H
-int launch_fusedxt420(const FusedXtArgs &x, hipStream_t stream);
+// The reconstruction capi.cpp's planner (plan_reconstruct) chose for a batch.  The kernels up to FUSEDXTW420 take a Fused420Args
+// block (launch_fused); the others the plane description of GenericArgs (launch_fused_flat, launch_fused_tile, launch_generic).
+enum class Recon : uint8_t {
+  FUSED420P, FUSED420, FUSED422, FUSED440, FUSED411, FUSED444, FUSED1, // 8 bit
+  FUSED420_12, FUSED422_12, FUSED444_12, FUSED1_12,                    // 12 bit, 16-bit samples out
+  FUSEDXT420, FUSEDXTW420,                                             // JPEG XT profile C, without / with residual hidden bits
+  FLAT, TILE,                                                          // fused_flat_kernel, fused_tile_kernel
+  PAIR, PAIR_LONG,                                                     // idct_planes(_long)_kernel + upsample_color_kernel
+  XT_MERGE, XT_MERGE_GENERAL, XT_MERGE1,                               // idct_planes_kernel + the JPEG XT merge kernels
+};
+// sampling layout of a frame as the fused kernels know it: three components with 1 x 1 chroma, or one component
+enum class Sampling : uint8_t { S420, S422, S440, S411, S444, GREY, OTHER };
+struct ReconPlan {
+  Recon kernel;
+  Sampling sampling;
+  bool fast;     // fast arithmetic: range check passed, every delta << 4 a signed 16-bit operand, int16 coefficients
+  bool wide;     // FUSED422 / FUSED440: chroma ranges between the packed gate and 8190, 32-bit filters
+  bool dot2;     // FUSED420P: the second transform pass in 16 bits too (range_max <= 1476, or MIJPEG_FLAG_FORCE_DOT2)
+  bool narrow12; // 12-bit three-component kernels: the colour sums fit 32 bits (colour12)
+  bool fast12;   // TILE: the fast flavour for a 12-bit frame inside the 12-bit range gates
+};
+
+// The kernels up to FUSEDXTW420: x.ext and x.luma_fits16 are read for the JPEG XT ones only
+int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t stream);
 int launch_generic(const GenericArgs &a, bool fast, hipStream_t stream);
 // The same frames in one pass through LDS (plain JPEG: no residual planes, int16 coefficients, tables by value): any sampling
 // layout, 1..4 components, 8 or 12 bit.  Uses the plane description of GenericArgs; no workspace.

@@ -13,4 +13,4 @@ timeout 200 python tools/multiscan_probe.py make /tmp/ms > /dev/null 2>&1
 MIJPEG_TRACE_SUBMIT=1 MIJPEG_READ_TIMES=1 timeout 200 python tools/multiscan_probe.py run /tmp/ms 6 > $O/multiscan_probe.txt 2>&1; grep "ran on" $O/multiscan_probe.txt
 ( cd /tmp && timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$O/multiscan_prof" -o ms -- python "$ROOT/tools/multiscan_probe.py" run /tmp/ms 4 > "$ROOT/$O/multiscan_prof.log" 2>&1 ); echo "multiscan rocprof exit $?"
 f=$(find $O/multiscan_prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && head -8 "$f"
-for i in 1 2; do timeout 120 python tools/xt_launches.py --hidden --time --launches 40 2>&1 | tail -1; MIJPEG_XTW_ONE_WAVE=1 timeout 120 python tools/xt_launches.py --hidden --time --launches 40 2>&1 | tail -1; done | tee $O/xtw_ab.txt
+for i in 1 2; do timeout 120 python tools/xt_launches.py --hidden --time --launches 40 2>&1 | tail -1; done | tee $O/xtw_ab.txt
