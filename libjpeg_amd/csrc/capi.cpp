@@ -18,130 +18,14 @@
 #include <thread>
 
 #include "../../include/mijpeg.h"
-#include "host_decoder.hpp"
+#include "decoder.hpp"
 #include "huffman_dev.hpp"
 #include "encoder.hpp"
 #include "forward.hpp"
 #include "hencode.hpp"
 #include "kernels.hpp"
-#include "request_model.hpp"
 
 using namespace mij;
-
-struct mijpeg_decoder {
-  int device = -1;
-  HostDecoder host;
-  const uint8_t *data = nullptr;
-  size_t size = 0;
-  bool parsed = false, decoded = false, uploaded = false;
-  bool parse_fresh = false; // host holds a full parse of (data, size) that nothing has touched since: mijpeg_decode_coefficients_device
-                            // found the stream not to qualify, the host decode that follows need not parse again
-  // coefficient store: pinned when a device is attached
-  int16_t *coef_host = nullptr;
-  size_t coef_host_cap = 0; // int16 units
-  int16_t *coef_dev = nullptr;
-  size_t coef_dev_cap = 0;
-  // reconstruction cache for the rectangle service
-  uint8_t *img_dev = nullptr;
-  size_t img_dev_cap = 0;
-  uint8_t *img_host = nullptr; // pinned
-  size_t img_host_cap = 0;
-  bool img_valid = false;      // img_dev holds the reconstructed frame for img_flags
-  bool img_host_valid = false; // ... and img_host its copy (being filled band by band, see band_events)
-  // the device-to-host copy of the reconstructed frame travels in bands of lines, one event each: a rectangle request
-  // waits for the bands it touches only, so the first stripes of a frame are served while the rest is still on its way
-  std::vector<hipEvent_t> band_events;
-  int band_lines = 0, bands = 0, bands_waited = 0;
-  uint32_t img_flags = 0;
-  int img_view = -1;           // component of a non-upsampled reconstruction, -1: the whole picture
-  // mijpeg_display_rect: the reference's state between DisplayRectangle calls (request_model.hpp) and the buffers of the
-  // requests that do not show the plain picture
-  RequestModel model, rmodel; // (rmodel: the residual image of a JPEG XT frame)
-  bool model_valid = false;
-  uint8_t *req_dev = nullptr, *req_host = nullptr; // frame-sized interleaved image (device; pinned host)
-  size_t req_dev_cap = 0, req_host_cap = 0;
-  int32_t *rowmap_dev = nullptr;
-  size_t rowmap_cap = 0;
-  int32_t *ws_dev = nullptr;
-  size_t ws_cap = 0; // bytes
-  // on-device entropy decoding: stream bytes, interval offsets, tables, status word
-  uint8_t *ent_dev = nullptr;
-  size_t ent_cap = 0;
-  uint8_t *ent_host = nullptr; // pinned staging for offsets + tables + status
-  size_t ent_host_cap = 0;
-  bool host_planes_stale = false; // coefficients live on the device only
-  double phase_prepare = 0, phase_device = 0; // last device entropy decode: host tables / upload + kernel
-  mijpeg_decoder *xt_helper = nullptr; // JPEG XT: second context that entropy-decodes the residual codestream concurrently
-  // JPEG XT alpha channel: an image of its own (ALFA box), decoded by a decoder object of its own that this one owns
-  // (mijpeg_alpha_channel); its codestream is copied here because every parse of the file rebuilds the boxes
-  mijpeg_decoder *alpha = nullptr;
-  bool alpha_ready = false;
-  int alpha_refusal = 0;          // the alpha image reads, its transformer would not build (or this path declines it): the code
-  std::string alpha_refusal_msg;
-  std::vector<uint8_t> alpha_data;
-  uint8_t *enc_dev = nullptr; // encoder direction: pixels + coefficients of one picture
-  size_t enc_cap = 0;
-  uint8_t *henc_dev[2] = {nullptr, nullptr}, *henc_out_dev[2] = {nullptr, nullptr}; // device entropy coder, two jobs: arrays; streams
-  size_t henc_cap[2] = {0, 0}, henc_out_cap[2] = {0, 0};
-  uint64_t *henc_host = nullptr; // pinned: byte counts read back from the device, code tables on their way up
-  uint8_t *walk_dev = nullptr, *walk_host = nullptr; // state of the device walk over streams without restart markers
-  size_t walk_cap = 0, walk_host_cap = 0;
-  int walk_rounds = 0;
-  uint32_t *walk_status_dev = nullptr;
-  hipStream_t copy_stream = nullptr;          // uploads of a batch's streams, ahead of the kernels that decode them
-  hipEvent_t ent_free = nullptr;              // behind the last kernel / copy that reads ent_dev
-  bool ent_free_valid = false;
-  std::vector<hipEvent_t> copy_events;
-  uint8_t *stage_host = nullptr;  // pinned gathering area for the streams of a batch
-  std::vector<uint8_t> host_stage; // the same for host-only objects (mijpeg_prepare_batch_host)
-  size_t stage_cap = 0;
-  // batches (mijpeg_decode_batch_device): one parsed decoder per stream, frame 0's info with the batch's worst range
-  std::vector<std::unique_ptr<HostDecoder>> batch_hosts;
-  mijpeg_info batch_info{};
-  int batch_frames = 0;
-  // a submitted batch whose device work has not been waited for yet (mijpeg_submit_batch_device)
-  int pend_n = 0;
-  const uint32_t *pend_status = nullptr;
-  int pend_walk_round = 0;                       // > 0: the batch went through the device walk with this many rounds, unchecked
-  const uint32_t *pend_walk_flags = nullptr;     // "something changed" per round (pinned)
-  const uint32_t *pend_walk_status = nullptr;    // per image (pinned)
-  std::chrono::steady_clock::time_point pend_t0;
-  // batches whose images bring different quantisation tables: [frames][4][64] deltas per component, on the device
-  uint16_t *batch_quant_dev = nullptr;
-  size_t batch_quant_cap = 0;
-  bool batch_own_tables = false;
-  std::vector<uint16_t> batch_quant_host;
-  // MIJPEG_FLAG_SPECULATIVE: the reconstruction of a submitted batch was launched on an ASSUMED range check (spec_assumed:
-  // what the last batch of this shape reported, rounded up to the kernel selection's next gate) behind the Huffman kernel,
-  // without the host waiting for what that kernel reports; finish_batch validates and launches again where the assumption
-  // did not hold (settle_speculation)
-  bool spec_active = false, spec_redone = false;
-  void *spec_dst = nullptr;
-  int64_t spec_frame_stride = 0, spec_row_stride = 0;
-  uint32_t spec_flags = 0;
-  int32_t spec_assumed[MIJPEG_MAX_COMPONENTS] = {0, 0, 0, 0};
-  int64_t spec_launched = 0, spec_redone_count = 0; // diagnostics (mijpeg_batch_speculation)
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  hipEvent_t chain_ev = nullptr; // mijpeg_stream_wait
-  hipEvent_t ms_ready = nullptr, ms_done = nullptr; // device_entropy_multiscan: the second frame's stream
-  hipStream_t ms_stream = nullptr;
-  int err_code = 0;
-  std::string err_msg;
-  double timing[4] = {0, 0, 0, 0};
-};
-
-static int set_error(mijpeg_decoder *d, int code, const std::string &msg)
-{
-  d->err_code = code;
-  d->err_msg = msg;
-  return code;
-}
-
-static int hip_fail(mijpeg_decoder *d, hipError_t e, const char *what)
-{
-  return set_error(d, MIJPEG_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-}
 
 // The boundary lets no C++ exception through (the reference turns everything into an error code at JPEG::Read /
 // DisplayRectangle, interface/jpeg.cpp:205-220, tools/environment.hpp:752-784): every extern "C" body is a function-try-block
@@ -175,12 +59,6 @@ static int boundary_catch(mijpeg_decoder *d, const char *where) noexcept
   }
   return code;
 }
-
-#define HIP_TRY(d, call)                                  \
-  do {                                                    \
-    hipError_t e_ = (call);                               \
-    if (e_ != hipSuccess) return hip_fail(d, e_, #call);  \
-  } while (0)
 
 // The large buffers of destroyed decoder objects -- pinned coefficient store and frame, their device mirrors -- wait here for
 // the next object on the same device: a client that constructs a JPEG object per picture (cmd/reconstruct.cpp does) would
@@ -289,15 +167,27 @@ static void release_big(int device, bool pinned, void *p, size_t bytes)
   if (pinned) (void)hipHostFree(p);
   else (void)hipFree(p);
 }
-// everything this object has enqueued is done (before one of its buffers changes hands while the object lives on: rare, a
-// buffer only grows when a larger picture arrives)
-static void quiesce(mijpeg_decoder *d)
+
+// A buffer that grows through the buffer cache: device memory, or pinned host memory (the coefficient store and the frame)
+static int ensure_cached(mijpeg_decoder *d, bool pinned, void **ptr, size_t *cap, size_t bytes)
 {
-  if (d->device < 0) return;
-  if (d->stream) (void)hipStreamSynchronize(d->stream);
-  if (d->copy_stream) (void)hipStreamSynchronize(d->copy_stream);
-  if (d->ms_stream) (void)hipStreamSynchronize(d->ms_stream);
+  if (*cap >= bytes) return MIJPEG_OK;
+  quiesce(d); // (the buffer may go to another object: nothing of this one may still read or write it)
+  release_big(d->device, pinned, *ptr, *cap);
+  *ptr = nullptr;
+  *cap = 0;
+  size_t got = 0;
+  if (void *p = buffer_cache().take(d->device, pinned, bytes, &got)) {
+    *ptr = p;
+    *cap = got;
+    return MIJPEG_OK;
+  }
+  HIP_TRY(d, pinned ? hipHostMalloc(ptr, bytes, hipHostMallocDefault) : hipMalloc(ptr, bytes));
+  *cap = bytes;
+  return MIJPEG_OK;
 }
+
+int ensure_dev(mijpeg_decoder *d, void **ptr, size_t *cap, size_t bytes) { return ensure_cached(d, false, ptr, cap, bytes); }
 
 // A batch that was submitted (mijpeg_submit_batch_device) and not waited for still reads the pinned staging buffers
 // (ent_host, stage_host, status words) from its asynchronous uploads: every entry point that rewrites them settles it first.
@@ -350,9 +240,7 @@ try {
   if (!d) return;
   if (d->device >= 0) {
     (void)hipSetDevice(d->device);
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
-    if (d->copy_stream) (void)hipStreamSynchronize(d->copy_stream); // (the buffers below may go to another object)
-    if (d->ms_stream) (void)hipStreamSynchronize(d->ms_stream);
+    quiesce(d); // (the buffers below may go to another object)
     release_big(d->device, true, d->coef_host, d->coef_host_cap * sizeof(int16_t));
     release_big(d->device, true, d->img_host, d->img_host_cap);
     release_big(d->device, false, d->coef_dev, d->coef_dev_cap * sizeof(int16_t));
@@ -416,44 +304,23 @@ try {
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(d, "mijpeg_read_header"); }
 
-static int ensure_dev(mijpeg_decoder *d, void **ptr, size_t *cap, size_t bytes);
-
 static int ensure_coef_store(mijpeg_decoder *d, size_t count, bool need_host = true)
 {
-  if (need_host && d->coef_host_cap < count) {
-    size_t cap = count;
-    if (d->device >= 0) {
-      quiesce(d); // (the buffer may go to another object: nothing of this one may still read or write it)
-      release_big(d->device, true, d->coef_host, d->coef_host_cap * sizeof(int16_t));
-      d->coef_host = nullptr;
-      d->coef_host_cap = 0;
-      size_t got = 0;
-      if (void *p = buffer_cache().take(d->device, true, count * sizeof(int16_t), &got)) {
-        d->coef_host = (int16_t *)p;
-        cap = got / sizeof(int16_t);
-      } else HIP_TRY(d, hipHostMalloc((void **)&d->coef_host, count * sizeof(int16_t), hipHostMallocDefault));
-    } else {
+  if (d->device < 0) {
+    if (need_host && d->coef_host_cap < count) {
       free(d->coef_host);
       d->coef_host = (int16_t *)malloc(count * sizeof(int16_t));
       if (!d->coef_host) return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the coefficient store");
+      d->coef_host_cap = count;
     }
-    d->coef_host_cap = cap;
+    return MIJPEG_OK;
   }
-  if (d->device >= 0 && d->coef_dev_cap < count) {
-    quiesce(d);
-    release_big(d->device, false, d->coef_dev, d->coef_dev_cap * sizeof(int16_t));
-    d->coef_dev = nullptr;
-    d->coef_dev_cap = 0;
-    size_t got = 0;
-    if (void *p = buffer_cache().take(d->device, false, count * sizeof(int16_t), &got)) {
-      d->coef_dev = (int16_t *)p;
-      d->coef_dev_cap = got / sizeof(int16_t);
-    } else {
-      HIP_TRY(d, hipMalloc((void **)&d->coef_dev, count * sizeof(int16_t)));
-      d->coef_dev_cap = count;
-    }
-  }
-  return MIJPEG_OK;
+  size_t host = d->coef_host_cap * sizeof(int16_t), dev = d->coef_dev_cap * sizeof(int16_t); // (the caps count int16)
+  int rc = need_host ? ensure_cached(d, true, (void **)&d->coef_host, &host, count * sizeof(int16_t)) : MIJPEG_OK;
+  if (!rc) rc = ensure_cached(d, false, (void **)&d->coef_dev, &dev, count * sizeof(int16_t));
+  d->coef_host_cap = host / sizeof(int16_t);
+  d->coef_dev_cap = dev / sizeof(int16_t);
+  return rc;
 }
 
 // The alpha channel of a JPEG XT file: the reference turns to the ALFA box behind the legacy codestream's EOI (and the residual
@@ -713,1065 +580,6 @@ const int16_t *mijpeg_coefficients(mijpeg_decoder *d, int component)
   return d->coef_host + d->host.info.coef_offset[component];
 }
 
-// ------------------------------------------------------------------------------------------------
-// on-device entropy decoding
-// ------------------------------------------------------------------------------------------------
-// Why a parsed stream cannot be entropy-decoded on the device (nullptr: it can).  `xt_part`: the stream is one of the
-// two codestreams of a JPEG XT profile C file (8-bit legacy or 12-bit residual frame without hidden refinement scans).
-static const char *device_entropy_obstacle(const HostDecoder &h, size_t size, bool xt_part = false)
-{
-  const mijpeg_info &f = h.info;
-  // one Huffman sequential scan over all components (or a single-component frame)
-  if (h.needs_sequential())
-    return "on-device entropy decoding: the stream is damaged; the host decoder walks it with the reference's resynchronisation (entropyparser.cpp:117-201)";
-  if (f.progressive) return "on-device entropy decoding: progressive frames are decoded on the host";
-  if (f.xt && !xt_part) return "on-device entropy decoding: not for this JPEG XT stream";
-  if (!h.residual_merged()) return "on-device entropy decoding: the legacy codestream has no EOI marker (the host decoder decides what is merged)";
-  // (a RESI box without a merging specification, a residual codestream header that does not match, tables looked up at the first
-  // request: what the reference reports behind the legacy frame's decode -- HostDecoder::decode reports it, this path would not)
-  if (h.verdict_pending()) return "on-device entropy decoding: the file's verdict is the host decoder's (residual codestream header / tables looked up at the first request)";
-  if (f.precision != 8 && !(xt_part && f.precision == 12)) return "on-device entropy decoding: 8-bit frames (12-bit residual frames of JPEG XT) only";
-  if (h.scans.size() != 1 || h.hidden_bits()) return "on-device entropy decoding: the frame has more than one scan";
-  const Scan &s = h.scans[0];
-  if (s.ncomp != f.components) return "on-device entropy decoding: the scan does not cover all components";
-  if (size > 0xfffffff0ull) return "on-device entropy decoding: stream too long";
-  for (int c = 0; c < f.components; c++)
-    if (f.hsamp[c] > 4 || f.vsamp[c] > 4) return "on-device entropy decoding: MCUs of more than 4 x 4 blocks of a component are decoded on the host";
-  return nullptr;
-}
-
-// Streams without restart markers: find their virtual restart intervals on the device.  Rounds of huffman_walk_kernel
-// until the hand-over states between neighbouring subsequences stop changing, prefix sums over the subsequences
-// (block numbers, DC predictors: huffman_walk_scan_kernel), and one EMIT walk that writes the interval tables the
-// decode kernel reads.  The host only looks at the per-round "something changed" flags.
-// `images_host` is the staging copy of the HuffImage array (first_interval = start of the image's interval entries).
-// Where the device's copy of image i's entropy coded data goes inside the launch's stream buffer (and inside the pinned
-// gathering area): a slot of the stream's own size -- known before the stream is parsed, so a batch's workers can write the
-// copy while they search it for markers -- rounded to 16 bytes, plus the pad the kernels' prefetch may run into.
-static size_t stream_slots(const size_t *sizes, int n, std::vector<size_t> &stream_off)
-{
-  stream_off.resize((size_t)n);
-  size_t off = 0;
-  for (int i = 0; i < n; i++) {
-    stream_off[(size_t)i] = off;
-    off += ((sizes[i] + 15) & ~(size_t)15) + HUFF_STREAM_PAD;
-  }
-  return off;
-}
-
-static int ensure_stage(mijpeg_decoder *d, size_t bytes)
-{
-  if (d->stage_cap >= bytes) return MIJPEG_OK;
-  if (d->stage_host) (void)hipHostFree(d->stage_host);
-  d->stage_host = nullptr;
-  d->stage_cap = 0;
-  HIP_TRY(d, hipHostMalloc((void **)&d->stage_host, bytes, hipHostMallocDefault));
-  d->stage_cap = bytes;
-  return MIJPEG_OK;
-}
-
-static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const std::vector<int> &dwalk, const HuffScanArgs &scan,
-                              const HuffImage *images_dev, uint32_t *ibegin_dev, uint8_t *iskip_dev, int16_t *ipred_dev,
-                              const HuffImage *images_host, const std::vector<size_t> &usize, bool defer = false)
-{
-  const mijpeg_info &f0 = hosts[0]->info;
-  const Scan &s0 = hosts[0]->scans[0];
-  HuffWalkArgs w;
-  memset(&w, 0, sizeof(w));
-  w.ncomp = s0.ncomp;
-  int B = 0;
-  for (int k = 0; k < s0.ncomp; k++) {
-    const int c = s0.sc[k].comp;
-    w.hs[k] = s0.ncomp > 1 ? f0.hsamp[c] : 1;
-    w.vs[k] = s0.ncomp > 1 ? f0.vsamp[c] : 1;
-    B += w.hs[k] * w.vs[k];
-  }
-  if (B > 64) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device walk");
-  w.nblk_mcu = B;
-  w.ntables = scan.ntables;
-  // subsequence size.  One image: the launch is latency-bound, its serial part is (distance the decoder needs to
-  // synchronise + two subsequences), so small ones.  Batches are throughput-bound and every round re-walks whole
-  // subsequences, so fewer rounds over larger ones (measured on 1, 4 and 16 8K frames: 128, 256, 512 bytes win).
-  size_t longest = 0, all_bytes = 0;
-  for (int i = 0; i < n; i++)
-    if (dwalk[(size_t)i]) {
-      const size_t len = usize[(size_t)i]; // (the device's copy: entropy coded data without the byte stuffing)
-      longest = std::max(longest, len);
-      all_bytes += len;
-    }
-  uint32_t sub_bytes = all_bytes <= ((size_t)8 << 20) ? 128 : all_bytes <= ((size_t)32 << 20) ? 256 : 512;
-  while (sub_bytes < 1024 && longest / sub_bytes > ((size_t)1 << 20)) sub_bytes <<= 1; // bounds the prefix-sum tiles
-  if (const char *e = getenv("MIJPEG_WALK_SUB")) sub_bytes = (uint32_t)std::max(32, std::min(4096, atoi(e))); // experiments
-  w.sub_bytes = sub_bytes;
-  // per image: its subsequences; per workgroup: image and first subsequence
-  std::vector<uint32_t> img_sub0((size_t)n, 0), img_nsub((size_t)n, 0), img_e0((size_t)n, 0), img_e1((size_t)n, 0), img_int0((size_t)n, 0);
-  uint32_t nsub_total = 0;
-  for (int i = 0; i < n; i++) {
-    const Scan &s = hosts[i]->scans[0];
-    (void)s;
-    img_e0[(size_t)i] = 0;
-    img_e1[(size_t)i] = (uint32_t)usize[(size_t)i];
-    img_int0[(size_t)i] = images_host[i].first_interval;
-    img_sub0[(size_t)i] = nsub_total;
-    if (dwalk[(size_t)i]) {
-      img_nsub[(size_t)i] = (uint32_t)((usize[(size_t)i] + sub_bytes - 1) / sub_bytes);
-      nsub_total += img_nsub[(size_t)i];
-    }
-  }
-  w.lanes = 64;
-  while (w.lanes > 1 && nsub_total / (uint32_t)w.lanes < 2048) w.lanes >>= 1;
-  if (const char *e = getenv("MIJPEG_WALK_LANES")) w.lanes = std::max(1, std::min(64, atoi(e))); // experiments (power of two)
-  w.waves_per_group = 4;
-  const uint32_t per_group = (uint32_t)(w.lanes * w.waves_per_group);
-  std::vector<uint32_t> sub_image, sub_first;
-  for (int i = 0; i < n; i++)
-    for (uint32_t k = 0; k < img_nsub[(size_t)i]; k += per_group) { sub_image.push_back((uint32_t)i); sub_first.push_back(k); }
-  w.n_groups = (int32_t)sub_image.size();
-  // one device buffer: [per group: image, first][per image: sub0, nsub, e0, e1, int0][per subsequence: state, stamp,
-  // nblocks, dcsum, first_block, first_pred][changed flag per round][status per image]
-  auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  constexpr int MAX_ROUNDS = 48;
-  const size_t G = sub_image.size(), S = nsub_total;
-  size_t o = 0;
-  const size_t o_simg = o; o = al(o + G * 4);
-  const size_t o_sfirst = o; o = al(o + G * 4);
-  const size_t o_isub0 = o; o = al(o + (size_t)n * 4);
-  const size_t o_insub = o; o = al(o + (size_t)n * 4);
-  const size_t o_e0 = o; o = al(o + (size_t)n * 4);
-  const size_t o_e1 = o; o = al(o + (size_t)n * 4);
-  const size_t o_int0 = o; o = al(o + (size_t)n * 4);
-  const size_t o_state = o; o = al(o + S * 8);
-  const size_t o_up_end = o; // up to here the host fills the buffer
-  const size_t o_flags = o; o = al(o + (size_t)(MAX_ROUNDS + 1) * 4 + (size_t)n * 4); // changed[], walk_status[]
-  const size_t o_stamp = o; o = al(o + S * 4);
-  const size_t o_zero_end = o; // flags and stamps start out as zero
-  const size_t o_nblk = o; o = al(o + S * 4);
-  const size_t o_dcsum = o; o = al(o + S * 16);
-  const size_t o_fblk = o; o = al(o + S * 4);
-  const size_t o_fpred = o; o = al(o + S * 16);
-  uint32_t most = 0;
-  for (int i = 0; i < n; i++) most = std::max(most, img_nsub[(size_t)i]);
-  const int tiles = (int)((most + HUFF_WALK_TILE - 1) / HUFF_WALK_TILE);
-  if (tiles > HUFF_WALK_TILE) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream too long for the device walk");
-  const size_t o_tiles = o; o = al(o + (size_t)n * tiles * HUFF_WALK_SUMS_BYTES);
-  const size_t total = o;
-  int rc = ensure_dev(d, (void **)&d->walk_dev, &d->walk_cap, total);
-  if (rc) return rc;
-  const size_t host_bytes = o_up_end + (o_stamp - o_flags);
-  if (d->walk_host_cap < host_bytes) {
-    if (d->walk_host) (void)hipHostFree(d->walk_host);
-    d->walk_host = nullptr;
-    d->walk_host_cap = 0;
-    HIP_TRY(d, hipHostMalloc((void **)&d->walk_host, host_bytes, hipHostMallocDefault));
-    d->walk_host_cap = host_bytes;
-  }
-  uint8_t *wh = d->walk_host, *wd = d->walk_dev;
-  memcpy(wh + o_simg, sub_image.data(), G * 4);
-  memcpy(wh + o_sfirst, sub_first.data(), G * 4);
-  memcpy(wh + o_isub0, img_sub0.data(), (size_t)n * 4);
-  memcpy(wh + o_insub, img_nsub.data(), (size_t)n * 4);
-  memcpy(wh + o_e0, img_e0.data(), (size_t)n * 4);
-  memcpy(wh + o_e1, img_e1.data(), (size_t)n * 4);
-  memcpy(wh + o_int0, img_int0.data(), (size_t)n * 4);
-  // the initial guess: every subsequence starts at its boundary (behind a stuffed zero if it falls on one) with the
-  // first block of an MCU; for the first subsequence of an image that is no guess
-  {
-    // (positions in the device's copy, which has no byte stuffing: nothing of the stream is looked at here)
-    uint64_t *st = (uint64_t *)(wh + o_state);
-    for (int i = 0; i < n; i++)
-      for (uint32_t k = 0; k < img_nsub[(size_t)i]; k++) st[img_sub0[(size_t)i] + k] = (uint64_t)k * sub_bytes;
-  }
-  HIP_TRY(d, hipMemcpyAsync(wd, wh, o_up_end, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(d, hipMemsetAsync(wd + o_flags, 0, o_zero_end - o_flags, d->stream));
-  w.data = scan.data;
-  w.images = images_dev;
-  w.tables = scan.tables;
-  w.sub_image = (const uint32_t *)(wd + o_simg);
-  w.sub_first = (const uint32_t *)(wd + o_sfirst);
-  w.img_sub0 = (const uint32_t *)(wd + o_isub0);
-  w.img_nsub = (const uint32_t *)(wd + o_insub);
-  w.img_e0 = (const uint32_t *)(wd + o_e0);
-  w.img_e1 = (const uint32_t *)(wd + o_e1);
-  w.img_int0 = (const uint32_t *)(wd + o_int0);
-  w.state = (uint64_t *)(wd + o_state);
-  w.stamp = (uint32_t *)(wd + o_stamp);
-  w.changed = (uint32_t *)(wd + o_flags);
-  w.walk_status = w.changed + MAX_ROUNDS + 1;
-  w.nblocks = (uint32_t *)(wd + o_nblk);
-  w.dcsum = (int32_t *)(wd + o_dcsum);
-  w.first_block = (uint32_t *)(wd + o_fblk);
-  w.first_pred = (int32_t *)(wd + o_fpred);
-  w.tile_sums = (WalkSums *)(wd + o_tiles);
-  w.tiles_per_image = tiles;
-  w.ibegin = ibegin_dev;
-  w.iskip = iskip_dev;
-  w.ipred = ipred_dev;
-  const int64_t total_blocks = (int64_t)s0.mcus_x * s0.mcus_y * B;
-  w.total_blocks = (uint32_t)total_blocks;
-  // rounds, launched back to back in bunches; between bunches the host looks at the flags: a round that changed no
-  // hand-over state means the states are the fixed point (and the counts of the lanes' last walks belong to it)
-  uint32_t *flags_host = (uint32_t *)(wh + o_up_end);
-  static const int first_bunch = getenv("MIJPEG_WALK_ROUNDS") ? std::max(1, std::min(MAX_ROUNDS, atoi(getenv("MIJPEG_WALK_ROUNDS")))) : 8;
-  int round = 0;
-  if (defer) {
-    // mijpeg_submit_batch_device: nobody looks at the flags between the rounds.  Enough rounds for the states to settle are
-    // launched in one go -- a round in which no lane is dirty costs a few microseconds (its workgroups leave before they
-    // load their tables) -- and whoever waits for the batch checks that the last one changed nothing (finish_batch).
-    const int rounds = std::min(MAX_ROUNDS, sub_bytes >= 512 ? 16 : sub_bytes >= 256 ? 24 : 40);
-    while (round < rounds) {
-      w.round = (uint32_t)++round;
-      if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
-    }
-    HIP_TRY(d, hipMemcpyAsync(flags_host, wd + o_flags, (size_t)(MAX_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, d->stream));
-    d->pend_walk_round = round;
-    d->pend_walk_flags = flags_host;
-  }
-  for (; !defer;) {
-    const int upto = round == 0 ? first_bunch : std::min(MAX_ROUNDS, round + 4);
-    while (round < upto) {
-      w.round = (uint32_t)++round;
-      if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
-    }
-    HIP_TRY(d, hipMemcpyAsync(flags_host, wd + o_flags, (size_t)(MAX_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
-    if (!flags_host[round]) break;
-    if (round == MAX_ROUNDS) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding did not settle");
-  }
-  d->walk_rounds = 1;
-  for (int r = 1; r <= round && !defer; r++)
-    if (flags_host[r]) d->walk_rounds = r + 1; // rounds that were needed: the last one that changed something, and one to see it
-  if (launch_huffman_walk_scan(w, n, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_scan_kernel launch");
-  // one interval size for the launch: the images share their geometry, hence their MCUs per virtual interval
-  int per = 0;
-  for (int i = 0; i < n; i++)
-    if (dwalk[(size_t)i]) per = dwalk[(size_t)i];
-  w.emit_every = (uint32_t)(per * B);
-  if (launch_huffman_walk(w, true, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
-  d->walk_status_dev = w.walk_status;
-  return MIJPEG_OK;
-}
-
-// What the Huffman kernel left in the status words of n images: errors, and per image the range check that selects the
-// arithmetic flavour of the reconstruction (fast_arith / range_max).
-static int evaluate_entropy_status(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const uint32_t *status_host)
-{
-  for (int i = 0; i < n; i++) {
-    const uint32_t *st = status_host + 8 * i;
-    // A DC prediction that leaves the 16-bit store (only damaged streams get there): the host decoder keeps 32-bit planes
-    if (st[0] == HUFF_ERR_OVERFLOW)
-      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "on-device entropy decoding: a DC coefficient leaves the 16 bit coefficient store (damaged stream); the host decoder keeps 32-bit coefficients for it");
-    // Damaged entropy coded data: which error the reference reports (or whether it decodes on after a resynchronisation)
-    // depends on its sequential walk; the host decoder restates that walk, the device decoder does not try to
-    if (st[0]) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the entropy coded data is damaged: the host decoder walks such streams like the reference does (DESIGN 4.0)");
-    mijpeg_info &f = hosts[i]->info;
-    f.fast_arith = 1;
-    for (int c = 0; c < f.components; c++) {
-      f.range_max[c] = (int32_t)std::min<uint32_t>(st[1 + c], 0x7fffffffu);
-      if (f.range_max[c] >= 16384) f.fast_arith = 0;
-    }
-    if (f.precision != 8) f.fast_arith = 0; // (as HostDecoder::decode has it: the fast flavour is derived for 8-bit frames; 12-bit kernels gate on range_max)
-  }
-  return MIJPEG_OK;
-}
-
-// Second-level tables of a device Huffman table: every code longer than the direct table's ten bits, grouped by its first
-// ten bits, in a 64-entry table indexed by the six bits that follow (entries as in the direct table: huff_dev_entry).  Codes
-// whose prefix finds no table left keep the direct entry HUFF_DEV_SUB | HUFF_DEV_NO_SUB: the kernels walk the canonical arrays
-// for those.
-static void fill_second_level(HuffDevTable &dst, const HuffTable &h, int ac)
-{
-  int prefix_of[HUFF_DEV_SUBTABLES], used = 0;
-  int code = 0, k = 0;
-  for (int l = 1; l <= 16; l++) {
-    for (int i = 0; i < h.counts[l - 1]; i++, code++, k++) {
-      if (l <= HUFF_DEV_LOOKAHEAD || k >= 256) continue;
-      if (code >= (1 << l)) return; // over-subscribed lengths: the host refuses such tables anyway
-      const int prefix = code >> (l - HUFF_DEV_LOOKAHEAD), rest = l - HUFF_DEV_LOOKAHEAD; // 1..6 bits behind the prefix
-      int t = 0;
-      while (t < used && prefix_of[t] != prefix) t++;
-      if (t == used) {
-        if (used == HUFF_DEV_SUBTABLES) continue;
-        prefix_of[used++] = prefix;
-        dst.fast[prefix] = (uint16_t)(HUFF_DEV_SUB | t);
-      }
-      const uint16_t e = (uint16_t)huff_dev_entry(l, h.values[k], ac);
-      const int first = (code & ((1 << rest) - 1)) << (6 - rest);
-      for (int j = 0; j < (1 << (6 - rest)); j++) dst.sub[t][first + j] = e;
-    }
-    code <<= 1;
-  }
-}
-
-// The host's decoder table in the device's form (huffman_dev.hpp): direct entries, second-level tables, the canonical arrays.
-// mode: 0 DC, 1 AC of a sequential scan, 2 AC of a progressive / refinement scan (huff_dev_entry).
-static void build_dev_table(HuffDevTable &dst, const HuffTable &src, int mode)
-{
-  memset(&dst, 0, sizeof(dst));
-  // the host's direct table ((length << 8) | symbol, 0 = a longer code or none) in the device's entry format
-  for (int x = 0; x < (1 << HUFF_DEV_LOOKAHEAD); x++) {
-    const uint16_t he = src.fast[x];
-    dst.fast[x] = he ? (uint16_t)huff_dev_entry(he >> 8, he & 0xffu, mode) : (uint16_t)(HUFF_DEV_SUB | HUFF_DEV_NO_SUB);
-  }
-  static const bool no_sub = getenv("MIJPEG_HUFF_NO_SUBTABLES") != nullptr; // A-B measurements: long codes walk the canonical arrays
-  if (!no_sub) fill_second_level(dst, src, mode);
-  memcpy(dst.maxcode, src.maxcode, sizeof(dst.maxcode));
-  memcpy(dst.valoff, src.valoff, sizeof(dst.valoff));
-  memcpy(dst.values, src.values, sizeof(dst.values));
-}
-
-// Entropy-decode n parsed images of identical frame geometry on the device, image i into coef_dev + i * frame_stride.
-// infos[i] receives fast_arith / range_max.  Returns MIJPEG_OK, MIJPEG_ERR_NOT_AVAILABLE (nothing touched) or an error.
-static int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
-                                int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part = false, bool defer = false)
-{
-  const mijpeg_info &f0 = hosts[0]->info;
-  const Scan &s0 = hosts[0]->scans[0];
-  int64_t total_intervals = 0;
-  std::vector<int64_t> nints((size_t)n);
-  std::vector<std::unique_ptr<VirtualIntervals>> virt((size_t)n); // restart points planned by the host's walk ...
-  std::vector<int> dwalk((size_t)n, 0);                           // ... or MCUs per virtual interval when the device walks
-  d->walk_rounds = 0;
-  const bool device_walk = !(getenv("MIJPEG_DEVICE_WALK") && atoi(getenv("MIJPEG_DEVICE_WALK")) == 0);
-  const auto tb0 = std::chrono::steady_clock::now();
-  for (int i = 0; i < n; i++) {
-    const char *why = device_entropy_obstacle(*hosts[i], sizes[i], xt_part);
-    if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
-    const mijpeg_info &f = hosts[i]->info;
-    const Scan &s = hosts[i]->scans[0];
-    if (f.width != f0.width || f.height != f0.height || f.components != f0.components || memcmp(f.hsamp, f0.hsamp, sizeof(f.hsamp)) ||
-        memcmp(f.vsamp, f0.vsamp, sizeof(f.vsamp)))
-      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share width, height and sampling factors");
-    // ... and what the one reconstruction launch applies to all of them: the colour transformation (an Adobe marker may
-    // switch it off per image), the sample precision, being a JPEG XT stream or not
-    if (f.ycbcr != f0.ycbcr || f.precision != f0.precision || f.xt != f0.xt)
-      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share colour transformation and precision");
-    for (int k = 0; k < s.ncomp; k++)
-      if (s.sc[k].comp != s0.sc[k].comp) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share the component order of their scan");
-    const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
-    int64_t nint;
-    if (s.restart_interval > 0) {
-      nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
-      if (nint > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many restart intervals");
-      if ((int64_t)s.interval_begin.size() < nint)
-        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)");
-      const std::vector<uint8_t> &rst = hosts[i]->restart_codes(0);
-      for (int64_t k = 0; k + 1 < nint; k++)
-        if (rst[(size_t)k] != 0xd0 + (k & 7))
-          return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart markers out of sequence: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)");
-    } else {
-      // no restart markers: the host's self-synchronising walk finds exact restart points ("virtual intervals"),
-      // about 16 K of them, and the device decodes from there
-      const int per = (int)std::min<int64_t>(64, std::max<int64_t>(1, total_mcus / 16384));
-      if (total_mcus < 256 || s.ecs_end - s.ecs_begin < 4096)
-        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream without restart markers is too small for speculative decoding");
-      if (device_walk) { // the restart points are found on the device (huffman_walk_kernel); their number is known already
-        dwalk[(size_t)i] = per;
-        nint = (total_mcus + per - 1) / per;
-      } else {
-        virt[(size_t)i].reset(new VirtualIntervals());
-        if (hosts[i]->plan_virtual_intervals(0, per, 0, *virt[(size_t)i]))
-          return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream without restart markers did not lend itself to speculative decoding");
-        nint = (int64_t)virt[(size_t)i]->byte_off.size();
-      }
-    }
-    nints[(size_t)i] = nint;
-    total_intervals += nint;
-  }
-  if (min_intervals <= 0) min_intervals = 2048; // below this the device runs mostly idle
-  if (total_intervals < min_intervals || total_intervals > 0x7fffffff)
-    return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too few restart intervals to occupy the device");
-
-  HuffScanArgs a;
-  memset(&a, 0, sizeof(a));
-  // decoding lanes per wave: about a thousand waves (one per SIMD) are what a small launch wants -- fewer lanes per wave
-  // mean more waves that each issue the same instructions for less, fuller waves mean longer steps (the slowest lane's
-  // block).  Measured with the bit-addressed reader and four-wave workgroups on one 8K 4:2:0 frame with 16200 intervals
-  // (tools/gpu_huff_lanes.sh): 1 lane 0.81 ms, 2: 0.52, 4: 0.33, 8: 0.26, 16: 0.26, 32: 0.27.
-  a.lanes = 64;
-  while (a.lanes > 1 && total_intervals / a.lanes < 768) a.lanes >>= 1;
-  if (const char *e = getenv("MIJPEG_HUFF_LANES")) { // tuning
-    const int l = atoi(e);
-    if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) a.lanes = l;
-  }
-  // one wave per SIMD and workgroup: with two-wave workgroups (which round 1 chose for the LDS they leave to others) the same
-  // eight waves per CU decode 37 % slower (0.60 against 0.38 ms per 32 4K frames; 3, 5, 6 waves: 0.55, 0.58, 0.48) -- the
-  // waves of a workgroup go to the SIMDs in cyclic order, and only a multiple of four loads them evenly
-  a.waves_per_group = 4;
-  if (const char *e = getenv("MIJPEG_HUFF_WAVES")) a.waves_per_group = std::max(1, std::min(8, atoi(e))); // tuning
-  const int per_group = a.lanes * a.waves_per_group; // intervals of one workgroup
-  // Tables in LDS: components that bring the same Huffman code (Cb and Cr practically always do) share one copy -- the
-  // workgroup's LDS footprint decides how many of them a CU holds.  The sharing pattern is that of image 0 and must hold
-  // for every image of the launch; the device walk indexes its tables by component and keeps one per component.
-  int tab_slot[MIJPEG_MAX_COMPONENTS][2];
-  int ntab = 0;
-  {
-    bool walk_any = false;
-    for (int i = 0; i < n; i++) walk_any |= dwalk[(size_t)i] > 0;
-    bool share = !walk_any && !getenv("MIJPEG_HUFF_NO_TABLE_SHARING");
-    for (int pass = 0; pass < 2; pass++) {
-      ntab = 0;
-      for (int k = 0; k < s0.ncomp; k++)
-        for (int t = 0; t < 2; t++) {
-          tab_slot[k][t] = -1;
-          for (int j = 0; j < k && share && tab_slot[k][t] < 0; j++)
-            if ((t ? s0.ac[k].same_code(s0.ac[j]) : s0.dc[k].same_code(s0.dc[j]))) tab_slot[k][t] = tab_slot[j][t];
-          if (tab_slot[k][t] < 0) tab_slot[k][t] = ntab++;
-        }
-      if (!share) break;
-      bool holds = true; // ... in every image?
-      for (int i = 1; i < n && holds; i++) {
-        const Scan &s = hosts[i]->scans[0];
-        for (int k = 0; k < s.ncomp && holds; k++)
-          for (int j = 0; j < k && holds; j++) {
-            if (tab_slot[k][0] == tab_slot[j][0] && !s.dc[k].same_code(s.dc[j])) holds = false;
-            if (tab_slot[k][1] == tab_slot[j][1] && !s.ac[k].same_code(s.ac[j])) holds = false;
-          }
-      }
-      if (holds) break;
-      share = false;
-    }
-  }
-  const size_t table_blob = (size_t)ntab * sizeof(HuffDevTable) + sizeof(HuffDevAux);
-
-  // device buffer: [streams, each padded][ibegin][iend][tables of every image][images][groups][status]
-  // What travels to the device is the entropy coded data of every image WITHOUT its byte stuffing and without the markers,
-  // one restart interval behind the other (HostDecoder::unstuff_piece; the marker search counted what leaves): the kernels
-  // address it by plain bit positions (huffman.hip, DevBits).
-  std::vector<size_t> usize((size_t)n);
-  std::vector<size_t> stream_off;
-  size_t off = stream_slots(sizes, n, stream_off);
-  int64_t n_groups = 0;
-  for (int i = 0; i < n; i++) {
-    usize[(size_t)i] = hosts[i]->scans[0].unstuffed_size;
-    if (usize[(size_t)i] >= ((size_t)1 << 28)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "entropy coded segment too large for the device decoder's bit addresses");
-    if (usize[(size_t)i] > sizes[i]) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "entropy coded segment larger than its stream");
-    if (!dwalk[(size_t)i] && !virt[(size_t)i] && (int64_t)hosts[i]->scans[0].interval_ubegin.size() < nints[(size_t)i])
-      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart intervals missing");
-    n_groups += (nints[(size_t)i] + per_group - 1) / per_group;
-  }
-  if (off > 0xfffffff0ull || n_groups > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "batch too large for one launch");
-  const size_t stream_bytes = off;
-  auto align16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  bool any_virtual = false, any_dwalk = false;
-  for (int i = 0; i < n; i++) {
-    any_virtual |= virt[(size_t)i] != nullptr || dwalk[(size_t)i] > 0;
-    any_dwalk |= dwalk[(size_t)i] > 0;
-  }
-  const size_t off_ib = stream_bytes, off_ie = off_ib + (size_t)total_intervals * 4;
-  const size_t off_isk = off_ie + (size_t)total_intervals * 4, off_ipr = align16(off_isk + (any_virtual ? (size_t)total_intervals : 0));
-  const size_t off_tab = align16(off_ipr + (any_virtual ? (size_t)total_intervals * 8 : 0));
-  const size_t off_img = align16(off_tab + (size_t)n * table_blob), off_grp = align16(off_img + (size_t)n * sizeof(HuffImage));
-  const size_t off_status = align16(off_grp + (size_t)n_groups * sizeof(HuffGroup)), status_bytes = (size_t)n * 32, total = off_status + status_bytes;
-  int rc = ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, total);
-  if (rc) return rc;
-  const size_t host_part = off_status - stream_bytes; // everything between the streams and the status words goes through pinned staging
-  if (d->ent_host_cap < host_part + status_bytes) {
-    if (d->ent_host) (void)hipHostFree(d->ent_host);
-    d->ent_host = nullptr;
-    d->ent_host_cap = 0;
-    HIP_TRY(d, hipHostMalloc((void **)&d->ent_host, host_part + status_bytes, hipHostMallocDefault));
-    d->ent_host_cap = host_part + status_bytes;
-  }
-  uint8_t *hp = d->ent_host - stream_bytes; // hp + device offset = staging address
-  uint32_t *ib = (uint32_t *)(hp + off_ib), *ie = (uint32_t *)(hp + off_ie);
-  HuffImage *images = (HuffImage *)(hp + off_img);
-  HuffGroup *groups = (HuffGroup *)(hp + off_grp);
-  int64_t first = 0, g = 0;
-  bool needs_clear = false;
-  for (int i = 0; i < n; i++) {
-    const mijpeg_info &f = hosts[i]->info;
-    const Scan &s = hosts[i]->scans[0];
-    const int64_t nint = nints[(size_t)i];
-    if (dwalk[(size_t)i]) { // filled in by the EMIT walk on the device
-      for (int64_t k = 0; k < nint; k++) { ib[first + k] = 0; ie[first + k] = (uint32_t)usize[(size_t)i]; }
-      memset(hp + off_isk + first, 0, (size_t)nint);
-      memset(hp + off_ipr + (size_t)first * 8, 0, (size_t)nint * 8);
-    } else if (virt[(size_t)i]) {
-      // the host's walk reports stream offsets: into the copy's (stuffed pairs in front of each, counted as the offsets go up)
-      const VirtualIntervals &vi = *virt[(size_t)i];
-      uint8_t *isk = hp + off_isk;
-      int16_t *ipr = (int16_t *)(hp + off_ipr);
-      const uint8_t *base = s.base ? s.base : datas[i];
-      size_t at = s.ecs_begin, pairs = 0;
-      for (int64_t k = 0; k < nint; k++) {
-        const size_t pos = vi.byte_off[(size_t)k];
-        while (at < pos) {
-          const uint8_t *q = (const uint8_t *)memchr(base + at, 0xff, pos - at);
-          if (!q) break;
-          at = (size_t)(q - base);
-          if (base[at + 1] == 0x00) { pairs++; at += 2; }
-          else at++;
-        }
-        at = std::max(at, pos);
-        ib[first + k] = (uint32_t)(pos - s.ecs_begin - pairs);
-        ie[first + k] = (uint32_t)usize[(size_t)i];
-        isk[first + k] = vi.bit_skip[(size_t)k];
-        memcpy(ipr + (first + k) * 4, &vi.pred[(size_t)k * 4], 8);
-      }
-    } else {
-      memcpy(ib + first, s.interval_ubegin.data(), (size_t)nint * 4);
-      memcpy(ie + first, s.interval_uend.data(), (size_t)nint * 4);
-      if (any_virtual) memset(hp + off_isk + first, 0, (size_t)nint);
-    }
-    HuffDevTable *tabs = (HuffDevTable *)(hp + off_tab + (size_t)i * table_blob);
-    HuffDevAux *aux = (HuffDevAux *)(tabs + ntab);
-    // images that bring the tables of the image in front of them (every frame of a camera or an encoder run does) share its
-    // blob: nothing to build, and the workgroups of both read the same lines
-    bool same_tables = i > 0;
-    if (same_tables) {
-      const mijpeg_info &fp = hosts[i - 1]->info;
-      const Scan &sp = hosts[i - 1]->scans[0];
-      for (int k = 0; k < s.ncomp && same_tables; k++) {
-        const int c = s.sc[k].comp;
-        same_tables = s.dc[k].same_code(sp.dc[k]) && s.ac[k].same_code(sp.ac[k]) &&
-                      !memcmp(f.quant[f.quant_index[c]], fp.quant[fp.quant_index[c]], sizeof(f.quant[0]));
-      }
-    }
-    memset(aux, 0, sizeof(*aux));
-    for (int k = 0; k < s.ncomp && !same_tables; k++) {
-      const HuffTable *src[2] = {&s.dc[k], &s.ac[k]};
-      for (int t = 0; t < 2; t++) {
-        build_dev_table(tabs[tab_slot[k][t]], *src[t], t);
-      }
-      const int c = s.sc[k].comp;
-      const uint16_t *delta = f.quant[f.quant_index[c]];
-      for (int z = 0; z < 80; z++) {
-        const uint32_t pos = scan_order()[z];
-        aux->zq[k][z] = ((uint32_t)delta[pos] << 16) | (pos * 2);
-      }
-    }
-    HuffImage &im = images[i];
-    im.stream_off = (uint32_t)stream_off[(size_t)i];
-    im.first_interval = (uint32_t)first;
-    im.n_intervals = (int32_t)nint;
-    im.restart_interval = dwalk[(size_t)i] ? dwalk[(size_t)i] : virt[(size_t)i] ? virt[(size_t)i]->mcus_per_interval : s.restart_interval;
-    im.virt = (virt[(size_t)i] || dwalk[(size_t)i]) ? 1u : 0u;
-    im.reserved = 0;
-    im.total_mcus = s.mcus_x * s.mcus_y;
-    im.mcus_x = s.mcus_x;
-    im.coef_base = (int64_t)i * frame_stride;
-    im.table_off = same_tables ? images[i - 1].table_off : (uint32_t)((size_t)i * table_blob);
-    im.status_off = (uint32_t)(i * 8);
-    for (int64_t k = 0; k < nint; k += per_group) {
-      groups[g].image = (uint32_t)i;
-      groups[g].first_interval = (uint32_t)k;
-      g++;
-    }
-    first += nint;
-    // an interleaved scan writes every block of every plane; a single-component scan of a frame whose only component
-    // has sampling factors > 1 leaves the MCU padding blocks untouched (they must read as zero)
-    if (s.ncomp == 1 && (s.mcus_x != f.blocks_w[s.sc[0].comp] || s.mcus_y != f.blocks_h[s.sc[0].comp])) needs_clear = true;
-  }
-  for (int k = 0; k < s0.ncomp; k++) {
-    const int c = s0.sc[k].comp;
-    a.comp_of[k] = c;
-    a.hs[k] = s0.ncomp > 1 ? f0.hsamp[c] : 1;
-    a.vs[k] = s0.ncomp > 1 ? f0.vsamp[c] : 1;
-    a.bw[k] = f0.blocks_w[c];
-    a.coef_off[k] = f0.coef_offset[c];
-    a.dc_tab[k] = tab_slot[k][0];
-    a.ac_tab[k] = tab_slot[k][1];
-  }
-  a.data = d->ent_dev;
-  a.ibegin = (const uint32_t *)(d->ent_dev + off_ib);
-  a.iend = (const uint32_t *)(d->ent_dev + off_ie);
-  a.iskip = d->ent_dev + off_isk;
-  a.ipred = (const int16_t *)(d->ent_dev + off_ipr);
-  a.images = (const HuffImage *)(d->ent_dev + off_img);
-  a.groups = (const HuffGroup *)(d->ent_dev + off_grp);
-  a.n_groups = (int32_t)n_groups;
-  a.ncomp = s0.ncomp;
-  a.ntables = ntab;
-  a.tables = d->ent_dev + off_tab;
-  a.coef = coef_dev;
-  a.status = (uint32_t *)(d->ent_dev + off_status);
-  const auto tb1 = std::chrono::steady_clock::now();
-  static const bool trace_phases = getenv("MIJPEG_TRACE_SUBMIT") != nullptr; // diagnostics: host time of the steps below, on stderr
-  auto mark = [&](const char *what) {
-    if (trace_phases) fprintf(stderr, "[mijpeg] %-28s %8.3f ms\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count() * 1e3);
-  };
-  HIP_TRY(d, hipMemcpyAsync(d->ent_dev + stream_bytes, d->ent_host, host_part, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(d, hipMemsetAsync(d->ent_dev + off_status, 0, status_bytes, d->stream));
-  if (needs_clear) HIP_TRY(d, hipMemsetAsync(coef_dev, 0, (size_t)n * (size_t)frame_stride * sizeof(int16_t), d->stream));
-  const int repeat = getenv("MIJPEG_HUFF_REPEAT") ? atoi(getenv("MIJPEG_HUFF_REPEAT")) : 1; // experiments: steady-state kernel time
-  // (a deferred batch always goes through the pinned gathering area: the caller's bytes are only read during the call)
-  const bool small = !defer && (n == 1 || stream_bytes < ((size_t)8 << 20));
-  {
-    const int src = ensure_stage(d, stream_bytes);
-    if (src) return src;
-  }
-  // the unstuffing gather of images [g0, g1) into the pinned area, spread over the pool: pieces of ~256 KiB of source
-  // (images whose marker search wrote the copy already -- a batch's workers do, set_unstuff_sink -- have nothing left to do)
-  auto gather = [&](int g0, int g1) {
-    struct Job { int image; HostDecoder::UnstuffPiece piece; };
-    std::vector<Job> jobs;
-    std::vector<HostDecoder::UnstuffPiece> ps;
-    for (int i = g0; i < g1; i++) {
-      if (hosts[i]->scans[0].unstuffed_at == d->stage_host + stream_off[(size_t)i]) continue;
-      ps.clear();
-      hosts[i]->unstuff_pieces(0, (size_t)256 << 10, ps);
-      for (const auto &p : ps) jobs.push_back(Job{i, p});
-    }
-    // (the sweep runs at about half of memcpy's rate: twice the workers the plain copy had)
-    if (jobs.empty()) return;
-    const int workers = std::max(1, std::min<int>((int)jobs.size(), std::min(default_threads(), 32)));
-    parallel_for(workers, [&](int w) {
-      for (size_t k = (size_t)w; k < jobs.size(); k += (size_t)workers) {
-        const int i = jobs[k].image;
-        hosts[i]->unstuff_piece(0, jobs[k].piece, d->stage_host + stream_off[(size_t)i]);
-      }
-    });
-  };
-  if (small) {
-    gather(0, n);
-    // (only what the copies occupy: a slot is as large as its stream, headers and all)
-    for (int i = 0; i < n; i++)
-      HIP_TRY(d, hipMemcpyAsync(d->ent_dev + stream_off[(size_t)i], d->stage_host + stream_off[(size_t)i], ((usize[(size_t)i] + 15) & ~(size_t)15) + HUFF_STREAM_PAD,
-                                hipMemcpyHostToDevice, d->stream));
-    if (any_dwalk) {
-      const int wrc = device_walk_images(d, hosts, n, dwalk, a, (const HuffImage *)(d->ent_dev + off_img), (uint32_t *)(d->ent_dev + off_ib),
-                                         d->ent_dev + off_isk, (int16_t *)(d->ent_dev + off_ipr), images, usize, defer);
-      if (wrc) return wrc;
-    }
-    for (int r = 0; r < std::max(1, repeat); r++)
-      if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
-  } else {
-    // large batches, in up to eight groups of images: the pool threads gather a group's streams into pinned memory, its
-    // DMA runs on a copy stream while the next group is gathered and while the kernel decodes the previous one
-    mark("staging buffer ready");
-    if (!d->copy_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
-    // Images per upload + launch.  A launch is latency-bound (the serial symbol chain of its longest restart interval,
-    // ~0.3 ms) until it holds several waves per SIMD: ~128 K restart intervals; more, smaller launches only pay when the
-    // batch is so large that the upload of one part hides behind the decode of another (profiles/r02/batch4k_*.txt:
-    // 32 x 4K frames in one launch 0.80 ms, in eight launches of four 8 x 0.39 ms).
-    const int64_t per_image = std::max<int64_t>(1, total_intervals / n);
-    int groups_of = (int)std::max<int64_t>(std::max(4, (n + 7) / 8), (131072 + per_image - 1) / per_image);
-    if (const char *e = getenv("MIJPEG_BATCH_GROUP")) groups_of = std::max(1, atoi(e)); // tuning
-    const int ngroups = (n + groups_of - 1) / groups_of;
-    while ((int)d->copy_events.size() < ngroups) {
-      hipEvent_t e;
-      HIP_TRY(d, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      d->copy_events.push_back(e);
-    }
-    // the copy stream must not overtake work that still reads the buffer from an earlier call: the Huffman kernels and the
-    // status copy of the previous batch (ent_free, recorded behind them).  NOT everything on d->stream: the reconstruction
-    // kernel of the previous batch does not touch this buffer, and an upload that waits for it leaves the link idle for the
-    // length of that kernel in every round of a pipeline (profiles/r03/batch4k_timeline.txt)
-    if (d->ent_free_valid) HIP_TRY(d, hipStreamWaitEvent(d->copy_stream, d->ent_free, 0));
-    int64_t wg0 = 0;
-    for (int gi = 0, g0 = 0; g0 < n; g0 += groups_of, gi++) {
-      const int g1 = std::min(n, g0 + groups_of);
-      gather(g0, g1);
-      const size_t b0 = stream_off[(size_t)g0], b1 = g1 < n ? stream_off[(size_t)g1] : stream_bytes;
-      HIP_TRY(d, hipMemcpyAsync(d->ent_dev + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
-      HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)gi], d->copy_stream));
-      HIP_TRY(d, hipStreamWaitEvent(d->stream, d->copy_events[(size_t)gi], 0));
-      if (any_dwalk) continue; // the walk below covers all images at once
-      int64_t wg1 = wg0;
-      for (int i = g0; i < g1; i++) wg1 += (nints[(size_t)i] + per_group - 1) / per_group;
-      HuffScanArgs part = a; // the workgroups of this group's images
-      part.groups = a.groups + wg0;
-      part.n_groups = (int32_t)(wg1 - wg0);
-      for (int r = 0; r < std::max(1, repeat); r++)
-        if (launch_huffman_scan(part, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
-      wg0 = wg1;
-    }
-    mark("groups gathered + enqueued");
-    if (any_dwalk) {
-      const int wrc = device_walk_images(d, hosts, n, dwalk, a, (const HuffImage *)(d->ent_dev + off_img), (uint32_t *)(d->ent_dev + off_ib),
-                                         d->ent_dev + off_isk, (int16_t *)(d->ent_dev + off_ipr), images, usize, defer);
-      if (wrc) return wrc;
-      mark("device walk enqueued");
-      for (int r = 0; r < std::max(1, repeat); r++)
-        if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
-    }
-  }
-  uint32_t *status_host = (uint32_t *)(d->ent_host + host_part);
-  HIP_TRY(d, hipMemcpyAsync(status_host, d->ent_dev + off_status, status_bytes, hipMemcpyDeviceToHost, d->stream));
-  uint32_t *walk_status_host = (uint32_t *)d->walk_host; // the walk's staging buffer is free again
-  if (any_dwalk) HIP_TRY(d, hipMemcpyAsync(walk_status_host, d->walk_status_dev, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
-  if (!d->ent_free) HIP_TRY(d, hipEventCreateWithFlags(&d->ent_free, hipEventDisableTiming));
-  HIP_TRY(d, hipEventRecord(d->ent_free, d->stream)); // from here on nothing enqueued so far reads the entropy buffers
-  d->ent_free_valid = true;
-  d->phase_prepare = std::chrono::duration<double>(tb1 - tb0).count(); // interval tables, Huffman tables
-  mark("status copies enqueued");
-  if (!any_dwalk) d->pend_walk_round = 0;
-  if (defer) { // mijpeg_submit_batch_device: the caller waits later (finish_batch)
-    d->pend_n = n;
-    d->pend_status = status_host;
-    d->pend_walk_status = any_dwalk ? walk_status_host : nullptr;
-    d->pend_t0 = tb1;
-    d->phase_device = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count(); // so far: gathering + enqueueing
-    return MIJPEG_OK;
-  }
-  HIP_TRY(d, hipStreamSynchronize(d->stream));
-  if (any_dwalk)
-    for (int i = 0; i < n; i++) {
-      if (walk_status_host[i] & 2)
-        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "on-device entropy decoding: a DC coefficient leaves the 16 bit coefficient store (damaged stream); the host decoder keeps 32-bit coefficients for it");
-      if (walk_status_host[i]) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding settled on something that is not a decode of the image");
-    }
-  d->phase_device = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count();  // upload + kernel + status
-  return evaluate_entropy_status(d, hosts, n, status_host);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Progressive frames and frames with hidden refinement scans on the device (huffman_prog_kernel)
-// ------------------------------------------------------------------------------------------------
-// One frame of a file: its decoder, the element type of its planes, where they start in the object's coefficient store.
-struct MultiScanFrame {
-  HostDecoder *h;
-  bool wide;        // int32 coefficients (JPEG XT residual frames with hidden bits)
-  int64_t base16;   // offset of the frame's planes in coef_dev, in int16 units
-};
-
-// nullptr: every scan of the frame can be decoded one restart interval per lane.
-static const char *multiscan_obstacle(const HostDecoder &h, bool xt_part, bool residual_frame)
-{
-  const mijpeg_info &f = h.info;
-  if (h.needs_sequential())
-    return "on-device entropy decoding: the stream is damaged; the host decoder walks it with the reference's resynchronisation (entropyparser.cpp:117-201)";
-  if (f.xt && !xt_part) return "on-device entropy decoding: not for this JPEG XT stream";
-  if (!h.residual_merged()) return "on-device entropy decoding: the legacy codestream has no EOI marker (the host decoder decides what is merged)";
-  if (h.verdict_pending()) return "on-device entropy decoding: the file's verdict is the host decoder's (residual codestream header / tables looked up at the first request)";
-  if (f.dnl) return "on-device entropy decoding: frames whose height arrives in a DNL marker are decoded on the host";
-  // (12-bit frames: the same int16 store as the host decoder's, a coefficient beyond it sends the frame there like everywhere)
-  if (f.precision < 8 || f.precision > 12 || (xt_part && !residual_frame && f.precision != 8))
-    return "on-device entropy decoding: frames of 8 to 12 bits (JPEG XT: an 8-bit legacy frame)";
-  if (h.scans.empty() || h.scans.size() > 4096) return "on-device entropy decoding: no scans, or more than the device path plans for";
-  if (!h.every_component_seen()) return "on-device entropy decoding: a component appears in no scan (the host decoder supplies its stand-in)";
-  for (int c = 0; c < f.components; c++)
-    if (f.hsamp[c] > 4 || f.vsamp[c] > 4) return "on-device entropy decoding: MCUs of more than 4 x 4 blocks of a component are decoded on the host";
-  for (size_t si = 0; si < h.scans.size(); si++) {
-    const Scan &s = h.scans[si];
-    if (s.residual) return "on-device entropy decoding: the residual scan types of part 8 are decoded on the host";
-    if (s.ncomp < 1 || (s.se > 0 && s.ss > 0 && s.ncomp != 1)) return "on-device entropy decoding: scan layout";
-    if (s.ah > 0 && !s.refinement) return "on-device entropy decoding: scan layout";
-    if (s.unstuffed_size >= ((size_t)1 << 28)) return "on-device entropy decoding: entropy coded segment too large for the device decoder's bit addresses";
-    const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
-    if (total_mcus < 1 || total_mcus > 0x7fffffff) return "on-device entropy decoding: scan layout";
-    if (s.restart_interval > 0) {
-      const int64_t nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
-      if ((int64_t)s.interval_begin.size() < nint || (int64_t)s.interval_ubegin.size() < nint)
-        return "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
-      const std::vector<uint8_t> &rst = h.restart_codes(si);
-      if ((int64_t)rst.size() + 1 < nint) return "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
-      for (int64_t k = 0; k + 1 < nint; k++)
-        if (rst[(size_t)k] != 0xd0 + (k & 7))
-          return "restart markers out of sequence: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
-    } else {
-      // One interval: one lane decodes the whole scan.  First passes could be cut into pieces that fall into step with the real
-      // decoder; an AC refinement scan cannot -- the bits a block takes depend on which block it is -- so scans
-      // without restart markers are left to the host's pipeline of scans unless they are small
-      if (s.interval_ubegin.empty()) return "on-device entropy decoding: scan without data";
-      if (s.unstuffed_size > ((size_t)24 << 10))
-        return "on-device entropy decoding: progressive / refinement scans without restart markers are serial by construction (refinementscan.cpp:584-700): host";
-    }
-    for (int k = 0; k < s.ncomp; k++) {
-      if (s.ss == 0 && s.ah == 0 && !s.dc[k].built) return "on-device entropy decoding: a Huffman table the scan names does not exist";
-      if (s.se > 0 && !s.ac[k].built) return "on-device entropy decoding: a Huffman table the scan names does not exist";
-    }
-  }
-  return nullptr;
-}
-
-// All scans of the given frames (one file: a progressive picture, or the two frames of a JPEG XT file): upload of the entropy
-// coded data without its stuffing, planes cleared, the scans launched level by level (scans that share a component one after
-// the other, the rest side by side), range pass.  MIJPEG_ERR_NOT_AVAILABLE: the host decoder's.
-static int device_entropy_multiscan(mijpeg_decoder *d, const MultiScanFrame *frames, int nframes, int min_intervals)
-{
-  struct Item { int frame; size_t scan; int level; int64_t nint; size_t stream_off; size_t table_off; int ntab; int dc_tab[4], ac_tab[4]; int64_t first; };
-  std::vector<Item> items;
-  const auto tm0 = std::chrono::steady_clock::now();
-  static const bool trace_phases = getenv("MIJPEG_TRACE_SUBMIT") != nullptr; // diagnostics: host time of the steps below, on stderr
-  auto mark = [&](const char *what) {
-    if (trace_phases) fprintf(stderr, "[mijpeg multiscan] %-28s %8.3f ms\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count() * 1e3);
-  };
-  auto align16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
-  size_t stream_bytes = 0, table_bytes = 0;
-  int64_t total_intervals = 0;
-  int max_tables = 1;
-  std::vector<int> frame_levels((size_t)nframes, 0);
-  for (int fi = 0; fi < nframes; fi++) {
-    const HostDecoder &h = *frames[fi].h;
-    std::vector<int> level(h.scans.size(), 0);
-    for (size_t j = 0; j < h.scans.size(); j++) {
-      const Scan &b = h.scans[j];
-      // (a scan of the AC kind writes whole blocks back: two scans that share a component never run side by side)
-      for (size_t i = 0; i < j; i++) {
-        const Scan &a = h.scans[i];
-        bool common = false;
-        for (int ka = 0; ka < a.ncomp; ka++)
-          for (int kb = 0; kb < b.ncomp; kb++) common |= a.sc[ka].comp == b.sc[kb].comp;
-        if (common) level[j] = std::max(level[j], level[i] + 1);
-      }
-      Item it;
-      memset(&it, 0, sizeof(it));
-      it.frame = fi;
-      it.scan = j;
-      it.level = level[j];
-      const int64_t total_mcus = (int64_t)b.mcus_x * b.mcus_y;
-      it.nint = b.restart_interval > 0 ? (total_mcus + b.restart_interval - 1) / b.restart_interval : 1;
-      it.table_off = table_bytes;
-      for (int k = 0; k < b.ncomp; k++) {
-        it.dc_tab[k] = it.ac_tab[k] = 0;
-        if (b.ss == 0 && b.ah == 0) it.dc_tab[k] = it.ntab++;
-        if (b.se > 0) it.ac_tab[k] = it.ntab++;
-      }
-      table_bytes += (size_t)it.ntab * sizeof(HuffDevTable);
-      max_tables = std::max(max_tables, it.ntab);
-      it.first = total_intervals;
-      total_intervals += it.nint;
-      frame_levels[(size_t)fi] = std::max(frame_levels[(size_t)fi], level[j] + 1);
-      items.push_back(it);
-    }
-  }
-  // The entropy coded data lies in the upload level by level: what the first launches read goes up first, and the rest is
-  // gathered and uploaded while they run (level_end[l]: end of level l's bytes).
-  int n_levels = 0;
-  for (int fi = 0; fi < nframes; fi++) n_levels = std::max(n_levels, frame_levels[(size_t)fi]);
-  std::vector<size_t> level_end((size_t)n_levels, 0);
-  for (int lv = 0; lv < n_levels; lv++) {
-    for (Item &it : items)
-      if (it.level == lv) {
-        it.stream_off = stream_bytes;
-        stream_bytes += align16(frames[it.frame].h->scans[it.scan].unstuffed_size) + HUFF_STREAM_PAD;
-      }
-    level_end[(size_t)lv] = stream_bytes;
-  }
-  if (stream_bytes > 0xfffffff0ull || total_intervals > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "file too large for one device decode");
-  // the largest launch decides whether the device is worth the trip ("auto"); every launch -- the scans of one level of one
-  // frame -- picks how many lanes of a wave decode by its own number of intervals: fewer lanes = more waves, less divergence
-  int lanes_env = 0;
-  if (const char *e = getenv("MIJPEG_HUFF_LANES")) { // tuning
-    const int l = atoi(e);
-    if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) lanes_env = l;
-  }
-  const int waves = 4;
-  int64_t widest = 0, n_groups = 0;
-  std::vector<std::vector<int>> level_lanes((size_t)nframes);
-  for (int fi = 0; fi < nframes; fi++)
-    for (int lv = 0; lv < frame_levels[(size_t)fi]; lv++) {
-      int64_t n = 0;
-      for (const Item &it : items)
-        if (it.frame == fi && it.level == lv) n += it.nint;
-      widest = std::max(widest, n);
-      int lanes = 64;
-      while (lanes > 1 && n / lanes < 768) lanes >>= 1;
-      if (lanes_env) lanes = lanes_env;
-      level_lanes[(size_t)fi].push_back(lanes);
-      for (const Item &it : items)
-        if (it.frame == fi && it.level == lv) n_groups += (it.nint + lanes * waves - 1) / (lanes * waves);
-    }
-  if (min_intervals <= 0) min_intervals = 2048;
-  if (widest < min_intervals) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too few restart intervals to occupy the device");
-  // device buffer: [streams][ibegin][iend][tables][scans][groups][status: 8 dwords per frame]
-  const size_t off_ib = stream_bytes, off_ie = off_ib + (size_t)total_intervals * 4, off_tab = align16(off_ie + (size_t)total_intervals * 4);
-  const size_t off_scan = align16(off_tab + table_bytes), off_grp = align16(off_scan + items.size() * sizeof(ProgScanDev));
-  const size_t off_status = align16(off_grp + (size_t)n_groups * sizeof(ProgGroup)), status_bytes = (size_t)nframes * 32, total = off_status + status_bytes;
-  int rc = ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, total);
-  if (rc) return rc;
-  const size_t host_part = off_status - stream_bytes;
-  if (d->ent_host_cap < host_part + status_bytes) {
-    if (d->ent_host) (void)hipHostFree(d->ent_host);
-    d->ent_host = nullptr;
-    d->ent_host_cap = 0;
-    HIP_TRY(d, hipHostMalloc((void **)&d->ent_host, host_part + status_bytes, hipHostMallocDefault));
-    d->ent_host_cap = host_part + status_bytes;
-  }
-  rc = ensure_stage(d, stream_bytes);
-  if (rc) return rc;
-  uint8_t *hp = d->ent_host - stream_bytes; // hp + device offset = staging address
-  uint32_t *ib = (uint32_t *)(hp + off_ib), *ie = (uint32_t *)(hp + off_ie);
-  ProgScanDev *sd = (ProgScanDev *)(hp + off_scan);
-  ProgGroup *groups = (ProgGroup *)(hp + off_grp);
-  // groups in launch order: frame, level, scan
-  std::vector<std::pair<int64_t, int64_t>> launches; // [first group, groups) of every (frame, level)
-  std::vector<int> launch_frame, launch_level;
-  int64_t g = 0;
-  for (int fi = 0; fi < nframes; fi++)
-    for (int lv = 0; lv < frame_levels[(size_t)fi]; lv++) {
-      const int64_t g0 = g;
-      const int per_group = level_lanes[(size_t)fi][(size_t)lv] * waves;
-      for (size_t ii = 0; ii < items.size(); ii++) {
-        const Item &it = items[ii];
-        if (it.frame != fi || it.level != lv) continue;
-        for (int64_t k = 0; k < it.nint; k += per_group) {
-          groups[g].scan = (uint32_t)ii;
-          groups[g].first_interval = (uint32_t)k;
-          g++;
-        }
-      }
-      if (g > g0) { launches.push_back(std::make_pair(g0, g - g0)); launch_frame.push_back(fi); launch_level.push_back(lv); }
-    }
-  for (size_t ii = 0; ii < items.size(); ii++) {
-    const Item &it = items[ii];
-    const HostDecoder &h = *frames[it.frame].h;
-    const mijpeg_info &f = h.info;
-    const Scan &s = h.scans[it.scan];
-    ProgScanDev &o = sd[ii];
-    memset(&o, 0, sizeof(o));
-    o.stream_off = (uint32_t)it.stream_off;
-    o.first_interval = (uint32_t)it.first;
-    o.n_intervals = (int32_t)it.nint;
-    o.total_mcus = s.mcus_x * s.mcus_y;
-    o.restart_interval = s.restart_interval > 0 ? s.restart_interval : o.total_mcus;
-    o.mcus_x = s.mcus_x;
-    o.ncomp = s.ncomp;
-    o.ntables = it.ntab;
-    o.table_off = (uint32_t)it.table_off;
-    o.ss = s.ss; o.se = s.se; o.ah = s.ah; o.al = s.al;
-    o.runs_legal = s.progressive_run ? 1 : 0;
-    HuffDevTable *tabs = (HuffDevTable *)(hp + off_tab + it.table_off);
-    for (int k = 0; k < s.ncomp; k++) {
-      const int c = s.sc[k].comp;
-      o.comp[k] = c;
-      o.hs[k] = s.ncomp > 1 ? f.hsamp[c] : 1;
-      o.vs[k] = s.ncomp > 1 ? f.vsamp[c] : 1;
-      o.bw[k] = f.blocks_w[c];
-      o.coef_off[k] = f.coef_offset[c] / (f.coef_wide ? 2 : 1);
-      o.dc_tab[k] = it.dc_tab[k];
-      o.ac_tab[k] = it.ac_tab[k];
-      if (s.ss == 0 && s.ah == 0) build_dev_table(tabs[it.dc_tab[k]], s.dc[k], 0);
-      if (s.se > 0) build_dev_table(tabs[it.ac_tab[k]], s.ac[k], 2);
-    }
-    memcpy(ib + it.first, s.interval_ubegin.data(), (size_t)it.nint * sizeof(uint32_t)); // (multiscan_obstacle: both lists hold nint entries at least)
-    memcpy(ie + it.first, s.interval_uend.data(), (size_t)it.nint * sizeof(uint32_t));
-  }
-  mark("tables + intervals");
-  // The entropy coded data of every scan without its stuffing, gathered by the pool in two goes: what the first launches read
-  // (level 0 of every frame), then the rest -- while the copy engine brings up the first part and the first launches run.
-  // Uploads on the copy stream, one event per level; the frames' launches wait for their level's event.
-  auto gather = [&](int lv0, int lv1) {
-    struct Job { size_t item; HostDecoder::UnstuffPiece piece; };
-    std::vector<Job> jobs;
-    std::vector<HostDecoder::UnstuffPiece> ps;
-    for (size_t ii = 0; ii < items.size(); ii++) {
-      if (items[ii].level < lv0 || items[ii].level >= lv1) continue;
-      ps.clear();
-      frames[items[ii].frame].h->unstuff_pieces(items[ii].scan, (size_t)256 << 10, ps);
-      for (const auto &pc : ps) jobs.push_back(Job{ii, pc});
-    }
-    if (jobs.empty()) return;
-    const int workers = std::max(1, std::min<int>((int)jobs.size(), std::min(default_threads(), 32)));
-    if (trace_phases) fprintf(stderr, "[mijpeg multiscan]   gather of levels %d..%d: %zu pieces on %d workers\n", lv0, lv1 - 1, jobs.size(), workers);
-    parallel_for(workers, [&](int w) {
-      for (size_t k = (size_t)w; k < jobs.size(); k += (size_t)workers) {
-        const Item &it = items[jobs[k].item];
-        frames[it.frame].h->unstuff_piece(it.scan, jobs[k].piece, d->stage_host + it.stream_off);
-      }
-    });
-  };
-  if (!d->copy_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
-  while (d->copy_events.size() < (size_t)n_levels) {
-    hipEvent_t e = nullptr;
-    HIP_TRY(d, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    d->copy_events.push_back(e);
-  }
-  if (d->ent_free_valid) HIP_TRY(d, hipStreamWaitEvent(d->copy_stream, d->ent_free, 0));
-  auto upload_levels = [&](int lv0, int lv1) -> int {
-    for (int lv = lv0; lv < lv1; lv++) {
-      const size_t b0 = lv ? level_end[(size_t)lv - 1] : 0, b1 = level_end[(size_t)lv];
-      if (lv == 0) HIP_TRY(d, hipMemcpyAsync(d->ent_dev + stream_bytes, d->ent_host, host_part, hipMemcpyHostToDevice, d->copy_stream));
-      if (b1 > b0) HIP_TRY(d, hipMemcpyAsync(d->ent_dev + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
-      HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)lv], d->copy_stream));
-    }
-    return 0;
-  };
-  ProgArgs a;
-  memset(&a, 0, sizeof(a));
-  a.data = d->ent_dev;
-  a.ibegin = (const uint32_t *)(d->ent_dev + off_ib);
-  a.iend = (const uint32_t *)(d->ent_dev + off_ie);
-  a.scans = (const ProgScanDev *)(d->ent_dev + off_scan);
-  a.waves_per_group = waves;
-  a.max_tables = max_tables;
-  a.tables = d->ent_dev + off_tab;
-  // the two frames of a JPEG XT file share nothing: the second one's launches go to a stream of their own
-  hipStream_t second = d->stream;
-  if (nframes > 1) {
-    if (!d->ms_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->ms_stream, hipStreamNonBlocking));
-    if (!d->ms_ready) HIP_TRY(d, hipEventCreateWithFlags(&d->ms_ready, hipEventDisableTiming));
-    if (!d->ms_done) HIP_TRY(d, hipEventCreateWithFlags(&d->ms_done, hipEventDisableTiming));
-    second = d->ms_stream;
-  }
-  auto launch_levels = [&](int lv0, int lv1) -> int {
-    for (size_t li = 0; li < launches.size(); li++) {
-      const int fi = launch_frame[li], lv = launch_level[li];
-      if (lv < lv0 || lv >= lv1) continue;
-      hipStream_t st = fi == 0 ? d->stream : second;
-      HIP_TRY(d, hipStreamWaitEvent(st, d->copy_events[(size_t)lv], 0));
-      a.groups = (const ProgGroup *)(d->ent_dev + off_grp) + launches[li].first;
-      a.n_groups = (int32_t)launches[li].second;
-      a.lanes = level_lanes[(size_t)fi][(size_t)lv];
-      a.wide = frames[fi].wide ? 1 : 0;
-      a.coef = (void *)(d->coef_dev + frames[fi].base16);
-      a.status = (uint32_t *)(d->ent_dev + off_status) + 8 * fi;
-      if (launch_huffman_prog(a, st)) return hip_fail(d, hipGetLastError(), "huffman_prog_kernel launch");
-    }
-    return 0;
-  };
-  // where to cut: behind the first level that brings a quarter of the bytes (a progressive frame's DC scan alone is over before
-  // anything could hide behind it); no cut when that is the last level
-  int cut = n_levels;
-  for (int lv = 0; lv + 1 < n_levels; lv++)
-    if (level_end[(size_t)lv] * 4 >= stream_bytes) { cut = lv + 1; break; }
-  const char *split_env = getenv("MIJPEG_MS_SPLIT"); // A-B: 0 = one gather, then everything enqueued
-  if (split_env && atoi(split_env) == 0) cut = n_levels;
-  gather(0, cut);
-  mark("first levels gathered");
-  if ((rc = upload_levels(0, cut))) return rc;
-  HIP_TRY(d, hipMemsetAsync(d->ent_dev + off_status, 0, status_bytes, d->stream));
-  if (nframes > 1) { // (behind whatever the object's stream still does with the planes, and the cleared status words)
-    HIP_TRY(d, hipEventRecord(d->ms_ready, d->stream));
-    HIP_TRY(d, hipStreamWaitEvent(second, d->ms_ready, 0));
-  }
-  // coefficients accumulate over the scans: the planes start out as zeros (coding/blockrow.cpp:77-87)
-  for (int fi = 0; fi < nframes; fi++) {
-    const mijpeg_info &f = frames[fi].h->info;
-    int64_t count = 0;
-    for (int c = 0; c < f.components; c++) count += (int64_t)f.blocks_w[c] * f.blocks_h[c] * 64;
-    HIP_TRY(d, hipMemsetAsync(d->coef_dev + frames[fi].base16, 0, (size_t)count * (frames[fi].wide ? 4 : 2), fi == 0 ? d->stream : second));
-  }
-  if ((rc = launch_levels(0, cut))) return rc;
-  if (cut < n_levels) {
-    gather(cut, n_levels);
-    mark("other levels gathered");
-    if ((rc = upload_levels(cut, n_levels))) return rc;
-    if ((rc = launch_levels(cut, n_levels))) return rc;
-  }
-  if (second != d->stream) {
-    HIP_TRY(d, hipEventRecord(d->ms_done, second));
-    HIP_TRY(d, hipStreamWaitEvent(d->stream, d->ms_done, 0));
-  }
-  for (int fi = 0; fi < nframes; fi++) {
-    const mijpeg_info &f = frames[fi].h->info;
-    CoefRangeArgs r;
-    memset(&r, 0, sizeof(r));
-    r.coef = (const void *)(d->coef_dev + frames[fi].base16);
-    r.wide = frames[fi].wide ? 1 : 0;
-    r.ncomp = f.components;
-    for (int c = 0; c < f.components; c++) {
-      r.coef_off[c] = f.coef_offset[c] / (f.coef_wide ? 2 : 1);
-      r.nblocks[c] = (int64_t)f.blocks_w[c] * f.blocks_h[c];
-      memcpy(r.q[c], f.quant[f.quant_index[c]], sizeof(r.q[c]));
-    }
-    r.status = (uint32_t *)(d->ent_dev + off_status) + 8 * fi;
-    if (launch_coef_range(r, d->stream)) return hip_fail(d, hipGetLastError(), "coef_range_kernel launch");
-  }
-  uint32_t *status_host = (uint32_t *)(d->ent_host + host_part);
-  HIP_TRY(d, hipMemcpyAsync(status_host, d->ent_dev + off_status, status_bytes, hipMemcpyDeviceToHost, d->stream));
-  if (!d->ent_free) HIP_TRY(d, hipEventCreateWithFlags(&d->ent_free, hipEventDisableTiming));
-  HIP_TRY(d, hipEventRecord(d->ent_free, d->stream));
-  d->ent_free_valid = true;
-  mark("launches enqueued");
-  HIP_TRY(d, hipStreamSynchronize(d->stream));
-  mark("device done");
-  std::vector<HostDecoder *> hosts((size_t)nframes);
-  for (int fi = 0; fi < nframes; fi++) hosts[(size_t)fi] = frames[fi].h;
-  return evaluate_entropy_status(d, hosts.data(), nframes, status_host);
-}
-
 int mijpeg_decode_coefficients_device(mijpeg_decoder *d, int min_intervals)
 try {
   if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
@@ -1815,17 +623,13 @@ try {
   // JPEG XT: the planes of the residual frame follow those of the legacy frame in the same store
   int64_t own_count = 0;
   for (int c = 0; c < d->host.info.components; c++) own_count += (int64_t)d->host.info.blocks_w[c] * d->host.info.blocks_h[c] * 64;
-  static const bool trace_read = getenv("MIJPEG_TRACE_SUBMIT") != nullptr; // diagnostics
+  const bool trace_read = TraceMarks::on();
   if (trace_read)
     fprintf(stderr, "[mijpeg device read] parse %.3f ms, checks + coefficient store %.3f ms\n", std::chrono::duration<double>(t_parsed - t0).count() * 1e3,
             std::chrono::duration<double>(clk::now() - t_parsed).count() * 1e3);
   if (multiscan) {
     MultiScanFrame fr[2] = {{h, false, 0}, {res, res && d->host.xt.residual_wide != 0, own_count}};
     rc = device_entropy_multiscan(d, fr, res ? 2 : 1, min_intervals);
-    if (!rc && res) {
-      for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) d->host.xt.residual.range_max[c] = res->info.range_max[c];
-      d->host.info.fast_arith = 0; // as HostDecoder::decode has it: the fast flavours are chosen per kernel for XT
-    }
   } else if (!res) {
     rc = device_entropy_batch(d, &h, &d->data, &d->size, 1, min_intervals, d->coef_dev, own_count, false);
   } else {
@@ -1854,10 +658,10 @@ try {
       mijpeg_last_error(d->xt_helper, &m);
       rc = set_error(d, rc2, m ? m : "residual codestream: device entropy decoding failed");
     }
-    if (!rc) {
-      for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) d->host.xt.residual.range_max[c] = res->info.range_max[c];
-      d->host.info.fast_arith = 0; // as HostDecoder::decode has it: the fast flavours are chosen per kernel for XT
-    }
+  }
+  if (!rc && res) {
+    for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) d->host.xt.residual.range_max[c] = res->info.range_max[c];
+    d->host.info.fast_arith = 0; // as HostDecoder::decode has it: the fast flavours are chosen per kernel for XT
   }
   d->timing[0] = std::chrono::duration<double>(clk::now() - t0).count();
   d->timing[1] = std::chrono::duration<double>(t_parsed - t0).count(); // header parse + restart marker search
@@ -1947,7 +751,7 @@ static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const 
   {
     std::vector<size_t> slot;
     const size_t total = stream_slots(sizes, n, slot);
-    const int src = ensure_stage(d, total);
+    const int src = ensure_pinned(d, &d->stage_host, &d->stage_cap, total);
     if (src) return src;
     parallel_for(std::min(n, default_threads()), [&](int w) {
       for (int i = w; i < n; i += std::min(n, default_threads())) {
@@ -1985,9 +789,8 @@ static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const 
   d->timing[1] = std::chrono::duration<double>(t_parsed - t0).count();
   d->timing[2] = d->phase_prepare;
   d->timing[3] = d->phase_device;
-  if (rc) { // copies may have been enqueued before the failure: nothing of this batch stays in flight
-    d->pend_n = 1;
-    (void)settle_pending(d);
+  if (rc) { // (device_entropy_batch has waited for whatever it enqueued before the failure)
+    d->pend_n = 0;
     return rc;
   }
   d->batch_own_tables = own_tables;
@@ -2031,14 +834,9 @@ static int finish_batch(mijpeg_decoder *d)
       const int rounds = d->pend_walk_round;
       d->pend_walk_round = 0;
       if (d->pend_walk_flags[rounds]) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding did not settle in the rounds a submitted batch gets: decode it with mijpeg_decode_batch_device");
-      d->walk_rounds = 1;
-      for (int r = 1; r <= rounds; r++)
-        if (d->pend_walk_flags[r]) d->walk_rounds = r + 1;
-      for (int i = 0; i < pn && d->pend_walk_status; i++) {
-        if (d->pend_walk_status[i] & 2)
-          return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "on-device entropy decoding: a DC coefficient leaves the 16 bit coefficient store (damaged stream); the host decoder keeps 32-bit coefficients for it");
-        if (d->pend_walk_status[i]) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding settled on something that is not a decode of the image");
-      }
+      d->walk_rounds = walk_rounds_needed(d->pend_walk_flags, rounds);
+      if (d->pend_walk_status)
+        if (const int wrc = walk_verdict(d, d->pend_walk_status, pn)) return wrc;
     }
     const int rc = evaluate_entropy_status(d, hosts.data(), pn, d->pend_status);
     if (rc) return rc;
@@ -2125,7 +923,7 @@ try {
   uint8_t *stage;
   if (d->device >= 0) {
     HIP_TRY(d, hipSetDevice(d->device));
-    if (const int src = ensure_stage(d, total)) return src;
+    if (const int src = ensure_pinned(d, &d->stage_host, &d->stage_cap, total)) return src;
     stage = d->stage_host;
   } else {
     if (d->host_stage.size() < total) d->host_stage.resize(total);
@@ -3135,13 +1933,8 @@ try {
   // pinned staging: [pixels][coefficients].  The picture goes up in bands, each gathered into pinned memory by the pool
   // threads while the DMA of the previous band runs; the coefficients come down into pinned memory the coder reads.
   const size_t stage_bytes = ((px_bytes + 255) & ~(size_t)255) + coef_bytes;
-  if (d->stage_cap < stage_bytes) {
-    if (d->stage_host) (void)hipHostFree(d->stage_host);
-    d->stage_host = nullptr;
-    d->stage_cap = 0;
-    HIP_TRY(d, hipHostMalloc((void **)&d->stage_host, stage_bytes, hipHostMallocDefault));
-    d->stage_cap = stage_bytes;
-  }
+  rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, stage_bytes);
+  if (rc) return rc;
   int16_t *coef_host = (int16_t *)(d->stage_host + ((px_bytes + 255) & ~(size_t)255));
   {
     const size_t band = std::max<size_t>((size_t)8 << 20, (px_bytes + 7) / 8) & ~(size_t)255;
@@ -3194,24 +1987,6 @@ try {
 // ------------------------------------------------------------------------------------------------
 // decoder-object reconstruction
 // ------------------------------------------------------------------------------------------------
-static int ensure_dev(mijpeg_decoder *d, void **ptr, size_t *cap, size_t bytes)
-{
-  if (*cap >= bytes) return MIJPEG_OK;
-  quiesce(d);
-  release_big(d->device, false, *ptr, *cap);
-  *ptr = nullptr;
-  *cap = 0;
-  size_t got = 0;
-  if (void *p = buffer_cache().take(d->device, false, bytes, &got)) {
-    *ptr = p;
-    *cap = got;
-    return MIJPEG_OK;
-  }
-  HIP_TRY(d, hipMalloc(ptr, bytes));
-  *cap = bytes;
-  return MIJPEG_OK;
-}
-
 // The frame as the reconstruction sees it: the whole picture, or -- without upsampling -- one component at its own
 // resolution, which is a single-component identity-transformed frame over that component's coefficient plane
 // (BlockBitmapRequester::ReconstructUnsampled with rr_bUpsampling = false: control/blockbitmaprequester.cpp:1013-1074,
@@ -3391,20 +2166,7 @@ static int serve_rect(mijpeg_decoder *d, int view, uint32_t flags, bool to_devic
   }
   if (!to_device && !d->img_host_valid) {
     HIP_TRY(d, hipSetDevice(d->device));
-    if (d->img_host_cap < padded) {
-      quiesce(d);
-      release_big(d->device, true, d->img_host, d->img_host_cap);
-      d->img_host = nullptr;
-      d->img_host_cap = 0;
-      size_t got = 0;
-      if (void *p = buffer_cache().take(d->device, true, padded, &got)) {
-        d->img_host = (uint8_t *)p;
-        d->img_host_cap = got;
-      } else {
-        HIP_TRY(d, hipHostMalloc((void **)&d->img_host, padded, hipHostMallocDefault));
-        d->img_host_cap = padded;
-      }
-    }
+    if (const int prc = ensure_cached(d, true, (void **)&d->img_host, &d->img_host_cap, padded)) return prc;
     // bands of about 4 MiB (at least 8 lines): enqueue all of them now, wait for them as they are asked for
     static const long band_mib = getenv("MIJPEG_RECT_BAND_MIB") ? atol(getenv("MIJPEG_RECT_BAND_MIB")) : 4; // tuning; <= 0: one band
     d->band_lines = band_mib <= 0 ? f.height : (int)std::max<size_t>(8, (((size_t)band_mib << 20) / std::max<size_t>(row, 1) + 7) & ~(size_t)7);
@@ -3587,13 +2349,7 @@ static int hand_out_request(mijpeg_decoder *d, int min_x, int min_y, int y_count
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     return MIJPEG_OK;
   }
-  if (d->req_host_cap < padded) {
-    if (d->req_host) (void)hipHostFree(d->req_host);
-    d->req_host = nullptr;
-    d->req_host_cap = 0;
-    HIP_TRY(d, hipHostMalloc((void **)&d->req_host, padded, hipHostMallocDefault));
-    d->req_host_cap = padded;
-  }
+  if (const int prc = ensure_pinned(d, &d->req_host, &d->req_host_cap, padded)) return prc;
   HIP_TRY(d, hipMemcpyAsync(d->req_host + (size_t)min_y * row, d->req_dev + (size_t)min_y * row, (size_t)y_count * row, hipMemcpyDeviceToHost,
                             d->stream));
   HIP_TRY(d, hipStreamSynchronize(d->stream));

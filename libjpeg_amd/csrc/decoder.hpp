@@ -1,0 +1,192 @@
+// decoder.hpp -- the decoder object of the C ABI and what its two translation units share: capi.cpp (the extern "C" bodies)
+// and entropy_device.cpp (entropy decoding on the device).  Private to libmijpeg.so.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <chrono>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/mijpeg.h"
+#include "host_decoder.hpp"
+#include "request_model.hpp"
+
+struct mijpeg_decoder {
+  int device = -1;
+  mij::HostDecoder host;
+  const uint8_t *data = nullptr;
+  size_t size = 0;
+  bool parsed = false, decoded = false, uploaded = false;
+  bool parse_fresh = false; // host holds a full parse of (data, size) that nothing has touched since: mijpeg_decode_coefficients_device
+                            // found the stream not to qualify, the host decode that follows need not parse again
+  // coefficient store: pinned when a device is attached
+  int16_t *coef_host = nullptr;
+  size_t coef_host_cap = 0; // int16 units
+  int16_t *coef_dev = nullptr;
+  size_t coef_dev_cap = 0;
+  // reconstruction cache for the rectangle service
+  uint8_t *img_dev = nullptr;
+  size_t img_dev_cap = 0;
+  uint8_t *img_host = nullptr; // pinned
+  size_t img_host_cap = 0;
+  bool img_valid = false;      // img_dev holds the reconstructed frame for img_flags
+  bool img_host_valid = false; // ... and img_host its copy (being filled band by band, see band_events)
+  // the device-to-host copy of the reconstructed frame travels in bands of lines, one event each: a rectangle request
+  // waits for the bands it touches only, so the first stripes of a frame are served while the rest is still on its way
+  std::vector<hipEvent_t> band_events;
+  int band_lines = 0, bands = 0, bands_waited = 0;
+  uint32_t img_flags = 0;
+  int img_view = -1;           // component of a non-upsampled reconstruction, -1: the whole picture
+  // mijpeg_display_rect: the reference's state between DisplayRectangle calls (request_model.hpp) and the buffers of the
+  // requests that do not show the plain picture
+  mij::RequestModel model, rmodel; // (rmodel: the residual image of a JPEG XT frame)
+  bool model_valid = false;
+  uint8_t *req_dev = nullptr, *req_host = nullptr; // frame-sized interleaved image (device; pinned host)
+  size_t req_dev_cap = 0, req_host_cap = 0;
+  int32_t *rowmap_dev = nullptr;
+  size_t rowmap_cap = 0;
+  int32_t *ws_dev = nullptr;
+  size_t ws_cap = 0; // bytes
+  // on-device entropy decoding: stream bytes, interval offsets, tables, status word
+  uint8_t *ent_dev = nullptr;
+  size_t ent_cap = 0;
+  uint8_t *ent_host = nullptr; // pinned staging for offsets + tables + status
+  size_t ent_host_cap = 0;
+  bool host_planes_stale = false; // coefficients live on the device only
+  double phase_prepare = 0, phase_device = 0; // last device entropy decode: host tables / upload + kernel
+  mijpeg_decoder *xt_helper = nullptr; // JPEG XT: second context that entropy-decodes the residual codestream concurrently
+  // JPEG XT alpha channel: an image of its own (ALFA box), decoded by a decoder object of its own that this one owns
+  // (mijpeg_alpha_channel); its codestream is copied here because every parse of the file rebuilds the boxes
+  mijpeg_decoder *alpha = nullptr;
+  bool alpha_ready = false;
+  int alpha_refusal = 0;          // the alpha image reads, its transformer would not build (or this path declines it): the code
+  std::string alpha_refusal_msg;
+  std::vector<uint8_t> alpha_data;
+  uint8_t *enc_dev = nullptr; // encoder direction: pixels + coefficients of one picture
+  size_t enc_cap = 0;
+  uint8_t *henc_dev[2] = {nullptr, nullptr}, *henc_out_dev[2] = {nullptr, nullptr}; // device entropy coder, two jobs: arrays; streams
+  size_t henc_cap[2] = {0, 0}, henc_out_cap[2] = {0, 0};
+  uint64_t *henc_host = nullptr; // pinned: byte counts read back from the device, code tables on their way up
+  uint8_t *walk_dev = nullptr, *walk_host = nullptr; // state of the device walk over streams without restart markers
+  size_t walk_cap = 0, walk_host_cap = 0;
+  int walk_rounds = 0;
+  uint32_t *walk_status_dev = nullptr;
+  hipStream_t copy_stream = nullptr;          // uploads of a batch's streams, ahead of the kernels that decode them
+  hipEvent_t ent_free = nullptr;              // behind the last kernel / copy that reads ent_dev
+  bool ent_free_valid = false;
+  std::vector<hipEvent_t> copy_events;
+  uint8_t *stage_host = nullptr;  // pinned gathering area for the streams of a batch
+  std::vector<uint8_t> host_stage; // the same for host-only objects (mijpeg_prepare_batch_host)
+  size_t stage_cap = 0;
+  // batches (mijpeg_decode_batch_device): one parsed decoder per stream, frame 0's info with the batch's worst range
+  std::vector<std::unique_ptr<mij::HostDecoder>> batch_hosts;
+  mijpeg_info batch_info{};
+  int batch_frames = 0;
+  // a submitted batch whose device work has not been waited for yet (mijpeg_submit_batch_device)
+  int pend_n = 0;
+  const uint32_t *pend_status = nullptr;
+  int pend_walk_round = 0;                       // > 0: the batch went through the device walk with this many rounds, unchecked
+  const uint32_t *pend_walk_flags = nullptr;     // "something changed" per round (pinned)
+  const uint32_t *pend_walk_status = nullptr;    // per image (pinned)
+  std::chrono::steady_clock::time_point pend_t0;
+  // batches whose images bring different quantisation tables: [frames][4][64] deltas per component, on the device
+  uint16_t *batch_quant_dev = nullptr;
+  size_t batch_quant_cap = 0;
+  bool batch_own_tables = false;
+  std::vector<uint16_t> batch_quant_host;
+  // MIJPEG_FLAG_SPECULATIVE: the reconstruction of a submitted batch was launched on an ASSUMED range check (spec_assumed:
+  // what the last batch of this shape reported, rounded up to the kernel selection's next gate) behind the Huffman kernel,
+  // without the host waiting for what that kernel reports; finish_batch validates and launches again where the assumption
+  // did not hold (settle_speculation)
+  bool spec_active = false, spec_redone = false;
+  void *spec_dst = nullptr;
+  int64_t spec_frame_stride = 0, spec_row_stride = 0;
+  uint32_t spec_flags = 0;
+  int32_t spec_assumed[MIJPEG_MAX_COMPONENTS] = {0, 0, 0, 0};
+  int64_t spec_launched = 0, spec_redone_count = 0; // diagnostics (mijpeg_batch_speculation)
+  hipStream_t stream = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipEvent_t chain_ev = nullptr; // mijpeg_stream_wait
+  hipEvent_t ms_ready = nullptr, ms_done = nullptr; // device_entropy_multiscan: the second frame's stream
+  hipStream_t ms_stream = nullptr;
+  int err_code = 0;
+  std::string err_msg;
+  double timing[4] = {0, 0, 0, 0};
+};
+
+inline int set_error(mijpeg_decoder *d, int code, const std::string &msg)
+{
+  d->err_code = code;
+  d->err_msg = msg;
+  return code;
+}
+
+inline int hip_fail(mijpeg_decoder *d, hipError_t e, const char *what)
+{
+  return set_error(d, MIJPEG_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+#define HIP_TRY(d, call)                                  \
+  do {                                                    \
+    hipError_t e_ = (call);                               \
+    if (e_ != hipSuccess) return hip_fail(d, e_, #call);  \
+  } while (0)
+
+// everything this object has enqueued is done (before one of its buffers changes hands while the object lives on: rare, a
+// buffer only grows when a larger picture arrives)
+inline void quiesce(mijpeg_decoder *d)
+{
+  if (d->device < 0) return;
+  if (d->stream) (void)hipStreamSynchronize(d->stream);
+  if (d->copy_stream) (void)hipStreamSynchronize(d->copy_stream);
+  if (d->ms_stream) (void)hipStreamSynchronize(d->ms_stream);
+}
+
+// Device buffers that grow through the buffer cache (capi.cpp): what this object has enqueued finishes before the old buffer goes
+int ensure_dev(mijpeg_decoder *d, void **ptr, size_t *cap, size_t bytes);
+
+// ... and their pinned counterpart, for staging buffers that are not handed to the buffer cache
+inline int ensure_pinned(mijpeg_decoder *d, uint8_t **ptr, size_t *cap, size_t bytes)
+{
+  if (*cap >= bytes) return MIJPEG_OK;
+  quiesce(d);
+  if (*ptr) (void)hipHostFree(*ptr);
+  *ptr = nullptr;
+  *cap = 0;
+  HIP_TRY(d, hipHostMalloc((void **)ptr, bytes, hipHostMallocDefault));
+  *cap = bytes;
+  return MIJPEG_OK;
+}
+
+// MIJPEG_TRACE_SUBMIT (diagnostics): the host time of the steps of a device decode, since t0, on stderr
+struct TraceMarks {
+  const char *who;
+  std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+  static bool on() { static const bool e = getenv("MIJPEG_TRACE_SUBMIT") != nullptr; return e; }
+  void operator()(const char *what) const
+  {
+    if (on()) fprintf(stderr, "[%s] %-28s %8.3f ms\n", who, what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
+  }
+};
+
+// ---- entropy_device.cpp: on-device entropy decoding ----
+// One frame of a file: its decoder, the element type of its planes, where they start in the object's coefficient store.
+struct MultiScanFrame {
+  mij::HostDecoder *h;
+  bool wide;        // int32 coefficients (JPEG XT residual frames with hidden bits)
+  int64_t base16;   // offset of the frame's planes in coef_dev, in int16 units
+};
+
+const char *device_entropy_obstacle(const mij::HostDecoder &h, size_t size, bool xt_part = false);
+const char *multiscan_obstacle(const mij::HostDecoder &h, bool xt_part, bool residual_frame);
+size_t stream_slots(const size_t *sizes, int n, std::vector<size_t> &stream_off);
+int device_entropy_batch(mijpeg_decoder *d, mij::HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
+                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part = false, bool defer = false);
+int device_entropy_multiscan(mijpeg_decoder *d, const MultiScanFrame *frames, int nframes, int min_intervals);
+int evaluate_entropy_status(mijpeg_decoder *d, mij::HostDecoder *const *hosts, int n, const uint32_t *status_host);
+int walk_rounds_needed(const uint32_t *changed, int rounds);
+int walk_verdict(mijpeg_decoder *d, const uint32_t *walk_status, int n);

@@ -1,0 +1,1049 @@
+// entropy_device.cpp -- entropy decoding on the device: which streams qualify, the upload of their entropy coded data and
+// tables, the launches of the Huffman kernels (huffman.hip) and what their status words say.  Host code only, compiled with
+// hipcc like capi.cpp, whose extern "C" bodies call it.
+#include <string.h>
+
+#include <algorithm>
+
+#include "decoder.hpp"
+#include "huffman_dev.hpp"
+#include "kernels.hpp"
+
+using namespace mij;
+
+// ------------------------------------------------------------------------------------------------
+// on-device entropy decoding
+// ------------------------------------------------------------------------------------------------
+// Why a parsed stream cannot be entropy-decoded on the device (nullptr: it can).  `xt_part`: the stream is one of the
+// two codestreams of a JPEG XT profile C file (8-bit legacy or 12-bit residual frame without hidden refinement scans).
+const char *device_entropy_obstacle(const HostDecoder &h, size_t size, bool xt_part)
+{
+  const mijpeg_info &f = h.info;
+  // one Huffman sequential scan over all components (or a single-component frame)
+  if (h.needs_sequential())
+    return "on-device entropy decoding: the stream is damaged; the host decoder walks it with the reference's resynchronisation (entropyparser.cpp:117-201)";
+  if (f.progressive) return "on-device entropy decoding: progressive frames are decoded on the host";
+  if (f.xt && !xt_part) return "on-device entropy decoding: not for this JPEG XT stream";
+  if (!h.residual_merged()) return "on-device entropy decoding: the legacy codestream has no EOI marker (the host decoder decides what is merged)";
+  // (a RESI box without a merging specification, a residual codestream header that does not match, tables looked up at the first
+  // request: what the reference reports behind the legacy frame's decode -- HostDecoder::decode reports it, this path would not)
+  if (h.verdict_pending()) return "on-device entropy decoding: the file's verdict is the host decoder's (residual codestream header / tables looked up at the first request)";
+  if (f.precision != 8 && !(xt_part && f.precision == 12)) return "on-device entropy decoding: 8-bit frames (12-bit residual frames of JPEG XT) only";
+  if (h.scans.size() != 1 || h.hidden_bits()) return "on-device entropy decoding: the frame has more than one scan";
+  const Scan &s = h.scans[0];
+  if (s.ncomp != f.components) return "on-device entropy decoding: the scan does not cover all components";
+  if (size > 0xfffffff0ull) return "on-device entropy decoding: stream too long";
+  for (int c = 0; c < f.components; c++)
+    if (f.hsamp[c] > 4 || f.vsamp[c] > 4) return "on-device entropy decoding: MCUs of more than 4 x 4 blocks of a component are decoded on the host";
+  return nullptr;
+}
+
+namespace { // steps the sequential, progressive and walk paths share
+
+// Workgroups of the Huffman kernels hold four waves, one per SIMD: with two-wave workgroups (which round 1 chose for the LDS
+// they leave to others) the same eight waves per CU decode 37 % slower (0.60 against 0.38 ms per 32 4K frames; 3, 5, 6 waves:
+// 0.55, 0.58, 0.48) -- the waves of a workgroup go to the SIMDs in cyclic order, and only a multiple of four loads them evenly
+constexpr int WAVES_PER_GROUP = 4;
+
+const char DC_OVERFLOW[] = "on-device entropy decoding: a DC coefficient leaves the 16 bit coefficient store (damaged stream); the host decoder keeps 32-bit coefficients for it";
+
+// The regions of a packed buffer: offsets handed out in order, each region starting on a 16-byte boundary.
+struct Layout {
+  size_t end = 0;
+  size_t take(size_t bytes) { const size_t at = end; end = (at + bytes + 15) & ~(size_t)15; return at; }
+};
+
+// Decoding lanes per wave for a launch of `intervals` restart intervals: about a thousand waves (one per SIMD) are what a small
+// launch wants -- fewer lanes per wave mean more waves that each issue the same instructions for less, fuller waves mean longer
+// steps (the slowest lane's block).  Measured with the bit-addressed reader and four-wave workgroups on one 8K 4:2:0 frame with
+// 16200 intervals (tools/gpu_huff_lanes.sh): 1 lane 0.81 ms, 2: 0.52, 4: 0.33, 8: 0.26, 16: 0.26, 32: 0.27.
+// MIJPEG_HUFF_LANES (a power of two up to 64) overrides the choice.
+int lanes_for(int64_t intervals)
+{
+  int lanes = 64;
+  while (lanes > 1 && intervals / lanes < 768) lanes >>= 1;
+  if (const char *e = getenv("MIJPEG_HUFF_LANES")) {
+    const int l = atoi(e);
+    if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) lanes = l;
+  }
+  return lanes;
+}
+
+// The buffer of one device decode: on the device [streams][tables, intervals ...][status words]; in pinned staging (ent_host)
+// everything behind the streams, at the same offsets less stream_bytes.  The staging part goes up in one copy, and the status
+// words come back into its end.
+int ensure_entropy_buffers(mijpeg_decoder *d, size_t stream_bytes, size_t tail_bytes)
+{
+  const int rc = ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, stream_bytes + tail_bytes);
+  return rc ? rc : ensure_pinned(d, &d->ent_host, &d->ent_host_cap, tail_bytes);
+}
+
+// The unstuffing gather: the device's copy of scans' entropy coded data (no byte stuffing, no markers: HostDecoder::unstuff_piece)
+// written into pinned staging by the pool, in pieces of ~256 KiB of source.
+struct Gather {
+  struct Job { const HostDecoder *h; size_t scan; HostDecoder::UnstuffPiece piece; uint8_t *dst; };
+  std::vector<Job> jobs;
+  std::vector<HostDecoder::UnstuffPiece> pieces;
+  void add(const HostDecoder *h, size_t scan, uint8_t *dst)
+  {
+    pieces.clear();
+    h->unstuff_pieces(scan, (size_t)256 << 10, pieces);
+    for (const auto &p : pieces) jobs.push_back(Job{h, scan, p, dst});
+  }
+  void run()
+  {
+    if (jobs.empty()) return;
+    // (the sweep runs at about half of memcpy's rate: twice the workers the plain copy had)
+    const int workers = std::max(1, std::min<int>((int)jobs.size(), std::min(default_threads(), 32)));
+    parallel_for(workers, [&](int w) {
+      for (size_t k = (size_t)w; k < jobs.size(); k += (size_t)workers) jobs[k].h->unstuff_piece(jobs[k].scan, jobs[k].piece, jobs[k].dst);
+    });
+    jobs.clear();
+  }
+};
+
+// The copy stream, with at least `events` events for its uploads.  It must not overtake work that still reads the entropy
+// buffer from an earlier call: the Huffman kernels and the status copy of the previous decode (ent_free, recorded behind them).
+// NOT everything on d->stream: the reconstruction kernel of a previous batch does not touch this buffer, and an upload that
+// waits for it leaves the link idle for the length of that kernel in every round of a pipeline (profiles/r03/batch4k_timeline.txt)
+int prepare_copy_stream(mijpeg_decoder *d, size_t events)
+{
+  if (!d->copy_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
+  while (d->copy_events.size() < events) {
+    hipEvent_t e = nullptr;
+    HIP_TRY(d, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    d->copy_events.push_back(e);
+  }
+  if (d->ent_free_valid) HIP_TRY(d, hipStreamWaitEvent(d->copy_stream, d->ent_free, 0));
+  return MIJPEG_OK;
+}
+
+// The status words back into pinned staging, and ent_free behind them: from there on nothing enqueued so far reads the entropy buffer
+int read_back_status(mijpeg_decoder *d, uint32_t *status_host, const uint8_t *status_dev, size_t bytes)
+{
+  HIP_TRY(d, hipMemcpyAsync(status_host, status_dev, bytes, hipMemcpyDeviceToHost, d->stream));
+  if (!d->ent_free) HIP_TRY(d, hipEventCreateWithFlags(&d->ent_free, hipEventDisableTiming));
+  HIP_TRY(d, hipEventRecord(d->ent_free, d->stream));
+  d->ent_free_valid = true;
+  return MIJPEG_OK;
+}
+
+// Once a device decode has put work on its streams, an exit with an error code or an exception waits for all of it: the caller
+// goes on to the host decoder, which reuses the staging buffers and coef_dev.  Success disarms the guard (a deferred batch is
+// waited for by finish_batch).
+struct QuiesceOnError {
+  mijpeg_decoder *d;
+  bool armed = false;
+  ~QuiesceOnError() { if (armed) quiesce(d); }
+};
+
+} // namespace
+
+// Where the device's copy of image i's entropy coded data goes inside the launch's stream buffer (and inside the pinned
+// gathering area): a slot of the stream's own size -- known before the stream is parsed, so a batch's workers can write the
+// copy while they search it for markers -- rounded to 16 bytes, plus the pad the kernels' prefetch may run into.
+size_t stream_slots(const size_t *sizes, int n, std::vector<size_t> &stream_off)
+{
+  stream_off.resize((size_t)n);
+  Layout slots;
+  for (int i = 0; i < n; i++) stream_off[(size_t)i] = slots.take(sizes[i] + HUFF_STREAM_PAD);
+  return slots.end;
+}
+
+// "Something changed" flags of walk rounds 1..rounds: the rounds that were needed -- the last one that changed something, and
+// one to see it
+int walk_rounds_needed(const uint32_t *changed, int rounds)
+{
+  int needed = 1;
+  for (int r = 1; r <= rounds; r++)
+    if (changed[r]) needed = r + 1;
+  return needed;
+}
+
+// What the walk's status words of n images say about the restart points it settled on
+int walk_verdict(mijpeg_decoder *d, const uint32_t *walk_status, int n)
+{
+  for (int i = 0; i < n; i++) {
+    if (walk_status[i] & 2) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, DC_OVERFLOW);
+    if (walk_status[i]) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding settled on something that is not a decode of the image");
+  }
+  return MIJPEG_OK;
+}
+
+// Streams without restart markers: find their virtual restart intervals on the device.  Rounds of huffman_walk_kernel
+// until the hand-over states between neighbouring subsequences stop changing, prefix sums over the subsequences
+// (block numbers, DC predictors: huffman_walk_scan_kernel), and one EMIT walk that writes the interval tables the
+// decode kernel reads.  The host only looks at the per-round "something changed" flags.
+// `images_host` is the staging copy of the HuffImage array (first_interval = start of the image's interval entries).
+static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const std::vector<int> &dwalk, const HuffScanArgs &scan,
+                              const HuffImage *images_dev, uint32_t *ibegin_dev, uint8_t *iskip_dev, int16_t *ipred_dev,
+                              const HuffImage *images_host, const std::vector<size_t> &usize, bool defer = false)
+{
+  const mijpeg_info &f0 = hosts[0]->info;
+  const Scan &s0 = hosts[0]->scans[0];
+  HuffWalkArgs w;
+  memset(&w, 0, sizeof(w));
+  w.ncomp = s0.ncomp;
+  int B = 0;
+  for (int k = 0; k < s0.ncomp; k++) {
+    const int c = s0.sc[k].comp;
+    w.hs[k] = s0.ncomp > 1 ? f0.hsamp[c] : 1;
+    w.vs[k] = s0.ncomp > 1 ? f0.vsamp[c] : 1;
+    B += w.hs[k] * w.vs[k];
+  }
+  if (B > 64) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device walk");
+  w.nblk_mcu = B;
+  w.ntables = scan.ntables;
+  // subsequence size.  One image: the launch is latency-bound, its serial part is (distance the decoder needs to
+  // synchronise + two subsequences), so small ones.  Batches are throughput-bound and every round re-walks whole
+  // subsequences, so fewer rounds over larger ones (measured on 1, 4 and 16 8K frames: 128, 256, 512 bytes win).
+  size_t longest = 0, all_bytes = 0;
+  for (int i = 0; i < n; i++)
+    if (dwalk[(size_t)i]) {
+      const size_t len = usize[(size_t)i]; // (the device's copy: entropy coded data without the byte stuffing)
+      longest = std::max(longest, len);
+      all_bytes += len;
+    }
+  uint32_t sub_bytes = all_bytes <= ((size_t)8 << 20) ? 128 : all_bytes <= ((size_t)32 << 20) ? 256 : 512;
+  while (sub_bytes < 1024 && longest / sub_bytes > ((size_t)1 << 20)) sub_bytes <<= 1; // bounds the prefix-sum tiles
+  if (const char *e = getenv("MIJPEG_WALK_SUB")) sub_bytes = (uint32_t)std::max(32, std::min(4096, atoi(e))); // experiments
+  w.sub_bytes = sub_bytes;
+  // per image: its subsequences; per workgroup: image and first subsequence
+  std::vector<uint32_t> img_sub0((size_t)n, 0), img_nsub((size_t)n, 0), img_e0((size_t)n, 0), img_e1((size_t)n, 0), img_int0((size_t)n, 0);
+  uint32_t nsub_total = 0;
+  for (int i = 0; i < n; i++) {
+    img_e0[(size_t)i] = 0;
+    img_e1[(size_t)i] = (uint32_t)usize[(size_t)i];
+    img_int0[(size_t)i] = images_host[i].first_interval;
+    img_sub0[(size_t)i] = nsub_total;
+    if (dwalk[(size_t)i]) {
+      img_nsub[(size_t)i] = (uint32_t)((usize[(size_t)i] + sub_bytes - 1) / sub_bytes);
+      nsub_total += img_nsub[(size_t)i];
+    }
+  }
+  w.lanes = 64;
+  while (w.lanes > 1 && nsub_total / (uint32_t)w.lanes < 2048) w.lanes >>= 1;
+  w.waves_per_group = WAVES_PER_GROUP;
+  const uint32_t per_group = (uint32_t)(w.lanes * w.waves_per_group);
+  std::vector<uint32_t> sub_image, sub_first;
+  for (int i = 0; i < n; i++)
+    for (uint32_t k = 0; k < img_nsub[(size_t)i]; k += per_group) { sub_image.push_back((uint32_t)i); sub_first.push_back(k); }
+  w.n_groups = (int32_t)sub_image.size();
+  // one device buffer: [per group: image, first][per image: sub0, nsub, e0, e1, int0][per subsequence: state] (the host fills
+  // these) [changed flag per round, status per image][per subsequence: stamp] (start out as zero) [per subsequence: nblocks,
+  // dcsum, first_block, first_pred][prefix-sum tiles]
+  constexpr int MAX_ROUNDS = 48;
+  const size_t G = sub_image.size(), S = nsub_total;
+  Layout L;
+  const size_t o_simg = L.take(G * 4), o_sfirst = L.take(G * 4);
+  const size_t o_isub0 = L.take((size_t)n * 4), o_insub = L.take((size_t)n * 4), o_e0 = L.take((size_t)n * 4), o_e1 = L.take((size_t)n * 4);
+  const size_t o_int0 = L.take((size_t)n * 4), o_state = L.take(S * 8);
+  const size_t o_up_end = L.end;
+  const size_t o_flags = L.take((size_t)(MAX_ROUNDS + 1) * 4 + (size_t)n * 4); // changed[], walk_status[]
+  const size_t o_stamp = L.take(S * 4);
+  const size_t o_zero_end = L.end;
+  const size_t o_nblk = L.take(S * 4), o_dcsum = L.take(S * 16), o_fblk = L.take(S * 4), o_fpred = L.take(S * 16);
+  uint32_t most = 0;
+  for (int i = 0; i < n; i++) most = std::max(most, img_nsub[(size_t)i]);
+  const int tiles = (int)((most + HUFF_WALK_TILE - 1) / HUFF_WALK_TILE);
+  if (tiles > HUFF_WALK_TILE) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream too long for the device walk");
+  const size_t o_tiles = L.take((size_t)n * tiles * HUFF_WALK_SUMS_BYTES);
+  int rc = ensure_dev(d, (void **)&d->walk_dev, &d->walk_cap, L.end);
+  if (rc) return rc;
+  // pinned: what the host fills, then room for the flags (and the status words, read back to the start)
+  rc = ensure_pinned(d, &d->walk_host, &d->walk_host_cap, o_up_end + (o_stamp - o_flags));
+  if (rc) return rc;
+  uint8_t *wh = d->walk_host, *wd = d->walk_dev;
+  memcpy(wh + o_simg, sub_image.data(), G * 4);
+  memcpy(wh + o_sfirst, sub_first.data(), G * 4);
+  memcpy(wh + o_isub0, img_sub0.data(), (size_t)n * 4);
+  memcpy(wh + o_insub, img_nsub.data(), (size_t)n * 4);
+  memcpy(wh + o_e0, img_e0.data(), (size_t)n * 4);
+  memcpy(wh + o_e1, img_e1.data(), (size_t)n * 4);
+  memcpy(wh + o_int0, img_int0.data(), (size_t)n * 4);
+  // the initial guess: every subsequence starts at its boundary (behind a stuffed zero if it falls on one) with the
+  // first block of an MCU; for the first subsequence of an image that is no guess
+  {
+    // (positions in the device's copy, which has no byte stuffing: nothing of the stream is looked at here)
+    uint64_t *st = (uint64_t *)(wh + o_state);
+    for (int i = 0; i < n; i++)
+      for (uint32_t k = 0; k < img_nsub[(size_t)i]; k++) st[img_sub0[(size_t)i] + k] = (uint64_t)k * sub_bytes;
+  }
+  HIP_TRY(d, hipMemcpyAsync(wd, wh, o_up_end, hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(d, hipMemsetAsync(wd + o_flags, 0, o_zero_end - o_flags, d->stream));
+  w.data = scan.data;
+  w.images = images_dev;
+  w.tables = scan.tables;
+  w.sub_image = (const uint32_t *)(wd + o_simg);
+  w.sub_first = (const uint32_t *)(wd + o_sfirst);
+  w.img_sub0 = (const uint32_t *)(wd + o_isub0);
+  w.img_nsub = (const uint32_t *)(wd + o_insub);
+  w.img_e0 = (const uint32_t *)(wd + o_e0);
+  w.img_e1 = (const uint32_t *)(wd + o_e1);
+  w.img_int0 = (const uint32_t *)(wd + o_int0);
+  w.state = (uint64_t *)(wd + o_state);
+  w.stamp = (uint32_t *)(wd + o_stamp);
+  w.changed = (uint32_t *)(wd + o_flags);
+  w.walk_status = w.changed + MAX_ROUNDS + 1;
+  w.nblocks = (uint32_t *)(wd + o_nblk);
+  w.dcsum = (int32_t *)(wd + o_dcsum);
+  w.first_block = (uint32_t *)(wd + o_fblk);
+  w.first_pred = (int32_t *)(wd + o_fpred);
+  w.tile_sums = (WalkSums *)(wd + o_tiles);
+  w.tiles_per_image = tiles;
+  w.ibegin = ibegin_dev;
+  w.iskip = iskip_dev;
+  w.ipred = ipred_dev;
+  const int64_t total_blocks = (int64_t)s0.mcus_x * s0.mcus_y * B;
+  w.total_blocks = (uint32_t)total_blocks;
+  // rounds, launched back to back in bunches; between bunches the host looks at the flags: a round that changed no
+  // hand-over state means the states are the fixed point (and the counts of the lanes' last walks belong to it)
+  uint32_t *flags_host = (uint32_t *)(wh + o_up_end);
+  constexpr int FIRST_BUNCH = 8;
+  int round = 0;
+  if (defer) {
+    // mijpeg_submit_batch_device: nobody looks at the flags between the rounds.  Enough rounds for the states to settle are
+    // launched in one go -- a round in which no lane is dirty costs a few microseconds (its workgroups leave before they
+    // load their tables) -- and whoever waits for the batch checks that the last one changed nothing (finish_batch).
+    const int rounds = std::min(MAX_ROUNDS, sub_bytes >= 512 ? 16 : sub_bytes >= 256 ? 24 : 40);
+    while (round < rounds) {
+      w.round = (uint32_t)++round;
+      if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+    }
+    HIP_TRY(d, hipMemcpyAsync(flags_host, wd + o_flags, (size_t)(MAX_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, d->stream));
+    d->pend_walk_round = round;
+    d->pend_walk_flags = flags_host;
+  }
+  for (; !defer;) {
+    const int upto = round == 0 ? FIRST_BUNCH : std::min(MAX_ROUNDS, round + 4);
+    while (round < upto) {
+      w.round = (uint32_t)++round;
+      if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+    }
+    HIP_TRY(d, hipMemcpyAsync(flags_host, wd + o_flags, (size_t)(MAX_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, d->stream));
+    HIP_TRY(d, hipStreamSynchronize(d->stream));
+    if (!flags_host[round]) break;
+    if (round == MAX_ROUNDS) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding did not settle");
+  }
+  d->walk_rounds = defer ? 1 : walk_rounds_needed(flags_host, round);
+  if (launch_huffman_walk_scan(w, n, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_scan_kernel launch");
+  // one interval size for the launch: the images share their geometry, hence their MCUs per virtual interval
+  int per = 0;
+  for (int i = 0; i < n; i++)
+    if (dwalk[(size_t)i]) per = dwalk[(size_t)i];
+  w.emit_every = (uint32_t)(per * B);
+  if (launch_huffman_walk(w, true, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+  d->walk_status_dev = w.walk_status;
+  return MIJPEG_OK;
+}
+
+// What the Huffman kernel left in the status words of n images: errors, and per image the range check that selects the
+// arithmetic flavour of the reconstruction (fast_arith / range_max).
+int evaluate_entropy_status(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const uint32_t *status_host)
+{
+  for (int i = 0; i < n; i++) {
+    const uint32_t *st = status_host + 8 * i;
+    // A DC prediction that leaves the 16-bit store (only damaged streams get there): the host decoder keeps 32-bit planes
+    if (st[0] == HUFF_ERR_OVERFLOW) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, DC_OVERFLOW);
+    // Damaged entropy coded data: which error the reference reports (or whether it decodes on after a resynchronisation)
+    // depends on its sequential walk; the host decoder restates that walk, the device decoder does not try to
+    if (st[0]) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the entropy coded data is damaged: the host decoder walks such streams like the reference does (DESIGN 4.0)");
+    mijpeg_info &f = hosts[i]->info;
+    f.fast_arith = 1;
+    for (int c = 0; c < f.components; c++) {
+      f.range_max[c] = (int32_t)std::min<uint32_t>(st[1 + c], 0x7fffffffu);
+      if (f.range_max[c] >= 16384) f.fast_arith = 0;
+    }
+    if (f.precision != 8) f.fast_arith = 0; // (as HostDecoder::decode has it: the fast flavour is derived for 8-bit frames; 12-bit kernels gate on range_max)
+  }
+  return MIJPEG_OK;
+}
+
+// Second-level tables of a device Huffman table: every code longer than the direct table's ten bits, grouped by its first
+// ten bits, in a 64-entry table indexed by the six bits that follow (entries as in the direct table: huff_dev_entry).  Codes
+// whose prefix finds no table left keep the direct entry HUFF_DEV_SUB | HUFF_DEV_NO_SUB: the kernels walk the canonical arrays
+// for those.
+static void fill_second_level(HuffDevTable &dst, const HuffTable &h, int ac)
+{
+  int prefix_of[HUFF_DEV_SUBTABLES], used = 0;
+  int code = 0, k = 0;
+  for (int l = 1; l <= 16; l++) {
+    for (int i = 0; i < h.counts[l - 1]; i++, code++, k++) {
+      if (l <= HUFF_DEV_LOOKAHEAD || k >= 256) continue;
+      if (code >= (1 << l)) return; // over-subscribed lengths: the host refuses such tables anyway
+      const int prefix = code >> (l - HUFF_DEV_LOOKAHEAD), rest = l - HUFF_DEV_LOOKAHEAD; // 1..6 bits behind the prefix
+      int t = 0;
+      while (t < used && prefix_of[t] != prefix) t++;
+      if (t == used) {
+        if (used == HUFF_DEV_SUBTABLES) continue;
+        prefix_of[used++] = prefix;
+        dst.fast[prefix] = (uint16_t)(HUFF_DEV_SUB | t);
+      }
+      const uint16_t e = (uint16_t)huff_dev_entry(l, h.values[k], ac);
+      const int first = (code & ((1 << rest) - 1)) << (6 - rest);
+      for (int j = 0; j < (1 << (6 - rest)); j++) dst.sub[t][first + j] = e;
+    }
+    code <<= 1;
+  }
+}
+
+// The host's decoder table in the device's form (huffman_dev.hpp): direct entries, second-level tables, the canonical arrays.
+// mode: 0 DC, 1 AC of a sequential scan, 2 AC of a progressive / refinement scan (huff_dev_entry).
+static void build_dev_table(HuffDevTable &dst, const HuffTable &src, int mode)
+{
+  memset(&dst, 0, sizeof(dst));
+  // the host's direct table ((length << 8) | symbol, 0 = a longer code or none) in the device's entry format
+  for (int x = 0; x < (1 << HUFF_DEV_LOOKAHEAD); x++) {
+    const uint16_t he = src.fast[x];
+    dst.fast[x] = he ? (uint16_t)huff_dev_entry(he >> 8, he & 0xffu, mode) : (uint16_t)(HUFF_DEV_SUB | HUFF_DEV_NO_SUB);
+  }
+  static const bool no_sub = getenv("MIJPEG_HUFF_NO_SUBTABLES") != nullptr; // A-B measurements: long codes walk the canonical arrays
+  if (!no_sub) fill_second_level(dst, src, mode);
+  memcpy(dst.maxcode, src.maxcode, sizeof(dst.maxcode));
+  memcpy(dst.valoff, src.valoff, sizeof(dst.valoff));
+  memcpy(dst.values, src.values, sizeof(dst.values));
+}
+
+// Entropy-decode n parsed images of identical frame geometry on the device, image i into coef_dev + i * frame_stride.
+// infos[i] receives fast_arith / range_max.  Returns MIJPEG_OK, MIJPEG_ERR_NOT_AVAILABLE (nothing touched) or an error.
+int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
+                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part, bool defer)
+{
+  const mijpeg_info &f0 = hosts[0]->info;
+  const Scan &s0 = hosts[0]->scans[0];
+  int64_t total_intervals = 0;
+  std::vector<int64_t> nints((size_t)n);
+  std::vector<std::unique_ptr<VirtualIntervals>> virt((size_t)n); // restart points planned by the host's walk ...
+  std::vector<int> dwalk((size_t)n, 0);                           // ... or MCUs per virtual interval when the device walks
+  d->walk_rounds = 0;
+  const bool device_walk = !(getenv("MIJPEG_DEVICE_WALK") && atoi(getenv("MIJPEG_DEVICE_WALK")) == 0);
+  const auto tb0 = std::chrono::steady_clock::now();
+  for (int i = 0; i < n; i++) {
+    const char *why = device_entropy_obstacle(*hosts[i], sizes[i], xt_part);
+    if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
+    const mijpeg_info &f = hosts[i]->info;
+    const Scan &s = hosts[i]->scans[0];
+    if (f.width != f0.width || f.height != f0.height || f.components != f0.components || memcmp(f.hsamp, f0.hsamp, sizeof(f.hsamp)) ||
+        memcmp(f.vsamp, f0.vsamp, sizeof(f.vsamp)))
+      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share width, height and sampling factors");
+    // ... and what the one reconstruction launch applies to all of them: the colour transformation (an Adobe marker may
+    // switch it off per image), the sample precision, being a JPEG XT stream or not
+    if (f.ycbcr != f0.ycbcr || f.precision != f0.precision || f.xt != f0.xt)
+      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share colour transformation and precision");
+    for (int k = 0; k < s.ncomp; k++)
+      if (s.sc[k].comp != s0.sc[k].comp) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share the component order of their scan");
+    const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
+    int64_t nint;
+    if (s.restart_interval > 0) {
+      nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
+      if (nint > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many restart intervals");
+      if ((int64_t)s.interval_begin.size() < nint)
+        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)");
+      const std::vector<uint8_t> &rst = hosts[i]->restart_codes(0);
+      for (int64_t k = 0; k + 1 < nint; k++)
+        if (rst[(size_t)k] != 0xd0 + (k & 7))
+          return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart markers out of sequence: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)");
+    } else {
+      // no restart markers: the host's self-synchronising walk finds exact restart points ("virtual intervals"),
+      // about 16 K of them, and the device decodes from there
+      const int per = (int)std::min<int64_t>(64, std::max<int64_t>(1, total_mcus / 16384));
+      if (total_mcus < 256 || s.ecs_end - s.ecs_begin < 4096)
+        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream without restart markers is too small for speculative decoding");
+      if (device_walk) { // the restart points are found on the device (huffman_walk_kernel); their number is known already
+        dwalk[(size_t)i] = per;
+        nint = (total_mcus + per - 1) / per;
+      } else {
+        virt[(size_t)i].reset(new VirtualIntervals());
+        if (hosts[i]->plan_virtual_intervals(0, per, 0, *virt[(size_t)i]))
+          return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream without restart markers did not lend itself to speculative decoding");
+        nint = (int64_t)virt[(size_t)i]->byte_off.size();
+      }
+    }
+    nints[(size_t)i] = nint;
+    total_intervals += nint;
+  }
+  if (min_intervals <= 0) min_intervals = 2048; // below this the device runs mostly idle
+  if (total_intervals < min_intervals || total_intervals > 0x7fffffff)
+    return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too few restart intervals to occupy the device");
+
+  HuffScanArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lanes = lanes_for(total_intervals);
+  a.waves_per_group = WAVES_PER_GROUP;
+  const int per_group = a.lanes * a.waves_per_group; // intervals of one workgroup
+  // Tables in LDS: components that bring the same Huffman code (Cb and Cr practically always do) share one copy -- the
+  // workgroup's LDS footprint decides how many of them a CU holds.  The sharing pattern is that of image 0 and must hold
+  // for every image of the launch; the device walk indexes its tables by component and keeps one per component.
+  int tab_slot[MIJPEG_MAX_COMPONENTS][2];
+  int ntab = 0;
+  {
+    bool walk_any = false;
+    for (int i = 0; i < n; i++) walk_any |= dwalk[(size_t)i] > 0;
+    bool share = !walk_any;
+    for (int pass = 0; pass < 2; pass++) {
+      ntab = 0;
+      for (int k = 0; k < s0.ncomp; k++)
+        for (int t = 0; t < 2; t++) {
+          tab_slot[k][t] = -1;
+          for (int j = 0; j < k && share && tab_slot[k][t] < 0; j++)
+            if ((t ? s0.ac[k].same_code(s0.ac[j]) : s0.dc[k].same_code(s0.dc[j]))) tab_slot[k][t] = tab_slot[j][t];
+          if (tab_slot[k][t] < 0) tab_slot[k][t] = ntab++;
+        }
+      if (!share) break;
+      bool holds = true; // ... in every image?
+      for (int i = 1; i < n && holds; i++) {
+        const Scan &s = hosts[i]->scans[0];
+        for (int k = 0; k < s.ncomp && holds; k++)
+          for (int j = 0; j < k && holds; j++) {
+            if (tab_slot[k][0] == tab_slot[j][0] && !s.dc[k].same_code(s.dc[j])) holds = false;
+            if (tab_slot[k][1] == tab_slot[j][1] && !s.ac[k].same_code(s.ac[j])) holds = false;
+          }
+      }
+      if (holds) break;
+      share = false;
+    }
+  }
+  const size_t table_blob = (size_t)ntab * sizeof(HuffDevTable) + sizeof(HuffDevAux);
+
+  // device buffer: [streams, each padded][ibegin][iend][iskip][ipred][tables of every image][images][groups][status]
+  // What travels to the device is the entropy coded data of every image WITHOUT its byte stuffing and without the markers,
+  // one restart interval behind the other (HostDecoder::unstuff_piece; the marker search counted what leaves): the kernels
+  // address it by plain bit positions (huffman.hip, DevBits).
+  std::vector<size_t> usize((size_t)n);
+  std::vector<size_t> stream_off;
+  const size_t stream_bytes = stream_slots(sizes, n, stream_off);
+  int64_t n_groups = 0;
+  for (int i = 0; i < n; i++) {
+    usize[(size_t)i] = hosts[i]->scans[0].unstuffed_size;
+    if (usize[(size_t)i] >= ((size_t)1 << 28)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "entropy coded segment too large for the device decoder's bit addresses");
+    if (usize[(size_t)i] > sizes[i]) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "entropy coded segment larger than its stream");
+    if (!dwalk[(size_t)i] && !virt[(size_t)i] && (int64_t)hosts[i]->scans[0].interval_ubegin.size() < nints[(size_t)i])
+      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart intervals missing");
+    n_groups += (nints[(size_t)i] + per_group - 1) / per_group;
+  }
+  if (stream_bytes > 0xfffffff0ull || n_groups > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "batch too large for one launch");
+  bool any_virtual = false, any_dwalk = false;
+  for (int i = 0; i < n; i++) {
+    any_virtual |= virt[(size_t)i] != nullptr || dwalk[(size_t)i] > 0;
+    any_dwalk |= dwalk[(size_t)i] > 0;
+  }
+  // offsets behind the streams: in the device buffer at dp, in pinned staging at hp
+  Layout L;
+  const size_t T = (size_t)total_intervals;
+  const size_t off_ib = L.take(T * 4), off_ie = L.take(T * 4), off_isk = L.take(any_virtual ? T : 0), off_ipr = L.take(any_virtual ? T * 8 : 0);
+  const size_t off_tab = L.take((size_t)n * table_blob), off_img = L.take((size_t)n * sizeof(HuffImage)), off_grp = L.take((size_t)n_groups * sizeof(HuffGroup));
+  const size_t status_bytes = (size_t)n * 32, off_status = L.take(status_bytes);
+  int rc = ensure_entropy_buffers(d, stream_bytes, L.end);
+  if (rc) return rc;
+  uint8_t *const hp = d->ent_host, *const dp = d->ent_dev + stream_bytes;
+  uint32_t *ib = (uint32_t *)(hp + off_ib), *ie = (uint32_t *)(hp + off_ie);
+  HuffImage *images = (HuffImage *)(hp + off_img);
+  HuffGroup *groups = (HuffGroup *)(hp + off_grp);
+  int64_t first = 0, g = 0;
+  bool needs_clear = false;
+  for (int i = 0; i < n; i++) {
+    const mijpeg_info &f = hosts[i]->info;
+    const Scan &s = hosts[i]->scans[0];
+    const int64_t nint = nints[(size_t)i];
+    if (dwalk[(size_t)i]) { // filled in by the EMIT walk on the device
+      for (int64_t k = 0; k < nint; k++) { ib[first + k] = 0; ie[first + k] = (uint32_t)usize[(size_t)i]; }
+      memset(hp + off_isk + first, 0, (size_t)nint);
+      memset(hp + off_ipr + (size_t)first * 8, 0, (size_t)nint * 8);
+    } else if (virt[(size_t)i]) {
+      // the host's walk reports stream offsets: into the copy's (stuffed pairs in front of each, counted as the offsets go up)
+      const VirtualIntervals &vi = *virt[(size_t)i];
+      uint8_t *isk = hp + off_isk;
+      int16_t *ipr = (int16_t *)(hp + off_ipr);
+      const uint8_t *base = s.base ? s.base : datas[i];
+      size_t at = s.ecs_begin, pairs = 0;
+      for (int64_t k = 0; k < nint; k++) {
+        const size_t pos = vi.byte_off[(size_t)k];
+        while (at < pos) {
+          const uint8_t *q = (const uint8_t *)memchr(base + at, 0xff, pos - at);
+          if (!q) break;
+          at = (size_t)(q - base);
+          if (base[at + 1] == 0x00) { pairs++; at += 2; }
+          else at++;
+        }
+        at = std::max(at, pos);
+        ib[first + k] = (uint32_t)(pos - s.ecs_begin - pairs);
+        ie[first + k] = (uint32_t)usize[(size_t)i];
+        isk[first + k] = vi.bit_skip[(size_t)k];
+        memcpy(ipr + (first + k) * 4, &vi.pred[(size_t)k * 4], 8);
+      }
+    } else {
+      memcpy(ib + first, s.interval_ubegin.data(), (size_t)nint * 4);
+      memcpy(ie + first, s.interval_uend.data(), (size_t)nint * 4);
+      if (any_virtual) memset(hp + off_isk + first, 0, (size_t)nint);
+    }
+    HuffDevTable *tabs = (HuffDevTable *)(hp + off_tab + (size_t)i * table_blob);
+    HuffDevAux *aux = (HuffDevAux *)(tabs + ntab);
+    // images that bring the tables of the image in front of them (every frame of a camera or an encoder run does) share its
+    // blob: nothing to build, and the workgroups of both read the same lines
+    bool same_tables = i > 0;
+    if (same_tables) {
+      const mijpeg_info &fp = hosts[i - 1]->info;
+      const Scan &sp = hosts[i - 1]->scans[0];
+      for (int k = 0; k < s.ncomp && same_tables; k++) {
+        const int c = s.sc[k].comp;
+        same_tables = s.dc[k].same_code(sp.dc[k]) && s.ac[k].same_code(sp.ac[k]) &&
+                      !memcmp(f.quant[f.quant_index[c]], fp.quant[fp.quant_index[c]], sizeof(f.quant[0]));
+      }
+    }
+    memset(aux, 0, sizeof(*aux));
+    for (int k = 0; k < s.ncomp && !same_tables; k++) {
+      const HuffTable *src[2] = {&s.dc[k], &s.ac[k]};
+      for (int t = 0; t < 2; t++) {
+        build_dev_table(tabs[tab_slot[k][t]], *src[t], t);
+      }
+      const int c = s.sc[k].comp;
+      const uint16_t *delta = f.quant[f.quant_index[c]];
+      for (int z = 0; z < 80; z++) {
+        const uint32_t pos = scan_order()[z];
+        aux->zq[k][z] = ((uint32_t)delta[pos] << 16) | (pos * 2);
+      }
+    }
+    HuffImage &im = images[i];
+    im.stream_off = (uint32_t)stream_off[(size_t)i];
+    im.first_interval = (uint32_t)first;
+    im.n_intervals = (int32_t)nint;
+    im.restart_interval = dwalk[(size_t)i] ? dwalk[(size_t)i] : virt[(size_t)i] ? virt[(size_t)i]->mcus_per_interval : s.restart_interval;
+    im.virt = (virt[(size_t)i] || dwalk[(size_t)i]) ? 1u : 0u;
+    im.reserved = 0;
+    im.total_mcus = s.mcus_x * s.mcus_y;
+    im.mcus_x = s.mcus_x;
+    im.coef_base = (int64_t)i * frame_stride;
+    im.table_off = same_tables ? images[i - 1].table_off : (uint32_t)((size_t)i * table_blob);
+    im.status_off = (uint32_t)(i * 8);
+    for (int64_t k = 0; k < nint; k += per_group) {
+      groups[g].image = (uint32_t)i;
+      groups[g].first_interval = (uint32_t)k;
+      g++;
+    }
+    first += nint;
+    // an interleaved scan writes every block of every plane; a single-component scan of a frame whose only component
+    // has sampling factors > 1 leaves the MCU padding blocks untouched (they must read as zero)
+    if (s.ncomp == 1 && (s.mcus_x != f.blocks_w[s.sc[0].comp] || s.mcus_y != f.blocks_h[s.sc[0].comp])) needs_clear = true;
+  }
+  for (int k = 0; k < s0.ncomp; k++) {
+    const int c = s0.sc[k].comp;
+    a.comp_of[k] = c;
+    a.hs[k] = s0.ncomp > 1 ? f0.hsamp[c] : 1;
+    a.vs[k] = s0.ncomp > 1 ? f0.vsamp[c] : 1;
+    a.bw[k] = f0.blocks_w[c];
+    a.coef_off[k] = f0.coef_offset[c];
+    a.dc_tab[k] = tab_slot[k][0];
+    a.ac_tab[k] = tab_slot[k][1];
+  }
+  a.data = d->ent_dev;
+  a.ibegin = (const uint32_t *)(dp + off_ib);
+  a.iend = (const uint32_t *)(dp + off_ie);
+  a.iskip = dp + off_isk;
+  a.ipred = (const int16_t *)(dp + off_ipr);
+  a.images = (const HuffImage *)(dp + off_img);
+  a.groups = (const HuffGroup *)(dp + off_grp);
+  a.n_groups = (int32_t)n_groups;
+  a.ncomp = s0.ncomp;
+  a.ntables = ntab;
+  a.tables = dp + off_tab;
+  a.coef = coef_dev;
+  a.status = (uint32_t *)(dp + off_status);
+  const TraceMarks mark{"mijpeg"};
+  const auto tb1 = mark.t0;
+  QuiesceOnError guard{d};
+  guard.armed = true;
+  HIP_TRY(d, hipMemcpyAsync(dp, hp, off_status, hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(d, hipMemsetAsync(dp + off_status, 0, status_bytes, d->stream));
+  if (needs_clear) HIP_TRY(d, hipMemsetAsync(coef_dev, 0, (size_t)n * (size_t)frame_stride * sizeof(int16_t), d->stream));
+  // (a deferred batch always goes through the pinned gathering area: the caller's bytes are only read during the call)
+  const bool small = !defer && (n == 1 || stream_bytes < ((size_t)8 << 20));
+  if ((rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, stream_bytes))) return rc;
+  // the unstuffing gather of images [g0, g1) into the pinned area (images whose marker search wrote the copy already -- a
+  // batch's workers do, set_unstuff_sink -- have nothing left to do)
+  Gather gather;
+  auto gather_images = [&](int g0, int g1) {
+    for (int i = g0; i < g1; i++)
+      if (hosts[i]->scans[0].unstuffed_at != d->stage_host + stream_off[(size_t)i]) gather.add(hosts[i], 0, d->stage_host + stream_off[(size_t)i]);
+    gather.run();
+  };
+  // streams without restart markers: the walk finds the intervals of every image, then one launch decodes them all
+  auto walk_and_decode = [&]() {
+    const int wrc = device_walk_images(d, hosts, n, dwalk, a, (const HuffImage *)(dp + off_img), (uint32_t *)(dp + off_ib), dp + off_isk,
+                                       (int16_t *)(dp + off_ipr), images, usize, defer);
+    if (wrc) return wrc;
+    mark("device walk enqueued");
+    if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+    return MIJPEG_OK;
+  };
+  if (small) {
+    gather_images(0, n);
+    // (only what the copies occupy: a slot is as large as its stream, headers and all)
+    for (int i = 0; i < n; i++)
+      HIP_TRY(d, hipMemcpyAsync(d->ent_dev + stream_off[(size_t)i], d->stage_host + stream_off[(size_t)i], ((usize[(size_t)i] + 15) & ~(size_t)15) + HUFF_STREAM_PAD,
+                                hipMemcpyHostToDevice, d->stream));
+    if (any_dwalk) {
+      if ((rc = walk_and_decode())) return rc;
+    } else if (launch_huffman_scan(a, d->stream))
+      return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+  } else {
+    // large batches, in up to eight groups of images: the pool threads gather a group's streams into pinned memory, its
+    // DMA runs on a copy stream while the next group is gathered and while the kernel decodes the previous one
+    mark("staging buffer ready");
+    // Images per upload + launch.  A launch is latency-bound (the serial symbol chain of its longest restart interval,
+    // ~0.3 ms) until it holds several waves per SIMD: ~128 K restart intervals; more, smaller launches only pay when the
+    // batch is so large that the upload of one part hides behind the decode of another (profiles/r02/batch4k_*.txt:
+    // 32 x 4K frames in one launch 0.80 ms, in eight launches of four 8 x 0.39 ms).
+    const int64_t per_image = std::max<int64_t>(1, total_intervals / n);
+    const int groups_of = (int)std::max<int64_t>(std::max(4, (n + 7) / 8), (131072 + per_image - 1) / per_image);
+    if ((rc = prepare_copy_stream(d, (size_t)((n + groups_of - 1) / groups_of)))) return rc;
+    int64_t wg0 = 0;
+    for (int gi = 0, g0 = 0; g0 < n; g0 += groups_of, gi++) {
+      const int g1 = std::min(n, g0 + groups_of);
+      gather_images(g0, g1);
+      const size_t b0 = stream_off[(size_t)g0], b1 = g1 < n ? stream_off[(size_t)g1] : stream_bytes;
+      HIP_TRY(d, hipMemcpyAsync(d->ent_dev + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
+      HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)gi], d->copy_stream));
+      HIP_TRY(d, hipStreamWaitEvent(d->stream, d->copy_events[(size_t)gi], 0));
+      if (any_dwalk) continue; // the walk below covers all images at once
+      int64_t wg1 = wg0;
+      for (int i = g0; i < g1; i++) wg1 += (nints[(size_t)i] + per_group - 1) / per_group;
+      HuffScanArgs part = a; // the workgroups of this group's images
+      part.groups = a.groups + wg0;
+      part.n_groups = (int32_t)(wg1 - wg0);
+      if (launch_huffman_scan(part, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+      wg0 = wg1;
+    }
+    mark("groups gathered + enqueued");
+    if (any_dwalk && (rc = walk_and_decode())) return rc;
+  }
+  uint32_t *status_host = (uint32_t *)(hp + off_status);
+  uint32_t *walk_status_host = (uint32_t *)d->walk_host; // the walk's staging buffer is free again
+  if (any_dwalk) HIP_TRY(d, hipMemcpyAsync(walk_status_host, d->walk_status_dev, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
+  if ((rc = read_back_status(d, status_host, dp + off_status, status_bytes))) return rc;
+  d->phase_prepare = std::chrono::duration<double>(tb1 - tb0).count(); // interval tables, Huffman tables
+  mark("status copies enqueued");
+  if (!any_dwalk) d->pend_walk_round = 0;
+  if (defer) { // mijpeg_submit_batch_device: the caller waits later (finish_batch)
+    guard.armed = false;
+    d->pend_n = n;
+    d->pend_status = status_host;
+    d->pend_walk_status = any_dwalk ? walk_status_host : nullptr;
+    d->pend_t0 = tb1;
+    d->phase_device = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count(); // so far: gathering + enqueueing
+    return MIJPEG_OK;
+  }
+  HIP_TRY(d, hipStreamSynchronize(d->stream));
+  guard.armed = false; // (everything of this call is behind the stream's last copy)
+  if (any_dwalk && (rc = walk_verdict(d, walk_status_host, n))) return rc;
+  d->phase_device = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count();  // upload + kernel + status
+  return evaluate_entropy_status(d, hosts, n, status_host);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Progressive frames and frames with hidden refinement scans on the device (huffman_prog_kernel)
+// ------------------------------------------------------------------------------------------------
+// nullptr: every scan of the frame can be decoded one restart interval per lane.
+const char *multiscan_obstacle(const HostDecoder &h, bool xt_part, bool residual_frame)
+{
+  const mijpeg_info &f = h.info;
+  if (h.needs_sequential())
+    return "on-device entropy decoding: the stream is damaged; the host decoder walks it with the reference's resynchronisation (entropyparser.cpp:117-201)";
+  if (f.xt && !xt_part) return "on-device entropy decoding: not for this JPEG XT stream";
+  if (!h.residual_merged()) return "on-device entropy decoding: the legacy codestream has no EOI marker (the host decoder decides what is merged)";
+  if (h.verdict_pending()) return "on-device entropy decoding: the file's verdict is the host decoder's (residual codestream header / tables looked up at the first request)";
+  if (f.dnl) return "on-device entropy decoding: frames whose height arrives in a DNL marker are decoded on the host";
+  // (12-bit frames: the same int16 store as the host decoder's, a coefficient beyond it sends the frame there like everywhere)
+  if (f.precision < 8 || f.precision > 12 || (xt_part && !residual_frame && f.precision != 8))
+    return "on-device entropy decoding: frames of 8 to 12 bits (JPEG XT: an 8-bit legacy frame)";
+  if (h.scans.empty() || h.scans.size() > 4096) return "on-device entropy decoding: no scans, or more than the device path plans for";
+  if (!h.every_component_seen()) return "on-device entropy decoding: a component appears in no scan (the host decoder supplies its stand-in)";
+  for (int c = 0; c < f.components; c++)
+    if (f.hsamp[c] > 4 || f.vsamp[c] > 4) return "on-device entropy decoding: MCUs of more than 4 x 4 blocks of a component are decoded on the host";
+  for (size_t si = 0; si < h.scans.size(); si++) {
+    const Scan &s = h.scans[si];
+    if (s.residual) return "on-device entropy decoding: the residual scan types of part 8 are decoded on the host";
+    if (s.ncomp < 1 || (s.se > 0 && s.ss > 0 && s.ncomp != 1)) return "on-device entropy decoding: scan layout";
+    if (s.ah > 0 && !s.refinement) return "on-device entropy decoding: scan layout";
+    if (s.unstuffed_size >= ((size_t)1 << 28)) return "on-device entropy decoding: entropy coded segment too large for the device decoder's bit addresses";
+    const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
+    if (total_mcus < 1 || total_mcus > 0x7fffffff) return "on-device entropy decoding: scan layout";
+    if (s.restart_interval > 0) {
+      const int64_t nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
+      if ((int64_t)s.interval_begin.size() < nint || (int64_t)s.interval_ubegin.size() < nint)
+        return "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
+      const std::vector<uint8_t> &rst = h.restart_codes(si);
+      if ((int64_t)rst.size() + 1 < nint) return "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
+      for (int64_t k = 0; k + 1 < nint; k++)
+        if (rst[(size_t)k] != 0xd0 + (k & 7))
+          return "restart markers out of sequence: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
+    } else {
+      // One interval: one lane decodes the whole scan.  First passes could be cut into pieces that fall into step with the real
+      // decoder; an AC refinement scan cannot -- the bits a block takes depend on which block it is -- so scans
+      // without restart markers are left to the host's pipeline of scans unless they are small
+      if (s.interval_ubegin.empty()) return "on-device entropy decoding: scan without data";
+      if (s.unstuffed_size > ((size_t)24 << 10))
+        return "on-device entropy decoding: progressive / refinement scans without restart markers are serial by construction (refinementscan.cpp:584-700): host";
+    }
+    for (int k = 0; k < s.ncomp; k++) {
+      if (s.ss == 0 && s.ah == 0 && !s.dc[k].built) return "on-device entropy decoding: a Huffman table the scan names does not exist";
+      if (s.se > 0 && !s.ac[k].built) return "on-device entropy decoding: a Huffman table the scan names does not exist";
+    }
+  }
+  return nullptr;
+}
+
+// All scans of the given frames (one file: a progressive picture, or the two frames of a JPEG XT file): upload of the entropy
+// coded data without its stuffing, planes cleared, the scans launched level by level (scans that share a component one after
+// the other, the rest side by side), range pass.  MIJPEG_ERR_NOT_AVAILABLE: the host decoder's.
+int device_entropy_multiscan(mijpeg_decoder *d, const MultiScanFrame *frames, int nframes, int min_intervals)
+{
+  struct Item { int frame; size_t scan; int level; int64_t nint; size_t stream_off; size_t table_off; int ntab; int dc_tab[4], ac_tab[4]; int64_t first; };
+  std::vector<Item> items;
+  const TraceMarks mark{"mijpeg multiscan"};
+  size_t table_bytes = 0;
+  int64_t total_intervals = 0;
+  int max_tables = 1;
+  std::vector<int> frame_levels((size_t)nframes, 0);
+  for (int fi = 0; fi < nframes; fi++) {
+    const HostDecoder &h = *frames[fi].h;
+    std::vector<int> level(h.scans.size(), 0);
+    for (size_t j = 0; j < h.scans.size(); j++) {
+      const Scan &b = h.scans[j];
+      // (a scan of the AC kind writes whole blocks back: two scans that share a component never run side by side)
+      for (size_t i = 0; i < j; i++) {
+        const Scan &a = h.scans[i];
+        bool common = false;
+        for (int ka = 0; ka < a.ncomp; ka++)
+          for (int kb = 0; kb < b.ncomp; kb++) common |= a.sc[ka].comp == b.sc[kb].comp;
+        if (common) level[j] = std::max(level[j], level[i] + 1);
+      }
+      Item it;
+      memset(&it, 0, sizeof(it));
+      it.frame = fi;
+      it.scan = j;
+      it.level = level[j];
+      const int64_t total_mcus = (int64_t)b.mcus_x * b.mcus_y;
+      it.nint = b.restart_interval > 0 ? (total_mcus + b.restart_interval - 1) / b.restart_interval : 1;
+      it.table_off = table_bytes;
+      for (int k = 0; k < b.ncomp; k++) {
+        it.dc_tab[k] = it.ac_tab[k] = 0;
+        if (b.ss == 0 && b.ah == 0) it.dc_tab[k] = it.ntab++;
+        if (b.se > 0) it.ac_tab[k] = it.ntab++;
+      }
+      table_bytes += (size_t)it.ntab * sizeof(HuffDevTable);
+      max_tables = std::max(max_tables, it.ntab);
+      it.first = total_intervals;
+      total_intervals += it.nint;
+      frame_levels[(size_t)fi] = std::max(frame_levels[(size_t)fi], level[j] + 1);
+      items.push_back(it);
+    }
+  }
+  // The entropy coded data lies in the upload level by level: what the first launches read goes up first, and the rest is
+  // gathered and uploaded while they run (level_end[l]: end of level l's bytes).
+  int n_levels = 0;
+  for (int fi = 0; fi < nframes; fi++) n_levels = std::max(n_levels, frame_levels[(size_t)fi]);
+  std::vector<size_t> level_end((size_t)n_levels, 0);
+  Layout streams;
+  for (int lv = 0; lv < n_levels; lv++) {
+    for (Item &it : items)
+      if (it.level == lv) it.stream_off = streams.take(frames[it.frame].h->scans[it.scan].unstuffed_size + HUFF_STREAM_PAD);
+    level_end[(size_t)lv] = streams.end;
+  }
+  const size_t stream_bytes = streams.end;
+  if (stream_bytes > 0xfffffff0ull || total_intervals > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "file too large for one device decode");
+  // the largest launch decides whether the device is worth the trip ("auto"); every launch -- the scans of one level of one
+  // frame -- picks how many lanes of a wave decode by its own number of intervals: fewer lanes = more waves, less divergence
+  const int waves = WAVES_PER_GROUP;
+  int64_t widest = 0, n_groups = 0;
+  std::vector<std::vector<int>> level_lanes((size_t)nframes);
+  for (int fi = 0; fi < nframes; fi++)
+    for (int lv = 0; lv < frame_levels[(size_t)fi]; lv++) {
+      int64_t n = 0;
+      for (const Item &it : items)
+        if (it.frame == fi && it.level == lv) n += it.nint;
+      widest = std::max(widest, n);
+      const int lanes = lanes_for(n);
+      level_lanes[(size_t)fi].push_back(lanes);
+      for (const Item &it : items)
+        if (it.frame == fi && it.level == lv) n_groups += (it.nint + lanes * waves - 1) / (lanes * waves);
+    }
+  if (min_intervals <= 0) min_intervals = 2048;
+  if (widest < min_intervals) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too few restart intervals to occupy the device");
+  // device buffer: [streams][ibegin][iend][tables][scans][groups][status: 8 dwords per frame]; offsets behind the streams: in
+  // the device buffer at dp, in pinned staging at hp
+  Layout L;
+  const size_t off_ib = L.take((size_t)total_intervals * 4), off_ie = L.take((size_t)total_intervals * 4), off_tab = L.take(table_bytes);
+  const size_t off_scan = L.take(items.size() * sizeof(ProgScanDev)), off_grp = L.take((size_t)n_groups * sizeof(ProgGroup));
+  const size_t status_bytes = (size_t)nframes * 32, off_status = L.take(status_bytes);
+  int rc = ensure_entropy_buffers(d, stream_bytes, L.end);
+  if (rc) return rc;
+  rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, stream_bytes);
+  if (rc) return rc;
+  uint8_t *const hp = d->ent_host, *const dp = d->ent_dev + stream_bytes;
+  uint32_t *ib = (uint32_t *)(hp + off_ib), *ie = (uint32_t *)(hp + off_ie);
+  ProgScanDev *sd = (ProgScanDev *)(hp + off_scan);
+  ProgGroup *groups = (ProgGroup *)(hp + off_grp);
+  // groups in launch order: frame, level, scan
+  struct Launch { int frame, level; int64_t g0, groups; };
+  std::vector<Launch> launches;
+  int64_t g = 0;
+  for (int fi = 0; fi < nframes; fi++)
+    for (int lv = 0; lv < frame_levels[(size_t)fi]; lv++) {
+      const int64_t g0 = g;
+      const int per_group = level_lanes[(size_t)fi][(size_t)lv] * waves;
+      for (size_t ii = 0; ii < items.size(); ii++) {
+        const Item &it = items[ii];
+        if (it.frame != fi || it.level != lv) continue;
+        for (int64_t k = 0; k < it.nint; k += per_group) {
+          groups[g].scan = (uint32_t)ii;
+          groups[g].first_interval = (uint32_t)k;
+          g++;
+        }
+      }
+      if (g > g0) launches.push_back(Launch{fi, lv, g0, g - g0});
+    }
+  for (size_t ii = 0; ii < items.size(); ii++) {
+    const Item &it = items[ii];
+    const HostDecoder &h = *frames[it.frame].h;
+    const mijpeg_info &f = h.info;
+    const Scan &s = h.scans[it.scan];
+    ProgScanDev &o = sd[ii];
+    memset(&o, 0, sizeof(o));
+    o.stream_off = (uint32_t)it.stream_off;
+    o.first_interval = (uint32_t)it.first;
+    o.n_intervals = (int32_t)it.nint;
+    o.total_mcus = s.mcus_x * s.mcus_y;
+    o.restart_interval = s.restart_interval > 0 ? s.restart_interval : o.total_mcus;
+    o.mcus_x = s.mcus_x;
+    o.ncomp = s.ncomp;
+    o.ntables = it.ntab;
+    o.table_off = (uint32_t)it.table_off;
+    o.ss = s.ss; o.se = s.se; o.ah = s.ah; o.al = s.al;
+    o.runs_legal = s.progressive_run ? 1 : 0;
+    HuffDevTable *tabs = (HuffDevTable *)(hp + off_tab + it.table_off);
+    for (int k = 0; k < s.ncomp; k++) {
+      const int c = s.sc[k].comp;
+      o.comp[k] = c;
+      o.hs[k] = s.ncomp > 1 ? f.hsamp[c] : 1;
+      o.vs[k] = s.ncomp > 1 ? f.vsamp[c] : 1;
+      o.bw[k] = f.blocks_w[c];
+      o.coef_off[k] = f.coef_offset[c] / (f.coef_wide ? 2 : 1);
+      o.dc_tab[k] = it.dc_tab[k];
+      o.ac_tab[k] = it.ac_tab[k];
+      if (s.ss == 0 && s.ah == 0) build_dev_table(tabs[it.dc_tab[k]], s.dc[k], 0);
+      if (s.se > 0) build_dev_table(tabs[it.ac_tab[k]], s.ac[k], 2);
+    }
+    memcpy(ib + it.first, s.interval_ubegin.data(), (size_t)it.nint * sizeof(uint32_t)); // (multiscan_obstacle: both lists hold nint entries at least)
+    memcpy(ie + it.first, s.interval_uend.data(), (size_t)it.nint * sizeof(uint32_t));
+  }
+  mark("tables + intervals");
+  // The entropy coded data of every scan without its stuffing, gathered by the pool in two goes: what the first launches read
+  // (level 0 of every frame), then the rest -- while the copy engine brings up the first part and the first launches run.
+  // Uploads on the copy stream, one event per level; the frames' launches wait for their level's event.
+  Gather gather;
+  auto gather_levels = [&](int lv0, int lv1) {
+    for (const Item &it : items)
+      if (it.level >= lv0 && it.level < lv1) gather.add(frames[it.frame].h, it.scan, d->stage_host + it.stream_off);
+    gather.run();
+  };
+  QuiesceOnError guard{d};
+  guard.armed = true;
+  if ((rc = prepare_copy_stream(d, (size_t)n_levels))) return rc;
+  auto upload_levels = [&](int lv0, int lv1) -> int {
+    for (int lv = lv0; lv < lv1; lv++) {
+      const size_t b0 = lv ? level_end[(size_t)lv - 1] : 0, b1 = level_end[(size_t)lv];
+      if (lv == 0) HIP_TRY(d, hipMemcpyAsync(dp, hp, off_status, hipMemcpyHostToDevice, d->copy_stream));
+      if (b1 > b0) HIP_TRY(d, hipMemcpyAsync(d->ent_dev + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
+      HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)lv], d->copy_stream));
+    }
+    return 0;
+  };
+  ProgArgs a;
+  memset(&a, 0, sizeof(a));
+  a.data = d->ent_dev;
+  a.ibegin = (const uint32_t *)(dp + off_ib);
+  a.iend = (const uint32_t *)(dp + off_ie);
+  a.scans = (const ProgScanDev *)(dp + off_scan);
+  a.waves_per_group = waves;
+  a.max_tables = max_tables;
+  a.tables = dp + off_tab;
+  // the two frames of a JPEG XT file share nothing: the second one's launches go to a stream of their own
+  hipStream_t second = d->stream;
+  if (nframes > 1) {
+    if (!d->ms_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->ms_stream, hipStreamNonBlocking));
+    if (!d->ms_ready) HIP_TRY(d, hipEventCreateWithFlags(&d->ms_ready, hipEventDisableTiming));
+    if (!d->ms_done) HIP_TRY(d, hipEventCreateWithFlags(&d->ms_done, hipEventDisableTiming));
+    second = d->ms_stream;
+  }
+  auto launch_levels = [&](int lv0, int lv1) -> int {
+    for (const Launch &l : launches) {
+      const int fi = l.frame, lv = l.level;
+      if (lv < lv0 || lv >= lv1) continue;
+      hipStream_t st = fi == 0 ? d->stream : second;
+      HIP_TRY(d, hipStreamWaitEvent(st, d->copy_events[(size_t)lv], 0));
+      a.groups = (const ProgGroup *)(dp + off_grp) + l.g0;
+      a.n_groups = (int32_t)l.groups;
+      a.lanes = level_lanes[(size_t)fi][(size_t)lv];
+      a.wide = frames[fi].wide ? 1 : 0;
+      a.coef = (void *)(d->coef_dev + frames[fi].base16);
+      a.status = (uint32_t *)(dp + off_status) + 8 * fi;
+      if (launch_huffman_prog(a, st)) return hip_fail(d, hipGetLastError(), "huffman_prog_kernel launch");
+    }
+    return 0;
+  };
+  // where to cut: behind the first level that brings a quarter of the bytes (a progressive frame's DC scan alone is over before
+  // anything could hide behind it); no cut when that is the last level
+  int cut = n_levels;
+  for (int lv = 0; lv + 1 < n_levels; lv++)
+    if (level_end[(size_t)lv] * 4 >= stream_bytes) { cut = lv + 1; break; }
+  gather_levels(0, cut);
+  mark("first levels gathered");
+  if ((rc = upload_levels(0, cut))) return rc;
+  HIP_TRY(d, hipMemsetAsync(dp + off_status, 0, status_bytes, d->stream));
+  if (nframes > 1) { // (behind whatever the object's stream still does with the planes, and the cleared status words)
+    HIP_TRY(d, hipEventRecord(d->ms_ready, d->stream));
+    HIP_TRY(d, hipStreamWaitEvent(second, d->ms_ready, 0));
+  }
+  // coefficients accumulate over the scans: the planes start out as zeros (coding/blockrow.cpp:77-87)
+  for (int fi = 0; fi < nframes; fi++) {
+    const mijpeg_info &f = frames[fi].h->info;
+    int64_t count = 0;
+    for (int c = 0; c < f.components; c++) count += (int64_t)f.blocks_w[c] * f.blocks_h[c] * 64;
+    HIP_TRY(d, hipMemsetAsync(d->coef_dev + frames[fi].base16, 0, (size_t)count * (frames[fi].wide ? 4 : 2), fi == 0 ? d->stream : second));
+  }
+  if ((rc = launch_levels(0, cut))) return rc;
+  if (cut < n_levels) {
+    gather_levels(cut, n_levels);
+    mark("other levels gathered");
+    if ((rc = upload_levels(cut, n_levels))) return rc;
+    if ((rc = launch_levels(cut, n_levels))) return rc;
+  }
+  if (second != d->stream) {
+    HIP_TRY(d, hipEventRecord(d->ms_done, second));
+    HIP_TRY(d, hipStreamWaitEvent(d->stream, d->ms_done, 0));
+  }
+  for (int fi = 0; fi < nframes; fi++) {
+    const mijpeg_info &f = frames[fi].h->info;
+    CoefRangeArgs r;
+    memset(&r, 0, sizeof(r));
+    r.coef = (const void *)(d->coef_dev + frames[fi].base16);
+    r.wide = frames[fi].wide ? 1 : 0;
+    r.ncomp = f.components;
+    for (int c = 0; c < f.components; c++) {
+      r.coef_off[c] = f.coef_offset[c] / (f.coef_wide ? 2 : 1);
+      r.nblocks[c] = (int64_t)f.blocks_w[c] * f.blocks_h[c];
+      memcpy(r.q[c], f.quant[f.quant_index[c]], sizeof(r.q[c]));
+    }
+    r.status = (uint32_t *)(dp + off_status) + 8 * fi;
+    if (launch_coef_range(r, d->stream)) return hip_fail(d, hipGetLastError(), "coef_range_kernel launch");
+  }
+  uint32_t *status_host = (uint32_t *)(hp + off_status);
+  if ((rc = read_back_status(d, status_host, dp + off_status, status_bytes))) return rc;
+  mark("launches enqueued");
+  HIP_TRY(d, hipStreamSynchronize(d->stream));
+  guard.armed = false; // (the second frame's stream and the copy stream are behind it)
+  mark("device done");
+  std::vector<HostDecoder *> hosts((size_t)nframes);
+  for (int fi = 0; fi < nframes; fi++) hosts[(size_t)fi] = frames[fi].h;
+  return evaluate_entropy_status(d, hosts.data(), nframes, status_host);
+}
