@@ -531,11 +531,9 @@ __device__ __forceinline__ void dequant_idct_sparse(const u32x4 (&rows)[8], cons
 // kernel itself runs at that copy's speed: 0.644-0.648 -> 0.667-0.674 of 8 TB/s on one box (profiles/r04/headline_variants.txt).
 // The 12-bit 4:2:0 kernel keeps the old order (13 % slower with the new one), and so does the single-component kernel (no
 // difference beyond the noise; profiles/r04/layouts_tile_order.txt); runs of 8, 15 or 30 tiles instead of a tile row measured the same;
-// MIJ_TILE_ORDER 1 gives it to all kernels for A-B builds.  ~0u: a padding workgroup (the launch has whole groups of 8 tile rows).
+// ~0u: a padding workgroup (the launch has whole groups of 8 tile rows).
 // ----------------------------------------------------------------------------------------------
-#ifndef MIJ_TILE_ORDER
-#define MIJ_TILE_ORDER 2
-#endif
+constexpr int MIJ_TILE_ORDER = 2; // 2: a tile row per XCD; 1: a contiguous eighth of the launch per XCD
 template <int ORDER = MIJ_TILE_ORDER> __device__ __forceinline__ unsigned tile_of_workgroup(unsigned b, unsigned tiles_x, unsigned tile_rows)
 {
   if (ORDER == 2) {
@@ -565,9 +563,7 @@ template <int ORDER = MIJ_TILE_ORDER> __device__ __forceinline__ TilePos tile_po
   const unsigned row = div_by(logical, tiles_x, a.magic_tx), col = logical - row * tiles_x, frame = div_by(row, tiles_y, a.magic_ty);
   return TilePos{(int)frame, (int)col, (int)(row - frame * tiles_y)};
 }
-#ifndef XT_TILE_ORDER
-#define XT_TILE_ORDER 2 // the JPEG XT kernels: 0.339 -> 0.332 ms per 8 x 4K frames with the tile-row order (profiles/r04/layouts_tile_order.txt)
-#endif
+constexpr int XT_TILE_ORDER = 2; // the JPEG XT kernels: 0.339 -> 0.332 ms per 8 x 4K frames with the tile-row order (profiles/r04/layouts_tile_order.txt)
 template <int ORDER = MIJ_TILE_ORDER> static unsigned workgroups_for_tiles(unsigned tiles_x, unsigned tile_rows)
 {
   return ORDER == 2 ? ((tile_rows + 7u) / 8u) * 8u * tiles_x : tiles_x * tile_rows;
@@ -805,36 +801,250 @@ __device__ __forceinline__ const int *frame_deltas(const Args &a, int frame, int
   return a.q[c];
 }
 
+// ----------------------------------------------------------------------------------------------
+// The steps every fused tile kernel shares, one definition each
+// ----------------------------------------------------------------------------------------------
+// Workgroup prologue: who this thread is, which tile of which frame the workgroup reconstructs, where that frame's coefficients lie.
+// padding: a workgroup beyond the last tile row (the launch is padded to whole groups of eight tile rows) -- the kernel returns.
+struct TileCtx {
+  int tid, lane, wave; // wave is wave-uniform (SGPR)
+  u32x4 *stage;        // the wave's fetch staging buffer
+  int frame, tx, ty;
+  const int16_t *__restrict__ coef;
+  bool padding;
+};
+template <int ORDER = MIJ_TILE_ORDER>
+__device__ __forceinline__ TileCtx tile_enter(const Fused420Args &a, u32x4 (*stage_all)[128])
+{
+  TileCtx t;
+  t.tid = threadIdx.x;
+  t.lane = t.tid & 63;
+  t.wave = __builtin_amdgcn_readfirstlane(t.tid >> 6);
+  t.stage = stage_all[t.wave];
+  const TilePos tp = tile_position<ORDER>(blockIdx.x, a); // (tile order: see there)
+  t.padding = tp.frame < 0;
+  t.frame = tp.frame; t.tx = tp.tx; t.ty = tp.ty;
+  t.coef = a.coef + (int64_t)tp.frame * a.coef_frame_stride;
+  return t;
+}
+
+// The wave's 16 x 4 blocks of a plane of bw x bh blocks (BLOCK_BYTES each): local block n = (lane >> 3) + 8 m sits at column
+// n & 15 = (lane >> 3) + 8 (m & 1), row n >> 4 = m >> 1; blocks outside the plane are redirected to a valid one and never used.
+// TileChunks is the chunkptr of load_blocks / fetch_blocks for them: load_tile_blocks requests the blocks, fetch_tile_blocks hands
+// every lane the rows of its own block as well.
+template <int BLOCK_BYTES>
+struct TileChunks {
+  int x0, gby0, bw, bh;
+  const char *pbase;
+  __device__ __forceinline__ TileChunks(const TileCtx &t, const void *plane, int bw, int bh)
+      : x0(t.tx * F420_TILE_BLOCKS + (t.lane >> 3)), gby0(t.ty * F420_TILE_BLOCKS + t.wave * 4), bw(bw), bh(bh),
+        pbase(reinterpret_cast<const char *>(plane) + (t.lane & 7) * 16) {}
+  __device__ __forceinline__ const u32x4 *operator()(int m) const
+  {
+    const int x = min(x0 + 8 * (m & 1), bw - 1), y = min(gby0 + (m >> 1), bh - 1);
+    return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * bw + x) * BLOCK_BYTES));
+  }
+};
+template <int BLOCK_BYTES = 128>
+__device__ __forceinline__ void load_tile_blocks(u32x4 (&raw)[8], const TileCtx &t, const void *plane, int bw, int bh)
+{
+  load_blocks(raw, TileChunks<BLOCK_BYTES>(t, plane, bw, bh));
+}
+template <int BLOCK_BYTES = 128>
+__device__ __forceinline__ void fetch_tile_blocks(u32x4 (&rows)[8], const TileCtx &t, const void *plane, int bw, int bh)
+{
+  fetch_blocks(rows, t.stage, t.lane, TileChunks<BLOCK_BYTES>(t, plane, bw, bh));
+}
+
+// Block prologue of phase B: the lane's block (bx, by) of the tile's 16 x 16, its first pixel, where its first line goes -- a
+// uniform frame base + a 32-bit lane offset (a frame of pixels is far below 4 GB) -- and how much of it lies inside the picture.
+struct BlockOut {
+  int bx, by, X0, Y0;
+  uint8_t *__restrict__ out_frame;
+  unsigned out_off;
+  int npx, nln;     // pixels per line and lines inside the picture (8 except on the right and bottom edges)
+  bool fast_store;  // whole lines: npx == 8
+  bool outside;     // the whole block lies outside the picture
+  __device__ __forceinline__ unsigned line_off(int l, const Fused420Args &a) const { return out_off + (unsigned)l * (unsigned)a.row_stride; }
+};
+template <int BYTES_PER_PIXEL>
+__device__ __forceinline__ BlockOut block_out(const Fused420Args &a, const TileCtx &t)
+{
+  BlockOut o;
+  o.bx = t.lane & 15; o.by = t.wave * 4 + (t.lane >> 4);
+  o.X0 = (t.tx * F420_TILE_BLOCKS + o.bx) * 8; o.Y0 = (t.ty * F420_TILE_BLOCKS + o.by) * 8;
+  o.outside = o.X0 >= a.width || o.Y0 >= a.height;
+  o.out_frame = a.out + (int64_t)t.frame * a.out_frame_stride;
+  o.out_off = (unsigned)o.Y0 * (unsigned)a.row_stride + (unsigned)o.X0 * (unsigned)BYTES_PER_PIXEL;
+  o.npx = min(8, a.width - o.X0);
+  o.nln = min(8, a.height - o.Y0);
+  o.fast_store = o.npx == 8;
+  return o;
+}
+
+// the LDS window p[3..8] of a chroma line with one 128-bit read (p is 16-byte aligned)
+template <class T>
+__device__ __forceinline__ void load6(const T *p, T (&d)[6])
+{
+  typedef T T4 __attribute__((ext_vector_type(4)));
+  const T4 mid = *reinterpret_cast<const T4 *>(p + 4);
+  d[0] = p[3]; d[1] = mid.x; d[2] = mid.y; d[3] = mid.z; d[4] = mid.w; d[5] = p[8];
+}
+
+// the two-fold horizontal filter in place (upsampler.cpp:291-303) on a block's eight columns; src[k] = v[k + 1]
+__device__ __forceinline__ void hfilter8(const int (&v)[6], int (&o)[8])
+{
+  o[7] = tap13(v[5], v[4], 1);
+  o[6] = tap13(v[3], v[4], 2);
+  o[5] = tap13(v[4], v[3], 1);
+  o[4] = tap13(v[2], v[3], 2);
+  o[3] = tap13(v[3], v[2], 1);
+  o[2] = tap13(v[1], v[2], 2);
+  o[1] = tap13(o[2], v[1], 1); // src[1] has already been overwritten by out[2]
+  o[0] = tap13(v[0], v[1], 2);
+}
+
+// 24-byte line pieces as three 8-byte non-temporal stores (the kernels that do not use store24_nt's 16 + 8)
+__device__ __forceinline__ void store24_3x8(uint8_t *dst, const unsigned (&w)[6])
+{
+  u32x2_any *d2 = reinterpret_cast<u32x2_any *>(dst);
+  __builtin_nontemporal_store(u32x2{w[0], w[1]}, d2);
+  __builtin_nontemporal_store(u32x2{w[2], w[3]}, d2 + 1);
+  __builtin_nontemporal_store(u32x2{w[4], w[5]}, d2 + 2);
+}
+
+// The 48-byte line pieces of the 12-bit kernels (8 pixels x 3 x 16 bit) leave as three 16-byte stores per lane, i.e. every store
+// instruction writes 16 bytes out of every 48: with the non-temporal hint the write counter showed 1.17 x the bytes written
+// (profiles/r05/summary_12bit_r05.txt: partial lines leave the cache before their neighbours arrive), without it the lines are
+// completed in L2 -- 12-bit 4:4:4 369 -> 429 Gpixel/s, 4:2:2 425 -> 477 (profiles/r05/f12_stores.txt).
+constexpr bool F12_TEMPORAL = true;     // fused422_12_kernel, fused444_12_kernel
+constexpr bool F420_12_TEMPORAL = true; // the 12-bit 4:2:0 kernel: 418-438 -> 491 Gpixel/s
+constexpr bool FXT_TEMPORAL = false;    // fusedxt420_kernel / fusedxtw420_kernel (config 5: 8 pixels x 3 half-float codes per line piece) keep the hint
+template <bool TEMPORAL>
+__device__ __forceinline__ void store48(uint8_t *dst, const unsigned (&w)[12])
+{
+  u32x4_any *d4 = reinterpret_cast<u32x4_any *>(dst);
+  if (TEMPORAL) {
+    d4[0] = u32x4{w[0], w[1], w[2], w[3]}; d4[1] = u32x4{w[4], w[5], w[6], w[7]}; d4[2] = u32x4{w[8], w[9], w[10], w[11]};
+  } else {
+    __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, d4);
+    __builtin_nontemporal_store(u32x4{w[4], w[5], w[6], w[7]}, d4 + 1);
+    __builtin_nontemporal_store(u32x4{w[8], w[9], w[10], w[11]}, d4 + 2);
+  }
+}
+
+// The 8-bit RGB line tail: eight pixels' colour sums (17 fraction bits, rounding inside) -> 24 bytes at base + off, or the first npx
+// pixels byte by byte on the picture's right edge.  STORE names the way out of a whole line: store24_nt's 16 + 8 bytes, or three
+// 8-byte stores (store24_3x8).  LINE_BY_LINE: a sched_barrier behind the whole line's stores (fused444_kernel: see there).
+__device__ __forceinline__ void store_rgb8_partial(uint8_t *dst, const int (&rr)[8], const int (&gg)[8], const int (&bb)[8], int npx)
+{
+#pragma unroll
+  for (int x = 0; x < 8; x++)
+    if (x < npx) {
+      dst[3 * x] = (uint8_t)clamp255(rr[x] >> 17); dst[3 * x + 1] = (uint8_t)clamp255(gg[x] >> 17); dst[3 * x + 2] = (uint8_t)clamp255(bb[x] >> 17);
+    }
+}
+enum Store24 { STORE24_NT, STORE24_3X8 };
+template <Store24 STORE, bool LINE_BY_LINE = false>
+__device__ __forceinline__ void store_rgb8_line(uint8_t *base, unsigned off, const int (&rr)[8], const int (&gg)[8], const int (&bb)[8],
+                                                bool fast_store, int npx)
+{
+  if (fast_store) {
+    // 24 bytes r0 g0 b0 r1 ... b7: clamp + pack two samples per instruction pair
+    unsigned w[6];
+    rgb_shift17_sat_pack(rr, gg, bb, w);
+    if (STORE == STORE24_NT) store24_nt(base, off, w);
+    else store24_3x8(base + off, w);
+    if (LINE_BY_LINE) __builtin_amdgcn_sched_barrier(0);
+  } else {
+    store_rgb8_partial(base + off, rr, gg, bb, npx);
+  }
+}
+
+// The 12-bit RGB line tail: eight pixels' colour values, clamped to [0, 4095] -> 48 bytes r0 g0 b0 r1 ... b7 of 16-bit samples
+// (store48<TEMPORAL>: see there), or the first npx pixels sample by sample.  LINE_BY_LINE as above.
+__device__ __forceinline__ unsigned clamp12(int v) { return (unsigned)min(max(v, 0), 4095); }
+template <bool TEMPORAL, bool LINE_BY_LINE = false>
+__device__ __forceinline__ void store_rgb12_line(uint8_t *dst, const int (&rr)[8], const int (&gg)[8], const int (&bb)[8], bool fast_store, int npx)
+{
+  if (fast_store) {
+    unsigned w[12];
+#pragma unroll
+    for (int x = 0; x < 8; x += 2) {
+      w[3 * (x / 2) + 0] = clamp12(rr[x]) | (clamp12(gg[x]) << 16);
+      w[3 * (x / 2) + 1] = clamp12(bb[x]) | (clamp12(rr[x + 1]) << 16);
+      w[3 * (x / 2) + 2] = clamp12(gg[x + 1]) | (clamp12(bb[x + 1]) << 16);
+    }
+    store48<TEMPORAL>(dst, w);
+    if (LINE_BY_LINE) __builtin_amdgcn_sched_barrier(0);
+  } else {
+    uint16_t *d16 = reinterpret_cast<uint16_t *>(dst);
+#pragma unroll
+    for (int x = 0; x < 8; x++)
+      if (x < npx) {
+        d16[3 * x] = (uint16_t)clamp12(rr[x]); d16[3 * x + 1] = (uint16_t)clamp12(gg[x]); d16[3 * x + 2] = (uint16_t)clamp12(bb[x]);
+      }
+  }
+}
+
+// The line tail of the JPEG XT kernels: eight pixels' 24 sixteen-bit codes, packed in pairs -> 48 bytes, or the first npx pixels' codes
+__device__ __forceinline__ void store_codes16_line(uint8_t *dst, const unsigned (&w)[12], bool fast_store, int npx)
+{
+  if (fast_store) {
+    store48<FXT_TEMPORAL>(dst, w);
+  } else {
+    unsigned short *d16 = reinterpret_cast<unsigned short *>(dst);
+#pragma unroll
+    for (int k = 0; k < 24; k++)
+      if (k < 3 * npx) d16[k] = (unsigned short)(w[k >> 1] >> ((k & 1) * 16));
+  }
+}
+
+// Where phase A puts a chroma sample in LDS: into the int16 half of its position's (Cb, Cr) dword -- one plane, the packed kernels --
+// or into the component's own int32 plane.  at = the position's index in the plane; row8: eight samples from a 16-byte aligned at.
+struct LdsPairHalf {
+  short *cp; // this component's half of every dword
+  __device__ __forceinline__ LdsPairHalf(unsigned *cpair, int comp) : cp(reinterpret_cast<short *>(cpair) + comp) {}
+  __device__ __forceinline__ void one(int at, int v) const { cp[2 * at] = (short)v; }
+  __device__ __forceinline__ void row8(int at, const int *v) const
+  {
+    short *dst = cp + 2 * at;
+#pragma unroll
+    for (int x = 0; x < 8; x++) dst[2 * x] = (short)v[x];
+  }
+};
+struct LdsPlane32 {
+  int *cp;
+  __device__ __forceinline__ LdsPlane32(int *plane) : cp(plane) {}
+  __device__ __forceinline__ void one(int at, int v) const { cp[at] = v; }
+  __device__ __forceinline__ void row8(int at, const int *v) const
+  {
+    i32x4 *dst = reinterpret_cast<i32x4 *>(cp + at);
+    dst[0] = i32x4{v[0], v[1], v[2], v[3]};
+    dst[1] = i32x4{v[4], v[5], v[6], v[7]};
+  }
+};
+
+// Workgroups per CU the register allocation must leave room for, and what else the measurements settled:
+// fused420p_kernel requests the luma blocks of phase B in front of phase A's transform (32 more registers across it; with
+// F420P_MINW 4 the allocation still leaves four workgroups per CU).  Measured on one box (profiles/r04/headline_variants.txt):
+// reference-encoded frames 0.617 -> 0.635, dense blocks 0.583 -> 0.595.  fused420_kernel does the same for 8-bit frames; its
+// 12-bit flavour measured 30 % slower with it (same file, visit x) and fetches at the start of phase B.
+constexpr int F420P_MINW = 4;     // (the per-frame-table build keeps 3: it spills at 4)
+constexpr int F420_FAST_MINW = 2; // the unpacked 4:2:0 kernel, fast flavour
+constexpr int F420_12_MINW = 2;   // ... and its 12-bit flavour
+
 // phase A of the 4:2:0 kernels with 32-bit chroma samples: the (8+2) x (8+2) chroma blocks of tile (tx, ty) -> LDS
-// F420P_PREFETCH: the luma blocks of phase B are requested in front of phase A's transform (32 more registers across it; with
-// F420P_MINW 4 the allocation still leaves four workgroups per CU); 0: at the start of phase B, for A-B builds.
-// Measured on one box (profiles/r04/headline_variants.txt): reference-encoded frames 0.617 -> 0.635, dense blocks 0.583 -> 0.595.
-#ifndef F420P_PREFETCH
-#define F420P_PREFETCH 1
-#endif
-#ifndef F420_12_PREFETCH
-#define F420_12_PREFETCH 0 // the same for the 12-bit flavour of fused420_kernel (A-B builds)
-#endif
-// F420P_STAGED: whole waves of whole blocks send a line's pixels through the wave's (idle) fetch staging buffer -- sixteen 24-byte
-// pieces per block row in, 96 chunks of 16 contiguous bytes out -- so that every store instruction writes whole aligned runs of the
-// four 384-byte line segments instead of 16 and then 8 bytes of every lane's 24: tools/microbench/stream_ceiling --staged puts the
-// kernel's access pattern at 0.74-0.755 of 8 TB/s with such stores, 0.71-0.72 with the pieces (profiles/r06/staged_stores.txt).
-#ifndef F420P_STAGED
-#define F420P_STAGED 1 // (0: the 24-byte pieces everywhere, for A-B builds)
-#endif
-#ifndef F420P_TEMPORAL
-#define F420P_TEMPORAL 0 // A-B builds: 1 = the pixel stores of aligned frames without the nt hint as well
-#endif
-#ifndef F420P_MINW
-#define F420P_MINW 4 // workgroups per CU the register allocation must leave room for (the per-frame-table build keeps 3: it spills at 4)
-#endif
 struct NoAfterFetch { __device__ __forceinline__ void operator()() const {} };
 // after_fetch: called between the chroma blocks' arrival and their transform -- where a caller requests the blocks it needs next
 // (fused420_kernel: the luma blocks of phase B; their latency then hides behind this transform)
 template <bool FAST, bool QDEV = false, bool PK = false, class AfterFetch = NoAfterFetch>
-__device__ __forceinline__ void f420_chroma_to_lds(const Fused420Args &a, const int16_t *__restrict__ coef, int (*cplane)[F420_CROWS * F420_CPITCH],
-                                                   u32x4 *stage, int lane, int wave, int tx, int ty, int frame = 0, AfterFetch after_fetch = AfterFetch())
+__device__ __forceinline__ void f420_chroma_to_lds(const Fused420Args &a, const TileCtx &t, int (*cplane)[F420_CROWS * F420_CPITCH],
+                                                   AfterFetch after_fetch = AfterFetch())
 {
+  const int16_t *__restrict__ coef = t.coef;
+  u32x4 *stage = t.stage;
+  const int lane = t.lane, wave = t.wave, tx = t.tx, ty = t.ty, frame = t.frame;
   const int comp = wave >> 1; // 0 = Cb, 1 = Cr (wave-uniform)
   const int16_t *__restrict__ plane = coef + (comp ? a.off_cr : a.off_cb);
   const int gx0 = tx * 8 - 1, gy0 = ty * 8 - 1;
@@ -917,54 +1127,71 @@ __device__ __forceinline__ void f420_chroma_edges(const Fused420Args &a, int (*c
   }
 }
 
+// phase A of the 4:2:2 kernels: a 128x128 tile needs 8 x 16 chroma blocks per component, 64 per wave (waves 0, 1: Cb, waves 2, 3:
+// Cr; upper / lower half of the tile), plus one COLUMN of the 16 blocks left and right of them: the horizontal filter needs
+// nothing else of the neighbours.  STORE (LdsPairHalf, LdsPlane32) says where a sample lands; LDS lines have F420_CPITCH dwords,
+// column pc <-> chroma x_rel = pc - 4.  PK16: the transform's first pass in 16 bits (8-bit frames with the tables in the arguments).
+constexpr int F422_CROWS = 128;
+template <bool QDEV, bool PK16, class STORE>
+__device__ __forceinline__ void f422_chroma_to_lds(const Fused420Args &a, const TileCtx &t, const STORE cp)
+{
+  const int lane = t.lane, wave = t.wave;
+  const int comp = wave >> 1; // 0 = Cb, 1 = Cr; wave-uniform
+  const int16_t *__restrict__ plane = t.coef + (comp ? a.off_cr : a.off_cb);
+  const int gx0 = t.tx * 8, gy0 = t.ty * 16 + (wave & 1) * 8;
+  const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
+  u32x4 rows[8];
+  { // the wave's 8 x 8 blocks: local block n = (lane >> 3) + 8 m is column n & 7 = lane >> 3, row n >> 3 = m
+    const int xx = min(gx0 + (lane >> 3), a.bw_c - 1);
+    fetch_blocks(rows, t.stage, lane, [&](int m) -> const u32x4 * {
+      const int yy = min(gy0 + m, a.bh_c - 1);
+      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_c + xx) * 128));
+    });
+    const int cbx = lane & 7, cby = lane >> 3;
+    if (gx0 + cbx < a.bw_c && gy0 + cby < a.bh_c) {
+      int v[64];
+      dequant_idct_sparse<PK16>(rows, frame_deltas<QDEV>(a, t.frame, 1 + comp), v);
+#pragma unroll
+      for (int r = 0; r < 8; r++) cp.row8((8 * ((wave & 1) * 8 + cby) + r) * F420_CPITCH + 8 * cbx + 4, v + r * 8);
+    }
+  }
+  { // halo columns: local block n = lane >> 3 (+ 8) is side n & 1 (0: left neighbour, 1: right neighbour), row n >> 1
+    fetch_blocks16(rows, t.stage, lane, [&](int m) -> const u32x4 * {
+      const int n = (lane >> 3) + 8 * m;
+      const int xx = min(max((n & 1) ? gx0 + 8 : gx0 - 1, 0), a.bw_c - 1), yy = min(gy0 + (n >> 1), a.bh_c - 1);
+      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_c + xx) * 128));
+    });
+    const int side = lane & 1, cby = lane >> 1, gx = side ? gx0 + 8 : gx0 - 1;
+    if (lane < 16 && gx >= 0 && gx < a.bw_c && gy0 + cby < a.bh_c) {
+      int col[8];
+      dequant_idct_column(rows, frame_deltas<QDEV>(a, t.frame, 1 + comp), side == 0, col); // left neighbour: its last column, right one: its first
+#pragma unroll
+      for (int r = 0; r < 8; r++) cp.one((8 * ((wave & 1) * 8 + cby) + r) * F420_CPITCH + (side ? 68 : 3), col[r]);
+    }
+  }
+}
+
+// image-edge tiles of the 4:2:2 kernels (uniform branch): replicate the last valid chroma column outwards, one thread per stored
+// line.  lines: PLANES x F422_CROWS of them, back to back (one plane of pairs, or the two components' planes)
+template <int PLANES, class T>
+__device__ __forceinline__ void f422_chroma_edges(const Fused420Args &a, T *lines, int tid, int tx)
+{
+  const int last_col = a.cw - 1 - tx * 64; // last valid chroma column, tile-relative
+  if ((tx == 0) | (last_col < 64)) {
+    if (tid < PLANES * F422_CROWS) {
+      T *p = lines + tid * F420_CPITCH;
+      if (tx == 0) p[3] = p[4];
+      if (last_col < 64) {
+        const T v = p[last_col + 4];
+        for (int pc = last_col + 5; pc <= 68; pc++) p[pc] = v;
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // P = 12 (FAST only): 12-bit frames (SOF1, P = 12) -- the same transforms and filters on samples sixteen times as large, the
 // colour stage rearranged so that it stays inside 32 bits (see there), 16-bit samples out (clamp 4095).
-// 24-byte line pieces as three 8-byte stores (the kernels that do not use store24_nt's 16 + 8): A-B macros for the hint
-#ifndef F444_TEMPORAL
-#define F444_TEMPORAL 0
-#endif
-#ifndef F420U_TEMPORAL
-#define F420U_TEMPORAL 0
-#endif
-template <bool TEMPORAL>
-__device__ __forceinline__ void store24_3x8(uint8_t *dst, const unsigned (&w)[6])
-{
-  u32x2_any *d2 = reinterpret_cast<u32x2_any *>(dst);
-  if (TEMPORAL) {
-    d2[0] = u32x2{w[0], w[1]}; d2[1] = u32x2{w[2], w[3]}; d2[2] = u32x2{w[4], w[5]};
-  } else {
-    __builtin_nontemporal_store(u32x2{w[0], w[1]}, d2);
-    __builtin_nontemporal_store(u32x2{w[2], w[3]}, d2 + 1);
-    __builtin_nontemporal_store(u32x2{w[4], w[5]}, d2 + 2);
-  }
-}
-
-// The 48-byte line pieces of the 12-bit kernels (8 pixels x 3 x 16 bit) leave as three 16-byte stores per lane, i.e. every store
-// instruction writes 16 bytes out of every 48: with the non-temporal hint the write counter showed 1.17 x the bytes written
-// (profiles/r05/summary_12bit_r05.txt: partial lines leave the cache before their neighbours arrive), without it the lines are
-// completed in L2 -- 12-bit 4:4:4 369 -> 429 Gpixel/s, 4:2:2 425 -> 477 (profiles/r05/f12_stores.txt).  0 = the hint, for A-B builds.
-#ifndef F12_TEMPORAL
-#define F12_TEMPORAL 1
-#endif
-#ifndef F420_12_TEMPORAL
-#define F420_12_TEMPORAL 1 // the 12-bit 4:2:0 kernel: 418-438 -> 491 Gpixel/s
-#endif
-#ifndef FXT_TEMPORAL
-#define FXT_TEMPORAL 0 // fusedxt420_kernel / fusedxtw420_kernel (config 5: 8 pixels x 3 half-float codes per line piece)
-#endif
-template <bool TEMPORAL = F12_TEMPORAL != 0>
-__device__ __forceinline__ void store48(uint8_t *dst, const unsigned (&w)[12])
-{
-  u32x4_any *d4 = reinterpret_cast<u32x4_any *>(dst);
-  if (TEMPORAL) {
-    d4[0] = u32x4{w[0], w[1], w[2], w[3]}; d4[1] = u32x4{w[4], w[5], w[6], w[7]}; d4[2] = u32x4{w[8], w[9], w[10], w[11]};
-  } else {
-    __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, d4);
-    __builtin_nontemporal_store(u32x4{w[4], w[5], w[6], w[7]}, d4 + 1);
-    __builtin_nontemporal_store(u32x4{w[8], w[9], w[10], w[11]}, d4 + 2);
-  }
-}
-
 template <bool FAST, int MINW, bool QDEV, int P = 8, bool N12 = false>
 __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(const Fused420Args a)
 {
@@ -972,66 +1199,32 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(const Fuse
   __shared__ __attribute__((aligned(16))) int cplane[2][F420_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
+  const TileCtx t = tile_enter<P == 8 ? MIJ_TILE_ORDER : 1>(a, stage_all);
+  if (t.padding) return;
 
-  const TilePos tp = tile_position<P == 8 ? MIJ_TILE_ORDER : 1>(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-
-  // the luma blocks of phase B are requested in front of phase A's transform (see fused420p_kernel; two workgroups per CU leave
-  // the 32 registers)
+  // the luma blocks of phase B are requested in front of phase A's transform (see F420P_MINW; two workgroups per CU leave the 32
+  // registers) -- 8-bit frames only: the 12-bit flavour fetches them at the start of phase B
   u32x4 yraw[8];
-  auto luma_loads = [&]() {
-    const int16_t *__restrict__ plane = coef + a.off_y;
-    const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-    // local block n = (lane >> 3) + 8 m sits at column n & 15 = (lane >> 3) + 8 (m & 1), row n >> 4 = m >> 1 of the wave's 16 x 4 blocks
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    load_blocks(yraw, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  };
-  // (8-bit frames only: the 12-bit flavour measured 30 % slower with it, profiles/r04/headline_variants.txt visit x)
-  constexpr bool PREFETCH = F420P_PREFETCH && (P == 8 || F420_12_PREFETCH);
-  if (PREFETCH) f420_chroma_to_lds<FAST, QDEV, !QDEV && P == 8>(a, coef, cplane, stage, lane, wave, tx, ty, frame, luma_loads);
-  else f420_chroma_to_lds<FAST, QDEV, !QDEV && P == 8>(a, coef, cplane, stage, lane, wave, tx, ty, frame);
+  auto luma_loads = [&]() { load_tile_blocks(yraw, t, t.coef + a.off_y, a.bw_y, a.bh_y); };
+  constexpr bool PREFETCH = P == 8;
+  if (PREFETCH) f420_chroma_to_lds<FAST, QDEV, !QDEV && P == 8>(a, t, cplane, luma_loads);
+  else f420_chroma_to_lds<FAST, QDEV, !QDEV && P == 8>(a, t, cplane);
   __syncthreads();
-  f420_chroma_edges(a, cplane, tid, tx, ty);
+  f420_chroma_edges(a, cplane, t.tid, t.tx, t.ty);
 
   // ------------------------------------------------------------------ phase B: luma + colour
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
   u32x4 rows[8];
   if (!PREFETCH) luma_loads();
-  transpose_blocks(rows, stage, lane, yraw);
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  if (X0 >= a.width || Y0 >= a.height) return; // no barrier below this point
+  transpose_blocks(rows, t.stage, t.lane, yraw);
+  const BlockOut o = block_out<P == 12 ? 6 : 3>(a, t);
+  if (o.outside) return; // no barrier below this point
   int yv[64];
-  if (FAST) dequant_idct_sparse<!QDEV && P == 8, P == 8>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, P == 8 ? LUMA_FOLD_R2 : 2048); // (8 bit: doubled sums, luma13)
-  else dequant_idct<false>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 128 << 7);
-
-  // uniform frame base + 32-bit lane offsets (a frame of pixels is far below 4 GB)
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * (P == 12 ? 6u : 3u);
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
+  if (FAST) dequant_idct_sparse<!QDEV && P == 8, P == 8>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 0, P == 8 ? LUMA_FOLD_R2 : 2048); // (8 bit: doubled sums, luma13)
+  else dequant_idct<false>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 128 << 7);
 
   // chroma window of this block: lines pr = 4 by + m (+0 top, +1 cur, +2 bot), columns pc = 4 bx + 3 + j
-  const int *cb_base = cplane[0] + (4 * by) * F420_CPITCH + 4 * bx;
-  const int *cr_base = cplane[1] + (4 * by) * F420_CPITCH + 4 * bx;
-
-  auto load6 = [](const int *p, int (&d)[6]) {
-    // p is 16-byte aligned; wanted: p[3..8]
-    const i32x4 mid = *reinterpret_cast<const i32x4 *>(p + 4);
-    d[0] = p[3]; d[1] = mid.x; d[2] = mid.y; d[3] = mid.z; d[4] = mid.w; d[5] = p[8];
-  };
+  const int *cb_base = cplane[0] + (4 * o.by) * F420_CPITCH + 4 * o.bx;
+  const int *cr_base = cplane[1] + (4 * o.by) * F420_CPITCH + 4 * o.bx;
 
   int cbT[6], cbC[6], cbB[6], crT[6], crC[6], crB[6];
   load6(cb_base, cbT); load6(cb_base + F420_CPITCH, cbC);
@@ -1053,22 +1246,10 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(const Fuse
         vb[j] = tap13(half ? cbB[j] : cbT[j], cbC[j], rnd);
         vr[j] = tap13(half ? crB[j] : crT[j], crC[j], rnd);
       }
-      // horizontal filter in place (upsampler.cpp:291-303); src[k] = v[k + 1]
       int ub[8], ur[8];
-      auto hfilt = [](const int (&v)[6], int (&o)[8]) {
-        o[7] = tap13(v[5], v[4], 1);
-        o[6] = tap13(v[3], v[4], 2);
-        o[5] = tap13(v[4], v[3], 1);
-        o[4] = tap13(v[2], v[3], 2);
-        o[3] = tap13(v[3], v[2], 1);
-        o[2] = tap13(v[1], v[2], 2);
-        o[1] = tap13(o[2], v[1], 1); // src[1] has already been overwritten by out[2]
-        o[0] = tap13(v[0], v[1], 2);
-      };
-      hfilt(vb, ub);
-      hfilt(vr, ur);
-      if (l < nln) {
-        uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
+      hfilter8(vb, ub);
+      hfilter8(vr, ur);
+      if (l < o.nln) {
         if (FAST && P == 12) {
           // (y * 8192 + (cb - 32768) * Lb + (cr - 32768) * Lr + 65536) >> 17, clamped to [0, 4095] (ycbcrtrafo.cpp:842-856,
           // :921-936; the reference accumulates in 64 bits).  With y = y' + 32768, cb - 32768 = cb' (no level shift in the
@@ -1079,24 +1260,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(const Fuse
           int rr[8], gg[8], bb[8];
 #pragma unroll
           for (int x = 0; x < 8; x++) colour12<N12>(yv[l * 8 + x], ub[x], ur[x], rr[x], gg[x], bb[x]);
-          auto c12 = [](int v) { return (unsigned)min(max(v, 0), 4095); };
-          if (fast_store) {
-            unsigned w[12]; // 48 bytes r0 g0 b0 r1 ... b7, 16-bit samples
-#pragma unroll
-            for (int x = 0; x < 8; x += 2) {
-              w[3 * (x / 2) + 0] = c12(rr[x]) | (c12(gg[x]) << 16);
-              w[3 * (x / 2) + 1] = c12(bb[x]) | (c12(rr[x + 1]) << 16);
-              w[3 * (x / 2) + 2] = c12(gg[x + 1]) | (c12(bb[x + 1]) << 16);
-            }
-            store48<F420_12_TEMPORAL != 0>(dst, w);
-          } else {
-            uint16_t *d16 = reinterpret_cast<uint16_t *>(dst);
-#pragma unroll
-            for (int x = 0; x < 8; x++)
-              if (x < npx) {
-                d16[3 * x] = (uint16_t)c12(rr[x]); d16[3 * x + 1] = (uint16_t)c12(gg[x]); d16[3 * x + 2] = (uint16_t)c12(bb[x]);
-              }
-          }
+          store_rgb12_line<F420_12_TEMPORAL>(o.out_frame + o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
         } else if (FAST) {
           // y, cb, cr arrive WITHOUT the level shift (DCOFF = false): with y = y' + 2048 and cb - 2048 = cb' the
           // reference's (y * 8192 + (cb - 2048) * Lb + (cr - 2048) * Lr + 65536) >> 17 becomes
@@ -1109,19 +1273,9 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(const Fuse
             gg[x] = mad24(ur[x], -L_CR_G, mad24(ub[x], -L_CB_G, yk));
             bb[x] = mad24(ub[x], L_CB_B, yk);
           }
-          if (fast_store) {
-            // 24 bytes r0 g0 b0 r1 ... b7: clamp + pack two samples per instruction pair
-            unsigned w[6];
-            rgb_shift17_sat_pack(rr, gg, bb, w);
-            store24_3x8<F420U_TEMPORAL != 0>(dst, w);
-          } else {
-#pragma unroll
-            for (int x = 0; x < 8; x++)
-              if (x < npx) {
-                dst[3 * x] = (uint8_t)clamp255(rr[x] >> 17); dst[3 * x + 1] = (uint8_t)clamp255(gg[x] >> 17); dst[3 * x + 2] = (uint8_t)clamp255(bb[x] >> 17);
-              }
-          }
+          store_rgb8_line<STORE24_3X8>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
         } else {
+          uint8_t *dst = o.out_frame + o.line_off(l, a);
           unsigned px[24];
 #pragma unroll
           for (int x = 0; x < 8; x++) {
@@ -1129,15 +1283,15 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(const Fuse
             ycc_to_rgb<false>(yv[l * 8 + x], ub[x], ur[x], r, g, b);
             px[3 * x] = r; px[3 * x + 1] = g; px[3 * x + 2] = b;
           }
-          if (fast_store) {
+          if (o.fast_store) {
             unsigned w[6];
 #pragma unroll
             for (int i = 0; i < 6; i++) w[i] = px[4 * i] | (px[4 * i + 1] << 8) | (px[4 * i + 2] << 16) | (px[4 * i + 3] << 24);
-            store24_3x8<F420U_TEMPORAL != 0>(dst, w);
+            store24_3x8(dst, w);
           } else {
 #pragma unroll
             for (int x = 0; x < 8; x++)
-              if (x < npx) {
+              if (x < o.npx) {
                 dst[3 * x] = (uint8_t)px[3 * x]; dst[3 * x + 1] = (uint8_t)px[3 * x + 1]; dst[3 * x + 2] = (uint8_t)px[3 * x + 2];
               }
           }
@@ -1193,29 +1347,13 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fus
   __shared__ __attribute__((aligned(16))) unsigned cpair[F420_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
-
-  const TilePos tp = tile_position(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-#if F420P_PREFETCH
-  // the luma blocks of phase B are requested early: their latency hides behind phase A's transform
+  const TileCtx t = tile_enter(a, stage_all);
+  if (t.padding) return;
+  const int tid = t.tid, lane = t.lane, wave = t.wave, frame = t.frame, tx = t.tx, ty = t.ty;
+  u32x4 *stage = t.stage;
+  const int16_t *__restrict__ coef = t.coef;
+  // the luma blocks of phase B are requested early: their latency hides behind phase A's transform (see F420P_MINW)
   u32x4 yraw[8];
-  auto luma_loads = [&]() {
-    const int16_t *__restrict__ plane = coef + a.off_y;
-    const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    load_blocks(yraw, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  };
-#endif
 
   // ------------------------------------------------------------------ phase A: chroma -> LDS halves
   {
@@ -1245,9 +1383,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fus
     const int idx = base + lane;
     const int cby = idx / F420_CGRID, cbx = idx - cby * F420_CGRID;
     const int gx = gx0 + cbx, gy = gy0 + cby;
-#if F420P_PREFETCH
-    luma_loads();
-#endif
+    load_tile_blocks(yraw, t, coef + a.off_y, a.bw_y, a.bh_y);
     if (idx < F420_CGRID * F420_CGRID && gx >= 0 && gy >= 0 && gx < a.bw_c && gy < a.bh_c) {
       int v[64];
       dequant_idct_sparse<!QDEV, false, D2>(rows, frame_deltas<QDEV>(a, frame, 1 + comp), v);
@@ -1300,39 +1436,19 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fus
   }
 
   // ------------------------------------------------------------------ phase B: luma, upsampling, colour
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
   u32x4 rows[8];
-#if F420P_PREFETCH
   transpose_blocks(rows, stage, lane, yraw);
-#else
-  {
-    const int16_t *__restrict__ plane = coef + a.off_y;
-    const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  }
-#endif
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  if (X0 >= a.width || Y0 >= a.height) return; // no barrier below this point
+  const BlockOut o = block_out<3>(a, t);
+  if (o.outside) return; // no barrier below this point
   int yv[64];
   dequant_idct_sparse<!QDEV, true, D2>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
 
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 3u;
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
+  const int bx = o.bx, by = o.by, npx = o.npx, nln = o.nln;
+  uint8_t *__restrict__ out_frame = o.out_frame;
+  const unsigned out_off = o.out_off;
+  const bool fast_store = o.fast_store;
   // chroma window of this block: lines pr = 4 by + m (+0 top, +1 cur, +2 bot), columns pc = 4 bx + 3 + j
   const unsigned *c_base = cpair + (4 * by) * F420_CPITCH + 4 * bx;
-  auto load6 = [](const unsigned *p, unsigned (&d)[6]) { // p is 16-byte aligned; wanted: p[3..8]
-    const u32x4 mid = *reinterpret_cast<const u32x4 *>(p + 4);
-    d[0] = p[3]; d[1] = mid.x; d[2] = mid.y; d[3] = mid.z; d[4] = mid.w; d[5] = p[8];
-  };
 
   // Blocks that lie wholly inside the picture -- all of them, for every wave but those on the right and bottom edges -- take a
   // copy of the loop without the per-line exec masks (wave-uniform choice: one ballot)
@@ -1340,7 +1456,11 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fus
   const unsigned base_lo = (unsigned)(uintptr_t)out_frame;
   auto lines = [&](auto full_tag, auto shift_tag, auto staged_tag) {
     constexpr bool FULL = decltype(full_tag)::value, SHIFTED = decltype(shift_tag)::value, STAGED = decltype(staged_tag)::value;
-    // STAGED: chunk c of the wave's 96 per line is bytes 16 (c % 24) .. of block row c / 24's segment; lanes 0..31 own a second one
+    // STAGED: whole waves of whole blocks send a line's pixels through the wave's (idle) fetch staging buffer -- sixteen 24-byte
+    // pieces per block row in, 96 chunks of 16 contiguous bytes out -- so that every store instruction writes whole aligned runs of
+    // the four 384-byte line segments instead of 16 and then 8 bytes of every lane's 24: tools/microbench/stream_ceiling --staged puts
+    // the kernel's access pattern at 0.74-0.755 of 8 TB/s with such stores, 0.71-0.72 with the pieces (profiles/r06/staged_stores.txt).
+    // Chunk c of the wave's 96 per line is bytes 16 (c % 24) .. of block row c / 24's segment; lanes 0..31 own a second one
     unsigned so0 = 0, so1 = 0;
     if (STAGED) {
       const unsigned wave_off = (unsigned)((ty * F420_TILE_BLOCKS + wave * 4) * 8) * (unsigned)a.row_stride + (unsigned)(tx * F420_TILE_BLOCKS * 8) * 3u;
@@ -1402,14 +1522,9 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fus
             }
             else if (SHIFTED && m) store24_nt_shifted(out_frame, off, w, bx, m);
             else if (SHIFTED) store24_nt<false>(out_frame, off, w);
-            else store24_nt<!F420P_TEMPORAL>(out_frame, off, w);
+            else store24_nt(out_frame, off, w);
           } else {
-            uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-#pragma unroll
-            for (int x = 0; x < 8; x++)
-              if (x < npx) {
-                dst[3 * x] = (uint8_t)clamp255(rr[x] >> 17); dst[3 * x + 1] = (uint8_t)clamp255(gg[x] >> 17); dst[3 * x + 2] = (uint8_t)clamp255(bb[x] >> 17);
-              }
+            store_rgb8_partial(out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride), rr, gg, bb, npx);
           }
         }
       }
@@ -1420,9 +1535,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fus
   };
   const bool whole = __builtin_amdgcn_ballot_w64(npx != 8 || nln != 8) == 0;
   if (whole && ((base_lo | (unsigned)a.row_stride) & 3u) && __builtin_amdgcn_ballot_w64(true) == ~0ull) lines(std::true_type{}, std::true_type{}, std::false_type{});
-#if F420P_STAGED
   else if (whole && __builtin_amdgcn_ballot_w64(true) == ~0ull) lines(std::true_type{}, std::false_type{}, std::true_type{});
-#endif
   else if (whole) lines(std::true_type{}, std::false_type{}, std::false_type{});
   else lines(std::false_type{}, std::false_type{}, std::false_type{});
 }
@@ -1434,8 +1547,6 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fus
 // needs (8 + 2) x 16 chroma blocks per component -- 1.25 rounds of transforms for the four waves where 4:2:0 needs
 // one -- and no halo lines; the samples of a line go through the horizontal filter only.  Same gate as the packed
 // 4:2:0 flavour (FAST arithmetic, chroma range_max < 2047), same store path.  Algorithmic bytes: 4 B in + 3 B out per pixel.
-constexpr int F422_CROWS = 128;
-
 // WIDE: the samples still travel through LDS as int16 pairs (|sample * 16| <= 4 * range_max < 2^15 for range_max < 8190,
 // the fused 4:4:4 kernel's bound, which legitimate 8-bit content cannot exceed: sum |c| q <= 8 sqrt(64 * 128^2) by
 // Cauchy-Schwarz), but the filter runs on unpacked 32-bit values: frames between the packed gate (2047) and 8190 --
@@ -1446,107 +1557,24 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(const Fuse
   __shared__ __attribute__((aligned(16))) unsigned cpair[F422_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
+  const TileCtx t = tile_enter(a, stage_all);
+  if (t.padding) return;
 
-  const TilePos tp = tile_position(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-
-  // ------------------------------------------------------------------ phase A: chroma -> LDS halves
-  // 8 x 16 blocks per component, 64 per wave (waves 0, 1: Cb, waves 2, 3: Cr; upper / lower half of the tile), plus one
-  // COLUMN of the 16 blocks left and right of them: the horizontal filter needs nothing else of the neighbours
-  {
-    const int comp = wave >> 1; // 0 = Cb (low halves), 1 = Cr (high halves); wave-uniform
-    const int16_t *__restrict__ plane = coef + (comp ? a.off_cr : a.off_cb);
-    const int gx0 = tx * 8, gy0 = ty * 16 + (wave & 1) * 8;
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    short *cp = reinterpret_cast<short *>(cpair) + comp; // this component's half of every dword
-    u32x4 rows[8];
-    { // the wave's 8 x 8 blocks: local block n = (lane >> 3) + 8 m is column n & 7 = lane >> 3, row n >> 3 = m
-      const int xx = min(gx0 + (lane >> 3), a.bw_c - 1);
-      fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-        const int yy = min(gy0 + m, a.bh_c - 1);
-        return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_c + xx) * 128));
-      });
-      const int cbx = lane & 7, cby = lane >> 3;
-      if (gx0 + cbx < a.bw_c && gy0 + cby < a.bh_c) {
-        int v[64];
-        dequant_idct_sparse<!QDEV>(rows, frame_deltas<QDEV>(a, frame, 1 + comp), v);
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-          short *dst = cp + 2 * ((8 * ((wave & 1) * 8 + cby) + r) * F420_CPITCH + 8 * cbx + 4);
-#pragma unroll
-          for (int x = 0; x < 8; x++) dst[2 * x] = (short)v[r * 8 + x];
-        }
-      }
-    }
-    { // halo columns: local block n = lane >> 3 (+ 8) is side n & 1 (0: left neighbour, 1: right neighbour), row n >> 1
-      fetch_blocks16(rows, stage, lane, [&](int m) -> const u32x4 * {
-        const int n = (lane >> 3) + 8 * m;
-        const int xx = min(max((n & 1) ? gx0 + 8 : gx0 - 1, 0), a.bw_c - 1), yy = min(gy0 + (n >> 1), a.bh_c - 1);
-        return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_c + xx) * 128));
-      });
-      const int side = lane & 1, cby = lane >> 1, gx = side ? gx0 + 8 : gx0 - 1;
-      if (lane < 16 && gx >= 0 && gx < a.bw_c && gy0 + cby < a.bh_c) {
-        int col[8];
-        dequant_idct_column(rows, frame_deltas<QDEV>(a, frame, 1 + comp), side == 0, col); // left neighbour: its last column, right one: its first
-#pragma unroll
-        for (int r = 0; r < 8; r++) cp[2 * ((8 * ((wave & 1) * 8 + cby) + r) * F420_CPITCH + (side ? 68 : 3))] = (short)col[r];
-      }
-    }
-  }
+  // ------------------------------------------------------------------ phase A: chroma -> LDS halves (Cb low, Cr high), edge fix-up
+  f422_chroma_to_lds<QDEV, !QDEV>(a, t, LdsPairHalf(cpair, t.wave >> 1));
   __syncthreads();
-
-  // ------------------------------------------------------------------ edge fix-up (uniform branch): columns only
-  {
-    const int last_col = a.cw - 1 - tx * 64; // last valid chroma column, tile-relative
-    if ((tx == 0) | (last_col < 64)) {
-      if (tid < F422_CROWS) { // one thread per stored line
-        unsigned *p = cpair + tid * F420_CPITCH;
-        if (tx == 0) p[3] = p[4];
-        if (last_col < 64) {
-          const unsigned v = p[last_col + 4];
-          for (int pc = last_col + 5; pc <= 68; pc++) p[pc] = v;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  f422_chroma_edges<1>(a, cpair, t.tid, t.tx);
 
   // ------------------------------------------------------------------ phase B: luma, upsampling, colour
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
   u32x4 rows[8];
-  {
-    const int16_t *__restrict__ plane = coef + a.off_y;
-    const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  }
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  if (X0 >= a.width || Y0 >= a.height) return; // no barrier below this point
+  fetch_tile_blocks(rows, t, t.coef + a.off_y, a.bw_y, a.bh_y);
+  const BlockOut o = block_out<3>(a, t);
+  if (o.outside) return; // no barrier below this point
   int yv[64];
-  dequant_idct_sparse<!QDEV, true>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
+  dequant_idct_sparse<!QDEV, true>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 0, LUMA_FOLD_R2);
 
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 3u;
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
   // chroma window of this block: lines pr = 8 by + l, columns pc = 4 bx + 3 + j
-  const unsigned *c_base = cpair + (8 * by) * F420_CPITCH + 4 * bx;
-  auto load6 = [](const unsigned *p, unsigned (&d)[6]) { // p is 16-byte aligned; wanted: p[3..8]
-    const u32x4 mid = *reinterpret_cast<const u32x4 *>(p + 4);
-    d[0] = p[3]; d[1] = mid.x; d[2] = mid.y; d[3] = mid.z; d[4] = mid.w; d[5] = p[8];
-  };
+  const unsigned *c_base = cpair + (8 * o.by) * F420_CPITCH + 4 * o.bx;
 #pragma unroll
   for (int l = 0; l < 8; l++) {
     {
@@ -1560,12 +1588,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(const Fuse
         int vb[6], vr[6];
 #pragma unroll
         for (int j = 0; j < 6; j++) { vb[j] = (int)(short)(v[j] & 0xffffu); vr[j] = (int)v[j] >> 16; }
-#define MIJ_HFILTER(o, s)                                                                                        \
-        o[7] = tap13(s[5], s[4], 1); o[6] = tap13(s[3], s[4], 2); o[5] = tap13(s[4], s[3], 1); o[4] = tap13(s[2], s[3], 2); \
-        o[3] = tap13(s[3], s[2], 1); o[2] = tap13(s[1], s[2], 2); o[1] = tap13(o[2], s[1], 1); o[0] = tap13(s[0], s[1], 2);
-        MIJ_HFILTER(ub, vb)
-        MIJ_HFILTER(ur, vr)
-#undef MIJ_HFILTER
+        hfilter8(vb, ub);
+        hfilter8(vr, ur);
       } else {
         u[7] = tap13_pk(v[5], v[4], 1);
         u[6] = tap13_pk(v[3], v[4], 2);
@@ -1576,7 +1600,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(const Fuse
         u[1] = tap13_pk(u[2], v[1], 1); // src[1] has already been overwritten by out[2]
         u[0] = tap13_pk(v[0], v[1], 2);
       }
-      if (l < nln) {
+      if (l < o.nln) {
         int rr[8], gg[8], bb[8];
 #pragma unroll
         for (int x = 0; x < 8; x++) {
@@ -1591,18 +1615,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(const Fuse
             gg[x] = dot2_16(u[x], -L_CB_G, -L_CR_G, yk);
           }
         }
-        if (fast_store) {
-          unsigned w[6];
-          rgb_shift17_sat_pack(rr, gg, bb, w);
-          store24_nt(out_frame, out_off + (unsigned)l * (unsigned)a.row_stride, w);
-        } else {
-          uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-#pragma unroll
-          for (int x = 0; x < 8; x++)
-            if (x < npx) {
-              dst[3 * x] = (uint8_t)clamp255(rr[x] >> 17); dst[3 * x + 1] = (uint8_t)clamp255(gg[x] >> 17); dst[3 * x + 2] = (uint8_t)clamp255(bb[x] >> 17);
-            }
-        }
+        store_rgb8_line<STORE24_NT>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
       }
     }
   }
@@ -1618,139 +1631,36 @@ __global__ __launch_bounds__(F420_THREADS, 2) void fused422_12_kernel(const Fuse
   __shared__ __attribute__((aligned(16))) int cplane[2][F422_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
+  const TileCtx t = tile_enter(a, stage_all);
+  if (t.padding) return;
 
-  const TilePos tp = tile_position(blockIdx.x, a);
-  if (tp.frame < 0) return;
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-
-  // ------------------------------------------------------------------ phase A: chroma -> LDS (see fused422_kernel)
-  {
-    const int comp = wave >> 1;
-    const int16_t *__restrict__ plane = coef + (comp ? a.off_cr : a.off_cb);
-    const int gx0 = tx * 8, gy0 = ty * 16 + (wave & 1) * 8;
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    int *cp = cplane[comp];
-    u32x4 rows[8];
-    {
-      const int xx = min(gx0 + (lane >> 3), a.bw_c - 1);
-      fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-        const int yy = min(gy0 + m, a.bh_c - 1);
-        return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_c + xx) * 128));
-      });
-      const int cbx = lane & 7, cby = lane >> 3;
-      if (gx0 + cbx < a.bw_c && gy0 + cby < a.bh_c) {
-        int v[64];
-        dequant_idct_sparse<false>(rows, frame_deltas<QDEV>(a, frame, 1 + comp), v);
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-          i32x4 *dst = reinterpret_cast<i32x4 *>(cp + (8 * ((wave & 1) * 8 + cby) + r) * F420_CPITCH + 8 * cbx + 4);
-          dst[0] = i32x4{v[r * 8 + 0], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3]};
-          dst[1] = i32x4{v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]};
-        }
-      }
-    }
-    {
-      fetch_blocks16(rows, stage, lane, [&](int m) -> const u32x4 * {
-        const int n = (lane >> 3) + 8 * m;
-        const int xx = min(max((n & 1) ? gx0 + 8 : gx0 - 1, 0), a.bw_c - 1), yy = min(gy0 + (n >> 1), a.bh_c - 1);
-        return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_c + xx) * 128));
-      });
-      const int side = lane & 1, cby = lane >> 1, gx = side ? gx0 + 8 : gx0 - 1;
-      if (lane < 16 && gx >= 0 && gx < a.bw_c && gy0 + cby < a.bh_c) {
-        int col[8];
-        dequant_idct_column(rows, frame_deltas<QDEV>(a, frame, 1 + comp), side == 0, col);
-#pragma unroll
-        for (int r = 0; r < 8; r++) cp[(8 * ((wave & 1) * 8 + cby) + r) * F420_CPITCH + (side ? 68 : 3)] = col[r];
-      }
-    }
-  }
+  // ------------------------------------------------------------------ phase A: chroma -> the component's LDS plane, edge fix-up
+  f422_chroma_to_lds<QDEV, false>(a, t, LdsPlane32(cplane[t.wave >> 1]));
   __syncthreads();
-  {
-    const int last_col = a.cw - 1 - tx * 64; // last valid chroma column, tile-relative
-    if ((tx == 0) | (last_col < 64)) {
-      if (tid < 2 * F422_CROWS) { // one thread per stored line and component
-        int *p = cplane[tid >> 7] + (tid & (F422_CROWS - 1)) * F420_CPITCH;
-        if (tx == 0) p[3] = p[4];
-        if (last_col < 64) {
-          const int v = p[last_col + 4];
-          for (int pc = last_col + 5; pc <= 68; pc++) p[pc] = v;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  f422_chroma_edges<2>(a, cplane[0], t.tid, t.tx);
 
   // ------------------------------------------------------------------ phase B: luma, upsampling, colour
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
   u32x4 rows[8];
-  {
-    const int16_t *__restrict__ plane = coef + a.off_y;
-    const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  }
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  if (X0 >= a.width || Y0 >= a.height) return; // no barrier below this point
+  fetch_tile_blocks(rows, t, t.coef + a.off_y, a.bw_y, a.bh_y);
+  const BlockOut o = block_out<6>(a, t);
+  if (o.outside) return; // no barrier below this point
   int yv[64];
-  dequant_idct_sparse<false>(rows, frame_deltas<QDEV>(a, frame, 0), yv);
+  dequant_idct_sparse<false>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv);
 
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 6u;
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
-  const int *cb_base = cplane[0] + (8 * by) * F420_CPITCH + 4 * bx;
-  const int *cr_base = cplane[1] + (8 * by) * F420_CPITCH + 4 * bx;
-  auto load6 = [](const int *p, int (&d)[6]) { // p is 16-byte aligned; wanted: p[3..8]
-    const i32x4 mid = *reinterpret_cast<const i32x4 *>(p + 4);
-    d[0] = p[3]; d[1] = mid.x; d[2] = mid.y; d[3] = mid.z; d[4] = mid.w; d[5] = p[8];
-  };
-  static_assert(L_CB_B % 4 == 0, "the blue product is taken at a quarter of the constant");
-  auto c12 = [](int v) { return (unsigned)min(max(v, 0), 4095); };
+  const int *cb_base = cplane[0] + (8 * o.by) * F420_CPITCH + 4 * o.bx;
+  const int *cr_base = cplane[1] + (8 * o.by) * F420_CPITCH + 4 * o.bx;
 #pragma unroll
   for (int l = 0; l < 8; l++) {
     int vb[6], vr[6], ub[8], ur[8];
     load6(cb_base + l * F420_CPITCH, vb);
     load6(cr_base + l * F420_CPITCH, vr);
-    // horizontal filter in place (upsampler.cpp:291-303); src[k] = v[k + 1]
-#define MIJ_HFILTER(o, s)                                                                                        \
-    o[7] = tap13(s[5], s[4], 1); o[6] = tap13(s[3], s[4], 2); o[5] = tap13(s[4], s[3], 1); o[4] = tap13(s[2], s[3], 2); \
-    o[3] = tap13(s[3], s[2], 1); o[2] = tap13(s[1], s[2], 2); o[1] = tap13(o[2], s[1], 1); o[0] = tap13(s[0], s[1], 2);
-    MIJ_HFILTER(ub, vb)
-    MIJ_HFILTER(ur, vr)
-#undef MIJ_HFILTER
-    if (l < nln) {
+    hfilter8(vb, ub);
+    hfilter8(vr, ur);
+    if (l < o.nln) {
       int rr[8], gg[8], bb[8];
 #pragma unroll
       for (int x = 0; x < 8; x++) colour12<N12>(yv[l * 8 + x], ub[x], ur[x], rr[x], gg[x], bb[x]);
-      uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-      if (fast_store) {
-        unsigned w[12];
-#pragma unroll
-        for (int x = 0; x < 8; x += 2) {
-          w[3 * (x / 2) + 0] = c12(rr[x]) | (c12(gg[x]) << 16);
-          w[3 * (x / 2) + 1] = c12(bb[x]) | (c12(rr[x + 1]) << 16);
-          w[3 * (x / 2) + 2] = c12(gg[x + 1]) | (c12(bb[x + 1]) << 16);
-        }
-        store48(dst, w);
-      } else {
-        uint16_t *d16 = reinterpret_cast<uint16_t *>(dst);
-#pragma unroll
-        for (int x = 0; x < 8; x++)
-          if (x < npx) {
-            d16[3 * x] = (uint16_t)c12(rr[x]); d16[3 * x + 1] = (uint16_t)c12(gg[x]); d16[3 * x + 2] = (uint16_t)c12(bb[x]);
-          }
-      }
+      store_rgb12_line<F12_TEMPORAL>(o.out_frame + o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
     }
   }
 }
@@ -1766,6 +1676,12 @@ __global__ __launch_bounds__(F420_THREADS, 2) void fused422_12_kernel(const Fuse
 // (Cb, Cr) int16 pairs (chroma range_max < 8190), the filter and the colour stage run on unpacked 32-bit values (the WIDE
 // arithmetic of fused422_kernel: the weights up to 7 leave no room for 16-bit sums).  Algorithmic bytes: 3 B in + 3 B out.
 __device__ __forceinline__ int f8(int wa, int x, int wb, int y, int r);
+// the four-fold horizontal core on c[-1], c[0], c[1], c[2] = s[0..3]
+__device__ __forceinline__ void hfilter4(const int (&s)[4], int (&o)[8])
+{
+  o[0] = f8(3, s[0], 5, s[1], 2); o[1] = f8(1, s[0], 7, s[1], 1); o[2] = f8(1, s[2], 7, s[1], 2); o[3] = f8(3, s[2], 5, s[1], 1);
+  o[4] = f8(3, s[1], 5, s[2], 2); o[5] = f8(1, s[1], 7, s[2], 1); o[6] = f8(1, s[3], 7, s[2], 2); o[7] = f8(3, s[3], 5, s[2], 1);
+}
 constexpr int F411_CPITCH = 40; // dwords per LDS chroma line; column pc <-> chroma x_rel = pc - 4 (3 and 36: the halo columns)
 
 template <int MINW, bool QDEV>
@@ -1774,15 +1690,11 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused411_kernel(const Fuse
   __shared__ __attribute__((aligned(16))) unsigned cpair[F422_CROWS * F411_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
-
-  const TilePos tp = tile_position(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
+  const TileCtx t = tile_enter(a, stage_all);
+  if (t.padding) return;
+  const int tid = t.tid, lane = t.lane, wave = t.wave, frame = t.frame, tx = t.tx, ty = t.ty;
+  u32x4 *stage = t.stage;
+  const int16_t *__restrict__ coef = t.coef;
 
   // ------------------------------------------------------------------ phase A: chroma -> LDS halves
   {
@@ -1845,31 +1757,15 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused411_kernel(const Fuse
   }
 
   // ------------------------------------------------------------------ phase B: luma, upsampling, colour
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
   u32x4 rows[8];
-  {
-    const int16_t *__restrict__ plane = coef + a.off_y;
-    const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  }
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  if (X0 >= a.width || Y0 >= a.height) return; // no barrier below this point
+  fetch_tile_blocks(rows, t, coef + a.off_y, a.bw_y, a.bh_y);
+  const BlockOut o = block_out<3>(a, t);
+  if (o.outside) return; // no barrier below this point
   int yv[64];
   dequant_idct_sparse<!QDEV, true>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
 
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 3u;
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
   // chroma window of this block: lines 8 by + l, columns x_rel = 2 bx - 1 .. 2 bx + 2, i.e. pc = 2 bx + 3 .. 2 bx + 6
-  const unsigned *c_base = cpair + (8 * by) * F411_CPITCH + 2 * bx + 3;
+  const unsigned *c_base = cpair + (8 * o.by) * F411_CPITCH + 2 * o.bx + 3;
 #pragma unroll
   for (int l = 0; l < 8; l++) {
     const unsigned *p = c_base + l * F411_CPITCH;
@@ -1877,15 +1773,10 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused411_kernel(const Fuse
     int cb[4], cr[4], ub[8], ur[8];
 #pragma unroll
     for (int j = 0; j < 4; j++) { cb[j] = (int)(short)(w[j] & 0xffffu); cr[j] = (int)w[j] >> 16; }
-    // no vertical filter; the four-fold horizontal core on c[-1], c[0], c[1], c[2] = s[0..3]
-#define MIJ_HFILTER4(o, s)                                                                                   \
-    o[0] = f8(3, s[0], 5, s[1], 2); o[1] = f8(1, s[0], 7, s[1], 1); o[2] = f8(1, s[2], 7, s[1], 2); o[3] = f8(3, s[2], 5, s[1], 1); \
-    o[4] = f8(3, s[1], 5, s[2], 2); o[5] = f8(1, s[1], 7, s[2], 1); o[6] = f8(1, s[3], 7, s[2], 2); o[7] = f8(3, s[3], 5, s[2], 1);
-    MIJ_HFILTER4(ub, cb)
-    MIJ_HFILTER4(ur, cr)
-#undef MIJ_HFILTER4
-    if (l < nln) {
-      uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
+    // no vertical filter
+    hfilter4(cb, ub);
+    hfilter4(cr, ur);
+    if (l < o.nln) {
       int rr[8], gg[8], bb[8];
 #pragma unroll
       for (int x = 0; x < 8; x++) {
@@ -1894,20 +1785,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused411_kernel(const Fuse
         bb[x] = mad24(ub[x], L_CB_B, yk);
         gg[x] = mad24(ur[x], -L_CR_G, mad24(ub[x], -L_CB_G, yk));
       }
-      if (fast_store) {
-        unsigned wd[6];
-        rgb_shift17_sat_pack(rr, gg, bb, wd);
-        u32x2_any *d2 = reinterpret_cast<u32x2_any *>(dst);
-        __builtin_nontemporal_store(u32x2{wd[0], wd[1]}, d2);
-        __builtin_nontemporal_store(u32x2{wd[2], wd[3]}, d2 + 1);
-        __builtin_nontemporal_store(u32x2{wd[4], wd[5]}, d2 + 2);
-      } else {
-#pragma unroll
-        for (int x = 0; x < 8; x++)
-          if (x < npx) {
-            dst[3 * x] = (uint8_t)clamp255(rr[x] >> 17); dst[3 * x + 1] = (uint8_t)clamp255(gg[x] >> 17); dst[3 * x + 2] = (uint8_t)clamp255(bb[x] >> 17);
-          }
-      }
+      store_rgb8_line<STORE24_3X8>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
     }
   }
 }
@@ -1926,15 +1804,11 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused440_kernel(const Fuse
   __shared__ __attribute__((aligned(16))) unsigned cpair[F440_CROWS * F440_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
-
-  const TilePos tp = tile_position(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
+  const TileCtx t = tile_enter(a, stage_all);
+  if (t.padding) return;
+  const int tid = t.tid, lane = t.lane, wave = t.wave, frame = t.frame, tx = t.tx, ty = t.ty;
+  u32x4 *stage = t.stage;
+  const int16_t *__restrict__ coef = t.coef;
 
   // ------------------------------------------------------------------ phase A: chroma -> LDS halves
   // line pr of the LDS plane is chroma line ty * 64 + pr - 1 (pr = 0 and 65: the lines above and below the tile)
@@ -2018,31 +1892,15 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused440_kernel(const Fuse
   }
 
   // ------------------------------------------------------------------ phase B: luma, upsampling, colour
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
   u32x4 rows[8];
-  {
-    const int16_t *__restrict__ plane = coef + a.off_y;
-    const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  }
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  if (X0 >= a.width || Y0 >= a.height) return; // no barrier below this point
+  fetch_tile_blocks(rows, t, coef + a.off_y, a.bw_y, a.bh_y);
+  const BlockOut o = block_out<3>(a, t);
+  if (o.outside) return; // no barrier below this point
   int yv[64];
   dequant_idct_sparse<!QDEV, true>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
 
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 3u;
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
   // chroma window of this block: lines pr = 4 by + m (+0 top, +1 cur, +2 bot), columns 8 bx + x
-  const unsigned *c_base = cpair + (4 * by) * F440_CPITCH + 8 * bx;
+  const unsigned *c_base = cpair + (4 * o.by) * F440_CPITCH + 8 * o.bx;
   auto load8 = [](const unsigned *p, unsigned (&d)[8]) {
     const u32x4 lo = *reinterpret_cast<const u32x4 *>(p), hi = *reinterpret_cast<const u32x4 *>(p + 4);
     d[0] = lo.x; d[1] = lo.y; d[2] = lo.z; d[3] = lo.w; d[4] = hi.x; d[5] = hi.y; d[6] = hi.z; d[7] = hi.w;
@@ -2070,7 +1928,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused440_kernel(const Fuse
           u[j] = tap13_pk(o, cC[j], (short)r);
         }
       }
-      if (l < nln) {
+      if (l < o.nln) {
         int rr[8], gg[8], bb[8];
 #pragma unroll
         for (int x = 0; x < 8; x++) {
@@ -2085,18 +1943,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused440_kernel(const Fuse
             gg[x] = dot2_16(u[x], -L_CB_G, -L_CR_G, yk);
           }
         }
-        if (fast_store) {
-          unsigned w[6];
-          rgb_shift17_sat_pack(rr, gg, bb, w);
-          store24_nt(out_frame, out_off + (unsigned)l * (unsigned)a.row_stride, w);
-        } else {
-          uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-#pragma unroll
-          for (int x = 0; x < 8; x++)
-            if (x < npx) {
-              dst[3 * x] = (uint8_t)clamp255(rr[x] >> 17); dst[3 * x + 1] = (uint8_t)clamp255(gg[x] >> 17); dst[3 * x + 2] = (uint8_t)clamp255(bb[x] >> 17);
-            }
-        }
+        store_rgb8_line<STORE24_NT>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
       }
     }
     // slide the three-line window
@@ -2120,9 +1967,6 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused440_kernel(const Fuse
 // below 2^31 (|row output| <= 16 M_r 725 / 512 with M_r the row's share of the sum, 725 = largest entry of the scaled
 // transform matrix; the column pass sees 22.7 M in total), so wrapping 32-bit and 24-bit-operand arithmetic agree.
 // The level shift 2^11 << 7 passes through both rounding shifts exactly and comes out as 2^15 (see dequant_idct).
-#ifndef FXT_PREFETCH
-#define FXT_PREFETCH 0
-#endif
 constexpr int FXT_MINW = 2;
 __global__ __launch_bounds__(F420_THREADS, FXT_MINW) void fusedxt420_kernel(const Fused420Args a, const FusedXtExtra x)
 {
@@ -2130,41 +1974,15 @@ __global__ __launch_bounds__(F420_THREADS, FXT_MINW) void fusedxt420_kernel(cons
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
   __shared__ int ltab[3 * 256];
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
-
-  const TilePos tp = tile_position<XT_TILE_ORDER>(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-  const int X0 = (gbx0 + bx) * 8, Y0 = (ty * F420_TILE_BLOCKS + by) * 8;
+  const TileCtx t = tile_enter<XT_TILE_ORDER>(a, stage_all);
+  if (t.padding) return;
+  const int16_t *__restrict__ coef = t.coef;
   u32x4 rows[8];
-  // the wave's 16 x 4 blocks of a plane of bw x bh blocks: local block n = (lane >> 3) + 8 m sits at column
-  // (lane >> 3) + 8 (m & 1), row m >> 1; blocks outside the plane are redirected to a valid one and never used
-  auto load_plane = [&](u32x4 (&raw)[8], const int16_t *__restrict__ plane, int bw, int bh) {
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    load_blocks(raw, [&](int m) -> const u32x4 * {
-      const int xx = min(x0 + 8 * (m & 1), bw - 1), yy = min(gby0 + (m >> 1), bh - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * bw + xx) * 128));
-    });
-  };
-  // FXT_PREFETCH (A-B builds): a plane's blocks are requested while the plane before them is transformed (two waves per SIMD hide
-  // little of a fetch by themselves), the first residual plane's in front of phase A
-#if FXT_PREFETCH
-  u32x4 rawA[8], rawB[8];
-  load_plane(rawA, coef + x.off_r[0], x.bw_r, x.bh_r);
-#endif
 
-  for (int i = tid; i < 3 * 256; i += F420_THREADS) ltab[i] = x.ltable[i] - x.out_shift; // the merge subtracts it anyway
-  f420_chroma_to_lds<true, false, true>(a, coef, cplane, stage, lane, wave, tx, ty); // (the legacy frame passed the 16384 range check: plan_reconstruct)
+  for (int i = t.tid; i < 3 * 256; i += F420_THREADS) ltab[i] = x.ltable[i] - x.out_shift; // the merge subtracts it anyway
+  f420_chroma_to_lds<true, false, true>(a, t, cplane); // (the legacy frame passed the 16384 range check: plan_reconstruct)
   __syncthreads();
-  f420_chroma_edges(a, cplane, tid, tx, ty);
+  f420_chroma_edges(a, cplane, t.tid, t.tx, t.ty);
 
   // ------------------------------------------------------------------ residual blocks -> packed, clamped samples
   unsigned rp0[32], rp1[32], rp2[32];
@@ -2180,52 +1998,24 @@ __global__ __launch_bounds__(F420_THREADS, FXT_MINW) void fusedxt420_kernel(cons
     }
   };
   int yv[64];
-#if FXT_PREFETCH
-  load_plane(rawB, coef + x.off_r[1], x.bw_r, x.bh_r);
-  __builtin_amdgcn_sched_barrier(0);
-  transpose_blocks(rows, stage, lane, rawA);
+  // (a plane's blocks are requested when the plane before them has been transformed; requesting them one plane ahead was measured
+  // and not adopted: profiles/r06/xt_packed_ab.txt)
+  fetch_tile_blocks(rows, t, coef + x.off_r[0], x.bw_r, x.bh_r);
   residual_rows(x.rq[0], rp0);
-  load_plane(rawA, coef + x.off_r[2], x.bw_r, x.bh_r);
-  __builtin_amdgcn_sched_barrier(0);
-  transpose_blocks(rows, stage, lane, rawB);
+  fetch_tile_blocks(rows, t, coef + x.off_r[1], x.bw_r, x.bh_r);
   residual_rows(x.rq[1], rp1);
-  load_plane(rawB, coef + a.off_y, a.bw_y, a.bh_y);
-  __builtin_amdgcn_sched_barrier(0);
-  transpose_blocks(rows, stage, lane, rawA);
+  fetch_tile_blocks(rows, t, coef + x.off_r[2], x.bw_r, x.bh_r);
   residual_rows(x.rq[2], rp2);
   // ------------------------------------------------------------------ legacy luma
-  transpose_blocks(rows, stage, lane, rawB);
+  fetch_tile_blocks(rows, t, coef + a.off_y, a.bw_y, a.bh_y);
   dequant_idct_sparse<true, true>(rows, a.q[0], yv, 0, LUMA_FOLD_R2);
-#else
-  auto fetch_plane = [&](const int16_t *__restrict__ plane, int bw, int bh) {
-    u32x4 raw[8];
-    load_plane(raw, plane, bw, bh);
-    transpose_blocks(rows, stage, lane, raw);
-  };
-  fetch_plane(coef + x.off_r[0], x.bw_r, x.bh_r);
-  residual_rows(x.rq[0], rp0);
-  fetch_plane(coef + x.off_r[1], x.bw_r, x.bh_r);
-  residual_rows(x.rq[1], rp1);
-  fetch_plane(coef + x.off_r[2], x.bw_r, x.bh_r);
-  residual_rows(x.rq[2], rp2);
-  // ------------------------------------------------------------------ legacy luma
-  fetch_plane(coef + a.off_y, a.bw_y, a.bh_y);
-  dequant_idct_sparse<true, true>(rows, a.q[0], yv, 0, LUMA_FOLD_R2);
-#endif
 
-  const bool active = X0 < a.width && Y0 < a.height;
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 6u;
-  const int npx = min(8, a.width - X0);
-  const int nln = active ? min(8, a.height - Y0) : 0;
-  const bool fast_store = npx == 8;
+  // (every lane runs the merge: the L tables are read by all of them; a block outside the picture stores no line)
+  const BlockOut o = block_out<6>(a, t);
+  const int nln = o.outside ? 0 : o.nln;
 
-  const int *cb_base = cplane[0] + (4 * by) * F420_CPITCH + 4 * bx;
-  const int *cr_base = cplane[1] + (4 * by) * F420_CPITCH + 4 * bx;
-  auto load6 = [](const int *p, int (&d)[6]) {
-    const i32x4 mid = *reinterpret_cast<const i32x4 *>(p + 4);
-    d[0] = p[3]; d[1] = mid.x; d[2] = mid.y; d[3] = mid.z; d[4] = mid.w; d[5] = p[8];
-  };
+  const int *cb_base = cplane[0] + (4 * o.by) * F420_CPITCH + 4 * o.bx;
+  const int *cr_base = cplane[1] + (4 * o.by) * F420_CPITCH + 4 * o.bx;
   // constants of the merge (see xt_merge_kernel)
   const int pinf = (x.out_max >> 1) - (x.out_max >> 6) - 1, minf = -pinf - 1; // largest finite half 0x7bff, and its mirror
   const unsigned pinf2 = (unsigned)pinf * 0x10001u, minf2 = ((unsigned)minf & 0xffffu) * 0x10001u;
@@ -2248,18 +2038,8 @@ __global__ __launch_bounds__(F420_THREADS, FXT_MINW) void fusedxt420_kernel(cons
         vr[j] = tap13(half ? crB[j] : crT[j], crC[j], rnd);
       }
       int ub[8], ur[8];
-      auto hfilt = [](const int (&v)[6], int (&o)[8]) {
-        o[7] = tap13(v[5], v[4], 1);
-        o[6] = tap13(v[3], v[4], 2);
-        o[5] = tap13(v[4], v[3], 1);
-        o[4] = tap13(v[2], v[3], 2);
-        o[3] = tap13(v[3], v[2], 1);
-        o[2] = tap13(v[1], v[2], 2);
-        o[1] = tap13(o[2], v[1], 1); // src[1] has already been overwritten by out[2]
-        o[0] = tap13(v[0], v[1], 2);
-      };
-      hfilt(vb, ub);
-      hfilt(vr, ur);
+      hfilter8(vb, ub);
+      hfilter8(vr, ur);
       int mm[24]; // legacy + residual - output shift, R G B of the eight pixels
 #pragma unroll
       for (int xx = 0; xx < 8; xx++) {
@@ -2311,17 +2091,7 @@ __global__ __launch_bounds__(F420_THREADS, FXT_MINW) void fusedxt420_kernel(cons
           w[i] = (unsigned)min(max(mm[2 * i], 0), x.out_max) | ((unsigned)min(max(mm[2 * i + 1], 0), x.out_max) << 16);
         }
       }
-      if (l < nln) {
-        uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-        if (fast_store) {
-          store48<FXT_TEMPORAL != 0>(dst, w);
-        } else {
-          unsigned short *d16 = reinterpret_cast<unsigned short *>(dst);
-#pragma unroll
-          for (int k = 0; k < 24; k++)
-            if (k < 3 * npx) d16[k] = (unsigned short)(w[k >> 1] >> ((k & 1) * 16));
-        }
-      }
+      if (l < nln) store_codes16_line(o.out_frame + o.line_off(l, a), w, o.fast_store, o.npx);
     }
 #pragma unroll
     for (int j = 0; j < 6; j++) { cbT[j] = cbC[j]; cbC[j] = cbB[j]; crT[j] = crC[j]; crC[j] = crB[j]; }
@@ -2363,9 +2133,6 @@ __device__ __forceinline__ void idct_column_quadwrap(int &s0, int &s1, int &s2, 
 // them per CU, and a register budget of 256 (profiles/r05/xt_kernels.txt has round 5's counters; profiles/r06/xt_kernels.txt these).
 // LUMA_LDS = false is round 5's kernel (one wave per SIMD, the luma block in registers): legacy frames whose luma leaves the
 // int16 line (sum |c| q >= 7600 -- 4 * that + 2056 must stay below 2^15: no photograph, but nothing forbids it) keep it.
-#ifndef XTW_HALF_BARRIER
-#define XTW_HALF_BARRIER 1
-#endif
 template <bool LUMA_LDS>
 __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_kernel(const Fused420Args a, const FusedXtExtra x)
 {
@@ -2375,35 +2142,20 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
   __shared__ ltab_t ltab[3 * 256];
   __shared__ __attribute__((aligned(16))) u32x4 luma_lines[LUMA_LDS ? 8 * F420_THREADS : 1]; // [line][thread]: 8 x int16, no two lanes on one bank
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
-
-  const TilePos tp = tile_position<XT_TILE_ORDER>(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
+  const TileCtx t = tile_enter<XT_TILE_ORDER>(a, stage_all);
+  if (t.padding) return;
+  const int tid = t.tid;
+  const int16_t *__restrict__ coef = t.coef;
 
   for (int i = tid; i < 3 * 256; i += F420_THREADS) ltab[i] = (ltab_t)(x.ltable[i] - x.out_shift);
-  f420_chroma_to_lds<true, false, true>(a, coef, cplane, stage, lane, wave, tx, ty); // (the legacy frame passed the 16384 range check: plan_reconstruct)
+  f420_chroma_to_lds<true, false, true>(a, t, cplane); // (the legacy frame passed the 16384 range check: plan_reconstruct)
   __syncthreads();
-  f420_chroma_edges(a, cplane, tid, tx, ty);
+  f420_chroma_edges(a, cplane, tid, t.tx, t.ty);
 
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-  const int X0 = (gbx0 + bx) * 8, Y0 = (ty * F420_TILE_BLOCKS + by) * 8;
   u32x4 rows[8];
 
   // ------------------------------------------------------------------ legacy luma
-  {
-    const int x0 = gbx0 + (lane >> 3);
-    const char *pbase = reinterpret_cast<const char *>(coef + a.off_y) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int xx = min(x0 + 8 * (m & 1), a.bw_y - 1), yy = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_y + xx) * 128));
-    });
-  }
+  fetch_tile_blocks(rows, t, coef + a.off_y, a.bw_y, a.bh_y);
   int yv[LUMA_LDS ? 1 : 64];
   if constexpr (LUMA_LDS) {
     int yw[64];
@@ -2440,12 +2192,7 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
     int v[64];
 #pragma unroll
     for (int h = 0; h < 2; h++) { // coefficients 32 h .. 32 h + 31 of every block: rows 4 h .. 4 h + 3
-      const int x0 = gbx0 + (lane >> 3);
-      const char *pbase = plane + (lane & 7) * 16 + h * 128;
-      fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-        const int xx = min(x0 + 8 * (m & 1), x.bw_r - 1), yy = min(gby0 + (m >> 1), x.bh_r - 1);
-        return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * x.bw_r + xx) * 256));
-      });
+      fetch_tile_blocks<256>(rows, t, plane + h * 128, x.bw_r, x.bh_r);
 #pragma unroll
       for (int k = 0; k < 8; k++) {
         const int base = 32 * h + 4 * k;
@@ -2454,7 +2201,7 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
         v[base + 2] = __mul24((int)rows[k].z, q[base + 2]);
         v[base + 3] = __mul24((int)rows[k].w, q[base + 3]);
       }
-      if (LUMA_LDS && XTW_HALF_BARRIER) __builtin_amdgcn_sched_barrier(0); // (the second half's rows are not asked for before the first half's are spent)
+      if (LUMA_LDS) __builtin_amdgcn_sched_barrier(0); // (the second half's rows are not asked for before the first half's are spent)
     }
 #pragma unroll
     for (int r = 0; r < 8; r++)
@@ -2518,19 +2265,12 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
   residual_block(x.off_r[2], x.rq[2], 2);
   __builtin_amdgcn_sched_barrier(0);
 
-  const bool active = X0 < a.width && Y0 < a.height;
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 6u;
-  const int npx = min(8, a.width - X0);
-  const int nln = active ? min(8, a.height - Y0) : 0;
-  const bool fast_store = npx == 8;
+  // (every lane runs the merge: the L tables are read by all of them; a block outside the picture stores no line)
+  const BlockOut o = block_out<6>(a, t);
+  const int nln = o.outside ? 0 : o.nln;
 
-  const int *cb_base = cplane[0] + (4 * by) * F420_CPITCH + 4 * bx;
-  const int *cr_base = cplane[1] + (4 * by) * F420_CPITCH + 4 * bx;
-  auto load6 = [](const int *p, int (&d)[6]) {
-    const i32x4 mid = *reinterpret_cast<const i32x4 *>(p + 4);
-    d[0] = p[3]; d[1] = mid.x; d[2] = mid.y; d[3] = mid.z; d[4] = mid.w; d[5] = p[8];
-  };
+  const int *cb_base = cplane[0] + (4 * o.by) * F420_CPITCH + 4 * o.bx;
+  const int *cr_base = cplane[1] + (4 * o.by) * F420_CPITCH + 4 * o.bx;
   const int pinf = (x.out_max >> 1) - (x.out_max >> 6) - 1, minf = -pinf - 1;
   const unsigned pinf2 = (unsigned)pinf * 0x10001u, minf2 = ((unsigned)minf & 0xffffu) * 0x10001u;
 
@@ -2552,18 +2292,8 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
         vr[j] = tap13(half ? crB[j] : crT[j], crC[j], rnd);
       }
       int ub[8], ur[8];
-      auto hfilt = [](const int (&v)[6], int (&o)[8]) {
-        o[7] = tap13(v[5], v[4], 1);
-        o[6] = tap13(v[3], v[4], 2);
-        o[5] = tap13(v[4], v[3], 1);
-        o[4] = tap13(v[2], v[3], 2);
-        o[3] = tap13(v[3], v[2], 1);
-        o[2] = tap13(v[1], v[2], 2);
-        o[1] = tap13(o[2], v[1], 1); // src[1] has already been overwritten by out[2]
-        o[0] = tap13(v[0], v[1], 2);
-      };
-      hfilt(vb, ub);
-      hfilt(vr, ur);
+      hfilter8(vb, ub);
+      hfilter8(vr, ur);
       int mm[24];
       u32x4 yl = u32x4{0, 0, 0, 0};
       if constexpr (LUMA_LDS) yl = luma_lines[l * F420_THREADS + tid]; // (written by this lane: no barrier)
@@ -2617,17 +2347,7 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
           w[i] = (unsigned)min(max(mm[2 * i], 0), x.out_max) | ((unsigned)min(max(mm[2 * i + 1], 0), x.out_max) << 16);
         }
       }
-      if (l < nln) {
-        uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-        if (fast_store) {
-          store48<FXT_TEMPORAL != 0>(dst, w);
-        } else {
-          unsigned short *d16 = reinterpret_cast<unsigned short *>(dst);
-#pragma unroll
-          for (int k = 0; k < 24; k++)
-            if (k < 3 * npx) d16[k] = (unsigned short)(w[k >> 1] >> ((k & 1) * 16));
-        }
-      }
+      if (l < nln) store_codes16_line(o.out_frame + o.line_off(l, a), w, o.fast_store, o.npx);
     }
 #pragma unroll
     for (int j = 0; j < 6; j++) { cbT[j] = cbC[j]; cbC[j] = cbB[j]; crT[j] = crC[j]; crC[j] = crB[j]; }
@@ -2648,29 +2368,12 @@ template <int MINW, bool QDEV>
 __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(const Fused420Args a)
 {
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
-
-  const TilePos tp = tile_position(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
-  const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-  const int x0 = gbx0 + (lane >> 3);
+  const TileCtx t = tile_enter(a, stage_all);
+  if (t.padding) return;
+  const int frame = t.frame;
 
   // all three planes have the same geometry (bw_y x bh_y blocks)
-  auto fetch = [&](u32x4 (&rows)[8], int64_t plane_off) {
-    const char *pbase = reinterpret_cast<const char *>(coef + plane_off) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  };
+  auto fetch = [&](u32x4 (&rows)[8], int64_t plane_off) { fetch_tile_blocks(rows, t, t.coef + plane_off, a.bw_y, a.bh_y); };
 
   unsigned cbp[32], crp[32];
   {
@@ -2687,23 +2390,17 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(const Fuse
     for (int i = 0; i < 32; i++) crp[i] = pack_lo16_now(v[2 * i + 1], v[2 * i]);
     __builtin_amdgcn_sched_barrier(0);
   }
+  const BlockOut o = block_out<3>(a, t);
   int yv[64];
   {
     u32x4 rows[8];
     fetch(rows, a.off_y);
-    const int X0 = gbx * 8, Y0 = gby * 8;
-    if (X0 >= a.width || Y0 >= a.height) return;
+    if (o.outside) return;
     dequant_idct_sparse<!QDEV, true>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
   }
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 3u;
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
 #pragma unroll
   for (int l = 0; l < 8; l++) {
-    if (l < nln) {
+    if (l < o.nln) {
       int rr[8], gg[8], bb[8];
 #pragma unroll
       for (int x = 0; x < 8; x++) {
@@ -2719,19 +2416,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(const Fuse
           bb[x] = mad16_lo(cb2, L_CB_B, yk);
         }
       }
-      uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-      if (fast_store) {
-        unsigned w[6];
-        rgb_shift17_sat_pack(rr, gg, bb, w);
-        store24_3x8<F444_TEMPORAL != 0>(dst, w);
-        __builtin_amdgcn_sched_barrier(0); // one line at a time: do not interleave the lines' temporaries
-      } else {
-#pragma unroll
-        for (int x = 0; x < 8; x++)
-          if (x < npx) {
-            dst[3 * x] = (uint8_t)clamp255(rr[x] >> 17); dst[3 * x + 1] = (uint8_t)clamp255(gg[x] >> 17); dst[3 * x + 2] = (uint8_t)clamp255(bb[x] >> 17);
-          }
-      }
+      // (LINE_BY_LINE: one line at a time -- do not interleave the lines' temporaries)
+      store_rgb8_line<STORE24_3X8, true>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
     }
   }
 }
@@ -2744,28 +2430,12 @@ template <bool QDEV, bool N12>
 __global__ __launch_bounds__(F420_THREADS, 2) void fused444_12_kernel(const Fused420Args a)
 {
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
+  const TileCtx t = tile_enter(a, stage_all);
+  if (t.padding) return;
+  const int frame = t.frame;
+  auto fetch = [&](u32x4 (&rows)[8], int64_t plane_off) { fetch_tile_blocks(rows, t, t.coef + plane_off, a.bw_y, a.bh_y); };
 
-  const TilePos tp = tile_position(blockIdx.x, a);
-  if (tp.frame < 0) return;
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
-  const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-  const int x0 = gbx0 + (lane >> 3);
-  auto fetch = [&](u32x4 (&rows)[8], int64_t plane_off) {
-    const char *pbase = reinterpret_cast<const char *>(coef + plane_off) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  };
-
+  const BlockOut o = block_out<6>(a, t);
   int cb[64], cr[64], yv[64];
   {
     u32x4 rows[8];
@@ -2776,43 +2446,16 @@ __global__ __launch_bounds__(F420_THREADS, 2) void fused444_12_kernel(const Fuse
     dequant_idct_sparse<false>(rows, frame_deltas<QDEV>(a, frame, 2), cr);
     __builtin_amdgcn_sched_barrier(0);
     fetch(rows, a.off_y);
-  
-    if (gbx * 8 >= a.width || gby * 8 >= a.height) return;
+    if (o.outside) return;
     dequant_idct_sparse<false>(rows, frame_deltas<QDEV>(a, frame, 0), yv);
   }
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * 6u;
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
-  static_assert(L_CB_B % 4 == 0, "the blue product is taken at a quarter of the constant");
-  auto c12 = [](int v) { return (unsigned)min(max(v, 0), 4095); };
 #pragma unroll
   for (int l = 0; l < 8; l++) {
-    if (l < nln) {
+    if (l < o.nln) {
       int rr[8], gg[8], bb[8];
 #pragma unroll
       for (int x = 0; x < 8; x++) colour12<N12>(yv[l * 8 + x], cb[l * 8 + x], cr[l * 8 + x], rr[x], gg[x], bb[x]);
-      uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-      if (fast_store) {
-        unsigned w[12]; // 48 bytes r0 g0 b0 r1 ... b7, 16-bit samples
-#pragma unroll
-        for (int x = 0; x < 8; x += 2) {
-          w[3 * (x / 2) + 0] = c12(rr[x]) | (c12(gg[x]) << 16);
-          w[3 * (x / 2) + 1] = c12(bb[x]) | (c12(rr[x + 1]) << 16);
-          w[3 * (x / 2) + 2] = c12(gg[x + 1]) | (c12(bb[x + 1]) << 16);
-        }
-        store48(dst, w);
-        __builtin_amdgcn_sched_barrier(0); // one line at a time
-      } else {
-        uint16_t *d16 = reinterpret_cast<uint16_t *>(dst);
-#pragma unroll
-        for (int x = 0; x < 8; x++)
-          if (x < npx) {
-            d16[3 * x] = (uint16_t)c12(rr[x]); d16[3 * x + 1] = (uint16_t)c12(gg[x]); d16[3 * x + 2] = (uint16_t)c12(bb[x]);
-          }
-      }
+      store_rgb12_line<F12_TEMPORAL, true>(o.out_frame + o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx); // (one line at a time)
     }
   }
 }
@@ -2829,37 +2472,19 @@ template <bool QDEV, int P = 8>
 __global__ __launch_bounds__(F420_THREADS, 4) void fused1_kernel(const Fused420Args a)
 {
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  u32x4 *stage = stage_all[wave];
+  const TileCtx t = tile_enter<1>(a, stage_all);
+  if (t.padding) return;
 
-  const TilePos tp = tile_position<1>(blockIdx.x, a); // (tile order: see there)
-  if (tp.frame < 0) return; // the launch is padded to whole groups of eight tile rows
-  const int frame = tp.frame, ty = tp.ty, tx = tp.tx;
-  const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-
-  const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
-  const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-  const int x0 = gbx0 + (lane >> 3);
   u32x4 rows[8];
-  {
-    const char *pbase = reinterpret_cast<const char *>(coef + a.off_y) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), a.bw_y - 1), y = min(gby0 + (m >> 1), a.bh_y - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * a.bw_y + x) * 128));
-    });
-  }
-  const int X0 = gbx * 8, Y0 = gby * 8;
-  if (X0 >= a.width || Y0 >= a.height) return;
+  fetch_tile_blocks(rows, t, t.coef + a.off_y, a.bw_y, a.bh_y);
+  const BlockOut o = block_out<P == 12 ? 2 : 1>(a, t);
+  if (o.outside) return;
   int v[64];
-  dequant_idct_sparse<!QDEV && P == 8>(rows, frame_deltas<QDEV>(a, frame, 0), v);
-  uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
-  const unsigned out_off = (unsigned)Y0 * (unsigned)a.row_stride + (unsigned)X0 * (P == 12 ? 2u : 1u);
-  const int npx = min(8, a.width - X0);
-  const int nln = min(8, a.height - Y0);
-  const bool fast_store = npx == 8;
+  dequant_idct_sparse<!QDEV && P == 8>(rows, frame_deltas<QDEV>(a, t.frame, 0), v);
+  uint8_t *__restrict__ out_frame = o.out_frame;
+  const unsigned out_off = o.out_off;
+  const int npx = o.npx, nln = o.nln;
+  const bool fast_store = o.fast_store;
   if (P == 12) {
     // COLOR_TO_INT with the level shift 2^11 << 4 the transform left out: (x + 32768 + 8) >> 4, clamped to [0, 4095]
 #pragma unroll
@@ -3339,9 +2964,7 @@ __device__ __forceinline__ int pick4(const int (&v)[MAXC], int c) { return c == 
 // sample and the column right of its last one exist in memory, image-edge tiles fill them with the replicated edge sample
 // (upsamplerbase.cpp:322-323), and phase B reads its columns without clamping any of them.
 constexpr int TILE_PAD = 8;
-#ifndef TILE_MINW
-#define TILE_MINW 3
-#endif
+constexpr int TILE_MINW = 3; // workgroups per CU of fused_tile_kernel
 
 // (wn n + wc c + r) >> sh: vertical filter with the phase's weights as data
 template <bool FAST>
@@ -3471,9 +3094,6 @@ __device__ __forceinline__ void tile_plane_line(const T *planes, const TileComp 
   }
 }
 
-#ifndef TILE_STRIP
-#define TILE_STRIP 1
-#endif
 template <bool FAST, bool NARROW>
 __global__ __launch_bounds__(256, TILE_MINW) void fused_tile_kernel(const GenericArgs a)
 {
@@ -3524,7 +3144,6 @@ __global__ __launch_bounds__(256, TILE_MINW) void fused_tile_kernel(const Generi
   // the (component, 64 blocks) chunks of the tile go to the four waves in turn: every wave transforms a quarter of the
   // tile's blocks whatever the components' sizes are.  One copy of the code for all components (the component is a uniform
   // run-time value here: phase A alone would otherwise be four times three transforms long).
-#ifndef TILE_SKIP_A // (A-B measurements: phase B alone)
   for (int chunk = wave; chunk < chunks; chunk += 4) {
     int c = 0, k = chunk;
 #pragma unroll
@@ -3564,7 +3183,6 @@ __global__ __launch_bounds__(256, TILE_MINW) void fused_tile_kernel(const Generi
       }
     }
   }
-#endif
   __syncthreads();
   if (edge) { // (uniform) tiles on the left / right image edge: the replicated columns of the horizontally subsampled planes
 #pragma unroll
@@ -3584,10 +3202,6 @@ __global__ __launch_bounds__(256, TILE_MINW) void fused_tile_kernel(const Generi
     __syncthreads();
   }
   // ------------------------------------------------------------------ phase B: lines of 8-pixel groups
-#ifdef TILE_SKIP_B // (A-B measurements: phase A alone)
-  if (tid == 0) a.out[(int64_t)frame * a.out_frame_stride + (int64_t)py0 * a.row_stride + px0] = (uint8_t)planes[base[0]];
-  return;
-#endif
   const int groups = (px1 - px0 + 8) >> 3, lines = py1 - py0 + 1;
   const int sb = a.sample_bytes;
   uint8_t *__restrict__ out_frame = a.out + (int64_t)frame * a.out_frame_stride;
@@ -3608,18 +3222,13 @@ __global__ __launch_bounds__(256, TILE_MINW) void fused_tile_kernel(const Generi
   // one instance per component count: the loops over components and the sample packing have static shapes
   auto phase_b = [&](auto NCc) {
     constexpr int NC = decltype(NCc)::value;
-    // A lane owns TILE_STRIP consecutive lines of one 8-pixel group (what depends on the column alone -- the group's place in every
-    // plane, the horizontal phase -- is then worked out once per strip).  The product is 1: strips of 2 and 4 lines measured 2-6 %
-    // SLOWER on every layout in round 6 (the stores of a wave spread over more lines; profiles/r06/tile_strips.txt); the switch
-    // stays for A-B builds.
-    const int strips = (lines + TILE_STRIP - 1) / TILE_STRIP;
-    for (int it = tid; it < groups * strips; it += 256) {
-      const int st = div_recip(it, rgroups), g = mad24(st, -groups, it);
+    // A lane owns one line of one 8-pixel group at a time: strips of 2 and 4 consecutive lines per lane measured 2-6 % SLOWER on
+    // every layout in round 6 (the stores of a wave spread over more lines; profiles/r06/tile_strips.txt).
+    const int items = lines * groups;
+    for (int it = tid; it < items; it += 256) {
+      const int ly = div_recip(it, rgroups), g = mad24(ly, -groups, it);
       const int X0 = px0 + 8 * g;
-#pragma unroll
-     for (int sub = 0; sub < TILE_STRIP; sub++) {
-      const int ly = st * TILE_STRIP + sub, Y = py0 + ly;
-      if (TILE_STRIP > 1 && ly >= lines) break;
+      const int Y = py0 + ly;
       int s[NC][8];
 #pragma unroll
       for (int c = 0; c < NC; c++) tile_plane_line<FAST, T>(planes, comp[c], X0, Y, s[c]);
@@ -3711,7 +3320,6 @@ __global__ __launch_bounds__(256, TILE_MINW) void fused_tile_kernel(const Generi
           }
         }
       }
-     }
     }
   };
   if (a.ncomp == 1) phase_b(std::integral_constant<int, 1>{});
@@ -4049,9 +3657,7 @@ __global__ __launch_bounds__(256) void bypass_planes_kernel(const GenericArgs a)
 // permutation of those: a 4 x 4 byte transpose for four components (8 v_perm_b32 per 4 pixels), 6 per 4 pixels for three.
 // Algorithmic bytes: 2 NC in + NC out per pixel (CMYK 12, RGB 9).  The tile kernel took these layouts through LDS before
 // (CMYK 0.49 of 8 TB/s).
-#ifndef FLAT4_MINW
-#define FLAT4_MINW 2 // four components: 64 packed dwords + a transform's 96 do not fit the 170 registers of three workgroups per CU
-#endif
+constexpr int FLAT4_MINW = 2; // four components: 64 packed dwords + a transform's 96 do not fit the 170 registers of three workgroups per CU
 template <int NC>
 __global__ __launch_bounds__(F420_THREADS, NC == 4 ? FLAT4_MINW : 3) void fused_flat_kernel(const GenericArgs a)
 {
@@ -4070,23 +3676,17 @@ __global__ __launch_bounds__(F420_THREADS, NC == 4 ? FLAT4_MINW : 3) void fused_
   const int ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
   const int16_t *__restrict__ coef = a.coef + (int64_t)frame * a.coef_frame_stride;
 
+  const TileCtx t = {tid, lane, wave, stage, frame, tx, ty, coef, false};
   const int bx = lane & 15, by = wave * 4 + (lane >> 4);
-  const int gbx = tx * F420_TILE_BLOCKS + bx, gby = ty * F420_TILE_BLOCKS + by;
-  const int gbx0 = tx * F420_TILE_BLOCKS, gby0 = ty * F420_TILE_BLOCKS + wave * 4;
-  const int x0 = gbx0 + (lane >> 3);
   const int bw = a.bw[0], bh = a.bh[0]; // every plane has the same geometry
-  const int X0 = gbx * 8, Y0 = gby * 8;
+  const int X0 = (tx * F420_TILE_BLOCKS + bx) * 8, Y0 = (ty * F420_TILE_BLOCKS + by) * 8;
 
   unsigned pk[NC][16]; // component c, pixels 4 k .. 4 k + 3 of the block (row k / 2, half k % 2)
 #pragma unroll
   for (int c = 0; c < NC; c++) {
     u32x4 rows[8];
     int v[64];
-    const char *pbase = reinterpret_cast<const char *>(coef + a.coef_off[c]) + (lane & 7) * 16;
-    fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-      const int x = min(x0 + 8 * (m & 1), bw - 1), y = min(gby0 + (m >> 1), bh - 1);
-      return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((y * bw + x) * 128));
-    });
+    fetch_tile_blocks(rows, t, coef + a.coef_off[c], bw, bh);
     if (c == NC - 1 && (X0 >= a.width || Y0 >= a.height)) return; // (no barrier in this kernel; the last fetch needed every lane)
     // level shift inside, + 8 of COLOR_TO_INT in the second pass's rounding constant: v = sample * 16 + 8
     dequant_idct_sparse<true>(rows, a.q[c], v, a.dcoff[c], 2048 + (8 << 12));
@@ -4161,12 +3761,6 @@ static Fused420Args with_tile_magic(const Fused420Args &a0)
   return a;
 }
 
-#ifndef F420_FAST_MINW
-#define F420_FAST_MINW 2 // workgroups per CU of the unpacked 4:2:0 kernel, fast flavour (A-B builds)
-#endif
-#ifndef F420_12_MINW
-#define F420_12_MINW 2
-#endif
 // The steps every fused launch shares: tile magic, the grid in the kernel's tile order, nothing to launch on an empty grid,
 // the error check
 template <int ORDER = MIJ_TILE_ORDER, typename... Extra>
