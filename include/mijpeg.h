@@ -418,6 +418,71 @@ int mijpeg_device_walk_rounds(mijpeg_decoder *d);
 /* Seconds spent in the phases of the last decode (huffman, h2d, kernel, d2h) -- diagnostics. */
 int mijpeg_last_timing(mijpeg_decoder *d, double out_seconds[4]);
 
+/* ---- ragged batches: n streams of ANY shapes in one device pass ---------------------------------------------------
+ * A folder of photographs instead of a film: the streams differ in width, height and sampling.  mijpeg_decode_ragged_device
+ * parses them in parallel and sorts the ones the batch kernels cover -- 8-bit Huffman sequential, one interleaved scan (or one
+ * component), intact, plain JPEG, in the layouts 4:2:0, 4:2:2, 4:4:4 and grey -- into one LAYOUT GROUP per layout.  Each group
+ * is entropy-decoded by ONE launch of the Huffman kernel (streams without restart markers: the device walk in front of it; too
+ * small for the walk: one interval, one lane) into coefficient stores packed back to back in the object's store, and
+ * mijpeg_reconstruct_ragged_device turns each group into pixels with one launch of the ragged flavour of its fused kernel per
+ * arithmetic flavour the range checks select, image i at dst_device[i] with row_strides[i] bytes per line.
+ * Every other stream -- progressive, 12 bit, other layouts, CMYK, DNL, JPEG XT, damaged -- takes the single-image route inside
+ * the same calls (a decoder object of its own that this one owns; its bytes are copied), so the caller gets all n pictures.
+ * status[i]: MIJPEG_OK or the JPGERR_* code of stream i; a stream in error does not stop the others, and the calls return
+ * MIJPEG_OK when they could work through the list.  min_intervals is handed to the single-image route (0: its default).
+ * What sends a stream to the single-image route is a property of that stream alone, with one exception: where a whole group's
+ * launch is refused -- its device walk does not settle within its rounds, or the group outgrows the launch's 32-bit offsets --
+ * every member of that group takes the single-image route (same pictures, counted as fallbacks).
+ * mijpeg_ragged_info: geometry and range check of image i after the decode (the caller sizes dst_device[i] from it);
+ * mijpeg_ragged_warning: the warning the single-image route left for image i, or NULL;
+ * mijpeg_ragged_route: 0 = image i was decoded by its group's launch, 1 = by the single-image route, *why says for what reason.
+ * Any other decode call on the object ends the ragged batch: its coefficient stores are reused. */
+int mijpeg_decode_ragged_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status);
+int mijpeg_ragged_info(mijpeg_decoder *d, int i, mijpeg_info *info);
+int mijpeg_ragged_warning(mijpeg_decoder *d, int i, const char **message);
+int mijpeg_ragged_route(mijpeg_decoder *d, int i, const char **why);
+/* dst_device and row_strides hold one entry per stream of the decode call; dst_device[i] == NULL (and images in error) are
+ * skipped.  An image whose own reconstruction fails (the single-image route, or a group image reconstructed by a launch of its
+ * own) does not stop the others: the call then returns the first such code, and mijpeg_last_error names the image.  A group
+ * launch that fails is the device's failure and ends the call. */
+int mijpeg_reconstruct_ragged_device(mijpeg_decoder *d, void *const *dst_device, const int64_t *row_strides, uint32_t flags, int sync);
+/* What the last mijpeg_decode_ragged_device + mijpeg_reconstruct_ragged_device of the object did. */
+typedef struct mijpeg_ragged_stats {
+  int32_t images;            /* streams of the call                                                          */
+  int32_t ragged;            /* ... entropy-decoded by a layout group's launch                                */
+  int32_t fallbacks;         /* ... that took the single-image route (those in error included)                */
+  int32_t errors;            /* ... whose status is an error                                                  */
+  int32_t entropy_launches;  /* launches of the Huffman kernel for the groups                                  */
+  int32_t walk_launches;     /* launches of the walk kernel (its rounds and the emitting pass), all groups     */
+  int32_t recon_launches;    /* ragged reconstruction launches (one per group and arithmetic flavour)          */
+  int32_t recon_single;      /* group images reconstructed by a launch of their own (no ragged flavour fits)   */
+} mijpeg_ragged_stats;
+int mijpeg_ragged_get_stats(mijpeg_decoder *d, mijpeg_ragged_stats *out);
+/* The planner behind the two calls, on its own (no device, no decoder object): n frame descriptions (as mijpeg_read_header or
+ * mijpeg_frame_layout fill them) -> group[i] (MIJPEG_RAGGED_420 ... _GREY, or -1: the single-image route) and, for group members,
+ * frames[i]: the frame's entry of the descriptor table.  Members of a group follow each other in list order; frame i occupies
+ * the workgroups [first_workgroup, first_workgroup + tiles_x * tiles_y) of its group's launch -- tiles of 128 x 128 pixels, row
+ * by row, no padding -- and coef_count coefficients from coef_base in the store, whose size *coef_total receives.
+ * group_workgroups[g]: the grid of group g.  (Where the range checks split a group into arithmetic flavours, each launch numbers
+ * its own frames the same way.)  MIJPEG_ERR_INVALID_PARAMETER for n < 1 or NULL lists. */
+#define MIJPEG_RAGGED_420 0
+#define MIJPEG_RAGGED_422 1
+#define MIJPEG_RAGGED_444 2
+#define MIJPEG_RAGGED_GREY 3
+#define MIJPEG_RAGGED_GROUPS 4
+typedef struct mijpeg_ragged_frame {
+  int64_t coef_base;               /* int16 index of the frame's coefficient store                       */
+  int64_t off_y, off_cb, off_cr;   /* its planes inside that store                                        */
+  int32_t first_workgroup;
+  int32_t tiles_x, tiles_y;
+  int32_t width, height;
+  int32_t bw_y, bh_y, bw_c, bh_c;  /* plane sizes in blocks (MCU padded)                                  */
+  int32_t cw, ch;                  /* valid chroma samples                                                */
+  int32_t reserved;
+} mijpeg_ragged_frame;
+int mijpeg_ragged_plan(const mijpeg_info *infos, int n, int32_t *group, mijpeg_ragged_frame *frames, int32_t group_workgroups[MIJPEG_RAGGED_GROUPS],
+                       int64_t *coef_total);
+
 /* ---- stateless device entry points (inputs and outputs resident in HBM) -------------------- */
 
 /* Describes a batch of equally shaped frames whose coefficient planes are already on the device. */

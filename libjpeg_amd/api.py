@@ -29,6 +29,7 @@ FLAG_FORCE_DOT2 = 64  # (testing) the packed 4:2:0 kernel's 16-bit second pass w
 
 ERR_DEVICE = -8191
 ERR_NOT_AVAILABLE = -1029
+ERR_INVALID_PARAMETER = -1024
 
 
 class MijpegInfo(C.Structure):
@@ -73,6 +74,18 @@ class MijpegForwardBatch(C.Structure):
 
 class MijpegBitmap(C.Structure):
     _fields_ = [("data", C.c_void_p), ("bytes_per_pixel", C.c_int32), ("bytes_per_row", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class MijpegRaggedStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("images", "ragged", "fallbacks", "errors", "entropy_launches", "walk_launches", "recon_launches", "recon_single")]
+
+
+class MijpegRaggedFrame(C.Structure):
+    _fields_ = [("coef_base", C.c_int64), ("off_y", C.c_int64), ("off_cb", C.c_int64), ("off_cr", C.c_int64)] + \
+               [(k, C.c_int32) for k in ("first_workgroup", "tiles_x", "tiles_y", "width", "height", "bw_y", "bh_y", "bw_c", "bh_c", "cw", "ch", "reserved")]
+
+
+RAGGED_GROUPS = ("420", "422", "444", "grey")  # MIJPEG_RAGGED_420 ...
 
 
 class MijpegError(RuntimeError):
@@ -125,6 +138,13 @@ def lib():
         L.mijpeg_finish_batch_device.argtypes = [C.c_void_p]
         L.mijpeg_batch_speculation.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.mijpeg_reconstruct_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_uint32, C.c_int]
+        L.mijpeg_decode_ragged_device.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_int32)]
+        L.mijpeg_ragged_info.argtypes = [C.c_void_p, C.c_int, P(MijpegInfo)]
+        L.mijpeg_ragged_warning.argtypes = [C.c_void_p, C.c_int, P(C.c_char_p)]
+        L.mijpeg_ragged_route.argtypes = [C.c_void_p, C.c_int, P(C.c_char_p)]
+        L.mijpeg_reconstruct_ragged_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int]
+        L.mijpeg_ragged_get_stats.argtypes = [C.c_void_p, P(MijpegRaggedStats)]
+        L.mijpeg_ragged_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mijpeg_device_walk_rounds.argtypes = [C.c_void_p]
         L.mijpeg_device_walk_rounds.restype = C.c_int
         L.mijpeg_speculative_scans.argtypes = [C.POINTER(C.c_int64)]
@@ -473,6 +493,55 @@ class Decoder:
             _foreign_work_done()
         self._check(lib().mijpeg_reconstruct_batch_device(self._h, dst_ptr, frame_stride, row_stride, flags, 1 if sync else 0))
 
+    def decode_ragged_device(self, streams, min_intervals: int = 0) -> list[int]:
+        """mijpeg_decode_ragged_device: n streams of any shapes -> coefficient stores in HBM, one Huffman launch per layout group;
+        what the batch kernels do not cover takes the single-image route inside the call.  -> status code per stream (0 = decoded)."""
+        n = len(streams)
+        self._batch = list(streams)
+        arr = (C.c_char_p * n)(*self._batch)
+        sizes = (C.c_size_t * n)(*[len(s) for s in self._batch])
+        status = (C.c_int32 * n)()
+        self._check(lib().mijpeg_decode_ragged_device(self._h, arr, sizes, n, min_intervals, status))
+        self.ragged_images = n
+        return list(status)
+
+    def ragged_info(self, i: int) -> MijpegInfo:
+        """Geometry and range check of image i of the last ragged decode (raises the stream's error for one that has none)."""
+        info = MijpegInfo()
+        self._check(lib().mijpeg_ragged_info(self._h, i, C.byref(info)))
+        return info
+
+    def ragged_warning(self, i: int):
+        """-> (code, message) the single-image route left for image i, or (0, None)."""
+        msg = C.c_char_p()
+        code = lib().mijpeg_ragged_warning(self._h, i, C.byref(msg))
+        return code, (msg.value.decode() if msg.value else None)
+
+    def ragged_route(self, i: int):
+        """-> (True, None) when image i was decoded by its layout group's launch, (False, reason) for the single-image route."""
+        why = C.c_char_p()
+        rc = lib().mijpeg_ragged_route(self._h, i, C.byref(why))
+        if rc < 0:
+            self._check(rc)
+        return rc == 0, (why.value.decode() if why.value else None)
+
+    def reconstruct_ragged_device(self, dst_ptrs, row_strides, flags: int = 0, sync: bool = True, wait_foreign: bool = True):
+        """mijpeg_reconstruct_ragged_device: image i -> dst_ptrs[i] (0 / None: skipped) with row_strides[i] bytes per line; one entry
+        per stream of the decode call (the library walks that many)."""
+        n = len(dst_ptrs)
+        if n != getattr(self, "ragged_images", -1) or len(row_strides) != n:
+            raise ValueError(f"{n} destinations and {len(row_strides)} row strides for the {getattr(self, 'ragged_images', 0)} images of the ragged batch")
+        if wait_foreign:
+            _foreign_work_done()
+        dst = (C.c_void_p * n)(*[p or None for p in dst_ptrs])
+        rows = (C.c_int64 * n)(*row_strides)
+        self._check(lib().mijpeg_reconstruct_ragged_device(self._h, dst, rows, flags, 1 if sync else 0))
+
+    def ragged_stats(self) -> dict:
+        st = MijpegRaggedStats()
+        self._check(lib().mijpeg_ragged_get_stats(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MijpegRaggedStats._fields_}
+
     def reconstruct_unsampled(self, comp: int, flags: int = 0) -> np.ndarray:
         """JPGTAG_DECODER_UPSAMPLE = false: component `comp` on its own sample grid, no colour transformation
         (what the reference CLI's -U writes into out_<comp>.raw)."""
@@ -671,6 +740,23 @@ def encode_coefficients(info: MijpegInfo, coef: np.ndarray, restart_interval: in
         return C.string_at(p, n.value)
     finally:
         L.mijpeg_free(p)
+
+
+def ragged_plan(infos):
+    """mijpeg_ragged_plan (no device needed): frame descriptions -> (group per frame, -1 = single-image route; MijpegRaggedFrame per
+    frame; grid of the four layout groups; size of the packed coefficient store)."""
+    n = len(infos)
+    arr = (MijpegInfo * max(n, 1))()
+    for i, f in enumerate(infos):
+        C.memmove(C.byref(arr[i]), C.byref(f), C.sizeof(MijpegInfo))
+    group = (C.c_int32 * max(n, 1))()
+    frames = (MijpegRaggedFrame * max(n, 1))()
+    grids = (C.c_int32 * len(RAGGED_GROUPS))()
+    total = C.c_int64()
+    rc = lib().mijpeg_ragged_plan(arr, n, group, frames, grids, C.byref(total))
+    if rc:
+        raise MijpegError(rc, "mijpeg_ragged_plan failed")
+    return list(group), list(frames), list(grids), total.value
 
 
 def workspace_bytes(info: MijpegInfo, frames: int, flags: int = 0, own_tables: bool = False, xt: "MijpegXtParams | None" = None) -> int:

@@ -108,6 +108,25 @@ struct mijpeg_decoder {
   uint32_t spec_flags = 0;
   int32_t spec_assumed[MIJPEG_MAX_COMPONENTS] = {0, 0, 0, 0};
   int64_t spec_launched = 0, spec_redone_count = 0; // diagnostics (mijpeg_batch_speculation)
+  // ragged batches (mijpeg_decode_ragged_device): per image where its coefficients lie, or the decoder object of its own that
+  // took it through the single-image route; the launches of the last call
+  struct RaggedImage {
+    mijpeg_info info{};
+    int64_t coef_base = 0;     // int16 index in coef_dev
+    int group = -1;            // layout group, -1: single-image route (child) or in error (status)
+    int status = 0;
+    mijpeg_decoder *child = nullptr;
+    std::string why_single;    // why it left (or never entered) the layout groups
+  };
+  std::vector<RaggedImage> ragged;
+  std::vector<mijpeg_decoder *> ragged_children; // kept from call to call
+  std::vector<uint8_t> own_input;                // a child's copy of its stream (the caller's bytes are only read during the call)
+  hipEvent_t ragged_uploaded = nullptr;          // behind the upload of the descriptor tables (the pinned copy is free again)
+  bool ragged_upload_pending = false;
+  int ragged_n = 0;
+  mijpeg_ragged_stats ragged_stats{};
+  uint8_t *ragged_desc_dev = nullptr, *ragged_desc_host = nullptr; // frame descriptor tables of the reconstruction launches (pinned copy)
+  size_t ragged_desc_cap = 0, ragged_desc_host_cap = 0;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t chain_ev = nullptr; // mijpeg_stream_wait
@@ -181,11 +200,20 @@ struct MultiScanFrame {
   int64_t base16;   // offset of the frame's planes in coef_dev, in int16 units
 };
 
+// Images of different sizes in one launch of device_entropy_batch (they share components and sampling factors)
+struct RaggedEntropy {
+  const int64_t *coef_base; // per image: int16 index of its coefficient store in coef_dev
+  int *verdict;             // out, per image: 0 decoded (info carries its range check), 1 damaged: the single-image route decides
+  int *entropy_launches, *walk_launches; // counted up per launch of huffman_scan_kernel / huffman_walk_kernel (rounds and emitting pass)
+};
+
 const char *device_entropy_obstacle(const mij::HostDecoder &h, size_t size, bool xt_part = false);
+const char *ragged_entropy_obstacle(const mij::HostDecoder &h, size_t size);
 const char *multiscan_obstacle(const mij::HostDecoder &h, bool xt_part, bool residual_frame);
 size_t stream_slots(const size_t *sizes, int n, std::vector<size_t> &stream_off);
 int device_entropy_batch(mijpeg_decoder *d, mij::HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
-                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part = false, bool defer = false);
+                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part = false, bool defer = false,
+                         const RaggedEntropy *ragged = nullptr);
 int device_entropy_multiscan(mijpeg_decoder *d, const MultiScanFrame *frames, int nframes, int min_intervals);
 int evaluate_entropy_status(mijpeg_decoder *d, mij::HostDecoder *const *hosts, int n, const uint32_t *status_host);
 int walk_rounds_needed(const uint32_t *changed, int rounds);

@@ -38,6 +38,52 @@ const char *device_entropy_obstacle(const HostDecoder &h, size_t size, bool xt_p
   return nullptr;
 }
 
+// Why the restart markers of a parsed sequential stream keep it from the device (nullptr: they do not, or it has none): the
+// intervals the kernel decodes side by side must all be there, in sequence.
+static const char *restart_markers_obstacle(const HostDecoder &h)
+{
+  const Scan &s = h.scans[0];
+  if (s.restart_interval <= 0) return nullptr;
+  const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
+  const int64_t nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
+  if (nint > 0x7fffffff) return "too many restart intervals";
+  if ((int64_t)s.interval_begin.size() < nint)
+    return "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
+  const std::vector<uint8_t> &rst = h.restart_codes(0);
+  for (int64_t k = 0; k + 1 < nint; k++)
+    if (rst[(size_t)k] != 0xd0 + (k & 7))
+      return "restart markers out of sequence: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
+  return nullptr;
+}
+
+// ... and the device's copy of its entropy coded data (no byte stuffing, no markers): inside the kernels' bit addresses, no
+// larger than the stream it came from.  *code: what the refusal is (a copy larger than its stream is the caller's mistake).
+static const char *stream_copy_obstacle(const HostDecoder &h, size_t size, int *code)
+{
+  const size_t usize = h.scans[0].unstuffed_size;
+  *code = MIJPEG_ERR_NOT_AVAILABLE;
+  if (usize >= ((size_t)1 << 28)) return "entropy coded segment too large for the device decoder's bit addresses";
+  if (usize > size) { *code = MIJPEG_ERR_INVALID_PARAMETER; return "entropy coded segment larger than its stream"; }
+  return nullptr;
+}
+
+// Everything device_entropy_batch would refuse ONE parsed stream for, whatever its neighbours in the launch are (the same
+// checks, asked stream by stream before the groups are formed): what mijpeg_decode_ragged_device sends to the single-image
+// route, so that only the odd member leaves its layout group.  The scan must list the components in frame order -- a launch
+// shares the order, and this is the one every group can share.
+const char *ragged_entropy_obstacle(const HostDecoder &h, size_t size)
+{
+  int code;
+  if (const char *why = device_entropy_obstacle(h, size, false)) return why;
+  if (const char *why = restart_markers_obstacle(h)) return why;
+  if (const char *why = stream_copy_obstacle(h, size, &code)) return why;
+  const Scan &s = h.scans[0];
+  if (s.restart_interval > 0 && s.interval_ubegin.size() < s.interval_begin.size()) return "restart intervals missing";
+  for (int k = 0; k < s.ncomp; k++)
+    if (s.sc[k].comp != k) return "the scan lists its components out of frame order";
+  return nullptr;
+}
+
 namespace { // steps the sequential, progressive and walk paths share
 
 // Workgroups of the Huffman kernels hold four waves, one per SIMD: with two-wave workgroups (which round 1 chose for the LDS
@@ -177,7 +223,8 @@ int walk_verdict(mijpeg_decoder *d, const uint32_t *walk_status, int n)
 // `images_host` is the staging copy of the HuffImage array (first_interval = start of the image's interval entries).
 static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const std::vector<int> &dwalk, const HuffScanArgs &scan,
                               const HuffImage *images_dev, uint32_t *ibegin_dev, uint8_t *iskip_dev, int16_t *ipred_dev,
-                              const HuffImage *images_host, const std::vector<size_t> &usize, bool defer = false)
+                              const HuffImage *images_host, const std::vector<size_t> &usize, bool defer = false, bool per_image = false,
+                              int *walk_launches = nullptr)
 {
   const mijpeg_info &f0 = hosts[0]->info;
   const Scan &s0 = hosts[0]->scans[0];
@@ -238,6 +285,8 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   const size_t o_simg = L.take(G * 4), o_sfirst = L.take(G * 4);
   const size_t o_isub0 = L.take((size_t)n * 4), o_insub = L.take((size_t)n * 4), o_e0 = L.take((size_t)n * 4), o_e1 = L.take((size_t)n * 4);
   const size_t o_int0 = L.take((size_t)n * 4), o_state = L.take(S * 8);
+  // images of different sizes (per_image): blocks per virtual interval and blocks in all, image by image
+  const size_t o_every = L.take(per_image ? (size_t)n * 4 : 0), o_blocks = L.take(per_image ? (size_t)n * 4 : 0);
   const size_t o_up_end = L.end;
   const size_t o_flags = L.take((size_t)(MAX_ROUNDS + 1) * 4 + (size_t)n * 4); // changed[], walk_status[]
   const size_t o_stamp = L.take(S * 4);
@@ -261,6 +310,16 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   memcpy(wh + o_e0, img_e0.data(), (size_t)n * 4);
   memcpy(wh + o_e1, img_e1.data(), (size_t)n * 4);
   memcpy(wh + o_int0, img_int0.data(), (size_t)n * 4);
+  if (per_image) {
+    uint32_t *every = (uint32_t *)(wh + o_every), *blocks = (uint32_t *)(wh + o_blocks);
+    for (int i = 0; i < n; i++) {
+      const Scan &s = hosts[i]->scans[0];
+      every[i] = (uint32_t)(std::max(1, dwalk[(size_t)i]) * B);
+      blocks[i] = (uint32_t)((int64_t)s.mcus_x * s.mcus_y * B);
+    }
+    w.img_emit_every = (const uint32_t *)(d->walk_dev + o_every);
+    w.img_total_blocks = (const uint32_t *)(d->walk_dev + o_blocks);
+  }
   // the initial guess: every subsequence starts at its boundary (behind a stuffed zero if it falls on one) with the
   // first block of an MCU; for the first subsequence of an image that is no guess
   {
@@ -294,8 +353,14 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   w.ibegin = ibegin_dev;
   w.iskip = iskip_dev;
   w.ipred = ipred_dev;
-  const int64_t total_blocks = (int64_t)s0.mcus_x * s0.mcus_y * B;
-  w.total_blocks = (uint32_t)total_blocks;
+  if (!per_image) {
+    // one interval size and one block count for the launch: the images share their geometry, hence their MCUs per virtual interval
+    int per = 0;
+    for (int i = 0; i < n; i++)
+      if (dwalk[(size_t)i]) per = dwalk[(size_t)i];
+    w.emit_every = (uint32_t)(per * B);
+    w.total_blocks = (uint32_t)((int64_t)s0.mcus_x * s0.mcus_y * B);
+  }
   // rounds, launched back to back in bunches; between bunches the host looks at the flags: a round that changed no
   // hand-over state means the states are the fixed point (and the counts of the lanes' last walks belong to it)
   uint32_t *flags_host = (uint32_t *)(wh + o_up_end);
@@ -319,6 +384,7 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
     while (round < upto) {
       w.round = (uint32_t)++round;
       if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+      if (walk_launches) ++*walk_launches;
     }
     HIP_TRY(d, hipMemcpyAsync(flags_host, wd + o_flags, (size_t)(MAX_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream));
@@ -327,12 +393,8 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   }
   d->walk_rounds = defer ? 1 : walk_rounds_needed(flags_host, round);
   if (launch_huffman_walk_scan(w, n, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_scan_kernel launch");
-  // one interval size for the launch: the images share their geometry, hence their MCUs per virtual interval
-  int per = 0;
-  for (int i = 0; i < n; i++)
-    if (dwalk[(size_t)i]) per = dwalk[(size_t)i];
-  w.emit_every = (uint32_t)(per * B);
   if (launch_huffman_walk(w, true, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+  if (walk_launches) ++*walk_launches;
   d->walk_status_dev = w.walk_status;
   return MIJPEG_OK;
 }
@@ -404,10 +466,13 @@ static void build_dev_table(HuffDevTable &dst, const HuffTable &src, int mode)
   memcpy(dst.values, src.values, sizeof(dst.values));
 }
 
-// Entropy-decode n parsed images of identical frame geometry on the device, image i into coef_dev + i * frame_stride.
-// infos[i] receives fast_arith / range_max.  Returns MIJPEG_OK, MIJPEG_ERR_NOT_AVAILABLE (nothing touched) or an error.
+// Entropy-decode n parsed images on the device with one launch of huffman_scan_kernel (large uniform batches: one per upload
+// group).  Without `ragged`: images of identical frame geometry, image i into coef_dev + i * frame_stride.  With it: images that
+// share components and sampling factors but not their size, image i into coef_dev + ragged->coef_base[i], plane geometry per
+// image; a damaged image is reported in ragged->verdict[i] instead of failing the call.
+// hosts[i]->info receives fast_arith / range_max.  Returns MIJPEG_OK, MIJPEG_ERR_NOT_AVAILABLE (nothing touched) or an error.
 int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
-                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part, bool defer)
+                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part, bool defer, const RaggedEntropy *ragged)
 {
   const mijpeg_info &f0 = hosts[0]->info;
   const Scan &s0 = hosts[0]->scans[0];
@@ -415,6 +480,7 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   std::vector<int64_t> nints((size_t)n);
   std::vector<std::unique_ptr<VirtualIntervals>> virt((size_t)n); // restart points planned by the host's walk ...
   std::vector<int> dwalk((size_t)n, 0);                           // ... or MCUs per virtual interval when the device walks
+  std::vector<char> single((size_t)n, 0);                         // ragged launches: no restart markers, the image is ONE interval
   d->walk_rounds = 0;
   const bool device_walk = !(getenv("MIJPEG_DEVICE_WALK") && atoi(getenv("MIJPEG_DEVICE_WALK")) == 0);
   const auto tb0 = std::chrono::steady_clock::now();
@@ -423,12 +489,13 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
     if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
     const mijpeg_info &f = hosts[i]->info;
     const Scan &s = hosts[i]->scans[0];
-    if (f.width != f0.width || f.height != f0.height || f.components != f0.components || memcmp(f.hsamp, f0.hsamp, sizeof(f.hsamp)) ||
+    if (((f.width != f0.width || f.height != f0.height) && !ragged) || f.components != f0.components || memcmp(f.hsamp, f0.hsamp, sizeof(f.hsamp)) ||
         memcmp(f.vsamp, f0.vsamp, sizeof(f.vsamp)))
       return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share width, height and sampling factors");
     // ... and what the one reconstruction launch applies to all of them: the colour transformation (an Adobe marker may
     // switch it off per image), the sample precision, being a JPEG XT stream or not
-    if (f.ycbcr != f0.ycbcr || f.precision != f0.precision || f.xt != f0.xt)
+    // (a ragged launch is followed by reconstruction launches that look at every image's own colour transformation)
+    if ((f.ycbcr != f0.ycbcr && !ragged) || f.precision != f0.precision || f.xt != f0.xt)
       return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share colour transformation and precision");
     for (int k = 0; k < s.ncomp; k++)
       if (s.sc[k].comp != s0.sc[k].comp) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share the component order of their scan");
@@ -436,13 +503,11 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
     int64_t nint;
     if (s.restart_interval > 0) {
       nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
-      if (nint > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many restart intervals");
-      if ((int64_t)s.interval_begin.size() < nint)
-        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)");
-      const std::vector<uint8_t> &rst = hosts[i]->restart_codes(0);
-      for (int64_t k = 0; k + 1 < nint; k++)
-        if (rst[(size_t)k] != 0xd0 + (k & 7))
-          return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart markers out of sequence: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)");
+      if (const char *bad = restart_markers_obstacle(*hosts[i])) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, bad);
+    } else if (ragged && (total_mcus < 256 || s.ecs_end - s.ecs_begin < 4096)) {
+      // too small for the walk: one interval, one lane -- every MCU of the image in sequence, as a host thread would
+      single[(size_t)i] = 1;
+      nint = 1;
     } else {
       // no restart markers: the host's self-synchronising walk finds exact restart points ("virtual intervals"),
       // about 16 K of them, and the device decodes from there
@@ -463,7 +528,7 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
     total_intervals += nint;
   }
   if (min_intervals <= 0) min_intervals = 2048; // below this the device runs mostly idle
-  if (total_intervals < min_intervals || total_intervals > 0x7fffffff)
+  if ((total_intervals < min_intervals && !ragged) || total_intervals > 0x7fffffff)
     return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too few restart intervals to occupy the device");
 
   HuffScanArgs a;
@@ -515,9 +580,9 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   int64_t n_groups = 0;
   for (int i = 0; i < n; i++) {
     usize[(size_t)i] = hosts[i]->scans[0].unstuffed_size;
-    if (usize[(size_t)i] >= ((size_t)1 << 28)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "entropy coded segment too large for the device decoder's bit addresses");
-    if (usize[(size_t)i] > sizes[i]) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "entropy coded segment larger than its stream");
-    if (!dwalk[(size_t)i] && !virt[(size_t)i] && (int64_t)hosts[i]->scans[0].interval_ubegin.size() < nints[(size_t)i])
+    int why_code;
+    if (const char *why = stream_copy_obstacle(*hosts[i], sizes[i], &why_code)) return set_error(d, why_code, why);
+    if (!dwalk[(size_t)i] && !virt[(size_t)i] && !single[(size_t)i] && (int64_t)hosts[i]->scans[0].interval_ubegin.size() < nints[(size_t)i])
       return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart intervals missing");
     n_groups += (nints[(size_t)i] + per_group - 1) / per_group;
   }
@@ -532,6 +597,7 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   const size_t T = (size_t)total_intervals;
   const size_t off_ib = L.take(T * 4), off_ie = L.take(T * 4), off_isk = L.take(any_virtual ? T : 0), off_ipr = L.take(any_virtual ? T * 8 : 0);
   const size_t off_tab = L.take((size_t)n * table_blob), off_img = L.take((size_t)n * sizeof(HuffImage)), off_grp = L.take((size_t)n_groups * sizeof(HuffGroup));
+  const size_t off_planes = L.take(ragged ? (size_t)n * sizeof(HuffPlanes) : 0);
   const size_t status_bytes = (size_t)n * 32, off_status = L.take(status_bytes);
   int rc = ensure_entropy_buffers(d, stream_bytes, L.end);
   if (rc) return rc;
@@ -571,6 +637,10 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
         isk[first + k] = vi.bit_skip[(size_t)k];
         memcpy(ipr + (first + k) * 4, &vi.pred[(size_t)k * 4], 8);
       }
+    } else if (single[(size_t)i]) {
+      ib[first] = 0;
+      ie[first] = (uint32_t)usize[(size_t)i];
+      if (any_virtual) hp[off_isk + first] = 0;
     } else {
       memcpy(ib + first, s.interval_ubegin.data(), (size_t)nint * 4);
       memcpy(ie + first, s.interval_uend.data(), (size_t)nint * 4);
@@ -607,12 +677,20 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
     im.stream_off = (uint32_t)stream_off[(size_t)i];
     im.first_interval = (uint32_t)first;
     im.n_intervals = (int32_t)nint;
-    im.restart_interval = dwalk[(size_t)i] ? dwalk[(size_t)i] : virt[(size_t)i] ? virt[(size_t)i]->mcus_per_interval : s.restart_interval;
+    im.restart_interval = dwalk[(size_t)i] ? dwalk[(size_t)i] : virt[(size_t)i] ? virt[(size_t)i]->mcus_per_interval : single[(size_t)i] ? s.mcus_x * s.mcus_y : s.restart_interval;
     im.virt = (virt[(size_t)i] || dwalk[(size_t)i]) ? 1u : 0u;
     im.reserved = 0;
     im.total_mcus = s.mcus_x * s.mcus_y;
     im.mcus_x = s.mcus_x;
-    im.coef_base = (int64_t)i * frame_stride;
+    im.coef_base = ragged ? ragged->coef_base[i] : (int64_t)i * frame_stride;
+    if (ragged) {
+      HuffPlanes &pl = ((HuffPlanes *)(hp + off_planes))[i];
+      memset(&pl, 0, sizeof(pl));
+      for (int k = 0; k < s.ncomp; k++) {
+        pl.bw[k] = (uint32_t)f.blocks_w[s.sc[k].comp];
+        pl.base[k] = (uint32_t)(f.coef_offset[s.sc[k].comp] >> 6);
+      }
+    }
     im.table_off = same_tables ? images[i - 1].table_off : (uint32_t)((size_t)i * table_blob);
     im.status_off = (uint32_t)(i * 8);
     for (int64_t k = 0; k < nint; k += per_group) {
@@ -625,6 +703,8 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
     // has sampling factors > 1 leaves the MCU padding blocks untouched (they must read as zero)
     if (s.ncomp == 1 && (s.mcus_x != f.blocks_w[s.sc[0].comp] || s.mcus_y != f.blocks_h[s.sc[0].comp])) needs_clear = true;
   }
+  // (the stores of a ragged launch lie between those of other launches: nothing to clear in one sweep, and no layout group holds such frames)
+  if (needs_clear && ragged) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "single components with sampling factors are not decoded in a ragged launch");
   for (int k = 0; k < s0.ncomp; k++) {
     const int c = s0.sc[k].comp;
     a.comp_of[k] = c;
@@ -648,6 +728,7 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   a.tables = dp + off_tab;
   a.coef = coef_dev;
   a.status = (uint32_t *)(dp + off_status);
+  a.planes = ragged ? (const HuffPlanes *)(dp + off_planes) : nullptr;
   const TraceMarks mark{"mijpeg"};
   const auto tb1 = mark.t0;
   QuiesceOnError guard{d};
@@ -669,10 +750,12 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   // streams without restart markers: the walk finds the intervals of every image, then one launch decodes them all
   auto walk_and_decode = [&]() {
     const int wrc = device_walk_images(d, hosts, n, dwalk, a, (const HuffImage *)(dp + off_img), (uint32_t *)(dp + off_ib), dp + off_isk,
-                                       (int16_t *)(dp + off_ipr), images, usize, defer);
+                                       (int16_t *)(dp + off_ipr), images, usize, defer, ragged != nullptr,
+                                       ragged ? ragged->walk_launches : nullptr);
     if (wrc) return wrc;
     mark("device walk enqueued");
     if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+    if (ragged) ++*ragged->entropy_launches;
     return MIJPEG_OK;
   };
   if (small) {
@@ -683,8 +766,10 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
                                 hipMemcpyHostToDevice, d->stream));
     if (any_dwalk) {
       if ((rc = walk_and_decode())) return rc;
-    } else if (launch_huffman_scan(a, d->stream))
-      return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+    } else {
+      if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+      if (ragged) ++*ragged->entropy_launches;
+    }
   } else {
     // large batches, in up to eight groups of images: the pool threads gather a group's streams into pinned memory, its
     // DMA runs on a copy stream while the next group is gathered and while the kernel decodes the previous one
@@ -704,17 +789,22 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
       HIP_TRY(d, hipMemcpyAsync(d->ent_dev + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
       HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)gi], d->copy_stream));
       HIP_TRY(d, hipStreamWaitEvent(d->stream, d->copy_events[(size_t)gi], 0));
-      if (any_dwalk) continue; // the walk below covers all images at once
+      if (any_dwalk || ragged) continue; // the walk below covers all images at once; a ragged group is one launch by contract
       int64_t wg1 = wg0;
       for (int i = g0; i < g1; i++) wg1 += (nints[(size_t)i] + per_group - 1) / per_group;
       HuffScanArgs part = a; // the workgroups of this group's images
       part.groups = a.groups + wg0;
       part.n_groups = (int32_t)(wg1 - wg0);
       if (launch_huffman_scan(part, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+      if (ragged) ++*ragged->entropy_launches;
       wg0 = wg1;
     }
     mark("groups gathered + enqueued");
     if (any_dwalk && (rc = walk_and_decode())) return rc;
+    if (ragged && !any_dwalk) {
+      if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+      if (ragged) ++*ragged->entropy_launches;
+    }
   }
   uint32_t *status_host = (uint32_t *)(hp + off_status);
   uint32_t *walk_status_host = (uint32_t *)d->walk_host; // the walk's staging buffer is free again
@@ -734,8 +824,17 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   }
   HIP_TRY(d, hipStreamSynchronize(d->stream));
   guard.armed = false; // (everything of this call is behind the stream's last copy)
-  if (any_dwalk && (rc = walk_verdict(d, walk_status_host, n))) return rc;
   d->phase_device = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count();  // upload + kernel + status
+  if (ragged) {
+    // image by image: one that the walk or the kernel found damaged goes to the single-image route, the others stand
+    for (int i = 0; i < n; i++) {
+      HostDecoder *h = hosts[i];
+      const bool bad = (any_dwalk && walk_status_host[i]) || evaluate_entropy_status(d, &h, 1, status_host + 8 * i) != MIJPEG_OK;
+      ragged->verdict[i] = bad ? 1 : 0;
+    }
+    return MIJPEG_OK;
+  }
+  if (any_dwalk && (rc = walk_verdict(d, walk_status_host, n))) return rc;
   return evaluate_entropy_status(d, hosts, n, status_host);
 }
 

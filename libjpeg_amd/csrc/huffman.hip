@@ -301,6 +301,21 @@ __global__ __launch_bounds__(512) void huffman_scan_kernel(const HuffScanArgs a)
   uint32_t qmax[4] = {0, 0, 0, 0};
   int err = 0;
   const int m0 = interval * img.restart_interval;
+  // plane geometry: the launch's, or the image's own (uniform either way)
+  uint32_t plane_bw[4], plane_base[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    plane_bw[k] = (uint32_t)a.bw[k];
+    plane_base[k] = (uint32_t)(a.coef_off[k] >> 6); // in blocks
+  }
+  if (a.planes) {
+    const HuffPlanes pl = a.planes[grp.image];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      plane_bw[k] = __builtin_amdgcn_readfirstlane(pl.bw[k]);
+      plane_base[k] = __builtin_amdgcn_readfirstlane(pl.base[k]);
+    }
+  }
   uint8_t *slot = stage + ln * 128;
   const int swz16 = (lane & 7) << 4;
   for (int mi = 0; mi < img.restart_interval; mi++) {
@@ -313,13 +328,13 @@ __global__ __launch_bounds__(512) void huffman_scan_kernel(const HuffScanArgs a)
       if (k >= a.ncomp) break;
       const HuffDevTable *dc = tabs + a.dc_tab[k], *ac = tabs + a.ac_tab[k];
       const int h = a.hs[k], v = a.vs[k];
-      const uint32_t comp_base = (uint32_t)(a.coef_off[k] >> 6); // in blocks
+      const uint32_t comp_base = plane_base[k];
       for (int by = 0; by < v; by++)
         for (int bx = 0; bx < h; bx++) {
           uint32_t blk = 0; // block number + 1
           if (live && !err) {
             err = dev_block(br, dc, ac, aux->zq[k], slot, swz16, pred[k], qmax[k]);
-            if (!err) blk = comp_base + (uint32_t)(my * v + by) * (uint32_t)a.bw[k] + (uint32_t)(mx * h + bx) + 1u;
+            if (!err) blk = comp_base + (uint32_t)(my * v + by) * plane_bw[k] + (uint32_t)(mx * h + bx) + 1u;
           }
           // top the ring up with what was requested a block ago
           if (decoding && pend_at == br.fill && br.room()) br.commit(pend0);
@@ -468,13 +483,15 @@ __global__ __launch_bounds__(256) void huffman_walk_kernel(const HuffWalkArgs a)
     for (int k = 0; k < 4; k++) pred[k] = a.first_pred[si * 4 + k];
   }
   uint32_t end_byte = e1, end_skip = 0;
+  const uint32_t emit_every = a.img_emit_every ? a.img_emit_every[img_i] : a.emit_every;
+  const uint32_t total_blocks = a.img_total_blocks ? a.img_total_blocks[img_i] : a.total_blocks;
   for (;;) {
     if (EMIT) {
-      if (nb >= my_blocks || g >= a.total_blocks) break;
-      if (g % a.emit_every == 0) {
+      if (nb >= my_blocks || g >= total_blocks) break;
+      if (g % emit_every == 0) {
         uint32_t q, sk;
         dev_exact_position(br, q, sk);
-        const uint32_t idx = a.img_int0[img_i] + g / a.emit_every;
+        const uint32_t idx = a.img_int0[img_i] + g / emit_every;
         a.ibegin[idx] = q;
         a.iskip[idx] = (uint8_t)sk;
 #pragma unroll
@@ -599,7 +616,8 @@ __global__ __launch_bounds__(WALK_TILE) void huffman_walk_tile_scan_kernel(const
 #pragma unroll
     for (int c = 0; c < 5; c++) ts[threadIdx.x].v[c] = incl.v[c] - mine.v[c];
   }
-  if (threadIdx.x == 0 && total.v[0] < (long long)a.total_blocks) atomicOr(&a.walk_status[img_i], 4u);
+  const uint32_t total_blocks = a.img_total_blocks ? a.img_total_blocks[img_i] : a.total_blocks;
+  if (threadIdx.x == 0 && total.v[0] < (long long)total_blocks) atomicOr(&a.walk_status[img_i], 4u);
 }
 // grid (tiles, images)
 __global__ __launch_bounds__(WALK_TILE) void huffman_walk_prefix_kernel(const HuffWalkArgs a)
@@ -615,7 +633,7 @@ __global__ __launch_bounds__(WALK_TILE) void huffman_walk_prefix_kernel(const Hu
 #pragma unroll
   for (int c = 0; c < 5; c++) run.v[c] += off.v[c] - mine.v[c]; // exclusive
   if (i >= nsub) return;
-  const long long total_blocks = a.total_blocks;
+  const long long total_blocks = a.img_total_blocks ? a.img_total_blocks[img_i] : a.total_blocks;
   const bool live = run.v[0] < total_blocks; // the subsequence starts inside the image, not in the padding behind it
   uint32_t bad = 0;
   if (live && mine.v[0] && walk_state_phase(a.state[s0 + i]) != (uint32_t)(run.v[0] % a.nblk_mcu)) bad |= 1;

@@ -61,8 +61,8 @@ struct HuffDevAux {
 };
 static_assert(sizeof(HuffDevAux) % 16 == 0, "copied in dwords");
 
-// One image of a batch (device memory).  All images of a launch share the frame geometry (components, sampling, plane
-// sizes); stream bytes, restart interval, Huffman tables and deltas are per image.
+// One image of a batch (device memory).  All images of a launch share components and sampling factors, and -- unless the
+// launch brings a HuffPlanes table -- the plane sizes; stream bytes, restart interval, Huffman tables and deltas are per image.
 struct HuffImage {
   uint32_t stream_off;       // byte offset of the image's codestream in `data` (16-byte aligned)
   uint32_t first_interval;   // its first entry in ibegin / iend (whose offsets are relative to stream_off)
@@ -72,6 +72,13 @@ struct HuffImage {
   uint32_t status_off;       // dword index of its 8-dword status block in `status`
   uint32_t virt;             // 1: the intervals are virtual (no markers): start `iskip` bits into the byte, predictors from `ipred`
   uint32_t reserved;
+};
+
+// Plane geometry of one image of a ragged launch (HuffScanArgs::planes, indexed like `images`): what bw[] and coef_off[] of
+// the argument block say for all images of a uniform one, per scan component.
+struct HuffPlanes {
+  uint32_t bw[4];    // plane width in blocks
+  uint32_t base[4];  // first block of the plane inside the image's coefficient store
 };
 
 // A workgroup works on ONE image (the tables in its LDS are that image's): first interval of the group inside the image.
@@ -99,6 +106,7 @@ struct HuffScanArgs {
   const uint8_t *tables;         // device: per image ntables tables followed by one HuffDevAux
   int16_t *coef;                 // coefficient stores
   uint32_t *status;              // device: per image [0] error (0 = ok), [1 + c] max over blocks of sum |c| q for frame component c
+  const HuffPlanes *planes;      // device, or null: per-image plane geometry (replaces bw / coef_off; mcus_x is per image anyway)
 };
 
 constexpr int HUFF_WALK_SUMS_BYTES = 40;
@@ -137,6 +145,8 @@ struct HuffWalkArgs {
   int32_t hs[4], vs[4];
   int32_t ntables, lanes, waves_per_group, n_groups;
   uint32_t sub_bytes;
+  // images of different sizes in one walk (or null: emit_every / total_blocks above hold for all), per image
+  const uint32_t *img_emit_every, *img_total_blocks;
 };
 
 // ---- progressive frames and hidden refinement scans (huffman_prog_kernel) -------------------------------------------------

@@ -828,6 +828,51 @@ __device__ __forceinline__ TileCtx tile_enter(const Fused420Args &a, u32x4 (*sta
   return t;
 }
 
+// Ragged launches (Fused420Args::ragged): frames of different sizes in one launch.  A compile-time flavour of the kernels that
+// have it, and nothing about the other instantiations changes.  The ragged ones overwrite the frame geometry in their copy of
+// the argument block -- which the rest of the kernel reads as ever -- from the frame's RaggedFrame entry, found by
+// a binary search of the prefix table of first workgroups, all of it workgroup-uniform (scalar loads, SGPRs).  The deltas
+// come through qdev (the kernel arguments hold one set), so q is never read and stays unset.
+// Tile order: XCD x takes the x-th contiguous eighth of the launch's tiles (order 1 above, over all frames), frame after frame
+// and row by row inside a frame: neighbouring tiles share an L2 whatever tiles_x their frame has, and no frame is padded to
+// eight tile rows -- a picture of one tile is one workgroup.
+__device__ __forceinline__ TileCtx tile_enter_ragged(Fused420Args &f, u32x4 (*stage_all)[128])
+{
+  const Fused420Args &a = f;
+  TileCtx t;
+  t.tid = threadIdx.x;
+  t.lane = t.tid & 63;
+  t.wave = __builtin_amdgcn_readfirstlane(t.tid >> 6);
+  t.stage = stage_all[t.wave];
+  const unsigned logical = tile_of_workgroup<1>(blockIdx.x, gridDim.x, 1u);
+  const uint32_t *__restrict__ first = a.ragged_first;
+  unsigned lo = 0, hi = (unsigned)a.frames; // first[lo] <= logical < first[hi]
+  while (hi - lo > 1) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (first[mid] <= logical) lo = mid;
+    else hi = mid;
+  }
+  const RaggedFrame *__restrict__ fr = a.ragged + lo;
+  const unsigned local = logical - first[lo], tiles_x = (unsigned)fr->tiles_x, row = local / tiles_x;
+  f.coef = a.coef + fr->coef_base;
+  f.coef_frame_stride = 0;
+  f.off_y = fr->off_y; f.off_cb = fr->off_cb; f.off_cr = fr->off_cr;
+  f.out = fr->out;
+  f.out_frame_stride = 0;
+  f.row_stride = fr->row_stride;
+  f.width = fr->width; f.height = fr->height;
+  f.bw_y = fr->bw_y; f.bh_y = fr->bh_y; f.bw_c = fr->bw_c; f.bh_c = fr->bh_c;
+  f.cw = fr->cw; f.ch = fr->ch;
+  f.tiles_x = fr->tiles_x; f.tiles_y = fr->tiles_y;
+  f.magic_tx = f.magic_ty = 0;
+  t.padding = false;
+  t.frame = fr->qframe; // (what the kernels index qdev with; the strides it is multiplied with are zero)
+  t.tx = (int)(local - row * tiles_x);
+  t.ty = (int)row;
+  t.coef = f.coef;
+  return t;
+}
+
 // The wave's 16 x 4 blocks of a plane of bw x bh blocks (BLOCK_BYTES each): local block n = (lane >> 3) + 8 m sits at column
 // n & 15 = (lane >> 3) + 8 (m & 1), row n >> 4 = m >> 1; blocks outside the plane are redirected to a valid one and never used.
 // TileChunks is the chunkptr of load_blocks / fetch_blocks for them: load_tile_blocks requests the blocks, fetch_tile_blocks hands
@@ -1192,14 +1237,15 @@ __device__ __forceinline__ void f422_chroma_edges(const Fused420Args &a, T *line
 
 // P = 12 (FAST only): 12-bit frames (SOF1, P = 12) -- the same transforms and filters on samples sixteen times as large, the
 // colour stage rearranged so that it stays inside 32 bits (see there), 16-bit samples out (clamp 4095).
-template <bool FAST, int MINW, bool QDEV, int P = 8, bool N12 = false>
-__global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(const Fused420Args a)
+template <bool FAST, int MINW, bool QDEV, int P = 8, bool N12 = false, bool RAGGED = false>
+__global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Args a)
 {
   static_assert(P == 8 || (P == 12 && FAST), "12-bit frames: FAST flavour only (the host checks the ranges)");
+  static_assert(!RAGGED || (QDEV && P == 8), "ragged launches: 8 bit, per-frame tables");
   __shared__ __attribute__((aligned(16))) int cplane[2][F420_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const TileCtx t = tile_enter<P == 8 ? MIJ_TILE_ORDER : 1>(a, stage_all);
+  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<P == 8 ? MIJ_TILE_ORDER : 1>(a, stage_all);
   if (t.padding) return;
 
   // the luma blocks of phase B are requested in front of phase A's transform (see F420P_MINW; two workgroups per CU leave the 32
@@ -1341,13 +1387,14 @@ __device__ __forceinline__ unsigned tap_sum_pk(unsigned a, unsigned w)
 
 // D2: the second pass of every transform on v_dot2 (idct_columns_dot2; admitted by the host where sum |c| q <= 1476 in all three
 // components: plan_reconstruct in capi.cpp)
-template <int MINW, bool QDEV, bool D2 = false>
-__global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fused420Args a)
+template <int MINW, bool QDEV, bool D2 = false, bool RAGGED = false>
+__global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420Args a)
 {
+  static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   __shared__ __attribute__((aligned(16))) unsigned cpair[F420_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const TileCtx t = tile_enter(a, stage_all);
+  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
   if (t.padding) return;
   const int tid = t.tid, lane = t.lane, wave = t.wave, frame = t.frame, tx = t.tx, ty = t.ty;
   u32x4 *stage = t.stage;
@@ -1551,13 +1598,14 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(const Fus
 // the fused 4:4:4 kernel's bound, which legitimate 8-bit content cannot exceed: sum |c| q <= 8 sqrt(64 * 128^2) by
 // Cauchy-Schwarz), but the filter runs on unpacked 32-bit values: frames between the packed gate (2047) and 8190 --
 // saturated colours with hard edges -- stay on a fused kernel instead of falling to the generic pair.
-template <int MINW, bool QDEV, bool WIDE>
-__global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(const Fused420Args a)
+template <int MINW, bool QDEV, bool WIDE, bool RAGGED = false>
+__global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(Fused420Args a)
 {
+  static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   __shared__ __attribute__((aligned(16))) unsigned cpair[F422_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const TileCtx t = tile_enter(a, stage_all);
+  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
   if (t.padding) return;
 
   // ------------------------------------------------------------------ phase A: chroma -> LDS halves (Cb low, Cr high), edge fix-up
@@ -2364,11 +2412,12 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
 // block fetch.  FAST arithmetic only, and only when the host's range check bounds every chroma sample by
 // 4 * range_max < 32768 (so the packing is exact); everything else takes the generic two-kernel path.
 // Algorithmic bytes: 3 x 2 B in + 3 B out = 9 B/pixel.
-template <int MINW, bool QDEV>
-__global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(const Fused420Args a)
+template <int MINW, bool QDEV, bool RAGGED = false>
+__global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(Fused420Args a)
 {
+  static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const TileCtx t = tile_enter(a, stage_all);
+  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
   if (t.padding) return;
   const int frame = t.frame;
 
@@ -2468,11 +2517,12 @@ __global__ __launch_bounds__(F420_THREADS, 2) void fused444_12_kernel(const Fuse
 // leaves out folded into the rounding constant, clamp, eight bytes per line.  Samples travel as packed int16 from the
 // addition on (range check: |sample * 16| <= 4 * range_max < 2^15).  Algorithmic bytes: 2 B in + 1 B out per pixel.
 // P = 12: 12-bit frames -- the same transform, 16-bit samples out (clamp 4095), samples as 32-bit values throughout.
-template <bool QDEV, int P = 8>
-__global__ __launch_bounds__(F420_THREADS, 4) void fused1_kernel(const Fused420Args a)
+template <bool QDEV, int P = 8, bool RAGGED = false>
+__global__ __launch_bounds__(F420_THREADS, 4) void fused1_kernel(Fused420Args a)
 {
+  static_assert(!RAGGED || (QDEV && P == 8), "ragged launches: 8 bit, per-frame tables");
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const TileCtx t = tile_enter<1>(a, stage_all);
+  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<1>(a, stage_all);
   if (t.padding) return;
 
   u32x4 rows[8];
@@ -3808,6 +3858,25 @@ int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t s)
     return launch_tiles<XT_TILE_ORDER>(x.luma_fits16 && x.ext.is_float ? fusedxtw420_kernel<true> : fusedxtw420_kernel<false>, a, s, x.ext);
   default: return -1; // (not a kernel of this launcher)
   }
+}
+
+// Frames of different sizes in one launch (Fused420Args::ragged): the ragged flavour of the kernel the plan names, per-frame tables,
+// one workgroup per tile and no padding (tile_enter's ragged branch)
+int launch_fused_ragged(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t s)
+{
+  if (!a.ragged || !a.ragged_first || !a.qdev || a.frames < 1) return -1;
+  if (workgroups == 0) return 0;
+  void (*kernel)(Fused420Args) = nullptr;
+  switch (p.kernel) {
+  case Recon::FUSED420P: kernel = fused420p_kernel<3, true, false, true>; break;
+  case Recon::FUSED420: kernel = p.fast ? fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : fused420_kernel<false, 2, true, 8, false, true>; break;
+  case Recon::FUSED422: kernel = p.wide ? fused422_kernel<3, true, true, true> : fused422_kernel<3, true, false, true>; break;
+  case Recon::FUSED444: kernel = fused444_kernel<2, true, true>; break;
+  case Recon::FUSED1: kernel = fused1_kernel<true, 8, true>; break;
+  default: return -1; // (no ragged flavour)
+  }
+  hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(F420_THREADS), 0, s, a);
+  return (int)hipGetLastError();
 }
 
 // per-frame tables as the client hands them over (u16 deltas, [frames][4][64]) -> the operands of the transforms (<< 4, int32)

@@ -39,7 +39,27 @@ struct Fused420Args {
   int32_t q[3][QROW];             // per component (Y, Cb, Cr): fill_deltas
   const int32_t *qdev;            // or null: per-frame tables in device memory, [frames][4][64] deltas << 4 (replace q)
   uint32_t magic_tx, magic_ty;    // set by the launchers: floor(2^32 / tiles_x) + 1 and the same for tiles_y, or 0 (kernels.hip tile_position)
+  // ragged launches (launch_fused_ragged; null otherwise): the frames differ in size, and a workgroup takes everything from
+  // `coef_frame_stride` to `tiles_y` above from its frame's entry.  `frames` counts the entries, `coef` is the store all
+  // coef_base count from.  (Behind everything else: the uniform kernels' argument offsets are what they were.)
+  const struct RaggedFrame *ragged;  // device: one entry per frame of the launch
+  const uint32_t *ragged_first;      // device: frames + 1 entries, first workgroup (in tile order) of every frame; the last is the grid
 };
+
+// One frame of a ragged launch (device memory; the workgroups read it with scalar loads).  Frame i occupies the workgroups
+// [first[i], first[i + 1]) of the launch's tile order, tiles_x * tiles_y of them, row by row.
+struct RaggedFrame {
+  int64_t coef_base;            // int16 index of the frame's coefficient store from Fused420Args::coef
+  int64_t off_y, off_cb, off_cr; // its planes inside that store
+  uint8_t *out;                 // the frame's first pixel
+  int64_t row_stride;           // bytes
+  int32_t width, height;
+  int32_t bw_y, bh_y, bw_c, bh_c, cw, ch; // as in Fused420Args
+  int32_t tiles_x, tiles_y;
+  int32_t qframe;               // the frame's index in Fused420Args::qdev
+  int32_t reserved;
+};
+static_assert(sizeof(RaggedFrame) == 96, "read in dwords by scalar loads");
 
 // fused JPEG XT profile C (8-bit 4:2:0 legacy frame + 12-bit 4:4:4 residual frame, see fusedxt420_kernel)
 struct FusedXtExtra {
@@ -141,6 +161,9 @@ struct ReconPlan {
 
 // The kernels up to FUSEDXTW420: x.ext and x.luma_fits16 are read for the JPEG XT ones only
 int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t stream);
+// Frames of different sizes in one launch of FUSED420P, FUSED420 (fast or safe), FUSED422 (wide or not), FUSED444 or FUSED1, 8 bit,
+// per-frame tables in a.qdev: a.ragged / a.ragged_first / a.frames describe them, `workgroups` is ragged_first[frames].
+int launch_fused_ragged(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t stream);
 int launch_generic(const GenericArgs &a, bool fast, hipStream_t stream);
 // The same frames in one pass through LDS (plain JPEG: no residual planes, int16 coefficients, tables by value): any sampling
 // layout, 1..4 components, 8 or 12 bit.  Uses the plane description of GenericArgs; no workspace.
