@@ -578,6 +578,75 @@ int mijpeg_encode_image_ex(mijpeg_decoder *d, const uint8_t *pixels, int32_t wid
 int mijpeg_encode_batch_device(mijpeg_decoder *d, const mijpeg_forward_batch *batch, int restart_interval, int optimize,
                                uint8_t **streams, size_t *sizes);
 
+/* ---- ragged encode: n pictures of ANY shapes in one device pass ------------------------------------------------------
+ * The encoder's counterpart of mijpeg_decode_ragged_device: a list of pictures that differ in size, sampling, quality and
+ * restart interval -> n baseline streams, stream i byte for byte what mijpeg_encode_image_ex writes for picture i.  The forward
+ * kernels run once per kernel family over all pictures (ragged flavours: a workgroup looks its picture up), the five passes of the
+ * device entropy coder once over all pictures: the number of launches and of host synchronisations does not grow
+ * with n.  Lists of equally shaped frames are served by mijpeg_encode_batch_device as well.  Which of the two is faster for them
+ * HAS NOT BEEN MEASURED (profiles/ragged_encode.txt, section 3): until it has, uniform lists are better served by the uniform
+ * call, whose cost is known. */
+typedef struct mijpeg_encode_frame {
+  const uint8_t *pixels;     /* interleaved 8-bit samples, `components` per pixel: device memory for mijpeg_encode_ragged_device,
+                                host memory for mijpeg_encode_ragged; the planner does not look at it                          */
+  int64_t row_stride;        /* bytes per line, >= width * components                                                           */
+  int32_t width, height;     /* 1 .. 65535                                                                                      */
+  int32_t components;        /* 1 (grey) or 3 (RGB in, YCbCr coded)                                                             */
+  int32_t hsamp[MIJPEG_MAX_COMPONENTS], vsamp[MIJPEG_MAX_COMPONENTS]; /* sampling factors per component, 1 .. 4                 */
+  int32_t quality;           /* as mijpeg_quality_tables takes it                                                               */
+  int32_t restart_interval;  /* MCUs per restart interval, 0 = none; 0 .. 65535                                                 */
+} mijpeg_encode_frame;
+
+/* What the planner decides for picture i.  A list is cut into PASSES where it would exceed the coder's limits (pass_blocks
+ * below); the index spaces start again in every pass. */
+typedef struct mijpeg_encode_ragged_item {
+  mijpeg_info info;          /* the frame as mijpeg_frame_layout completes it, the tables of `quality` in quant[0], quant[1]     */
+  int64_t coef_base;         /* int16 index of its coefficient store in the pass's packed scratch store                         */
+  uint32_t blocks;           /* blocks of its scan (MCUs * blocks per MCU)                                                       */
+  uint32_t intervals;        /* restart intervals of its scan (1 without restart markers)                                        */
+  uint32_t first_block;      /* in the pass's block index space: a multiple of 256, the picture owns whole workgroups            */
+  uint32_t first_interval;   /* in the pass's concatenated interval list                                                         */
+  int32_t pass;
+  int32_t reserved;
+} mijpeg_encode_ragged_item;
+typedef struct mijpeg_encode_ragged_totals {
+  int64_t coef_count;        /* int16 elements of the largest pass's coefficient store                                           */
+  uint64_t blocks;           /* index space of all passes together (every picture padded to a multiple of 256)                   */
+  uint64_t intervals;        /* all pictures                                                                                     */
+  int32_t passes;
+  int32_t reserved;
+} mijpeg_encode_ragged_totals;
+/* The planner on its own (no device, no decoder object).  pass_blocks: most blocks (padded) of a pass, 0 = the default (2^24; at
+ * most 2^30, what the coder's prefix sums take; a picture larger than the limit is a pass of its own).  MIJPEG_ERR_INVALID_PARAMETER
+ * for n < 1, NULL lists and any description outside the ranges above, fractional subsampling factors included. */
+int mijpeg_encode_ragged_plan(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,
+                              mijpeg_encode_ragged_totals *totals);
+
+/* Pictures resident in DEVICE memory -> streams[i] / sizes[i] in host memory (malloc'ed: mijpeg_free).  optimize != 0: Huffman
+ * tables optimised per picture.  flags: 0.  On any failure every stream already allocated is freed, all streams[i] are NULL and
+ * all sizes[i] are 0.  Scratch (coefficients, bit counts, plain stream, output arena) belongs to the decoder object.  The
+ * environment variable MIJPEG_ENCODE_RAGGED_PASS_BLOCKS overrides pass_blocks (testing).  Passes are cut by blocks alone: one
+ * whose plain stream would reach 2^30 stuffing chunks (64 GiB -- out of reach below 2^28 blocks a pass, sixteen times the default)
+ * is refused with MIJPEG_ERR_NOT_AVAILABLE instead of being cut again. */
+int mijpeg_encode_ragged_device(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint32_t flags,
+                                uint8_t **streams, size_t *sizes);
+/* The same for pictures in HOST memory: gathered into pinned staging, uploaded in one piece, then the device path. */
+int mijpeg_encode_ragged(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint32_t flags,
+                         uint8_t **streams, size_t *sizes);
+/* What the last ragged encode of the object did. */
+typedef struct mijpeg_encode_ragged_stats {
+  int32_t pictures;
+  int32_t passes;
+  int32_t forward_launches;  /* ragged forward kernels, at most six per pass                                                     */
+  int32_t coder_launches;    /* count, prefix-sum, interval, gather, emit and stuffing kernels, summed (a prefix sum takes one,
+                                three or five launches with the SIZE of its input)                                               */
+  int32_t host_syncs;        /* host waits for the device: per pass one for the plain sizes, one for the 0xFF counts, one for the
+                                download, one more for the statistics with optimize (buffers that grow wait as well: not counted) */
+  int32_t reserved;
+  int64_t bytes_downloaded;  /* the output arenas                                                                                */
+} mijpeg_encode_ragged_stats;
+int mijpeg_encode_ragged_get_stats(mijpeg_decoder *d, mijpeg_encode_ragged_stats *out);
+
 /* Worker threads mijpeg_decode_coefficients uses for threads <= 0 (MIJPEG_THREADS overrides; default min(cores, 64)). */
 int mijpeg_default_threads(void);
 

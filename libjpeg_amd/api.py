@@ -88,6 +88,41 @@ class MijpegRaggedFrame(C.Structure):
 RAGGED_GROUPS = ("420", "422", "444", "grey")  # MIJPEG_RAGGED_420 ...
 
 
+class MijpegEncodeFrame(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("row_stride", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32),
+                ("hsamp", C.c_int32 * 4), ("vsamp", C.c_int32 * 4), ("quality", C.c_int32), ("restart_interval", C.c_int32)]
+
+
+class MijpegEncodeRaggedItem(C.Structure):
+    _fields_ = [("info", MijpegInfo), ("coef_base", C.c_int64), ("blocks", C.c_uint32), ("intervals", C.c_uint32), ("first_block", C.c_uint32),
+                ("first_interval", C.c_uint32), ("pass_", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MijpegEncodeRaggedTotals(C.Structure):
+    _fields_ = [("coef_count", C.c_int64), ("blocks", C.c_uint64), ("intervals", C.c_uint64), ("passes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MijpegEncodeRaggedStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("pictures", "passes", "forward_launches", "coder_launches", "host_syncs", "reserved")] + [("bytes_downloaded", C.c_int64)]
+
+
+# sampling factors (hsamp, vsamp) per component of the layouts the encoder takes by name
+ENCODE_LAYOUTS = {"444": ((1, 1, 1), (1, 1, 1)), "420": ((2, 1, 1), (2, 1, 1)), "422": ((2, 1, 1), (1, 1, 1)), "440": ((1, 1, 1), (2, 1, 1)),
+                  "411": ((4, 1, 1), (1, 1, 1))}
+
+
+def encode_frame(width: int, height: int, components: int, quality: int = 85, subsampling="444", restart_mcus: int = 0, pixels: int = 0,
+                 row_stride: int | None = None) -> MijpegEncodeFrame:
+    """A mijpeg_encode_frame.  subsampling: a name of ENCODE_LAYOUTS or (hsamp, vsamp) tuples; pixels: address (device or host)."""
+    hs, vs = ENCODE_LAYOUTS[subsampling] if isinstance(subsampling, str) else subsampling
+    e = MijpegEncodeFrame()
+    e.pixels, e.row_stride = pixels or None, width * components if row_stride is None else row_stride
+    e.width, e.height, e.components, e.quality, e.restart_interval = int(width), int(height), int(components), int(quality), int(restart_mcus)
+    for c in range(min(4, len(hs))):
+        e.hsamp[c], e.vsamp[c] = hs[c], vs[c]
+    return e
+
+
 class MijpegError(RuntimeError):
     def __init__(self, code: int, message: str):
         super().__init__(f"mijpeg error {code}: {message}")
@@ -145,6 +180,12 @@ def lib():
         L.mijpeg_reconstruct_ragged_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int]
         L.mijpeg_ragged_get_stats.argtypes = [C.c_void_p, P(MijpegRaggedStats)]
         L.mijpeg_ragged_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mijpeg_encode_ragged_plan.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mijpeg_encode_ragged_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mijpeg_encode_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mijpeg_encode_ragged_get_stats.argtypes = [C.c_void_p, P(MijpegEncodeRaggedStats)]
+        L.mijpeg_free.argtypes = [C.c_void_p]
+        L.mijpeg_free.restype = None
         L.mijpeg_device_walk_rounds.argtypes = [C.c_void_p]
         L.mijpeg_device_walk_rounds.restype = C.c_int
         L.mijpeg_speculative_scans.argtypes = [C.POINTER(C.c_int64)]
@@ -335,6 +376,39 @@ class Decoder:
             out.append(C.string_at(ptrs[f], sizes[f]))
             L.mijpeg_free(ptrs[f])
         return out
+
+    def _encode_ragged(self, fn, frames, optimize: bool, flags: int = 0):
+        n = len(frames)
+        arr = (MijpegEncodeFrame * max(n, 1))(*frames)
+        ptrs, sizes = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
+        self._check(fn(self._h, arr, n, 1 if optimize else 0, flags, ptrs, sizes))
+        out = []
+        for i in range(n):
+            out.append(C.string_at(ptrs[i], sizes[i]))
+            lib().mijpeg_free(ptrs[i])
+        return out
+
+    def encode_ragged_device(self, frames, optimize: bool = False):
+        """mijpeg_encode_ragged_device: MijpegEncodeFrame descriptions (api.encode_frame) of pictures resident in HBM -> list of
+        baseline JPEG streams, each what `encode` writes for that picture; launches and host waits do not grow with the list."""
+        _foreign_work_done()
+        return self._encode_ragged(lib().mijpeg_encode_ragged_device, frames, optimize)
+
+    def encode_ragged(self, images, quality=85, subsampling="444", restart_mcus=0, optimize: bool = False):
+        """mijpeg_encode_ragged: (H, W, 3) / (H, W) uint8 arrays in host memory -> list of baseline JPEG streams.  quality,
+        subsampling (a name of ENCODE_LAYOUTS) and restart_mcus: one value for all or a list with one per picture."""
+        imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+        per = lambda v, i: v[i] if isinstance(v, (list, tuple)) else v
+        frames = []
+        for i, im in enumerate(imgs):
+            nc = 1 if im.ndim == 2 or im.shape[2] == 1 else im.shape[2]
+            frames.append(encode_frame(im.shape[1], im.shape[0], nc, per(quality, i), per(subsampling, i), per(restart_mcus, i), im.ctypes.data))
+        return self._encode_ragged(lib().mijpeg_encode_ragged, frames, optimize)
+
+    def encode_ragged_stats(self) -> dict:
+        st = MijpegEncodeRaggedStats()
+        self._check(lib().mijpeg_encode_ragged_get_stats(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MijpegEncodeRaggedStats._fields_ if k != "reserved"}
 
     def xt_params(self) -> MijpegXtParams:
         xt = MijpegXtParams()
@@ -757,6 +831,18 @@ def ragged_plan(infos):
     if rc:
         raise MijpegError(rc, "mijpeg_ragged_plan failed")
     return list(group), list(frames), list(grids), total.value
+
+
+def encode_ragged_plan(frames, pass_blocks: int = 0):
+    """mijpeg_encode_ragged_plan (no device needed): MijpegEncodeFrame descriptions -> (MijpegEncodeRaggedItem per picture, totals)."""
+    n = len(frames)
+    arr = (MijpegEncodeFrame * max(n, 1))(*frames)
+    items = (MijpegEncodeRaggedItem * max(n, 1))()
+    totals = MijpegEncodeRaggedTotals()
+    rc = lib().mijpeg_encode_ragged_plan(arr, n, pass_blocks, items, C.byref(totals))
+    if rc:
+        raise MijpegError(rc, "mijpeg_encode_ragged_plan failed")
+    return list(items)[:n], totals
 
 
 def workspace_bytes(info: MijpegInfo, frames: int, flags: int = 0, own_tables: bool = False, xt: "MijpegXtParams | None" = None) -> int:

@@ -31,7 +31,7 @@ using namespace mij;
 // DisplayRectangle, interface/jpeg.cpp:205-220, tools/environment.hpp:752-784): every extern "C" body is a function-try-block
 // whose handler lands here.  Out of memory is the reference's JPGERR_OUT_OF_MEMORY; anything else is a defect of this library
 // and reported as such, not as a verdict on the stream.
-static int boundary_catch(mijpeg_decoder *d, const char *where) noexcept
+int boundary_catch(mijpeg_decoder *d, const char *where) noexcept
 {
   int code = MIJPEG_ERR_PHASE_ERROR;
   const char *what = "unexpected exception";
@@ -261,6 +261,10 @@ try {
       if (d->henc_out_dev[k]) (void)hipFree(d->henc_out_dev[k]);
     }
     if (d->henc_host) (void)hipHostFree(d->henc_host);
+    if (d->eragged_dev) (void)hipFree(d->eragged_dev);
+    if (d->eragged_out_dev) (void)hipFree(d->eragged_out_dev);
+    if (d->eragged_host) (void)hipHostFree(d->eragged_host);
+    if (d->eragged_down) (void)hipHostFree(d->eragged_down);
     if (d->walk_host) (void)hipHostFree(d->walk_host);
     if (d->req_dev) (void)hipFree(d->req_dev);
     if (d->req_host) (void)hipHostFree(d->req_host);
@@ -2006,54 +2010,8 @@ try {
 
 int mijpeg_launch_forward(const mijpeg_forward_batch *b, void *stream)
 try {
-  if (!b || !b->pixels_dev || !b->coef_dev || b->frames < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  const mijpeg_info &f = b->info;
-  if (f.precision != 8 || (f.components != 1 && f.components != 3) || f.xt) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED;
   ForwardArgs a;
-  memset(&a, 0, sizeof(a));
-  a.pixels = b->pixels_dev;
-  a.pixel_frame_stride = b->pixel_frame_stride;
-  a.pixel_row_stride = b->pixel_row_stride;
-  a.coef = b->coef_dev;
-  a.coef_frame_stride = b->coef_frame_stride;
-  a.width = f.width;
-  a.height = f.height;
-  a.ncomp = f.components;
-  a.ycbcr = f.ycbcr;
-  a.frames = b->frames;
-  const bool dword_lines = (((uintptr_t)b->pixels_dev | (uintptr_t)b->pixel_frame_stride | (uintptr_t)b->pixel_row_stride) & 3) == 0;
-  uint64_t blocks = 0;
-  for (int c = 0; c < f.components; c++) {
-    if (f.subx[c] < 1 || f.suby[c] < 1 || f.blocks_w[c] < 1 || f.blocks_h[c] < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-    a.subx[c] = f.subx[c];
-    a.suby[c] = f.suby[c];
-    a.bw[c] = f.blocks_w[c];
-    a.bh[c] = f.blocks_h[c];
-    a.nbx[c] = ((f.width + f.subx[c] - 1) / f.subx[c] + 7) >> 3;
-    a.nby[c] = ((f.height + f.suby[c] - 1) / f.suby[c] + 7) >> 3;
-    a.coef_off[c] = f.coef_offset[c];
-    a.fast[c] = dword_lines && f.components == 3 && f.ycbcr && f.subx[c] <= 2 && f.suby[c] <= 2 && !getenv("MIJPEG_FORWARD_SLOW");
-    a.fast_nbx[c] = f.width / (8 * f.subx[c]);
-    a.fast_nby[c] = f.height / (8 * f.suby[c]);
-    a.first_block[c] = (uint32_t)blocks;
-    blocks += (uint64_t)f.blocks_w[c] * f.blocks_h[c];
-    for (int i = 0; i < 64; i++) {
-      const uint16_t delta = f.quant[f.quant_index[c]][i];
-      if (delta == 0) return MIJPEG_ERR_INVALID_PARAMETER;
-      // LONG(FLOAT(1L << QUANTIZER_BITS) / delta + 0.5), dct/idct.cpp:106: a single precision quotient
-      volatile float q = (float)(1L << 30) / (float)delta;
-      a.invq[c][i] = (int32_t)((double)q + 0.5);
-    }
-  }
-  if (blocks > 0xffffffffull) return MIJPEG_ERR_INVALID_PARAMETER;
-  a.first_block[f.components] = (uint32_t)blocks;
-  if (a.fast[0] && a.fast[1] && a.fast[2] && f.subx[0] == 1 && f.suby[0] == 1 && f.subx[1] == 2 && f.suby[1] == 2 && f.subx[2] == 2 && f.suby[2] == 2 &&
-      f.width >= 128 && f.height >= 128 && !getenv("MIJPEG_FORWARD_NO_TILES")) {
-    a.tiled420 = 1;
-    const int tx = f.width >> 7, ty = f.height >> 7;
-    a.tile_nbx[0] = tx * 16; a.tile_nby[0] = ty * 16;
-    for (int c = 1; c < 3; c++) { a.tile_nbx[c] = tx * 8; a.tile_nby[c] = ty * 8; }
-  }
+  if (const int rc = forward_args_of(b, a)) return rc;
   return launch_forward(a, (hipStream_t)stream) ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
 } catch (...) { return boundary_catch(nullptr, "mijpeg_launch_forward"); }
 
@@ -2096,11 +2054,7 @@ struct HencJob {
   int upload_tables()
   {
     HencTables *h = (HencTables *)((uint8_t *)d->henc_host + 64 + (size_t)slot * sizeof(HencTables)); // pinned, one per slot
-    memset(h, 0, sizeof(*h));
-    for (int t = 0; t < 2; t++) {
-      for (int k = 0; k < 16; k++) { h->dc_code[t][k] = tabs.dc[t].code[k]; h->dc_len[t][k] = tabs.dc[t].len[k]; }
-      for (int k = 0; k < 256; k++) { h->ac_code[t][k] = tabs.ac[t].code[k]; h->ac_len[t][k] = tabs.ac[t].len[k]; }
-    }
+    henc_pack_tables(h, tabs);
     HIP_TRY(d, hipMemcpyAsync((void *)a.tables, h, sizeof(*h), hipMemcpyHostToDevice, stream));
     return MIJPEG_OK;
   }
@@ -2112,28 +2066,8 @@ struct HencJob {
     const int nc = info.components;
     memset(&a, 0, sizeof(a));
     a.coef = coef_dev;
-    a.ncomp = nc;
-    a.mcus_x = info.mcus_x;
-    a.total_mcus = info.mcus_x * info.mcus_y;
-    a.ri = ri ? ri : a.total_mcus;
-    int B = 0;
-    for (int c = 0; c < nc; c++) {
-      a.hs[c] = nc > 1 ? info.hsamp[c] : 1;
-      a.vs[c] = nc > 1 ? info.vsamp[c] : 1;
-      a.bw[c] = info.blocks_w[c];
-      a.nbx[c] = ((info.width + info.subx[c] - 1) / info.subx[c] + 7) >> 3;
-      a.nby[c] = ((info.height + info.suby[c] - 1) / info.suby[c] + 7) >> 3;
-      a.coef_off[c] = info.coef_offset[c];
-      for (int by = 0; by < a.vs[c]; by++)
-        for (int bx = 0; bx < a.hs[c]; bx++) {
-          if (B >= 64) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device entropy coder");
-          a.blk_comp[B] = (uint8_t)c;
-          a.blk_bx[B] = (uint8_t)bx;
-          a.blk_by[B] = (uint8_t)by;
-          B++;
-        }
-    }
-    a.blocks_per_mcu = B;
+    if (!henc_frame_geometry(a, info, ri)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device entropy coder");
+    const int B = a.blocks_per_mcu;
     const uint64_t nblocks = (uint64_t)a.total_mcus * (uint64_t)B;
     if (nblocks >= ((uint64_t)1 << 30)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "frame too large for the device entropy coder");
     a.total_blocks = (uint32_t)nblocks;

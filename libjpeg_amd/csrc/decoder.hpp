@@ -127,6 +127,11 @@ struct mijpeg_decoder {
   mijpeg_ragged_stats ragged_stats{};
   uint8_t *ragged_desc_dev = nullptr, *ragged_desc_host = nullptr; // frame descriptor tables of the reconstruction launches (pinned copy)
   size_t ragged_desc_cap = 0, ragged_desc_host_cap = 0;
+  // ragged encode (encode_device.cpp): descriptors, coder arrays and coefficient store of a pass; plain stream and output arena;
+  // pinned: descriptors on their way up and counts read back; the downloaded arena
+  uint8_t *eragged_dev = nullptr, *eragged_out_dev = nullptr, *eragged_host = nullptr, *eragged_down = nullptr;
+  size_t eragged_cap = 0, eragged_out_cap = 0, eragged_host_cap = 0, eragged_down_cap = 0;
+  mijpeg_encode_ragged_stats eragged_stats{};
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t chain_ev = nullptr; // mijpeg_stream_wait
@@ -191,6 +196,23 @@ struct TraceMarks {
     if (on()) fprintf(stderr, "[%s] %-28s %8.3f ms\n", who, what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3);
   }
 };
+
+// The boundary of the C ABI (capi.cpp): the handler of every extern "C" function-try-block
+int boundary_catch(mijpeg_decoder *d, const char *where) noexcept;
+
+// ---- encode_device.cpp: what the encoder entry points share ----
+namespace mij {
+struct ForwardArgs;
+struct HencArgs;
+struct HencTables;
+struct EncTables;
+}
+// the forward kernels' argument block for a batch (geometry, routing, quantiser multipliers): MIJPEG_OK or the refusal
+int forward_args_of(const mijpeg_forward_batch *b, mij::ForwardArgs &a);
+// MCU structure and plane geometry of a frame for the device entropy coder (ri: MCUs per interval, 0 = none); false: more than
+// 64 blocks per MCU
+bool henc_frame_geometry(mij::HencArgs &a, const mijpeg_info &info, int ri);
+void henc_pack_tables(mij::HencTables *h, const mij::EncTables &t);
 
 // ---- entropy_device.cpp: on-device entropy decoding ----
 // One frame of a file: its decoder, the element type of its planes, where they start in the object's coefficient store.

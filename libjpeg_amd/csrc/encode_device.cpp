@@ -1,0 +1,557 @@
+// encode_device.cpp -- the encoder direction's host side that more than one entry point needs (argument blocks of the forward
+// kernels and of the device entropy coder) and the RAGGED ENCODE: lists of pictures of any shapes through one device pass
+// (mijpeg_encode_ragged_plan / _device / mijpeg_encode_ragged).  Private to libmijpeg.so.
+//
+// A pass of the ragged encode:
+//   plan        per picture: frame layout, block and interval counts, its place in the pass's index spaces, its coefficient store
+//   upload      ONE copy of the descriptor tables: a ForwardArgs and a HencArgs per picture, the prefix tables, the work lists
+//   forward     at most six launches (forward.hip, ragged flavours) whatever the number of pictures
+//   coder       count [statistics first: one read-back of all histograms, n table sets built on the host, one upload], prefix
+//               sums, interval bytes, prefix sums -> read-back of the plain sizes (sync) -> layout of the plain buffer, emit,
+//               0xFF counts, prefix sums -> read-back (sync) -> stuffing -> ONE download of the output arena (sync)
+//   assembly    headers in front of every picture's piece, EOI behind it
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+
+#include "decoder.hpp"
+#include "encoder.hpp"
+#include "forward.hpp"
+#include "hencode.hpp"
+
+using namespace mij;
+
+// ------------------------------------------------------------------------------------------------
+// argument blocks (shared with capi.cpp: mijpeg_launch_forward, HencJob)
+// ------------------------------------------------------------------------------------------------
+int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a)
+{
+  if (!b || !b->pixels_dev || !b->coef_dev || b->frames < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  const mijpeg_info &f = b->info;
+  if (f.precision != 8 || (f.components != 1 && f.components != 3) || f.xt) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED;
+  memset(&a, 0, sizeof(a));
+  a.pixels = b->pixels_dev;
+  a.pixel_frame_stride = b->pixel_frame_stride;
+  a.pixel_row_stride = b->pixel_row_stride;
+  a.coef = b->coef_dev;
+  a.coef_frame_stride = b->coef_frame_stride;
+  a.width = f.width;
+  a.height = f.height;
+  a.ncomp = f.components;
+  a.ycbcr = f.ycbcr;
+  a.frames = b->frames;
+  const bool dword_lines = (((uintptr_t)b->pixels_dev | (uintptr_t)b->pixel_frame_stride | (uintptr_t)b->pixel_row_stride) & 3) == 0;
+  uint64_t blocks = 0;
+  for (int c = 0; c < f.components; c++) {
+    if (f.subx[c] < 1 || f.suby[c] < 1 || f.blocks_w[c] < 1 || f.blocks_h[c] < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+    a.subx[c] = f.subx[c];
+    a.suby[c] = f.suby[c];
+    a.bw[c] = f.blocks_w[c];
+    a.bh[c] = f.blocks_h[c];
+    a.nbx[c] = ((f.width + f.subx[c] - 1) / f.subx[c] + 7) >> 3;
+    a.nby[c] = ((f.height + f.suby[c] - 1) / f.suby[c] + 7) >> 3;
+    a.coef_off[c] = f.coef_offset[c];
+    a.fast[c] = dword_lines && f.components == 3 && f.ycbcr && f.subx[c] <= 2 && f.suby[c] <= 2 && !getenv("MIJPEG_FORWARD_SLOW");
+    a.fast_nbx[c] = f.width / (8 * f.subx[c]);
+    a.fast_nby[c] = f.height / (8 * f.suby[c]);
+    a.first_block[c] = (uint32_t)blocks;
+    blocks += (uint64_t)f.blocks_w[c] * f.blocks_h[c];
+    for (int i = 0; i < 64; i++) {
+      const uint16_t delta = f.quant[f.quant_index[c]][i];
+      if (delta == 0) return MIJPEG_ERR_INVALID_PARAMETER;
+      // LONG(FLOAT(1L << QUANTIZER_BITS) / delta + 0.5), dct/idct.cpp:106: a single precision quotient
+      volatile float q = (float)(1L << 30) / (float)delta;
+      a.invq[c][i] = (int32_t)((double)q + 0.5);
+    }
+  }
+  if (blocks > 0xffffffffull) return MIJPEG_ERR_INVALID_PARAMETER;
+  a.first_block[f.components] = (uint32_t)blocks;
+  if (a.fast[0] && a.fast[1] && a.fast[2] && f.subx[0] == 1 && f.suby[0] == 1 && f.subx[1] == 2 && f.suby[1] == 2 && f.subx[2] == 2 && f.suby[2] == 2 &&
+      f.width >= 128 && f.height >= 128 && !getenv("MIJPEG_FORWARD_NO_TILES")) {
+    a.tiled420 = 1;
+    const int tx = f.width >> 7, ty = f.height >> 7;
+    a.tile_nbx[0] = tx * 16; a.tile_nby[0] = ty * 16;
+    for (int c = 1; c < 3; c++) { a.tile_nbx[c] = tx * 8; a.tile_nby[c] = ty * 8; }
+  }
+  return MIJPEG_OK;
+}
+
+bool henc_frame_geometry(HencArgs &a, const mijpeg_info &info, int ri)
+{
+  const int nc = info.components;
+  a.ncomp = nc;
+  a.mcus_x = info.mcus_x;
+  a.total_mcus = info.mcus_x * info.mcus_y;
+  a.ri = ri ? ri : a.total_mcus;
+  int B = 0;
+  for (int c = 0; c < nc; c++) {
+    a.hs[c] = nc > 1 ? info.hsamp[c] : 1;
+    a.vs[c] = nc > 1 ? info.vsamp[c] : 1;
+    a.bw[c] = info.blocks_w[c];
+    a.nbx[c] = ((info.width + info.subx[c] - 1) / info.subx[c] + 7) >> 3;
+    a.nby[c] = ((info.height + info.suby[c] - 1) / info.suby[c] + 7) >> 3;
+    a.coef_off[c] = info.coef_offset[c];
+    for (int by = 0; by < a.vs[c]; by++)
+      for (int bx = 0; bx < a.hs[c]; bx++) {
+        if (B >= 64) return false;
+        a.blk_comp[B] = (uint8_t)c;
+        a.blk_bx[B] = (uint8_t)bx;
+        a.blk_by[B] = (uint8_t)by;
+        B++;
+      }
+  }
+  a.blocks_per_mcu = B;
+  return true;
+}
+
+void henc_pack_tables(HencTables *h, const EncTables &t)
+{
+  memset(h, 0, sizeof(*h));
+  for (int k = 0; k < 2; k++) {
+    for (int i = 0; i < 16; i++) { h->dc_code[k][i] = t.dc[k].code[i]; h->dc_len[k][i] = t.dc[k].len[i]; }
+    for (int i = 0; i < 256; i++) { h->ac_code[k][i] = t.ac[k].code[i]; h->ac_len[k][i] = t.ac[k].len[i]; }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// ragged encode: the planner
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+constexpr uint32_t PASS_BLOCKS_DEFAULT = 1u << 24; // 2 GiB of coefficients at most
+constexpr uint32_t PASS_BLOCKS_MAX = 1u << 30;     // exclusive_scan_u32's reach
+
+uint32_t pad256(uint32_t x) { return (x + 255u) & ~255u; }
+
+// one picture's description -> its frame (layout, tables of its quality), blocks and intervals; MIJPEG_OK or INVALID_PARAMETER
+int plan_one(const mijpeg_encode_frame &e, mijpeg_info &f, uint32_t &blocks, uint32_t &intervals)
+{
+  if ((e.components != 1 && e.components != 3) || e.width < 1 || e.width > 65535 || e.height < 1 || e.height > 65535 ||
+      e.restart_interval < 0 || e.restart_interval > 65535)
+    return MIJPEG_ERR_INVALID_PARAMETER;
+  memset(&f, 0, sizeof(f));
+  f.width = e.width;
+  f.height = e.height;
+  f.components = e.components;
+  f.precision = 8;
+  f.ycbcr = e.components == 3 ? 1 : 0;
+  int per_mcu = 0;
+  for (int c = 0; c < e.components; c++) {
+    if (e.hsamp[c] < 1 || e.hsamp[c] > 4 || e.vsamp[c] < 1 || e.vsamp[c] > 4) return MIJPEG_ERR_INVALID_PARAMETER;
+    f.hsamp[c] = e.hsamp[c];
+    f.vsamp[c] = e.vsamp[c];
+    f.quant_index[c] = 0; // (as mijpeg_encode_image_ex: the reference's frame header selects table 0 for every component)
+    per_mcu += e.components > 1 ? e.hsamp[c] * e.vsamp[c] : 1;
+  }
+  if (per_mcu > 64) return MIJPEG_ERR_INVALID_PARAMETER;
+  mijpeg_quality_tables(e.quality, f.quant[0], f.quant[1]);
+  if (mijpeg_frame_layout(&f)) return MIJPEG_ERR_INVALID_PARAMETER;
+  const uint64_t mcus = (uint64_t)f.mcus_x * (uint64_t)f.mcus_y, nb = mcus * (uint64_t)per_mcu;
+  if (nb >= PASS_BLOCKS_MAX) return MIJPEG_ERR_INVALID_PARAMETER;
+  blocks = (uint32_t)nb;
+  const uint64_t ri = e.restart_interval ? (uint64_t)e.restart_interval : mcus;
+  intervals = (uint32_t)((mcus + ri - 1) / ri);
+  return MIJPEG_OK;
+}
+
+int plan_list(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items, mijpeg_encode_ragged_totals *totals)
+{
+  if (!frames || !items || !totals || n < 1 || pass_blocks > PASS_BLOCKS_MAX) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (pass_blocks == 0) pass_blocks = PASS_BLOCKS_DEFAULT;
+  memset(totals, 0, sizeof(*totals));
+  int pass = 0;
+  uint64_t at_block = 0, at_interval = 0;
+  int64_t at_coef = 0;
+  for (int i = 0; i < n; i++) {
+    mijpeg_encode_ragged_item &it = items[i];
+    memset(&it, 0, sizeof(it));
+    if (const int rc = plan_one(frames[i], it.info, it.blocks, it.intervals)) return rc;
+    const uint32_t padded = pad256(it.blocks);
+    if (at_block > 0 && at_block + padded > pass_blocks) { // (a picture beyond the limit is a pass of its own)
+      pass++;
+      at_block = at_interval = 0;
+      at_coef = 0;
+    }
+    it.pass = pass;
+    it.first_block = (uint32_t)at_block;
+    it.first_interval = (uint32_t)at_interval;
+    it.coef_base = at_coef;
+    at_block += padded;
+    at_interval += it.intervals;
+    at_coef += (it.info.coef_count + 127) & ~(int64_t)127; // stores start on 256-byte boundaries
+    totals->blocks += padded;
+    totals->intervals += it.intervals;
+    totals->coef_count = std::max(totals->coef_count, at_coef);
+  }
+  totals->passes = pass + 1;
+  return MIJPEG_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ragged encode: one pass on the device
+// ------------------------------------------------------------------------------------------------
+struct Carver { // lays regions out in a buffer, 256-byte aligned
+  size_t at = 0;
+  size_t take(size_t bytes)
+  {
+    const size_t o = at;
+    at = (at + bytes + 255) & ~(size_t)255;
+    return o;
+  }
+};
+
+// launches of an exclusive_scan_u32 over n elements (hencode.hip)
+int scan_launches(uint32_t n)
+{
+  const uint32_t t1 = n / 1024 + 1;
+  return t1 == 1 ? 1 : t1 / 1024 + 1 == 1 ? 3 : 5;
+}
+
+#define LAUNCHED(d, call, what, count)                                          \
+  do {                                                                          \
+    if (call) return hip_fail(d, hipGetLastError(), what " launch");            \
+    (d)->eragged_stats.coder_launches += (count);                               \
+  } while (0)
+
+int sync_counted(mijpeg_decoder *d)
+{
+  HIP_TRY(d, hipStreamSynchronize(d->stream));
+  d->eragged_stats.host_syncs++;
+  return MIJPEG_OK;
+}
+
+// pictures [p0, p1) of the list: one pass.  frames[i].pixels are device addresses.
+int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijpeg_encode_ragged_item *items, int p0, int p1, int optimize,
+                uint8_t **streams, size_t *sizes)
+{
+  const uint32_t n = (uint32_t)(p1 - p0);
+  const mijpeg_encode_ragged_item &last = items[p1 - 1];
+  const uint32_t N = last.first_block + pad256(last.blocks), I = last.first_interval + last.intervals;
+  const int64_t coef_total = last.coef_base + ((last.info.coef_count + 127) & ~(int64_t)127);
+  hipStream_t stream = d->stream;
+
+  // ---- the forward kernels' work lists (routing: launch_forward's, per picture)
+  std::vector<ForwardArgs> fargs(n);
+  std::vector<uint32_t> wl_first[FORWARD_RAGGED_LAUNCHES], wl_item[FORWARD_RAGGED_LAUNCHES];
+  for (uint32_t p = 0; p < n; p++) {
+    const mijpeg_encode_frame &e = frames[p0 + p];
+    mijpeg_forward_batch b;
+    memset(&b, 0, sizeof(b));
+    b.info = items[p0 + p].info;
+    b.pixels_dev = e.pixels;
+    b.pixel_row_stride = e.row_stride;
+    b.pixel_frame_stride = e.row_stride * (int64_t)e.height;
+    b.coef_dev = (int16_t *)16; // (placed below, once the store's address is known)
+    b.coef_frame_stride = b.info.coef_count;
+    b.frames = 1;
+    if (const int rc = forward_args_of(&b, fargs[p])) return set_error(d, rc, "invalid frame for the forward kernels");
+    int which[5], comp[5];
+    uint32_t wgs[5];
+    const int k = forward_ragged_items(fargs[p], which, wgs, comp);
+    for (int j = 0; j < k; j++) {
+      std::vector<uint32_t> &first = wl_first[which[j]];
+      const uint64_t at = first.empty() ? 0 : first.back();
+      if (first.empty()) first.push_back(0);
+      if (at + wgs[j] > 0x7fffffffull) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "pass too large for one forward launch");
+      first.push_back((uint32_t)(at + wgs[j])); // (entry k: first workgroup of item k; the grid behind the last)
+      wl_item[which[j]].push_back(p * 4u + (uint32_t)comp[j]);
+    }
+  }
+
+  // ---- arena 1: descriptor tables (one upload), coder arrays, coefficient store
+  Carver up; // the part that is uploaded in one piece: same offsets in the pinned buffer and on the device
+  const size_t o_fargs = up.take((size_t)n * sizeof(ForwardArgs));
+  const size_t o_hargs = up.take((size_t)n * sizeof(HencArgs));
+  const size_t o_fblock = up.take(((size_t)n + 1) * 4);
+  const size_t o_fint = up.take(((size_t)n + 1) * 4);
+  size_t o_wl_first[FORWARD_RAGGED_LAUNCHES], o_wl_item[FORWARD_RAGGED_LAUNCHES];
+  for (int l = 0; l < FORWARD_RAGGED_LAUNCHES; l++) {
+    o_wl_first[l] = up.take(wl_first[l].size() * 4);
+    o_wl_item[l] = up.take(wl_item[l].size() * 4);
+  }
+  const size_t o_stdtab = up.take(sizeof(HencTables));
+  const size_t up_bytes = up.at;
+  Carver dv = up; // device only (or uploaded / read back later)
+  const size_t o_fchunk = dv.take(((size_t)n + 1) * 4);
+  const size_t o_tabs = dv.take(optimize ? (size_t)n * sizeof(HencTables) : 0);
+  const size_t o_hist = dv.take(optimize ? (size_t)n * 4 * 256 * 4 : 0);
+  const size_t o_gather = dv.take(((size_t)n + 1) * 8);
+  const size_t o_bits = dv.take((size_t)N * 4);
+  const size_t o_bitpos = dv.take(((size_t)N + 1) * 8);
+  const size_t o_ibytes = dv.take((size_t)I * 4);
+  const size_t o_istart = dv.take(((size_t)I + 1) * 8);
+  const size_t o_scratch = dv.take((((size_t)N / 1024 + 8) * 2 + 8192) * 8);
+  const size_t o_coef = dv.take((size_t)coef_total * sizeof(int16_t));
+  int rc = ensure_dev(d, (void **)&d->eragged_dev, &d->eragged_cap, dv.at);
+  if (rc) return rc;
+  // pinned: the upload, then what comes back or goes up later
+  Carver hp = up;
+  const size_t h_fchunk = hp.take(((size_t)n + 1) * 4);
+  const size_t h_tabs = hp.take(optimize ? (size_t)n * sizeof(HencTables) : 0);
+  const size_t h_hist = hp.take(optimize ? (size_t)n * 4 * 256 * 4 : 0);
+  const size_t h_istart = hp.take(((size_t)n + 1) * 8);
+  const size_t h_ffs = hp.take(((size_t)n + 1) * 8);
+  rc = ensure_pinned(d, &d->eragged_host, &d->eragged_host_cap, hp.at);
+  if (rc) return rc;
+  uint8_t *dev = d->eragged_dev, *host = d->eragged_host;
+  int16_t *coef = (int16_t *)(dev + o_coef);
+  uint64_t *scratch = (uint64_t *)(dev + o_scratch);
+
+  // ---- fill the tables
+  std::vector<EncTables> tabs(optimize ? n : 1);
+  enc_standard_tables(tabs[0]);
+  henc_pack_tables((HencTables *)(host + o_stdtab), tabs[0]);
+  ForwardArgs *hf = (ForwardArgs *)(host + o_fargs);
+  HencArgs *hh = (HencArgs *)(host + o_hargs);
+  uint32_t *h_first_block = (uint32_t *)(host + o_fblock), *h_first_int = (uint32_t *)(host + o_fint);
+  for (uint32_t p = 0; p < n; p++) {
+    const mijpeg_encode_ragged_item &it = items[p0 + p];
+    fargs[p].coef = coef + it.coef_base;
+    hf[p] = fargs[p];
+    HencArgs &a = hh[p];
+    memset(&a, 0, sizeof(a));
+    if (!henc_frame_geometry(a, it.info, frames[p0 + p].restart_interval)) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "too many blocks per MCU");
+    a.coef = coef + it.coef_base;
+    // statistics are counted with the standard tables' lengths (any would do), the real pass with the picture's own
+    a.tables = (const HencTables *)(dev + o_stdtab);
+    a.total_blocks = it.blocks;
+    a.n_intervals = it.intervals;
+    a.bits = (uint32_t *)(dev + o_bits) + it.first_block;
+    a.bitpos = (const uint64_t *)(dev + o_bitpos) + it.first_block;
+    a.ibytes = (uint32_t *)(dev + o_ibytes) + it.first_interval;
+    a.istart = (const uint64_t *)(dev + o_istart) + it.first_interval;
+    a.hist = optimize ? (uint32_t *)(dev + o_hist) + (size_t)p * 4 * 256 : nullptr;
+    h_first_block[p] = it.first_block;
+    h_first_int[p] = it.first_interval;
+  }
+  h_first_block[n] = N;
+  h_first_int[n] = I;
+  ForwardRaggedPlan plan;
+  memset(&plan, 0, sizeof(plan));
+  for (int l = 0; l < FORWARD_RAGGED_LAUNCHES; l++) {
+    if (wl_item[l].empty()) continue;
+    memcpy(host + o_wl_first[l], wl_first[l].data(), wl_first[l].size() * 4);
+    memcpy(host + o_wl_item[l], wl_item[l].data(), wl_item[l].size() * 4);
+    plan.launch[l].pics = (const ForwardArgs *)(dev + o_fargs);
+    plan.launch[l].first_wg = (const uint32_t *)(dev + o_wl_first[l]);
+    plan.launch[l].item = (const uint32_t *)(dev + o_wl_item[l]);
+    plan.launch[l].items = (uint32_t)wl_item[l].size();
+    plan.grid[l] = wl_first[l].back();
+  }
+  HIP_TRY(d, hipMemcpyAsync(dev, host, up_bytes, hipMemcpyHostToDevice, stream));
+
+  // ---- forward kernels
+  if (launch_forward_ragged(plan, stream, &d->eragged_stats.forward_launches)) return hip_fail(d, hipGetLastError(), "ragged forward kernel launch");
+
+  // ---- coder: count, prefix sums, plain sizes
+  HencBatchArgs b;
+  memset(&b, 0, sizeof(b));
+  b.pics = (const HencArgs *)(dev + o_hargs);
+  b.first_block = (const uint32_t *)(dev + o_fblock);
+  b.first_interval = (const uint32_t *)(dev + o_fint);
+  b.first_chunk = (const uint32_t *)(dev + o_fchunk);
+  b.n = n;
+  b.total_blocks = N;
+  b.total_intervals = I;
+  if (optimize) {
+    HIP_TRY(d, hipMemsetAsync(dev + o_hist, 0, (size_t)n * 4 * 256 * 4, stream));
+    LAUNCHED(d, henc_count(b, true, stream), "henc_count_kernel", 1);
+    HIP_TRY(d, hipMemcpyAsync(host + h_hist, dev + o_hist, (size_t)n * 4 * 256 * 4, hipMemcpyDeviceToHost, stream));
+    if ((rc = sync_counted(d))) return rc;
+    HencTables *ht = (HencTables *)(host + h_tabs);
+    for (uint32_t p = 0; p < n; p++) {
+      const uint32_t(*hist)[256] = (const uint32_t(*)[256])(host + h_hist) + (size_t)p * 4;
+      enc_standard_tables(tabs[p]);
+      enc_optimal_tables(tabs[p], hist, hist + 2, items[p0 + p].info.components > 1 ? 2 : 1);
+      henc_pack_tables(ht + p, tabs[p]);
+      hh[p].tables = (const HencTables *)(dev + o_tabs) + p;
+    }
+    HIP_TRY(d, hipMemcpyAsync(dev + o_tabs, ht, (size_t)n * sizeof(HencTables), hipMemcpyHostToDevice, stream));
+    HIP_TRY(d, hipMemcpyAsync(dev + o_hargs, hh, (size_t)n * sizeof(HencArgs), hipMemcpyHostToDevice, stream)); // (tables now the pictures' own)
+  }
+  LAUNCHED(d, henc_count(b, false, stream), "henc_count_kernel", 1);
+  LAUNCHED(d, exclusive_scan_u32((const uint32_t *)(dev + o_bits), (uint64_t *)(dev + o_bitpos), N, scratch, stream), "scan", scan_launches(N));
+  LAUNCHED(d, henc_interval_bytes(b, stream), "henc_interval_bytes_kernel", 1);
+  LAUNCHED(d, exclusive_scan_u32((const uint32_t *)(dev + o_ibytes), (uint64_t *)(dev + o_istart), I, scratch, stream), "scan", scan_launches(I));
+  LAUNCHED(d, henc_gather((const uint64_t *)(dev + o_istart), b.first_interval, (uint64_t *)(dev + o_gather), n + 1, stream), "henc_gather_kernel", 1);
+  HIP_TRY(d, hipMemcpyAsync(host + h_istart, dev + o_gather, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
+  if ((rc = sync_counted(d))) return rc;
+
+  // ---- layout of the plain buffer: every picture on a chunk boundary
+  // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check)
+  const uint64_t *g_istart = (const uint64_t *)(host + h_istart);
+  uint32_t *h_first_chunk = (uint32_t *)(host + h_fchunk);
+  uint64_t chunks = 0;
+  for (uint32_t p = 0; p < n; p++) {
+    h_first_chunk[p] = (uint32_t)chunks;
+    chunks += (g_istart[p + 1] - g_istart[p] + HENC_STUFF_CHUNK - 1) / HENC_STUFF_CHUNK;
+    if (chunks >= PASS_BLOCKS_MAX) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "pass too large for the device entropy coder's output arena");
+  }
+  h_first_chunk[n] = (uint32_t)chunks;
+  const size_t plain_total = (size_t)chunks * HENC_STUFF_CHUNK;
+  Carver ob;
+  const size_t q_plain = ob.take(plain_total + 16);
+  const size_t q_ffc = ob.take(((size_t)chunks + 1) * 4);
+  const size_t q_ffs = ob.take(((size_t)chunks + 1) * 8);
+  const size_t q_out = ob.take(plain_total * 2 + (size_t)I * 2 + 16);
+  const size_t q_scratch = ob.take((((size_t)chunks / 1024 + 8) * 2 + 8192) * 8); // (the chunks may outnumber the blocks: a scratch of their own)
+  rc = ensure_dev(d, (void **)&d->eragged_out_dev, &d->eragged_out_cap, ob.at);
+  if (rc) return rc;
+  uint8_t *od = d->eragged_out_dev;
+  b.total_chunks = (uint32_t)chunks;
+  b.plain = (uint32_t *)(od + q_plain);
+  b.ffcount = (uint32_t *)(od + q_ffc);
+  b.ffstart = (const uint64_t *)(od + q_ffs);
+  b.out = od + q_out;
+  HIP_TRY(d, hipMemcpyAsync(dev + o_fchunk, h_first_chunk, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(d, hipMemsetAsync(od + q_plain, 0, plain_total + 16, stream));
+  LAUNCHED(d, henc_emit(b, stream), "henc_emit_kernel", 1);
+  LAUNCHED(d, henc_count_ff(b, stream), "henc_count_ff_kernel", 1);
+  LAUNCHED(d, exclusive_scan_u32(b.ffcount, (uint64_t *)b.ffstart, b.total_chunks, (uint64_t *)(od + q_scratch), stream), "scan", scan_launches(b.total_chunks));
+  LAUNCHED(d, henc_gather(b.ffstart, b.first_chunk, (uint64_t *)(dev + o_gather), n + 1, stream), "henc_gather_kernel", 1);
+  LAUNCHED(d, henc_stuff(b, stream), "henc_stuff_kernel", 1);
+  HIP_TRY(d, hipMemcpyAsync(host + h_ffs, dev + o_gather, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
+  if ((rc = sync_counted(d))) return rc;
+
+  // ---- one download of the arena, then the streams
+  const uint64_t *g_ffs = (const uint64_t *)(host + h_ffs);
+  const size_t arena = plain_total + (size_t)g_ffs[n] + 2 * ((size_t)I - n);
+  rc = ensure_pinned(d, &d->eragged_down, &d->eragged_down_cap, arena + 16);
+  if (rc) return rc;
+  HIP_TRY(d, hipMemcpyAsync(d->eragged_down, b.out, arena, hipMemcpyDeviceToHost, stream));
+  std::vector<std::vector<uint8_t>> heads(n); // (the headers are written while the copy runs)
+  for (uint32_t p = 0; p < n; p++)
+    enc_write_headers(heads[p], items[p0 + p].info, tabs[optimize ? p : 0], frames[p0 + p].restart_interval);
+  if ((rc = sync_counted(d))) return rc;
+  d->eragged_stats.bytes_downloaded += (int64_t)arena;
+  for (uint32_t p = 0; p < n; p++) {
+    const mijpeg_encode_ragged_item &it = items[p0 + p];
+    const size_t at = (size_t)h_first_chunk[p] * HENC_STUFF_CHUNK + (size_t)g_ffs[p] + 2 * ((size_t)it.first_interval - p);
+    const size_t ecs = (size_t)(g_istart[p + 1] - g_istart[p]) + (size_t)(g_ffs[p + 1] - g_ffs[p]) + 2 * ((size_t)it.intervals - 1);
+    const size_t hs = heads[p].size();
+    uint8_t *s = (uint8_t *)malloc(hs + ecs + 2);
+    if (!s) return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the stream");
+    memcpy(s, heads[p].data(), hs);
+    memcpy(s + hs, d->eragged_down + at, ecs);
+    s[hs + ecs] = 0xff;
+    s[hs + ecs + 1] = 0xd9;
+    streams[p0 + p] = s;
+    sizes[p0 + p] = hs + ecs + 2;
+  }
+  return MIJPEG_OK;
+}
+
+uint32_t pass_blocks_setting()
+{
+  const char *e = getenv("MIJPEG_ENCODE_RAGGED_PASS_BLOCKS"); // (testing: cut small lists into several passes)
+  if (!e) return 0;
+  const unsigned long long v = strtoull(e, nullptr, 10);
+  return (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 256), PASS_BLOCKS_MAX);
+}
+
+// the list, pass by pass; pixels in device memory
+int encode_list(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint8_t **streams, size_t *sizes)
+{
+  std::vector<mijpeg_encode_ragged_item> items((size_t)n);
+  mijpeg_encode_ragged_totals totals;
+  int rc = plan_list(frames, n, pass_blocks_setting(), items.data(), &totals);
+  if (rc) return set_error(d, rc, "invalid picture description in the list");
+  for (int i = 0; i < n; i++)
+    if (!frames[i].pixels || frames[i].row_stride < (int64_t)frames[i].width * frames[i].components)
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "picture without pixels or with a row stride below its width");
+  d->eragged_stats.pictures = n;
+  for (int p0 = 0; p0 < n && !rc;) {
+    int p1 = p0 + 1;
+    while (p1 < n && items[(size_t)p1].pass == items[(size_t)p0].pass) p1++;
+    rc = encode_pass(d, frames, items.data(), p0, p1, optimize, streams, sizes);
+    d->eragged_stats.passes++;
+    p0 = p1;
+  }
+  return rc;
+}
+
+int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes, bool host_pixels)
+{
+  if (!d || !frames || !streams || !sizes || n < 1 || flags != 0) return MIJPEG_ERR_INVALID_PARAMETER;
+  for (int i = 0; i < n; i++) { streams[i] = nullptr; sizes[i] = 0; }
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  HIP_TRY(d, hipSetDevice(d->device));
+  const auto t_begin = std::chrono::steady_clock::now();
+  d->eragged_stats = mijpeg_encode_ragged_stats{};
+  int rc = MIJPEG_OK;
+  std::vector<mijpeg_encode_frame> on_device;
+  if (host_pixels) {
+    // gather into pinned staging (the workers share the pictures), one upload, then the device path on the copies
+    quiesce(d); // (a batch that was submitted and not waited for may still read the staging area)
+    std::vector<size_t> off((size_t)n + 1, 0);
+    for (int i = 0; i < n && !rc; i++) {
+      const mijpeg_encode_frame &e = frames[i];
+      if (!e.pixels || e.height < 1 || e.height > 65535 || e.width < 1 || e.width > 65535 || (e.components != 1 && e.components != 3) ||
+          e.row_stride < (int64_t)e.width * e.components)
+        rc = set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "invalid picture description in the list");
+      else
+        off[(size_t)i + 1] = (off[(size_t)i] + (size_t)e.row_stride * (size_t)e.height + 255) & ~(size_t)255;
+    }
+    const size_t total = off[(size_t)n];
+    if (!rc) rc = ensure_dev(d, (void **)&d->enc_dev, &d->enc_cap, total + 256);
+    if (!rc) rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, total + 256);
+    if (!rc) {
+      const int workers = std::max(1, std::min(std::min(default_threads(), 16), n));
+      parallel_for(workers, [&](int w) {
+        for (int i = w; i < n; i += workers) memcpy(d->stage_host + off[(size_t)i], frames[i].pixels, (size_t)frames[i].row_stride * (size_t)frames[i].height);
+      });
+      const hipError_t e = hipMemcpyAsync(d->enc_dev, d->stage_host, total, hipMemcpyHostToDevice, d->stream);
+      if (e != hipSuccess) rc = hip_fail(d, e, "upload of the pictures");
+      on_device.assign(frames, frames + n);
+      for (int i = 0; i < n; i++) on_device[(size_t)i].pixels = d->enc_dev + off[(size_t)i];
+      frames = on_device.data();
+    }
+  }
+  if (!rc) rc = encode_list(d, frames, n, optimize, streams, sizes);
+  if (rc) {
+    (void)hipStreamSynchronize(d->stream);
+    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+  }
+  d->timing[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); // mijpeg_last_timing: the whole call
+  d->timing[1] = d->timing[2] = d->timing[3] = 0;
+  return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int mijpeg_encode_ragged_plan(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,
+                              mijpeg_encode_ragged_totals *totals)
+try {
+  return plan_list(frames, n, pass_blocks, items, totals);
+} catch (...) { return boundary_catch(nullptr, "mijpeg_encode_ragged_plan"); }
+
+int mijpeg_encode_ragged_device(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint32_t flags, uint8_t **streams,
+                                size_t *sizes)
+try {
+  return encode_entry(d, frames, n, optimize, flags, streams, sizes, false);
+} catch (...) {
+  if (streams && sizes)
+    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+  return boundary_catch(d, "mijpeg_encode_ragged_device");
+}
+
+int mijpeg_encode_ragged(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes)
+try {
+  return encode_entry(d, frames, n, optimize, flags, streams, sizes, true);
+} catch (...) {
+  if (streams && sizes)
+    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+  return boundary_catch(d, "mijpeg_encode_ragged");
+}
+
+int mijpeg_encode_ragged_get_stats(mijpeg_decoder *d, mijpeg_encode_ragged_stats *out)
+try {
+  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
+  *out = d->eragged_stats;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_encode_ragged_get_stats"); }
+
+} // extern "C"

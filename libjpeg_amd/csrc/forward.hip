@@ -18,6 +18,8 @@
 //                          transformation): per-pixel gather
 // The integer work is in 32-bit wrapping arithmetic like the reference's LONG; the quantiser is its 64-bit
 // multiply-and-shift.
+// Each kernel has a RAGGED flavour for lists of pictures of different shapes (ForwardRaggedArgs): the workgroup looks its
+// picture up and runs the same body on that picture's argument block in device memory.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -75,7 +77,8 @@ __device__ __forceinline__ int ycc_component(int c, int r, int g, int b)
 }
 
 // forward transform of one block of samples, quantisation, 128-byte store (idct.cpp:125-170 columns, :174-218 rows)
-__device__ __forceinline__ void transform_and_store(const int (&blk)[64], const int *__restrict__ invq, int16_t *dst)
+template <class Q>
+__device__ __forceinline__ void transform_and_store_from(const int (&blk)[64], Q invq, int16_t *dst)
 {
   // pass over columns (idct.cpp:125-170), then rows with quantisation (:174-218)
   int t[64];
@@ -108,6 +111,16 @@ __device__ __forceinline__ void transform_and_store(const int (&blk)[64], const 
   u32x4 *d4 = reinterpret_cast<u32x4 *>(dst);
 #pragma unroll
   for (int i = 0; i < 8; i++) d4[i] = u32x4{packed[4 * i], packed[4 * i + 1], packed[4 * i + 2], packed[4 * i + 3]};
+}
+
+// invq from the kernel's own arguments, or -- ragged flavours -- from the picture's argument block in the constant address space
+__device__ __forceinline__ void transform_and_store(const int (&blk)[64], const int *__restrict__ invq, int16_t *dst)
+{
+  transform_and_store_from(blk, invq, dst);
+}
+__device__ __forceinline__ void transform_and_store(const int (&blk)[64], const __attribute__((address_space(4))) int *invq, int16_t *dst)
+{
+  transform_and_store_from(blk, invq, dst);
 }
 
 // Interior blocks of RGB -> YCbCr frames with subsampling factors 1 or 2: the block's SX*8 x SY*8 pixels are read as
@@ -150,11 +163,49 @@ __device__ __forceinline__ void gather_block_fast(const uint8_t *img, int64_t ro
   }
 }
 
-__global__ __launch_bounds__(256) void fdct_blocks_kernel(const ForwardArgs a)
+// ---- where a workgroup finds its arguments ----------------------------------------------------------------------
+template <bool RAGGED>
+struct KernelArgs {
+  typedef ForwardArgs type;
+};
+template <>
+struct KernelArgs<true> {
+  typedef ForwardRaggedArgs type;
+};
+// the argument block of a picture in device memory, read-only for the whole launch: the constant address space makes every
+// read of it with a uniform address a scalar load (the geometry and the quantiser multipliers stay in SGPRs)
+typedef const __attribute__((address_space(4))) ForwardArgs ConstForwardArgs;
+typedef const __attribute__((address_space(4))) uint32_t const_u32;
+
+struct RaggedItem {
+  unsigned pic, comp, wg; // picture, component, workgroup inside the item -- uniform
+};
+__device__ __forceinline__ RaggedItem find_item(const ForwardRaggedArgs &r)
 {
+  const_u32 *first = (const_u32 *)r.first_wg;
+  unsigned lo = 0, hi = r.items; // first[lo] <= blockIdx.x < first[hi]
+  while (hi - lo > 1) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (first[mid] <= blockIdx.x) lo = mid;
+    else hi = mid;
+  }
+  const unsigned it = ((const_u32 *)r.item)[lo];
+  return RaggedItem{it >> 2, it & 3u, blockIdx.x - first[lo]};
+}
+
+// the argument block the workgroup works with: the kernel's own, or -- ragged -- its picture's in device memory
+__device__ __forceinline__ const ForwardArgs &args_of(const ForwardArgs &k, const RaggedItem &) { return k; }
+__device__ __forceinline__ ConstForwardArgs &args_of(const ForwardRaggedArgs &k, const RaggedItem &it) { return *((ConstForwardArgs *)k.pics + it.pic); }
+
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelArgs<RAGGED>::type k)
+{
+  RaggedItem it{};
+  if constexpr (RAGGED) it = find_item(k);
+  auto &a = args_of(k, it);
   const unsigned per_frame = a.first_block[a.ncomp];
-  const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned frame = blockIdx.y;
+  const unsigned gid = (RAGGED ? it.wg : blockIdx.x) * blockDim.x + threadIdx.x;
+  const unsigned frame = RAGGED ? 0u : blockIdx.y;
   if (gid >= per_frame) return;
   int c = 0;
   while (c + 1 < a.ncomp && gid >= a.first_block[c + 1]) c++;
@@ -221,12 +272,17 @@ __global__ __launch_bounds__(256) void fdct_blocks_kernel(const ForwardArgs a)
 // luma block, and leaves the 4 x 4 box-filtered chroma samples of its pixels (sums of 2 x 2, >> 2) in LDS; after a
 // barrier 128 lanes pick up the 64 + 64 chroma blocks of the tile and transform them.  Compared with the per-component
 // kernels no pixel is fetched or unpacked twice.  grid (tiles_x * tiles_y, frames)
-__global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const ForwardArgs a)
+template <bool RAGGED>
+__global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const typename KernelArgs<RAGGED>::type k)
 {
   __shared__ short chroma[2][64 * 64]; // [Cb, Cr][64 lines of 64 samples]
+  RaggedItem it{};
+  if constexpr (RAGGED) it = find_item(k);
+  auto &a = args_of(k, it);
   const int tiles_x = a.width >> 7;
-  const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
-  const unsigned frame = blockIdx.y;
+  const int tile = RAGGED ? (int)it.wg : (int)blockIdx.x;
+  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
+  const unsigned frame = RAGGED ? 0u : blockIdx.y;
   const uint8_t *img = a.pixels + (int64_t)frame * a.pixel_frame_stride;
   int16_t *coef = a.coef + (int64_t)frame * a.coef_frame_stride;
   const int lane = threadIdx.x;
@@ -279,10 +335,19 @@ __global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const ForwardArgs 
 }
 
 // the interior blocks of component c: grid (blocks of 256 lanes over fast_nbx * fast_nby, frames)
-template <int SX, int SY>
-__global__ __launch_bounds__(256, SX * SY == 4 ? 2 : 3) void fdct_interior_kernel(const ForwardArgs a, int c)
+// (The uniform 2 x 2 flavour fills its 256 registers and spills 32 bytes a lane; the ragged one needs a few more and gets one
+// workgroup per CU instead -- 512 registers, the surplus in AGPRs -- so that it touches no scratch memory.  It only sees what
+// the tile kernel leaves of a 4:2:0 picture: the strips right of and below the whole tiles, and pictures below 128 x 128.)
+template <int SX, int SY, bool RAGGED>
+__global__ __launch_bounds__(256, SX * SY == 4 ? (RAGGED ? 1 : 2) : 3) void fdct_interior_kernel(const typename KernelArgs<RAGGED>::type k, int c)
 {
-  const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x, frame = blockIdx.y;
+  RaggedItem it{};
+  if constexpr (RAGGED) {
+    it = find_item(k);
+    c = (int)it.comp;
+  }
+  auto &a = args_of(k, it);
+  const unsigned gid = (RAGGED ? it.wg : blockIdx.x) * blockDim.x + threadIdx.x, frame = RAGGED ? 0u : blockIdx.y;
   const unsigned n = (unsigned)a.fast_nbx[c] * (unsigned)a.fast_nby[c];
   if (gid >= n) return;
   const int by = (int)(gid / (unsigned)a.fast_nbx[c]), bx = (int)(gid - (unsigned)by * (unsigned)a.fast_nbx[c]);
@@ -298,19 +363,57 @@ int launch_forward(const ForwardArgs &a, hipStream_t stream)
 {
   const unsigned per_frame = a.first_block[a.ncomp];
   if (per_frame == 0 || a.frames < 1) return 0;
-  if (a.tiled420) hipLaunchKernelGGL(fdct420_tile_kernel, dim3((unsigned)(a.width >> 7) * (unsigned)(a.height >> 7), a.frames), dim3(256), 0, stream, a);
+  if (a.tiled420) hipLaunchKernelGGL(fdct420_tile_kernel<false>, dim3((unsigned)(a.width >> 7) * (unsigned)(a.height >> 7), a.frames), dim3(256), 0, stream, a);
   for (int c = 0; c < a.ncomp; c++) {
     if (!a.fast[c]) continue;
     const unsigned n = (unsigned)a.fast_nbx[c] * (unsigned)a.fast_nby[c];
     if (n == 0) continue;
     const dim3 grid((n + 255) / 256, a.frames);
     const int key = a.subx[c] * 4 + a.suby[c];
-    if (key == 5) hipLaunchKernelGGL((fdct_interior_kernel<1, 1>), grid, dim3(256), 0, stream, a, c);
-    else if (key == 10) hipLaunchKernelGGL((fdct_interior_kernel<2, 2>), grid, dim3(256), 0, stream, a, c);
-    else if (key == 9) hipLaunchKernelGGL((fdct_interior_kernel<2, 1>), grid, dim3(256), 0, stream, a, c);
-    else hipLaunchKernelGGL((fdct_interior_kernel<1, 2>), grid, dim3(256), 0, stream, a, c);
+    if (key == 5) hipLaunchKernelGGL((fdct_interior_kernel<1, 1, false>), grid, dim3(256), 0, stream, a, c);
+    else if (key == 10) hipLaunchKernelGGL((fdct_interior_kernel<2, 2, false>), grid, dim3(256), 0, stream, a, c);
+    else if (key == 9) hipLaunchKernelGGL((fdct_interior_kernel<2, 1, false>), grid, dim3(256), 0, stream, a, c);
+    else hipLaunchKernelGGL((fdct_interior_kernel<1, 2, false>), grid, dim3(256), 0, stream, a, c);
   }
-  hipLaunchKernelGGL(fdct_blocks_kernel, dim3((per_frame + 255) / 256, a.frames), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(fdct_blocks_kernel<false>, dim3((per_frame + 255) / 256, a.frames), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+int forward_ragged_items(const ForwardArgs &a, int which[5], uint32_t wgs[5], int comp[5])
+{
+  int k = 0;
+  const unsigned per_frame = a.first_block[a.ncomp];
+  if (per_frame == 0) return 0;
+  if (a.tiled420) { which[k] = 0; wgs[k] = (unsigned)(a.width >> 7) * (unsigned)(a.height >> 7); comp[k++] = 0; }
+  for (int c = 0; c < a.ncomp; c++) {
+    if (!a.fast[c]) continue;
+    const unsigned n = (unsigned)a.fast_nbx[c] * (unsigned)a.fast_nby[c];
+    if (n == 0) continue;
+    const int key = a.subx[c] * 4 + a.suby[c];
+    which[k] = key == 5 ? 1 : key == 10 ? 2 : key == 9 ? 3 : 4;
+    wgs[k] = (n + 255) / 256;
+    comp[k++] = c;
+  }
+  which[k] = 5; wgs[k] = (per_frame + 255) / 256; comp[k++] = 0;
+  return k;
+}
+
+int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *launches)
+{
+  for (int l = 0; l < FORWARD_RAGGED_LAUNCHES; l++) {
+    const ForwardRaggedArgs &r = p.launch[l];
+    if (r.items == 0 || p.grid[l] == 0) continue;
+    const dim3 grid(p.grid[l]);
+    switch (l) {
+    case 0: hipLaunchKernelGGL(fdct420_tile_kernel<true>, grid, dim3(256), 0, stream, r); break;
+    case 1: hipLaunchKernelGGL((fdct_interior_kernel<1, 1, true>), grid, dim3(256), 0, stream, r, 0); break;
+    case 2: hipLaunchKernelGGL((fdct_interior_kernel<2, 2, true>), grid, dim3(256), 0, stream, r, 0); break;
+    case 3: hipLaunchKernelGGL((fdct_interior_kernel<2, 1, true>), grid, dim3(256), 0, stream, r, 0); break;
+    case 4: hipLaunchKernelGGL((fdct_interior_kernel<1, 2, true>), grid, dim3(256), 0, stream, r, 0); break;
+    default: hipLaunchKernelGGL(fdct_blocks_kernel<true>, grid, dim3(256), 0, stream, r); break;
+    }
+    if (launches) ++*launches;
+  }
   return (int)hipGetLastError();
 }
 

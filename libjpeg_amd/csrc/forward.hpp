@@ -29,5 +29,28 @@ struct ForwardArgs {
 
 int launch_forward(const ForwardArgs &a, hipStream_t stream);
 
+// Ragged flavour: pictures of different sizes and layouts in one launch per kernel family.  Every picture has a filled
+// ForwardArgs of its own in device memory (frames = 1, its own pixels, coefficient store and invq: the 1 KiB of quantiser
+// multipliers per picture).  A launch is a list of work items -- a picture, for the interior kernels a picture's component --
+// each with a whole number of workgroups; a workgroup finds its item by a binary search over first_wg and never spans two.
+struct ForwardRaggedArgs {
+  const ForwardArgs *pics;   // device
+  const uint32_t *first_wg;  // device, items + 1 entries: first workgroup of every item, the launch's grid behind the last
+  const uint32_t *item;      // device, per item: picture * 4 + component
+  uint32_t items;
+};
+// The launches of a ragged list, in the order launch_forward_ragged issues them: the 4:2:0 tile kernel, the interior kernels
+// <1,1> <2,2> <2,1> <1,2>, the per-block kernel.  The routing per picture is launch_forward's.
+constexpr int FORWARD_RAGGED_LAUNCHES = 6;
+struct ForwardRaggedPlan {
+  ForwardRaggedArgs launch[FORWARD_RAGGED_LAUNCHES]; // items == 0: not launched
+  uint32_t grid[FORWARD_RAGGED_LAUNCHES];
+};
+// The work items picture `a` contributes: wgs[k] workgroups and item component comp[k] per entry, launch index which[k]; returns
+// the number of entries (at most 5).  Host side of the routing rule, shared by the planner and the launcher.
+int forward_ragged_items(const ForwardArgs &a, int which[5], uint32_t wgs[5], int comp[5]);
+// returns 0 or a hipError_t; *launches: kernels launched
+int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *launches);
+
 } // namespace mij
 #endif

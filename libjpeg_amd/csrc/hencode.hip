@@ -11,6 +11,8 @@
 //             words, hence atomicOr on a zeroed buffer); the last block of an interval pads with one-bits
 //   stuff     0xFF bytes per 64-byte chunk, prefix sums, then every chunk is copied to its place with a zero byte behind
 //             every 0xFF and the RSTn markers in front of the intervals
+// Every pass exists in two flavours that share their code (OneFrame / Batch below): for one frame, whose argument block travels
+// with the launch, and over all pictures of a list at once.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -26,6 +28,7 @@ constexpr uint8_t ZZ[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 
                             30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+constexpr int STUFF_CHUNK = HENC_STUFF_CHUNK;
 
 __device__ __forceinline__ int category(int v)
 {
@@ -112,17 +115,49 @@ __device__ __forceinline__ void load_tables(HencTables *lds, const HencTables *s
   __syncthreads();
 }
 
-template <bool STATS>
-__global__ __launch_bounds__(256) void henc_count_kernel(const HencArgs a)
+// ---- how a kernel finds its arguments ---------------------------------------------------------------------------
+// OneFrame: the launch is one frame's and carries the argument block; a lane's index in the launch is its block, interval or
+// chunk.  Batch: the launch runs over all pictures of a pass (HencBatchArgs, hencode.hpp); a workgroup of the per-block kernels,
+// a lane of the others, looks its picture up in the pass's prefix table and goes on with that picture's argument block in
+// device memory and the index inside the picture.
+struct OneFrame {
+  typedef HencArgs Args;
+  static constexpr bool BATCH = false;
+};
+struct Batch {
+  typedef HencBatchArgs Args;
+  static constexpr bool BATCH = true;
+};
+
+// last picture whose entry of `first` is at or below x; first: n + 1 ascending entries, first[0] = 0, x < first[n]
+__device__ __forceinline__ uint32_t find_picture(const HencBatchArgs &b, const uint32_t *first, uint32_t x)
+{
+  uint32_t lo = 0, hi = b.n;
+  while (hi - lo > 1) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (first[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+__device__ __forceinline__ const HencArgs &args_of(const HencArgs &k, uint32_t) { return k; }
+__device__ __forceinline__ const HencArgs &args_of(const HencBatchArgs &k, uint32_t pic) { return k.pics[pic]; }
+
+template <class F, bool STATS>
+__global__ __launch_bounds__(256) void henc_count_kernel(const typename F::Args k)
 {
   __shared__ HencTables tab;
   __shared__ uint32_t hist[STATS ? 4 * 256 : 1];
+  uint32_t pic = 0; // (a picture's blocks are padded to whole workgroups: uniform)
+  if constexpr (F::BATCH) pic = find_picture(k, k.first_block, blockIdx.x * blockDim.x);
+  const HencArgs &a = args_of(k, pic);
   load_tables(&tab, a.tables);
   if (STATS) {
     for (unsigned i = threadIdx.x; i < 4 * 256; i += blockDim.x) hist[i] = 0;
     __syncthreads();
   }
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (F::BATCH) s -= k.first_block[pic];
   if (s < a.total_blocks) {
     const BlockRef r = locate(a, s);
     uint32_t bits = 0;
@@ -138,6 +173,8 @@ __global__ __launch_bounds__(256) void henc_count_kernel(const HencArgs a)
           if (STATS) atomicAdd(&hist[512 + t * 256 + sym], 1u);
         });
     a.bits[s] = bits;
+  } else if (F::BATCH) {
+    a.bits[s] = 0; // padding up to the next picture's first block
   }
   if (STATS) {
     __syncthreads();
@@ -147,9 +184,17 @@ __global__ __launch_bounds__(256) void henc_count_kernel(const HencArgs a)
 }
 
 // bytes of every interval before stuffing: its bits rounded up
-__global__ __launch_bounds__(256) void henc_interval_bytes_kernel(const HencArgs a)
+template <class F>
+__global__ __launch_bounds__(256) void henc_interval_bytes_kernel(const typename F::Args k)
 {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t pic = 0;
+  if constexpr (F::BATCH) {
+    if (i >= k.total_intervals) return;
+    pic = find_picture(k, k.first_interval, i);
+    i -= k.first_interval[pic];
+  }
+  const HencArgs &a = args_of(k, pic);
   if (i >= a.n_intervals) return;
   const uint64_t per = (uint64_t)a.ri * (uint64_t)a.blocks_per_mcu;
   const uint64_t b0 = (uint64_t)i * per, b1 = min((uint64_t)a.total_blocks, b0 + per);
@@ -191,19 +236,26 @@ struct WordWriter {
   }
 };
 
-__global__ __launch_bounds__(256) void henc_emit_kernel(const HencArgs a)
+template <class F>
+__global__ __launch_bounds__(256) void henc_emit_kernel(const typename F::Args k)
 {
   __shared__ HencTables tab;
+  uint32_t pic = 0;
+  if constexpr (F::BATCH) pic = find_picture(k, k.first_block, blockIdx.x * blockDim.x);
+  const HencArgs &a = args_of(k, pic);
   load_tables(&tab, a.tables);
-  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if constexpr (F::BATCH) s -= k.first_block[pic];
   if (s >= a.total_blocks) return;
   const BlockRef r = locate(a, s);
   const uint64_t per = (uint64_t)a.ri * (uint64_t)a.blocks_per_mcu;
   const uint32_t interval = (uint32_t)(s / per);
   const uint64_t first = (uint64_t)interval * per;
-  const uint64_t pos = a.istart[interval] * 8 + (a.bitpos[s] - a.bitpos[first]);
+  uint64_t ibyte = a.istart[interval]; // where the interval starts in the plain stream
+  if constexpr (F::BATCH) ibyte = (uint64_t)k.first_chunk[pic] * STUFF_CHUNK + (ibyte - a.istart[0]);
+  const uint64_t pos = ibyte * 8 + (a.bitpos[s] - a.bitpos[first]);
   WordWriter w;
-  w.open(a.plain, pos);
+  w.open(k.plain, pos);
   const int t = r.table;
   walk_symbols(
       r,
@@ -225,8 +277,6 @@ __global__ __launch_bounds__(256) void henc_emit_kernel(const HencArgs a)
 
 __device__ __forceinline__ uint32_t plain_byte(const uint32_t *plain, uint64_t u) { return (plain[u >> 2] >> (24 - 8 * (int)(u & 3))) & 0xffu; }
 
-constexpr int STUFF_CHUNK = HENC_STUFF_CHUNK;
-
 __global__ __launch_bounds__(256) void henc_count_ff_kernel(const HencArgs a)
 {
   const uint64_t chunk = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -242,28 +292,52 @@ __global__ __launch_bounds__(256) void henc_count_ff_kernel(const HencArgs a)
   a.ffcount[chunk] = n;
 }
 
-// Copies chunk by chunk: a zero byte behind every 0xFF, RSTn in front of every interval but the first
-__global__ __launch_bounds__(256) void henc_stuff_kernel(const HencArgs a)
+// Copies chunk by chunk: a zero byte behind every 0xFF, RSTn in front of every interval but the first (of the picture)
+template <class F>
+__global__ __launch_bounds__(256) void henc_stuff_kernel(const typename F::Args k)
 {
-  const uint64_t chunk = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint64_t chunk = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // Batch: the picture's plain stream starts at byte `origin` of the common buffer, its istart entries count from `i0`, and its
+  // output lies behind the stuffing bytes and markers of the pictures in front (HencBatchArgs)
+  uint32_t pic = 0;
+  uint64_t origin = 0, i0 = 0, plain_bytes, out_at = 0;
+  if constexpr (F::BATCH) {
+    if (chunk >= k.total_chunks) return;
+    pic = find_picture(k, k.first_chunk, (uint32_t)chunk);
+    origin = (uint64_t)k.first_chunk[pic] * STUFF_CHUNK;
+    out_at = origin + k.ffstart[chunk] + 2ull * (uint64_t)(k.first_interval[pic] - pic);
+    chunk -= k.first_chunk[pic];
+  }
+  const HencArgs &a = args_of(k, pic);
+  if constexpr (F::BATCH) {
+    i0 = a.istart[0];
+    plain_bytes = a.istart[a.n_intervals] - i0;
+  } else {
+    plain_bytes = a.plain_bytes;
+  }
+  auto istart = [&](uint32_t i) -> uint64_t {
+    if constexpr (F::BATCH) return a.istart[i] - i0;
+    else return a.istart[i];
+  };
   const uint64_t u0 = chunk * STUFF_CHUNK;
-  if (u0 >= a.plain_bytes) return;
-  const uint64_t u1 = min(a.plain_bytes, u0 + STUFF_CHUNK);
+  if (u0 >= plain_bytes) return;
+  const uint64_t u1 = min(plain_bytes, u0 + STUFF_CHUNK);
   // first interval whose start lies at or behind u0 (istart is ascending, istart[0] = 0)
   uint32_t lo = 0, hi = a.n_intervals;
   while (lo < hi) {
     const uint32_t mid = (lo + hi) >> 1;
-    if (a.istart[mid] < u0) lo = mid + 1;
+    if (istart(mid) < u0) lo = mid + 1;
     else hi = mid;
   }
   uint32_t next = lo; // intervals [1, next) have put their markers in front of earlier bytes
-  uint8_t *q = a.out + u0 + a.ffstart[chunk] + 2ull * (uint64_t)(next > 0 ? next - 1 : 0);
+  if constexpr (!F::BATCH) out_at = a.ffstart[chunk];
+  uint8_t *q = k.out + u0 + out_at + 2ull * (uint64_t)(next > 0 ? next - 1 : 0);
   for (uint64_t u = u0; u < u1; u++) {
-    while (next < a.n_intervals && a.istart[next] == u) {
+    while (next < a.n_intervals && istart(next) == u) {
       if (next > 0) { *q++ = 0xff; *q++ = (uint8_t)(0xd0 + ((next - 1) & 7)); }
       next++;
     }
-    const uint32_t b = plain_byte(a.plain, u);
+    const uint32_t b = plain_byte(k.plain, origin + u);
     *q++ = (uint8_t)b;
     if (b == 0xff) *q++ = 0;
   }
@@ -308,6 +382,13 @@ __global__ __launch_bounds__(SCAN_TILE) void scan_apply_kernel(const T *in, cons
   if (i <= n) out[i] = before + v - mine;
 }
 
+// dst[i] = src[idx[i]]
+__global__ __launch_bounds__(256) void henc_gather_kernel(const uint64_t *src, const uint32_t *idx, uint64_t *dst, uint32_t n)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) dst[i] = src[idx[i]];
+}
+
 } // namespace
 
 int exclusive_scan_u32(const uint32_t *in, uint64_t *out, uint32_t n, uint64_t *scratch, hipStream_t stream)
@@ -337,18 +418,18 @@ int exclusive_scan_u32(const uint32_t *in, uint64_t *out, uint32_t n, uint64_t *
 int henc_count(const HencArgs &a, bool statistics, hipStream_t stream)
 {
   const dim3 grid((a.total_blocks + 255) / 256);
-  if (statistics) hipLaunchKernelGGL(henc_count_kernel<true>, grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(henc_count_kernel<false>, grid, dim3(256), 0, stream, a);
+  if (statistics) hipLaunchKernelGGL((henc_count_kernel<OneFrame, true>), grid, dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL((henc_count_kernel<OneFrame, false>), grid, dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }
 int henc_interval_bytes(const HencArgs &a, hipStream_t stream)
 {
-  hipLaunchKernelGGL(henc_interval_bytes_kernel, dim3((a.n_intervals + 255) / 256), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(henc_interval_bytes_kernel<OneFrame>, dim3((a.n_intervals + 255) / 256), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }
 int henc_emit(const HencArgs &a, hipStream_t stream)
 {
-  hipLaunchKernelGGL(henc_emit_kernel, dim3((a.total_blocks + 255) / 256), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(henc_emit_kernel<OneFrame>, dim3((a.total_blocks + 255) / 256), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }
 static inline uint32_t stuff_chunks(const HencArgs &a) { return (uint32_t)((a.plain_bytes + STUFF_CHUNK - 1) / STUFF_CHUNK); }
@@ -359,7 +440,45 @@ int henc_count_ff(const HencArgs &a, hipStream_t stream)
 }
 int henc_stuff(const HencArgs &a, hipStream_t stream)
 {
-  hipLaunchKernelGGL(henc_stuff_kernel, dim3((stuff_chunks(a) + 255) / 256), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(henc_stuff_kernel<OneFrame>, dim3((stuff_chunks(a) + 255) / 256), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+// ---- the same passes over all pictures of a list ----------------------------------------------------------------
+int henc_count(const HencBatchArgs &b, bool statistics, hipStream_t stream)
+{
+  const dim3 grid(b.total_blocks / 256); // (padded per picture)
+  if (statistics) hipLaunchKernelGGL((henc_count_kernel<Batch, true>), grid, dim3(256), 0, stream, b);
+  else hipLaunchKernelGGL((henc_count_kernel<Batch, false>), grid, dim3(256), 0, stream, b);
+  return (int)hipGetLastError();
+}
+int henc_interval_bytes(const HencBatchArgs &b, hipStream_t stream)
+{
+  hipLaunchKernelGGL(henc_interval_bytes_kernel<Batch>, dim3((b.total_intervals + 255) / 256), dim3(256), 0, stream, b);
+  return (int)hipGetLastError();
+}
+int henc_emit(const HencBatchArgs &b, hipStream_t stream)
+{
+  hipLaunchKernelGGL(henc_emit_kernel<Batch>, dim3(b.total_blocks / 256), dim3(256), 0, stream, b);
+  return (int)hipGetLastError();
+}
+int henc_count_ff(const HencBatchArgs &b, hipStream_t stream)
+{
+  // the gaps between the pictures are zero like the tail behind a single frame's stream: the one-frame kernel counts the lot
+  HencArgs a{};
+  a.plain = b.plain;
+  a.plain_bytes = (uint64_t)b.total_chunks * STUFF_CHUNK;
+  a.ffcount = b.ffcount;
+  return henc_count_ff(a, stream);
+}
+int henc_stuff(const HencBatchArgs &b, hipStream_t stream)
+{
+  hipLaunchKernelGGL(henc_stuff_kernel<Batch>, dim3((b.total_chunks + 255) / 256), dim3(256), 0, stream, b);
+  return (int)hipGetLastError();
+}
+int henc_gather(const uint64_t *src, const uint32_t *idx, uint64_t *dst, uint32_t n, hipStream_t stream)
+{
+  hipLaunchKernelGGL(henc_gather_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, src, idx, dst, n);
   return (int)hipGetLastError();
 }
 

@@ -37,11 +37,40 @@ struct HencArgs {
   uint32_t *hist;               // optional statistics: [2][256] DC symbol counts, [2][256] AC symbol counts
 };
 
+// Batch-wide flavour (encode_device.cpp): ONE launch of every pass over all pictures of a list.  Every picture has an argument
+// block of its own in device memory whose bits / bitpos / ibytes / istart point at the picture's own first block and first
+// interval inside arrays that run over the whole pass (the kernels only ever look at differences of bitpos and istart, so the
+// picture's entries of the pass-wide prefix sums serve as they are) and whose coef / tables / hist are the picture's.  plain,
+// ffcount, ffstart and out of those blocks are not read: they are the pass's, below.
+//   blocks     padded per picture to a multiple of 256: a workgroup belongs to one picture, padding lanes write bits = 0
+//   intervals  the pictures' lists one behind the other; every picture starts a new interval
+//   plain      picture p from byte first_chunk[p] * HENC_STUFF_CHUNK of a common zeroed buffer: no word and no chunk is shared
+//   out        the plain layout with the stuffing bytes and markers of everything in front added: picture p's entropy coded
+//              segment starts at first_chunk[p] * HENC_STUFF_CHUNK + ffstart[first_chunk[p]] + 2 * (first_interval[p] - p)
+struct HencBatchArgs {
+  const HencArgs *pics;           // device, n entries
+  const uint32_t *first_block;    // n + 1 entries, multiples of 256
+  const uint32_t *first_interval; // n + 1 entries
+  const uint32_t *first_chunk;    // n + 1 entries (known once the plain sizes are: henc_emit and later)
+  uint32_t n, total_blocks, total_intervals, total_chunks;
+  uint32_t *plain;
+  uint32_t *ffcount;
+  const uint64_t *ffstart;
+  uint8_t *out;
+};
+
 int henc_count(const HencArgs &a, bool statistics, hipStream_t stream);      // bits[] (and hist[])
 int henc_interval_bytes(const HencArgs &a, hipStream_t stream);              // ibytes[] from bitpos[]
 int henc_emit(const HencArgs &a, hipStream_t stream);                        // plain[]
 int henc_count_ff(const HencArgs &a, hipStream_t stream);                    // ffcount[]
 int henc_stuff(const HencArgs &a, hipStream_t stream);                       // out[]
+int henc_count(const HencBatchArgs &b, bool statistics, hipStream_t stream);
+int henc_interval_bytes(const HencBatchArgs &b, hipStream_t stream);
+int henc_emit(const HencBatchArgs &b, hipStream_t stream);
+int henc_count_ff(const HencBatchArgs &b, hipStream_t stream); // (the one-frame kernel over the common plain buffer)
+int henc_stuff(const HencBatchArgs &b, hipStream_t stream);
+// dst[i] = src[idx[i]], i < n: the entries of a pass-wide prefix sum the host lays the pictures out with
+int henc_gather(const uint64_t *src, const uint32_t *idx, uint64_t *dst, uint32_t n, hipStream_t stream);
 // out[i] = sum of in[0..i) for i = 0..n (n + 1 entries); scratch: at least (n / 1024 + 2) * 2 uint64
 int exclusive_scan_u32(const uint32_t *in, uint64_t *out, uint32_t n, uint64_t *scratch, hipStream_t stream);
 
