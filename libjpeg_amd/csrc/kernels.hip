@@ -1403,53 +1403,119 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
   u32x4 yraw[8];
 
   // ------------------------------------------------------------------ phase A: chroma -> LDS halves
+  // Of the tile's 10 x 10 chroma blocks per component the filters read the 8 x 8 interior in full, but of the ring around it only
+  // the column, the line or the single sample that touches the interior.  The four waves take four roles (wave-uniform: no
+  // divergence between the transforms): the interior of Cb, the interior of Cr, the ring of Cb, the ring of Cr.  The roles rotate
+  // with the workgroup so that every SIMD of a CU sees the heavier interior waves and the lighter ring waves alike.
+  // LDS line pr <-> chroma line ty * 64 + pr - 1, column pc <-> chroma column tx * 64 + pc - 4.
   {
-    const int comp = wave >> 1; // 0 = Cb (low halves), 1 = Cr (high halves); wave-uniform
+    const int role = (wave + (int)((blockIdx.x >> 3) + (blockIdx.x >> 8))) & 3; // (>> 3: workgroups of one XCD; >> 8: of one CU, roughly)
+    const int comp = role & 1; // 0 = Cb (low halves), 1 = Cr (high halves); wave-uniform
     const int16_t *__restrict__ plane = coef + (comp ? a.off_cr : a.off_cb);
-    const int gx0 = tx * 8 - 1, gy0 = ty * 8 - 1;
-    const int base = (wave & 1) * 64;
-    const bool inside = gx0 >= 0 && gy0 >= 0 && gx0 + F420_CGRID <= a.bw_c && gy0 + F420_CGRID <= a.bh_c;
-    u32x4 rows[8];
-    const int idx0 = base + (lane >> 3);
     const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    if (inside) {
-      const unsigned off0 = (unsigned)((gy0 * a.bw_c + gx0) * 128), rowb = (unsigned)a.bw_c * 128u;
+    const int *q = frame_deltas<QDEV>(a, frame, 1 + comp);
+    short *cp = reinterpret_cast<short *>(cpair) + comp; // this component's half of every dword
+    const int gx0 = tx * 8, gy0 = ty * 8;                // the interior's first block
+    const int nb = lane >> 3;
+    if (role < 2) {
+      // interior: local block n = (lane >> 3) + 8 m is column lane >> 3 of row m -- one load covers a row's 1 KB
+      u32x4 rows[8];
+      const unsigned xoff = (unsigned)min(gx0 + nb, a.bw_c - 1) * 128u;
       fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-        const unsigned i = (unsigned)min(idx0 + 8 * m, F420_CGRID * F420_CGRID - 1);
-        const unsigned y = (i * 205u) >> 11, x = i - y * F420_CGRID; // i / 10, i % 10 for i < 1029
-        return reinterpret_cast<const u32x4 *>(pbase + (off0 + y * rowb + x * 128u));
+        const int yy = min(gy0 + m, a.bh_c - 1);
+        return reinterpret_cast<const u32x4 *>(pbase + ((unsigned)(yy * a.bw_c) * 128u + xoff));
       });
+      load_tile_blocks(yraw, t, coef + a.off_y, a.bw_y, a.bh_y);
+      const int cbx = lane & 7, cby = lane >> 3;
+      if (gx0 + cbx < a.bw_c && gy0 + cby < a.bh_c) {
+        int at = (8 * cby + 1) * F420_CPITCH + 8 * cbx + 4; // the lane's first sample
+        // (per-frame tables: the index is formed here and held across the transform.  The build then allocates the 133 registers
+        // this instantiation had before the ring was split off, the count tests/test_ragged_batch.py holds it to; 132 otherwise.
+        // Three workgroups per CU either way.)
+        if (QDEV) asm volatile("" : "+v"(at));
+        int v[64];
+        dequant_idct_sparse<!QDEV, false, D2>(rows, q, v);
+        short *dst = cp + 2 * at; // one base per lane: the 64 stores take immediate offsets
+#pragma unroll
+        for (int r = 0; r < 8; r++)
+#pragma unroll
+          for (int x = 0; x < 8; x++) dst[2 * (r * F420_CPITCH + x)] = (short)v[r * 8 + x];
+      }
     } else {
-      fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-        const int i = min(idx0 + 8 * m, F420_CGRID * F420_CGRID - 1);
-        const int y = (i * 205) >> 11, x = i - y * F420_CGRID;
-        const int gx = min(max(gx0 + x, 0), a.bw_c - 1), gy = min(max(gy0 + y, 0), a.bh_c - 1);
-        return reinterpret_cast<const u32x4 *>(pbase + (unsigned)((gy * a.bw_c + gx) * 128));
-      });
-    }
-    const int idx = base + lane;
-    const int cby = idx / F420_CGRID, cbx = idx - cby * F420_CGRID;
-    const int gx = gx0 + cbx, gy = gy0 + cby;
-    load_tile_blocks(yraw, t, coef + a.off_y, a.bw_y, a.bh_y);
-    if (idx < F420_CGRID * F420_CGRID && gx >= 0 && gy >= 0 && gx < a.bw_c && gy < a.bh_c) {
-      int v[64];
-      dequant_idct_sparse<!QDEV, false, D2>(rows, frame_deltas<QDEV>(a, frame, 1 + comp), v);
-      short *cp = reinterpret_cast<short *>(cpair) + comp; // this component's half of every dword
+      // ring.  Columns and corners, lane-owns-block: block n = 0..15 is the left (n even) or right (n odd) neighbour of interior
+      // row n >> 1; n = 16..19 are the corners (bit 0: right, bit 1: below).  Lines, on the fetching lanes: the blocks above and
+      // below interior column lane >> 3 (dequant_idct_line8).  All five requests leave before the luma request.
+      auto chunk = [&](int gx, int gy) -> u32x4 {
+        const int xx = min(max(gx, 0), a.bw_c - 1), yy = min(max(gy, 0), a.bh_c - 1);
+        return *reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_c + xx) * 128));
+      };
+      const int gxs = (nb & 1) ? gx0 + 8 : gx0 - 1;
+      const u32x4 side0 = chunk(gxs, gy0 + (nb >> 1)), side1 = chunk(gxs, gy0 + 4 + (nb >> 1));
+      const u32x4 corner = chunk(gxs, (nb & 2) ? gy0 + 8 : gy0 - 1);
+      const u32x4 above = chunk(gx0 + nb, gy0 - 1), below = chunk(gx0 + nb, gy0 + 8);
+      load_tile_blocks(yraw, t, coef + a.off_y, a.bw_y, a.bh_y);
+      {
+        u32x4 rows[8];
+        const int k = lane & 7;
+        stage[nb * 8 + (k ^ nb)] = side0;
+        stage[(nb + 8) * 8 + (k ^ nb)] = side1;
+        __builtin_amdgcn_wave_barrier();
+        if (lane < 16) {
 #pragma unroll
-      for (int r = 0; r < 8; r++) {
-        const int pr = 8 * cby + r - 7;
-        const int line = pr * F420_CPITCH;
-        if (pr >= 0 && pr < F420_CROWS) {
-          if (cbx == 0) {
-            cp[2 * (line + 3)] = (short)v[r * 8 + 7];
-          } else if (cbx == F420_CGRID - 1) {
-            cp[2 * (line + 68)] = (short)v[r * 8 + 0];
+          for (int r = 0; r < 8; r++) rows[r] = stage[lane * 8 + (r ^ (lane & 7))];
+        }
+        __builtin_amdgcn_wave_barrier();
+        stage[nb * 8 + (k ^ nb)] = corner; // (blocks 4..7 repeat 0..3 and are not read)
+        __builtin_amdgcn_wave_barrier();
+        if (lane >= 16 && lane < 20) {
+#pragma unroll
+          for (int r = 0; r < 8; r++) rows[r] = stage[(lane - 16) * 8 + (r ^ (lane - 16))];
+        }
+        __builtin_amdgcn_wave_barrier();
+        const bool right = lane & 1, is_corner = lane >= 16, low = lane & 2;
+        const int gx = right ? gx0 + 8 : gx0 - 1, gy = is_corner ? (low ? gy0 + 8 : gy0 - 1) : gy0 + (lane >> 1);
+        if (lane < 20 && gx >= 0 && gx < a.bw_c && gy >= 0 && gy < a.bh_c) {
+          int col[8];
+          dequant_idct_column(rows, q, !right, col); // left neighbour: its last column, right one: its first
+          const int pc = right ? 68 : 3;
+          if (is_corner) {
+            cp[2 * ((low ? F420_CROWS - 1 : 0) * F420_CPITCH + pc)] = (short)(low ? col[0] : col[7]);
           } else {
-            short *dst = cp + 2 * (line + 8 * cbx - 4);
+            short *dst = cp + 2 * ((8 * (lane >> 1) + 1) * F420_CPITCH + pc);
 #pragma unroll
-            for (int x = 0; x < 8; x++) dst[2 * x] = (short)v[r * 8 + x];
+            for (int r = 0; r < 8; r++) dst[2 * r * F420_CPITCH] = (short)col[r];
           }
         }
+      }
+      {
+        constexpr int W[8] = {512, FIX9(1.501321110) - FIX9(0.899976223) - FIX9(0.390180644) + FIX9(1.175875602), FIX9(0.541196100) + FIX9(0.765366865),
+                              FIX9(1.175875602), 512, FIX9(1.175875602) - FIX9(0.390180644), FIX9(0.541196100), FIX9(1.175875602) - FIX9(0.899976223)};
+        const int k = lane & 7;
+        // the deltas of row k, per lane: read from the kernel argument segment itself (see fused440_kernel)
+        typedef const __attribute__((address_space(4))) int kernarg_int;
+        int qrow[8];
+        if (QDEV) {
+          const int *qk = q + k * 8;
+#pragma unroll
+          for (int i = 0; i < 8; i++) qrow[i] = qk[i];
+        } else {
+          kernarg_int *qk = (kernarg_int *)__builtin_amdgcn_kernarg_segment_ptr() + (offsetof(Fused420Args, q) / sizeof(int) + (1 + comp) * QROW + k * 8);
+#pragma unroll
+          for (int i = 0; i < 8; i++) qrow[i] = qk[i];
+        }
+        const int weight = W[k];
+        int line[8];
+        short *dst = cp + 2 * (8 * nb + 4 + k);
+        const bool col_ok = gx0 + nb < a.bw_c;
+        auto mine = [&](const int (&l)[8]) { // line[k] without a register-indexed access
+          const int a01 = (k & 1) ? l[1] : l[0], a23 = (k & 1) ? l[3] : l[2], a45 = (k & 1) ? l[5] : l[4], a67 = (k & 1) ? l[7] : l[6];
+          const int lo = (k & 2) ? a23 : a01, hi = (k & 2) ? a67 : a45;
+          return (short)((k & 4) ? hi : lo);
+        };
+        dequant_idct_line8(above, qrow, (k & 1) ? -weight : weight, line); // the block above: its last line (even - odd)
+        if (col_ok && gy0 > 0) dst[0] = mine(line);
+        dequant_idct_line8(below, qrow, weight, line); // the block below: its first line (even + odd)
+        if (col_ok && gy0 + 8 < a.bh_c) dst[2 * (F420_CROWS - 1) * F420_CPITCH] = mine(line);
       }
     }
   }

@@ -2,7 +2,8 @@
 // frames (coefficients int16 planar: 3 B/pixel in, interleaved RGB: 3 B/pixel out):
 //   copy     : the ideal -- every lane reads 16 contiguous bytes and writes 16 contiguous bytes, grid-stride, dwordx4 both ways;
 //   pattern  : the fused kernel's access pattern -- one workgroup per 128 x 128 tile (XCD-aware order), phase A reads the
-//              10 x 10 chroma blocks of both planes (1 KB per wave-instruction), phase B the 16 x 16 luma blocks, then every lane
+//              10 x 10 chroma blocks of both planes (two waves the 8 x 8 interiors, 1 KB per wave-instruction; two waves the rings:
+//              chroma_loads below), phase B the 16 x 16 luma blocks, then every lane
 //              writes the 8 lines of its 8 x 8 block as 24-byte pieces (dwordx4 + dwordx2, non-temporal), lines 23 040 B apart;
 //   pattern-t: the same with temporal stores.
 // The stored values are a cheap mix of what was loaded, so nothing is optimised away.  Prints ms per launch and TB/s of the
@@ -35,6 +36,31 @@ __global__ __launch_bounds__(256) void copy_kernel(const u32x4 *__restrict__ in,
   }
 }
 
+// Phase A of fused420p_kernel, loads only: the wave's role rotates with the workgroup; roles 0, 1 fetch the 8 x 8 interior blocks
+// of Cb, Cr (load m: the eight blocks of row m), roles 2, 3 the ring of Cb, Cr in five loads -- the left / right neighbours of
+// rows 0..3 and of rows 4..7, the corners (each twice, as the kernel has it), the blocks above, the blocks below.
+__device__ __forceinline__ void chroma_loads(const int16_t *coef, int64_t off_cb, int64_t off_cr, int tx, int ty, int wave, int lane, u32x4 &acc)
+{
+  const int role = (wave + (int)((blockIdx.x >> 3) + (blockIdx.x >> 8))) & 3, nb = lane >> 3;
+  const char *pbase = reinterpret_cast<const char *>(coef + ((role & 1) ? off_cr : off_cb)) + (lane & 7) * 16;
+  const int gx0 = tx * 8, gy0 = ty * 8;
+  auto chunk = [&](int gx, int gy) {
+    const int xx = min(max(gx, 0), BWC - 1), yy = min(max(gy, 0), BHC - 1);
+    acc ^= *reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * BWC + xx) * 128));
+  };
+  if (role < 2) {
+#pragma unroll
+    for (int m = 0; m < 8; m++) chunk(gx0 + nb, gy0 + m);
+  } else {
+    const int gxs = (nb & 1) ? gx0 + 8 : gx0 - 1;
+    chunk(gxs, gy0 + (nb >> 1));
+    chunk(gxs, gy0 + 4 + (nb >> 1));
+    chunk(gxs, (nb & 2) ? gy0 + 8 : gy0 - 1);
+    chunk(gx0 + nb, gy0 - 1);
+    chunk(gx0 + nb, gy0 + 8);
+  }
+}
+
 template <bool NT>
 __global__ __launch_bounds__(256, 4) void pattern_kernel(const int16_t *__restrict__ coef_all, uint8_t *__restrict__ out_all)
 {
@@ -50,16 +76,7 @@ __global__ __launch_bounds__(256, 4) void pattern_kernel(const int16_t *__restri
   const int16_t *coef = coef_all + frame * COEF_FRAME;
   const int64_t off_cb = (int64_t)BWY * BHY * 64, off_cr = off_cb + (int64_t)BWC * BHC * 64;
   u32x4 acc = {0, 0, 0, 0};
-  { // phase A: waves 0, 1 Cb, waves 2, 3 Cr; 100 blocks each over two waves
-    const int16_t *plane = coef + (wave >> 1 ? off_cr : off_cb);
-    const int gx0 = tx * 8 - 1, gy0 = ty * 8 - 1, base = (wave & 1) * 64;
-#pragma unroll
-    for (int m = 0; m < 8; m++) {
-      const int i = min(base + (lane >> 3) + 8 * m, 99), y = i / 10, x = i - y * 10;
-      const int gx = min(max(gx0 + x, 0), BWC - 1), gy = min(max(gy0 + y, 0), BHC - 1);
-      acc ^= *reinterpret_cast<const u32x4 *>(reinterpret_cast<const char *>(plane) + (lane & 7) * 16 + (unsigned)((gy * BWC + gx) * 128));
-    }
-  }
+  chroma_loads(coef, off_cb, off_cr, tx, ty, wave, lane, acc); // phase A
   __syncthreads();
   { // phase B: 16 x 4 luma blocks per wave
     const int gbx0 = tx * 16, gby0 = ty * 16 + wave * 4;
@@ -115,7 +132,9 @@ __global__ __launch_bounds__(256, 4) void shape_kernel(const int16_t *__restrict
   const int64_t off_cb = (int64_t)BWY * BHY * 64, off_cr = off_cb + (int64_t)BWC * BHC * 64;
   u32x4 acc = {(uint32_t)tid, 0, 0, 0};
   if (MODE != 2) {
-    { // chroma grid incl. halo, both planes: 2 * NC blocks over 4 waves, 8 blocks per wave-instruction
+    if (TBX == 16 && TBY == 16) { // the kernel's own tile: its phase A
+      chroma_loads(coef, off_cb, off_cr, tx, ty, wave, lane, acc);
+    } else { // chroma grid incl. halo, both planes: 2 * NC blocks over 4 waves, 8 blocks per wave-instruction
       const int gx0 = tx * (TBX / 2) - 1, gy0 = ty * (TBY / 2) - 1;
       for (int i0 = wave * 8 + (lane >> 3); i0 < 2 * NC; i0 += 32) {
         const int pl = i0 >= NC, i = i0 - pl * NC, y = i / CGX, x = i - y * CGX;
