@@ -1,6 +1,7 @@
 // capi.cpp -- the C ABI of include/mijpeg.h: decoder object (host entropy decoding + streaming upload +
-// GPU reconstruction + rectangle service) and the stateless batch launch.  Compiled with hipcc (host side
-// only uses the HIP runtime API).  There is NO CPU fallback for the reconstruction: without a device the
+// GPU reconstruction + rectangle service) and uniform batches.  The kernel selection and the launch are in
+// reconstruct_device.cpp, ragged batches in ragged_decode.cpp, the encoder direction in encode_device.cpp.  Compiled with
+// hipcc (host side only uses the HIP runtime API).  There is NO CPU fallback for the reconstruction: without a device the
 // reconstruct calls fail with MIJPEG_ERR_DEVICE.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -9,7 +10,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <new>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -20,10 +20,8 @@
 #include "../../include/mijpeg.h"
 #include "decoder.hpp"
 #include "huffman_dev.hpp"
-#include "encoder.hpp"
-#include "forward.hpp"
-#include "hencode.hpp"
 #include "kernels.hpp"
+#include "reconstruct.hpp"
 
 using namespace mij;
 
@@ -189,9 +187,29 @@ static int ensure_cached(mijpeg_decoder *d, bool pinned, void **ptr, size_t *cap
 
 int ensure_dev(mijpeg_decoder *d, void **ptr, size_t *cap, size_t bytes) { return ensure_cached(d, false, ptr, cap, bytes); }
 
+// The coefficient store for `count` int16: the device mirror and, where need_host, the (pinned) host planes
+int ensure_coef_store(mijpeg_decoder *d, size_t count, bool need_host)
+{
+  if (d->device < 0) {
+    if (need_host && d->coef_host_cap < count) {
+      free(d->coef_host);
+      d->coef_host = (int16_t *)malloc(count * sizeof(int16_t));
+      if (!d->coef_host) return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the coefficient store");
+      d->coef_host_cap = count;
+    }
+    return MIJPEG_OK;
+  }
+  size_t host = d->coef_host_cap * sizeof(int16_t), dev = d->coef_dev_cap * sizeof(int16_t); // (the caps count int16)
+  int rc = need_host ? ensure_cached(d, true, (void **)&d->coef_host, &host, count * sizeof(int16_t)) : MIJPEG_OK;
+  if (!rc) rc = ensure_cached(d, false, (void **)&d->coef_dev, &dev, count * sizeof(int16_t));
+  d->coef_host_cap = host / sizeof(int16_t);
+  d->coef_dev_cap = dev / sizeof(int16_t);
+  return rc;
+}
+
 // A batch that was submitted (mijpeg_submit_batch_device) and not waited for still reads the pinned staging buffers
 // (ent_host, stage_host, status words) from its asynchronous uploads: every entry point that rewrites them settles it first.
-static int settle_pending(mijpeg_decoder *d)
+int settle_pending(mijpeg_decoder *d)
 {
   if (!d->pend_n) return MIJPEG_OK;
   d->pend_n = 0;
@@ -312,25 +330,6 @@ try {
   if (info) *info = d->host.info;
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(d, "mijpeg_read_header"); }
-
-static int ensure_coef_store(mijpeg_decoder *d, size_t count, bool need_host = true)
-{
-  if (d->device < 0) {
-    if (need_host && d->coef_host_cap < count) {
-      free(d->coef_host);
-      d->coef_host = (int16_t *)malloc(count * sizeof(int16_t));
-      if (!d->coef_host) return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the coefficient store");
-      d->coef_host_cap = count;
-    }
-    return MIJPEG_OK;
-  }
-  size_t host = d->coef_host_cap * sizeof(int16_t), dev = d->coef_dev_cap * sizeof(int16_t); // (the caps count int16)
-  int rc = need_host ? ensure_cached(d, true, (void **)&d->coef_host, &host, count * sizeof(int16_t)) : MIJPEG_OK;
-  if (!rc) rc = ensure_cached(d, false, (void **)&d->coef_dev, &dev, count * sizeof(int16_t));
-  d->coef_host_cap = host / sizeof(int16_t);
-  d->coef_dev_cap = dev / sizeof(int16_t);
-  return rc;
-}
 
 // The alpha channel of a JPEG XT file: the reference turns to the ALFA box behind the legacy codestream's EOI (and the residual
 // codestream), inside JPEG::Read (Image::ParseTrailer, codestream/image.cpp:1430-1460): what is wrong with it fails the read,
@@ -689,19 +688,6 @@ try {
 // Aggregation over the images of a decoded batch: what one reconstruction launch for all of them needs to know.
 static int finish_batch(mijpeg_decoder *d);
 
-// The range gates of the kernel selection (plan_reconstruct): a kernel or flavour is admitted where mijpeg_info::range_max
-// (sum |c| q of a block) is below its gate
-constexpr int32_t GATE_DOT2 = 1477;          // fused420p_kernel's second pass on v_dot2 (idct_columns_dot2: sum |c| q <= 1476)
-constexpr int32_t GATE_PACKED = 2047;        // chroma filtered as int16 pairs (packed 4:2:0, 4:2:2, 4:4:0)
-constexpr int32_t GATE_INT16_SAMPLES = 7600; // int16 sample planes of the kernel pair; int16 luma of fusedxtw420_kernel<true>
-constexpr int32_t GATE_FUSED8 = 8190;        // chroma of the 8-bit fused 4:2:2 / 4:4:0 / 4:1:1 / 4:4:4 kernels, fused1_kernel
-constexpr int32_t GATE_XT_LEGACY = 16384;    // legacy frame of the JPEG XT kernels (fused, and the merge's 32-bit colour stage)
-constexpr int32_t GATE_12_CHROMA = 45056;    // 12-bit fused kernels: chroma (every component of fused_tile_kernel's fast12)
-constexpr int32_t GATE_12_LUMA = 49152;      // 12-bit fused kernels: luma
-constexpr int32_t GATE_XT_RESIDUAL = 65536;  // residual frame of the fused JPEG XT kernels
-constexpr int32_t RANGE_GATES[] = { // (ascending)
-    GATE_DOT2, GATE_PACKED, GATE_INT16_SAMPLES, GATE_FUSED8, GATE_XT_LEGACY, GATE_12_CHROMA, GATE_12_LUMA, GATE_XT_RESIDUAL};
-
 // What the last finished batch of shared tables reported, for the speculative launch of the next one (MIJPEG_FLAG_SPECULATIVE):
 // frame geometry, tables, and the range check that selected its kernel.  Process-wide: the decoder objects of a pipeline work
 // on chunks of the same material.
@@ -736,7 +722,6 @@ bool same_shape_and_tables(const mijpeg_info &a, const mijpeg_info &b)
   return true;
 }
 } // namespace
-static int settle_speculation(mijpeg_decoder *d);
 
 static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, bool defer)
 {
@@ -897,7 +882,7 @@ static int finish_batch(mijpeg_decoder *d)
 
 // A speculative launch is validated: the batch is finished the ordinary way (wait, errors, range check), and where the range
 // check is not the one the launch assumed the reconstruction runs again with the kernel the real one selects.
-static int settle_speculation(mijpeg_decoder *d)
+extern "C++" int settle_speculation(mijpeg_decoder *d) // (C++ linkage as decoder.hpp declares it: ragged_decode.cpp calls it too)
 {
   if (!d->spec_active) return MIJPEG_OK;
   d->spec_active = false;
@@ -1022,27 +1007,10 @@ try {
     if (rc) return rc;
   }
   if (d->batch_frames < 1 && !speculate) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded batch: call mijpeg_decode_batch_device first");
-  mijpeg_batch b;
-  memset(&b, 0, sizeof(b));
-  b.info = speculate ? assumed : d->batch_info;
-  b.coef_dev = d->coef_dev;
-  b.coef_frame_stride = b.info.coef_count;
-  b.out_dev = (uint8_t *)dst_device;
-  b.out_row_stride = row_stride;
-  b.out_frame_stride = frame_stride;
-  b.frames = speculate ? -d->batch_frames : d->batch_frames;
+  mijpeg_batch b = batch_of(speculate ? assumed : d->batch_info, d->coef_dev, dst_device, row_stride, frame_stride, speculate ? -d->batch_frames : d->batch_frames,
+                            flags & ~(MIJPEG_FLAG_DEVICE_OUTPUT | MIJPEG_FLAG_NO_UPSAMPLING | MIJPEG_FLAG_SPECULATIVE));
   b.quant_dev = d->batch_own_tables ? d->batch_quant_dev : nullptr;
-  b.flags = flags & ~(MIJPEG_FLAG_DEVICE_OUTPUT | MIJPEG_FLAG_NO_UPSAMPLING | MIJPEG_FLAG_SPECULATIVE);
-  const size_t ws = mijpeg_workspace_bytes(&b);
-  if (ws) {
-    const int rc = ensure_dev(d, (void **)&d->ws_dev, &d->ws_cap, ws);
-    if (rc) return rc;
-    b.workspace = d->ws_dev;
-    b.workspace_bytes = d->ws_cap;
-  }
-  const int rc = mijpeg_launch_reconstruct(&b, d->stream);
-  if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError())
-                                                           : std::string("reconstruction not available for this batch"));
+  if (const int rc = reconstruct_on(d, b, nullptr, "batch")) return rc;
   if (speculate) {
     d->spec_active = true;
     d->spec_redone = false;
@@ -1110,1210 +1078,6 @@ try {
 } catch (...) { return boundary_catch(d, "mijpeg_last_timing"); }
 
 // ------------------------------------------------------------------------------------------------
-// stateless batch launch
-// ------------------------------------------------------------------------------------------------
-static Sampling sampling_of(const mijpeg_info &f)
-{
-  if (f.components == 1) return Sampling::GREY;
-  if (f.components != 3 || f.hsamp[1] != 1 || f.vsamp[1] != 1 || f.hsamp[2] != 1 || f.vsamp[2] != 1) return Sampling::OTHER;
-  const int h = f.hsamp[0], v = f.vsamp[0];
-  return h == 2 && v == 2 ? Sampling::S420 : h == 2 && v == 1 ? Sampling::S422 : h == 1 && v == 2 ? Sampling::S440
-         : h == 4 && v == 1 ? Sampling::S411 : h == 1 && v == 1 ? Sampling::S444 : Sampling::OTHER;
-}
-
-// The fused kernels address inside a frame with 32-bit byte offsets (planes and pixels; frames are 64 bits apart): frames
-// beyond that -- a 65535 x 65535 picture has 8.6 GB of luma coefficients and 12.9 GB of pixels -- take the generic kernels,
-// whose addressing is 64 bits wide throughout.
-// DNL frames (mijpeg_info::dnl): the vertical filter of a subsampled component reads the line below the picture's last one,
-// and when the picture ends on a block row boundary that line belongs to the block row the first scan creates behind the
-// picture -- unless it met the marker before it got there.  Then the row does not exist, the reference reads NULL and
-// transforms it to samples of value 0 (control/blockbitmaprequester.cpp:1097-1108, dct/idct.cpp:336-338): no coefficients
-// give that, the unfused kernels write the zeros themselves (GenericArgs::zero_from).
-static bool dnl_row_missing(const mijpeg_info &f)
-{
-  if (!f.dnl) return false;
-  for (int c = 0; c < f.components && c < MIJPEG_MAX_COMPONENTS; c++) {
-    const int ch = (f.height + f.suby[c] - 1) / f.suby[c];
-    if (f.suby[c] > 1 && (ch & 7) == 0 && f.rows[c] <= (ch >> 3)) return true;
-  }
-  return false;
-}
-
-static bool fits32(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  const uint64_t lim = 0xffffffffull;
-  if (f.coef_wide) return false; // int32 coefficients (damaged stream): the unfused kernels' business
-  if (dnl_row_missing(f)) return false; // (the fused kernels have no way to say "this block row is NULL")
-  for (int c = 0; c < f.components; c++)
-    if ((uint64_t)f.blocks_w[c] * (uint64_t)f.blocks_h[c] * 128u > lim) return false;
-  if (f.xt && b->xt)
-    for (int c = 0; c < b->xt->residual.components; c++)
-      if ((uint64_t)b->xt->residual.blocks_w[c] * (uint64_t)b->xt->residual.blocks_h[c] * 128u > lim) return false;
-  if (b->out_row_stride < 0) return false; // bottom-up bitmaps: the offsets are unsigned
-  // (a batch description without strides -- mijpeg_kernel_name, mijpeg_workspace_bytes asked ahead of time -- is taken to
-  // have tightly packed lines)
-  const uint64_t line = (uint64_t)f.width * (uint64_t)f.components * (f.xt ? (uint64_t)(f.sample_bytes > 1 ? 2 : 1) : f.precision > 8 ? 2u : 1u);
-  const uint64_t rs = b->out_row_stride ? (uint64_t)b->out_row_stride : line;
-  return (uint64_t)f.height * rs + line <= lim;
-}
-
-// every delta << 4 a signed 16-bit operand (the fast transforms)
-static bool deltas_fit16(const mijpeg_info &f)
-{
-  if (f.components > MIJPEG_MAX_COMPONENTS) return false;
-  for (int c = 0; c < f.components; c++) {
-    if ((unsigned)f.quant_index[c] >= 4) return false;
-    for (int i = 0; i < 64; i++)
-      if (f.quant[f.quant_index[c]][i] > 2047) return false;
-  }
-  return true;
-}
-
-// The 12-bit kernels' colour stage in one 32-bit sum per channel (colour12<true>, kernels.hip): the luma sample times 16 is at most
-// 4.02 * range_max[0] + 2 in magnitude, a chroma sample behind the upsampling filters 4.02 * range_max[c] + 4 (the bounds of
-// the 12-bit gate of plan_reconstruct; the filters are convex combinations plus a rounding), so (|y'| + 32776) * 8192 + 14516 |c| --
-// 14516 is the largest weight a channel puts on chroma, 2819 + 5850 the green one's -- stays below 2^31 where this holds.  Monotone
-// in every range: a speculative launch that assumed larger ranges and selected the flavour holds for the smaller ones.
-static bool narrow12_colour(const mijpeg_info &f)
-{
-  if (f.precision != 12 || f.components != 3) return false;
-  const int64_t ry = f.range_max[0], rc = std::max(f.range_max[1], f.range_max[2]);
-  if (ry <= 0 || rc < 0) return false;
-  const int64_t sum = ((402 * ry + 99) / 100 + 2 + 32776) * 8192 + 14516 * ((402 * rc + 99) / 100 + 4);
-  return sum < ((int64_t)1 << 31);
-}
-
-// JPEG XT: the L transformation in force for this launch.  A request without colour transformation (the command line's -c)
-// replaces the STANDARD YCbCr transformation by the identity and leaves everything else of the merge alone
-// (colortrafo/colortransformerfactory.cpp:231-232: `if (ltrafo == YCbCr && disabletorgb) ltrafo = Identity`)
-static bool xt_ltrafo_ycbcr(const mijpeg_batch *b)
-{
-  const mijpeg_xt_params &x = *b->xt;
-  return x.ltrafo_ycbcr && !((b->flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM) && x.ltrafo_standard);
-}
-
-// JPEG XT profile C in the shape the fused kernels cover (the legacy frame's part is plan_reconstruct's): 12-bit 4:4:4
-// residual frame of the legacy frame's size, L transformation on, the residual frame within the range the fast transforms
-// are exact for
-static bool fused_xt_shape(const mijpeg_batch *b)
-{
-  const mijpeg_xt_params &x = *b->xt;
-  const mijpeg_info &r = x.residual;
-  if (x.general) return false; // free-form matrices, table gathers, DCT bypass: xt_merge_general_kernel
-  if (x.no_residual) return false; // (a legacy codestream without its EOI: the unfused merge kernels know how to merge nothing)
-  // hidden bits in the RESIDUAL frame (-rR n: 13..16-bit samples, int32 coefficients) have a kernel of their own
-  // (fusedxtw420_kernel); hidden bits in the legacy frame change its precision and stay on the three-kernel path
-  if (x.hidden_bits || x.residual_hidden_bits < 0 || x.residual_hidden_bits > 4 || (x.residual_wide != 0) != (x.residual_hidden_bits > 0) ||
-      x.ltable_entries != 256 || !xt_ltrafo_ycbcr(b) || r.precision != 12 || r.components != 3 || x.out_max != 65535 || x.out_shift != 32768)
-    return false;
-  for (int c = 0; c < 3; c++)
-    if (r.subx[c] != 1 || r.suby[c] != 1 || r.blocks_w[c] != r.blocks_w[0] || r.blocks_h[c] != r.blocks_h[0] || r.range_max[c] >= GATE_XT_RESIDUAL)
-      return false;
-  return deltas_fit16(r) && r.width == b->info.width && r.height == b->info.height;
-}
-
-// Which kernel reconstructs a batch, and in which flavour: the one place that decides it (mijpeg_kernel_name,
-// mijpeg_workspace_bytes and launch_reconstruct_ex each ask once).  Safe on any batch description, a JPEG XT frame without
-// its parameter block and a batch without strides included.  (A rectangle request needs MIJPEG_FLAG_FORCE_GENERIC, which
-// alone rules out the fused, flat and tile kernels.)
-static ReconPlan plan_reconstruct(const mijpeg_batch *b)
-{
-  const mijpeg_info &f = b->info;
-  const int32_t *r = f.range_max;
-  const bool generic = b->flags & MIJPEG_FLAG_FORCE_GENERIC, safe = b->flags & MIJPEG_FLAG_FORCE_SAFE;
-  const bool ycc = f.ycbcr && !(b->flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM); // (the fused three-component kernels transform colour)
-  const bool deltas16 = deltas_fit16(f); // (false for more components than a frame can have)
-  const auto chroma_below = [&](int32_t gate) { return r[1] < gate && r[2] < gate; };
-  ReconPlan p{};
-  p.sampling = sampling_of(f);
-  p.fast = f.fast_arith && !safe && !f.coef_wide && deltas16;
-  const auto plan = [&](Recon k) { p.kernel = k; return p; };
-  if (f.xt) {
-    // (fast_arith itself is never set for XT frames: the generic kernels run SAFE on them; the fused ones check the range here)
-    if (b->xt && p.sampling == Sampling::S420 && f.precision == 8 && !generic && !safe && deltas16 && r[0] < GATE_XT_LEGACY &&
-        chroma_below(GATE_XT_LEGACY) && fits32(b) && fused_xt_shape(b))
-      return plan(b->xt->residual_hidden_bits ? Recon::FUSEDXTW420 : Recon::FUSEDXT420);
-    if (f.coef_wide) return plan(Recon::PAIR_LONG);
-    if (f.components == 1) return plan(Recon::XT_MERGE1);
-    return plan(b->xt && b->xt->general ? Recon::XT_MERGE_GENERAL : Recon::XT_MERGE);
-  }
-  if (f.coef_wide) return plan(Recon::PAIR_LONG); // int32 coefficients (damaged stream)
-  const bool fits = f.components >= 1 && f.components <= MIJPEG_MAX_COMPONENTS && fits32(b); // (no missing DNL row either)
-  if (fits && !generic && f.precision == 8) {
-    // single components: samples travel as packed int16
-    if (p.sampling == Sampling::GREY && p.fast && r[0] < GATE_FUSED8) return plan(Recon::FUSED1);
-    // 4:2:0 in any range; the packed flavour filters (Cb, Cr) pairs in 16 bits: every chroma sample * 16 is bounded by
-    // 4 * range_max, and the filter sums a + 3 b + r by four times that.  Where the first-pass results of every transform fit
-    // 16 bits its second pass runs on v_dot2 as well (MIJPEG_FLAG_FORCE_DOT2, for testing: whatever the range check says).
-    if (p.sampling == Sampling::S420 && ycc) {
-      if (!p.fast || !chroma_below(GATE_PACKED)) return plan(Recon::FUSED420);
-      p.dot2 = !b->quant_dev && ((b->flags & MIJPEG_FLAG_FORCE_DOT2) || (r[0] < GATE_DOT2 && chroma_below(GATE_DOT2)));
-      return plan(Recon::FUSED420P);
-    }
-    // 4:2:2, 4:4:0 (what a losslessly rotated 4:2:2 picture is), 4:1:1, 4:4:4: chroma samples travel through LDS as int16 pairs
-    // (4 * range_max < 32768); 4:2:2 and 4:4:0 filter on the pairs below the packed gate, on 32-bit values between the two
-    if (p.sampling != Sampling::GREY && p.sampling != Sampling::OTHER && ycc && p.fast && chroma_below(GATE_FUSED8)) {
-      const Sampling s = p.sampling;
-      p.wide = (s == Sampling::S422 || s == Sampling::S440) && !chroma_below(GATE_PACKED);
-      return plan(s == Sampling::S422 ? Recon::FUSED422 : s == Sampling::S440 ? Recon::FUSED440 : s == Sampling::S411 ? Recon::FUSED411 : Recon::FUSED444);
-    }
-  }
-  // 12 bit (SOF1, P = 12): 4:2:0, 4:2:2, 4:4:4 and single components inside the ranges the 12-bit flavours are exact for: every
-  // delta << 4 a signed 16-bit operand; sum |c| q < 49152 bounds every butterfly intermediate by 1573 * 16 * 49152 < 2^31 (first
-  // pass; the second pass sees at most 22.2 * range_max per column) and every multiplicand by 2^23; chroma sum |c| q < 45056 bounds
-  // the chroma samples (times 16) by 4.02 * 45056 + 2 < 181 200 (|basis| <= 1/4 per coefficient, the 9-bit constants and the
-  // roundings add < 0.5 %), whose products with the colour constants (11485; 2819 + 5850; 14516 taken as 4 * 3629) fit 32 bits.
-  // (The horizontal filter of 4:2:2 weighs samples below 2^18 with 4 in total.)
-  if (fits && !generic && f.precision == 12 && !safe && deltas16 && r[0] > 0 && r[0] < GATE_12_LUMA) {
-    if (p.sampling == Sampling::GREY) return plan(Recon::FUSED1_12);
-    const Sampling s = p.sampling;
-    if ((s == Sampling::S420 || s == Sampling::S422 || s == Sampling::S444) && ycc && chroma_below(GATE_12_CHROMA)) {
-      p.narrow12 = narrow12_colour(f);
-      return plan(s == Sampling::S420 ? Recon::FUSED420_12 : s == Sampling::S422 ? Recon::FUSED422_12 : Recon::FUSED444_12);
-    }
-  }
-  // every component 1 x 1, three or four of them, 8 bit, no colour transformation, fast arithmetic: fused_flat_kernel
-  // (CMYK; RGB stored as such -- Adobe transform 0, a merging specification with the identity L transformation, the caller's
-  // MIJPEG_FLAG_NO_COLOR_TRANSFORM on a 4:4:4 frame)
-  bool flat = f.precision == 8 && !b->quant_dev && !generic && (f.components == 4 || (f.components == 3 && !ycc)) && p.fast && fits;
-  for (int c = 0; c < f.components && flat; c++)
-    flat = f.subx[c] == 1 && f.suby[c] == 1 && f.blocks_w[c] == f.blocks_w[0] && f.blocks_h[c] == f.blocks_h[0];
-  if (flat) return plan(Recon::FLAT);
-  // plain JPEG frames of any layout go through LDS in one pass (fused_tile_kernel); the pair with its sample planes in HBM
-  // stays for per-frame tables in device memory, MIJPEG_FLAG_FORCE_GENERIC (rectangle requests) and missing DNL rows
-  if (b->quant_dev || generic || dnl_row_missing(f)) return plan(Recon::PAIR);
-  // 12-bit frames of the tile kernel: the bounds of the 12-bit gate above, the chroma one for every component (the upsampling
-  // filters weigh two samples, < 2^18 each with the level shift, with at most 8 in total: far inside the fast flavour's 24-bit
-  // operands and 32-bit sums)
-  p.fast12 = f.precision == 12 && !safe && deltas16 && r[0] > 0;
-  for (int c = 0; c < f.components && p.fast12; c++) p.fast12 = r[c] < GATE_12_CHROMA;
-  return plan(Recon::TILE);
-}
-
-// per Recon: the name, and that of the flavour (ReconPlan::wide, ReconPlan::narrow12) where the kernel has one
-static const char *const RECON_NAMES[][2] = {
-    {"fused420p_kernel", nullptr},
-    {"fused420_kernel", nullptr},
-    {"fused422_kernel", "fused422_kernel<wide>"},
-    {"fused440_kernel", "fused440_kernel<wide>"},
-    {"fused411_kernel", nullptr},
-    {"fused444_kernel", nullptr},
-    {"fused1_kernel", nullptr},
-    {"fused420_kernel<12>", "fused420_kernel<12>/narrow"},
-    {"fused422_12_kernel", "fused422_12_kernel/narrow"},
-    {"fused444_12_kernel", "fused444_12_kernel/narrow"},
-    {"fused1_kernel<12>", nullptr},
-    {"fusedxt420_kernel", nullptr},
-    {"fusedxtw420_kernel", nullptr},
-    {"fused_flat_kernel", nullptr},
-    {"fused_tile_kernel", nullptr},
-    {"idct_planes_kernel+upsample_color_kernel", nullptr},
-    {"idct_planes_long_kernel+upsample_color_kernel", nullptr},
-    {"idct_planes_kernel+xt_merge_kernel", nullptr},
-    {"idct_planes_kernel+xt_merge_general_kernel", nullptr},
-    {"idct_planes_kernel+xt_merge1_kernel", nullptr},
-};
-static_assert(sizeof(RECON_NAMES) / sizeof(RECON_NAMES[0]) == (size_t)Recon::XT_MERGE1 + 1, "one name per kernel");
-
-const char *mijpeg_kernel_name(const mijpeg_batch *b)
-try {
-  if (!b) return "";
-  const ReconPlan p = plan_reconstruct(b);
-  return RECON_NAMES[(int)p.kernel][p.wide || p.narrow12 ? 1 : 0];
-} catch (...) { (void)boundary_catch(nullptr, "mijpeg_kernel_name"); return nullptr; }
-
-static const size_t LUT_BYTES = 3 * 4096 * sizeof(int32_t);
-
-// JPEG XT with real Q / R2 tables (mijpeg_xt_params.general): they travel in the workspace behind everything else
-static size_t xt_table_bytes(const mijpeg_batch *b)
-{
-  if (!b->info.xt || !b->xt || !b->xt->general) return 0;
-  size_t n = 0;
-  for (int c = 0; c < 3; c++) {
-    if (b->xt->qtable[c]) n += (size_t)b->xt->qtable_entries * sizeof(int32_t);
-    if (b->xt->r2table[c]) n += ((size_t)(b->xt->out_max + 1) << 4) * sizeof(int32_t);
-  }
-  return n;
-}
-
-// per-frame tables (quant_dev) are expanded to the transforms' operands (deltas << 4, int32) in the workspace
-static size_t expanded_tables_bytes(const mijpeg_batch *b) { return b->quant_dev ? (size_t)b->frames * 4 * 64 * sizeof(int32_t) : 0; }
-
-static bool is_fused_xt(Recon k) { return k == Recon::FUSEDXT420 || k == Recon::FUSEDXTW420; }
-
-static size_t workspace_need(const mijpeg_batch *b, const ReconPlan &p)
-{
-  if (is_fused_xt(p.kernel)) return LUT_BYTES;
-  if (p.kernel < Recon::FUSEDXT420) return expanded_tables_bytes(b);
-  // [LUT_BYTES: L lookup tables (JPEG XT, up to 3 x 4096 entries)] [per frame: int32 sample planes, one sample per
-  // coefficient: coef_count of them, fewer when the residual planes hold 32-bit coefficients] [expanded per-frame tables]
-  // [JPEG XT tables]
-  return LUT_BYTES + (size_t)b->info.coef_count * sizeof(int32_t) * (size_t)b->frames + expanded_tables_bytes(b) + xt_table_bytes(b);
-}
-
-size_t mijpeg_workspace_bytes(const mijpeg_batch *b)
-try {
-  return b ? workspace_need(b, plan_reconstruct(b)) : 0;
-} catch (...) { (void)boundary_catch(nullptr, "mijpeg_workspace_bytes"); return 0; }
-
-// What a rectangle request that does not show the plain picture adds to a launch (request_model.hpp; GenericArgs::rowmap ...)
-struct RequestExtra {
-  const int32_t *rowmap_dev;
-  int32_t rowmap_stride;
-  int32_t corner_x, corner_y, y_base, y_count;
-  int32_t wstart[MAXP], wlimit[MAXP]; // per plane (JPEG XT: legacy planes, then residual planes)
-  int32_t ycc;
-};
-static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const RequestExtra *rx);
-
-int mijpeg_launch_reconstruct(const mijpeg_batch *b, void *stream)
-try {
-  return launch_reconstruct_ex(b, stream, nullptr);
-} catch (...) { return boundary_catch(nullptr, "mijpeg_launch_reconstruct"); }
-
-static int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const RequestExtra *rx)
-{
-  if (!b || !b->coef_dev || !b->out_dev || b->frames < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (rx && !(b->flags & MIJPEG_FLAG_FORCE_GENERIC)) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (b->quant_dev && b->info.xt) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED; // per-frame tables: plain JPEG only
-  const mijpeg_info &f = b->info;
-  if ((f.precision != 8 && f.precision != 12) || f.components < 1 || f.components > 4) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED;
-  if (f.xt && (!b->xt || (f.components != 3 && f.components != 1))) return MIJPEG_ERR_MISSING_PARAMETER; // (one component: grey scale with a residual)
-  if (f.coef_wide && (f.xt || b->quant_dev)) return MIJPEG_ERR_INVALID_PARAMETER; // int32 planes: single plain JPEG frames only
-  const ReconPlan p = plan_reconstruct(b);
-  const size_t need = workspace_need(b, p);
-  if (need && (!b->workspace || b->workspace_bytes < need)) return MIJPEG_ERR_MISSING_PARAMETER;
-  hipStream_t s = (hipStream_t)stream;
-  int rc;
-  const int32_t *qdev = nullptr;
-  if (b->quant_dev) {
-    int32_t *dst = (int32_t *)((char *)b->workspace + (need - expanded_tables_bytes(b) - xt_table_bytes(b)));
-    if (launch_expand_deltas(b->quant_dev, dst, b->frames, s)) return MIJPEG_ERR_DEVICE;
-    qdev = dst;
-  }
-  if (p.kernel <= Recon::FUSEDXTW420) {
-    FusedXtArgs xa;
-    memset(&xa, 0, sizeof(xa));
-    Fused420Args &a = xa.base;
-    a.coef = b->coef_dev;
-    a.coef_frame_stride = b->coef_frame_stride;
-    a.off_y = f.coef_offset[0];
-    a.off_cb = f.coef_offset[1];
-    a.off_cr = f.coef_offset[2];
-    a.out = b->out_dev;
-    a.out_frame_stride = b->out_frame_stride;
-    a.row_stride = b->out_row_stride;
-    a.width = f.width;
-    a.height = f.height;
-    a.bw_y = f.blocks_w[0];
-    a.bh_y = f.blocks_h[0];
-    a.bw_c = f.blocks_w[1];
-    a.bh_c = f.blocks_h[1];
-    const bool full_height = p.sampling == Sampling::S422 || p.sampling == Sampling::S411; // (chroma subsampled horizontally only)
-    a.cw = p.sampling == Sampling::S440 ? f.width : p.sampling == Sampling::S411 ? (f.width + 3) / 4 : (f.width + 1) / 2;
-    a.ch = full_height ? f.height : (f.height + 1) / 2;
-    // DNL frames: the reference's upsamplers never learnt the height (upsampling/upsamplerbase.cpp:61-75), their line buffers
-    // have no bottom edge: below the last chroma line comes what the block rows hold (the padding of the last one, then the
-    // MCU row the first scan created behind the picture: the store has it, include/mijpeg.h) instead of that line again
-    if (f.dnl && !full_height && f.components > 1) a.ch = a.bh_c * 8;
-    a.tiles_x = (f.width + 127) / 128;
-    a.tiles_y = (f.height + 127) / 128;
-    a.frames = b->frames;
-    for (int c = 0; c < 3; c++)
-      fill_deltas(a.q[c], f.quant[f.quant_index[c]]);
-    a.qdev = qdev;
-    if (is_fused_xt(p.kernel)) {
-      const mijpeg_xt_params &x = *b->xt;
-      const mijpeg_info &r = x.residual;
-      for (int c = 0; c < 3; c++) {
-        xa.ext.off_r[c] = r.coef_offset[c];
-        for (int i = 0; i < 64; i++) xa.ext.rq[c][i] = (int32_t)r.quant[r.quant_index[c]][i] << 4;
-        if (hipMemcpyAsync((int32_t *)b->workspace + (size_t)c * 256, x.ltable[c], 256 * sizeof(int32_t), hipMemcpyHostToDevice, s) != hipSuccess)
-          return MIJPEG_ERR_DEVICE;
-      }
-      xa.ext.bw_r = r.blocks_w[0];
-      xa.ext.bh_r = r.blocks_h[0];
-      xa.ext.ltable = (const int32_t *)b->workspace;
-      xa.ext.rtrafo_ycbcr = x.rtrafo_ycbcr;
-      xa.ext.is_float = x.is_float;
-      xa.ext.out_max = x.out_max;
-      xa.ext.out_shift = x.out_shift;
-      xa.ext.rprecision = r.precision + x.residual_hidden_bits;
-      // (the two-wave flavour of the hidden-bit kernel keeps the luma block as int16: sample * 16 + 2056 with |sample * 16| <= 4 sum |c| q)
-      xa.luma_fits16 = f.range_max[0] < GATE_INT16_SAMPLES ? 1 : 0;
-    }
-    rc = launch_fused(p, xa, s);
-  } else {
-    GenericArgs a;
-    memset(&a, 0, sizeof(a));
-    a.coef = b->coef_dev;
-    a.coef_frame_stride = b->coef_frame_stride;
-    a.samples = (int32_t *)((char *)b->workspace + LUT_BYTES);
-    a.sample_frame_stride = f.coef_count;
-    a.out = b->out_dev;
-    a.out_frame_stride = b->out_frame_stride;
-    a.row_stride = b->out_row_stride;
-    a.width = f.width;
-    a.height = f.height;
-    a.ncomp = f.components;
-    a.ycbcr = (f.ycbcr && !(b->flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM)) ? 1 : 0;
-    a.frames = b->frames;
-    a.qdev = qdev;
-    a.nplanes = f.components;
-    a.sample_bytes = f.xt ? (b->xt->out_max > 255 ? 2 : 1) : f.precision > 8 ? 2 : 1;
-    a.maxval = (1 << f.precision) - 1;
-    a.dcshift = (1 << (f.precision - 1)) << 4;
-    int64_t sample_off = 0;
-    auto plane = [&](int p, const mijpeg_info &g, int c, int precision) {
-      a.coef_off[p] = g.coef_offset[c];
-      a.sample_off[p] = sample_off;
-      sample_off += (int64_t)g.blocks_w[c] * g.blocks_h[c] * 64;
-      a.bw[p] = g.blocks_w[c];
-      a.bh[p] = g.blocks_h[c];
-      a.subx[p] = g.subx[c];
-      a.suby[p] = g.suby[c];
-      a.cw[p] = (g.width + g.subx[c] - 1) / g.subx[c];
-      a.ch[p] = (g.height + g.suby[c] - 1) / g.suby[c];
-      if (g.dnl && g.suby[c] > 1) { // no bottom edge, see above; rows nobody created are NULL: zeros
-        if ((a.ch[p] & 7) == 0 && g.rows[c] <= (a.ch[p] >> 3)) a.zero_from[p] = g.rows[c];
-        a.ch[p] = g.blocks_h[c] * 8;
-      }
-      a.dcoff[p] = (1 << (precision - 1)) << 7;
-      fill_deltas(a.q[p], g.quant[g.quant_index[c]]);
-    };
-    // JPEG XT frames reconstruct at their precision plus the bits that travelled in hidden refinement scans
-    // (Frame::HiddenPrecisionOf, marker/frame.cpp:368-373)
-    const int lprec = f.precision + (f.xt ? b->xt->hidden_bits : 0);
-    for (int c = 0; c < f.components; c++) plane(c, f, c, lprec);
-    if (f.coef_wide) { a.wide_first = 0; a.wide_count = f.components; a.wide_long = 1; }
-    // int16 sample planes between the two kernels: |sample * 16| <= 2048 (level shift) + 4 * range_max must fit 16 bits
-    a.narrow = p.fast && !f.xt && f.precision == 8;
-    for (int c = 0; c < f.components && a.narrow; c++)
-      if (f.range_max[c] >= GATE_INT16_SAMPLES) a.narrow = 0;
-    a.maxval = (1 << lprec) - 1;
-    a.dcshift = (1 << (lprec - 1)) << 4;
-    if (f.xt) {
-      const mijpeg_xt_params &x = *b->xt;
-      const int rprec = x.residual.precision + x.residual_hidden_bits;
-      // (a parameter block filled in before the lossless flavours existed has zeros there: with clamping that means four bits)
-      const int xrbits = (x.rbits == 0 && x.clamp) ? 4 : x.rbits;
-      if (x.hidden_bits < 0 || x.hidden_bits > 4 || x.residual_hidden_bits < 0 || x.residual_hidden_bits > 4 || rprec - (x.rct ? 1 : 0) > 16 ||
-          x.ltable_entries != (256 << x.hidden_bits) || (x.residual_wide != 0) != (x.residual_hidden_bits > 0 || x.residual.precision > 12) ||
-          (xrbits != 4 && !(x.general && x.rdct_bypass)) || (x.rct && (x.clamp || xrbits != 1)) || (!x.clamp && !x.general))
-        return MIJPEG_ERR_INVALID_PARAMETER;
-      // the flavours without clamping (RCT, lossless identity) index their Q tables directly: a caller-made block without them is refused
-      if ((x.rct || !x.clamp) && !x.no_residual)
-        for (int c = 0; c < x.residual.components && c < 3; c++)
-          if (!x.qtable[c]) return MIJPEG_ERR_INVALID_PARAMETER;
-      for (int c = 0; c < x.residual.components && c < 3; c++) plane(3 + c, x.residual, c, rprec); // (one component: planes 4, 5 stay empty)
-      if (!x.residual.components) // (no residual frame at all -- a specification without a residual codestream: the merge reads nothing there)
-        for (int pn = 3; pn < 6; pn++) a.subx[pn] = a.suby[pn] = 1;
-      // int32 planes: beyond 12 bits (hidden bits included) the reference transforms with IDCT<4,QUAD>, up to 12 with the LONG
-      // flavour like every other frame (codestream/tables.cpp:1876-1891) -- the same numbers until a damaged scan leaves a
-      // coefficient that overflows 32 bits on the way (an 8-bit alpha residual with one hidden bit and 52 241 in a block:
-      // tools/xt_gpu_damage_campaign.py, seed 2002)
-      if (x.residual_wide) { a.wide_first = 3; a.wide_count = 3; a.wide_long = rprec <= 12 ? 1 : 0; }
-      a.ltable_entries = x.ltable_entries;
-      a.nplanes = 6;
-      a.xt = 1;
-      a.ycbcr = xt_ltrafo_ycbcr(b) ? 1 : 0; // the L transformation of the merging specification, or the identity the -c switch puts in its place
-      a.rtrafo_ycbcr = x.rtrafo_ycbcr;
-      a.out_shift = x.out_shift;
-      a.out_max = x.out_max;
-      a.is_float = x.is_float;
-      a.rprecision = rprec;
-      a.xt_no_residual = x.no_residual;
-      a.xt_rct = x.rct;
-      a.xt_noclamp = x.clamp ? 0 : 1;
-      a.xt_rbits = x.residual.components ? xrbits : 4;
-      a.legacy32 = lprec == 8 && f.range_max[0] < GATE_XT_LEGACY && f.range_max[1] < GATE_XT_LEGACY && f.range_max[2] < GATE_XT_LEGACY &&
-                   !(b->flags & MIJPEG_FLAG_FORCE_SAFE);
-      a.ltable = (const int32_t *)b->workspace;
-      for (int c = 0; c < 3; c++)
-        if (hipMemcpyAsync((int32_t *)b->workspace + (size_t)c * x.ltable_entries, x.ltable[c], (size_t)x.ltable_entries * sizeof(int32_t),
-                           hipMemcpyHostToDevice, s) != hipSuccess)
-          return MIJPEG_ERR_DEVICE;
-      if (x.general) {
-        if (x.residual.components && x.qtable_entries != (1 << (rprec - (xrbits == 1) + xrbits))) return MIJPEG_ERR_INVALID_PARAMETER; // (no residual frame: no Q tables)
-        a.xt_general = 1;
-        a.rbypass = x.rdct_bypass;
-        a.rnoise = x.noise_shaping;
-        a.rdcshift = (1 << rprec) >> 1;
-        memcpy(a.lmat, x.lmat, sizeof(a.lmat));
-        memcpy(a.rmat, x.rmat, sizeof(a.rmat));
-        memcpy(a.cmat, x.cmat, sizeof(a.cmat));
-        char *tp = (char *)b->workspace + (need - xt_table_bytes(b));
-        for (int c = 0; c < 3; c++) {
-          // only the highest-frequency delta is used, with the colour bits folded in (residualblockhelper.cpp:351-364)
-          // (m_usQuantization is a UWORD: deltas >= 4096 wrap; shifted where the path has more than one fractional bit)
-          a.rquant63[c] = xrbits > 1 ? ((int32_t)x.residual.quant[x.residual.quant_index[c]][63] << xrbits) & 0xffff : (int32_t)x.residual.quant[x.residual.quant_index[c]][63];
-          // (components that share a table share its copy)
-          for (int j = 0; j < c; j++) {
-            if (x.qtable[c] && x.qtable[j] == x.qtable[c]) a.qlut[c] = a.qlut[j];
-            if (x.r2table[c] && x.r2table[j] == x.r2table[c]) a.r2lut[c] = a.r2lut[j];
-          }
-          if (x.qtable[c] && !a.qlut[c]) {
-            const size_t n = (size_t)x.qtable_entries * sizeof(int32_t);
-            if (hipMemcpyAsync(tp, x.qtable[c], n, hipMemcpyHostToDevice, s) != hipSuccess) return MIJPEG_ERR_DEVICE;
-            a.qlut[c] = (const int32_t *)tp;
-            tp += n;
-          }
-          if (x.r2table[c] && !a.r2lut[c]) {
-            const size_t n = ((size_t)(x.out_max + 1) << 4) * sizeof(int32_t);
-            if (hipMemcpyAsync(tp, x.r2table[c], n, hipMemcpyHostToDevice, s) != hipSuccess) return MIJPEG_ERR_DEVICE;
-            a.r2lut[c] = (const int32_t *)tp;
-            tp += n;
-          }
-        }
-      }
-    }
-    if (rx) {
-      a.rowmap = rx->rowmap_dev;
-      a.rowmap_stride = rx->rowmap_stride;
-      a.request = 1;
-      a.req_x0 = rx->corner_x;
-      a.req_y0 = rx->corner_y;
-      a.y_base = rx->y_base;
-      a.y_count = rx->y_count;
-      for (int c = 0; c < a.nplanes && c < MAXP; c++) {
-        a.wstart[c] = rx->wstart[c];
-        a.wlimit[c] = rx->wlimit[c];
-      }
-      if (!f.xt) a.ycbcr = rx->ycc; // the colour transformer the first request built (colortransformerfactory.cpp:220-221)
-    }
-    rc = p.kernel == Recon::FLAT ? launch_fused_flat(a, s) : p.kernel == Recon::TILE ? launch_fused_tile(a, p.fast || p.fast12, s) : -1;
-    if (rc == -1) rc = launch_generic(a, p.fast, s); // (also where no tile of fused_tile_kernel fits LDS)
-  }
-  return rc ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
-}
-
-
-// ------------------------------------------------------------------------------------------------
-// ragged batches: streams of any shapes in one device pass (include/mijpeg.h)
-// ------------------------------------------------------------------------------------------------
-// The layout group of a frame description, or -1: 8-bit plain sequential frames in the four layouts whose fused kernels have a
-// ragged flavour, every plane inside the kernels' 32-bit offsets
-static int ragged_group_of(const mijpeg_info &f)
-{
-  if (f.precision != 8 || f.xt || f.progressive || f.coef_wide || f.dnl || f.width < 1 || f.height < 1 || f.coef_count < 64) return -1;
-  if (f.components != 1 && f.components != 3) return -1;
-  for (int c = 0; c < f.components; c++)
-    if ((unsigned)f.quant_index[c] >= 4 || f.blocks_w[c] < 1 || f.blocks_h[c] < 1 || (uint64_t)f.blocks_w[c] * (uint64_t)f.blocks_h[c] * 128u > 0xffffffffull) return -1;
-  switch (sampling_of(f)) {
-  case Sampling::S420: return MIJPEG_RAGGED_420;
-  case Sampling::S422: return MIJPEG_RAGGED_422;
-  case Sampling::S444: return MIJPEG_RAGGED_444;
-  case Sampling::GREY: return f.hsamp[0] == 1 && f.vsamp[0] == 1 ? MIJPEG_RAGGED_GREY : -1; // (sampling factors on a single component: MCU padding nobody decodes)
-  default: return -1;
-  }
-}
-
-// Grouping, workgroup ranges and coefficient bases of n frames; excluded[i] != 0 (optional) keeps frame i out of the groups
-static int ragged_plan(const mijpeg_info *infos, int n, const char *excluded, int32_t *group, mijpeg_ragged_frame *frames, int32_t *group_workgroups, int64_t *coef_total)
-{
-  int64_t base = 0;
-  uint64_t grid[MIJPEG_RAGGED_GROUPS] = {0, 0, 0, 0};
-  for (int i = 0; i < n; i++) {
-    const mijpeg_info &f = infos[i];
-    mijpeg_ragged_frame &r = frames[i];
-    memset(&r, 0, sizeof(r));
-    int g = excluded && excluded[i] ? -1 : ragged_group_of(f);
-    const uint64_t tiles_x = g < 0 ? 0 : ((uint64_t)f.width + 127) / 128, tiles_y = g < 0 ? 0 : ((uint64_t)f.height + 127) / 128;
-    if (g >= 0 && grid[g] + tiles_x * tiles_y > 0x7fffffffull) g = -1; // (a grid holds 2^31 - 1 workgroups)
-    group[i] = g;
-    if (g < 0) continue;
-    r.coef_base = base;
-    base += f.coef_count;
-    r.off_y = f.coef_offset[0];
-    r.off_cb = f.components > 1 ? f.coef_offset[1] : 0;
-    r.off_cr = f.components > 1 ? f.coef_offset[2] : 0;
-    r.first_workgroup = (int32_t)grid[g];
-    r.tiles_x = (int32_t)tiles_x;
-    r.tiles_y = (int32_t)tiles_y;
-    grid[g] += tiles_x * tiles_y;
-    r.width = f.width;
-    r.height = f.height;
-    r.bw_y = f.blocks_w[0];
-    r.bh_y = f.blocks_h[0];
-    r.bw_c = f.components > 1 ? f.blocks_w[1] : 0;
-    r.bh_c = f.components > 1 ? f.blocks_h[1] : 0;
-    // valid chroma samples, as launch_reconstruct_ex has them for these layouts
-    r.cw = (f.width + 1) / 2;
-    r.ch = g == MIJPEG_RAGGED_422 ? f.height : (f.height + 1) / 2;
-  }
-  for (int g = 0; g < MIJPEG_RAGGED_GROUPS; g++) group_workgroups[g] = (int32_t)grid[g];
-  *coef_total = base;
-  return MIJPEG_OK;
-}
-
-int mijpeg_ragged_plan(const mijpeg_info *infos, int n, int32_t *group, mijpeg_ragged_frame *frames, int32_t group_workgroups[MIJPEG_RAGGED_GROUPS], int64_t *coef_total)
-try {
-  if (!infos || !group || !frames || !group_workgroups || !coef_total || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  return ragged_plan(infos, n, nullptr, group, frames, group_workgroups, coef_total);
-} catch (...) { return boundary_catch(nullptr, "mijpeg_ragged_plan"); }
-
-// Image i through the single-image route, on a decoder object of its own (kept from call to call)
-static void ragged_single_image(mijpeg_decoder *d, int i, int k, const uint8_t *data, size_t size, int min_intervals)
-{
-  mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-  r.group = -1;
-  r.child = nullptr;
-  if ((size_t)k >= d->ragged_children.size()) {
-    mijpeg_decoder *c = nullptr;
-    const int rc = mijpeg_create(&c, d->device);
-    if (rc) { r.status = rc; return; }
-    d->ragged_children.push_back(c);
-  }
-  mijpeg_decoder *c = d->ragged_children[(size_t)k];
-  r.child = c;
-  if (data) c->own_input.assign(data, data + size);
-  else c->own_input.clear();
-  int rc = mijpeg_set_input(c, data ? c->own_input.data() : nullptr, data ? size : 0);
-  if (!rc) {
-    rc = mijpeg_decode_coefficients_device(c, min_intervals);
-    if (rc == MIJPEG_ERR_NOT_AVAILABLE) rc = mijpeg_decode_coefficients(c, 0);
-  }
-  if (!rc) rc = mijpeg_get_info(c, &r.info);
-  r.status = rc;
-}
-
-int mijpeg_decode_ragged_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status)
-try {
-  if (!d || !streams || !sizes || !status || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
-  HIP_TRY(d, hipSetDevice(d->device));
-  if (d->spec_active) (void)settle_speculation(d); // (an unvalidated batch of the uniform calls is abandoned here)
-  if (const int prc = settle_pending(d)) return prc;
-  d->batch_frames = 0;
-  d->ragged_n = 0;
-  d->img_valid = d->model_valid = d->uploaded = d->decoded = false;
-  d->ragged_stats = mijpeg_ragged_stats{};
-  if (d->batch_hosts.size() < (size_t)n) d->batch_hosts.resize((size_t)n);
-  for (auto &h : d->batch_hosts)
-    if (!h) h.reset(new HostDecoder());
-  d->ragged.assign((size_t)n, mijpeg_decoder::RaggedImage{});
-  // headers and restart markers of all streams, one stream per worker
-  std::vector<int> rcs((size_t)n, 0);
-  const int workers = std::min(n, default_threads());
-  parallel_for(workers, [&](int w) {
-    for (int i = w; i < n; i += workers) rcs[(size_t)i] = streams[i] && sizes[i] ? d->batch_hosts[(size_t)i]->parse(streams[i], sizes[i], false) : MIJPEG_ERR_STREAM_EMPTY;
-  });
-  // what the batch kernels cover goes into the layout groups
-  std::vector<char> excluded((size_t)n, 0);
-  std::vector<mijpeg_info> infos((size_t)n);
-  for (int i = 0; i < n; i++) {
-    const char *why = rcs[(size_t)i] ? "the stream does not parse as the batch decoder reads it" : ragged_entropy_obstacle(*d->batch_hosts[(size_t)i], sizes[i]);
-    excluded[(size_t)i] = why != nullptr;
-    if (why) d->ragged[(size_t)i].why_single = why;
-    if (excluded[(size_t)i]) memset(&infos[(size_t)i], 0, sizeof(mijpeg_info));
-    else infos[(size_t)i] = d->batch_hosts[(size_t)i]->info;
-  }
-  std::vector<int32_t> group((size_t)n);
-  std::vector<mijpeg_ragged_frame> frames((size_t)n);
-  int32_t grids[MIJPEG_RAGGED_GROUPS];
-  int64_t coef_total = 0;
-  ragged_plan(infos.data(), n, excluded.data(), group.data(), frames.data(), grids, &coef_total);
-  for (int i = 0; i < n; i++)
-    if (group[(size_t)i] < 0 && !excluded[(size_t)i]) d->ragged[(size_t)i].why_single = "no layout group for this frame: 8-bit sequential 4:2:0, 4:2:2, 4:4:4 and grey frames have one";
-  if (coef_total > 0) {
-    const int rc = ensure_coef_store(d, (size_t)coef_total, false);
-    if (rc) return rc;
-  }
-  // one launch of the Huffman kernel per group (the walk in front of it where streams have no restart markers)
-  for (int g = 0; g < MIJPEG_RAGGED_GROUPS; g++) {
-    std::vector<int> members;
-    for (int i = 0; i < n; i++)
-      if (group[(size_t)i] == g) members.push_back(i);
-    if (members.empty()) continue;
-    const size_t m = members.size();
-    std::vector<HostDecoder *> hosts(m);
-    std::vector<const uint8_t *> datas(m);
-    std::vector<size_t> gsizes(m);
-    std::vector<int64_t> bases(m);
-    std::vector<int> verdict(m, 1);
-    for (size_t k = 0; k < m; k++) {
-      const int i = members[k];
-      hosts[k] = d->batch_hosts[(size_t)i].get();
-      datas[k] = streams[i];
-      gsizes[k] = sizes[i];
-      bases[k] = frames[(size_t)i].coef_base;
-    }
-    int scan_launches = 0, walk_launches = 0;
-    const RaggedEntropy re{bases.data(), verdict.data(), &scan_launches, &walk_launches};
-    const int rc = device_entropy_batch(d, hosts.data(), datas.data(), gsizes.data(), (int)m, 1, d->coef_dev, 0, false, false, &re);
-    d->ragged_stats.entropy_launches += scan_launches;
-    d->ragged_stats.walk_launches += walk_launches;
-    if (rc && rc != MIJPEG_ERR_NOT_AVAILABLE) return rc; // (the device, memory: not a verdict on a stream)
-    // What is left to refuse a whole group once every member passed ragged_entropy_obstacle: its device walk did not settle
-    // or has more subsequences than its prefix sums hold, the launch outgrew 32-bit offsets.  Every member then takes the
-    // single-image route, with the launch's message as the reason (mijpeg_ragged_route).
-    const std::string group_refusal = rc ? "the layout group's launch was refused: " + d->err_msg : std::string();
-    for (size_t k = 0; k < m; k++) {
-      const int i = members[k];
-      if (rc || verdict[k]) { // damaged: the single-image route decides
-        group[(size_t)i] = -1;
-        d->ragged[(size_t)i].why_single = rc ? group_refusal : std::string("the device decoder found the entropy coded data damaged");
-        continue;
-      }
-      mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-      r.group = g;
-      r.info = hosts[k]->info;
-      r.coef_base = frames[(size_t)i].coef_base;
-      d->ragged_stats.ragged++;
-    }
-  }
-  // everything else: the single-image route, stream by stream
-  int children = 0;
-  for (int i = 0; i < n; i++) {
-    if (group[(size_t)i] >= 0) continue;
-    ragged_single_image(d, i, children++, streams[i], sizes[i], min_intervals);
-    d->ragged_stats.fallbacks++;
-    if (d->ragged[(size_t)i].status) d->ragged_stats.errors++;
-  }
-  for (int i = 0; i < n; i++) status[i] = d->ragged[(size_t)i].status;
-  d->ragged_stats.images = n;
-  d->ragged_n = n;
-  d->err_code = 0;
-  d->err_msg.clear();
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_decode_ragged_device"); }
-
-int mijpeg_ragged_info(mijpeg_decoder *d, int i, mijpeg_info *info)
-try {
-  if (!d || !info || i < 0) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (i >= d->ragged_n) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no such image: call mijpeg_decode_ragged_device first");
-  const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-  if (r.status) {
-    const char *msg = nullptr;
-    if (r.child) (void)mijpeg_last_error(r.child, &msg);
-    return set_error(d, r.status, msg ? msg : "the stream could not be decoded");
-  }
-  *info = r.info;
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_ragged_info"); }
-
-int mijpeg_ragged_warning(mijpeg_decoder *d, int i, const char **message)
-try {
-  if (message) *message = nullptr;
-  if (!d || i < 0 || i >= d->ragged_n) return 0;
-  const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-  return r.child && !r.status ? mijpeg_last_warning(r.child, message) : 0;
-} catch (...) { return boundary_catch(d, "mijpeg_ragged_warning"); }
-
-int mijpeg_ragged_route(mijpeg_decoder *d, int i, const char **why)
-try {
-  if (why) *why = nullptr;
-  if (!d || i < 0) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (i >= d->ragged_n) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no such image: call mijpeg_decode_ragged_device first");
-  const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-  if (r.group >= 0) return 0;
-  if (why) *why = r.why_single.c_str();
-  return 1;
-} catch (...) { return boundary_catch(d, "mijpeg_ragged_route"); }
-
-int mijpeg_ragged_get_stats(mijpeg_decoder *d, mijpeg_ragged_stats *out)
-try {
-  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
-  *out = d->ragged_stats;
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_ragged_get_stats"); }
-
-int mijpeg_reconstruct_ragged_device(mijpeg_decoder *d, void *const *dst_device, const int64_t *row_strides, uint32_t flags, int sync)
-try {
-  if (!d || !dst_device || !row_strides) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
-  if (d->ragged_n < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded ragged batch: call mijpeg_decode_ragged_device first");
-  HIP_TRY(d, hipSetDevice(d->device));
-  const int n = d->ragged_n;
-  flags &= ~(uint32_t)(MIJPEG_FLAG_DEVICE_OUTPUT | MIJPEG_FLAG_NO_UPSAMPLING | MIJPEG_FLAG_SPECULATIVE);
-  d->ragged_stats.recon_launches = d->ragged_stats.recon_single = 0;
-  // Which kernel every group image takes, from ITS range check: images of a group that agree on kernel and arithmetic flavour
-  // share a launch -- one outlier beyond the fast gates runs the SAFE flavour alone instead of taking the group along.
-  // (quant_dev is only tested by the planner: the ragged launches read per-frame tables.)
-  static const uint16_t per_frame_tables = 0;
-  auto describe = [&](int i, bool own_tables) {
-    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-    mijpeg_batch b;
-    memset(&b, 0, sizeof(b));
-    b.info = r.info;
-    b.coef_dev = d->coef_dev + r.coef_base;
-    b.coef_frame_stride = r.info.coef_count;
-    b.quant_dev = own_tables ? &per_frame_tables : nullptr;
-    b.out_dev = (uint8_t *)dst_device[i];
-    b.out_row_stride = row_strides[i];
-    b.out_frame_stride = 0;
-    b.frames = 1;
-    b.flags = flags;
-    return b;
-  };
-  struct Launch { ReconPlan p; int group; std::vector<int> members; };
-  std::vector<Launch> launches;
-  std::vector<int> singles;
-  for (int i = 0; i < n; i++) {
-    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-    if (r.status || r.group < 0 || !dst_device[i]) continue;
-    const mijpeg_batch b = describe(i, true);
-    const ReconPlan p = plan_reconstruct(&b);
-    const bool has_flavour = (r.group == MIJPEG_RAGGED_420 && (p.kernel == Recon::FUSED420P || p.kernel == Recon::FUSED420)) ||
-                             (r.group == MIJPEG_RAGGED_422 && p.kernel == Recon::FUSED422) || (r.group == MIJPEG_RAGGED_444 && p.kernel == Recon::FUSED444) ||
-                             (r.group == MIJPEG_RAGGED_GREY && p.kernel == Recon::FUSED1);
-    if (!has_flavour) { singles.push_back(i); continue; }
-    size_t l = 0;
-    while (l < launches.size() && !(launches[l].group == r.group && launches[l].p.kernel == p.kernel && launches[l].p.fast == p.fast && launches[l].p.wide == p.wide)) l++;
-    if (l == launches.size()) launches.push_back(Launch{p, r.group, {}});
-    launches[l].members.push_back(i);
-  }
-  // descriptor tables of all launches in one upload: per launch [frames][first workgroups][deltas << 4, per frame 4 x 64]
-  if (!launches.empty()) {
-    size_t bytes = 0;
-    std::vector<size_t> at(launches.size());
-    for (size_t l = 0; l < launches.size(); l++) {
-      const size_t m = launches[l].members.size();
-      at[l] = bytes;
-      bytes += m * sizeof(RaggedFrame) + ((m + 1) * 4 + 15) / 16 * 16 + m * 4 * 64 * sizeof(int32_t);
-    }
-    int rc = ensure_dev(d, (void **)&d->ragged_desc_dev, &d->ragged_desc_cap, bytes);
-    if (rc) return rc;
-    if (d->ragged_upload_pending) { // (the pinned copy travels asynchronously: the last call's must have left)
-      HIP_TRY(d, hipEventSynchronize(d->ragged_uploaded));
-      d->ragged_upload_pending = false;
-    }
-    if ((rc = ensure_pinned(d, &d->ragged_desc_host, &d->ragged_desc_host_cap, bytes))) return rc;
-    std::vector<uint32_t> grid(launches.size());
-    for (size_t l = 0; l < launches.size(); l++) {
-      const std::vector<int> &mem = launches[l].members;
-      const size_t m = mem.size();
-      RaggedFrame *fr = (RaggedFrame *)(d->ragged_desc_host + at[l]);
-      uint32_t *first = (uint32_t *)(fr + m);
-      int32_t *q = (int32_t *)((uint8_t *)first + ((m + 1) * 4 + 15) / 16 * 16);
-      // the launch's own frames through the planner: first workgroups, tile grids, plane sizes
-      std::vector<mijpeg_info> infos(m);
-      std::vector<int32_t> grp(m);
-      std::vector<mijpeg_ragged_frame> pf(m);
-      int32_t grids[MIJPEG_RAGGED_GROUPS];
-      int64_t unused = 0;
-      for (size_t k = 0; k < m; k++) infos[k] = d->ragged[(size_t)mem[k]].info;
-      ragged_plan(infos.data(), (int)m, nullptr, grp.data(), pf.data(), grids, &unused);
-      for (size_t k = 0; k < m; k++) {
-        const int i = mem[k];
-        const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-        if (grp[k] != launches[l].group) return set_error(d, MIJPEG_ERR_PHASE_ERROR, "ragged planner disagrees with itself");
-        RaggedFrame &x = fr[k];
-        memset(&x, 0, sizeof(x));
-        x.coef_base = r.coef_base;
-        x.off_y = pf[k].off_y; x.off_cb = pf[k].off_cb; x.off_cr = pf[k].off_cr;
-        x.out = (uint8_t *)dst_device[i];
-        x.row_stride = row_strides[i];
-        x.width = pf[k].width; x.height = pf[k].height;
-        x.bw_y = pf[k].bw_y; x.bh_y = pf[k].bh_y; x.bw_c = pf[k].bw_c; x.bh_c = pf[k].bh_c;
-        x.cw = pf[k].cw; x.ch = pf[k].ch;
-        x.tiles_x = pf[k].tiles_x; x.tiles_y = pf[k].tiles_y;
-        x.qframe = (int32_t)k;
-        first[k] = (uint32_t)pf[k].first_workgroup;
-        for (int c = 0; c < 4; c++)
-          for (int z = 0; z < 64; z++) q[(k * 4 + (size_t)c) * 64 + (size_t)z] = c < r.info.components ? (int32_t)r.info.quant[r.info.quant_index[c]][z] << 4 : 16;
-      }
-      grid[l] = (uint32_t)grids[launches[l].group];
-      first[m] = grid[l];
-    }
-    HIP_TRY(d, hipMemcpyAsync(d->ragged_desc_dev, d->ragged_desc_host, bytes, hipMemcpyHostToDevice, d->stream));
-    if (!d->ragged_uploaded) HIP_TRY(d, hipEventCreateWithFlags(&d->ragged_uploaded, hipEventDisableTiming));
-    HIP_TRY(d, hipEventRecord(d->ragged_uploaded, d->stream));
-    d->ragged_upload_pending = true;
-    for (size_t l = 0; l < launches.size(); l++) {
-      const size_t m = launches[l].members.size();
-      Fused420Args a;
-      memset(&a, 0, sizeof(a));
-      a.coef = d->coef_dev;
-      a.frames = (int32_t)m;
-      a.ragged = (const RaggedFrame *)(d->ragged_desc_dev + at[l]);
-      a.ragged_first = (const uint32_t *)(a.ragged + m);
-      a.qdev = (const int32_t *)((const uint8_t *)a.ragged_first + ((m + 1) * 4 + 15) / 16 * 16);
-      if (launch_fused_ragged(launches[l].p, a, grid[l], d->stream))
-        return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-      d->ragged_stats.recon_launches++;
-    }
-  }
-  // One image whose reconstruction fails does not stop the others, whichever route it takes: the call works through the list
-  // and then returns the first such code, with a message that names the image.  (A launch of a whole group that fails, or
-  // memory that cannot be had for the tables, is the device's failure and ends the call at once; what was enqueued stays
-  // ordered on the object's stream, and the next call waits for the descriptor upload as usual.)
-  int failed = MIJPEG_OK;
-  std::string failed_msg;
-  // group images no ragged flavour fits (ranges beyond the fused kernels' gates, no colour transformation, ...): the existing kernels
-  for (int i : singles) {
-    mijpeg_batch b = describe(i, false);
-    const size_t ws = mijpeg_workspace_bytes(&b);
-    int rc = ws ? ensure_dev(d, (void **)&d->ws_dev, &d->ws_cap, ws) : MIJPEG_OK;
-    if (!rc) {
-      b.workspace = ws ? d->ws_dev : nullptr;
-      b.workspace_bytes = ws ? d->ws_cap : 0;
-      rc = mijpeg_launch_reconstruct(&b, d->stream);
-    }
-    if (rc) {
-      if (!failed) {
-        failed = rc;
-        failed_msg = "image " + std::to_string(i) + " of the ragged batch was not reconstructed";
-      }
-      continue;
-    }
-    d->ragged_stats.recon_single++;
-  }
-  // images of the single-image route, on their own objects (which wait for their kernels themselves)
-  for (int i = 0; i < n; i++) {
-    mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-    if (!r.child || r.status || !dst_device[i]) continue;
-    const int rc = mijpeg_reconstruct_device(r.child, dst_device[i], row_strides[i], flags, 1);
-    if (rc && !failed) {
-      const char *msg = nullptr;
-      (void)mijpeg_last_error(r.child, &msg);
-      failed = rc;
-      failed_msg = "image " + std::to_string(i) + " of the ragged batch was not reconstructed: " + (msg ? msg : "");
-    }
-  }
-  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
-  if (failed) return set_error(d, failed, failed_msg);
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_device"); }
-
-// ------------------------------------------------------------------------------------------------
-// encoder direction of the block pipeline
-// ------------------------------------------------------------------------------------------------
-int mijpeg_frame_layout(mijpeg_info *f)
-try {
-  if (!f || f->width < 1 || f->height < 1 || f->width > 65535 || f->height > 65535 || f->components < 1 || f->components > MIJPEG_MAX_COMPONENTS)
-    return MIJPEG_ERR_INVALID_PARAMETER;
-  int hmax = 1, vmax = 1;
-  for (int c = 0; c < f->components; c++) {
-    if (f->hsamp[c] < 1 || f->hsamp[c] > 4 || f->vsamp[c] < 1 || f->vsamp[c] > 4 || f->quant_index[c] < 0 || f->quant_index[c] > 3)
-      return MIJPEG_ERR_INVALID_PARAMETER;
-    hmax = std::max(hmax, f->hsamp[c]);
-    vmax = std::max(vmax, f->vsamp[c]);
-  }
-  f->mcus_x = (f->width + 8 * hmax - 1) / (8 * hmax);
-  f->mcus_y = (f->height + 8 * vmax - 1) / (8 * vmax);
-  int64_t off = 0;
-  for (int c = 0; c < f->components; c++) {
-    if (hmax % f->hsamp[c] || vmax % f->vsamp[c]) return MIJPEG_ERR_INVALID_PARAMETER; // fractional subsampling factors
-    f->subx[c] = hmax / f->hsamp[c];
-    f->suby[c] = vmax / f->vsamp[c];
-    f->blocks_w[c] = f->mcus_x * f->hsamp[c];
-    f->blocks_h[c] = f->mcus_y * f->vsamp[c];
-    f->coef_offset[c] = off;
-    off += (int64_t)f->blocks_w[c] * f->blocks_h[c] * 64;
-  }
-  f->coef_count = off;
-  f->sample_bytes = 1;
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(nullptr, "mijpeg_frame_layout"); }
-
-int mijpeg_launch_forward(const mijpeg_forward_batch *b, void *stream)
-try {
-  ForwardArgs a;
-  if (const int rc = forward_args_of(b, a)) return rc;
-  return launch_forward(a, (hipStream_t)stream) ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
-} catch (...) { return boundary_catch(nullptr, "mijpeg_launch_forward"); }
-
-void mijpeg_quality_tables(int quality, uint16_t luma[64], uint16_t chroma[64])
-try {
-  // ISO/IEC 10918-1 Annex K.1 / K.2 matrices, natural order
-  static const uint8_t K1[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
-                                 14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
-                                 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-  static const uint8_t K2[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-  quality = std::min(100, std::max(1, quality));
-  const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2; // quantization.cpp:296-299
-  for (int j = 0; j < 64; j++) {
-    luma[j] = (uint16_t)std::min(255, std::max(1, (K1[j] * scale + 50) / 100)); // :411, :443-466
-    chroma[j] = (uint16_t)std::min(255, std::max(1, (K2[j] * scale + 50) / 100));
-  }
-} catch (...) { (void)boundary_catch(nullptr, "mijpeg_quality_tables"); }
-
-// Entropy coding of one frame's coefficient planes on the device (hencode.hip) and download of the finished stream, as a
-// job of three stages with a host synchronisation in front of the second and the third (the byte counts the next stage
-// sizes its buffers and copies with come from the device).  Two jobs on two streams with two sets of buffers overlap:
-// mijpeg_encode_batch_device keeps the next frame's first stage in flight while it waits for the current frame.
-struct HencJob {
-  mijpeg_decoder *d = nullptr;
-  const mijpeg_info *f = nullptr;
-  int slot = 0, restart_interval = 0;
-  hipStream_t stream = nullptr;
-  HencArgs a;
-  EncTables tabs;
-  uint64_t *readback = nullptr; // pinned: [0] plain bytes, [1] 0xFF bytes
-  uint64_t *scratch = nullptr;
-  uint32_t chunks = 0;
-  uint8_t *result = nullptr;
-  size_t head_size = 0, ecs = 0;
-  std::vector<uint8_t> head;
-
-  static size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
-  int upload_tables()
-  {
-    HencTables *h = (HencTables *)((uint8_t *)d->henc_host + 64 + (size_t)slot * sizeof(HencTables)); // pinned, one per slot
-    henc_pack_tables(h, tabs);
-    HIP_TRY(d, hipMemcpyAsync((void *)a.tables, h, sizeof(*h), hipMemcpyHostToDevice, stream));
-    return MIJPEG_OK;
-  }
-
-  // geometry, buffers, tables (optimised ones cost a synchronisation of their own), then count + prefix sums
-  int stage_a(mijpeg_decoder *dec, const mijpeg_info &info, const int16_t *coef_dev, int ri, int optimize, int slot_, hipStream_t st)
-  {
-    d = dec; f = &info; slot = slot_; stream = st; restart_interval = ri;
-    const int nc = info.components;
-    memset(&a, 0, sizeof(a));
-    a.coef = coef_dev;
-    if (!henc_frame_geometry(a, info, ri)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device entropy coder");
-    const int B = a.blocks_per_mcu;
-    const uint64_t nblocks = (uint64_t)a.total_mcus * (uint64_t)B;
-    if (nblocks >= ((uint64_t)1 << 30)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "frame too large for the device entropy coder");
-    a.total_blocks = (uint32_t)nblocks;
-    a.n_intervals = (uint32_t)((a.total_mcus + a.ri - 1) / a.ri);
-    const uint32_t N = a.total_blocks, I = a.n_intervals;
-    // arena 1: tables, statistics, block and interval arrays, scan scratch
-    size_t o = 0;
-    const size_t o_tab = o; o = al(o + sizeof(HencTables));
-    const size_t o_hist = o; o = al(o + 4 * 256 * 4);
-    const size_t o_bits = o; o = al(o + (size_t)N * 4);
-    const size_t o_bitpos = o; o = al(o + ((size_t)N + 1) * 8);
-    const size_t o_ibytes = o; o = al(o + (size_t)I * 4);
-    const size_t o_istart = o; o = al(o + ((size_t)I + 1) * 8);
-    const size_t scratch_words = ((size_t)N / 1024 + 8) * 2 + 8192;
-    const size_t o_scratch = o; o = al(o + scratch_words * 8);
-    int rc = ensure_dev(d, (void **)&d->henc_dev[slot], &d->henc_cap[slot], o);
-    if (rc) return rc;
-    if (!d->henc_host) HIP_TRY(d, hipHostMalloc((void **)&d->henc_host, 64 + 2 * sizeof(HencTables), hipHostMallocDefault));
-    readback = d->henc_host + 2 * slot;
-    uint8_t *base = d->henc_dev[slot];
-    a.tables = (const HencTables *)(base + o_tab);
-    a.hist = (uint32_t *)(base + o_hist);
-    a.bits = (uint32_t *)(base + o_bits);
-    a.bitpos = (const uint64_t *)(base + o_bitpos);
-    a.ibytes = (uint32_t *)(base + o_ibytes);
-    a.istart = (const uint64_t *)(base + o_istart);
-    scratch = (uint64_t *)(base + o_scratch);
-    enc_standard_tables(tabs);
-    rc = upload_tables();
-    if (rc) return rc;
-    if (optimize) { // symbol statistics first, tables from them (Annex K.2)
-      HIP_TRY(d, hipMemsetAsync(base + o_hist, 0, 4 * 256 * 4, stream));
-      if (henc_count(a, true, stream)) return hip_fail(d, hipGetLastError(), "henc_count_kernel launch");
-      uint32_t hist[4][256];
-      HIP_TRY(d, hipMemcpyAsync(hist, base + o_hist, sizeof(hist), hipMemcpyDeviceToHost, stream));
-      HIP_TRY(d, hipStreamSynchronize(stream));
-      enc_optimal_tables(tabs, hist, hist + 2, nc > 1 ? 2 : 1);
-      rc = upload_tables();
-      if (rc) return rc;
-    }
-    if (henc_count(a, false, stream)) return hip_fail(d, hipGetLastError(), "henc_count_kernel launch");
-    if (exclusive_scan_u32(a.bits, (uint64_t *)a.bitpos, N, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
-    if (henc_interval_bytes(a, stream)) return hip_fail(d, hipGetLastError(), "henc_interval_bytes_kernel launch");
-    if (exclusive_scan_u32(a.ibytes, (uint64_t *)a.istart, I, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
-    HIP_TRY(d, hipMemcpyAsync(&readback[0], a.istart + I, 8, hipMemcpyDeviceToHost, stream));
-    return MIJPEG_OK;
-  }
-
-  // plain stream, stuffing
-  int stage_b()
-  {
-    HIP_TRY(d, hipStreamSynchronize(stream));
-    const uint64_t plain_bytes = readback[0];
-    const uint32_t I = a.n_intervals;
-    // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check)
-    chunks = (uint32_t)((plain_bytes + HENC_STUFF_CHUNK - 1) / HENC_STUFF_CHUNK);
-    size_t q = 0;
-    const size_t q_plain = q; q = al(q + (size_t)plain_bytes + 16);
-    const size_t q_ffc = q; q = al(q + (size_t)chunks * 4 + 4);
-    const size_t q_ffs = q; q = al(q + ((size_t)chunks + 1) * 8);
-    const size_t q_out = q; q = al(q + (size_t)plain_bytes * 2 + (size_t)I * 2 + 16);
-    const int rc = ensure_dev(d, (void **)&d->henc_out_dev[slot], &d->henc_out_cap[slot], q);
-    if (rc) return rc;
-    uint8_t *ob = d->henc_out_dev[slot];
-    a.plain = (uint32_t *)(ob + q_plain);
-    a.plain_bytes = plain_bytes;
-    a.ffcount = (uint32_t *)(ob + q_ffc);
-    a.ffstart = (const uint64_t *)(ob + q_ffs);
-    a.out = ob + q_out;
-    HIP_TRY(d, hipMemsetAsync(ob + q_plain, 0, al((size_t)plain_bytes + 16), stream));
-    if (henc_emit(a, stream)) return hip_fail(d, hipGetLastError(), "henc_emit_kernel launch");
-    if (henc_count_ff(a, stream)) return hip_fail(d, hipGetLastError(), "henc_count_ff_kernel launch");
-    if (exclusive_scan_u32(a.ffcount, (uint64_t *)a.ffstart, chunks, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
-    if (henc_stuff(a, stream)) return hip_fail(d, hipGetLastError(), "henc_stuff_kernel launch");
-    HIP_TRY(d, hipMemcpyAsync(&readback[1], a.ffstart + chunks, 8, hipMemcpyDeviceToHost, stream));
-    return MIJPEG_OK;
-  }
-
-  // headers on the host, download of the entropy coded data behind them
-  int stage_c()
-  {
-    HIP_TRY(d, hipStreamSynchronize(stream));
-    ecs = (size_t)a.plain_bytes + (size_t)readback[1] + (size_t)(a.n_intervals - 1) * 2;
-    head.clear();
-    enc_write_headers(head, *f, tabs, restart_interval);
-    head_size = head.size();
-    result = (uint8_t *)malloc(head_size + ecs + 2);
-    if (!result) return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the stream");
-    memcpy(result, head.data(), head_size);
-    const hipError_t e = hipMemcpyAsync(result + head_size, a.out, ecs, hipMemcpyDeviceToHost, stream);
-    if (e != hipSuccess) { free(result); result = nullptr; return hip_fail(d, e, "download of the stream"); }
-    return MIJPEG_OK;
-  }
-
-  int finish(uint8_t **out_stream, size_t *out_size)
-  {
-    const hipError_t e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) { free(result); result = nullptr; return hip_fail(d, e, "download of the stream"); }
-    result[head_size + ecs] = 0xff;
-    result[head_size + ecs + 1] = 0xd9;
-    *out_stream = result;
-    *out_size = head_size + ecs + 2;
-    result = nullptr;
-    return MIJPEG_OK;
-  }
-};
-
-static int device_entropy_code(mijpeg_decoder *d, const mijpeg_info &f, const int16_t *coef_dev, int restart_interval, int optimize,
-                               uint8_t **stream, size_t *size)
-{
-  HencJob job;
-  int rc = job.stage_a(d, f, coef_dev, restart_interval, optimize, 0, d->stream);
-  if (!rc) rc = job.stage_b();
-  if (!rc) rc = job.stage_c();
-  if (!rc) rc = job.finish(stream, size);
-  return rc;
-}
-
-int mijpeg_encode_batch_device(mijpeg_decoder *d, const mijpeg_forward_batch *b, int restart_interval, int optimize, uint8_t **streams, size_t *sizes)
-try {
-  if (!d || !b || !streams || !sizes || b->frames < 1 || restart_interval < 0 || restart_interval > 65535) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
-  HIP_TRY(d, hipSetDevice(d->device));
-  for (int f = 0; f < b->frames; f++) { streams[f] = nullptr; sizes[f] = 0; }
-  const auto t_begin = std::chrono::steady_clock::now();
-  int rc = mijpeg_launch_forward(b, d->stream);
-  if (rc) return set_error(d, rc, "forward kernel launch failed");
-  // frame f on stream f & 1 with buffer set f & 1: while the host waits for one frame's byte counts and download, the
-  // other frame's kernels run
-  if (!d->copy_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
-  HIP_TRY(d, hipEventRecord(d->ev0, d->stream));
-  HIP_TRY(d, hipStreamWaitEvent(d->copy_stream, d->ev0, 0));
-  hipStream_t st[2] = {d->stream, d->copy_stream};
-  HencJob jobs[2];
-  auto coef_of = [&](int f) { return b->coef_dev + (int64_t)f * b->coef_frame_stride; };
-  rc = jobs[0].stage_a(d, b->info, coef_of(0), restart_interval, optimize, 0, st[0]);
-  for (int f = 0; f < b->frames && !rc; f++) {
-    HencJob &cur = jobs[f & 1], &nxt = jobs[(f + 1) & 1];
-    if (f + 1 < b->frames) rc = nxt.stage_a(d, b->info, coef_of(f + 1), restart_interval, optimize, (f + 1) & 1, st[(f + 1) & 1]);
-    if (!rc) rc = cur.stage_b();
-    if (!rc) rc = cur.stage_c();
-    if (!rc) rc = cur.finish(&streams[f], &sizes[f]);
-  }
-  (void)hipStreamSynchronize(d->copy_stream);
-  (void)hipStreamSynchronize(d->stream);
-  if (rc)
-    for (int f = 0; f < b->frames; f++) { free(streams[f]); streams[f] = nullptr; sizes[f] = 0; }
-  d->timing[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); // mijpeg_last_timing: the whole call
-  d->timing[1] = d->timing[2] = d->timing[3] = 0;
-  return rc;
-} catch (...) { return boundary_catch(d, "mijpeg_encode_batch_device"); }
-
-int mijpeg_encode_image(mijpeg_decoder *d, const uint8_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
-                        int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint8_t **stream, size_t *size)
-try {
-  return mijpeg_encode_image_ex(d, pixels, width, height, components, row_stride, quality, hsamp, vsamp, restart_interval, optimize, 0, stream, size);
-} catch (...) { return boundary_catch(d, "mijpeg_encode_image"); }
-
-int mijpeg_encode_image_ex(mijpeg_decoder *d, const uint8_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
-                           int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint32_t flags,
-                           uint8_t **stream, size_t *size)
-try {
-  using clk = std::chrono::steady_clock;
-  const auto t_begin = clk::now();
-  if (!d || !pixels || !stream || !size || (components != 1 && components != 3) || row_stride < (int64_t)width * components)
-    return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
-  HIP_TRY(d, hipSetDevice(d->device));
-  mijpeg_forward_batch b;
-  memset(&b, 0, sizeof(b));
-  mijpeg_info &f = b.info;
-  f.width = width;
-  f.height = height;
-  f.components = components;
-  f.precision = 8;
-  f.ycbcr = components == 3 ? 1 : 0;
-  for (int c = 0; c < components; c++) {
-    f.hsamp[c] = hsamp ? hsamp[c] : 1;
-    f.vsamp[c] = vsamp ? vsamp[c] : 1;
-    // the reference encoder defines a luma and a chroma table but its frame header selects table 0 for every component
-    // (what its own files show: tests/test_encoder.py::test_quality_tables_are_the_reference_encoders), so that is
-    // what reproduces its coefficients
-    f.quant_index[c] = 0;
-  }
-  mijpeg_quality_tables(quality, f.quant[0], f.quant[1]);
-  int rc = mijpeg_frame_layout(&f);
-  if (rc) return set_error(d, rc, "invalid frame layout for encoding");
-  const size_t px_bytes = (size_t)row_stride * (size_t)height, coef_bytes = (size_t)f.coef_count * sizeof(int16_t);
-  rc = ensure_dev(d, (void **)&d->enc_dev, &d->enc_cap, px_bytes + 256 + coef_bytes);
-  if (rc) return rc;
-  int16_t *coef_dev = (int16_t *)(d->enc_dev + ((px_bytes + 255) & ~(size_t)255));
-  // pinned staging: [pixels][coefficients].  The picture goes up in bands, each gathered into pinned memory by the pool
-  // threads while the DMA of the previous band runs; the coefficients come down into pinned memory the coder reads.
-  const size_t stage_bytes = ((px_bytes + 255) & ~(size_t)255) + coef_bytes;
-  rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, stage_bytes);
-  if (rc) return rc;
-  int16_t *coef_host = (int16_t *)(d->stage_host + ((px_bytes + 255) & ~(size_t)255));
-  {
-    const size_t band = std::max<size_t>((size_t)8 << 20, (px_bytes + 7) / 8) & ~(size_t)255;
-    for (size_t b0 = 0; b0 < px_bytes; b0 += band) {
-      const size_t len = std::min(band, px_bytes - b0);
-      const size_t pieces = (len + ((size_t)1 << 20) - 1) >> 20;
-      const int workers = (int)std::min<size_t>(pieces, (size_t)std::min(default_threads(), 16));
-      parallel_for(workers, [&](int w) {
-        for (size_t k = (size_t)w; k < pieces; k += (size_t)workers) {
-          const size_t o = b0 + (k << 20), n = std::min<size_t>((size_t)1 << 20, b0 + len - o);
-          memcpy(d->stage_host + o, pixels + o, n);
-        }
-      });
-      HIP_TRY(d, hipMemcpyAsync(d->enc_dev + b0, d->stage_host + b0, len, hipMemcpyHostToDevice, d->stream));
-    }
-  }
-  b.pixels_dev = d->enc_dev;
-  b.pixel_row_stride = row_stride;
-  b.pixel_frame_stride = (int64_t)px_bytes;
-  b.coef_dev = coef_dev;
-  b.coef_frame_stride = f.coef_count;
-  b.frames = 1;
-  const auto t_up = clk::now(); // uploads enqueued (the gathering is synchronous)
-  rc = mijpeg_launch_forward(&b, d->stream);
-  if (rc) return set_error(d, rc, "forward kernel launch failed");
-  static const bool env_host_coder = getenv("MIJPEG_ENTROPY_CODER") && !strcmp(getenv("MIJPEG_ENTROPY_CODER"), "host");
-  if (!(flags & MIJPEG_ENCODE_HOST_CODER) && !env_host_coder) {
-    if (restart_interval < 0 || restart_interval > 65535) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "invalid restart interval");
-    rc = device_entropy_code(d, f, coef_dev, restart_interval, optimize, stream, size);
-    d->timing[0] = std::chrono::duration<double>(t_up - t_begin).count();
-    d->timing[1] = std::chrono::duration<double>(clk::now() - t_up).count(); // kernels, entropy coder and download of the stream
-    d->timing[2] = d->timing[3] = 0;
-    if (rc != MIJPEG_ERR_NOT_AVAILABLE) return rc;
-  }
-  HIP_TRY(d, hipStreamSynchronize(d->stream));
-  const auto t_kernel = clk::now();
-  HIP_TRY(d, hipMemcpyAsync(coef_host, coef_dev, coef_bytes, hipMemcpyDeviceToHost, d->stream));
-  HIP_TRY(d, hipStreamSynchronize(d->stream));
-  const auto t_down = clk::now();
-  rc = mijpeg_encode_coefficients(&f, coef_host, restart_interval, optimize, 0, stream, size);
-  // mijpeg_last_timing: gather + upload, kernels (incl. the rest of the upload), download, entropy coder
-  d->timing[0] = std::chrono::duration<double>(t_up - t_begin).count();
-  d->timing[1] = std::chrono::duration<double>(t_kernel - t_up).count();
-  d->timing[2] = std::chrono::duration<double>(t_down - t_kernel).count();
-  d->timing[3] = std::chrono::duration<double>(clk::now() - t_down).count();
-  if (rc) return set_error(d, rc, "entropy coding failed");
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_encode_image_ex"); }
-
-// ------------------------------------------------------------------------------------------------
 // decoder-object reconstruction
 // ------------------------------------------------------------------------------------------------
 // The frame as the reconstruction sees it: the whole picture, or -- without upsampling -- one component at its own
@@ -2343,27 +1107,10 @@ static mijpeg_info view_of(const mijpeg_info &f, int comp)
 static int reconstruct_view(mijpeg_decoder *d, int comp, void *dst_device, int64_t row_stride, uint32_t flags, int sync)
 {
   HIP_TRY(d, hipSetDevice(d->device));
-  mijpeg_batch b;
-  memset(&b, 0, sizeof(b));
-  b.info = view_of(d->host.info, comp);
-  b.coef_dev = d->coef_dev + (comp < 0 ? 0 : d->host.info.coef_offset[comp]);
-  b.coef_frame_stride = b.info.coef_count;
-  b.out_dev = (uint8_t *)dst_device;
-  b.out_row_stride = row_stride;
-  b.out_frame_stride = row_stride * b.info.height;
-  b.frames = 1;
-  b.flags = flags;
+  const mijpeg_info v = view_of(d->host.info, comp);
+  mijpeg_batch b = batch_of(v, d->coef_dev + (comp < 0 ? 0 : d->host.info.coef_offset[comp]), dst_device, row_stride, row_stride * v.height, 1, flags);
   b.xt = d->host.is_xt() ? &d->host.xt : nullptr;
-  const size_t ws = mijpeg_workspace_bytes(&b);
-  if (ws) {
-    int rc = ensure_dev(d, (void **)&d->ws_dev, &d->ws_cap, ws);
-    if (rc) return rc;
-    b.workspace = d->ws_dev;
-    b.workspace_bytes = d->ws_cap;
-  }
-  const int rc = mijpeg_launch_reconstruct(&b, d->stream);
-  if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError())
-                                                           : std::string("reconstruction not available for this stream"));
+  if (const int rc = reconstruct_on(d, b, nullptr, "stream")) return rc;
   if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
   return MIJPEG_OK;
 }
@@ -2778,10 +1525,6 @@ try {
     }
     // ---- not the plain picture: both images through the unfused kernels with their row maps on this request's lines
     HIP_TRY(d, hipSetDevice(d->device));
-    mijpeg_batch b;
-    memset(&b, 0, sizeof(b));
-    b.info = f;
-    b.xt = &x;
     const int sb = f.sample_bytes > 0 ? f.sample_bytes : 2;
     const size_t row = ((size_t)f.width * 3 * sb + 7) & ~(size_t)7, padded = row * f.height;
     int rc = ensure_dev(d, (void **)&d->req_dev, &d->req_dev_cap, padded);
@@ -2801,20 +1544,8 @@ try {
     if (rc) return rc;
     HIP_TRY(d, hipMemcpyAsync(d->rowmap_dev, maps.data(), maps.size() * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream)); // `maps` is pageable and leaves scope
-    b.coef_dev = d->coef_dev;
-    b.coef_frame_stride = f.coef_count;
-    b.out_dev = d->req_dev;
-    b.out_row_stride = (int64_t)row;
-    b.out_frame_stride = (int64_t)padded;
-    b.frames = 1;
-    b.flags = pass | MIJPEG_FLAG_FORCE_GENERIC;
-    const size_t ws = mijpeg_workspace_bytes(&b);
-    if (ws) {
-      rc = ensure_dev(d, (void **)&d->ws_dev, &d->ws_cap, ws);
-      if (rc) return rc;
-      b.workspace = d->ws_dev;
-      b.workspace_bytes = d->ws_cap;
-    }
+    mijpeg_batch b = batch_of(f, d->coef_dev, d->req_dev, (int64_t)row, (int64_t)padded, 1, pass | MIJPEG_FLAG_FORCE_GENERIC);
+    b.xt = &x;
     const int y_count = pl.max_y - pl.min_y + 1;
     RequestExtra rx;
     memset(&rx, 0, sizeof(rx));
@@ -2833,9 +1564,7 @@ try {
       rx.wstart[pn] = up ? p.wstart[c] : 0;
       rx.wlimit[pn] = up ? p.wlimit[c] : (f.height + g.suby[c] - 1) / std::max(1, g.suby[c]);
     }
-    rc = launch_reconstruct_ex(&b, d->stream, &rx);
-    if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError())
-                                                             : std::string("reconstruction not available for this request"));
+    if ((rc = reconstruct_on(d, b, &rx, "request"))) return rc;
     return hand_out_request(d, pl.min_x, pl.min_y, y_count, cx1, cy1, 0, 2, 3, sb, row, padded, -1, false, to_device, dst, bpp, bpr);
   }
   ensure_request_models(d);
@@ -2877,11 +1606,8 @@ try {
   // ---- not the plain picture: row maps, zeros, displaced upsampler output -> the generic kernels on this request's lines
   HIP_TRY(d, hipSetDevice(d->device));
   const bool all_on_view = vc >= 0 && p.ycc;
-  mijpeg_batch b;
-  memset(&b, 0, sizeof(b));
-  b.info = request_frame(f, vc, all_on_view);
-  b.info.ycbcr = p.ycc ? 1 : 0;
-  const mijpeg_info &g = b.info;
+  mijpeg_info g = request_frame(f, vc, all_on_view);
+  g.ycbcr = p.ycc ? 1 : 0;
   const int nc = g.components, sb = g.sample_bytes > 0 ? g.sample_bytes : 1;
   const size_t row = ((size_t)g.width * nc * sb + 7) & ~(size_t)7, padded = row * g.height;
   int rc = ensure_dev(d, (void **)&d->req_dev, &d->req_dev_cap, padded);
@@ -2914,20 +1640,8 @@ try {
     if (rc) return rc;
     HIP_TRY(d, hipMemcpyAsync(d->rowmap_dev, maps.data(), maps.size() * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
     HIP_TRY(d, hipStreamSynchronize(d->stream)); // `maps` is pageable and leaves scope; uploads of the coefficients are complete too
-    b.coef_dev = d->coef_dev + (vc >= 0 && !all_on_view ? f.coef_offset[vc] : 0);
-    b.coef_frame_stride = g.coef_count;
-    b.out_dev = d->req_dev;
-    b.out_row_stride = (int64_t)row;
-    b.out_frame_stride = (int64_t)padded;
-    b.frames = 1;
-    b.flags = pass | MIJPEG_FLAG_FORCE_GENERIC | (p.ycc ? 0u : MIJPEG_FLAG_NO_COLOR_TRANSFORM);
-    const size_t ws = mijpeg_workspace_bytes(&b);
-    if (ws) {
-      rc = ensure_dev(d, (void **)&d->ws_dev, &d->ws_cap, ws);
-      if (rc) return rc;
-      b.workspace = d->ws_dev;
-      b.workspace_bytes = d->ws_cap;
-    }
+    mijpeg_batch b = batch_of(g, d->coef_dev + (vc >= 0 && !all_on_view ? f.coef_offset[vc] : 0), d->req_dev, (int64_t)row, (int64_t)padded, 1,
+                              pass | MIJPEG_FLAG_FORCE_GENERIC | (p.ycc ? 0u : MIJPEG_FLAG_NO_COLOR_TRANSFORM));
     RequestExtra rx;
     memset(&rx, 0, sizeof(rx));
     rx.rowmap_dev = d->rowmap_dev;
@@ -2943,9 +1657,7 @@ try {
       rx.wstart[c] = up ? p.wstart[pc] : 0;
       rx.wlimit[c] = up ? p.wlimit[pc] : (g.dnl && g.suby[c] > 1) ? g.blocks_h[c] * 8 : (g.height + g.suby[c] - 1) / g.suby[c];
     }
-    rc = launch_reconstruct_ex(&b, d->stream, &rx);
-    if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError())
-                                                             : std::string("reconstruction not available for this request"));
+    if ((rc = reconstruct_on(d, b, &rx, "request"))) return rc;
   }
   return hand_out_request(d, p.min_x, p.min_y, y_count, cx1, cy1, min_comp, max_comp, nc, sb, row, padded, vc, all_on_view, to_device, dst, bpp, bpr);
 } catch (...) { return boundary_catch(d, "mijpeg_display_rect"); }

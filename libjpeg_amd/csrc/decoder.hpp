@@ -1,5 +1,6 @@
-// decoder.hpp -- the decoder object of the C ABI and what its two translation units share: capi.cpp (the extern "C" bodies)
-// and entropy_device.cpp (entropy decoding on the device).  Private to libmijpeg.so.
+// decoder.hpp -- the decoder object of the C ABI and what its translation units share: capi.cpp (the object, single images, uniform
+// batches, rectangles), entropy_device.cpp, reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp and encode_device.cpp.
+// Private to libmijpeg.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -173,7 +174,13 @@ inline void quiesce(mijpeg_decoder *d)
 // Device buffers that grow through the buffer cache (capi.cpp): what this object has enqueued finishes before the old buffer goes
 int ensure_dev(mijpeg_decoder *d, void **ptr, size_t *cap, size_t bytes);
 
-// ... and their pinned counterpart, for staging buffers that are not handed to the buffer cache
+// capi.cpp: the coefficient store for `count` int16 (device mirror; pinned host planes where need_host); a batch that was submitted
+// and not waited for is settled before its staging buffers are rewritten; a speculative launch is validated
+int ensure_coef_store(mijpeg_decoder *d, size_t count, bool need_host = true);
+int settle_pending(mijpeg_decoder *d);
+int settle_speculation(mijpeg_decoder *d);
+
+// ... and ensure_dev's pinned counterpart, for staging buffers that are not handed to the buffer cache
 inline int ensure_pinned(mijpeg_decoder *d, uint8_t **ptr, size_t *cap, size_t bytes)
 {
   if (*cap >= bytes) return MIJPEG_OK;
@@ -199,20 +206,6 @@ struct TraceMarks {
 
 // The boundary of the C ABI (capi.cpp): the handler of every extern "C" function-try-block
 int boundary_catch(mijpeg_decoder *d, const char *where) noexcept;
-
-// ---- encode_device.cpp: what the encoder entry points share ----
-namespace mij {
-struct ForwardArgs;
-struct HencArgs;
-struct HencTables;
-struct EncTables;
-}
-// the forward kernels' argument block for a batch (geometry, routing, quantiser multipliers): MIJPEG_OK or the refusal
-int forward_args_of(const mijpeg_forward_batch *b, mij::ForwardArgs &a);
-// MCU structure and plane geometry of a frame for the device entropy coder (ri: MCUs per interval, 0 = none); false: more than
-// 64 blocks per MCU
-bool henc_frame_geometry(mij::HencArgs &a, const mijpeg_info &info, int ri);
-void henc_pack_tables(mij::HencTables *h, const mij::EncTables &t);
 
 // ---- entropy_device.cpp: on-device entropy decoding ----
 // One frame of a file: its decoder, the element type of its planes, where they start in the object's coefficient store.

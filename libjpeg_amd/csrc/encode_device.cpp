@@ -1,6 +1,7 @@
-// encode_device.cpp -- the encoder direction's host side that more than one entry point needs (argument blocks of the forward
-// kernels and of the device entropy coder) and the RAGGED ENCODE: lists of pictures of any shapes through one device pass
-// (mijpeg_encode_ragged_plan / _device / mijpeg_encode_ragged).  Private to libmijpeg.so.
+// encode_device.cpp -- the encoder direction on the device: frame layout and quality tables, the argument blocks of the forward
+// kernels and of the device entropy coder, the per-frame coder (HencJob: mijpeg_encode_image(_ex), mijpeg_encode_batch_device) and
+// the RAGGED ENCODE: lists of pictures of any shapes through one device pass (mijpeg_encode_ragged_plan / _device /
+// mijpeg_encode_ragged).  The entropy coder on the host is encoder.cpp.  Private to libmijpeg.so.
 //
 // A pass of the ragged encode:
 //   plan        per picture: frame layout, block and interval counts, its place in the pass's index spaces, its coefficient store
@@ -10,6 +11,7 @@
 //               sums, interval bytes, prefix sums -> read-back of the plain sizes (sync) -> layout of the plain buffer, emit,
 //               0xFF counts, prefix sums -> read-back (sync) -> stuffing -> ONE download of the output arena (sync)
 //   assembly    headers in front of every picture's piece, EOI behind it
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -23,9 +25,10 @@
 using namespace mij;
 
 // ------------------------------------------------------------------------------------------------
-// argument blocks (shared with capi.cpp: mijpeg_launch_forward, HencJob)
+// argument blocks
 // ------------------------------------------------------------------------------------------------
-int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a)
+// the forward kernels' argument block for a batch (geometry, routing, quantiser multipliers): MIJPEG_OK or the refusal
+static int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a)
 {
   if (!b || !b->pixels_dev || !b->coef_dev || b->frames < 1) return MIJPEG_ERR_INVALID_PARAMETER;
   const mijpeg_info &f = b->info;
@@ -77,7 +80,9 @@ int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a)
   return MIJPEG_OK;
 }
 
-bool henc_frame_geometry(HencArgs &a, const mijpeg_info &info, int ri)
+// MCU structure and plane geometry of a frame for the device entropy coder (ri: MCUs per interval, 0 = none); false: more than
+// 64 blocks per MCU
+static bool henc_frame_geometry(HencArgs &a, const mijpeg_info &info, int ri)
 {
   const int nc = info.components;
   a.ncomp = nc;
@@ -105,7 +110,7 @@ bool henc_frame_geometry(HencArgs &a, const mijpeg_info &info, int ri)
   return true;
 }
 
-void henc_pack_tables(HencTables *h, const EncTables &t)
+static void henc_pack_tables(HencTables *h, const EncTables &t)
 {
   memset(h, 0, sizeof(*h));
   for (int k = 0; k < 2; k++) {
@@ -115,10 +120,211 @@ void henc_pack_tables(HencTables *h, const EncTables &t)
 }
 
 // ------------------------------------------------------------------------------------------------
-// ragged encode: the planner
+// helpers; the per-frame coder
 // ------------------------------------------------------------------------------------------------
 namespace {
 
+struct Carver { // lays regions out in a buffer, 256-byte aligned
+  size_t at = 0;
+  size_t take(size_t bytes)
+  {
+    const size_t o = at;
+    at = (at + bytes + 255) & ~(size_t)255;
+    return o;
+  }
+};
+
+// what an exclusive_scan_u32 over n elements needs as scratch (hencode.hip)
+size_t scan_scratch_bytes(size_t n) { return ((n / 1024 + 8) * 2 + 8192) * 8; }
+
+// The frame of a picture to encode: its layout and the tables of its quality (hsamp, vsamp: null = 1 x 1 throughout).  What
+// mijpeg_frame_layout says to it.
+int picture_info_of(int32_t width, int32_t height, int32_t components, const int32_t *hsamp, const int32_t *vsamp, int quality, mijpeg_info &f)
+{
+  memset(&f, 0, sizeof(f));
+  f.width = width;
+  f.height = height;
+  f.components = components;
+  f.precision = 8;
+  f.ycbcr = components == 3 ? 1 : 0;
+  for (int c = 0; c < components; c++) {
+    f.hsamp[c] = hsamp ? hsamp[c] : 1;
+    f.vsamp[c] = vsamp ? vsamp[c] : 1;
+    // the reference encoder defines a luma and a chroma table but its frame header selects table 0 for every component
+    // (what its own files show: tests/test_encoder.py::test_quality_tables_are_the_reference_encoders), so that is
+    // what reproduces its coefficients
+    f.quant_index[c] = 0;
+  }
+  mijpeg_quality_tables(quality, f.quant[0], f.quant[1]);
+  return mijpeg_frame_layout(&f);
+}
+
+// A finished stream in memory the client frees: headers, `ecs` bytes of entropy coded data, EOI.  ecs_src null: the caller puts
+// the data there itself (a download from the device: no copy on the host in between).
+int assemble_stream(const std::vector<uint8_t> &head, const uint8_t *ecs_src, size_t ecs, uint8_t **out, size_t *size)
+{
+  const size_t hs = head.size();
+  uint8_t *s = (uint8_t *)malloc(hs + ecs + 2);
+  if (!s) return MIJPEG_ERR_OUT_OF_MEMORY;
+  memcpy(s, head.data(), hs);
+  if (ecs_src) memcpy(s + hs, ecs_src, ecs);
+  s[hs + ecs] = 0xff;
+  s[hs + ecs + 1] = 0xd9;
+  *out = s;
+  *size = hs + ecs + 2;
+  return MIJPEG_OK;
+}
+
+// Entropy coding of one frame's coefficient planes on the device (hencode.hip) and download of the finished stream, as a
+// job of three stages with a host synchronisation in front of the second and the third (the byte counts the next stage
+// sizes its buffers and copies with come from the device).  Two jobs on two streams with two sets of buffers overlap:
+// mijpeg_encode_batch_device keeps the next frame's first stage in flight while it waits for the current frame.
+struct HencJob {
+  mijpeg_decoder *d = nullptr;
+  const mijpeg_info *f = nullptr;
+  int slot = 0, restart_interval = 0;
+  hipStream_t stream = nullptr;
+  HencArgs a;
+  EncTables tabs;
+  uint64_t *readback = nullptr; // pinned: [0] plain bytes, [1] 0xFF bytes
+  uint64_t *scratch = nullptr;
+  uint32_t chunks = 0;
+  uint8_t *result = nullptr;
+  size_t result_size = 0;
+  std::vector<uint8_t> head;
+
+  int upload_tables()
+  {
+    HencTables *h = (HencTables *)((uint8_t *)d->henc_host + 64 + (size_t)slot * sizeof(HencTables)); // pinned, one per slot
+    henc_pack_tables(h, tabs);
+    HIP_TRY(d, hipMemcpyAsync((void *)a.tables, h, sizeof(*h), hipMemcpyHostToDevice, stream));
+    return MIJPEG_OK;
+  }
+
+  // geometry, buffers, tables (optimised ones cost a synchronisation of their own), then count + prefix sums
+  int stage_a(mijpeg_decoder *dec, const mijpeg_info &info, const int16_t *coef_dev, int ri, int optimize, int slot_, hipStream_t st)
+  {
+    d = dec; f = &info; slot = slot_; stream = st; restart_interval = ri;
+    const int nc = info.components;
+    memset(&a, 0, sizeof(a));
+    a.coef = coef_dev;
+    if (!henc_frame_geometry(a, info, ri)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device entropy coder");
+    const int B = a.blocks_per_mcu;
+    const uint64_t nblocks = (uint64_t)a.total_mcus * (uint64_t)B;
+    if (nblocks >= ((uint64_t)1 << 30)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "frame too large for the device entropy coder");
+    a.total_blocks = (uint32_t)nblocks;
+    a.n_intervals = (uint32_t)((a.total_mcus + a.ri - 1) / a.ri);
+    const uint32_t N = a.total_blocks, I = a.n_intervals;
+    // arena 1: tables, statistics, block and interval arrays, scan scratch
+    Carver ar;
+    const size_t o_tab = ar.take(sizeof(HencTables));
+    const size_t o_hist = ar.take(4 * 256 * 4);
+    const size_t o_bits = ar.take((size_t)N * 4);
+    const size_t o_bitpos = ar.take(((size_t)N + 1) * 8);
+    const size_t o_ibytes = ar.take((size_t)I * 4);
+    const size_t o_istart = ar.take(((size_t)I + 1) * 8);
+    const size_t o_scratch = ar.take(scan_scratch_bytes(N));
+    int rc = ensure_dev(d, (void **)&d->henc_dev[slot], &d->henc_cap[slot], ar.at);
+    if (rc) return rc;
+    if (!d->henc_host) HIP_TRY(d, hipHostMalloc((void **)&d->henc_host, 64 + 2 * sizeof(HencTables), hipHostMallocDefault));
+    readback = d->henc_host + 2 * slot;
+    uint8_t *base = d->henc_dev[slot];
+    a.tables = (const HencTables *)(base + o_tab);
+    a.hist = (uint32_t *)(base + o_hist);
+    a.bits = (uint32_t *)(base + o_bits);
+    a.bitpos = (const uint64_t *)(base + o_bitpos);
+    a.ibytes = (uint32_t *)(base + o_ibytes);
+    a.istart = (const uint64_t *)(base + o_istart);
+    scratch = (uint64_t *)(base + o_scratch);
+    enc_standard_tables(tabs);
+    rc = upload_tables();
+    if (rc) return rc;
+    if (optimize) { // symbol statistics first, tables from them (Annex K.2)
+      HIP_TRY(d, hipMemsetAsync(base + o_hist, 0, 4 * 256 * 4, stream));
+      if (henc_count(a, true, stream)) return hip_fail(d, hipGetLastError(), "henc_count_kernel launch");
+      uint32_t hist[4][256];
+      HIP_TRY(d, hipMemcpyAsync(hist, base + o_hist, sizeof(hist), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(d, hipStreamSynchronize(stream));
+      enc_optimal_tables(tabs, hist, hist + 2, nc > 1 ? 2 : 1);
+      rc = upload_tables();
+      if (rc) return rc;
+    }
+    if (henc_count(a, false, stream)) return hip_fail(d, hipGetLastError(), "henc_count_kernel launch");
+    if (exclusive_scan_u32(a.bits, (uint64_t *)a.bitpos, N, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
+    if (henc_interval_bytes(a, stream)) return hip_fail(d, hipGetLastError(), "henc_interval_bytes_kernel launch");
+    if (exclusive_scan_u32(a.ibytes, (uint64_t *)a.istart, I, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
+    HIP_TRY(d, hipMemcpyAsync(&readback[0], a.istart + I, 8, hipMemcpyDeviceToHost, stream));
+    return MIJPEG_OK;
+  }
+
+  // plain stream, stuffing
+  int stage_b()
+  {
+    HIP_TRY(d, hipStreamSynchronize(stream));
+    const uint64_t plain_bytes = readback[0];
+    const uint32_t I = a.n_intervals;
+    // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check)
+    chunks = (uint32_t)((plain_bytes + HENC_STUFF_CHUNK - 1) / HENC_STUFF_CHUNK);
+    Carver ar;
+    const size_t q_plain = ar.take((size_t)plain_bytes + 16);
+    const size_t q_ffc = ar.take((size_t)chunks * 4 + 4);
+    const size_t q_ffs = ar.take(((size_t)chunks + 1) * 8);
+    const size_t q_out = ar.take((size_t)plain_bytes * 2 + (size_t)I * 2 + 16);
+    const int rc = ensure_dev(d, (void **)&d->henc_out_dev[slot], &d->henc_out_cap[slot], ar.at);
+    if (rc) return rc;
+    uint8_t *ob = d->henc_out_dev[slot];
+    a.plain = (uint32_t *)(ob + q_plain);
+    a.plain_bytes = plain_bytes;
+    a.ffcount = (uint32_t *)(ob + q_ffc);
+    a.ffstart = (const uint64_t *)(ob + q_ffs);
+    a.out = ob + q_out;
+    HIP_TRY(d, hipMemsetAsync(ob + q_plain, 0, q_ffc - q_plain, stream)); // (the region with its padding)
+    if (henc_emit(a, stream)) return hip_fail(d, hipGetLastError(), "henc_emit_kernel launch");
+    if (henc_count_ff(a, stream)) return hip_fail(d, hipGetLastError(), "henc_count_ff_kernel launch");
+    if (exclusive_scan_u32(a.ffcount, (uint64_t *)a.ffstart, chunks, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
+    if (henc_stuff(a, stream)) return hip_fail(d, hipGetLastError(), "henc_stuff_kernel launch");
+    HIP_TRY(d, hipMemcpyAsync(&readback[1], a.ffstart + chunks, 8, hipMemcpyDeviceToHost, stream));
+    return MIJPEG_OK;
+  }
+
+  // headers on the host, download of the entropy coded data straight into the stream, behind them
+  int stage_c()
+  {
+    HIP_TRY(d, hipStreamSynchronize(stream));
+    const size_t ecs = (size_t)a.plain_bytes + (size_t)readback[1] + (size_t)(a.n_intervals - 1) * 2;
+    head.clear();
+    enc_write_headers(head, *f, tabs, restart_interval);
+    if (assemble_stream(head, nullptr, ecs, &result, &result_size)) return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the stream");
+    const hipError_t e = hipMemcpyAsync(result + head.size(), a.out, ecs, hipMemcpyDeviceToHost, stream);
+    if (e != hipSuccess) { free(result); result = nullptr; return hip_fail(d, e, "download of the stream"); }
+    return MIJPEG_OK;
+  }
+
+  int finish(uint8_t **out_stream, size_t *out_size)
+  {
+    const hipError_t e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { free(result); result = nullptr; return hip_fail(d, e, "download of the stream"); }
+    *out_stream = result;
+    *out_size = result_size;
+    result = nullptr;
+    return MIJPEG_OK;
+  }
+};
+
+int device_entropy_code(mijpeg_decoder *d, const mijpeg_info &f, const int16_t *coef_dev, int restart_interval, int optimize,
+                               uint8_t **stream, size_t *size)
+{
+  HencJob job;
+  int rc = job.stage_a(d, f, coef_dev, restart_interval, optimize, 0, d->stream);
+  if (!rc) rc = job.stage_b();
+  if (!rc) rc = job.stage_c();
+  if (!rc) rc = job.finish(stream, size);
+  return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ragged encode: the planner
+// ------------------------------------------------------------------------------------------------
 constexpr uint32_t PASS_BLOCKS_DEFAULT = 1u << 24; // 2 GiB of coefficients at most
 constexpr uint32_t PASS_BLOCKS_MAX = 1u << 30;     // exclusive_scan_u32's reach
 
@@ -130,23 +336,13 @@ int plan_one(const mijpeg_encode_frame &e, mijpeg_info &f, uint32_t &blocks, uin
   if ((e.components != 1 && e.components != 3) || e.width < 1 || e.width > 65535 || e.height < 1 || e.height > 65535 ||
       e.restart_interval < 0 || e.restart_interval > 65535)
     return MIJPEG_ERR_INVALID_PARAMETER;
-  memset(&f, 0, sizeof(f));
-  f.width = e.width;
-  f.height = e.height;
-  f.components = e.components;
-  f.precision = 8;
-  f.ycbcr = e.components == 3 ? 1 : 0;
   int per_mcu = 0;
   for (int c = 0; c < e.components; c++) {
     if (e.hsamp[c] < 1 || e.hsamp[c] > 4 || e.vsamp[c] < 1 || e.vsamp[c] > 4) return MIJPEG_ERR_INVALID_PARAMETER;
-    f.hsamp[c] = e.hsamp[c];
-    f.vsamp[c] = e.vsamp[c];
-    f.quant_index[c] = 0; // (as mijpeg_encode_image_ex: the reference's frame header selects table 0 for every component)
     per_mcu += e.components > 1 ? e.hsamp[c] * e.vsamp[c] : 1;
   }
   if (per_mcu > 64) return MIJPEG_ERR_INVALID_PARAMETER;
-  mijpeg_quality_tables(e.quality, f.quant[0], f.quant[1]);
-  if (mijpeg_frame_layout(&f)) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (picture_info_of(e.width, e.height, e.components, e.hsamp, e.vsamp, e.quality, f)) return MIJPEG_ERR_INVALID_PARAMETER;
   const uint64_t mcus = (uint64_t)f.mcus_x * (uint64_t)f.mcus_y, nb = mcus * (uint64_t)per_mcu;
   if (nb >= PASS_BLOCKS_MAX) return MIJPEG_ERR_INVALID_PARAMETER;
   blocks = (uint32_t)nb;
@@ -191,16 +387,6 @@ int plan_list(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mi
 // ------------------------------------------------------------------------------------------------
 // ragged encode: one pass on the device
 // ------------------------------------------------------------------------------------------------
-struct Carver { // lays regions out in a buffer, 256-byte aligned
-  size_t at = 0;
-  size_t take(size_t bytes)
-  {
-    const size_t o = at;
-    at = (at + bytes + 255) & ~(size_t)255;
-    return o;
-  }
-};
-
 // launches of an exclusive_scan_u32 over n elements (hencode.hip)
 int scan_launches(uint32_t n)
 {
@@ -281,7 +467,7 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   const size_t o_bitpos = dv.take(((size_t)N + 1) * 8);
   const size_t o_ibytes = dv.take((size_t)I * 4);
   const size_t o_istart = dv.take(((size_t)I + 1) * 8);
-  const size_t o_scratch = dv.take((((size_t)N / 1024 + 8) * 2 + 8192) * 8);
+  const size_t o_scratch = dv.take(scan_scratch_bytes(N));
   const size_t o_coef = dv.take((size_t)coef_total * sizeof(int16_t));
   int rc = ensure_dev(d, (void **)&d->eragged_dev, &d->eragged_cap, dv.at);
   if (rc) return rc;
@@ -395,7 +581,7 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   const size_t q_ffc = ob.take(((size_t)chunks + 1) * 4);
   const size_t q_ffs = ob.take(((size_t)chunks + 1) * 8);
   const size_t q_out = ob.take(plain_total * 2 + (size_t)I * 2 + 16);
-  const size_t q_scratch = ob.take((((size_t)chunks / 1024 + 8) * 2 + 8192) * 8); // (the chunks may outnumber the blocks: a scratch of their own)
+  const size_t q_scratch = ob.take(scan_scratch_bytes((size_t)chunks)); // (the chunks may outnumber the blocks: a scratch of their own)
   rc = ensure_dev(d, (void **)&d->eragged_out_dev, &d->eragged_out_cap, ob.at);
   if (rc) return rc;
   uint8_t *od = d->eragged_out_dev;
@@ -429,15 +615,8 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
     const mijpeg_encode_ragged_item &it = items[p0 + p];
     const size_t at = (size_t)h_first_chunk[p] * HENC_STUFF_CHUNK + (size_t)g_ffs[p] + 2 * ((size_t)it.first_interval - p);
     const size_t ecs = (size_t)(g_istart[p + 1] - g_istart[p]) + (size_t)(g_ffs[p + 1] - g_ffs[p]) + 2 * ((size_t)it.intervals - 1);
-    const size_t hs = heads[p].size();
-    uint8_t *s = (uint8_t *)malloc(hs + ecs + 2);
-    if (!s) return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the stream");
-    memcpy(s, heads[p].data(), hs);
-    memcpy(s + hs, d->eragged_down + at, ecs);
-    s[hs + ecs] = 0xff;
-    s[hs + ecs + 1] = 0xd9;
-    streams[p0 + p] = s;
-    sizes[p0 + p] = hs + ecs + 2;
+    if (assemble_stream(heads[p], d->eragged_down + at, ecs, &streams[p0 + p], &sizes[p0 + p]))
+      return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the stream");
   }
   return MIJPEG_OK;
 }
@@ -521,6 +700,170 @@ int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, in
 } // namespace
 
 extern "C" {
+
+int mijpeg_frame_layout(mijpeg_info *f)
+try {
+  if (!f || f->width < 1 || f->height < 1 || f->width > 65535 || f->height > 65535 || f->components < 1 || f->components > MIJPEG_MAX_COMPONENTS)
+    return MIJPEG_ERR_INVALID_PARAMETER;
+  int hmax = 1, vmax = 1;
+  for (int c = 0; c < f->components; c++) {
+    if (f->hsamp[c] < 1 || f->hsamp[c] > 4 || f->vsamp[c] < 1 || f->vsamp[c] > 4 || f->quant_index[c] < 0 || f->quant_index[c] > 3)
+      return MIJPEG_ERR_INVALID_PARAMETER;
+    hmax = std::max(hmax, f->hsamp[c]);
+    vmax = std::max(vmax, f->vsamp[c]);
+  }
+  f->mcus_x = (f->width + 8 * hmax - 1) / (8 * hmax);
+  f->mcus_y = (f->height + 8 * vmax - 1) / (8 * vmax);
+  int64_t off = 0;
+  for (int c = 0; c < f->components; c++) {
+    if (hmax % f->hsamp[c] || vmax % f->vsamp[c]) return MIJPEG_ERR_INVALID_PARAMETER; // fractional subsampling factors
+    f->subx[c] = hmax / f->hsamp[c];
+    f->suby[c] = vmax / f->vsamp[c];
+    f->blocks_w[c] = f->mcus_x * f->hsamp[c];
+    f->blocks_h[c] = f->mcus_y * f->vsamp[c];
+    f->coef_offset[c] = off;
+    off += (int64_t)f->blocks_w[c] * f->blocks_h[c] * 64;
+  }
+  f->coef_count = off;
+  f->sample_bytes = 1;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(nullptr, "mijpeg_frame_layout"); }
+
+int mijpeg_launch_forward(const mijpeg_forward_batch *b, void *stream)
+try {
+  ForwardArgs a;
+  if (const int rc = forward_args_of(b, a)) return rc;
+  return launch_forward(a, (hipStream_t)stream) ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
+} catch (...) { return boundary_catch(nullptr, "mijpeg_launch_forward"); }
+
+void mijpeg_quality_tables(int quality, uint16_t luma[64], uint16_t chroma[64])
+try {
+  // ISO/IEC 10918-1 Annex K.1 / K.2 matrices, natural order
+  static const uint8_t K1[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
+                                 14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                                 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+  static const uint8_t K2[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+  quality = std::min(100, std::max(1, quality));
+  const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2; // quantization.cpp:296-299
+  for (int j = 0; j < 64; j++) {
+    luma[j] = (uint16_t)std::min(255, std::max(1, (K1[j] * scale + 50) / 100)); // :411, :443-466
+    chroma[j] = (uint16_t)std::min(255, std::max(1, (K2[j] * scale + 50) / 100));
+  }
+} catch (...) { (void)boundary_catch(nullptr, "mijpeg_quality_tables"); }
+
+int mijpeg_encode_batch_device(mijpeg_decoder *d, const mijpeg_forward_batch *b, int restart_interval, int optimize, uint8_t **streams, size_t *sizes)
+try {
+  if (!d || !b || !streams || !sizes || b->frames < 1 || restart_interval < 0 || restart_interval > 65535) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  HIP_TRY(d, hipSetDevice(d->device));
+  for (int f = 0; f < b->frames; f++) { streams[f] = nullptr; sizes[f] = 0; }
+  const auto t_begin = std::chrono::steady_clock::now();
+  int rc = mijpeg_launch_forward(b, d->stream);
+  if (rc) return set_error(d, rc, "forward kernel launch failed");
+  // frame f on stream f & 1 with buffer set f & 1: while the host waits for one frame's byte counts and download, the
+  // other frame's kernels run
+  if (!d->copy_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking));
+  HIP_TRY(d, hipEventRecord(d->ev0, d->stream));
+  HIP_TRY(d, hipStreamWaitEvent(d->copy_stream, d->ev0, 0));
+  hipStream_t st[2] = {d->stream, d->copy_stream};
+  HencJob jobs[2];
+  auto coef_of = [&](int f) { return b->coef_dev + (int64_t)f * b->coef_frame_stride; };
+  rc = jobs[0].stage_a(d, b->info, coef_of(0), restart_interval, optimize, 0, st[0]);
+  for (int f = 0; f < b->frames && !rc; f++) {
+    HencJob &cur = jobs[f & 1], &nxt = jobs[(f + 1) & 1];
+    if (f + 1 < b->frames) rc = nxt.stage_a(d, b->info, coef_of(f + 1), restart_interval, optimize, (f + 1) & 1, st[(f + 1) & 1]);
+    if (!rc) rc = cur.stage_b();
+    if (!rc) rc = cur.stage_c();
+    if (!rc) rc = cur.finish(&streams[f], &sizes[f]);
+  }
+  (void)hipStreamSynchronize(d->copy_stream);
+  (void)hipStreamSynchronize(d->stream);
+  if (rc)
+    for (int f = 0; f < b->frames; f++) { free(streams[f]); streams[f] = nullptr; sizes[f] = 0; }
+  d->timing[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); // mijpeg_last_timing: the whole call
+  d->timing[1] = d->timing[2] = d->timing[3] = 0;
+  return rc;
+} catch (...) { return boundary_catch(d, "mijpeg_encode_batch_device"); }
+
+int mijpeg_encode_image(mijpeg_decoder *d, const uint8_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
+                        int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint8_t **stream, size_t *size)
+try {
+  return mijpeg_encode_image_ex(d, pixels, width, height, components, row_stride, quality, hsamp, vsamp, restart_interval, optimize, 0, stream, size);
+} catch (...) { return boundary_catch(d, "mijpeg_encode_image"); }
+
+int mijpeg_encode_image_ex(mijpeg_decoder *d, const uint8_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
+                           int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint32_t flags,
+                           uint8_t **stream, size_t *size)
+try {
+  using clk = std::chrono::steady_clock;
+  const auto t_begin = clk::now();
+  if (!d || !pixels || !stream || !size || (components != 1 && components != 3) || row_stride < (int64_t)width * components)
+    return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  HIP_TRY(d, hipSetDevice(d->device));
+  mijpeg_forward_batch b;
+  memset(&b, 0, sizeof(b));
+  mijpeg_info &f = b.info;
+  int rc = picture_info_of(width, height, components, hsamp, vsamp, quality, f);
+  if (rc) return set_error(d, rc, "invalid frame layout for encoding");
+  const size_t px_bytes = (size_t)row_stride * (size_t)height, coef_bytes = (size_t)f.coef_count * sizeof(int16_t);
+  rc = ensure_dev(d, (void **)&d->enc_dev, &d->enc_cap, px_bytes + 256 + coef_bytes);
+  if (rc) return rc;
+  int16_t *coef_dev = (int16_t *)(d->enc_dev + ((px_bytes + 255) & ~(size_t)255));
+  // pinned staging: [pixels][coefficients].  The picture goes up in bands, each gathered into pinned memory by the pool
+  // threads while the DMA of the previous band runs; the coefficients come down into pinned memory the coder reads.
+  const size_t stage_bytes = ((px_bytes + 255) & ~(size_t)255) + coef_bytes;
+  rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, stage_bytes);
+  if (rc) return rc;
+  int16_t *coef_host = (int16_t *)(d->stage_host + ((px_bytes + 255) & ~(size_t)255));
+  {
+    const size_t band = std::max<size_t>((size_t)8 << 20, (px_bytes + 7) / 8) & ~(size_t)255;
+    for (size_t b0 = 0; b0 < px_bytes; b0 += band) {
+      const size_t len = std::min(band, px_bytes - b0);
+      const size_t pieces = (len + ((size_t)1 << 20) - 1) >> 20;
+      const int workers = (int)std::min<size_t>(pieces, (size_t)std::min(default_threads(), 16));
+      parallel_for(workers, [&](int w) {
+        for (size_t k = (size_t)w; k < pieces; k += (size_t)workers) {
+          const size_t o = b0 + (k << 20), n = std::min<size_t>((size_t)1 << 20, b0 + len - o);
+          memcpy(d->stage_host + o, pixels + o, n);
+        }
+      });
+      HIP_TRY(d, hipMemcpyAsync(d->enc_dev + b0, d->stage_host + b0, len, hipMemcpyHostToDevice, d->stream));
+    }
+  }
+  b.pixels_dev = d->enc_dev;
+  b.pixel_row_stride = row_stride;
+  b.pixel_frame_stride = (int64_t)px_bytes;
+  b.coef_dev = coef_dev;
+  b.coef_frame_stride = f.coef_count;
+  b.frames = 1;
+  const auto t_up = clk::now(); // uploads enqueued (the gathering is synchronous)
+  rc = mijpeg_launch_forward(&b, d->stream);
+  if (rc) return set_error(d, rc, "forward kernel launch failed");
+  static const bool env_host_coder = getenv("MIJPEG_ENTROPY_CODER") && !strcmp(getenv("MIJPEG_ENTROPY_CODER"), "host");
+  if (!(flags & MIJPEG_ENCODE_HOST_CODER) && !env_host_coder) {
+    if (restart_interval < 0 || restart_interval > 65535) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "invalid restart interval");
+    rc = device_entropy_code(d, f, coef_dev, restart_interval, optimize, stream, size);
+    d->timing[0] = std::chrono::duration<double>(t_up - t_begin).count();
+    d->timing[1] = std::chrono::duration<double>(clk::now() - t_up).count(); // kernels, entropy coder and download of the stream
+    d->timing[2] = d->timing[3] = 0;
+    if (rc != MIJPEG_ERR_NOT_AVAILABLE) return rc;
+  }
+  HIP_TRY(d, hipStreamSynchronize(d->stream));
+  const auto t_kernel = clk::now();
+  HIP_TRY(d, hipMemcpyAsync(coef_host, coef_dev, coef_bytes, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(d, hipStreamSynchronize(d->stream));
+  const auto t_down = clk::now();
+  rc = mijpeg_encode_coefficients(&f, coef_host, restart_interval, optimize, 0, stream, size);
+  // mijpeg_last_timing: gather + upload, kernels (incl. the rest of the upload), download, entropy coder
+  d->timing[0] = std::chrono::duration<double>(t_up - t_begin).count();
+  d->timing[1] = std::chrono::duration<double>(t_kernel - t_up).count();
+  d->timing[2] = std::chrono::duration<double>(t_down - t_kernel).count();
+  d->timing[3] = std::chrono::duration<double>(clk::now() - t_down).count();
+  if (rc) return set_error(d, rc, "entropy coding failed");
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_encode_image_ex"); }
 
 int mijpeg_encode_ragged_plan(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,
                               mijpeg_encode_ragged_totals *totals)

@@ -1,5 +1,5 @@
 // encoder.hpp -- Huffman code tables and header writer shared by the host entropy coder (encoder.cpp) and the host side of
-// the device entropy coder (capi.cpp / hencode.hip); internal to libmijpeg.so.
+// the device entropy coder (encode_device.cpp / hencode.hip); internal to libmijpeg.so.
 #ifndef MIJ_ENCODER_HPP
 #define MIJ_ENCODER_HPP
 #include <stdint.h>

@@ -137,8 +137,8 @@ struct GenericArgs {
   int32_t tile_w, tile_h, tiles_x, tiles_y;
 };
 
-// The reconstruction capi.cpp's planner (plan_reconstruct) chose for a batch.  The kernels up to FUSEDXTW420 take a Fused420Args
-// block (launch_fused); the others the plane description of GenericArgs (launch_fused_flat, launch_fused_tile, launch_generic).
+// The reconstruction the planner (plan_reconstruct, reconstruct_device.cpp) chose for a batch.  The kernels up to FUSEDXTW420 take a
+// Fused420Args block (launch_fused); the others the plane description of GenericArgs (launch_fused_flat, launch_fused_tile, launch_generic).
 enum class Recon : uint8_t {
   FUSED420P, FUSED420, FUSED422, FUSED440, FUSED411, FUSED444, FUSED1, // 8 bit
   FUSED420_12, FUSED422_12, FUSED444_12, FUSED1_12,                    // 12 bit, 16-bit samples out

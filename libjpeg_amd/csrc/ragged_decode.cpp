@@ -1,0 +1,369 @@
+// ragged_decode.cpp -- ragged batches: streams of any shapes in one device pass (include/mijpeg.h): the planner, the
+// decode (a Huffman launch per layout group, the single-image route for the rest) and the reconstruction.  Private to libmijpeg.so.
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+
+#include "reconstruct.hpp"
+
+using namespace mij;
+
+// The layout group of a frame description, or -1: 8-bit plain sequential frames in the four layouts whose fused kernels have a
+// ragged flavour, every plane inside the kernels' 32-bit offsets
+static int ragged_group_of(const mijpeg_info &f)
+{
+  if (f.precision != 8 || f.xt || f.progressive || f.coef_wide || f.dnl || f.width < 1 || f.height < 1 || f.coef_count < 64) return -1;
+  if (f.components != 1 && f.components != 3) return -1;
+  for (int c = 0; c < f.components; c++)
+    if ((unsigned)f.quant_index[c] >= 4 || f.blocks_w[c] < 1 || f.blocks_h[c] < 1 || (uint64_t)f.blocks_w[c] * (uint64_t)f.blocks_h[c] * 128u > 0xffffffffull) return -1;
+  switch (sampling_of(f)) {
+  case Sampling::S420: return MIJPEG_RAGGED_420;
+  case Sampling::S422: return MIJPEG_RAGGED_422;
+  case Sampling::S444: return MIJPEG_RAGGED_444;
+  case Sampling::GREY: return f.hsamp[0] == 1 && f.vsamp[0] == 1 ? MIJPEG_RAGGED_GREY : -1; // (sampling factors on a single component: MCU padding nobody decodes)
+  default: return -1;
+  }
+}
+
+// Grouping, workgroup ranges and coefficient bases of n frames; excluded[i] != 0 (optional) keeps frame i out of the groups
+static int ragged_plan(const mijpeg_info *infos, int n, const char *excluded, int32_t *group, mijpeg_ragged_frame *frames, int32_t *group_workgroups, int64_t *coef_total)
+{
+  int64_t base = 0;
+  uint64_t grid[MIJPEG_RAGGED_GROUPS] = {0, 0, 0, 0};
+  for (int i = 0; i < n; i++) {
+    const mijpeg_info &f = infos[i];
+    mijpeg_ragged_frame &r = frames[i];
+    memset(&r, 0, sizeof(r));
+    int g = excluded && excluded[i] ? -1 : ragged_group_of(f);
+    if (g >= 0) fused_geometry(f, sampling_of(f), r); // (what the uniform launches of the same kernels get)
+    const uint64_t tiles = (uint64_t)r.tiles_x * (uint64_t)r.tiles_y;
+    if (g >= 0 && grid[g] + tiles > 0x7fffffffull) { // (a grid holds 2^31 - 1 workgroups)
+      g = -1;
+      memset(&r, 0, sizeof(r));
+    }
+    group[i] = g;
+    if (g < 0) continue;
+    r.coef_base = base;
+    base += f.coef_count;
+    r.first_workgroup = (int32_t)grid[g];
+    grid[g] += tiles;
+  }
+  for (int g = 0; g < MIJPEG_RAGGED_GROUPS; g++) group_workgroups[g] = (int32_t)grid[g];
+  *coef_total = base;
+  return MIJPEG_OK;
+}
+
+// The descriptor table of a launch of m frames, `at` bytes into the upload: [frames][first workgroups, m + 1 of them, padded to 16
+// bytes][deltas << 4, per frame 4 x 64]: where its parts begin and where it ends
+struct DescTable {
+  size_t frames, first, deltas, end;
+  DescTable(size_t at, size_t m) : frames(at), first(frames + m * sizeof(RaggedFrame)), deltas(first + ((m + 1) * 4 + 15) / 16 * 16), end(deltas + m * 4 * 64 * sizeof(int32_t)) {}
+};
+
+// Image i through the single-image route, on a decoder object of its own (kept from call to call)
+static void ragged_single_image(mijpeg_decoder *d, int i, int k, const uint8_t *data, size_t size, int min_intervals)
+{
+  mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+  r.group = -1;
+  r.child = nullptr;
+  if ((size_t)k >= d->ragged_children.size()) {
+    mijpeg_decoder *c = nullptr;
+    const int rc = mijpeg_create(&c, d->device);
+    if (rc) { r.status = rc; return; }
+    d->ragged_children.push_back(c);
+  }
+  mijpeg_decoder *c = d->ragged_children[(size_t)k];
+  r.child = c;
+  if (data) c->own_input.assign(data, data + size);
+  else c->own_input.clear();
+  int rc = mijpeg_set_input(c, data ? c->own_input.data() : nullptr, data ? size : 0);
+  if (!rc) {
+    rc = mijpeg_decode_coefficients_device(c, min_intervals);
+    if (rc == MIJPEG_ERR_NOT_AVAILABLE) rc = mijpeg_decode_coefficients(c, 0);
+  }
+  if (!rc) rc = mijpeg_get_info(c, &r.info);
+  r.status = rc;
+}
+
+extern "C" {
+
+int mijpeg_ragged_plan(const mijpeg_info *infos, int n, int32_t *group, mijpeg_ragged_frame *frames, int32_t group_workgroups[MIJPEG_RAGGED_GROUPS], int64_t *coef_total)
+try {
+  if (!infos || !group || !frames || !group_workgroups || !coef_total || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  return ragged_plan(infos, n, nullptr, group, frames, group_workgroups, coef_total);
+} catch (...) { return boundary_catch(nullptr, "mijpeg_ragged_plan"); }
+
+int mijpeg_decode_ragged_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status)
+try {
+  if (!d || !streams || !sizes || !status || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  HIP_TRY(d, hipSetDevice(d->device));
+  if (d->spec_active) (void)settle_speculation(d); // (an unvalidated batch of the uniform calls is abandoned here)
+  if (const int prc = settle_pending(d)) return prc;
+  d->batch_frames = 0;
+  d->ragged_n = 0;
+  d->img_valid = d->model_valid = d->uploaded = d->decoded = false;
+  d->ragged_stats = mijpeg_ragged_stats{};
+  if (d->batch_hosts.size() < (size_t)n) d->batch_hosts.resize((size_t)n);
+  for (auto &h : d->batch_hosts)
+    if (!h) h.reset(new HostDecoder());
+  d->ragged.assign((size_t)n, mijpeg_decoder::RaggedImage{});
+  // headers and restart markers of all streams, one stream per worker
+  std::vector<int> rcs((size_t)n, 0);
+  const int workers = std::min(n, default_threads());
+  parallel_for(workers, [&](int w) {
+    for (int i = w; i < n; i += workers) rcs[(size_t)i] = streams[i] && sizes[i] ? d->batch_hosts[(size_t)i]->parse(streams[i], sizes[i], false) : MIJPEG_ERR_STREAM_EMPTY;
+  });
+  // what the batch kernels cover goes into the layout groups
+  std::vector<char> excluded((size_t)n, 0);
+  std::vector<mijpeg_info> infos((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const char *why = rcs[(size_t)i] ? "the stream does not parse as the batch decoder reads it" : ragged_entropy_obstacle(*d->batch_hosts[(size_t)i], sizes[i]);
+    excluded[(size_t)i] = why != nullptr;
+    if (why) d->ragged[(size_t)i].why_single = why;
+    if (excluded[(size_t)i]) memset(&infos[(size_t)i], 0, sizeof(mijpeg_info));
+    else infos[(size_t)i] = d->batch_hosts[(size_t)i]->info;
+  }
+  std::vector<int32_t> group((size_t)n);
+  std::vector<mijpeg_ragged_frame> frames((size_t)n);
+  int32_t grids[MIJPEG_RAGGED_GROUPS];
+  int64_t coef_total = 0;
+  ragged_plan(infos.data(), n, excluded.data(), group.data(), frames.data(), grids, &coef_total);
+  for (int i = 0; i < n; i++)
+    if (group[(size_t)i] < 0 && !excluded[(size_t)i]) d->ragged[(size_t)i].why_single = "no layout group for this frame: 8-bit sequential 4:2:0, 4:2:2, 4:4:4 and grey frames have one";
+  if (coef_total > 0) {
+    const int rc = ensure_coef_store(d, (size_t)coef_total, false);
+    if (rc) return rc;
+  }
+  // one launch of the Huffman kernel per group (the walk in front of it where streams have no restart markers)
+  for (int g = 0; g < MIJPEG_RAGGED_GROUPS; g++) {
+    std::vector<int> members;
+    for (int i = 0; i < n; i++)
+      if (group[(size_t)i] == g) members.push_back(i);
+    if (members.empty()) continue;
+    const size_t m = members.size();
+    std::vector<HostDecoder *> hosts(m);
+    std::vector<const uint8_t *> datas(m);
+    std::vector<size_t> gsizes(m);
+    std::vector<int64_t> bases(m);
+    std::vector<int> verdict(m, 1);
+    for (size_t k = 0; k < m; k++) {
+      const int i = members[k];
+      hosts[k] = d->batch_hosts[(size_t)i].get();
+      datas[k] = streams[i];
+      gsizes[k] = sizes[i];
+      bases[k] = frames[(size_t)i].coef_base;
+    }
+    int scan_launches = 0, walk_launches = 0;
+    const RaggedEntropy re{bases.data(), verdict.data(), &scan_launches, &walk_launches};
+    const int rc = device_entropy_batch(d, hosts.data(), datas.data(), gsizes.data(), (int)m, 1, d->coef_dev, 0, false, false, &re);
+    d->ragged_stats.entropy_launches += scan_launches;
+    d->ragged_stats.walk_launches += walk_launches;
+    if (rc && rc != MIJPEG_ERR_NOT_AVAILABLE) return rc; // (the device, memory: not a verdict on a stream)
+    // What is left to refuse a whole group once every member passed ragged_entropy_obstacle: its device walk did not settle
+    // or has more subsequences than its prefix sums hold, the launch outgrew 32-bit offsets.  Every member then takes the
+    // single-image route, with the launch's message as the reason (mijpeg_ragged_route).
+    const std::string group_refusal = rc ? "the layout group's launch was refused: " + d->err_msg : std::string();
+    for (size_t k = 0; k < m; k++) {
+      const int i = members[k];
+      if (rc || verdict[k]) { // damaged: the single-image route decides
+        group[(size_t)i] = -1;
+        d->ragged[(size_t)i].why_single = rc ? group_refusal : std::string("the device decoder found the entropy coded data damaged");
+        continue;
+      }
+      mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+      r.group = g;
+      r.info = hosts[k]->info;
+      r.coef_base = frames[(size_t)i].coef_base;
+      d->ragged_stats.ragged++;
+    }
+  }
+  // everything else: the single-image route, stream by stream
+  int children = 0;
+  for (int i = 0; i < n; i++) {
+    if (group[(size_t)i] >= 0) continue;
+    ragged_single_image(d, i, children++, streams[i], sizes[i], min_intervals);
+    d->ragged_stats.fallbacks++;
+    if (d->ragged[(size_t)i].status) d->ragged_stats.errors++;
+  }
+  for (int i = 0; i < n; i++) status[i] = d->ragged[(size_t)i].status;
+  d->ragged_stats.images = n;
+  d->ragged_n = n;
+  d->err_code = 0;
+  d->err_msg.clear();
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_decode_ragged_device"); }
+
+int mijpeg_ragged_info(mijpeg_decoder *d, int i, mijpeg_info *info)
+try {
+  if (!d || !info || i < 0) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (i >= d->ragged_n) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no such image: call mijpeg_decode_ragged_device first");
+  const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+  if (r.status) {
+    const char *msg = nullptr;
+    if (r.child) (void)mijpeg_last_error(r.child, &msg);
+    return set_error(d, r.status, msg ? msg : "the stream could not be decoded");
+  }
+  *info = r.info;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_ragged_info"); }
+
+int mijpeg_ragged_warning(mijpeg_decoder *d, int i, const char **message)
+try {
+  if (message) *message = nullptr;
+  if (!d || i < 0 || i >= d->ragged_n) return 0;
+  const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+  return r.child && !r.status ? mijpeg_last_warning(r.child, message) : 0;
+} catch (...) { return boundary_catch(d, "mijpeg_ragged_warning"); }
+
+int mijpeg_ragged_route(mijpeg_decoder *d, int i, const char **why)
+try {
+  if (why) *why = nullptr;
+  if (!d || i < 0) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (i >= d->ragged_n) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no such image: call mijpeg_decode_ragged_device first");
+  const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+  if (r.group >= 0) return 0;
+  if (why) *why = r.why_single.c_str();
+  return 1;
+} catch (...) { return boundary_catch(d, "mijpeg_ragged_route"); }
+
+int mijpeg_ragged_get_stats(mijpeg_decoder *d, mijpeg_ragged_stats *out)
+try {
+  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
+  *out = d->ragged_stats;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_ragged_get_stats"); }
+
+int mijpeg_reconstruct_ragged_device(mijpeg_decoder *d, void *const *dst_device, const int64_t *row_strides, uint32_t flags, int sync)
+try {
+  if (!d || !dst_device || !row_strides) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  if (d->ragged_n < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded ragged batch: call mijpeg_decode_ragged_device first");
+  HIP_TRY(d, hipSetDevice(d->device));
+  const int n = d->ragged_n;
+  flags &= ~(uint32_t)(MIJPEG_FLAG_DEVICE_OUTPUT | MIJPEG_FLAG_NO_UPSAMPLING | MIJPEG_FLAG_SPECULATIVE);
+  d->ragged_stats.recon_launches = d->ragged_stats.recon_single = 0;
+  // Which kernel every group image takes, from ITS range check: images of a group that agree on kernel and arithmetic flavour
+  // share a launch -- one outlier beyond the fast gates runs the SAFE flavour alone instead of taking the group along.
+  // (quant_dev is only tested by the planner: the ragged launches read per-frame tables.)
+  static const uint16_t per_frame_tables = 0;
+  auto describe = [&](int i, bool own_tables) {
+    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    mijpeg_batch b = batch_of(r.info, d->coef_dev + r.coef_base, dst_device[i], row_strides[i], 0, 1, flags);
+    b.quant_dev = own_tables ? &per_frame_tables : nullptr;
+    return b;
+  };
+  struct Launch { ReconPlan p; int group; std::vector<int> members; };
+  std::vector<Launch> launches;
+  std::vector<int> singles;
+  for (int i = 0; i < n; i++) {
+    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    if (r.status || r.group < 0 || !dst_device[i]) continue;
+    const mijpeg_batch b = describe(i, true);
+    const ReconPlan p = plan_reconstruct(&b);
+    const bool has_flavour = (r.group == MIJPEG_RAGGED_420 && (p.kernel == Recon::FUSED420P || p.kernel == Recon::FUSED420)) ||
+                             (r.group == MIJPEG_RAGGED_422 && p.kernel == Recon::FUSED422) || (r.group == MIJPEG_RAGGED_444 && p.kernel == Recon::FUSED444) ||
+                             (r.group == MIJPEG_RAGGED_GREY && p.kernel == Recon::FUSED1);
+    if (!has_flavour) { singles.push_back(i); continue; }
+    size_t l = 0;
+    while (l < launches.size() && !(launches[l].group == r.group && launches[l].p.kernel == p.kernel && launches[l].p.fast == p.fast && launches[l].p.wide == p.wide)) l++;
+    if (l == launches.size()) launches.push_back(Launch{p, r.group, {}});
+    launches[l].members.push_back(i);
+  }
+  // descriptor tables of all launches in one upload, one DescTable behind the other
+  if (!launches.empty()) {
+    std::vector<DescTable> tables;
+    for (const Launch &l : launches) tables.emplace_back(tables.empty() ? 0 : tables.back().end, l.members.size());
+    const size_t bytes = tables.back().end;
+    int rc = ensure_dev(d, (void **)&d->ragged_desc_dev, &d->ragged_desc_cap, bytes);
+    if (rc) return rc;
+    if (d->ragged_upload_pending) { // (the pinned copy travels asynchronously: the last call's must have left)
+      HIP_TRY(d, hipEventSynchronize(d->ragged_uploaded));
+      d->ragged_upload_pending = false;
+    }
+    if ((rc = ensure_pinned(d, &d->ragged_desc_host, &d->ragged_desc_host_cap, bytes))) return rc;
+    std::vector<uint32_t> grid(launches.size());
+    for (size_t l = 0; l < launches.size(); l++) {
+      const std::vector<int> &mem = launches[l].members;
+      const size_t m = mem.size();
+      RaggedFrame *fr = (RaggedFrame *)(d->ragged_desc_host + tables[l].frames);
+      uint32_t *first = (uint32_t *)(d->ragged_desc_host + tables[l].first);
+      int32_t *q = (int32_t *)(d->ragged_desc_host + tables[l].deltas);
+      // the launch's own frames through the planner: their first workgroups, the grid
+      std::vector<mijpeg_info> infos(m);
+      std::vector<int32_t> grp(m);
+      std::vector<mijpeg_ragged_frame> pf(m);
+      int32_t grids[MIJPEG_RAGGED_GROUPS];
+      int64_t unused = 0;
+      for (size_t k = 0; k < m; k++) infos[k] = d->ragged[(size_t)mem[k]].info;
+      ragged_plan(infos.data(), (int)m, nullptr, grp.data(), pf.data(), grids, &unused);
+      for (size_t k = 0; k < m; k++) {
+        const int i = mem[k];
+        const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+        if (grp[k] != launches[l].group) return set_error(d, MIJPEG_ERR_PHASE_ERROR, "ragged planner disagrees with itself");
+        RaggedFrame &x = fr[k];
+        memset(&x, 0, sizeof(x));
+        fused_geometry(r.info, launches[l].p.sampling, x);
+        x.coef_base = r.coef_base;
+        x.out = (uint8_t *)dst_device[i];
+        x.row_stride = row_strides[i];
+        x.qframe = (int32_t)k;
+        first[k] = (uint32_t)pf[k].first_workgroup;
+        for (int c = 0; c < 4; c++)
+          for (int z = 0; z < 64; z++) q[(k * 4 + (size_t)c) * 64 + (size_t)z] = c < r.info.components ? (int32_t)r.info.quant[r.info.quant_index[c]][z] << 4 : 16;
+      }
+      grid[l] = (uint32_t)grids[launches[l].group];
+      first[m] = grid[l];
+    }
+    HIP_TRY(d, hipMemcpyAsync(d->ragged_desc_dev, d->ragged_desc_host, bytes, hipMemcpyHostToDevice, d->stream));
+    if (!d->ragged_uploaded) HIP_TRY(d, hipEventCreateWithFlags(&d->ragged_uploaded, hipEventDisableTiming));
+    HIP_TRY(d, hipEventRecord(d->ragged_uploaded, d->stream));
+    d->ragged_upload_pending = true;
+    for (size_t l = 0; l < launches.size(); l++) {
+      Fused420Args a;
+      memset(&a, 0, sizeof(a));
+      a.coef = d->coef_dev;
+      a.frames = (int32_t)launches[l].members.size();
+      a.ragged = (const RaggedFrame *)(d->ragged_desc_dev + tables[l].frames);
+      a.ragged_first = (const uint32_t *)(d->ragged_desc_dev + tables[l].first);
+      a.qdev = (const int32_t *)(d->ragged_desc_dev + tables[l].deltas);
+      if (launch_fused_ragged(launches[l].p, a, grid[l], d->stream))
+        return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+      d->ragged_stats.recon_launches++;
+    }
+  }
+  // One image whose reconstruction fails does not stop the others, whichever route it takes: the call works through the list
+  // and then returns the first such code, with a message that names the image.  (A launch of a whole group that fails, or
+  // memory that cannot be had for the tables, is the device's failure and ends the call at once; what was enqueued stays
+  // ordered on the object's stream, and the next call waits for the descriptor upload as usual.)
+  int failed = MIJPEG_OK;
+  std::string failed_msg;
+  // group images no ragged flavour fits (ranges beyond the fused kernels' gates, no colour transformation, ...): the existing kernels
+  for (int i : singles) {
+    mijpeg_batch b = describe(i, false);
+    const int rc = reconstruct_on(d, b, nullptr, nullptr); // (no noun: this call reports the first failure, below)
+    if (!rc) d->ragged_stats.recon_single++;
+    else if (!failed) {
+      failed = rc;
+      failed_msg = "image " + std::to_string(i) + " of the ragged batch was not reconstructed";
+    }
+  }
+  // images of the single-image route, on their own objects (which wait for their kernels themselves)
+  for (int i = 0; i < n; i++) {
+    mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    if (!r.child || r.status || !dst_device[i]) continue;
+    const int rc = mijpeg_reconstruct_device(r.child, dst_device[i], row_strides[i], flags, 1);
+    if (rc && !failed) {
+      const char *msg = nullptr;
+      (void)mijpeg_last_error(r.child, &msg);
+      failed = rc;
+      failed_msg = "image " + std::to_string(i) + " of the ragged batch was not reconstructed: " + (msg ? msg : "");
+    }
+  }
+  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  if (failed) return set_error(d, failed, failed_msg);
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_device"); }
+
+} // extern "C"

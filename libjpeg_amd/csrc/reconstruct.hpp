@@ -1,0 +1,58 @@
+// reconstruct.hpp -- what reconstruct_device.cpp (kernel selection, workspace and launch of the reconstruction) shares with the
+// decoder object's entry points in capi.cpp and ragged_decode.cpp.  Private to libmijpeg.so.
+#pragma once
+#include "decoder.hpp"
+#include "kernels.hpp"
+
+// The range gates of the kernel selection (plan_reconstruct): a kernel or flavour is admitted where mijpeg_info::range_max
+// (sum |c| q of a block) is below its gate
+constexpr int32_t GATE_DOT2 = 1477;          // fused420p_kernel's second pass on v_dot2 (idct_columns_dot2: sum |c| q <= 1476)
+constexpr int32_t GATE_PACKED = 2047;        // chroma filtered as int16 pairs (packed 4:2:0, 4:2:2, 4:4:0)
+constexpr int32_t GATE_INT16_SAMPLES = 7600; // int16 sample planes of the kernel pair; int16 luma of fusedxtw420_kernel<true>
+constexpr int32_t GATE_FUSED8 = 8190;        // chroma of the 8-bit fused 4:2:2 / 4:4:0 / 4:1:1 / 4:4:4 kernels, fused1_kernel
+constexpr int32_t GATE_XT_LEGACY = 16384;    // legacy frame of the JPEG XT kernels (fused, and the merge's 32-bit colour stage)
+constexpr int32_t GATE_12_CHROMA = 45056;    // 12-bit fused kernels: chroma (every component of fused_tile_kernel's fast12)
+constexpr int32_t GATE_12_LUMA = 49152;      // 12-bit fused kernels: luma
+constexpr int32_t GATE_XT_RESIDUAL = 65536;  // residual frame of the fused JPEG XT kernels
+constexpr int32_t RANGE_GATES[] = { // (ascending)
+    GATE_DOT2, GATE_PACKED, GATE_INT16_SAMPLES, GATE_FUSED8, GATE_XT_LEGACY, GATE_12_CHROMA, GATE_12_LUMA, GATE_XT_RESIDUAL};
+
+mij::Sampling sampling_of(const mijpeg_info &f);
+// Which kernel reconstructs a batch, and in which flavour; what it needs as workspace
+mij::ReconPlan plan_reconstruct(const mijpeg_batch *b);
+size_t workspace_need(const mijpeg_batch *b, const mij::ReconPlan &p);
+
+// A frame as the fused kernels address it, into g (Fused420Args, RaggedFrame, the planner's mijpeg_ragged_frame): its size, the
+// luma and chroma planes in blocks and where they start in the coefficient store, valid chroma samples, the grid of 128 x 128 tiles
+template <class Frame> void fused_geometry(const mijpeg_info &f, mij::Sampling s, Frame &g)
+{
+  const bool colour = f.components > 1;
+  g.width = f.width; g.height = f.height;
+  g.off_y = f.coef_offset[0]; g.off_cb = colour ? f.coef_offset[1] : 0; g.off_cr = colour ? f.coef_offset[2] : 0;
+  g.bw_y = f.blocks_w[0]; g.bh_y = f.blocks_h[0]; g.bw_c = colour ? f.blocks_w[1] : 0; g.bh_c = colour ? f.blocks_h[1] : 0;
+  const bool full_height = s == mij::Sampling::S422 || s == mij::Sampling::S411; // (chroma subsampled horizontally only)
+  g.cw = s == mij::Sampling::S440 ? f.width : s == mij::Sampling::S411 ? (f.width + 3) / 4 : (f.width + 1) / 2;
+  g.ch = full_height ? f.height : (f.height + 1) / 2;
+  // DNL frames: the reference's upsamplers never learnt the height (upsampling/upsamplerbase.cpp:61-75), their line buffers
+  // have no bottom edge: below the last chroma line comes what the block rows hold (the padding of the last one, then the
+  // MCU row the first scan created behind the picture: the store has it, include/mijpeg.h) instead of that line again
+  if (f.dnl && !full_height && colour) g.ch = g.bh_c * 8;
+  g.tiles_x = (f.width + 127) / 128; g.tiles_y = (f.height + 127) / 128;
+}
+
+// What a rectangle request that does not show the plain picture adds to a launch (request_model.hpp; GenericArgs::rowmap ...)
+struct RequestExtra {
+  const int32_t *rowmap_dev;
+  int32_t rowmap_stride;
+  int32_t corner_x, corner_y, y_base, y_count;
+  int32_t wstart[mij::MAXP], wlimit[mij::MAXP]; // per plane (JPEG XT: legacy planes, then residual planes)
+  int32_t ycc;
+};
+int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const RequestExtra *rx);
+
+// `frames` frames of `info`, their coefficient stores one behind the other from coef_dev, to out_dev (strides in bytes)
+mijpeg_batch batch_of(const mijpeg_info &info, const int16_t *coef_dev, void *out_dev, int64_t row_stride, int64_t frame_stride, int frames, uint32_t flags);
+
+// The batch on the object's stream: sizes the workspace, grows d->ws_dev, launches, sets the object's error ("... not available
+// for this <noun>"; no noun: the code alone, the caller reports)
+int reconstruct_on(mijpeg_decoder *d, mijpeg_batch &b, const RequestExtra *rx, const char *noun);

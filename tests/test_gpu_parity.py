@@ -1555,12 +1555,12 @@ KERNEL_12 = {"420": "fused420_kernel<12>", "444": "fused444_12_kernel", "422": "
 
 def _k12(name):
     """The 12-bit kernels come in two flavours of the colour stage ("/narrow": every channel's sum in 32 bits, narrow12_colour in
-    capi.cpp); the kernel is the part in front."""
+    reconstruct_device.cpp); the kernel is the part in front."""
     return name.split("/")[0]
 
 
 def _narrow12_admits(ry, rc):
-    """capi.cpp narrow12_colour, restated: (|y'| + 32776) * 8192 + 14516 |c| < 2^31 with |y'| <= 4.02 ry + 2, |c| <= 4.02 rc + 4"""
+    """reconstruct_device.cpp narrow12_colour, restated: (|y'| + 32776) * 8192 + 14516 |c| < 2^31 with |y'| <= 4.02 ry + 2, |c| <= 4.02 rc + 4"""
     return ((402 * ry + 99) // 100 + 2 + 32776) * 8192 + 14516 * ((402 * rc + 99) // 100 + 4) < 2 ** 31
 
 

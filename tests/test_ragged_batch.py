@@ -77,6 +77,9 @@ def test_planner_groups_ranges_and_bases():
             assert fr.first_workgroup == at, (g, i)
             at += fr.tiles_x * fr.tiles_y
             assert (fr.width, fr.height, fr.bw_y, fr.bh_y) == (f.width, f.height, f.blocks_w[0], f.blocks_h[0])
+            # valid chroma samples, as the uniform launches of the same kernels have them: only 4:2:2 keeps the full height
+            assert fr.cw == (f.width + 1) // 2
+            assert fr.ch == (f.height if g == api.RAGGED_GROUPS.index("422") else (f.height + 1) // 2)
             if f.components == 3:
                 assert (fr.bw_c, fr.bh_c, fr.off_cb, fr.off_cr) == (f.blocks_w[1], f.blocks_h[1], f.coef_offset[1], f.coef_offset[2])
         assert grids[g] == at
