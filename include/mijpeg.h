@@ -69,7 +69,7 @@ typedef struct mijpeg_decoder mijpeg_decoder;
 typedef struct mijpeg_info {
   int32_t width, height;     /* JPGTAG_IMAGE_WIDTH / HEIGHT                                     */
   int32_t components;        /* JPGTAG_IMAGE_DEPTH                                              */
-  int32_t precision;         /* JPGTAG_IMAGE_PRECISION (8 on this path)                         */
+  int32_t precision;         /* JPGTAG_IMAGE_PRECISION: 8 or 12 (16 for JPEG XT)                */
   int32_t hsamp[MIJPEG_MAX_COMPONENTS], vsamp[MIJPEG_MAX_COMPONENTS]; /* SOF Hi, Vi              */
   int32_t subx[MIJPEG_MAX_COMPONENTS], suby[MIJPEG_MAX_COMPONENTS];   /* JPGTAG_IMAGE_SUBX/SUBY  */
   int32_t quant_index[MIJPEG_MAX_COMPONENTS];                         /* SOF Tqi                 */
@@ -522,14 +522,17 @@ const char *mijpeg_kernel_name(const mijpeg_batch *batch);
  * downsampling (upsampling/downsampler.cpp:70-139), forward DCT + quantisation (dct/idct.cpp:114-222), for frames
  * resident in HBM.  Entropy coding and marker writing are not part of it. */
 
-/* Completes *info from width, height, components (1 or 3), precision (8), hsamp[], vsamp[], quant_index[] and quant[][]:
- * MCU grid, subsampling factors, plane sizes, coef_offset[] and coef_count, as a frame header with these values
- * would produce (marker/frame.cpp, marker/component.cpp).  Returns MIJPEG_OK or MIJPEG_ERR_INVALID_PARAMETER. */
+/* Completes *info from width, height, components (1 or 3), precision (8, or 12: an extended sequential frame), hsamp[], vsamp[],
+ * quant_index[] and quant[][]: MCU grid, subsampling factors, plane sizes, coef_offset[] and coef_count, as a frame header with
+ * these values would produce (marker/frame.cpp, marker/component.cpp).  Returns MIJPEG_OK or MIJPEG_ERR_INVALID_PARAMETER
+ * (any other precision included). */
 int mijpeg_frame_layout(mijpeg_info *info);
 
 typedef struct mijpeg_forward_batch {
   mijpeg_info info;            /* completed by mijpeg_frame_layout; ycbcr = 1: RGB in, YCbCr coded; 0: identity   */
-  const uint8_t *pixels_dev;   /* interleaved 8-bit samples, `components` per pixel; frame f at + f * pixel_frame_stride */
+  const uint8_t *pixels_dev;   /* interleaved 8-bit samples, `components` per pixel; frame f at + f * pixel_frame_stride.
+                                  info.precision == 12: the address of native-endian uint16_t samples, 0..4095, on a 2-byte
+                                  boundary; the strides stay in bytes and are even                                    */
   int64_t pixel_frame_stride;  /* bytes                                                                            */
   int64_t pixel_row_stride;    /* bytes per line                                                                   */
   int16_t *coef_dev;           /* out: quantised coefficients in the layout the decoder reads (natural order inside a
@@ -547,7 +550,11 @@ int mijpeg_launch_forward(const mijpeg_forward_batch *batch, void *stream);
  * Huffman-sequential scan (codestream/sequentialscan.cpp:430-676 WriteMCU / EncodeBlock; segment syntax: marker/ directory).
  * restart_interval: MCUs per restart interval, 0 = none (the intervals are coded in parallel on `threads` threads,
  * <= 0: default); optimize != 0: Huffman tables optimised for the picture (Annex K.2) instead of the Annex K.3 tables.
- * MCU padding blocks are coded as "same DC, no AC".  *stream is malloc'ed: release it with mijpeg_free. */
+ * MCU padding blocks are coded as "same DC, no AC".  *stream is malloc'ed: release it with mijpeg_free.
+ * info->precision == 12: an extended sequential (SOF1, P = 12) stream; DC differences up to category 15 and AC coefficients up to
+ * category 14 are coded (8 bits: 11 and 10), anything beyond is MIJPEG_ERR_OVERFLOW_PARAMETER.  The Annex K.3 tables have no codes
+ * for categories 12..15, so at precision 12 the Huffman tables are ALWAYS built from the picture's statistics and `optimize` is
+ * ignored -- here, in mijpeg_encode_image16 and in mijpeg_encode_batch_device, on the host and on the device coder alike. */
 int mijpeg_encode_coefficients(const mijpeg_info *info, const int16_t *coef, int restart_interval, int optimize, int threads,
                                uint8_t **stream, size_t *size);
 void mijpeg_free(void *p);
@@ -572,9 +579,20 @@ int mijpeg_encode_image_ex(mijpeg_decoder *d, const uint8_t *pixels, int32_t wid
                            int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint32_t flags,
                            uint8_t **stream, size_t *size);
 
+/* The same for a picture of 16-bit samples: interleaved native-endian uint16_t, 0..4095, `components` (1 or 3) per pixel,
+ * row_stride_bytes (even) bytes per line -> an extended sequential stream (SOF1, P = 12: what `jpeg -q quality -s ... -z
+ * restart_interval -h in.ppm out.jpg` of the reference writes for a PNM with maxval 4095, coefficient for coefficient and
+ * quantiser table for table; the Huffman tables are the picture's own, see mijpeg_encode_coefficients).  precision: 12 -- anything
+ * else is MIJPEG_ERR_INVALID_PARAMETER.  The quantiser tables of `quality` are the reference's for 12-bit frames: not limited to
+ * 255 as mijpeg_quality_tables' are, so low qualities write 16-bit DQT entries.  flags: as mijpeg_encode_image_ex. */
+int mijpeg_encode_image16(mijpeg_decoder *d, const uint16_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride_bytes,
+                          int precision, int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, uint32_t flags,
+                          uint8_t **stream, size_t *size);
+
 /* Frames that are already in device memory (a renderer's or a video pipeline's output): forward kernels for the whole batch in
  * one launch, then the device entropy coder frame by frame; only the finished streams cross PCIe.  batch->coef_dev is
- * scratch for the coefficient planes (frames * coef_frame_stride int16).  streams[f] is malloc'ed (mijpeg_free). */
+ * scratch for the coefficient planes (frames * coef_frame_stride int16).  streams[f] is malloc'ed (mijpeg_free).
+ * batch->info.precision == 12: frames of 16-bit samples (mijpeg_forward_batch), streams as mijpeg_encode_image16 writes them. */
 int mijpeg_encode_batch_device(mijpeg_decoder *d, const mijpeg_forward_batch *batch, int restart_interval, int optimize,
                                uint8_t **streams, size_t *sizes);
 
@@ -586,6 +604,8 @@ int mijpeg_encode_batch_device(mijpeg_decoder *d, const mijpeg_forward_batch *ba
  * with n.  Lists of equally shaped frames are served by mijpeg_encode_batch_device as well.  Which of the two is faster for them
  * HAS NOT BEEN MEASURED (profiles/ragged_encode.txt, section 3): until it has, uniform lists are better served by the uniform
  * call, whose cost is known. */
+/* The ragged calls take 8-bit pictures only: mijpeg_encode_frame has no precision field and its layout is not touched.  12-bit
+ * pictures go through mijpeg_encode_image16 or mijpeg_encode_batch_device. */
 typedef struct mijpeg_encode_frame {
   const uint8_t *pixels;     /* interleaved 8-bit samples, `components` per pixel: device memory for mijpeg_encode_ragged_device,
                                 host memory for mijpeg_encode_ragged; the planner does not look at it                          */

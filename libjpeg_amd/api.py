@@ -340,7 +340,10 @@ class Decoder:
     def encode(self, img: np.ndarray, quality: int = 85, subsampling: str = "444", restart_mcus: int = 0, optimize: bool = False,
                coder: str = "gpu") -> bytes:
         """mijpeg_encode_image_ex: (H, W, 3) RGB or (H, W) grey uint8 picture -> baseline JPEG; forward transform on the device,
-        entropy coder on the device (coder="gpu") or on the host cores (coder="host")."""
+        entropy coder on the device (coder="gpu") or on the host cores (coder="host").  A uint16 picture (samples 0..4095) goes
+        through mijpeg_encode_image16 -> extended sequential 12-bit JPEG; its Huffman tables are always the picture's own."""
+        if np.asarray(img).dtype == np.uint16:
+            return self._encode16(np.ascontiguousarray(img), quality, subsampling, restart_mcus, coder)
         img = np.ascontiguousarray(img, np.uint8)
         h, w = img.shape[:2]
         nc = 1 if img.ndim == 2 else img.shape[2]
@@ -358,9 +361,26 @@ class Decoder:
         finally:
             L.mijpeg_free(p)
 
+    def _encode16(self, img: np.ndarray, quality: int, subsampling: str, restart_mcus: int, coder: str, precision: int = 12) -> bytes:
+        h, w = img.shape[:2]
+        nc = 1 if img.ndim == 2 else img.shape[2]
+        hs, vs = ENCODE_LAYOUTS[subsampling] if isinstance(subsampling, str) else subsampling
+        L = lib()
+        L.mijpeg_encode_image16.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int32), C.c_int, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+        L.mijpeg_free.argtypes = [C.c_void_p]
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(L.mijpeg_encode_image16(self._h, img.ctypes.data, w, h, nc, w * nc * 2, precision, quality, (C.c_int32 * 4)(*hs, 1), (C.c_int32 * 4)(*vs, 1),
+                                            restart_mcus, 1 if coder == "host" else 0, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            L.mijpeg_free(p)
+
     def encode_batch_device(self, info: MijpegInfo, pixels_dev: int, coef_dev: int, frames: int, pixel_row_stride: int, pixel_frame_stride: int,
                             restart_mcus: int = 0, optimize: bool = False):
-        """mijpeg_encode_batch_device: frames resident in HBM -> list of baseline JPEG streams (forward kernels + device entropy coder)."""
+        """mijpeg_encode_batch_device: frames resident in HBM -> list of baseline JPEG streams (forward kernels + device entropy coder).
+        info.precision == 12 (frame_layout(..., precision=12)): pixels_dev holds uint16 samples, the streams are extended sequential."""
         _foreign_work_done()
         b = MijpegForwardBatch()
         C.memmove(C.byref(b.info), C.byref(info), C.sizeof(MijpegInfo))
@@ -762,11 +782,11 @@ def launch_reconstruct(info: MijpegInfo, coef_dev: int, out_dev: int, frames: in
         raise MijpegError(rc, "mijpeg_launch_reconstruct failed")
 
 
-def frame_layout(width: int, height: int, components: int, hsamp, vsamp, quant, quant_index=None, ycbcr: int = 1) -> MijpegInfo:
+def frame_layout(width: int, height: int, components: int, hsamp, vsamp, quant, quant_index=None, ycbcr: int = 1, precision: int = 8) -> MijpegInfo:
     """mijpeg_frame_layout: geometry of a frame to be coded (encoder direction).  quant: up to four tables of 64 deltas,
     natural order; quant_index[c]: table of component c (default 0 for the first, 1 for the others)."""
     f = MijpegInfo()
-    f.width, f.height, f.components, f.precision, f.ycbcr = width, height, components, 8, ycbcr
+    f.width, f.height, f.components, f.precision, f.ycbcr = width, height, components, precision, ycbcr
     for c in range(components):
         f.hsamp[c], f.vsamp[c] = hsamp[c], vsamp[c]
         f.quant_index[c] = (0 if c == 0 else min(1, len(quant) - 1)) if quant_index is None else quant_index[c]

@@ -244,7 +244,8 @@ static int Reconstruct(const char *infile, const char *outfile, bool colortrafo,
 }
 
 // Encoder direction (the reference CLI's `jpeg -bl -q n [-s HxV,HxV,HxV] [-z n] [-h] source.ppm target.jpg`, cmd/main.cpp ->
-// cmd/encodec.cpp): binary PNM (P5 / P6, maxval 255) in, baseline JPEG out, as a tag/hook client of class JPEG:
+// cmd/encodec.cpp): binary PNM (P5 / P6, maxval 255) in, baseline JPEG out, as a tag/hook client of class JPEG; maxval 4095
+// (big-endian 16-bit samples) in, extended sequential 12-bit JPEG out -- with -bl the reference's refusal (-1024):
 // JPEG::ProvideImage pulls the picture eight lines at a time through a bitmap hook that reads them from the file
 // (cmd/bitmaphook.cpp:102-340 in its encoder role), JPEG::Write pushes the stream through the file I/O hook.
 // -s takes the reference's SUBSAMPLING factors per component (1x1,2x2,2x2 = 4:2:0).
@@ -252,6 +253,7 @@ struct SourceStripe {
   FILE *in;
   unsigned char *mem; // eight lines, interleaved
   int width, depth, next_line;
+  int sample_bytes;   // 1, or 2: the file's big-endian samples are turned into native words
 };
 
 static JPG_LONG SourceBitmapHook(struct JPG_Hook *hook, struct JPG_TagItem *tags)
@@ -261,28 +263,33 @@ static JPG_LONG SourceBitmapHook(struct JPG_Hook *hook, struct JPG_TagItem *tags
   const JPG_LONG comp = tags->GetTagData(JPGTAG_BIO_COMPONENT), miny = tags->GetTagData(JPGTAG_BIO_MINY), maxy = tags->GetTagData(JPGTAG_BIO_MAXY);
   if (comp == 0) { // a new stripe: read its lines (the requests arrive top-down, component by component)
     if (miny != s->next_line) return -1;
-    const size_t bytes = (size_t)(maxy - miny + 1) * (size_t)s->width * (size_t)s->depth;
+    const size_t bytes = (size_t)(maxy - miny + 1) * (size_t)s->width * (size_t)s->depth * (size_t)s->sample_bytes;
     if (fread(s->mem, 1, bytes, s->in) != bytes) return -1;
+    if (s->sample_bytes == 2)
+      for (size_t i = 0; i < bytes; i += 2) {
+        const unsigned short v = (unsigned short)((s->mem[i] << 8) | s->mem[i + 1]);
+        memcpy(s->mem + i, &v, 2);
+      }
     s->next_line = maxy + 1;
   }
-  const JPG_LONG bpr = s->width * s->depth;
-  tags->SetTagPtr(JPGTAG_BIO_MEMORY, s->mem + comp - (ptrdiff_t)miny * bpr); // address of canvas pixel (0,0)
+  const JPG_LONG bpr = s->width * s->depth * s->sample_bytes;
+  tags->SetTagPtr(JPGTAG_BIO_MEMORY, s->mem + comp * s->sample_bytes - (ptrdiff_t)miny * bpr); // address of canvas pixel (0,0)
   tags->SetTagData(JPGTAG_BIO_WIDTH, s->width);
   tags->SetTagData(JPGTAG_BIO_HEIGHT, 8 + miny);
   tags->SetTagData(JPGTAG_BIO_BYTESPERROW, bpr);
-  tags->SetTagData(JPGTAG_BIO_BYTESPERPIXEL, s->depth);
-  tags->SetTagData(JPGTAG_BIO_PIXELTYPE, CTYP_UBYTE);
+  tags->SetTagData(JPGTAG_BIO_BYTESPERPIXEL, s->depth * s->sample_bytes);
+  tags->SetTagData(JPGTAG_BIO_PIXELTYPE, s->sample_bytes == 2 ? CTYP_UWORD : CTYP_UBYTE);
   return 0;
 }
 
-static int Encode(const char *src, const char *dst, int quality, const char *sub, int restart, bool optimize, int device)
+static int Encode(const char *src, const char *dst, int quality, const char *sub, int restart, bool optimize, bool baseline, int device)
 {
   FILE *in = fopen(src, "rb");
   if (!in) { perror(src); return 10; }
   int w = 0, h = 0, maxval = 0;
   char magic[3] = {0, 0, 0};
-  if (fscanf(in, "%2s %d %d %d", magic, &w, &h, &maxval) != 4 || magic[0] != 'P' || (magic[1] != '5' && magic[1] != '6') || maxval != 255 || w < 1 || h < 1) {
-    fprintf(stderr, "%s: only binary PGM / PPM files with 8 bits per sample are supported as encoder input\n", src);
+  if (fscanf(in, "%2s %d %d %d", magic, &w, &h, &maxval) != 4 || magic[0] != 'P' || (magic[1] != '5' && magic[1] != '6') || (maxval != 255 && maxval != 4095) || w < 1 || h < 1) {
+    fprintf(stderr, "%s: only binary PGM / PPM files with 8 or 12 bits per sample (maxval 255 or 4095) are supported as encoder input\n", src);
     fclose(in);
     return 10;
   }
@@ -294,7 +301,8 @@ static int Encode(const char *src, const char *dst, int quality, const char *sub
     if (sscanf(sub, "%dx%d,%dx%d,%dx%d", &sx[0], &sy[0], &sx[1], &sy[1], &sx[2], &sy[2]) != 6) { fprintf(stderr, "-s expects e.g. 1x1,2x2,2x2\n"); fclose(in); return 5; }
     for (int c = 0; c < 3; c++) { subx[c] = (unsigned char)sx[c]; suby[c] = (unsigned char)sy[c]; }
   }
-  SourceStripe stripe = {in, (unsigned char *)malloc((size_t)w * (size_t)nc * 8), w, nc, 0};
+  const int sample_bytes = maxval == 4095 ? 2 : 1;
+  SourceStripe stripe = {in, (unsigned char *)malloc((size_t)w * (size_t)nc * 8 * (size_t)sample_bytes), w, nc, 0, sample_bytes};
   FILE *out = fopen(dst, "wb");
   if (!stripe.mem || !out) { perror(dst); fclose(in); if (out) fclose(out); free(stripe.mem); return 10; }
   struct JPG_Hook bmhook(SourceBitmapHook, &stripe), filehook(FileHook, out);
@@ -311,8 +319,9 @@ static int Encode(const char *src, const char *dst, int quality, const char *sub
                                   JPG_ValueTag(JPGTAG_IMAGE_WIDTH, w),
                                   JPG_ValueTag(JPGTAG_IMAGE_HEIGHT, h),
                                   JPG_ValueTag(JPGTAG_IMAGE_DEPTH, nc),
-                                  JPG_ValueTag(JPGTAG_IMAGE_PRECISION, 8),
-                                  JPG_ValueTag(JPGTAG_IMAGE_FRAMETYPE, JPGFLAG_BASELINE | (optimize ? JPGFLAG_OPTIMIZE_HUFFMAN : 0)),
+                                  JPG_ValueTag(JPGTAG_IMAGE_PRECISION, sample_bytes == 2 ? 12 : 8),
+                                  // (8 bits: baseline is what the encoder writes anyway; 12 bits: sequential unless -bl asks for the refusal)
+                                  JPG_ValueTag(JPGTAG_IMAGE_FRAMETYPE, (sample_bytes == 2 && !baseline ? JPGFLAG_SEQUENTIAL : JPGFLAG_BASELINE) | (optimize ? JPGFLAG_OPTIMIZE_HUFFMAN : 0)),
                                   JPG_ValueTag(JPGTAG_IMAGE_QUALITY, quality),
                                   JPG_ValueTag(JPGTAG_IMAGE_RESTART_INTERVAL, restart),
                                   JPG_PointerTag(JPGTAG_IMAGE_SUBX, subx),
@@ -340,13 +349,13 @@ int main(int argc, char **argv)
   int threads = 0, device = -1;
   int quality = -1, restart = 0;
   const char *sub = NULL, *alpha = NULL;
-  bool optimize = false;
+  bool optimize = false, baseline = false;
   while (argc > 3) {
     if (!strcmp(argv[1], "-q") && argc > 4) { quality = atoi(argv[2]); argv += 2; argc -= 2; continue; }
     if (!strcmp(argv[1], "-s") && argc > 4) { sub = argv[2]; argv += 2; argc -= 2; continue; }
     if (!strcmp(argv[1], "-z") && argc > 4) { restart = atoi(argv[2]); argv += 2; argc -= 2; continue; }
     if (!strcmp(argv[1], "-h")) { optimize = true; argv++; argc--; continue; }
-    if (!strcmp(argv[1], "-bl")) { argv++; argc--; continue; } // baseline is what the encoder writes anyway
+    if (!strcmp(argv[1], "-bl")) { baseline = true; argv++; argc--; continue; } // (8-bit input: baseline is what the encoder writes anyway)
     if (!strcmp(argv[1], "-c")) { colortrafo = false; argv++; argc--; }
     else if (!strcmp(argv[1], "-U")) { upsample = false; argv++; argc--; }
     else if (!strcmp(argv[1], "-al") && argc > 4) { alpha = argv[2]; argv += 2; argc -= 2; }
@@ -359,9 +368,10 @@ int main(int argc, char **argv)
                     "  reconstructs a Huffman sequential JPEG on an MI355X and writes a binary PNM,\n"
                     "  byte-identical to the output of the reference `jpeg source.jpg target.ppm`\n"
                     "       %s -q quality [-bl] [-s 1x1,2x2,2x2] [-z restart-interval] [-h] [-d device] source.ppm target.jpg\n"
-                    "  encodes a binary PNM as baseline JPEG: the coefficients the reference encoder computes\n", argv[0], argv[0]);
+                    "  encodes a binary PNM as baseline JPEG (maxval 4095, without -bl: as 12-bit extended sequential JPEG):\n"
+                    "  the coefficients the reference encoder computes\n", argv[0], argv[0]);
     return 5;
   }
-  if (quality >= 0) return Encode(argv[1], argv[2], quality, sub, restart, optimize, device);
+  if (quality >= 0) return Encode(argv[1], argv[2], quality, sub, restart, optimize, baseline, device);
   return Reconstruct(argv[1], argv[2], colortrafo, alpha, upsample, threads, device);
 }

@@ -32,7 +32,9 @@ static int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a)
 {
   if (!b || !b->pixels_dev || !b->coef_dev || b->frames < 1) return MIJPEG_ERR_INVALID_PARAMETER;
   const mijpeg_info &f = b->info;
-  if (f.precision != 8 || (f.components != 1 && f.components != 3) || f.xt) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED;
+  if ((f.precision != 8 && f.precision != 12) || (f.components != 1 && f.components != 3) || f.xt) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED;
+  // precision 12: 16-bit samples, every line on a 2-byte boundary
+  if (f.precision == 12 && (((uintptr_t)b->pixels_dev | (uintptr_t)b->pixel_frame_stride | (uintptr_t)b->pixel_row_stride) & 1)) return MIJPEG_ERR_INVALID_PARAMETER;
   memset(&a, 0, sizeof(a));
   a.pixels = b->pixels_dev;
   a.pixel_frame_stride = b->pixel_frame_stride;
@@ -44,6 +46,8 @@ static int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a)
   a.ncomp = f.components;
   a.ycbcr = f.ycbcr;
   a.frames = b->frames;
+  // (the interior and tile kernels read lines as dwords, 16 bytes at a time at precision 12: with 2-byte samples too the
+  // condition is that every line starts on a dword boundary -- a block's first pixel is 24 or 48 bytes into its line)
   const bool dword_lines = (((uintptr_t)b->pixels_dev | (uintptr_t)b->pixel_frame_stride | (uintptr_t)b->pixel_row_stride) & 3) == 0;
   uint64_t blocks = 0;
   for (int c = 0; c < f.components; c++) {
@@ -139,13 +143,33 @@ size_t scan_scratch_bytes(size_t n) { return ((n / 1024 + 8) * 2 + 8192) * 8; }
 
 // The frame of a picture to encode: its layout and the tables of its quality (hsamp, vsamp: null = 1 x 1 throughout).  What
 // mijpeg_frame_layout says to it.
-int picture_info_of(int32_t width, int32_t height, int32_t components, const int32_t *hsamp, const int32_t *vsamp, int quality, mijpeg_info &f)
+// Quantization::InitDefaultTables (marker/quantization.cpp:275-466) with the default (Annex K) matrices, natural order: entries
+// limited to `limit` -- 255 in 8-bit frames (:456-459: "the table entries shall be byte-sized"), 32767 at precision 12 (:446-447),
+// where low qualities give 16-bit DQT entries (tests/golden/enc12: q 2)
+void quality_tables_of(int quality, int limit, uint16_t luma[64], uint16_t chroma[64])
+{
+  // ISO/IEC 10918-1 Annex K.1 / K.2 matrices, natural order
+  static const uint8_t K1[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
+                                 14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
+                                 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+  static const uint8_t K2[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
+  quality = std::min(100, std::max(1, quality));
+  const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2; // quantization.cpp:296-299
+  for (int j = 0; j < 64; j++) {
+    luma[j] = (uint16_t)std::min(limit, std::max(1, (K1[j] * scale + 50) / 100)); // :411, :443-466
+    chroma[j] = (uint16_t)std::min(limit, std::max(1, (K2[j] * scale + 50) / 100));
+  }
+}
+
+int picture_info_of(int32_t width, int32_t height, int32_t components, const int32_t *hsamp, const int32_t *vsamp, int quality, mijpeg_info &f,
+                    int precision = 8)
 {
   memset(&f, 0, sizeof(f));
   f.width = width;
   f.height = height;
   f.components = components;
-  f.precision = 8;
+  f.precision = precision;
   f.ycbcr = components == 3 ? 1 : 0;
   for (int c = 0; c < components; c++) {
     f.hsamp[c] = hsamp ? hsamp[c] : 1;
@@ -155,7 +179,7 @@ int picture_info_of(int32_t width, int32_t height, int32_t components, const int
     // what reproduces its coefficients
     f.quant_index[c] = 0;
   }
-  mijpeg_quality_tables(quality, f.quant[0], f.quant[1]);
+  quality_tables_of(quality, precision == 12 ? 32767 : 255, f.quant[0], f.quant[1]);
   return mijpeg_frame_layout(&f);
 }
 
@@ -239,7 +263,8 @@ struct HencJob {
     enc_standard_tables(tabs);
     rc = upload_tables();
     if (rc) return rc;
-    if (optimize) { // symbol statistics first, tables from them (Annex K.2)
+    // precision 12: the Annex K.3 tables have no codes for categories 12..15, so the tables are always the picture's own
+    if (optimize || info.precision == 12) { // symbol statistics first, tables from them (Annex K.2)
       HIP_TRY(d, hipMemsetAsync(base + o_hist, 0, 4 * 256 * 4, stream));
       if (henc_count(a, true, stream)) return hip_fail(d, hipGetLastError(), "henc_count_kernel launch");
       uint32_t hist[4][256];
@@ -263,7 +288,8 @@ struct HencJob {
     HIP_TRY(d, hipStreamSynchronize(stream));
     const uint64_t plain_bytes = readback[0];
     const uint32_t I = a.n_intervals;
-    // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check)
+    // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check;
+    // of 12-bit pixels at most 15 / 14 bits, which the tables built from the statistics cover)
     chunks = (uint32_t)((plain_bytes + HENC_STUFF_CHUNK - 1) / HENC_STUFF_CHUNK);
     Carver ar;
     const size_t q_plain = ar.take((size_t)plain_bytes + 16);
@@ -703,7 +729,8 @@ extern "C" {
 
 int mijpeg_frame_layout(mijpeg_info *f)
 try {
-  if (!f || f->width < 1 || f->height < 1 || f->width > 65535 || f->height > 65535 || f->components < 1 || f->components > MIJPEG_MAX_COMPONENTS)
+  if (!f || f->width < 1 || f->height < 1 || f->width > 65535 || f->height > 65535 || f->components < 1 || f->components > MIJPEG_MAX_COMPONENTS ||
+      (f->precision != 8 && f->precision != 12))
     return MIJPEG_ERR_INVALID_PARAMETER;
   int hmax = 1, vmax = 1;
   for (int c = 0; c < f->components; c++) {
@@ -725,7 +752,7 @@ try {
     off += (int64_t)f->blocks_w[c] * f->blocks_h[c] * 64;
   }
   f->coef_count = off;
-  f->sample_bytes = 1;
+  f->sample_bytes = f->precision == 12 ? 2 : 1;
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(nullptr, "mijpeg_frame_layout"); }
 
@@ -733,23 +760,12 @@ int mijpeg_launch_forward(const mijpeg_forward_batch *b, void *stream)
 try {
   ForwardArgs a;
   if (const int rc = forward_args_of(b, a)) return rc;
-  return launch_forward(a, (hipStream_t)stream) ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
+  return launch_forward(a, b->info.precision, (hipStream_t)stream) ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
 } catch (...) { return boundary_catch(nullptr, "mijpeg_launch_forward"); }
 
 void mijpeg_quality_tables(int quality, uint16_t luma[64], uint16_t chroma[64])
 try {
-  // ISO/IEC 10918-1 Annex K.1 / K.2 matrices, natural order
-  static const uint8_t K1[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
-                                 14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
-                                 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
-  static const uint8_t K2[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
-                                 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-  quality = std::min(100, std::max(1, quality));
-  const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2; // quantization.cpp:296-299
-  for (int j = 0; j < 64; j++) {
-    luma[j] = (uint16_t)std::min(255, std::max(1, (K1[j] * scale + 50) / 100)); // :411, :443-466
-    chroma[j] = (uint16_t)std::min(255, std::max(1, (K2[j] * scale + 50) / 100));
-  }
+  quality_tables_of(quality, 255, luma, chroma);
 } catch (...) { (void)boundary_catch(nullptr, "mijpeg_quality_tables"); }
 
 int mijpeg_encode_batch_device(mijpeg_decoder *d, const mijpeg_forward_batch *b, int restart_interval, int optimize, uint8_t **streams, size_t *sizes)
@@ -792,20 +808,21 @@ try {
   return mijpeg_encode_image_ex(d, pixels, width, height, components, row_stride, quality, hsamp, vsamp, restart_interval, optimize, 0, stream, size);
 } catch (...) { return boundary_catch(d, "mijpeg_encode_image"); }
 
-int mijpeg_encode_image_ex(mijpeg_decoder *d, const uint8_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
-                           int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint32_t flags,
+// the body of mijpeg_encode_image_ex and mijpeg_encode_image16: `pixels` are 8-bit samples or, precision 12, uint16_t samples
+static int encode_image_of(mijpeg_decoder *d, const uint8_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
+                           int precision, int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint32_t flags,
                            uint8_t **stream, size_t *size)
-try {
+{
   using clk = std::chrono::steady_clock;
   const auto t_begin = clk::now();
-  if (!d || !pixels || !stream || !size || (components != 1 && components != 3) || row_stride < (int64_t)width * components)
+  if (!d || !pixels || !stream || !size || (components != 1 && components != 3) || row_stride < (int64_t)width * components * (precision == 12 ? 2 : 1))
     return MIJPEG_ERR_INVALID_PARAMETER;
   if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
   HIP_TRY(d, hipSetDevice(d->device));
   mijpeg_forward_batch b;
   memset(&b, 0, sizeof(b));
   mijpeg_info &f = b.info;
-  int rc = picture_info_of(width, height, components, hsamp, vsamp, quality, f);
+  int rc = picture_info_of(width, height, components, hsamp, vsamp, quality, f, precision);
   if (rc) return set_error(d, rc, "invalid frame layout for encoding");
   const size_t px_bytes = (size_t)row_stride * (size_t)height, coef_bytes = (size_t)f.coef_count * sizeof(int16_t);
   rc = ensure_dev(d, (void **)&d->enc_dev, &d->enc_cap, px_bytes + 256 + coef_bytes);
@@ -863,7 +880,22 @@ try {
   d->timing[3] = std::chrono::duration<double>(clk::now() - t_down).count();
   if (rc) return set_error(d, rc, "entropy coding failed");
   return MIJPEG_OK;
+}
+
+int mijpeg_encode_image_ex(mijpeg_decoder *d, const uint8_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
+                           int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint32_t flags,
+                           uint8_t **stream, size_t *size)
+try {
+  return encode_image_of(d, pixels, width, height, components, row_stride, 8, quality, hsamp, vsamp, restart_interval, optimize, flags, stream, size);
 } catch (...) { return boundary_catch(d, "mijpeg_encode_image_ex"); }
+
+int mijpeg_encode_image16(mijpeg_decoder *d, const uint16_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
+                          int precision, int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, uint32_t flags,
+                          uint8_t **stream, size_t *size)
+try {
+  if (precision != 12 || (row_stride & 1) || ((uintptr_t)pixels & 1) || (flags & ~MIJPEG_ENCODE_HOST_CODER)) return MIJPEG_ERR_INVALID_PARAMETER;
+  return encode_image_of(d, (const uint8_t *)pixels, width, height, components, row_stride, 12, quality, hsamp, vsamp, restart_interval, 1, flags, stream, size);
+} catch (...) { return boundary_catch(d, "mijpeg_encode_image16"); }
 
 int mijpeg_encode_ragged_plan(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,
                               mijpeg_encode_ragged_totals *totals)

@@ -160,15 +160,17 @@ inline int category(int v)
 }
 
 // One block: sequentialscan.cpp EncodeBlock.  Either codes it (bw != null) or counts its symbols.
-// Returns false when a value does not fit the 8-bit processes (DC differences of more than 11, AC coefficients of more
-// than 10 bits: Tables F.1 / F.2), for which neither the Annex K tables nor SOF0 have room.
+// Returns false when a value does not fit the frame's processes (Tables F.1 / F.2): at precision 8 DC differences of more
+// than 11 and AC coefficients of more than 10 bits, for which neither the Annex K tables nor SOF0 have room; at precision
+// 12 (dc_max 15, ac_max 14) what SOF1 has room for.  A code word and the value bits behind it are put separately, at most
+// 16 bits each, so the widest symbol (31 bits at precision 12) is within BitWriter::put's reach.
 inline bool code_block(const int16_t *blk, int &pred, const EncTable &dc, const EncTable &ac, BitWriter *bw, uint32_t *dcfreq, uint32_t *acfreq,
-                       const uint8_t *zz)
+                       const uint8_t *zz, int dc_max = 11, int ac_max = 10)
 {
   const int diff = (blk ? blk[0] : pred) - pred;
   pred += diff;
   int s = category(diff);
-  if (s > 11) return false;
+  if (s > dc_max) return false;
   if (bw) {
     bw->put(dc.code[s], dc.len[s]);
     if (s) bw->put((unsigned)(diff < 0 ? diff - 1 : diff), s);
@@ -184,7 +186,7 @@ inline bool code_block(const int16_t *blk, int &pred, const EncTable &dc, const 
         run -= 16;
       }
       s = category(v);
-      if (s > 10) return false;
+      if (s > ac_max) return false;
       const int sym = (run << 4) | s;
       if (bw) {
         bw->put(ac.code[sym], ac.len[sym]);
@@ -229,7 +231,7 @@ void enc_optimal_tables(EncTables &t, const uint32_t dcfreq[2][256], const uint3
   }
 }
 
-// SOI, DQT, SOF0, DHT, DRI, SOS: everything in front of the entropy coded data
+// SOI, DQT, SOF0 (precision 12: SOF1, extended sequential), DHT, DRI, SOS: everything in front of the entropy coded data
 void enc_write_headers(std::vector<uint8_t> &o, const mijpeg_info &f, const EncTables &tabs, int restart_interval)
 {
   const int nc = f.components;
@@ -251,9 +253,9 @@ void enc_write_headers(std::vector<uint8_t> &o, const mijpeg_info &f, const EncT
         o.push_back((uint8_t)f.quant[t][zz[k]]);
       }
     }
-  o.push_back(0xff); o.push_back(0xc0);
+  o.push_back(0xff); o.push_back(f.precision == 12 ? 0xc1 : 0xc0);
   put16(o, (unsigned)(8 + 3 * nc));
-  o.push_back(8);
+  o.push_back((uint8_t)(f.precision == 12 ? 12 : 8));
   put16(o, (unsigned)f.height);
   put16(o, (unsigned)f.width);
   o.push_back((uint8_t)nc);
@@ -291,8 +293,11 @@ extern "C" int mijpeg_encode_coefficients(const mijpeg_info *info, const int16_t
 try {
   if (!info || !coef || !stream || !size || restart_interval < 0 || restart_interval > 65535) return MIJPEG_ERR_INVALID_PARAMETER;
   const mijpeg_info &f = *info;
-  if (f.precision != 8 || (f.components != 1 && f.components != 3)) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED;
+  if ((f.precision != 8 && f.precision != 12) || (f.components != 1 && f.components != 3)) return MIJPEG_ERR_OPERATION_UNIMPLEMENTED;
   const int nc = f.components;
+  const bool p12 = f.precision == 12;
+  const int dc_max = p12 ? 15 : 11, ac_max = p12 ? 14 : 10;
+  if (p12) optimize = 1; // Annex K.3 has no codes for categories 12..15: the tables are always the picture's own
   const uint8_t *zz = scan_order();
   const int64_t total_mcus = (int64_t)f.mcus_x * f.mcus_y;
   const int64_t ri = restart_interval ? restart_interval : total_mcus;
@@ -317,16 +322,16 @@ try {
           for (int bx = 0; bx < hs[c]; bx++) {
             const int gx = mx * hs[c] + bx, gy = my * vs[c] + by;
             const int16_t *blk = (gx < nbx[c] && gy < nby[c]) ? coef + f.coef_offset[c] + ((int64_t)gy * f.blocks_w[c] + gx) * 64 : nullptr;
-            if (!code_block(blk, pred[c], dct[t], act[t], bw, dcf ? dcf[t] : nullptr, acf ? acf[t] : nullptr, zz)) out_of_range.store(true, std::memory_order_relaxed);
+            if (!code_block(blk, pred[c], dct[t], act[t], bw, dcf ? dcf[t] : nullptr, acf ? acf[t] : nullptr, zz, dc_max, ac_max)) out_of_range.store(true, std::memory_order_relaxed);
           }
       }
     }
   };
   int blocks_per_mcu = 0;
   for (int c = 0; c < nc; c++) blocks_per_mcu += hs[c] * vs[c];
-  // bytes `mcus` MCUs can take at most: 63 AC coefficients of 16 + 10 bits and a DC difference of 16 + 11 bits per block,
-  // every byte stuffed, plus slack for the word-wise writer
-  auto worst_case_bytes = [&](int64_t mcus) -> size_t { return (size_t)mcus * (size_t)blocks_per_mcu * 420 + 64; };
+  // bytes `mcus` MCUs can take at most: 63 AC coefficients of 16 + 10 bits and a DC difference of 16 + 11 bits per block
+  // (precision 12: 16 + 14 and 16 + 15 bits: 1921 bits, 241 bytes), every byte stuffed, plus slack for the word-wise writer
+  auto worst_case_bytes = [&](int64_t mcus) -> size_t { return (size_t)mcus * (size_t)blocks_per_mcu * (p12 ? 484 : 420) + 64; };
   auto walk_interval = [&](int64_t i, const EncTable *dct, const EncTable *act, BitWriter *bw, uint32_t (*dcf)[256], uint32_t (*acf)[256]) {
     int pred[4] = {0, 0, 0, 0};
     walk_mcus(i * ri, std::min(total_mcus, i * ri + ri), pred, dct, act, bw, dcf, acf);
@@ -469,7 +474,7 @@ try {
       part_len[(size_t)w] = (size_t)(q - part_mem[(size_t)w].get());
     });
   }
-  if (out_of_range.load()) return MIJPEG_ERR_OVERFLOW_PARAMETER; // coefficients outside what an 8-bit frame can hold
+  if (out_of_range.load()) return MIJPEG_ERR_OVERFLOW_PARAMETER; // coefficients outside what a frame of this precision can hold
   // the stream
   std::vector<uint8_t> o;
   EncTables tabs;

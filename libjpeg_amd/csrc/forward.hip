@@ -20,6 +20,12 @@
 // multiply-and-shift.
 // Each kernel has a RAGGED flavour for lists of pictures of different shapes (ForwardRaggedArgs): the workgroup looks its
 // picture up and runs the same body on that picture's argument block in device memory.
+// Each kernel also has a precision-12 flavour (template parameter P; extended sequential frames, SOF1): interleaved native-endian
+// uint16_t samples, 0..4095.  What differs from the 8-bit flavour is cited where it does: the level shift 2^(P-1) in the colour
+// transformation's DC offset, its clamp, the pre-fill of partial blocks and the transform's dcoffset; the width of the loads;
+// the type of the chroma samples in LDS.  The transform itself is the same wrapping 32-bit one (Tables::BuildDCT,
+// codestream/tables.cpp:1876-1906, takes LOSSYDCT<COLOR_BITS, LONG> up to precision 12); where 16-bit samples make the
+// reference's LONG wrap, so does this.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -30,6 +36,7 @@ namespace mij {
 #define F9(x) ((int)((x) * 512.0 + 0.5)) // TO_FIX, dct/idct.cpp:65
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4_dword_aligned __attribute__((aligned(4))); // a 16-byte load from a dword-aligned line
 
 __device__ __forceinline__ int wadd(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
 __device__ __forceinline__ int wsub(int a, int b) { return (int)((unsigned)a - (unsigned)b); }
@@ -65,19 +72,21 @@ __device__ __forceinline__ void fdct_1d(const int (&s)[8], int (&o)[8])
   o[7] = wadd(wadd(tt3, tt10), tt13);
 }
 
-// component `c` of the forward L transformation of one pixel (ycbcrtrafo.cpp:176-199): FIX_TO_COLOR, clamp
+// component `c` of the forward L transformation of one pixel (ycbcrtrafo.cpp:176-199): FIX_TO_COLOR, clamp; m_lDCShift is
+// 2^(P-1), m_lMax 2^P - 1 (12-bit samples: the sums stay below 2^30, the reference's QUAD is not needed)
+template <int P>
 __device__ __forceinline__ int ycc_component(int c, int r, int g, int b)
 {
-  const int dc = (128 << 13) + 256;
+  const int dc = ((1 << (P - 1)) << 13) + 256;
   int v;
   if (c == 0) v = (r * 2449 + g * 4809 + b * 934 + 256) >> 9;
   else if (c == 1) v = (r * -1382 + g * -2714 + b * 4096 + dc) >> 9;
   else v = (r * 4096 + g * -3430 + b * -666 + dc) >> 9;
-  return min(max(v, 0), (256 << 4) - 1);
+  return min(max(v, 0), ((1 << P) << 4) - 1);
 }
 
 // forward transform of one block of samples, quantisation, 128-byte store (idct.cpp:125-170 columns, :174-218 rows)
-template <class Q>
+template <int P, class Q>
 __device__ __forceinline__ void transform_and_store_from(const int (&blk)[64], Q invq, int16_t *dst)
 {
   // pass over columns (idct.cpp:125-170), then rows with quantisation (:174-218)
@@ -93,7 +102,7 @@ __device__ __forceinline__ void transform_and_store_from(const int (&blk)[64], Q
     for (int k = 1; k < 8; k++)
       if (k != 4) t[k * 8 + col] = wadd(o[k], 256) >> 9; // FIXED_TO_INTERMEDIATE
   }
-  const int dcoffset = 128 << 10; // 2^(P-1) << (preshift + 3 + 3)
+  const int dcoffset = (1 << (P - 1)) << 10; // 2^(P-1) << (preshift + 3 + 3)
   unsigned packed[32];
 #pragma unroll
   for (int r = 0; r < 8; r++) {
@@ -114,32 +123,58 @@ __device__ __forceinline__ void transform_and_store_from(const int (&blk)[64], Q
 }
 
 // invq from the kernel's own arguments, or -- ragged flavours -- from the picture's argument block in the constant address space
+template <int P>
 __device__ __forceinline__ void transform_and_store(const int (&blk)[64], const int *__restrict__ invq, int16_t *dst)
 {
-  transform_and_store_from(blk, invq, dst);
+  transform_and_store_from<P>(blk, invq, dst);
 }
+template <int P>
 __device__ __forceinline__ void transform_and_store(const int (&blk)[64], const __attribute__((address_space(4))) int *invq, int16_t *dst)
 {
-  transform_and_store_from(blk, invq, dst);
+  transform_and_store_from<P>(blk, invq, dst);
+}
+
+// One line of W pixels' worth of interleaved RGB samples as dwords: ND of them.  8-bit: dword loads; 12-bit (2-byte samples, rows
+// of 48 bytes per 8 pixels): 16-byte loads
+template <int P, int ND>
+__device__ __forceinline__ void load_line(const uint8_t *line, unsigned (&dw)[ND])
+{
+  if constexpr (P == 8) {
+    const unsigned *l = reinterpret_cast<const unsigned *>(line);
+#pragma unroll
+    for (int i = 0; i < ND; i++) dw[i] = l[i];
+  } else {
+    const u32x4_dword_aligned *l = reinterpret_cast<const u32x4_dword_aligned *>(line);
+#pragma unroll
+    for (int i = 0; i < ND / 4; i++) {
+      const u32x4 v = l[i];
+      dw[4 * i] = v.x; dw[4 * i + 1] = v.y; dw[4 * i + 2] = v.z; dw[4 * i + 3] = v.w;
+    }
+  }
+}
+// sample s (pixel * 3 + channel) of such a line
+template <int P, int ND>
+__device__ __forceinline__ int line_sample(const unsigned (&d)[ND], int s)
+{
+  if constexpr (P == 8) return (int)((d[s >> 2] >> (8 * (s & 3))) & 0xffu);
+  else return (int)((d[s >> 1] >> (16 * (s & 1))) & 0xffffu);
 }
 
 // Interior blocks of RGB -> YCbCr frames with subsampling factors 1 or 2: the block's SX*8 x SY*8 pixels are read as
-// dwords (rows of 24 * SX bytes; the host checks that lines start dword-aligned), the bytes picked apart in registers,
-// only the block's own component computed, the box filter's division a shift (the sums are not negative).
-template <int SX, int SY>
+// dwords (rows of 24 * SX bytes, 48 * SX at precision 12; the host checks that lines start dword-aligned), the samples picked
+// apart in registers, only the block's own component computed, the box filter's division a shift (the sums are not negative).
+template <int SX, int SY, int P>
 __device__ __forceinline__ void gather_block_fast(const uint8_t *img, int64_t row_stride, int x0, int y0, int c, int (&blk)[64])
 {
-  constexpr int ND = 6 * SX;                 // dwords per line of the block
-  constexpr int RB = 8 / (SX * SY);          // output rows per batch: 48 dwords in flight at a time, one memory round trip each
+  constexpr int SB = P == 8 ? 1 : 2;         // bytes per sample
+  constexpr int ND = 6 * SX * SB;            // dwords per line of the block
+  constexpr int RB = 8 / (SX * SY * SB);     // output rows per batch: 48 dwords in flight at a time, one memory round trip each
 #pragma unroll
   for (int r0 = 0; r0 < 8; r0 += RB) {
     unsigned dw[RB * SY][ND];
 #pragma unroll
-    for (int l = 0; l < RB * SY; l++) {
-      const unsigned *line = reinterpret_cast<const unsigned *>(img + (int64_t)(y0 + r0 * SY + l) * row_stride + (int64_t)x0 * 3);
-#pragma unroll
-      for (int i = 0; i < ND; i++) dw[l][i] = line[i];
-    }
+    for (int l = 0; l < RB * SY; l++)
+      load_line<P>(img + (int64_t)(y0 + r0 * SY + l) * row_stride + (int64_t)x0 * (3 * SB), dw[l]);
     __builtin_amdgcn_sched_barrier(0); // the loads of one batch together, those of the next not before this one is used up
 #pragma unroll
     for (int rr = 0; rr < RB; rr++) {
@@ -150,11 +185,9 @@ __device__ __forceinline__ void gather_block_fast(const uint8_t *img, int64_t ro
         for (int i = 0; i < 8; i++)
 #pragma unroll
           for (int k = 0; k < SX; k++) {
-            const int j = 3 * (i * SX + k); // byte of the pixel's R inside the line
-            const unsigned *d = dw[rr * SY + ly];
-            const int r8 = (int)((d[j >> 2] >> (8 * (j & 3))) & 0xffu), g8 = (int)((d[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xffu),
-                      b8 = (int)((d[(j + 2) >> 2] >> (8 * ((j + 2) & 3))) & 0xffu);
-            acc[i] += ycc_component(c, r8, g8, b8);
+            const int j = 3 * (i * SX + k); // sample of the pixel's R inside the line
+            const auto &d = dw[rr * SY + ly];
+            acc[i] += ycc_component<P>(c, line_sample<P>(d, j), line_sample<P>(d, j + 1), line_sample<P>(d, j + 2));
           }
 #pragma unroll
       for (int i = 0; i < 8; i++) blk[(r0 + rr) * 8 + i] = acc[i] >> (SX * SY == 4 ? 2 : SX * SY == 2 ? 1 : 0);
@@ -197,7 +230,7 @@ __device__ __forceinline__ RaggedItem find_item(const ForwardRaggedArgs &r)
 __device__ __forceinline__ const ForwardArgs &args_of(const ForwardArgs &k, const RaggedItem &) { return k; }
 __device__ __forceinline__ ConstForwardArgs &args_of(const ForwardRaggedArgs &k, const RaggedItem &it) { return *((ConstForwardArgs *)k.pics + it.pic); }
 
-template <bool RAGGED>
+template <bool RAGGED, int P>
 __global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelArgs<RAGGED>::type k)
 {
   RaggedItem it{};
@@ -222,9 +255,15 @@ __global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelA
   const uint8_t *img = a.pixels + (int64_t)frame * a.pixel_frame_stride;
   const bool ycc = nc == 3 && a.ycbcr;
   auto sample = [&](int x, int y) -> int { // component c of pixel (x, y), x < W, y < H, with COLOR_BITS fractional bits
-    const uint8_t *p = img + (int64_t)y * a.pixel_row_stride + (int64_t)x * nc;
-    if (ycc) return ycc_component(c, p[0], p[1], p[2]);
-    return (int)p[c] << 4;
+    if constexpr (P == 8) {
+      const uint8_t *p = img + (int64_t)y * a.pixel_row_stride + (int64_t)x * nc;
+      if (ycc) return ycc_component<P>(c, p[0], p[1], p[2]);
+      return (int)p[c] << 4;
+    } else {
+      const uint16_t *p = reinterpret_cast<const uint16_t *>(img + (int64_t)y * a.pixel_row_stride) + (int64_t)x * nc;
+      if (ycc) return ycc_component<P>(c, p[0], p[1], p[2]);
+      return (int)p[c] << 4;
+    }
   };
   int blk[64];
   // interior blocks of frames the fast kernels cover are theirs
@@ -237,7 +276,7 @@ __global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelA
 #pragma unroll
       for (int i = 0; i < 8; i++) {
         const int x = bx * 8 + i;
-        blk[r * 8 + i] = (x < W && y < H) ? sample(x, y) : (128 << 4);
+        blk[r * 8 + i] = (x < W && y < H) ? sample(x, y) : ((1 << (P - 1)) << 4);
       }
     }
   } else {
@@ -264,7 +303,7 @@ __global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelA
       for (int i = 0; i < 8; i++) blk[r * 8 + i] = norm > 1 ? acc[i] / norm : acc[i];
     }
   }
-  transform_and_store(blk, a.invq[c], dst);
+  transform_and_store<P>(blk, a.invq[c], dst);
 }
 
 // 4:2:0, tiles of 128 x 128 pixels that lie wholly inside the picture: one workgroup of 256 lanes per tile.  Every lane reads
@@ -272,10 +311,24 @@ __global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelA
 // luma block, and leaves the 4 x 4 box-filtered chroma samples of its pixels (sums of 2 x 2, >> 2) in LDS; after a
 // barrier 128 lanes pick up the 64 + 64 chroma blocks of the tile and transform them.  Compared with the per-component
 // kernels no pixel is fetched or unpacked twice.  grid (tiles_x * tiles_y, frames)
-template <bool RAGGED>
+// Precision 12: a lane's 8 x 8 pixels are 8 rows of 48 bytes, three 16-byte loads each, taken in two batches of four rows (48
+// dwords in flight, as at 8 bits); the box-filtered chroma with its 4 fractional bits reaches 65535, so the LDS samples are
+// unsigned there.
+template <int P>
+struct ChromaSample {
+  typedef short type;
+};
+template <>
+struct ChromaSample<12> {
+  typedef unsigned short type;
+};
+template <bool RAGGED, int P>
 __global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const typename KernelArgs<RAGGED>::type k)
 {
-  __shared__ short chroma[2][64 * 64]; // [Cb, Cr][64 lines of 64 samples]
+  typedef typename ChromaSample<P>::type chroma_t;
+  constexpr int SB = P == 8 ? 1 : 2; // bytes per sample
+  constexpr int RB = 8 / SB;         // rows per batch of loads
+  __shared__ chroma_t chroma[2][64 * 64]; // [Cb, Cr][64 lines of 64 samples]
   RaggedItem it{};
   if constexpr (RAGGED) it = find_item(k);
   auto &a = args_of(k, it);
@@ -289,57 +342,58 @@ __global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const typename Ker
   const int lbx = lane & 15, lby = lane >> 4; // luma block inside the tile
   const int x0 = tx * 128 + lbx * 8, y0 = ty * 128 + lby * 8;
   {
-    unsigned dw[8][6];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-      const unsigned *line = reinterpret_cast<const unsigned *>(img + (int64_t)(y0 + r) * a.pixel_row_stride + (int64_t)x0 * 3);
-#pragma unroll
-      for (int i = 0; i < 6; i++) dw[r][i] = line[i];
-    }
     int blk[64];
-    short *cb = chroma[0] + (lby * 4) * 64 + lbx * 4, *cr = chroma[1] + (lby * 4) * 64 + lbx * 4;
+    chroma_t *cb = chroma[0] + (lby * 4) * 64 + lbx * 4, *cr = chroma[1] + (lby * 4) * 64 + lbx * 4;
 #pragma unroll
-    for (int r = 0; r < 8; r += 2) {
-      int sb[4] = {0, 0, 0, 0}, sr[4] = {0, 0, 0, 0};
+    for (int r0 = 0; r0 < 8; r0 += RB) {
+      unsigned dw[RB][6 * SB];
 #pragma unroll
-      for (int rr = 0; rr < 2; rr++)
+      for (int r = 0; r < RB; r++) load_line<P>(img + (int64_t)(y0 + r0 + r) * a.pixel_row_stride + (int64_t)x0 * (3 * SB), dw[r]);
+      if constexpr (RB < 8) __builtin_amdgcn_sched_barrier(0); // the loads of one batch together, as in gather_block_fast
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
-          const int j = 3 * i;
-          const unsigned *d = dw[r + rr];
-          const int r8 = (int)((d[j >> 2] >> (8 * (j & 3))) & 0xffu), g8 = (int)((d[(j + 1) >> 2] >> (8 * ((j + 1) & 3))) & 0xffu),
-                    b8 = (int)((d[(j + 2) >> 2] >> (8 * ((j + 2) & 3))) & 0xffu);
-          blk[(r + rr) * 8 + i] = ycc_component(0, r8, g8, b8);
-          sb[i >> 1] += ycc_component(1, r8, g8, b8);
-          sr[i >> 1] += ycc_component(2, r8, g8, b8);
+      for (int r = r0; r < r0 + RB; r += 2) {
+        int sb[4] = {0, 0, 0, 0}, sr[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int rr = 0; rr < 2; rr++)
+#pragma unroll
+          for (int i = 0; i < 8; i++) {
+            const int j = 3 * i;
+            const auto &d = dw[r - r0 + rr];
+            const int r8 = line_sample<P>(d, j), g8 = line_sample<P>(d, j + 1), b8 = line_sample<P>(d, j + 2);
+            blk[(r + rr) * 8 + i] = ycc_component<P>(0, r8, g8, b8);
+            sb[i >> 1] += ycc_component<P>(1, r8, g8, b8);
+            sr[i >> 1] += ycc_component<P>(2, r8, g8, b8);
+          }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          cb[(r >> 1) * 64 + i] = (chroma_t)(sb[i] >> 2);
+          cr[(r >> 1) * 64 + i] = (chroma_t)(sr[i] >> 2);
         }
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        cb[(r >> 1) * 64 + i] = (short)(sb[i] >> 2);
-        cr[(r >> 1) * 64 + i] = (short)(sr[i] >> 2);
       }
+      if constexpr (RB < 8) __builtin_amdgcn_sched_barrier(0);
     }
-    transform_and_store(blk, a.invq[0], coef + a.coef_off[0] + ((int64_t)(y0 >> 3) * a.bw[0] + (x0 >> 3)) * 64);
+    transform_and_store<P>(blk, a.invq[0], coef + a.coef_off[0] + ((int64_t)(y0 >> 3) * a.bw[0] + (x0 >> 3)) * 64);
   }
   __syncthreads();
   if (lane < 128) {
     const int c = 1 + (lane >> 6), n = lane & 63, cbx = n & 7, cby = n >> 3;
-    const short *src = chroma[c - 1] + (cby * 8) * 64 + cbx * 8;
+    const chroma_t *src = chroma[c - 1] + (cby * 8) * 64 + cbx * 8;
     int blk[64];
 #pragma unroll
     for (int r = 0; r < 8; r++)
 #pragma unroll
       for (int i = 0; i < 8; i++) blk[r * 8 + i] = src[r * 64 + i];
-    transform_and_store(blk, a.invq[c], coef + a.coef_off[c] + ((int64_t)(ty * 8 + cby) * a.bw[c] + (tx * 8 + cbx)) * 64);
+    transform_and_store<P>(blk, a.invq[c], coef + a.coef_off[c] + ((int64_t)(ty * 8 + cby) * a.bw[c] + (tx * 8 + cbx)) * 64);
   }
 }
 
 // the interior blocks of component c: grid (blocks of 256 lanes over fast_nbx * fast_nby, frames)
 // (The uniform 2 x 2 flavour fills its 256 registers and spills 32 bytes a lane; the ragged one needs a few more and gets one
 // workgroup per CU instead -- 512 registers, the surplus in AGPRs -- so that it touches no scratch memory.  It only sees what
-// the tile kernel leaves of a 4:2:0 picture: the strips right of and below the whole tiles, and pictures below 128 x 128.)
-template <int SX, int SY, bool RAGGED>
-__global__ __launch_bounds__(256, SX * SY == 4 ? (RAGGED ? 1 : 2) : 3) void fdct_interior_kernel(const typename KernelArgs<RAGGED>::type k, int c)
+// the tile kernel leaves of a 4:2:0 picture: the strips right of and below the whole tiles, and pictures below 128 x 128.
+// The precision-12 2 x 2 flavour would spill 22 registers at two workgroups per CU and gets one as well.)
+template <int SX, int SY, bool RAGGED, int P>
+__global__ __launch_bounds__(256, SX * SY == 4 ? (RAGGED || P == 12 ? 1 : 2) : 3) void fdct_interior_kernel(const typename KernelArgs<RAGGED>::type k, int c)
 {
   RaggedItem it{};
   if constexpr (RAGGED) {
@@ -355,28 +409,34 @@ __global__ __launch_bounds__(256, SX * SY == 4 ? (RAGGED ? 1 : 2) : 3) void fdct
   int16_t *dst = a.coef + (int64_t)frame * a.coef_frame_stride + a.coef_off[c] + ((int64_t)by * a.bw[c] + bx) * 64;
   const uint8_t *img = a.pixels + (int64_t)frame * a.pixel_frame_stride;
   int blk[64];
-  gather_block_fast<SX, SY>(img, a.pixel_row_stride, (bx * SX) << 3, (by * SY) << 3, c, blk);
-  transform_and_store(blk, a.invq[c], dst);
+  gather_block_fast<SX, SY, P>(img, a.pixel_row_stride, (bx * SX) << 3, (by * SY) << 3, c, blk);
+  transform_and_store<P>(blk, a.invq[c], dst);
 }
 
-int launch_forward(const ForwardArgs &a, hipStream_t stream)
+template <int P>
+static int launch_forward_of(const ForwardArgs &a, hipStream_t stream)
 {
   const unsigned per_frame = a.first_block[a.ncomp];
   if (per_frame == 0 || a.frames < 1) return 0;
-  if (a.tiled420) hipLaunchKernelGGL(fdct420_tile_kernel<false>, dim3((unsigned)(a.width >> 7) * (unsigned)(a.height >> 7), a.frames), dim3(256), 0, stream, a);
+  if (a.tiled420) hipLaunchKernelGGL((fdct420_tile_kernel<false, P>), dim3((unsigned)(a.width >> 7) * (unsigned)(a.height >> 7), a.frames), dim3(256), 0, stream, a);
   for (int c = 0; c < a.ncomp; c++) {
     if (!a.fast[c]) continue;
     const unsigned n = (unsigned)a.fast_nbx[c] * (unsigned)a.fast_nby[c];
     if (n == 0) continue;
     const dim3 grid((n + 255) / 256, a.frames);
     const int key = a.subx[c] * 4 + a.suby[c];
-    if (key == 5) hipLaunchKernelGGL((fdct_interior_kernel<1, 1, false>), grid, dim3(256), 0, stream, a, c);
-    else if (key == 10) hipLaunchKernelGGL((fdct_interior_kernel<2, 2, false>), grid, dim3(256), 0, stream, a, c);
-    else if (key == 9) hipLaunchKernelGGL((fdct_interior_kernel<2, 1, false>), grid, dim3(256), 0, stream, a, c);
-    else hipLaunchKernelGGL((fdct_interior_kernel<1, 2, false>), grid, dim3(256), 0, stream, a, c);
+    if (key == 5) hipLaunchKernelGGL((fdct_interior_kernel<1, 1, false, P>), grid, dim3(256), 0, stream, a, c);
+    else if (key == 10) hipLaunchKernelGGL((fdct_interior_kernel<2, 2, false, P>), grid, dim3(256), 0, stream, a, c);
+    else if (key == 9) hipLaunchKernelGGL((fdct_interior_kernel<2, 1, false, P>), grid, dim3(256), 0, stream, a, c);
+    else hipLaunchKernelGGL((fdct_interior_kernel<1, 2, false, P>), grid, dim3(256), 0, stream, a, c);
   }
-  hipLaunchKernelGGL(fdct_blocks_kernel<false>, dim3((per_frame + 255) / 256, a.frames), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL((fdct_blocks_kernel<false, P>), dim3((per_frame + 255) / 256, a.frames), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
+}
+
+int launch_forward(const ForwardArgs &a, int precision, hipStream_t stream)
+{
+  return precision == 12 ? launch_forward_of<12>(a, stream) : launch_forward_of<8>(a, stream);
 }
 
 int forward_ragged_items(const ForwardArgs &a, int which[5], uint32_t wgs[5], int comp[5])
@@ -405,12 +465,12 @@ int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *l
     if (r.items == 0 || p.grid[l] == 0) continue;
     const dim3 grid(p.grid[l]);
     switch (l) {
-    case 0: hipLaunchKernelGGL(fdct420_tile_kernel<true>, grid, dim3(256), 0, stream, r); break;
-    case 1: hipLaunchKernelGGL((fdct_interior_kernel<1, 1, true>), grid, dim3(256), 0, stream, r, 0); break;
-    case 2: hipLaunchKernelGGL((fdct_interior_kernel<2, 2, true>), grid, dim3(256), 0, stream, r, 0); break;
-    case 3: hipLaunchKernelGGL((fdct_interior_kernel<2, 1, true>), grid, dim3(256), 0, stream, r, 0); break;
-    case 4: hipLaunchKernelGGL((fdct_interior_kernel<1, 2, true>), grid, dim3(256), 0, stream, r, 0); break;
-    default: hipLaunchKernelGGL(fdct_blocks_kernel<true>, grid, dim3(256), 0, stream, r); break;
+    case 0: hipLaunchKernelGGL((fdct420_tile_kernel<true, 8>), grid, dim3(256), 0, stream, r); break;
+    case 1: hipLaunchKernelGGL((fdct_interior_kernel<1, 1, true, 8>), grid, dim3(256), 0, stream, r, 0); break;
+    case 2: hipLaunchKernelGGL((fdct_interior_kernel<2, 2, true, 8>), grid, dim3(256), 0, stream, r, 0); break;
+    case 3: hipLaunchKernelGGL((fdct_interior_kernel<2, 1, true, 8>), grid, dim3(256), 0, stream, r, 0); break;
+    case 4: hipLaunchKernelGGL((fdct_interior_kernel<1, 2, true, 8>), grid, dim3(256), 0, stream, r, 0); break;
+    default: hipLaunchKernelGGL((fdct_blocks_kernel<true, 8>), grid, dim3(256), 0, stream, r); break;
     }
     if (launches) ++*launches;
   }

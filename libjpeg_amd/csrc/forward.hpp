@@ -7,7 +7,7 @@
 namespace mij {
 
 struct ForwardArgs {
-  const uint8_t *pixels;          // interleaved 8-bit samples, ncomp per pixel
+  const uint8_t *pixels;          // interleaved samples, ncomp per pixel: 8-bit, or -- precision 12 -- native-endian uint16_t
   int64_t pixel_frame_stride;     // bytes
   int64_t pixel_row_stride;       // bytes
   int16_t *coef;                  // coefficient store, the decoder's layout
@@ -27,7 +27,8 @@ struct ForwardArgs {
   int32_t invq[4][64];            // quantiser multipliers LONG(FLOAT(1 << 30) / delta + 0.5), per component, natural order
 };
 
-int launch_forward(const ForwardArgs &a, hipStream_t stream);
+// precision: 8, or 12 (a.pixels are 16-bit samples 0..4095; strides stay in bytes)
+int launch_forward(const ForwardArgs &a, int precision, hipStream_t stream);
 
 // Ragged flavour: pictures of different sizes and layouts in one launch per kernel family.  Every picture has a filled
 // ForwardArgs of its own in device memory (frames = 1, its own pixels, coefficient store and invq: the 1 KiB of quantiser
@@ -41,6 +42,7 @@ struct ForwardRaggedArgs {
 };
 // The launches of a ragged list, in the order launch_forward_ragged issues them: the 4:2:0 tile kernel, the interior kernels
 // <1,1> <2,2> <2,1> <1,2>, the per-block kernel.  The routing per picture is launch_forward's.
+// (8-bit pictures only: there is no ragged 12-bit flavour)
 constexpr int FORWARD_RAGGED_LAUNCHES = 6;
 struct ForwardRaggedPlan {
   ForwardRaggedArgs launch[FORWARD_RAGGED_LAUNCHES]; // items == 0: not launched

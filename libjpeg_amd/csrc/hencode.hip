@@ -1,4 +1,5 @@
-// hencode.hip -- baseline Huffman entropy coder on the device, so that the coefficients the forward kernels produce
+// hencode.hip -- Huffman-sequential entropy coder (baseline, and the 12-bit extended sequential frames' categories up to 15 / 14:
+// the tables index 16 DC categories and all 256 AC symbols) on the device, so that the coefficients the forward kernels produce
 // never leave HBM: what SequentialScan::WriteMCU / EncodeBlock (codestream/sequentialscan.cpp:430-676) and the byte
 // stuffing bit writer (io/bitstream.hpp) do, restated as data-parallel passes.  Same stream as the host coder of
 // encoder.cpp, byte for byte.
@@ -214,7 +215,10 @@ struct WordWriter {
     fill = (int)(bitpos & 31);
     cur = 0;
   }
-  __device__ __forceinline__ void put(uint32_t bits, int len) // len <= 27
+  // len <= 27.  A code word (<= 16 bits) and the value bits behind it (<= 11, precision 12: <= 15) are put one after the other, so
+  // the 31 bits of the widest 12-bit symbol never arrive in one call; a put that crosses a word boundary ORs `room` bits into the
+  // current word and keeps the other len - room < 32 for the next
+  __device__ __forceinline__ void put(uint32_t bits, int len)
   {
     if (len == 0) return;
     bits &= (1u << len) - 1u;

@@ -6,7 +6,8 @@
 
 namespace mij {
 
-// code word and length per symbol of the four tables of a scan (DC/AC for the first component, DC/AC for the others)
+// code word and length per symbol of the four tables of a scan (DC/AC for the first component, DC/AC for the others); DC categories
+// 0..15 and every AC run/size symbol have a place, so the tables serve 12-bit frames (categories to 15 / 14) as they are
 struct HencTables {
   uint16_t dc_code[2][16];
   uint16_t ac_code[2][256];

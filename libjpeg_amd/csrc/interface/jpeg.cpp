@@ -90,7 +90,8 @@ struct JPEG::Impl {
     return false;
   }
   // encoder direction: the picture as ProvideImage collects it, and its parameters
-  std::vector<uint8_t> picture;
+  std::vector<uint8_t> picture; // interleaved samples: bytes, or -- enc_precision 12 -- native-endian 16-bit words
+  int enc_precision = 8;
   int enc_width = 0, enc_height = 0, enc_depth = 0, enc_quality = 75, enc_restart = 0, enc_lines = 0;
   bool enc_optimize = false, enc_ycbcr = true;
   int32_t enc_hsamp[4] = {1, 1, 1, 1}, enc_vsamp[4] = {1, 1, 1, 1};
@@ -636,10 +637,16 @@ try {
     const JPG_LONG w = tags->GetTagData(JPGTAG_IMAGE_WIDTH, 0), h = tags->GetTagData(JPGTAG_IMAGE_HEIGHT, 0), depth = tags->GetTagData(JPGTAG_IMAGE_DEPTH, 3);
     const JPG_LONG prec = tags->GetTagData(JPGTAG_IMAGE_PRECISION, 8), type = tags->GetTagData(JPGTAG_IMAGE_FRAMETYPE, JPGFLAG_BASELINE);
     if (w < 1 || h < 1 || w > 65535 || h > 65535) return p->fail(JPGERR_OVERFLOW_PARAMETER, "image dimensions must be between 1 and 65535");
-    if ((depth != 1 && depth != 3) || prec != 8) return p->fail(JPGERR_NOT_IMPLEMENTED, "the accelerated encoder handles 8-bit images of one or three components");
+    // precisions as the reference's encoder takes them: 9..11 are no JPEG precisions, 12 is not a baseline one (both -1024);
+    // beyond 12 it would write JPEG XT
+    if (prec > 8 && prec < 12) return p->fail(JPGERR_INVALID_PARAMETER, "JPEG supports only 8 or 12 bit sample precision");
+    if (prec == 12 && (type & ~JPGFLAG_OPTIMIZE_HUFFMAN) == JPGFLAG_BASELINE)
+      return p->fail(JPGERR_INVALID_PARAMETER, "baseline Huffman coding only supports 8bpp scans");
+    if ((depth != 1 && depth != 3) || (prec != 8 && prec != 12))
+      return p->fail(JPGERR_NOT_IMPLEMENTED, "the accelerated encoder handles 8-bit and 12-bit images of one or three components");
     if ((type & ~JPGFLAG_OPTIMIZE_HUFFMAN) != JPGFLAG_BASELINE && (type & ~JPGFLAG_OPTIMIZE_HUFFMAN) != JPGFLAG_SEQUENTIAL)
       return p->fail(JPGERR_NOT_IMPLEMENTED, "the accelerated encoder writes baseline / sequential Huffman frames only");
-    p->enc_width = w; p->enc_height = h; p->enc_depth = depth;
+    p->enc_width = w; p->enc_height = h; p->enc_depth = depth; p->enc_precision = (int)prec;
     p->enc_optimize = (type & JPGFLAG_OPTIMIZE_HUFFMAN) != 0;
     p->enc_quality = tags->GetTagData(JPGTAG_IMAGE_QUALITY, 75);
     p->enc_restart = tags->GetTagData(JPGTAG_IMAGE_RESTART_INTERVAL, 0);
@@ -659,7 +666,7 @@ try {
       p->enc_hsamp[c] = mx / sx;
       p->enc_vsamp[c] = my / sy;
     }
-    p->picture.assign((size_t)w * (size_t)h * (size_t)depth, 0);
+    p->picture.assign((size_t)w * (size_t)h * (size_t)depth * (prec == 12 ? 2 : 1), 0);
     p->enc_lines = 0;
   }
   struct JPG_Hook *bmh = (struct JPG_Hook *)tags->GetTagPtr(JPGTAG_BIH_HOOK, nullptr);
@@ -678,7 +685,7 @@ try {
           JPG_ValueTag(JPGTAG_BIO_HEIGHT, 0),
           JPG_ValueTag(JPGTAG_BIO_BYTESPERROW, 0),
           JPG_ValueTag(JPGTAG_BIO_BYTESPERPIXEL, 0),
-          JPG_ValueTag(JPGTAG_BIO_PIXELTYPE, CTYP_UBYTE),
+          JPG_ValueTag(JPGTAG_BIO_PIXELTYPE, p->enc_precision == 12 ? CTYP_UWORD : CTYP_UBYTE),
           JPG_ValueTag(JPGTAG_BIO_ROI, 0),
           JPG_ValueTag(JPGTAG_BIO_COMPONENT, c),
           JPG_PointerTag(JPGTAG_BIO_USERDATA, nullptr),
@@ -698,11 +705,20 @@ try {
       if (r < 0) return p->fail(r, "BitMapHook signalled an error");
       const unsigned char *mem = (const unsigned char *)ht[1].ti_Data.ti_pPtr;
       const JPG_LONG bpr = ht[4].ti_Data.ti_lData, bpp = ht[5].ti_Data.ti_lData, type = ht[6].ti_Data.ti_lData;
+      if (p->enc_precision == 12) {
+        if (!mem || type != CTYP_UWORD) return p->fail(JPGERR_INVALID_PARAMETER, "the accelerated encoder expects CTYP_UWORD pixel data from the bitmap hook for 12-bit images");
+        for (JPG_LONG y = miny; y <= maxy; y++) { // mem is the address of canvas pixel (0,0)
+          const unsigned char *src = mem + (ptrdiff_t)y * bpr;
+          unsigned char *dst = p->picture.data() + (((size_t)y * (size_t)w) * (size_t)nc + (size_t)c) * 2;
+          for (int x = 0; x < w; x++) memcpy(dst + (size_t)x * (size_t)nc * 2, src + (ptrdiff_t)x * bpp, 2);
+        }
+      } else {
       if (!mem || type != CTYP_UBYTE) return p->fail(JPGERR_INVALID_PARAMETER, "the accelerated encoder expects CTYP_UBYTE pixel data from the bitmap hook");
       for (JPG_LONG y = miny; y <= maxy; y++) { // mem is the address of canvas pixel (0,0)
         const unsigned char *src = mem + (ptrdiff_t)y * bpr;
         unsigned char *dst = p->picture.data() + ((size_t)y * (size_t)w) * (size_t)nc + (size_t)c;
         for (int x = 0; x < w; x++) dst[(size_t)x * (size_t)nc] = src[(ptrdiff_t)x * bpp];
+      }
       }
       ht[0].ti_Data.ti_lData = JPGFLAG_BIO_RELEASE;
       r = bmh->CallLong(ht);
@@ -724,7 +740,10 @@ try {
   if (!io) return p->fail(JPGERR_MISSING_PARAMETER, "no I/O hook (JPGTAG_HOOK_IOHOOK) specified");
   uint8_t *stream = nullptr;
   size_t size = 0;
-  const int rc = mijpeg_encode_image(p->dec, p->picture.data(), p->enc_width, p->enc_height, p->enc_depth, (int64_t)p->enc_width * p->enc_depth, p->enc_quality,
+  const int rc = p->enc_precision == 12
+                     ? mijpeg_encode_image16(p->dec, (const uint16_t *)p->picture.data(), p->enc_width, p->enc_height, p->enc_depth,
+                                             (int64_t)p->enc_width * p->enc_depth * 2, 12, p->enc_quality, p->enc_hsamp, p->enc_vsamp, p->enc_restart, 0, &stream, &size)
+                     : mijpeg_encode_image(p->dec, p->picture.data(), p->enc_width, p->enc_height, p->enc_depth, (int64_t)p->enc_width * p->enc_depth, p->enc_quality,
                                      p->enc_hsamp, p->enc_vsamp, p->enc_restart, p->enc_optimize ? 1 : 0, &stream, &size);
   if (rc) return p->fail_from_decoder(rc);
   for (size_t at = 0; at < size;) { // io/iostream.cpp: the stream goes out through the hook in pieces
