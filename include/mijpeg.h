@@ -604,12 +604,13 @@ int mijpeg_encode_batch_device(mijpeg_decoder *d, const mijpeg_forward_batch *ba
  * with n.  Lists of equally shaped frames are served by mijpeg_encode_batch_device as well.  Which of the two is faster for them
  * HAS NOT BEEN MEASURED (profiles/ragged_encode.txt, section 3): until it has, uniform lists are better served by the uniform
  * call, whose cost is known. */
-/* The ragged calls take 8-bit pictures only: mijpeg_encode_frame has no precision field and its layout is not touched.  12-bit
- * pictures go through mijpeg_encode_image16 or mijpeg_encode_batch_device. */
+/* mijpeg_encode_frame has no precision field and its layout is not touched: the calls above take 8-bit pictures, and lists with
+ * 12-bit pictures in them go through the ...16 flavours below, which take the precision of every picture in a parallel array. */
 typedef struct mijpeg_encode_frame {
   const uint8_t *pixels;     /* interleaved 8-bit samples, `components` per pixel: device memory for mijpeg_encode_ragged_device,
-                                host memory for mijpeg_encode_ragged; the planner does not look at it                          */
-  int64_t row_stride;        /* bytes per line, >= width * components                                                           */
+                                host memory for mijpeg_encode_ragged; the planner does not look at it.  A 12-bit picture of the
+                                ...16 calls: native-endian uint16_t samples 0..4095 at an even address                          */
+  int64_t row_stride;        /* bytes per line, >= width * components (12-bit picture: even, >= width * components * 2)         */
   int32_t width, height;     /* 1 .. 65535                                                                                      */
   int32_t components;        /* 1 (grey) or 3 (RGB in, YCbCr coded)                                                             */
   int32_t hsamp[MIJPEG_MAX_COMPONENTS], vsamp[MIJPEG_MAX_COMPONENTS]; /* sampling factors per component, 1 .. 4                 */
@@ -620,7 +621,8 @@ typedef struct mijpeg_encode_frame {
 /* What the planner decides for picture i.  A list is cut into PASSES where it would exceed the coder's limits (pass_blocks
  * below); the index spaces start again in every pass. */
 typedef struct mijpeg_encode_ragged_item {
-  mijpeg_info info;          /* the frame as mijpeg_frame_layout completes it, the tables of `quality` in quant[0], quant[1]     */
+  mijpeg_info info;          /* the frame as mijpeg_frame_layout completes it at the picture's precision, the tables of `quality`
+                                in quant[0], quant[1]                                                                            */
   int64_t coef_base;         /* int16 index of its coefficient store in the pass's packed scratch store                         */
   uint32_t blocks;           /* blocks of its scan (MCUs * blocks per MCU)                                                       */
   uint32_t intervals;        /* restart intervals of its scan (1 without restart markers)                                        */
@@ -657,15 +659,32 @@ int mijpeg_encode_ragged(mijpeg_decoder *d, const mijpeg_encode_frame *frames, i
 typedef struct mijpeg_encode_ragged_stats {
   int32_t pictures;
   int32_t passes;
-  int32_t forward_launches;  /* ragged forward kernels, at most six per pass                                                     */
+  int32_t forward_launches;  /* ragged forward kernels, at most six per pass for each precision present: at most twelve          */
   int32_t coder_launches;    /* count, prefix-sum, interval, gather, emit and stuffing kernels, summed (a prefix sum takes one,
                                 three or five launches with the SIZE of its input)                                               */
   int32_t host_syncs;        /* host waits for the device: per pass one for the plain sizes, one for the 0xFF counts, one for the
-                                download, one more for the statistics with optimize (buffers that grow wait as well: not counted) */
+                                download, one more for the statistics in a pass with optimize or with a 12-bit picture in it (an
+                                8-bit pass without optimize stays at three; buffers that grow wait as well: not counted)         */
   int32_t reserved;
   int64_t bytes_downloaded;  /* the output arenas                                                                                */
 } mijpeg_encode_ragged_stats;
 int mijpeg_encode_ragged_get_stats(mijpeg_decoder *d, mijpeg_encode_ragged_stats *out);
+
+/* The same three calls for lists in which every picture is 8-bit or 12-bit, freely mixed.  precision: NULL = 8 for every picture
+ * (the calls above are these with NULL), otherwise precision[i] is 8 or 12 -- anything else is MIJPEG_ERR_INVALID_PARAMETER.  For a
+ * 12-bit picture frames[i].pixels addresses interleaved native-endian uint16_t samples, 0..4095, on a 2-byte boundary, and
+ * row_stride (still bytes) is even and at least width * components * 2; a violation is MIJPEG_ERR_INVALID_PARAMETER with all
+ * outputs cleared as above.  Stream i is byte for byte what mijpeg_encode_image16 (flags 0) writes for a 12-bit picture -- an
+ * extended sequential frame, SOF1 with P = 12, the reference's quantiser tables for 12-bit frames (16-bit DQT entries at low
+ * qualities) -- and what mijpeg_encode_image_ex writes for an 8-bit one.  12-bit pictures always get Huffman tables from their
+ * own statistics, as everywhere else at precision 12; `optimize` speaks for the 8-bit pictures of the list only, which keep the
+ * Annex K.3 tables without it.  Blocks, intervals, index spaces, pass cuts and coef_base of the plan do not depend on precision. */
+int mijpeg_encode_ragged_plan16(const mijpeg_encode_frame *frames, const int32_t *precision, int n, uint32_t pass_blocks,
+                                mijpeg_encode_ragged_item *items, mijpeg_encode_ragged_totals *totals);
+int mijpeg_encode_ragged_device16(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int32_t *precision, int n,
+                                  int optimize, uint32_t flags, uint8_t **streams, size_t *sizes);
+int mijpeg_encode_ragged16(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int32_t *precision, int n,
+                           int optimize, uint32_t flags, uint8_t **streams, size_t *sizes);
 
 /* Worker threads mijpeg_decode_coefficients uses for threads <= 0 (MIJPEG_THREADS overrides; default min(cores, 64)). */
 int mijpeg_default_threads(void);

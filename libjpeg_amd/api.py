@@ -184,6 +184,9 @@ def lib():
         L.mijpeg_encode_ragged_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_encode_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_encode_ragged_get_stats.argtypes = [C.c_void_p, P(MijpegEncodeRaggedStats)]
+        L.mijpeg_encode_ragged_plan16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mijpeg_encode_ragged_device16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mijpeg_encode_ragged16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_free.argtypes = [C.c_void_p]
         L.mijpeg_free.restype = None
         L.mijpeg_device_walk_rounds.argtypes = [C.c_void_p]
@@ -397,33 +400,44 @@ class Decoder:
             L.mijpeg_free(ptrs[f])
         return out
 
-    def _encode_ragged(self, fn, frames, optimize: bool, flags: int = 0):
+    def _encode_ragged(self, fn, frames, optimize: bool, flags: int = 0, precision=None):
+        """fn: one of the ragged encode entry points; with `precision` (8 or 12 per picture) its ...16 flavour."""
         n = len(frames)
         arr = (MijpegEncodeFrame * max(n, 1))(*frames)
         ptrs, sizes = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))()
-        self._check(fn(self._h, arr, n, 1 if optimize else 0, flags, ptrs, sizes))
+        if precision is None:
+            self._check(fn(self._h, arr, n, 1 if optimize else 0, flags, ptrs, sizes))
+        else:
+            self._check(fn(self._h, arr, _precision_array(precision, n), n, 1 if optimize else 0, flags, ptrs, sizes))
         out = []
         for i in range(n):
             out.append(C.string_at(ptrs[i], sizes[i]))
             lib().mijpeg_free(ptrs[i])
         return out
 
-    def encode_ragged_device(self, frames, optimize: bool = False):
+    def encode_ragged_device(self, frames, optimize: bool = False, precision=None):
         """mijpeg_encode_ragged_device: MijpegEncodeFrame descriptions (api.encode_frame) of pictures resident in HBM -> list of
-        baseline JPEG streams, each what `encode` writes for that picture; launches and host waits do not grow with the list."""
+        baseline JPEG streams, each what `encode` writes for that picture; launches and host waits do not grow with the list.
+        precision: 8 or 12 per picture (mijpeg_encode_ragged_device16: a 12-bit picture's pixels are uint16 samples, its row stride
+        counts bytes, its stream is extended sequential and its Huffman tables are its own whatever `optimize` says)."""
         _foreign_work_done()
-        return self._encode_ragged(lib().mijpeg_encode_ragged_device, frames, optimize)
+        if precision is None:
+            return self._encode_ragged(lib().mijpeg_encode_ragged_device, frames, optimize)
+        return self._encode_ragged(lib().mijpeg_encode_ragged_device16, frames, optimize, precision=precision)
 
     def encode_ragged(self, images, quality=85, subsampling="444", restart_mcus=0, optimize: bool = False):
-        """mijpeg_encode_ragged: (H, W, 3) / (H, W) uint8 arrays in host memory -> list of baseline JPEG streams.  quality,
-        subsampling (a name of ENCODE_LAYOUTS) and restart_mcus: one value for all or a list with one per picture."""
-        imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+        """mijpeg_encode_ragged16: (H, W, 3) / (H, W) arrays in host memory -> list of JPEG streams.  uint16 arrays are 12-bit
+        pictures (samples 0..4095 -> extended sequential streams), everything else is taken as uint8 (-> baseline streams); both
+        may appear in one list.  quality, subsampling (a name of ENCODE_LAYOUTS) and restart_mcus: one value for all or a list
+        with one per picture."""
+        imgs = [np.ascontiguousarray(im, np.uint16 if np.asarray(im).dtype == np.uint16 else np.uint8) for im in images]
         per = lambda v, i: v[i] if isinstance(v, (list, tuple)) else v
         frames = []
         for i, im in enumerate(imgs):
             nc = 1 if im.ndim == 2 or im.shape[2] == 1 else im.shape[2]
-            frames.append(encode_frame(im.shape[1], im.shape[0], nc, per(quality, i), per(subsampling, i), per(restart_mcus, i), im.ctypes.data))
-        return self._encode_ragged(lib().mijpeg_encode_ragged, frames, optimize)
+            frames.append(encode_frame(im.shape[1], im.shape[0], nc, per(quality, i), per(subsampling, i), per(restart_mcus, i), im.ctypes.data,
+                                       im.shape[1] * nc * im.itemsize))
+        return self._encode_ragged(lib().mijpeg_encode_ragged16, frames, optimize, precision=[12 if im.itemsize == 2 else 8 for im in imgs])
 
     def encode_ragged_stats(self) -> dict:
         st = MijpegEncodeRaggedStats()
@@ -853,13 +867,25 @@ def ragged_plan(infos):
     return list(group), list(frames), list(grids), total.value
 
 
-def encode_ragged_plan(frames, pass_blocks: int = 0):
-    """mijpeg_encode_ragged_plan (no device needed): MijpegEncodeFrame descriptions -> (MijpegEncodeRaggedItem per picture, totals)."""
+def _precision_array(precision, n: int):
+    """The parallel precision array of the ...16 ragged encode calls: one value for all pictures or one per picture."""
+    values = [int(precision)] * n if np.ndim(precision) == 0 else [int(p) for p in precision]
+    if len(values) != n:
+        raise ValueError(f"{len(values)} precisions for {n} pictures")
+    return (C.c_int32 * max(n, 1))(*values)
+
+
+def encode_ragged_plan(frames, pass_blocks: int = 0, precision=None):
+    """mijpeg_encode_ragged_plan (no device needed): MijpegEncodeFrame descriptions -> (MijpegEncodeRaggedItem per picture, totals).
+    precision: 8 or 12 per picture (mijpeg_encode_ragged_plan16); None: 8-bit pictures."""
     n = len(frames)
     arr = (MijpegEncodeFrame * max(n, 1))(*frames)
     items = (MijpegEncodeRaggedItem * max(n, 1))()
     totals = MijpegEncodeRaggedTotals()
-    rc = lib().mijpeg_encode_ragged_plan(arr, n, pass_blocks, items, C.byref(totals))
+    if precision is None:
+        rc = lib().mijpeg_encode_ragged_plan(arr, n, pass_blocks, items, C.byref(totals))
+    else:
+        rc = lib().mijpeg_encode_ragged_plan16(arr, _precision_array(precision, n), n, pass_blocks, items, C.byref(totals))
     if rc:
         raise MijpegError(rc, "mijpeg_encode_ragged_plan failed")
     return list(items)[:n], totals

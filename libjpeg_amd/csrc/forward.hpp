@@ -40,13 +40,16 @@ struct ForwardRaggedArgs {
   const uint32_t *item;      // device, per item: picture * 4 + component
   uint32_t items;
 };
-// The launches of a ragged list, in the order launch_forward_ragged issues them: the 4:2:0 tile kernel, the interior kernels
-// <1,1> <2,2> <2,1> <1,2>, the per-block kernel.  The routing per picture is launch_forward's.
-// (8-bit pictures only: there is no ragged 12-bit flavour)
+// The launches of a ragged list of one precision, in the order launch_forward_ragged issues them: the 4:2:0 tile kernel, the interior
+// kernels <1,1> <2,2> <2,1> <1,2>, the per-block kernel.  The routing per picture is launch_forward's.
+// Precision is a property of the picture: the 8-bit pictures of a list have their work lists (0 .. 5), the 12-bit pictures theirs
+// (6 .. 11, forward_ragged_list), so a workgroup never sees pictures of two precisions and a list of both costs at most twelve launches.
 constexpr int FORWARD_RAGGED_LAUNCHES = 6;
+constexpr int FORWARD_RAGGED_LISTS = 2 * FORWARD_RAGGED_LAUNCHES;
+inline int forward_ragged_list(int which, int precision) { return which + (precision == 12 ? FORWARD_RAGGED_LAUNCHES : 0); }
 struct ForwardRaggedPlan {
-  ForwardRaggedArgs launch[FORWARD_RAGGED_LAUNCHES]; // items == 0: not launched
-  uint32_t grid[FORWARD_RAGGED_LAUNCHES];
+  ForwardRaggedArgs launch[FORWARD_RAGGED_LISTS]; // items == 0: not launched
+  uint32_t grid[FORWARD_RAGGED_LISTS];
 };
 // The work items picture `a` contributes: wgs[k] workgroups and item component comp[k] per entry, launch index which[k]; returns
 // the number of entries (at most 5).  Host side of the routing rule, shared by the planner and the launcher.

@@ -152,6 +152,9 @@ __global__ __launch_bounds__(256) void henc_count_kernel(const typename F::Args 
   uint32_t pic = 0; // (a picture's blocks are padded to whole workgroups: uniform)
   if constexpr (F::BATCH) pic = find_picture(k, k.first_block, blockIdx.x * blockDim.x);
   const HencArgs &a = args_of(k, pic);
+  // a list may hold pictures that keep the shared tables beside pictures that get their own (8-bit pictures without optimised
+  // tables beside 12-bit ones): the statistics launch skips the former -- the whole workgroup, its picture is uniform
+  if (STATS && F::BATCH && !a.hist) return;
   load_tables(&tab, a.tables);
   if (STATS) {
     for (unsigned i = threadIdx.x; i < 4 * 256; i += blockDim.x) hist[i] = 0;

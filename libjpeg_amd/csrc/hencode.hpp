@@ -35,7 +35,8 @@ struct HencArgs {
   uint32_t *ffcount;            // per HENC_STUFF_CHUNK bytes of the plain stream: 0xFF bytes in them
   const uint64_t *ffstart;      // exclusive prefix sums of ffcount (chunks + 1 entries)
   uint8_t *out;                 // entropy coded data with stuffing and RSTn markers
-  uint32_t *hist;               // optional statistics: [2][256] DC symbol counts, [2][256] AC symbol counts
+  uint32_t *hist;               // optional statistics: [2][256] DC symbol counts, [2][256] AC symbol counts (null in a list: the
+                                // picture takes no part in the statistics launch)
 };
 
 // Batch-wide flavour (encode_device.cpp): ONE launch of every pass over all pictures of a list.  Every picture has an argument
