@@ -559,6 +559,23 @@ int mijpeg_encode_coefficients(const mijpeg_info *info, const int16_t *coef, int
                                uint8_t **stream, size_t *size);
 void mijpeg_free(void *p);
 
+/* The device twin of mijpeg_encode_coefficients: the planes are in DEVICE memory (coef_dev, the layout of *info: what
+ * mijpeg_launch_forward writes and what mijpeg_device_coefficients returns), the device entropy coder (hencode.hip) codes them,
+ * and only the finished stream comes down -- byte for byte the stream mijpeg_encode_coefficients writes for the same planes,
+ * restart interval and `optimize` (precision 12: the tables are always the picture's own).  So a stream that was entropy-decoded on
+ * the device can be coded again with another restart interval or with optimised tables without its coefficients leaving HBM.
+ * The caller wrote the coefficients, so they are checked as the host coder checks them: a DC difference beyond category 11 (15 at
+ * precision 12) or an AC coefficient beyond category 10 (14) is MIJPEG_ERR_OVERFLOW_PARAMETER and no stream, whatever int16
+ * values stand there; the object serves the next call as usual.  The check takes the symbol statistics in a launch of its own,
+ * which with `optimize` (or precision 12) are the statistics the tables are built from anyway; with the standard tables it costs
+ * one launch and one host synchronisation more than the pixel entry points spend.  Arguments are checked before a device is
+ * touched: null pointers, a restart interval outside 0..65535 (INVALID_PARAMETER), a precision other than 8 or 12 or a
+ * component count other than 1 or 3 (OPERATION_UNIMPLEMENTED), more than 64 blocks per MCU or more than 2^30 - 1025 blocks
+ * (NOT_AVAILABLE), an object without a device (NOT_AVAILABLE).  coef_dev must not have work pending on other streams.
+ * *stream is malloc'ed (mijpeg_free).  mijpeg_last_timing: [0] the whole call. */
+int mijpeg_encode_coefficients_device(mijpeg_decoder *d, const mijpeg_info *info, const int16_t *coef_dev, int restart_interval,
+                                      int optimize, uint8_t **stream, size_t *size);
+
 /* The quantiser tables the reference encoder derives from `-q quality` with its default (Annex K) matrices:
  * Quantization::InitDefaultTables, marker/quantization.cpp:275-466, for 8-bit frames -- natural order. */
 void mijpeg_quality_tables(int quality, uint16_t luma[64], uint16_t chroma[64]);

@@ -400,6 +400,21 @@ class Decoder:
             L.mijpeg_free(ptrs[f])
         return out
 
+    def encode_coefficients_device(self, info: MijpegInfo, coef_dev: int, restart_interval: int = 0, optimize: bool = False) -> bytes:
+        """mijpeg_encode_coefficients_device: quantised coefficient planes resident in HBM (int16, the layout of `info`: what
+        device_coefficients() returns after a device entropy decode) -> the stream encode_coefficients writes for the same planes."""
+        _foreign_work_done()
+        L = lib()
+        L.mijpeg_encode_coefficients_device.argtypes = [C.c_void_p, C.POINTER(MijpegInfo), C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                                        C.POINTER(C.c_size_t)]
+        L.mijpeg_free.argtypes = [C.c_void_p]
+        p, n = C.c_void_p(), C.c_size_t()
+        self._check(L.mijpeg_encode_coefficients_device(self._h, C.byref(info), coef_dev, restart_interval, 1 if optimize else 0, C.byref(p), C.byref(n)))
+        try:
+            return C.string_at(p, n.value)
+        finally:
+            L.mijpeg_free(p)
+
     def _encode_ragged(self, fn, frames, optimize: bool, flags: int = 0, precision=None):
         """fn: one of the ragged encode entry points; with `precision` (8 or 12 per picture) its ...16 flavour."""
         n = len(frames)

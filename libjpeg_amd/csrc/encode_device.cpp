@@ -140,8 +140,10 @@ struct Carver { // lays regions out in a buffer, 256-byte aligned
   }
 };
 
-// what an exclusive_scan_u32 over n elements needs as scratch (hencode.hip)
-size_t scan_scratch_bytes(size_t n) { return ((n / 1024 + 8) * 2 + 8192) * 8; }
+// what an exclusive_scan_u32 over n elements needs as scratch (ScanLayout, hencode.hpp), rounded up; n beyond the scan's reach: the
+// scan refuses whatever it is given
+size_t scan_scratch_bytes(size_t n) { return (size_t)(scan_layout((uint32_t)std::min<size_t>(n, HENC_SCAN_MAX)).words + 32) * 8; }
+size_t scan_scratch_words(size_t n) { return scan_scratch_bytes(n) / 8; }
 
 // The frame of a picture to encode: its layout and the tables of its quality (hsamp, vsamp: null = 1 x 1 throughout).  What
 // mijpeg_frame_layout says to it.
@@ -213,7 +215,8 @@ struct HencJob {
   HencArgs a;
   EncTables tabs;
   uint64_t *readback = nullptr; // pinned: [0] plain bytes, [1] 0xFF bytes
-  uint64_t *scratch = nullptr;
+  uint64_t *scratch = nullptr; // of the scans over blocks and intervals (stage_a); the scan over chunks has its own (stage_b)
+  size_t scratch_words = 0;
   uint32_t chunks = 0;
   uint8_t *result = nullptr;
   size_t result_size = 0;
@@ -227,8 +230,13 @@ struct HencJob {
     return MIJPEG_OK;
   }
 
-  // geometry, buffers, tables (optimised ones cost a synchronisation of their own), then count + prefix sums
-  int stage_a(mijpeg_decoder *dec, const mijpeg_info &info, const int16_t *coef_dev, int ri, int optimize, int slot_, hipStream_t st)
+  // geometry, buffers, tables (optimised ones cost a synchronisation of their own), then count + prefix sums.
+  // check_range: the coefficients are the caller's own (mijpeg_encode_coefficients_device), not the forward kernels': the symbol
+  // statistics are always taken, by the survey kernel that is safe for any int16 content, and a DC difference or an AC coefficient
+  // beyond what a frame of this precision codes (encoder.cpp code_block: categories 11 / 10, precision 12: 15 / 14) is refused
+  // before any kernel looks a code up.  One launch and one synchronisation more where the tables are the standard ones.
+  int stage_a(mijpeg_decoder *dec, const mijpeg_info &info, const int16_t *coef_dev, int ri, int optimize, int slot_, hipStream_t st,
+              bool check_range = false)
   {
     d = dec; f = &info; slot = slot_; stream = st; restart_interval = ri;
     const int nc = info.components;
@@ -237,7 +245,7 @@ struct HencJob {
     if (!henc_frame_geometry(a, info, ri)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device entropy coder");
     const int B = a.blocks_per_mcu;
     const uint64_t nblocks = (uint64_t)a.total_mcus * (uint64_t)B;
-    if (nblocks >= ((uint64_t)1 << 30)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "frame too large for the device entropy coder");
+    if (nblocks > HENC_SCAN_MAX) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "frame too large for the device entropy coder"); // (2^30 - 1025 blocks)
     a.total_blocks = (uint32_t)nblocks;
     a.n_intervals = (uint32_t)((a.total_mcus + a.ri - 1) / a.ri);
     const uint32_t N = a.total_blocks, I = a.n_intervals;
@@ -249,7 +257,8 @@ struct HencJob {
     const size_t o_bitpos = ar.take(((size_t)N + 1) * 8);
     const size_t o_ibytes = ar.take((size_t)I * 4);
     const size_t o_istart = ar.take(((size_t)I + 1) * 8);
-    const size_t o_scratch = ar.take(scan_scratch_bytes(N));
+    const size_t o_scratch = ar.take(scan_scratch_bytes(N)); // (for the blocks, then for the intervals: never more of them than blocks)
+    scratch_words = scan_scratch_words(N);
     int rc = ensure_dev(d, (void **)&d->henc_dev[slot], &d->henc_cap[slot], ar.at);
     if (rc) return rc;
     if (!d->henc_host) HIP_TRY(d, hipHostMalloc((void **)&d->henc_host, 64 + 2 * sizeof(HencTables), hipHostMallocDefault));
@@ -266,20 +275,30 @@ struct HencJob {
     rc = upload_tables();
     if (rc) return rc;
     // precision 12: the Annex K.3 tables have no codes for categories 12..15, so the tables are always the picture's own
-    if (optimize || info.precision == 12) { // symbol statistics first, tables from them (Annex K.2)
+    const bool own_tables = optimize || info.precision == 12;
+    if (own_tables || check_range) { // symbol statistics first, tables from them (Annex K.2)
       HIP_TRY(d, hipMemsetAsync(base + o_hist, 0, 4 * 256 * 4, stream));
-      if (henc_count(a, true, stream)) return hip_fail(d, hipGetLastError(), "henc_count_kernel launch");
+      if (check_range ? henc_survey(a, stream) : henc_count(a, true, stream)) return hip_fail(d, hipGetLastError(), "statistics kernel launch");
       uint32_t hist[4][256];
       HIP_TRY(d, hipMemcpyAsync(hist, base + o_hist, sizeof(hist), hipMemcpyDeviceToHost, stream));
       HIP_TRY(d, hipStreamSynchronize(stream));
-      enc_optimal_tables(tabs, hist, hist + 2, nc > 1 ? 2 : 1);
-      rc = upload_tables();
-      if (rc) return rc;
+      if (check_range) {
+        const int dc_max = info.precision == 12 ? 15 : 11, ac_max = info.precision == 12 ? 14 : 10;
+        bool beyond = false;
+        for (int t = 0; t < 2; t++)
+          for (int i = 0; i < 256; i++) beyond |= (hist[t][i] && i > dc_max) || (hist[2 + t][i] && (i & 15) > ac_max);
+        if (beyond) return set_error(d, MIJPEG_ERR_OVERFLOW_PARAMETER, "coefficients outside what a frame of this precision can hold");
+      }
+      if (own_tables) {
+        enc_optimal_tables(tabs, hist, hist + 2, nc > 1 ? 2 : 1);
+        rc = upload_tables();
+        if (rc) return rc;
+      }
     }
     if (henc_count(a, false, stream)) return hip_fail(d, hipGetLastError(), "henc_count_kernel launch");
-    if (exclusive_scan_u32(a.bits, (uint64_t *)a.bitpos, N, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
+    if (const int e = exclusive_scan_u32(a.bits, (uint64_t *)a.bitpos, N, scratch, scratch_words, stream)) return hip_fail(d, (hipError_t)e, "scan over the blocks");
     if (henc_interval_bytes(a, stream)) return hip_fail(d, hipGetLastError(), "henc_interval_bytes_kernel launch");
-    if (exclusive_scan_u32(a.ibytes, (uint64_t *)a.istart, I, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
+    if (const int e = exclusive_scan_u32(a.ibytes, (uint64_t *)a.istart, I, scratch, scratch_words, stream)) return hip_fail(d, (hipError_t)e, "scan over the intervals");
     HIP_TRY(d, hipMemcpyAsync(&readback[0], a.istart + I, 8, hipMemcpyDeviceToHost, stream));
     return MIJPEG_OK;
   }
@@ -298,6 +317,7 @@ struct HencJob {
     const size_t q_ffc = ar.take((size_t)chunks * 4 + 4);
     const size_t q_ffs = ar.take(((size_t)chunks + 1) * 8);
     const size_t q_out = ar.take((size_t)plain_bytes * 2 + (size_t)I * 2 + 16);
+    const size_t q_scratch = ar.take(scan_scratch_bytes(chunks)); // (the chunks may outnumber the blocks: a scratch of their own)
     const int rc = ensure_dev(d, (void **)&d->henc_out_dev[slot], &d->henc_out_cap[slot], ar.at);
     if (rc) return rc;
     uint8_t *ob = d->henc_out_dev[slot];
@@ -309,7 +329,8 @@ struct HencJob {
     HIP_TRY(d, hipMemsetAsync(ob + q_plain, 0, q_ffc - q_plain, stream)); // (the region with its padding)
     if (henc_emit(a, stream)) return hip_fail(d, hipGetLastError(), "henc_emit_kernel launch");
     if (henc_count_ff(a, stream)) return hip_fail(d, hipGetLastError(), "henc_count_ff_kernel launch");
-    if (exclusive_scan_u32(a.ffcount, (uint64_t *)a.ffstart, chunks, scratch, stream)) return hip_fail(d, hipGetLastError(), "scan launch");
+    if (const int e = exclusive_scan_u32(a.ffcount, (uint64_t *)a.ffstart, chunks, (uint64_t *)(ob + q_scratch), scan_scratch_words(chunks), stream))
+      return hip_fail(d, (hipError_t)e, "scan over the chunks");
     if (henc_stuff(a, stream)) return hip_fail(d, hipGetLastError(), "henc_stuff_kernel launch");
     HIP_TRY(d, hipMemcpyAsync(&readback[1], a.ffstart + chunks, 8, hipMemcpyDeviceToHost, stream));
     return MIJPEG_OK;
@@ -340,10 +361,10 @@ struct HencJob {
 };
 
 int device_entropy_code(mijpeg_decoder *d, const mijpeg_info &f, const int16_t *coef_dev, int restart_interval, int optimize,
-                               uint8_t **stream, size_t *size)
+                               uint8_t **stream, size_t *size, bool check_range = false)
 {
   HencJob job;
-  int rc = job.stage_a(d, f, coef_dev, restart_interval, optimize, 0, d->stream);
+  int rc = job.stage_a(d, f, coef_dev, restart_interval, optimize, 0, d->stream, check_range);
   if (!rc) rc = job.stage_b();
   if (!rc) rc = job.stage_c();
   if (!rc) rc = job.finish(stream, size);
@@ -422,15 +443,20 @@ int plan_list(const mijpeg_encode_frame *frames, const int32_t *precision, int n
 // ragged encode: one pass on the device
 // ------------------------------------------------------------------------------------------------
 // launches of an exclusive_scan_u32 over n elements (hencode.hip)
-int scan_launches(uint32_t n)
+constexpr int scan_launches(uint32_t n)
 {
   const uint32_t t1 = n / 1024 + 1;
   return t1 == 1 ? 1 : t1 / 1024 + 1 == 1 ? 3 : 5;
 }
+static_assert(scan_launches(0) == scan_layout(0).launches && scan_launches(1023) == scan_layout(1023).launches &&
+                  scan_launches(1024) == scan_layout(1024).launches && scan_launches((1u << 20) - 1025) == scan_layout((1u << 20) - 1025).launches &&
+                  scan_launches((1u << 20) - 1024) == scan_layout((1u << 20) - 1024).launches && scan_launches(1u << 20) == scan_layout(1u << 20).launches &&
+                  scan_launches((1u << 30) - 1) == scan_layout((1u << 30) - 1).launches,
+              "the launches the statistics count are the launches the scan makes");
 
 #define LAUNCHED(d, call, what, count)                                          \
   do {                                                                          \
-    if (call) return hip_fail(d, hipGetLastError(), what " launch");            \
+    if (const int e_ = (call)) return hip_fail(d, (hipError_t)e_, what " launch"); \
     (d)->eragged_stats.coder_launches += (count);                               \
   } while (0)
 
@@ -509,6 +535,7 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   const size_t o_ibytes = dv.take((size_t)I * 4);
   const size_t o_istart = dv.take(((size_t)I + 1) * 8);
   const size_t o_scratch = dv.take(scan_scratch_bytes(N));
+  const size_t scratch_words = scan_scratch_words(N);
   const size_t o_coef = dv.take((size_t)coef_total * sizeof(int16_t));
   int rc = ensure_dev(d, (void **)&d->eragged_dev, &d->eragged_cap, dv.at);
   if (rc) return rc;
@@ -601,9 +628,9 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
     HIP_TRY(d, hipMemcpyAsync(dev + o_hargs, hh, (size_t)n * sizeof(HencArgs), hipMemcpyHostToDevice, stream)); // (tables now the pictures' own)
   }
   LAUNCHED(d, henc_count(b, false, stream), "henc_count_kernel", 1);
-  LAUNCHED(d, exclusive_scan_u32((const uint32_t *)(dev + o_bits), (uint64_t *)(dev + o_bitpos), N, scratch, stream), "scan", scan_launches(N));
+  LAUNCHED(d, exclusive_scan_u32((const uint32_t *)(dev + o_bits), (uint64_t *)(dev + o_bitpos), N, scratch, scratch_words, stream), "scan", scan_launches(N));
   LAUNCHED(d, henc_interval_bytes(b, stream), "henc_interval_bytes_kernel", 1);
-  LAUNCHED(d, exclusive_scan_u32((const uint32_t *)(dev + o_ibytes), (uint64_t *)(dev + o_istart), I, scratch, stream), "scan", scan_launches(I));
+  LAUNCHED(d, exclusive_scan_u32((const uint32_t *)(dev + o_ibytes), (uint64_t *)(dev + o_istart), I, scratch, scratch_words, stream), "scan", scan_launches(I));
   LAUNCHED(d, henc_gather((const uint64_t *)(dev + o_istart), b.first_interval, (uint64_t *)(dev + o_gather), n + 1, stream), "henc_gather_kernel", 1);
   HIP_TRY(d, hipMemcpyAsync(host + h_istart, dev + o_gather, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
   if ((rc = sync_counted(d))) return rc;
@@ -639,7 +666,8 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   HIP_TRY(d, hipMemsetAsync(od + q_plain, 0, plain_total + 16, stream));
   LAUNCHED(d, henc_emit(b, stream), "henc_emit_kernel", 1);
   LAUNCHED(d, henc_count_ff(b, stream), "henc_count_ff_kernel", 1);
-  LAUNCHED(d, exclusive_scan_u32(b.ffcount, (uint64_t *)b.ffstart, b.total_chunks, (uint64_t *)(od + q_scratch), stream), "scan", scan_launches(b.total_chunks));
+  LAUNCHED(d, exclusive_scan_u32(b.ffcount, (uint64_t *)b.ffstart, b.total_chunks, (uint64_t *)(od + q_scratch), scan_scratch_words((size_t)chunks), stream), "scan",
+           scan_launches(b.total_chunks));
   LAUNCHED(d, henc_gather(b.ffstart, b.first_chunk, (uint64_t *)(dev + o_gather), n + 1, stream), "henc_gather_kernel", 1);
   LAUNCHED(d, henc_stuff(b, stream), "henc_stuff_kernel", 1);
   HIP_TRY(d, hipMemcpyAsync(host + h_ffs, dev + o_gather, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
@@ -832,6 +860,40 @@ try {
   d->timing[1] = d->timing[2] = d->timing[3] = 0;
   return rc;
 } catch (...) { return boundary_catch(d, "mijpeg_encode_batch_device"); }
+
+int mijpeg_encode_coefficients_device(mijpeg_decoder *d, const mijpeg_info *info, const int16_t *coef_dev, int restart_interval, int optimize,
+                                      uint8_t **stream, size_t *size)
+try {
+  // (the checks and codes of mijpeg_encode_coefficients, then HencJob::stage_a's, before anything touches a device)
+  if (!d || !info || !coef_dev || !stream || !size || restart_interval < 0 || restart_interval > 65535) return MIJPEG_ERR_INVALID_PARAMETER;
+  *stream = nullptr;
+  *size = 0;
+  const mijpeg_info &f = *info;
+  if ((f.precision != 8 && f.precision != 12) || (f.components != 1 && f.components != 3))
+    return set_error(d, MIJPEG_ERR_OPERATION_UNIMPLEMENTED, "the entropy coder takes 8-bit and 12-bit frames of one or three components");
+  // (a zeroed or hand-built info: the geometry helper divides by subx / suby and multiplies the MCU counts as ints)
+  bool laid_out = f.mcus_x >= 1 && f.mcus_y >= 1 && (int64_t)f.mcus_x * f.mcus_y <= INT32_MAX;
+  for (int c = 0; c < f.components; c++) laid_out = laid_out && f.subx[c] >= 1 && f.suby[c] >= 1 && f.hsamp[c] >= 1 && f.vsamp[c] >= 1 && f.blocks_w[c] >= 1;
+  if (!laid_out) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "frame without a layout (mijpeg_frame_layout)");
+  HencArgs geometry;
+  memset(&geometry, 0, sizeof(geometry));
+  if (!henc_frame_geometry(geometry, f, restart_interval)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device entropy coder");
+  if ((uint64_t)geometry.total_mcus * (uint64_t)geometry.blocks_per_mcu > HENC_SCAN_MAX) // (2^30 blocks or more, and the 1024 counts below)
+    return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "frame too large for the device entropy coder");
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  HIP_TRY(d, hipSetDevice(d->device));
+  const auto t_begin = std::chrono::steady_clock::now();
+  int rc = device_entropy_code(d, f, coef_dev, restart_interval, optimize, stream, size, true);
+  if (rc) {
+    (void)hipStreamSynchronize(d->stream);
+    free(*stream);
+    *stream = nullptr;
+    *size = 0;
+  }
+  d->timing[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); // mijpeg_last_timing: the whole call
+  d->timing[1] = d->timing[2] = d->timing[3] = 0;
+  return rc;
+} catch (...) { return boundary_catch(d, "mijpeg_encode_coefficients_device"); }
 
 int mijpeg_encode_image(mijpeg_decoder *d, const uint8_t *pixels, int32_t width, int32_t height, int32_t components, int64_t row_stride,
                         int quality, const int32_t *hsamp, const int32_t *vsamp, int restart_interval, int optimize, uint8_t **stream, size_t *size)

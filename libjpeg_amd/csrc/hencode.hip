@@ -79,12 +79,13 @@ __device__ __forceinline__ BlockRef locate(const HencArgs &a, uint32_t s)
 }
 
 // Walks the symbols of a block in coding order: f_dc(category, difference), f_ac(symbol, value, category)
-// (sequentialscan.cpp EncodeBlock: DC difference, then run/size symbols with ZRL for runs beyond 15 and EOB)
-template <class FD, class FA>
+// (sequentialscan.cpp EncodeBlock: DC difference, then run/size symbols with ZRL for runs beyond 15 and EOB).  SAT: the categories
+// saturate at HENC_SURVEY_DC_CAT and HENC_SURVEY_AC_CAT, so that any int16 content gives a DC category and an AC symbol below 256
+template <bool SAT = false, class FD, class FA>
 __device__ __forceinline__ void walk_symbols(const BlockRef &r, FD f_dc, FA f_ac)
 {
   const int diff = (r.blk ? (int)r.blk[0] : r.pred) - r.pred;
-  f_dc(category(diff), diff);
+  f_dc(SAT ? min(category(diff), HENC_SURVEY_DC_CAT) : category(diff), diff);
   if (!r.blk) { f_ac(0, 0, 0); return; }
   unsigned wd[32]; // the block in registers
 #pragma unroll
@@ -100,7 +101,7 @@ __device__ __forceinline__ void walk_symbols(const BlockRef &r, FD f_dc, FA f_ac
     const int v = (nat & 1) ? (int)d >> 16 : (int)(short)(d & 0xffffu);
     if (v != 0) {
       while (run > 15) { f_ac(0xf0, 0, 0); run -= 16; }
-      const int s = category(v);
+      const int s = SAT ? min(category(v), HENC_SURVEY_AC_CAT) : category(v);
       f_ac((run << 4) | s, v, s);
       run = 0;
     } else run++;
@@ -185,6 +186,26 @@ __global__ __launch_bounds__(256) void henc_count_kernel(const typename F::Args 
     for (unsigned i = threadIdx.x; i < 4 * 256; i += blockDim.x)
       if (hist[i]) atomicAdd(&a.hist[i], hist[i]);
   }
+}
+
+// The symbol statistics of a frame whose coefficients the caller wrote, with saturating categories (walk_symbols<true>): no table
+// is indexed, no length looked up, so every int16 value is safe here.  The host refuses the frame from the histogram where a
+// category is beyond the frame's precision; otherwise the histogram is what henc_count_kernel<., true> counts.
+__global__ __launch_bounds__(256) void henc_survey_kernel(const HencArgs a)
+{
+  __shared__ uint32_t hist[4 * 256];
+  for (unsigned i = threadIdx.x; i < 4 * 256; i += blockDim.x) hist[i] = 0;
+  __syncthreads();
+  const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s < a.total_blocks) {
+    const BlockRef r = locate(a, s);
+    const int t = r.table;
+    walk_symbols<true>(
+        r, [&](int cat, int) { atomicAdd(&hist[t * 256 + cat], 1u); }, [&](int sym, int, int) { atomicAdd(&hist[512 + t * 256 + sym], 1u); });
+  }
+  __syncthreads();
+  for (unsigned i = threadIdx.x; i < 4 * 256; i += blockDim.x)
+    if (hist[i]) atomicAdd(&a.hist[i], hist[i]);
 }
 
 // bytes of every interval before stuffing: its bits rounded up
@@ -351,7 +372,7 @@ __global__ __launch_bounds__(256) void henc_stuff_kernel(const typename F::Args 
 }
 
 // ---- exclusive prefix sums: tiles of 1024, recursively ----------------------------------------------------------
-constexpr int SCAN_TILE = 1024;
+constexpr int SCAN_TILE = (int)HENC_SCAN_TILE;
 template <class T>
 __global__ __launch_bounds__(SCAN_TILE) void scan_tile_sums_kernel(const T *in, uint64_t *sums, uint32_t n)
 {
@@ -398,22 +419,22 @@ __global__ __launch_bounds__(256) void henc_gather_kernel(const uint64_t *src, c
 
 } // namespace
 
-int exclusive_scan_u32(const uint32_t *in, uint64_t *out, uint32_t n, uint64_t *scratch, hipStream_t stream)
+int exclusive_scan_u32(const uint32_t *in, uint64_t *out, uint32_t n, uint64_t *scratch, size_t scratch_words, hipStream_t stream)
 {
-  // level 0: n elements (u32); level 1: tile sums (u64), scanned in place of `scratch`; level 2 if needed
-  const uint32_t t1 = n / SCAN_TILE + 1; // tiles incl. the one that holds out[n]
-  if (t1 == 1) {
+  // level 0: n elements (u32); level 1: tile sums (u64), scanned in `scratch`; level 2 if needed (ScanLayout, hencode.hpp)
+  const ScanLayout l = scan_layout(n);
+  if (!l.in_reach || l.words > scratch_words) return (int)hipErrorInvalidValue;
+  const uint32_t t1 = l.tiles1, t2 = l.tiles2;
+  if (l.launches == 1) {
     hipLaunchKernelGGL((scan_apply_kernel<uint32_t>), dim3(1), dim3(SCAN_TILE), 0, stream, in, (const uint64_t *)nullptr, out, n);
     return (int)hipGetLastError();
   }
-  uint64_t *sums1 = scratch, *off1 = scratch + t1 + 1; // off1: t1 + 1 entries
+  uint64_t *sums1 = scratch + l.sums1, *off1 = scratch + l.off1;
   hipLaunchKernelGGL((scan_tile_sums_kernel<uint32_t>), dim3(t1), dim3(SCAN_TILE), 0, stream, in, sums1, n);
-  const uint32_t t2 = t1 / SCAN_TILE + 1;
-  if (t2 == 1) {
+  if (l.launches == 3) {
     hipLaunchKernelGGL((scan_apply_kernel<uint64_t>), dim3(1), dim3(SCAN_TILE), 0, stream, (const uint64_t *)sums1, (const uint64_t *)nullptr, off1, t1);
   } else {
-    uint64_t *sums2 = off1 + t1 + 1, *off2 = sums2 + t2 + 1;
-    if (t2 > SCAN_TILE) return (int)hipErrorInvalidValue; // more than 2^30 elements
+    uint64_t *sums2 = scratch + l.sums2, *off2 = scratch + l.off2;
     hipLaunchKernelGGL((scan_tile_sums_kernel<uint64_t>), dim3(t2), dim3(SCAN_TILE), 0, stream, (const uint64_t *)sums1, sums2, t1);
     hipLaunchKernelGGL((scan_apply_kernel<uint64_t>), dim3(1), dim3(SCAN_TILE), 0, stream, (const uint64_t *)sums2, (const uint64_t *)nullptr, off2, t2);
     hipLaunchKernelGGL((scan_apply_kernel<uint64_t>), dim3(t2), dim3(SCAN_TILE), 0, stream, (const uint64_t *)sums1, (const uint64_t *)off2, off1, t1);
@@ -427,6 +448,11 @@ int henc_count(const HencArgs &a, bool statistics, hipStream_t stream)
   const dim3 grid((a.total_blocks + 255) / 256);
   if (statistics) hipLaunchKernelGGL((henc_count_kernel<OneFrame, true>), grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL((henc_count_kernel<OneFrame, false>), grid, dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+int henc_survey(const HencArgs &a, hipStream_t stream)
+{
+  hipLaunchKernelGGL(henc_survey_kernel, dim3((a.total_blocks + 255) / 256), dim3(256), 0, stream, a);
   return (int)hipGetLastError();
 }
 int henc_interval_bytes(const HencArgs &a, hipStream_t stream)

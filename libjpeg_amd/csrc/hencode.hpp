@@ -2,6 +2,7 @@
 #ifndef MIJ_HENCODE_HPP
 #define MIJ_HENCODE_HPP
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace mij {
@@ -61,7 +62,12 @@ struct HencBatchArgs {
   uint8_t *out;
 };
 
+// where the categories of henc_survey saturate: above every category a frame can code (DC 11 / 15, AC 10 / 14), small enough for
+// (run << 4) | category to stay an AC symbol and for the DC category to stay inside its row of hist[]
+constexpr int HENC_SURVEY_DC_CAT = 17, HENC_SURVEY_AC_CAT = 15;
+
 int henc_count(const HencArgs &a, bool statistics, hipStream_t stream);      // bits[] (and hist[])
+int henc_survey(const HencArgs &a, hipStream_t stream);                      // hist[] alone, safe for any int16 content
 int henc_interval_bytes(const HencArgs &a, hipStream_t stream);              // ibytes[] from bitpos[]
 int henc_emit(const HencArgs &a, hipStream_t stream);                        // plain[]
 int henc_count_ff(const HencArgs &a, hipStream_t stream);                    // ffcount[]
@@ -73,8 +79,69 @@ int henc_count_ff(const HencBatchArgs &b, hipStream_t stream); // (the one-frame
 int henc_stuff(const HencBatchArgs &b, hipStream_t stream);
 // dst[i] = src[idx[i]], i < n: the entries of a pass-wide prefix sum the host lays the pictures out with
 int henc_gather(const uint64_t *src, const uint32_t *idx, uint64_t *dst, uint32_t n, hipStream_t stream);
-// out[i] = sum of in[0..i) for i = 0..n (n + 1 entries); scratch: at least (n / 1024 + 2) * 2 uint64
-int exclusive_scan_u32(const uint32_t *in, uint64_t *out, uint32_t n, uint64_t *scratch, hipStream_t stream);
+// ---- exclusive prefix sums (hencode.hip): tiles of HENC_SCAN_TILE, recursively -------------------------------------
+// The scratch of an exclusive_scan_u32 over n elements, in uint64 words; this is its only statement: the scan takes its pointers
+// from it and its callers their buffer sizes.
+//   level 0   the n elements in tiles1 = n / TILE + 1 tiles (the last one holds out[n]); one tile: one launch, no scratch
+//   level 1   sums1[tiles1]: the tiles' sums (and one spare word); off1[tiles1 + 1]: their exclusive prefix sums.  Up to TILE - 1
+//             of them are scanned by one workgroup: three launches
+//   level 2   beyond that sums1 is scanned in tiles2 = tiles1 / TILE + 1 tiles of its own: sums2[tiles2] (and a spare word),
+//             off2[tiles2 + 1]: five launches.  One workgroup scans sums2, so tiles2 <= TILE: n <= HENC_SCAN_MAX
+constexpr uint32_t HENC_SCAN_TILE = 1024;
+struct ScanLayout {
+  uint32_t tiles1, tiles2;
+  int launches;                     // 1, 3 or 5
+  uint64_t sums1, off1, sums2, off2; // first word of each array
+  uint64_t end1, end2;              // behind off1, behind off2 (0 where the level does not exist)
+  uint64_t words;                   // all of it
+  bool in_reach;                    // n <= HENC_SCAN_MAX
+};
+constexpr ScanLayout scan_layout(uint32_t n)
+{
+  ScanLayout l{};
+  l.tiles1 = n / HENC_SCAN_TILE + 1;
+  l.tiles2 = l.tiles1 / HENC_SCAN_TILE + 1;
+  l.in_reach = l.tiles2 <= HENC_SCAN_TILE;
+  l.launches = 1;
+  if (l.tiles1 == 1) return l;
+  l.sums1 = 0;
+  l.off1 = l.sums1 + l.tiles1 + 1;
+  l.end1 = l.off1 + l.tiles1 + 1;
+  l.words = l.end1;
+  l.launches = 3;
+  if (l.tiles2 == 1) return l;
+  l.sums2 = l.end1;
+  l.off2 = l.sums2 + l.tiles2 + 1;
+  l.end2 = l.off2 + l.tiles2 + 1;
+  l.words = l.end2;
+  l.launches = 5;
+  return l;
+}
+constexpr uint32_t HENC_SCAN_MAX = (HENC_SCAN_TILE * HENC_SCAN_TILE - 1) * HENC_SCAN_TILE - 1; // 2^30 - 1025
+constexpr bool scan_layout_consistent(uint32_t n)
+{
+  const ScanLayout l = scan_layout(n);
+  const bool one = l.launches == 1 && l.tiles1 == 1 && l.words == 0;
+  const bool three = l.launches == 3 && l.tiles1 > 1 && l.tiles2 == 1 && l.off1 == (uint64_t)l.tiles1 + 1 && l.end1 == 2 * ((uint64_t)l.tiles1 + 1) && l.words == l.end1;
+  const bool five = l.launches == 5 && l.tiles2 > 1 && l.sums2 == l.end1 && l.end1 == 2 * ((uint64_t)l.tiles1 + 1) &&
+                    l.end2 == l.end1 + 2 * ((uint64_t)l.tiles2 + 1) && l.words == l.end2;
+  return one || three || five;
+}
+static_assert(scan_layout_consistent(0) && scan_layout(0).launches == 1, "one tile");
+static_assert(scan_layout_consistent(1023) && scan_layout(1023).launches == 1, "one tile: 1023 elements and the total");
+static_assert(scan_layout_consistent(1024) && scan_layout(1024).launches == 3 && scan_layout(1024).words == 6, "two tiles");
+static_assert(scan_layout_consistent((1u << 20) - 1025) && scan_layout((1u << 20) - 1025).launches == 3 && scan_layout((1u << 20) - 1025).words == 2 * 1024,
+              "1023 tile sums: the last count one workgroup scans");
+static_assert(scan_layout_consistent((1u << 20) - 1024) && scan_layout((1u << 20) - 1024).launches == 5 && scan_layout((1u << 20) - 1024).words == 2 * 1025 + 2 * 3,
+              "1024 tile sums: the second level");
+static_assert(scan_layout_consistent(1u << 20) && scan_layout(1u << 20).launches == 5 && scan_layout(1u << 20).words == 2 * 1026 + 2 * 3, "second level");
+static_assert(scan_layout_consistent((1u << 30) - 1) && scan_layout((1u << 30) - 1).launches == 5 && scan_layout((1u << 30) - 1).words == 2 * ((1u << 20) + 1) + 2 * 1026,
+              "the layout arithmetic holds past the scan's reach");
+static_assert(scan_layout(HENC_SCAN_MAX).in_reach && !scan_layout(HENC_SCAN_MAX + 1).in_reach && !scan_layout((1u << 30) - 1).in_reach, "the scan's reach");
+
+// out[i] = sum of in[0..i) for i = 0..n (n + 1 entries); scratch: scratch_words uint64, at least scan_layout(n).words of them.
+// hipErrorInvalidValue, before anything is launched, where the scratch is smaller or n is beyond HENC_SCAN_MAX
+int exclusive_scan_u32(const uint32_t *in, uint64_t *out, uint32_t n, uint64_t *scratch, size_t scratch_words, hipStream_t stream);
 
 } // namespace mij
 #endif

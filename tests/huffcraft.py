@@ -294,6 +294,8 @@ def content(kind: str, shapes, precision: int, rng: np.random.Generator, dc_cats
     shaped to stay inside it.  DC values stay inside int16 (the predictor with them)."""
     dmax, amax = max_categories(precision)
     dc_cats = set(range(dmax + 1)) if dc_cats is None else dc_cats
+    if ac_syms is not None:  # (no AC coefficient of a category the tables have no symbol for; amax only shapes `boundaries`)
+        amax = min(amax, max(s & 15 for s in ac_syms))
     planes = [np.zeros(s + (64,), np.int32) for s in shapes]
     if dc_cats == {0}:  # degenerate: no DC difference, AC (0, 1) only (EOB or a +-1 at each next position)
         for p in planes:
