@@ -1,8 +1,10 @@
 // encode_device.cpp -- the encoder direction on the device: frame layout and quality tables, the argument blocks of the forward
-// kernels and of the device entropy coder, the per-frame coder (HencJob: mijpeg_encode_image(_ex), mijpeg_encode_batch_device) and
-// the RAGGED ENCODE: lists of pictures of any shapes through one device pass (mijpeg_encode_ragged_plan / _device /
-// mijpeg_encode_ragged and their ...16 flavours with a precision per picture).  The entropy coder on the host is
-// encoder.cpp.  Private to libmijpeg.so.
+// kernels and of the device entropy coder, and that coder's two host drivers: the per-frame coder (HencJob: mijpeg_encode_image(_ex|16),
+// mijpeg_encode_coefficients_device, mijpeg_encode_batch_device) and the RAGGED ENCODE, lists of pictures of any shapes through one
+// device pass (mijpeg_encode_ragged_plan / _device / mijpeg_encode_ragged and their ...16 flavours with a precision per picture;
+// DESIGN 4.3b).  What the two drivers share is stated once: the buffers are coder_layout() and output_layout() of hencode.hpp, the
+// launches coder_stage_one / coder_stage_two over either argument type, the table rule codes_with_own_tables / tables_from_statistics.
+// The entropy coder on the host is encoder.cpp.  Private to libmijpeg.so.
 //
 // A pass of the ragged encode:
 //   plan        per picture: frame layout, block and interval counts, its place in the pass's index spaces, its coefficient store
@@ -126,7 +128,7 @@ static void henc_pack_tables(HencTables *h, const EncTables &t)
 }
 
 // ------------------------------------------------------------------------------------------------
-// helpers; the per-frame coder
+// helpers
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -135,15 +137,32 @@ struct Carver { // lays regions out in a buffer, 256-byte aligned
   size_t take(size_t bytes)
   {
     const size_t o = at;
-    at = (at + bytes + 255) & ~(size_t)255;
+    at += henc_aligned(bytes);
     return o;
   }
 };
 
-// what an exclusive_scan_u32 over n elements needs as scratch (ScanLayout, hencode.hpp), rounded up; n beyond the scan's reach: the
-// scan refuses whatever it is given
-size_t scan_scratch_bytes(size_t n) { return (size_t)(scan_layout((uint32_t)std::min<size_t>(n, HENC_SCAN_MAX)).words + 32) * 8; }
-size_t scan_scratch_words(size_t n) { return scan_scratch_bytes(n) / 8; }
+// What the entry points ask of a picture before they look further: 8 or 12 bits, one or three components, width and height in
+// 1..65535 ...
+bool shape_in_order(int precision, int components, int64_t width, int64_t height)
+{
+  return (precision == 8 || precision == 12) && (components == 1 || components == 3) && width >= 1 && width <= 65535 && height >= 1 && height <= 65535;
+}
+// ... and a row stride (bytes) that holds a line of it
+bool line_fits(int precision, int components, int64_t width, int64_t row_stride) { return row_stride >= width * components * (precision == 12 ? 2 : 1); }
+
+// A call that failed leaves nothing behind: what it produced is freed, pointers null, sizes 0 ...
+void drop_streams(uint8_t **streams, size_t *sizes, int n)
+{
+  if (!streams || !sizes) return;
+  for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+}
+// ... and mijpeg_last_timing of the calls that have no phases to tell apart: the whole call
+void whole_call_timing(mijpeg_decoder *d, std::chrono::steady_clock::time_point t_begin)
+{
+  d->timing[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
+  d->timing[1] = d->timing[2] = d->timing[3] = 0;
+}
 
 // The frame of a picture to encode: its layout and the tables of its quality (hsamp, vsamp: null = 1 x 1 throughout).  What
 // mijpeg_frame_layout says to it.
@@ -203,7 +222,92 @@ int assemble_stream(const std::vector<uint8_t> &head, const uint8_t *ecs_src, si
   return MIJPEG_OK;
 }
 
-// Entropy coding of one frame's coefficient planes on the device (hencode.hip) and download of the finished stream, as a
+// ------------------------------------------------------------------------------------------------
+// the device entropy coder's host side, shared by the per-frame coder (HencArgs) and the passes of a list (HencBatchArgs)
+// ------------------------------------------------------------------------------------------------
+constexpr size_t HENC_HIST_BYTES = 4 * 256 * sizeof(uint32_t); // a picture's symbol statistics: HencArgs::hist
+// the widest categories a frame codes (encoder.cpp code_block): DC differences and AC coefficients, at precision 8 and at 12
+constexpr int DC_CATEGORY_MAX_8 = 11, AC_CATEGORY_MAX_8 = 10, DC_CATEGORY_MAX_12 = 15, AC_CATEGORY_MAX_12 = 14;
+
+// Huffman tables from the picture's own statistics: with `optimize`, and always at precision 12, where the Annex K.3 tables have
+// no codes for categories 12..15.  (Coefficients the forward kernels make of 8-bit pixels always have a code in the standard
+// tables, at most 11 / 10 bits, the host coder's check; of 12-bit pixels at most 15 / 14 bits, which tables of their own cover.)
+bool codes_with_own_tables(const mijpeg_info &f, int optimize) { return optimize || f.precision == 12; }
+
+// ... and where the coefficients are a caller's: does a henc_survey histogram hold a category a frame of this precision cannot code?
+bool beyond_coding_range(const uint32_t hist[4][256], int precision)
+{
+  const int dc_max = precision == 12 ? DC_CATEGORY_MAX_12 : DC_CATEGORY_MAX_8, ac_max = precision == 12 ? AC_CATEGORY_MAX_12 : AC_CATEGORY_MAX_8;
+  bool beyond = false;
+  for (int t = 0; t < 2; t++)
+    for (int i = 0; i < 256; i++) beyond |= (hist[t][i] && i > dc_max) || (hist[2 + t][i] && (i & 15) > ac_max);
+  return beyond;
+}
+
+// histogram of a picture -> its tables (Annex K.2; a single component: one pair) -> as the kernels read them
+void tables_from_statistics(const uint32_t hist[4][256], int components, EncTables &t, HencTables *packed)
+{
+  enc_standard_tables(t);
+  enc_optimal_tables(t, hist, hist + 2, components > 1 ? 2 : 1);
+  henc_pack_tables(packed, t);
+}
+
+// a picture's view of the arrays of coder_layout() at `base`: from its first block and first interval
+void point_into(HencArgs &a, uint8_t *base, const CoderLayout &l, uint32_t first_block = 0, uint32_t first_interval = 0)
+{
+  a.bits = (uint32_t *)(base + l.bits) + first_block;
+  a.bitpos = (const uint64_t *)(base + l.bitpos) + first_block;
+  a.ibytes = (uint32_t *)(base + l.ibytes) + first_interval;
+  a.istart = (const uint64_t *)(base + l.istart) + first_interval;
+}
+// the arena of output_layout() at `base`: a frame's or a pass's
+template <class Args> void point_into(Args &a, uint8_t *base, const OutputLayout &l)
+{
+  a.plain = (uint32_t *)(base + l.plain);
+  a.ffcount = (uint32_t *)(base + l.ffcount);
+  a.ffstart = (const uint64_t *)(base + l.ffstart);
+  a.out = base + l.out;
+}
+
+// a launch of the coder: its failure under its name, or `count` more launches where a driver keeps count (`counter`, may be null)
+#define LAUNCHED(d, call, what, count, counter)                          \
+  do {                                                                   \
+    if (const int e_ = (call)) return hip_fail(d, (hipError_t)e_, what); \
+    if (counter) *(counter) += (count);                                  \
+  } while (0)
+struct ScanNames { const char *blocks, *intervals, *chunks; }; // what a driver calls its three scans when one fails
+constexpr ScanNames FRAME_SCANS{"scan over the blocks", "scan over the intervals", "scan over the chunks"}, PASS_SCANS{"scan launch", "scan launch", "scan launch"};
+
+// Stage one: code lengths per block, their prefix sums, bytes per interval, their prefix sums -- istart[I] is the plain stream's size.
+template <class Args>
+int coder_stage_one(mijpeg_decoder *d, const Args &args, uint8_t *base, const CoderLayout &l, hipStream_t stream, const ScanNames &scans, int32_t *launches)
+{
+  uint64_t *bitpos = (uint64_t *)(base + l.bitpos), *istart = (uint64_t *)(base + l.istart), *scratch = (uint64_t *)(base + l.scratch);
+  LAUNCHED(d, henc_count(args, false, stream), "henc_count_kernel launch", 1, launches);
+  LAUNCHED(d, exclusive_scan_u32((uint32_t *)(base + l.bits), bitpos, l.N, scratch, l.scratch_words, stream), scans.blocks, scan_layout(l.N).launches, launches);
+  LAUNCHED(d, henc_interval_bytes(args, stream), "henc_interval_bytes_kernel launch", 1, launches);
+  LAUNCHED(d, exclusive_scan_u32((uint32_t *)(base + l.ibytes), istart, l.I, scratch, l.scratch_words, stream), scans.intervals, scan_layout(l.I).launches, launches);
+  return MIJPEG_OK;
+}
+
+// Stage two, once the plain sizes are known and `args` point into the arena: the zeroed plain stream, the code words into it, 0xFF
+// bytes per chunk, their prefix sums -- ffstart[chunks] is what the stuffing adds --, then the stuffed stream with its markers.
+// before_stuff: what a driver enqueues between the last scan and the stuffing kernel.
+template <class Args, class BeforeStuff>
+int coder_stage_two(mijpeg_decoder *d, const Args &args, uint8_t *base, const OutputLayout &l, hipStream_t stream, const ScanNames &scans, int32_t *launches,
+                    BeforeStuff before_stuff)
+{
+  HIP_TRY(d, hipMemsetAsync(base + l.plain, 0, l.zeroed, stream));
+  LAUNCHED(d, henc_emit(args, stream), "henc_emit_kernel launch", 1, launches);
+  LAUNCHED(d, henc_count_ff(args, stream), "henc_count_ff_kernel launch", 1, launches);
+  LAUNCHED(d, exclusive_scan_u32(args.ffcount, (uint64_t *)args.ffstart, l.chunks, (uint64_t *)(base + l.scratch), l.scratch_words, stream), scans.chunks,
+           scan_layout(l.chunks).launches, launches);
+  if (const int rc = before_stuff()) return rc;
+  LAUNCHED(d, henc_stuff(args, stream), "henc_stuff_kernel launch", 1, launches);
+  return MIJPEG_OK;
+}
+
+// The per-frame coder: entropy coding of one frame's coefficient planes on the device (hencode.hip) and download of the finished stream, as a
 // job of three stages with a host synchronisation in front of the second and the third (the byte counts the next stage
 // sizes its buffers and copies with come from the device).  Two jobs on two streams with two sets of buffers overlap:
 // mijpeg_encode_batch_device keeps the next frame's first stage in flight while it waits for the current frame.
@@ -215,123 +319,73 @@ struct HencJob {
   HencArgs a;
   EncTables tabs;
   uint64_t *readback = nullptr; // pinned: [0] plain bytes, [1] 0xFF bytes
-  uint64_t *scratch = nullptr; // of the scans over blocks and intervals (stage_a); the scan over chunks has its own (stage_b)
-  size_t scratch_words = 0;
+  HencTables *packed = nullptr; // pinned: the slot's tables on their way up
   uint32_t chunks = 0;
   uint8_t *result = nullptr;
   size_t result_size = 0;
   std::vector<uint8_t> head;
 
-  int upload_tables()
-  {
-    HencTables *h = (HencTables *)((uint8_t *)d->henc_host + 64 + (size_t)slot * sizeof(HencTables)); // pinned, one per slot
-    henc_pack_tables(h, tabs);
-    HIP_TRY(d, hipMemcpyAsync((void *)a.tables, h, sizeof(*h), hipMemcpyHostToDevice, stream));
-    return MIJPEG_OK;
-  }
-
-  // geometry, buffers, tables (optimised ones cost a synchronisation of their own), then count + prefix sums.
+  // geometry, buffers, tables (the picture's own cost a synchronisation of their own), then stage one.
   // check_range: the coefficients are the caller's own (mijpeg_encode_coefficients_device), not the forward kernels': the symbol
-  // statistics are always taken, by the survey kernel that is safe for any int16 content, and a DC difference or an AC coefficient
-  // beyond what a frame of this precision codes (encoder.cpp code_block: categories 11 / 10, precision 12: 15 / 14) is refused
-  // before any kernel looks a code up.  One launch and one synchronisation more where the tables are the standard ones.
+  // statistics are always taken, by the survey kernel that is safe for any int16 content, and what beyond_coding_range() finds is
+  // refused before any kernel looks a code up.  One launch and one synchronisation more where the tables are the standard ones.
   int stage_a(mijpeg_decoder *dec, const mijpeg_info &info, const int16_t *coef_dev, int ri, int optimize, int slot_, hipStream_t st,
               bool check_range = false)
   {
     d = dec; f = &info; slot = slot_; stream = st; restart_interval = ri;
-    const int nc = info.components;
     memset(&a, 0, sizeof(a));
     a.coef = coef_dev;
     if (!henc_frame_geometry(a, info, ri)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device entropy coder");
-    const int B = a.blocks_per_mcu;
-    const uint64_t nblocks = (uint64_t)a.total_mcus * (uint64_t)B;
+    const uint64_t nblocks = (uint64_t)a.total_mcus * (uint64_t)a.blocks_per_mcu;
     if (nblocks > HENC_SCAN_MAX) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "frame too large for the device entropy coder"); // (2^30 - 1025 blocks)
     a.total_blocks = (uint32_t)nblocks;
     a.n_intervals = (uint32_t)((a.total_mcus + a.ri - 1) / a.ri);
-    const uint32_t N = a.total_blocks, I = a.n_intervals;
-    // arena 1: tables, statistics, block and interval arrays, scan scratch
+    // arena 1: tables, statistics, the arrays over blocks and intervals
+    const CoderLayout l = coder_layout(a.total_blocks, a.n_intervals);
     Carver ar;
-    const size_t o_tab = ar.take(sizeof(HencTables));
-    const size_t o_hist = ar.take(4 * 256 * 4);
-    const size_t o_bits = ar.take((size_t)N * 4);
-    const size_t o_bitpos = ar.take(((size_t)N + 1) * 8);
-    const size_t o_ibytes = ar.take((size_t)I * 4);
-    const size_t o_istart = ar.take(((size_t)I + 1) * 8);
-    const size_t o_scratch = ar.take(scan_scratch_bytes(N)); // (for the blocks, then for the intervals: never more of them than blocks)
-    scratch_words = scan_scratch_words(N);
+    const size_t o_tab = ar.take(sizeof(HencTables)), o_hist = ar.take(HENC_HIST_BYTES), o_coder = ar.take(l.end);
     int rc = ensure_dev(d, (void **)&d->henc_dev[slot], &d->henc_cap[slot], ar.at);
     if (rc) return rc;
     if (!d->henc_host) HIP_TRY(d, hipHostMalloc((void **)&d->henc_host, 64 + 2 * sizeof(HencTables), hipHostMallocDefault));
     readback = d->henc_host + 2 * slot;
+    packed = (HencTables *)((uint8_t *)d->henc_host + 64 + (size_t)slot * sizeof(HencTables));
     uint8_t *base = d->henc_dev[slot];
     a.tables = (const HencTables *)(base + o_tab);
     a.hist = (uint32_t *)(base + o_hist);
-    a.bits = (uint32_t *)(base + o_bits);
-    a.bitpos = (const uint64_t *)(base + o_bitpos);
-    a.ibytes = (uint32_t *)(base + o_ibytes);
-    a.istart = (const uint64_t *)(base + o_istart);
-    scratch = (uint64_t *)(base + o_scratch);
+    point_into(a, base + o_coder, l);
     enc_standard_tables(tabs);
-    rc = upload_tables();
-    if (rc) return rc;
-    // precision 12: the Annex K.3 tables have no codes for categories 12..15, so the tables are always the picture's own
-    const bool own_tables = optimize || info.precision == 12;
-    if (own_tables || check_range) { // symbol statistics first, tables from them (Annex K.2)
-      HIP_TRY(d, hipMemsetAsync(base + o_hist, 0, 4 * 256 * 4, stream));
-      if (check_range ? henc_survey(a, stream) : henc_count(a, true, stream)) return hip_fail(d, hipGetLastError(), "statistics kernel launch");
+    henc_pack_tables(packed, tabs);
+    HIP_TRY(d, hipMemcpyAsync((void *)a.tables, packed, sizeof(*packed), hipMemcpyHostToDevice, stream));
+    const bool own_tables = codes_with_own_tables(info, optimize);
+    if (own_tables || check_range) { // symbol statistics first, tables from them
+      HIP_TRY(d, hipMemsetAsync(a.hist, 0, HENC_HIST_BYTES, stream));
+      if (const int e = check_range ? henc_survey(a, stream) : henc_count(a, true, stream)) return hip_fail(d, (hipError_t)e, "statistics kernel launch");
       uint32_t hist[4][256];
-      HIP_TRY(d, hipMemcpyAsync(hist, base + o_hist, sizeof(hist), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(d, hipMemcpyAsync(hist, a.hist, sizeof(hist), hipMemcpyDeviceToHost, stream));
       HIP_TRY(d, hipStreamSynchronize(stream));
-      if (check_range) {
-        const int dc_max = info.precision == 12 ? 15 : 11, ac_max = info.precision == 12 ? 14 : 10;
-        bool beyond = false;
-        for (int t = 0; t < 2; t++)
-          for (int i = 0; i < 256; i++) beyond |= (hist[t][i] && i > dc_max) || (hist[2 + t][i] && (i & 15) > ac_max);
-        if (beyond) return set_error(d, MIJPEG_ERR_OVERFLOW_PARAMETER, "coefficients outside what a frame of this precision can hold");
-      }
+      if (check_range && beyond_coding_range(hist, info.precision))
+        return set_error(d, MIJPEG_ERR_OVERFLOW_PARAMETER, "coefficients outside what a frame of this precision can hold");
       if (own_tables) {
-        enc_optimal_tables(tabs, hist, hist + 2, nc > 1 ? 2 : 1);
-        rc = upload_tables();
-        if (rc) return rc;
+        tables_from_statistics(hist, info.components, tabs, packed);
+        HIP_TRY(d, hipMemcpyAsync((void *)a.tables, packed, sizeof(*packed), hipMemcpyHostToDevice, stream));
       }
     }
-    if (henc_count(a, false, stream)) return hip_fail(d, hipGetLastError(), "henc_count_kernel launch");
-    if (const int e = exclusive_scan_u32(a.bits, (uint64_t *)a.bitpos, N, scratch, scratch_words, stream)) return hip_fail(d, (hipError_t)e, "scan over the blocks");
-    if (henc_interval_bytes(a, stream)) return hip_fail(d, hipGetLastError(), "henc_interval_bytes_kernel launch");
-    if (const int e = exclusive_scan_u32(a.ibytes, (uint64_t *)a.istart, I, scratch, scratch_words, stream)) return hip_fail(d, (hipError_t)e, "scan over the intervals");
-    HIP_TRY(d, hipMemcpyAsync(&readback[0], a.istart + I, 8, hipMemcpyDeviceToHost, stream));
+    if ((rc = coder_stage_one(d, a, base + o_coder, l, stream, FRAME_SCANS, nullptr))) return rc;
+    HIP_TRY(d, hipMemcpyAsync(&readback[0], a.istart + a.n_intervals, 8, hipMemcpyDeviceToHost, stream));
     return MIJPEG_OK;
   }
 
-  // plain stream, stuffing
+  // the plain size is there: arena 2, stage two
   int stage_b()
   {
     HIP_TRY(d, hipStreamSynchronize(stream));
-    const uint64_t plain_bytes = readback[0];
-    const uint32_t I = a.n_intervals;
-    // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check;
-    // of 12-bit pixels at most 15 / 14 bits, which the tables built from the statistics cover)
-    chunks = (uint32_t)((plain_bytes + HENC_STUFF_CHUNK - 1) / HENC_STUFF_CHUNK);
-    Carver ar;
-    const size_t q_plain = ar.take((size_t)plain_bytes + 16);
-    const size_t q_ffc = ar.take((size_t)chunks * 4 + 4);
-    const size_t q_ffs = ar.take(((size_t)chunks + 1) * 8);
-    const size_t q_out = ar.take((size_t)plain_bytes * 2 + (size_t)I * 2 + 16);
-    const size_t q_scratch = ar.take(scan_scratch_bytes(chunks)); // (the chunks may outnumber the blocks: a scratch of their own)
-    const int rc = ensure_dev(d, (void **)&d->henc_out_dev[slot], &d->henc_out_cap[slot], ar.at);
+    a.plain_bytes = readback[0];
+    chunks = (uint32_t)((a.plain_bytes + HENC_STUFF_CHUNK - 1) / HENC_STUFF_CHUNK);
+    const OutputLayout l = output_layout(chunks, a.n_intervals);
+    int rc = ensure_dev(d, (void **)&d->henc_out_dev[slot], &d->henc_out_cap[slot], l.end);
     if (rc) return rc;
-    uint8_t *ob = d->henc_out_dev[slot];
-    a.plain = (uint32_t *)(ob + q_plain);
-    a.plain_bytes = plain_bytes;
-    a.ffcount = (uint32_t *)(ob + q_ffc);
-    a.ffstart = (const uint64_t *)(ob + q_ffs);
-    a.out = ob + q_out;
-    HIP_TRY(d, hipMemsetAsync(ob + q_plain, 0, q_ffc - q_plain, stream)); // (the region with its padding)
-    if (henc_emit(a, stream)) return hip_fail(d, hipGetLastError(), "henc_emit_kernel launch");
-    if (henc_count_ff(a, stream)) return hip_fail(d, hipGetLastError(), "henc_count_ff_kernel launch");
-    if (const int e = exclusive_scan_u32(a.ffcount, (uint64_t *)a.ffstart, chunks, (uint64_t *)(ob + q_scratch), scan_scratch_words(chunks), stream))
-      return hip_fail(d, (hipError_t)e, "scan over the chunks");
-    if (henc_stuff(a, stream)) return hip_fail(d, hipGetLastError(), "henc_stuff_kernel launch");
+    point_into(a, d->henc_out_dev[slot], l);
+    if ((rc = coder_stage_two(d, a, d->henc_out_dev[slot], l, stream, FRAME_SCANS, nullptr, [] { return MIJPEG_OK; }))) return rc;
     HIP_TRY(d, hipMemcpyAsync(&readback[1], a.ffstart + chunks, 8, hipMemcpyDeviceToHost, stream));
     return MIJPEG_OK;
   }
@@ -383,9 +437,7 @@ uint32_t pad256(uint32_t x) { return (x + 255u) & ~255u; }
 // INVALID_PARAMETER
 int plan_one(const mijpeg_encode_frame &e, int precision, mijpeg_info &f, uint32_t &blocks, uint32_t &intervals)
 {
-  if ((precision != 8 && precision != 12) || (e.components != 1 && e.components != 3) || e.width < 1 || e.width > 65535 || e.height < 1 || e.height > 65535 ||
-      e.restart_interval < 0 || e.restart_interval > 65535)
-    return MIJPEG_ERR_INVALID_PARAMETER;
+  if (!shape_in_order(precision, e.components, e.width, e.height) || e.restart_interval < 0 || e.restart_interval > 65535) return MIJPEG_ERR_INVALID_PARAMETER;
   int per_mcu = 0;
   for (int c = 0; c < e.components; c++) {
     if (e.hsamp[c] < 1 || e.hsamp[c] > 4 || e.vsamp[c] < 1 || e.vsamp[c] > 4) return MIJPEG_ERR_INVALID_PARAMETER;
@@ -442,24 +494,6 @@ int plan_list(const mijpeg_encode_frame *frames, const int32_t *precision, int n
 // ------------------------------------------------------------------------------------------------
 // ragged encode: one pass on the device
 // ------------------------------------------------------------------------------------------------
-// launches of an exclusive_scan_u32 over n elements (hencode.hip)
-constexpr int scan_launches(uint32_t n)
-{
-  const uint32_t t1 = n / 1024 + 1;
-  return t1 == 1 ? 1 : t1 / 1024 + 1 == 1 ? 3 : 5;
-}
-static_assert(scan_launches(0) == scan_layout(0).launches && scan_launches(1023) == scan_layout(1023).launches &&
-                  scan_launches(1024) == scan_layout(1024).launches && scan_launches((1u << 20) - 1025) == scan_layout((1u << 20) - 1025).launches &&
-                  scan_launches((1u << 20) - 1024) == scan_layout((1u << 20) - 1024).launches && scan_launches(1u << 20) == scan_layout(1u << 20).launches &&
-                  scan_launches((1u << 30) - 1) == scan_layout((1u << 30) - 1).launches,
-              "the launches the statistics count are the launches the scan makes");
-
-#define LAUNCHED(d, call, what, count)                                          \
-  do {                                                                          \
-    if (const int e_ = (call)) return hip_fail(d, (hipError_t)e_, what " launch"); \
-    (d)->eragged_stats.coder_launches += (count);                               \
-  } while (0)
-
 int sync_counted(mijpeg_decoder *d)
 {
   HIP_TRY(d, hipStreamSynchronize(d->stream));
@@ -480,12 +514,11 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   // ---- the forward kernels' work lists (routing: launch_forward's, per picture)
   std::vector<ForwardArgs> fargs(n);
   std::vector<uint32_t> wl_first[FORWARD_RAGGED_LISTS], wl_item[FORWARD_RAGGED_LISTS]; // per precision and kernel family
-  // pictures that get Huffman tables from their own statistics: all with `optimize`, the 12-bit ones always (the Annex K.3 tables
-  // have no codes for categories 12..15); own_index: their place in the histogram and table arenas
+  // own_index: the place of a picture that codes with tables of its own in the histogram and table arenas
   std::vector<uint32_t> own_index(n, UINT32_MAX);
   uint32_t n_own = 0;
   for (uint32_t p = 0; p < n; p++) {
-    if (optimize || items[p0 + p].info.precision == 12) own_index[p] = n_own++;
+    if (codes_with_own_tables(items[p0 + p].info, optimize)) own_index[p] = n_own++;
     const mijpeg_encode_frame &e = frames[p0 + p];
     mijpeg_forward_batch b;
     memset(&b, 0, sizeof(b));
@@ -526,16 +559,12 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   const size_t up_bytes = up.at;
   Carver dv = up; // device only (or uploaded / read back later)
   const size_t o_fchunk = dv.take(((size_t)n + 1) * 4);
-  const size_t hist_bytes = (size_t)n_own * 4 * 256 * 4; // (the arenas hold the pictures that use them)
+  const size_t hist_bytes = (size_t)n_own * HENC_HIST_BYTES; // (the arenas hold the pictures that use them)
   const size_t o_tabs = dv.take((size_t)n_own * sizeof(HencTables));
   const size_t o_hist = dv.take(hist_bytes);
   const size_t o_gather = dv.take(((size_t)n + 1) * 8);
-  const size_t o_bits = dv.take((size_t)N * 4);
-  const size_t o_bitpos = dv.take(((size_t)N + 1) * 8);
-  const size_t o_ibytes = dv.take((size_t)I * 4);
-  const size_t o_istart = dv.take(((size_t)I + 1) * 8);
-  const size_t o_scratch = dv.take(scan_scratch_bytes(N));
-  const size_t scratch_words = scan_scratch_words(N);
+  const CoderLayout cl = coder_layout(N, I);
+  const size_t o_coder = dv.take(cl.end);
   const size_t o_coef = dv.take((size_t)coef_total * sizeof(int16_t));
   int rc = ensure_dev(d, (void **)&d->eragged_dev, &d->eragged_cap, dv.at);
   if (rc) return rc;
@@ -550,7 +579,6 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   if (rc) return rc;
   uint8_t *dev = d->eragged_dev, *host = d->eragged_host;
   int16_t *coef = (int16_t *)(dev + o_coef);
-  uint64_t *scratch = (uint64_t *)(dev + o_scratch);
 
   // ---- fill the tables
   EncTables std_tabs; // Annex K.3: what the 8-bit pictures code with unless their tables are optimised
@@ -572,10 +600,7 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
     a.tables = (const HencTables *)(dev + o_stdtab);
     a.total_blocks = it.blocks;
     a.n_intervals = it.intervals;
-    a.bits = (uint32_t *)(dev + o_bits) + it.first_block;
-    a.bitpos = (const uint64_t *)(dev + o_bitpos) + it.first_block;
-    a.ibytes = (uint32_t *)(dev + o_ibytes) + it.first_interval;
-    a.istart = (const uint64_t *)(dev + o_istart) + it.first_interval;
+    point_into(a, dev + o_coder, cl, it.first_block, it.first_interval);
     a.hist = own_index[p] != UINT32_MAX ? (uint32_t *)(dev + o_hist) + (size_t)own_index[p] * 4 * 256 : nullptr;
     h_first_block[p] = it.first_block;
     h_first_int[p] = it.first_interval;
@@ -609,35 +634,28 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   b.n = n;
   b.total_blocks = N;
   b.total_intervals = I;
+  int32_t *launches = &d->eragged_stats.coder_launches;
   if (n_own) { // (the statistics launch runs over the pass; workgroups of pictures without a histogram leave at once)
     HIP_TRY(d, hipMemsetAsync(dev + o_hist, 0, hist_bytes, stream));
-    LAUNCHED(d, henc_count(b, true, stream), "henc_count_kernel", 1);
+    LAUNCHED(d, henc_count(b, true, stream), "henc_count_kernel launch", 1, launches);
     HIP_TRY(d, hipMemcpyAsync(host + h_hist, dev + o_hist, hist_bytes, hipMemcpyDeviceToHost, stream));
     if ((rc = sync_counted(d))) return rc;
     HencTables *ht = (HencTables *)(host + h_tabs);
     for (uint32_t p = 0; p < n; p++) {
       const uint32_t o = own_index[p];
       if (o == UINT32_MAX) continue;
-      const uint32_t(*hist)[256] = (const uint32_t(*)[256])(host + h_hist) + (size_t)o * 4;
-      enc_standard_tables(tabs[o]);
-      enc_optimal_tables(tabs[o], hist, hist + 2, items[p0 + p].info.components > 1 ? 2 : 1);
-      henc_pack_tables(ht + o, tabs[o]);
+      tables_from_statistics((const uint32_t(*)[256])(host + h_hist) + (size_t)o * 4, items[p0 + p].info.components, tabs[o], ht + o);
       hh[p].tables = (const HencTables *)(dev + o_tabs) + o;
     }
     HIP_TRY(d, hipMemcpyAsync(dev + o_tabs, ht, (size_t)n_own * sizeof(HencTables), hipMemcpyHostToDevice, stream));
     HIP_TRY(d, hipMemcpyAsync(dev + o_hargs, hh, (size_t)n * sizeof(HencArgs), hipMemcpyHostToDevice, stream)); // (tables now the pictures' own)
   }
-  LAUNCHED(d, henc_count(b, false, stream), "henc_count_kernel", 1);
-  LAUNCHED(d, exclusive_scan_u32((const uint32_t *)(dev + o_bits), (uint64_t *)(dev + o_bitpos), N, scratch, scratch_words, stream), "scan", scan_launches(N));
-  LAUNCHED(d, henc_interval_bytes(b, stream), "henc_interval_bytes_kernel", 1);
-  LAUNCHED(d, exclusive_scan_u32((const uint32_t *)(dev + o_ibytes), (uint64_t *)(dev + o_istart), I, scratch, scratch_words, stream), "scan", scan_launches(I));
-  LAUNCHED(d, henc_gather((const uint64_t *)(dev + o_istart), b.first_interval, (uint64_t *)(dev + o_gather), n + 1, stream), "henc_gather_kernel", 1);
+  if ((rc = coder_stage_one(d, b, dev + o_coder, cl, stream, PASS_SCANS, launches))) return rc;
+  LAUNCHED(d, henc_gather((const uint64_t *)(dev + o_coder + cl.istart), b.first_interval, (uint64_t *)(dev + o_gather), n + 1, stream), "henc_gather_kernel launch", 1, launches);
   HIP_TRY(d, hipMemcpyAsync(host + h_istart, dev + o_gather, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
   if ((rc = sync_counted(d))) return rc;
 
   // ---- layout of the plain buffer: every picture on a chunk boundary
-  // (coefficients the forward kernels make of 8-bit pixels always have a code: at most 11 / 10 bits, the host coder's check; of
-  // 12-bit pixels at most 15 / 14 bits, which the tables built from the statistics cover)
   const uint64_t *g_istart = (const uint64_t *)(host + h_istart);
   uint32_t *h_first_chunk = (uint32_t *)(host + h_fchunk);
   uint64_t chunks = 0;
@@ -648,28 +666,17 @@ int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijp
   }
   h_first_chunk[n] = (uint32_t)chunks;
   const size_t plain_total = (size_t)chunks * HENC_STUFF_CHUNK;
-  Carver ob;
-  const size_t q_plain = ob.take(plain_total + 16);
-  const size_t q_ffc = ob.take(((size_t)chunks + 1) * 4);
-  const size_t q_ffs = ob.take(((size_t)chunks + 1) * 8);
-  const size_t q_out = ob.take(plain_total * 2 + (size_t)I * 2 + 16);
-  const size_t q_scratch = ob.take(scan_scratch_bytes((size_t)chunks)); // (the chunks may outnumber the blocks: a scratch of their own)
-  rc = ensure_dev(d, (void **)&d->eragged_out_dev, &d->eragged_out_cap, ob.at);
+  const OutputLayout ol = output_layout((uint32_t)chunks, I);
+  rc = ensure_dev(d, (void **)&d->eragged_out_dev, &d->eragged_out_cap, ol.end);
   if (rc) return rc;
-  uint8_t *od = d->eragged_out_dev;
-  b.total_chunks = (uint32_t)chunks;
-  b.plain = (uint32_t *)(od + q_plain);
-  b.ffcount = (uint32_t *)(od + q_ffc);
-  b.ffstart = (const uint64_t *)(od + q_ffs);
-  b.out = od + q_out;
+  b.total_chunks = ol.chunks;
+  point_into(b, d->eragged_out_dev, ol);
   HIP_TRY(d, hipMemcpyAsync(dev + o_fchunk, h_first_chunk, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, stream));
-  HIP_TRY(d, hipMemsetAsync(od + q_plain, 0, plain_total + 16, stream));
-  LAUNCHED(d, henc_emit(b, stream), "henc_emit_kernel", 1);
-  LAUNCHED(d, henc_count_ff(b, stream), "henc_count_ff_kernel", 1);
-  LAUNCHED(d, exclusive_scan_u32(b.ffcount, (uint64_t *)b.ffstart, b.total_chunks, (uint64_t *)(od + q_scratch), scan_scratch_words((size_t)chunks), stream), "scan",
-           scan_launches(b.total_chunks));
-  LAUNCHED(d, henc_gather(b.ffstart, b.first_chunk, (uint64_t *)(dev + o_gather), n + 1, stream), "henc_gather_kernel", 1);
-  LAUNCHED(d, henc_stuff(b, stream), "henc_stuff_kernel", 1);
+  rc = coder_stage_two(d, b, d->eragged_out_dev, ol, stream, PASS_SCANS, launches, [&]() -> int { // (where every picture's piece of `out` lies)
+    LAUNCHED(d, henc_gather(b.ffstart, b.first_chunk, (uint64_t *)(dev + o_gather), n + 1, stream), "henc_gather_kernel launch", 1, launches);
+    return MIJPEG_OK;
+  });
+  if (rc) return rc;
   HIP_TRY(d, hipMemcpyAsync(host + h_ffs, dev + o_gather, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, stream));
   if ((rc = sync_counted(d))) return rc;
 
@@ -706,9 +713,8 @@ uint32_t pass_blocks_setting()
 // pixels, and a row stride that holds a line; 16-bit samples: address and stride on 2-byte boundaries
 bool pixels_in_order(const mijpeg_encode_frame &e, int precision)
 {
-  const int sb = precision == 12 ? 2 : 1;
-  if (!e.pixels || e.row_stride < (int64_t)e.width * e.components * sb) return false;
-  return sb == 1 || (((uintptr_t)e.pixels | (uintptr_t)e.row_stride) & 1) == 0;
+  if (!e.pixels || !line_fits(precision, e.components, e.width, e.row_stride)) return false;
+  return precision != 12 || (((uintptr_t)e.pixels | (uintptr_t)e.row_stride) & 1) == 0;
 }
 
 // the list, pass by pass; pixels in device memory
@@ -751,8 +757,7 @@ int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int
     for (int i = 0; i < n && !rc; i++) {
       const mijpeg_encode_frame &e = frames[i];
       const int pr = precision_of(precision, i);
-      if ((pr != 8 && pr != 12) || e.height < 1 || e.height > 65535 || e.width < 1 || e.width > 65535 || (e.components != 1 && e.components != 3) ||
-          !pixels_in_order(e, pr))
+      if (!shape_in_order(pr, e.components, e.width, e.height) || !pixels_in_order(e, pr))
         rc = set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "invalid picture description in the list");
       else
         off[(size_t)i + 1] = (off[(size_t)i] + (size_t)e.row_stride * (size_t)e.height + 255) & ~(size_t)255;
@@ -775,10 +780,9 @@ int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int
   if (!rc) rc = encode_list(d, frames, precision, n, optimize, streams, sizes);
   if (rc) {
     (void)hipStreamSynchronize(d->stream);
-    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+    drop_streams(streams, sizes, n);
   }
-  d->timing[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); // mijpeg_last_timing: the whole call
-  d->timing[1] = d->timing[2] = d->timing[3] = 0;
+  whole_call_timing(d, t_begin);
   return rc;
 }
 
@@ -854,10 +858,8 @@ try {
   }
   (void)hipStreamSynchronize(d->copy_stream);
   (void)hipStreamSynchronize(d->stream);
-  if (rc)
-    for (int f = 0; f < b->frames; f++) { free(streams[f]); streams[f] = nullptr; sizes[f] = 0; }
-  d->timing[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); // mijpeg_last_timing: the whole call
-  d->timing[1] = d->timing[2] = d->timing[3] = 0;
+  if (rc) drop_streams(streams, sizes, b->frames);
+  whole_call_timing(d, t_begin);
   return rc;
 } catch (...) { return boundary_catch(d, "mijpeg_encode_batch_device"); }
 
@@ -886,12 +888,9 @@ try {
   int rc = device_entropy_code(d, f, coef_dev, restart_interval, optimize, stream, size, true);
   if (rc) {
     (void)hipStreamSynchronize(d->stream);
-    free(*stream);
-    *stream = nullptr;
-    *size = 0;
+    drop_streams(stream, size, 1);
   }
-  d->timing[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count(); // mijpeg_last_timing: the whole call
-  d->timing[1] = d->timing[2] = d->timing[3] = 0;
+  whole_call_timing(d, t_begin);
   return rc;
 } catch (...) { return boundary_catch(d, "mijpeg_encode_coefficients_device"); }
 
@@ -908,8 +907,8 @@ static int encode_image_of(mijpeg_decoder *d, const uint8_t *pixels, int32_t wid
 {
   using clk = std::chrono::steady_clock;
   const auto t_begin = clk::now();
-  if (!d || !pixels || !stream || !size || (components != 1 && components != 3) || row_stride < (int64_t)width * components * (precision == 12 ? 2 : 1))
-    return MIJPEG_ERR_INVALID_PARAMETER;
+  // (width and height are mijpeg_frame_layout's to refuse, below and under its own message)
+  if (!d || !pixels || !stream || !size || (components != 1 && components != 3) || !line_fits(precision, components, width, row_stride)) return MIJPEG_ERR_INVALID_PARAMETER;
   if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
   HIP_TRY(d, hipSetDevice(d->device));
   mijpeg_forward_batch b;
@@ -1001,8 +1000,7 @@ int mijpeg_encode_ragged_device16(mijpeg_decoder *d, const mijpeg_encode_frame *
 try {
   return encode_entry(d, frames, precision, n, optimize, flags, streams, sizes, false);
 } catch (...) {
-  if (streams && sizes)
-    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+  drop_streams(streams, sizes, n);
   return boundary_catch(d, "mijpeg_encode_ragged_device16");
 }
 
@@ -1011,8 +1009,7 @@ int mijpeg_encode_ragged16(mijpeg_decoder *d, const mijpeg_encode_frame *frames,
 try {
   return encode_entry(d, frames, precision, n, optimize, flags, streams, sizes, true);
 } catch (...) {
-  if (streams && sizes)
-    for (int i = 0; i < n; i++) { free(streams[i]); streams[i] = nullptr; sizes[i] = 0; }
+  drop_streams(streams, sizes, n);
   return boundary_catch(d, "mijpeg_encode_ragged16");
 }
 

@@ -139,6 +139,67 @@ static_assert(scan_layout_consistent((1u << 30) - 1) && scan_layout((1u << 30) -
               "the layout arithmetic holds past the scan's reach");
 static_assert(scan_layout(HENC_SCAN_MAX).in_reach && !scan_layout(HENC_SCAN_MAX + 1).in_reach && !scan_layout((1u << 30) - 1).in_reach, "the scan's reach");
 
+// ---- the coder's buffers (encode_device.cpp) ------------------------------------------------------------------------
+// Their only statement, for one frame and for a pass of a list alike: the host drivers take offsets, sizes, the extent to zero and
+// the scans' capacity from here.  Offsets are bytes from the start of a 256-byte aligned region; every array starts on such a boundary.
+constexpr size_t henc_aligned(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+// words of scratch for an exclusive_scan_u32 over n elements, some to spare (n beyond the scan's reach: the scan refuses whatever it gets)
+constexpr size_t scan_scratch_words(size_t n) { return (size_t)scan_layout((uint32_t)(n < HENC_SCAN_MAX ? n : HENC_SCAN_MAX)).words + 32; }
+
+// the arrays over N blocks and I intervals: bits[N], bitpos[N + 1], ibytes[I], istart[I + 1], ONE scratch for the scan over the
+// blocks and then the one over the intervals
+struct CoderLayout { uint32_t N, I; size_t bits, bitpos, ibytes, istart, scratch, end, scratch_words; };
+constexpr CoderLayout coder_layout(uint32_t N, uint32_t I)
+{
+  CoderLayout l{N, I};
+  l.bitpos = l.bits + henc_aligned((size_t)N * 4);
+  l.ibytes = l.bitpos + henc_aligned(((size_t)N + 1) * 8);
+  l.istart = l.ibytes + henc_aligned((size_t)I * 4);
+  l.scratch = l.istart + henc_aligned(((size_t)I + 1) * 8);
+  l.scratch_words = scan_scratch_words(N > I ? N : I);
+  l.end = l.scratch + henc_aligned(l.scratch_words * 8);
+  return l;
+}
+// the output arena of a plain stream of `chunks` times HENC_STUFF_CHUNK bytes in I intervals: the plain stream (`zeroed` bytes of
+// it are cleared before henc_emit), ffcount[chunks + 1], ffstart[chunks + 1], out (every byte stuffed and a marker per interval at
+// the most), and a scratch for the scan over the CHUNKS, which may outnumber the blocks
+struct OutputLayout { uint32_t chunks; size_t plain, ffcount, ffstart, out, scratch, end, zeroed, scratch_words; };
+constexpr OutputLayout output_layout(uint32_t chunks, uint32_t I)
+{
+  OutputLayout l{chunks};
+  l.zeroed = (size_t)chunks * HENC_STUFF_CHUNK + 16;
+  l.ffcount = l.plain + henc_aligned(l.zeroed);
+  l.ffstart = l.ffcount + henc_aligned(((size_t)chunks + 1) * 4);
+  l.out = l.ffstart + henc_aligned(((size_t)chunks + 1) * 8);
+  l.scratch = l.out + henc_aligned((size_t)chunks * HENC_STUFF_CHUNK * 2 + (size_t)I * 2 + 16);
+  l.scratch_words = scan_scratch_words(chunks);
+  l.end = l.scratch + henc_aligned(l.scratch_words * 8);
+  return l;
+}
+// every region starts at or behind the end of the one before it, and a scratch holds what scan_layout() says its scans take
+constexpr bool coder_layout_consistent(uint32_t N, uint32_t I)
+{
+  const CoderLayout l = coder_layout(N, I);
+  return l.bitpos >= l.bits + (size_t)N * 4 && l.ibytes >= l.bitpos + ((size_t)N + 1) * 8 && l.istart >= l.ibytes + (size_t)I * 4 && l.scratch >= l.istart + ((size_t)I + 1) * 8 &&
+         l.end >= l.scratch + l.scratch_words * 8 && l.scratch_words >= scan_layout(N).words && l.scratch_words >= scan_layout(I).words;
+}
+constexpr bool output_layout_consistent(uint32_t chunks, uint32_t I)
+{
+  const OutputLayout l = output_layout(chunks, I);
+  const size_t plain_bytes = (size_t)chunks * HENC_STUFF_CHUNK;
+  return l.zeroed >= plain_bytes && l.ffcount >= l.plain + l.zeroed && l.ffstart >= l.ffcount + ((size_t)chunks + 1) * 4 && l.out >= l.ffstart + ((size_t)chunks + 1) * 8 &&
+         l.scratch >= l.out + 2 * plain_bytes + 2 * (size_t)I + 16 && l.end >= l.scratch + l.scratch_words * 8 && l.scratch_words >= scan_layout(chunks).words;
+}
+static_assert(coder_layout_consistent(0, 0) && coder_layout_consistent(1023, 1023) && coder_layout_consistent(1024, 1) && coder_layout_consistent(1024, 1024) &&
+                  coder_layout_consistent((1u << 20) - 1025, 1) && coder_layout_consistent((1u << 20) - 1024, (1u << 20) - 1024) &&
+                  coder_layout_consistent(HENC_SCAN_MAX, 1) && coder_layout_consistent(HENC_SCAN_MAX, HENC_SCAN_MAX),
+              "the arrays over blocks and intervals do not overlap and their scratch holds either scan");
+static_assert(output_layout_consistent(0, 1) && output_layout_consistent(1023, 1) && output_layout_consistent(1024, 1024) && output_layout_consistent((1u << 20) - 1025, 1) &&
+                  output_layout_consistent((1u << 20) - 1024, 65536) && output_layout_consistent(HENC_SCAN_MAX, 1),
+              "the regions of the output arena do not overlap; the zeroed extent reaches the last chunk's end and stops in front of ffcount");
+static_assert(coder_layout(1u << 22, 1).scratch_words < scan_layout(1u << 23).words && output_layout(1u << 23, 1).scratch_words >= scan_layout(1u << 23).words,
+              "the scan over the chunks has a scratch sized from the chunks: 2^22 blocks of 128 bytes each are 2^23 chunks, past the blocks' scratch");
+
 // out[i] = sum of in[0..i) for i = 0..n (n + 1 entries); scratch: scratch_words uint64, at least scan_layout(n).words of them.
 // hipErrorInvalidValue, before anything is launched, where the scratch is smaller or n is beyond HENC_SCAN_MAX
 int exclusive_scan_u32(const uint32_t *in, uint64_t *out, uint32_t n, uint64_t *scratch, size_t scratch_words, hipStream_t stream);

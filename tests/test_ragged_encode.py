@@ -371,8 +371,12 @@ def test_launches_and_synchronisations_do_not_grow_with_n(dec, optimize):
         for i in range(n):
             assert streams[i] == _single(dec, imgs[i], 85, cases[i][2], 0, optimize), (n, i, cases[i])
         del keep
+    print("coder statistics", optimize, stats)
     for k in ("forward_launches", "coder_launches", "host_syncs"):
         assert stats[4][k] == stats[64][k] and stats[4][k] > 0, (k, stats)
+    # seven single launches (count, interval bytes, two gathers, emit, 0xFF count, stuffing), three for the prefix sum over 1024 or
+    # 16384 padded blocks, one each for the sums over intervals and chunks, one more for the statistics
+    assert stats[64]["coder_launches"] == (13 if optimize else 12)
     assert stats[64]["host_syncs"] <= 4 * stats[64]["passes"]
     assert stats[64]["host_syncs"] == (4 if optimize else 3)
     assert stats[64]["forward_launches"] <= 6
