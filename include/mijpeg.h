@@ -254,6 +254,26 @@ mijpeg_decoder *mijpeg_batch_pipeline_decoder(mijpeg_batch_pipeline *p, int k);
  * no device involved (works on host-only objects).  This is what a rank's cores do per chunk of a batch; `bench.py
  * --emulate-world N` runs it in neighbour processes to load the host the way the other ranks of a node would. */
 int mijpeg_prepare_batch_host(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n);
+/* Opt-in: search the restart markers and strip the byte stuffing on the DEVICE (on = 1; off, 0, by default; anything else is
+ * MIJPEG_ERR_INVALID_PARAMETER).  With it on, mijpeg_decode_coefficients_device, mijpeg_decode_batch_device,
+ * mijpeg_submit_batch_device / mijpeg_finish_batch_device and mijpeg_prepare_batch_host (its host half) parse the headers only,
+ * copy the raw entropy coded segment into the staging slot with one memcpy, and two kernel passes in front of the Huffman
+ * launch write the copy without stuffing and markers and the interval tables where that launch reads them.  Every image of the
+ * call must qualify -- plain (no JPEG XT, no DNL) 8-bit Huffman sequential, one scan over all components, DRI > 0, FF D9 as the
+ * last two bytes of the stream -- else the whole call takes the ordinary route.  The search must come out plain as well: no fill
+ * byte, exactly the markers the MCU count asks for, in sequence, and the segment ending at the FF of that closing EOI.  Where it
+ * does not, the synchronous calls run the ordinary route inside the same call (the caller sees what it would have seen with the
+ * option off); mijpeg_finish_batch_device, which no longer has the bytes, answers MIJPEG_ERR_NOT_AVAILABLE as it does for damaged
+ * streams.  The ragged calls, multi-scan / progressive / JPEG XT frames, streams without restart markers, class JPEG and the
+ * command line ignore the option.  stats: images of this object that went through the device search, and images of calls that
+ * took the ordinary route although the option was on (either pointer may be NULL). */
+int mijpeg_set_device_markers(mijpeg_decoder *d, int on);
+int mijpeg_device_markers_stats(mijpeg_decoder *d, int64_t *searched, int64_t *declined);
+/* ... for every decoder object of a pipeline (on < 0: leave as is).  Returns the setting. */
+int mijpeg_batch_pipeline_device_markers(mijpeg_batch_pipeline *p, int on);
+/* Diagnostics: where the last mijpeg_prepare_batch_host / batch submit with the option on put the raw segment of image i (host
+ * memory, valid until the object's next call) and its size in *bytes; NULL when that call took the ordinary route. */
+const uint8_t *mijpeg_device_markers_staging(mijpeg_decoder *d, int image, size_t *bytes);
 /* Wait for everything the object has enqueued on its stream (e.g. a reconstruction launched with sync = 0). */
 int mijpeg_synchronize(mijpeg_decoder *d);
 /* ... or let a stream of the CLIENT's wait for it instead of the host: everything the object has enqueued so far (uploads, entropy
@@ -406,6 +426,21 @@ int mijpeg_last_warning(mijpeg_decoder *d, const char **message);
  * NULL or too small: nothing is copied then), or a negative error code.  *n_intervals (may be NULL): restart intervals. */
 int64_t mijpeg_unstuffed_scan(mijpeg_decoder *d, uint8_t *dst, size_t capacity, uint32_t *begin, size_t n_begin, size_t piece_bytes,
                               int32_t *n_intervals);
+
+/* Diagnostics, the device twin of mijpeg_unstuffed_scan: the segment-level primitive behind mijpeg_set_device_markers on `size`
+ * raw bytes as they lie in the file from the first entropy coded byte on (terminator and whatever follows included), for a frame
+ * whose header asks for `expect` restart intervals.  A byte pair is only ever interpreted from its FF.  *term: position of the
+ * first FF whose follower is none of 00, FF, D0..D7 -- nothing at or behind it is interpreted, kept or counted -- or `size` with
+ * flag 8 (NO_END) when there is none (a lone FF as last byte included; size = 0 is legal).  In front of it FF 00 keeps the FF and
+ * drops the 00, FF Dn drops both and is restart marker k = 0, 1, ..., FF FF sets flag 1 (FILL).  Flag 2 (SEQUENCE): a marker's
+ * code is not 0xD0 + (k & 7); flag 4 (COUNT): markers + 1 != expect.  With *flags == 0: dst holds the kept bytes back to back and
+ * zeros from there to `capacity` (>= size), begin[0] = 0, begin[k + 1] = end[k] = kept bytes in front of marker k,
+ * end[expect - 1] = the return value (`expect` entries each; either may be NULL).  With a flag set only *flags and *term are
+ * defined.  The call uploads, runs the kernels, checks that nothing outside the device copies of dst / begin / end was written
+ * (MIJPEG_ERR_PHASE_ERROR otherwise) and downloads.  Returns the number of kept bytes or a negative error code; segments of
+ * 2^28 bytes or more are MIJPEG_ERR_NOT_AVAILABLE. */
+int64_t mijpeg_device_marker_search(mijpeg_decoder *d, const uint8_t *segment, size_t size, int32_t expect, uint8_t *dst, size_t capacity,
+                                    uint32_t *begin, uint32_t *end, uint32_t *term, uint32_t *flags);
 
 /* Diagnostics: number of scans without restart markers that the host decoder decoded in parallel (self-synchronising
  * speculative decoding) since the library was loaded; *pieces (may be NULL) = ranges they were stitched from. */

@@ -189,6 +189,14 @@ def lib():
         L.mijpeg_encode_ragged16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_free.argtypes = [C.c_void_p]
         L.mijpeg_free.restype = None
+        L.mijpeg_set_device_markers.argtypes = [C.c_void_p, C.c_int]
+        L.mijpeg_device_markers_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.mijpeg_batch_pipeline_device_markers.argtypes = [C.c_void_p, C.c_int]
+        L.mijpeg_device_markers_staging.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]
+        L.mijpeg_device_markers_staging.restype = C.c_void_p
+        L.mijpeg_device_marker_search.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.mijpeg_device_marker_search.restype = C.c_int64
         L.mijpeg_device_walk_rounds.argtypes = [C.c_void_p]
         L.mijpeg_device_walk_rounds.restype = C.c_int
         L.mijpeg_speculative_scans.argtypes = [C.POINTER(C.c_int64)]
@@ -577,6 +585,37 @@ class Decoder:
         L = lib()
         L.mijpeg_prepare_batch_host.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int]
         self._check(L.mijpeg_prepare_batch_host(self._h, arr, sizes, n))
+
+    def set_device_markers(self, on) -> None:
+        """mijpeg_set_device_markers: restart marker search and unstuffing of qualifying device decodes on the device (opt-in)."""
+        self._check(lib().mijpeg_set_device_markers(self._h, int(on)))
+
+    def device_markers_stats(self):
+        """mijpeg_device_markers_stats -> (searched, declined): images of this object that went through the device search, images
+        of calls that took the ordinary route although the option was on."""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(lib().mijpeg_device_markers_stats(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def device_markers_staging(self, image: int):
+        """mijpeg_device_markers_staging: the raw segment of image `image` as the last batch call with the option on staged it
+        (bytes), or None when that call took the ordinary route."""
+        n = C.c_size_t()
+        p = lib().mijpeg_device_markers_staging(self._h, image, C.byref(n))
+        return C.string_at(p, n.value) if p else None
+
+    def device_marker_search(self, segment: bytes, expect: int, capacity: int | None = None):
+        """mijpeg_device_marker_search (diagnostics) -> dict(total, dst, begin, end, term, flags): the search kernels on one raw
+        segment; dst holds `capacity` bytes (default: the segment's size + 256)."""
+        capacity = len(segment) + 256 if capacity is None else capacity
+        dst = np.zeros(capacity, np.uint8)
+        begin, end = np.zeros(expect, np.uint32), np.zeros(expect, np.uint32)
+        term, flags = C.c_uint32(), C.c_uint32()
+        total = lib().mijpeg_device_marker_search(self._h, segment, len(segment), expect, dst.ctypes.data, capacity, begin.ctypes.data, end.ctypes.data,
+                                                  C.byref(term), C.byref(flags))
+        if total < 0:
+            self._check(int(total))
+        return dict(total=int(total), dst=dst, begin=begin, end=end, term=term.value, flags=flags.value)
 
     @staticmethod
     def stream_arrays(streams):

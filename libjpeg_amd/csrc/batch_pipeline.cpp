@@ -32,6 +32,7 @@ struct mijpeg_batch_pipeline {
   // diagnostics of the last run
   int32_t chunks = 0, fallbacks = 0, redone = 0;
   bool speculate = false, finished_once = false;
+  int device_markers = 0;
   std::vector<float> submit_ms;
   int err_code = 0;
   std::string err_msg;
@@ -297,6 +298,17 @@ int mijpeg_batch_pipeline_speculation(mijpeg_batch_pipeline *p, int on)
   if (!p) return MIJPEG_ERR_INVALID_PARAMETER;
   if (on >= 0) p->speculate = on != 0;
   return p->redone; // chunks of the last run whose speculative reconstruction had to be made again
+}
+
+int mijpeg_batch_pipeline_device_markers(mijpeg_batch_pipeline *p, int on)
+{
+  if (!p || on > 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (on >= 0) {
+    for (mijpeg_decoder *d : p->dec)
+      if (const int rc = mijpeg_set_device_markers(d, on)) return rc;
+    p->device_markers = on;
+  }
+  return p->device_markers;
 }
 
 int mijpeg_batch_pipeline_last_error(mijpeg_batch_pipeline *p, const char **message)

@@ -588,22 +588,46 @@ const int16_t *mijpeg_coefficients(mijpeg_decoder *d, int component)
   return d->coef_host + d->host.info.coef_offset[component];
 }
 
-int mijpeg_decode_coefficients_device(mijpeg_decoder *d, int min_intervals)
-try {
-  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (!d->data) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no input stream has been set");
+// The marker route of a call (mijpeg_set_device_markers) is an attempt: it ends well, or the call runs the ordinary route as if
+// the option were off -- error state included (whatever the attempt reported is taken back).  Counts the images either way.
+static int with_device_markers(mijpeg_decoder *d, int images, const std::function<int(bool)> &attempt)
+{
+  if (d->device_markers == 1) {
+    const int keep_code = d->err_code;
+    const std::string keep_msg = d->err_msg;
+    d->markers_retry = false;
+    d->markers_staged.clear();
+    if (attempt(true) == MIJPEG_OK) {
+      d->markers_searched += images;
+      return MIJPEG_OK;
+    }
+    d->markers_staged.clear();
+    d->markers_declined += images;
+    d->err_code = keep_code;
+    d->err_msg = keep_msg;
+  }
+  return attempt(false);
+}
+
+static int decode_coefficients_device(mijpeg_decoder *d, int min_intervals, bool markers)
+{
   if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
   HIP_TRY(d, hipSetDevice(d->device));
   if (const int prc = settle_pending(d)) return prc;
   using clk = std::chrono::steady_clock;
   const auto t0 = clk::now();
   d->parse_fresh = false;
+  if (markers) d->host.set_skip_search(); // (headers only: the device searches the segment)
   int rc = d->host.parse(d->data, d->size, false);
   if (rc) return set_error(d, rc, d->host.error.message);
   d->parsed = true;
   d->batch_frames = 0;
   const auto t_parsed = clk::now();
   HostDecoder *h = &d->host, *res = d->host.residual();
+  if (markers) {
+    const char *why = res ? "device marker search: plain 8-bit frames only" : device_markers_obstacle(d->host, d->size);
+    if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
+  }
   // (a stream that does not qualify: the parse is as good as the one mijpeg_decode_coefficients would make next)
   d->parse_fresh = true;
   // progressive frames and frames with hidden refinement scans: every scan one restart interval per lane (huffman_prog_kernel)
@@ -639,7 +663,7 @@ try {
     MultiScanFrame fr[2] = {{h, false, 0}, {res, res && d->host.xt.residual_wide != 0, own_count}};
     rc = device_entropy_multiscan(d, fr, res ? 2 : 1, min_intervals);
   } else if (!res) {
-    rc = device_entropy_batch(d, &h, &d->data, &d->size, 1, min_intervals, d->coef_dev, own_count, false);
+    rc = device_entropy_batch(d, &h, &d->data, &d->size, 1, min_intervals, d->coef_dev, own_count, false, false, nullptr, markers);
   } else {
     // JPEG XT: the two codestreams are independent, so the residual one is decoded at the same time by a helper object
     // (own stream, own buffers) on a thread of its own, straight into the planes behind the legacy frame's
@@ -680,6 +704,14 @@ try {
   d->uploaded = true;
   d->host_planes_stale = true;
   return decode_alpha_channel(d, 0);
+}
+
+int mijpeg_decode_coefficients_device(mijpeg_decoder *d, int min_intervals)
+try {
+  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (!d->data) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no input stream has been set");
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  return with_device_markers(d, 1, [&](bool markers) { return decode_coefficients_device(d, min_intervals, markers); });
 } catch (...) { return boundary_catch(d, "mijpeg_decode_coefficients_device"); }
 
 // ------------------------------------------------------------------------------------------------
@@ -723,7 +755,7 @@ bool same_shape_and_tables(const mijpeg_info &a, const mijpeg_info &b)
 }
 } // namespace
 
-static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, bool defer)
+static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, bool defer, bool markers)
 {
   if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
   if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
@@ -752,7 +784,8 @@ static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const 
       for (int i = w; i < n; i += std::min(n, default_threads())) {
         // (a worker walks ~3 GB/s this way: good for the many small streams of a batch; a large stream is searched in
         // parallel chunks and gathered in parallel pieces instead -- device_entropy_batch sees which it was)
-        if (sizes[i] <= ((size_t)2 << 20) || n >= default_threads()) d->batch_hosts[(size_t)i]->set_unstuff_sink(d->stage_host + slot[(size_t)i], sizes[i]);
+        if (markers) d->batch_hosts[(size_t)i]->set_skip_search(); // (headers only: the device searches the segments)
+        else if (sizes[i] <= ((size_t)2 << 20) || n >= default_threads()) d->batch_hosts[(size_t)i]->set_unstuff_sink(d->stage_host + slot[(size_t)i], sizes[i]);
         rcs[(size_t)i] = d->batch_hosts[(size_t)i]->parse(streams[i], sizes[i], false);
       }
     });
@@ -763,7 +796,8 @@ static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const 
   std::vector<HostDecoder *> hosts((size_t)n);
   for (int i = 0; i < n; i++) hosts[(size_t)i] = d->batch_hosts[(size_t)i].get();
   for (int i = 0; i < n; i++)
-    if (const char *why = device_entropy_obstacle(*hosts[(size_t)i], sizes[i])) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
+    if (const char *why = markers ? device_markers_obstacle(*hosts[(size_t)i], sizes[i]) : device_entropy_obstacle(*hosts[(size_t)i], sizes[i]))
+      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
   const mijpeg_info &f0 = hosts[0]->info;
   // one reconstruction launch serves the batch; images with tables of their own (motion JPEG under rate control) make it
   // read per-frame tables from device memory instead of the kernel arguments
@@ -779,7 +813,12 @@ static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const 
   d->uploaded = false;
   d->decoded = false;
   d->pend_n = 0;
-  rc = device_entropy_batch(d, hosts.data(), streams, sizes, n, min_intervals, d->coef_dev, f0.coef_count, false, defer);
+  rc = device_entropy_batch(d, hosts.data(), streams, sizes, n, min_intervals, d->coef_dev, f0.coef_count, false, defer, nullptr, markers);
+  if (!rc && markers) {
+    std::vector<size_t> slot;
+    stream_slots(sizes, n, slot);
+    for (int i = 0; i < n; i++) d->markers_staged.emplace_back(slot[(size_t)i], sizes[i] - hosts[(size_t)i]->scans[0].ecs_begin);
+  }
   d->timing[0] = std::chrono::duration<double>(clk::now() - t0).count();
   d->timing[1] = std::chrono::duration<double>(t_parsed - t0).count();
   d->timing[2] = d->phase_prepare;
@@ -832,6 +871,15 @@ static int finish_batch(mijpeg_decoder *d)
       d->walk_rounds = walk_rounds_needed(d->pend_walk_flags, rounds);
       if (d->pend_walk_status)
         if (const int wrc = walk_verdict(d, d->pend_walk_status, pn)) return wrc;
+    }
+    if (d->pend_markers) { // the device searched the segments: is every search good?  (The bytes are gone: the caller's fallback takes over)
+      const uint32_t *results = d->pend_markers;
+      d->pend_markers = nullptr;
+      if (!device_markers_good(results, d->markers_want_term.data(), pn)) {
+        d->markers_searched -= pn;
+        d->markers_declined += pn;
+        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: a segment is not the plain case; the host searches such streams (mijpeg_decode_batch_device)");
+      }
     }
     const int rc = evaluate_entropy_status(d, hosts.data(), pn, d->pend_status);
     if (rc) return rc;
@@ -902,12 +950,12 @@ extern "C++" int settle_speculation(mijpeg_decoder *d) // (C++ linkage as decode
 
 int mijpeg_decode_batch_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals)
 try {
-  return submit_batch(d, streams, sizes, n, min_intervals, false);
+  if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  return with_device_markers(d, n, [&](bool markers) { return submit_batch(d, streams, sizes, n, min_intervals, false, markers); });
 } catch (...) { return boundary_catch(d, "mijpeg_decode_batch_device"); }
 
-int mijpeg_prepare_batch_host(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n)
-try {
-  if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+static int prepare_batch_host(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, bool markers)
+{
   if (const int prc = settle_pending(d)) return prc;
   d->batch_frames = 0;
   if (d->batch_hosts.size() < (size_t)n) d->batch_hosts.resize((size_t)n); // never shrinks: a pipeline's chunks differ in size, and
@@ -928,18 +976,65 @@ try {
   const int workers = std::min(n, default_threads());
   parallel_for(workers, [&](int w) {
     for (int i = w; i < n; i += workers) {
-      d->batch_hosts[(size_t)i]->set_unstuff_sink(stage + slot[(size_t)i], sizes[i]);
-      rcs[(size_t)i] = d->batch_hosts[(size_t)i]->parse(streams[i], sizes[i], false);
+      HostDecoder &h = *d->batch_hosts[(size_t)i];
+      if (markers) h.set_skip_search(); // (the host half of the marker route: headers, and one memcpy of the raw segment)
+      else h.set_unstuff_sink(stage + slot[(size_t)i], sizes[i]);
+      rcs[(size_t)i] = h.parse(streams[i], sizes[i], false);
+      if (markers && !rcs[(size_t)i] && !h.scans.empty() && h.scans[0].search_skipped)
+        memcpy(stage + slot[(size_t)i], streams[i] + h.scans[0].ecs_begin, sizes[i] - h.scans[0].ecs_begin);
     }
   });
   for (int i = 0; i < n; i++)
     if (rcs[(size_t)i]) return set_error(d, rcs[(size_t)i], d->batch_hosts[(size_t)i]->error.message);
+  for (int i = 0; i < n && markers; i++)
+    if (const char *why = device_markers_obstacle(*d->batch_hosts[(size_t)i], sizes[i])) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
+  for (int i = 0; i < n && markers; i++) d->markers_staged.emplace_back(slot[(size_t)i], sizes[i] - d->batch_hosts[(size_t)i]->scans[0].ecs_begin);
   return MIJPEG_OK;
+}
+
+int mijpeg_prepare_batch_host(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n)
+try {
+  if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  return with_device_markers(d, n, [&](bool markers) { return prepare_batch_host(d, streams, sizes, n, markers); });
 } catch (...) { return boundary_catch(d, "mijpeg_prepare_batch_host"); }
+
+int mijpeg_set_device_markers(mijpeg_decoder *d, int on)
+try {
+  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (on != 0 && on != 1) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "mijpeg_set_device_markers: on must be 0 or 1");
+  d->device_markers = on;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_set_device_markers"); }
+
+int mijpeg_device_markers_stats(mijpeg_decoder *d, int64_t *searched, int64_t *declined)
+try {
+  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (searched) *searched = d->markers_searched;
+  if (declined) *declined = d->markers_declined;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_device_markers_stats"); }
+
+const uint8_t *mijpeg_device_markers_staging(mijpeg_decoder *d, int image, size_t *bytes)
+{
+  if (!d || image < 0 || (size_t)image >= d->markers_staged.size()) return nullptr;
+  const uint8_t *stage = d->device >= 0 ? d->stage_host : d->host_stage.data();
+  if (!stage) return nullptr;
+  if (bytes) *bytes = d->markers_staged[(size_t)image].second;
+  return stage + d->markers_staged[(size_t)image].first;
+}
+
+int64_t mijpeg_device_marker_search(mijpeg_decoder *d, const uint8_t *segment, size_t size, int32_t expect, uint8_t *dst, size_t capacity,
+                                    uint32_t *begin, uint32_t *end, uint32_t *term, uint32_t *flags)
+try {
+  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (expect > (1 << 26)) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "mijpeg_device_marker_search: expect");
+  return device_marker_search(d, segment, size, expect, dst, capacity, begin, end, term, flags);
+} catch (...) { return boundary_catch(d, "mijpeg_device_marker_search"); }
 
 int mijpeg_submit_batch_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals)
 try {
-  return submit_batch(d, streams, sizes, n, min_intervals, true);
+  if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  return with_device_markers(d, n, [&](bool markers) { return submit_batch(d, streams, sizes, n, min_intervals, true, markers); });
 } catch (...) { return boundary_catch(d, "mijpeg_submit_batch_device"); }
 
 int mijpeg_synchronize(mijpeg_decoder *d)

@@ -94,6 +94,15 @@ struct mijpeg_decoder {
   const uint32_t *pend_walk_flags = nullptr;     // "something changed" per round (pinned)
   const uint32_t *pend_walk_status = nullptr;    // per image (pinned)
   std::chrono::steady_clock::time_point pend_t0;
+  // mijpeg_set_device_markers: the restart marker search and the unstuffing of qualifying batches run on the device (markers.hip).
+  // markers_retry: the marker route declined inside a synchronous call, which then runs the host route; pend_markers: the
+  // result words (flags, term, total, markers per image, pinned) of a submitted batch, markers_want_term the `term` of a good one
+  int device_markers = 0;
+  int64_t markers_searched = 0, markers_declined = 0; // images
+  bool markers_retry = false;
+  const uint32_t *pend_markers = nullptr;
+  std::vector<uint32_t> markers_want_term;
+  std::vector<std::pair<size_t, size_t>> markers_staged; // the last call that took the marker route: slot offset and raw bytes per image
   // batches whose images bring different quantisation tables: [frames][4][64] deltas per component, on the device
   uint16_t *batch_quant_dev = nullptr;
   size_t batch_quant_cap = 0;
@@ -228,7 +237,14 @@ const char *multiscan_obstacle(const mij::HostDecoder &h, bool xt_part, bool res
 size_t stream_slots(const size_t *sizes, int n, std::vector<size_t> &stream_off);
 int device_entropy_batch(mijpeg_decoder *d, mij::HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
                          int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part = false, bool defer = false,
-                         const RaggedEntropy *ragged = nullptr);
+                         const RaggedEntropy *ragged = nullptr, bool markers = false);
+// the marker route: why a stream parsed with HostDecoder::set_skip_search stays on the host route (nullptr: it qualifies); what
+// the result words of n images say (true: every search is good)
+const char *device_markers_obstacle(const mij::HostDecoder &h, size_t size);
+bool device_markers_good(const uint32_t *results, const uint32_t *want_term, int n);
+// mijpeg_device_marker_search's body (include/mijpeg.h)
+int64_t device_marker_search(mijpeg_decoder *d, const uint8_t *segment, size_t size, int32_t expect, uint8_t *dst, size_t capacity,
+                             uint32_t *begin, uint32_t *end, uint32_t *term, uint32_t *flags);
 int device_entropy_multiscan(mijpeg_decoder *d, const MultiScanFrame *frames, int nframes, int min_intervals);
 int evaluate_entropy_status(mijpeg_decoder *d, mij::HostDecoder *const *hosts, int n, const uint32_t *status_host);
 int walk_rounds_needed(const uint32_t *changed, int rounds);

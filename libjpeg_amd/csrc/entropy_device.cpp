@@ -8,6 +8,7 @@
 #include "decoder.hpp"
 #include "huffman_dev.hpp"
 #include "kernels.hpp"
+#include "markers.hpp"
 
 using namespace mij;
 
@@ -82,6 +83,32 @@ const char *ragged_entropy_obstacle(const HostDecoder &h, size_t size)
   for (int k = 0; k < s.ncomp; k++)
     if (s.sc[k].comp != k) return "the scan lists its components out of frame order";
   return nullptr;
+}
+
+// The marker route (mijpeg_set_device_markers, markers.hip): what keeps one stream, parsed with HostDecoder::set_skip_search, on the
+// host route.  What the parse itself asks for -- a plain 8-bit Huffman sequential frame, one scan over all components, DRI > 0,
+// FF D9 as the last two bytes -- shows in Scan::search_skipped.
+const char *device_markers_obstacle(const HostDecoder &h, size_t size)
+{
+  if (const char *why = device_entropy_obstacle(h, size, false)) return why;
+  const Scan &s = h.scans[0];
+  if (!s.search_skipped) return "device marker search: not a plain 8-bit sequential stream with restart markers that ends in EOI";
+  if (h.info.xt || h.is_xt() || h.info.dnl || h.info.precision != 8) return "device marker search: plain 8-bit frames only";
+  if (s.restart_interval <= 0 || size < s.ecs_begin + 2) return "device marker search: streams with restart markers only";
+  if (size - s.ecs_begin >= MARKERS_MAX_SEGMENT) return "entropy coded segment too large for the device decoder's bit addresses";
+  const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
+  if ((total_mcus + s.restart_interval - 1) / s.restart_interval > 0x7fffffff) return "too many restart intervals";
+  return nullptr;
+}
+
+// Good: no flag, and the segment ends at the FF of the EOI the stream closes with
+bool device_markers_good(const uint32_t *results, const uint32_t *want_term, int n)
+{
+  for (int i = 0; i < n; i++) {
+    const MarkerResult &r = ((const MarkerResult *)results)[i];
+    if (r.flags != 0 || r.term != want_term[i]) return false;
+  }
+  return true;
 }
 
 namespace { // steps the sequential, progressive and walk paths share
@@ -472,8 +499,12 @@ static void build_dev_table(HuffDevTable &dst, const HuffTable &src, int mode)
 // image; a damaged image is reported in ragged->verdict[i] instead of failing the call.
 // hosts[i]->info receives fast_arith / range_max.  Returns MIJPEG_OK, MIJPEG_ERR_NOT_AVAILABLE (nothing touched) or an error.
 int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
-                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part, bool defer, const RaggedEntropy *ragged)
+                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part, bool defer, const RaggedEntropy *ragged, bool markers)
 {
+  // `markers`: the streams were parsed without a marker search (device_markers_obstacle holds for each): their raw segments go up,
+  // and the search kernels write the copies and the interval tables in front of the Huffman launch.  On a search that is not
+  // good the call answers MIJPEG_ERR_NOT_AVAILABLE with d->markers_retry set (deferred: mijpeg_finish_batch_device looks).
+  if (markers && (ragged || xt_part)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: uniform batches of plain streams only");
   const mijpeg_info &f0 = hosts[0]->info;
   const Scan &s0 = hosts[0]->scans[0];
   int64_t total_intervals = 0;
@@ -485,7 +516,7 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   const bool device_walk = !(getenv("MIJPEG_DEVICE_WALK") && atoi(getenv("MIJPEG_DEVICE_WALK")) == 0);
   const auto tb0 = std::chrono::steady_clock::now();
   for (int i = 0; i < n; i++) {
-    const char *why = device_entropy_obstacle(*hosts[i], sizes[i], xt_part);
+    const char *why = markers ? device_markers_obstacle(*hosts[i], sizes[i]) : device_entropy_obstacle(*hosts[i], sizes[i], xt_part);
     if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
     const mijpeg_info &f = hosts[i]->info;
     const Scan &s = hosts[i]->scans[0];
@@ -503,7 +534,8 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
     int64_t nint;
     if (s.restart_interval > 0) {
       nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
-      if (const char *bad = restart_markers_obstacle(*hosts[i])) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, bad);
+      if (!markers)
+        if (const char *bad = restart_markers_obstacle(*hosts[i])) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, bad);
     } else if (ragged && (total_mcus < 256 || s.ecs_end - s.ecs_begin < 4096)) {
       // too small for the walk: one interval, one lane -- every MCU of the image in sequence, as a host thread would
       single[(size_t)i] = 1;
@@ -579,10 +611,12 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   const size_t stream_bytes = stream_slots(sizes, n, stream_off);
   int64_t n_groups = 0;
   for (int i = 0; i < n; i++) {
-    usize[(size_t)i] = hosts[i]->scans[0].unstuffed_size;
+    // (the marker route: the raw segment, terminator included -- the copy is no longer)
+    usize[(size_t)i] = markers ? sizes[i] - hosts[i]->scans[0].ecs_begin : hosts[i]->scans[0].unstuffed_size;
     int why_code;
-    if (const char *why = stream_copy_obstacle(*hosts[i], sizes[i], &why_code)) return set_error(d, why_code, why);
-    if (!dwalk[(size_t)i] && !virt[(size_t)i] && !single[(size_t)i] && (int64_t)hosts[i]->scans[0].interval_ubegin.size() < nints[(size_t)i])
+    if (!markers)
+      if (const char *why = stream_copy_obstacle(*hosts[i], sizes[i], &why_code)) return set_error(d, why_code, why);
+    if (!markers && !dwalk[(size_t)i] && !virt[(size_t)i] && !single[(size_t)i] && (int64_t)hosts[i]->scans[0].interval_ubegin.size() < nints[(size_t)i])
       return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart intervals missing");
     n_groups += (nints[(size_t)i] + per_group - 1) / per_group;
   }
@@ -598,9 +632,21 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   const size_t off_ib = L.take(T * 4), off_ie = L.take(T * 4), off_isk = L.take(any_virtual ? T : 0), off_ipr = L.take(any_virtual ? T * 8 : 0);
   const size_t off_tab = L.take((size_t)n * table_blob), off_img = L.take((size_t)n * sizeof(HuffImage)), off_grp = L.take((size_t)n_groups * sizeof(HuffGroup));
   const size_t off_planes = L.take(ragged ? (size_t)n * sizeof(HuffPlanes) : 0);
+  // the marker route: descriptors of the search (images, chunks) and, right in front of the status words and read back with
+  // them, its result words; behind the status words and on the device only its scratch and the raw segments (slots as in front)
+  uint32_t marker_chunks = 0;
+  for (int i = 0; markers && i < n; i++) marker_chunks += markers_chunks(usize[(size_t)i]);
+  const size_t off_mimg = L.take(markers ? (size_t)n * sizeof(MarkerImage) : 0), off_mchunk = L.take(markers ? (size_t)marker_chunks * sizeof(MarkerChunk) : 0);
+  const size_t off_mres = L.take(markers ? (size_t)n * sizeof(MarkerResult) : 0);
   const size_t status_bytes = (size_t)n * 32, off_status = L.take(status_bytes);
-  int rc = ensure_entropy_buffers(d, stream_bytes, L.end);
+  static_assert(sizeof(MarkerResult) == 16, "the result words end where the status words begin");
+  const size_t tail_bytes = L.end;
+  const MarkerScratch mscratch = markers_scratch(marker_chunks);
+  const size_t off_mscratch = L.take(markers ? mscratch.end : 0), off_raw = L.take(markers ? stream_bytes : 0);
+  int rc = markers ? ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, stream_bytes + L.end) : ensure_entropy_buffers(d, stream_bytes, tail_bytes);
+  if (!rc && markers) rc = ensure_pinned(d, &d->ent_host, &d->ent_host_cap, tail_bytes);
   if (rc) return rc;
+  if (markers && stream_bytes + L.end > 0xfffffff0ull) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "batch too large for one launch");
   uint8_t *const hp = d->ent_host, *const dp = d->ent_dev + stream_bytes;
   uint32_t *ib = (uint32_t *)(hp + off_ib), *ie = (uint32_t *)(hp + off_ie);
   HuffImage *images = (HuffImage *)(hp + off_img);
@@ -637,6 +683,26 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
         isk[first + k] = vi.bit_skip[(size_t)k];
         memcpy(ipr + (first + k) * 4, &vi.pred[(size_t)k * 4], 8);
       }
+    } else if (markers) {
+      // written by the search kernels; entries they leave alone (a search that is not good) must not send the Huffman kernel anywhere
+      memset(ib + first, 0, (size_t)nint * 4);
+      memset(ie + first, 0, (size_t)nint * 4);
+      MarkerImage &mi = ((MarkerImage *)(hp + off_mimg))[i];
+      MarkerResult &mr = ((MarkerResult *)(hp + off_mres))[i];
+      uint32_t chunk_at = i ? ((MarkerImage *)(hp + off_mimg))[i - 1].first_chunk + ((MarkerImage *)(hp + off_mimg))[i - 1].n_chunks : 0;
+      mi.raw_off = (uint32_t)stream_off[(size_t)i];
+      mi.size = (uint32_t)usize[(size_t)i];
+      mi.dst_off = (uint32_t)stream_off[(size_t)i];
+      mi.dst_cap = (uint32_t)((i + 1 < n ? stream_off[(size_t)i + 1] : stream_bytes) - stream_off[(size_t)i]);
+      mi.first_interval = (uint32_t)first;
+      mi.expect = (uint32_t)nint;
+      mi.first_chunk = chunk_at;
+      mi.n_chunks = markers_chunks(usize[(size_t)i]);
+      MarkerChunk *mc = (MarkerChunk *)(hp + off_mchunk) + chunk_at;
+      for (uint32_t k = 0; k < mi.n_chunks; k++) mc[k] = MarkerChunk{(uint32_t)i, k};
+      mr.flags = 0;
+      mr.term = mi.size;
+      mr.total = mr.markers = 0;
     } else if (single[(size_t)i]) {
       ib[first] = 0;
       ie[first] = (uint32_t)usize[(size_t)i];
@@ -729,6 +795,32 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   a.coef = coef_dev;
   a.status = (uint32_t *)(dp + off_status);
   a.planes = ragged ? (const HuffPlanes *)(dp + off_planes) : nullptr;
+  MarkerArgs ma;
+  memset(&ma, 0, sizeof(ma));
+  if (markers) {
+    uint8_t *const ms = dp + off_mscratch;
+    ma.raw = dp + off_raw;
+    ma.dst = d->ent_dev;
+    ma.ibegin = (uint32_t *)(dp + off_ib);
+    ma.iend = (uint32_t *)(dp + off_ie);
+    ma.images = (const MarkerImage *)(dp + off_mimg);
+    ma.chunks = (const MarkerChunk *)(dp + off_mchunk);
+    ma.kept = (uint32_t *)(ms + mscratch.kept);
+    ma.marks = (uint32_t *)(ms + mscratch.marks);
+    ma.kept_at = (const uint64_t *)(ms + mscratch.kept_at);
+    ma.marks_at = (const uint64_t *)(ms + mscratch.marks_at);
+    ma.results = (MarkerResult *)(dp + off_mres);
+  }
+  // the search of images [g0, g1) on the object's stream, behind their upload
+  auto search_images = [&](int g0, int g1) -> int {
+    const MarkerImage *mi = (const MarkerImage *)(hp + off_mimg);
+    MarkerArgs part = ma;
+    part.chunk0 = mi[g0].first_chunk;
+    part.n_chunks = mi[g1 - 1].first_chunk + mi[g1 - 1].n_chunks - part.chunk0;
+    if (launch_marker_search(part, (uint64_t *)(dp + off_mscratch + mscratch.scan), mscratch.scan_words, d->stream))
+      return hip_fail(d, hipGetLastError(), "marker search launch");
+    return MIJPEG_OK;
+  };
   const TraceMarks mark{"mijpeg"};
   const auto tb1 = mark.t0;
   QuiesceOnError guard{d};
@@ -743,6 +835,12 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   // batch's workers do, set_unstuff_sink -- have nothing left to do)
   Gather gather;
   auto gather_images = [&](int g0, int g1) {
+    if (markers) { // one memcpy per image: the raw segment into its slot
+      auto copy = [&](int i) { memcpy(d->stage_host + stream_off[(size_t)i], datas[i] + hosts[i]->scans[0].ecs_begin, usize[(size_t)i]); };
+      if (g1 - g0 > 1) parallel_for(g1 - g0, [&](int k) { copy(g0 + k); });
+      else copy(g0);
+      return;
+    }
     for (int i = g0; i < g1; i++)
       if (hosts[i]->scans[0].unstuffed_at != d->stage_host + stream_off[(size_t)i]) gather.add(hosts[i], 0, d->stage_host + stream_off[(size_t)i]);
     gather.run();
@@ -761,9 +859,13 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   if (small) {
     gather_images(0, n);
     // (only what the copies occupy: a slot is as large as its stream, headers and all)
-    for (int i = 0; i < n; i++)
+    for (int i = 0; i < n && !markers; i++)
       HIP_TRY(d, hipMemcpyAsync(d->ent_dev + stream_off[(size_t)i], d->stage_host + stream_off[(size_t)i], ((usize[(size_t)i] + 15) & ~(size_t)15) + HUFF_STREAM_PAD,
                                 hipMemcpyHostToDevice, d->stream));
+    for (int i = 0; i < n && markers; i++)
+      if (usize[(size_t)i])
+        HIP_TRY(d, hipMemcpyAsync(dp + off_raw + stream_off[(size_t)i], d->stage_host + stream_off[(size_t)i], usize[(size_t)i], hipMemcpyHostToDevice, d->stream));
+    if (markers && (rc = search_images(0, n))) return rc;
     if (any_dwalk) {
       if ((rc = walk_and_decode())) return rc;
     } else {
@@ -786,9 +888,10 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
       const int g1 = std::min(n, g0 + groups_of);
       gather_images(g0, g1);
       const size_t b0 = stream_off[(size_t)g0], b1 = g1 < n ? stream_off[(size_t)g1] : stream_bytes;
-      HIP_TRY(d, hipMemcpyAsync(d->ent_dev + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
+      HIP_TRY(d, hipMemcpyAsync((markers ? dp + off_raw : d->ent_dev) + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
       HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)gi], d->copy_stream));
       HIP_TRY(d, hipStreamWaitEvent(d->stream, d->copy_events[(size_t)gi], 0));
+      if (markers && (rc = search_images(g0, g1))) return rc;
       if (any_dwalk || ragged) continue; // the walk below covers all images at once; a ragged group is one launch by contract
       int64_t wg1 = wg0;
       for (int i = g0; i < g1; i++) wg1 += (nints[(size_t)i] + per_group - 1) / per_group;
@@ -809,7 +912,13 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
   uint32_t *status_host = (uint32_t *)(hp + off_status);
   uint32_t *walk_status_host = (uint32_t *)d->walk_host; // the walk's staging buffer is free again
   if (any_dwalk) HIP_TRY(d, hipMemcpyAsync(walk_status_host, d->walk_status_dev, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
-  if ((rc = read_back_status(d, status_host, dp + off_status, status_bytes))) return rc;
+  // (the marker route's result words lie right in front of the status words: one copy)
+  if ((rc = read_back_status(d, (uint32_t *)(hp + off_mres), dp + off_mres, off_status - off_mres + status_bytes))) return rc;
+  d->pend_markers = nullptr;
+  if (markers) {
+    d->markers_want_term.resize((size_t)n);
+    for (int i = 0; i < n; i++) d->markers_want_term[(size_t)i] = (uint32_t)usize[(size_t)i] - 2u;
+  }
   d->phase_prepare = std::chrono::duration<double>(tb1 - tb0).count(); // interval tables, Huffman tables
   mark("status copies enqueued");
   if (!any_dwalk) d->pend_walk_round = 0;
@@ -818,6 +927,7 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
     d->pend_n = n;
     d->pend_status = status_host;
     d->pend_walk_status = any_dwalk ? walk_status_host : nullptr;
+    d->pend_markers = markers ? (const uint32_t *)(hp + off_mres) : nullptr;
     d->pend_t0 = tb1;
     d->phase_device = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count(); // so far: gathering + enqueueing
     return MIJPEG_OK;
@@ -833,6 +943,13 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
       ragged->verdict[i] = bad ? 1 : 0;
     }
     return MIJPEG_OK;
+  }
+  if (markers) {
+    if (!device_markers_good((const uint32_t *)(hp + off_mres), d->markers_want_term.data(), n)) {
+      d->markers_retry = true;
+      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: the segment is not the plain case; the host searches it");
+    }
+    for (int i = 0; i < n; i++) hosts[i]->scans[0].unstuffed_size = ((const MarkerResult *)(hp + off_mres))[i].total;
   }
   if (any_dwalk && (rc = walk_verdict(d, walk_status_host, n))) return rc;
   return evaluate_entropy_status(d, hosts, n, status_host);
@@ -1145,4 +1262,89 @@ int device_entropy_multiscan(mijpeg_decoder *d, const MultiScanFrame *frames, in
   std::vector<HostDecoder *> hosts((size_t)nframes);
   for (int fi = 0; fi < nframes; fi++) hosts[(size_t)fi] = frames[fi].h;
   return evaluate_entropy_status(d, hosts.data(), nframes, status_host);
+}
+
+// ------------------------------------------------------------------------------------------------
+// mijpeg_device_marker_search: the search kernels on one segment of the caller's, with guard bytes around the device copies of
+// everything they write
+// ------------------------------------------------------------------------------------------------
+int64_t device_marker_search(mijpeg_decoder *d, const uint8_t *segment, size_t size, int32_t expect, uint8_t *dst, size_t capacity,
+                             uint32_t *begin, uint32_t *end, uint32_t *term, uint32_t *flags)
+{
+  if ((!segment && size) || expect < 1 || (!dst && capacity) || !term || !flags) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "mijpeg_device_marker_search: arguments");
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  if (size >= MARKERS_MAX_SEGMENT || capacity >= ((size_t)1 << 30))
+    return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "entropy coded segment too large for the device decoder's bit addresses");
+  if (capacity < size) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "mijpeg_device_marker_search: the destination needs the segment's size");
+  HIP_TRY(d, hipSetDevice(d->device));
+  if (const int prc = settle_pending(d)) return prc;
+  quiesce(d); // (the entropy buffers change hands)
+  constexpr size_t GUARD = 64;
+  constexpr uint8_t PATTERN = 0xa5;
+  const uint32_t C = markers_chunks(size);
+  const size_t E = (size_t)expect;
+  // [raw][guard dst guard begin guard end guard][image, chunks, result] go up, everything from the first guard on comes back
+  Layout L;
+  const size_t o_raw = L.take(size), o_g0 = L.take(GUARD), o_dst = L.take(capacity), o_g1 = L.take(GUARD), o_begin = L.take(E * 4), o_g2 = L.take(GUARD);
+  const size_t o_end = L.take(E * 4), o_g3 = L.take(GUARD), o_img = L.take(sizeof(MarkerImage)), o_chunk = L.take((size_t)C * sizeof(MarkerChunk));
+  const size_t o_res = L.take(sizeof(MarkerResult)), o_up_end = L.end;
+  const MarkerScratch ms = markers_scratch(C);
+  const size_t o_scratch = L.take(ms.end);
+  int rc = ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, L.end);
+  if (!rc) rc = ensure_pinned(d, &d->ent_host, &d->ent_host_cap, o_up_end);
+  if (rc) return rc;
+  uint8_t *const hp = d->ent_host, *const dp = d->ent_dev;
+  memset(hp, PATTERN, o_up_end); // (the regions the kernels write start out as the pattern too: what they leave alone shows)
+  if (size) memcpy(hp + o_raw, segment, size);
+  MarkerImage &im = *(MarkerImage *)(hp + o_img);
+  im.raw_off = (uint32_t)o_raw;
+  im.size = (uint32_t)size;
+  im.dst_off = (uint32_t)o_dst;
+  im.dst_cap = (uint32_t)capacity;
+  im.first_interval = 0;
+  im.expect = (uint32_t)expect;
+  im.first_chunk = 0;
+  im.n_chunks = C;
+  for (uint32_t k = 0; k < C; k++) ((MarkerChunk *)(hp + o_chunk))[k] = MarkerChunk{0, k};
+  MarkerResult &res = *(MarkerResult *)(hp + o_res);
+  res.flags = 0;
+  res.term = (uint32_t)size;
+  res.total = res.markers = 0;
+  MarkerArgs a;
+  memset(&a, 0, sizeof(a));
+  a.raw = dp;
+  a.dst = dp;
+  a.ibegin = (uint32_t *)(dp + o_begin);
+  a.iend = (uint32_t *)(dp + o_end);
+  a.images = (const MarkerImage *)(dp + o_img);
+  a.chunks = (const MarkerChunk *)(dp + o_chunk);
+  a.chunk0 = 0;
+  a.n_chunks = C;
+  a.kept = (uint32_t *)(dp + o_scratch + ms.kept);
+  a.marks = (uint32_t *)(dp + o_scratch + ms.marks);
+  a.kept_at = (const uint64_t *)(dp + o_scratch + ms.kept_at);
+  a.marks_at = (const uint64_t *)(dp + o_scratch + ms.marks_at);
+  a.results = (MarkerResult *)(dp + o_res);
+  QuiesceOnError guard{d};
+  guard.armed = true;
+  HIP_TRY(d, hipMemcpyAsync(dp, hp, o_up_end, hipMemcpyHostToDevice, d->stream));
+  if (launch_marker_search(a, (uint64_t *)(dp + o_scratch + ms.scan), ms.scan_words, d->stream)) return hip_fail(d, hipGetLastError(), "marker search launch");
+  HIP_TRY(d, hipMemcpyAsync(hp + o_g0, dp + o_g0, o_up_end - o_g0, hipMemcpyDeviceToHost, d->stream));
+  HIP_TRY(d, hipStreamSynchronize(d->stream));
+  guard.armed = false;
+  const size_t guards[4] = {o_g0, o_g1, o_g2, o_g3};
+  for (size_t g : guards)
+    for (size_t k = 0; k < GUARD; k++)
+      if (hp[g + k] != PATTERN) return set_error(d, MIJPEG_ERR_PHASE_ERROR, "device marker search: bytes outside the buffers handed in were written");
+  // (the pads between a region's last byte and the next 16-byte boundary belong to the guards)
+  const size_t region_end[3] = {o_dst + capacity, o_begin + E * 4, o_end + E * 4}, next[3] = {o_g1, o_g2, o_g3};
+  for (int r = 0; r < 3; r++)
+    for (size_t k = region_end[r]; k < next[r]; k++)
+      if (hp[k] != PATTERN) return set_error(d, MIJPEG_ERR_PHASE_ERROR, "device marker search: bytes outside the buffers handed in were written");
+  if (capacity) memcpy(dst, hp + o_dst, capacity);
+  if (begin) memcpy(begin, hp + o_begin, E * 4);
+  if (end) memcpy(end, hp + o_end, E * 4);
+  *term = res.term;
+  *flags = res.flags;
+  return (int64_t)res.total;
 }

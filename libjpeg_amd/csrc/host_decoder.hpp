@@ -76,6 +76,9 @@ struct Scan {
   bool progressive_run = false; // EOB runs are legal (m_bProgressive)
   bool residual = false;        // the residual scan type of part 8 (SequentialScan(.., true, true), marker/scan.cpp:483-489)
   int lowbit = 0;               // point transform incl. hidden bits
+  // The restart marker search was left to the device (HostDecoder::set_skip_search): ecs_end is where the closing EOI stands,
+  // the interval lists are empty and unstuffed_size is unknown.  Only device_entropy_batch's marker route reads such a scan.
+  bool search_skipped = false;
 };
 
 struct StreamError {
@@ -158,6 +161,10 @@ public:
   // it walks the segment -- one pass over the stream instead of two.  `capacity` bytes at dst (the stream's size is enough).
   // Scan::unstuffed_at tells whether it did (it does not when the search runs in parallel chunks).
   void set_unstuff_sink(uint8_t *dst, size_t capacity) { sink_ = dst; sink_cap_ = capacity; }
+  // The device searches the restart markers (markers.hip): the NEXT parse() does not search the one scan of a plain 8-bit Huffman
+  // sequential frame with DRI > 0 whose stream ends in FF D9 -- it takes the FF of that EOI for the end of the segment and walks on
+  // from there.  Scan::search_skipped tells whether it did; every other stream is parsed as always.
+  void set_skip_search() { skip_search_ = true; }
   void unstuff_pieces(size_t scan, size_t piece_bytes, std::vector<UnstuffPiece> &out) const;
   void unstuff_piece(size_t scan, const UnstuffPiece &p, uint8_t *dst) const;
 
@@ -237,6 +244,7 @@ private:
   size_t sink_cap_ = 0;
   uint8_t *active_sink_ = nullptr; // ... which takes it over (and forgets it whatever becomes of the parse)
   size_t active_cap_ = 0;
+  bool skip_search_ = false, active_skip_ = false; // set_skip_search: armed for the next parse() only, like the sink
   bool needs_sequential_ = false;
   bool walked_ = false;
   std::vector<WalkedScan> walked_scans_;

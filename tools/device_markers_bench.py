@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Restart marker search and unstuffing on the device (mijpeg_set_device_markers) against the host's, option off
+and on alternating in one process, medians of --reps with [min .. max]:
+
+  --part a   mijpeg_prepare_batch_host -- the host half of a batch submit -- over 32 4K 4:2:0 Q85 DRI 8 streams with one worker
+             (MIJPEG_THREADS=1 unless the environment says otherwise), ms per stream.  Needs no GPU.
+  --part b   the pipeline (libjpeg_amd.batch.BatchShard, chunks of 32, two decoder objects) over 256 such streams, ms per batch,
+             with the worker pool the environment gives (MIJPEG_THREADS).
+  --part c   the option-on pipeline alone, a few times -- the run to put under a kernel-trace-only profiler for the search
+             launches' times (marker_count_kernel, marker_write_kernel, the scans between them).
+
+    python tools/device_markers_bench.py --part a|b|c [--reps 9] [--streams 32] [--batch 256] [--out FILE]   (--out appends)
+
+(d), bench.py on the parent build and on this one, is two runs of bench.py and not part of this script.
+"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+if "--part=a" in sys.argv or ("--part" in sys.argv[:-1] and sys.argv[sys.argv.index("--part") + 1] == "a"):  # (the pool is sized when the library loads)
+    os.environ.setdefault("MIJPEG_THREADS", "1")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from libjpeg_amd import api, batch, synth  # noqa: E402
+
+
+def med(xs):
+    return f"{statistics.median(xs):8.3f} [{min(xs):.3f} .. {max(xs):.3f}]"
+
+
+def alternate(fa, fb, reps):
+    a, b = [], []
+    fa(), fb()  # warm: buffers grown, pages touched
+    for _ in range(reps):
+        a.append(fa())
+        b.append(fb())
+    return a, b
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--streams", type=int, default=32)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--part", required=True, choices=["a", "b", "c"])
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    distinct = [synth.synth_jpeg(3840, 2160, 500 + i, 85, "420", 8) for i in range(4)]
+    streams = [distinct[i % 4] for i in range(args.streams)]
+    say(f"streams: 4K 4:2:0 Q85 DRI 8, {sum(map(len, streams)) / len(streams) / 1e6:.2f} MB each; MIJPEG_THREADS={os.environ.get('MIJPEG_THREADS', 'unset')}, "
+        f"{api.lib().mijpeg_default_threads()} workers")
+
+    if args.part == "a":
+        off, on = api.Decoder(None), api.Decoder(None)
+        on.set_device_markers(1)
+
+        def host_half(d):
+            def run():
+                t0 = time.perf_counter()
+                d.prepare_batch_host(streams)
+                return (time.perf_counter() - t0) * 1e3 / len(streams)
+            return run
+
+        a, b = alternate(host_half(off), host_half(on), args.reps)
+        assert on.device_markers_stats()[1] == 0, "the option-on half declined"
+        say(f"(a) mijpeg_prepare_batch_host over {args.streams} streams, ms per stream")
+        say(f"    option off  {med(a)}")
+        say(f"    option on   {med(b)}")
+        off.close()
+        on.close()
+        return finish(args, lines)
+
+    import torch
+
+    many = [distinct[i % 4] for i in range(args.batch)]
+
+    def pipeline(shard):
+        def run():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            shard.run()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+        return run
+
+    s_on = batch.BatchShard(many, 0, chunk=32, depth=2, device_markers=True)
+    if args.part == "c":
+        for _ in range(3):
+            pipeline(s_on)()
+        assert s_on.fallbacks == 0
+        s_on.close()
+        return 0
+    s_off = batch.BatchShard(many, 0, chunk=32, depth=2)
+    a, b = alternate(pipeline(s_off), pipeline(s_on), args.reps)
+    assert s_on.fallbacks == 0 and sum(d.device_markers_stats()[1] for d in s_on.decoders) == 0, "the option-on pipeline declined"
+    assert bool((s_off.out == s_on.out).all()), "pixels differ"
+    say(f"(b) pipeline over {args.batch} streams (chunks of 32, two decoder objects), ms per batch")
+    say(f"    option off  {med(a)}")
+    say(f"    option on   {med(b)}")
+    s_off.close()
+    s_on.close()
+    return finish(args, lines)
+
+
+def finish(args, lines):
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
