@@ -289,9 +289,13 @@ def uses(dc: Table, ac: Table):
 CONTENTS = ("sparse", "boundaries", "runs", "dc_extremes")
 
 
-def content(kind: str, shapes, precision: int, rng: np.random.Generator, dc_cats=None, ac_syms=None):
+def content(kind: str, shapes, precision: int, rng: np.random.Generator, dc_cats=None, ac_syms=None, **history):
     """One int32 plane (bh, bw, 64) per shape.  dc_cats / ac_syms: what the tables can code (None: everything); content is
-    shaped to stay inside it.  DC values stay inside int16 (the predictor with them)."""
+    shaped to stay inside it.  DC values stay inside int16 (the predictor with them).  kind "history" (not in CONTENTS: it is
+    made for a scan script) takes history_content's keywords."""
+    if kind == "history":
+        return history_content(shapes, precision, rng, dc_cats, ac_syms, **history)
+    assert not history
     dmax, amax = max_categories(precision)
     dc_cats = set(range(dmax + 1)) if dc_cats is None else dc_cats
     if ac_syms is not None:  # (no AC coefficient of a category the tables have no symbol for; amax only shapes `boundaries`)
@@ -349,6 +353,108 @@ def content(kind: str, shapes, precision: int, rng: np.random.Generator, dc_cats
     return planes
 
 
+HISTORY_PATTERNS = ("trailing", "empty", "all", "corners", "alternating", "run_new", "zrl", "zrl_long")
+
+
+def history_content(shapes, precision: int, rng: np.random.Generator, dc_cats=None, ac_syms=None, top_al: int = 1, extents=None,
+                    dc_outside: bool = True, phase: int = 0, patterns=HISTORY_PATTERNS):
+    """Blocks for the refinement scans of a script whose AC first passes have Al = top_al (>= 1).  For the scan at level a
+    (Ah = a + 1, Al = a) a coefficient is HISTORY when |v| >= 2 << a, NEW when |v| >> a == 1, and a free zero below that.
+    "History" here has |v| >= 2 << top_al: history in every refinement scan, with random correction bits at every level;
+    new(a) has |v| >> a == 1: a free zero above level a, coded at level a, history below it.  Block i of component c's own
+    blocks (extents, default: the whole plane; in scan order) takes pattern (i + phase + c) % 8, shaped by n = phase + i // 8:
+      trailing     new coefficients at positions 1.., history only behind the last one: the block ends in an EOB whose
+                   corrections wait for the run to be flushed -- and the next block
+      empty        (no AC coefficient) extends that run,
+      all          as do all 63 positions history, and
+      corners      positions 1, 31, 32, 33, 62 and 63: history (every third n), else history and new of one level alternating;
+      alternating  history and new coefficients alternating, the new ones spread over every level (and level top_al: magnitude
+                   one in the first pass), a free zero now and then;
+      run_new      12 + 3 (n % 13) history positions, then one new coefficient of every level top_al - 1 .. 0: the symbol of
+                   level a arrives with 12 + 3 (n % 13) + (top_al - 1 - a) correction bits, 12 .. 50 over 13 blocks;
+      zrl          16 free zeros with 1 + n % 16 history positions in between, then new coefficients as above: ZRL with corrections;
+      zrl_long     16 free zeros with 26 + n % 18 history positions in between: more correction bits behind the ZRL than a
+                   32-bit window holds behind its code.
+    Outside the extents the blocks carry a DC value only (none with dc_outside False, which may be given per component: the
+    script has a DC scan of the component alone).  dc_cats / ac_syms as in content(); the refinement symbols (run, 1), ZRL and EOB must be codable."""
+    assert top_al >= 1
+    dmax, amax = max_categories(precision)
+    if ac_syms is not None:
+        assert {0x00, 0xF0} | {(r << 4) | 1 for r in range(16)} <= set(ac_syms)
+        amax = min(amax, min(max(s & 15 for s in ac_syms if s >> 4 == r) for r in range(16)))
+    if dc_cats is not None:  # (DC differences of up to the largest category that comes with every smaller one)
+        dmax = min(dmax, next(c for c in range(17) if c + 1 not in dc_cats))
+    assert amax >= 3 and dmax >= 4 + top_al
+    extents = list(extents) if extents is not None else list(shapes)
+    big = (1 << amax) - 1
+    outside = [dc_outside] * len(shapes) if isinstance(dc_outside, bool) else list(dc_outside)
+
+    def sign():
+        return int(rng.choice([-1, 1]))
+
+    def hist():  # two or three bits in the first pass (now and then the widest category), random bits below
+        if rng.random() < 0.06:
+            return sign() * big
+        return sign() * ((int(rng.integers(2, 8)) << top_al) | int(rng.integers(0, 1 << top_al)))
+
+    def new(a):
+        return sign() * ((1 << a) | int(rng.integers(0, 1 << a)))
+
+    def news(z, k, first=None):  # one new coefficient of every level first .. 0 from position k on
+        for a in range(top_al - 1 if first is None else first, -1, -1):
+            if k <= 63:
+                z[k] = new(a)
+                k += 1
+
+    def spread(z, zeros, nh):  # `zeros` free positions with nh history positions among them, from position 1 on -> next position
+        order = np.zeros(zeros + nh, bool)
+        order[np.round(np.linspace(0, zeros + nh - 2, nh)).astype(int)] = True  # (the last position stays a zero)
+        assert order.sum() == nh
+        for i, h in enumerate(order):
+            if h:
+                z[1 + i] = hist()
+        return 1 + zeros + nh
+
+    planes = [np.zeros(s + (64,), np.int32) for s in shapes]
+    lim = min((1 << (dmax - 1)) - 1, (1 << (precision + 2)) - 1)
+    for ci, (p, (eh, ew), keep_dc) in enumerate(zip(planes, extents, outside)):
+        nb = p.shape[0] * p.shape[1]
+        dc = np.clip(np.cumsum(rng.integers(-lim // 4, lim // 4 + 1, nb)), -lim // 2, lim // 2).reshape(p.shape[:2])
+        p[:, :, 0] = dc
+        if not keep_dc:
+            p[eh:, :, 0] = 0
+            p[:, ew:, 0] = 0
+        for i in range(eh * ew):
+            z = np.zeros(64, np.int64)
+            kind, n = patterns[(i + phase + ci) % len(patterns)], phase + i // len(patterns)
+            if kind == "trailing":
+                news(z, 1)
+                for k in rng.choice(np.arange(top_al + 2, 64), 1 + n % 9, replace=False):
+                    z[k] = hist()
+            elif kind == "all":
+                z[1:] = [hist() for _ in range(63)]
+            elif kind == "corners":
+                a = n % top_al
+                for j, k in enumerate((1, 31, 32, 33, 62, 63)):
+                    z[k] = hist() if n % 3 == 0 or (j + n) % 2 else new(a)
+            elif kind == "alternating":
+                for k in range(1, 64):
+                    a = (k // 2 + n) % (top_al + 2)
+                    z[k] = hist() if k % 2 else 0 if a > top_al else new(a)
+            elif kind == "run_new":
+                nh = 12 + 3 * (n % 13)
+                z[1:1 + nh] = [hist() for _ in range(nh)]
+                news(z, 1 + nh)
+            elif kind == "zrl":
+                news(z, spread(z, 16, 1 + n % 16))
+            elif kind == "zrl_long":
+                news(z, spread(z, 16, 26 + n % 18), first=(n // 18) % top_al)
+            else:
+                assert kind == "empty", kind
+            p[i // ew, i % ew, ZZ[1:]] = z[1:]
+    return planes
+
+
 def saturating_block(plane: np.ndarray, quant: np.ndarray, precision: int = 12):
     """Fill the first block of `plane` so that sum |c| q passes 2^31 (the range check saturates): needs 16-bit deltas."""
     amax = (1 << max_categories(precision)[1]) - 1
@@ -401,6 +507,119 @@ def plane_shapes(width: int, height: int, samp):
     return [(my * v, mx * h) for h, v in samp]
 
 
+def scan_extents(width: int, height: int, samp):
+    """(blocks_h, blocks_w) a non-interleaved scan of every component covers: the component's own blocks (A.2.3), which is less
+    than plane_shapes' when the frame is not whole MCUs.  Interleaved scans cover the whole planes."""
+    hmax, vmax, _, _ = _layout(width, height, samp)
+    if len(samp) == 1:  # (one component: every scan is non-interleaved, the MCU is one block)
+        return [(-(-height // 8), -(-width // 8))]
+    return [(-(-(-(-height * v // vmax)) // 8), -(-(-(-width * h // hmax)) // 8)) for h, v in samp]
+
+
+class Trace:
+    """What the AC scans of a stream coded, as the writer saw it (write(trace=)): one record per scan.  tot: the bits of a code
+    and what belongs to it (the value bits of a first pass, the sign bit of a refinement scan's new coefficient, nothing for
+    ZRL); ncorr: the correction bits that follow it."""
+
+    def __init__(self):
+        self.scans = []
+
+    def begin(self, comps, ss, se, ah, al):
+        self.scans.append({"comps": tuple(comps), "ss": ss, "se": se, "ah": ah, "al": al,
+                           "symbols": [],      # tot + ncorr of every coded coefficient
+                           "zrl": [],          # (tot, ncorr) of every ZRL
+                           "trailing": [],     # correction bits behind the last symbol of every block that is not empty (refinement)
+                           "runs": [],         # (blocks, correction bits, empty blocks that joined it behind correction bits) of every EOB run
+                           "skipped": 0,       # blocks that a decoder meets inside an EOB run (skip > 0)
+                           "blocks": []})      # per block, in scan order: (symbols coded in it, trailing correction bits, inside a run)
+
+    def symbol(self, tot, ncorr):
+        self.scans[-1]["symbols"].append(tot + ncorr)
+
+    def zrl(self, tot, ncorr):
+        self.scans[-1]["zrl"].append((tot, ncorr))
+
+    def trailing(self, ncorr):
+        self.scans[-1]["trailing"].append(ncorr)
+
+    def done(self, symbols, ncorr):
+        self.scans[-1]["blocks"].append((symbols, ncorr, self._in_run))
+
+    def run(self, blocks, ncorr, empty_behind):
+        self.scans[-1]["runs"].append((blocks, ncorr, empty_behind))
+
+    def block(self, in_run):
+        self._in_run = bool(in_run)
+        self.scans[-1]["skipped"] += bool(in_run)
+
+
+def check_script(script, nc: int):
+    """T.81 G.1.1.1: DC scans have Ss = Se = 0, AC scans one component and 1 <= Ss <= Se <= 63; a first pass (Ah = 0) codes
+    coefficients no scan has coded, a refinement has Ah = the Al of the scan before it over the same coefficients and lowers
+    it by one; the DC first pass of a component comes before its AC scans.  In the end every coefficient is complete."""
+    al_of = [[None] * 64 for _ in range(nc)]
+    for comps, ss, se, ah, al in script:
+        assert len(set(comps)) == len(comps) >= 1 and all(0 <= c < nc for c in comps), comps
+        assert (ss == 0 and se == 0) or (1 <= ss <= se <= 63 and len(comps) == 1), (comps, ss, se)
+        assert 0 <= al <= 13 and 0 <= ah <= 13
+        for c in comps:
+            if ss:
+                assert al_of[c][0] is not None, "AC scan in front of the component's DC first pass"
+            for k in range(ss, se + 1):
+                if ah == 0:
+                    assert al_of[c][k] is None, (c, k, "coded twice")
+                else:
+                    assert al_of[c][k] == ah and al == ah - 1, (c, k, al_of[c][k], ah, al)
+                al_of[c][k] = al
+    assert all(a == 0 for c in al_of for a in c), "coefficients left incomplete"
+
+
+def scripts(nc: int):
+    """{name: (script, top_al)}: scan scripts aimed at the refinement pass and the level scheduler; top_al is the Al of the AC
+    first passes (what history_content shapes its magnitudes by).
+      deep     DC with Al = 3, every component's 1..63 with Al = 3, then DC and AC refinement 3 -> 2 -> 1 -> 0: at the last
+               level all 63 positions of a block can be history
+      split32  bands 1..31 and 32..63 (the device keeps the history in two 32-bit masks, split at position 32) with Al = 2, the
+               last component first; refined in the opposite order
+      split33  bands 1..32 and 33..63 with Al = 1; one DC scan per component, the last component first; a band's refinement
+               stands in front of first passes of other bands and components, so that the scans of one level of the device's
+               schedule are of different components AND kinds
+      single   bands 63..63, 1..1, 2..2 and 3..62 with Al = 2, refined 2 -> 1 -> 0 in another band order each time"""
+    every, rev = tuple(range(nc)), list(range(nc))[::-1]
+    deep = [(every, 0, 0, 0, 3)] + [((c,), 1, 63, 0, 3) for c in range(nc)]
+    for al in (2, 1, 0):
+        deep += [(every, 0, 0, al + 1, al)] + [((c,), 1, 63, al + 1, al) for c in range(nc)]
+    split32 = [(every, 0, 0, 0, 1)]
+    split32 += [((c,), ss, se, 0, 2) for c in rev for ss, se in ((1, 31), (32, 63))]
+    split32 += [((c,), ss, se, 2, 1) for c in range(nc) for ss, se in ((32, 63), (1, 31))] + [(every, 0, 0, 1, 0)]
+    split32 += [((c,), ss, se, 1, 0) for c in rev for ss, se in ((32, 63), (1, 31))]
+    lo, hi = (1, 32), (33, 63)
+    split33 = [((c,), 0, 0, 0, 1) for c in rev]
+    first_lo, refine_lo, first_hi = (lo, 0), (lo, 1), (hi, 0)
+    # the i-th AC scan of every component shares a level of the device's schedule: another kind for every component
+    turns = ([first_lo, refine_lo, first_hi], [first_hi, first_lo, refine_lo], [first_lo, first_hi, refine_lo])
+    for i in range(3):
+        for c in rev:
+            (ss, se), ah = turns[c % 3][i]
+            split33.append(((c,), ss, se, ah, 0 if ah else 1))
+    split33 += [((c,), 0, 0, 1, 0) for c in range(nc)]
+    split33 += [((c,), hi[0], hi[1], 1, 0) for c in rev]
+    single_bands = [(63, 63), (1, 1), (2, 2), (3, 62)]
+    single = [(every, 0, 0, 0, 0)] + [((c,), ss, se, 0, 2) for c in range(nc) for ss, se in single_bands]
+    single += [((c,), ss, se, 2, 1) for c in rev for ss, se in (single_bands[2], single_bands[0], single_bands[3], single_bands[1])]
+    single += [((c,), ss, se, 1, 0) for c in range(nc) for ss, se in (single_bands[3], single_bands[1], single_bands[0], single_bands[2])]
+    out = {"deep": (deep, 3), "split32": (split32, 2), "split33": (split33, 1), "single": (single, 2)}
+    for script, _ in out.values():
+        check_script(script, nc)
+    return out
+
+
+def own_dc_scans(script, nc: int):
+    """Per component: has the script a DC scan of the component alone (in a frame of more components)?  Then the blocks outside
+    the component's own ones can carry nothing at all."""
+    return [nc > 1 and any(ss == 0 and comps == (c,) for comps, ss, _, _, _ in script) for c in range(nc)]
+
+
 def _progressive_script(nc: int):
     """(components, Ss, Se, Ah, Al): DC first with Al = 1, AC first passes with and without point transform, DC and AC
     refinement.  Component 0's band 1..5 is coded at full precision in one pass (the widest categories live there)."""
@@ -412,21 +631,21 @@ def _progressive_script(nc: int):
 
 
 def write(planes, width: int, height: int, samp, tables, precision: int = 8, quant=None, dri: int = 0, progressive: bool = False,
-          quant16: bool = False, script=None, used: set | None = None) -> bytes:
+          quant16: bool = False, script=None, used: set | None = None, trace: "Trace | None" = None) -> bytes:
     """A stream that carries exactly `planes`.
 
     tables: per component (DC Table, AC Table); equal tables share one DHT slot.  quant: per component 64 deltas in natural
-    order (default: all ones).  quant16: Pq = 1 (16-bit entries; implies SOF1 unless progressive).  A progressive frame needs
-    a size of whole MCUs (its non-interleaved scans cover the component's own blocks only).  used: receives (id(table), symbol)
-    of every Huffman symbol written."""
+    order (default: all ones).  quant16: Pq = 1 (16-bit entries; implies SOF1 unless progressive).  The non-interleaved scans
+    of a progressive frame cover the component's own blocks only (scan_extents): outside them a plane may hold nothing such a
+    scan would have to carry (_scan asserts it; with an interleaved DC scan that leaves the DC values).  used: receives
+    (id(table), symbol) of every Huffman symbol written.  trace: receives what the AC scans coded (Trace)."""
     nc = len(samp)
     assert len(planes) == nc == len(tables)
     shapes = plane_shapes(width, height, samp)
     for p, s in zip(planes, shapes):
         assert p.shape == s + (64,), (p.shape, s)
     hmax, vmax, mx, my = _layout(width, height, samp)
-    if progressive:
-        assert width % (8 * hmax) == 0 and height % (8 * vmax) == 0, "progressive: whole MCUs"
+    extents = scan_extents(width, height, samp)
     quant = [np.ones(64, np.int64)] * nc if quant is None else [np.asarray(q, np.int64) for q in quant]
     qids, qtabs = [], []
     for q in quant:
@@ -467,15 +686,28 @@ def write(planes, width: int, height: int, samp, tables, precision: int = 8, qua
 
     if not progressive:
         out += sos(tuple(range(nc)), 0, 63, 0, 0)
-        out += _scan(planes, tables, samp, mx, my, tuple(range(nc)), 0, 63, 0, 0, dri, False, used)
+        out += _scan(planes, tables, samp, mx, my, tuple(range(nc)), 0, 63, 0, 0, dri, False, used, extents)
     else:
         for comps, ss, se, ah, al in (script or _progressive_script(nc)):
             out += sos(comps, ss, se, ah, al)
-            out += _scan(planes, tables, samp, mx, my, comps, ss, se, ah, al, dri, True, used)
+            if trace is not None:
+                trace.begin(comps, ss, se, ah, al)
+            out += _scan(planes, tables, samp, mx, my, comps, ss, se, ah, al, dri, True, used, extents, trace)
     return bytes(out) + b"\xff\xd9"
 
 
-def _scan(planes, tables, samp, mx, my, comps, ss, se, ah, al, dri, progressive, used=None) -> bytes:
+def _outside_is_empty(plane, ext, ss, se, ah, al) -> bool:
+    """Nothing for this scan in the blocks of `plane` outside the extent `ext`?"""
+    out = np.ones(plane.shape[:2], bool)
+    out[:ext[0], :ext[1]] = False
+    blk = plane[out]
+    if ss == 0:
+        dc = blk[:, 0] >> al
+        return not (dc.any() if ah == 0 else (dc & 1).any())
+    return not blk[:, ZZ[ss:se + 1]].any()
+
+
+def _scan(planes, tables, samp, mx, my, comps, ss, se, ah, al, dri, progressive, used=None, extents=None, trace=None) -> bytes:
     """Entropy coded data of one scan (restart markers included)."""
     bw = _Writer(used)
     interleaved = len(comps) > 1
@@ -485,14 +717,19 @@ def _scan(planes, tables, samp, mx, my, comps, ss, se, ah, al, dri, progressive,
     else:
         c = comps[0]
         # a non-interleaved scan covers the component's own blocks: with whole MCUs (or one component) the whole plane
-        bh, bwid = planes[c].shape[:2] if len(samp) == 1 or progressive else (None, None)
-        assert bh is not None
+        assert len(samp) == 1 or progressive
+        bh, bwid = extents[c] if extents is not None else planes[c].shape[:2]
+        assert _outside_is_empty(planes[c], (bh, bwid), ss, se, ah, al), "coefficients outside the component's own blocks"
         units = [[(c, y, x)] for y in range(bh) for x in range(bwid)]
     pred = {c: 0 for c in comps}
-    state = {"eobrun": 0, "be": []}  # EOB run and the correction bits that wait for it (refinement)
+    # EOB run and the correction bits that wait for it (refinement); for the trace: empty blocks that joined a run with such bits
+    state = {"eobrun": 0, "be": [], "empty_behind": 0}
 
     def flush_eobrun(ac):
         n = state["eobrun"]
+        if trace is not None and n:
+            trace.run(n, len(state["be"]), state["empty_behind"])
+        state["empty_behind"] = 0
         if n:
             r = n.bit_length() - 1
             bw.code(ac, r << 4)
@@ -524,9 +761,9 @@ def _scan(planes, tables, samp, mx, my, comps, ss, se, ah, al, dri, progressive,
                     continue
                 _ac_sequential(bw, ac_t, blk)
             elif ah == 0:
-                _ac_first(bw, ac_t, blk, ss, se, al, state, flush_eobrun)
+                _ac_first(bw, ac_t, blk, ss, se, al, state, flush_eobrun, trace)
             else:
-                _ac_refine(bw, ac_t, blk, ss, se, al, state, flush_eobrun)
+                _ac_refine(bw, ac_t, blk, ss, se, al, state, flush_eobrun, trace)
     if progressive and ss > 0:
         flush_eobrun(tables[comps[0]][1])
     bw.flush()
@@ -555,7 +792,9 @@ def _pt(v: int, al: int) -> int:
     return (abs(v) >> al) * (1 if v > 0 else -1)
 
 
-def _ac_first(bw, ac, blk, ss, se, al, state, flush_eobrun):
+def _ac_first(bw, ac, blk, ss, se, al, state, flush_eobrun, trace=None):
+    if trace is not None:
+        trace.block(state["eobrun"] > 0)
     if not (np.abs(blk[ZZ[ss:se + 1]]) >> al).any():  # (the common case of a large sparse picture: one more block in the run)
         state["eobrun"] += 1
         if state["eobrun"] == 0x7FFF:
@@ -571,7 +810,12 @@ def _ac_first(bw, ac, blk, ss, se, al, state, flush_eobrun):
         while r > 15:
             bw.code(ac, 0xF0)
             r -= 16
+            if trace is not None:
+                trace.zrl(ac.length(0xF0), 0)
         bw.value(ac, r, v)
+        if trace is not None:
+            s = int(abs(v)).bit_length()
+            trace.symbol(ac.length((r << 4) | s) + s, 0)
         r = 0
     if r:
         state["eobrun"] += 1
@@ -579,10 +823,15 @@ def _ac_first(bw, ac, blk, ss, se, al, state, flush_eobrun):
             flush_eobrun(ac)
 
 
-def _ac_refine(bw, ac, blk, ss, se, al, state, flush_eobrun):
+def _ac_refine(bw, ac, blk, ss, se, al, state, flush_eobrun, trace=None):
     """G.1.2.3: newly non-zero coefficients (magnitude 1 at this Al) are coded with a run of coefficients that have been zero so
     far; coefficients that were non-zero before contribute a correction bit, sent behind the next symbol (or the EOB run)."""
+    if trace is not None:
+        trace.block(state["eobrun"] > 0)
     if not (np.abs(blk[ZZ[ss:se + 1]]) >> al).any():
+        state["empty_behind"] += bool(state["be"])
+        if trace is not None:
+            trace.done(0, 0)
         state["eobrun"] += 1
         if state["eobrun"] == 0x7FFF:
             flush_eobrun(ac)
@@ -590,7 +839,7 @@ def _ac_refine(bw, ac, blk, ss, se, al, state, flush_eobrun):
     vals = [int(v) for v in blk[ZZ[ss:se + 1]]]
     mag = [abs(v) >> al for v in vals]
     eob = max((i for i, a in enumerate(mag) if a == 1), default=-1)
-    r, br = 0, []
+    r, br, coded = 0, [], 0
     for i, a in enumerate(mag):
         if a == 0:
             r += 1
@@ -601,6 +850,8 @@ def _ac_refine(bw, ac, blk, ss, se, al, state, flush_eobrun):
             r -= 16
             for bit in br:
                 bw.put(bit, 1)
+            if trace is not None:
+                trace.zrl(ac.length(0xF0), len(br))
             br = []
         if a > 1:
             br.append(a & 1)
@@ -610,7 +861,12 @@ def _ac_refine(bw, ac, blk, ss, se, al, state, flush_eobrun):
         bw.put(1 if vals[i] > 0 else 0, 1)
         for bit in br:
             bw.put(bit, 1)
-        br, r = [], 0
+        if trace is not None:
+            trace.symbol(ac.length((r << 4) | 1) + 1, len(br))
+        br, r, coded = [], 0, coded + 1
+    if trace is not None:
+        trace.trailing(len(br))
+        trace.done(coded, len(br))
     if r or br:
         state["eobrun"] += 1
         state["be"] += br
