@@ -663,18 +663,22 @@ static int decode_coefficients_device(mijpeg_decoder *d, int min_intervals, bool
     MultiScanFrame fr[2] = {{h, false, 0}, {res, res && d->host.xt.residual_wide != 0, own_count}};
     rc = device_entropy_multiscan(d, fr, res ? 2 : 1, min_intervals);
   } else if (!res) {
-    rc = device_entropy_batch(d, &h, &d->data, &d->size, 1, min_intervals, d->coef_dev, own_count, false, false, nullptr, markers);
+    EntropyBatchOptions opt;
+    opt.markers = markers;
+    rc = device_entropy_batch(d, &h, &d->data, &d->size, 1, min_intervals, d->coef_dev, own_count, opt);
   } else {
     // JPEG XT: the two codestreams are independent, so the residual one is decoded at the same time by a helper object
     // (own stream, own buffers) on a thread of its own, straight into the planes behind the legacy frame's
     if (!d->xt_helper && mijpeg_create(&d->xt_helper, d->device) != MIJPEG_OK) return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "no helper decoder for the residual codestream");
     const uint8_t *rdata = res->stream_base();
     const size_t rsize = res->stream_size();
+    EntropyBatchOptions opt;
+    opt.xt_part = true;
     int rc2 = MIJPEG_OK;
     std::thread helper([&]() {
       try {
         if (hipSetDevice(d->device) != hipSuccess) { rc2 = MIJPEG_ERR_DEVICE; return; }
-        rc2 = device_entropy_batch(d->xt_helper, &res, &rdata, &rsize, 1, min_intervals, d->coef_dev + own_count, res->info.coef_count, true);
+        rc2 = device_entropy_batch(d->xt_helper, &res, &rdata, &rsize, 1, min_intervals, d->coef_dev + own_count, res->info.coef_count, opt);
       } catch (...) { // (nothing may leave a thread's function)
         rc2 = boundary_catch(d->xt_helper, "residual codestream, device entropy decoding");
       }
@@ -683,7 +687,7 @@ static int decode_coefficients_device(mijpeg_decoder *d, int min_intervals, bool
       std::thread &t;
       ~Joiner() { if (t.joinable()) t.join(); }
     } joiner{helper};
-    rc = device_entropy_batch(d, &h, &d->data, &d->size, 1, min_intervals, d->coef_dev, own_count, true);
+    rc = device_entropy_batch(d, &h, &d->data, &d->size, 1, min_intervals, d->coef_dev, own_count, opt);
     helper.join();
     if (!rc && rc2) {
       const char *m = nullptr;
@@ -813,7 +817,10 @@ static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const 
   d->uploaded = false;
   d->decoded = false;
   d->pend_n = 0;
-  rc = device_entropy_batch(d, hosts.data(), streams, sizes, n, min_intervals, d->coef_dev, f0.coef_count, false, defer, nullptr, markers);
+  EntropyBatchOptions opt;
+  opt.defer = defer;
+  opt.markers = markers;
+  rc = device_entropy_batch(d, hosts.data(), streams, sizes, n, min_intervals, d->coef_dev, f0.coef_count, opt);
   if (!rc && markers) {
     std::vector<size_t> slot;
     stream_slots(sizes, n, slot);

@@ -235,9 +235,15 @@ const char *device_entropy_obstacle(const mij::HostDecoder &h, size_t size, bool
 const char *ragged_entropy_obstacle(const mij::HostDecoder &h, size_t size);
 const char *multiscan_obstacle(const mij::HostDecoder &h, bool xt_part, bool residual_frame);
 size_t stream_slots(const size_t *sizes, int n, std::vector<size_t> &stream_off);
+// How device_entropy_batch is asked to work: a caller names what it sets
+struct EntropyBatchOptions {
+  bool xt_part = false;                  // the stream is one of the two codestreams of a JPEG XT file
+  bool defer = false;                    // enqueue only: mijpeg_finish_batch_device waits and looks at the status words
+  bool markers = false;                  // the marker route: the streams were parsed without a marker search, the device searches them
+  const RaggedEntropy *ragged = nullptr; // images of different sizes
+};
 int device_entropy_batch(mijpeg_decoder *d, mij::HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
-                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part = false, bool defer = false,
-                         const RaggedEntropy *ragged = nullptr, bool markers = false);
+                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, const EntropyBatchOptions &opt);
 // the marker route: why a stream parsed with HostDecoder::set_skip_search stays on the host route (nullptr: it qualifies); what
 // the result words of n images say (true: every search is good)
 const char *device_markers_obstacle(const mij::HostDecoder &h, size_t size);

@@ -15,42 +15,58 @@ using namespace mij;
 // ------------------------------------------------------------------------------------------------
 // on-device entropy decoding
 // ------------------------------------------------------------------------------------------------
+// What keeps a parsed stream from every device path, sequential or not: damage, a JPEG XT stream that is not decoded as one of its
+// file's two codestreams, a missing EOI, a verdict that is the host decoder's.  `sequential_only`: progressive frames as well
+// (asked where the sequential path always asked it: behind the damage).
+static const char *stream_obstacle(const HostDecoder &h, bool xt_part, bool sequential_only)
+{
+  const mijpeg_info &f = h.info;
+  if (h.needs_sequential())
+    return "on-device entropy decoding: the stream is damaged; the host decoder walks it with the reference's resynchronisation (entropyparser.cpp:117-201)";
+  if (sequential_only && f.progressive) return "on-device entropy decoding: progressive frames are decoded on the host";
+  if (f.xt && !xt_part) return "on-device entropy decoding: not for this JPEG XT stream";
+  if (!h.residual_merged()) return "on-device entropy decoding: the legacy codestream has no EOI marker (the host decoder decides what is merged)";
+  // (a RESI box without a merging specification, a residual codestream header that does not match, tables looked up at the first
+  // request: what the reference reports behind the legacy frame's decode -- HostDecoder::decode reports it, this path would not)
+  if (h.verdict_pending()) return "on-device entropy decoding: the file's verdict is the host decoder's (residual codestream header / tables looked up at the first request)";
+  return nullptr;
+}
+
+static const char *sampling_obstacle(const mijpeg_info &f)
+{
+  for (int c = 0; c < f.components; c++)
+    if (f.hsamp[c] > 4 || f.vsamp[c] > 4) return "on-device entropy decoding: MCUs of more than 4 x 4 blocks of a component are decoded on the host";
+  return nullptr;
+}
+
 // Why a parsed stream cannot be entropy-decoded on the device (nullptr: it can).  `xt_part`: the stream is one of the
 // two codestreams of a JPEG XT profile C file (8-bit legacy or 12-bit residual frame without hidden refinement scans).
 const char *device_entropy_obstacle(const HostDecoder &h, size_t size, bool xt_part)
 {
   const mijpeg_info &f = h.info;
   // one Huffman sequential scan over all components (or a single-component frame)
-  if (h.needs_sequential())
-    return "on-device entropy decoding: the stream is damaged; the host decoder walks it with the reference's resynchronisation (entropyparser.cpp:117-201)";
-  if (f.progressive) return "on-device entropy decoding: progressive frames are decoded on the host";
-  if (f.xt && !xt_part) return "on-device entropy decoding: not for this JPEG XT stream";
-  if (!h.residual_merged()) return "on-device entropy decoding: the legacy codestream has no EOI marker (the host decoder decides what is merged)";
-  // (a RESI box without a merging specification, a residual codestream header that does not match, tables looked up at the first
-  // request: what the reference reports behind the legacy frame's decode -- HostDecoder::decode reports it, this path would not)
-  if (h.verdict_pending()) return "on-device entropy decoding: the file's verdict is the host decoder's (residual codestream header / tables looked up at the first request)";
+  if (const char *why = stream_obstacle(h, xt_part, true)) return why;
   if (f.precision != 8 && !(xt_part && f.precision == 12)) return "on-device entropy decoding: 8-bit frames (12-bit residual frames of JPEG XT) only";
   if (h.scans.size() != 1 || h.hidden_bits()) return "on-device entropy decoding: the frame has more than one scan";
   const Scan &s = h.scans[0];
   if (s.ncomp != f.components) return "on-device entropy decoding: the scan does not cover all components";
   if (size > 0xfffffff0ull) return "on-device entropy decoding: stream too long";
-  for (int c = 0; c < f.components; c++)
-    if (f.hsamp[c] > 4 || f.vsamp[c] > 4) return "on-device entropy decoding: MCUs of more than 4 x 4 blocks of a component are decoded on the host";
-  return nullptr;
+  return sampling_obstacle(f);
 }
 
-// Why the restart markers of a parsed sequential stream keep it from the device (nullptr: they do not, or it has none): the
+// Why the restart markers of scan `si` of a parsed stream keep it from the device (nullptr: they do not, or it has none): the
 // intervals the kernel decodes side by side must all be there, in sequence.
-static const char *restart_markers_obstacle(const HostDecoder &h)
+static const char *restart_markers_obstacle(const HostDecoder &h, size_t si)
 {
-  const Scan &s = h.scans[0];
+  static const char MISSING[] = "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
+  const Scan &s = h.scans[si];
   if (s.restart_interval <= 0) return nullptr;
   const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
   const int64_t nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
   if (nint > 0x7fffffff) return "too many restart intervals";
-  if ((int64_t)s.interval_begin.size() < nint)
-    return "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
-  const std::vector<uint8_t> &rst = h.restart_codes(0);
+  if ((int64_t)s.interval_begin.size() < nint) return MISSING;
+  const std::vector<uint8_t> &rst = h.restart_codes(si);
+  if ((int64_t)rst.size() + 1 < nint) return MISSING;
   for (int64_t k = 0; k + 1 < nint; k++)
     if (rst[(size_t)k] != 0xd0 + (k & 7))
       return "restart markers out of sequence: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
@@ -76,7 +92,7 @@ const char *ragged_entropy_obstacle(const HostDecoder &h, size_t size)
 {
   int code;
   if (const char *why = device_entropy_obstacle(h, size, false)) return why;
-  if (const char *why = restart_markers_obstacle(h)) return why;
+  if (const char *why = restart_markers_obstacle(h, 0)) return why;
   if (const char *why = stream_copy_obstacle(h, size, &code)) return why;
   const Scan &s = h.scans[0];
   if (s.restart_interval > 0 && s.interval_ubegin.size() < s.interval_begin.size()) return "restart intervals missing";
@@ -142,13 +158,52 @@ int lanes_for(int64_t intervals)
   return lanes;
 }
 
-// The buffer of one device decode: on the device [streams][tables, intervals ...][status words]; in pinned staging (ent_host)
-// everything behind the streams, at the same offsets less stream_bytes.  The staging part goes up in one copy, and the status
-// words come back into its end.
-int ensure_entropy_buffers(mijpeg_decoder *d, size_t stream_bytes, size_t tail_bytes)
+// The buffer of one device decode: on the device [streams][tables, intervals ...][status words][what only the device keeps:
+// `device_extra` bytes]; in pinned staging (ent_host) everything behind the streams up to the status words, at the same offsets
+// less stream_bytes.  The staging part goes up in one copy, and the status words come back into its end.
+int ensure_entropy_buffers(mijpeg_decoder *d, size_t stream_bytes, size_t tail_bytes, size_t device_extra = 0)
 {
-  const int rc = ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, stream_bytes + tail_bytes);
+  const int rc = ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, stream_bytes + tail_bytes + device_extra);
   return rc ? rc : ensure_pinned(d, &d->ent_host, &d->ent_host_cap, tail_bytes);
+}
+
+// Blocks of scan component k in one MCU: an interleaved scan uses the frame's sampling factors, a single-component scan 1 x 1
+struct McuBlocks { int h, v; };
+McuBlocks mcu_blocks(const mijpeg_info &f, const Scan &s, int k)
+{
+  const int c = s.sc[k].comp;
+  return s.ncomp > 1 ? McuBlocks{f.hsamp[c], f.vsamp[c]} : McuBlocks{1, 1};
+}
+
+// One image of a marker search in staging: its descriptor, its chunks (at chunks[im.first_chunk]) and a fresh result
+void stage_marker_image(MarkerImage &im, MarkerChunk *chunks, MarkerResult &res, uint32_t image, const MarkerImage &desc)
+{
+  im = desc;
+  im.n_chunks = markers_chunks(im.size);
+  for (uint32_t k = 0; k < im.n_chunks; k++) chunks[im.first_chunk + k] = MarkerChunk{image, k};
+  res.flags = 0;
+  res.term = im.size;
+  res.total = res.markers = 0;
+}
+
+// The argument block of a search over device memory (chunk0 / n_chunks: the caller's launch)
+MarkerArgs marker_args(const uint8_t *raw, uint8_t *dst, uint32_t *ibegin, uint32_t *iend, const MarkerImage *images, const MarkerChunk *chunks,
+                       MarkerResult *results, uint8_t *scratch, const MarkerScratch &ms)
+{
+  MarkerArgs a;
+  memset(&a, 0, sizeof(a));
+  a.raw = raw;
+  a.dst = dst;
+  a.ibegin = ibegin;
+  a.iend = iend;
+  a.images = images;
+  a.chunks = chunks;
+  a.kept = (uint32_t *)(scratch + ms.kept);
+  a.marks = (uint32_t *)(scratch + ms.marks);
+  a.kept_at = (const uint64_t *)(scratch + ms.kept_at);
+  a.marks_at = (const uint64_t *)(scratch + ms.marks_at);
+  a.results = results;
+  return a;
 }
 
 // The unstuffing gather: the device's copy of scans' entropy coded data (no byte stuffing, no markers: HostDecoder::unstuff_piece)
@@ -210,6 +265,39 @@ struct QuiesceOnError {
   ~QuiesceOnError() { if (armed) quiesce(d); }
 };
 
+// Where the restart intervals of one image of a launch come from: what device_entropy_batch's stages switch on
+enum class IntervalSource {
+  RestartMarkers, // found by the host's marker search (Scan::interval_ubegin / interval_uend)
+  HostWalk,       // no markers: the host's self-synchronising walk plans exact restart points (MIJPEG_DEVICE_WALK=0)
+  DeviceWalk,     // no markers: huffman_walk_kernel finds them in front of the decode; their number is known already
+  WholeScan,      // no markers, a small member of a ragged launch: ONE interval, one lane -- every MCU in sequence, as a host thread would
+  MarkerSearch,   // the raw segment goes up; the search kernels (markers.hip) write the copy and the interval tables
+};
+
+struct ImagePlan {
+  IntervalSource source = IntervalSource::RestartMarkers;
+  int64_t n_intervals = 0, first_interval = 0; // its entries in the launch's interval tables
+  int mcus_per_interval = 0;                   // the restart interval, or MCUs per virtual interval
+  size_t copy_bytes = 0; // the device's copy of its entropy coded data (MarkerSearch: the raw segment, terminator included -- the copy is no longer)
+  size_t slot_off = 0;   // its slot in the stream buffer (stream_slots)
+  std::unique_ptr<VirtualIntervals> walked; // HostWalk: the restart points
+  bool virtual_intervals() const { return source == IntervalSource::HostWalk || source == IntervalSource::DeviceWalk; }
+};
+
+struct BatchPlan {
+  std::vector<ImagePlan> images;
+  int64_t total_intervals = 0, n_groups = 0;
+  int lanes = 0, per_group = 0; // decoding lanes per wave; intervals of one workgroup
+  size_t stream_bytes = 0;      // all slots
+  uint32_t marker_chunks = 0;
+  bool any_virtual = false; // some image has virtual intervals: the launch carries bit skips and DC predictors per interval
+  bool any_dwalk = false;   // ... found by the device walk
+  bool needs_clear = false; // some scan leaves blocks of its planes unwritten: the planes are cleared first
+  int n() const { return (int)images.size(); }
+  int64_t groups_of(int i) const { return (images[(size_t)i].n_intervals + per_group - 1) / per_group; }
+  size_t slot_end(int i) const { return i + 1 < n() ? images[(size_t)i + 1].slot_off : stream_bytes; }
+};
+
 } // namespace
 
 // Where the device's copy of image i's entropy coded data goes inside the launch's stream buffer (and inside the pinned
@@ -247,12 +335,18 @@ int walk_verdict(mijpeg_decoder *d, const uint32_t *walk_status, int n)
 // until the hand-over states between neighbouring subsequences stop changing, prefix sums over the subsequences
 // (block numbers, DC predictors: huffman_walk_scan_kernel), and one EMIT walk that writes the interval tables the
 // decode kernel reads.  The host only looks at the per-round "something changed" flags.
-// `images_host` is the staging copy of the HuffImage array (first_interval = start of the image's interval entries).
-static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const std::vector<int> &dwalk, const HuffScanArgs &scan,
-                              const HuffImage *images_dev, uint32_t *ibegin_dev, uint8_t *iskip_dev, int16_t *ipred_dev,
-                              const HuffImage *images_host, const std::vector<size_t> &usize, bool defer = false, bool per_image = false,
-                              int *walk_launches = nullptr)
+// The images of `plan` whose source is the device walk are walked; `scan` is the argument block of the decode that follows (its
+// data, images and tables are the walk's), `intervals` the tables the EMIT walk writes.
+struct DeviceIntervals { uint32_t *ibegin; uint8_t *iskip; int16_t *ipred; };
+static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, const BatchPlan &plan, const EntropyBatchOptions &opt, const HuffScanArgs &scan,
+                              const DeviceIntervals &intervals)
 {
+  const int n = plan.n();
+  const bool defer = opt.defer, per_image = opt.ragged != nullptr; // (images of different sizes: interval sizes and block counts image by image)
+  int *const walk_launches = opt.ragged ? opt.ragged->walk_launches : nullptr;
+  // MCUs per virtual interval of the images that are walked, 0 for the others
+  auto dwalk = [&](int i) { return plan.images[(size_t)i].source == IntervalSource::DeviceWalk ? plan.images[(size_t)i].mcus_per_interval : 0; };
+  auto usize = [&](int i) { return plan.images[(size_t)i].copy_bytes; }; // (the device's copy: entropy coded data without the byte stuffing)
   const mijpeg_info &f0 = hosts[0]->info;
   const Scan &s0 = hosts[0]->scans[0];
   HuffWalkArgs w;
@@ -260,10 +354,10 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   w.ncomp = s0.ncomp;
   int B = 0;
   for (int k = 0; k < s0.ncomp; k++) {
-    const int c = s0.sc[k].comp;
-    w.hs[k] = s0.ncomp > 1 ? f0.hsamp[c] : 1;
-    w.vs[k] = s0.ncomp > 1 ? f0.vsamp[c] : 1;
-    B += w.hs[k] * w.vs[k];
+    const McuBlocks b = mcu_blocks(f0, s0, k);
+    w.hs[k] = b.h;
+    w.vs[k] = b.v;
+    B += b.h * b.v;
   }
   if (B > 64) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device walk");
   w.nblk_mcu = B;
@@ -273,8 +367,8 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   // subsequences, so fewer rounds over larger ones (measured on 1, 4 and 16 8K frames: 128, 256, 512 bytes win).
   size_t longest = 0, all_bytes = 0;
   for (int i = 0; i < n; i++)
-    if (dwalk[(size_t)i]) {
-      const size_t len = usize[(size_t)i]; // (the device's copy: entropy coded data without the byte stuffing)
+    if (dwalk(i)) {
+      const size_t len = usize(i);
       longest = std::max(longest, len);
       all_bytes += len;
     }
@@ -287,11 +381,11 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   uint32_t nsub_total = 0;
   for (int i = 0; i < n; i++) {
     img_e0[(size_t)i] = 0;
-    img_e1[(size_t)i] = (uint32_t)usize[(size_t)i];
-    img_int0[(size_t)i] = images_host[i].first_interval;
+    img_e1[(size_t)i] = (uint32_t)usize(i);
+    img_int0[(size_t)i] = (uint32_t)plan.images[(size_t)i].first_interval;
     img_sub0[(size_t)i] = nsub_total;
-    if (dwalk[(size_t)i]) {
-      img_nsub[(size_t)i] = (uint32_t)((usize[(size_t)i] + sub_bytes - 1) / sub_bytes);
+    if (dwalk(i)) {
+      img_nsub[(size_t)i] = (uint32_t)((usize(i) + sub_bytes - 1) / sub_bytes);
       nsub_total += img_nsub[(size_t)i];
     }
   }
@@ -341,7 +435,7 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
     uint32_t *every = (uint32_t *)(wh + o_every), *blocks = (uint32_t *)(wh + o_blocks);
     for (int i = 0; i < n; i++) {
       const Scan &s = hosts[i]->scans[0];
-      every[i] = (uint32_t)(std::max(1, dwalk[(size_t)i]) * B);
+      every[i] = (uint32_t)(std::max(1, dwalk(i)) * B);
       blocks[i] = (uint32_t)((int64_t)s.mcus_x * s.mcus_y * B);
     }
     w.img_emit_every = (const uint32_t *)(d->walk_dev + o_every);
@@ -358,7 +452,7 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   HIP_TRY(d, hipMemcpyAsync(wd, wh, o_up_end, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(d, hipMemsetAsync(wd + o_flags, 0, o_zero_end - o_flags, d->stream));
   w.data = scan.data;
-  w.images = images_dev;
+  w.images = scan.images;
   w.tables = scan.tables;
   w.sub_image = (const uint32_t *)(wd + o_simg);
   w.sub_first = (const uint32_t *)(wd + o_sfirst);
@@ -377,14 +471,14 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, int 
   w.first_pred = (int32_t *)(wd + o_fpred);
   w.tile_sums = (WalkSums *)(wd + o_tiles);
   w.tiles_per_image = tiles;
-  w.ibegin = ibegin_dev;
-  w.iskip = iskip_dev;
-  w.ipred = ipred_dev;
+  w.ibegin = intervals.ibegin;
+  w.iskip = intervals.iskip;
+  w.ipred = intervals.ipred;
   if (!per_image) {
     // one interval size and one block count for the launch: the images share their geometry, hence their MCUs per virtual interval
     int per = 0;
     for (int i = 0; i < n; i++)
-      if (dwalk[(size_t)i]) per = dwalk[(size_t)i];
+      if (dwalk(i)) per = dwalk(i);
     w.emit_every = (uint32_t)(per * B);
     w.total_blocks = (uint32_t)((int64_t)s0.mcus_x * s0.mcus_y * B);
   }
@@ -493,30 +587,25 @@ static void build_dev_table(HuffDevTable &dst, const HuffTable &src, int mode)
   memcpy(dst.values, src.values, sizeof(dst.values));
 }
 
-// Entropy-decode n parsed images on the device with one launch of huffman_scan_kernel (large uniform batches: one per upload
-// group).  Without `ragged`: images of identical frame geometry, image i into coef_dev + i * frame_stride.  With it: images that
-// share components and sampling factors but not their size, image i into coef_dev + ragged->coef_base[i], plane geometry per
-// image; a damaged image is reported in ragged->verdict[i] instead of failing the call.
-// hosts[i]->info receives fast_arith / range_max.  Returns MIJPEG_OK, MIJPEG_ERR_NOT_AVAILABLE (nothing touched) or an error.
-int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
-                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, bool xt_part, bool defer, const RaggedEntropy *ragged, bool markers)
+// ------------------------------------------------------------------------------------------------
+// device_entropy_batch and its stages: qualify and count, table slots, layout, fill staging, kernel arguments, enqueue, read back
+// and verdict
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// Qualify and count: what keeps image i from the device, what the images of a launch must share, where each image's intervals come
+// from and how many they are, the `min_intervals` gate; then the device copies and their slots.  Nothing has been touched when this
+// refuses.
+int plan_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const size_t *sizes, int n, int min_intervals, const EntropyBatchOptions &opt, BatchPlan &plan)
 {
-  // `markers`: the streams were parsed without a marker search (device_markers_obstacle holds for each): their raw segments go up,
-  // and the search kernels write the copies and the interval tables in front of the Huffman launch.  On a search that is not
-  // good the call answers MIJPEG_ERR_NOT_AVAILABLE with d->markers_retry set (deferred: mijpeg_finish_batch_device looks).
-  if (markers && (ragged || xt_part)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: uniform batches of plain streams only");
+  const bool ragged = opt.ragged != nullptr;
   const mijpeg_info &f0 = hosts[0]->info;
   const Scan &s0 = hosts[0]->scans[0];
-  int64_t total_intervals = 0;
-  std::vector<int64_t> nints((size_t)n);
-  std::vector<std::unique_ptr<VirtualIntervals>> virt((size_t)n); // restart points planned by the host's walk ...
-  std::vector<int> dwalk((size_t)n, 0);                           // ... or MCUs per virtual interval when the device walks
-  std::vector<char> single((size_t)n, 0);                         // ragged launches: no restart markers, the image is ONE interval
+  plan.images.resize((size_t)n);
   d->walk_rounds = 0;
   const bool device_walk = !(getenv("MIJPEG_DEVICE_WALK") && atoi(getenv("MIJPEG_DEVICE_WALK")) == 0);
-  const auto tb0 = std::chrono::steady_clock::now();
   for (int i = 0; i < n; i++) {
-    const char *why = markers ? device_markers_obstacle(*hosts[i], sizes[i]) : device_entropy_obstacle(*hosts[i], sizes[i], xt_part);
+    const char *why = opt.markers ? device_markers_obstacle(*hosts[i], sizes[i]) : device_entropy_obstacle(*hosts[i], sizes[i], opt.xt_part);
     if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
     const mijpeg_info &f = hosts[i]->info;
     const Scan &s = hosts[i]->scans[0];
@@ -530,143 +619,183 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
       return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share colour transformation and precision");
     for (int k = 0; k < s.ncomp; k++)
       if (s.sc[k].comp != s0.sc[k].comp) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share the component order of their scan");
+    ImagePlan &p = plan.images[(size_t)i];
     const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
-    int64_t nint;
+    const bool small = total_mcus < 256 || s.ecs_end - s.ecs_begin < 4096; // too small for a walk
     if (s.restart_interval > 0) {
-      nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
-      if (!markers)
-        if (const char *bad = restart_markers_obstacle(*hosts[i])) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, bad);
-    } else if (ragged && (total_mcus < 256 || s.ecs_end - s.ecs_begin < 4096)) {
-      // too small for the walk: one interval, one lane -- every MCU of the image in sequence, as a host thread would
-      single[(size_t)i] = 1;
-      nint = 1;
+      p.source = opt.markers ? IntervalSource::MarkerSearch : IntervalSource::RestartMarkers;
+      p.mcus_per_interval = s.restart_interval;
+      p.n_intervals = (total_mcus + s.restart_interval - 1) / s.restart_interval;
+      if (!opt.markers)
+        if (const char *bad = restart_markers_obstacle(*hosts[i], 0)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, bad);
+    } else if (ragged && small) {
+      p.source = IntervalSource::WholeScan;
+      p.mcus_per_interval = s.mcus_x * s.mcus_y;
+      p.n_intervals = 1;
     } else {
-      // no restart markers: the host's self-synchronising walk finds exact restart points ("virtual intervals"),
-      // about 16 K of them, and the device decodes from there
+      // no restart markers: the decode starts from exact restart points ("virtual intervals"), about 16 K of them
       const int per = (int)std::min<int64_t>(64, std::max<int64_t>(1, total_mcus / 16384));
-      if (total_mcus < 256 || s.ecs_end - s.ecs_begin < 4096)
-        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream without restart markers is too small for speculative decoding");
-      if (device_walk) { // the restart points are found on the device (huffman_walk_kernel); their number is known already
-        dwalk[(size_t)i] = per;
-        nint = (total_mcus + per - 1) / per;
+      if (small) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream without restart markers is too small for speculative decoding");
+      if (device_walk) {
+        p.source = IntervalSource::DeviceWalk;
+        p.mcus_per_interval = per;
+        p.n_intervals = (total_mcus + per - 1) / per;
       } else {
-        virt[(size_t)i].reset(new VirtualIntervals());
-        if (hosts[i]->plan_virtual_intervals(0, per, 0, *virt[(size_t)i]))
+        p.source = IntervalSource::HostWalk;
+        p.walked.reset(new VirtualIntervals());
+        if (hosts[i]->plan_virtual_intervals(0, per, 0, *p.walked))
           return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream without restart markers did not lend itself to speculative decoding");
-        nint = (int64_t)virt[(size_t)i]->byte_off.size();
+        p.mcus_per_interval = p.walked->mcus_per_interval;
+        p.n_intervals = (int64_t)p.walked->byte_off.size();
       }
     }
-    nints[(size_t)i] = nint;
-    total_intervals += nint;
+    plan.total_intervals += p.n_intervals;
   }
   if (min_intervals <= 0) min_intervals = 2048; // below this the device runs mostly idle
-  if ((total_intervals < min_intervals && !ragged) || total_intervals > 0x7fffffff)
+  if ((plan.total_intervals < min_intervals && !ragged) || plan.total_intervals > 0x7fffffff)
     return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too few restart intervals to occupy the device");
-
-  HuffScanArgs a;
-  memset(&a, 0, sizeof(a));
-  a.lanes = lanes_for(total_intervals);
-  a.waves_per_group = WAVES_PER_GROUP;
-  const int per_group = a.lanes * a.waves_per_group; // intervals of one workgroup
-  // Tables in LDS: components that bring the same Huffman code (Cb and Cr practically always do) share one copy -- the
-  // workgroup's LDS footprint decides how many of them a CU holds.  The sharing pattern is that of image 0 and must hold
-  // for every image of the launch; the device walk indexes its tables by component and keeps one per component.
-  int tab_slot[MIJPEG_MAX_COMPONENTS][2];
-  int ntab = 0;
-  {
-    bool walk_any = false;
-    for (int i = 0; i < n; i++) walk_any |= dwalk[(size_t)i] > 0;
-    bool share = !walk_any;
-    for (int pass = 0; pass < 2; pass++) {
-      ntab = 0;
-      for (int k = 0; k < s0.ncomp; k++)
-        for (int t = 0; t < 2; t++) {
-          tab_slot[k][t] = -1;
-          for (int j = 0; j < k && share && tab_slot[k][t] < 0; j++)
-            if ((t ? s0.ac[k].same_code(s0.ac[j]) : s0.dc[k].same_code(s0.dc[j]))) tab_slot[k][t] = tab_slot[j][t];
-          if (tab_slot[k][t] < 0) tab_slot[k][t] = ntab++;
-        }
-      if (!share) break;
-      bool holds = true; // ... in every image?
-      for (int i = 1; i < n && holds; i++) {
-        const Scan &s = hosts[i]->scans[0];
-        for (int k = 0; k < s.ncomp && holds; k++)
-          for (int j = 0; j < k && holds; j++) {
-            if (tab_slot[k][0] == tab_slot[j][0] && !s.dc[k].same_code(s.dc[j])) holds = false;
-            if (tab_slot[k][1] == tab_slot[j][1] && !s.ac[k].same_code(s.ac[j])) holds = false;
-          }
-      }
-      if (holds) break;
-      share = false;
-    }
-  }
-  const size_t table_blob = (size_t)ntab * sizeof(HuffDevTable) + sizeof(HuffDevAux);
-
-  // device buffer: [streams, each padded][ibegin][iend][iskip][ipred][tables of every image][images][groups][status]
+  plan.lanes = lanes_for(plan.total_intervals);
+  plan.per_group = plan.lanes * WAVES_PER_GROUP;
   // What travels to the device is the entropy coded data of every image WITHOUT its byte stuffing and without the markers,
   // one restart interval behind the other (HostDecoder::unstuff_piece; the marker search counted what leaves): the kernels
   // address it by plain bit positions (huffman.hip, DevBits).
-  std::vector<size_t> usize((size_t)n);
   std::vector<size_t> stream_off;
-  const size_t stream_bytes = stream_slots(sizes, n, stream_off);
-  int64_t n_groups = 0;
+  plan.stream_bytes = stream_slots(sizes, n, stream_off);
   for (int i = 0; i < n; i++) {
-    // (the marker route: the raw segment, terminator included -- the copy is no longer)
-    usize[(size_t)i] = markers ? sizes[i] - hosts[i]->scans[0].ecs_begin : hosts[i]->scans[0].unstuffed_size;
-    int why_code;
-    if (!markers)
-      if (const char *why = stream_copy_obstacle(*hosts[i], sizes[i], &why_code)) return set_error(d, why_code, why);
-    if (!markers && !dwalk[(size_t)i] && !virt[(size_t)i] && !single[(size_t)i] && (int64_t)hosts[i]->scans[0].interval_ubegin.size() < nints[(size_t)i])
-      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart intervals missing");
-    n_groups += (nints[(size_t)i] + per_group - 1) / per_group;
-  }
-  if (stream_bytes > 0xfffffff0ull || n_groups > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "batch too large for one launch");
-  bool any_virtual = false, any_dwalk = false;
-  for (int i = 0; i < n; i++) {
-    any_virtual |= virt[(size_t)i] != nullptr || dwalk[(size_t)i] > 0;
-    any_dwalk |= dwalk[(size_t)i] > 0;
-  }
-  // offsets behind the streams: in the device buffer at dp, in pinned staging at hp
-  Layout L;
-  const size_t T = (size_t)total_intervals;
-  const size_t off_ib = L.take(T * 4), off_ie = L.take(T * 4), off_isk = L.take(any_virtual ? T : 0), off_ipr = L.take(any_virtual ? T * 8 : 0);
-  const size_t off_tab = L.take((size_t)n * table_blob), off_img = L.take((size_t)n * sizeof(HuffImage)), off_grp = L.take((size_t)n_groups * sizeof(HuffGroup));
-  const size_t off_planes = L.take(ragged ? (size_t)n * sizeof(HuffPlanes) : 0);
-  // the marker route: descriptors of the search (images, chunks) and, right in front of the status words and read back with
-  // them, its result words; behind the status words and on the device only its scratch and the raw segments (slots as in front)
-  uint32_t marker_chunks = 0;
-  for (int i = 0; markers && i < n; i++) marker_chunks += markers_chunks(usize[(size_t)i]);
-  const size_t off_mimg = L.take(markers ? (size_t)n * sizeof(MarkerImage) : 0), off_mchunk = L.take(markers ? (size_t)marker_chunks * sizeof(MarkerChunk) : 0);
-  const size_t off_mres = L.take(markers ? (size_t)n * sizeof(MarkerResult) : 0);
-  const size_t status_bytes = (size_t)n * 32, off_status = L.take(status_bytes);
-  static_assert(sizeof(MarkerResult) == 16, "the result words end where the status words begin");
-  const size_t tail_bytes = L.end;
-  const MarkerScratch mscratch = markers_scratch(marker_chunks);
-  const size_t off_mscratch = L.take(markers ? mscratch.end : 0), off_raw = L.take(markers ? stream_bytes : 0);
-  int rc = markers ? ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, stream_bytes + L.end) : ensure_entropy_buffers(d, stream_bytes, tail_bytes);
-  if (!rc && markers) rc = ensure_pinned(d, &d->ent_host, &d->ent_host_cap, tail_bytes);
-  if (rc) return rc;
-  if (markers && stream_bytes + L.end > 0xfffffff0ull) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "batch too large for one launch");
-  uint8_t *const hp = d->ent_host, *const dp = d->ent_dev + stream_bytes;
-  uint32_t *ib = (uint32_t *)(hp + off_ib), *ie = (uint32_t *)(hp + off_ie);
-  HuffImage *images = (HuffImage *)(hp + off_img);
-  HuffGroup *groups = (HuffGroup *)(hp + off_grp);
-  int64_t first = 0, g = 0;
-  bool needs_clear = false;
-  for (int i = 0; i < n; i++) {
+    ImagePlan &p = plan.images[(size_t)i];
     const mijpeg_info &f = hosts[i]->info;
     const Scan &s = hosts[i]->scans[0];
-    const int64_t nint = nints[(size_t)i];
-    if (dwalk[(size_t)i]) { // filled in by the EMIT walk on the device
-      for (int64_t k = 0; k < nint; k++) { ib[first + k] = 0; ie[first + k] = (uint32_t)usize[(size_t)i]; }
-      memset(hp + off_isk + first, 0, (size_t)nint);
-      memset(hp + off_ipr + (size_t)first * 8, 0, (size_t)nint * 8);
-    } else if (virt[(size_t)i]) {
+    p.slot_off = stream_off[(size_t)i];
+    p.first_interval = i ? plan.images[(size_t)i - 1].first_interval + plan.images[(size_t)i - 1].n_intervals : 0;
+    if (opt.markers) {
+      p.copy_bytes = sizes[i] - s.ecs_begin;
+      plan.marker_chunks += markers_chunks(p.copy_bytes);
+    } else {
+      p.copy_bytes = s.unstuffed_size;
+      int why_code;
+      if (const char *why = stream_copy_obstacle(*hosts[i], sizes[i], &why_code)) return set_error(d, why_code, why);
+    }
+    if (p.source == IntervalSource::RestartMarkers && (int64_t)s.interval_ubegin.size() < p.n_intervals)
+      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart intervals missing");
+    plan.n_groups += plan.groups_of(i);
+    plan.any_virtual |= p.virtual_intervals();
+    plan.any_dwalk |= p.source == IntervalSource::DeviceWalk;
+    // an interleaved scan writes every block of every plane; a single-component scan of a frame whose only component
+    // has sampling factors > 1 leaves the MCU padding blocks untouched (they must read as zero)
+    if (s.ncomp == 1 && (s.mcus_x != f.blocks_w[s.sc[0].comp] || s.mcus_y != f.blocks_h[s.sc[0].comp])) plan.needs_clear = true;
+  }
+  // (the stores of a ragged launch lie between those of other launches: nothing to clear in one sweep, and no layout group holds such frames)
+  if (plan.needs_clear && ragged) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "single components with sampling factors are not decoded in a ragged launch");
+  return MIJPEG_OK;
+}
+
+// Table slots.  Tables in LDS: components that bring the same Huffman code (Cb and Cr practically always do) share one copy -- the
+// workgroup's LDS footprint decides how many of them a CU holds.  The sharing pattern is that of image 0 and must hold
+// for every image of the launch; the device walk indexes its tables by component and keeps one per component.
+struct TableSlots {
+  int slot[MIJPEG_MAX_COMPONENTS][2]; // per scan component: DC, AC
+  int ntab = 0;
+  size_t blob_bytes() const { return (size_t)ntab * sizeof(HuffDevTable) + sizeof(HuffDevAux); } // one image's tables
+};
+TableSlots share_table_slots(HostDecoder *const *hosts, int n, bool any_dwalk)
+{
+  const Scan &s0 = hosts[0]->scans[0];
+  TableSlots t;
+  bool share = !any_dwalk;
+  for (int pass = 0; pass < 2; pass++) {
+    t.ntab = 0;
+    for (int k = 0; k < s0.ncomp; k++)
+      for (int x = 0; x < 2; x++) {
+        t.slot[k][x] = -1;
+        for (int j = 0; j < k && share && t.slot[k][x] < 0; j++)
+          if ((x ? s0.ac[k].same_code(s0.ac[j]) : s0.dc[k].same_code(s0.dc[j]))) t.slot[k][x] = t.slot[j][x];
+        if (t.slot[k][x] < 0) t.slot[k][x] = t.ntab++;
+      }
+    if (!share) break;
+    bool holds = true; // ... in every image?
+    for (int i = 1; i < n && holds; i++) {
+      const Scan &s = hosts[i]->scans[0];
+      for (int k = 0; k < s.ncomp && holds; k++)
+        for (int j = 0; j < k && holds; j++) {
+          if (t.slot[k][0] == t.slot[j][0] && !s.dc[k].same_code(s.dc[j])) holds = false;
+          if (t.slot[k][1] == t.slot[j][1] && !s.ac[k].same_code(s.ac[j])) holds = false;
+        }
+    }
+    if (holds) break;
+    share = false;
+  }
+  return t;
+}
+
+// Layout.  The device buffer is [streams, each padded] and behind them, at these offsets,
+//   [ibegin][iend][iskip][ipred][tables of every image][images][groups][planes][marker images][marker chunks][marker results][status]
+//   | [marker scratch][raw segments, slots as in front]
+// Pinned staging (ent_host) holds the part in front of the bar at the same offsets; it goes up as far as the status words, and
+// the marker results and the status words come back in one copy.  What is behind the bar exists on the device only.
+struct BatchLayout {
+  size_t stream_bytes;
+  size_t ibegin, iend, iskip, ipred, tables, images, groups, planes, mimages, mchunks, mresults, status;
+  size_t status_bytes, tail_bytes; // tail_bytes: everything in front of the bar
+  MarkerScratch scratch;
+  size_t mscratch, raw, end;
+  size_t upload_bytes() const { return status; }
+  size_t read_back_bytes() const { return status + status_bytes - mresults; }
+  size_t device_extra() const { return end - tail_bytes; }
+};
+// nullptr, or why the launch does not fit its 32-bit offsets
+const char *batch_layout(const BatchPlan &plan, size_t table_blob, const EntropyBatchOptions &opt, BatchLayout &l)
+{
+  static_assert(sizeof(MarkerResult) == 16, "the result words end where the status words begin");
+  const size_t n = (size_t)plan.n(), T = (size_t)plan.total_intervals;
+  Layout L;
+  l.stream_bytes = plan.stream_bytes;
+  l.ibegin = L.take(T * 4);
+  l.iend = L.take(T * 4);
+  l.iskip = L.take(plan.any_virtual ? T : 0);
+  l.ipred = L.take(plan.any_virtual ? T * 8 : 0);
+  l.tables = L.take(n * table_blob);
+  l.images = L.take(n * sizeof(HuffImage));
+  l.groups = L.take((size_t)plan.n_groups * sizeof(HuffGroup));
+  l.planes = L.take(opt.ragged ? n * sizeof(HuffPlanes) : 0);
+  l.mimages = L.take(opt.markers ? n * sizeof(MarkerImage) : 0);
+  l.mchunks = L.take(opt.markers ? (size_t)plan.marker_chunks * sizeof(MarkerChunk) : 0);
+  l.mresults = L.take(opt.markers ? n * sizeof(MarkerResult) : 0);
+  l.status_bytes = n * 32;
+  l.status = L.take(l.status_bytes);
+  l.tail_bytes = L.end;
+  l.scratch = markers_scratch(plan.marker_chunks);
+  l.mscratch = L.take(opt.markers ? l.scratch.end : 0);
+  l.raw = L.take(opt.markers ? plan.stream_bytes : 0);
+  l.end = L.end;
+  if (plan.stream_bytes > 0xfffffff0ull || plan.n_groups > 0x7fffffff || (opt.markers && plan.stream_bytes + l.end > 0xfffffff0ull)) return "batch too large for one launch";
+  return nullptr;
+}
+
+// Fill staging: the pinned copy (at hp) of everything the layout places behind the streams, image by image
+struct Staging {
+  const BatchPlan &plan;
+  const BatchLayout &l;
+  uint8_t *hp;
+
+  // image i: its entries in the interval tables
+  void intervals(int i, const Scan &s, const uint8_t *data) const
+  {
+    const ImagePlan &p = plan.images[(size_t)i];
+    const int64_t first = p.first_interval, nint = p.n_intervals;
+    uint32_t *ib = (uint32_t *)(hp + l.ibegin) + first, *ie = (uint32_t *)(hp + l.iend) + first;
+    // (iskip and ipred exist where some image of the launch has virtual intervals)
+    uint8_t *isk = plan.any_virtual ? hp + l.iskip + first : nullptr;
+    int16_t *ipr = plan.any_virtual ? (int16_t *)(hp + l.ipred) + first * 4 : nullptr;
+    switch (p.source) {
+    case IntervalSource::DeviceWalk: // filled in by the EMIT walk on the device
+      for (int64_t k = 0; k < nint; k++) { ib[k] = 0; ie[k] = (uint32_t)p.copy_bytes; }
+      memset(isk, 0, (size_t)nint);
+      memset(ipr, 0, (size_t)nint * 8);
+      break;
+    case IntervalSource::HostWalk: {
       // the host's walk reports stream offsets: into the copy's (stuffed pairs in front of each, counted as the offsets go up)
-      const VirtualIntervals &vi = *virt[(size_t)i];
-      uint8_t *isk = hp + off_isk;
-      int16_t *ipr = (int16_t *)(hp + off_ipr);
-      const uint8_t *base = s.base ? s.base : datas[i];
+      const VirtualIntervals &vi = *p.walked;
+      const uint8_t *base = s.base ? s.base : data;
       size_t at = s.ecs_begin, pairs = 0;
       for (int64_t k = 0; k < nint; k++) {
         const size_t pos = vi.byte_off[(size_t)k];
@@ -678,44 +807,47 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
           else at++;
         }
         at = std::max(at, pos);
-        ib[first + k] = (uint32_t)(pos - s.ecs_begin - pairs);
-        ie[first + k] = (uint32_t)usize[(size_t)i];
-        isk[first + k] = vi.bit_skip[(size_t)k];
-        memcpy(ipr + (first + k) * 4, &vi.pred[(size_t)k * 4], 8);
+        ib[k] = (uint32_t)(pos - s.ecs_begin - pairs);
+        ie[k] = (uint32_t)p.copy_bytes;
+        isk[k] = vi.bit_skip[(size_t)k];
+        memcpy(ipr + k * 4, &vi.pred[(size_t)k * 4], 8);
       }
-    } else if (markers) {
-      // written by the search kernels; entries they leave alone (a search that is not good) must not send the Huffman kernel anywhere
-      memset(ib + first, 0, (size_t)nint * 4);
-      memset(ie + first, 0, (size_t)nint * 4);
-      MarkerImage &mi = ((MarkerImage *)(hp + off_mimg))[i];
-      MarkerResult &mr = ((MarkerResult *)(hp + off_mres))[i];
-      uint32_t chunk_at = i ? ((MarkerImage *)(hp + off_mimg))[i - 1].first_chunk + ((MarkerImage *)(hp + off_mimg))[i - 1].n_chunks : 0;
-      mi.raw_off = (uint32_t)stream_off[(size_t)i];
-      mi.size = (uint32_t)usize[(size_t)i];
-      mi.dst_off = (uint32_t)stream_off[(size_t)i];
-      mi.dst_cap = (uint32_t)((i + 1 < n ? stream_off[(size_t)i + 1] : stream_bytes) - stream_off[(size_t)i]);
-      mi.first_interval = (uint32_t)first;
-      mi.expect = (uint32_t)nint;
-      mi.first_chunk = chunk_at;
-      mi.n_chunks = markers_chunks(usize[(size_t)i]);
-      MarkerChunk *mc = (MarkerChunk *)(hp + off_mchunk) + chunk_at;
-      for (uint32_t k = 0; k < mi.n_chunks; k++) mc[k] = MarkerChunk{(uint32_t)i, k};
-      mr.flags = 0;
-      mr.term = mi.size;
-      mr.total = mr.markers = 0;
-    } else if (single[(size_t)i]) {
-      ib[first] = 0;
-      ie[first] = (uint32_t)usize[(size_t)i];
-      if (any_virtual) hp[off_isk + first] = 0;
-    } else {
-      memcpy(ib + first, s.interval_ubegin.data(), (size_t)nint * 4);
-      memcpy(ie + first, s.interval_uend.data(), (size_t)nint * 4);
-      if (any_virtual) memset(hp + off_isk + first, 0, (size_t)nint);
+      break;
     }
-    HuffDevTable *tabs = (HuffDevTable *)(hp + off_tab + (size_t)i * table_blob);
-    HuffDevAux *aux = (HuffDevAux *)(tabs + ntab);
-    // images that bring the tables of the image in front of them (every frame of a camera or an encoder run does) share its
-    // blob: nothing to build, and the workgroups of both read the same lines
+    case IntervalSource::MarkerSearch: {
+      // written by the search kernels; entries they leave alone (a search that is not good) must not send the Huffman kernel anywhere
+      memset(ib, 0, (size_t)nint * 4);
+      memset(ie, 0, (size_t)nint * 4);
+      MarkerImage *mi = (MarkerImage *)(hp + l.mimages);
+      const uint32_t chunk_at = i ? mi[i - 1].first_chunk + mi[i - 1].n_chunks : 0;
+      // {raw_off, size, dst_off, dst_cap, first_interval, expect, first_chunk}
+      stage_marker_image(mi[i], (MarkerChunk *)(hp + l.mchunks), ((MarkerResult *)(hp + l.mresults))[i], (uint32_t)i,
+                         MarkerImage{(uint32_t)p.slot_off, (uint32_t)p.copy_bytes, (uint32_t)p.slot_off, (uint32_t)(plan.slot_end(i) - p.slot_off), (uint32_t)first,
+                                     (uint32_t)nint, chunk_at, 0});
+      break;
+    }
+    case IntervalSource::WholeScan:
+      ib[0] = 0;
+      ie[0] = (uint32_t)p.copy_bytes;
+      if (isk) isk[0] = 0;
+      break;
+    case IntervalSource::RestartMarkers:
+      memcpy(ib, s.interval_ubegin.data(), (size_t)nint * 4);
+      memcpy(ie, s.interval_uend.data(), (size_t)nint * 4);
+      if (isk) memset(isk, 0, (size_t)nint);
+      break;
+    }
+  }
+
+  // ... its Huffman tables and dequantisation words; returns where they lie in the table region.  Images that bring the tables of the
+  // image in front of them (every frame of a camera or an encoder run does) share its blob, at `table_off_in_front`: nothing to build,
+  // and the workgroups of both read the same lines
+  uint32_t tables(HostDecoder *const *hosts, int i, const TableSlots &slots, uint32_t table_off_in_front) const
+  {
+    const mijpeg_info &f = hosts[i]->info;
+    const Scan &s = hosts[i]->scans[0];
+    HuffDevTable *tabs = (HuffDevTable *)(hp + l.tables + (size_t)i * slots.blob_bytes());
+    HuffDevAux *aux = (HuffDevAux *)(tabs + slots.ntab);
     bool same_tables = i > 0;
     if (same_tables) {
       const mijpeg_info &fp = hosts[i - 1]->info;
@@ -727,11 +859,10 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
       }
     }
     memset(aux, 0, sizeof(*aux));
-    for (int k = 0; k < s.ncomp && !same_tables; k++) {
-      const HuffTable *src[2] = {&s.dc[k], &s.ac[k]};
-      for (int t = 0; t < 2; t++) {
-        build_dev_table(tabs[tab_slot[k][t]], *src[t], t);
-      }
+    if (same_tables) return table_off_in_front;
+    for (int k = 0; k < s.ncomp; k++) {
+      build_dev_table(tabs[slots.slot[k][0]], s.dc[k], 0);
+      build_dev_table(tabs[slots.slot[k][1]], s.ac[k], 1);
       const int c = s.sc[k].comp;
       const uint16_t *delta = f.quant[f.quant_index[c]];
       for (int z = 0; z < 80; z++) {
@@ -739,140 +870,181 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
         aux->zq[k][z] = ((uint32_t)delta[pos] << 16) | (pos * 2);
       }
     }
-    HuffImage &im = images[i];
-    im.stream_off = (uint32_t)stream_off[(size_t)i];
-    im.first_interval = (uint32_t)first;
-    im.n_intervals = (int32_t)nint;
-    im.restart_interval = dwalk[(size_t)i] ? dwalk[(size_t)i] : virt[(size_t)i] ? virt[(size_t)i]->mcus_per_interval : single[(size_t)i] ? s.mcus_x * s.mcus_y : s.restart_interval;
-    im.virt = (virt[(size_t)i] || dwalk[(size_t)i]) ? 1u : 0u;
+    return (uint32_t)((size_t)i * slots.blob_bytes());
+  }
+
+  // ... and its descriptor, its plane geometry (ragged launches) and its workgroups, from groups[g] on
+  void descriptors(int i, const mijpeg_info &f, const Scan &s, uint32_t table_off, int64_t coef_base, bool ragged, int64_t &g) const
+  {
+    const ImagePlan &p = plan.images[(size_t)i];
+    HuffImage &im = ((HuffImage *)(hp + l.images))[i];
+    im.stream_off = (uint32_t)p.slot_off;
+    im.first_interval = (uint32_t)p.first_interval;
+    im.n_intervals = (int32_t)p.n_intervals;
+    im.restart_interval = p.mcus_per_interval;
+    im.virt = p.virtual_intervals() ? 1u : 0u;
     im.reserved = 0;
     im.total_mcus = s.mcus_x * s.mcus_y;
     im.mcus_x = s.mcus_x;
-    im.coef_base = ragged ? ragged->coef_base[i] : (int64_t)i * frame_stride;
+    im.coef_base = coef_base;
+    im.table_off = table_off;
+    im.status_off = (uint32_t)(i * 8);
     if (ragged) {
-      HuffPlanes &pl = ((HuffPlanes *)(hp + off_planes))[i];
+      HuffPlanes &pl = ((HuffPlanes *)(hp + l.planes))[i];
       memset(&pl, 0, sizeof(pl));
       for (int k = 0; k < s.ncomp; k++) {
         pl.bw[k] = (uint32_t)f.blocks_w[s.sc[k].comp];
         pl.base[k] = (uint32_t)(f.coef_offset[s.sc[k].comp] >> 6);
       }
     }
-    im.table_off = same_tables ? images[i - 1].table_off : (uint32_t)((size_t)i * table_blob);
-    im.status_off = (uint32_t)(i * 8);
-    for (int64_t k = 0; k < nint; k += per_group) {
+    HuffGroup *groups = (HuffGroup *)(hp + l.groups);
+    for (int64_t k = 0; k < p.n_intervals; k += plan.per_group) {
       groups[g].image = (uint32_t)i;
       groups[g].first_interval = (uint32_t)k;
       g++;
     }
-    first += nint;
-    // an interleaved scan writes every block of every plane; a single-component scan of a frame whose only component
-    // has sampling factors > 1 leaves the MCU padding blocks untouched (they must read as zero)
-    if (s.ncomp == 1 && (s.mcus_x != f.blocks_w[s.sc[0].comp] || s.mcus_y != f.blocks_h[s.sc[0].comp])) needs_clear = true;
   }
-  // (the stores of a ragged launch lie between those of other launches: nothing to clear in one sweep, and no layout group holds such frames)
-  if (needs_clear && ragged) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "single components with sampling factors are not decoded in a ragged launch");
+};
+
+// Kernel arguments of the scan kernel: the regions of the layout in the object's buffer, the geometry the images share (image 0's)
+HuffScanArgs scan_args(const mijpeg_decoder *d, const HostDecoder &h0, const BatchPlan &plan, const TableSlots &slots, const BatchLayout &l, int16_t *coef_dev, bool ragged)
+{
+  const mijpeg_info &f0 = h0.info;
+  const Scan &s0 = h0.scans[0];
+  uint8_t *const dp = d->ent_dev + l.stream_bytes;
+  HuffScanArgs a;
+  memset(&a, 0, sizeof(a));
+  a.lanes = plan.lanes;
+  a.waves_per_group = WAVES_PER_GROUP;
   for (int k = 0; k < s0.ncomp; k++) {
     const int c = s0.sc[k].comp;
     a.comp_of[k] = c;
-    a.hs[k] = s0.ncomp > 1 ? f0.hsamp[c] : 1;
-    a.vs[k] = s0.ncomp > 1 ? f0.vsamp[c] : 1;
+    const McuBlocks b = mcu_blocks(f0, s0, k);
+    a.hs[k] = b.h;
+    a.vs[k] = b.v;
     a.bw[k] = f0.blocks_w[c];
     a.coef_off[k] = f0.coef_offset[c];
-    a.dc_tab[k] = tab_slot[k][0];
-    a.ac_tab[k] = tab_slot[k][1];
+    a.dc_tab[k] = slots.slot[k][0];
+    a.ac_tab[k] = slots.slot[k][1];
   }
   a.data = d->ent_dev;
-  a.ibegin = (const uint32_t *)(dp + off_ib);
-  a.iend = (const uint32_t *)(dp + off_ie);
-  a.iskip = dp + off_isk;
-  a.ipred = (const int16_t *)(dp + off_ipr);
-  a.images = (const HuffImage *)(dp + off_img);
-  a.groups = (const HuffGroup *)(dp + off_grp);
-  a.n_groups = (int32_t)n_groups;
+  a.ibegin = (const uint32_t *)(dp + l.ibegin);
+  a.iend = (const uint32_t *)(dp + l.iend);
+  a.iskip = dp + l.iskip;
+  a.ipred = (const int16_t *)(dp + l.ipred);
+  a.images = (const HuffImage *)(dp + l.images);
+  a.groups = (const HuffGroup *)(dp + l.groups);
+  a.n_groups = (int32_t)plan.n_groups;
   a.ncomp = s0.ncomp;
-  a.ntables = ntab;
-  a.tables = dp + off_tab;
+  a.ntables = slots.ntab;
+  a.tables = dp + l.tables;
   a.coef = coef_dev;
-  a.status = (uint32_t *)(dp + off_status);
-  a.planes = ragged ? (const HuffPlanes *)(dp + off_planes) : nullptr;
-  MarkerArgs ma;
-  memset(&ma, 0, sizeof(ma));
-  if (markers) {
-    uint8_t *const ms = dp + off_mscratch;
-    ma.raw = dp + off_raw;
-    ma.dst = d->ent_dev;
-    ma.ibegin = (uint32_t *)(dp + off_ib);
-    ma.iend = (uint32_t *)(dp + off_ie);
-    ma.images = (const MarkerImage *)(dp + off_mimg);
-    ma.chunks = (const MarkerChunk *)(dp + off_mchunk);
-    ma.kept = (uint32_t *)(ms + mscratch.kept);
-    ma.marks = (uint32_t *)(ms + mscratch.marks);
-    ma.kept_at = (const uint64_t *)(ms + mscratch.kept_at);
-    ma.marks_at = (const uint64_t *)(ms + mscratch.marks_at);
-    ma.results = (MarkerResult *)(dp + off_mres);
-  }
-  // the search of images [g0, g1) on the object's stream, behind their upload
-  auto search_images = [&](int g0, int g1) -> int {
-    const MarkerImage *mi = (const MarkerImage *)(hp + off_mimg);
-    MarkerArgs part = ma;
-    part.chunk0 = mi[g0].first_chunk;
-    part.n_chunks = mi[g1 - 1].first_chunk + mi[g1 - 1].n_chunks - part.chunk0;
-    if (launch_marker_search(part, (uint64_t *)(dp + off_mscratch + mscratch.scan), mscratch.scan_words, d->stream))
-      return hip_fail(d, hipGetLastError(), "marker search launch");
-    return MIJPEG_OK;
-  };
-  const TraceMarks mark{"mijpeg"};
-  const auto tb1 = mark.t0;
-  QuiesceOnError guard{d};
-  guard.armed = true;
-  HIP_TRY(d, hipMemcpyAsync(dp, hp, off_status, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(d, hipMemsetAsync(dp + off_status, 0, status_bytes, d->stream));
-  if (needs_clear) HIP_TRY(d, hipMemsetAsync(coef_dev, 0, (size_t)n * (size_t)frame_stride * sizeof(int16_t), d->stream));
-  // (a deferred batch always goes through the pinned gathering area: the caller's bytes are only read during the call)
-  const bool small = !defer && (n == 1 || stream_bytes < ((size_t)8 << 20));
-  if ((rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, stream_bytes))) return rc;
+  a.status = (uint32_t *)(dp + l.status);
+  a.planes = ragged ? (const HuffPlanes *)(dp + l.planes) : nullptr;
+  return a;
+}
+
+// Enqueue: the streams of the images go up and the kernels are launched behind them, on d->stream and d->copy_stream
+struct Enqueue {
+  mijpeg_decoder *d;
+  HostDecoder *const *hosts;
+  const uint8_t *const *datas;
+  const BatchPlan &plan;
+  const BatchLayout &l;
+  const HuffScanArgs &scan;
+  const MarkerArgs &search; // (the marker route)
+  const EntropyBatchOptions &opt;
+  const TraceMarks &mark;
+  Gather gather;
+
+  uint8_t *tail_dev() const { return d->ent_dev + l.stream_bytes; }
+
   // the unstuffing gather of images [g0, g1) into the pinned area (images whose marker search wrote the copy already -- a
   // batch's workers do, set_unstuff_sink -- have nothing left to do)
-  Gather gather;
-  auto gather_images = [&](int g0, int g1) {
-    if (markers) { // one memcpy per image: the raw segment into its slot
-      auto copy = [&](int i) { memcpy(d->stage_host + stream_off[(size_t)i], datas[i] + hosts[i]->scans[0].ecs_begin, usize[(size_t)i]); };
+  void gather_images(int g0, int g1)
+  {
+    if (opt.markers) { // one memcpy per image: the raw segment into its slot
+      auto copy = [&](int i) { memcpy(d->stage_host + plan.images[(size_t)i].slot_off, datas[i] + hosts[i]->scans[0].ecs_begin, plan.images[(size_t)i].copy_bytes); };
       if (g1 - g0 > 1) parallel_for(g1 - g0, [&](int k) { copy(g0 + k); });
       else copy(g0);
       return;
     }
-    for (int i = g0; i < g1; i++)
-      if (hosts[i]->scans[0].unstuffed_at != d->stage_host + stream_off[(size_t)i]) gather.add(hosts[i], 0, d->stage_host + stream_off[(size_t)i]);
-    gather.run();
-  };
-  // streams without restart markers: the walk finds the intervals of every image, then one launch decodes them all
-  auto walk_and_decode = [&]() {
-    const int wrc = device_walk_images(d, hosts, n, dwalk, a, (const HuffImage *)(dp + off_img), (uint32_t *)(dp + off_ib), dp + off_isk,
-                                       (int16_t *)(dp + off_ipr), images, usize, defer, ragged != nullptr,
-                                       ragged ? ragged->walk_launches : nullptr);
-    if (wrc) return wrc;
-    mark("device walk enqueued");
-    if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
-    if (ragged) ++*ragged->entropy_launches;
-    return MIJPEG_OK;
-  };
-  if (small) {
-    gather_images(0, n);
-    // (only what the copies occupy: a slot is as large as its stream, headers and all)
-    for (int i = 0; i < n && !markers; i++)
-      HIP_TRY(d, hipMemcpyAsync(d->ent_dev + stream_off[(size_t)i], d->stage_host + stream_off[(size_t)i], ((usize[(size_t)i] + 15) & ~(size_t)15) + HUFF_STREAM_PAD,
-                                hipMemcpyHostToDevice, d->stream));
-    for (int i = 0; i < n && markers; i++)
-      if (usize[(size_t)i])
-        HIP_TRY(d, hipMemcpyAsync(dp + off_raw + stream_off[(size_t)i], d->stage_host + stream_off[(size_t)i], usize[(size_t)i], hipMemcpyHostToDevice, d->stream));
-    if (markers && (rc = search_images(0, n))) return rc;
-    if (any_dwalk) {
-      if ((rc = walk_and_decode())) return rc;
-    } else {
-      if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
-      if (ragged) ++*ragged->entropy_launches;
+    for (int i = g0; i < g1; i++) {
+      uint8_t *const slot = d->stage_host + plan.images[(size_t)i].slot_off;
+      if (hosts[i]->scans[0].unstuffed_at != slot) gather.add(hosts[i], 0, slot);
     }
-  } else {
+    gather.run();
+  }
+
+  // the upload of images [g0, g1) from the pinned area.  Without `done`: on the object's stream, image by image, only what the
+  // copies occupy (a slot is as large as its stream, headers and all).  With it: their slots in one copy on the copy stream,
+  // `done` recorded behind it, and the object's stream waits for that.
+  int upload_images(int g0, int g1, hipEvent_t done = nullptr)
+  {
+    uint8_t *const dst = opt.markers ? tail_dev() + l.raw : d->ent_dev; // (the marker route: the raw segments, the search writes the copies)
+    if (done) {
+      const size_t b0 = plan.images[(size_t)g0].slot_off, b1 = plan.slot_end(g1 - 1);
+      HIP_TRY(d, hipMemcpyAsync(dst + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
+      HIP_TRY(d, hipEventRecord(done, d->copy_stream));
+      HIP_TRY(d, hipStreamWaitEvent(d->stream, done, 0));
+      return MIJPEG_OK;
+    }
+    for (int i = g0; i < g1; i++) {
+      const ImagePlan &p = plan.images[(size_t)i];
+      const size_t bytes = opt.markers ? p.copy_bytes : ((p.copy_bytes + 15) & ~(size_t)15) + HUFF_STREAM_PAD;
+      if (bytes) HIP_TRY(d, hipMemcpyAsync(dst + p.slot_off, d->stage_host + p.slot_off, bytes, hipMemcpyHostToDevice, d->stream));
+    }
+    return MIJPEG_OK;
+  }
+
+  // the marker search of images [g0, g1) on the object's stream, behind their upload
+  int search_images(int g0, int g1)
+  {
+    const MarkerImage *mi = (const MarkerImage *)(d->ent_host + l.mimages);
+    MarkerArgs part = search;
+    part.chunk0 = mi[g0].first_chunk;
+    part.n_chunks = mi[g1 - 1].first_chunk + mi[g1 - 1].n_chunks - part.chunk0;
+    if (launch_marker_search(part, (uint64_t *)(tail_dev() + l.mscratch + l.scratch.scan), l.scratch.scan_words, d->stream))
+      return hip_fail(d, hipGetLastError(), "marker search launch");
+    return MIJPEG_OK;
+  }
+
+  // the scan kernel for workgroups [wg0, wg1) of the launch
+  int launch_scan(int64_t wg0, int64_t wg1)
+  {
+    HuffScanArgs part = scan;
+    part.groups = scan.groups + wg0;
+    part.n_groups = (int32_t)(wg1 - wg0);
+    if (launch_huffman_scan(part, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
+    if (opt.ragged) ++*opt.ragged->entropy_launches;
+    return MIJPEG_OK;
+  }
+
+  // every image in one launch; streams without restart markers: the walk finds the intervals of every image first
+  int decode_all()
+  {
+    if (plan.any_dwalk) {
+      uint8_t *const dp = tail_dev();
+      const int rc = device_walk_images(d, hosts, plan, opt, scan, DeviceIntervals{(uint32_t *)(dp + l.ibegin), dp + l.iskip, (int16_t *)(dp + l.ipred)});
+      if (rc) return rc;
+      mark("device walk enqueued");
+    }
+    return launch_scan(0, plan.n_groups);
+  }
+
+  int run()
+  {
+    const int n = plan.n();
+    int rc;
+    // (a deferred batch always goes through the pinned gathering area: the caller's bytes are only read during the call)
+    const bool small = !opt.defer && (n == 1 || plan.stream_bytes < ((size_t)8 << 20));
+    if ((rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, plan.stream_bytes))) return rc;
+    if (small) {
+      gather_images(0, n);
+      if ((rc = upload_images(0, n))) return rc;
+      if (opt.markers && (rc = search_images(0, n))) return rc;
+      return decode_all();
+    }
     // large batches, in up to eight groups of images: the pool threads gather a group's streams into pinned memory, its
     // DMA runs on a copy stream while the next group is gathered and while the kernel decodes the previous one
     mark("staging buffer ready");
@@ -880,79 +1052,147 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
     // ~0.3 ms) until it holds several waves per SIMD: ~128 K restart intervals; more, smaller launches only pay when the
     // batch is so large that the upload of one part hides behind the decode of another (profiles/r02/batch4k_*.txt:
     // 32 x 4K frames in one launch 0.80 ms, in eight launches of four 8 x 0.39 ms).
-    const int64_t per_image = std::max<int64_t>(1, total_intervals / n);
+    const int64_t per_image = std::max<int64_t>(1, plan.total_intervals / n);
     const int groups_of = (int)std::max<int64_t>(std::max(4, (n + 7) / 8), (131072 + per_image - 1) / per_image);
     if ((rc = prepare_copy_stream(d, (size_t)((n + groups_of - 1) / groups_of)))) return rc;
+    // the walk covers all images at once; a ragged group is one launch by contract
+    const bool launch_per_group = !plan.any_dwalk && !opt.ragged;
     int64_t wg0 = 0;
     for (int gi = 0, g0 = 0; g0 < n; g0 += groups_of, gi++) {
       const int g1 = std::min(n, g0 + groups_of);
       gather_images(g0, g1);
-      const size_t b0 = stream_off[(size_t)g0], b1 = g1 < n ? stream_off[(size_t)g1] : stream_bytes;
-      HIP_TRY(d, hipMemcpyAsync((markers ? dp + off_raw : d->ent_dev) + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
-      HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)gi], d->copy_stream));
-      HIP_TRY(d, hipStreamWaitEvent(d->stream, d->copy_events[(size_t)gi], 0));
-      if (markers && (rc = search_images(g0, g1))) return rc;
-      if (any_dwalk || ragged) continue; // the walk below covers all images at once; a ragged group is one launch by contract
+      if ((rc = upload_images(g0, g1, d->copy_events[(size_t)gi]))) return rc;
+      if (opt.markers && (rc = search_images(g0, g1))) return rc;
+      if (!launch_per_group) continue;
       int64_t wg1 = wg0;
-      for (int i = g0; i < g1; i++) wg1 += (nints[(size_t)i] + per_group - 1) / per_group;
-      HuffScanArgs part = a; // the workgroups of this group's images
-      part.groups = a.groups + wg0;
-      part.n_groups = (int32_t)(wg1 - wg0);
-      if (launch_huffman_scan(part, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
-      if (ragged) ++*ragged->entropy_launches;
+      for (int i = g0; i < g1; i++) wg1 += plan.groups_of(i);
+      if ((rc = launch_scan(wg0, wg1))) return rc; // the workgroups of this group's images
       wg0 = wg1;
     }
     mark("groups gathered + enqueued");
-    if (any_dwalk && (rc = walk_and_decode())) return rc;
-    if (ragged && !any_dwalk) {
-      if (launch_huffman_scan(a, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_scan_kernel launch");
-      if (ragged) ++*ragged->entropy_launches;
-    }
+    return launch_per_group ? MIJPEG_OK : decode_all();
   }
-  uint32_t *status_host = (uint32_t *)(hp + off_status);
-  uint32_t *walk_status_host = (uint32_t *)d->walk_host; // the walk's staging buffer is free again
-  if (any_dwalk) HIP_TRY(d, hipMemcpyAsync(walk_status_host, d->walk_status_dev, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
+};
+
+// Read back: the walk's status words, the marker results and the status words (pinned); the deferred hand-over or the verdict
+struct ReadBack {
+  uint32_t *status, *walk_status; // walk_status: null without a device walk
+  const uint32_t *markers;        // null off the marker route
+};
+int read_back(mijpeg_decoder *d, const BatchPlan &plan, const BatchLayout &l, const EntropyBatchOptions &opt, ReadBack &back)
+{
+  uint8_t *const hp = d->ent_host, *const dp = d->ent_dev + l.stream_bytes;
+  const int n = plan.n();
+  back.status = (uint32_t *)(hp + l.status);
+  back.walk_status = plan.any_dwalk ? (uint32_t *)d->walk_host : nullptr; // the walk's staging buffer is free again
+  back.markers = opt.markers ? (const uint32_t *)(hp + l.mresults) : nullptr;
+  if (plan.any_dwalk) HIP_TRY(d, hipMemcpyAsync(back.walk_status, d->walk_status_dev, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream));
   // (the marker route's result words lie right in front of the status words: one copy)
-  if ((rc = read_back_status(d, (uint32_t *)(hp + off_mres), dp + off_mres, off_status - off_mres + status_bytes))) return rc;
+  if (const int rc = read_back_status(d, (uint32_t *)(hp + l.mresults), dp + l.mresults, l.read_back_bytes())) return rc;
   d->pend_markers = nullptr;
-  if (markers) {
+  if (opt.markers) {
     d->markers_want_term.resize((size_t)n);
-    for (int i = 0; i < n; i++) d->markers_want_term[(size_t)i] = (uint32_t)usize[(size_t)i] - 2u;
+    for (int i = 0; i < n; i++) d->markers_want_term[(size_t)i] = (uint32_t)plan.images[(size_t)i].copy_bytes - 2u;
   }
+  return MIJPEG_OK;
+}
+
+// mijpeg_submit_batch_device: the caller waits later (finish_batch)
+void hand_over(mijpeg_decoder *d, int n, const ReadBack &back, std::chrono::steady_clock::time_point t0)
+{
+  d->pend_n = n;
+  d->pend_status = back.status;
+  d->pend_walk_status = back.walk_status;
+  d->pend_markers = back.markers;
+  d->pend_t0 = t0;
+}
+
+// What the words that came back say, once the stream is idle
+int verdict(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const ReadBack &back, const EntropyBatchOptions &opt)
+{
+  if (opt.ragged) {
+    // image by image: one that the walk or the kernel found damaged goes to the single-image route, the others stand
+    for (int i = 0; i < n; i++) {
+      HostDecoder *h = hosts[i];
+      const bool bad = (back.walk_status && back.walk_status[i]) || evaluate_entropy_status(d, &h, 1, back.status + 8 * i) != MIJPEG_OK;
+      opt.ragged->verdict[i] = bad ? 1 : 0;
+    }
+    return MIJPEG_OK;
+  }
+  if (opt.markers) {
+    if (!device_markers_good(back.markers, d->markers_want_term.data(), n)) {
+      d->markers_retry = true;
+      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: the segment is not the plain case; the host searches it");
+    }
+    for (int i = 0; i < n; i++) hosts[i]->scans[0].unstuffed_size = ((const MarkerResult *)back.markers)[i].total;
+  }
+  if (back.walk_status)
+    if (const int rc = walk_verdict(d, back.walk_status, n)) return rc;
+  return evaluate_entropy_status(d, hosts, n, back.status);
+}
+
+} // namespace
+
+// Entropy-decode n parsed images on the device with one launch of huffman_scan_kernel (large uniform batches: one per upload
+// group).  Without opt.ragged: images of identical frame geometry, image i into coef_dev + i * frame_stride.  With it: images that
+// share components and sampling factors but not their size, image i into coef_dev + ragged->coef_base[i], plane geometry per
+// image; a damaged image is reported in ragged->verdict[i] instead of failing the call.
+// opt.markers: the streams were parsed without a marker search (device_markers_obstacle holds for each): their raw segments go up,
+// and the search kernels write the copies and the interval tables in front of the Huffman launch.  On a search that is not
+// good the call answers MIJPEG_ERR_NOT_AVAILABLE with d->markers_retry set (deferred: mijpeg_finish_batch_device looks).
+// hosts[i]->info receives fast_arith / range_max.  Returns MIJPEG_OK, MIJPEG_ERR_NOT_AVAILABLE (nothing touched) or an error.
+int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
+                         int min_intervals, int16_t *coef_dev, int64_t frame_stride, const EntropyBatchOptions &opt)
+{
+  if (opt.markers && (opt.ragged || opt.xt_part)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: uniform batches of plain streams only");
+  const auto tb0 = std::chrono::steady_clock::now();
+  int rc;
+  BatchPlan plan;
+  if ((rc = plan_batch(d, hosts, sizes, n, min_intervals, opt, plan))) return rc;
+  const TableSlots slots = share_table_slots(hosts, n, plan.any_dwalk);
+  BatchLayout l;
+  if (const char *why = batch_layout(plan, slots.blob_bytes(), opt, l)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
+  if ((rc = ensure_entropy_buffers(d, l.stream_bytes, l.tail_bytes, l.device_extra()))) return rc;
+  uint8_t *const hp = d->ent_host, *const dp = d->ent_dev + l.stream_bytes;
+  const Staging staging{plan, l, hp};
+  int64_t g = 0;
+  uint32_t table_off = 0;
+  for (int i = 0; i < n; i++) {
+    const Scan &s = hosts[i]->scans[0];
+    staging.intervals(i, s, datas[i]);
+    table_off = staging.tables(hosts, i, slots, table_off);
+    staging.descriptors(i, hosts[i]->info, s, table_off, opt.ragged ? opt.ragged->coef_base[i] : (int64_t)i * frame_stride, opt.ragged != nullptr, g);
+  }
+  const HuffScanArgs scan = scan_args(d, *hosts[0], plan, slots, l, coef_dev, opt.ragged != nullptr);
+  MarkerArgs search;
+  memset(&search, 0, sizeof(search));
+  if (opt.markers)
+    search = marker_args(dp + l.raw, d->ent_dev, (uint32_t *)(dp + l.ibegin), (uint32_t *)(dp + l.iend), (const MarkerImage *)(dp + l.mimages),
+                         (const MarkerChunk *)(dp + l.mchunks), (MarkerResult *)(dp + l.mresults), dp + l.mscratch, l.scratch);
+  const TraceMarks mark{"mijpeg"};
+  const auto tb1 = mark.t0;
+  QuiesceOnError guard{d};
+  guard.armed = true;
+  HIP_TRY(d, hipMemcpyAsync(dp, hp, l.upload_bytes(), hipMemcpyHostToDevice, d->stream));
+  HIP_TRY(d, hipMemsetAsync(dp + l.status, 0, l.status_bytes, d->stream));
+  if (plan.needs_clear) HIP_TRY(d, hipMemsetAsync(coef_dev, 0, (size_t)n * (size_t)frame_stride * sizeof(int16_t), d->stream));
+  Enqueue enqueue{d, hosts, datas, plan, l, scan, search, opt, mark, Gather{}};
+  if ((rc = enqueue.run())) return rc;
+  ReadBack back;
+  if ((rc = read_back(d, plan, l, opt, back))) return rc;
   d->phase_prepare = std::chrono::duration<double>(tb1 - tb0).count(); // interval tables, Huffman tables
   mark("status copies enqueued");
-  if (!any_dwalk) d->pend_walk_round = 0;
-  if (defer) { // mijpeg_submit_batch_device: the caller waits later (finish_batch)
+  if (!plan.any_dwalk) d->pend_walk_round = 0;
+  if (opt.defer) {
     guard.armed = false;
-    d->pend_n = n;
-    d->pend_status = status_host;
-    d->pend_walk_status = any_dwalk ? walk_status_host : nullptr;
-    d->pend_markers = markers ? (const uint32_t *)(hp + off_mres) : nullptr;
-    d->pend_t0 = tb1;
+    hand_over(d, n, back, tb1);
     d->phase_device = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count(); // so far: gathering + enqueueing
     return MIJPEG_OK;
   }
   HIP_TRY(d, hipStreamSynchronize(d->stream));
   guard.armed = false; // (everything of this call is behind the stream's last copy)
   d->phase_device = std::chrono::duration<double>(std::chrono::steady_clock::now() - tb1).count();  // upload + kernel + status
-  if (ragged) {
-    // image by image: one that the walk or the kernel found damaged goes to the single-image route, the others stand
-    for (int i = 0; i < n; i++) {
-      HostDecoder *h = hosts[i];
-      const bool bad = (any_dwalk && walk_status_host[i]) || evaluate_entropy_status(d, &h, 1, status_host + 8 * i) != MIJPEG_OK;
-      ragged->verdict[i] = bad ? 1 : 0;
-    }
-    return MIJPEG_OK;
-  }
-  if (markers) {
-    if (!device_markers_good((const uint32_t *)(hp + off_mres), d->markers_want_term.data(), n)) {
-      d->markers_retry = true;
-      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: the segment is not the plain case; the host searches it");
-    }
-    for (int i = 0; i < n; i++) hosts[i]->scans[0].unstuffed_size = ((const MarkerResult *)(hp + off_mres))[i].total;
-  }
-  if (any_dwalk && (rc = walk_verdict(d, walk_status_host, n))) return rc;
-  return evaluate_entropy_status(d, hosts, n, status_host);
+  return verdict(d, hosts, n, back, opt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -962,19 +1202,14 @@ int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uin
 const char *multiscan_obstacle(const HostDecoder &h, bool xt_part, bool residual_frame)
 {
   const mijpeg_info &f = h.info;
-  if (h.needs_sequential())
-    return "on-device entropy decoding: the stream is damaged; the host decoder walks it with the reference's resynchronisation (entropyparser.cpp:117-201)";
-  if (f.xt && !xt_part) return "on-device entropy decoding: not for this JPEG XT stream";
-  if (!h.residual_merged()) return "on-device entropy decoding: the legacy codestream has no EOI marker (the host decoder decides what is merged)";
-  if (h.verdict_pending()) return "on-device entropy decoding: the file's verdict is the host decoder's (residual codestream header / tables looked up at the first request)";
+  if (const char *why = stream_obstacle(h, xt_part, false)) return why;
   if (f.dnl) return "on-device entropy decoding: frames whose height arrives in a DNL marker are decoded on the host";
   // (12-bit frames: the same int16 store as the host decoder's, a coefficient beyond it sends the frame there like everywhere)
   if (f.precision < 8 || f.precision > 12 || (xt_part && !residual_frame && f.precision != 8))
     return "on-device entropy decoding: frames of 8 to 12 bits (JPEG XT: an 8-bit legacy frame)";
   if (h.scans.empty() || h.scans.size() > 4096) return "on-device entropy decoding: no scans, or more than the device path plans for";
   if (!h.every_component_seen()) return "on-device entropy decoding: a component appears in no scan (the host decoder supplies its stand-in)";
-  for (int c = 0; c < f.components; c++)
-    if (f.hsamp[c] > 4 || f.vsamp[c] > 4) return "on-device entropy decoding: MCUs of more than 4 x 4 blocks of a component are decoded on the host";
+  if (const char *why = sampling_obstacle(f)) return why;
   for (size_t si = 0; si < h.scans.size(); si++) {
     const Scan &s = h.scans[si];
     if (s.residual) return "on-device entropy decoding: the residual scan types of part 8 are decoded on the host";
@@ -985,13 +1220,9 @@ const char *multiscan_obstacle(const HostDecoder &h, bool xt_part, bool residual
     if (total_mcus < 1 || total_mcus > 0x7fffffff) return "on-device entropy decoding: scan layout";
     if (s.restart_interval > 0) {
       const int64_t nint = (total_mcus + s.restart_interval - 1) / s.restart_interval;
-      if ((int64_t)s.interval_begin.size() < nint || (int64_t)s.interval_ubegin.size() < nint)
+      if ((int64_t)s.interval_ubegin.size() < nint) // (the copy's interval table is the one that goes up)
         return "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
-      const std::vector<uint8_t> &rst = h.restart_codes(si);
-      if ((int64_t)rst.size() + 1 < nint) return "restart markers missing: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
-      for (int64_t k = 0; k + 1 < nint; k++)
-        if (rst[(size_t)k] != 0xd0 + (k & 7))
-          return "restart markers out of sequence: the host decoder resynchronises like the reference (entropyparser.cpp:117-201)";
+      if (const char *why = restart_markers_obstacle(h, si)) return why;
     } else {
       // One interval: one lane decodes the whole scan.  First passes could be cut into pieces that fall into step with the real
       // decoder; an AC refinement scan cannot -- the bits a block takes depend on which block it is -- so scans
@@ -1140,8 +1371,9 @@ int device_entropy_multiscan(mijpeg_decoder *d, const MultiScanFrame *frames, in
     for (int k = 0; k < s.ncomp; k++) {
       const int c = s.sc[k].comp;
       o.comp[k] = c;
-      o.hs[k] = s.ncomp > 1 ? f.hsamp[c] : 1;
-      o.vs[k] = s.ncomp > 1 ? f.vsamp[c] : 1;
+      const McuBlocks b = mcu_blocks(f, s, k);
+      o.hs[k] = b.h;
+      o.vs[k] = b.v;
       o.bw[k] = f.blocks_w[c];
       o.coef_off[k] = f.coef_offset[c] / (f.coef_wide ? 2 : 1);
       o.dc_tab[k] = it.dc_tab[k];
@@ -1296,35 +1528,14 @@ int64_t device_marker_search(mijpeg_decoder *d, const uint8_t *segment, size_t s
   uint8_t *const hp = d->ent_host, *const dp = d->ent_dev;
   memset(hp, PATTERN, o_up_end); // (the regions the kernels write start out as the pattern too: what they leave alone shows)
   if (size) memcpy(hp + o_raw, segment, size);
-  MarkerImage &im = *(MarkerImage *)(hp + o_img);
-  im.raw_off = (uint32_t)o_raw;
-  im.size = (uint32_t)size;
-  im.dst_off = (uint32_t)o_dst;
-  im.dst_cap = (uint32_t)capacity;
-  im.first_interval = 0;
-  im.expect = (uint32_t)expect;
-  im.first_chunk = 0;
-  im.n_chunks = C;
-  for (uint32_t k = 0; k < C; k++) ((MarkerChunk *)(hp + o_chunk))[k] = MarkerChunk{0, k};
   MarkerResult &res = *(MarkerResult *)(hp + o_res);
-  res.flags = 0;
-  res.term = (uint32_t)size;
-  res.total = res.markers = 0;
-  MarkerArgs a;
-  memset(&a, 0, sizeof(a));
-  a.raw = dp;
-  a.dst = dp;
-  a.ibegin = (uint32_t *)(dp + o_begin);
-  a.iend = (uint32_t *)(dp + o_end);
-  a.images = (const MarkerImage *)(dp + o_img);
-  a.chunks = (const MarkerChunk *)(dp + o_chunk);
+  // {raw_off, size, dst_off, dst_cap, first_interval, expect, first_chunk}
+  stage_marker_image(*(MarkerImage *)(hp + o_img), (MarkerChunk *)(hp + o_chunk), res, 0,
+                     MarkerImage{(uint32_t)o_raw, (uint32_t)size, (uint32_t)o_dst, (uint32_t)capacity, 0, (uint32_t)expect, 0, 0});
+  MarkerArgs a = marker_args(dp, dp, (uint32_t *)(dp + o_begin), (uint32_t *)(dp + o_end), (const MarkerImage *)(dp + o_img), (const MarkerChunk *)(dp + o_chunk),
+                             (MarkerResult *)(dp + o_res), dp + o_scratch, ms);
   a.chunk0 = 0;
   a.n_chunks = C;
-  a.kept = (uint32_t *)(dp + o_scratch + ms.kept);
-  a.marks = (uint32_t *)(dp + o_scratch + ms.marks);
-  a.kept_at = (const uint64_t *)(dp + o_scratch + ms.kept_at);
-  a.marks_at = (const uint64_t *)(dp + o_scratch + ms.marks_at);
-  a.results = (MarkerResult *)(dp + o_res);
   QuiesceOnError guard{d};
   guard.armed = true;
   HIP_TRY(d, hipMemcpyAsync(dp, hp, o_up_end, hipMemcpyHostToDevice, d->stream));

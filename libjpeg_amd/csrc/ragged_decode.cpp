@@ -157,7 +157,9 @@ try {
     }
     int scan_launches = 0, walk_launches = 0;
     const RaggedEntropy re{bases.data(), verdict.data(), &scan_launches, &walk_launches};
-    const int rc = device_entropy_batch(d, hosts.data(), datas.data(), gsizes.data(), (int)m, 1, d->coef_dev, 0, false, false, &re);
+    EntropyBatchOptions opt;
+    opt.ragged = &re;
+    const int rc = device_entropy_batch(d, hosts.data(), datas.data(), gsizes.data(), (int)m, 1, d->coef_dev, 0, opt);
     d->ragged_stats.entropy_launches += scan_launches;
     d->ragged_stats.walk_launches += walk_launches;
     if (rc && rc != MIJPEG_ERR_NOT_AVAILABLE) return rc; // (the device, memory: not a verdict on a stream)

@@ -10,6 +10,7 @@ import pytest
 
 from conftest import BIG_CASES, MANIFEST, P12_CASES, SMALL_CASES, XT_CASES, big_jpeg, golden_jpeg, golden_pixels
 from libjpeg_amd import api, synth
+from route_streams import grey_2x2_jpeg, host_decodes, noise_jpeg
 
 pytestmark = pytest.mark.gpu
 
@@ -1257,6 +1258,70 @@ def test_batch_without_restart_markers(oracle, w, h, sub, n, mixed):
     for i in range(n):
         assert np.array_equal(res[i], oracle.decode(streams[i])), i
     d.close()
+
+
+@pytest.mark.parametrize("deferred", [False, True])
+def test_host_walk_in_uniform_batches(monkeypatch, deferred):
+    """MIJPEG_DEVICE_WALK=0 in a batch, in one call and submitted: the host plans every image's restart points, one launch decodes
+    them.  A batch's planes stay in HBM, so what is compared are the range check the Huffman kernel reports and the pixels, both
+    with the host decoder's."""
+    torch = _torch()
+    monkeypatch.setenv("MIJPEG_DEVICE_WALK", "0")
+    w = h = 256
+    streams = [noise_jpeg(w, h, 40 + i) for i in range(3)]
+    want = host_decodes(streams)
+    d = api.Decoder(0)
+    if deferred:
+        d.submit_batch_device(streams, 1)
+        info = d.finish_batch_device()
+    else:
+        info = d.decode_batch_device(streams, min_intervals=1)
+    assert d.device_walk_rounds() == 0
+    assert list(info.range_max)[:3] == [max(x[1][c] for x in want) for c in range(3)]
+    out = torch.zeros((3, h, w * 3), dtype=torch.uint8, device="cuda")
+    d.reconstruct_batch_device(out.data_ptr(), h * w * 3, w * 3)
+    res = out.cpu().numpy().reshape(3, h, w, 3)
+    for i in range(3):
+        assert np.array_equal(res[i], want[i][0]), i
+    d.close()
+
+
+def test_single_component_with_sampling_factors_on_the_device(dec):
+    """A frame whose only component has sampling factors 2 x 2, 40 x 24: its scan covers 5 x 3 blocks of planes that hold 6 x 4,
+    and the blocks it leaves out must read as zero although the store held another picture's coefficients."""
+    data = grey_2x2_jpeg(40, 24, 5, 2)
+    host = api.Decoder(0)
+    hi = host.read(data)
+    want = host.coefficients(0)
+    assert want.shape[:2] == (4, 6) and want[:3, :5].any() and not want[:, 5].any() and not want[3].any()
+    dec.read(noise_jpeg(64, 48, 9, restart_mcus=1), entropy="gpu")  # (what the store holds before)
+    assert dec.entropy_used == "gpu" and dec.coefficients(0).reshape(-1, 64)[:24].any(axis=1).all()  # (the 24 blocks the planes will lie on)
+    gi = dec.read(data, entropy="gpu")
+    assert dec.entropy_used == "gpu"
+    assert np.array_equal(dec.coefficients(0), want)
+    assert list(gi.range_max) == list(hi.range_max) and gi.fast_arith == hi.fast_arith
+    assert np.array_equal(dec.reconstruct(), host.reconstruct())
+    host.close()
+
+
+def test_xt_codestreams_with_restart_markers_on_the_device(dec):
+    """Both codestreams of a JPEG XT profile C file (8-bit legacy frame 4:2:0, 12-bit residual frame, restart markers every two
+    MCUs in each, no hidden bits) through the sequential device decoder, the residual one on the helper object: planes of both
+    frames, range checks and codes equal the host decoder's."""
+    data = golden_jpeg("profile_c_129x71_420_dri2")
+    host = api.Decoder(0)
+    hi = host.read(data)
+    assert hi.xt and not hi.progressive and not host.xt_params().residual_wide
+    gi = dec.read(data, entropy="gpu")
+    assert dec.entropy_used == "gpu" and dec.device_walk_rounds() == 0
+    assert list(gi.range_max) == list(hi.range_max)
+    assert list(dec.xt_params().residual.range_max) == list(host.xt_params().residual.range_max)
+    codes = dec.reconstruct()  # (before the planes are fetched: the device copy is what the kernels read)
+    assert np.array_equal(codes, host.reconstruct())
+    for c in range(3):
+        assert np.array_equal(dec.coefficients(c), host.coefficients(c)), c
+        assert np.array_equal(dec.residual_coefficients(c), host.residual_coefficients(c)), c
+    host.close()
 
 
 def test_device_walk_on_damaged_streams_agrees_with_the_host(dec):

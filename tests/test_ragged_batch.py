@@ -20,6 +20,7 @@ import pytest
 
 from conftest import ROOT, golden_jpeg
 from libjpeg_amd import api, synth
+from route_streams import grey_2x2_jpeg, host_decodes, noise_jpeg
 from test_isa_guard import LIB, gfx950_code_objects
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
@@ -390,6 +391,57 @@ def test_arithmetic_outlier_inside_a_group(oracle):
     for i in range(4):
         assert np.array_equal(pics[i], exp[i]), i
     assert not any(touched)
+    d.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("walk", ["device", "host"])
+def test_every_interval_source_in_one_group(monkeypatch, walk):
+    """One 4:4:4 group whose members get their intervals in three ways: a stream without restart markers that is walked (on the
+    device, or with MIJPEG_DEVICE_WALK=0 on the host), one too small for a walk (64 x 64: the whole scan is one interval) and one
+    with restart markers.  The walked one is 256 x 256, the smallest either walk takes: noise for the host's planner, which wants
+    four 32 KiB segments, a picture for the device's (on the noise this group's launch is refused and its members take the
+    single-image route).  One Huffman launch; walk launches only where the device walks.  The planes stay in HBM: range checks
+    and pixels are compared with the host decoder's."""
+    monkeypatch.setenv("MIJPEG_DEVICE_WALK", "1" if walk == "device" else "0")
+    walked = synth.synth_jpeg(256, 256, 21, 95, "444", 0) if walk == "device" else noise_jpeg(256, 256, 21, "444", 0)
+    streams = [walked, noise_jpeg(64, 64, 22, "444", 0), noise_jpeg(200, 136, 23, "444", 3)]
+    want = host_decodes(streams)
+    d = api.Decoder(0)
+    assert d.decode_ragged_device(streams) == [0] * 3
+    st = d.ragged_stats()
+    assert st["ragged"] == 3 and st["fallbacks"] == 0 and st["entropy_launches"] == 1, (st, [d.ragged_route(i) for i in range(3)])
+    assert (st["walk_launches"] > 0) == (walk == "device"), st
+    infos = [d.ragged_info(i) for i in range(3)]
+    for i, f in enumerate(infos):
+        assert d.ragged_route(i) == (True, None)
+        assert list(f.range_max) == want[i][1] and int(f.fast_arith) == want[i][2], i
+    pics, touched = _reconstruct_guarded(d, infos, (0, 4, 13))
+    assert not any(touched)
+    for i in range(3):
+        assert np.array_equal(pics[i], want[i][0]), i
+    d.close()
+
+
+@pytest.mark.gpu
+def test_single_component_with_sampling_factors_leaves_the_groups():
+    """A frame whose only component has sampling factors 2 x 2 (40 x 24: its scan leaves blocks of its planes unwritten) is not
+    decoded in a ragged launch: it takes the single-image route, which clears the planes first."""
+    odd = grey_2x2_jpeg(40, 24, 5, 2)
+    streams = [_encode(64, 64, 31, 85, "grey", 2, False), odd]
+    want = host_decodes(streams)
+    d = api.Decoder(0)
+    assert d.decode_ragged_device(streams) == [0, 0]
+    assert d.ragged_route(0) == (True, None)
+    assert d.ragged_route(1) == (False, "no layout group for this frame: 8-bit sequential 4:2:0, 4:2:2, 4:4:4 and grey frames have one")
+    infos = [d.ragged_info(i) for i in range(2)]
+    assert list(infos[1].range_max) == want[1][1]
+    pics, touched = _reconstruct_guarded(d, infos, (0, 4))
+    assert not any(touched)
+    for i in range(2):
+        assert np.array_equal(pics[i], want[i][0].reshape(pics[i].shape)), i
+    st = d.ragged_stats()
+    assert st["ragged"] == 1 and st["fallbacks"] == 1 and st["errors"] == 0, st
     d.close()
 
 
