@@ -517,6 +517,25 @@ typedef struct mijpeg_ragged_frame {
 } mijpeg_ragged_frame;
 int mijpeg_ragged_plan(const mijpeg_info *infos, int n, int32_t *group, mijpeg_ragged_frame *frames, int32_t group_workgroups[MIJPEG_RAGGED_GROUPS],
                        int64_t *coef_total);
+/* Lists that mix 8-bit and 12-bit pictures (the decoder's counterpart of mijpeg_encode_ragged_device16).  The calls
+ * above keep 12-bit frames out of the layout groups; these give a plain 12-bit Huffman sequential frame (SOF1, P = 12, one
+ * interleaved scan or one component) the 12-bit group of its layout -- 4:2:0, 4:2:2, 4:4:4 or grey 1 x 1 -- and are the calls
+ * above on everything else.  mijpeg_ragged_plan16: groups 0..3 as ever, 4..7 for the 12-bit frames; geometry, workgroup ranges
+ * and stores as above, the stores packed back to back in list order across both precisions (int16 coefficients either way).
+ * mijpeg_decode_ragged_device16: one Huffman launch per layout and precision present, at most eight.
+ * mijpeg_reconstruct_ragged_device serves whichever decode call filled the object: the images of a 12-bit group that agree on
+ * kernel and colour-stage flavour (mijpeg_kernel_name: "/narrow" or not) share a launch -- at most two per three-component group,
+ * one for grey -- and an image beyond the 12-bit kernels' gates, or without the YCbCr transformation, is reconstructed by a
+ * launch of its own (recon_single).  A 12-bit picture's destination holds 16-bit samples: row_strides[i] is in bytes, as
+ * mijpeg_reconstruct_device takes it for such a frame.  The other mijpeg_ragged_* calls read either call's batch. */
+#define MIJPEG_RAGGED_420_12 4
+#define MIJPEG_RAGGED_422_12 5
+#define MIJPEG_RAGGED_444_12 6
+#define MIJPEG_RAGGED_GREY_12 7
+#define MIJPEG_RAGGED_GROUPS16 8
+int mijpeg_ragged_plan16(const mijpeg_info *infos, int n, int32_t *group, mijpeg_ragged_frame *frames, int32_t group_workgroups[MIJPEG_RAGGED_GROUPS16],
+                         int64_t *coef_total);
+int mijpeg_decode_ragged_device16(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status);
 
 /* ---- stateless device entry points (inputs and outputs resident in HBM) -------------------- */
 

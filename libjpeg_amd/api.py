@@ -86,6 +86,7 @@ class MijpegRaggedFrame(C.Structure):
 
 
 RAGGED_GROUPS = ("420", "422", "444", "grey")  # MIJPEG_RAGGED_420 ...
+RAGGED_GROUPS16 = RAGGED_GROUPS + ("420_12", "422_12", "444_12", "grey_12")  # ... MIJPEG_RAGGED_420_12 ...: the ...16 calls
 
 
 class MijpegEncodeFrame(C.Structure):
@@ -180,6 +181,8 @@ def lib():
         L.mijpeg_reconstruct_ragged_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int]
         L.mijpeg_ragged_get_stats.argtypes = [C.c_void_p, P(MijpegRaggedStats)]
         L.mijpeg_ragged_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mijpeg_ragged_plan16.argtypes = L.mijpeg_ragged_plan.argtypes
+        L.mijpeg_decode_ragged_device16.argtypes = L.mijpeg_decode_ragged_device.argtypes
         L.mijpeg_encode_ragged_plan.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_encode_ragged_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_encode_ragged.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -655,15 +658,17 @@ class Decoder:
             _foreign_work_done()
         self._check(lib().mijpeg_reconstruct_batch_device(self._h, dst_ptr, frame_stride, row_stride, flags, 1 if sync else 0))
 
-    def decode_ragged_device(self, streams, min_intervals: int = 0) -> list[int]:
+    def decode_ragged_device(self, streams, min_intervals: int = 0, with_12bit: bool = False) -> list[int]:
         """mijpeg_decode_ragged_device: n streams of any shapes -> coefficient stores in HBM, one Huffman launch per layout group;
-        what the batch kernels do not cover takes the single-image route inside the call.  -> status code per stream (0 = decoded)."""
+        what the batch kernels do not cover takes the single-image route inside the call.  -> status code per stream (0 = decoded).
+        with_12bit: mijpeg_decode_ragged_device16 -- plain 12-bit frames have layout groups of their own instead of taking that route."""
         n = len(streams)
         self._batch = list(streams)
         arr = (C.c_char_p * n)(*self._batch)
         sizes = (C.c_size_t * n)(*[len(s) for s in self._batch])
         status = (C.c_int32 * n)()
-        self._check(lib().mijpeg_decode_ragged_device(self._h, arr, sizes, n, min_intervals, status))
+        fn = lib().mijpeg_decode_ragged_device16 if with_12bit else lib().mijpeg_decode_ragged_device
+        self._check(fn(self._h, arr, sizes, n, min_intervals, status))
         self.ragged_images = n
         return list(status)
 
@@ -907,17 +912,26 @@ def encode_coefficients(info: MijpegInfo, coef: np.ndarray, restart_interval: in
 def ragged_plan(infos):
     """mijpeg_ragged_plan (no device needed): frame descriptions -> (group per frame, -1 = single-image route; MijpegRaggedFrame per
     frame; grid of the four layout groups; size of the packed coefficient store)."""
+    return _ragged_plan(infos, "mijpeg_ragged_plan", RAGGED_GROUPS)
+
+
+def ragged_plan16(infos):
+    """mijpeg_ragged_plan16: ragged_plan with the 12-bit layout groups (RAGGED_GROUPS16: eight grids)."""
+    return _ragged_plan(infos, "mijpeg_ragged_plan16", RAGGED_GROUPS16)
+
+
+def _ragged_plan(infos, call, groups):
     n = len(infos)
     arr = (MijpegInfo * max(n, 1))()
     for i, f in enumerate(infos):
         C.memmove(C.byref(arr[i]), C.byref(f), C.sizeof(MijpegInfo))
     group = (C.c_int32 * max(n, 1))()
     frames = (MijpegRaggedFrame * max(n, 1))()
-    grids = (C.c_int32 * len(RAGGED_GROUPS))()
+    grids = (C.c_int32 * len(groups))()
     total = C.c_int64()
-    rc = lib().mijpeg_ragged_plan(arr, n, group, frames, grids, C.byref(total))
+    rc = getattr(lib(), call)(arr, n, group, frames, grids, C.byref(total))
     if rc:
-        raise MijpegError(rc, "mijpeg_ragged_plan failed")
+        raise MijpegError(rc, call + " failed")
     return list(group), list(frames), list(grids), total.value
 
 

@@ -134,6 +134,7 @@ struct mijpeg_decoder {
   hipEvent_t ragged_uploaded = nullptr;          // behind the upload of the descriptor tables (the pinned copy is free again)
   bool ragged_upload_pending = false;
   int ragged_n = 0;
+  bool ragged_with12 = false;                    // the batch was grouped by mijpeg_decode_ragged_device16's planner (12-bit groups)
   mijpeg_ragged_stats ragged_stats{};
   uint8_t *ragged_desc_dev = nullptr, *ragged_desc_host = nullptr; // frame descriptor tables of the reconstruction launches (pinned copy)
   size_t ragged_desc_cap = 0, ragged_desc_host_cap = 0;
@@ -231,8 +232,9 @@ struct RaggedEntropy {
   int *entropy_launches, *walk_launches; // counted up per launch of huffman_scan_kernel / huffman_walk_kernel (rounds and emitting pass)
 };
 
-const char *device_entropy_obstacle(const mij::HostDecoder &h, size_t size, bool xt_part = false);
-const char *ragged_entropy_obstacle(const mij::HostDecoder &h, size_t size);
+// plain12: plain 12-bit frames (SOF1, P = 12) pass as well -- mijpeg_decode_ragged_device16 alone asks with it
+const char *device_entropy_obstacle(const mij::HostDecoder &h, size_t size, bool xt_part = false, bool plain12 = false);
+const char *ragged_entropy_obstacle(const mij::HostDecoder &h, size_t size, bool plain12 = false);
 const char *multiscan_obstacle(const mij::HostDecoder &h, bool xt_part, bool residual_frame);
 size_t stream_slots(const size_t *sizes, int n, std::vector<size_t> &stream_off);
 // How device_entropy_batch is asked to work: a caller names what it sets
@@ -241,6 +243,7 @@ struct EntropyBatchOptions {
   bool defer = false;                    // enqueue only: mijpeg_finish_batch_device waits and looks at the status words
   bool markers = false;                  // the marker route: the streams were parsed without a marker search, the device searches them
   const RaggedEntropy *ragged = nullptr; // images of different sizes
+  bool plain12 = false;                  // ... which may be plain 12-bit frames (all of a launch or none: one precision per launch)
 };
 int device_entropy_batch(mijpeg_decoder *d, mij::HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
                          int min_intervals, int16_t *coef_dev, int64_t frame_stride, const EntropyBatchOptions &opt);

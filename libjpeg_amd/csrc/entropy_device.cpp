@@ -41,12 +41,14 @@ static const char *sampling_obstacle(const mijpeg_info &f)
 
 // Why a parsed stream cannot be entropy-decoded on the device (nullptr: it can).  `xt_part`: the stream is one of the
 // two codestreams of a JPEG XT profile C file (8-bit legacy or 12-bit residual frame without hidden refinement scans).
-const char *device_entropy_obstacle(const HostDecoder &h, size_t size, bool xt_part)
+const char *device_entropy_obstacle(const HostDecoder &h, size_t size, bool xt_part, bool plain12)
 {
   const mijpeg_info &f = h.info;
   // one Huffman sequential scan over all components (or a single-component frame)
   if (const char *why = stream_obstacle(h, xt_part, true)) return why;
-  if (f.precision != 8 && !(xt_part && f.precision == 12)) return "on-device entropy decoding: 8-bit frames (12-bit residual frames of JPEG XT) only";
+  // (plain12: the ragged call with 12-bit groups.  The kernel is the one that decodes the residual frames: DC categories to 15,
+  // AC categories to 15 into the int16 store, code + value bits <= 31, a DC prediction beyond int16 is HUFF_ERR_OVERFLOW.)
+  if (f.precision != 8 && !((xt_part || plain12) && f.precision == 12)) return "on-device entropy decoding: 8-bit frames (12-bit residual frames of JPEG XT) only";
   if (h.scans.size() != 1 || h.hidden_bits()) return "on-device entropy decoding: the frame has more than one scan";
   const Scan &s = h.scans[0];
   if (s.ncomp != f.components) return "on-device entropy decoding: the scan does not cover all components";
@@ -88,10 +90,10 @@ static const char *stream_copy_obstacle(const HostDecoder &h, size_t size, int *
 // checks, asked stream by stream before the groups are formed): what mijpeg_decode_ragged_device sends to the single-image
 // route, so that only the odd member leaves its layout group.  The scan must list the components in frame order -- a launch
 // shares the order, and this is the one every group can share.
-const char *ragged_entropy_obstacle(const HostDecoder &h, size_t size)
+const char *ragged_entropy_obstacle(const HostDecoder &h, size_t size, bool plain12)
 {
   int code;
-  if (const char *why = device_entropy_obstacle(h, size, false)) return why;
+  if (const char *why = device_entropy_obstacle(h, size, false, plain12)) return why;
   if (const char *why = restart_markers_obstacle(h, 0)) return why;
   if (const char *why = stream_copy_obstacle(h, size, &code)) return why;
   const Scan &s = h.scans[0];
@@ -605,7 +607,7 @@ int plan_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const size_t *sizes
   d->walk_rounds = 0;
   const bool device_walk = !(getenv("MIJPEG_DEVICE_WALK") && atoi(getenv("MIJPEG_DEVICE_WALK")) == 0);
   for (int i = 0; i < n; i++) {
-    const char *why = opt.markers ? device_markers_obstacle(*hosts[i], sizes[i]) : device_entropy_obstacle(*hosts[i], sizes[i], opt.xt_part);
+    const char *why = opt.markers ? device_markers_obstacle(*hosts[i], sizes[i]) : device_entropy_obstacle(*hosts[i], sizes[i], opt.xt_part, ragged && opt.plain12);
     if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
     const mijpeg_info &f = hosts[i]->info;
     const Scan &s = hosts[i]->scans[0];

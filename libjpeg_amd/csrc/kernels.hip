@@ -832,7 +832,8 @@ __device__ __forceinline__ TileCtx tile_enter(const Fused420Args &a, u32x4 (*sta
 // have it, and nothing about the other instantiations changes.  The ragged ones overwrite the frame geometry in their copy of
 // the argument block -- which the rest of the kernel reads as ever -- from the frame's RaggedFrame entry, found by
 // a binary search of the prefix table of first workgroups, all of it workgroup-uniform (scalar loads, SGPRs).  The deltas
-// come through qdev (the kernel arguments hold one set), so q is never read and stays unset.
+// come through qdev (the kernel arguments hold one set), so q is never read and stays unset.  Nothing here depends on the sample
+// precision: the 12-bit kernels' ragged flavours enter the same way (the destination's lines hold 16-bit samples, that is all).
 // Tile order: XCD x takes the x-th contiguous eighth of the launch's tiles (order 1 above, over all frames), frame after frame
 // and row by row inside a frame: neighbouring tiles share an L2 whatever tiles_x their frame has, and no frame is padded to
 // eight tile rows -- a picture of one tile is one workgroup.
@@ -1237,118 +1238,16 @@ __device__ __forceinline__ void f422_chroma_edges(const Fused420Args &a, T *line
 
 // P = 12 (FAST only): 12-bit frames (SOF1, P = 12) -- the same transforms and filters on samples sixteen times as large, the
 // colour stage rearranged so that it stays inside 32 bits (see there), 16-bit samples out (clamp 4095).
-template <bool FAST, int MINW, bool QDEV, int P = 8, bool N12 = false, bool RAGGED = false>
-__global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Args a)
-{
-  static_assert(P == 8 || (P == 12 && FAST), "12-bit frames: FAST flavour only (the host checks the ranges)");
-  static_assert(!RAGGED || (QDEV && P == 8), "ragged launches: 8 bit, per-frame tables");
-  __shared__ __attribute__((aligned(16))) int cplane[2][F420_CROWS * F420_CPITCH];
-  __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-
-  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<P == 8 ? MIJ_TILE_ORDER : 1>(a, stage_all);
-  if (t.padding) return;
-
-  // the luma blocks of phase B are requested in front of phase A's transform (see F420P_MINW; two workgroups per CU leave the 32
-  // registers) -- 8-bit frames only: the 12-bit flavour fetches them at the start of phase B
-  u32x4 yraw[8];
-  auto luma_loads = [&]() { load_tile_blocks(yraw, t, t.coef + a.off_y, a.bw_y, a.bh_y); };
-  constexpr bool PREFETCH = P == 8;
-  if (PREFETCH) f420_chroma_to_lds<FAST, QDEV, !QDEV && P == 8>(a, t, cplane, luma_loads);
-  else f420_chroma_to_lds<FAST, QDEV, !QDEV && P == 8>(a, t, cplane);
-  __syncthreads();
-  f420_chroma_edges(a, cplane, t.tid, t.tx, t.ty);
-
-  // ------------------------------------------------------------------ phase B: luma + colour
-  u32x4 rows[8];
-  if (!PREFETCH) luma_loads();
-  transpose_blocks(rows, t.stage, t.lane, yraw);
-  const BlockOut o = block_out<P == 12 ? 6 : 3>(a, t);
-  if (o.outside) return; // no barrier below this point
-  int yv[64];
-  if (FAST) dequant_idct_sparse<!QDEV && P == 8, P == 8>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 0, P == 8 ? LUMA_FOLD_R2 : 2048); // (8 bit: doubled sums, luma13)
-  else dequant_idct<false>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 128 << 7);
-
-  // chroma window of this block: lines pr = 4 by + m (+0 top, +1 cur, +2 bot), columns pc = 4 bx + 3 + j
-  const int *cb_base = cplane[0] + (4 * o.by) * F420_CPITCH + 4 * o.bx;
-  const int *cr_base = cplane[1] + (4 * o.by) * F420_CPITCH + 4 * o.bx;
-
-  int cbT[6], cbC[6], cbB[6], crT[6], crC[6], crB[6];
-  load6(cb_base, cbT); load6(cb_base + F420_CPITCH, cbC);
-  load6(cr_base, crT); load6(cr_base + F420_CPITCH, crC);
-
-#pragma unroll
-  for (int m = 0; m < 4; m++) {
-    load6(cb_base + (m + 2) * F420_CPITCH, cbB);
-    load6(cr_base + (m + 2) * F420_CPITCH, crB);
-#pragma unroll
-    for (int half = 0; half < 2; half++) {
-      const int l = 2 * m + half;
-      // vertical filter (upsampler.cpp:149-165): even output lines look up, odd ones down; the
-      // rounding constant alternates with the buffer column parity
-      int vb[6], vr[6];
-#pragma unroll
-      for (int j = 0; j < 6; j++) {
-        const int rnd = ((j & 1) ^ half) ? 1 : 2;
-        vb[j] = tap13(half ? cbB[j] : cbT[j], cbC[j], rnd);
-        vr[j] = tap13(half ? crB[j] : crT[j], crC[j], rnd);
-      }
-      int ub[8], ur[8];
-      hfilter8(vb, ub);
-      hfilter8(vr, ur);
-      if (l < o.nln) {
-        if (FAST && P == 12) {
-          // (y * 8192 + (cb - 32768) * Lb + (cr - 32768) * Lr + 65536) >> 17, clamped to [0, 4095] (ycbcrtrafo.cpp:842-856,
-          // :921-936; the reference accumulates in 64 bits).  With y = y' + 32768, cb - 32768 = cb' (no level shift in the
-          // transforms) and c L = q 2^13 + r, 0 <= r < 2^13:  ((y' + 32776 + q) 2^13 + r) >> 17 = (y' + 32776 + q) >> 4
-          // exactly.  The products must fit 32 bits: |c| <= 4.02 * 45056 + 2 < 181 200 by the host's range check (an IDCT
-          // output times 16 is at most 4 sum |c_k| q_k; the 9-bit constants and the two roundings add < 0.5 %), times 11485
-          // < 2^31; Lb = 14516 = 4 * 3629 is applied as (c * 3629) >> 11, which is the same number.
-          int rr[8], gg[8], bb[8];
-#pragma unroll
-          for (int x = 0; x < 8; x++) colour12<N12>(yv[l * 8 + x], ub[x], ur[x], rr[x], gg[x], bb[x]);
-          store_rgb12_line<F420_12_TEMPORAL>(o.out_frame + o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
-        } else if (FAST) {
-          // y, cb, cr arrive WITHOUT the level shift (DCOFF = false): with y = y' + 2048 and cb - 2048 = cb' the
-          // reference's (y * 8192 + (cb - 2048) * Lb + (cr - 2048) * Lr + 65536) >> 17 becomes
-          // (y' * 8192 + K + cb' * Lb + cr' * Lr) >> 17 with one constant K for all three channels
-          int rr[8], gg[8], bb[8];
-#pragma unroll
-          for (int x = 0; x < 8; x++) {
-            const int yk = luma13(yv[l * 8 + x]); // (level shift and rounding are inside: LUMA_FOLD_R2)
-            rr[x] = mad24(ur[x], L_CR_R, yk); // still scaled by 2^17
-            gg[x] = mad24(ur[x], -L_CR_G, mad24(ub[x], -L_CB_G, yk));
-            bb[x] = mad24(ub[x], L_CB_B, yk);
-          }
-          store_rgb8_line<STORE24_3X8>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
-        } else {
-          uint8_t *dst = o.out_frame + o.line_off(l, a);
-          unsigned px[24];
-#pragma unroll
-          for (int x = 0; x < 8; x++) {
-            int r, g, b;
-            ycc_to_rgb<false>(yv[l * 8 + x], ub[x], ur[x], r, g, b);
-            px[3 * x] = r; px[3 * x + 1] = g; px[3 * x + 2] = b;
-          }
-          if (o.fast_store) {
-            unsigned w[6];
-#pragma unroll
-            for (int i = 0; i < 6; i++) w[i] = px[4 * i] | (px[4 * i + 1] << 8) | (px[4 * i + 2] << 16) | (px[4 * i + 3] << 24);
-            store24_3x8(dst, w);
-          } else {
-#pragma unroll
-            for (int x = 0; x < 8; x++)
-              if (x < o.npx) {
-                dst[3 * x] = (uint8_t)px[3 * x]; dst[3 * x + 1] = (uint8_t)px[3 * x + 1]; dst[3 * x + 2] = (uint8_t)px[3 * x + 2];
-              }
-          }
-        }
-      }
-    }
-    // slide the three-line window
-#pragma unroll
-    for (int j = 0; j < 6; j++) { cbT[j] = cbC[j]; cbC[j] = cbB[j]; crT[j] = crC[j]; crC[j] = crB[j]; }
-  }
-}
+// The kernel's text is fused420_kernel.inc, included twice: here for every instantiation the library had before the 12-bit ragged
+// ones, and once more in mij::ragged12 for fused420_kernel<true, F420_12_MINW, true, 12, N12, true> alone.  As plain instantiations of
+// the template here those two would compile just as well; they stand apart because tests/test_ragged_batch.py lists, by mangled name,
+// the ragged instantiations mij:: holds, and pins the register count of every uniform one (which wrapping the body in a shared
+// __device__ function moves).  A second inclusion leaves every existing instantiation instruction for instruction as it was
+// (profiles/ragged_decode12.txt); a change that may touch that test can fold them back into mij.  fused1_kernel: the same.
+#include "fused420_kernel.inc"
+namespace ragged12 {
+#include "fused420_kernel.inc"
+} // namespace ragged12
 
 // ==============================================================================================
 // fused 4:2:0 kernel, packed chroma flavour
@@ -1739,13 +1638,14 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(Fused420Ar
 // samples as 32-bit values in two LDS planes (a 12-bit chroma sample times 16 does not fit 16 bits: 72 KB + the fetch staging
 // = half a CU's LDS, two workgroups per CU), fused420_kernel<.., 12>'s colour stage behind the horizontal filter.  Gates:
 // plan_reconstruct's 12-bit gate (capi.cpp), the 12-bit 4:2:0 kernel's.
-template <bool QDEV, bool N12>
-__global__ __launch_bounds__(F420_THREADS, 2) void fused422_12_kernel(const Fused420Args a)
+template <bool QDEV, bool N12, bool RAGGED = false>
+__global__ __launch_bounds__(F420_THREADS, 2) void fused422_12_kernel(Fused420Args a)
 {
+  static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   __shared__ __attribute__((aligned(16))) int cplane[2][F422_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const TileCtx t = tile_enter(a, stage_all);
+  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
   if (t.padding) return;
 
   // ------------------------------------------------------------------ phase A: chroma -> the component's LDS plane, edge fix-up
@@ -2541,11 +2441,12 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(Fused420Ar
 // 32-bit values (64 + 64 VGPRs: a 12-bit chroma sample times 16 does not fit 16 bits), two waves per SIMD.  The colour stage is
 // fused420_kernel<.., 12>'s: (y' + 32776 + (c L >> 13)) >> 4 clamped to [0, 4095], exact under the host's range gates
 // (plan_reconstruct: the 12-bit 4:2:0 kernel's bounds; there is no filter between transform and colour stage here).
-template <bool QDEV, bool N12>
-__global__ __launch_bounds__(F420_THREADS, 2) void fused444_12_kernel(const Fused420Args a)
+template <bool QDEV, bool N12, bool RAGGED = false>
+__global__ __launch_bounds__(F420_THREADS, 2) void fused444_12_kernel(Fused420Args a)
 {
+  static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const TileCtx t = tile_enter(a, stage_all);
+  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
   if (t.padding) return;
   const int frame = t.frame;
   auto fetch = [&](u32x4 (&rows)[8], int64_t plane_off) { fetch_tile_blocks(rows, t, t.coef + plane_off, a.bw_y, a.bh_y); };
@@ -2583,67 +2484,11 @@ __global__ __launch_bounds__(F420_THREADS, 2) void fused444_12_kernel(const Fuse
 // leaves out folded into the rounding constant, clamp, eight bytes per line.  Samples travel as packed int16 from the
 // addition on (range check: |sample * 16| <= 4 * range_max < 2^15).  Algorithmic bytes: 2 B in + 1 B out per pixel.
 // P = 12: 12-bit frames -- the same transform, 16-bit samples out (clamp 4095), samples as 32-bit values throughout.
-template <bool QDEV, int P = 8, bool RAGGED = false>
-__global__ __launch_bounds__(F420_THREADS, 4) void fused1_kernel(Fused420Args a)
-{
-  static_assert(!RAGGED || (QDEV && P == 8), "ragged launches: 8 bit, per-frame tables");
-  __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<1>(a, stage_all);
-  if (t.padding) return;
-
-  u32x4 rows[8];
-  fetch_tile_blocks(rows, t, t.coef + a.off_y, a.bw_y, a.bh_y);
-  const BlockOut o = block_out<P == 12 ? 2 : 1>(a, t);
-  if (o.outside) return;
-  int v[64];
-  dequant_idct_sparse<!QDEV && P == 8>(rows, frame_deltas<QDEV>(a, t.frame, 0), v);
-  uint8_t *__restrict__ out_frame = o.out_frame;
-  const unsigned out_off = o.out_off;
-  const int npx = o.npx, nln = o.nln;
-  const bool fast_store = o.fast_store;
-  if (P == 12) {
-    // COLOR_TO_INT with the level shift 2^11 << 4 the transform left out: (x + 32768 + 8) >> 4, clamped to [0, 4095]
-#pragma unroll
-    for (int l = 0; l < 8; l++) {
-      if (l < nln) {
-        unsigned w[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          const unsigned lo = (unsigned)min(max((v[l * 8 + 2 * i] + (32768 + 8)) >> 4, 0), 4095);
-          const unsigned hi = (unsigned)min(max((v[l * 8 + 2 * i + 1] + (32768 + 8)) >> 4, 0), 4095);
-          w[i] = lo | (hi << 16);
-        }
-        uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-        if (fast_store) {
-          __builtin_nontemporal_store(u32x4{w[0], w[1], w[2], w[3]}, reinterpret_cast<u32x4_any *>(dst));
-        } else {
-          uint16_t *d16 = reinterpret_cast<uint16_t *>(dst);
-#pragma unroll
-          for (int x = 0; x < 8; x++)
-            if (x < npx) d16[x] = (uint16_t)(w[x >> 1] >> (16 * (x & 1)));
-        }
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int l = 0; l < 8; l++) {
-    if (l < nln) {
-      unsigned b4[2]; // four clamped samples each: level shift, COLOR_TO_INT's rounding, shift, clamp
-#pragma unroll
-      for (int h = 0; h < 2; h++)
-        b4[h] = ashr_sat_pack4<4>(v[l * 8 + 4 * h] + (2048 + 8), v[l * 8 + 4 * h + 1] + (2048 + 8), v[l * 8 + 4 * h + 2] + (2048 + 8), v[l * 8 + 4 * h + 3] + (2048 + 8));
-      uint8_t *dst = out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride);
-      if (fast_store) {
-        __builtin_nontemporal_store(u32x2{b4[0], b4[1]}, reinterpret_cast<u32x2_any *>(dst));
-      } else {
-#pragma unroll
-        for (int x = 0; x < 8; x++)
-          if (x < npx) dst[x] = (uint8_t)(b4[x >> 2] >> (8 * (x & 3)));
-      }
-    }
-  }
-}
+// (fused1_kernel.inc, and once more in mij::ragged12 for fused1_kernel<true, 12, true>: see fused420_kernel)
+#include "fused1_kernel.inc"
+namespace ragged12 {
+#include "fused1_kernel.inc"
+} // namespace ragged12
 
 // ==============================================================================================
 // generic path, kernel 1: dequant + IDCT of every block of every component into int32 sample planes
@@ -3939,6 +3784,13 @@ int launch_fused_ragged(const ReconPlan &p, const Fused420Args &a, unsigned work
   case Recon::FUSED422: kernel = p.wide ? fused422_kernel<3, true, true, true> : fused422_kernel<3, true, false, true>; break;
   case Recon::FUSED444: kernel = fused444_kernel<2, true, true>; break;
   case Recon::FUSED1: kernel = fused1_kernel<true, 8, true>; break;
+  // 12 bit: the occupancy of the uniform per-frame-table builds (two workgroups per CU; grey four)
+  case Recon::FUSED420_12:
+    kernel = p.narrow12 ? ragged12::fused420_kernel<true, F420_12_MINW, true, 12, true, true> : ragged12::fused420_kernel<true, F420_12_MINW, true, 12, false, true>;
+    break;
+  case Recon::FUSED422_12: kernel = p.narrow12 ? fused422_12_kernel<true, true, true> : fused422_12_kernel<true, false, true>; break;
+  case Recon::FUSED444_12: kernel = p.narrow12 ? fused444_12_kernel<true, true, true> : fused444_12_kernel<true, false, true>; break;
+  case Recon::FUSED1_12: kernel = ragged12::fused1_kernel<true, 12, true>; break;
   default: return -1; // (no ragged flavour)
   }
   hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(F420_THREADS), 0, s, a);

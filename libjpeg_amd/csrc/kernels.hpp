@@ -161,7 +161,8 @@ struct ReconPlan {
 
 // The kernels up to FUSEDXTW420: x.ext and x.luma_fits16 are read for the JPEG XT ones only
 int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t stream);
-// Frames of different sizes in one launch of FUSED420P, FUSED420 (fast or safe), FUSED422 (wide or not), FUSED444 or FUSED1, 8 bit,
+// Frames of different sizes in one launch of FUSED420P, FUSED420 (fast or safe), FUSED422 (wide or not), FUSED444 or FUSED1 (8 bit), or
+// of FUSED420_12, FUSED422_12, FUSED444_12 (narrow12 or not) or FUSED1_12 (12 bit: the lines of a.ragged[i].out hold 16-bit samples),
 // per-frame tables in a.qdev: a.ragged / a.ragged_first / a.frames describe them, `workgroups` is ragged_first[frames].
 int launch_fused_ragged(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t stream);
 int launch_generic(const GenericArgs &a, bool fast, hipStream_t stream);

@@ -10,32 +10,37 @@
 using namespace mij;
 
 // The layout group of a frame description, or -1: 8-bit plain sequential frames in the four layouts whose fused kernels have a
-// ragged flavour, every plane inside the kernels' 32-bit offsets
-static int ragged_group_of(const mijpeg_info &f)
+// ragged flavour, every plane inside the kernels' 32-bit offsets.  with12 (the ...16 calls): 12-bit ones as well, in the groups
+// MIJPEG_RAGGED_420_12 ... of the same layouts (MIJPEG_RAGGED_GROUPS further on)
+static int ragged_group_of(const mijpeg_info &f, bool with12)
 {
-  if (f.precision != 8 || f.xt || f.progressive || f.coef_wide || f.dnl || f.width < 1 || f.height < 1 || f.coef_count < 64) return -1;
+  if ((f.precision != 8 && !(with12 && f.precision == 12)) || f.xt || f.progressive || f.coef_wide || f.dnl || f.width < 1 || f.height < 1 || f.coef_count < 64) return -1;
   if (f.components != 1 && f.components != 3) return -1;
   for (int c = 0; c < f.components; c++)
     if ((unsigned)f.quant_index[c] >= 4 || f.blocks_w[c] < 1 || f.blocks_h[c] < 1 || (uint64_t)f.blocks_w[c] * (uint64_t)f.blocks_h[c] * 128u > 0xffffffffull) return -1;
+  const int p12 = f.precision == 12 ? MIJPEG_RAGGED_GROUPS : 0;
   switch (sampling_of(f)) {
-  case Sampling::S420: return MIJPEG_RAGGED_420;
-  case Sampling::S422: return MIJPEG_RAGGED_422;
-  case Sampling::S444: return MIJPEG_RAGGED_444;
-  case Sampling::GREY: return f.hsamp[0] == 1 && f.vsamp[0] == 1 ? MIJPEG_RAGGED_GREY : -1; // (sampling factors on a single component: MCU padding nobody decodes)
+  case Sampling::S420: return MIJPEG_RAGGED_420 + p12;
+  case Sampling::S422: return MIJPEG_RAGGED_422 + p12;
+  case Sampling::S444: return MIJPEG_RAGGED_444 + p12;
+  case Sampling::GREY: return f.hsamp[0] == 1 && f.vsamp[0] == 1 ? MIJPEG_RAGGED_GREY + p12 : -1; // (sampling factors on a single component: MCU padding nobody decodes)
   default: return -1;
   }
 }
+static_assert(MIJPEG_RAGGED_420_12 == MIJPEG_RAGGED_420 + MIJPEG_RAGGED_GROUPS && MIJPEG_RAGGED_GREY_12 == MIJPEG_RAGGED_GREY + MIJPEG_RAGGED_GROUPS &&
+              MIJPEG_RAGGED_GROUPS16 == 2 * MIJPEG_RAGGED_GROUPS, "the 12-bit groups follow the 8-bit ones, layout by layout");
 
-// Grouping, workgroup ranges and coefficient bases of n frames; excluded[i] != 0 (optional) keeps frame i out of the groups
-static int ragged_plan(const mijpeg_info *infos, int n, const char *excluded, int32_t *group, mijpeg_ragged_frame *frames, int32_t *group_workgroups, int64_t *coef_total)
+// Grouping, workgroup ranges and coefficient bases of n frames; excluded[i] != 0 (optional) keeps frame i out of the groups.
+// with12: the planner of the ...16 calls -- group_workgroups holds MIJPEG_RAGGED_GROUPS16 grids, MIJPEG_RAGGED_GROUPS without it.
+static int ragged_plan(const mijpeg_info *infos, int n, const char *excluded, bool with12, int32_t *group, mijpeg_ragged_frame *frames, int32_t *group_workgroups, int64_t *coef_total)
 {
   int64_t base = 0;
-  uint64_t grid[MIJPEG_RAGGED_GROUPS] = {0, 0, 0, 0};
+  uint64_t grid[MIJPEG_RAGGED_GROUPS16] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (int i = 0; i < n; i++) {
     const mijpeg_info &f = infos[i];
     mijpeg_ragged_frame &r = frames[i];
     memset(&r, 0, sizeof(r));
-    int g = excluded && excluded[i] ? -1 : ragged_group_of(f);
+    int g = excluded && excluded[i] ? -1 : ragged_group_of(f, with12);
     if (g >= 0) fused_geometry(f, sampling_of(f), r); // (what the uniform launches of the same kernels get)
     const uint64_t tiles = (uint64_t)r.tiles_x * (uint64_t)r.tiles_y;
     if (g >= 0 && grid[g] + tiles > 0x7fffffffull) { // (a grid holds 2^31 - 1 workgroups)
@@ -49,7 +54,7 @@ static int ragged_plan(const mijpeg_info *infos, int n, const char *excluded, in
     r.first_workgroup = (int32_t)grid[g];
     grid[g] += tiles;
   }
-  for (int g = 0; g < MIJPEG_RAGGED_GROUPS; g++) group_workgroups[g] = (int32_t)grid[g];
+  for (int g = 0; g < (with12 ? MIJPEG_RAGGED_GROUPS16 : MIJPEG_RAGGED_GROUPS); g++) group_workgroups[g] = (int32_t)grid[g];
   *coef_total = base;
   return MIJPEG_OK;
 }
@@ -86,16 +91,10 @@ static void ragged_single_image(mijpeg_decoder *d, int i, int k, const uint8_t *
   r.status = rc;
 }
 
-extern "C" {
-
-int mijpeg_ragged_plan(const mijpeg_info *infos, int n, int32_t *group, mijpeg_ragged_frame *frames, int32_t group_workgroups[MIJPEG_RAGGED_GROUPS], int64_t *coef_total)
-try {
-  if (!infos || !group || !frames || !group_workgroups || !coef_total || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  return ragged_plan(infos, n, nullptr, group, frames, group_workgroups, coef_total);
-} catch (...) { return boundary_catch(nullptr, "mijpeg_ragged_plan"); }
-
-int mijpeg_decode_ragged_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status)
-try {
+// The two decode calls' body.  with12: mijpeg_decode_ragged_device16 -- plain 12-bit frames pass the entropy obstacle and have layout
+// groups of their own (a Huffman launch decodes one precision: plan_batch), everything else is the same call
+static int decode_ragged(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status, bool with12)
+{
   if (!d || !streams || !sizes || !status || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
   if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
   HIP_TRY(d, hipSetDevice(d->device));
@@ -119,7 +118,7 @@ try {
   std::vector<char> excluded((size_t)n, 0);
   std::vector<mijpeg_info> infos((size_t)n);
   for (int i = 0; i < n; i++) {
-    const char *why = rcs[(size_t)i] ? "the stream does not parse as the batch decoder reads it" : ragged_entropy_obstacle(*d->batch_hosts[(size_t)i], sizes[i]);
+    const char *why = rcs[(size_t)i] ? "the stream does not parse as the batch decoder reads it" : ragged_entropy_obstacle(*d->batch_hosts[(size_t)i], sizes[i], with12);
     excluded[(size_t)i] = why != nullptr;
     if (why) d->ragged[(size_t)i].why_single = why;
     if (excluded[(size_t)i]) memset(&infos[(size_t)i], 0, sizeof(mijpeg_info));
@@ -127,17 +126,20 @@ try {
   }
   std::vector<int32_t> group((size_t)n);
   std::vector<mijpeg_ragged_frame> frames((size_t)n);
-  int32_t grids[MIJPEG_RAGGED_GROUPS];
+  int32_t grids[MIJPEG_RAGGED_GROUPS16];
   int64_t coef_total = 0;
-  ragged_plan(infos.data(), n, excluded.data(), group.data(), frames.data(), grids, &coef_total);
+  ragged_plan(infos.data(), n, excluded.data(), with12, group.data(), frames.data(), grids, &coef_total);
+  d->ragged_with12 = with12; // (mijpeg_reconstruct_ragged_device numbers each launch's frames with the same planner)
   for (int i = 0; i < n; i++)
-    if (group[(size_t)i] < 0 && !excluded[(size_t)i]) d->ragged[(size_t)i].why_single = "no layout group for this frame: 8-bit sequential 4:2:0, 4:2:2, 4:4:4 and grey frames have one";
+    if (group[(size_t)i] < 0 && !excluded[(size_t)i])
+      d->ragged[(size_t)i].why_single = with12 ? "no layout group for this frame: 8-bit and 12-bit sequential 4:2:0, 4:2:2, 4:4:4 and grey frames have one"
+                                               : "no layout group for this frame: 8-bit sequential 4:2:0, 4:2:2, 4:4:4 and grey frames have one";
   if (coef_total > 0) {
     const int rc = ensure_coef_store(d, (size_t)coef_total, false);
     if (rc) return rc;
   }
   // one launch of the Huffman kernel per group (the walk in front of it where streams have no restart markers)
-  for (int g = 0; g < MIJPEG_RAGGED_GROUPS; g++) {
+  for (int g = 0; g < (with12 ? MIJPEG_RAGGED_GROUPS16 : MIJPEG_RAGGED_GROUPS); g++) {
     std::vector<int> members;
     for (int i = 0; i < n; i++)
       if (group[(size_t)i] == g) members.push_back(i);
@@ -159,6 +161,7 @@ try {
     const RaggedEntropy re{bases.data(), verdict.data(), &scan_launches, &walk_launches};
     EntropyBatchOptions opt;
     opt.ragged = &re;
+    opt.plain12 = g >= MIJPEG_RAGGED_GROUPS;
     const int rc = device_entropy_batch(d, hosts.data(), datas.data(), gsizes.data(), (int)m, 1, d->coef_dev, 0, opt);
     d->ragged_stats.entropy_launches += scan_launches;
     d->ragged_stats.walk_launches += walk_launches;
@@ -195,7 +198,32 @@ try {
   d->err_code = 0;
   d->err_msg.clear();
   return MIJPEG_OK;
+}
+
+extern "C" {
+
+int mijpeg_ragged_plan(const mijpeg_info *infos, int n, int32_t *group, mijpeg_ragged_frame *frames, int32_t group_workgroups[MIJPEG_RAGGED_GROUPS], int64_t *coef_total)
+try {
+  if (!infos || !group || !frames || !group_workgroups || !coef_total || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  return ragged_plan(infos, n, nullptr, false, group, frames, group_workgroups, coef_total);
+} catch (...) { return boundary_catch(nullptr, "mijpeg_ragged_plan"); }
+
+int mijpeg_ragged_plan16(const mijpeg_info *infos, int n, int32_t *group, mijpeg_ragged_frame *frames, int32_t group_workgroups[MIJPEG_RAGGED_GROUPS16], int64_t *coef_total)
+try {
+  if (!infos || !group || !frames || !group_workgroups || !coef_total || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  return ragged_plan(infos, n, nullptr, true, group, frames, group_workgroups, coef_total);
+} catch (...) { return boundary_catch(nullptr, "mijpeg_ragged_plan16"); }
+
+int mijpeg_decode_ragged_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status)
+try {
+  return decode_ragged(d, streams, sizes, n, min_intervals, status, false);
 } catch (...) { return boundary_catch(d, "mijpeg_decode_ragged_device"); }
+
+int mijpeg_decode_ragged_device16(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status)
+try {
+  return decode_ragged(d, streams, sizes, n, min_intervals, status, true);
+} catch (...) { return boundary_catch(d, "mijpeg_decode_ragged_device16"); }
+
 
 int mijpeg_ragged_info(mijpeg_decoder *d, int i, mijpeg_info *info)
 try {
@@ -248,7 +276,9 @@ try {
   d->ragged_stats.recon_launches = d->ragged_stats.recon_single = 0;
   // Which kernel every group image takes, from ITS range check: images of a group that agree on kernel and arithmetic flavour
   // share a launch -- one outlier beyond the fast gates runs the SAFE flavour alone instead of taking the group along.
-  // (quant_dev is only tested by the planner: the ragged launches read per-frame tables.)
+  // (quant_dev is only tested by the planner: the ragged launches read per-frame tables.)  12-bit groups: kernel and narrow12, i.e.
+  // at most two launches per three-component group; an image beyond the 12-bit gates or without the YCbCr transformation gets
+  // no fused kernel from the planner and is reconstructed by a launch of its own.
   static const uint16_t per_frame_tables = 0;
   auto describe = [&](int i, bool own_tables) {
     const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
@@ -266,10 +296,12 @@ try {
     const ReconPlan p = plan_reconstruct(&b);
     const bool has_flavour = (r.group == MIJPEG_RAGGED_420 && (p.kernel == Recon::FUSED420P || p.kernel == Recon::FUSED420)) ||
                              (r.group == MIJPEG_RAGGED_422 && p.kernel == Recon::FUSED422) || (r.group == MIJPEG_RAGGED_444 && p.kernel == Recon::FUSED444) ||
-                             (r.group == MIJPEG_RAGGED_GREY && p.kernel == Recon::FUSED1);
+                             (r.group == MIJPEG_RAGGED_GREY && p.kernel == Recon::FUSED1) || (r.group == MIJPEG_RAGGED_420_12 && p.kernel == Recon::FUSED420_12) ||
+                             (r.group == MIJPEG_RAGGED_422_12 && p.kernel == Recon::FUSED422_12) || (r.group == MIJPEG_RAGGED_444_12 && p.kernel == Recon::FUSED444_12) ||
+                             (r.group == MIJPEG_RAGGED_GREY_12 && p.kernel == Recon::FUSED1_12);
     if (!has_flavour) { singles.push_back(i); continue; }
     size_t l = 0;
-    while (l < launches.size() && !(launches[l].group == r.group && launches[l].p.kernel == p.kernel && launches[l].p.fast == p.fast && launches[l].p.wide == p.wide)) l++;
+    while (l < launches.size() && !(launches[l].group == r.group && launches[l].p.kernel == p.kernel && launches[l].p.fast == p.fast && launches[l].p.wide == p.wide && launches[l].p.narrow12 == p.narrow12)) l++;
     if (l == launches.size()) launches.push_back(Launch{p, r.group, {}});
     launches[l].members.push_back(i);
   }
@@ -296,10 +328,10 @@ try {
       std::vector<mijpeg_info> infos(m);
       std::vector<int32_t> grp(m);
       std::vector<mijpeg_ragged_frame> pf(m);
-      int32_t grids[MIJPEG_RAGGED_GROUPS];
+      int32_t grids[MIJPEG_RAGGED_GROUPS16];
       int64_t unused = 0;
       for (size_t k = 0; k < m; k++) infos[k] = d->ragged[(size_t)mem[k]].info;
-      ragged_plan(infos.data(), (int)m, nullptr, grp.data(), pf.data(), grids, &unused);
+      ragged_plan(infos.data(), (int)m, nullptr, d->ragged_with12, grp.data(), pf.data(), grids, &unused);
       for (size_t k = 0; k < m; k++) {
         const int i = mem[k];
         const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];

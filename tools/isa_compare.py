@@ -1,11 +1,12 @@
 """Do two builds of libmijpeg.so hold the same machine code for the kernels both have?
 
-    python tools/isa_compare.py OLD/libmijpeg.so NEW/libmijpeg.so [--kernels REGEX] [--appended Lb0E]
+    python tools/isa_compare.py OLD/libmijpeg.so NEW/libmijpeg.so [--kernels REGEX] [--appended Lb0E] [--mask-pcrel]
 
 Disassembles the gfx950 code objects of both libraries (llvm-objdump, addresses and encodings left out, comments stripped) and
 compares, kernel by kernel, the instruction lists.  --appended: the mangled spelling of template arguments the NEW build has
 behind the OLD ones (a flavour added as a defaulted last template parameter: `Lb0E` is `false`), so that the old name finds its
-new twin.  Prints one line per kernel and the totals; exit status 1 when something differs.
+new twin.  --mask-pcrel: the literal of the s_add_u32 behind an s_getpc_b64 -- the distance from the kernel to a constant table in
+.rodata, which moves whenever the code object gains or loses a kernel -- is left out of the comparison.  Prints one line per kernel and the totals; exit status 1 when something differs.
 """
 import argparse
 import os
@@ -20,7 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from test_isa_guard import OBJDUMP, gfx950_code_objects  # noqa: E402
 
 
-def kernels(path):
+def kernels(path, mask_pcrel=False):
     out = {}
     for co in gfx950_code_objects(path):
         with tempfile.NamedTemporaryFile(suffix=".co", delete=False) as f:
@@ -33,7 +34,10 @@ def kernels(path):
             if m:
                 cur = out.setdefault(m.group(1), [])
             elif cur is not None and ln.strip():
-                cur.append(re.sub(r"//.*", "", ln).strip())
+                ins = re.sub(r"//.*", "", ln).strip()
+                if mask_pcrel and cur and cur[-1].startswith("s_getpc_b64") and ins.startswith("s_add_u32"):
+                    ins = re.sub(r"0x[0-9a-f]+$", "<pc-relative>", ins)
+                cur.append(ins)
     return out
 
 
@@ -43,8 +47,9 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--kernels", default=r"fused(420p|420|422|444|1)_kernel")
     ap.add_argument("--appended", default="")
+    ap.add_argument("--mask-pcrel", action="store_true")
     args = ap.parse_args()
-    a, b = kernels(args.old), kernels(args.new)
+    a, b = kernels(args.old, args.mask_pcrel), kernels(args.new, args.mask_pcrel)
     same = different = missing = 0
     for name in sorted(a):
         if not re.search(args.kernels, name):
