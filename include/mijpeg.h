@@ -259,14 +259,23 @@ int mijpeg_prepare_batch_host(mijpeg_decoder *d, const uint8_t *const *streams, 
  * mijpeg_submit_batch_device / mijpeg_finish_batch_device and mijpeg_prepare_batch_host (its host half) parse the headers only,
  * copy the raw entropy coded segment into the staging slot with one memcpy, and two kernel passes in front of the Huffman
  * launch write the copy without stuffing and markers and the interval tables where that launch reads them.  Every image of the
- * call must qualify -- plain (no JPEG XT, no DNL) 8-bit Huffman sequential, one scan over all components, DRI > 0, FF D9 as the
- * last two bytes of the stream -- else the whole call takes the ordinary route.  The search must come out plain as well: no fill
- * byte, exactly the markers the MCU count asks for, in sequence, and the segment ending at the FF of that closing EOI.  Where it
- * does not, the synchronous calls run the ordinary route inside the same call (the caller sees what it would have seen with the
- * option off); mijpeg_finish_batch_device, which no longer has the bytes, answers MIJPEG_ERR_NOT_AVAILABLE as it does for damaged
- * streams.  The ragged calls, multi-scan / progressive / JPEG XT frames, streams without restart markers, class JPEG and the
- * command line ignore the option.  stats: images of this object that went through the device search, and images of calls that
- * took the ordinary route although the option was on (either pointer may be NULL). */
+ * call must qualify -- plain (no JPEG XT, no DNL) 8-bit Huffman sequential, one scan over all components, FF D9 as the last two
+ * bytes of the stream -- else the whole call takes the ordinary route.  Streams with restart markers (DRI > 0) and without may
+ * share a batch.  A stream without restart markers is searched with one expected interval (no marker at all), a small fit step puts
+ * the size of its copy where the device walk reads it, and the walk finds its virtual restart intervals as it does with the
+ * option off; in the batch calls it must be large enough for a walk (256 MCUs, 4096 bytes) as it must be there, and
+ * mijpeg_decode_coefficients_device, the single-image call, keeps the host's search for such a stream.  The search
+ * must come out plain as well: no fill byte, exactly the markers the MCU count asks for, in sequence, and the segment ending at the
+ * FF of that closing EOI.  Where it does not, the synchronous calls run the ordinary route inside the same call (the caller sees
+ * what it would have seen with the option off); mijpeg_finish_batch_device, which no longer has the bytes, answers
+ * MIJPEG_ERR_NOT_AVAILABLE as it does for damaged streams.  The ragged calls (mijpeg_decode_ragged_device / ...16) honour the option
+ * member by member: a member whose parse could leave the search to the device is searched inside its layout group's one launch,
+ * beside members that were searched on the host (bytes behind EOI, the 12-bit groups); a small stream without restart markers is
+ * searched as its one interval; a member whose search or decode is not good takes the single-image route, with its reason in
+ * mijpeg_ragged_route, and the other members keep their result.  Multi-scan / progressive / JPEG XT / DNL / 12-bit streams, the
+ * single-image route of the ragged calls, class JPEG and the command line ignore the option.  stats: images of this object that
+ * went through the device search, and images of calls that took the ordinary route although the option was on -- in a ragged
+ * call, every member the device did not search (either pointer may be NULL). */
 int mijpeg_set_device_markers(mijpeg_decoder *d, int on);
 int mijpeg_device_markers_stats(mijpeg_decoder *d, int64_t *searched, int64_t *declined);
 /* ... for every decoder object of a pipeline (on < 0: leave as is).  Returns the setting. */

@@ -626,6 +626,9 @@ static int decode_coefficients_device(mijpeg_decoder *d, int min_intervals, bool
   HostDecoder *h = &d->host, *res = d->host.residual();
   if (markers) {
     const char *why = res ? "device marker search: plain 8-bit frames only" : device_markers_obstacle(d->host, d->size);
+    // This call keeps what it did for a stream without restart markers: the ordinary route, host search included (the batch
+    // calls and the ragged calls are where such streams are searched on the device)
+    if (!why && d->host.scans[0].restart_interval <= 0) why = "device marker search: the single-image call searches streams without restart markers on the host";
     if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
   }
   // (a stream that does not qualify: the parse is as good as the one mijpeg_decode_coefficients would make next)
@@ -871,6 +874,18 @@ static int finish_batch(mijpeg_decoder *d)
     }
     HIP_TRY(d, hipStreamSynchronize(d->stream));
     d->phase_device += std::chrono::duration<double>(std::chrono::steady_clock::now() - d->pend_t0).count();
+    // the device searched the segments: is every search good?  (The bytes are gone: the caller's fallback takes over.)  Asked first:
+    // the walk of a stream without restart markers follows its search, and has walked nothing behind one that is not good
+    if (d->pend_markers) {
+      const uint32_t *results = d->pend_markers;
+      d->pend_markers = nullptr;
+      if (!device_markers_good(results, d->markers_want_term.data(), pn)) {
+        d->markers_searched -= pn;
+        d->markers_declined += pn;
+        d->pend_walk_round = 0;
+        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: a segment is not the plain case; the host searches such streams (mijpeg_decode_batch_device)");
+      }
+    }
     if (d->pend_walk_round > 0) { // streams without restart markers: did the walk settle within the rounds it was given?
       const int rounds = d->pend_walk_round;
       d->pend_walk_round = 0;
@@ -878,15 +893,6 @@ static int finish_batch(mijpeg_decoder *d)
       d->walk_rounds = walk_rounds_needed(d->pend_walk_flags, rounds);
       if (d->pend_walk_status)
         if (const int wrc = walk_verdict(d, d->pend_walk_status, pn)) return wrc;
-    }
-    if (d->pend_markers) { // the device searched the segments: is every search good?  (The bytes are gone: the caller's fallback takes over)
-      const uint32_t *results = d->pend_markers;
-      d->pend_markers = nullptr;
-      if (!device_markers_good(results, d->markers_want_term.data(), pn)) {
-        d->markers_searched -= pn;
-        d->markers_declined += pn;
-        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: a segment is not the plain case; the host searches such streams (mijpeg_decode_batch_device)");
-      }
     }
     const int rc = evaluate_entropy_status(d, hosts.data(), pn, d->pend_status);
     if (rc) return rc;

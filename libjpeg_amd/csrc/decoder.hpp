@@ -228,7 +228,8 @@ struct MultiScanFrame {
 // Images of different sizes in one launch of device_entropy_batch (they share components and sampling factors)
 struct RaggedEntropy {
   const int64_t *coef_base; // per image: int16 index of its coefficient store in coef_dev
-  int *verdict;             // out, per image: 0 decoded (info carries its range check), 1 damaged: the single-image route decides
+  int *verdict;             // out, per image: 0 decoded (info carries its range check), 1 damaged: the single-image route decides,
+                            // 2 (the marker route) the device's search of its segment is not good: the same
   int *entropy_launches, *walk_launches; // counted up per launch of huffman_scan_kernel / huffman_walk_kernel (rounds and emitting pass)
 };
 
@@ -242,14 +243,16 @@ struct EntropyBatchOptions {
   bool xt_part = false;                  // the stream is one of the two codestreams of a JPEG XT file
   bool defer = false;                    // enqueue only: mijpeg_finish_batch_device waits and looks at the status words
   bool markers = false;                  // the marker route: the streams were parsed without a marker search, the device searches them
+                                         // (a ragged launch: those of its members whose Scan::search_skipped says so, the others as always)
   const RaggedEntropy *ragged = nullptr; // images of different sizes
   bool plain12 = false;                  // ... which may be plain 12-bit frames (all of a launch or none: one precision per launch)
 };
 int device_entropy_batch(mijpeg_decoder *d, mij::HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
                          int min_intervals, int16_t *coef_dev, int64_t frame_stride, const EntropyBatchOptions &opt);
-// the marker route: why a stream parsed with HostDecoder::set_skip_search stays on the host route (nullptr: it qualifies); what
+// the marker route: why a stream parsed with HostDecoder::set_skip_search stays on the host route (nullptr: it qualifies; ragged: as
+// a member of a ragged launch, where a stream without restart markers that is too small for a walk is one interval); what
 // the result words of n images say (true: every search is good)
-const char *device_markers_obstacle(const mij::HostDecoder &h, size_t size);
+const char *device_markers_obstacle(const mij::HostDecoder &h, size_t size, bool ragged = false);
 bool device_markers_good(const uint32_t *results, const uint32_t *want_term, int n);
 // mijpeg_device_marker_search's body (include/mijpeg.h)
 int64_t device_marker_search(mijpeg_decoder *d, const uint8_t *segment, size_t size, int32_t expect, uint8_t *dst, size_t capacity,

@@ -94,27 +94,42 @@ const char *ragged_entropy_obstacle(const HostDecoder &h, size_t size, bool plai
 {
   int code;
   if (const char *why = device_entropy_obstacle(h, size, false, plain12)) return why;
-  if (const char *why = restart_markers_obstacle(h, 0)) return why;
-  if (const char *why = stream_copy_obstacle(h, size, &code)) return why;
   const Scan &s = h.scans[0];
-  if (s.restart_interval > 0 && s.interval_ubegin.size() < s.interval_begin.size()) return "restart intervals missing";
+  if (s.search_skipped) { // (the marker route: the device searches the segment, and the launch's verdict says what it found)
+    if (const char *why = device_markers_obstacle(h, size, true)) return why;
+  } else {
+    if (const char *why = restart_markers_obstacle(h, 0)) return why;
+    if (const char *why = stream_copy_obstacle(h, size, &code)) return why;
+    if (s.restart_interval > 0 && s.interval_ubegin.size() < s.interval_begin.size()) return "restart intervals missing";
+  }
   for (int k = 0; k < s.ncomp; k++)
     if (s.sc[k].comp != k) return "the scan lists its components out of frame order";
   return nullptr;
 }
 
 // The marker route (mijpeg_set_device_markers, markers.hip): what keeps one stream, parsed with HostDecoder::set_skip_search, on the
-// host route.  What the parse itself asks for -- a plain 8-bit Huffman sequential frame, one scan over all components, DRI > 0,
-// FF D9 as the last two bytes -- shows in Scan::search_skipped.
-const char *device_markers_obstacle(const HostDecoder &h, size_t size)
+// host route.  What the parse itself asks for -- a plain 8-bit Huffman sequential frame, one scan over all components, FF D9 as
+// the last two bytes -- shows in Scan::search_skipped.  A stream without restart markers is searched with one expected interval
+// and then walked on the device (huffman_walk_kernel), so it must be large enough for a walk, and the walk must not be switched
+// off (MIJPEG_DEVICE_WALK=0: the host plans the restart points, which needs the host's search).
+static bool too_small_for_a_walk(const Scan &s) { return (int64_t)s.mcus_x * s.mcus_y < 256 || s.ecs_end - s.ecs_begin < 4096; }
+static bool device_walk_enabled() { return !(getenv("MIJPEG_DEVICE_WALK") && atoi(getenv("MIJPEG_DEVICE_WALK")) == 0); }
+static const char TOO_SMALL_FOR_A_WALK[] = "stream without restart markers is too small for speculative decoding";
+
+const char *device_markers_obstacle(const HostDecoder &h, size_t size, bool ragged)
 {
   if (const char *why = device_entropy_obstacle(h, size, false)) return why;
   const Scan &s = h.scans[0];
-  if (!s.search_skipped) return "device marker search: not a plain 8-bit sequential stream with restart markers that ends in EOI";
+  if (!s.search_skipped) return "device marker search: not a plain 8-bit sequential stream that ends in EOI";
   if (h.info.xt || h.is_xt() || h.info.dnl || h.info.precision != 8) return "device marker search: plain 8-bit frames only";
-  if (s.restart_interval <= 0 || size < s.ecs_begin + 2) return "device marker search: streams with restart markers only";
+  if (size < s.ecs_begin + 2) return "device marker search: no room for the closing EOI";
   if (size - s.ecs_begin >= MARKERS_MAX_SEGMENT) return "entropy coded segment too large for the device decoder's bit addresses";
   const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
+  if (s.restart_interval <= 0) {
+    if (too_small_for_a_walk(s)) return ragged ? nullptr : TOO_SMALL_FOR_A_WALK; // (a ragged launch decodes it as one interval)
+    if (!device_walk_enabled()) return "device marker search: streams without restart markers need the device walk";
+    return nullptr;
+  }
   if ((total_mcus + s.restart_interval - 1) / s.restart_interval > 0x7fffffff) return "too many restart intervals";
   return nullptr;
 }
@@ -274,6 +289,8 @@ enum class IntervalSource {
   DeviceWalk,     // no markers: huffman_walk_kernel finds them in front of the decode; their number is known already
   WholeScan,      // no markers, a small member of a ragged launch: ONE interval, one lane -- every MCU in sequence, as a host thread would
   MarkerSearch,   // the raw segment goes up; the search kernels (markers.hip) write the copy and the interval tables
+  SearchedWalk,   // no markers, the raw segment goes up: searched with ONE expected interval, fitted (marker_fit_kernel), then walked like DeviceWalk
+  SearchedWhole,  // WholeScan whose raw segment goes up: searched with one expected interval, which writes its copy and the end of its one interval
 };
 
 struct ImagePlan {
@@ -283,7 +300,9 @@ struct ImagePlan {
   size_t copy_bytes = 0; // the device's copy of its entropy coded data (MarkerSearch: the raw segment, terminator included -- the copy is no longer)
   size_t slot_off = 0;   // its slot in the stream buffer (stream_slots)
   std::unique_ptr<VirtualIntervals> walked; // HostWalk: the restart points
-  bool virtual_intervals() const { return source == IntervalSource::HostWalk || source == IntervalSource::DeviceWalk; }
+  bool device_walked() const { return source == IntervalSource::DeviceWalk || source == IntervalSource::SearchedWalk; }
+  bool searched() const { return source == IntervalSource::MarkerSearch || source == IntervalSource::SearchedWalk || source == IntervalSource::SearchedWhole; }
+  bool virtual_intervals() const { return source == IntervalSource::HostWalk || device_walked(); }
 };
 
 struct BatchPlan {
@@ -339,16 +358,20 @@ int walk_verdict(mijpeg_decoder *d, const uint32_t *walk_status, int n)
 // decode kernel reads.  The host only looks at the per-round "something changed" flags.
 // The images of `plan` whose source is the device walk are walked; `scan` is the argument block of the decode that follows (its
 // data, images and tables are the walk's), `intervals` the tables the EMIT walk writes.
-struct DeviceIntervals { uint32_t *ibegin; uint8_t *iskip; int16_t *ipred; };
+// Images whose source is SearchedWalk (the marker route, `search` its argument block): everything here is sized from the raw
+// segment, an upper bound of the copy the search writes, and the fit step (launch_marker_fit) puts what the search found --
+// the copy's size, the subsequences it really has, the end of every virtual interval -- where the walk kernels read it.
+struct DeviceIntervals { uint32_t *ibegin, *iend; uint8_t *iskip; int16_t *ipred; };
 static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, const BatchPlan &plan, const EntropyBatchOptions &opt, const HuffScanArgs &scan,
-                              const DeviceIntervals &intervals)
+                              const DeviceIntervals &intervals, const MarkerArgs &search)
 {
   const int n = plan.n();
   const bool defer = opt.defer, per_image = opt.ragged != nullptr; // (images of different sizes: interval sizes and block counts image by image)
   int *const walk_launches = opt.ragged ? opt.ragged->walk_launches : nullptr;
   // MCUs per virtual interval of the images that are walked, 0 for the others
-  auto dwalk = [&](int i) { return plan.images[(size_t)i].source == IntervalSource::DeviceWalk ? plan.images[(size_t)i].mcus_per_interval : 0; };
-  auto usize = [&](int i) { return plan.images[(size_t)i].copy_bytes; }; // (the device's copy: entropy coded data without the byte stuffing)
+  auto dwalk = [&](int i) { return plan.images[(size_t)i].device_walked() ? plan.images[(size_t)i].mcus_per_interval : 0; };
+  // (the device's copy: entropy coded data without the byte stuffing; SearchedWalk: the raw segment, which is no shorter)
+  auto usize = [&](int i) { return plan.images[(size_t)i].copy_bytes; };
   const mijpeg_info &f0 = hosts[0]->info;
   const Scan &s0 = hosts[0]->scans[0];
   HuffWalkArgs w;
@@ -399,8 +422,10 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, cons
   for (int i = 0; i < n; i++)
     for (uint32_t k = 0; k < img_nsub[(size_t)i]; k += per_group) { sub_image.push_back((uint32_t)i); sub_first.push_back(k); }
   w.n_groups = (int32_t)sub_image.size();
-  // one device buffer: [per group: image, first][per image: sub0, nsub, e0, e1, int0][per subsequence: state] (the host fills
-  // these) [changed flag per round, status per image][per subsequence: stamp] (start out as zero) [per subsequence: nblocks,
+  // one device buffer: [per group: image, first][per image: sub0, nsub, e0, e1, int0][per subsequence: state][per image, ragged
+  // launches: blocks per interval, blocks][per image, the fit step: virtual intervals] (the host fills these; nsub and e1 of a
+  // SearchedWalk image are bounds the fit step replaces) [changed flag per round, status per image][per subsequence: stamp]
+  // (start out as zero) [per subsequence: nblocks,
   // dcsum, first_block, first_pred][prefix-sum tiles]
   constexpr int MAX_ROUNDS = 48;
   const size_t G = sub_image.size(), S = nsub_total;
@@ -410,6 +435,10 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, cons
   const size_t o_int0 = L.take((size_t)n * 4), o_state = L.take(S * 8);
   // images of different sizes (per_image): blocks per virtual interval and blocks in all, image by image
   const size_t o_every = L.take(per_image ? (size_t)n * 4 : 0), o_blocks = L.take(per_image ? (size_t)n * 4 : 0);
+  // the fit step: virtual intervals of every image that is walked behind its search, 0 for the others
+  bool any_fit = false;
+  for (int i = 0; i < n; i++) any_fit |= plan.images[(size_t)i].source == IntervalSource::SearchedWalk;
+  const size_t o_fit = L.take(any_fit ? (size_t)n * 4 : 0);
   const size_t o_up_end = L.end;
   const size_t o_flags = L.take((size_t)(MAX_ROUNDS + 1) * 4 + (size_t)n * 4); // changed[], walk_status[]
   const size_t o_stamp = L.take(S * 4);
@@ -451,8 +480,26 @@ static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, cons
     for (int i = 0; i < n; i++)
       for (uint32_t k = 0; k < img_nsub[(size_t)i]; k++) st[img_sub0[(size_t)i] + k] = (uint64_t)k * sub_bytes;
   }
+  if (any_fit) {
+    uint32_t *fit = (uint32_t *)(wh + o_fit);
+    for (int i = 0; i < n; i++) fit[i] = plan.images[(size_t)i].source == IntervalSource::SearchedWalk ? (uint32_t)plan.images[(size_t)i].n_intervals : 0u;
+  }
   HIP_TRY(d, hipMemcpyAsync(wd, wh, o_up_end, hipMemcpyHostToDevice, d->stream));
   HIP_TRY(d, hipMemsetAsync(wd + o_flags, 0, o_zero_end - o_flags, d->stream));
+  if (any_fit) { // (behind the search on this stream, behind the upload and the cleared status words, in front of the first round)
+    MarkerFitArgs fit;
+    memset(&fit, 0, sizeof(fit));
+    fit.images = search.images;
+    fit.results = search.results;
+    fit.fit_intervals = (const uint32_t *)(wd + o_fit);
+    fit.img_e1 = (uint32_t *)(wd + o_e1);
+    fit.img_nsub = (uint32_t *)(wd + o_insub);
+    fit.walk_status = (uint32_t *)(wd + o_flags) + MAX_ROUNDS + 1;
+    fit.iend = intervals.iend;
+    fit.sub_bytes = sub_bytes;
+    fit.n_images = (uint32_t)n;
+    if (launch_marker_fit(fit, d->stream)) return hip_fail(d, hipGetLastError(), "marker_fit_kernel launch");
+  }
   w.data = scan.data;
   w.images = scan.images;
   w.tables = scan.tables;
@@ -605,9 +652,11 @@ int plan_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const size_t *sizes
   const Scan &s0 = hosts[0]->scans[0];
   plan.images.resize((size_t)n);
   d->walk_rounds = 0;
-  const bool device_walk = !(getenv("MIJPEG_DEVICE_WALK") && atoi(getenv("MIJPEG_DEVICE_WALK")) == 0);
+  const bool device_walk = device_walk_enabled();
   for (int i = 0; i < n; i++) {
-    const char *why = opt.markers ? device_markers_obstacle(*hosts[i], sizes[i]) : device_entropy_obstacle(*hosts[i], sizes[i], opt.xt_part, ragged && opt.plain12);
+    // the marker route: every image of a uniform call; of a ragged launch the members whose parse left the search to the device
+    const bool searched = opt.markers && (!ragged || (!hosts[i]->scans.empty() && hosts[i]->scans[0].search_skipped));
+    const char *why = searched ? device_markers_obstacle(*hosts[i], sizes[i], ragged) : device_entropy_obstacle(*hosts[i], sizes[i], opt.xt_part, ragged && opt.plain12);
     if (why) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
     const mijpeg_info &f = hosts[i]->info;
     const Scan &s = hosts[i]->scans[0];
@@ -623,23 +672,23 @@ int plan_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const size_t *sizes
       if (s.sc[k].comp != s0.sc[k].comp) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "the images of a batch must share the component order of their scan");
     ImagePlan &p = plan.images[(size_t)i];
     const int64_t total_mcus = (int64_t)s.mcus_x * s.mcus_y;
-    const bool small = total_mcus < 256 || s.ecs_end - s.ecs_begin < 4096; // too small for a walk
+    const bool small = too_small_for_a_walk(s);
     if (s.restart_interval > 0) {
-      p.source = opt.markers ? IntervalSource::MarkerSearch : IntervalSource::RestartMarkers;
+      p.source = searched ? IntervalSource::MarkerSearch : IntervalSource::RestartMarkers;
       p.mcus_per_interval = s.restart_interval;
       p.n_intervals = (total_mcus + s.restart_interval - 1) / s.restart_interval;
-      if (!opt.markers)
+      if (!searched)
         if (const char *bad = restart_markers_obstacle(*hosts[i], 0)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, bad);
     } else if (ragged && small) {
-      p.source = IntervalSource::WholeScan;
+      p.source = searched ? IntervalSource::SearchedWhole : IntervalSource::WholeScan;
       p.mcus_per_interval = s.mcus_x * s.mcus_y;
       p.n_intervals = 1;
     } else {
       // no restart markers: the decode starts from exact restart points ("virtual intervals"), about 16 K of them
       const int per = (int)std::min<int64_t>(64, std::max<int64_t>(1, total_mcus / 16384));
-      if (small) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream without restart markers is too small for speculative decoding");
-      if (device_walk) {
-        p.source = IntervalSource::DeviceWalk;
+      if (small) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, TOO_SMALL_FOR_A_WALK);
+      if (device_walk || searched) { // (the marker route: device_markers_obstacle asked for the device walk)
+        p.source = searched ? IntervalSource::SearchedWalk : IntervalSource::DeviceWalk;
         p.mcus_per_interval = per;
         p.n_intervals = (total_mcus + per - 1) / per;
       } else {
@@ -669,7 +718,7 @@ int plan_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const size_t *sizes
     const Scan &s = hosts[i]->scans[0];
     p.slot_off = stream_off[(size_t)i];
     p.first_interval = i ? plan.images[(size_t)i - 1].first_interval + plan.images[(size_t)i - 1].n_intervals : 0;
-    if (opt.markers) {
+    if (p.searched()) {
       p.copy_bytes = sizes[i] - s.ecs_begin;
       plan.marker_chunks += markers_chunks(p.copy_bytes);
     } else {
@@ -681,7 +730,7 @@ int plan_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const size_t *sizes
       return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "restart intervals missing");
     plan.n_groups += plan.groups_of(i);
     plan.any_virtual |= p.virtual_intervals();
-    plan.any_dwalk |= p.source == IntervalSource::DeviceWalk;
+    plan.any_dwalk |= p.device_walked();
     // an interleaved scan writes every block of every plane; a single-component scan of a frame whose only component
     // has sampling factors > 1 leaves the MCU padding blocks untouched (they must read as zero)
     if (s.ncomp == 1 && (s.mcus_x != f.blocks_w[s.sc[0].comp] || s.mcus_y != f.blocks_h[s.sc[0].comp])) plan.needs_clear = true;
@@ -735,6 +784,7 @@ TableSlots share_table_slots(HostDecoder *const *hosts, int n, bool any_dwalk)
 // Pinned staging (ent_host) holds the part in front of the bar at the same offsets; it goes up as far as the status words, and
 // the marker results and the status words come back in one copy.  What is behind the bar exists on the device only.
 struct BatchLayout {
+  bool markers; // the launch has the marker route's regions (some of its images are searched on the device)
   size_t stream_bytes;
   size_t ibegin, iend, iskip, ipred, tables, images, groups, planes, mimages, mchunks, mresults, status;
   size_t status_bytes, tail_bytes; // tail_bytes: everything in front of the bar
@@ -750,6 +800,7 @@ const char *batch_layout(const BatchPlan &plan, size_t table_blob, const Entropy
   static_assert(sizeof(MarkerResult) == 16, "the result words end where the status words begin");
   const size_t n = (size_t)plan.n(), T = (size_t)plan.total_intervals;
   Layout L;
+  l.markers = opt.markers;
   l.stream_bytes = plan.stream_bytes;
   l.ibegin = L.take(T * 4);
   l.iend = L.take(T * 4);
@@ -788,7 +839,36 @@ struct Staging {
     // (iskip and ipred exist where some image of the launch has virtual intervals)
     uint8_t *isk = plan.any_virtual ? hp + l.iskip + first : nullptr;
     int16_t *ipr = plan.any_virtual ? (int16_t *)(hp + l.ipred) + first * 4 : nullptr;
+    // the marker route: the image's descriptor, its chunks and a fresh result for a search that expects `expect` intervals
+    auto stage_search = [&](uint32_t expect) {
+      MarkerImage *mi = (MarkerImage *)(hp + l.mimages);
+      const uint32_t chunk_at = i ? mi[i - 1].first_chunk + mi[i - 1].n_chunks : 0;
+      // {raw_off, size, dst_off, dst_cap, first_interval, expect, first_chunk}
+      stage_marker_image(mi[i], (MarkerChunk *)(hp + l.mchunks), ((MarkerResult *)(hp + l.mresults))[i], (uint32_t)i,
+                         MarkerImage{(uint32_t)p.slot_off, (uint32_t)p.copy_bytes, (uint32_t)p.slot_off, (uint32_t)(plan.slot_end(i) - p.slot_off), (uint32_t)first,
+                                     expect, chunk_at, 0});
+    };
+    if (l.markers && !p.searched()) { // a marker launch's image that is not searched: no chunks, a result that reads as good
+      MarkerImage *mi = (MarkerImage *)(hp + l.mimages);
+      memset(&mi[i], 0, sizeof(MarkerImage));
+      mi[i].first_chunk = i ? mi[i - 1].first_chunk + mi[i - 1].n_chunks : 0;
+      memset(&((MarkerResult *)(hp + l.mresults))[i], 0, sizeof(MarkerResult));
+    }
     switch (p.source) {
+    case IntervalSource::SearchedWhole: // the search's begin[0] = 0 and end[0] = total are the one interval
+      ib[0] = ie[0] = 0;
+      if (isk) isk[0] = 0;
+      stage_search(1);
+      break;
+    case IntervalSource::SearchedWalk:
+      // begin by the EMIT walk, end by the fit step behind the search (the search's own begin[0] = 0 and end[0] = total agree with
+      // both); zeroed like MarkerSearch's, so that a search that is not good leaves every interval empty at offset 0 of the slot
+      memset(ib, 0, (size_t)nint * 4);
+      memset(ie, 0, (size_t)nint * 4);
+      memset(isk, 0, (size_t)nint);
+      memset(ipr, 0, (size_t)nint * 8);
+      stage_search(1);
+      break;
     case IntervalSource::DeviceWalk: // filled in by the EMIT walk on the device
       for (int64_t k = 0; k < nint; k++) { ib[k] = 0; ie[k] = (uint32_t)p.copy_bytes; }
       memset(isk, 0, (size_t)nint);
@@ -820,12 +900,8 @@ struct Staging {
       // written by the search kernels; entries they leave alone (a search that is not good) must not send the Huffman kernel anywhere
       memset(ib, 0, (size_t)nint * 4);
       memset(ie, 0, (size_t)nint * 4);
-      MarkerImage *mi = (MarkerImage *)(hp + l.mimages);
-      const uint32_t chunk_at = i ? mi[i - 1].first_chunk + mi[i - 1].n_chunks : 0;
-      // {raw_off, size, dst_off, dst_cap, first_interval, expect, first_chunk}
-      stage_marker_image(mi[i], (MarkerChunk *)(hp + l.mchunks), ((MarkerResult *)(hp + l.mresults))[i], (uint32_t)i,
-                         MarkerImage{(uint32_t)p.slot_off, (uint32_t)p.copy_bytes, (uint32_t)p.slot_off, (uint32_t)(plan.slot_end(i) - p.slot_off), (uint32_t)first,
-                                     (uint32_t)nint, chunk_at, 0});
+      if (isk) memset(isk, 0, (size_t)nint);
+      stage_search((uint32_t)nint);
       break;
     }
     case IntervalSource::WholeScan:
@@ -965,15 +1041,17 @@ struct Enqueue {
   // batch's workers do, set_unstuff_sink -- have nothing left to do)
   void gather_images(int g0, int g1)
   {
-    if (opt.markers) { // one memcpy per image: the raw segment into its slot
-      auto copy = [&](int i) { memcpy(d->stage_host + plan.images[(size_t)i].slot_off, datas[i] + hosts[i]->scans[0].ecs_begin, plan.images[(size_t)i].copy_bytes); };
+    if (opt.markers) { // one memcpy per searched image: the raw segment into its slot
+      auto copy = [&](int i) {
+        const ImagePlan &p = plan.images[(size_t)i];
+        if (p.searched()) memcpy(d->stage_host + p.slot_off, datas[i] + hosts[i]->scans[0].ecs_begin, p.copy_bytes);
+      };
       if (g1 - g0 > 1) parallel_for(g1 - g0, [&](int k) { copy(g0 + k); });
       else copy(g0);
-      return;
     }
     for (int i = g0; i < g1; i++) {
       uint8_t *const slot = d->stage_host + plan.images[(size_t)i].slot_off;
-      if (hosts[i]->scans[0].unstuffed_at != slot) gather.add(hosts[i], 0, slot);
+      if (!plan.images[(size_t)i].searched() && hosts[i]->scans[0].unstuffed_at != slot) gather.add(hosts[i], 0, slot);
     }
     gather.run();
   }
@@ -983,18 +1061,25 @@ struct Enqueue {
   // `done` recorded behind it, and the object's stream waits for that.
   int upload_images(int g0, int g1, hipEvent_t done = nullptr)
   {
-    uint8_t *const dst = opt.markers ? tail_dev() + l.raw : d->ent_dev; // (the marker route: the raw segments, the search writes the copies)
+    // (the marker route: a searched image's raw segment goes beside the slots, the search writes the copy into its slot)
+    auto dst_of = [&](int i) { return plan.images[(size_t)i].searched() ? tail_dev() + l.raw : d->ent_dev; };
     if (done) {
-      const size_t b0 = plan.images[(size_t)g0].slot_off, b1 = plan.slot_end(g1 - 1);
-      HIP_TRY(d, hipMemcpyAsync(dst + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
+      // images that go to the same place travel in one copy (a uniform launch: all of them)
+      for (int i0 = g0; i0 < g1;) {
+        int i1 = i0 + 1;
+        while (i1 < g1 && dst_of(i1) == dst_of(i0)) i1++;
+        const size_t b0 = plan.images[(size_t)i0].slot_off, b1 = plan.slot_end(i1 - 1);
+        HIP_TRY(d, hipMemcpyAsync(dst_of(i0) + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
+        i0 = i1;
+      }
       HIP_TRY(d, hipEventRecord(done, d->copy_stream));
       HIP_TRY(d, hipStreamWaitEvent(d->stream, done, 0));
       return MIJPEG_OK;
     }
     for (int i = g0; i < g1; i++) {
       const ImagePlan &p = plan.images[(size_t)i];
-      const size_t bytes = opt.markers ? p.copy_bytes : ((p.copy_bytes + 15) & ~(size_t)15) + HUFF_STREAM_PAD;
-      if (bytes) HIP_TRY(d, hipMemcpyAsync(dst + p.slot_off, d->stage_host + p.slot_off, bytes, hipMemcpyHostToDevice, d->stream));
+      const size_t bytes = p.searched() ? p.copy_bytes : ((p.copy_bytes + 15) & ~(size_t)15) + HUFF_STREAM_PAD;
+      if (bytes) HIP_TRY(d, hipMemcpyAsync(dst_of(i) + p.slot_off, d->stage_host + p.slot_off, bytes, hipMemcpyHostToDevice, d->stream));
     }
     return MIJPEG_OK;
   }
@@ -1027,7 +1112,8 @@ struct Enqueue {
   {
     if (plan.any_dwalk) {
       uint8_t *const dp = tail_dev();
-      const int rc = device_walk_images(d, hosts, plan, opt, scan, DeviceIntervals{(uint32_t *)(dp + l.ibegin), dp + l.iskip, (int16_t *)(dp + l.ipred)});
+      const int rc = device_walk_images(d, hosts, plan, opt, scan,
+                                        DeviceIntervals{(uint32_t *)(dp + l.ibegin), (uint32_t *)(dp + l.iend), dp + l.iskip, (int16_t *)(dp + l.ipred)}, search);
       if (rc) return rc;
       mark("device walk enqueued");
     }
@@ -1094,7 +1180,8 @@ int read_back(mijpeg_decoder *d, const BatchPlan &plan, const BatchLayout &l, co
   d->pend_markers = nullptr;
   if (opt.markers) {
     d->markers_want_term.resize((size_t)n);
-    for (int i = 0; i < n; i++) d->markers_want_term[(size_t)i] = (uint32_t)plan.images[(size_t)i].copy_bytes - 2u;
+    for (int i = 0; i < n; i++) // (an image of the launch that is not searched: its result was staged as zeros and stays so)
+      d->markers_want_term[(size_t)i] = plan.images[(size_t)i].searched() ? (uint32_t)plan.images[(size_t)i].copy_bytes - 2u : 0u;
   }
   return MIJPEG_OK;
 }
@@ -1118,6 +1205,10 @@ int verdict(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const ReadBack 
       HostDecoder *h = hosts[i];
       const bool bad = (back.walk_status && back.walk_status[i]) || evaluate_entropy_status(d, &h, 1, back.status + 8 * i) != MIJPEG_OK;
       opt.ragged->verdict[i] = bad ? 1 : 0;
+      if (!opt.markers || !h->scans[0].search_skipped) continue;
+      // a member the device searched: the search's verdict comes first
+      if (!device_markers_good(back.markers + 4 * i, d->markers_want_term.data() + i, 1)) opt.ragged->verdict[i] = 2;
+      else h->scans[0].unstuffed_size = ((const MarkerResult *)back.markers)[i].total;
     }
     return MIJPEG_OK;
   }
@@ -1140,13 +1231,14 @@ int verdict(mijpeg_decoder *d, HostDecoder *const *hosts, int n, const ReadBack 
 // share components and sampling factors but not their size, image i into coef_dev + ragged->coef_base[i], plane geometry per
 // image; a damaged image is reported in ragged->verdict[i] instead of failing the call.
 // opt.markers: the streams were parsed without a marker search (device_markers_obstacle holds for each): their raw segments go up,
-// and the search kernels write the copies and the interval tables in front of the Huffman launch.  On a search that is not
+// and the search kernels write the copies and the interval tables in front of the Huffman launch.  A ragged launch: those of its
+// members whose Scan::search_skipped says so, side by side with members that are not; ragged->verdict[i] = 2 for a search that is not good.  On a search that is not
 // good the call answers MIJPEG_ERR_NOT_AVAILABLE with d->markers_retry set (deferred: mijpeg_finish_batch_device looks).
 // hosts[i]->info receives fast_arith / range_max.  Returns MIJPEG_OK, MIJPEG_ERR_NOT_AVAILABLE (nothing touched) or an error.
 int device_entropy_batch(mijpeg_decoder *d, HostDecoder *const *hosts, const uint8_t *const *datas, const size_t *sizes, int n,
                          int min_intervals, int16_t *coef_dev, int64_t frame_stride, const EntropyBatchOptions &opt)
 {
-  if (opt.markers && (opt.ragged || opt.xt_part)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: uniform batches of plain streams only");
+  if (opt.markers && opt.xt_part) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: plain streams only");
   const auto tb0 = std::chrono::steady_clock::now();
   int rc;
   BatchPlan plan;

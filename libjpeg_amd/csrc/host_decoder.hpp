@@ -162,8 +162,8 @@ public:
   // Scan::unstuffed_at tells whether it did (it does not when the search runs in parallel chunks).
   void set_unstuff_sink(uint8_t *dst, size_t capacity) { sink_ = dst; sink_cap_ = capacity; }
   // The device searches the restart markers (markers.hip): the NEXT parse() does not search the one scan of a plain 8-bit Huffman
-  // sequential frame with DRI > 0 whose stream ends in FF D9 -- it takes the FF of that EOI for the end of the segment and walks on
-  // from there.  Scan::search_skipped tells whether it did; every other stream is parsed as always.
+  // sequential frame (with restart markers or without) whose stream ends in FF D9 -- it takes the FF of that EOI for the end of the
+  // segment and walks on from there.  Scan::search_skipped tells whether it did; every other stream is parsed as always.
   void set_skip_search() { skip_search_ = true; }
   void unstuff_pieces(size_t scan, size_t piece_bytes, std::vector<UnstuffPiece> &out) const;
   void unstuff_piece(size_t scan, const UnstuffPiece &p, uint8_t *dst) const;

@@ -119,8 +119,11 @@ struct HuffWalkArgs {
   const uint32_t *sub_image;     // device, per workgroup: image of the workgroup's subsequences ...
   const uint32_t *sub_first;     // ... and index of its first subsequence inside the image
   const uint32_t *img_sub0;      // device, per image: index of its first subsequence in the state arrays
-  const uint32_t *img_nsub;      // per image: number of subsequences
-  const uint32_t *img_e0, *img_e1; // per image: entropy coded segment [e0, e1) relative to stream_off
+  // per image: number of subsequences, and the entropy coded segment [e0, e1) relative to stream_off.  The kernels read both from
+  // device memory: for an image that is walked behind its marker search the host uploads bounds (from the raw segment) and the
+  // fit step (markers.hpp) writes the copy's real nsub and e1 in front of the first round; lanes and tiles beyond nsub leave
+  const uint32_t *img_nsub;
+  const uint32_t *img_e0, *img_e1;
   // start state of every subsequence (byte | bits to skip << 32 | block inside the MCU << 40), updated in place: a
   // lane writes its successor's, stamps it with the round, and sets changed[round]
   uint64_t *state;
@@ -130,6 +133,7 @@ struct HuffWalkArgs {
   uint32_t *nblocks;             // out: blocks that start inside the subsequence
   int32_t *dcsum;                // out: four per subsequence
   uint32_t *walk_status;         // per image, from the prefix sums: 1 phase mismatch | 2 DC out of range | 4 too few blocks
+                                 // (| 8 from the fit step, HUFF_WALK_NOT_SEARCHED: nothing to walk, nsub = 0)
   struct WalkSums *tile_sums;    // scratch of the prefix sums: tiles_per_image entries of HUFF_WALK_SUMS_BYTES per image
   int32_t tiles_per_image;       // ceil(max subsequences per image / 1024), at most 1024
   // EMIT only

@@ -179,7 +179,34 @@ __global__ __launch_bounds__(GROUP) void marker_write_kernel(MarkerArgs a)
   for (uint32_t z = all_kept + threadIdx.x; z < im.dst_cap; z += (uint32_t)GROUP) out[z] = 0;
 }
 
+// One wave per image, behind pass 2 (contract: MarkerFitArgs)
+__global__ __launch_bounds__(64) void marker_fit_kernel(MarkerFitArgs a)
+{
+  const uint32_t i = blockIdx.x;
+  if (i >= a.n_images) return;
+  const uint32_t nint = a.fit_intervals[i];
+  if (nint == 0) return;
+  const MarkerImage im = a.images[i];
+  const MarkerResult r = a.results[i];
+  const bool good = r.flags == 0 && im.size >= 2 && r.term == im.size - 2 && r.total > 0 && r.total <= im.size;
+  const uint32_t total = good ? r.total : 0;
+  if (threadIdx.x == 0) {
+    const uint32_t bound = a.img_nsub[i]; // the host's, from the raw size
+    a.img_e1[i] = total;
+    a.img_nsub[i] = min((total + a.sub_bytes - 1) / a.sub_bytes, bound);
+    if (!good) a.walk_status[i] = HUFF_WALK_NOT_SEARCHED;
+  }
+  for (uint32_t k = threadIdx.x; k < nint; k += 64) a.iend[im.first_interval + k] = total;
+}
+
 } // namespace
+
+int launch_marker_fit(const MarkerFitArgs &a, hipStream_t stream)
+{
+  if (a.n_images == 0) return 0;
+  hipLaunchKernelGGL(marker_fit_kernel, dim3(a.n_images), dim3(64), 0, stream, a);
+  return (int)hipGetLastError();
+}
 
 MarkerScratch markers_scratch(uint32_t n_chunks)
 {

@@ -70,5 +70,23 @@ MarkerScratch markers_scratch(uint32_t n_chunks);
 // scratch laid out by markers_scratch, `scan_scratch` at its scan part.  0 or a hipError_t.
 int launch_marker_search(const MarkerArgs &a, uint64_t *scan_scratch, size_t scan_words, hipStream_t stream);
 
+// The fit step: streams without restart markers are searched with expect = 1 and then walked (huffman_walk_kernel), and only the
+// search knows how many bytes the copy holds.  The host sized the walk from the raw segment -- an upper bound; behind pass 2 one
+// wave per image writes what the walk really reads: img_e1 = total, img_nsub = ceil(total / sub_bytes) (never more than the
+// host's bound, which it finds in img_nsub) and iend = total for each of the image's virtual intervals.  A search that is not
+// good (a flag, or term not at the FF of the closing EOI) or that kept nothing: img_nsub = 0, so that no lane walks, and
+// HUFF_WALK_NOT_SEARCHED in the image's walk status.
+constexpr uint32_t HUFF_WALK_NOT_SEARCHED = 8; // (beside the walk's own status bits 1, 2, 4: huffman_dev.hpp)
+struct MarkerFitArgs {
+  const MarkerImage *images;    // device: size, first_interval
+  const MarkerResult *results;  // device: what pass 2 left
+  const uint32_t *fit_intervals; // device, per image: its virtual intervals, 0 = not an image the walk follows the search for
+  uint32_t *img_e1, *img_nsub;  // device, per image: the walk's (HuffWalkArgs)
+  uint32_t *walk_status;        // device, per image
+  uint32_t *iend;               // device: the interval table
+  uint32_t sub_bytes, n_images;
+};
+int launch_marker_fit(const MarkerFitArgs &a, hipStream_t stream);
+
 } // namespace mij
 #endif

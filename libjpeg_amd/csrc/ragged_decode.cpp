@@ -108,12 +108,21 @@ static int decode_ragged(mijpeg_decoder *d, const uint8_t *const *streams, const
   for (auto &h : d->batch_hosts)
     if (!h) h.reset(new HostDecoder());
   d->ragged.assign((size_t)n, mijpeg_decoder::RaggedImage{});
-  // headers and restart markers of all streams, one stream per worker
+  // headers and restart markers of all streams, one stream per worker.  mijpeg_set_device_markers: headers only where the parse
+  // can leave the search to the device (HostDecoder::set_skip_search; Scan::search_skipped tells) -- such members are searched
+  // inside their layout group's launch, beside members that were searched here
+  const bool markers = d->device_markers == 1;
   std::vector<int> rcs((size_t)n, 0);
   const int workers = std::min(n, default_threads());
   parallel_for(workers, [&](int w) {
-    for (int i = w; i < n; i += workers) rcs[(size_t)i] = streams[i] && sizes[i] ? d->batch_hosts[(size_t)i]->parse(streams[i], sizes[i], false) : MIJPEG_ERR_STREAM_EMPTY;
+    for (int i = w; i < n; i += workers) {
+      if (!streams[i] || !sizes[i]) { rcs[(size_t)i] = MIJPEG_ERR_STREAM_EMPTY; continue; }
+      if (markers) d->batch_hosts[(size_t)i]->set_skip_search(); // (armed for the parse that follows)
+      rcs[(size_t)i] = d->batch_hosts[(size_t)i]->parse(streams[i], sizes[i], false);
+    }
   });
+  auto skipped = [&](int i) { return !rcs[(size_t)i] && !d->batch_hosts[(size_t)i]->scans.empty() && d->batch_hosts[(size_t)i]->scans[0].search_skipped; };
+  int64_t searched = 0;
   // what the batch kernels cover goes into the layout groups
   std::vector<char> excluded((size_t)n, 0);
   std::vector<mijpeg_info> infos((size_t)n);
@@ -162,6 +171,7 @@ static int decode_ragged(mijpeg_decoder *d, const uint8_t *const *streams, const
     EntropyBatchOptions opt;
     opt.ragged = &re;
     opt.plain12 = g >= MIJPEG_RAGGED_GROUPS;
+    for (size_t k = 0; k < m; k++) opt.markers |= skipped(members[k]);
     const int rc = device_entropy_batch(d, hosts.data(), datas.data(), gsizes.data(), (int)m, 1, d->coef_dev, 0, opt);
     d->ragged_stats.entropy_launches += scan_launches;
     d->ragged_stats.walk_launches += walk_launches;
@@ -174,9 +184,13 @@ static int decode_ragged(mijpeg_decoder *d, const uint8_t *const *streams, const
       const int i = members[k];
       if (rc || verdict[k]) { // damaged: the single-image route decides
         group[(size_t)i] = -1;
-        d->ragged[(size_t)i].why_single = rc ? group_refusal : std::string("the device decoder found the entropy coded data damaged");
+        d->ragged[(size_t)i].why_single = rc                 ? group_refusal
+                                          : verdict[k] == 2 ? std::string("device marker search: the segment is not the plain case; the host searches it")
+                                                            : std::string("the device decoder found the entropy coded data damaged");
+        if (!rc && skipped(i)) searched++; // (the device searched it, whatever it found)
         continue;
       }
+      if (skipped(i)) searched++;
       mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
       r.group = g;
       r.info = hosts[k]->info;
@@ -193,6 +207,10 @@ static int decode_ragged(mijpeg_decoder *d, const uint8_t *const *streams, const
     if (d->ragged[(size_t)i].status) d->ragged_stats.errors++;
   }
   for (int i = 0; i < n; i++) status[i] = d->ragged[(size_t)i].status;
+  if (markers) { // mijpeg_device_markers_stats: members the device searched, and all the others
+    d->markers_searched += searched;
+    d->markers_declined += n - searched;
+  }
   d->ragged_stats.images = n;
   d->ragged_n = n;
   d->err_code = 0;
