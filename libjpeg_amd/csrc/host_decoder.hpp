@@ -172,7 +172,7 @@ public:
   size_t stream_size() const { return size_; }
   HostDecoder *residual() const { return residual_; } // JPEG XT: decoder of the residual codestream
   // JPEG XT, for one decode(): block rows [y0, y1) of residual component c hold their final coefficients -- called from a
-  // worker thread while the decode goes on (the last refinement window's appliers, decode_t), so that the owner can send them
+  // worker thread while the decode goes on (the last refinement window's reporter, ScanWindow::report_rows), so that the owner can send them
   // on their way; residual_rows_reported(c) = rows it has been told about when decode() returns (0: none, or told and taken
   // back -- a decode that fell back to the sequential walk)
   void set_residual_rows_callback(std::function<void(int, int, int)> cb) { final_rows_cb_ = std::move(cb); }
@@ -180,7 +180,7 @@ public:
   int hidden_bits() const { return hidden_; }
   // hidden refinement scans follow the visible ones (with a merging specification that never arrived they refine zero hidden bits)
   bool has_hidden_scans() const { return hidden_ > 0 || !hidden_src_.empty(); }
-  // JPEG XT: the legacy codestream came to its EOI, i.e. the reference merges the residual codestream (else nothing: see decode_t)
+  // JPEG XT: the legacy codestream came to its EOI, i.e. the reference merges the residual codestream (else nothing: see FrameDecode::xt_verdicts)
   bool residual_merged() const { return eoi_image_; }
   // what decode() would still have to say about this file beside decoding it: a residual codestream whose header is refused, a
   // quantiser table of the residual image that is looked up at the first request (the device decoders leave such files to it)
@@ -275,7 +275,7 @@ private:
   std::vector<uint8_t> rst_code_;
   std::vector<std::vector<size_t>> scan_interval_end_;
   std::vector<std::vector<uint8_t>> scan_rst_code_;
-  // the mask planes of deferred AC refinement scans (decode_t; kept between reads, never initialised)
+  // the mask planes of deferred AC refinement scans (ScanWindow::reserve_mask_planes; kept between reads, never initialised)
   std::unique_ptr<uint64_t[]> refine_scratch_;
   size_t refine_scratch_cap_ = 0;
   // ... and the residual decoder's, which is a new object with every parse, while there is none
@@ -321,6 +321,11 @@ private:
   bool eoi_frame_ = true, eoi_image_ = true; // the walk's frame / image trailer stood at an EOI (RefWalker::frame_eoi / image_eoi)
   std::vector<const XtBox *> hidden_src_; // this frame's hidden refinement scans in box order (elements of the legacy decoder's boxes_)
   template <class T> int decode_t(T *coef, int threads, const std::function<void(int, int)> &on_rows_done);
+  // decode_t's stages (host_decoder.cpp): what one decode carries from stage to stage with the scan loop's strategies and the
+  // epilogues, and a pipeline window of a progressive frame's scans
+  template <class T> struct FrameDecode;
+  template <class T> struct ScanWindow;
+  int decode_residual(void *base, int threads); // the residual frame into its planes, 16 or 32 bits wide (xt.residual_wide)
   template <class T> int decode_scan_speculative(T *coef, const Scan &s, int threads, uint32_t (&qmax_out)[MIJPEG_MAX_COMPONENTS],
                                                  VirtualIntervals *plan_only = nullptr, bool first_pass = false);
   int fail(int code, const char *msg);
