@@ -98,6 +98,33 @@ def craft_stream(rng: np.random.Generator, samp, w: int, h: int, dri: int = 0, t
     return bytes(out) + bytes(bw.out) + b"\xff\xd9"
 
 
+def dense_block(rng: np.random.Generator, units: int) -> np.ndarray:
+    """63 AC terms of both signs with sum |c| = units exactly: the remainder of the scaling is spent on coefficient 1."""
+    v = rng.integers(-40, 41, size=64)
+    v[0] = 0
+    v = (v * (units / max(1, int(np.abs(v).sum())))).astype(np.int64)
+    v[1] += np.sign(v[1] or 1) * (units - int(np.abs(v).sum()))
+    return v
+
+
+def blocks_at(rng: np.random.Generator, bh: int, bw: int, units: int) -> np.ndarray:
+    """bh x bw blocks with sum |c| = units each: the DC term alone, one AC coefficient of either sign at a random position, or a
+    dense block (the three kinds of test_fused420p_ring._at_budget under one delta for all 64 terms)."""
+    p = np.zeros((bh, bw, 64), np.int32)
+    kind = rng.integers(0, 4, size=(bh, bw))
+    sign = rng.choice([-1, 1], size=(bh, bw))
+    p[..., 0] = np.where(kind == 0, sign * units, 0)
+    k = rng.integers(1, 64, size=(bh, bw))
+    for by in range(bh):
+        for bx in range(bw):
+            if kind[by, bx] == 1:
+                p[by, bx, k[by, bx]] = sign[by, bx] * units
+            elif kind[by, bx] >= 2:
+                p[by, bx] = dense_block(rng, units)
+    assert (np.abs(p).sum(axis=2) == units).all()
+    return p
+
+
 def random_layout(rng: np.random.Generator):
     """(samp, w, h, dri): 1..4 components, sampling factors 1..4, at most ten blocks per MCU (the syntax's limit)."""
     while True:

@@ -20,6 +20,7 @@ import functools
 import numpy as np
 import pytest
 
+from craft import blocks_at as _blocks_at  # (the three kinds of blocks at a budget: shared with test_tile_pair_gates)
 from libjpeg_amd import api, synth
 from test_fused420p_ring import CONTENTS, _luma
 from test_gpu_parity import _narrow12_chroma_limit
@@ -47,27 +48,6 @@ def _split(budget, which=0):
 
 
 # ------------------------------------------------------------------------------------------------ crafted streams
-def _blocks_at(rng, bh, bw, units):
-    """bh x bw blocks with sum |c| = units each, the three kinds of test_fused420p_ring._at_budget under one delta for all 64 terms."""
-    p = np.zeros((bh, bw, 64), np.int32)
-    kind = rng.integers(0, 4, size=(bh, bw))
-    sign = rng.choice([-1, 1], size=(bh, bw))
-    p[..., 0] = np.where(kind == 0, sign * units, 0)
-    k = rng.integers(1, 64, size=(bh, bw))
-    for by in range(bh):
-        for bx in range(bw):
-            if kind[by, bx] == 1:
-                p[by, bx, k[by, bx]] = sign[by, bx] * units
-            elif kind[by, bx] >= 2:
-                v = rng.integers(-40, 41, size=64)
-                v[0] = 0
-                v = (v * (units / max(1, int(np.abs(v).sum())))).astype(np.int64)
-                v[1] += np.sign(v[1] or 1) * (units - int(np.abs(v).sum()))  # spend the rest: the sum is exactly `units`
-                p[by, bx] = v
-    assert (np.abs(p).sum(axis=2) == units).all()
-    return p
-
-
 def _layout(layout, w, h, precision, tables):
     hs, vs = LAYOUTS[layout]
     return api.frame_layout(w, h, len(hs), hs, vs, tables[:2 if len(hs) > 1 else 1], precision=precision)
