@@ -546,6 +546,42 @@ int mijpeg_ragged_plan16(const mijpeg_info *infos, int n, int32_t *group, mijpeg
                          int64_t *coef_total);
 int mijpeg_decode_ragged_device16(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, int32_t *status);
 
+/* ---- planar output: component planes (C, H, W) instead of interleaved pixels -------------------------
+ * The planar twins of mijpeg_reconstruct_device, mijpeg_reconstruct_batch_device and mijpeg_reconstruct_ragged_device: same
+ * objects, same streams, same `sync`, same error codes (and the ragged call's per-image error rule); every picture those calls
+ * reconstruct comes back planar.  Component c of a picture goes to its own plane: sample (x, y) at plane + y * row_stride +
+ * x * sample_bytes (1, or 2 for 12-bit and JPEG XT frames: native-endian 16-bit samples), row_stride >= width * sample_bytes,
+ * any plane address, any stride.  Which kernel reconstructs a picture is decided as for the interleaved calls; an 8-bit
+ * three-component picture whose kernel is the fused 4:2:0 (packed, fast or safe), 4:2:2 (packed or wide) or 4:4:4 one is
+ * written to its planes by the planar flavour of that kernel's ragged launch -- one launch per kernel and flavour for all such
+ * pictures of the call, the pixel bytes cross HBM once -- a one-component picture is its own plane, and everything else (12 bit,
+ * JPEG XT, 4:4:0, 4:1:1, CMYK, no colour transformation, frames beyond the fused gates, MIJPEG_FLAG_FORCE_GENERIC) is
+ * reconstructed interleaved into a buffer of the object and taken apart by a second kernel.
+ * flags: MIJPEG_FLAG_FORCE_SAFE, MIJPEG_FLAG_FORCE_GENERIC (forces the two-pass route), MIJPEG_FLAG_NO_COLOR_TRANSFORM; others are
+ * ignored.  MIJPEG_ERR_INVALID_PARAMETER -- before anything is launched -- for NULL arguments, a row_stride below a line of
+ * samples, or a NULL plane of a component the picture has.
+ * planes[c]: first sample of component c; row_stride: bytes per plane line. */
+int mijpeg_reconstruct_planar_device(mijpeg_decoder *d, void *const planes[MIJPEG_MAX_COMPONENTS], int64_t row_stride, uint32_t flags, int sync);
+/* a decoded uniform batch as (N, C, H, W): frame f, component c at dst_device + f * frame_stride + c * plane_stride (bytes;
+ * plane_stride >= height * row_stride, frame_stride >= components * plane_stride).  A submitted batch is waited for
+ * (MIJPEG_FLAG_SPECULATIVE has no planar form). */
+int mijpeg_reconstruct_batch_planar_device(mijpeg_decoder *d, void *dst_device, int64_t frame_stride, int64_t plane_stride, int64_t row_stride,
+                                           uint32_t flags, int sync);
+/* after mijpeg_decode_ragged_device / ...16: image i, component c at planes[i * MIJPEG_MAX_COMPONENTS + c], its lines
+ * row_strides[i] bytes apart; planes[i * MIJPEG_MAX_COMPONENTS] == NULL (and images in error) are skipped. */
+int mijpeg_reconstruct_ragged_planar_device(mijpeg_decoder *d, void *const *planes, const int64_t *row_strides, uint32_t flags, int sync);
+/* What the object's last planar call did: pictures it wrote; of those, in one pass (a fused planar launch, or a one-component
+ * picture's own kernel) and in two; launches of the fused planar kernels, and of the kernel that takes interleaved pictures apart. */
+typedef struct mijpeg_planar_stats {
+  int32_t images, fused, two_pass, fused_launches, two_pass_launches;
+} mijpeg_planar_stats;
+int mijpeg_planar_stats_get(mijpeg_decoder *d, mijpeg_planar_stats *out);
+/* The second pass of the two-pass route on its own, on the object's stream (no wait): an interleaved picture in device memory
+ * (components x sample_bytes per pixel, src_row_stride bytes per line) -> its planes.  components 1..4, sample_bytes 1 or 2.
+ * (tools/planar_bench.py times it behind the interleaved launch; a client that holds interleaved pictures may use it as well.) */
+int mijpeg_deinterleave_device(mijpeg_decoder *d, const void *src_device, int64_t src_row_stride, int32_t width, int32_t height, int32_t components,
+                               int32_t sample_bytes, void *const planes[MIJPEG_MAX_COMPONENTS], int64_t row_stride);
+
 /* ---- stateless device entry points (inputs and outputs resident in HBM) -------------------- */
 
 /* Describes a batch of equally shaped frames whose coefficient planes are already on the device. */

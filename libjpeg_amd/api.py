@@ -80,6 +80,10 @@ class MijpegRaggedStats(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("images", "ragged", "fallbacks", "errors", "entropy_launches", "walk_launches", "recon_launches", "recon_single")]
 
 
+class MijpegPlanarStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("images", "fused", "two_pass", "fused_launches", "two_pass_launches")]
+
+
 class MijpegRaggedFrame(C.Structure):
     _fields_ = [("coef_base", C.c_int64), ("off_y", C.c_int64), ("off_cb", C.c_int64), ("off_cr", C.c_int64)] + \
                [(k, C.c_int32) for k in ("first_workgroup", "tiles_x", "tiles_y", "width", "height", "bw_y", "bh_y", "bw_c", "bh_c", "cw", "ch", "reserved")]
@@ -180,6 +184,11 @@ def lib():
         L.mijpeg_ragged_route.argtypes = [C.c_void_p, C.c_int, P(C.c_char_p)]
         L.mijpeg_reconstruct_ragged_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int]
         L.mijpeg_ragged_get_stats.argtypes = [C.c_void_p, P(MijpegRaggedStats)]
+        L.mijpeg_reconstruct_planar_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_uint32, C.c_int]
+        L.mijpeg_reconstruct_batch_planar_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_int]
+        L.mijpeg_reconstruct_ragged_planar_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int]
+        L.mijpeg_planar_stats_get.argtypes = [C.c_void_p, P(MijpegPlanarStats)]
+        L.mijpeg_deinterleave_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int64]
         L.mijpeg_ragged_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mijpeg_ragged_plan16.argtypes = L.mijpeg_ragged_plan.argtypes
         L.mijpeg_decode_ragged_device16.argtypes = L.mijpeg_decode_ragged_device.argtypes
@@ -708,6 +717,50 @@ class Decoder:
         st = MijpegRaggedStats()
         self._check(lib().mijpeg_ragged_get_stats(self._h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in MijpegRaggedStats._fields_}
+
+    # ---- planar output: component planes instead of interleaved pixels (include/mijpeg.h)
+    def reconstruct_planar_device(self, plane_ptrs, row_stride: int, flags: int = 0, sync: bool = True):
+        """mijpeg_reconstruct_planar_device: component c of the decoded picture -> plane_ptrs[c], row_stride bytes per plane line."""
+        _foreign_work_done()
+        ptrs = list(plane_ptrs) + [None] * (4 - len(plane_ptrs))
+        dst = (C.c_void_p * 4)(*[p or None for p in ptrs])
+        self._check(lib().mijpeg_reconstruct_planar_device(self._h, dst, row_stride, flags, 1 if sync else 0))
+
+    def reconstruct_batch_planar_device(self, dst_ptr: int, frame_stride: int, plane_stride: int, row_stride: int, flags: int = 0,
+                                        sync: bool = True, wait_foreign: bool = True):
+        """mijpeg_reconstruct_batch_planar_device: the decoded uniform batch as (N, C, H, W) with the given strides in bytes."""
+        if wait_foreign:
+            _foreign_work_done()
+        self._check(lib().mijpeg_reconstruct_batch_planar_device(self._h, dst_ptr, frame_stride, plane_stride, row_stride, flags, 1 if sync else 0))
+
+    def reconstruct_ragged_planar_device(self, plane_ptrs, row_strides, flags: int = 0, sync: bool = True, wait_foreign: bool = True):
+        """mijpeg_reconstruct_ragged_planar_device: plane_ptrs[i] = the plane addresses of image i (None / empty: skipped), one entry
+        per stream of the decode call; row_strides[i] bytes per line of its planes."""
+        n = len(plane_ptrs)
+        if n != getattr(self, "ragged_images", -1) or len(row_strides) != n:
+            raise ValueError(f"{n} destinations and {len(row_strides)} row strides for the {getattr(self, 'ragged_images', 0)} images of the ragged batch")
+        if wait_foreign:
+            _foreign_work_done()
+        flat = []
+        for p in plane_ptrs:
+            p = list(p or [])
+            flat += [q or None for q in p] + [None] * (4 - len(p))
+        dst = (C.c_void_p * (4 * n))(*flat)
+        rows = (C.c_int64 * n)(*row_strides)
+        self._check(lib().mijpeg_reconstruct_ragged_planar_device(self._h, dst, rows, flags, 1 if sync else 0))
+
+    def deinterleave_device(self, src_ptr: int, src_row_stride: int, width: int, height: int, components: int, sample_bytes: int, plane_ptrs,
+                            row_stride: int):
+        """mijpeg_deinterleave_device: an interleaved picture in device memory -> its planes, on the object's stream (no wait)."""
+        ptrs = list(plane_ptrs) + [None] * (4 - len(plane_ptrs))
+        dst = (C.c_void_p * 4)(*[p or None for p in ptrs])
+        self._check(lib().mijpeg_deinterleave_device(self._h, src_ptr, src_row_stride, width, height, components, sample_bytes, dst, row_stride))
+
+    def planar_stats(self) -> dict:
+        """What the object's last planar call did (mijpeg_planar_stats)."""
+        st = MijpegPlanarStats()
+        self._check(lib().mijpeg_planar_stats_get(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MijpegPlanarStats._fields_}
 
     def reconstruct_unsampled(self, comp: int, flags: int = 0) -> np.ndarray:
         """JPGTAG_DECODER_UPSAMPLE = false: component `comp` on its own sample grid, no colour transformation

@@ -264,6 +264,7 @@ try {
     release_big(d->device, false, d->coef_dev, d->coef_dev_cap * sizeof(int16_t));
     release_big(d->device, false, d->img_dev, d->img_dev_cap);
     if (d->ws_dev) (void)hipFree(d->ws_dev);
+    if (d->planar_tmp_dev) (void)hipFree(d->planar_tmp_dev);
     if (d->batch_quant_dev) (void)hipFree(d->batch_quant_dev);
     if (d->ent_dev) (void)hipFree(d->ent_dev);
     if (d->ent_host) (void)hipHostFree(d->ent_host);
@@ -1134,6 +1135,41 @@ try {
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(d, "mijpeg_reconstruct_batch_device"); }
 
+int mijpeg_reconstruct_batch_planar_device(mijpeg_decoder *d, void *dst_device, int64_t frame_stride, int64_t plane_stride, int64_t row_stride, uint32_t flags,
+                                           int sync)
+try {
+  if (!d || !dst_device) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device >= 0) HIP_TRY(d, hipSetDevice(d->device));
+  if (d->batch_frames < 0) { // submitted with mijpeg_submit_batch_device: wait for it now
+    const int rc = d->spec_active ? settle_speculation(d) : finish_batch(d);
+    if (rc) return rc;
+  }
+  if (d->batch_frames < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded batch: call mijpeg_decode_batch_device first");
+  const mijpeg_info &f = d->batch_info;
+  void *first[MIJPEG_MAX_COMPONENTS] = {dst_device, dst_device, dst_device, dst_device};
+  if (planar_check(f, first, row_stride) || plane_stride < row_stride * f.height || frame_stride < plane_stride * f.components)
+    return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "planar destination: the strides do not hold a line, a plane or a frame");
+  d->planar_stats = mijpeg_planar_stats{};
+  std::vector<PlanarItem> items((size_t)d->batch_frames);
+  for (int i = 0; i < d->batch_frames; i++) {
+    PlanarItem &it = items[(size_t)i];
+    it.info = &d->batch_info;
+    it.coef_dev = d->coef_dev + (int64_t)i * f.coef_count;
+    for (int c = 0; c < f.components; c++) it.planes[c] = (uint8_t *)dst_device + i * frame_stride + c * plane_stride;
+    for (int c = f.components; c < MIJPEG_MAX_COMPONENTS; c++) it.planes[c] = nullptr;
+    it.row_stride = row_stride;
+    if (d->batch_own_tables) {
+      it.own_deltas = d->batch_quant_host.data() + (size_t)i * 4 * 64;
+      it.own_deltas_dev = d->batch_quant_dev + (size_t)i * 4 * 64;
+    }
+  }
+  const int rc = reconstruct_planar_items(d, items.data(), d->batch_frames, flags & PLANAR_FLAGS, nullptr);
+  if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? "planar reconstruction: a kernel launch failed" : "planar reconstruction not available for this batch");
+  d->planar_stats.images = d->batch_frames;
+  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_batch_planar_device"); }
+
 const int16_t *mijpeg_device_coefficients(mijpeg_decoder *d) { return (d && d->uploaded) ? d->coef_dev : nullptr; }
 
 int mijpeg_last_error(mijpeg_decoder *d, const char **message)
@@ -1231,6 +1267,28 @@ try {
   if (!dst_device) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "destination pointer is NULL");
   return reconstruct_view(d, -1, dst_device, row_stride, flags & ~(MIJPEG_FLAG_DEVICE_OUTPUT | MIJPEG_FLAG_NO_UPSAMPLING), sync);
 } catch (...) { return boundary_catch(d, "mijpeg_reconstruct_device"); }
+
+int mijpeg_reconstruct_planar_device(mijpeg_decoder *d, void *const planes[MIJPEG_MAX_COMPONENTS], int64_t row_stride, uint32_t flags, int sync)
+try {
+  if (!d || !planes) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->parsed && planar_check(d->host.info, planes, row_stride))
+    return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "planar destination: a plane pointer is NULL or the row stride is smaller than a line of samples");
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_DEVICE, "decoder was created without a device: no reconstruction path");
+  if (!d->uploaded) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded coefficients: call mijpeg_decode_coefficients first");
+  HIP_TRY(d, hipSetDevice(d->device));
+  d->planar_stats = mijpeg_planar_stats{};
+  PlanarItem it;
+  it.info = &d->host.info;
+  it.coef_dev = d->coef_dev;
+  for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) it.planes[c] = c < d->host.info.components ? planes[c] : nullptr;
+  it.row_stride = row_stride;
+  it.xt = d->host.is_xt() ? &d->host.xt : nullptr;
+  const int rc = reconstruct_planar_items(d, &it, 1, flags & PLANAR_FLAGS, nullptr);
+  if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? "planar reconstruction: a kernel launch failed" : "planar reconstruction not available for this stream");
+  d->planar_stats.images = 1;
+  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_planar_device"); }
 
 void *mijpeg_host_alloc(size_t bytes)
 try {

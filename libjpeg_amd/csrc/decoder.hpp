@@ -138,6 +138,11 @@ struct mijpeg_decoder {
   mijpeg_ragged_stats ragged_stats{};
   uint8_t *ragged_desc_dev = nullptr, *ragged_desc_host = nullptr; // frame descriptor tables of the reconstruction launches (pinned copy)
   size_t ragged_desc_cap = 0, ragged_desc_host_cap = 0;
+  // planar calls (reconstruct_planar_items): the interleaved picture of the two-pass route; what the last call did.  (The tables
+  // of the fused planar launches travel in ragged_desc_dev / ragged_desc_host.)
+  uint8_t *planar_tmp_dev = nullptr;
+  size_t planar_tmp_cap = 0;
+  mijpeg_planar_stats planar_stats{};
   // ragged encode (encode_device.cpp): descriptors, coder arrays and coefficient store of a pass; plain stream and output arena;
   // pinned: descriptors on their way up and counts read back; the downloaded arena
   uint8_t *eragged_dev = nullptr, *eragged_out_dev = nullptr, *eragged_host = nullptr, *eragged_down = nullptr;

@@ -1,13 +1,16 @@
-// fused420_kernel.inc -- the text of fused420_kernel, included by kernels.hip (see there: once in mij, once in mij::ragged12)
+// fused420_kernel.inc -- the text of fused420_kernel, included by kernels.hip (see there: once in mij, once in mij::ragged12, once
+// in mij::planar, where PLANAR_OUT is true: component planes out)
 template <bool FAST, int MINW, bool QDEV, int P = 8, bool N12 = false, bool RAGGED = false>
 __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Args a)
 {
   static_assert(P == 8 || (P == 12 && FAST), "12-bit frames: FAST flavour only (the host checks the ranges)");
   static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
+  static_assert(!PLANAR_OUT || (RAGGED && P == 8), "planar output: the 8-bit ragged flavours");
   __shared__ __attribute__((aligned(16))) int cplane[2][F420_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
-  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<P == 8 ? MIJ_TILE_ORDER : 1>(a, stage_all);
+  PlanarBases pb{};
+  const TileCtx t = PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<P == 8 ? MIJ_TILE_ORDER : 1>(a, stage_all);
   if (t.padding) return;
 
   // the luma blocks of phase B are requested in front of phase A's transform (see F420P_MINW; two workgroups per CU leave the 32
@@ -24,7 +27,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Ar
   u32x4 rows[8];
   if (!PREFETCH) luma_loads();
   transpose_blocks(rows, t.stage, t.lane, yraw);
-  const BlockOut o = block_out<P == 12 ? 6 : 3>(a, t);
+  const BlockOut o = block_out<PLANAR_OUT ? 1 : P == 12 ? 6 : 3>(a, t);
   if (o.outside) return; // no barrier below this point
   int yv[64];
   if (FAST) dequant_idct_sparse<!QDEV && P == 8, P == 8>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 0, P == 8 ? LUMA_FOLD_R2 : 2048); // (8 bit: doubled sums, luma13)
@@ -81,7 +84,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Ar
             gg[x] = mad24(ur[x], -L_CR_G, mad24(ub[x], -L_CB_G, yk));
             bb[x] = mad24(ub[x], L_CB_B, yk);
           }
-          store_rgb8_line<STORE24_3X8>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
+          if (PLANAR_OUT) store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
+          else store_rgb8_line<STORE24_3X8>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
         } else {
           uint8_t *dst = o.out_frame + o.line_off(l, a);
           unsigned px[24];
@@ -91,7 +95,9 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Ar
             ycc_to_rgb<false>(yv[l * 8 + x], ub[x], ur[x], r, g, b);
             px[3 * x] = r; px[3 * x + 1] = g; px[3 * x + 2] = b;
           }
-          if (o.fast_store) {
+          if (PLANAR_OUT) {
+            store_planar8_bytes(o.out_frame, pb, o.line_off(l, a), px, o.fast_store, o.npx);
+          } else if (o.fast_store) {
             unsigned w[6];
 #pragma unroll
             for (int i = 0; i < 6; i++) w[i] = px[4 * i] | (px[4 * i + 1] << 8) | (px[4 * i + 2] << 16) | (px[4 * i + 3] << 24);

@@ -1007,6 +1007,69 @@ __device__ __forceinline__ void store_rgb8_line(uint8_t *base, unsigned off, con
   }
 }
 
+// ----------------------------------------------------------------------------------------------
+// Planar output: the ragged flavours of the 8-bit three-component kernels once more, in mij::planar, with component planes out
+// ----------------------------------------------------------------------------------------------
+// The kernels' texts (the .inc files) read PLANAR_OUT where their line tail begins; mij::planar declares its own, true, in
+// front of its inclusions, and nothing else about the texts differs -- the instantiations here fold every planar branch away.
+// A lane's eight pixels of a line are eight contiguous bytes in each plane, the sixteen lanes of a block row write 128 contiguous
+// bytes per plane: three 8-byte stores at plane + Y * row_stride + X0, no 24-byte pieces, no staging, no shifted copy.  Plane
+// bases and row strides are the caller's: gfx950 stores dwords at any address.
+constexpr bool PLANAR_OUT = false;
+constexpr bool PLANAR_NT = true; // the non-temporal hint on the plane stores
+struct PlanarBases { uint8_t *g, *b; }; // the frame's second and third plane (the first: Fused420Args::out, as ever); wave-uniform
+
+// tile_enter_ragged and the frame's entry of the PlanarFrame table, which a planar launch passes in Fused420Args::out.  (The frame's
+// position in the launch's tables is what RaggedFrame::qframe holds: every frame of a ragged launch brings its own deltas.)
+__device__ __forceinline__ TileCtx tile_enter_planar(Fused420Args &f, u32x4 (*stage_all)[128], PlanarBases &pb)
+{
+  const PlanarFrame *__restrict__ planes = reinterpret_cast<const PlanarFrame *>(f.out);
+  const TileCtx t = tile_enter_ragged(f, stage_all);
+  pb.g = planes[t.frame].g; pb.b = planes[t.frame].b;
+  return t;
+}
+
+// 8 bytes at base + off (uniform base, 32-bit lane offset: the `saddr` form, see store24_nt), any alignment
+__device__ __forceinline__ void store8_plane(uint8_t *__restrict__ base, unsigned off, unsigned lo, unsigned hi)
+{
+  const u32x2 v = {lo, hi};
+  if (PLANAR_NT) asm volatile("global_store_dwordx2 %0, %1, %2 nt" : : "v"(off), "v"(v), "s"(base) : "memory");
+  else asm volatile("global_store_dwordx2 %0, %1, %2" : : "v"(off), "v"(v), "s"(base) : "memory");
+}
+// The planar line tail of the fast flavours: eight pixels' colour sums (17 fraction bits, rounding inside) -> 8 bytes per plane at
+// off, or the first npx samples of each on the picture's right edge
+__device__ __forceinline__ void store_planar8_line(uint8_t *r, const PlanarBases &pb, unsigned off, const int (&rr)[8], const int (&gg)[8],
+                                                   const int (&bb)[8], bool fast_store, int npx)
+{
+  if (fast_store) {
+    store8_plane(r, off, ashr_sat_pack4<17>(rr[0], rr[1], rr[2], rr[3]), ashr_sat_pack4<17>(rr[4], rr[5], rr[6], rr[7]));
+    store8_plane(pb.g, off, ashr_sat_pack4<17>(gg[0], gg[1], gg[2], gg[3]), ashr_sat_pack4<17>(gg[4], gg[5], gg[6], gg[7]));
+    store8_plane(pb.b, off, ashr_sat_pack4<17>(bb[0], bb[1], bb[2], bb[3]), ashr_sat_pack4<17>(bb[4], bb[5], bb[6], bb[7]));
+  } else {
+    uint8_t *dr = r + off, *dg = pb.g + off, *db = pb.b + off;
+#pragma unroll
+    for (int x = 0; x < 8; x++)
+      if (x < npx) { dr[x] = (uint8_t)clamp255(rr[x] >> 17); dg[x] = (uint8_t)clamp255(gg[x] >> 17); db[x] = (uint8_t)clamp255(bb[x] >> 17); }
+  }
+}
+// ... and of the SAFE flavour: px = r0 g0 b0 r1 ... b7, every one a byte already
+__device__ __forceinline__ void store_planar8_bytes(uint8_t *r, const PlanarBases &pb, unsigned off, const unsigned (&px)[24], bool fast_store, int npx)
+{
+  uint8_t *const plane[3] = {r, pb.g, pb.b};
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    if (fast_store) {
+      store8_plane(plane[c], off, px[c] | (px[3 + c] << 8) | (px[6 + c] << 16) | (px[9 + c] << 24),
+                   px[12 + c] | (px[15 + c] << 8) | (px[18 + c] << 16) | (px[21 + c] << 24));
+    } else {
+      uint8_t *d = plane[c] + off;
+#pragma unroll
+      for (int x = 0; x < 8; x++)
+        if (x < npx) d[x] = (uint8_t)px[3 * x + c];
+    }
+  }
+}
+
 // The 12-bit RGB line tail: eight pixels' colour values, clamped to [0, 4095] -> 48 bytes r0 g0 b0 r1 ... b7 of 16-bit samples
 // (store48<TEMPORAL>: see there), or the first npx pixels sample by sample.  LINE_BY_LINE as above.
 __device__ __forceinline__ unsigned clamp12(int v) { return (unsigned)min(max(v, 0), 4095); }
@@ -1284,355 +1347,9 @@ __device__ __forceinline__ unsigned tap_sum_pk(unsigned a, unsigned w)
   return __builtin_bit_cast(unsigned, t);
 }
 
-// D2: the second pass of every transform on v_dot2 (idct_columns_dot2; admitted by the host where sum |c| q <= 1476 in all three
-// components: plan_reconstruct in capi.cpp)
-template <int MINW, bool QDEV, bool D2 = false, bool RAGGED = false>
-__global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420Args a)
-{
-  static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
-  __shared__ __attribute__((aligned(16))) unsigned cpair[F420_CROWS * F420_CPITCH];
-  __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
+#include "fused420p_kernel.inc"
 
-  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
-  if (t.padding) return;
-  const int tid = t.tid, lane = t.lane, wave = t.wave, frame = t.frame, tx = t.tx, ty = t.ty;
-  u32x4 *stage = t.stage;
-  const int16_t *__restrict__ coef = t.coef;
-  // the luma blocks of phase B are requested early: their latency hides behind phase A's transform (see F420P_MINW)
-  u32x4 yraw[8];
-
-  // ------------------------------------------------------------------ phase A: chroma -> LDS halves
-  // Of the tile's 10 x 10 chroma blocks per component the filters read the 8 x 8 interior in full, but of the ring around it only
-  // the column, the line or the single sample that touches the interior.  The four waves take four roles (wave-uniform: no
-  // divergence between the transforms): the interior of Cb, the interior of Cr, the ring of Cb, the ring of Cr.  The roles rotate
-  // with the workgroup so that every SIMD of a CU sees the heavier interior waves and the lighter ring waves alike.
-  // LDS line pr <-> chroma line ty * 64 + pr - 1, column pc <-> chroma column tx * 64 + pc - 4.
-  {
-    const int role = (wave + (int)((blockIdx.x >> 3) + (blockIdx.x >> 8))) & 3; // (>> 3: workgroups of one XCD; >> 8: of one CU, roughly)
-    const int comp = role & 1; // 0 = Cb (low halves), 1 = Cr (high halves); wave-uniform
-    const int16_t *__restrict__ plane = coef + (comp ? a.off_cr : a.off_cb);
-    const char *pbase = reinterpret_cast<const char *>(plane) + (lane & 7) * 16;
-    const int *q = frame_deltas<QDEV>(a, frame, 1 + comp);
-    short *cp = reinterpret_cast<short *>(cpair) + comp; // this component's half of every dword
-    const int gx0 = tx * 8, gy0 = ty * 8;                // the interior's first block
-    const int nb = lane >> 3;
-    if (role < 2) {
-      // interior: local block n = (lane >> 3) + 8 m is column lane >> 3 of row m -- one load covers a row's 1 KB
-      u32x4 rows[8];
-      const unsigned xoff = (unsigned)min(gx0 + nb, a.bw_c - 1) * 128u;
-      fetch_blocks(rows, stage, lane, [&](int m) -> const u32x4 * {
-        const int yy = min(gy0 + m, a.bh_c - 1);
-        return reinterpret_cast<const u32x4 *>(pbase + ((unsigned)(yy * a.bw_c) * 128u + xoff));
-      });
-      load_tile_blocks(yraw, t, coef + a.off_y, a.bw_y, a.bh_y);
-      const int cbx = lane & 7, cby = lane >> 3;
-      if (gx0 + cbx < a.bw_c && gy0 + cby < a.bh_c) {
-        int at = (8 * cby + 1) * F420_CPITCH + 8 * cbx + 4; // the lane's first sample
-        // (per-frame tables: the index is formed here and held across the transform.  The build then allocates the 133 registers
-        // this instantiation had before the ring was split off, the count tests/test_ragged_batch.py holds it to; 132 otherwise.
-        // Three workgroups per CU either way.)
-        if (QDEV) asm volatile("" : "+v"(at));
-        int v[64];
-        dequant_idct_sparse<!QDEV, false, D2>(rows, q, v);
-        short *dst = cp + 2 * at; // one base per lane: the 64 stores take immediate offsets
-#pragma unroll
-        for (int r = 0; r < 8; r++)
-#pragma unroll
-          for (int x = 0; x < 8; x++) dst[2 * (r * F420_CPITCH + x)] = (short)v[r * 8 + x];
-      }
-    } else {
-      // ring.  Columns and corners, lane-owns-block: block n = 0..15 is the left (n even) or right (n odd) neighbour of interior
-      // row n >> 1; n = 16..19 are the corners (bit 0: right, bit 1: below).  Lines, on the fetching lanes: the blocks above and
-      // below interior column lane >> 3 (dequant_idct_line8).  All five requests leave before the luma request.
-      auto chunk = [&](int gx, int gy) -> u32x4 {
-        const int xx = min(max(gx, 0), a.bw_c - 1), yy = min(max(gy, 0), a.bh_c - 1);
-        return *reinterpret_cast<const u32x4 *>(pbase + (unsigned)((yy * a.bw_c + xx) * 128));
-      };
-      const int gxs = (nb & 1) ? gx0 + 8 : gx0 - 1;
-      const u32x4 side0 = chunk(gxs, gy0 + (nb >> 1)), side1 = chunk(gxs, gy0 + 4 + (nb >> 1));
-      const u32x4 corner = chunk(gxs, (nb & 2) ? gy0 + 8 : gy0 - 1);
-      const u32x4 above = chunk(gx0 + nb, gy0 - 1), below = chunk(gx0 + nb, gy0 + 8);
-      load_tile_blocks(yraw, t, coef + a.off_y, a.bw_y, a.bh_y);
-      {
-        u32x4 rows[8];
-        const int k = lane & 7;
-        stage[nb * 8 + (k ^ nb)] = side0;
-        stage[(nb + 8) * 8 + (k ^ nb)] = side1;
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 16) {
-#pragma unroll
-          for (int r = 0; r < 8; r++) rows[r] = stage[lane * 8 + (r ^ (lane & 7))];
-        }
-        __builtin_amdgcn_wave_barrier();
-        stage[nb * 8 + (k ^ nb)] = corner; // (blocks 4..7 repeat 0..3 and are not read)
-        __builtin_amdgcn_wave_barrier();
-        if (lane >= 16 && lane < 20) {
-#pragma unroll
-          for (int r = 0; r < 8; r++) rows[r] = stage[(lane - 16) * 8 + (r ^ (lane - 16))];
-        }
-        __builtin_amdgcn_wave_barrier();
-        const bool right = lane & 1, is_corner = lane >= 16, low = lane & 2;
-        const int gx = right ? gx0 + 8 : gx0 - 1, gy = is_corner ? (low ? gy0 + 8 : gy0 - 1) : gy0 + (lane >> 1);
-        if (lane < 20 && gx >= 0 && gx < a.bw_c && gy >= 0 && gy < a.bh_c) {
-          int col[8];
-          dequant_idct_column(rows, q, !right, col); // left neighbour: its last column, right one: its first
-          const int pc = right ? 68 : 3;
-          if (is_corner) {
-            cp[2 * ((low ? F420_CROWS - 1 : 0) * F420_CPITCH + pc)] = (short)(low ? col[0] : col[7]);
-          } else {
-            short *dst = cp + 2 * ((8 * (lane >> 1) + 1) * F420_CPITCH + pc);
-#pragma unroll
-            for (int r = 0; r < 8; r++) dst[2 * r * F420_CPITCH] = (short)col[r];
-          }
-        }
-      }
-      {
-        constexpr int W[8] = {512, FIX9(1.501321110) - FIX9(0.899976223) - FIX9(0.390180644) + FIX9(1.175875602), FIX9(0.541196100) + FIX9(0.765366865),
-                              FIX9(1.175875602), 512, FIX9(1.175875602) - FIX9(0.390180644), FIX9(0.541196100), FIX9(1.175875602) - FIX9(0.899976223)};
-        const int k = lane & 7;
-        // the deltas of row k, per lane: read from the kernel argument segment itself (see fused440_kernel)
-        typedef const __attribute__((address_space(4))) int kernarg_int;
-        int qrow[8];
-        if (QDEV) {
-          const int *qk = q + k * 8;
-#pragma unroll
-          for (int i = 0; i < 8; i++) qrow[i] = qk[i];
-        } else {
-          kernarg_int *qk = (kernarg_int *)__builtin_amdgcn_kernarg_segment_ptr() + (offsetof(Fused420Args, q) / sizeof(int) + (1 + comp) * QROW + k * 8);
-#pragma unroll
-          for (int i = 0; i < 8; i++) qrow[i] = qk[i];
-        }
-        const int weight = W[k];
-        int line[8];
-        short *dst = cp + 2 * (8 * nb + 4 + k);
-        const bool col_ok = gx0 + nb < a.bw_c;
-        auto mine = [&](const int (&l)[8]) { // line[k] without a register-indexed access
-          const int a01 = (k & 1) ? l[1] : l[0], a23 = (k & 1) ? l[3] : l[2], a45 = (k & 1) ? l[5] : l[4], a67 = (k & 1) ? l[7] : l[6];
-          const int lo = (k & 2) ? a23 : a01, hi = (k & 2) ? a67 : a45;
-          return (short)((k & 4) ? hi : lo);
-        };
-        dequant_idct_line8(above, qrow, (k & 1) ? -weight : weight, line); // the block above: its last line (even - odd)
-        if (col_ok && gy0 > 0) dst[0] = mine(line);
-        dequant_idct_line8(below, qrow, weight, line); // the block below: its first line (even + odd)
-        if (col_ok && gy0 + 8 < a.bh_c) dst[2 * (F420_CROWS - 1) * F420_CPITCH] = mine(line);
-      }
-    }
-  }
-  __syncthreads();
-
-  // ------------------------------------------------------------------ edge fix-up (uniform branch)
-  {
-    const int last_col = a.cw - 1 - tx * 64; // last valid chroma column, tile-relative
-    const int last_row = a.ch - 1 - ty * 64;
-    const bool edge = (tx == 0) | (ty == 0) | (last_col < 64) | (last_row < 64);
-    if (edge) {
-      if (tid < F420_CROWS) { // one thread per stored line: replicate columns
-        unsigned *p = cpair + tid * F420_CPITCH;
-        if (tx == 0) p[3] = p[4];
-        if (last_col < 64) {
-          const unsigned v = p[last_col + 4];
-          for (int pc = last_col + 5; pc <= 68; pc++) p[pc] = v;
-        }
-      }
-      __syncthreads();
-      if (tid < F420_CROWS) { // one thread per stored column: replicate lines
-        auto at = [&](int pr) -> unsigned & { return cpair[pr * F420_CPITCH + 3 + tid]; };
-        if (ty == 0) at(0) = at(1);
-        if (last_row < 64) {
-          const unsigned v = at(last_row + 1);
-          for (int pr = last_row + 2; pr < F420_CROWS; pr++) at(pr) = v;
-        }
-      }
-      __syncthreads();
-    }
-  }
-
-  // ------------------------------------------------------------------ phase B: luma, upsampling, colour
-  u32x4 rows[8];
-  transpose_blocks(rows, stage, lane, yraw);
-  const BlockOut o = block_out<3>(a, t);
-  if (o.outside) return; // no barrier below this point
-  int yv[64];
-  dequant_idct_sparse<!QDEV, true, D2>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
-
-  const int bx = o.bx, by = o.by, npx = o.npx, nln = o.nln;
-  uint8_t *__restrict__ out_frame = o.out_frame;
-  const unsigned out_off = o.out_off;
-  const bool fast_store = o.fast_store;
-  // chroma window of this block: lines pr = 4 by + m (+0 top, +1 cur, +2 bot), columns pc = 4 bx + 3 + j
-  const unsigned *c_base = cpair + (4 * by) * F420_CPITCH + 4 * bx;
-
-  // Blocks that lie wholly inside the picture -- all of them, for every wave but those on the right and bottom edges -- take a
-  // copy of the loop without the per-line exec masks (wave-uniform choice: one ballot)
-  // (a third copy, FULL with every lane active, for frames whose lines do not all start on a dword: store24_nt_shifted)
-  const unsigned base_lo = (unsigned)(uintptr_t)out_frame;
-  auto lines = [&](auto full_tag, auto shift_tag, auto staged_tag) {
-    constexpr bool FULL = decltype(full_tag)::value, SHIFTED = decltype(shift_tag)::value, STAGED = decltype(staged_tag)::value;
-    // STAGED: whole waves of whole blocks send a line's pixels through the wave's (idle) fetch staging buffer -- sixteen 24-byte
-    // pieces per block row in, 96 chunks of 16 contiguous bytes out -- so that every store instruction writes whole aligned runs of
-    // the four 384-byte line segments instead of 16 and then 8 bytes of every lane's 24: tools/microbench/stream_ceiling --staged puts
-    // the kernel's access pattern at 0.74-0.755 of 8 TB/s with such stores, 0.71-0.72 with the pieces (profiles/r06/staged_stores.txt).
-    // Chunk c of the wave's 96 per line is bytes 16 (c % 24) .. of block row c / 24's segment; lanes 0..31 own a second one
-    unsigned so0 = 0, so1 = 0;
-    if (STAGED) {
-      const unsigned wave_off = (unsigned)((ty * F420_TILE_BLOCKS + wave * 4) * 8) * (unsigned)a.row_stride + (unsigned)(tx * F420_TILE_BLOCKS * 8) * 3u;
-      const unsigned c1 = 64u + (unsigned)lane;
-      so0 = wave_off + ((unsigned)lane / 24u) * 8u * (unsigned)a.row_stride + ((unsigned)lane % 24u) * 16u;
-      so1 = wave_off + (c1 / 24u) * 8u * (unsigned)a.row_stride + (c1 % 24u) * 16u;
-    }
-    unsigned cT[6], cC[6], cB[6];
-    load6(c_base, cT);
-    load6(c_base + F420_CPITCH, cC);
-#pragma unroll
-    for (int m = 0; m < 4; m++) {
-      load6(c_base + (m + 2) * F420_CPITCH, cB);
-      // 3 * centre + rounding, both roundings, for the two lines that share the centre line
-      unsigned w1[6], w2[6];
-#pragma unroll
-      for (int j = 0; j < 6; j++) { w1[j] = centre3_pk(cC[j], 1); w2[j] = centre3_pk(cC[j], 2); }
-#pragma unroll
-      for (int half = 0; half < 2; half++) {
-        const int l = 2 * m + half;
-        // vertical filter (upsampler.cpp:149-165), both components at once
-        unsigned v[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) v[j] = tap_sum_pk(half ? cB[j] : cT[j], ((j & 1) ^ half) ? w1[j] : w2[j]);
-        // horizontal filter in place (upsampler.cpp:291-303); src[k] = v[k + 1]
-        unsigned u[8];
-        u[7] = tap13_pk(v[5], v[4], 1);
-        u[6] = tap13_pk(v[3], v[4], 2);
-        u[5] = tap13_pk(v[4], v[3], 1);
-        u[4] = tap13_pk(v[2], v[3], 2);
-        u[3] = tap13_pk(v[3], v[2], 1);
-        u[2] = tap13_pk(v[1], v[2], 2);
-        u[1] = tap13_pk(u[2], v[1], 1); // src[1] has already been overwritten by out[2]
-        u[0] = tap13_pk(v[0], v[1], 2);
-        if (FULL || l < nln) {
-          int rr[8], gg[8], bb[8];
-#pragma unroll
-          for (int x = 0; x < 8; x++) {
-            const int yk = luma13(yv[l * 8 + x]); // (level shift and rounding are inside: LUMA_FOLD_R2)
-            rr[x] = mad16_hi(u[x], L_CR_R, yk); // still scaled by 2^17
-            bb[x] = mad16_lo(u[x], L_CB_B, yk);
-            gg[x] = dot2_16(u[x], -L_CB_G, -L_CR_G, yk);
-          }
-          if (FULL || fast_store) {
-            unsigned w[6];
-            rgb_shift17_sat_pack(rr, gg, bb, w);
-            const unsigned off = out_off + (unsigned)l * (unsigned)a.row_stride;
-            const int m = SHIFTED ? (int)__builtin_amdgcn_readfirstlane((base_lo + (unsigned)l * (unsigned)a.row_stride) & 3u) : 0;
-            if (STAGED) {
-              unsigned *sw = reinterpret_cast<unsigned *>(stage);
-              u32x2 *pw = reinterpret_cast<u32x2 *>(sw + lane * 6);
-              pw[0] = u32x2{w[0], w[1]}; pw[1] = u32x2{w[2], w[3]}; pw[2] = u32x2{w[4], w[5]};
-              __builtin_amdgcn_wave_barrier();
-              const u32x4 v0 = *reinterpret_cast<const u32x4 *>(sw + lane * 4);
-              const u32x4 v1 = *reinterpret_cast<const u32x4 *>(sw + ((lane & 31) + 64) * 4);
-              __builtin_amdgcn_wave_barrier();
-              store16_nt(out_frame, so0 + (unsigned)l * (unsigned)a.row_stride, v0);
-              if (lane < 32) store16_nt(out_frame, so1 + (unsigned)l * (unsigned)a.row_stride, v1);
-            }
-            else if (SHIFTED && m) store24_nt_shifted(out_frame, off, w, bx, m);
-            else if (SHIFTED) store24_nt<false>(out_frame, off, w);
-            else store24_nt(out_frame, off, w);
-          } else {
-            store_rgb8_partial(out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride), rr, gg, bb, npx);
-          }
-        }
-      }
-      // slide the three-line window
-#pragma unroll
-      for (int j = 0; j < 6; j++) { cT[j] = cC[j]; cC[j] = cB[j]; }
-    }
-  };
-  const bool whole = __builtin_amdgcn_ballot_w64(npx != 8 || nln != 8) == 0;
-  if (whole && ((base_lo | (unsigned)a.row_stride) & 3u) && __builtin_amdgcn_ballot_w64(true) == ~0ull) lines(std::true_type{}, std::true_type{}, std::false_type{});
-  else if (whole && __builtin_amdgcn_ballot_w64(true) == ~0ull) lines(std::true_type{}, std::false_type{}, std::true_type{});
-  else if (whole) lines(std::true_type{}, std::false_type{}, std::false_type{});
-  else lines(std::false_type{}, std::false_type{}, std::false_type{});
-}
-
-// ==============================================================================================
-// fused 4:2:2 kernel (Y 1x1, Cb/Cr subsampled 2x1), packed chroma
-// ==============================================================================================
-// fused420p_kernel without the vertical direction: the chroma planes have the luma plane's height, so a 128x128 tile
-// needs (8 + 2) x 16 chroma blocks per component -- 1.25 rounds of transforms for the four waves where 4:2:0 needs
-// one -- and no halo lines; the samples of a line go through the horizontal filter only.  Same gate as the packed
-// 4:2:0 flavour (FAST arithmetic, chroma range_max < 2047), same store path.  Algorithmic bytes: 4 B in + 3 B out per pixel.
-// WIDE: the samples still travel through LDS as int16 pairs (|sample * 16| <= 4 * range_max < 2^15 for range_max < 8190,
-// the fused 4:4:4 kernel's bound, which legitimate 8-bit content cannot exceed: sum |c| q <= 8 sqrt(64 * 128^2) by
-// Cauchy-Schwarz), but the filter runs on unpacked 32-bit values: frames between the packed gate (2047) and 8190 --
-// saturated colours with hard edges -- stay on a fused kernel instead of falling to the generic pair.
-template <int MINW, bool QDEV, bool WIDE, bool RAGGED = false>
-__global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(Fused420Args a)
-{
-  static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
-  __shared__ __attribute__((aligned(16))) unsigned cpair[F422_CROWS * F420_CPITCH];
-  __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-
-  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
-  if (t.padding) return;
-
-  // ------------------------------------------------------------------ phase A: chroma -> LDS halves (Cb low, Cr high), edge fix-up
-  f422_chroma_to_lds<QDEV, !QDEV>(a, t, LdsPairHalf(cpair, t.wave >> 1));
-  __syncthreads();
-  f422_chroma_edges<1>(a, cpair, t.tid, t.tx);
-
-  // ------------------------------------------------------------------ phase B: luma, upsampling, colour
-  u32x4 rows[8];
-  fetch_tile_blocks(rows, t, t.coef + a.off_y, a.bw_y, a.bh_y);
-  const BlockOut o = block_out<3>(a, t);
-  if (o.outside) return; // no barrier below this point
-  int yv[64];
-  dequant_idct_sparse<!QDEV, true>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 0, LUMA_FOLD_R2);
-
-  // chroma window of this block: lines pr = 8 by + l, columns pc = 4 bx + 3 + j
-  const unsigned *c_base = cpair + (8 * o.by) * F420_CPITCH + 4 * o.bx;
-#pragma unroll
-  for (int l = 0; l < 8; l++) {
-    {
-      // no vertical filter (VerticalFilterCore<1>, upsampler.cpp:118-131: a copy); horizontal filter in place
-      // (upsampler.cpp:291-303); src[k] = v[k + 1]
-      unsigned v[6];
-      load6(c_base + l * F420_CPITCH, v);
-      unsigned u[8];
-      int ub[8], ur[8]; // WIDE: the two components on their own, 32 bits
-      if (WIDE) {
-        int vb[6], vr[6];
-#pragma unroll
-        for (int j = 0; j < 6; j++) { vb[j] = (int)(short)(v[j] & 0xffffu); vr[j] = (int)v[j] >> 16; }
-        hfilter8(vb, ub);
-        hfilter8(vr, ur);
-      } else {
-        u[7] = tap13_pk(v[5], v[4], 1);
-        u[6] = tap13_pk(v[3], v[4], 2);
-        u[5] = tap13_pk(v[4], v[3], 1);
-        u[4] = tap13_pk(v[2], v[3], 2);
-        u[3] = tap13_pk(v[3], v[2], 1);
-        u[2] = tap13_pk(v[1], v[2], 2);
-        u[1] = tap13_pk(u[2], v[1], 1); // src[1] has already been overwritten by out[2]
-        u[0] = tap13_pk(v[0], v[1], 2);
-      }
-      if (l < o.nln) {
-        int rr[8], gg[8], bb[8];
-#pragma unroll
-        for (int x = 0; x < 8; x++) {
-          const int yk = luma13(yv[l * 8 + x]); // (level shift and rounding are inside: LUMA_FOLD_R2)
-          if (WIDE) {
-            rr[x] = mad24(ur[x], L_CR_R, yk); // still scaled by 2^17
-            bb[x] = mad24(ub[x], L_CB_B, yk);
-            gg[x] = mad24(ur[x], -L_CR_G, mad24(ub[x], -L_CB_G, yk));
-          } else {
-            rr[x] = mad16_hi(u[x], L_CR_R, yk); // still scaled by 2^17
-            bb[x] = mad16_lo(u[x], L_CB_B, yk);
-            gg[x] = dot2_16(u[x], -L_CB_G, -L_CR_G, yk);
-          }
-        }
-        store_rgb8_line<STORE24_NT>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
-      }
-    }
-  }
-}
+#include "fused422_kernel.inc"
 
 // 12-bit flavour of the 4:2:2 kernel (SOF1, P = 12; 16-bit samples out, 4 B in + 6 B out per pixel): the same tile, the chroma
 // samples as 32-bit values in two LDS planes (a 12-bit chroma sample times 16 does not fit 16 bits: 72 KB + the fetch staging
@@ -2368,74 +2085,17 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
   }
 }
 
-// ==============================================================================================
-// fused 4:4:4 kernel (three components, no subsampling, YCbCr): ReconstructUnsampled,
-// control/blockbitmaprequester.cpp:1013-1074
-// ==============================================================================================
-// One lane owns one block POSITION and transforms its Cb, Cr and Y blocks one after the other; the two
-// chroma results are kept as packed int16 pairs (32 + 32 VGPRs) that the colour multiply-adds read half by half
-// (v_mad_i32_i16 op_sel), the luma result stays in 64 VGPRs.  No barrier, no halo, LDS only for the coalesced
-// block fetch.  FAST arithmetic only, and only when the host's range check bounds every chroma sample by
-// 4 * range_max < 32768 (so the packing is exact); everything else takes the generic two-kernel path.
-// Algorithmic bytes: 3 x 2 B in + 3 B out = 9 B/pixel.
-template <int MINW, bool QDEV, bool RAGGED = false>
-__global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(Fused420Args a)
-{
-  static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
-  __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
-  if (t.padding) return;
-  const int frame = t.frame;
+#include "fused444_kernel.inc"
 
-  // all three planes have the same geometry (bw_y x bh_y blocks)
-  auto fetch = [&](u32x4 (&rows)[8], int64_t plane_off) { fetch_tile_blocks(rows, t, t.coef + plane_off, a.bw_y, a.bh_y); };
-
-  unsigned cbp[32], crp[32];
-  {
-    u32x4 rows[8];
-    int v[64];
-    fetch(rows, a.off_cb);
-    dequant_idct_sparse<!QDEV>(rows, frame_deltas<QDEV>(a, frame, 1), v);
-#pragma unroll
-    for (int i = 0; i < 32; i++) cbp[i] = pack_lo16_now(v[2 * i + 1], v[2 * i]);
-    __builtin_amdgcn_sched_barrier(0); // keep the next component's loads from being hoisted above this transform (register pressure)
-    fetch(rows, a.off_cr);
-    dequant_idct_sparse<!QDEV>(rows, frame_deltas<QDEV>(a, frame, 2), v);
-#pragma unroll
-    for (int i = 0; i < 32; i++) crp[i] = pack_lo16_now(v[2 * i + 1], v[2 * i]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  const BlockOut o = block_out<3>(a, t);
-  int yv[64];
-  {
-    u32x4 rows[8];
-    fetch(rows, a.off_y);
-    if (o.outside) return;
-    dequant_idct_sparse<!QDEV, true>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
-  }
-#pragma unroll
-  for (int l = 0; l < 8; l++) {
-    if (l < o.nln) {
-      int rr[8], gg[8], bb[8];
-#pragma unroll
-      for (int x = 0; x < 8; x++) {
-        const int yk = luma13(yv[l * 8 + x]); // (level shift and rounding are inside: LUMA_FOLD_R2)
-        const unsigned cb2 = cbp[(l * 8 + x) >> 1], cr2 = crp[(l * 8 + x) >> 1];
-        if (x & 1) {
-          rr[x] = mad16_hi(cr2, L_CR_R, yk);
-          gg[x] = mad16_hi(cr2, -L_CR_G, mad16_hi(cb2, -L_CB_G, yk));
-          bb[x] = mad16_hi(cb2, L_CB_B, yk);
-        } else {
-          rr[x] = mad16_lo(cr2, L_CR_R, yk);
-          gg[x] = mad16_lo(cr2, -L_CR_G, mad16_lo(cb2, -L_CB_G, yk));
-          bb[x] = mad16_lo(cb2, L_CB_B, yk);
-        }
-      }
-      // (LINE_BY_LINE: one line at a time -- do not interleave the lines' temporaries)
-      store_rgb8_line<STORE24_3X8, true>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
-    }
-  }
-}
+// The planar flavours (see PLANAR_OUT): the four texts once more.  launch_fused_planar instantiates the six ragged ones; they stand
+// in a namespace of their own for ragged12's reason -- tests/test_ragged_batch.py pins the set of mij::fused*_kernel names.
+namespace planar {
+constexpr bool PLANAR_OUT = true;
+#include "fused420_kernel.inc"
+#include "fused420p_kernel.inc"
+#include "fused422_kernel.inc"
+#include "fused444_kernel.inc"
+} // namespace planar
 
 // 12-bit flavour (SOF1, P = 12; 16-bit samples out, 6 B in + 6 B out per pixel): the same decomposition with the chroma blocks kept as
 // 32-bit values (64 + 64 VGPRs: a 12-bit chroma sample times 16 does not fit 16 bits), two waves per SIMD.  The colour stage is
@@ -3797,6 +3457,28 @@ int launch_fused_ragged(const ReconPlan &p, const Fused420Args &a, unsigned work
   return (int)hipGetLastError();
 }
 
+bool planar_twin(const ReconPlan &p)
+{
+  return p.kernel == Recon::FUSED420P || p.kernel == Recon::FUSED420 || p.kernel == Recon::FUSED422 || p.kernel == Recon::FUSED444;
+}
+
+// launch_fused_ragged with component planes out (a.out: the PlanarFrame table).  The occupancy of the interleaved ragged flavours.
+int launch_fused_planar(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t s)
+{
+  if (!a.ragged || !a.ragged_first || !a.qdev || !a.out || a.frames < 1) return -1;
+  if (workgroups == 0) return 0;
+  void (*kernel)(Fused420Args) = nullptr;
+  switch (p.kernel) {
+  case Recon::FUSED420P: kernel = planar::fused420p_kernel<3, true, false, true>; break;
+  case Recon::FUSED420: kernel = p.fast ? planar::fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : planar::fused420_kernel<false, 2, true, 8, false, true>; break;
+  case Recon::FUSED422: kernel = p.wide ? planar::fused422_kernel<3, true, true, true> : planar::fused422_kernel<3, true, false, true>; break;
+  case Recon::FUSED444: kernel = planar::fused444_kernel<2, true, true>; break;
+  default: return -1; // (no planar twin)
+  }
+  hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(F420_THREADS), 0, s, a);
+  return (int)hipGetLastError();
+}
+
 // per-frame tables as the client hands them over (u16 deltas, [frames][4][64]) -> the operands of the transforms (<< 4, int32)
 __global__ __launch_bounds__(256) void expand_deltas_kernel(const uint16_t *__restrict__ in, int32_t *__restrict__ out, int n)
 {
@@ -3983,6 +3665,78 @@ int launch_scatter_rect(const ScatterArgs &a, hipStream_t stream)
 {
   if (a.w <= 0 || a.h <= 0) return 0;
   hipLaunchKernelGGL(scatter_rect_kernel, dim3((a.w + 255) / 256, a.h), dim3(256), 0, stream, a);
+  return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Interleaved frame -> component planes: the second pass of the planar requests whose kernel has no planar flavour
+// ------------------------------------------------------------------------------------------------
+// One lane takes eight pixels of a line -- 8 * NC * SB contiguous bytes, read in 16-byte pieces (and one of 8 where that leaves a
+// remainder; at any address) -- and writes one store of 8 * SB bytes per plane: the 64 lanes of a wave read 64 * 8 * NC * SB
+// contiguous bytes and write 512 * SB contiguous bytes per plane.  The last lane of a line copies its npx < 8 pixels sample by sample.
+constexpr int DEINT_LINES = 4; // lines per workgroup (one wave each)
+template <int NC, int SB>
+__global__ __launch_bounds__(64 * DEINT_LINES) void deinterleave_kernel(const DeinterleaveArgs a)
+{
+  constexpr int BYTES = 8 * NC * SB;
+  const int chunk = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * DEINT_LINES + threadIdx.y;
+  const int x0 = chunk * 8;
+  if (x0 >= a.width || y >= a.height) return;
+  const uint8_t *__restrict__ src = a.src + (int64_t)y * a.src_row + (int64_t)chunk * BYTES;
+  const int64_t dst_off = (int64_t)y * a.dst_row + (int64_t)x0 * SB;
+  const int npx = min(8, a.width - x0);
+  if (npx == 8) {
+    unsigned w[BYTES / 4];
+#pragma unroll
+    for (int i = 0; i < BYTES / 16; i++) {
+      const u32x4 v = reinterpret_cast<const u32x4_any *>(src)[i];
+      w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+    }
+    if (BYTES % 16) {
+      const u32x2 v = *reinterpret_cast<const u32x2_any *>(src + (BYTES - 8));
+      w[BYTES / 4 - 2] = v.x; w[BYTES / 4 - 1] = v.y;
+    }
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      unsigned o[2 * SB];
+#pragma unroll
+      for (int k = 0; k < 2 * SB; k++) o[k] = 0;
+#pragma unroll
+      for (int x = 0; x < 8; x++) {
+        const int e = x * NC + c; // the sample's index in the lane's piece
+        if (SB == 1) o[x >> 2] |= ((w[e >> 2] >> (8 * (e & 3))) & 0xffu) << (8 * (x & 3));
+        else o[x >> 1] |= ((w[e >> 1] >> (16 * (e & 1))) & 0xffffu) << (16 * (x & 1));
+      }
+      uint8_t *dst = a.dst[c] + dst_off;
+      if (SB == 1) *reinterpret_cast<u32x2_any *>(dst) = u32x2{o[0], o[1]};
+      else *reinterpret_cast<u32x4_any *>(dst) = u32x4{o[0], o[1], o[2 * SB - 2], o[2 * SB - 1]};
+    }
+  } else {
+    for (int x = 0; x < npx; x++)
+#pragma unroll
+      for (int c = 0; c < NC; c++)
+#pragma unroll
+        for (int k = 0; k < SB; k++) a.dst[c][dst_off + x * SB + k] = src[(x * NC + c) * SB + k];
+  }
+}
+
+int launch_deinterleave(const DeinterleaveArgs &a, hipStream_t stream)
+{
+  if (a.width <= 0 || a.height <= 0) return 0;
+  if (a.ncomp < 1 || a.ncomp > 4 || (a.sample_bytes != 1 && a.sample_bytes != 2)) return -1;
+  const dim3 grid((unsigned)((a.width + 511) / 512), (unsigned)((a.height + DEINT_LINES - 1) / DEINT_LINES)), block(64, DEINT_LINES);
+  void (*kernel)(const DeinterleaveArgs) = nullptr;
+  switch (a.ncomp * 2 + a.sample_bytes - 1) {
+  case 2: kernel = deinterleave_kernel<1, 1>; break;
+  case 3: kernel = deinterleave_kernel<1, 2>; break;
+  case 4: kernel = deinterleave_kernel<2, 1>; break;
+  case 5: kernel = deinterleave_kernel<2, 2>; break;
+  case 6: kernel = deinterleave_kernel<3, 1>; break;
+  case 7: kernel = deinterleave_kernel<3, 2>; break;
+  case 8: kernel = deinterleave_kernel<4, 1>; break;
+  default: kernel = deinterleave_kernel<4, 2>; break;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
   return (int)hipGetLastError();
 }
 

@@ -61,6 +61,15 @@ struct RaggedFrame {
 };
 static_assert(sizeof(RaggedFrame) == 96, "read in dwords by scalar loads");
 
+// Planar output (launch_fused_planar): the planar flavours of the ragged kernels write component planes instead of interleaved
+// pixels.  RaggedFrame stays what it is -- `out` is the frame's first plane, `row_stride` the bytes of a line of EVERY plane -- and
+// the other two planes travel in a table of their own, entry i beside RaggedFrame i.  A ragged launch never reads
+// Fused420Args::out (every workgroup takes its frame's); in a planar launch it carries that table.
+struct PlanarFrame {
+  uint8_t *g, *b; // first sample of the frame's second and third plane
+};
+static_assert(sizeof(PlanarFrame) == 16, "read in dwords by scalar loads");
+
 // fused JPEG XT profile C (8-bit 4:2:0 legacy frame + 12-bit 4:4:4 residual frame, see fusedxt420_kernel)
 struct FusedXtExtra {
   int64_t off_r[3];           // residual planes (int16 units from the frame's coefficient base)
@@ -165,6 +174,20 @@ int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t stream);
 // of FUSED420_12, FUSED422_12, FUSED444_12 (narrow12 or not) or FUSED1_12 (12 bit: the lines of a.ragged[i].out hold 16-bit samples),
 // per-frame tables in a.qdev: a.ragged / a.ragged_first / a.frames describe them, `workgroups` is ragged_first[frames].
 int launch_fused_ragged(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t stream);
+// The same launch with component planes out: FUSED420P, FUSED420 (fast or safe), FUSED422 (wide or not) and FUSED444, 8 bit.
+// a.out = the launch's PlanarFrame table (device).  -1: the plan has no planar twin (planar_twin says so beforehand).
+bool planar_twin(const ReconPlan &p);
+int launch_fused_planar(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t stream);
+// Interleaved pixels (ncomp x sample_bytes per pixel) -> ncomp planes: the second pass of every planar request without a twin
+struct DeinterleaveArgs {
+  const uint8_t *src;
+  int64_t src_row;            // bytes per line of src
+  int32_t ncomp, sample_bytes; // 1..4; 1 or 2
+  int32_t width, height;
+  uint8_t *dst[4];
+  int64_t dst_row;            // bytes per line of every plane
+};
+int launch_deinterleave(const DeinterleaveArgs &a, hipStream_t stream);
 int launch_generic(const GenericArgs &a, bool fast, hipStream_t stream);
 // The same frames in one pass through LDS (plain JPEG: no residual planes, int16 coefficients, tables by value): any sampling
 // layout, 1..4 components, 8 or 12 bit.  Uses the plane description of GenericArgs; no workspace.

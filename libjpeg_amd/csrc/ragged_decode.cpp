@@ -418,4 +418,62 @@ try {
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_device"); }
 
+// The planar twin: the group images are the items of one reconstruct_planar_items call on this object (one fused planar launch per
+// kernel and flavour across ALL layout groups' 8-bit colour members; the rest in two passes), the images of the single-image
+// route are lists of one on their own objects.
+int mijpeg_reconstruct_ragged_planar_device(mijpeg_decoder *d, void *const *planes, const int64_t *row_strides, uint32_t flags, int sync)
+try {
+  if (!d || !planes || !row_strides) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  if (d->ragged_n < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded ragged batch: call mijpeg_decode_ragged_device first");
+  const int n = d->ragged_n;
+  flags &= PLANAR_FLAGS;
+  auto wanted = [&](int i) { return !d->ragged[(size_t)i].status && planes[(size_t)i * MIJPEG_MAX_COMPONENTS] != nullptr; };
+  for (int i = 0; i < n; i++) // every destination, before anything is launched
+    if (wanted(i) && planar_check(d->ragged[(size_t)i].info, planes + (size_t)i * MIJPEG_MAX_COMPONENTS, row_strides[i]))
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "planar destination of image " + std::to_string(i) + ": a plane pointer is NULL or the row stride is smaller than a line of samples");
+  HIP_TRY(d, hipSetDevice(d->device));
+  d->planar_stats = mijpeg_planar_stats{};
+  std::vector<PlanarItem> items;
+  std::vector<int> item_image;
+  for (int i = 0; i < n; i++) {
+    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    if (!wanted(i) || r.group < 0) continue;
+    PlanarItem it;
+    it.info = &r.info;
+    it.coef_dev = d->coef_dev + r.coef_base;
+    for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) it.planes[c] = c < r.info.components ? planes[(size_t)i * MIJPEG_MAX_COMPONENTS + c] : nullptr;
+    it.row_stride = row_strides[i];
+    items.push_back(it);
+    item_image.push_back(i);
+  }
+  int failed = MIJPEG_OK, failed_item = -1;
+  std::string failed_msg;
+  if (!items.empty()) {
+    failed = reconstruct_planar_items(d, items.data(), (int)items.size(), flags, &failed_item);
+    if (failed && failed_item < 0) return failed; // (a group launch or the tables' memory: the device's failure ends the call)
+    if (failed) failed_msg = "image " + std::to_string(item_image[(size_t)failed_item]) + " of the ragged batch was not reconstructed";
+    d->planar_stats.images = d->planar_stats.fused + d->planar_stats.two_pass;
+  }
+  // images of the single-image route, on their own objects (which wait for their kernels themselves)
+  for (int i = 0; i < n; i++) {
+    mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    if (!r.child || !wanted(i)) continue;
+    const int rc = mijpeg_reconstruct_planar_device(r.child, planes + (size_t)i * MIJPEG_MAX_COMPONENTS, row_strides[i], flags, 1);
+    if (!rc) {
+      const mijpeg_planar_stats &s = r.child->planar_stats;
+      d->planar_stats.images += s.images; d->planar_stats.fused += s.fused; d->planar_stats.two_pass += s.two_pass;
+      d->planar_stats.fused_launches += s.fused_launches; d->planar_stats.two_pass_launches += s.two_pass_launches;
+    } else if (!failed) {
+      const char *msg = nullptr;
+      (void)mijpeg_last_error(r.child, &msg);
+      failed = rc;
+      failed_msg = "image " + std::to_string(i) + " of the ragged batch was not reconstructed: " + (msg ? msg : "");
+    }
+  }
+  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  if (failed) return set_error(d, failed, failed_msg);
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_planar_device"); }
+
 } // extern "C"

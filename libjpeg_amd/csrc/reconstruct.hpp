@@ -56,3 +56,25 @@ mijpeg_batch batch_of(const mijpeg_info &info, const int16_t *coef_dev, void *ou
 // The batch on the object's stream: sizes the workspace, grows d->ws_dev, launches, sets the object's error ("... not available
 // for this <noun>"; no noun: the code alone, the caller reports)
 int reconstruct_on(mijpeg_decoder *d, mijpeg_batch &b, const RequestExtra *rx, const char *noun);
+
+// ---- planar output: component planes instead of interleaved pixels ----
+// One picture of a planar call: its frame description and coefficient store (in the object's device memory), where its planes go.
+struct PlanarItem {
+  const mijpeg_info *info;
+  const int16_t *coef_dev;
+  void *planes[MIJPEG_MAX_COMPONENTS]; // device; [0 .. components)
+  int64_t row_stride;                  // bytes per line of every plane
+  const uint16_t *own_deltas = nullptr;     // host, [4][64] per COMPONENT: the frame's own tables in a batch that has them (else info's)
+  const uint16_t *own_deltas_dev = nullptr; // ... and their place on the device
+  const mijpeg_xt_params *xt = nullptr;
+};
+constexpr uint32_t PLANAR_FLAGS = MIJPEG_FLAG_FORCE_SAFE | MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM; // what the planar calls take
+// bytes per sample of a frame's reconstruction
+inline int sample_bytes_of(const mijpeg_info &f) { return f.xt ? (f.sample_bytes > 1 ? 2 : 1) : f.precision > 8 ? 2 : 1; }
+// MIJPEG_ERR_INVALID_PARAMETER where a plane of a component the frame has is missing or row_stride is below a line of samples
+int planar_check(const mijpeg_info &f, void *const *planes, int64_t row_stride);
+// The items on the object's stream (nothing is waited for): those whose plan (plan_reconstruct, per-frame tables) has a planar twin
+// share one launch of it per kernel and flavour; the others are reconstructed interleaved into the object's staging buffer and
+// taken apart by deinterleave_kernel.  One-component frames are their own plane.  Adds to d->planar_stats.  An item that fails
+// does not stop the others: -> the first such code, *failed_item its index (a launch of a whole group that fails ends the call).
+int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, uint32_t flags, int *failed_item);
