@@ -134,12 +134,12 @@ struct mijpeg_decoder {
   hipEvent_t ragged_uploaded = nullptr;          // behind the upload of the descriptor tables (the pinned copy is free again)
   bool ragged_upload_pending = false;
   int ragged_n = 0;
-  bool ragged_with12 = false;                    // the batch was grouped by mijpeg_decode_ragged_device16's planner (12-bit groups)
   mijpeg_ragged_stats ragged_stats{};
-  uint8_t *ragged_desc_dev = nullptr, *ragged_desc_host = nullptr; // frame descriptor tables of the reconstruction launches (pinned copy)
+  // launch_fused_lists (reconstruct_device.cpp) alone writes these: the tables of a list call's launches, interleaved or planar
+  // (fused_list.hpp), and their pinned copy, which ragged_uploaded guards from one call to the next
+  uint8_t *ragged_desc_dev = nullptr, *ragged_desc_host = nullptr;
   size_t ragged_desc_cap = 0, ragged_desc_host_cap = 0;
-  // planar calls (reconstruct_planar_items): the interleaved picture of the two-pass route; what the last call did.  (The tables
-  // of the fused planar launches travel in ragged_desc_dev / ragged_desc_host.)
+  // planar calls (reconstruct_planar_items): the interleaved picture of the two-pass route; what the last call did
   uint8_t *planar_tmp_dev = nullptr;
   size_t planar_tmp_cap = 0;
   mijpeg_planar_stats planar_stats{};

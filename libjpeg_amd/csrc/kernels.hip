@@ -2087,7 +2087,7 @@ __global__ __launch_bounds__(F420_THREADS, LUMA_LDS ? 2 : 1) void fusedxtw420_ke
 
 #include "fused444_kernel.inc"
 
-// The planar flavours (see PLANAR_OUT): the four texts once more.  launch_fused_planar instantiates the six ragged ones; they stand
+// The planar flavours (see PLANAR_OUT): the four texts once more.  fused_list_kernel instantiates the six ragged ones; they stand
 // in a namespace of their own for ragged12's reason -- tests/test_ragged_batch.py pins the set of mij::fused*_kernel names.
 namespace planar {
 constexpr bool PLANAR_OUT = true;
@@ -3432,49 +3432,41 @@ int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t s)
 }
 
 // Frames of different sizes in one launch (Fused420Args::ragged): the ragged flavour of the kernel the plan names, per-frame tables,
-// one workgroup per tile and no padding (tile_enter's ragged branch)
-int launch_fused_ragged(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t s)
+// one workgroup per tile and no padding (tile_enter's ragged branch); planar: the one with component planes out.  Null: there is none.
+static void (*fused_list_kernel(const ReconPlan &p, bool planar))(Fused420Args)
 {
-  if (!a.ragged || !a.ragged_first || !a.qdev || a.frames < 1) return -1;
-  if (workgroups == 0) return 0;
-  void (*kernel)(Fused420Args) = nullptr;
-  switch (p.kernel) {
-  case Recon::FUSED420P: kernel = fused420p_kernel<3, true, false, true>; break;
-  case Recon::FUSED420: kernel = p.fast ? fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : fused420_kernel<false, 2, true, 8, false, true>; break;
-  case Recon::FUSED422: kernel = p.wide ? fused422_kernel<3, true, true, true> : fused422_kernel<3, true, false, true>; break;
-  case Recon::FUSED444: kernel = fused444_kernel<2, true, true>; break;
-  case Recon::FUSED1: kernel = fused1_kernel<true, 8, true>; break;
+  if (!planar) switch (p.kernel) {
+  case Recon::FUSED420P: return fused420p_kernel<3, true, false, true>;
+  case Recon::FUSED420: return p.fast ? fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : fused420_kernel<false, 2, true, 8, false, true>;
+  case Recon::FUSED422: return p.wide ? fused422_kernel<3, true, true, true> : fused422_kernel<3, true, false, true>;
+  case Recon::FUSED444: return fused444_kernel<2, true, true>;
+  case Recon::FUSED1: return fused1_kernel<true, 8, true>;
   // 12 bit: the occupancy of the uniform per-frame-table builds (two workgroups per CU; grey four)
   case Recon::FUSED420_12:
-    kernel = p.narrow12 ? ragged12::fused420_kernel<true, F420_12_MINW, true, 12, true, true> : ragged12::fused420_kernel<true, F420_12_MINW, true, 12, false, true>;
-    break;
-  case Recon::FUSED422_12: kernel = p.narrow12 ? fused422_12_kernel<true, true, true> : fused422_12_kernel<true, false, true>; break;
-  case Recon::FUSED444_12: kernel = p.narrow12 ? fused444_12_kernel<true, true, true> : fused444_12_kernel<true, false, true>; break;
-  case Recon::FUSED1_12: kernel = ragged12::fused1_kernel<true, 12, true>; break;
-  default: return -1; // (no ragged flavour)
+    return p.narrow12 ? ragged12::fused420_kernel<true, F420_12_MINW, true, 12, true, true> : ragged12::fused420_kernel<true, F420_12_MINW, true, 12, false, true>;
+  case Recon::FUSED422_12: return p.narrow12 ? fused422_12_kernel<true, true, true> : fused422_12_kernel<true, false, true>;
+  case Recon::FUSED444_12: return p.narrow12 ? fused444_12_kernel<true, true, true> : fused444_12_kernel<true, false, true>;
+  case Recon::FUSED1_12: return ragged12::fused1_kernel<true, 12, true>;
+  default: return nullptr; // (no ragged flavour)
   }
-  hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(F420_THREADS), 0, s, a);
-  return (int)hipGetLastError();
+  switch (p.kernel) { // planar: the occupancy of the interleaved ragged flavours
+  case Recon::FUSED420P: return planar::fused420p_kernel<3, true, false, true>;
+  case Recon::FUSED420: return p.fast ? planar::fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : planar::fused420_kernel<false, 2, true, 8, false, true>;
+  case Recon::FUSED422: return p.wide ? planar::fused422_kernel<3, true, true, true> : planar::fused422_kernel<3, true, false, true>;
+  case Recon::FUSED444: return planar::fused444_kernel<2, true, true>;
+  default: return nullptr; // (no planar twin)
+  }
 }
 
-bool planar_twin(const ReconPlan &p)
-{
-  return p.kernel == Recon::FUSED420P || p.kernel == Recon::FUSED420 || p.kernel == Recon::FUSED422 || p.kernel == Recon::FUSED444;
-}
+bool ragged_twin(const ReconPlan &p) { return fused_list_kernel(p, false) != nullptr; }
+bool planar_twin(const ReconPlan &p) { return fused_list_kernel(p, true) != nullptr; }
 
-// launch_fused_ragged with component planes out (a.out: the PlanarFrame table).  The occupancy of the interleaved ragged flavours.
-int launch_fused_planar(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t s)
+int launch_fused_list(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, bool planar, hipStream_t s)
 {
-  if (!a.ragged || !a.ragged_first || !a.qdev || !a.out || a.frames < 1) return -1;
+  if (!a.ragged || !a.ragged_first || !a.qdev || (planar && !a.out) || a.frames < 1) return -1;
   if (workgroups == 0) return 0;
-  void (*kernel)(Fused420Args) = nullptr;
-  switch (p.kernel) {
-  case Recon::FUSED420P: kernel = planar::fused420p_kernel<3, true, false, true>; break;
-  case Recon::FUSED420: kernel = p.fast ? planar::fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : planar::fused420_kernel<false, 2, true, 8, false, true>; break;
-  case Recon::FUSED422: kernel = p.wide ? planar::fused422_kernel<3, true, true, true> : planar::fused422_kernel<3, true, false, true>; break;
-  case Recon::FUSED444: kernel = planar::fused444_kernel<2, true, true>; break;
-  default: return -1; // (no planar twin)
-  }
+  void (*kernel)(Fused420Args) = fused_list_kernel(p, planar);
+  if (!kernel) return -1;
   hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(F420_THREADS), 0, s, a);
   return (int)hipGetLastError();
 }

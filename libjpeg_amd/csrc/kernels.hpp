@@ -39,7 +39,7 @@ struct Fused420Args {
   int32_t q[3][QROW];             // per component (Y, Cb, Cr): fill_deltas
   const int32_t *qdev;            // or null: per-frame tables in device memory, [frames][4][64] deltas << 4 (replace q)
   uint32_t magic_tx, magic_ty;    // set by the launchers: floor(2^32 / tiles_x) + 1 and the same for tiles_y, or 0 (kernels.hip tile_position)
-  // ragged launches (launch_fused_ragged; null otherwise): the frames differ in size, and a workgroup takes everything from
+  // ragged launches (launch_fused_list; null otherwise): the frames differ in size, and a workgroup takes everything from
   // `coef_frame_stride` to `tiles_y` above from its frame's entry.  `frames` counts the entries, `coef` is the store all
   // coef_base count from.  (Behind everything else: the uniform kernels' argument offsets are what they were.)
   const struct RaggedFrame *ragged;  // device: one entry per frame of the launch
@@ -61,7 +61,7 @@ struct RaggedFrame {
 };
 static_assert(sizeof(RaggedFrame) == 96, "read in dwords by scalar loads");
 
-// Planar output (launch_fused_planar): the planar flavours of the ragged kernels write component planes instead of interleaved
+// Planar output (launch_fused_list, planar): the planar flavours of the ragged kernels write component planes instead of interleaved
 // pixels.  RaggedFrame stays what it is -- `out` is the frame's first plane, `row_stride` the bytes of a line of EVERY plane -- and
 // the other two planes travel in a table of their own, entry i beside RaggedFrame i.  A ragged launch never reads
 // Fused420Args::out (every workgroup takes its frame's); in a planar launch it carries that table.
@@ -173,11 +173,11 @@ int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t stream);
 // Frames of different sizes in one launch of FUSED420P, FUSED420 (fast or safe), FUSED422 (wide or not), FUSED444 or FUSED1 (8 bit), or
 // of FUSED420_12, FUSED422_12, FUSED444_12 (narrow12 or not) or FUSED1_12 (12 bit: the lines of a.ragged[i].out hold 16-bit samples),
 // per-frame tables in a.qdev: a.ragged / a.ragged_first / a.frames describe them, `workgroups` is ragged_first[frames].
-int launch_fused_ragged(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t stream);
-// The same launch with component planes out: FUSED420P, FUSED420 (fast or safe), FUSED422 (wide or not) and FUSED444, 8 bit.
-// a.out = the launch's PlanarFrame table (device).  -1: the plan has no planar twin (planar_twin says so beforehand).
+// planar: the same launch with component planes out -- FUSED420P, FUSED420 (fast or safe), FUSED422 (wide or not) and FUSED444,
+// 8 bit; a.out = the launch's PlanarFrame table (device).  -1: the plan has no such kernel (ragged_twin, planar_twin say so beforehand).
+bool ragged_twin(const ReconPlan &p);
 bool planar_twin(const ReconPlan &p);
-int launch_fused_planar(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, hipStream_t stream);
+int launch_fused_list(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, bool planar, hipStream_t stream);
 // Interleaved pixels (ncomp x sample_bytes per pixel) -> ncomp planes: the second pass of every planar request without a twin
 struct DeinterleaveArgs {
   const uint8_t *src;

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <string>
 
+#include "fused_list.hpp"
 #include "reconstruct.hpp"
 
 using namespace mij;
@@ -58,13 +59,6 @@ static int ragged_plan(const mijpeg_info *infos, int n, const char *excluded, bo
   *coef_total = base;
   return MIJPEG_OK;
 }
-
-// The descriptor table of a launch of m frames, `at` bytes into the upload: [frames][first workgroups, m + 1 of them, padded to 16
-// bytes][deltas << 4, per frame 4 x 64]: where its parts begin and where it ends
-struct DescTable {
-  size_t frames, first, deltas, end;
-  DescTable(size_t at, size_t m) : frames(at), first(frames + m * sizeof(RaggedFrame)), deltas(first + ((m + 1) * 4 + 15) / 16 * 16), end(deltas + m * 4 * 64 * sizeof(int32_t)) {}
-};
 
 // Image i through the single-image route, on a decoder object of its own (kept from call to call)
 static void ragged_single_image(mijpeg_decoder *d, int i, int k, const uint8_t *data, size_t size, int min_intervals)
@@ -138,7 +132,6 @@ static int decode_ragged(mijpeg_decoder *d, const uint8_t *const *streams, const
   int32_t grids[MIJPEG_RAGGED_GROUPS16];
   int64_t coef_total = 0;
   ragged_plan(infos.data(), n, excluded.data(), with12, group.data(), frames.data(), grids, &coef_total);
-  d->ragged_with12 = with12; // (mijpeg_reconstruct_ragged_device numbers each launch's frames with the same planner)
   for (int i = 0; i < n; i++)
     if (group[(size_t)i] < 0 && !excluded[(size_t)i])
       d->ragged[(size_t)i].why_single = with12 ? "no layout group for this frame: 8-bit and 12-bit sequential 4:2:0, 4:2:2, 4:4:4 and grey frames have one"
@@ -304,87 +297,22 @@ try {
     b.quant_dev = own_tables ? &per_frame_tables : nullptr;
     return b;
   };
-  struct Launch { ReconPlan p; int group; std::vector<int> members; };
-  std::vector<Launch> launches;
+  std::vector<FusedListItem> items;
+  std::vector<FusedListLaunch> launches;
   std::vector<int> singles;
   for (int i = 0; i < n; i++) {
     const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
     if (r.status || r.group < 0 || !dst_device[i]) continue;
     const mijpeg_batch b = describe(i, true);
     const ReconPlan p = plan_reconstruct(&b);
-    const bool has_flavour = (r.group == MIJPEG_RAGGED_420 && (p.kernel == Recon::FUSED420P || p.kernel == Recon::FUSED420)) ||
-                             (r.group == MIJPEG_RAGGED_422 && p.kernel == Recon::FUSED422) || (r.group == MIJPEG_RAGGED_444 && p.kernel == Recon::FUSED444) ||
-                             (r.group == MIJPEG_RAGGED_GREY && p.kernel == Recon::FUSED1) || (r.group == MIJPEG_RAGGED_420_12 && p.kernel == Recon::FUSED420_12) ||
-                             (r.group == MIJPEG_RAGGED_422_12 && p.kernel == Recon::FUSED422_12) || (r.group == MIJPEG_RAGGED_444_12 && p.kernel == Recon::FUSED444_12) ||
-                             (r.group == MIJPEG_RAGGED_GREY_12 && p.kernel == Recon::FUSED1_12);
-    if (!has_flavour) { singles.push_back(i); continue; }
-    size_t l = 0;
-    while (l < launches.size() && !(launches[l].group == r.group && launches[l].p.kernel == p.kernel && launches[l].p.fast == p.fast && launches[l].p.wide == p.wide && launches[l].p.narrow12 == p.narrow12)) l++;
-    if (l == launches.size()) launches.push_back(Launch{p, r.group, {}});
-    launches[l].members.push_back(i);
+    if (!ragged_twin(p)) { singles.push_back(i); continue; } // (a ragged kernel is its layout group's: tests/test_ragged_twin_cpu.py)
+    fused_list_add(launches, p, (int)items.size(), r.info);
+    items.push_back(FusedListItem{&r.info, r.coef_base, {dst_device[i], nullptr, nullptr}, row_strides[i]});
   }
-  // descriptor tables of all launches in one upload, one DescTable behind the other
-  if (!launches.empty()) {
-    std::vector<DescTable> tables;
-    for (const Launch &l : launches) tables.emplace_back(tables.empty() ? 0 : tables.back().end, l.members.size());
-    const size_t bytes = tables.back().end;
-    int rc = ensure_dev(d, (void **)&d->ragged_desc_dev, &d->ragged_desc_cap, bytes);
-    if (rc) return rc;
-    if (d->ragged_upload_pending) { // (the pinned copy travels asynchronously: the last call's must have left)
-      HIP_TRY(d, hipEventSynchronize(d->ragged_uploaded));
-      d->ragged_upload_pending = false;
-    }
-    if ((rc = ensure_pinned(d, &d->ragged_desc_host, &d->ragged_desc_host_cap, bytes))) return rc;
-    std::vector<uint32_t> grid(launches.size());
-    for (size_t l = 0; l < launches.size(); l++) {
-      const std::vector<int> &mem = launches[l].members;
-      const size_t m = mem.size();
-      RaggedFrame *fr = (RaggedFrame *)(d->ragged_desc_host + tables[l].frames);
-      uint32_t *first = (uint32_t *)(d->ragged_desc_host + tables[l].first);
-      int32_t *q = (int32_t *)(d->ragged_desc_host + tables[l].deltas);
-      // the launch's own frames through the planner: their first workgroups, the grid
-      std::vector<mijpeg_info> infos(m);
-      std::vector<int32_t> grp(m);
-      std::vector<mijpeg_ragged_frame> pf(m);
-      int32_t grids[MIJPEG_RAGGED_GROUPS16];
-      int64_t unused = 0;
-      for (size_t k = 0; k < m; k++) infos[k] = d->ragged[(size_t)mem[k]].info;
-      ragged_plan(infos.data(), (int)m, nullptr, d->ragged_with12, grp.data(), pf.data(), grids, &unused);
-      for (size_t k = 0; k < m; k++) {
-        const int i = mem[k];
-        const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
-        if (grp[k] != launches[l].group) return set_error(d, MIJPEG_ERR_PHASE_ERROR, "ragged planner disagrees with itself");
-        RaggedFrame &x = fr[k];
-        memset(&x, 0, sizeof(x));
-        fused_geometry(r.info, launches[l].p.sampling, x);
-        x.coef_base = r.coef_base;
-        x.out = (uint8_t *)dst_device[i];
-        x.row_stride = row_strides[i];
-        x.qframe = (int32_t)k;
-        first[k] = (uint32_t)pf[k].first_workgroup;
-        for (int c = 0; c < 4; c++)
-          for (int z = 0; z < 64; z++) q[(k * 4 + (size_t)c) * 64 + (size_t)z] = c < r.info.components ? (int32_t)r.info.quant[r.info.quant_index[c]][z] << 4 : 16;
-      }
-      grid[l] = (uint32_t)grids[launches[l].group];
-      first[m] = grid[l];
-    }
-    HIP_TRY(d, hipMemcpyAsync(d->ragged_desc_dev, d->ragged_desc_host, bytes, hipMemcpyHostToDevice, d->stream));
-    if (!d->ragged_uploaded) HIP_TRY(d, hipEventCreateWithFlags(&d->ragged_uploaded, hipEventDisableTiming));
-    HIP_TRY(d, hipEventRecord(d->ragged_uploaded, d->stream));
-    d->ragged_upload_pending = true;
-    for (size_t l = 0; l < launches.size(); l++) {
-      Fused420Args a;
-      memset(&a, 0, sizeof(a));
-      a.coef = d->coef_dev;
-      a.frames = (int32_t)launches[l].members.size();
-      a.ragged = (const RaggedFrame *)(d->ragged_desc_dev + tables[l].frames);
-      a.ragged_first = (const uint32_t *)(d->ragged_desc_dev + tables[l].first);
-      a.qdev = (const int32_t *)(d->ragged_desc_dev + tables[l].deltas);
-      if (launch_fused_ragged(launches[l].p, a, grid[l], d->stream))
-        return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-      d->ragged_stats.recon_launches++;
-    }
-  }
+  // descriptor tables of all launches in one upload, then the launches
+  const int made = launch_fused_lists(d, items.data(), launches, false);
+  if (made < 0) return made;
+  d->ragged_stats.recon_launches = made;
   // One image whose reconstruction fails does not stop the others, whichever route it takes: the call works through the list
   // and then returns the first such code, with a message that names the image.  (A launch of a whole group that fails, or
   // memory that cannot be had for the tables, is the device's failure and ends the call at once; what was enqueued stays

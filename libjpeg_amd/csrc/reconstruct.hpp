@@ -57,6 +57,13 @@ mijpeg_batch batch_of(const mijpeg_info &info, const int16_t *coef_dev, void *ou
 // for this <noun>"; no noun: the code alone, the caller reports)
 int reconstruct_on(mijpeg_decoder *d, mijpeg_batch &b, const RequestExtra *rx, const char *noun);
 
+// ---- lists of differently shaped frames in fused launches (fused_list.hpp: items, launches, table layout) ----
+struct FusedListItem;
+struct FusedListLaunch;
+// The launches on the object's stream (nothing is waited for): their tables into d->ragged_desc_host once the last call's upload
+// has left it, one upload, one launch_fused_list each.  -> the number of launches made, or the (negative) error, set on the object.
+int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std::vector<FusedListLaunch> &launches, bool planar);
+
 // ---- planar output: component planes instead of interleaved pixels ----
 // One picture of a planar call: its frame description and coefficient store (in the object's device memory), where its planes go.
 struct PlanarItem {

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <string>
 
+#include "fused_list.hpp"
 #include "reconstruct.hpp"
 
 using namespace mij;
@@ -512,20 +513,43 @@ int planar_check(const mijpeg_info &f, void *const *planes, int64_t row_stride)
   return row_stride >= (int64_t)f.width * sample_bytes_of(f) ? MIJPEG_OK : MIJPEG_ERR_INVALID_PARAMETER;
 }
 
-// The tables of a fused planar launch of m frames, `at` bytes into the upload: ragged_decode.cpp's DescTable (frames, first
-// workgroups padded to 16 bytes, deltas) and the PlanarFrame entries behind it
-struct PlanarTable {
-  size_t frames, first, deltas, planes, end;
-  PlanarTable(size_t at, size_t m)
-      : frames(at), first(frames + m * sizeof(RaggedFrame)), deltas(first + ((m + 1) * 4 + 15) / 16 * 16), planes(deltas + m * 4 * 64 * sizeof(int32_t)),
-        end(planes + m * sizeof(PlanarFrame)) {}
-};
+int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std::vector<FusedListLaunch> &launches, bool planar)
+{
+  if (launches.empty()) return 0;
+  const std::vector<FusedListTable> tables = fused_list_layout(launches, planar);
+  const size_t bytes = tables.back().end;
+  int rc = ensure_dev(d, (void **)&d->ragged_desc_dev, &d->ragged_desc_cap, bytes);
+  if (rc) return rc;
+  if (d->ragged_upload_pending) { // (the pinned copy travels asynchronously: the last call's must have left)
+    HIP_TRY(d, hipEventSynchronize(d->ragged_uploaded));
+    d->ragged_upload_pending = false;
+  }
+  if ((rc = ensure_pinned(d, &d->ragged_desc_host, &d->ragged_desc_host_cap, bytes))) return rc;
+  for (size_t l = 0; l < launches.size(); l++) fused_list_fill(d->ragged_desc_host, tables[l], launches[l], items, planar);
+  HIP_TRY(d, hipMemcpyAsync(d->ragged_desc_dev, d->ragged_desc_host, bytes, hipMemcpyHostToDevice, d->stream));
+  if (!d->ragged_uploaded) HIP_TRY(d, hipEventCreateWithFlags(&d->ragged_uploaded, hipEventDisableTiming));
+  HIP_TRY(d, hipEventRecord(d->ragged_uploaded, d->stream));
+  d->ragged_upload_pending = true;
+  for (size_t l = 0; l < launches.size(); l++) {
+    Fused420Args a;
+    memset(&a, 0, sizeof(a));
+    a.coef = d->coef_dev;
+    a.frames = (int32_t)launches[l].members.size();
+    a.ragged = (const RaggedFrame *)(d->ragged_desc_dev + tables[l].frames);
+    a.ragged_first = (const uint32_t *)(d->ragged_desc_dev + tables[l].first);
+    a.qdev = (const int32_t *)(d->ragged_desc_dev + tables[l].deltas);
+    if (planar) a.out = d->ragged_desc_dev + tables[l].planes; // (the PlanarFrame table: kernels.hpp)
+    if (launch_fused_list(launches[l].p, a, (unsigned)launches[l].grid, planar, d->stream))
+      return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+  }
+  return (int)launches.size();
+}
 
 int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, uint32_t flags, int *failed_item)
 {
   static const uint16_t per_frame_tables = 0; // (the planner only asks whether a batch brings per-frame tables: the planar launches do)
-  struct Launch { ReconPlan p; std::vector<int> members; uint64_t grid; };
-  std::vector<Launch> launches;
+  std::vector<FusedListItem> fused;
+  std::vector<FusedListLaunch> launches;
   std::vector<int> two_pass;
   size_t staging = 0;
   for (int i = 0; i < n; i++) {
@@ -536,77 +560,18 @@ int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, 
     if (f.components == 1) { two_pass.push_back(i); continue; } // (its own plane: the existing kernel, no second pass)
     b.quant_dev = &per_frame_tables;
     const ReconPlan p = plan_reconstruct(&b);
-    const uint64_t tiles = (uint64_t)((f.width + 127) / 128) * (uint64_t)((f.height + 127) / 128);
-    size_t l = 0;
-    while (l < launches.size() && !(launches[l].p.kernel == p.kernel && launches[l].p.fast == p.fast && launches[l].p.wide == p.wide && launches[l].grid + tiles <= 0x7fffffffull)) l++;
-    if (f.components != 3 || f.precision != 8 || f.xt || !planar_twin(p) || tiles > 0x7fffffffull) {
+    if (f.components != 3 || f.precision != 8 || f.xt || !planar_twin(p) || fused_list_tiles(f) > 0x7fffffffull) {
       two_pass.push_back(i);
       staging = std::max(staging, (size_t)f.height * (size_t)f.width * (size_t)f.components * (size_t)sample_bytes_of(f));
       continue;
     }
-    if (l == launches.size()) launches.push_back(Launch{p, {}, 0});
-    launches[l].members.push_back(i);
-    launches[l].grid += tiles;
+    fused_list_add(launches, p, (int)fused.size(), f);
+    fused.push_back(FusedListItem{&f, it.coef_dev - d->coef_dev, {it.planes[0], it.planes[1], it.planes[2]}, it.row_stride, it.own_deltas}); // (every item's store lies in the object's)
   }
-  if (!launches.empty()) {
-    std::vector<PlanarTable> tables;
-    for (const Launch &l : launches) tables.emplace_back(tables.empty() ? 0 : tables.back().end, l.members.size());
-    const size_t bytes = tables.back().end;
-    int rc = ensure_dev(d, (void **)&d->ragged_desc_dev, &d->ragged_desc_cap, bytes);
-    if (rc) return rc;
-    if (d->ragged_upload_pending) { // (the pinned copy travels asynchronously: the last call's must have left)
-      HIP_TRY(d, hipEventSynchronize(d->ragged_uploaded));
-      d->ragged_upload_pending = false;
-    }
-    if ((rc = ensure_pinned(d, &d->ragged_desc_host, &d->ragged_desc_host_cap, bytes))) return rc;
-    for (size_t l = 0; l < launches.size(); l++) {
-      const std::vector<int> &mem = launches[l].members;
-      RaggedFrame *fr = (RaggedFrame *)(d->ragged_desc_host + tables[l].frames);
-      uint32_t *first = (uint32_t *)(d->ragged_desc_host + tables[l].first);
-      int32_t *q = (int32_t *)(d->ragged_desc_host + tables[l].deltas);
-      PlanarFrame *pl = (PlanarFrame *)(d->ragged_desc_host + tables[l].planes);
-      uint32_t at = 0;
-      for (size_t k = 0; k < mem.size(); k++) {
-        const PlanarItem &it = items[mem[k]];
-        const mijpeg_info &f = *it.info;
-        RaggedFrame &x = fr[k];
-        memset(&x, 0, sizeof(x));
-        fused_geometry(f, launches[l].p.sampling, x);
-        x.coef_base = it.coef_dev - d->coef_dev; // (every item's store lies in the object's)
-        x.out = (uint8_t *)it.planes[0];
-        x.row_stride = it.row_stride;
-        x.qframe = (int32_t)k;
-        pl[k].g = (uint8_t *)it.planes[1];
-        pl[k].b = (uint8_t *)it.planes[2];
-        first[k] = at;
-        at += (uint32_t)(x.tiles_x * x.tiles_y);
-        for (int c = 0; c < 4; c++)
-          for (int z = 0; z < 64; z++) {
-            const uint16_t delta = c >= f.components ? 1 : it.own_deltas ? it.own_deltas[c * 64 + z] : f.quant[f.quant_index[c]][z];
-            q[(k * 4 + (size_t)c) * 64 + (size_t)z] = (int32_t)delta << 4;
-          }
-      }
-      first[mem.size()] = at;
-    }
-    HIP_TRY(d, hipMemcpyAsync(d->ragged_desc_dev, d->ragged_desc_host, bytes, hipMemcpyHostToDevice, d->stream));
-    if (!d->ragged_uploaded) HIP_TRY(d, hipEventCreateWithFlags(&d->ragged_uploaded, hipEventDisableTiming));
-    HIP_TRY(d, hipEventRecord(d->ragged_uploaded, d->stream));
-    d->ragged_upload_pending = true;
-    for (size_t l = 0; l < launches.size(); l++) {
-      Fused420Args a;
-      memset(&a, 0, sizeof(a));
-      a.coef = d->coef_dev;
-      a.frames = (int32_t)launches[l].members.size();
-      a.ragged = (const RaggedFrame *)(d->ragged_desc_dev + tables[l].frames);
-      a.ragged_first = (const uint32_t *)(d->ragged_desc_dev + tables[l].first);
-      a.qdev = (const int32_t *)(d->ragged_desc_dev + tables[l].deltas);
-      a.out = d->ragged_desc_dev + tables[l].planes; // (the PlanarFrame table: kernels.hpp)
-      if (launch_fused_planar(launches[l].p, a, (unsigned)launches[l].grid, d->stream))
-        return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
-      d->planar_stats.fused_launches++;
-      d->planar_stats.fused += (int32_t)launches[l].members.size();
-    }
-  }
+  const int made = launch_fused_lists(d, fused.data(), launches, true);
+  if (made < 0) return made;
+  d->planar_stats.fused_launches += made;
+  d->planar_stats.fused += (int32_t)fused.size();
   // the others: the picture as the existing kernels write it, into the staging buffer (one after the other: the stream orders
   // them), and deinterleave_kernel behind each
   if (staging) {

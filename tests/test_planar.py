@@ -218,6 +218,46 @@ def test_ragged_list(oracle):
     d.close()
 
 
+def test_back_to_back_calls_share_the_pinned_tables(oracle):
+    """The interleaved and the planar list call fill the same pinned tables (launch_fused_lists): three calls that nobody waits
+    for in between, each into fresh destinations, write what the synchronised calls wrote -- the second and third wait for the
+    upload before them instead of overwriting tables that are still on their way.  Three pictures of one or two tiles in three
+    layouts: three launches per call, one table behind the other."""
+    import torch
+
+    streams = [synth.synth_jpeg(136, 8, 4801, 85, "420", 0), synth.synth_jpeg(8, 136, 4802, 85, "422", 0), synth.synth_jpeg(16, 16, 4803, 85, "444", 0)]
+    d = api.Decoder(0)
+    assert d.decode_ragged_device(streams) == [0, 0, 0]
+    infos = [d.ragged_info(i) for i in range(3)]
+    assert [(f.width, f.height) for f in infos] == [(136, 8), (8, 136), (16, 16)]
+
+    def interleaved(sync):
+        outs = [torch.full((f.height, f.width, 3), GUARD, dtype=torch.uint8, device="cuda") for f in infos]
+        d.reconstruct_ragged_device([t.data_ptr() for t in outs], [f.width * 3 for f in infos], sync=sync)
+        return outs
+
+    def planar(sync):
+        dsts = [Dest(1, 3, f.height, f.width) for f in infos]
+        d.reconstruct_ragged_planar_device([dst.ptrs() for dst in dsts], [dst.row for dst in dsts], sync=sync)
+        return dsts
+
+    exp = [t.cpu().numpy() for t in interleaved(True)]
+    assert d.ragged_stats()["recon_launches"] == 3 and d.ragged_stats()["recon_single"] == 0
+    exp_planes = [dst.result()[0][0] for dst in planar(True)]
+    assert d.planar_stats() == dict(images=3, fused=3, two_pass=0, fused_launches=3, two_pass_launches=0)
+    assert np.array_equal(exp[0], oracle.decode(streams[0]))
+    for i in range(3):
+        assert _same(exp_planes[i], _expect_planes(exp[i])), i
+    first, second, third = interleaved(False), planar(False), interleaved(False)
+    d.synchronize()
+    for i in range(3):
+        assert np.array_equal(first[i].cpu().numpy(), exp[i]), i
+        planes, touched = second[i].result()
+        assert _same(planes[0], exp_planes[i]) and touched == 0, i
+        assert np.array_equal(third[i].cpu().numpy(), exp[i]), i
+    d.close()
+
+
 def test_decode_mixed_chw():
     streams = [synth.synth_jpeg(141, 150, 4701, 85, "420", 0), synth.synth_jpeg(64, 33, 4702, 85, "444", 2),
                synth.encode_jpeg(synth.synth_image(50, 20, 4703, channels=1), 85, "444", 0), golden_jpeg("p12_64x48_444"),

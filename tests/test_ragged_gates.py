@@ -1,4 +1,4 @@
-"""The ragged flavours of the fused reconstruction kernels (launch_fused_ragged, tile_enter_ragged) at their arithmetic
+"""The ragged flavours of the fused reconstruction kernels (launch_fused_list, tile_enter_ragged) at their arithmetic
 gates and over their launch geometry.  The uniform twins of these kernels are pinned by crafted coefficient planes through
 api.launch_reconstruct, which cannot launch a ragged flavour; here the crafted planes are coded to streams (api.encode_coefficients,
 host-only) and reach the ragged launches the way every list does: Decoder.decode_ragged_device + reconstruct_ragged_device.  The

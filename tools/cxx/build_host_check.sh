@@ -2,7 +2,8 @@
 # Builds tools/cxx/prepare_batch_host_check.cpp together with the library's HOST code under AddressSanitizer and
 # UndefinedBehaviorSanitizer into a directory of the caller's (default: a temporary one) -- nothing in the tree is touched.
 # The kernel translation units (*.hip) keep the ordinary build's objects (libjpeg_amd/csrc/build/, built by `make`): only their
-# launch stubs are host code, and the program never launches anything.  The program is a stand-alone executable linked with the
+# launch stubs are host code, and the program never launches anything.  Host code alone is instrumented: -Xarch_host on the compile
+# lines, -fno-gpu-sanitize on the link line -- no device code object of this build carries a sanitizer.  The program is a stand-alone executable linked with the
 # sanitizers' runtimes; run it on a machine without a device, on stream files:
 #
 #   tools/cxx/build_host_check.sh /tmp/hostcheck && /tmp/hostcheck/prepare_batch_host_check a.jpg b.jpg ...
@@ -23,7 +24,7 @@ done
 "$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/interface/jpeg.cpp" -o "$OUT/jpeg_class.o" &
 "$CXX" -O1 -std=c++17 -pthread $SAN -c "$ROOT/tools/cxx/prepare_batch_host_check.cpp" -o "$OUT/check.o" &
 wait
-"$HIPCC" --offload-arch=gfx950 -fsanitize=address,undefined -o "$OUT/prepare_batch_host_check" "$OUT"/check.o "$OUT"/capi.o "$OUT"/reconstruct_device.o \
+"$HIPCC" --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize -o "$OUT/prepare_batch_host_check" "$OUT"/check.o "$OUT"/capi.o "$OUT"/reconstruct_device.o \
   "$OUT"/ragged_decode.o "$OUT"/entropy_device.o "$OUT"/encode_device.o "$OUT"/batch_pipeline.o "$OUT"/host_decoder.o "$OUT"/encoder.o "$OUT"/jpeg_class.o \
   "$SRC"/build/kernels.o "$SRC"/build/forward.o "$SRC"/build/hencode.o "$SRC"/build/huffman.o "$SRC"/build/markers.o -pthread
 echo "$OUT/prepare_batch_host_check"
