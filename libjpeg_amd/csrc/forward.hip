@@ -278,25 +278,6 @@ int launch_forward(const ForwardArgs &a, int precision, hipStream_t stream)
   return precision == 12 ? launch_forward_of<12>(a, stream) : launch_forward_of<8>(a, stream);
 }
 
-int forward_ragged_items(const ForwardArgs &a, int which[5], uint32_t wgs[5], int comp[5])
-{
-  int k = 0;
-  const unsigned per_frame = a.first_block[a.ncomp];
-  if (per_frame == 0) return 0;
-  if (a.tiled420) { which[k] = 0; wgs[k] = (unsigned)(a.width >> 7) * (unsigned)(a.height >> 7); comp[k++] = 0; }
-  for (int c = 0; c < a.ncomp; c++) {
-    if (!a.fast[c]) continue;
-    const unsigned n = (unsigned)a.fast_nbx[c] * (unsigned)a.fast_nby[c];
-    if (n == 0) continue;
-    const int key = a.subx[c] * 4 + a.suby[c];
-    which[k] = key == 5 ? 1 : key == 10 ? 2 : key == 9 ? 3 : 4;
-    wgs[k] = (n + 255) / 256;
-    comp[k++] = c;
-  }
-  which[k] = 5; wgs[k] = (per_frame + 255) / 256; comp[k++] = 0;
-  return k;
-}
-
 int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *launches)
 {
   for (int l = 0; l < FORWARD_RAGGED_LISTS; l++) {

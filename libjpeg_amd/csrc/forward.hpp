@@ -52,8 +52,25 @@ struct ForwardRaggedPlan {
   uint32_t grid[FORWARD_RAGGED_LISTS];
 };
 // The work items picture `a` contributes: wgs[k] workgroups and item component comp[k] per entry, launch index which[k]; returns
-// the number of entries (at most 5).  Host side of the routing rule, shared by the planner and the launcher.
-int forward_ragged_items(const ForwardArgs &a, int which[5], uint32_t wgs[5], int comp[5]);
+// the number of entries (at most 5).  Host side of the routing rule: plain arithmetic, what launch_forward launches for a frame.
+inline int forward_ragged_items(const ForwardArgs &a, int which[5], uint32_t wgs[5], int comp[5])
+{
+  int k = 0;
+  const unsigned per_frame = a.first_block[a.ncomp];
+  if (per_frame == 0) return 0;
+  if (a.tiled420) { which[k] = 0; wgs[k] = (unsigned)(a.width >> 7) * (unsigned)(a.height >> 7); comp[k++] = 0; }
+  for (int c = 0; c < a.ncomp; c++) {
+    if (!a.fast[c]) continue;
+    const unsigned n = (unsigned)a.fast_nbx[c] * (unsigned)a.fast_nby[c];
+    if (n == 0) continue;
+    const int key = a.subx[c] * 4 + a.suby[c];
+    which[k] = key == 5 ? 1 : key == 10 ? 2 : key == 9 ? 3 : 4;
+    wgs[k] = (n + 255) / 256;
+    comp[k++] = c;
+  }
+  which[k] = 5; wgs[k] = (per_frame + 255) / 256; comp[k++] = 0;
+  return k;
+}
 // returns 0 or a hipError_t; *launches: kernels launched
 int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *launches);
 

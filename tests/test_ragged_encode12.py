@@ -267,6 +267,38 @@ def test_pass_cutting_is_invisible(dec, monkeypatch):
     del keep
 
 
+def test_reused_arenas_under_three_layouts(dec):
+    """Three calls back to back on one object, so that the pass's arenas are laid out three ways over the same memory: eight pictures
+    of every routing (4:4:4, 4:2:0 of one MCU, below a tile, exactly one tile, a tile with edge strips, 4:2:2, 1 x 2, grey) with
+    precisions alternating 8 and 12 and no `optimize` -- table and histogram arenas of four --, then its first two pictures as 8-bit
+    ones -- empty arenas, everything behind them further to the front --, then the first list again."""
+    shapes = [(8, 8, "444"), (16, 16, "420"), (127, 127, "420"), (128, 128, "420"), (136, 130, "420"), (17, 9, "422"), (9, 17, "440"), (33, 7, "grey")]
+    cases = [(w, h, lay, (30, 85, 100, 2)[i % 4], 0, 12 if i % 2 else 8) for i, (w, h, lay) in enumerate(shapes)]
+    imgs = [_picture(w, h, lay, p, 900 + i) for i, (w, h, lay, _, _, p) in enumerate(cases)]
+    two_cases = [c[:5] + (8,) for c in cases[:2]]
+    two_imgs = [imgs[0], _picture(16, 16, "420", 8, 901)]
+    expected = [_single(dec, im, q, lay, ri, False) for im, (_, _, lay, q, ri, _) in zip(imgs, cases)]
+    two_expected = [_single(dec, im, q, lay, ri, False) for im, (_, _, lay, q, ri, _) in zip(two_imgs, two_cases)]
+    frames, keep = _device_frames(cases, imgs)
+    two_frames, two_keep = _device_frames(two_cases, two_imgs)
+    first = dec.encode_ragged_device(frames, False, precision=_precisions(imgs))
+    first_stats = dec.encode_ragged_stats()
+    two = dec.encode_ragged_device(two_frames, False, precision=[8, 8])
+    two_stats = dec.encode_ragged_stats()
+    again = dec.encode_ragged_device(frames, False, precision=_precisions(imgs))
+    assert dec.encode_ragged_stats() == first_stats
+    assert first_stats["pictures"] == 8 and first_stats["passes"] == 1 and first_stats["host_syncs"] == 4
+    assert two_stats["pictures"] == 2 and two_stats["passes"] == 1 and two_stats["host_syncs"] == 3
+    assert len(first) == len(again) == 8 and len(two) == 2
+    for i, c in enumerate(cases):
+        assert _sof(expected[i]) == ((0xC1, 12) if c[5] == 12 else (0xC0, 8))
+        assert first[i] == expected[i], ("first", i, c)
+        assert again[i] == expected[i], ("again", i, c)
+    for i, c in enumerate(two_cases):
+        assert two[i] == two_expected[i], ("two", i, c)
+    del keep, two_keep
+
+
 def test_failure_leaves_nothing_behind(dec):
     L = api.lib()
     cases, imgs = _small_list(6, (8, 12))

@@ -2,7 +2,8 @@
 ragged flavour (ragged_twin, kernels.hip) and asks nothing about the group: that rests on the planner (plan_reconstruct) naming a
 kernel of the ragged families only for frames of that family's layout and precision.  Pinned here, without a device, over every
 layout the planner tells apart, both precisions, the colour transformation on and off, both arithmetic flavours and every range
-gate from both sides.  tests/cxx/fused_list_tables.cpp: the tables of those launches (fused_list.hpp) under the sanitizers."""
+gate from both sides.  tests/cxx/fused_list_tables.cpp: the tables of those launches (fused_list.hpp) under the sanitizers;
+tests/cxx/encode_list_tables.cpp: the other direction's device-free half, the passes of the ragged encode (encode_list.hpp)."""
 import ctypes as C
 import itertools
 import os
@@ -49,13 +50,26 @@ def test_a_ragged_kernel_is_named_for_its_layout_group_only():
     assert all(g < 0 for f, g in zip(infos, group) if (f.hsamp[0], f.vsamp[0]) in ((1, 2), (4, 1)) or (f.components == 1 and f.hsamp[0] == 2))
 
 
+def _run_under_sanitizers(tmp_path, name, *more_sources):
+    """tests/cxx/<name>.cpp (and library sources that need no device) as a program of its own under AddressSanitizer and UBSan."""
+    cxx = "/opt/rocm/lib/llvm/bin/clang++"  # (ROCm's host clang++: a plain host compile, no device code)
+    exe = str(tmp_path / name)
+    csrc = os.path.join(ROOT, "libjpeg_amd", "csrc")
+    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-isystem", "/opt/rocm/include", "-I", csrc,
+                    os.path.join(ROOT, "tests", "cxx", name + ".cpp"), *[os.path.join(csrc, s) for s in more_sources], "-pthread", "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("OK "), (r.stdout[-500:], r.stderr[-3000:])
+
+
 def test_fused_list_tables_under_sanitizers(tmp_path):
     """tests/cxx/fused_list_tables.cpp, a program of its own around fused_list.hpp: grouping, layout and fill of the list launches'
     tables, every field read back from a heap buffer of exactly the layout's size, under AddressSanitizer and UBSan."""
-    cxx = "/opt/rocm/lib/llvm/bin/clang++"  # (ROCm's host clang++: a plain host compile, no device code)
-    exe = str(tmp_path / "fused_list_tables")
-    subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-fno-omit-frame-pointer", "-D__HIP_PLATFORM_AMD__", "-isystem", "/opt/rocm/include", "-I", os.path.join(ROOT, "libjpeg_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "cxx", "fused_list_tables.cpp"), "-o", exe], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and r.stdout.startswith("OK "), (r.stdout[-500:], r.stderr[-3000:])
+    _run_under_sanitizers(tmp_path, "fused_list_tables")
+
+
+def test_encode_list_tables_under_sanitizers(tmp_path):
+    """tests/cxx/encode_list_tables.cpp, a program of its own around encode_list.hpp and encoder.cpp: the passes of the ragged
+    encode from the real planner, layout and fill -- arenas of exactly their sizes, every pointer, prefix table and work list read
+    back, the plain buffer and every picture's piece of a fake output arena -- under AddressSanitizer and UBSan."""
+    _run_under_sanitizers(tmp_path, "encode_list_tables", "encoder.cpp")
