@@ -531,20 +531,28 @@ class Decoder:
         self._check(lib().mijpeg_reconstruct_rect(self._h, x0, y0, x1, y1, comp0, comp1, flags, dst, bpp, bpr))
         return out
 
-    def display_rect(self, canvas: np.ndarray, x0, y0, x1, y1, comp0=0, comp1=None, flags: int = 0, bm_height: int | None = None) -> None:
+    def display_rect(self, canvas: np.ndarray, x0, y0, x1, y1, comp0=0, comp1=None, flags: int = 0, bm_height: int | None = None,
+                     bm_width=None, device_ptrs=None) -> None:
         """mijpeg_display_rect: one JPEG::DisplayRectangle call of a sequence (the object keeps the reference's state between
-        calls).  canvas: (ncomp, H, W) planar uint8 / uint16, written in place; bm_height: BIO_HEIGHT the hook would report."""
+        calls).  canvas: (ncomp, H, W) planar uint8 / uint16, written in place; bm_height: BIO_HEIGHT the hook would report;
+        bm_width: BIO_WIDTH, one value or one per component (default: the canvas's width).  device_ptrs: per component the device
+        address of pixel (0, 0) of a plane laid out like canvas[c] -- the bitmaps live in device memory (MIJPEG_FLAG_DEVICE_OUTPUT)
+        and `canvas` only describes them."""
         f = self.info
         nc = f.components
         comp1 = nc - 1 if comp1 is None else comp1
         sb = canvas.dtype.itemsize
         H, W = canvas.shape[1:]
+        widths = [W] * nc if bm_width is None else list(bm_width) if np.ndim(bm_width) else [bm_width] * nc
+        if device_ptrs is not None:
+            _foreign_work_done()
+            flags |= FLAG_DEVICE_OUTPUT
         maps = (MijpegBitmap * 4)()
         for c in range(nc):
-            maps[c].data = canvas[c].ctypes.data
+            maps[c].data = canvas[c].ctypes.data if device_ptrs is None else device_ptrs[c]
             maps[c].bytes_per_pixel = sb
             maps[c].bytes_per_row = canvas.strides[1]
-            maps[c].width = W
+            maps[c].width = widths[c]
             maps[c].height = H if bm_height is None else bm_height
         self._check(lib().mijpeg_display_rect(self._h, x0, y0, x1, y1, comp0, comp1, flags, maps))
 

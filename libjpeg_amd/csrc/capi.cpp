@@ -1,8 +1,8 @@
 // capi.cpp -- the C ABI of include/mijpeg.h: decoder object (host entropy decoding + streaming upload +
-// GPU reconstruction + rectangle service) and uniform batches.  The kernel selection and the launch are in
-// reconstruct_device.cpp, ragged batches in ragged_decode.cpp, the encoder direction in encode_device.cpp.  Compiled with
-// hipcc (host side only uses the HIP runtime API).  There is NO CPU fallback for the reconstruction: without a device the
-// reconstruct calls fail with MIJPEG_ERR_DEVICE.
+// GPU reconstruction of whole frames) and uniform batches.  The kernel selection and the launch are in
+// reconstruct_device.cpp, the rectangle service in rect_service.cpp, ragged batches in ragged_decode.cpp, the encoder direction
+// in encode_device.cpp.  Compiled with hipcc (host side only uses the HIP runtime API).  There is NO CPU fallback for the
+// reconstruction: without a device the reconstruct calls fail with MIJPEG_ERR_DEVICE.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -167,7 +167,7 @@ static void release_big(int device, bool pinned, void *p, size_t bytes)
 }
 
 // A buffer that grows through the buffer cache: device memory, or pinned host memory (the coefficient store and the frame)
-static int ensure_cached(mijpeg_decoder *d, bool pinned, void **ptr, size_t *cap, size_t bytes)
+int ensure_cached(mijpeg_decoder *d, bool pinned, void **ptr, size_t *cap, size_t bytes)
 {
   if (*cap >= bytes) return MIJPEG_OK;
   quiesce(d); // (the buffer may go to another object: nothing of this one may still read or write it)
@@ -1224,41 +1224,6 @@ try {
 // ------------------------------------------------------------------------------------------------
 // decoder-object reconstruction
 // ------------------------------------------------------------------------------------------------
-// The frame as the reconstruction sees it: the whole picture, or -- without upsampling -- one component at its own
-// resolution, which is a single-component identity-transformed frame over that component's coefficient plane
-// (BlockBitmapRequester::ReconstructUnsampled with rr_bUpsampling = false: control/blockbitmaprequester.cpp:1013-1074,
-// control/bitmapctrl.cpp:273-294; the colour transformation is off then, codestream/rectanglerequest.cpp:157-159).
-static mijpeg_info view_of(const mijpeg_info &f, int comp)
-{
-  if (comp < 0) return f;
-  mijpeg_info v = f;
-  v.components = 1;
-  v.width = (f.width + f.subx[comp] - 1) / f.subx[comp];
-  v.height = (f.height + f.suby[comp] - 1) / f.suby[comp];
-  v.hsamp[0] = v.vsamp[0] = v.subx[0] = v.suby[0] = 1;
-  v.quant_index[0] = f.quant_index[comp];
-  v.blocks_w[0] = f.blocks_w[comp];
-  v.blocks_h[0] = f.blocks_h[comp];
-  v.mcus_x = v.blocks_w[0];
-  v.mcus_y = v.blocks_h[0];
-  v.coef_offset[0] = 0;
-  v.coef_count = (int64_t)v.blocks_w[0] * v.blocks_h[0] * 64;
-  v.range_max[0] = f.range_max[comp];
-  v.ycbcr = 0;
-  return v;
-}
-
-static int reconstruct_view(mijpeg_decoder *d, int comp, void *dst_device, int64_t row_stride, uint32_t flags, int sync)
-{
-  HIP_TRY(d, hipSetDevice(d->device));
-  const mijpeg_info v = view_of(d->host.info, comp);
-  mijpeg_batch b = batch_of(v, d->coef_dev + (comp < 0 ? 0 : d->host.info.coef_offset[comp]), dst_device, row_stride, row_stride * v.height, 1, flags);
-  b.xt = d->host.is_xt() ? &d->host.xt : nullptr;
-  if (const int rc = reconstruct_on(d, b, nullptr, "stream")) return rc;
-  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
-  return MIJPEG_OK;
-}
-
 int mijpeg_reconstruct_device(mijpeg_decoder *d, void *dst_device, int64_t row_stride, uint32_t flags, int sync)
 try {
   if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
@@ -1329,504 +1294,6 @@ try {
   d->img_valid = false;
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(d, "mijpeg_reconstruct_host"); }
-
-static int serve_rect(mijpeg_decoder *d, int view, uint32_t flags, bool to_device, int32_t min_x, int32_t min_y, int32_t max_x, int32_t max_y,
-                      int32_t min_comp, int32_t max_comp, void *const dst[MIJPEG_MAX_COMPONENTS],
-                      const int32_t bytes_per_pixel[MIJPEG_MAX_COMPONENTS], const int32_t bytes_per_row[MIJPEG_MAX_COMPONENTS]);
-
-int mijpeg_reconstruct_rect(mijpeg_decoder *d, int32_t min_x, int32_t min_y, int32_t max_x, int32_t max_y, int32_t min_comp,
-                            int32_t max_comp, uint32_t flags, void *const dst[MIJPEG_MAX_COMPONENTS],
-                            const int32_t bytes_per_pixel[MIJPEG_MAX_COMPONENTS],
-                            const int32_t bytes_per_row[MIJPEG_MAX_COMPONENTS])
-try {
-  if (!d || !dst || !bytes_per_pixel || !bytes_per_row) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device < 0) return set_error(d, MIJPEG_ERR_DEVICE, "decoder was created without a device: no reconstruction path");
-  if (!d->uploaded) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded coefficients: call mijpeg_decode_coefficients first");
-  const bool to_device = (flags & MIJPEG_FLAG_DEVICE_OUTPUT) != 0;
-  const bool unsampled = (flags & MIJPEG_FLAG_NO_UPSAMPLING) != 0;
-  flags &= ~(MIJPEG_FLAG_DEVICE_OUTPUT | MIJPEG_FLAG_NO_UPSAMPLING);
-  int view = -1; // component whose own sample grid is reconstructed, -1: the upsampled picture
-  if (unsampled) {
-    // control/bitmapctrl.cpp:273-294: one component at a time, no colour transformation, and the rectangle (given
-    // on the canvas) shrinks to the component's grid
-    if (min_comp < 0) min_comp = 0;
-    if (max_comp >= d->host.info.components) max_comp = d->host.info.components - 1;
-    if (min_comp != max_comp)
-      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "if upsampling is disabled, components can only be reconstructed one by one");
-    if (d->host.is_xt())
-      return set_error(d, MIJPEG_ERR_OPERATION_UNIMPLEMENTED, "JPEG XT frames are not reconstructed without upsampling (the reference merges the component with residual scratch buffers it never initialised)");
-    view = min_comp;
-    flags |= MIJPEG_FLAG_NO_COLOR_TRANSFORM;
-    const int sx = d->host.info.subx[view], sy = d->host.info.suby[view];
-    min_x = (std::max(min_x, 0) + sx - 1) / sx;
-    max_x = (max_x + sx) / sx - 1;
-    min_y = (std::max(min_y, 0) + sy - 1) / sy;
-    max_y = (max_y + sy) / sy - 1;
-  }
-  void *vdst[MIJPEG_MAX_COMPONENTS] = {dst[0], dst[1], dst[2], dst[3]};
-  int32_t vbpp[MIJPEG_MAX_COMPONENTS] = {bytes_per_pixel[0], bytes_per_pixel[1], bytes_per_pixel[2], bytes_per_pixel[3]};
-  int32_t vbpr[MIJPEG_MAX_COMPONENTS] = {bytes_per_row[0], bytes_per_row[1], bytes_per_row[2], bytes_per_row[3]};
-  if (view >= 0) { // the view has one component, number 0
-    vdst[0] = dst[view];
-    vbpp[0] = bytes_per_pixel[view];
-    vbpr[0] = bytes_per_row[view];
-    min_comp = max_comp = 0;
-  }
-  return serve_rect(d, view, flags, to_device, min_x, min_y, max_x, max_y, min_comp, max_comp, vdst, vbpp, vbpr);
-} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_rect"); }
-
-// The rectangle [min_x, max_x] x [min_y, max_y] (on the grid of `view`: the canvas, or a component's own samples) of the
-// plain picture, components [min_comp, max_comp] of the view, into the bitmaps.
-static int serve_rect(mijpeg_decoder *d, int view, uint32_t flags, bool to_device, int32_t min_x, int32_t min_y, int32_t max_x, int32_t max_y,
-                      int32_t min_comp, int32_t max_comp, void *const dst[MIJPEG_MAX_COMPONENTS],
-                      const int32_t bytes_per_pixel[MIJPEG_MAX_COMPONENTS], const int32_t bytes_per_row[MIJPEG_MAX_COMPONENTS])
-{
-  const mijpeg_info f = view_of(d->host.info, view);
-  const int sb = f.sample_bytes > 0 ? f.sample_bytes : 1; // bytes per sample
-  const int nc = f.components;
-  // the whole frame is reconstructed once per (stream, flags, view) and then served rectangle by rectangle,
-  // which is what the stripe loop of cmd/reconstruct.cpp:334-342 asks for
-  const size_t row = ((size_t)f.width * nc * sb + 7) & ~(size_t)7;
-  const size_t padded = row * f.height;
-  using clk = std::chrono::steady_clock;
-  if (!d->img_valid || d->img_flags != flags || d->img_view != view) {
-    HIP_TRY(d, hipSetDevice(d->device));
-    int rc = ensure_dev(d, (void **)&d->img_dev, &d->img_dev_cap, padded);
-    if (rc) return rc;
-    auto t0 = clk::now();
-    HIP_TRY(d, hipStreamSynchronize(d->stream)); // uploads complete
-    auto t1 = clk::now();
-    rc = reconstruct_view(d, view, d->img_dev, (int64_t)row, flags, to_device ? 1 : 0); // host requests: the copy below follows in stream order
-    if (rc) return rc;
-    d->timing[1] = std::chrono::duration<double>(t1 - t0).count();
-    d->timing[2] = std::chrono::duration<double>(clk::now() - t1).count();
-    d->timing[3] = 0;
-    d->img_valid = true;
-    d->img_host_valid = false;
-    d->img_flags = flags;
-    d->img_view = view;
-  }
-  if (!to_device && !d->img_host_valid) {
-    HIP_TRY(d, hipSetDevice(d->device));
-    if (const int prc = ensure_cached(d, true, (void **)&d->img_host, &d->img_host_cap, padded)) return prc;
-    // bands of about 4 MiB (at least 8 lines): enqueue all of them now, wait for them as they are asked for
-    static const long band_mib = getenv("MIJPEG_RECT_BAND_MIB") ? atol(getenv("MIJPEG_RECT_BAND_MIB")) : 4; // tuning; <= 0: one band
-    d->band_lines = band_mib <= 0 ? f.height : (int)std::max<size_t>(8, (((size_t)band_mib << 20) / std::max<size_t>(row, 1) + 7) & ~(size_t)7);
-    d->bands = (f.height + d->band_lines - 1) / d->band_lines;
-    while ((int)d->band_events.size() < d->bands) {
-      hipEvent_t e;
-      HIP_TRY(d, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      d->band_events.push_back(e);
-    }
-    for (int b = 0; b < d->bands; b++) {
-      const size_t y0 = (size_t)b * d->band_lines, y1 = std::min<size_t>(f.height, y0 + d->band_lines);
-      HIP_TRY(d, hipMemcpyAsync(d->img_host + y0 * row, d->img_dev + y0 * row, (y1 - y0) * row, hipMemcpyDeviceToHost, d->stream));
-      HIP_TRY(d, hipEventRecord(d->band_events[(size_t)b], d->stream));
-    }
-    d->bands_waited = 0;
-    d->img_host_valid = true;
-  }
-  // bands [0, upto] of the host copy have arrived when this returns
-  auto wait_bands = [&](int upto) -> int {
-    auto t2 = clk::now();
-    for (; d->bands_waited <= upto && d->bands_waited < d->bands; d->bands_waited++)
-      HIP_TRY(d, hipEventSynchronize(d->band_events[(size_t)d->bands_waited]));
-    d->timing[3] += std::chrono::duration<double>(clk::now() - t2).count();
-    return MIJPEG_OK;
-  };
-  if (min_x < 0) min_x = 0;
-  if (min_y < 0) min_y = 0;
-  if (max_x >= f.width) max_x = f.width - 1;
-  if (max_y >= f.height) max_y = f.height - 1;
-  if (min_comp < 0) min_comp = 0;
-  if (max_comp >= nc) max_comp = nc - 1;
-  // an empty request after clipping is served by doing nothing (codestream/rectanglerequest.cpp clips alike)
-  if (min_x > max_x || min_y > max_y || min_comp > max_comp) return MIJPEG_OK;
-  if (to_device) {
-    ScatterArgs a;
-    memset(&a, 0, sizeof(a));
-    a.src = d->img_dev;
-    a.src_row = (int64_t)row;
-    a.ncomp = nc;
-    a.sample_bytes = sb;
-    a.x0 = min_x;
-    a.y0 = min_y;
-    a.w = max_x - min_x + 1;
-    a.h = max_y - min_y + 1;
-    a.c0 = min_comp;
-    a.c1 = max_comp;
-    for (int c = 0; c < nc; c++) {
-      a.dst[c] = (uint8_t *)dst[c];
-      a.bytes_per_pixel[c] = bytes_per_pixel[c];
-      a.bytes_per_row[c] = bytes_per_row[c];
-    }
-    HIP_TRY(d, hipSetDevice(d->device));
-    if (launch_scatter_rect(a, d->stream)) return hip_fail(d, hipGetLastError(), "scatter_rect_kernel launch");
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
-    return MIJPEG_OK;
-  }
-  // interleaved destination (the layout cmd/bitmaphook.cpp hands out): whole lines at once
-  bool interleaved = min_comp == 0 && max_comp == nc - 1 && dst[0];
-  for (int c = 0; c < nc && interleaved; c++)
-    interleaved = dst[c] == (uint8_t *)dst[0] + c * sb && bytes_per_pixel[c] == nc * sb && bytes_per_row[c] == bytes_per_row[0];
-  if (interleaved) {
-    const size_t line = (size_t)(max_x - min_x + 1) * nc * sb;
-    const int lines = max_y - min_y + 1;
-    auto copy_lines = [&](int y0, int y1) {
-      for (int y = y0; y < y1; y++)
-        memcpy((uint8_t *)dst[0] + (ptrdiff_t)y * bytes_per_row[0] + (ptrdiff_t)min_x * nc * sb,
-               d->img_host + (size_t)y * row + (size_t)min_x * nc * sb, line);
-    };
-    // big rectangles (whole frames) are copied by the worker pool, one memcpy stream per worker, in a few slabs: the
-    // workers copy slab k while the bands of slab k + 1 are still arriving
-    const int parts = (int)std::min<size_t>((size_t)std::min(default_threads(), 16), line * lines / (4u << 20));
-    if (parts > 1) {
-      const int slabs = std::min(4, std::max(1, lines / (8 * d->band_lines)));
-      for (int k = 0; k < slabs; k++) {
-        const int s0 = min_y + (int)((int64_t)lines * k / slabs), s1 = min_y + (int)((int64_t)lines * (k + 1) / slabs);
-        if (const int rc = wait_bands((s1 - 1) / d->band_lines)) return rc;
-        parallel_for(parts, [&](int i) { copy_lines(s0 + (int)((int64_t)(s1 - s0) * i / parts), s0 + (int)((int64_t)(s1 - s0) * (i + 1) / parts)); });
-      }
-    } else {
-      if (const int rc = wait_bands(max_y / d->band_lines)) return rc;
-      copy_lines(min_y, max_y + 1);
-    }
-    return MIJPEG_OK;
-  }
-  if (const int rc = wait_bands(max_y / d->band_lines)) return rc;
-  for (int c = min_comp; c <= max_comp; c++) {
-    if (!dst[c]) continue;
-    for (int y = min_y; y <= max_y; y++) {
-      const uint8_t *src = d->img_host + (size_t)y * row + ((size_t)min_x * nc + c) * sb;
-      uint8_t *out = (uint8_t *)dst[c] + (ptrdiff_t)y * bytes_per_row[c] + (ptrdiff_t)min_x * bytes_per_pixel[c];
-      const int n = max_x - min_x + 1;
-      const int bpp = bytes_per_pixel[c];
-      if (sb == 1) {
-        if (nc == 1 && bpp == 1) memcpy(out, src, (size_t)n);
-        else
-          for (int x = 0; x < n; x++) out[(ptrdiff_t)x * bpp] = src[(size_t)x * nc];
-      } else {
-        for (int x = 0; x < n; x++) memcpy(out + (ptrdiff_t)x * bpp, src + (size_t)x * nc * 2, 2);
-      }
-    }
-  }
-  return MIJPEG_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// JPEG::DisplayRectangle as a sequence of calls: request_model.hpp plans, this serves
-// ------------------------------------------------------------------------------------------------
-// Frame description for a request that does not show the plain picture: the whole picture, or -- without upsampling --
-// the grid of component `view` with every component of the frame on it (the ones that were not asked for are zeros; only
-// a colour transformer left over from earlier upsampled requests makes them matter).
-static mijpeg_info request_frame(const mijpeg_info &f, int view, bool all_components)
-{
-  if (view < 0) return f;
-  if (!all_components) return view_of(f, view);
-  mijpeg_info v = f;
-  v.width = (f.width + f.subx[view] - 1) / f.subx[view];
-  v.height = (f.height + f.suby[view] - 1) / f.suby[view];
-  for (int c = 0; c < f.components; c++) {
-    v.hsamp[c] = v.vsamp[c] = v.subx[c] = v.suby[c] = 1;
-    v.blocks_w[c] = f.blocks_w[view];
-    v.blocks_h[c] = f.blocks_h[view];
-    v.coef_offset[c] = f.coef_offset[view]; // read only where the row map says so: component `view`
-    v.quant_index[c] = f.quant_index[view];
-    v.range_max[c] = f.range_max[view];
-  }
-  v.mcus_x = v.blocks_w[0];
-  v.mcus_y = v.blocks_h[0];
-  return v;
-}
-
-// The request models of a decoded image start with its first DisplayRectangle call (every decode resets them): one for a plain
-// frame; two for a JPEG XT frame -- legacy and residual image share m_bSubsampling (request_model.hpp)
-static void ensure_request_models(mijpeg_decoder *d)
-{
-  if (d->model_valid) return;
-  const mijpeg_info &f = d->host.info;
-  if (d->host.is_xt() && f.components == 3) {
-    const mijpeg_info &r = d->host.xt.residual;
-    bool lsub = false, rsub = false;
-    for (int c = 0; c < 3; c++) {
-      lsub = lsub || f.subx[c] > 1 || f.suby[c] > 1;
-      rsub = rsub || r.subx[c] > 1 || r.suby[c] > 1;
-    }
-    d->model.reset(3, f.width, f.height, f.subx, f.suby, true, false, nullptr, nullptr, rsub);
-    d->rmodel.reset(3, f.width, f.height, r.subx, r.suby, true, false, nullptr, nullptr, lsub);
-  } else
-    d->model.reset(f.components, f.width, f.height, f.subx, f.suby, f.ycbcr != 0, f.dnl != 0, f.rows, f.blocks_h);
-  d->model_valid = true;
-}
-
-// The lines a request reconstructed into d->req_dev (row bytes each, nc interleaved samples of sb bytes) go out to the client's
-// bitmaps: columns [min_x, cx1[c]], lines [min_y, cy1[c]] of component c
-static int hand_out_request(mijpeg_decoder *d, int min_x, int min_y, int y_count, const int32_t *cx1, const int32_t *cy1, int min_comp, int max_comp,
-                            int nc, int sb, size_t row, size_t padded, int vc, bool all_on_view, bool to_device, void *const *dst, const int32_t *bpp,
-                            const int32_t *bpr)
-{
-  // hand the lines out
-  for (int c = min_comp; c <= max_comp; c++) {
-    if (!dst[c] || cx1[c] < min_x || cy1[c] < min_y) continue;
-    const int plane = vc >= 0 ? (all_on_view ? c : 0) : c;
-    if (to_device) {
-      ScatterArgs a;
-      memset(&a, 0, sizeof(a));
-      a.src = d->req_dev;
-      a.src_row = (int64_t)row;
-      a.ncomp = nc;
-      a.sample_bytes = sb;
-      a.x0 = min_x;
-      a.y0 = min_y;
-      a.w = cx1[c] - min_x + 1;
-      a.h = cy1[c] - min_y + 1;
-      a.c0 = a.c1 = plane;
-      a.dst[plane] = (uint8_t *)dst[c];
-      a.bytes_per_pixel[plane] = bpp[c];
-      a.bytes_per_row[plane] = bpr[c];
-      if (launch_scatter_rect(a, d->stream)) return hip_fail(d, hipGetLastError(), "scatter_rect_kernel launch");
-    }
-  }
-  if (to_device) {
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
-    return MIJPEG_OK;
-  }
-  if (const int prc = ensure_pinned(d, &d->req_host, &d->req_host_cap, padded)) return prc;
-  HIP_TRY(d, hipMemcpyAsync(d->req_host + (size_t)min_y * row, d->req_dev + (size_t)min_y * row, (size_t)y_count * row, hipMemcpyDeviceToHost,
-                            d->stream));
-  HIP_TRY(d, hipStreamSynchronize(d->stream));
-  for (int c = min_comp; c <= max_comp; c++) {
-    if (!dst[c] || cx1[c] < min_x || cy1[c] < min_y) continue;
-    const int plane = vc >= 0 ? (all_on_view ? c : 0) : c;
-    const int n = cx1[c] - min_x + 1;
-    for (int y = min_y; y <= cy1[c]; y++) {
-      const uint8_t *src = d->req_host + (size_t)y * row + ((size_t)min_x * nc + plane) * sb;
-      uint8_t *out = (uint8_t *)dst[c] + (ptrdiff_t)y * bpr[c] + (ptrdiff_t)min_x * bpp[c];
-      if (sb == 1)
-        for (int x = 0; x < n; x++) out[(ptrdiff_t)x * bpp[c]] = src[(size_t)x * nc];
-      else
-        for (int x = 0; x < n; x++) memcpy(out + (ptrdiff_t)x * bpp[c], src + (size_t)x * nc * 2, 2);
-    }
-  }
-  return MIJPEG_OK;
-}
-
-int mijpeg_display_rect(mijpeg_decoder *d, int32_t min_x, int32_t min_y, int32_t max_x, int32_t max_y, int32_t min_comp, int32_t max_comp,
-                        uint32_t flags, const mijpeg_bitmap bitmaps[MIJPEG_MAX_COMPONENTS])
-try {
-  if (!d || !bitmaps) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device < 0) return set_error(d, MIJPEG_ERR_DEVICE, "decoder was created without a device: no reconstruction path");
-  if (!d->uploaded) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded coefficients: call mijpeg_decode_coefficients first");
-  const mijpeg_info &f = d->host.info;
-  const bool to_device = (flags & MIJPEG_FLAG_DEVICE_OUTPUT) != 0;
-  const bool upsample = !(flags & MIJPEG_FLAG_NO_UPSAMPLING);
-  const bool ctrafo = !(flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM);
-  const uint32_t pass = flags & (MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_FORCE_SAFE);
-  if (min_comp < 0) min_comp = 0;
-  if (max_comp >= f.components) max_comp = f.components - 1;
-  if (!upsample && min_comp != max_comp && min_comp <= max_comp)
-    return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "if upsampling is disabled, components can only be reconstructed one by one");
-  void *dst[MIJPEG_MAX_COMPONENTS];
-  int32_t bpp[MIJPEG_MAX_COMPONENTS], bpr[MIJPEG_MAX_COMPONENTS];
-  uint32_t bm_h[MIJPEG_MAX_COMPONENTS], bm_w[MIJPEG_MAX_COMPONENTS];
-  for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) {
-    dst[c] = bitmaps[c].data;
-    bpp[c] = bitmaps[c].bytes_per_pixel;
-    bpr[c] = bitmaps[c].bytes_per_row;
-    bm_w[c] = bitmaps[c].width;
-    bm_h[c] = bitmaps[c].height;
-  }
-  if (d->host.is_xt()) {
-    // JPEG XT: the residual image has row cursors and upsamplers of its own beside the legacy image's
-    // (control/blockbitmaprequester.cpp:228-232, 356-372, 1118-1146, 1197-1222): one request model per image, fed the same
-    // requests.  In the contract: what the reference's command line asks for -- all three components, upsampling and colour
-    // transformation on -- with any order and size of rectangles.  (A component subset merges with whatever m_ppDTemp holds from
-    // the block before, a request without the transformation builds another transformer: served as the plain picture.)
-    const mijpeg_xt_params &x = d->host.xt;
-    auto plain_picture = [&]() -> int {
-      uint32_t maxmcu = 0xffffffffu;
-      for (int c = min_comp; c <= max_comp; c++) maxmcu = std::min(maxmcu, (bm_h[c] >> 3) - 1u);
-      if (maxmcu != 0xffffffffu && (int64_t)max_y > (int64_t)maxmcu * 8 + 7) max_y = (int32_t)(maxmcu * 8 + 7);
-      if (max_y < min_y) return MIJPEG_OK;
-      return mijpeg_reconstruct_rect(d, min_x, min_y, max_x, max_y, min_comp, max_comp, flags, dst, bpp, bpr);
-    };
-    if (!upsample || !ctrafo || min_comp != 0 || max_comp != 2 || f.components != 3) return plain_picture();
-    const mijpeg_info &r = x.residual;
-    ensure_request_models(d);
-    const RequestPlan pl = d->model.request(min_x, min_y, max_x, max_y, 0, 2, true, true, bm_h);
-    const RequestPlan pr = x.no_residual ? pl : d->rmodel.request(min_x, min_y, max_x, max_y, 0, 2, true, true, bm_h);
-    if (pl.nothing) return MIJPEG_OK;
-    // a residual component without an upsampler whose cursor stands behind its last row: `rrow->BlockAt(x)` on a NULL row
-    // (:1057-1058, :1201-1202) -- the reference does not survive this request
-    if (!x.no_residual)
-      for (int c = 0; c < 3; c++)
-        if (!(pr.upsampling_path && pr.upsampler[c]))
-          for (int g = pr.g0[c]; g <= pr.g1[c]; g++)
-            if (g >= (int)pr.rowmap[c].size() || pr.rowmap[c][(size_t)g] < 0)
-              return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST,
-                               "the request walks the residual image's row cursor behind its last row (the reference dereferences a NULL row here)");
-    // BitmapCtrl::ExtractBitmap (interface/imagebitmap.cpp:58-129): blocks whose corner lies outside the bitmap the hook described
-    // are not written
-    int32_t cx1[MIJPEG_MAX_COMPONENTS], cy1[MIJPEG_MAX_COMPONENTS];
-    for (int c = 0; c < 3; c++) {
-      auto last_in = [](int32_t lo, int32_t hi, uint32_t extent) -> int32_t {
-        if ((uint32_t)lo >= extent) return lo - 1;
-        const int64_t last_block = ((int64_t)extent - 1) >> 3;
-        return (int32_t)std::min<int64_t>(hi, std::max<int64_t>(last_block, lo >> 3) * 8 + 7);
-      };
-      cx1[c] = last_in(pl.min_x, pl.max_x, bm_w[c]);
-      cy1[c] = last_in(pl.min_y, pl.max_y, bm_h[c]);
-    }
-    if (pl.plain && (x.no_residual || pr.plain)) {
-      for (int c = 0; c <= 2;) { // components with the same writable extent go out together (all of them, normally)
-        int e = c;
-        while (e + 1 <= 2 && cx1[e + 1] == cx1[c] && cy1[e + 1] == cy1[c]) e++;
-        if (cx1[c] >= pl.min_x && cy1[c] >= pl.min_y) {
-          const int rc = mijpeg_reconstruct_rect(d, pl.min_x, pl.min_y, cx1[c], cy1[c], c, e, flags, dst, bpp, bpr);
-          if (rc) return rc;
-        }
-        c = e + 1;
-      }
-      return MIJPEG_OK;
-    }
-    // ---- not the plain picture: both images through the unfused kernels with their row maps on this request's lines
-    HIP_TRY(d, hipSetDevice(d->device));
-    const int sb = f.sample_bytes > 0 ? f.sample_bytes : 2;
-    const size_t row = ((size_t)f.width * 3 * sb + 7) & ~(size_t)7, padded = row * f.height;
-    int rc = ensure_dev(d, (void **)&d->req_dev, &d->req_dev_cap, padded);
-    if (rc) return rc;
-    int stride = 1;
-    for (int c = 0; c < 3; c++) stride = std::max(stride, std::max(f.blocks_h[c], r.blocks_h[c]));
-    std::vector<int32_t> maps((size_t)6 * stride);
-    for (int pn = 0; pn < 6; pn++) {
-      const RequestPlan &p = pn < 3 ? pl : pr;
-      const int c = pn % 3;
-      int32_t *m = maps.data() + (size_t)pn * stride;
-      for (int g = 0; g < stride; g++) m[g] = g;
-      if (pn >= 3 && x.no_residual) continue;
-      for (int g = p.g0[c]; g <= p.g1[c] && g < stride && g < (int)p.rowmap[c].size(); g++) m[g] = p.rowmap[c][(size_t)g];
-    }
-    rc = ensure_dev(d, (void **)&d->rowmap_dev, &d->rowmap_cap, maps.size() * sizeof(int32_t));
-    if (rc) return rc;
-    HIP_TRY(d, hipMemcpyAsync(d->rowmap_dev, maps.data(), maps.size() * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream)); // `maps` is pageable and leaves scope
-    mijpeg_batch b = batch_of(f, d->coef_dev, d->req_dev, (int64_t)row, (int64_t)padded, 1, pass | MIJPEG_FLAG_FORCE_GENERIC);
-    b.xt = &x;
-    const int y_count = pl.max_y - pl.min_y + 1;
-    RequestExtra rx;
-    memset(&rx, 0, sizeof(rx));
-    rx.rowmap_dev = d->rowmap_dev;
-    rx.rowmap_stride = stride;
-    rx.corner_x = pl.corner_x;
-    rx.corner_y = pl.corner_y;
-    rx.y_base = pl.min_y;
-    rx.y_count = y_count;
-    rx.ycc = 1;
-    for (int pn = 0; pn < 6; pn++) {
-      const RequestPlan &p = pn < 3 ? pl : pr;
-      const mijpeg_info &g = pn < 3 ? f : r;
-      const int c = pn % 3;
-      const bool up = p.upsampling_path && p.upsampler[c] && !(pn >= 3 && x.no_residual);
-      rx.wstart[pn] = up ? p.wstart[c] : 0;
-      rx.wlimit[pn] = up ? p.wlimit[c] : (f.height + g.suby[c] - 1) / std::max(1, g.suby[c]);
-    }
-    if ((rc = reconstruct_on(d, b, &rx, "request"))) return rc;
-    return hand_out_request(d, pl.min_x, pl.min_y, y_count, cx1, cy1, 0, 2, 3, sb, row, padded, -1, false, to_device, dst, bpp, bpr);
-  }
-  ensure_request_models(d);
-  const RequestPlan p = d->model.request(min_x, min_y, max_x, max_y, min_comp, max_comp, upsample, ctrafo, bm_h);
-  if (p.nothing) return MIJPEG_OK;
-  // BitmapCtrl::ExtractBitmap (interface/imagebitmap.cpp:58-129): a block whose corner lies outside the bitmap the hook
-  // described is blank -- nothing of it is written; one that starts inside is written in full
-  int32_t cx1[MIJPEG_MAX_COMPONENTS], cy1[MIJPEG_MAX_COMPONENTS];
-  auto last_inside = [](int32_t lo, int32_t hi, uint32_t extent) -> int32_t { // last sample of the blocks whose corner is below extent
-    if ((uint32_t)lo >= extent) return lo - 1;
-    const int64_t last_block = ((int64_t)extent - 1) >> 3; // the last block whose (aligned) corner is inside
-    return (int32_t)std::min<int64_t>(hi, std::max<int64_t>(last_block, lo >> 3) * 8 + 7);
-  };
-  for (int c = 0; c < f.components; c++) {
-    cx1[c] = last_inside(p.min_x, p.max_x, bm_w[c]);
-    cy1[c] = last_inside(p.min_y, p.max_y, bm_h[c]);
-  }
-  const int vc = p.view; // without upsampling the single component of the view is number 0 there
-  if (p.plain) {
-    const uint32_t fl = pass | (p.ycc || !f.ycbcr ? 0u : MIJPEG_FLAG_NO_COLOR_TRANSFORM) | (vc >= 0 ? MIJPEG_FLAG_NO_COLOR_TRANSFORM : 0u);
-    // components with the same writable extent go out together (all of them, normally: one interleaved copy)
-    for (int c = min_comp; c <= max_comp;) {
-      int e = c;
-      while (e + 1 <= max_comp && cx1[e + 1] == cx1[c] && cy1[e + 1] == cy1[c]) e++;
-      if (cx1[c] >= p.min_x && cy1[c] >= p.min_y) {
-        int rc;
-        if (vc >= 0) {
-          void *vdst[MIJPEG_MAX_COMPONENTS] = {dst[vc], nullptr, nullptr, nullptr};
-          int32_t vbpp[MIJPEG_MAX_COMPONENTS] = {bpp[vc], 0, 0, 0}, vbpr[MIJPEG_MAX_COMPONENTS] = {bpr[vc], 0, 0, 0};
-          rc = serve_rect(d, vc, fl, to_device, p.min_x, p.min_y, cx1[c], cy1[c], 0, 0, vdst, vbpp, vbpr);
-        } else
-          rc = serve_rect(d, -1, fl, to_device, p.min_x, p.min_y, cx1[c], cy1[c], c, e, dst, bpp, bpr);
-        if (rc) return rc;
-      }
-      c = e + 1;
-    }
-    return MIJPEG_OK;
-  }
-  // ---- not the plain picture: row maps, zeros, displaced upsampler output -> the generic kernels on this request's lines
-  HIP_TRY(d, hipSetDevice(d->device));
-  const bool all_on_view = vc >= 0 && p.ycc;
-  mijpeg_info g = request_frame(f, vc, all_on_view);
-  g.ycbcr = p.ycc ? 1 : 0;
-  const int nc = g.components, sb = g.sample_bytes > 0 ? g.sample_bytes : 1;
-  const size_t row = ((size_t)g.width * nc * sb + 7) & ~(size_t)7, padded = row * g.height;
-  int rc = ensure_dev(d, (void **)&d->req_dev, &d->req_dev_cap, padded);
-  if (rc) return rc;
-  // row maps: identity outside what the plan defines; components that were not asked for are zeros
-  int stride = 1;
-  for (int c = 0; c < nc; c++) stride = std::max(stride, g.blocks_h[c]);
-  std::vector<int32_t> maps((size_t)nc * stride);
-  bool all_zero = !p.ycc;
-  for (int c = 0; c < nc; c++) {
-    const int pc = vc >= 0 ? (all_on_view ? c : vc) : c; // component of the frame behind plane c of the request frame
-    int32_t *m = maps.data() + (size_t)c * stride;
-    for (int r = 0; r < stride; r++) m[r] = r;
-    if (!p.requested[pc]) {
-      for (int r = 0; r < stride; r++) m[r] = -1;
-      continue;
-    }
-    // (a component that appears in no scan carries coefficients that transform to zeros in every row: host_decoder.cpp)
-    for (int r = p.g0[pc]; r <= p.g1[pc] && r < stride && r < (int)p.rowmap[pc].size(); r++) {
-      m[r] = p.rowmap[pc][(size_t)r];
-      if (m[r] >= 0) all_zero = false;
-    }
-  }
-  const int y_count = p.max_y - p.min_y + 1;
-  if (all_zero) {
-    // every sample the request shows is the transform of "no row": 0 through the filters and the identity transformation
-    HIP_TRY(d, hipMemsetAsync(d->req_dev + (size_t)p.min_y * row, 0, (size_t)y_count * row, d->stream));
-  } else {
-    rc = ensure_dev(d, (void **)&d->rowmap_dev, &d->rowmap_cap, maps.size() * sizeof(int32_t));
-    if (rc) return rc;
-    HIP_TRY(d, hipMemcpyAsync(d->rowmap_dev, maps.data(), maps.size() * sizeof(int32_t), hipMemcpyHostToDevice, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream)); // `maps` is pageable and leaves scope; uploads of the coefficients are complete too
-    mijpeg_batch b = batch_of(g, d->coef_dev + (vc >= 0 && !all_on_view ? f.coef_offset[vc] : 0), d->req_dev, (int64_t)row, (int64_t)padded, 1,
-                              pass | MIJPEG_FLAG_FORCE_GENERIC | (p.ycc ? 0u : MIJPEG_FLAG_NO_COLOR_TRANSFORM));
-    RequestExtra rx;
-    memset(&rx, 0, sizeof(rx));
-    rx.rowmap_dev = d->rowmap_dev;
-    rx.rowmap_stride = stride;
-    rx.corner_x = p.corner_x;
-    rx.corner_y = p.corner_y;
-    rx.y_base = p.min_y;
-    rx.y_count = y_count;
-    rx.ycc = p.ycc ? 1 : 0;
-    for (int c = 0; c < nc; c++) {
-      const int pc = vc >= 0 ? vc : c;
-      const bool up = vc < 0 && p.upsampling_path && p.upsampler[pc] && p.requested[pc];
-      rx.wstart[c] = up ? p.wstart[pc] : 0;
-      rx.wlimit[c] = up ? p.wlimit[pc] : (g.dnl && g.suby[c] > 1) ? g.blocks_h[c] * 8 : (g.height + g.suby[c] - 1) / g.suby[c];
-    }
-    if ((rc = reconstruct_on(d, b, &rx, "request"))) return rc;
-  }
-  return hand_out_request(d, p.min_x, p.min_y, y_count, cx1, cy1, min_comp, max_comp, nc, sb, row, padded, vc, all_on_view, to_device, dst, bpp, bpr);
-} catch (...) { return boundary_catch(d, "mijpeg_display_rect"); }
 
 // The scans of one codestream in the order the reference meets them: the codestream's own, then the ones that live in its
 // refinement boxes.  A frame whose decode went through the sequential walk (damaged streams, DNL frames, the residual scan types of
@@ -1903,36 +1370,5 @@ try {
     }
   return n;
 } catch (...) { return boundary_catch(d, "mijpeg_scan_grids"); }
-
-int mijpeg_display_plan(mijpeg_decoder *d, int32_t min_x, int32_t min_y, int32_t max_x, int32_t max_y, int32_t min_comp, int32_t max_comp,
-                        uint32_t flags, const uint32_t bm_height[MIJPEG_MAX_COMPONENTS], int32_t out[8 + 6 * MIJPEG_MAX_COMPONENTS])
-try {
-  if (!d || !bm_height || !out) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->host.info.components < 1 || d->host.info.width < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no parsed stream: call mijpeg_read_header first");
-  const mijpeg_info &f = d->host.info;
-  ensure_request_models(d);
-  const RequestPlan p = d->model.request(min_x, min_y, max_x, max_y, min_comp, max_comp, !(flags & MIJPEG_FLAG_NO_UPSAMPLING),
-                                         !(flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM), bm_height);
-  bool rplain = true;
-  if (d->host.is_xt() && f.components == 3 && !d->host.xt.no_residual) // (the residual image: cursors through mijpeg_display_cursor(4 + c))
-    rplain = d->rmodel.request(min_x, min_y, max_x, max_y, min_comp, max_comp, !(flags & MIJPEG_FLAG_NO_UPSAMPLING),
-                               !(flags & MIJPEG_FLAG_NO_COLOR_TRANSFORM), bm_height).plain;
-  out[0] = p.nothing; out[1] = p.plain && rplain; out[2] = p.ycc; out[3] = p.view;
-  out[4] = p.min_x; out[5] = p.min_y; out[6] = p.max_x; out[7] = p.max_y;
-  for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) {
-    int32_t *o = out + 8 + 6 * c;
-    o[0] = d->model.cursor(c); o[1] = p.g0[c]; o[2] = p.g1[c]; o[3] = p.wstart[c]; o[4] = p.wlimit[c];
-    int zeros = 0;
-    for (int g = p.g0[c]; g <= p.g1[c] && g < (int)p.rowmap[c].size(); g++) zeros += p.rowmap[c][(size_t)g] < 0;
-    o[5] = zeros;
-  }
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_display_plan"); }
-
-int mijpeg_display_cursor(mijpeg_decoder *d, int component)
-try {
-  if (!d || component < 0 || component >= 2 * MIJPEG_MAX_COMPONENTS || !d->model_valid) return 0;
-  return component >= MIJPEG_MAX_COMPONENTS ? d->rmodel.cursor(component - MIJPEG_MAX_COMPONENTS) : d->model.cursor(component);
-} catch (...) { return boundary_catch(d, "mijpeg_display_cursor"); }
 
 } // extern "C"

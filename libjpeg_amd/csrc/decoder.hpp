@@ -1,5 +1,6 @@
 // decoder.hpp -- the decoder object of the C ABI and what its translation units share: capi.cpp (the object, single images, uniform
-// batches, rectangles), entropy_device.cpp, reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp and encode_device.cpp.
+// batches), rect_service.cpp (rectangles), entropy_device.cpp, reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp and
+// encode_device.cpp.
 // Private to libmijpeg.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,7 +30,7 @@ struct mijpeg_decoder {
   size_t coef_host_cap = 0; // int16 units
   int16_t *coef_dev = nullptr;
   size_t coef_dev_cap = 0;
-  // reconstruction cache for the rectangle service
+  // reconstruction cache for the rectangle service (rect_service.cpp)
   uint8_t *img_dev = nullptr;
   size_t img_dev_cap = 0;
   uint8_t *img_host = nullptr; // pinned
@@ -188,6 +189,8 @@ inline void quiesce(mijpeg_decoder *d)
 
 // Device buffers that grow through the buffer cache (capi.cpp): what this object has enqueued finishes before the old buffer goes
 int ensure_dev(mijpeg_decoder *d, void **ptr, size_t *cap, size_t bytes);
+// ... and the same for either kind the cache keeps: device memory, or (pinned) host memory -- the coefficient store, the frame
+int ensure_cached(mijpeg_decoder *d, bool pinned, void **ptr, size_t *cap, size_t bytes);
 
 // capi.cpp: the coefficient store for `count` int16 (device mirror; pinned host planes where need_host); a batch that was submitted
 // and not waited for is settled before its staging buffers are rewritten; a speculative launch is validated

@@ -1,8 +1,9 @@
 // reconstruct.hpp -- what reconstruct_device.cpp (kernel selection, workspace and launch of the reconstruction) shares with the
-// decoder object's entry points in capi.cpp and ragged_decode.cpp.  Private to libmijpeg.so.
+// decoder object's entry points in capi.cpp, rect_service.cpp and ragged_decode.cpp.  Private to libmijpeg.so.
 #pragma once
 #include "decoder.hpp"
 #include "kernels.hpp"
+#include "rect_request.hpp"
 
 // The range gates of the kernel selection (plan_reconstruct): a kernel or flavour is admitted where mijpeg_info::range_max
 // (sum |c| q of a block) is below its gate
@@ -40,14 +41,7 @@ template <class Frame> void fused_geometry(const mijpeg_info &f, mij::Sampling s
   g.tiles_x = (f.width + 127) / 128; g.tiles_y = (f.height + 127) / 128;
 }
 
-// What a rectangle request that does not show the plain picture adds to a launch (request_model.hpp; GenericArgs::rowmap ...)
-struct RequestExtra {
-  const int32_t *rowmap_dev;
-  int32_t rowmap_stride;
-  int32_t corner_x, corner_y, y_base, y_count;
-  int32_t wstart[mij::MAXP], wlimit[mij::MAXP]; // per plane (JPEG XT: legacy planes, then residual planes)
-  int32_t ycc;
-};
+// rx: what a rectangle request that does not show the plain picture adds to a launch (RequestExtra, rect_request.hpp)
 int launch_reconstruct_ex(const mijpeg_batch *b, void *stream, const RequestExtra *rx);
 
 // `frames` frames of `info`, their coefficient stores one behind the other from coef_dev, to out_dev (strides in bytes)
@@ -56,6 +50,9 @@ mijpeg_batch batch_of(const mijpeg_info &info, const int16_t *coef_dev, void *ou
 // The batch on the object's stream: sizes the workspace, grows d->ws_dev, launches, sets the object's error ("... not available
 // for this <noun>"; no noun: the code alone, the caller reports)
 int reconstruct_on(mijpeg_decoder *d, mijpeg_batch &b, const RequestExtra *rx, const char *noun);
+// The decoded frame -- or, without upsampling, component `comp` of it on its own grid (view_of, rect_request.hpp) -- on the
+// object's stream into dst_device; sync: the call waits for it
+int reconstruct_view(mijpeg_decoder *d, int comp, void *dst_device, int64_t row_stride, uint32_t flags, int sync);
 
 // ---- lists of differently shaped frames in fused launches (fused_list.hpp: items, launches, table layout) ----
 struct FusedListItem;

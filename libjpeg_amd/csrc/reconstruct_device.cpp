@@ -502,6 +502,17 @@ int reconstruct_on(mijpeg_decoder *d, mijpeg_batch &b, const RequestExtra *rx, c
   return rc;
 }
 
+int reconstruct_view(mijpeg_decoder *d, int comp, void *dst_device, int64_t row_stride, uint32_t flags, int sync)
+{
+  HIP_TRY(d, hipSetDevice(d->device));
+  const mijpeg_info v = view_of(d->host.info, comp);
+  mijpeg_batch b = batch_of(v, d->coef_dev + (comp < 0 ? 0 : d->host.info.coef_offset[comp]), dst_device, row_stride, row_stride * v.height, 1, flags);
+  b.xt = d->host.is_xt() ? &d->host.xt : nullptr;
+  if (const int rc = reconstruct_on(d, b, nullptr, "stream")) return rc;
+  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  return MIJPEG_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // planar output
 // ------------------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@
 //     a request whose corner is off the 8-pixel grid sees subsampled components displaced in its first row / column of
 //     blocks, with the vertical filter clamped at the end of the upsampler's buffered window instead of the image.
 // This class keeps that state and turns one request into a PLAN: per component and block row the coefficient row to
-// transform (or "zeros"), the displacement and the filter window -- which capi.cpp either recognises as the plain picture
+// transform (or "zeros"), the displacement and the filter window -- which rect_service.cpp either recognises as the plain picture
 // (served from the cached whole-frame reconstruction) or hands to the generic kernels (kernels.hip, GenericArgs::rowmap).
 // Pure host integer logic, no device code.  tests/test_rect_calls.py drives it against the real reference library.
 #ifndef MIJ_REQUEST_MODEL_HPP

@@ -356,10 +356,11 @@ def cli_requests(width: int, height: int, ncomp: int, ctrafo: int = 1):
     return [(0, y0, -1, y1, c, c, 1, ctrafo, 8) for c in range(ncomp) for y0, y1 in stripes]
 
 
-def run_requests(data: bytes, requests, cursors=None, decoded=None):
+def run_requests(data: bytes, requests, cursors=None, decoded=None, bm_width=None):
     """A sequence of JPEG::DisplayRectangle calls through the oracle's stateful restatement (oj_requester): requests =
     [(minx, miny, maxx, maxy, c0, c1, upsample, ctrafo, hmode)] as tests/cxx/rect_calls.cpp reads them ->
-    (info, [return code per call], canvas planes (ncomp, H, W) initialised to 0xAA)."""
+    (info, [return code per call], canvas planes (ncomp, H, W) initialised to 0xAA).  bm_width: the BIO_WIDTH the hook reports
+    (default: the canvas's width, which the canvas keeps either way)."""
     info, planes = decoded if decoded is not None else decode_coefficients(data)
     planes = [np.ascontiguousarray(p, np.int32) for p in planes]
     sb = 2 if info.precision > 8 else 1
@@ -377,7 +378,7 @@ def run_requests(data: bytes, requests, cursors=None, decoded=None):
             bpr = (C.c_int * 4)(W * sb, W * sb, W * sb, W * sb)
             hh = miny + hmode if hmode else H
             bmh = (C.c_int * 4)(hh, hh, hh, hh)
-            bmw = (C.c_int * 4)(W, W, W, W)
+            bmw = (C.c_int * 4)(*([W if bm_width is None else bm_width] * 4))
             rcs.append(lib().oj_requester_display(rq, minx, miny, maxx, maxy, c0, c1, ups, ctrafo, dst, bpp, bpr, bmw, bmh, sb))
             if cursors is not None:  # the row each component's cursor stands at after the call
                 cursors.append([lib().oj_requester_cursor(rq, c) for c in range(nc)])
@@ -386,10 +387,11 @@ def run_requests(data: bytes, requests, cursors=None, decoded=None):
     return info, rcs, canvas
 
 
-def run_requests_xt(data: bytes, requests, cursors=None):
+def run_requests_xt(data: bytes, requests, cursors=None, bm_width=None):
     """run_requests on a JPEG XT stream (profile C): the residual image's cursors and upsamplers beside the legacy image's
     (oj_xt_requester_new) -> (info, [return code per call], canvas planes (3, H, W) of uint16 codes -- or uint8 samples when the
-    output conversion has no extra range bits -- initialised to 0xAA.., is_float).  cursors: per call the six cursor rows (legacy, residual)."""
+    output conversion has no extra range bits -- initialised to 0xAA.., is_float).  cursors: per call the six cursor rows (legacy, residual);
+    bm_width as in run_requests."""
     info, rq, is_float, out_max = OjInfo(), C.c_void_p(), C.c_int(0), C.c_int(0)
     rc = lib().oj_xt_requester_new(data, len(data), C.byref(info), C.byref(rq), C.byref(is_float), C.byref(out_max))
     if rc:
@@ -407,7 +409,7 @@ def run_requests_xt(data: bytes, requests, cursors=None):
             bpr = (C.c_int * 4)(W * sb, W * sb, W * sb, W * sb)
             hh = miny + hmode if hmode else H
             bmh = (C.c_int * 4)(hh, hh, hh, hh)
-            bmw = (C.c_int * 4)(W, W, W, W)
+            bmw = (C.c_int * 4)(*([W if bm_width is None else bm_width] * 4))
             rcs.append(lib().oj_requester_display(rq, minx, miny, maxx, maxy, c0, c1, ups, ctrafo, dst, bpp, bpr, bmw, bmh, sb))
             if cursors is not None:
                 cursors.append([lib().oj_requester_cursor(rq, c) for c in range(3)] + [lib().oj_requester_cursor(rq, 4 + c) for c in range(3)])

@@ -266,3 +266,111 @@ def _read_cli_output(path, oracle):
         bits, w, h = (int(x) for x in m.groups())
         planes.append(np.fromfile(line, np.uint8 if bits <= 8 else ">u2").reshape(h, w))
     return np.stack(planes, axis=-1)
+
+
+# ------------------------------------------------------------------------------------------------ product, the service's rare branches
+# mijpeg_display_rect into DEVICE bitmaps on requests that are not the plain picture (one scatter per component out of the request's
+# image), and bitmaps that report a width below the request (BitmapCtrl::ExtractBitmap, interface/imagebitmap.cpp:58-129: a block
+# whose corner lies outside the bitmap is not written, one that starts inside is written in full -- the canvases here stay as wide
+# as the frame).
+NARROW = (0, 1, 8, 9, -1)  # reported widths; -1: the frame's less one
+
+
+def pgx_loop(w, h, nc):
+    return [(0, y, -1, min(y + 7, h - 1), c, c, 1, 1, 8) for c in range(nc) for y in range(0, h, 8)]
+
+
+def _grey12():
+    """12-bit grey, 45 x 37: a stripe, a stripe further down (the cursor stands at row 1: not the picture), an unaligned window."""
+    from libjpeg_amd import synth
+    data = synth.to_12bit(craft.craft_stream(np.random.default_rng(3), [(1, 1)], 45, 37))
+    return data, 45, 37, [(0, 0, -1, 7, 0, 0, 1, 1, 8), (0, 16, -1, 31, 0, 0, 1, 1, 0), (3, 5, 40, 36, 0, 0, 1, 1, 0)]
+
+
+def _random420():
+    rng = np.random.default_rng(118)
+    data = craft.craft_stream(rng, [(2, 2), (1, 1), (1, 1)], 70, 50)
+    return data, 70, 50, random_script(rng, 70, 50, 3, fullwidth=False)
+
+
+SERVICE_FRAMES = {
+    "c2_pgx": lambda: (craft.craft_stream(np.random.default_rng(1), [(1, 1), (2, 1)], 50, 40), 50, 40, pgx_loop(50, 40, 2)),
+    "c4_pgx": lambda: (craft.craft_stream(np.random.default_rng(2), [(2, 2), (1, 1), (1, 2), (2, 2)], 52, 44), 52, 44, pgx_loop(52, 44, 4)),
+    "c3_420_random": _random420,
+    "grey12": _grey12,
+}
+_expected = {}
+
+
+def service_case(oracle, name, bm_width=None):
+    """(stream, w, h, requests, the oracle's canvas for that reported width): computed once, shared, never written to."""
+    data, w, h, req = SERVICE_FRAMES[name]()
+    bm_width = w - 1 if bm_width == -1 else bm_width
+    if (name, bm_width) not in _expected:
+        _, rcs, exp = oracle.run_requests(data, req, bm_width=bm_width)
+        assert not any(rcs)
+        exp.setflags(write=False)
+        _expected[name, bm_width] = exp
+    return data, w, h, req, bm_width, _expected[name, bm_width]
+
+
+def routes_taken(data, w, h, req, xt=False):
+    """mijpeg_display_plan on a host-only decoder: the `plain` verdicts of the requests that show something."""
+    d = api.Decoder(None)
+    d.read_header(data)
+    seen = set()
+    for (x0, y0, x1, y1, c0, c1, ups, ct, hm) in req:
+        flags = 0 if xt else (0 if ct else api.FLAG_NO_COLOR_TRANSFORM) | (0 if ups else api.FLAG_NO_UPSAMPLING)
+        plan = d.display_plan(x0, y0, w - 1 if x1 < 0 else x1, h - 1 if y1 < 0 else y1, c0, c1, flags, (y0 + hm) if hm else h)
+        if not plan["nothing"]:
+            seen.add(plan["plain"])
+    d.close()
+    return seen
+
+
+def display_sequence(dec, w, h, req, like, device, bm_width=None, xt=False):
+    """The requests through mijpeg_display_rect into a canvas shaped like `like` and filled with 0xAA: host memory, or a torch
+    tensor on the decoder's device -> the canvas."""
+    canvas = np.full(like.shape, 0xAAAA if like.dtype == np.uint16 else 0xAA, like.dtype)
+    ptrs = dev = None
+    if device:
+        import torch
+        dev = torch.from_numpy(canvas.view(np.int16) if canvas.dtype == np.uint16 else canvas).cuda()
+        ptrs = [dev[c].data_ptr() for c in range(canvas.shape[0])]
+    for (x0, y0, x1, y1, c0, c1, ups, ct, hm) in req:
+        flags = 0 if xt else (0 if ct else api.FLAG_NO_COLOR_TRANSFORM) | (0 if ups else api.FLAG_NO_UPSAMPLING)
+        dec.display_rect(canvas, x0, y0, w - 1 if x1 < 0 else x1, h - 1 if y1 < 0 else y1, c0, c1, flags, bm_height=(y0 + hm) if hm else h,
+                         bm_width=bm_width, device_ptrs=ptrs)
+    return canvas if dev is None else dev.cpu().numpy().view(like.dtype)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(SERVICE_FRAMES))
+def test_gpu_display_rect_into_device_bitmaps(oracle, name):
+    """The same sequence twice on fresh decodes, into host bitmaps and into device bitmaps: both the oracle's canvas.  The
+    sequence takes both routes (the cached plain picture, the generic kernels on the request's lines)."""
+    data, w, h, req, _, exp = service_case(oracle, name)
+    assert routes_taken(data, w, h, req) == {0, 1}
+    dec = api.Decoder(0)
+    for device in (False, True):
+        dec.read(data, entropy="host")
+        got = display_sequence(dec, w, h, req, exp, device)
+        assert np.array_equal(got, exp), (name, device)
+    dec.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(SERVICE_FRAMES))
+def test_gpu_display_rect_into_narrow_bitmaps(oracle, name):
+    """Bitmaps that report fewer columns than the request asks for, host and device: the oracle's canvas for that width."""
+    data, w, h, req, _, full = service_case(oracle, name)
+    assert routes_taken(data, w, h, req) == {0, 1}
+    assert not np.array_equal(service_case(oracle, name, 9)[5], full)  # (the width matters: the test is not vacuous)
+    dec = api.Decoder(0)
+    for narrow in NARROW:
+        _, _, _, _, bm_width, exp = service_case(oracle, name, narrow)
+        for device in (False, True):
+            dec.read(data, entropy="host")
+            got = display_sequence(dec, w, h, req, exp, device, bm_width=bm_width)
+            assert np.array_equal(got, exp), (name, bm_width, device)
+    dec.close()

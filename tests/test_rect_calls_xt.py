@@ -182,3 +182,29 @@ def test_gpu_c_abi_random_sequences(oracle):
         n += 1
     dec.close()
     assert n >= 100 and refused >= 3
+
+
+XT_SERVICE = "x420__window_then_rest"  # the smallest golden sequence with a request that is not the plain picture (and one that is)
+
+
+@pytest.mark.gpu
+def test_gpu_display_rect_device_and_narrow_bitmaps(oracle):
+    """mijpeg_display_rect on an XT frame into host and into device bitmaps, at the full width and at reported widths below the
+    request: the oracle's canvas for that width.  The sequence takes both routes (both images through the generic kernels; the
+    cached plain picture)."""
+    from test_rect_calls import NARROW, display_sequence, routes_taken
+    data, req, _ = golden(XT_SERVICE)
+    _, h, w = SEQUENCES[XT_SERVICE]["shape"]
+    assert routes_taken(data, w, h, req, xt=True) == {0, 1}
+    full = oracle.run_requests_xt(data, req)[2]
+    dec = api.Decoder(0)
+    for narrow in (None,) + NARROW:
+        bm_width = w - 1 if narrow == -1 else narrow
+        _, rcs, exp, _ = oracle.run_requests_xt(data, req, bm_width=bm_width)
+        assert not any(rcs)
+        assert bm_width != 9 or not np.array_equal(exp, full)  # (the width matters)
+        for device in (False, True):
+            dec.read(data, entropy="host")
+            got = display_sequence(dec, w, h, req, exp, device, bm_width=bm_width, xt=True)
+            assert np.array_equal(got, exp), (bm_width, device)
+    dec.close()
