@@ -582,6 +582,42 @@ int mijpeg_planar_stats_get(mijpeg_decoder *d, mijpeg_planar_stats *out);
 int mijpeg_deinterleave_device(mijpeg_decoder *d, const void *src_device, int64_t src_row_stride, int32_t width, int32_t height, int32_t components,
                                int32_t sample_bytes, void *const planes[MIJPEG_MAX_COMPONENTS], int64_t row_stride);
 
+/* ---- crop windows of a ragged batch: only their tiles are reconstructed --------------------------------
+ * What a data loader asks of a folder of photographs: a crop of every picture, a different one per picture.  The calls follow
+ * mijpeg_decode_ragged_device / ...16 exactly as mijpeg_reconstruct_ragged_device and its planar twin do -- same object, same
+ * `flags`, same `sync`, same per-image error rule, the coefficient stores valid until the next decode call, so one decode serves any
+ * number of crop calls -- and write, per picture, the rectangle rects[i] of what those calls write, byte for byte (the stateless rule
+ * of mijpeg_reconstruct_rect: every request is answered from the plain picture).
+ * rects[i] is on picture i's canvas, inclusive (JPGTAG_DECODER_MINX .. MAXY).  max_x / max_y beyond the picture are clipped to its
+ * last column / line (INT32_MAX: "to the edge").  MIJPEG_ERR_INVALID_PARAMETER for the call, BEFORE anything is launched or written
+ * (and with the statistics of the last call left alone): NULL arguments, a min_x / min_y below 0 or beyond the picture, min > max
+ * after clipping, a row_strides[i] below one line of the crop, a NULL plane of a component the picture has.
+ * Pixel (min_x, min_y) lands at dst_device[i] (sample c of it at planes[i * MIJPEG_MAX_COMPONENTS + c]), lines row_strides[i] bytes
+ * apart; any base address, any stride; nothing but the crop's own bytes is written -- not the padding of a line, not a byte in
+ * front of or behind the buffer.  dst_device[i] == NULL (planes[i * MIJPEG_MAX_COMPONENTS] == NULL) and pictures in error are skipped.
+ * An 8-bit group picture whose kernel has a ragged flavour (planar: a planar twin; grey is its own plane) is written by the WINDOW
+ * flavour of that kernel: the launch holds only the 128 x 128 tiles the window touches and stores only the window's pixels.  Every
+ * other picture -- 12-bit groups, group pictures reconstructed by a launch of their own, the single-image route (progressive, JPEG
+ * XT, CMYK, 4:4:0, 4:1:1, DNL, ...), a crop whose offsets do not fit 32 bits -- is reconstructed in full into a buffer of the object
+ * and its rectangle copied out on the object's stream (`copied`): the caller gets all n crops whatever the stream is. */
+typedef struct mijpeg_rect { int32_t min_x, min_y, max_x, max_y; } mijpeg_rect;   /* inclusive, as JPGTAG_DECODER_MINX..MAXY */
+int mijpeg_reconstruct_ragged_rect_device(mijpeg_decoder *d, const mijpeg_rect *rects, void *const *dst_device, const int64_t *row_strides,
+                                          uint32_t flags, int sync);
+int mijpeg_reconstruct_ragged_rect_planar_device(mijpeg_decoder *d, const mijpeg_rect *rects, void *const *planes, const int64_t *row_strides,
+                                                 uint32_t flags, int sync);
+/* What the object's last crop call did. */
+typedef struct mijpeg_ragged_rect_stats {
+  int32_t images, fused, copied;        /* pictures written; by a window launch; by full reconstruction + rectangle copy */
+  int32_t launches;                     /* window launches of the fused kernels                                         */
+  int64_t workgroups, workgroups_full;  /* tiles those launches ran; tiles the same pictures have in all                 */
+} mijpeg_ragged_rect_stats;
+int mijpeg_ragged_rect_stats_get(mijpeg_decoder *d, mijpeg_ragged_rect_stats *out);
+/* The planner on its own, no device: per picture the clipped window in tiles of 128 x 128 -- first tile column and row, tiles per
+ * window row, window rows; picture i runs tiles_x[i] * tiles_y[i] workgroups.  Only width and height of infos[i] are read.
+ * MIJPEG_ERR_INVALID_PARAMETER for NULL lists, n < 1 or a rectangle the calls above refuse (nothing is then defined). */
+int mijpeg_ragged_rect_plan(const mijpeg_info *infos, const mijpeg_rect *rects, int n, int32_t *tile_x0, int32_t *tile_y0, int32_t *tiles_x,
+                            int32_t *tiles_y);
+
 /* ---- stateless device entry points (inputs and outputs resident in HBM) -------------------- */
 
 /* Describes a batch of equally shaped frames whose coefficient planes are already on the device. */

@@ -84,6 +84,15 @@ class MijpegPlanarStats(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("images", "fused", "two_pass", "fused_launches", "two_pass_launches")]
 
 
+class MijpegRect(C.Structure):
+    """mijpeg_rect: a crop window on a picture's canvas, inclusive."""
+    _fields_ = [(k, C.c_int32) for k in ("min_x", "min_y", "max_x", "max_y")]
+
+
+class MijpegRaggedRectStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("images", "fused", "copied", "launches")] + [("workgroups", C.c_int64), ("workgroups_full", C.c_int64)]
+
+
 class MijpegRaggedFrame(C.Structure):
     _fields_ = [("coef_base", C.c_int64), ("off_y", C.c_int64), ("off_cb", C.c_int64), ("off_cr", C.c_int64)] + \
                [(k, C.c_int32) for k in ("first_workgroup", "tiles_x", "tiles_y", "width", "height", "bw_y", "bh_y", "bw_c", "bh_c", "cw", "ch", "reserved")]
@@ -188,6 +197,10 @@ def lib():
         L.mijpeg_reconstruct_batch_planar_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_int]
         L.mijpeg_reconstruct_ragged_planar_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int]
         L.mijpeg_planar_stats_get.argtypes = [C.c_void_p, P(MijpegPlanarStats)]
+        L.mijpeg_reconstruct_ragged_rect_device.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_uint32, C.c_int]
+        L.mijpeg_reconstruct_ragged_rect_planar_device.argtypes = L.mijpeg_reconstruct_ragged_rect_device.argtypes
+        L.mijpeg_ragged_rect_stats_get.argtypes = [C.c_void_p, P(MijpegRaggedRectStats)]
+        L.mijpeg_ragged_rect_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mijpeg_deinterleave_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int64]
         L.mijpeg_ragged_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mijpeg_ragged_plan16.argtypes = L.mijpeg_ragged_plan.argtypes
@@ -757,6 +770,41 @@ class Decoder:
         rows = (C.c_int64 * n)(*row_strides)
         self._check(lib().mijpeg_reconstruct_ragged_planar_device(self._h, dst, rows, flags, 1 if sync else 0))
 
+    # ---- crop windows of a ragged batch (include/mijpeg.h)
+    def reconstruct_ragged_rect_device(self, rects, dst_ptrs, row_strides, flags: int = 0, sync: bool = True, wait_foreign: bool = True):
+        """mijpeg_reconstruct_ragged_rect_device: pixel (min_x, min_y) of image i -> dst_ptrs[i] (0 / None: skipped), row_strides[i] bytes
+        per line of the crop.  rects[i]: (min_x, min_y, max_x, max_y), inclusive; max beyond the picture is clipped (RECT_TO_EDGE)."""
+        n = len(dst_ptrs)
+        if n != getattr(self, "ragged_images", -1) or len(row_strides) != n or len(rects) != n:
+            raise ValueError(f"{len(rects)} crops, {n} destinations and {len(row_strides)} row strides for the {getattr(self, 'ragged_images', 0)} images of the ragged batch")
+        if wait_foreign:
+            _foreign_work_done()
+        dst = (C.c_void_p * n)(*[p or None for p in dst_ptrs])
+        rows = (C.c_int64 * n)(*row_strides)
+        self._check(lib().mijpeg_reconstruct_ragged_rect_device(self._h, rect_array(rects), dst, rows, flags, 1 if sync else 0))
+
+    def reconstruct_ragged_rect_planar_device(self, rects, plane_ptrs, row_strides, flags: int = 0, sync: bool = True, wait_foreign: bool = True):
+        """mijpeg_reconstruct_ragged_rect_planar_device: sample (min_x, min_y) of component c of image i -> plane_ptrs[i][c] (None /
+        empty: the image is skipped), row_strides[i] bytes per line of every plane of the crop."""
+        n = len(plane_ptrs)
+        if n != getattr(self, "ragged_images", -1) or len(row_strides) != n or len(rects) != n:
+            raise ValueError(f"{len(rects)} crops, {n} destinations and {len(row_strides)} row strides for the {getattr(self, 'ragged_images', 0)} images of the ragged batch")
+        if wait_foreign:
+            _foreign_work_done()
+        flat = []
+        for p in plane_ptrs:
+            p = list(p or [])
+            flat += [q or None for q in p] + [None] * (4 - len(p))
+        dst = (C.c_void_p * (4 * n))(*flat)
+        rows = (C.c_int64 * n)(*row_strides)
+        self._check(lib().mijpeg_reconstruct_ragged_rect_planar_device(self._h, rect_array(rects), dst, rows, flags, 1 if sync else 0))
+
+    def ragged_rect_stats(self) -> dict:
+        """What the object's last crop call did (mijpeg_ragged_rect_stats)."""
+        st = MijpegRaggedRectStats()
+        self._check(lib().mijpeg_ragged_rect_stats_get(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MijpegRaggedRectStats._fields_}
+
     def deinterleave_device(self, src_ptr: int, src_row_stride: int, width: int, height: int, components: int, sample_bytes: int, plane_ptrs,
                             row_stride: int):
         """mijpeg_deinterleave_device: an interleaved picture in device memory -> its planes, on the object's stream (no wait)."""
@@ -968,6 +1016,43 @@ def encode_coefficients(info: MijpegInfo, coef: np.ndarray, restart_interval: in
         return C.string_at(p, n.value)
     finally:
         L.mijpeg_free(p)
+
+
+RECT_TO_EDGE = 2**31 - 1  # max_x / max_y of a crop: "to the picture's edge"
+
+
+def rect_array(rects):
+    """(min_x, min_y, max_x, max_y) tuples or MijpegRect -> the array the crop calls take (an array made here passes through: a caller
+    that repeats a call converts once -- the conversion of 256 rectangles costs about as much host time as the launch they describe,
+    profiles/ragged_rect.txt)."""
+    if isinstance(rects, C.Array):
+        return rects
+    import array
+    import itertools
+
+    try:
+        flat = array.array("i", itertools.chain.from_iterable((r.min_x, r.min_y, r.max_x, r.max_y) if isinstance(r, MijpegRect) else r for r in rects))
+    except (OverflowError, TypeError) as e:
+        raise ValueError(f"crop rectangles are four 32-bit integers each: {e}") from None
+    if flat.itemsize != 4 or len(flat) != 4 * len(rects):
+        raise ValueError("crop rectangles are (min_x, min_y, max_x, max_y)")
+    if not rects:
+        flat = array.array("i", [0] * 4)
+    return (MijpegRect * (len(flat) // 4)).from_buffer(flat)
+
+
+def ragged_rect_plan(infos, rects):
+    """mijpeg_ragged_rect_plan (no device needed): per picture the clipped window in 128 x 128 tiles -> lists tile_x0, tile_y0, tiles_x,
+    tiles_y; picture i runs tiles_x[i] * tiles_y[i] workgroups.  Raises MijpegError for a rectangle the crop calls refuse."""
+    n = len(infos)
+    arr = (MijpegInfo * max(n, 1))()
+    for i, f in enumerate(infos):
+        C.memmove(C.byref(arr[i]), C.byref(f), C.sizeof(MijpegInfo))
+    out = [(C.c_int32 * max(n, 1))() for _ in range(4)]
+    rc = lib().mijpeg_ragged_rect_plan(arr, rect_array(rects), n, *out)
+    if rc:
+        raise MijpegError(rc, "mijpeg_ragged_rect_plan failed")
+    return tuple(list(o)[:n] for o in out)
 
 
 def ragged_plan(infos):

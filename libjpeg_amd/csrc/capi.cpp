@@ -265,6 +265,7 @@ try {
     release_big(d->device, false, d->img_dev, d->img_dev_cap);
     if (d->ws_dev) (void)hipFree(d->ws_dev);
     if (d->planar_tmp_dev) (void)hipFree(d->planar_tmp_dev);
+    if (d->rect_tmp_dev) (void)hipFree(d->rect_tmp_dev);
     if (d->batch_quant_dev) (void)hipFree(d->batch_quant_dev);
     if (d->ent_dev) (void)hipFree(d->ent_dev);
     if (d->ent_host) (void)hipHostFree(d->ent_host);

@@ -144,6 +144,11 @@ struct mijpeg_decoder {
   uint8_t *planar_tmp_dev = nullptr;
   size_t planar_tmp_cap = 0;
   mijpeg_planar_stats planar_stats{};
+  // crop calls (mijpeg_reconstruct_ragged_rect_device and its planar twin, ragged_decode.cpp): the full picture of the copy route
+  // (a child's own: its reconstruction runs on the child's stream); what the last call did
+  uint8_t *rect_tmp_dev = nullptr;
+  size_t rect_tmp_cap = 0;
+  mijpeg_ragged_rect_stats rect_stats{};
   // ragged encode (encode_device.cpp): descriptors, coder arrays and coefficient store of a pass; plain stream and output arena;
   // pinned: descriptors on their way up and counts read back; the downloaded arena
   uint8_t *eragged_dev = nullptr, *eragged_out_dev = nullptr, *eragged_host = nullptr, *eragged_down = nullptr;

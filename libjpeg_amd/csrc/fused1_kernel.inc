@@ -1,15 +1,20 @@
-// fused1_kernel.inc -- the text of fused1_kernel, included by kernels.hip (see there: once in mij, once in mij::ragged12)
+// fused1_kernel.inc -- the text of fused1_kernel, included by kernels.hip (see there: once in mij, once in mij::ragged12, once in
+// mij::window, where WINDOW_OUT is true: the crop windows of a list)
 template <bool QDEV, int P = 8, bool RAGGED = false>
 __global__ __launch_bounds__(F420_THREADS, 4) void fused1_kernel(Fused420Args a)
 {
   static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
+  static_assert(!WINDOW_OUT || (RAGGED && P == 8), "crop windows: the 8-bit ragged flavour");
+  PlanarBases pb{}; // (a single component is its own plane)
+  WindowBox wb{};
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
-  const TileCtx t = RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<1>(a, stage_all);
+  const TileCtx t = WINDOW_OUT ? tile_enter_window<false>(a, stage_all, pb, wb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<1>(a, stage_all);
   if (t.padding) return;
 
   u32x4 rows[8];
   fetch_tile_blocks(rows, t, t.coef + a.off_y, a.bw_y, a.bh_y);
-  const BlockOut o = block_out<P == 12 ? 2 : 1>(a, t);
+  WindowClip wc{};
+  const BlockOut o = WINDOW_OUT ? block_out_window<P == 12 ? 2 : 1>(a, t, wb, wc) : block_out<P == 12 ? 2 : 1>(a, t);
   if (o.outside) return;
   int v[64];
   dequant_idct_sparse<!QDEV && P == 8>(rows, frame_deltas<QDEV>(a, t.frame, 0), v);
@@ -44,7 +49,7 @@ __global__ __launch_bounds__(F420_THREADS, 4) void fused1_kernel(Fused420Args a)
   }
 #pragma unroll
   for (int l = 0; l < 8; l++) {
-    if (l < nln) {
+    if (WINDOW_OUT ? l >= wc.ln0 && l < nln : l < nln) {
       unsigned b4[2]; // four clamped samples each: level shift, COLOR_TO_INT's rounding, shift, clamp
 #pragma unroll
       for (int h = 0; h < 2; h++)
@@ -55,7 +60,7 @@ __global__ __launch_bounds__(F420_THREADS, 4) void fused1_kernel(Fused420Args a)
       } else {
 #pragma unroll
         for (int x = 0; x < 8; x++)
-          if (x < npx) dst[x] = (uint8_t)(b4[x >> 2] >> (8 * (x & 3)));
+          if (WINDOW_OUT ? x >= wc.px0 && x < npx : x < npx) dst[x] = (uint8_t)(b4[x >> 2] >> (8 * (x & 3)));
       }
     }
   }

@@ -1,16 +1,19 @@
 // fused420_kernel.inc -- the text of fused420_kernel, included by kernels.hip (see there: once in mij, once in mij::ragged12, once
-// in mij::planar, where PLANAR_OUT is true: component planes out)
+// in mij::planar, where PLANAR_OUT is true: component planes out; in mij::window and mij::window::planar, where WINDOW_OUT is true:
+// the crop windows of a list)
 template <bool FAST, int MINW, bool QDEV, int P = 8, bool N12 = false, bool RAGGED = false>
 __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Args a)
 {
   static_assert(P == 8 || (P == 12 && FAST), "12-bit frames: FAST flavour only (the host checks the ranges)");
   static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   static_assert(!PLANAR_OUT || (RAGGED && P == 8), "planar output: the 8-bit ragged flavours");
+  static_assert(!WINDOW_OUT || (RAGGED && P == 8), "crop windows: the 8-bit ragged flavours");
   __shared__ __attribute__((aligned(16))) int cplane[2][F420_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
   PlanarBases pb{};
-  const TileCtx t = PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<P == 8 ? MIJ_TILE_ORDER : 1>(a, stage_all);
+  WindowBox wb{};
+  const TileCtx t = WINDOW_OUT ? tile_enter_window<PLANAR_OUT>(a, stage_all, pb, wb) : PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter<P == 8 ? MIJ_TILE_ORDER : 1>(a, stage_all);
   if (t.padding) return;
 
   // the luma blocks of phase B are requested in front of phase A's transform (see F420P_MINW; two workgroups per CU leave the 32
@@ -27,7 +30,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Ar
   u32x4 rows[8];
   if (!PREFETCH) luma_loads();
   transpose_blocks(rows, t.stage, t.lane, yraw);
-  const BlockOut o = block_out<PLANAR_OUT ? 1 : P == 12 ? 6 : 3>(a, t);
+  WindowClip wc{};
+  const BlockOut o = WINDOW_OUT ? block_out_window<PLANAR_OUT ? 1 : P == 12 ? 6 : 3>(a, t, wb, wc) : block_out<PLANAR_OUT ? 1 : P == 12 ? 6 : 3>(a, t);
   if (o.outside) return; // no barrier below this point
   int yv[64];
   if (FAST) dequant_idct_sparse<!QDEV && P == 8, P == 8>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 0, P == 8 ? LUMA_FOLD_R2 : 2048); // (8 bit: doubled sums, luma13)
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Ar
       int ub[8], ur[8];
       hfilter8(vb, ub);
       hfilter8(vr, ur);
-      if (l < o.nln) {
+      if (WINDOW_OUT ? l >= wc.ln0 && l < o.nln : l < o.nln) {
         if (FAST && P == 12) {
           // (y * 8192 + (cb - 32768) * Lb + (cr - 32768) * Lr + 65536) >> 17, clamped to [0, 4095] (ycbcrtrafo.cpp:842-856,
           // :921-936; the reference accumulates in 64 bits).  With y = y' + 32768, cb - 32768 = cb' (no level shift in the
@@ -84,7 +88,9 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Ar
             gg[x] = mad24(ur[x], -L_CR_G, mad24(ub[x], -L_CB_G, yk));
             bb[x] = mad24(ub[x], L_CB_B, yk);
           }
-          if (PLANAR_OUT) store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
+          if (WINDOW_OUT && PLANAR_OUT) store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx, wc.px0);
+          else if (WINDOW_OUT) store_rgb8_line<STORE24_3X8>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx, wc.px0);
+          else if (PLANAR_OUT) store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
           else store_rgb8_line<STORE24_3X8>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
         } else {
           uint8_t *dst = o.out_frame + o.line_off(l, a);
@@ -95,7 +101,9 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Ar
             ycc_to_rgb<false>(yv[l * 8 + x], ub[x], ur[x], r, g, b);
             px[3 * x] = r; px[3 * x + 1] = g; px[3 * x + 2] = b;
           }
-          if (PLANAR_OUT) {
+          if (WINDOW_OUT && PLANAR_OUT) {
+            store_planar8_bytes(o.out_frame, pb, o.line_off(l, a), px, o.fast_store, o.npx, wc.px0);
+          } else if (PLANAR_OUT) {
             store_planar8_bytes(o.out_frame, pb, o.line_off(l, a), px, o.fast_store, o.npx);
           } else if (o.fast_store) {
             unsigned w[6];
@@ -105,7 +113,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420_kernel(Fused420Ar
           } else {
 #pragma unroll
             for (int x = 0; x < 8; x++)
-              if (x < o.npx) {
+              if (WINDOW_OUT ? x >= wc.px0 && x < o.npx : x < o.npx) {
                 dst[3 * x] = (uint8_t)px[3 * x]; dst[3 * x + 1] = (uint8_t)px[3 * x + 1]; dst[3 * x + 2] = (uint8_t)px[3 * x + 2];
               }
           }

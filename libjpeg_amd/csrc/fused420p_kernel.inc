@@ -1,4 +1,5 @@
-// fused420p_kernel.inc -- the text of fused420p_kernel, included by kernels.hip (see there: once in mij, once in mij::planar)
+// fused420p_kernel.inc -- the text of fused420p_kernel, included by kernels.hip (see there: once in mij, once in mij::planar, and in
+// mij::window and mij::window::planar, where WINDOW_OUT is true: the crop windows of a list)
 // D2: the second pass of every transform on v_dot2 (idct_columns_dot2; admitted by the host where sum |c| q <= 1476 in all three
 // components: plan_reconstruct in capi.cpp)
 template <int MINW, bool QDEV, bool D2 = false, bool RAGGED = false>
@@ -6,11 +7,13 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
 {
   static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   static_assert(!PLANAR_OUT || RAGGED, "planar output: the ragged flavours");
+  static_assert(!WINDOW_OUT || RAGGED, "crop windows: the ragged flavours");
   __shared__ __attribute__((aligned(16))) unsigned cpair[F420_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
   PlanarBases pb{};
-  const TileCtx t = PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
+  WindowBox wb{};
+  const TileCtx t = WINDOW_OUT ? tile_enter_window<PLANAR_OUT>(a, stage_all, pb, wb) : PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
   if (t.padding) return;
   const int tid = t.tid, lane = t.lane, wave = t.wave, frame = t.frame, tx = t.tx, ty = t.ty;
   u32x4 *stage = t.stage;
@@ -167,7 +170,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
   // ------------------------------------------------------------------ phase B: luma, upsampling, colour
   u32x4 rows[8];
   transpose_blocks(rows, stage, lane, yraw);
-  const BlockOut o = block_out<PLANAR_OUT ? 1 : 3>(a, t);
+  WindowClip wc{};
+  const BlockOut o = WINDOW_OUT ? block_out_window<PLANAR_OUT ? 1 : 3>(a, t, wb, wc) : block_out<PLANAR_OUT ? 1 : 3>(a, t);
   if (o.outside) return; // no barrier below this point
   int yv[64];
   dequant_idct_sparse<!QDEV, true, D2>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
@@ -224,7 +228,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
         u[2] = tap13_pk(v[1], v[2], 2);
         u[1] = tap13_pk(u[2], v[1], 1); // src[1] has already been overwritten by out[2]
         u[0] = tap13_pk(v[0], v[1], 2);
-        if (FULL || l < nln) {
+        if (FULL || (WINDOW_OUT ? l >= wc.ln0 && l < nln : l < nln)) {
           int rr[8], gg[8], bb[8];
 #pragma unroll
           for (int x = 0; x < 8; x++) {
@@ -235,7 +239,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
           }
           if (PLANAR_OUT) {
             // (planar: three 8-byte stores per line whatever the planes' alignment -- FULL only drops the per-line masks)
-            store_planar8_line(out_frame, pb, out_off + (unsigned)l * (unsigned)a.row_stride, rr, gg, bb, FULL || fast_store, npx);
+            if (WINDOW_OUT) store_planar8_line(out_frame, pb, out_off + (unsigned)l * (unsigned)a.row_stride, rr, gg, bb, FULL || fast_store, npx, wc.px0);
+            else store_planar8_line(out_frame, pb, out_off + (unsigned)l * (unsigned)a.row_stride, rr, gg, bb, FULL || fast_store, npx);
           } else if (FULL || fast_store) {
             unsigned w[6];
             rgb_shift17_sat_pack(rr, gg, bb, w);
@@ -256,7 +261,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
             else if (SHIFTED) store24_nt<false>(out_frame, off, w);
             else store24_nt(out_frame, off, w);
           } else {
-            store_rgb8_partial(out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride), rr, gg, bb, npx);
+            if (WINDOW_OUT) store_rgb8_partial(out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride), rr, gg, bb, npx, wc.px0);
+            else store_rgb8_partial(out_frame + (out_off + (unsigned)l * (unsigned)a.row_stride), rr, gg, bb, npx);
           }
         }
       }
@@ -265,7 +271,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
       for (int j = 0; j < 6; j++) { cT[j] = cC[j]; cC[j] = cB[j]; }
     }
   };
-  const bool whole = __builtin_amdgcn_ballot_w64(npx != 8 || nln != 8) == 0;
+  // (the window flavours: wholly inside the WINDOW -- the interior of a crop runs the code the interior of a picture runs)
+  const bool whole = WINDOW_OUT ? __builtin_amdgcn_ballot_w64(npx != 8 || nln != 8 || (wc.px0 | wc.ln0) != 0) == 0 : __builtin_amdgcn_ballot_w64(npx != 8 || nln != 8) == 0;
   if (PLANAR_OUT) {
     if (whole) lines(std::true_type{}, std::false_type{}, std::false_type{});
     else lines(std::false_type{}, std::false_type{}, std::false_type{});

@@ -1,4 +1,5 @@
-// fused422_kernel.inc -- the text of fused422_kernel, included by kernels.hip (see there: once in mij, once in mij::planar)
+// fused422_kernel.inc -- the text of fused422_kernel, included by kernels.hip (see there: once in mij, once in mij::planar, and in
+// mij::window and mij::window::planar, where WINDOW_OUT is true: the crop windows of a list)
 // ==============================================================================================
 // fused 4:2:2 kernel (Y 1x1, Cb/Cr subsampled 2x1), packed chroma
 // ==============================================================================================
@@ -15,11 +16,13 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(Fused420Ar
 {
   static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   static_assert(!PLANAR_OUT || RAGGED, "planar output: the ragged flavours");
+  static_assert(!WINDOW_OUT || RAGGED, "crop windows: the ragged flavours");
   __shared__ __attribute__((aligned(16))) unsigned cpair[F422_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
   PlanarBases pb{};
-  const TileCtx t = PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
+  WindowBox wb{};
+  const TileCtx t = WINDOW_OUT ? tile_enter_window<PLANAR_OUT>(a, stage_all, pb, wb) : PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
   if (t.padding) return;
 
   // ------------------------------------------------------------------ phase A: chroma -> LDS halves (Cb low, Cr high), edge fix-up
@@ -30,7 +33,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(Fused420Ar
   // ------------------------------------------------------------------ phase B: luma, upsampling, colour
   u32x4 rows[8];
   fetch_tile_blocks(rows, t, t.coef + a.off_y, a.bw_y, a.bh_y);
-  const BlockOut o = block_out<PLANAR_OUT ? 1 : 3>(a, t);
+  WindowClip wc{};
+  const BlockOut o = WINDOW_OUT ? block_out_window<PLANAR_OUT ? 1 : 3>(a, t, wb, wc) : block_out<PLANAR_OUT ? 1 : 3>(a, t);
   if (o.outside) return; // no barrier below this point
   int yv[64];
   dequant_idct_sparse<!QDEV, true>(rows, frame_deltas<QDEV>(a, t.frame, 0), yv, 0, LUMA_FOLD_R2);
@@ -62,7 +66,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(Fused420Ar
         u[1] = tap13_pk(u[2], v[1], 1); // src[1] has already been overwritten by out[2]
         u[0] = tap13_pk(v[0], v[1], 2);
       }
-      if (l < o.nln) {
+      if (WINDOW_OUT ? l >= wc.ln0 && l < o.nln : l < o.nln) {
         int rr[8], gg[8], bb[8];
 #pragma unroll
         for (int x = 0; x < 8; x++) {
@@ -77,7 +81,9 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused422_kernel(Fused420Ar
             gg[x] = dot2_16(u[x], -L_CB_G, -L_CR_G, yk);
           }
         }
-        if (PLANAR_OUT) store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
+        if (WINDOW_OUT && PLANAR_OUT) store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx, wc.px0);
+        else if (WINDOW_OUT) store_rgb8_line<STORE24_NT>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx, wc.px0);
+        else if (PLANAR_OUT) store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
         else store_rgb8_line<STORE24_NT>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
       }
     }

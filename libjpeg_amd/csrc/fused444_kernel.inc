@@ -1,4 +1,5 @@
-// fused444_kernel.inc -- the text of fused444_kernel, included by kernels.hip (see there: once in mij, once in mij::planar)
+// fused444_kernel.inc -- the text of fused444_kernel, included by kernels.hip (see there: once in mij, once in mij::planar, and in
+// mij::window and mij::window::planar, where WINDOW_OUT is true: the crop windows of a list)
 // ==============================================================================================
 // fused 4:4:4 kernel (three components, no subsampling, YCbCr): ReconstructUnsampled,
 // control/blockbitmaprequester.cpp:1013-1074
@@ -14,9 +15,11 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(Fused420Ar
 {
   static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   static_assert(!PLANAR_OUT || RAGGED, "planar output: the ragged flavours");
+  static_assert(!WINDOW_OUT || RAGGED, "crop windows: the ragged flavours");
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
   PlanarBases pb{};
-  const TileCtx t = PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
+  WindowBox wb{};
+  const TileCtx t = WINDOW_OUT ? tile_enter_window<PLANAR_OUT>(a, stage_all, pb, wb) : PLANAR_OUT ? tile_enter_planar(a, stage_all, pb) : RAGGED ? tile_enter_ragged(a, stage_all) : tile_enter(a, stage_all);
   if (t.padding) return;
   const int frame = t.frame;
 
@@ -38,7 +41,8 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(Fused420Ar
     for (int i = 0; i < 32; i++) crp[i] = pack_lo16_now(v[2 * i + 1], v[2 * i]);
     __builtin_amdgcn_sched_barrier(0);
   }
-  const BlockOut o = block_out<PLANAR_OUT ? 1 : 3>(a, t);
+  WindowClip wc{};
+  const BlockOut o = WINDOW_OUT ? block_out_window<PLANAR_OUT ? 1 : 3>(a, t, wb, wc) : block_out<PLANAR_OUT ? 1 : 3>(a, t);
   int yv[64];
   {
     u32x4 rows[8];
@@ -48,7 +52,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(Fused420Ar
   }
 #pragma unroll
   for (int l = 0; l < 8; l++) {
-    if (l < o.nln) {
+    if (WINDOW_OUT ? l >= wc.ln0 && l < o.nln : l < o.nln) {
       int rr[8], gg[8], bb[8];
 #pragma unroll
       for (int x = 0; x < 8; x++) {
@@ -66,8 +70,11 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused444_kernel(Fused420Ar
       }
       // (LINE_BY_LINE: one line at a time -- do not interleave the lines' temporaries)
       if (PLANAR_OUT) {
-        store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
+        if (WINDOW_OUT) store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx, wc.px0);
+        else store_planar8_line(o.out_frame, pb, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
         if (o.fast_store) __builtin_amdgcn_sched_barrier(0);
+      } else if (WINDOW_OUT) {
+        store_rgb8_line<STORE24_3X8, true>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx, wc.px0);
       } else {
         store_rgb8_line<STORE24_3X8, true>(o.out_frame, o.line_off(l, a), rr, gg, bb, o.fast_store, o.npx);
       }

@@ -837,7 +837,11 @@ __device__ __forceinline__ TileCtx tile_enter(const Fused420Args &a, u32x4 (*sta
 // Tile order: XCD x takes the x-th contiguous eighth of the launch's tiles (order 1 above, over all frames), frame after frame
 // and row by row inside a frame: neighbouring tiles share an L2 whatever tiles_x their frame has, and no frame is padded to
 // eight tile rows -- a picture of one tile is one workgroup.
-__device__ __forceinline__ TileCtx tile_enter_ragged(Fused420Args &f, u32x4 (*stage_all)[128])
+// WINDOW (the window flavours, mij::window further on): `first` is the prefix of the frames' WINDOW tiles and the workgroup's tile is
+// counted from the window's first tile column and row (WindowFrame); the frame's geometry is the picture's as ever.
+struct WindowBox { int min_x, min_y, max_x, max_y; }; // the frame's clipped crop rectangle, inclusive; wave-uniform
+template <bool WINDOW = false>
+__device__ __forceinline__ TileCtx tile_enter_ragged(Fused420Args &f, u32x4 (*stage_all)[128], const WindowFrame *__restrict__ windows = nullptr, WindowBox *wb = nullptr)
 {
   const Fused420Args &a = f;
   TileCtx t;
@@ -854,7 +858,7 @@ __device__ __forceinline__ TileCtx tile_enter_ragged(Fused420Args &f, u32x4 (*st
     else hi = mid;
   }
   const RaggedFrame *__restrict__ fr = a.ragged + lo;
-  const unsigned local = logical - first[lo], tiles_x = (unsigned)fr->tiles_x, row = local / tiles_x;
+  const unsigned local = logical - first[lo], tiles_x = WINDOW ? (unsigned)windows[lo].wtiles_x : (unsigned)fr->tiles_x, row = local / tiles_x;
   f.coef = a.coef + fr->coef_base;
   f.coef_frame_stride = 0;
   f.off_y = fr->off_y; f.off_cb = fr->off_cb; f.off_cr = fr->off_cr;
@@ -870,6 +874,11 @@ __device__ __forceinline__ TileCtx tile_enter_ragged(Fused420Args &f, u32x4 (*st
   t.frame = fr->qframe; // (what the kernels index qdev with; the strides it is multiplied with are zero)
   t.tx = (int)(local - row * tiles_x);
   t.ty = (int)row;
+  if (WINDOW) {
+    const WindowFrame *__restrict__ w = windows + lo;
+    t.tx += w->tile_x0; t.ty += w->tile_y0;
+    wb->min_x = w->min_x; wb->min_y = w->min_y; wb->max_x = w->max_x; wb->max_y = w->max_y;
+  }
   t.coef = f.coef;
   return t;
 }
@@ -925,6 +934,20 @@ __device__ __forceinline__ BlockOut block_out(const Fused420Args &a, const TileC
   o.npx = min(8, a.width - o.X0);
   o.nln = min(8, a.height - o.Y0);
   o.fast_store = o.npx == 8;
+  return o;
+}
+// The window flavours clip the block to the frame's crop window instead (WindowBox: inside the picture, the host clipped it): the
+// block's pixels [px0, npx) of its lines [ln0, nln) are the window's.  outside: the block does not meet the window; fast_store: all
+// eight pixels of a line are inside.  Everything else -- where the block lies, where its first line goes -- is the picture's.
+struct WindowClip { int px0, ln0; };
+template <int BYTES_PER_PIXEL>
+__device__ __forceinline__ BlockOut block_out_window(const Fused420Args &a, const TileCtx &t, const WindowBox &wb, WindowClip &wc)
+{
+  BlockOut o = block_out<BYTES_PER_PIXEL>(a, t);
+  o.npx = min(8, wb.max_x + 1 - o.X0); o.nln = min(8, wb.max_y + 1 - o.Y0);
+  wc.px0 = max(0, wb.min_x - o.X0); wc.ln0 = max(0, wb.min_y - o.Y0);
+  o.outside = o.npx <= wc.px0 || o.nln <= wc.ln0;
+  o.fast_store = o.npx == 8 && wc.px0 == 0;
   return o;
 }
 
@@ -1006,6 +1029,22 @@ __device__ __forceinline__ void store_rgb8_line(uint8_t *base, unsigned off, con
     store_rgb8_partial(base + off, rr, gg, bb, npx);
   }
 }
+// ... and of the window flavours: the partial line is the pixels [px0, npx)
+__device__ __forceinline__ void store_rgb8_partial(uint8_t *dst, const int (&rr)[8], const int (&gg)[8], const int (&bb)[8], int npx, int px0)
+{
+#pragma unroll
+  for (int x = 0; x < 8; x++)
+    if (x >= px0 && x < npx) {
+      dst[3 * x] = (uint8_t)clamp255(rr[x] >> 17); dst[3 * x + 1] = (uint8_t)clamp255(gg[x] >> 17); dst[3 * x + 2] = (uint8_t)clamp255(bb[x] >> 17);
+    }
+}
+template <Store24 STORE, bool LINE_BY_LINE = false>
+__device__ __forceinline__ void store_rgb8_line(uint8_t *base, unsigned off, const int (&rr)[8], const int (&gg)[8], const int (&bb)[8],
+                                                bool fast_store, int npx, int px0)
+{
+  if (fast_store) store_rgb8_line<STORE, LINE_BY_LINE>(base, off, rr, gg, bb, true, 8);
+  else store_rgb8_partial(base + off, rr, gg, bb, npx, px0);
+}
 
 // ----------------------------------------------------------------------------------------------
 // Planar output: the ragged flavours of the 8-bit three-component kernels once more, in mij::planar, with component planes out
@@ -1016,6 +1055,7 @@ __device__ __forceinline__ void store_rgb8_line(uint8_t *base, unsigned off, con
 // bytes per plane: three 8-byte stores at plane + Y * row_stride + X0, no 24-byte pieces, no staging, no shifted copy.  Plane
 // bases and row strides are the caller's: gfx950 stores dwords at any address.
 constexpr bool PLANAR_OUT = false;
+constexpr bool WINDOW_OUT = false; // (mij::window declares its own, true: the crop windows of a list, see there)
 constexpr bool PLANAR_NT = true; // the non-temporal hint on the plane stores
 struct PlanarBases { uint8_t *g, *b; }; // the frame's second and third plane (the first: Fused420Args::out, as ever); wave-uniform
 
@@ -1026,6 +1066,17 @@ __device__ __forceinline__ TileCtx tile_enter_planar(Fused420Args &f, u32x4 (*st
   const PlanarFrame *__restrict__ planes = reinterpret_cast<const PlanarFrame *>(f.out);
   const TileCtx t = tile_enter_ragged(f, stage_all);
   pb.g = planes[t.frame].g; pb.b = planes[t.frame].b;
+  return t;
+}
+// The window flavours' entry: the frame's WindowFrame (and PlanarFrame, PLANAR) entry beside its RaggedFrame.  The tables come in
+// Fused420Args::out: [PlanarFrame x frames, PLANAR][WindowFrame x frames].
+template <bool PLANAR>
+__device__ __forceinline__ TileCtx tile_enter_window(Fused420Args &f, u32x4 (*stage_all)[128], PlanarBases &pb, WindowBox &wb)
+{
+  const PlanarFrame *__restrict__ planes = reinterpret_cast<const PlanarFrame *>(f.out);
+  const WindowFrame *__restrict__ windows = PLANAR ? reinterpret_cast<const WindowFrame *>(planes + f.frames) : reinterpret_cast<const WindowFrame *>(f.out);
+  const TileCtx t = tile_enter_ragged<true>(f, stage_all, windows, &wb);
+  if (PLANAR) { pb.g = planes[t.frame].g; pb.b = planes[t.frame].b; }
   return t;
 }
 
@@ -1066,6 +1117,40 @@ __device__ __forceinline__ void store_planar8_bytes(uint8_t *r, const PlanarBase
 #pragma unroll
       for (int x = 0; x < 8; x++)
         if (x < npx) d[x] = (uint8_t)px[3 * x + c];
+    }
+  }
+}
+// ... and the two of the window flavours: the partial line is the samples [px0, npx) of each plane
+__device__ __forceinline__ void store_planar8_line(uint8_t *r, const PlanarBases &pb, unsigned off, const int (&rr)[8], const int (&gg)[8],
+                                                   const int (&bb)[8], bool fast_store, int npx, int px0)
+{
+  if (fast_store) {
+    store_planar8_line(r, pb, off, rr, gg, bb, true, 8);
+  } else {
+    uint8_t *dr = r + off, *dg = pb.g + off, *db = pb.b + off;
+#pragma unroll
+    for (int x = 0; x < 8; x++)
+      if (x >= px0 && x < npx) { dr[x] = (uint8_t)clamp255(rr[x] >> 17); dg[x] = (uint8_t)clamp255(gg[x] >> 17); db[x] = (uint8_t)clamp255(bb[x] >> 17); }
+  }
+}
+__device__ __forceinline__ void store_planar8_bytes(uint8_t *r, const PlanarBases &pb, unsigned off, const unsigned (&px)[24], bool fast_store, int npx, int px0)
+{
+  // The planes' eight bytes each, packed once; a partial line leaves them in a loop that stays rolled.  (Unrolled like the tails above, the
+  // 24 guarded byte stores per line put the SAFE flavour's line loop beyond what the compiler unrolls, and the luma block went to scratch.)
+  const unsigned lo[3] = {px[0] | (px[3] << 8) | (px[6] << 16) | (px[9] << 24), px[1] | (px[4] << 8) | (px[7] << 16) | (px[10] << 24),
+                          px[2] | (px[5] << 8) | (px[8] << 16) | (px[11] << 24)};
+  const unsigned hi[3] = {px[12] | (px[15] << 8) | (px[18] << 16) | (px[21] << 24), px[13] | (px[16] << 8) | (px[19] << 16) | (px[22] << 24),
+                          px[14] | (px[17] << 8) | (px[20] << 16) | (px[23] << 24)};
+  if (fast_store) {
+    store8_plane(r, off, lo[0], hi[0]);
+    store8_plane(pb.g, off, lo[1], hi[1]);
+    store8_plane(pb.b, off, lo[2], hi[2]);
+  } else {
+    uint8_t *dr = r + off, *dg = pb.g + off, *db = pb.b + off;
+#pragma nounroll
+    for (int x = px0; x < npx; x++) {
+      const unsigned sh = 8u * ((unsigned)x & 3u);
+      dr[x] = (uint8_t)((x < 4 ? lo[0] : hi[0]) >> sh); dg[x] = (uint8_t)((x < 4 ? lo[1] : hi[1]) >> sh); db[x] = (uint8_t)((x < 4 ? lo[2] : hi[2]) >> sh);
     }
   }
 }
@@ -2149,6 +2234,29 @@ __global__ __launch_bounds__(F420_THREADS, 2) void fused444_12_kernel(Fused420Ar
 namespace ragged12 {
 #include "fused1_kernel.inc"
 } // namespace ragged12
+
+// The window flavours (see WINDOW_OUT, WindowFrame in kernels.hpp): the five texts once more for the crop windows of a list, and the
+// four three-component ones a second time with planes out.  A launch holds only the tiles its frames' windows touch (a tile recomputes
+// its own halo: it does not care whether its neighbours run), phase A is what it is everywhere, and phase B clips every block to the
+// window instead of the picture: block_out's [px0, npx) x [ln0, nln).  The destination is addressed from canvas pixel (0, 0) as ever --
+// the host biased the base (fused_list_fill) -- so no offset formula differs, the staged and the shifted stores' included, and the
+// interior of a window takes the copies of the line loop the interior of a picture takes.  In namespaces of their own for planar's
+// reason; fused_list_kernel instantiates the seven ragged ones of mij::window and the six of mij::window::planar.
+namespace window {
+constexpr bool WINDOW_OUT = true;
+#include "fused420_kernel.inc"
+#include "fused420p_kernel.inc"
+#include "fused422_kernel.inc"
+#include "fused444_kernel.inc"
+#include "fused1_kernel.inc"
+namespace planar {
+constexpr bool PLANAR_OUT = true;
+#include "fused420_kernel.inc"
+#include "fused420p_kernel.inc"
+#include "fused422_kernel.inc"
+#include "fused444_kernel.inc"
+} // namespace planar
+} // namespace window
 
 // ==============================================================================================
 // generic path, kernel 1: dequant + IDCT of every block of every component into int32 sample planes
@@ -3433,8 +3541,23 @@ int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t s)
 
 // Frames of different sizes in one launch (Fused420Args::ragged): the ragged flavour of the kernel the plan names, per-frame tables,
 // one workgroup per tile and no padding (tile_enter's ragged branch); planar: the one with component planes out.  Null: there is none.
-static void (*fused_list_kernel(const ReconPlan &p, bool planar))(Fused420Args)
+static void (*fused_list_kernel(const ReconPlan &p, bool planar, bool window = false))(Fused420Args)
 {
+  if (window && !planar) switch (p.kernel) { // the crop windows of the 8-bit ragged flavours, at their occupancy
+  case Recon::FUSED420P: return window::fused420p_kernel<3, true, false, true>;
+  case Recon::FUSED420: return p.fast ? window::fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : window::fused420_kernel<false, 2, true, 8, false, true>;
+  case Recon::FUSED422: return p.wide ? window::fused422_kernel<3, true, true, true> : window::fused422_kernel<3, true, false, true>;
+  case Recon::FUSED444: return window::fused444_kernel<2, true, true>;
+  case Recon::FUSED1: return window::fused1_kernel<true, 8, true>;
+  default: return nullptr; // (no window flavour: 12 bit)
+  }
+  if (window) switch (p.kernel) {
+  case Recon::FUSED420P: return window::planar::fused420p_kernel<3, true, false, true>;
+  case Recon::FUSED420: return p.fast ? window::planar::fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : window::planar::fused420_kernel<false, 2, true, 8, false, true>;
+  case Recon::FUSED422: return p.wide ? window::planar::fused422_kernel<3, true, true, true> : window::planar::fused422_kernel<3, true, false, true>;
+  case Recon::FUSED444: return window::planar::fused444_kernel<2, true, true>;
+  default: return nullptr;
+  }
   if (!planar) switch (p.kernel) {
   case Recon::FUSED420P: return fused420p_kernel<3, true, false, true>;
   case Recon::FUSED420: return p.fast ? fused420_kernel<true, F420_FAST_MINW, true, 8, false, true> : fused420_kernel<false, 2, true, 8, false, true>;
@@ -3460,12 +3583,13 @@ static void (*fused_list_kernel(const ReconPlan &p, bool planar))(Fused420Args)
 
 bool ragged_twin(const ReconPlan &p) { return fused_list_kernel(p, false) != nullptr; }
 bool planar_twin(const ReconPlan &p) { return fused_list_kernel(p, true) != nullptr; }
+bool window_twin(const ReconPlan &p, bool planar) { return fused_list_kernel(p, planar, true) != nullptr; }
 
-int launch_fused_list(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, bool planar, hipStream_t s)
+int launch_fused_list(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, bool planar, hipStream_t s, bool window)
 {
-  if (!a.ragged || !a.ragged_first || !a.qdev || (planar && !a.out) || a.frames < 1) return -1;
+  if (!a.ragged || !a.ragged_first || !a.qdev || ((planar || window) && !a.out) || a.frames < 1) return -1;
   if (workgroups == 0) return 0;
-  void (*kernel)(Fused420Args) = fused_list_kernel(p, planar);
+  void (*kernel)(Fused420Args) = fused_list_kernel(p, planar, window);
   if (!kernel) return -1;
   hipLaunchKernelGGL(kernel, dim3(workgroups), dim3(F420_THREADS), 0, s, a);
   return (int)hipGetLastError();

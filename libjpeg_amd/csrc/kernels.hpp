@@ -70,6 +70,19 @@ struct PlanarFrame {
 };
 static_assert(sizeof(PlanarFrame) == 16, "read in dwords by scalar loads");
 
+// Window launches (launch_fused_list, window): the window flavours of the 8-bit ragged kernels run only the
+// tiles a frame's crop window touches and write only the window's pixels.  RaggedFrame stays what it is here too -- the frame's real
+// geometry: halo and edge replication depend on the picture -- and the window travels in a table of its own, entry i beside
+// RaggedFrame i: workgroup `local` of the frame is tile (tile_x0 + local % wtiles_x, tile_y0 + local / wtiles_x).  `out` (and the
+// planes of PlanarFrame) are BIASED: the address canvas pixel (0, 0) would have if pixel (min_x, min_y) lies at the caller's pointer,
+// so that every offset the kernels form from picture coordinates stays what it is; only offsets of pixels inside the window are
+// dereferenced.  A window launch passes the table in Fused420Args::out; a planar one the PlanarFrame table there and this one behind it.
+struct WindowFrame {
+  int32_t tile_x0, tile_y0, wtiles_x, wtiles_y; // the window in tiles of 128 x 128: min >> 7 ... max >> 7
+  int32_t min_x, min_y, max_x, max_y;           // the clipped rectangle, inclusive
+};
+static_assert(sizeof(WindowFrame) == 32, "read in dwords by scalar loads");
+
 // fused JPEG XT profile C (8-bit 4:2:0 legacy frame + 12-bit 4:4:4 residual frame, see fusedxt420_kernel)
 struct FusedXtExtra {
   int64_t off_r[3];           // residual planes (int16 units from the frame's coefficient base)
@@ -175,9 +188,12 @@ int launch_fused(const ReconPlan &p, const FusedXtArgs &x, hipStream_t stream);
 // per-frame tables in a.qdev: a.ragged / a.ragged_first / a.frames describe them, `workgroups` is ragged_first[frames].
 // planar: the same launch with component planes out -- FUSED420P, FUSED420 (fast or safe), FUSED422 (wide or not) and FUSED444,
 // 8 bit; a.out = the launch's PlanarFrame table (device).  -1: the plan has no such kernel (ragged_twin, planar_twin say so beforehand).
+// window: the same launch over crop windows (WindowFrame) -- the 8-bit kernels among those above, planar or not; a.out = the launch's
+// WindowFrame table (device), behind its PlanarFrame table in a planar launch; `workgroups` counts the windows' tiles.
 bool ragged_twin(const ReconPlan &p);
 bool planar_twin(const ReconPlan &p);
-int launch_fused_list(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, bool planar, hipStream_t stream);
+bool window_twin(const ReconPlan &p, bool planar);
+int launch_fused_list(const ReconPlan &p, const Fused420Args &a, unsigned workgroups, bool planar, hipStream_t stream, bool window = false);
 // Interleaved pixels (ncomp x sample_bytes per pixel) -> ncomp planes: the second pass of every planar request without a twin
 struct DeinterleaveArgs {
   const uint8_t *src;

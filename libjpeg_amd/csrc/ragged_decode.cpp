@@ -405,3 +405,166 @@ try {
 } catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_planar_device"); }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// crop windows (include/mijpeg.h)
+// ------------------------------------------------------------------------------------------------
+// The rectangle w of the full picture at `full` (interleaved, tightly packed lines) to the caller's memory on the object's stream:
+// a strided device copy, or -- planar -- deinterleave_kernel with an offset source
+static int copy_rect_out(mijpeg_decoder *d, const uint8_t *full, const mijpeg_info &f, const mijpeg_rect &w, void *const *ptrs, int64_t row_stride, bool planar)
+{
+  const int sb = sample_bytes_of(f);
+  const int64_t bpp = (int64_t)f.components * sb, line = (int64_t)f.width * bpp;
+  const int32_t cw = w.max_x - w.min_x + 1, ch = w.max_y - w.min_y + 1;
+  const uint8_t *src = full + (int64_t)w.min_y * line + (int64_t)w.min_x * bpp;
+  if (!planar) {
+    HIP_TRY(d, hipMemcpy2DAsync(ptrs[0], (size_t)row_stride, src, (size_t)line, (size_t)(cw * bpp), (size_t)ch, hipMemcpyDeviceToDevice, d->stream));
+    return MIJPEG_OK;
+  }
+  DeinterleaveArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = src;
+  a.src_row = line;
+  a.ncomp = f.components; a.sample_bytes = sb;
+  a.width = cw; a.height = ch;
+  for (int c = 0; c < f.components; c++) a.dst[c] = (uint8_t *)ptrs[c];
+  a.dst_row = row_stride;
+  return launch_deinterleave(a, d->stream) ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
+}
+
+// The two crop calls' body.  planar: ptrs holds MIJPEG_MAX_COMPONENTS entries per picture, else one.
+static int reconstruct_ragged_rect(mijpeg_decoder *d, const mijpeg_rect *rects, void *const *ptrs, const int64_t *row_strides, uint32_t flags, int sync, bool planar)
+{
+  if (!d || !rects || !ptrs || !row_strides) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  if (d->ragged_n < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded ragged batch: call mijpeg_decode_ragged_device first");
+  const int n = d->ragged_n;
+  const size_t per = planar ? MIJPEG_MAX_COMPONENTS : 1;
+  flags &= planar ? PLANAR_FLAGS : ~(uint32_t)(MIJPEG_FLAG_DEVICE_OUTPUT | MIJPEG_FLAG_NO_UPSAMPLING | MIJPEG_FLAG_SPECULATIVE);
+  auto wanted = [&](int i) { return !d->ragged[(size_t)i].status && ptrs[(size_t)i * per] != nullptr; };
+  // every rectangle and every destination, before anything is launched, written or counted
+  std::vector<mijpeg_rect> win((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if (!wanted(i)) continue;
+    const mijpeg_info &f = d->ragged[(size_t)i].info;
+    if (!fused_window_clip(rects[i], f.width, f.height, win[(size_t)i]))
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "crop of image " + std::to_string(i) + ": min_x / min_y lie outside the picture, or min > max");
+    const int64_t crop_line = (int64_t)(win[(size_t)i].max_x - win[(size_t)i].min_x + 1) * sample_bytes_of(f) * (planar ? 1 : f.components);
+    bool ok = f.components >= 1 && f.components <= MIJPEG_MAX_COMPONENTS && row_strides[i] >= crop_line;
+    for (int c = 0; planar && ok && c < f.components; c++) ok = ptrs[(size_t)i * per + (size_t)c] != nullptr;
+    if (!ok)
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "crop destination of image " + std::to_string(i) + ": the row stride is smaller than a line of the crop, or a plane pointer is NULL");
+  }
+  HIP_TRY(d, hipSetDevice(d->device));
+  d->rect_stats = mijpeg_ragged_rect_stats{};
+  // Group pictures whose plan has a window flavour (plan_reconstruct with the crop's stride: fits32 is the kernels' 32-bit offsets
+  // from canvas pixel (0, 0)) share one window launch per kernel and arithmetic flavour, as the full calls' launches do
+  static const uint16_t per_frame_tables = 0; // (the planner only asks whether a batch brings per-frame tables: the list launches do)
+  std::vector<FusedListItem> items;
+  std::vector<FusedListLaunch> launches;
+  std::vector<int> copies; // group pictures of the copy route
+  bool children = false;
+  size_t staging = 0;
+  for (int i = 0; i < n; i++) {
+    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    if (!wanted(i)) continue;
+    if (r.group < 0) { children |= r.child != nullptr; continue; }
+    void *const *p = ptrs + (size_t)i * per;
+    mijpeg_batch b = batch_of(r.info, d->coef_dev + r.coef_base, p[0], row_strides[i], 0, 1, flags);
+    b.quant_dev = &per_frame_tables;
+    const ReconPlan plan = plan_reconstruct(&b);
+    if (!window_twin(plan, planar && r.info.components == 3)) {
+      copies.push_back(i);
+      staging = std::max(staging, (size_t)r.info.height * (size_t)r.info.width * (size_t)r.info.components * (size_t)sample_bytes_of(r.info));
+      continue;
+    }
+    fused_list_add(launches, plan, (int)items.size(), r.info, &win[(size_t)i]);
+    const bool planes = planar && r.info.components == 3;
+    items.push_back(FusedListItem{&r.info, r.coef_base, {p[0], planes ? p[1] : nullptr, planes ? p[2] : nullptr}, row_strides[i], nullptr, &win[(size_t)i]});
+    d->rect_stats.workgroups_full += (int64_t)fused_list_tiles(r.info);
+  }
+  // (a child reconstructs into its own buffer on its own stream, and this object's stream copies from there: the copies an earlier
+  // call without sync left on this stream are done before a child's buffer is written again)
+  if (children) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  const int made = launch_fused_lists(d, items.data(), launches, planar, true);
+  if (made < 0) return made;
+  d->rect_stats.launches = made;
+  d->rect_stats.fused = (int32_t)items.size();
+  for (const FusedListLaunch &l : launches) d->rect_stats.workgroups += (int64_t)l.grid;
+  // The copy route: the picture in full, as the full calls reconstruct it, into a buffer of the object (one after the other: the
+  // stream orders them), and its rectangle to the caller.  One picture that fails does not stop the others (the full calls' rule).
+  if (staging) {
+    const int rc = ensure_dev(d, (void **)&d->rect_tmp_dev, &d->rect_tmp_cap, staging);
+    if (rc) return rc;
+  }
+  int failed = MIJPEG_OK;
+  std::string failed_msg;
+  auto fail = [&](int i, int rc, const char *msg) {
+    if (failed) return;
+    failed = rc;
+    failed_msg = "image " + std::to_string(i) + " of the ragged batch was not reconstructed" + (msg ? std::string(": ") + msg : std::string());
+  };
+  for (int i : copies) {
+    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    const int64_t line = (int64_t)r.info.width * r.info.components * sample_bytes_of(r.info);
+    mijpeg_batch b = batch_of(r.info, d->coef_dev + r.coef_base, d->rect_tmp_dev, line, line * r.info.height, 1, flags);
+    int rc = reconstruct_on(d, b, nullptr, nullptr);
+    if (!rc) rc = copy_rect_out(d, d->rect_tmp_dev, r.info, win[(size_t)i], ptrs + (size_t)i * per, row_strides[i], planar);
+    if (rc) fail(i, rc, nullptr);
+    else d->rect_stats.copied++;
+  }
+  for (int i = 0; i < n; i++) {
+    mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    if (!r.child || !wanted(i)) continue;
+    mijpeg_decoder *c = r.child;
+    const int64_t line = (int64_t)r.info.width * r.info.components * sample_bytes_of(r.info);
+    int rc = ensure_dev(c, (void **)&c->rect_tmp_dev, &c->rect_tmp_cap, (size_t)(line * r.info.height));
+    if (!rc) rc = mijpeg_reconstruct_device(c, c->rect_tmp_dev, line, flags, 1); // (waits: the copy below is on another stream)
+    if (rc) {
+      const char *msg = nullptr;
+      (void)mijpeg_last_error(c, &msg);
+      fail(i, rc, msg ? msg : "");
+      continue;
+    }
+    rc = copy_rect_out(d, c->rect_tmp_dev, r.info, win[(size_t)i], ptrs + (size_t)i * per, row_strides[i], planar);
+    if (rc) fail(i, rc, nullptr);
+    else d->rect_stats.copied++;
+  }
+  d->rect_stats.images = d->rect_stats.fused + d->rect_stats.copied;
+  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  if (failed) return set_error(d, failed, failed_msg);
+  return MIJPEG_OK;
+}
+
+extern "C" {
+
+int mijpeg_reconstruct_ragged_rect_device(mijpeg_decoder *d, const mijpeg_rect *rects, void *const *dst_device, const int64_t *row_strides, uint32_t flags, int sync)
+try {
+  return reconstruct_ragged_rect(d, rects, dst_device, row_strides, flags, sync, false);
+} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_rect_device"); }
+
+int mijpeg_reconstruct_ragged_rect_planar_device(mijpeg_decoder *d, const mijpeg_rect *rects, void *const *planes, const int64_t *row_strides, uint32_t flags, int sync)
+try {
+  return reconstruct_ragged_rect(d, rects, planes, row_strides, flags, sync, true);
+} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_rect_planar_device"); }
+
+int mijpeg_ragged_rect_stats_get(mijpeg_decoder *d, mijpeg_ragged_rect_stats *out)
+try {
+  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
+  *out = d->rect_stats;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_ragged_rect_stats_get"); }
+
+int mijpeg_ragged_rect_plan(const mijpeg_info *infos, const mijpeg_rect *rects, int n, int32_t *tile_x0, int32_t *tile_y0, int32_t *tiles_x, int32_t *tiles_y)
+try {
+  if (!infos || !rects || !tile_x0 || !tile_y0 || !tiles_x || !tiles_y || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
+  for (int i = 0; i < n; i++) {
+    mijpeg_rect w;
+    if (!fused_window_clip(rects[i], infos[i].width, infos[i].height, w)) return MIJPEG_ERR_INVALID_PARAMETER;
+    const WindowFrame t = fused_window_tiles(w);
+    tile_x0[i] = t.tile_x0; tile_y0[i] = t.tile_y0; tiles_x[i] = t.wtiles_x; tiles_y[i] = t.wtiles_y;
+  }
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(nullptr, "mijpeg_ragged_rect_plan"); }
+
+} // extern "C"

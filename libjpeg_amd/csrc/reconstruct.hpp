@@ -59,7 +59,9 @@ struct FusedListItem;
 struct FusedListLaunch;
 // The launches on the object's stream (nothing is waited for): their tables into d->ragged_desc_host once the last call's upload
 // has left it, one upload, one launch_fused_list each.  -> the number of launches made, or the (negative) error, set on the object.
-int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std::vector<FusedListLaunch> &launches, bool planar);
+// window: the launches run the items' crop windows (FusedListItem::window, every item has one); a planar window call's
+// one-component launches are their own plane and take the interleaved window flavour.
+int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std::vector<FusedListLaunch> &launches, bool planar, bool window = false);
 
 // ---- planar output: component planes instead of interleaved pixels ----
 // One picture of a planar call: its frame description and coefficient store (in the object's device memory), where its planes go.

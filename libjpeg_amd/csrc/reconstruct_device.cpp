@@ -524,10 +524,10 @@ int planar_check(const mijpeg_info &f, void *const *planes, int64_t row_stride)
   return row_stride >= (int64_t)f.width * sample_bytes_of(f) ? MIJPEG_OK : MIJPEG_ERR_INVALID_PARAMETER;
 }
 
-int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std::vector<FusedListLaunch> &launches, bool planar)
+int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std::vector<FusedListLaunch> &launches, bool planar, bool window)
 {
   if (launches.empty()) return 0;
-  const std::vector<FusedListTable> tables = fused_list_layout(launches, planar);
+  const std::vector<FusedListTable> tables = fused_list_layout(launches, planar, window);
   const size_t bytes = tables.back().end;
   int rc = ensure_dev(d, (void **)&d->ragged_desc_dev, &d->ragged_desc_cap, bytes);
   if (rc) return rc;
@@ -536,7 +536,7 @@ int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std:
     d->ragged_upload_pending = false;
   }
   if ((rc = ensure_pinned(d, &d->ragged_desc_host, &d->ragged_desc_host_cap, bytes))) return rc;
-  for (size_t l = 0; l < launches.size(); l++) fused_list_fill(d->ragged_desc_host, tables[l], launches[l], items, planar);
+  for (size_t l = 0; l < launches.size(); l++) fused_list_fill(d->ragged_desc_host, tables[l], launches[l], items, planar, window);
   HIP_TRY(d, hipMemcpyAsync(d->ragged_desc_dev, d->ragged_desc_host, bytes, hipMemcpyHostToDevice, d->stream));
   if (!d->ragged_uploaded) HIP_TRY(d, hipEventCreateWithFlags(&d->ragged_uploaded, hipEventDisableTiming));
   HIP_TRY(d, hipEventRecord(d->ragged_uploaded, d->stream));
@@ -549,8 +549,10 @@ int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std:
     a.ragged = (const RaggedFrame *)(d->ragged_desc_dev + tables[l].frames);
     a.ragged_first = (const uint32_t *)(d->ragged_desc_dev + tables[l].first);
     a.qdev = (const int32_t *)(d->ragged_desc_dev + tables[l].deltas);
-    if (planar) a.out = d->ragged_desc_dev + tables[l].planes; // (the PlanarFrame table: kernels.hpp)
-    if (launch_fused_list(launches[l].p, a, (unsigned)launches[l].grid, planar, d->stream))
+    const bool planes = planar && !(window && launches[l].p.sampling == Sampling::GREY); // (a window call's grey launches: their own plane)
+    if (planes) a.out = d->ragged_desc_dev + tables[l].planes; // (the PlanarFrame table: kernels.hpp; a window launch finds its WindowFrame table behind it)
+    else if (window) a.out = d->ragged_desc_dev + tables[l].windows;
+    if (launch_fused_list(launches[l].p, a, (unsigned)launches[l].grid, planes, d->stream, window))
       return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
   }
   return (int)launches.size();
