@@ -811,7 +811,9 @@ int mijpeg_encode_ragged(mijpeg_decoder *d, const mijpeg_encode_frame *frames, i
 typedef struct mijpeg_encode_ragged_stats {
   int32_t pictures;
   int32_t passes;
-  int32_t forward_launches;  /* ragged forward kernels, at most six per pass for each precision present: at most twelve          */
+  int32_t forward_launches;  /* ragged forward kernels, at most six per pass for each flavour of picture present -- 8-bit
+                                interleaved, 12-bit interleaved, 8-bit planar: at most twelve per pass of an interleaved call,
+                                at most eighteen per pass of a planar one (mijpeg_encode_ragged_planar_device16)                 */
   int32_t coder_launches;    /* count, prefix-sum, interval, gather, emit and stuffing kernels, summed (a prefix sum takes one,
                                 three or five launches with the SIZE of its input)                                               */
   int32_t host_syncs;        /* host waits for the device: per pass one for the plain sizes, one for the 0xFF counts, one for the
@@ -837,6 +839,47 @@ int mijpeg_encode_ragged_device16(mijpeg_decoder *d, const mijpeg_encode_frame *
                                   int optimize, uint32_t flags, uint8_t **streams, size_t *sizes);
 int mijpeg_encode_ragged16(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int32_t *precision, int n,
                            int optimize, uint32_t flags, uint8_t **streams, size_t *sizes);
+
+/* ---- planar (CHW) input for the ragged encode ----------------------------------------------------------
+ * mijpeg_encode_ragged_device16 for pictures whose samples lie in component planes, as mijpeg_reconstruct_ragged_planar_device
+ * writes them: planes[i * MIJPEG_MAX_COMPONENTS + c] is the device address of plane c of picture i, c < frames[i].components (a
+ * grey picture has one plane); frames[i].pixels is ignored; frames[i].row_stride is the line pitch in bytes of every plane of
+ * picture i, at least width * sample_bytes; sample (x, y) of component c is at plane[c] + y * row_stride + x * sample_bytes.
+ * Planes may lie anywhere, in any order, in separate allocations.  precision: as above, NULL = 8; a 12-bit picture's planes hold
+ * native-endian uint16_t samples 0..4095 at even addresses with an even pitch.
+ * Stream i is byte for byte what mijpeg_encode_ragged_device16 writes for the interleaved picture with the same samples and the same
+ * description, precision and `optimize`; the call takes what that call takes -- 1 or 3 components, any sampling factors, 8 or 12 bit,
+ * any sizes, any alignment -- and the route only decides the speed:
+ *   fused      8-bit pictures of three components: read by the planar-input flavours of the ragged forward kernels.  Planes and
+ *              pitch on dword boundaries: the tile and interior kernels where the interleaved picture takes them; otherwise the
+ *              per-block kernel alone, byte by byte
+ *   two_pass   12-bit pictures of three components: interleaved into scratch of the object first, ONE launch per picture, in front
+ *              of the forward launches of the picture's pass and on the same stream; then the 12-bit interleaved work lists
+ *   own_plane  one-component pictures of either precision: their plane is the interleaved picture
+ * All arguments are checked for every picture before anything is launched, written or counted (the statistics of the last call
+ * stay): MIJPEG_ERR_INVALID_PARAMETER for NULL lists, n < 1, flags != 0, a description mijpeg_encode_ragged_plan16 refuses, a NULL
+ * plane that a picture needs, a pitch below one line, an odd address or pitch at 12 bit, a precision other than 8 or 12.  An object
+ * without a device: MIJPEG_ERR_NOT_AVAILABLE.  On any failure all streams[i] are NULL and all sizes[i] are 0.
+ * It adds to a pass of the interleaved call the plane table in the pass's one upload, at most six forward launches and the
+ * interleave launches; no host wait.  mijpeg_encode_ragged_get_stats speaks of a planar call as of any other. */
+int mijpeg_encode_ragged_planar_device16(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const void *const *planes,
+                                         const int32_t *precision, int n, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes);
+/* What the object's last planar encode did. */
+typedef struct mijpeg_encode_planar_stats {
+  int32_t pictures;
+  int32_t fused;               /* read by the planar-input forward flavours                                    */
+  int32_t two_pass;            /* interleaved first                                                            */
+  int32_t own_plane;           /* one-component pictures                                                       */
+  int32_t interleave_launches; /* one per two_pass picture                                                     */
+  int32_t reserved;
+} mijpeg_encode_planar_stats;
+int mijpeg_encode_planar_stats_get(mijpeg_decoder *d, mijpeg_encode_planar_stats *out);
+/* The first pass of the two-pass route on its own, the mirror image of mijpeg_deinterleave_device: `components` planes in device
+ * memory (plane_row_stride bytes per line of each) -> an interleaved picture (components x sample_bytes per pixel, dst_row_stride
+ * bytes per line), on the object's stream; sync != 0 waits for it.  components 1..4, sample_bytes 1 or 2; any addresses and
+ * pitches that hold a line.  Nothing but the lines' own bytes is written. */
+int mijpeg_interleave_device(mijpeg_decoder *d, const void *const planes[MIJPEG_MAX_COMPONENTS], int64_t plane_row_stride, int32_t width,
+                             int32_t height, int32_t components, int32_t sample_bytes, void *dst_device, int64_t dst_row_stride, int sync);
 
 /* Worker threads mijpeg_decode_coefficients uses for threads <= 0 (MIJPEG_THREADS overrides; default min(cores, 64)). */
 int mijpeg_default_threads(void);

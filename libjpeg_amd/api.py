@@ -120,6 +120,10 @@ class MijpegEncodeRaggedStats(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("pictures", "passes", "forward_launches", "coder_launches", "host_syncs", "reserved")] + [("bytes_downloaded", C.c_int64)]
 
 
+class MijpegEncodePlanarStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("pictures", "fused", "two_pass", "own_plane", "interleave_launches", "reserved")]
+
+
 # sampling factors (hsamp, vsamp) per component of the layouts the encoder takes by name
 ENCODE_LAYOUTS = {"444": ((1, 1, 1), (1, 1, 1)), "420": ((2, 1, 1), (2, 1, 1)), "422": ((2, 1, 1), (1, 1, 1)), "440": ((1, 1, 1), (2, 1, 1)),
                   "411": ((4, 1, 1), (1, 1, 1))}
@@ -212,6 +216,9 @@ def lib():
         L.mijpeg_encode_ragged_plan16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_encode_ragged_device16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_encode_ragged16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mijpeg_encode_ragged_planar_device16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.mijpeg_encode_planar_stats_get.argtypes = [C.c_void_p, P(MijpegEncodePlanarStats)]
+        L.mijpeg_interleave_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int]
         L.mijpeg_free.argtypes = [C.c_void_p]
         L.mijpeg_free.restype = None
         L.mijpeg_set_device_markers.argtypes = [C.c_void_p, C.c_int]
@@ -472,6 +479,37 @@ class Decoder:
         if precision is None:
             return self._encode_ragged(lib().mijpeg_encode_ragged_device, frames, optimize)
         return self._encode_ragged(lib().mijpeg_encode_ragged_device16, frames, optimize, precision=precision)
+
+    def encode_ragged_planar_device(self, frames, planes, optimize: bool = False, precision=None):
+        """mijpeg_encode_ragged_planar_device16: encode_ragged_device for pictures that lie in HBM as component planes.  planes[i]:
+        the device addresses of picture i's planes (one for grey, three for colour, anywhere); frames[i].row_stride: the line pitch
+        in bytes of every plane of picture i; frames[i].pixels is ignored.  Stream i is what encode_ragged_device writes for the
+        interleaved picture with the same samples."""
+        _foreign_work_done()
+        n = len(frames)
+        if len(planes) != n:
+            raise ValueError(f"{len(planes)} plane lists for {n} pictures")
+        flat = []
+        for p in planes:
+            p = list(p or [])
+            flat += [q or None for q in p[:4]] + [None] * (4 - len(p))
+        table = (C.c_void_p * (4 * max(n, 1)))(*flat)
+        fn = lambda h, arr, prec, *rest: lib().mijpeg_encode_ragged_planar_device16(h, arr, table, prec, *rest)
+        return self._encode_ragged(fn, frames, optimize, precision=precision if precision is not None else [8] * n)
+
+    def encode_planar_stats(self) -> dict:
+        """What the object's last planar encode did (mijpeg_encode_planar_stats)."""
+        st = MijpegEncodePlanarStats()
+        self._check(lib().mijpeg_encode_planar_stats_get(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MijpegEncodePlanarStats._fields_ if k != "reserved"}
+
+    def interleave_device(self, plane_ptrs, plane_row_stride: int, width: int, height: int, components: int, sample_bytes: int, dst_ptr: int,
+                          dst_row_stride: int, sync: bool = True):
+        """mijpeg_interleave_device: planes in device memory -> an interleaved picture, on the object's stream."""
+        ptrs = list(plane_ptrs) + [None] * (4 - len(plane_ptrs))
+        src = (C.c_void_p * 4)(*[p or None for p in ptrs])
+        self._check(lib().mijpeg_interleave_device(self._h, src, plane_row_stride, width, height, components, sample_bytes, dst_ptr, dst_row_stride,
+                                                   1 if sync else 0))
 
     def encode_ragged(self, images, quality=85, subsampling="444", restart_mcus=0, optimize: bool = False):
         """mijpeg_encode_ragged16: (H, W, 3) / (H, W) arrays in host memory -> list of JPEG streams.  uint16 arrays are 12-bit
@@ -1087,6 +1125,14 @@ def _precision_array(precision, n: int):
     if len(values) != n:
         raise ValueError(f"{len(values)} precisions for {n} pictures")
     return (C.c_int32 * max(n, 1))(*values)
+
+
+def interleave_device(decoder: "Decoder", plane_ptrs, plane_row_stride: int, width: int, height: int, components: int, sample_bytes: int, dst_ptr: int,
+                      dst_row_stride: int, sync: bool = True) -> None:
+    """mijpeg_interleave_device on `decoder`'s stream: `components` planes in device memory -> an interleaved picture, the kernel of
+    the planar encode's two-pass route on its own (Decoder.interleave_device)."""
+    _foreign_work_done()
+    decoder.interleave_device(plane_ptrs, plane_row_stride, width, height, components, sample_bytes, dst_ptr, dst_row_stride, sync)
 
 
 def encode_ragged_plan(frames, pass_blocks: int = 0, precision=None):

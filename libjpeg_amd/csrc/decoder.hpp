@@ -154,6 +154,10 @@ struct mijpeg_decoder {
   uint8_t *eragged_dev = nullptr, *eragged_out_dev = nullptr, *eragged_host = nullptr, *eragged_down = nullptr;
   size_t eragged_cap = 0, eragged_out_cap = 0, eragged_host_cap = 0, eragged_down_cap = 0;
   mijpeg_encode_ragged_stats eragged_stats{};
+  // planar input (mijpeg_encode_ragged_planar_device16): what the last call did; the interleaved pictures of its two-pass route
+  // lie in enc_dev
+  mijpeg_encode_planar_stats eplanar_stats{};
+  double eragged_forward_s = 0; // MIJPEG_ENCODE_RAGGED_TIME_FORWARD: device time of the last ragged encode's forward stages (0: not timed)
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t chain_ev = nullptr; // mijpeg_stream_wait

@@ -11,7 +11,9 @@
 // A pass of the ragged encode (EncodePassLayout and the stages of EncodePass):
 //   plan        per picture: frame layout, block and interval counts, its place in the pass's index spaces, its coefficient store
 //   upload      ONE copy of the descriptor tables: a ForwardArgs and a HencArgs per picture, the prefix tables, the work lists
-//   forward     at most six launches per precision present (forward.hip, ragged flavours) whatever the number of pictures
+//   forward     at most six launches per precision present (forward.hip, ragged flavours) whatever the number of pictures; a list
+//               that came as planes (mijpeg_encode_ragged_planar_device16): six more for its 8-bit colour pictures, whose
+//               plane table goes up with the descriptors, and in front of them one interleave launch per 12-bit colour picture
 //   coder       count [statistics first, for the pictures that get tables of their own -- all with `optimize`, the 12-bit ones
 //               always: one read-back of their histograms, the table sets built on the host, one upload], prefix
 //               sums, interval bytes, prefix sums -> read-back of the plain sizes (sync) -> layout of the plain buffer, emit,
@@ -258,6 +260,7 @@ struct EncodePass {
   EncTables std_tabs; // Annex K.3: what the 8-bit pictures code with unless their tables are optimised
   std::vector<EncTables> tabs; // of the pictures with tables of their own
   std::vector<std::vector<uint8_t>> heads;
+  bool timed = false; // MIJPEG_ENCODE_RAGGED_TIME_FORWARD: an event behind the forward launches (encode_passes has one in front)
 
   // arena 1 and its pinned twin; the descriptor tables, one upload
   int descriptors_up()
@@ -276,6 +279,7 @@ struct EncodePass {
   int forward()
   {
     if (launch_forward_ragged(a.forward, stream, &d->eragged_stats.forward_launches)) return hip_fail(d, hipGetLastError(), "ragged forward kernel launch");
+    if (timed) HIP_TRY(d, hipEventRecord(d->ev1, stream));
     return MIJPEG_OK;
   }
 
@@ -350,13 +354,15 @@ struct EncodePass {
   }
 };
 
-// pictures [p0, p1) of the list: one pass.  frames[i].pixels are device addresses.
+// pictures [p0, p1) of the list: one pass.  frames[i].pixels are device addresses; planes: the list's plane table where its pictures
+// came as planes (PlanarList), one entry per picture
 int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijpeg_encode_ragged_item *items, int p0, int p1, int optimize,
-                uint8_t **streams, size_t *sizes)
+                uint8_t **streams, size_t *sizes, const ForwardPlanes *planes = nullptr, bool timed = false)
 {
-  const EncodePassLayout layout(frames, items, p0, p1, optimize);
+  const EncodePassLayout layout(frames, items, p0, p1, optimize, planes);
   if (layout.error) return set_error(d, layout.error, layout.why);
   EncodePass pass{d, layout, streams + p0, sizes + p0};
+  pass.timed = timed;
   int rc = pass.descriptors_up();
   if (!rc) rc = pass.forward();
   if (!rc && layout.n_own) rc = pass.own_tables_up();
@@ -375,25 +381,154 @@ uint32_t pass_blocks_setting()
   return (uint32_t)std::min<unsigned long long>(std::max<unsigned long long>(v, 256), PASS_BLOCKS_MAX);
 }
 
+// A list whose pictures came as component planes (mijpeg_encode_ragged_planar_device16), as the one driver takes it: per picture the
+// frame its pass is laid out with and its entry of the plane table.
+//   own_plane  one component: the plane is the interleaved picture
+//   fused      8 bit, three components: plane 0 and the planes' pitch in the frame, planes 1 and 2 in the table
+//   two_pass   12 bit, three components: the interleaved copy in d->enc_dev, made in front of the picture's pass (interleave_pass)
+struct PlanarList {
+  const void *const *planes; // the caller's, MIJPEG_MAX_COMPONENTS per picture
+  std::vector<mijpeg_encode_frame> frames;
+  std::vector<ForwardPlanes> table;
+
+  PlanarList(const mijpeg_encode_frame *caller, const void *const *planes_, int n)
+      : planes(planes_), frames(caller, caller + n), table((size_t)n, ForwardPlanes{nullptr, nullptr})
+  {
+    for (int i = 0; i < n; i++) frames[(size_t)i].pixels = (const uint8_t *)plane(i, 0);
+  }
+  const void *plane(int i, int c) const { return planes[(size_t)i * MIJPEG_MAX_COMPONENTS + c]; }
+};
+
+// what picture i of a planar list needs: its planes, a pitch that holds a line; 16-bit samples on 2-byte boundaries
+bool planes_in_order(const mijpeg_encode_frame &e, int precision, const void *const *planes)
+{
+  const int sb = precision == 12 ? 2 : 1;
+  if (e.row_stride < (int64_t)e.width * sb) return false;
+  uintptr_t bits = (uintptr_t)e.row_stride;
+  for (int c = 0; c < e.components; c++) {
+    if (!planes[c]) return false;
+    bits |= (uintptr_t)planes[c];
+  }
+  return sb == 1 || (bits & 1) == 0;
+}
+
+// the routes of the pictures [p0, p1) of a planar list; the two-pass pictures interleaved into d->enc_dev, ONE launch per picture, on
+// the stream the pass's forward launches follow on (lines of the copy on dword boundaries: the tile and interior kernels).
+// MIJPEG_ENCODE_PLANAR_TWO_PASS (testing, tools/planar_encode_bench.py): the 8-bit colour pictures take that route as well -- the
+// route their planar kernels replace.
+int interleave_pass(mijpeg_decoder *d, PlanarList &pl, const mijpeg_encode_ragged_item *items, int p0, int p1)
+{
+  const bool all_two_pass = getenv("MIJPEG_ENCODE_PLANAR_TWO_PASS") != nullptr;
+  auto two_pass = [&](const mijpeg_info &f) { return f.components == 3 && (f.precision == 12 || all_two_pass); };
+  auto line_of = [](const mijpeg_info &f) { return ((size_t)f.width * 3 * (f.precision == 12 ? 2 : 1) + 3) & ~(size_t)3; };
+  std::vector<size_t> at((size_t)(p1 - p0), 0);
+  size_t total = 0;
+  for (int i = p0; i < p1; i++) {
+    const mijpeg_info &f = items[(size_t)i].info;
+    if (!two_pass(f)) continue;
+    at[(size_t)(i - p0)] = total;
+    total += (line_of(f) * (size_t)f.height + 255) & ~(size_t)255;
+  }
+  if (total)
+    if (const int rc = ensure_dev(d, (void **)&d->enc_dev, &d->enc_cap, total)) return rc;
+  for (int i = p0; i < p1; i++) {
+    const mijpeg_info &f = items[(size_t)i].info;
+    mijpeg_encode_frame &e = pl.frames[(size_t)i];
+    if (f.components == 1) {
+      d->eplanar_stats.own_plane++;
+    } else if (!two_pass(f)) {
+      pl.table[(size_t)i] = ForwardPlanes{(const uint8_t *)pl.plane(i, 1), (const uint8_t *)pl.plane(i, 2)};
+      d->eplanar_stats.fused++;
+    } else {
+      InterleaveArgs a;
+      memset(&a, 0, sizeof(a));
+      for (int c = 0; c < 3; c++) a.src[c] = (const uint8_t *)pl.plane(i, c);
+      a.src_row = e.row_stride;
+      a.ncomp = 3; a.sample_bytes = f.precision == 12 ? 2 : 1;
+      a.width = f.width; a.height = f.height;
+      a.dst = d->enc_dev + at[(size_t)(i - p0)];
+      a.dst_row = (int64_t)line_of(f);
+      if (launch_interleave(a, d->stream)) return hip_fail(d, hipGetLastError(), "interleave_kernel launch");
+      e.pixels = a.dst;
+      e.row_stride = a.dst_row;
+      d->eplanar_stats.two_pass++;
+      d->eplanar_stats.interleave_launches++;
+    }
+  }
+  return MIJPEG_OK;
+}
+
+// a planned list, pass by pass; pixels in device memory, or -- planar -- planes
+int encode_passes(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijpeg_encode_ragged_item *items, int n, int optimize, uint8_t **streams,
+                  size_t *sizes, PlanarList *planar = nullptr)
+{
+  int rc = MIJPEG_OK;
+  d->eragged_stats.pictures = n;
+  // MIJPEG_ENCODE_RAGGED_TIME_FORWARD (testing, tools/planar_encode_bench.py): the device time from the first thing a pass enqueues
+  // -- the interleave launches of a planar list, the upload of the descriptors -- to the end of its forward launches, between two
+  // events, summed over the passes: mijpeg_last_timing [1].  Unset: no event is recorded.
+  const bool timed = getenv("MIJPEG_ENCODE_RAGGED_TIME_FORWARD") != nullptr;
+  d->eragged_forward_s = 0;
+  for (int p0 = 0; p0 < n && !rc;) {
+    int p1 = p0 + 1;
+    while (p1 < n && items[(size_t)p1].pass == items[(size_t)p0].pass) p1++;
+    if (timed) HIP_TRY(d, hipEventRecord(d->ev0, d->stream));
+    if (planar) rc = interleave_pass(d, *planar, items, p0, p1);
+    if (!rc) rc = encode_pass(d, planar ? planar->frames.data() : frames, items, p0, p1, optimize, streams, sizes, planar ? planar->table.data() : nullptr, timed);
+    if (timed && !rc) { // (the pass has waited for its download: both events are behind us)
+      float ms = 0;
+      HIP_TRY(d, hipEventElapsedTime(&ms, d->ev0, d->ev1));
+      d->eragged_forward_s += ms * 1e-3;
+    }
+    d->eragged_stats.passes++;
+    p0 = p1;
+  }
+  return rc;
+}
+
 // the list, pass by pass; pixels in device memory
 int encode_list(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int32_t *precision, int n, int optimize, uint8_t **streams, size_t *sizes)
 {
   std::vector<mijpeg_encode_ragged_item> items((size_t)n);
   mijpeg_encode_ragged_totals totals;
-  int rc = plan_list(frames, precision, n, pass_blocks_setting(), items.data(), &totals);
+  const int rc = plan_list(frames, precision, n, pass_blocks_setting(), items.data(), &totals);
   if (rc) return set_error(d, rc, "invalid picture description in the list");
   for (int i = 0; i < n; i++)
     if (!pixels_in_order(frames[i], items[(size_t)i].info.precision))
       return set_error(d, MIJPEG_ERR_INVALID_PARAMETER,
                        "picture without pixels, with a row stride below its width, or with 16-bit samples off their 2-byte boundaries");
-  d->eragged_stats.pictures = n;
-  for (int p0 = 0; p0 < n && !rc;) {
-    int p1 = p0 + 1;
-    while (p1 < n && items[(size_t)p1].pass == items[(size_t)p0].pass) p1++;
-    rc = encode_pass(d, frames, items.data(), p0, p1, optimize, streams, sizes);
-    d->eragged_stats.passes++;
-    p0 = p1;
+  return encode_passes(d, frames, items.data(), n, optimize, streams, sizes);
+}
+
+// the planar entry: everything is checked for every picture before anything is launched, written or counted
+int encode_planar_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const void *const *planes, const int32_t *precision, int n, int optimize,
+                        uint32_t flags, uint8_t **streams, size_t *sizes)
+{
+  if (streams && sizes)
+    for (int i = 0; i < n; i++) { streams[i] = nullptr; sizes[i] = 0; }
+  if (!d || !frames || !planes || !streams || !sizes || n < 1 || flags != 0) return MIJPEG_ERR_INVALID_PARAMETER;
+  std::vector<mijpeg_encode_ragged_item> items((size_t)n);
+  mijpeg_encode_ragged_totals totals;
+  if (const int rc = plan_list(frames, precision, n, pass_blocks_setting(), items.data(), &totals)) return set_error(d, rc, "invalid picture description in the list");
+  for (int i = 0; i < n; i++)
+    if (!planes_in_order(frames[i], items[(size_t)i].info.precision, planes + (size_t)i * MIJPEG_MAX_COMPONENTS))
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER,
+                       "picture without one of its planes, with a pitch below its width, or with 16-bit samples off their 2-byte boundaries");
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  HIP_TRY(d, hipSetDevice(d->device));
+  const auto t_begin = std::chrono::steady_clock::now();
+  d->eragged_stats = mijpeg_encode_ragged_stats{};
+  d->eragged_forward_s = 0;
+  d->eplanar_stats = mijpeg_encode_planar_stats{};
+  d->eplanar_stats.pictures = n;
+  PlanarList list(frames, planes, n);
+  const int rc = encode_passes(d, frames, items.data(), n, optimize, streams, sizes, &list);
+  if (rc) {
+    (void)hipStreamSynchronize(d->stream);
+    drop_streams(streams, sizes, n);
   }
+  whole_call_timing(d, t_begin);
+  d->timing[1] = d->eragged_forward_s;
   return rc;
 }
 
@@ -406,6 +541,7 @@ int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int
   HIP_TRY(d, hipSetDevice(d->device));
   const auto t_begin = std::chrono::steady_clock::now();
   d->eragged_stats = mijpeg_encode_ragged_stats{};
+  d->eragged_forward_s = 0;
   int rc = MIJPEG_OK;
   std::vector<mijpeg_encode_frame> on_device;
   if (host_pixels) {
@@ -441,6 +577,7 @@ int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int
     drop_streams(streams, sizes, n);
   }
   whole_call_timing(d, t_begin);
+  d->timing[1] = d->eragged_forward_s;
   return rc;
 }
 
@@ -646,6 +783,45 @@ try {
   drop_streams(streams, sizes, n);
   return boundary_catch(d, "mijpeg_encode_ragged16");
 }
+
+int mijpeg_encode_ragged_planar_device16(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const void *const *planes, const int32_t *precision, int n,
+                                         int optimize, uint32_t flags, uint8_t **streams, size_t *sizes)
+try {
+  return encode_planar_entry(d, frames, planes, precision, n, optimize, flags, streams, sizes);
+} catch (...) {
+  drop_streams(streams, sizes, n);
+  return boundary_catch(d, "mijpeg_encode_ragged_planar_device16");
+}
+
+int mijpeg_encode_planar_stats_get(mijpeg_decoder *d, mijpeg_encode_planar_stats *out)
+try {
+  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
+  *out = d->eplanar_stats;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_encode_planar_stats_get"); }
+
+int mijpeg_interleave_device(mijpeg_decoder *d, const void *const planes[MIJPEG_MAX_COMPONENTS], int64_t plane_row_stride, int32_t width, int32_t height,
+                             int32_t components, int32_t sample_bytes, void *dst_device, int64_t dst_row_stride, int sync)
+try {
+  if (!d || !dst_device || !planes || width < 1 || height < 1 || components < 1 || components > MIJPEG_MAX_COMPONENTS || (sample_bytes != 1 && sample_bytes != 2))
+    return MIJPEG_ERR_INVALID_PARAMETER;
+  for (int c = 0; c < components; c++)
+    if (!planes[c]) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (plane_row_stride < (int64_t)width * sample_bytes || dst_row_stride < (int64_t)width * sample_bytes * components) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  HIP_TRY(d, hipSetDevice(d->device));
+  InterleaveArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int c = 0; c < components; c++) a.src[c] = (const uint8_t *)planes[c];
+  a.src_row = plane_row_stride;
+  a.ncomp = components; a.sample_bytes = sample_bytes;
+  a.width = width; a.height = height;
+  a.dst = (uint8_t *)dst_device;
+  a.dst_row = dst_row_stride;
+  if (launch_interleave(a, d->stream)) return hip_fail(d, hipGetLastError(), "interleave_kernel launch");
+  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_interleave_device"); }
 
 // the 8-bit entry points: the same calls without a precision array
 int mijpeg_encode_ragged_plan(const mijpeg_encode_frame *frames, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,

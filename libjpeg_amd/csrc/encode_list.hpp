@@ -2,7 +2,9 @@
 // tables of its quality), the planner of the ragged encode, the argument blocks of the forward kernels and of the device entropy
 // coder, and a pass of a list as plain data: what is in it (EncodePassLayout: index spaces, work lists, every offset of its three
 // arenas), what the one upload holds (fill_upload), the tables the pictures' own statistics give (own_tables), where the pictures
-// lie in the plain buffer (chunk_layout) and in the downloaded arena (arena_bytes, stream_piece).  encode_device.cpp enqueues, waits
+// lie in the plain buffer (chunk_layout) and in the downloaded arena (arena_bytes, stream_piece).  A list that came as component
+// planes adds a plane table to the pass and a third set of work lists, through defaulted arguments; tests/cxx/
+// encode_list_planar_tables.cpp is their program.  encode_device.cpp enqueues, waits
 // and copies.  Calls nothing of the HIP runtime: a plain host compiler builds tests/cxx/encode_list_tables.cpp around it and
 // encoder.cpp.  Private to libmijpeg.so.
 #pragma once
@@ -178,8 +180,10 @@ inline int plan_list(const mijpeg_encode_frame *frames, const int32_t *precision
 // ------------------------------------------------------------------------------------------------
 // argument blocks
 // ------------------------------------------------------------------------------------------------
-// the forward kernels' argument block for a batch (geometry, routing, quantiser multipliers): MIJPEG_OK or the refusal
-inline int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a)
+// the forward kernels' argument block for a batch (geometry, routing, quantiser multipliers): MIJPEG_OK or the refusal.
+// planes: the picture is planar -- b->pixels_dev is its plane 0, b->pixel_row_stride the pitch of all three, *planes its
+// planes 1 and 2; the fast condition then asks all three plane addresses and the pitch to be multiples of 4
+inline int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a, const ForwardPlanes *planes = nullptr)
 {
   if (!b || !b->pixels_dev || !b->coef_dev || b->frames < 1) return MIJPEG_ERR_INVALID_PARAMETER;
   const mijpeg_info &f = b->info;
@@ -199,7 +203,8 @@ inline int forward_args_of(const mijpeg_forward_batch *b, ForwardArgs &a)
   a.frames = b->frames;
   // (the interior and tile kernels read lines as dwords, 16 bytes at a time at precision 12: with 2-byte samples too the
   // condition is that every line starts on a dword boundary -- a block's first pixel is 24 or 48 bytes into its line)
-  const bool dword_lines = (((uintptr_t)b->pixels_dev | (uintptr_t)b->pixel_frame_stride | (uintptr_t)b->pixel_row_stride) & 3) == 0;
+  const bool dword_lines = (((uintptr_t)b->pixels_dev | (uintptr_t)b->pixel_frame_stride | (uintptr_t)b->pixel_row_stride |
+                             (planes ? (uintptr_t)planes->p1 | (uintptr_t)planes->p2 : 0)) & 3) == 0;
   uint64_t blocks = 0;
   for (int c = 0; c < f.components; c++) {
     if (f.subx[c] < 1 || f.suby[c] < 1 || f.blocks_w[c] < 1 || f.blocks_h[c] < 1) return MIJPEG_ERR_INVALID_PARAMETER;
@@ -347,18 +352,25 @@ struct EncodePassLayout {
   uint32_t n_own = 0;                     // arenas, which hold the pictures that use them; UINT32_MAX: the standard tables
   std::vector<ForwardArgs> fargs;         // per picture (routing: launch_forward's); coef is fill_upload's
   std::vector<HencArgs> hargs;            // per picture, the geometry alone
-  ForwardWorkList lists[FORWARD_RAGGED_LISTS]; // per precision and kernel family
+  ForwardWorkList lists[FORWARD_RAGGED_LISTS]; // per flavour (8 bit, 12 bit, planar 8 bit) and kernel family
+  const ForwardPlanes *planes;            // the pass's first, or null: planes 1 and 2 of the planar pictures (p1 set), nulls for the others
+  uint32_t n_planar = 0;                  // planar pictures of the pass; none: no plane table goes up
   CoderLayout coder;                      // coder_layout(N, I), at `coder_at` of the device arena
   // uploaded in one piece (pinned and device): descriptors, prefix tables (n + 1 entries), work lists, the standard tables
   size_t fargs_at, hargs_at, first_block_at, first_interval_at, wl_first_at[FORWARD_RAGGED_LISTS], wl_item_at[FORWARD_RAGGED_LISTS], std_tables_at, up_bytes;
+  size_t planes_at;                       // the plane table, n entries behind the standard tables (empty without planar pictures)
   // device only, behind them: first_chunk[n + 1], own tables and histograms, the gathered prefix sums, coder arrays, coefficients
   size_t d_first_chunk, d_tables, d_hist, d_gather, coder_at, coef_at, dev_bytes;
   // pinned, behind the upload: what goes up later (first_chunk, own tables) and what comes back (histograms, gathered sums)
   size_t h_first_chunk, h_tables, h_hist, h_istart, h_ffstart, host_bytes;
   size_t hist_bytes;
 
-  EncodePassLayout(const mijpeg_encode_frame *all_frames, const mijpeg_encode_ragged_item *all_items, int p0, int p1, int optimize)
-      : frames(all_frames + p0), items(all_items + p0), n((uint32_t)(p1 - p0)), own_index(n, UINT32_MAX), fargs(n), hargs(n)
+  // all_planes: one entry per picture of the list; a planar picture's frame holds plane 0 in `pixels` and the planes' pitch in
+  // `row_stride`, its entry planes 1 and 2 (only 8-bit pictures of three components are planar here)
+  EncodePassLayout(const mijpeg_encode_frame *all_frames, const mijpeg_encode_ragged_item *all_items, int p0, int p1, int optimize,
+                   const ForwardPlanes *all_planes = nullptr)
+      : frames(all_frames + p0), items(all_items + p0), n((uint32_t)(p1 - p0)), own_index(n, UINT32_MAX), fargs(n), hargs(n),
+        planes(all_planes ? all_planes + p0 : nullptr)
   {
     const mijpeg_encode_ragged_item &last = items[n - 1];
     N = last.first_block + pad256(last.blocks);
@@ -375,6 +387,7 @@ struct EncodePassLayout {
       wl_item_at[l] = up.take(lists[l].item.size() * 4);
     }
     std_tables_at = up.take(sizeof(HencTables));
+    planes_at = up.take(n_planar ? (size_t)n * sizeof(ForwardPlanes) : 0);
     up_bytes = up.at;
     hist_bytes = (size_t)n_own * HENC_HIST_BYTES;
     coder = coder_layout(N, I);
@@ -409,12 +422,14 @@ struct EncodePassLayout {
       b.coef_dev = (int16_t *)16; // (placed by fill_upload, once the store's address is known)
       b.coef_frame_stride = b.info.coef_count;
       b.frames = 1;
-      if (const int rc = forward_args_of(&b, fargs[p])) return refuse(rc, "invalid frame for the forward kernels");
+      if (planar(p) && (b.info.precision != 8 || b.info.components != 3)) return refuse(MIJPEG_ERR_INVALID_PARAMETER, "planar picture without a planar kernel");
+      if (const int rc = forward_args_of(&b, fargs[p], planar(p) ? planes + p : nullptr)) return refuse(rc, "invalid frame for the forward kernels");
+      n_planar += planar(p);
       int which[5], comp[5];
       uint32_t wgs[5];
       const int k = forward_ragged_items(fargs[p], which, wgs, comp);
       for (int j = 0; j < k; j++)
-        if (!work_list_append(lists[forward_ragged_list(which[j], b.info.precision)], p * 4u + (uint32_t)comp[j], wgs[j]))
+        if (!work_list_append(lists[forward_ragged_list(which[j], b.info.precision, planar(p))], p * 4u + (uint32_t)comp[j], wgs[j]))
           return refuse(MIJPEG_ERR_NOT_AVAILABLE, "pass too large for one forward launch");
       memset(&hargs[p], 0, sizeof(HencArgs));
       if (!henc_frame_geometry(hargs[p], items[p].info, e.restart_interval)) return refuse(MIJPEG_ERR_INVALID_PARAMETER, "too many blocks per MCU");
@@ -422,6 +437,7 @@ struct EncodePassLayout {
   }
   void refuse(int code, const char *message) { error = code; why = message; }
   bool own(uint32_t p) const { return own_index[p] != UINT32_MAX; }
+  bool planar(uint32_t p) const { return planes && planes[p].p1; }
 };
 
 // What the kernels of a pass are launched with
@@ -431,7 +447,7 @@ struct EncodePassArgs {
 };
 
 // The uploaded part into `host` (up_bytes of it), with the addresses it will have at `dev`: a ForwardArgs and a HencArgs per
-// picture, first_block and first_interval, the work lists, the standard tables (std_tabs, packed).  Statistics are counted with
+// picture, first_block and first_interval, the work lists, the standard tables (std_tabs, packed), the plane table of a pass with planar pictures.  Statistics are counted with
 // the standard tables' lengths (any would do), the real pass with the picture's own (own_tables).
 inline EncodePassArgs fill_upload(uint8_t *host, uint8_t *dev, const EncodePassLayout &L, const EncTables &std_tabs)
 {
@@ -469,6 +485,10 @@ inline EncodePassArgs fill_upload(uint8_t *host, uint8_t *dev, const EncodePassL
     a.forward.launch[l].item = (const uint32_t *)(dev + L.wl_item_at[l]);
     a.forward.launch[l].items = (uint32_t)w.item.size();
     a.forward.grid[l] = w.first.back();
+  }
+  if (L.n_planar) {
+    memcpy(host + L.planes_at, L.planes, (size_t)L.n * sizeof(ForwardPlanes));
+    a.forward.planes = (const ForwardPlanes *)(dev + L.planes_at);
   }
   a.coder.pics = (const HencArgs *)(dev + L.hargs_at);
   a.coder.first_block = (const uint32_t *)(dev + L.first_block_at);

@@ -26,6 +26,9 @@
 // the type of the chroma samples in LDS.  The transform itself is the same wrapping 32-bit one (Tables::BuildDCT,
 // codestream/tables.cpp:1876-1906, takes LOSSYDCT<COLOR_BITS, LONG> up to precision 12); where 16-bit samples make the
 // reference's LONG wrap, so does this.
+// The ragged 8-bit kernels also have a PLANAR-INPUT flavour (namespace mij::planar_in): a picture's three samples come
+// from three planes, found through a table beside the argument blocks; everything behind the samples is the same text.
+// interleave_kernel makes an interleaved picture of planes for the pictures those flavours do not take.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -160,6 +163,34 @@ __device__ __forceinline__ int line_sample(const unsigned (&d)[ND], int s)
   else return (int)((d[s >> 1] >> (16 * (s & 1))) & 0xffffu);
 }
 
+// Planar input, 8 bit: the same line of W pixels out of three planes, W contiguous bytes of each -- ND / 3 dwords per plane (two:
+// one 8-byte load; four: one 16-byte load), plane after plane in dw.  Lines start dword-aligned, no more is asked (as at 12 bit).
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef u32x2 u32x2_dword_aligned __attribute__((aligned(4)));
+template <int ND>
+__device__ __forceinline__ void load_line_planar(const uint8_t *l0, const uint8_t *l1, const uint8_t *l2, unsigned (&dw)[ND])
+{
+  constexpr int PD = ND / 3; // dwords of a plane's line
+  static_assert(PD == 2 || PD == 4, "8 or 16 pixels of a line");
+  const uint8_t *const l[3] = {l0, l1, l2};
+#pragma unroll
+  for (int ch = 0; ch < 3; ch++) {
+    if constexpr (PD == 2) {
+      const u32x2 v = *reinterpret_cast<const u32x2_dword_aligned *>(l[ch]);
+      dw[ch * PD] = v.x; dw[ch * PD + 1] = v.y;
+    } else {
+      const u32x4 v = *reinterpret_cast<const u32x4_dword_aligned *>(l[ch]);
+      dw[ch * PD] = v.x; dw[ch * PD + 1] = v.y; dw[ch * PD + 2] = v.z; dw[ch * PD + 3] = v.w;
+    }
+  }
+}
+// channel ch of pixel i of such a line: byte i of the plane's dwords
+template <int ND>
+__device__ __forceinline__ int line_sample_planar(const unsigned (&d)[ND], int ch, int i)
+{
+  return (int)((d[ch * (ND / 3) + (i >> 2)] >> (8 * (i & 3))) & 0xffu);
+}
+
 // Interior blocks of RGB -> YCbCr frames with subsampling factors 1 or 2: the block's SX*8 x SY*8 pixels are read as
 // dwords (rows of 24 * SX bytes, 48 * SX at precision 12; the host checks that lines start dword-aligned), the samples picked
 // apart in registers, only the block's own component computed, the box filter's division a shift (the sums are not negative).
@@ -188,6 +219,43 @@ __device__ __forceinline__ void gather_block_fast(const uint8_t *img, int64_t ro
             const int j = 3 * (i * SX + k); // sample of the pixel's R inside the line
             const auto &d = dw[rr * SY + ly];
             acc[i] += ycc_component<P>(c, line_sample<P>(d, j), line_sample<P>(d, j + 1), line_sample<P>(d, j + 2));
+          }
+#pragma unroll
+      for (int i = 0; i < 8; i++) blk[(r0 + rr) * 8 + i] = acc[i] >> (SX * SY == 4 ? 2 : SX * SY == 2 ? 1 : 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+// The same block out of three planes (8 bit): lines of 8 * SX bytes per plane, 6 * SX dwords a line and 48 in flight as above;
+// R, G and B of a pixel are the same byte of the three planes' dwords.
+template <int SX, int SY>
+__device__ __forceinline__ void gather_block_fast_planar(const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, int64_t row_stride, int x0, int y0, int c,
+                                                         int (&blk)[64])
+{
+  constexpr int ND = 6 * SX;
+  constexpr int RB = 8 / (SX * SY);
+#pragma unroll
+  for (int r0 = 0; r0 < 8; r0 += RB) {
+    unsigned dw[RB * SY][ND];
+#pragma unroll
+    for (int l = 0; l < RB * SY; l++) {
+      const int64_t at = (int64_t)(y0 + r0 * SY + l) * row_stride + x0;
+      load_line_planar(p0 + at, p1 + at, p2 + at, dw[l]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int rr = 0; rr < RB; rr++) {
+      int acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+      for (int ly = 0; ly < SY; ly++)
+#pragma unroll
+        for (int i = 0; i < 8; i++)
+#pragma unroll
+          for (int k = 0; k < SX; k++) {
+            const int j = i * SX + k; // the pixel inside the line
+            const auto &d = dw[rr * SY + ly];
+            acc[i] += ycc_component<8>(c, line_sample_planar(d, 0, j), line_sample_planar(d, 1, j), line_sample_planar(d, 2, j));
           }
 #pragma unroll
       for (int i = 0; i < 8; i++) blk[(r0 + rr) * 8 + i] = acc[i] >> (SX * SY == 4 ? 2 : SX * SY == 2 ? 1 : 0);
@@ -240,6 +308,23 @@ __device__ __forceinline__ RaggedItem find_item(const ForwardRaggedArgs &r)
 __device__ __forceinline__ const ForwardArgs &args_of(const ForwardArgs &k, const RaggedItem &) { return k; }
 __device__ __forceinline__ ConstForwardArgs &args_of(const ForwardRaggedArgs &k, const RaggedItem &it) { return *((ConstForwardArgs *)k.pics + it.pic); }
 
+// Planes 1 and 2 of the workgroup's picture where the input is planar (PL: the including namespace's PLANAR_IN), read like the
+// argument block through the constant address space: the bases stay in SGPRs.  Elsewhere two nulls nobody reads, and no code.
+struct InputPlanes {
+  const uint8_t *p1, *p2;
+};
+typedef const __attribute__((address_space(4))) ForwardPlanes ConstForwardPlanes;
+template <bool PL, class K>
+__device__ __forceinline__ InputPlanes input_planes(const K &k, const RaggedItem &it)
+{
+  if constexpr (PL) {
+    ConstForwardPlanes &e = *((ConstForwardPlanes *)k.planes + it.pic);
+    return InputPlanes{e.p1, e.p2};
+  } else
+    return InputPlanes{nullptr, nullptr};
+}
+
+constexpr bool PLANAR_IN = false; // (mij and mij::ragged12: interleaved input; mij::planar_in below says otherwise)
 #include "forward_kernels.inc"
 
 // The ragged 12-bit flavours are the same text once more, in a namespace of their own.  As plain instantiations <..., true, 12> of the
@@ -251,6 +336,88 @@ __device__ __forceinline__ ConstForwardArgs &args_of(const ForwardRaggedArgs &k,
 namespace ragged12 {
 #include "forward_kernels.inc"
 } // namespace ragged12
+
+// The planar-input flavours, by the same rule a third copy: 8-bit pictures of three components whose samples lie in
+// three planes.  PLANAR_IN selects where a pixel's three samples come from and nothing else; the copies above fold it away.  The
+// kernels of this copy take ForwardRaggedPlanarArgs -- the ragged arguments and the table of planes 1 and 2 -- and only the six
+// ragged 8-bit flavours <..., true, 8> are instantiated from it.
+namespace planar_in {
+constexpr bool PLANAR_IN = true;
+template <bool RAGGED>
+struct KernelArgs {
+  typedef ForwardRaggedPlanarArgs type;
+};
+#include "forward_kernels.inc"
+} // namespace planar_in
+
+// ---- planes -> interleaved picture: the first pass of the two-pass route of planar input ------------------------------------------
+// One lane takes eight pixels of a line: one load of 8 * SB bytes per plane (at any address), 8 * NC * SB contiguous bytes out in
+// 16-byte pieces (and one of 8 where that leaves a remainder).  The last lane of a line copies its npx < 8 pixels sample by sample.
+typedef u32x2 u32x2_any __attribute__((aligned(1)));
+typedef u32x4 u32x4_any __attribute__((aligned(1)));
+constexpr int INTERLEAVE_LINES = 4; // lines per workgroup (one wave each)
+template <int NC, int SB>
+__global__ __launch_bounds__(64 * INTERLEAVE_LINES) void interleave_kernel(const InterleaveArgs a)
+{
+  constexpr int BYTES = 8 * NC * SB;
+  const int chunk = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * INTERLEAVE_LINES + threadIdx.y;
+  const int x0 = chunk * 8;
+  if (x0 >= a.width || y >= a.height) return;
+  const int64_t src_off = (int64_t)y * a.src_row + (int64_t)x0 * SB;
+  uint8_t *__restrict__ dst = a.dst + (int64_t)y * a.dst_row + (int64_t)chunk * BYTES;
+  const int npx = min(8, a.width - x0);
+  if (npx == 8) {
+    unsigned w[BYTES / 4];
+#pragma unroll
+    for (int i = 0; i < BYTES / 4; i++) w[i] = 0;
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      unsigned s[2 * SB];
+      if constexpr (SB == 1) {
+        const u32x2 v = *reinterpret_cast<const u32x2_any *>(a.src[c] + src_off);
+        s[0] = v.x; s[1] = v.y;
+      } else {
+        const u32x4 v = *reinterpret_cast<const u32x4_any *>(a.src[c] + src_off);
+        s[0] = v.x; s[1] = v.y; s[2 * SB - 2] = v.z; s[2 * SB - 1] = v.w;
+      }
+#pragma unroll
+      for (int x = 0; x < 8; x++) {
+        const int e = x * NC + c; // the sample's index in the lane's piece
+        if constexpr (SB == 1) w[e >> 2] |= ((s[x >> 2] >> (8 * (x & 3))) & 0xffu) << (8 * (e & 3));
+        else w[e >> 1] |= ((s[x >> 1] >> (16 * (x & 1))) & 0xffffu) << (16 * (e & 1));
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < BYTES / 16; i++) reinterpret_cast<u32x4_any *>(dst)[i] = u32x4{w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]};
+    if constexpr (BYTES % 16 != 0) *reinterpret_cast<u32x2_any *>(dst + (BYTES - 8)) = u32x2{w[BYTES / 4 - 2], w[BYTES / 4 - 1]};
+  } else {
+    for (int x = 0; x < npx; x++)
+#pragma unroll
+      for (int c = 0; c < NC; c++)
+#pragma unroll
+        for (int k = 0; k < SB; k++) dst[(x * NC + c) * SB + k] = a.src[c][src_off + x * SB + k];
+  }
+}
+
+int launch_interleave(const InterleaveArgs &a, hipStream_t stream)
+{
+  if (a.width <= 0 || a.height <= 0) return 0;
+  if (a.ncomp < 1 || a.ncomp > 4 || (a.sample_bytes != 1 && a.sample_bytes != 2)) return -1;
+  const dim3 grid((unsigned)((a.width + 511) / 512), (unsigned)((a.height + INTERLEAVE_LINES - 1) / INTERLEAVE_LINES)), block(64, INTERLEAVE_LINES);
+  void (*kernel)(const InterleaveArgs) = nullptr;
+  switch (a.ncomp * 2 + a.sample_bytes - 1) {
+  case 2: kernel = interleave_kernel<1, 1>; break;
+  case 3: kernel = interleave_kernel<1, 2>; break;
+  case 4: kernel = interleave_kernel<2, 1>; break;
+  case 5: kernel = interleave_kernel<2, 2>; break;
+  case 6: kernel = interleave_kernel<3, 1>; break;
+  case 7: kernel = interleave_kernel<3, 2>; break;
+  case 8: kernel = interleave_kernel<4, 1>; break;
+  default: kernel = interleave_kernel<4, 2>; break;
+  }
+  hipLaunchKernelGGL(kernel, grid, block, 0, stream, a);
+  return (int)hipGetLastError();
+}
 
 template <int P>
 static int launch_forward_of(const ForwardArgs &a, hipStream_t stream)
@@ -284,6 +451,10 @@ int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *l
     const ForwardRaggedArgs &r = p.launch[l];
     if (r.items == 0 || p.grid[l] == 0) continue;
     const dim3 grid(p.grid[l]);
+    ForwardRaggedPlanarArgs rp;
+    static_cast<ForwardRaggedArgs &>(rp) = r;
+    rp.planes = p.planes;
+    if (l >= 2 * FORWARD_RAGGED_LAUNCHES && !p.planes) return (int)hipErrorInvalidValue; // a planar list without its plane table
     switch (l) {
     case 0: hipLaunchKernelGGL((fdct420_tile_kernel<true, 8>), grid, dim3(256), 0, stream, r); break;
     case 1: hipLaunchKernelGGL((fdct_interior_kernel<1, 1, true, 8>), grid, dim3(256), 0, stream, r, 0); break;
@@ -297,7 +468,14 @@ int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *l
     case 8: hipLaunchKernelGGL((ragged12::fdct_interior_kernel<2, 2, true, 12>), grid, dim3(256), 0, stream, r, 0); break;
     case 9: hipLaunchKernelGGL((ragged12::fdct_interior_kernel<2, 1, true, 12>), grid, dim3(256), 0, stream, r, 0); break;
     case 10: hipLaunchKernelGGL((ragged12::fdct_interior_kernel<1, 2, true, 12>), grid, dim3(256), 0, stream, r, 0); break;
-    default: hipLaunchKernelGGL((ragged12::fdct_blocks_kernel<true, 12>), grid, dim3(256), 0, stream, r); break;
+    case 11: hipLaunchKernelGGL((ragged12::fdct_blocks_kernel<true, 12>), grid, dim3(256), 0, stream, r); break;
+    // the lists of the planar 8-bit pictures of three components
+    case 12: hipLaunchKernelGGL((planar_in::fdct420_tile_kernel<true, 8>), grid, dim3(256), 0, stream, rp); break;
+    case 13: hipLaunchKernelGGL((planar_in::fdct_interior_kernel<1, 1, true, 8>), grid, dim3(256), 0, stream, rp, 0); break;
+    case 14: hipLaunchKernelGGL((planar_in::fdct_interior_kernel<2, 2, true, 8>), grid, dim3(256), 0, stream, rp, 0); break;
+    case 15: hipLaunchKernelGGL((planar_in::fdct_interior_kernel<2, 1, true, 8>), grid, dim3(256), 0, stream, rp, 0); break;
+    case 16: hipLaunchKernelGGL((planar_in::fdct_interior_kernel<1, 2, true, 8>), grid, dim3(256), 0, stream, rp, 0); break;
+    default: hipLaunchKernelGGL((planar_in::fdct_blocks_kernel<true, 8>), grid, dim3(256), 0, stream, rp); break;
     }
     if (launches) ++*launches;
   }

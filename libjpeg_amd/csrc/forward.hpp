@@ -40,16 +40,32 @@ struct ForwardRaggedArgs {
   const uint32_t *item;      // device, per item: picture * 4 + component
   uint32_t items;
 };
+// Planar input: an 8-bit picture of three components whose samples lie in three planes.  Its ForwardArgs holds plane 0
+// in `pixels` and the planes' line pitch in `pixel_row_stride`; planes 1 and 2 travel in a table beside `pics`, one entry of 16 bytes
+// per picture of the pass (an interleaved picture's entry is two nulls).  ForwardArgs itself is what it was.
+struct ForwardPlanes {
+  const uint8_t *p1, *p2;
+};
+// what the planar-input flavours (mij::planar_in) are launched with: the ragged arguments and that table
+struct ForwardRaggedPlanarArgs : ForwardRaggedArgs {
+  const ForwardPlanes *planes; // device, indexed by picture like pics
+};
 // The launches of a ragged list of one precision, in the order launch_forward_ragged issues them: the 4:2:0 tile kernel, the interior
 // kernels <1,1> <2,2> <2,1> <1,2>, the per-block kernel.  The routing per picture is launch_forward's.
 // Precision is a property of the picture: the 8-bit pictures of a list have their work lists (0 .. 5), the 12-bit pictures theirs
-// (6 .. 11, forward_ragged_list), so a workgroup never sees pictures of two precisions and a list of both costs at most twelve launches.
+// (6 .. 11, forward_ragged_list), and the planar 8-bit pictures of three components theirs (12 .. 17), so a workgroup never sees
+// pictures of two flavours.  An interleaved list costs at most twelve launches a pass; a planar list, whose colour pictures are in
+// 12 .. 17 (8 bit) or 6 .. 11 (12 bit, interleaved first) and whose grey pictures are in 0 .. 5 and 6 .. 11, at most eighteen.
 constexpr int FORWARD_RAGGED_LAUNCHES = 6;
-constexpr int FORWARD_RAGGED_LISTS = 2 * FORWARD_RAGGED_LAUNCHES;
-inline int forward_ragged_list(int which, int precision) { return which + (precision == 12 ? FORWARD_RAGGED_LAUNCHES : 0); }
+constexpr int FORWARD_RAGGED_LISTS = 3 * FORWARD_RAGGED_LAUNCHES;
+inline int forward_ragged_list(int which, int precision, bool planar = false)
+{
+  return which + (planar ? 2 * FORWARD_RAGGED_LAUNCHES : precision == 12 ? FORWARD_RAGGED_LAUNCHES : 0);
+}
 struct ForwardRaggedPlan {
   ForwardRaggedArgs launch[FORWARD_RAGGED_LISTS]; // items == 0: not launched
   uint32_t grid[FORWARD_RAGGED_LISTS];
+  const ForwardPlanes *planes;                    // device; what lists 12 .. 17 read beside pics (null without them)
 };
 // The work items picture `a` contributes: wgs[k] workgroups and item component comp[k] per entry, launch index which[k]; returns
 // the number of entries (at most 5).  Host side of the routing rule: plain arithmetic, what launch_forward launches for a frame.
@@ -73,6 +89,18 @@ inline int forward_ragged_items(const ForwardArgs &a, int which[5], uint32_t wgs
 }
 // returns 0 or a hipError_t; *launches: kernels launched
 int launch_forward_ragged(const ForwardRaggedPlan &p, hipStream_t stream, int *launches);
+
+// Component planes -> an interleaved picture (ncomp x sample_bytes per pixel): the first pass of the two-pass route of planar input,
+// deinterleave_kernel turned round
+struct InterleaveArgs {
+  const uint8_t *src[4];
+  int64_t src_row;             // bytes per line of every plane
+  int32_t ncomp, sample_bytes; // 1..4; 1 or 2
+  int32_t width, height;
+  uint8_t *dst;
+  int64_t dst_row;             // bytes per line of dst
+};
+int launch_interleave(const InterleaveArgs &a, hipStream_t stream);
 
 } // namespace mij
 #endif

@@ -1,6 +1,7 @@
 // forward_kernels.inc -- the text of the three forward kernels (forward.hip includes it; see there for what they compute and for
-// the helpers they call).  It is included twice: in namespace mij, where the uniform flavours of both precisions and the ragged
-// 8-bit flavours are instantiated, and in namespace mij::ragged12 for the ragged 12-bit flavours (the reason is in forward.hip).
+// the helpers they call).  It is included three times: in namespace mij, where the uniform flavours of both precisions and the ragged
+// 8-bit flavours are instantiated, in namespace mij::ragged12 for the ragged 12-bit flavours (the reason is in forward.hip), and in
+// namespace mij::planar_in, where PLANAR_IN is true and the pixel's three samples come from three planes (ragged 8-bit flavours only).
 // No include guard on purpose.
 template <bool RAGGED, int P>
 __global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelArgs<RAGGED>::type k)
@@ -27,7 +28,12 @@ __global__ __launch_bounds__(256) void fdct_blocks_kernel(const typename KernelA
   const uint8_t *img = a.pixels + (int64_t)frame * a.pixel_frame_stride;
   const bool ycc = nc == 3 && a.ycbcr;
   auto sample = [&](int x, int y) -> int { // component c of pixel (x, y), x < W, y < H, with COLOR_BITS fractional bits
-    if constexpr (P == 8) {
+    if constexpr (PLANAR_IN) { // three planes of bytes (img is plane 0), read byte by byte: any address, any pitch
+      const InputPlanes pl = input_planes<PLANAR_IN>(k, it); // (uniform and read-only: loaded once, outside the loops)
+      const int64_t at = (int64_t)y * a.pixel_row_stride + x;
+      if (ycc) return ycc_component<P>(c, img[at], pl.p1[at], pl.p2[at]);
+      return (int)(c == 0 ? img : c == 1 ? pl.p1 : pl.p2)[at] << 4;
+    } else if constexpr (P == 8) {
       const uint8_t *p = img + (int64_t)y * a.pixel_row_stride + (int64_t)x * nc;
       if (ycc) return ycc_component<P>(c, p[0], p[1], p[2]);
       return (int)p[c] << 4;
@@ -105,6 +111,7 @@ __global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const typename Ker
   const int lane = threadIdx.x;
   const int lbx = lane & 15, lby = lane >> 4; // luma block inside the tile
   const int x0 = tx * 128 + lbx * 8, y0 = ty * 128 + lby * 8;
+  const InputPlanes pl = input_planes<PLANAR_IN>(k, it);
   {
     int blk[64];
     chroma_t *cb = chroma[0] + (lby * 4) * 64 + lbx * 4, *cr = chroma[1] + (lby * 4) * 64 + lbx * 4;
@@ -112,7 +119,13 @@ __global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const typename Ker
     for (int r0 = 0; r0 < 8; r0 += RB) {
       unsigned dw[RB][6 * SB];
 #pragma unroll
-      for (int r = 0; r < RB; r++) load_line<P>(img + (int64_t)(y0 + r0 + r) * a.pixel_row_stride + (int64_t)x0 * (3 * SB), dw[r]);
+      for (int r = 0; r < RB; r++) {
+        if constexpr (PLANAR_IN) { // 8 bytes of each plane: two dwords x 3 planes where the interleaved line is 6 dwords
+          const int64_t at = (int64_t)(y0 + r0 + r) * a.pixel_row_stride + x0;
+          load_line_planar(img + at, pl.p1 + at, pl.p2 + at, dw[r]);
+        } else
+          load_line<P>(img + (int64_t)(y0 + r0 + r) * a.pixel_row_stride + (int64_t)x0 * (3 * SB), dw[r]);
+      }
       if constexpr (RB < 8) __builtin_amdgcn_sched_barrier(0); // the loads of one batch together, as in gather_block_fast
 #pragma unroll
       for (int r = r0; r < r0 + RB; r += 2) {
@@ -123,7 +136,9 @@ __global__ __launch_bounds__(256, 2) void fdct420_tile_kernel(const typename Ker
           for (int i = 0; i < 8; i++) {
             const int j = 3 * i;
             const auto &d = dw[r - r0 + rr];
-            const int r8 = line_sample<P>(d, j), g8 = line_sample<P>(d, j + 1), b8 = line_sample<P>(d, j + 2);
+            const int r8 = PLANAR_IN ? line_sample_planar(d, 0, i) : line_sample<P>(d, j);
+            const int g8 = PLANAR_IN ? line_sample_planar(d, 1, i) : line_sample<P>(d, j + 1);
+            const int b8 = PLANAR_IN ? line_sample_planar(d, 2, i) : line_sample<P>(d, j + 2);
             blk[(r + rr) * 8 + i] = ycc_component<P>(0, r8, g8, b8);
             sb[i >> 1] += ycc_component<P>(1, r8, g8, b8);
             sr[i >> 1] += ycc_component<P>(2, r8, g8, b8);
@@ -173,6 +188,10 @@ __global__ __launch_bounds__(256, SX * SY == 4 ? (RAGGED || P == 12 ? 1 : 2) : 3
   int16_t *dst = a.coef + (int64_t)frame * a.coef_frame_stride + a.coef_off[c] + ((int64_t)by * a.bw[c] + bx) * 64;
   const uint8_t *img = a.pixels + (int64_t)frame * a.pixel_frame_stride;
   int blk[64];
-  gather_block_fast<SX, SY, P>(img, a.pixel_row_stride, (bx * SX) << 3, (by * SY) << 3, c, blk);
+  if constexpr (PLANAR_IN) {
+    const InputPlanes pl = input_planes<PLANAR_IN>(k, it);
+    gather_block_fast_planar<SX, SY>(img, pl.p1, pl.p2, a.pixel_row_stride, (bx * SX) << 3, (by * SY) << 3, c, blk);
+  } else
+    gather_block_fast<SX, SY, P>(img, a.pixel_row_stride, (bx * SX) << 3, (by * SY) << 3, c, blk);
   transform_and_store<P>(blk, a.invq[c], dst);
 }

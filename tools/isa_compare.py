@@ -35,6 +35,8 @@ def kernels(path, mask_pcrel=False):
                 cur = out.setdefault(m.group(1), [])
             elif cur is not None and ln.strip():
                 ins = re.sub(r"//.*", "", ln).strip()
+                if ins == "...":  # (llvm-objdump's mark for zero padding between two symbols: layout, not an instruction)
+                    continue
                 if mask_pcrel and cur and cur[-1].startswith("s_getpc_b64") and ins.startswith("s_add_u32"):
                     ins = re.sub(r"0x[0-9a-f]+$", "<pc-relative>", ins)
                 cur.append(ins)
