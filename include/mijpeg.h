@@ -618,6 +618,48 @@ int mijpeg_ragged_rect_stats_get(mijpeg_decoder *d, mijpeg_ragged_rect_stats *ou
 int mijpeg_ragged_rect_plan(const mijpeg_info *infos, const mijpeg_rect *rects, int n, int32_t *tile_x0, int32_t *tile_y0, int32_t *tiles_x,
                             int32_t *tiles_y);
 
+/* ---- crops of a ragged batch resized into ONE batch tensor, one resample launch for the list ------------
+ * What a loader does between the decoder and a training batch: a window of a different size from every picture (RandomResizedCrop,
+ * resize + centre crop), all of them out_width x out_height afterwards, in the slots of one (N, C, H, W) or (N, H, W, C) tensor.  The
+ * call follows mijpeg_decode_ragged_device / ...16 exactly as the crop calls above do (same object, the coefficient stores stay valid,
+ * same `flags` masking, same `sync`).  Stage 1 is the crop call's own body with destinations in an arena of the object -- so window
+ * launches, the copy route and child objects all deliver --, stage 2 ONE launch of the resample kernel on the object's stream, for
+ * any n.
+ * The filter is defined in integers, so that host, kernel and a model in numpy cannot disagree: a separable triangle filter whose
+ * support grows with the reduction (Pillow's BILINEAR, antialias=True elsewhere), horizontally first, rounded to 8 bits, then
+ * vertically.  One axis, n source samples (the clipped crop's extent), m output samples, output o, source i:
+ *   S = 2 max(n, m),  D(i) = |(2i + 1) m - (2o + 1) n|,  w(i) = max(0, S - D(i));  the taps of o: the run of i in [0, n) with w(i) > 0;
+ *   W = sum w(i),  k(i) = floor((w(i) 2^14 + floor(W / 2)) / W);  2^14 - sum k(i) is added to k at the tap with the largest w (the
+ *   lowest such i);  out = min(255, (sum k(i) p(i) + 2^13) >> 14).            m == n is the identity: the crop call's bytes.
+ * rects[i]: as the crop calls take and clip it; rects == NULL: whole pictures.  Slot i of the destination belongs to picture i:
+ * dst_device + i * image_stride, channel c at + c * plane_stride (plane_stride != 0: planar) or interleaved in the pixel
+ * (plane_stride == 0), lines row_stride bytes apart.  channels is 1 or 3; a one-component picture in a 3-channel batch is written to
+ * all three channels.  Nothing but the served slots' own out_height lines of out_width pixels is written.
+ * MIJPEG_ERR_INVALID_PARAMETER for the call, before anything is launched, written or counted: NULL d or dst_device, out_width or
+ * out_height below 1 (or above 65535), channels not 1 or 3, a rectangle the crop calls refuse, a row_stride below a line, a
+ * plane_stride below a plane's lines, an image_stride below a slot's data, a slot that spans 4 GiB or more.
+ * Per picture, status[i] (n entries, may be NULL): 0 = served; the decode status of a picture in error; MIJPEG_ERR_NOT_IMPLEMENTED for
+ * 16-bit samples (12 bit, JPEG XT), two or four components, three components into channels == 1, and a crop of 4 GiB or more.  Such a
+ * picture's slot is not written, the others are served. */
+#define MIJPEG_ERR_NOT_IMPLEMENTED MIJPEG_ERR_OPERATION_UNIMPLEMENTED
+int mijpeg_reconstruct_ragged_resized_device(mijpeg_decoder *d, const mijpeg_rect *rects /* NULL: whole pictures */, int32_t out_width,
+                                             int32_t out_height, int32_t channels, void *dst_device, int64_t image_stride,
+                                             int64_t plane_stride /* 0: interleaved */, int64_t row_stride, uint32_t flags,
+                                             int32_t *status /* n, may be NULL */, int sync);
+/* What the object's last resized call did. */
+typedef struct mijpeg_ragged_resized_stats {
+  int32_t images, resampled, refused;   /* pictures of the list; served; not served (status[i] != 0)                      */
+  int32_t window_launches;              /* stage 1: what the crop call reports as `launches` for the same rectangles      */
+  int32_t resample_launches;            /* stage 2: 1 whenever resampled > 0                                              */
+  int32_t reserved;
+  int64_t arena_bytes;                  /* the crops of this call, each padded to 16 bytes                                */
+} mijpeg_ragged_resized_stats;
+int mijpeg_ragged_resized_stats_get(mijpeg_decoder *d, mijpeg_ragged_resized_stats *out);
+/* The filter's taps for one axis, no device: first[m], count[m] and the weights of output o at weights[o * capacity_per_output ...]
+ * (zero behind its count).  -> the axis's maximal tap count (<= min(n, 2 ceil(max(n, m) / m) + 1)); with a NULL array only that.
+ * 0: n or m outside 1 .. 65535, or a capacity below the maximal count. */
+int32_t mijpeg_resample_taps(int32_t n, int32_t m, int32_t *first, int32_t *count, int16_t *weights, int32_t capacity_per_output);
+
 /* ---- stateless device entry points (inputs and outputs resident in HBM) -------------------- */
 
 /* Describes a batch of equally shaped frames whose coefficient planes are already on the device. */

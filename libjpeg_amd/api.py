@@ -30,6 +30,7 @@ FLAG_FORCE_DOT2 = 64  # (testing) the packed 4:2:0 kernel's 16-bit second pass w
 ERR_DEVICE = -8191
 ERR_NOT_AVAILABLE = -1029
 ERR_INVALID_PARAMETER = -1024
+ERR_NOT_IMPLEMENTED = -1034  # MIJPEG_ERR_NOT_IMPLEMENTED (= MIJPEG_ERR_OPERATION_UNIMPLEMENTED)
 
 
 class MijpegInfo(C.Structure):
@@ -91,6 +92,10 @@ class MijpegRect(C.Structure):
 
 class MijpegRaggedRectStats(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("images", "fused", "copied", "launches")] + [("workgroups", C.c_int64), ("workgroups_full", C.c_int64)]
+
+
+class MijpegRaggedResizedStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("images", "resampled", "refused", "window_launches", "resample_launches", "reserved")] + [("arena_bytes", C.c_int64)]
 
 
 class MijpegRaggedFrame(C.Structure):
@@ -205,6 +210,11 @@ def lib():
         L.mijpeg_reconstruct_ragged_rect_planar_device.argtypes = L.mijpeg_reconstruct_ragged_rect_device.argtypes
         L.mijpeg_ragged_rect_stats_get.argtypes = [C.c_void_p, P(MijpegRaggedRectStats)]
         L.mijpeg_ragged_rect_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mijpeg_reconstruct_ragged_resized_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                               C.c_uint32, C.POINTER(C.c_int32), C.c_int]
+        L.mijpeg_ragged_resized_stats_get.argtypes = [C.c_void_p, P(MijpegRaggedResizedStats)]
+        L.mijpeg_resample_taps.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+        L.mijpeg_resample_taps.restype = C.c_int32
         L.mijpeg_deinterleave_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int64]
         L.mijpeg_ragged_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.mijpeg_ragged_plan16.argtypes = L.mijpeg_ragged_plan.argtypes
@@ -843,6 +853,28 @@ class Decoder:
         self._check(lib().mijpeg_ragged_rect_stats_get(self._h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in MijpegRaggedRectStats._fields_}
 
+    # ---- crops resized into one batch tensor (include/mijpeg.h)
+    def reconstruct_ragged_resized_device(self, rects, out_width: int, out_height: int, channels: int, dst_ptr: int, image_stride: int, plane_stride: int,
+                                          row_stride: int, flags: int = 0, sync: bool = True, wait_foreign: bool = True) -> list[int]:
+        """mijpeg_reconstruct_ragged_resized_device: the crop rects[i] (None: whole pictures; (min_x, min_y, max_x, max_y), inclusive) of
+        picture i of the last ragged decode, resized to out_width x out_height, into slot i at dst_ptr + i * image_stride; planar with
+        plane_stride != 0, interleaved with 0.  -> status per picture: 0 = served, its decode status, or ERR_NOT_IMPLEMENTED."""
+        n = getattr(self, "ragged_images", 0)
+        if rects is not None and len(rects) != n:
+            raise ValueError(f"{len(rects)} crops for the {n} images of the ragged batch")
+        if wait_foreign:
+            _foreign_work_done()
+        status = (C.c_int32 * max(1, n))()
+        self._check(lib().mijpeg_reconstruct_ragged_resized_device(self._h, rect_array(rects) if rects is not None else None, out_width, out_height, channels,
+                                                                   dst_ptr or None, image_stride, plane_stride, row_stride, flags, status, 1 if sync else 0))
+        return list(status)[:n]
+
+    def ragged_resized_stats(self) -> dict:
+        """What the object's last resized call did (mijpeg_ragged_resized_stats)."""
+        st = MijpegRaggedResizedStats()
+        self._check(lib().mijpeg_ragged_resized_stats_get(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MijpegRaggedResizedStats._fields_ if k != "reserved"}
+
     def deinterleave_device(self, src_ptr: int, src_row_stride: int, width: int, height: int, components: int, sample_bytes: int, plane_ptrs,
                             row_stride: int):
         """mijpeg_deinterleave_device: an interleaved picture in device memory -> its planes, on the object's stream (no wait)."""
@@ -1077,6 +1109,18 @@ def rect_array(rects):
     if not rects:
         flat = array.array("i", [0] * 4)
     return (MijpegRect * (len(flat) // 4)).from_buffer(flat)
+
+
+def resample_taps(n: int, m: int):
+    """mijpeg_resample_taps (no device needed): the integer triangle filter's taps for one axis of n source and m output samples ->
+    (first, count, weights): int32 arrays of m entries and an int16 array (m, maximal count), zero behind an output's count."""
+    cap = lib().mijpeg_resample_taps(n, m, None, None, None, 0)
+    if cap < 1:
+        raise MijpegError(ERR_INVALID_PARAMETER, f"mijpeg_resample_taps: no taps for {n} -> {m} samples (1 .. 65535 each)")
+    first, count, weights = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, cap), np.int16)
+    if lib().mijpeg_resample_taps(n, m, first.ctypes.data, count.ctypes.data, weights.ctypes.data, cap) != cap:
+        raise MijpegError(ERR_INVALID_PARAMETER, "mijpeg_resample_taps failed")
+    return first, count, weights
 
 
 def ragged_rect_plan(infos, rects):

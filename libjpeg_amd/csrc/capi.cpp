@@ -275,6 +275,10 @@ try {
     if (d->ragged_desc_dev) (void)hipFree(d->ragged_desc_dev);
     if (d->ragged_desc_host) (void)hipHostFree(d->ragged_desc_host);
     if (d->ragged_uploaded) (void)hipEventDestroy(d->ragged_uploaded);
+    if (d->resized_arena_dev) (void)hipFree(d->resized_arena_dev);
+    if (d->resized_desc_dev) (void)hipFree(d->resized_desc_dev);
+    if (d->resized_desc_host) (void)hipHostFree(d->resized_desc_host);
+    if (d->resized_uploaded) (void)hipEventDestroy(d->resized_uploaded);
     if (d->enc_dev) (void)hipFree(d->enc_dev);
     for (int k = 0; k < 2; k++) {
       if (d->henc_dev[k]) (void)hipFree(d->henc_dev[k]);

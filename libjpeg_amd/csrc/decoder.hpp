@@ -149,6 +149,13 @@ struct mijpeg_decoder {
   uint8_t *rect_tmp_dev = nullptr;
   size_t rect_tmp_cap = 0;
   mijpeg_ragged_rect_stats rect_stats{};
+  // resized call (mijpeg_reconstruct_ragged_resized_device, ragged_decode.cpp): the arena of the crops, the call's tables
+  // (resample_taps.hpp) and their pinned copy, which resized_uploaded guards from one call to the next; what the last call did
+  uint8_t *resized_arena_dev = nullptr, *resized_desc_dev = nullptr, *resized_desc_host = nullptr;
+  size_t resized_arena_cap = 0, resized_desc_cap = 0, resized_desc_host_cap = 0;
+  hipEvent_t resized_uploaded = nullptr;
+  bool resized_upload_pending = false;
+  mijpeg_ragged_resized_stats resized_stats{};
   // ragged encode (encode_device.cpp): descriptors, coder arrays and coefficient store of a pass; plain stream and output arena;
   // pinned: descriptors on their way up and counts read back; the downloaded arena
   uint8_t *eragged_dev = nullptr, *eragged_out_dev = nullptr, *eragged_host = nullptr, *eragged_down = nullptr;

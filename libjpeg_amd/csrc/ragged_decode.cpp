@@ -7,6 +7,7 @@
 
 #include "fused_list.hpp"
 #include "reconstruct.hpp"
+#include "resample.hpp"
 
 using namespace mij;
 
@@ -566,5 +567,162 @@ try {
   }
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(nullptr, "mijpeg_ragged_rect_plan"); }
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// crops resized into one batch tensor (include/mijpeg.h)
+// ------------------------------------------------------------------------------------------------
+// Why the resized call does not serve a decoded picture, or 0
+static int resized_refusal(const mijpeg_info &f, int32_t channels)
+{
+  if (sample_bytes_of(f) != 1) return MIJPEG_ERR_NOT_IMPLEMENTED;
+  if (f.components != 1 && f.components != 3) return MIJPEG_ERR_NOT_IMPLEMENTED;
+  if (f.components == 3 && channels == 1) return MIJPEG_ERR_NOT_IMPLEMENTED;
+  return 0;
+}
+
+// Stage 2: the tables of the served pictures in one pinned upload, and the one launch
+static int launch_resample(mijpeg_decoder *d, const ResampleItem *items, const ResampleLayout &L, int32_t out_w, int32_t out_h, int32_t channels, void *dst,
+                           int64_t image_stride, int64_t plane_stride, int64_t row_stride)
+{
+  int rc = ensure_dev(d, (void **)&d->resized_desc_dev, &d->resized_desc_cap, L.table_bytes);
+  if (rc) return rc;
+  if (d->resized_upload_pending) { // (the pinned copy travels asynchronously: the last call's must have left)
+    HIP_TRY(d, hipEventSynchronize(d->resized_uploaded));
+    d->resized_upload_pending = false;
+  }
+  if ((rc = ensure_pinned(d, &d->resized_desc_host, &d->resized_desc_host_cap, L.table_bytes))) return rc;
+  const int served = (int)L.per.size(), workers = std::min(served, default_threads());
+  std::vector<char> bad((size_t)workers, 0);
+  parallel_for(workers, [&](int w) { // (a division per tap: a list of 256 pictures has half a million)
+    for (int k = w; k < served; k += workers)
+      if (!resample_fill(d->resized_desc_host, L, (size_t)k, items, out_w, out_h, image_stride)) bad[(size_t)w] = 1;
+  });
+  resample_fill_first(d->resized_desc_host, L);
+  for (char b : bad)
+    if (b) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "the resample filter has no taps for these sizes");
+  HIP_TRY(d, hipMemcpyAsync(d->resized_desc_dev, d->resized_desc_host, L.table_bytes, hipMemcpyHostToDevice, d->stream));
+  if (!d->resized_uploaded) HIP_TRY(d, hipEventCreateWithFlags(&d->resized_uploaded, hipEventDisableTiming));
+  HIP_TRY(d, hipEventRecord(d->resized_uploaded, d->stream));
+  d->resized_upload_pending = true;
+  ResampleArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = d->resized_arena_dev;
+  a.dst = (uint8_t *)dst;
+  a.tables = d->resized_desc_dev;
+  a.pictures = (const ResamplePicture *)(d->resized_desc_dev + L.pictures);
+  a.first = (const uint32_t *)(d->resized_desc_dev + L.first);
+  a.served = served;
+  a.out_w = out_w; a.out_h = out_h; a.channels = channels;
+  a.plane_stride = (uint32_t)plane_stride; a.row_stride = (uint32_t)row_stride;
+  if (launch_resample_list(a, (unsigned)L.workgroups, d->stream))
+    return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+  return MIJPEG_OK;
+}
+
+static int reconstruct_ragged_resized(mijpeg_decoder *d, const mijpeg_rect *rects, int32_t out_w, int32_t out_h, int32_t channels, void *dst, int64_t image_stride,
+                                      int64_t plane_stride, int64_t row_stride, uint32_t flags, int32_t *status, int sync)
+{
+  if (!d || !dst) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  if (d->ragged_n < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded ragged batch: call mijpeg_decode_ragged_device first");
+  const int n = d->ragged_n;
+  // every parameter, before anything is launched, written or counted
+  if (out_w < 1 || out_h < 1 || out_w > RESAMPLE_MAX_AXIS || out_h > RESAMPLE_MAX_AXIS) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "resized call: out_width and out_height are 1 .. 65535");
+  if (channels != 1 && channels != 3) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "resized call: channels is 1 or 3");
+  const bool planar = plane_stride != 0;
+  if (row_stride < 1 || row_stride > 0xffffffffll || plane_stride < 0 || plane_stride > 0xffffffffll) // (what follows then stays inside 64 bits)
+    return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "resized call: a stride is smaller than the data it spans, or a slot spans 4 GiB or more");
+  const int64_t line = (int64_t)out_w * (planar ? 1 : channels), plane = (int64_t)(out_h - 1) * row_stride + line;
+  const int64_t slot = planar ? (int64_t)(channels - 1) * plane_stride + plane : plane;
+  if (row_stride < line || (planar && plane_stride < plane) || image_stride < slot || slot > 0xffffffffll)
+    return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "resized call: a stride is smaller than the data it spans, or a slot spans 4 GiB or more");
+  const mijpeg_rect whole{0, 0, INT32_MAX, INT32_MAX};
+  std::vector<mijpeg_rect> asked((size_t)n, whole), win((size_t)n);
+  for (int i = 0; i < n; i++) {
+    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    if (r.status) continue;
+    if (rects) asked[(size_t)i] = rects[i];
+    if (!fused_window_clip(asked[(size_t)i], r.info.width, r.info.height, win[(size_t)i]))
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "crop of image " + std::to_string(i) + ": min_x / min_y lie outside the picture, or min > max");
+  }
+  // who is served, and where everything lies
+  std::vector<ResampleItem> items((size_t)n);
+  std::vector<int32_t> st((size_t)n, 0);
+  for (int i = 0; i < n; i++) {
+    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    ResampleItem &it = items[(size_t)i];
+    it.slot = i;
+    st[(size_t)i] = r.status ? r.status : resized_refusal(r.info, channels);
+    if (st[(size_t)i]) continue;
+    it.src_w = win[(size_t)i].max_x - win[(size_t)i].min_x + 1;
+    it.src_h = win[(size_t)i].max_y - win[(size_t)i].min_y + 1;
+    it.comps = r.info.components;
+    if ((uint64_t)it.src_w * (uint64_t)it.src_h * (uint64_t)it.comps > 0xffffffffull) { st[(size_t)i] = MIJPEG_ERR_NOT_IMPLEMENTED; continue; } // (the kernel's 32-bit offsets)
+    it.served = true;
+  }
+  {
+    const int workers = std::min(n, default_threads());
+    parallel_for(workers, [&](int w) { // (a pass over every output sample of both axes: one picture per worker)
+      for (int i = w; i < n; i += workers)
+        if (items[(size_t)i].served) resample_item_caps(items[(size_t)i], out_w, out_h);
+    });
+  }
+  const ResampleLayout L = resample_layout(items.data(), n, out_w, out_h);
+  if (L.table_bytes > 0xffffffffull || L.workgroups > 0x7fffffffull)
+    return set_error(d, MIJPEG_ERR_OVERFLOW_PARAMETER, "resized call: the list's tap tables pass 4 GiB or its tiles a grid of 2^31 - 1 workgroups");
+  HIP_TRY(d, hipSetDevice(d->device));
+  mijpeg_ragged_resized_stats stats{};
+  stats.images = n;
+  stats.resampled = (int32_t)L.per.size();
+  stats.refused = n - stats.resampled;
+  stats.arena_bytes = (int64_t)L.arena_bytes;
+  if (!L.per.empty()) {
+    // stage 1: the crop call's body, destinations in the arena (its statistics stay the last crop call's)
+    const int rc = ensure_dev(d, (void **)&d->resized_arena_dev, &d->resized_arena_cap, L.arena_bytes + RESAMPLE_ARENA_SPARE);
+    if (rc) return rc;
+    std::vector<void *> ptrs((size_t)n, nullptr);
+    std::vector<int64_t> rows((size_t)n, 0);
+    for (const ResampleLayout::Per &p : L.per) {
+      ptrs[(size_t)p.item] = d->resized_arena_dev + p.src_off;
+      rows[(size_t)p.item] = (int64_t)items[(size_t)p.item].src_w * items[(size_t)p.item].comps;
+    }
+    const mijpeg_ragged_rect_stats kept = d->rect_stats;
+    const int rc1 = reconstruct_ragged_rect(d, asked.data(), ptrs.data(), rows.data(), flags, 0, false);
+    stats.window_launches = d->rect_stats.launches;
+    d->rect_stats = kept;
+    if (rc1) return rc1;
+    // stage 2: one launch for the list
+    const int rc2 = launch_resample(d, items.data(), L, out_w, out_h, channels, dst, image_stride, plane_stride, row_stride);
+    if (rc2) return rc2;
+    stats.resample_launches = 1;
+  }
+  d->resized_stats = stats;
+  if (status)
+    for (int i = 0; i < n; i++) status[i] = st[(size_t)i];
+  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
+  return MIJPEG_OK;
+}
+
+extern "C" {
+
+int mijpeg_reconstruct_ragged_resized_device(mijpeg_decoder *d, const mijpeg_rect *rects, int32_t out_width, int32_t out_height, int32_t channels, void *dst_device,
+                                             int64_t image_stride, int64_t plane_stride, int64_t row_stride, uint32_t flags, int32_t *status, int sync)
+try {
+  return reconstruct_ragged_resized(d, rects, out_width, out_height, channels, dst_device, image_stride, plane_stride, row_stride, flags, status, sync);
+} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_resized_device"); }
+
+int mijpeg_ragged_resized_stats_get(mijpeg_decoder *d, mijpeg_ragged_resized_stats *out)
+try {
+  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
+  *out = d->resized_stats;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_ragged_resized_stats_get"); }
+
+int32_t mijpeg_resample_taps(int32_t n, int32_t m, int32_t *first, int32_t *count, int16_t *weights, int32_t capacity_per_output)
+try {
+  return resample_taps(n, m, first, count, weights, capacity_per_output);
+} catch (...) { (void)boundary_catch(nullptr, "mijpeg_resample_taps"); return 0; }
 
 } // extern "C"
