@@ -1398,12 +1398,20 @@ def _forward_on_device(info, img, frames=1):
     h, w = img.shape[:2]
     nc = 1 if img.ndim == 2 else img.shape[2]
     px = torch.from_numpy(np.ascontiguousarray(img)).cuda()
+    launched = frames
     if frames > 1:
-        px = px.unsqueeze(0).repeat(frames, *([1] * px.dim())).contiguous()
-    coef = torch.full((frames, int(info.coef_count)), 0x5A5A, dtype=torch.int16, device="cuda")
-    api.launch_forward(info, px.data_ptr(), coef.data_ptr(), frames, w * nc, h * w * nc, stream=torch.cuda.current_stream().cuda_stream)
+        # the launch gets one frame more: its second frame is another picture (this one turned round), the ones behind it are `img`
+        # again.  The caller sees the frames of `img` alone, and they are right only if pixel_frame_stride and coef_frame_stride are used
+        launched = frames + 1
+        other = torch.from_numpy(np.ascontiguousarray(img[::-1, ::-1])).cuda()
+        px = torch.stack([other if f == 1 else px for f in range(launched)]).contiguous()
+    coef = torch.full((launched, int(info.coef_count)), 0x5A5A, dtype=torch.int16, device="cuda")
+    api.launch_forward(info, px.data_ptr(), coef.data_ptr(), launched, w * nc, h * w * nc, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     out = coef.cpu().numpy()
+    if frames > 1:
+        assert not np.array_equal(out[1], out[0])  # (the other picture was read)
+        out = np.delete(out, 1, axis=0)
     res = []
     for f in range(frames):
         res.append([out[f, info.coef_offset[c]:info.coef_offset[c] + info.blocks_w[c] * info.blocks_h[c] * 64]
