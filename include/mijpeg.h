@@ -660,6 +660,50 @@ int mijpeg_ragged_resized_stats_get(mijpeg_decoder *d, mijpeg_ragged_resized_sta
  * 0: n or m outside 1 .. 65535, or a capacity below the maximal count. */
 int32_t mijpeg_resample_taps(int32_t n, int32_t m, int32_t *first, int32_t *count, int16_t *weights, int32_t capacity_per_output);
 
+/* ---- ... as a normalised float batch, mirrored per picture, still one resample launch -------------------
+ * What a training step does to the resized batch -- flip a random half of the pictures, x / 255, subtract a mean, divide by a
+ * deviation, cast --, in the resample launch's store epilogue.  Everything the resized call says holds here too: the object, `flags`,
+ * `sync`, clipping, refusals and status[i], the arena and stage 1, "nothing but the served slots' own lines is written" and "invalid
+ * parameters are refused before anything is launched, written or counted".  Every stride is in BYTES.
+ * Let v be the sample the resized call writes for a pixel and picture component (an integer 0 .. 255).  For output channel c
+ *   y = fl32(fl32((float)v * scale[c]) + bias[c])
+ * two IEEE binary32 operations, each rounded to nearest-even -- NOT a fused multiply-add.  A one-component picture in a 3-channel
+ * batch uses the same v with each channel's own scale[c], bias[c].  The stored element:
+ *   MIJPEG_SAMPLE_F32   y
+ *   MIJPEG_SAMPLE_F16   binary16 of y, to nearest-even
+ *   MIJPEG_SAMPLE_BF16  the upper 16 bits of bits(y) + 0x7fff + ((bits(y) >> 16) & 1): to nearest-even for every finite y
+ *   MIJPEG_SAMPLE_U8    v (scale and bias are not read)
+ * A result that is subnormal in the stored type is outside the contract: it may be flushed to zero.
+ * mirror[i] != 0: slot i holds the lines of the unmirrored slot reversed -- column x is column out_width - 1 - x of what the call
+ * writes without the flag.  Resize, then flip; not flip, then resize (the two differ where the filter's remainder goes to "the lowest
+ * such i").
+ * MIJPEG_ERR_INVALID_PARAMETER, besides the resized call's cases and as early: format == NULL, sample outside 0 .. 3, reserved != 0,
+ * for float samples a scale[c] or bias[c] with c < channels that is not finite, and dst_device, image_stride, plane_stride or
+ * row_stride that is no multiple of the element size (1, 4, 2, 2 bytes).  The resized call's stride checks apply with lines, planes
+ * and slots in bytes of that element; a slot still spans less than 4 GiB. */
+#define MIJPEG_SAMPLE_U8   0
+#define MIJPEG_SAMPLE_F32  1
+#define MIJPEG_SAMPLE_F16  2
+#define MIJPEG_SAMPLE_BF16 3
+typedef struct mijpeg_batch_format {
+  int32_t sample;            /* MIJPEG_SAMPLE_*                                                  */
+  int32_t reserved;          /* 0                                                                */
+  float scale[3], bias[3];   /* per OUTPUT channel; ignored for MIJPEG_SAMPLE_U8                 */
+  const uint8_t *mirror;     /* n flags (0 / non-0), host memory, read before the call returns; NULL: none mirrored */
+} mijpeg_batch_format;
+int mijpeg_reconstruct_ragged_normalized_device(mijpeg_decoder *d, const mijpeg_rect *rects /* NULL: whole pictures */, int32_t out_width,
+                                                int32_t out_height, int32_t channels, const mijpeg_batch_format *format, void *dst_device,
+                                                int64_t image_stride, int64_t plane_stride /* 0: interleaved */, int64_t row_stride,
+                                                uint32_t flags, int32_t *status /* n, may be NULL */, int sync);
+/* What the last resized or normalised call of the object stored: mijpeg_ragged_resized_stats keeps its members and meanings for both
+ * calls (resample_launches is 1 for any n); this is beside it.  The resized call sets {MIJPEG_SAMPLE_U8, 0}. */
+typedef struct mijpeg_ragged_normalized_stats {
+  int32_t sample;            /* MIJPEG_SAMPLE_* of the call                                      */
+  int32_t mirrored;          /* served pictures written mirrored                                 */
+  int32_t reserved[2];
+} mijpeg_ragged_normalized_stats;
+int mijpeg_ragged_normalized_stats_get(mijpeg_decoder *d, mijpeg_ragged_normalized_stats *out);
+
 /* ---- stateless device entry points (inputs and outputs resident in HBM) -------------------- */
 
 /* Describes a batch of equally shaped frames whose coefficient planes are already on the device. */

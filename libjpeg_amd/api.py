@@ -98,6 +98,19 @@ class MijpegRaggedResizedStats(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("images", "resampled", "refused", "window_launches", "resample_launches", "reserved")] + [("arena_bytes", C.c_int64)]
 
 
+SAMPLE_U8, SAMPLE_F32, SAMPLE_F16, SAMPLE_BF16 = 0, 1, 2, 3  # MIJPEG_SAMPLE_*
+SAMPLE_BYTES = {SAMPLE_U8: 1, SAMPLE_F32: 4, SAMPLE_F16: 2, SAMPLE_BF16: 2}
+
+
+class MijpegBatchFormat(C.Structure):
+    """mijpeg_batch_format: what the normalised resized call stores per sample, and which pictures it mirrors."""
+    _fields_ = [("sample", C.c_int32), ("reserved", C.c_int32), ("scale", C.c_float * 3), ("bias", C.c_float * 3), ("mirror", C.c_void_p)]
+
+
+class MijpegRaggedNormalizedStats(C.Structure):
+    _fields_ = [("sample", C.c_int32), ("mirrored", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 class MijpegRaggedFrame(C.Structure):
     _fields_ = [("coef_base", C.c_int64), ("off_y", C.c_int64), ("off_cb", C.c_int64), ("off_cr", C.c_int64)] + \
                [(k, C.c_int32) for k in ("first_workgroup", "tiles_x", "tiles_y", "width", "height", "bw_y", "bh_y", "bw_c", "bh_c", "cw", "ch", "reserved")]
@@ -213,6 +226,9 @@ def lib():
         L.mijpeg_reconstruct_ragged_resized_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                                C.c_uint32, C.POINTER(C.c_int32), C.c_int]
         L.mijpeg_ragged_resized_stats_get.argtypes = [C.c_void_p, P(MijpegRaggedResizedStats)]
+        L.mijpeg_reconstruct_ragged_normalized_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P(MijpegBatchFormat), C.c_void_p, C.c_int64,
+                                                                  C.c_int64, C.c_int64, C.c_uint32, C.POINTER(C.c_int32), C.c_int]
+        L.mijpeg_ragged_normalized_stats_get.argtypes = [C.c_void_p, P(MijpegRaggedNormalizedStats)]
         L.mijpeg_resample_taps.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
         L.mijpeg_resample_taps.restype = C.c_int32
         L.mijpeg_deinterleave_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int64]
@@ -874,6 +890,41 @@ class Decoder:
         st = MijpegRaggedResizedStats()
         self._check(lib().mijpeg_ragged_resized_stats_get(self._h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in MijpegRaggedResizedStats._fields_ if k != "reserved"}
+
+    # ---- ... as a normalised float batch, mirrored per picture (include/mijpeg.h)
+    def reconstruct_ragged_normalized_device(self, rects, out_width: int, out_height: int, channels: int, sample: int, scale, bias, mirror, dst_ptr: int,
+                                             image_stride: int, plane_stride: int, row_stride: int, flags: int = 0, sync: bool = True,
+                                             wait_foreign: bool = True) -> list[int]:
+        """mijpeg_reconstruct_ragged_normalized_device: the resized call with `sample` (SAMPLE_U8 / F32 / F16 / BF16) elements; a float
+        element of channel c is fl32(fl32(v * scale[c]) + bias[c]) of the 8-bit sample v the resized call writes (scale, bias: up to three
+        numbers, or None with SAMPLE_U8).  mirror: None or one truth value per picture of the ragged batch -- that slot's lines reversed.
+        Strides are in BYTES and multiples of the element size.  -> status per picture, as the resized call gives it."""
+        n = getattr(self, "ragged_images", 0)
+        if rects is not None and len(rects) != n:
+            raise ValueError(f"{len(rects)} crops for the {n} images of the ragged batch")
+        if mirror is not None and len(mirror) != n:
+            raise ValueError(f"{len(mirror)} mirror flags for the {n} images of the ragged batch")
+        fmt = MijpegBatchFormat()
+        fmt.sample = int(sample)
+        for k, v in enumerate(list(scale or ())[:3]):
+            fmt.scale[k] = v
+        for k, v in enumerate(list(bias or ())[:3]):
+            fmt.bias[k] = v
+        flags_array = (C.c_uint8 * max(1, n))(*[1 if m else 0 for m in mirror]) if mirror is not None else None  # (alive until the call returns)
+        fmt.mirror = C.cast(flags_array, C.c_void_p) if flags_array is not None else None
+        if wait_foreign:
+            _foreign_work_done()
+        status = (C.c_int32 * max(1, n))()
+        self._check(lib().mijpeg_reconstruct_ragged_normalized_device(self._h, rect_array(rects) if rects is not None else None, out_width, out_height, channels,
+                                                                      C.byref(fmt), dst_ptr or None, image_stride, plane_stride, row_stride, flags, status,
+                                                                      1 if sync else 0))
+        return list(status)[:n]
+
+    def ragged_normalized_stats(self) -> dict:
+        """Sample type and mirrored pictures of the object's last resized or normalised call (mijpeg_ragged_normalized_stats)."""
+        st = MijpegRaggedNormalizedStats()
+        self._check(lib().mijpeg_ragged_normalized_stats_get(self._h, C.byref(st)))
+        return dict(sample=int(st.sample), mirrored=int(st.mirrored))
 
     def deinterleave_device(self, src_ptr: int, src_row_stride: int, width: int, height: int, components: int, sample_bytes: int, plane_ptrs,
                             row_stride: int):

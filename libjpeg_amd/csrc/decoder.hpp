@@ -156,6 +156,7 @@ struct mijpeg_decoder {
   hipEvent_t resized_uploaded = nullptr;
   bool resized_upload_pending = false;
   mijpeg_ragged_resized_stats resized_stats{};
+  mijpeg_ragged_normalized_stats normalized_stats{}; // (the normalised call's sample type and mirrored pictures: set wherever resized_stats is)
   // ragged encode (encode_device.cpp): descriptors, coder arrays and coefficient store of a pass; plain stream and output arena;
   // pinned: descriptors on their way up and counts read back; the downloaded arena
   uint8_t *eragged_dev = nullptr, *eragged_out_dev = nullptr, *eragged_host = nullptr, *eragged_down = nullptr;

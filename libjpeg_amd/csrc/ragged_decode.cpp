@@ -3,6 +3,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 
 #include "fused_list.hpp"
@@ -571,8 +572,12 @@ try {
 } // extern "C"
 
 // ------------------------------------------------------------------------------------------------
-// crops resized into one batch tensor (include/mijpeg.h)
+// crops resized into one batch tensor (include/mijpeg.h), and the same as a normalised float batch, mirrored per
+// picture: one driver, the resized call is its {uint8 samples, nobody mirrored}
 // ------------------------------------------------------------------------------------------------
+static_assert(MIJPEG_SAMPLE_U8 == RESAMPLE_U8 && MIJPEG_SAMPLE_F32 == RESAMPLE_F32 && MIJPEG_SAMPLE_F16 == RESAMPLE_F16 && MIJPEG_SAMPLE_BF16 == RESAMPLE_BF16,
+              "the header's sample types are the kernels'");
+
 // Why the resized call does not serve a decoded picture, or 0
 static int resized_refusal(const mijpeg_info &f, int32_t channels)
 {
@@ -583,8 +588,8 @@ static int resized_refusal(const mijpeg_info &f, int32_t channels)
 }
 
 // Stage 2: the tables of the served pictures in one pinned upload, and the one launch
-static int launch_resample(mijpeg_decoder *d, const ResampleItem *items, const ResampleLayout &L, int32_t out_w, int32_t out_h, int32_t channels, void *dst,
-                           int64_t image_stride, int64_t plane_stride, int64_t row_stride)
+static int launch_resample(mijpeg_decoder *d, const ResampleItem *items, const ResampleLayout &L, int32_t out_w, int32_t out_h, int32_t channels,
+                           const mijpeg_batch_format &format, void *dst, int64_t image_stride, int64_t plane_stride, int64_t row_stride)
 {
   int rc = ensure_dev(d, (void **)&d->resized_desc_dev, &d->resized_desc_cap, L.table_bytes);
   if (rc) return rc;
@@ -616,25 +621,36 @@ static int launch_resample(mijpeg_decoder *d, const ResampleItem *items, const R
   a.served = served;
   a.out_w = out_w; a.out_h = out_h; a.channels = channels;
   a.plane_stride = (uint32_t)plane_stride; a.row_stride = (uint32_t)row_stride;
-  if (launch_resample_list(a, (unsigned)L.workgroups, d->stream))
+  if (format.sample != MIJPEG_SAMPLE_U8)
+    for (int c = 0; c < channels; c++) { a.scale[c] = format.scale[c]; a.bias[c] = format.bias[c]; }
+  if (launch_resample_list(a, format.sample, (unsigned)L.workgroups, d->stream))
     return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
   return MIJPEG_OK;
 }
 
-static int reconstruct_ragged_resized(mijpeg_decoder *d, const mijpeg_rect *rects, int32_t out_w, int32_t out_h, int32_t channels, void *dst, int64_t image_stride,
-                                      int64_t plane_stride, int64_t row_stride, uint32_t flags, int32_t *status, int sync)
+static int reconstruct_ragged_resized(mijpeg_decoder *d, const mijpeg_rect *rects, int32_t out_w, int32_t out_h, int32_t channels, const mijpeg_batch_format *format,
+                                      void *dst, int64_t image_stride, int64_t plane_stride, int64_t row_stride, uint32_t flags, int32_t *status, int sync)
 {
   if (!d || !dst) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (!format) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "normalised call: format is NULL");
   if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
   if (d->ragged_n < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded ragged batch: call mijpeg_decode_ragged_device first");
   const int n = d->ragged_n;
   // every parameter, before anything is launched, written or counted
   if (out_w < 1 || out_h < 1 || out_w > RESAMPLE_MAX_AXIS || out_h > RESAMPLE_MAX_AXIS) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "resized call: out_width and out_height are 1 .. 65535");
   if (channels != 1 && channels != 3) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "resized call: channels is 1 or 3");
+  if (format->sample < MIJPEG_SAMPLE_U8 || format->sample > MIJPEG_SAMPLE_BF16 || format->reserved != 0)
+    return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "normalised call: sample is a MIJPEG_SAMPLE_*, reserved is 0");
+  if (format->sample != MIJPEG_SAMPLE_U8)
+    for (int c = 0; c < channels; c++)
+      if (!std::isfinite(format->scale[c]) || !std::isfinite(format->bias[c])) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "normalised call: scale and bias are finite");
+  const int64_t es = (int64_t)resample_sample_bytes(format->sample); // (every stride is in bytes)
+  if ((uintptr_t)dst % (uintptr_t)es || image_stride % es || plane_stride % es || row_stride % es)
+    return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "normalised call: dst_device and the strides are multiples of the element size");
   const bool planar = plane_stride != 0;
   if (row_stride < 1 || row_stride > 0xffffffffll || plane_stride < 0 || plane_stride > 0xffffffffll) // (what follows then stays inside 64 bits)
     return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "resized call: a stride is smaller than the data it spans, or a slot spans 4 GiB or more");
-  const int64_t line = (int64_t)out_w * (planar ? 1 : channels), plane = (int64_t)(out_h - 1) * row_stride + line;
+  const int64_t line = (int64_t)out_w * (planar ? 1 : channels) * es, plane = (int64_t)(out_h - 1) * row_stride + line;
   const int64_t slot = planar ? (int64_t)(channels - 1) * plane_stride + plane : plane;
   if (row_stride < line || (planar && plane_stride < plane) || image_stride < slot || slot > 0xffffffffll)
     return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "resized call: a stride is smaller than the data it spans, or a slot spans 4 GiB or more");
@@ -659,6 +675,7 @@ static int reconstruct_ragged_resized(mijpeg_decoder *d, const mijpeg_rect *rect
     it.src_w = win[(size_t)i].max_x - win[(size_t)i].min_x + 1;
     it.src_h = win[(size_t)i].max_y - win[(size_t)i].min_y + 1;
     it.comps = r.info.components;
+    it.mirror = format->mirror && format->mirror[i];
     if ((uint64_t)it.src_w * (uint64_t)it.src_h * (uint64_t)it.comps > 0xffffffffull) { st[(size_t)i] = MIJPEG_ERR_NOT_IMPLEMENTED; continue; } // (the kernel's 32-bit offsets)
     it.served = true;
   }
@@ -678,6 +695,9 @@ static int reconstruct_ragged_resized(mijpeg_decoder *d, const mijpeg_rect *rect
   stats.resampled = (int32_t)L.per.size();
   stats.refused = n - stats.resampled;
   stats.arena_bytes = (int64_t)L.arena_bytes;
+  mijpeg_ragged_normalized_stats nstats{};
+  nstats.sample = format->sample;
+  for (const ResampleLayout::Per &p : L.per) nstats.mirrored += items[(size_t)p.item].mirror ? 1 : 0;
   if (!L.per.empty()) {
     // stage 1: the crop call's body, destinations in the arena (its statistics stay the last crop call's)
     const int rc = ensure_dev(d, (void **)&d->resized_arena_dev, &d->resized_arena_cap, L.arena_bytes + RESAMPLE_ARENA_SPARE);
@@ -694,11 +714,12 @@ static int reconstruct_ragged_resized(mijpeg_decoder *d, const mijpeg_rect *rect
     d->rect_stats = kept;
     if (rc1) return rc1;
     // stage 2: one launch for the list
-    const int rc2 = launch_resample(d, items.data(), L, out_w, out_h, channels, dst, image_stride, plane_stride, row_stride);
+    const int rc2 = launch_resample(d, items.data(), L, out_w, out_h, channels, *format, dst, image_stride, plane_stride, row_stride);
     if (rc2) return rc2;
     stats.resample_launches = 1;
   }
   d->resized_stats = stats;
+  d->normalized_stats = nstats;
   if (status)
     for (int i = 0; i < n; i++) status[i] = st[(size_t)i];
   if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
@@ -710,8 +731,23 @@ extern "C" {
 int mijpeg_reconstruct_ragged_resized_device(mijpeg_decoder *d, const mijpeg_rect *rects, int32_t out_width, int32_t out_height, int32_t channels, void *dst_device,
                                              int64_t image_stride, int64_t plane_stride, int64_t row_stride, uint32_t flags, int32_t *status, int sync)
 try {
-  return reconstruct_ragged_resized(d, rects, out_width, out_height, channels, dst_device, image_stride, plane_stride, row_stride, flags, status, sync);
+  static const mijpeg_batch_format plain = {MIJPEG_SAMPLE_U8, 0, {0, 0, 0}, {0, 0, 0}, nullptr};
+  return reconstruct_ragged_resized(d, rects, out_width, out_height, channels, &plain, dst_device, image_stride, plane_stride, row_stride, flags, status, sync);
 } catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_resized_device"); }
+
+int mijpeg_reconstruct_ragged_normalized_device(mijpeg_decoder *d, const mijpeg_rect *rects, int32_t out_width, int32_t out_height, int32_t channels,
+                                                const mijpeg_batch_format *format, void *dst_device, int64_t image_stride, int64_t plane_stride, int64_t row_stride,
+                                                uint32_t flags, int32_t *status, int sync)
+try {
+  return reconstruct_ragged_resized(d, rects, out_width, out_height, channels, format, dst_device, image_stride, plane_stride, row_stride, flags, status, sync);
+} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_ragged_normalized_device"); }
+
+int mijpeg_ragged_normalized_stats_get(mijpeg_decoder *d, mijpeg_ragged_normalized_stats *out)
+try {
+  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
+  *out = d->normalized_stats;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_ragged_normalized_stats_get"); }
 
 int mijpeg_ragged_resized_stats_get(mijpeg_decoder *d, mijpeg_ragged_resized_stats *out)
 try {

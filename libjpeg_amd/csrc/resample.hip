@@ -12,6 +12,11 @@
 // loaded without a loop -- 3, 5 or 8 of them, by the axis's maximal count, a three-component pixel in one unaligned word, which is
 // why the arena ends in 16 spare bytes.
 // Stores are contiguous along x: a wave writes 64 neighbouring pixels of one line.
+//
+// The normalised flavours are the same text up to round8(acc): their store epilogue maps the 8-bit sample v to
+// fl32(fl32((float)v * scale[c]) + bias[c]) -- two roundings, never a fused multiply-add -- and stores it as binary32, binary16 or
+// bfloat16.  A mirrored picture is a matter of its x table (resample_taps.hpp): no kernel here knows the flag.
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include "resample.hpp"
@@ -55,7 +60,35 @@ __device__ __forceinline__ unsigned filter_row(const uint8_t *__restrict__ row, 
   return packed;
 }
 
-template <int SC>
+// The normalised call's float value of the 8-bit sample v: a product and a sum, each rounded to nearest-even.  A contracted fma would
+// round once, and the header's __fmul_rn / __fadd_rn are plain operators the compiler may contract: so the operators stand here,
+// under the pragma that forbids it
+__device__ __forceinline__ float normalized(int v, float scale, float bias)
+{
+#pragma clang fp contract(off)
+  const float product = (float)v * scale;
+  return product + bias;
+}
+
+// One sample of the destination, OUT a MIJPEG_SAMPLE_* of include/mijpeg.h: the 8-bit sample itself, or its float value in the
+// stored type
+template <int OUT>
+__device__ __forceinline__ void store_sample(uint8_t *__restrict__ at, int v, float scale, float bias)
+{
+  if (OUT == RESAMPLE_U8) {
+    *at = (uint8_t)v;
+    return;
+  }
+  const float y = normalized(v, scale, bias);
+  if (OUT == RESAMPLE_F32) *reinterpret_cast<float *>(at) = y;
+  else if (OUT == RESAMPLE_F16) *reinterpret_cast<unsigned short *>(at) = __half_as_ushort(__float2half_rn(y));
+  else {
+    const unsigned bits = __float_as_uint(y); // (to nearest-even on the upper 16 bits, as torch's conversion has it for finite values)
+    *reinterpret_cast<unsigned short *>(at) = (unsigned short)((bits + 0x7fffu + ((bits >> 16) & 1u)) >> 16);
+  }
+}
+
+template <int SC, int OUT>
 __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const ResamplePicture &p, unsigned tx, unsigned ty, unsigned (*px)[TW], int16_t (*wy)[SH])
 {
   constexpr int KR = RESAMPLE_REG_TAPS;
@@ -139,9 +172,10 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const Resam
     __syncthreads();
   }
   if (!xin) return;
-  // 64-bit base of the slot, 32-bit offsets inside it
+  // 64-bit base of the slot, 32-bit byte offsets inside it
+  constexpr unsigned ES = OUT == RESAMPLE_U8 ? 1u : OUT == RESAMPLE_F32 ? 4u : 2u;
   uint8_t *__restrict__ out = a.dst + p.dst_off;
-  const unsigned cstep = a.plane_stride ? a.plane_stride : 1u, pix = a.plane_stride ? 1u : (unsigned)a.channels;
+  const unsigned cstep = a.plane_stride ? a.plane_stride : ES, pix = (a.plane_stride ? 1u : (unsigned)a.channels) * ES;
 #pragma unroll
   for (int j = 0; j < 4; j++) {
     const int oy = oy0 + (int)g * 4 + j;
@@ -149,36 +183,59 @@ __device__ __forceinline__ void resample_tile(const ResampleArgs &a, const Resam
     const unsigned at = (unsigned)oy * a.row_stride + (unsigned)ox * pix;
     if (SC == 3) {
 #pragma unroll
-      for (int c = 0; c < SC; c++) out[at + (unsigned)c * cstep] = (uint8_t)round8(acc[j][c]);
-    } else {
+      for (int c = 0; c < SC; c++) store_sample<OUT>(out + (at + (unsigned)c * cstep), round8(acc[j][c]), a.scale[c], a.bias[c]);
+    } else if (OUT == RESAMPLE_U8) {
       const uint8_t v = (uint8_t)round8(acc[j][0]);
       for (int c = 0; c < a.channels; c++) out[at + (unsigned)c * cstep] = v; // (a grey picture in a 3-channel batch: all three)
+    } else {
+      const int v = round8(acc[j][0]);
+#pragma unroll
+      for (int c = 0; c < 3; c++) // (... each with its channel's constants, which stay in scalar registers: no indexed access)
+        if (c < a.channels) store_sample<OUT>(out + (at + (unsigned)c * cstep), v, a.scale[c], a.bias[c]);
     }
   }
 }
 
-__global__ __launch_bounds__(RESAMPLE_GROUP) void resample_list_kernel(ResampleArgs a)
-{
-  __shared__ unsigned px[SH][TW];                         // the strip behind the horizontal pass
-  __shared__ __attribute__((aligned(16))) int16_t wy[TH][SH]; // its vertical weights per output line of the tile
-  const unsigned wg = blockIdx.x;
-  const uint32_t *__restrict__ first = a.first;
-  unsigned lo = 0, hi = (unsigned)a.served; // first[lo] <= wg < first[hi]
-  while (hi - lo > 1) {
-    const unsigned mid = (lo + hi) >> 1;
-    if (first[mid] <= wg) lo = mid;
-    else hi = mid;
-  }
-  const ResamplePicture p = a.pictures[lo];
-  const unsigned local = wg - first[lo], ty = local / (unsigned)p.tiles_x, tx = local - ty * (unsigned)p.tiles_x;
-  if (p.comps == 3) resample_tile<3>(a, p, tx, ty, px, wy);
-  else resample_tile<1>(a, p, tx, ty, px, wy);
-}
+// A workgroup's frame around resample_tile, the text both kernels below share: its picture from the prefix table of first workgroups
+// (wave-uniform loads, a binary search), its tile in it, the tile by the picture's components.  A macro and no function template:
+// through a function the uint8 kernel compiles to the same number of instructions in another order and with other registers, and it
+// is to stay, instruction for instruction, the kernel profiles/ragged_resized.txt measured
+#define RESAMPLE_WORKGROUP(OUT)                                                                                                   \
+  __shared__ unsigned px[SH][TW];                             /* the strip behind the horizontal pass */                           \
+  __shared__ __attribute__((aligned(16))) int16_t wy[TH][SH]; /* its vertical weights per output line of the tile */               \
+  const unsigned wg = blockIdx.x;                                                                                                  \
+  const uint32_t *__restrict__ first = a.first;                                                                                    \
+  unsigned lo = 0, hi = (unsigned)a.served; /* first[lo] <= wg < first[hi] */                                                      \
+  while (hi - lo > 1) {                                                                                                            \
+    const unsigned mid = (lo + hi) >> 1;                                                                                           \
+    if (first[mid] <= wg) lo = mid;                                                                                                \
+    else hi = mid;                                                                                                                 \
+  }                                                                                                                                \
+  const ResamplePicture p = a.pictures[lo];                                                                                        \
+  const unsigned local = wg - first[lo], ty = local / (unsigned)p.tiles_x, tx = local - ty * (unsigned)p.tiles_x;                  \
+  if (p.comps == 3) resample_tile<3, OUT>(a, p, tx, ty, px, wy);                                                                   \
+  else resample_tile<1, OUT>(a, p, tx, ty, px, wy);
 
-int launch_resample_list(const ResampleArgs &a, unsigned grid, hipStream_t stream)
+__global__ __launch_bounds__(RESAMPLE_GROUP) void resample_list_kernel(ResampleArgs a) { RESAMPLE_WORKGROUP(RESAMPLE_U8) }
+
+// The normalised call's float flavours: OUT is RESAMPLE_F32, RESAMPLE_F16 or RESAMPLE_BF16
+template <int OUT>
+__global__ __launch_bounds__(RESAMPLE_GROUP) void resample_list_normalized_kernel(ResampleArgs a) { RESAMPLE_WORKGROUP(OUT) }
+#undef RESAMPLE_WORKGROUP
+
+int launch_resample_list(const ResampleArgs &a, int sample, unsigned grid, hipStream_t stream)
 {
   if (!grid) return 0;
-  hipLaunchKernelGGL(resample_list_kernel, dim3(grid), dim3(RESAMPLE_GROUP), 0, stream, a);
+  // the one place a kernel is chosen: the uint8 kernel serves the resized call and the normalised call's uint8 samples
+  void (*kernel)(ResampleArgs) = nullptr;
+  switch (sample) {
+  case RESAMPLE_U8: kernel = resample_list_kernel; break;
+  case RESAMPLE_F32: kernel = resample_list_normalized_kernel<RESAMPLE_F32>; break;
+  case RESAMPLE_F16: kernel = resample_list_normalized_kernel<RESAMPLE_F16>; break;
+  case RESAMPLE_BF16: kernel = resample_list_normalized_kernel<RESAMPLE_BF16>; break;
+  default: return (int)hipErrorInvalidValue; // (a missing kernel is an error)
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(RESAMPLE_GROUP), 0, stream, a);
   return (int)hipGetLastError();
 }
 

@@ -117,6 +117,7 @@ struct ResampleItem {
   int32_t slot = 0;          // its index in the list = its slot in the destination
   int32_t src_w = 0, src_h = 0, comps = 0;
   int32_t xcap = 0, ycap = 0; // the axes' maximal tap counts where the caller has them (resample_item_caps: one picture per worker); 0: resample_layout counts
+  bool mirror = false;       // its slot holds the lines reversed (resize, then flip): resample_fill reverses the x table's columns
 };
 inline void resample_item_caps(ResampleItem &it, int32_t out_w, int32_t out_h)
 {
@@ -166,8 +167,22 @@ inline ResampleLayout resample_layout(const ResampleItem *items, int n, int32_t 
   return L;
 }
 
+// An axis table's columns in reverse order: output o carries first, count and the weights of output m - 1 - o.  The kernel reads a
+// column's run as it stands and stores along x as ever, so a picture filled this way comes out mirrored without the kernel knowing.
+inline void resample_mirror_axis(int32_t *first, int32_t *count, int16_t *weights, int32_t m, int32_t cap)
+{
+  for (int32_t o = 0, r = m - 1; o < r; o++, r--) {
+    const int32_t f = first[o], c = count[o];
+    first[o] = first[r]; count[o] = count[r];
+    first[r] = f; count[r] = c;
+    int16_t *a = weights + (size_t)o * (size_t)cap, *b = weights + (size_t)r * (size_t)cap;
+    for (int32_t t = 0; t < cap; t++) { const int16_t k = a[t]; a[t] = b[t]; b[t] = k; }
+  }
+}
+
 // The tables of served picture k into host (table_bytes of it); k == 0 also writes nothing else: resample_fill_first closes the prefix
-// table.  false where an axis has no taps (sizes resample_taps refuses)
+// table.  A mirrored item's x table is filled in reverse; its y table is what it would be without the flag.  false where an axis has
+// no taps (sizes resample_taps refuses)
 inline bool resample_fill(uint8_t *host, const ResampleLayout &L, size_t k, const ResampleItem *items, int32_t out_w, int32_t out_h, int64_t image_stride)
 {
   const ResampleLayout::Per &p = L.per[k];
@@ -181,8 +196,11 @@ inline bool resample_fill(uint8_t *host, const ResampleLayout &L, size_t k, cons
   d.xcap = p.xcap; d.ycap = p.ycap;
   ((uint32_t *)(host + L.first))[k] = p.first_workgroup;
   int32_t *xt = (int32_t *)(host + p.xtab), *yt = (int32_t *)(host + p.ytab);
-  return resample_taps(it.src_w, out_w, xt, xt + out_w, (int16_t *)(xt + 2 * (size_t)out_w), p.xcap) == p.xcap && p.xcap > 0 &&
-         resample_taps(it.src_h, out_h, yt, yt + out_h, (int16_t *)(yt + 2 * (size_t)out_h), p.ycap) == p.ycap && p.ycap > 0;
+  if (!(resample_taps(it.src_w, out_w, xt, xt + out_w, (int16_t *)(xt + 2 * (size_t)out_w), p.xcap) == p.xcap && p.xcap > 0 &&
+        resample_taps(it.src_h, out_h, yt, yt + out_h, (int16_t *)(yt + 2 * (size_t)out_h), p.ycap) == p.ycap && p.ycap > 0))
+    return false;
+  if (it.mirror) resample_mirror_axis(xt, xt + out_w, (int16_t *)(xt + 2 * (size_t)out_w), out_w, p.xcap);
+  return true;
 }
 inline void resample_fill_first(uint8_t *host, const ResampleLayout &L) { ((uint32_t *)(host + L.first))[L.per.size()] = (uint32_t)L.workgroups; }
 
