@@ -967,6 +967,68 @@ int mijpeg_encode_planar_stats_get(mijpeg_decoder *d, mijpeg_encode_planar_stats
 int mijpeg_interleave_device(mijpeg_decoder *d, const void *const planes[MIJPEG_MAX_COMPONENTS], int64_t plane_row_stride, int32_t width,
                              int32_t height, int32_t components, int32_t sample_bytes, void *dst_device, int64_t dst_row_stride, int sync);
 
+/* ---- ragged transcode: decoded lists recoded from their coefficients in HBM -------------------------------
+ * The pictures of the object's last mijpeg_decode_ragged_device / ...16 call, coded again as baseline (8 bit) or extended sequential
+ * (12 bit) Huffman streams from the quantised planes the decode left in device memory: no inverse transform, no pixels, no second
+ * generation of DCT loss.  Per picture the source's quantiser tables are kept -- the recode is lossless: the output decodes to the
+ * source's coefficients -- or replaced by those of a quality, the planes requantised in the coefficient domain by ONE launch per pass
+ * of requant_list_kernel.  The rule, in integers, for coefficient c at position k with source entry a and target entry b:
+ *   v = c * a;  r = sign(v) * floor((|v| + floor(b / 2)) / b)            (to nearest, halves away from zero; b == a gives r == c)
+ * r outside what a frame of the picture's precision P codes -- DC in [-2^(P+2), 2^(P+2) - 1], |AC| <= 2^(P+2) - 1 -- refuses the
+ * picture with MIJPEG_ERR_OVERFLOW_PARAMETER; kept pictures pass the same check (a crafted stream's own planes may lie outside).
+ * The passes are those of the ragged encode with the requant launch in place of the forward launches: launches and host waits do
+ * not grow with the list, MIJPEG_ENCODE_RAGGED_PASS_BLOCKS cuts them, 12-bit pictures always get Huffman tables of their own and
+ * `optimize` speaks for the 8-bit ones.  The outputs carry the headers every encoder call here writes (DQT, SOF0 / SOF1, DHT, DRI,
+ * SOS): APPn, COM and ICC segments of the source are NOT carried across.  Sampling and size never change; the output is never
+ * progressive or arithmetic coded (a progressive source comes out sequential).
+ * Served: members of the layout groups, and pictures of the single-image route whose object holds int16 planes of a plain Huffman
+ * frame of 8 or 12 bits with 1 or 3 components (progressive, SOF1, DNL, 4:4:0, 4:1:1, ...).  A one-component output has sampling
+ * factors 1 x 1 whatever the source's header said.  status[i] per picture, the others are served:
+ *   MIJPEG_ERR_NOT_IMPLEMENTED      JPEG XT, 2 or 4 components, 32-bit planes (coef_wide), a table entry of 0, or a kept 8-bit picture with
+ *                                   a table entry above 255 (no baseline DQT holds it)
+ *   MIJPEG_ERR_NOT_AVAILABLE        more blocks per MCU than the device entropy coder takes, or 2^30 blocks or more
+ *   MIJPEG_ERR_OVERFLOW_PARAMETER   a requantised (or kept) value outside the coding range
+ *   the decode's status             where the decode of the picture failed
+ * streams[i] / sizes[i]: malloc'ed (mijpeg_free); NULL / 0 for a picture that is refused or skipped.  The decode's stores stay as
+ * they are: reconstruction calls may precede or follow.  Arguments are checked before a device is touched: NULL lists or flags != 0,
+ * a quality outside -1 .. 100 or a restart interval outside -1 .. 65535 are MIJPEG_ERR_INVALID_PARAMETER; an object without a device
+ * MIJPEG_ERR_NOT_AVAILABLE; without a decoded ragged batch MIJPEG_ERR_OBJECT_DOESNT_EXIST.  On a failure of the call all streams[i]
+ * are NULL and all sizes[i] 0. */
+#define MIJPEG_TRANSCODE_KEEP 0     /* quality: the source's quantiser tables (lossless recode) */
+#define MIJPEG_TRANSCODE_SKIP (-1)  /* quality: no stream for this picture, status MIJPEG_OK    */
+typedef struct mijpeg_transcode_spec {
+  int32_t quality;           /* 1..100 as mijpeg_quality_tables takes it (at precision 12: entries to 32767), KEEP or SKIP */
+  int32_t restart_interval;  /* MCUs per restart interval 0..65535, or -1: the source's                                    */
+} mijpeg_transcode_spec;
+/* specs: one per picture of the decoded batch, or NULL: keep everything (tables and restart intervals). */
+int mijpeg_transcode_ragged_device(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int optimize, uint32_t flags, uint8_t **streams,
+                                   size_t *sizes, int32_t *status);
+/* What the object's last transcode call did. */
+typedef struct mijpeg_transcode_ragged_stats {
+  int32_t pictures;          /* of the decoded batch                                                                           */
+  int32_t served;            /* pictures with a stream                                                                         */
+  int32_t kept;              /* ... of them with the source's tables                                                           */
+  int32_t refused;           /* pictures with a status: the decode's, a refusal of the plan, the range check                   */
+  int32_t children;          /* served pictures of the single-image route                                                      */
+  int32_t passes;
+  int32_t requant_launches;  /* one per pass                                                                                   */
+  int32_t coder_launches;    /* as mijpeg_encode_ragged_stats counts them                                                      */
+  int32_t host_syncs;        /* per pass: plain sizes (the range flags travel with them), 0xFF counts, download, one more for the
+                                statistics of pictures with tables of their own.  Waiting for a child's own stream, once per child
+                                in front of the first pass, is not counted                                                     */
+  int32_t child_uploads;     /* children whose planes were decoded on the host and travelled to the device for this            */
+  int64_t bytes_downloaded;  /* the output arenas                                                                              */
+} mijpeg_transcode_ragged_stats;
+int mijpeg_transcode_ragged_stats_get(mijpeg_decoder *d, mijpeg_transcode_ragged_stats *out);
+/* The plan of one picture, no device and no object: source frame + spec -> the output frame (layout, tables, quant_index), its
+ * restart interval, kept (1: the source's tables).  Returns the picture's status as above (MIJPEG_OK for SKIP: *out zeroed);
+ * MIJPEG_ERR_INVALID_PARAMETER for NULL arguments and a spec outside its ranges.  *out is zeroed on every refusal. */
+int mijpeg_transcode_plan(const mijpeg_info *source, const mijpeg_transcode_spec *spec, mijpeg_info *out, int32_t *restart_interval, int32_t *kept);
+/* The rule over n blocks (64 coefficients each, natural order) in host memory: src -> dst (may be the same) with source table
+ * q_old and target table q_new (no entry 0), clamped into the coding range of `precision` (8 or 12).  Returns the number of
+ * coefficients that were clamped, or MIJPEG_ERR_INVALID_PARAMETER.  The kernel's host twin: one header states the rule for both. */
+int64_t mijpeg_requantize(const int16_t *src, int16_t *dst, int64_t n, const uint16_t q_old[64], const uint16_t q_new[64], int precision);
+
 /* Worker threads mijpeg_decode_coefficients uses for threads <= 0 (MIJPEG_THREADS overrides; default min(cores, 64)). */
 int mijpeg_default_threads(void);
 

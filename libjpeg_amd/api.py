@@ -30,6 +30,7 @@ FLAG_FORCE_DOT2 = 64  # (testing) the packed 4:2:0 kernel's 16-bit second pass w
 ERR_DEVICE = -8191
 ERR_NOT_AVAILABLE = -1029
 ERR_INVALID_PARAMETER = -1024
+ERR_OVERFLOW_PARAMETER = -1028
 ERR_NOT_IMPLEMENTED = -1034  # MIJPEG_ERR_NOT_IMPLEMENTED (= MIJPEG_ERR_OPERATION_UNIMPLEMENTED)
 
 
@@ -142,6 +143,18 @@ class MijpegEncodePlanarStats(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("pictures", "fused", "two_pass", "own_plane", "interleave_launches", "reserved")]
 
 
+class MijpegTranscodeSpec(C.Structure):
+    _fields_ = [("quality", C.c_int32), ("restart_interval", C.c_int32)]
+
+
+class MijpegTranscodeRaggedStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("pictures", "served", "kept", "refused", "children", "passes", "requant_launches", "coder_launches", "host_syncs",
+                                         "child_uploads")] + [("bytes_downloaded", C.c_int64)]
+
+
+TRANSCODE_KEEP, TRANSCODE_SKIP = 0, -1  # mijpeg_transcode_spec.quality: the source's tables; no stream for this picture
+
+
 # sampling factors (hsamp, vsamp) per component of the layouts the encoder takes by name
 ENCODE_LAYOUTS = {"444": ((1, 1, 1), (1, 1, 1)), "420": ((2, 1, 1), (2, 1, 1)), "422": ((2, 1, 1), (1, 1, 1)), "440": ((1, 1, 1), (2, 1, 1)),
                   "411": ((4, 1, 1), (1, 1, 1))}
@@ -245,6 +258,12 @@ def lib():
         L.mijpeg_encode_ragged_planar_device16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
         L.mijpeg_encode_planar_stats_get.argtypes = [C.c_void_p, P(MijpegEncodePlanarStats)]
         L.mijpeg_interleave_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int]
+        if hasattr(L, "mijpeg_transcode_ragged_device"):  # (MIJPEG_LIBRARY may name a build from before the ragged transcode: its calls then fail by name)
+            L.mijpeg_transcode_ragged_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.mijpeg_transcode_ragged_stats_get.argtypes = [C.c_void_p, P(MijpegTranscodeRaggedStats)]
+            L.mijpeg_transcode_plan.argtypes = [P(MijpegInfo), P(MijpegTranscodeSpec), P(MijpegInfo), P(C.c_int32), P(C.c_int32)]
+            L.mijpeg_requantize.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
+            L.mijpeg_requantize.restype = C.c_int64
         L.mijpeg_free.argtypes = [C.c_void_p]
         L.mijpeg_free.restype = None
         L.mijpeg_set_device_markers.argtypes = [C.c_void_p, C.c_int]
@@ -555,6 +574,32 @@ class Decoder:
         st = MijpegEncodeRaggedStats()
         self._check(lib().mijpeg_encode_ragged_get_stats(self._h, C.byref(st)))
         return {k: int(getattr(st, k)) for k, _ in MijpegEncodeRaggedStats._fields_ if k != "reserved"}
+
+    def transcode_ragged_device(self, specs=None, optimize: bool = False):
+        """mijpeg_transcode_ragged_device: the pictures of the last decode_ragged_device call coded again from their quantised planes in
+        HBM.  specs: None (keep every picture's tables and restart interval) or one (quality, restart_interval) per
+        picture -- quality 1..100, TRANSCODE_KEEP or TRANSCODE_SKIP; restart_interval 0..65535 or -1 for the source's.
+        -> (streams, status): bytes or None per picture, and its status code (0 with None: skipped)."""
+        n = getattr(self, "ragged_images", 0)
+        arr = None
+        if specs is not None:
+            specs = list(specs)
+            if len(specs) != n:
+                raise ValueError(f"{len(specs)} specs for the {n} images of the ragged batch")
+            arr = (MijpegTranscodeSpec * max(n, 1))(*[MijpegTranscodeSpec(int(q), int(r)) for q, r in specs])
+        ptrs, sizes, status = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), (C.c_int32 * max(n, 1))()
+        self._check(lib().mijpeg_transcode_ragged_device(self._h, arr, 1 if optimize else 0, 0, ptrs, sizes, status))
+        out = []
+        for i in range(n):
+            out.append(C.string_at(ptrs[i], sizes[i]) if ptrs[i] else None)
+            lib().mijpeg_free(ptrs[i])
+        return out, list(status)[:n]
+
+    def transcode_ragged_stats(self) -> dict:
+        """What the object's last transcode call did (mijpeg_transcode_ragged_stats)."""
+        st = MijpegTranscodeRaggedStats()
+        self._check(lib().mijpeg_transcode_ragged_stats_get(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MijpegTranscodeRaggedStats._fields_}
 
     def xt_params(self) -> MijpegXtParams:
         xt = MijpegXtParams()
@@ -1137,6 +1182,26 @@ def encode_coefficients(info: MijpegInfo, coef: np.ndarray, restart_interval: in
         return C.string_at(p, n.value)
     finally:
         L.mijpeg_free(p)
+
+
+def transcode_plan(source: MijpegInfo, quality: int = TRANSCODE_KEEP, restart_interval: int = -1):
+    """mijpeg_transcode_plan (no device): a decoded picture's frame + spec -> (status, output MijpegInfo, restart interval, kept).
+    status is the picture's refusal or 0; the output frame is zeroed on a refusal and for TRANSCODE_SKIP."""
+    spec, out, ri, kept = MijpegTranscodeSpec(int(quality), int(restart_interval)), MijpegInfo(), C.c_int32(), C.c_int32()
+    rc = lib().mijpeg_transcode_plan(C.byref(source), C.byref(spec), C.byref(out), C.byref(ri), C.byref(kept))
+    return rc, out, ri.value, bool(kept.value)
+
+
+def requantize(blocks: np.ndarray, q_old, q_new, precision: int = 8):
+    """mijpeg_requantize, the host twin of requant_list_kernel: (n, 64) int16 coefficients (natural order) under table q_old ->
+    (the values under q_new, clamped into the coding range of `precision`; how many were clamped)."""
+    src = np.ascontiguousarray(blocks, np.int16).reshape(-1, 64)
+    dst = np.empty_like(src)
+    a, b = np.ascontiguousarray(q_old, np.uint16).reshape(64), np.ascontiguousarray(q_new, np.uint16).reshape(64)
+    clamped = lib().mijpeg_requantize(src.ctypes.data, dst.ctypes.data, src.shape[0], a.ctypes.data, b.ctypes.data, int(precision))
+    if clamped < 0:
+        raise MijpegError(int(clamped), "mijpeg_requantize failed")
+    return dst, int(clamped)
 
 
 RECT_TO_EDGE = 2**31 - 1  # max_x / max_y of a crop: "to the picture's edge"

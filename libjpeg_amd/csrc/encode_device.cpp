@@ -19,6 +19,9 @@
 //               sums, interval bytes, prefix sums -> read-back of the plain sizes (sync) -> layout of the plain buffer, emit,
 //               0xFF counts, prefix sums -> read-back (sync) -> stuffing -> ONE download of the output arena (sync)
 //   assembly    headers in front of every picture's piece, EOI behind it
+// The RAGGED TRANSCODE (mijpeg_transcode_ragged_device) is the same pass with another first stage: the pictures are those
+// of the object's decoded ragged batch, `forward` is ONE launch of requant_list_kernel (requant.hip) from the decode's stores into the
+// pass's coefficient store, its range flags come back with the plain sizes, and a flagged picture's piece is dropped at assembly.
 #include <stdlib.h>
 #include <string.h>
 
@@ -261,6 +264,7 @@ struct EncodePass {
   std::vector<EncTables> tabs; // of the pictures with tables of their own
   std::vector<std::vector<uint8_t>> heads;
   bool timed = false; // MIJPEG_ENCODE_RAGGED_TIME_FORWARD: an event behind the forward launches (encode_passes has one in front)
+  int32_t *status = nullptr; // a transcode pass: of the pass's first picture (a picture refused by its range flag gets no stream)
 
   // arena 1 and its pinned twin; the descriptor tables, one upload
   int descriptors_up()
@@ -280,6 +284,15 @@ struct EncodePass {
   {
     if (launch_forward_ragged(a.forward, stream, &d->eragged_stats.forward_launches)) return hip_fail(d, hipGetLastError(), "ragged forward kernel launch");
     if (timed) HIP_TRY(d, hipEventRecord(d->ev1, stream));
+    return MIJPEG_OK;
+  }
+
+  // a transcode pass's first stage: the planes of all its pictures requantised (or copied, where the tables are kept) into the
+  // pass's coefficient store, range-checked, ONE launch
+  int requant()
+  {
+    if (const int e = launch_requant_list(a.requant, a.requant_grid, stream)) return hip_fail(d, (hipError_t)e, "requant_list_kernel launch");
+    d->transcode_stats.requant_launches++;
     return MIJPEG_OK;
   }
 
@@ -304,6 +317,8 @@ struct EncodePass {
     LAUNCHED(d, henc_gather((const uint64_t *)(dev + L.coder_at + L.coder.istart), a.coder.first_interval, (uint64_t *)(dev + L.d_gather), L.n + 1, stream),
              "henc_gather_kernel launch", 1, launches);
     HIP_TRY(d, hipMemcpyAsync(host + L.h_istart, dev + L.d_gather, ((size_t)L.n + 1) * 8, hipMemcpyDeviceToHost, stream));
+    if (L.sources) // (a transcode pass: the range flags of its requant launch come back with the same wait)
+      HIP_TRY(d, hipMemcpyAsync(host + L.h_flags, dev + L.rq_flags_at, (size_t)L.n * 4, hipMemcpyDeviceToHost, stream));
     return sync_counted(d);
   }
 
@@ -346,6 +361,10 @@ struct EncodePass {
   int assemble()
   {
     for (uint32_t p = 0; p < L.n; p++) {
+      if (L.sources && ((const uint32_t *)(host + L.h_flags))[p]) { // (a value outside the coding range: the clamped planes' piece is dropped)
+        status[p] = MIJPEG_ERR_OVERFLOW_PARAMETER;
+        continue;
+      }
       const StreamPiece piece = stream_piece(host, L, p);
       if (assemble_stream(heads[p], d->eragged_down + piece.at, piece.ecs, &streams[p], &sizes[p]))
         return set_error(d, MIJPEG_ERR_OUT_OF_MEMORY, "out of memory for the stream");
@@ -357,14 +376,16 @@ struct EncodePass {
 // pictures [p0, p1) of the list: one pass.  frames[i].pixels are device addresses; planes: the list's plane table where its pictures
 // came as planes (PlanarList), one entry per picture
 int encode_pass(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const mijpeg_encode_ragged_item *items, int p0, int p1, int optimize,
-                uint8_t **streams, size_t *sizes, const ForwardPlanes *planes = nullptr, bool timed = false)
+                uint8_t **streams, size_t *sizes, const ForwardPlanes *planes = nullptr, bool timed = false, const RequantSource *sources = nullptr,
+                int32_t *status = nullptr)
 {
-  const EncodePassLayout layout(frames, items, p0, p1, optimize, planes);
+  const EncodePassLayout layout(frames, items, p0, p1, optimize, planes, sources);
   if (layout.error) return set_error(d, layout.error, layout.why);
   EncodePass pass{d, layout, streams + p0, sizes + p0};
   pass.timed = timed;
+  pass.status = status ? status + p0 : nullptr;
   int rc = pass.descriptors_up();
-  if (!rc) rc = pass.forward();
+  if (!rc) rc = sources ? pass.requant() : pass.forward();
   if (!rc && layout.n_own) rc = pass.own_tables_up();
   if (!rc) rc = pass.plain_sizes();
   if (!rc) rc = pass.stuffed_sizes();
@@ -581,9 +602,161 @@ int encode_entry(mijpeg_decoder *d, const mijpeg_encode_frame *frames, const int
   return rc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// ragged transcode (include/mijpeg.h): the pictures of the object's decoded ragged batch, coded again from their planes
+// ------------------------------------------------------------------------------------------------
+// The planes of a picture of the single-image route, on the device and at rest: the child decoded on its own stream (a host decode
+// sent its planes up behind it), and this object's stream is about to read them.  Per child: a wait, and the upload where none was made
+int child_planes(mijpeg_decoder *d, mijpeg_decoder *c, const mijpeg_info &f, const int16_t **planes)
+{
+  if (!c->uploaded) {
+    int rc = ensure_coef_store(c, (size_t)f.coef_count, true);
+    if (!rc && hipMemcpyAsync(c->coef_dev, c->coef_host, (size_t)f.coef_count * sizeof(int16_t), hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = MIJPEG_ERR_DEVICE;
+    if (rc) return set_error(d, rc, "upload of a child's coefficient planes");
+    c->uploaded = true;
+  }
+  if (!c->host_planes_stale) d->transcode_stats.child_uploads++;
+  quiesce(c);
+  *planes = c->coef_dev;
+  return MIJPEG_OK;
+}
+
+int transcode_entry(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes, int32_t *status)
+{
+  if (!d || !streams || !sizes || !status || flags != 0) return MIJPEG_ERR_INVALID_PARAMETER;
+  const int n = d->ragged_n;
+  for (int i = 0; i < n; i++) { streams[i] = nullptr; sizes[i] = 0; status[i] = MIJPEG_OK; }
+  for (int i = 0; specs && i < n; i++)
+    if (!transcode_spec_in_order(specs[i]))
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "transcode spec " + std::to_string(i) + ": quality is 1 .. 100, KEEP or SKIP, restart_interval 0 .. 65535 or -1");
+  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
+  if (n < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded ragged batch: call mijpeg_decode_ragged_device first");
+  HIP_TRY(d, hipSetDevice(d->device));
+  const auto t_begin = std::chrono::steady_clock::now();
+  mijpeg_transcode_ragged_stats &stats = d->transcode_stats;
+  stats = mijpeg_transcode_ragged_stats{};
+  stats.pictures = n;
+  // the plan: who is served, every served picture's output frame and its place in the passes
+  const mijpeg_transcode_spec keep{MIJPEG_TRANSCODE_KEEP, -1};
+  std::vector<int> picture; // of served slot k
+  std::vector<mijpeg_encode_frame> frames;
+  std::vector<mijpeg_encode_ragged_item> items;
+  std::vector<RequantSource> sources;
+  std::vector<char> kept;
+  mijpeg_encode_ragged_totals totals;
+  memset(&totals, 0, sizeof(totals));
+  const uint32_t pass_blocks = pass_blocks_setting();
+  PassCutter cut{pass_blocks ? pass_blocks : PASS_BLOCKS_DEFAULT};
+  int rc = MIJPEG_OK;
+  for (int i = 0; i < n && !rc; i++) {
+    const mijpeg_decoder::RaggedImage &r = d->ragged[(size_t)i];
+    const mijpeg_transcode_spec &spec = specs ? specs[i] : keep;
+    if (r.status) { status[i] = r.status; continue; }
+    if (spec.quality == MIJPEG_TRANSCODE_SKIP) continue;
+    if (r.group < 0 && !(r.child && r.child->decoded)) { status[i] = MIJPEG_ERR_NOT_AVAILABLE; continue; }
+    mijpeg_encode_ragged_item it;
+    memset(&it, 0, sizeof(it));
+    int ri = 0;
+    bool keeps = false;
+    if ((status[i] = transcode_plan_one(r.info, spec, it.info, ri, keeps, it.blocks, it.intervals))) continue;
+    RequantSource src{r.info, d->coef_dev + r.coef_base};
+    if (r.group < 0) {
+      if ((rc = child_planes(d, r.child, r.info, &src.planes))) break;
+      stats.children++;
+    }
+    mijpeg_encode_frame e;
+    memset(&e, 0, sizeof(e));
+    e.width = it.info.width; e.height = it.info.height; e.components = it.info.components;
+    for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) { e.hsamp[c] = it.info.hsamp[c]; e.vsamp[c] = it.info.vsamp[c]; }
+    e.quality = spec.quality;
+    e.restart_interval = ri;
+    cut.place(it, &totals);
+    picture.push_back(i);
+    frames.push_back(e);
+    items.push_back(it);
+    sources.push_back(src);
+    kept.push_back(keeps);
+  }
+  // the passes: an encode pass each, its first stage the requant launch (the counters of the last ragged encode stay that call's)
+  const int m = (int)picture.size();
+  std::vector<uint8_t *> out((size_t)m, nullptr);
+  std::vector<size_t> out_size((size_t)m, 0);
+  std::vector<int32_t> out_status((size_t)m, MIJPEG_OK);
+  const mijpeg_encode_ragged_stats encode_stats = d->eragged_stats;
+  d->eragged_stats = mijpeg_encode_ragged_stats{};
+  for (int p0 = 0; p0 < m && !rc;) {
+    int p1 = p0 + 1;
+    while (p1 < m && items[(size_t)p1].pass == items[(size_t)p0].pass) p1++;
+    rc = encode_pass(d, frames.data(), items.data(), p0, p1, optimize, out.data(), out_size.data(), nullptr, false, sources.data(), out_status.data());
+    stats.passes++;
+    p0 = p1;
+  }
+  stats.coder_launches = d->eragged_stats.coder_launches;
+  stats.host_syncs = d->eragged_stats.host_syncs;
+  stats.bytes_downloaded = d->eragged_stats.bytes_downloaded;
+  d->eragged_stats = encode_stats;
+  if (rc) {
+    (void)hipStreamSynchronize(d->stream);
+    drop_streams(out.data(), out_size.data(), m);
+    for (int i = 0; i < n; i++) status[i] = MIJPEG_OK;
+  } else {
+    for (int k = 0; k < m; k++) {
+      const int i = picture[(size_t)k];
+      streams[i] = out[(size_t)k];
+      sizes[i] = out_size[(size_t)k];
+      status[i] = out_status[(size_t)k];
+      if (streams[i]) { stats.served++; stats.kept += kept[(size_t)k]; }
+    }
+    for (int i = 0; i < n; i++) stats.refused += status[i] != MIJPEG_OK;
+  }
+  whole_call_timing(d, t_begin);
+  return rc;
+}
+
 } // namespace
 
 extern "C" {
+
+int mijpeg_transcode_ragged_device(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes,
+                                   int32_t *status)
+try {
+  return transcode_entry(d, specs, optimize, flags, streams, sizes, status);
+} catch (...) {
+  if (d) drop_streams(streams, sizes, d->ragged_n);
+  return boundary_catch(d, "mijpeg_transcode_ragged_device");
+}
+
+int mijpeg_transcode_ragged_stats_get(mijpeg_decoder *d, mijpeg_transcode_ragged_stats *out)
+try {
+  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
+  *out = d->transcode_stats;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_transcode_ragged_stats_get"); }
+
+int mijpeg_transcode_plan(const mijpeg_info *source, const mijpeg_transcode_spec *spec, mijpeg_info *out, int32_t *restart_interval, int32_t *kept)
+try {
+  if (out) memset(out, 0, sizeof(*out));
+  if (restart_interval) *restart_interval = 0;
+  if (kept) *kept = 0;
+  if (!source || !spec || !out || !restart_interval || !kept || !transcode_spec_in_order(*spec)) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (spec->quality == MIJPEG_TRANSCODE_SKIP) return MIJPEG_OK;
+  int ri = 0;
+  bool keeps = false;
+  uint32_t blocks = 0, intervals = 0;
+  const int rc = transcode_plan_one(*source, *spec, *out, ri, keeps, blocks, intervals);
+  if (rc) return rc;
+  *restart_interval = ri;
+  *kept = keeps;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(nullptr, "mijpeg_transcode_plan"); }
+
+int64_t mijpeg_requantize(const int16_t *src, int16_t *dst, int64_t n, const uint16_t q_old[64], const uint16_t q_new[64], int precision)
+try {
+  if (!src || !dst || n < 0 || !q_old || !q_new || (precision != 8 && precision != 12)) return MIJPEG_ERR_INVALID_PARAMETER;
+  for (int k = 0; k < 64; k++)
+    if (!q_old[k] || !q_new[k]) return MIJPEG_ERR_INVALID_PARAMETER;
+  return requantize_blocks(src, dst, n, q_old, q_new, precision);
+} catch (...) { return boundary_catch(nullptr, "mijpeg_requantize"); }
 
 int mijpeg_frame_layout(mijpeg_info *f)
 try {

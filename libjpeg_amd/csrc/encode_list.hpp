@@ -4,7 +4,9 @@
 // arenas), what the one upload holds (fill_upload), the tables the pictures' own statistics give (own_tables), where the pictures
 // lie in the plain buffer (chunk_layout) and in the downloaded arena (arena_bytes, stream_piece).  A list that came as component
 // planes adds a plane table to the pass and a third set of work lists, through defaulted arguments; tests/cxx/
-// encode_list_planar_tables.cpp is their program.  encode_device.cpp enqueues, waits
+// encode_list_planar_tables.cpp is their program.  A pass of the ragged transcode is the same pass with another first
+// stage: transcode_plan_one makes a decoded picture's output frame, and a layout built with `sources` carries the requant work list,
+// descriptors and range flags (requant.hpp) in place of the forward lists; tests/cxx/transcode_tables.cpp.  encode_device.cpp enqueues, waits
 // and copies.  Calls nothing of the HIP runtime: a plain host compiler builds tests/cxx/encode_list_tables.cpp around it and
 // encoder.cpp.  Private to libmijpeg.so.
 #pragma once
@@ -17,6 +19,7 @@
 #include "encoder.hpp"
 #include "forward.hpp"
 #include "hencode.hpp"
+#include "requant.hpp"
 
 namespace mij {
 
@@ -142,20 +145,16 @@ inline int plan_one(const mijpeg_encode_frame &e, int precision, mijpeg_info &f,
 // precision of picture i of a list: the array's entry, 8 without an array
 inline int precision_of(const int32_t *precision, int i) { return precision ? precision[i] : 8; }
 
-// (blocks, intervals, index spaces, pass cuts and coefficient bases do not depend on the precision: coefficients are int16 either way)
-inline int plan_list(const mijpeg_encode_frame *frames, const int32_t *precision, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,
-                     mijpeg_encode_ragged_totals *totals)
-{
-  if (!frames || !items || !totals || n < 1 || pass_blocks > PASS_BLOCKS_MAX) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (pass_blocks == 0) pass_blocks = PASS_BLOCKS_DEFAULT;
-  memset(totals, 0, sizeof(*totals));
+// Where the pictures of a list lie in their passes, one after the other: a picture whose frame, blocks and intervals are known gets
+// its pass, its place in the pass's index spaces and its coefficient base; the totals grow.  The ragged encode and the ragged
+// transcode cut their lists with it.
+struct PassCutter {
+  uint32_t pass_blocks; // (not 0)
   int pass = 0;
   uint64_t at_block = 0, at_interval = 0;
   int64_t at_coef = 0;
-  for (int i = 0; i < n; i++) {
-    mijpeg_encode_ragged_item &it = items[i];
-    memset(&it, 0, sizeof(it));
-    if (const int rc = plan_one(frames[i], precision_of(precision, i), it.info, it.blocks, it.intervals)) return rc;
+  void place(mijpeg_encode_ragged_item &it, mijpeg_encode_ragged_totals *totals)
+  {
     const uint32_t padded = pad256(it.blocks);
     if (at_block > 0 && at_block + padded > pass_blocks) { // (a picture beyond the limit is a pass of its own)
       pass++;
@@ -173,9 +172,85 @@ inline int plan_list(const mijpeg_encode_frame *frames, const int32_t *precision
     totals->intervals += it.intervals;
     totals->coef_count = std::max(totals->coef_count, at_coef);
   }
-  totals->passes = pass + 1;
+};
+
+// (blocks, intervals, index spaces, pass cuts and coefficient bases do not depend on the precision: coefficients are int16 either way)
+inline int plan_list(const mijpeg_encode_frame *frames, const int32_t *precision, int n, uint32_t pass_blocks, mijpeg_encode_ragged_item *items,
+                     mijpeg_encode_ragged_totals *totals)
+{
+  if (!frames || !items || !totals || n < 1 || pass_blocks > PASS_BLOCKS_MAX) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (pass_blocks == 0) pass_blocks = PASS_BLOCKS_DEFAULT;
+  memset(totals, 0, sizeof(*totals));
+  PassCutter cut{pass_blocks};
+  for (int i = 0; i < n; i++) {
+    mijpeg_encode_ragged_item &it = items[i];
+    memset(&it, 0, sizeof(it));
+    if (const int rc = plan_one(frames[i], precision_of(precision, i), it.info, it.blocks, it.intervals)) return rc;
+    cut.place(it, totals);
+  }
+  totals->passes = cut.pass + 1;
   return MIJPEG_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// ragged transcode: the plan of a picture
+// ------------------------------------------------------------------------------------------------
+inline bool transcode_spec_in_order(const mijpeg_transcode_spec &s)
+{
+  return s.quality >= MIJPEG_TRANSCODE_SKIP && s.quality <= 100 && s.restart_interval >= -1 && s.restart_interval <= 65535;
+}
+
+inline bool henc_frame_geometry(HencArgs &a, const mijpeg_info &info, int ri); // (below, with the argument blocks)
+
+// A decoded picture's frame + spec (not SKIP, in order) -> the frame of its output, its restart interval, kept or not, the blocks
+// and intervals of its scan; MIJPEG_OK or the picture's refusal, `out` zeroed.
+//   a quality   what picture_info_of completes for the source's shape, sampling and precision: every component on table 0
+//   kept        the same layout with the source's tables and quant_index, which enc_write_headers writes generally
+// A one-component scan is not interleaved, so its output has sampling factors 1 x 1: the coders walk info.mcus_x * mcus_y blocks.
+inline int transcode_plan_one(const mijpeg_info &src, const mijpeg_transcode_spec &spec, mijpeg_info &out, int &ri, bool &kept, uint32_t &blocks, uint32_t &intervals)
+{
+  auto refuse = [&](int code) { memset(&out, 0, sizeof(out)); return code; };
+  kept = spec.quality == MIJPEG_TRANSCODE_KEEP;
+  ri = spec.restart_interval < 0 ? src.restart_interval : spec.restart_interval;
+  if (src.xt || (src.components != 1 && src.components != 3) || src.coef_wide || (src.precision != 8 && src.precision != 12) || ri < 0 || ri > 65535)
+    return refuse(MIJPEG_ERR_NOT_IMPLEMENTED);
+  int32_t hs[MIJPEG_MAX_COMPONENTS] = {1, 1, 1, 1}, vs[MIJPEG_MAX_COMPONENTS] = {1, 1, 1, 1};
+  int per_mcu = 1;
+  if (src.components == 3) {
+    per_mcu = 0;
+    for (int c = 0; c < 3; c++) {
+      hs[c] = src.hsamp[c];
+      vs[c] = src.vsamp[c];
+      per_mcu += hs[c] * vs[c];
+    }
+  }
+  if (picture_info_of(src.width, src.height, src.components, hs, vs, kept ? 50 : spec.quality, out, src.precision)) return refuse(MIJPEG_ERR_NOT_IMPLEMENTED);
+  for (int c = 0; c < src.components; c++) {
+    if ((unsigned)src.quant_index[c] >= 4 || src.blocks_w[c] < 1 || src.blocks_h[c] < 1) return refuse(MIJPEG_ERR_NOT_IMPLEMENTED);
+    for (int k = 0; k < 64; k++) {
+      const uint16_t a = src.quant[src.quant_index[c]][k];
+      if (a == 0 || (kept && src.precision == 8 && a > 255)) return refuse(MIJPEG_ERR_NOT_IMPLEMENTED); // (no division by it; no baseline DQT holds it)
+    }
+  }
+  if (kept) {
+    memcpy(out.quant, src.quant, sizeof(out.quant));
+    for (int c = 0; c < src.components; c++) out.quant_index[c] = src.quant_index[c];
+  }
+  HencArgs geometry;
+  memset(&geometry, 0, sizeof(geometry));
+  const uint64_t mcus = (uint64_t)out.mcus_x * (uint64_t)out.mcus_y, nb = mcus * (uint64_t)per_mcu;
+  if (!henc_frame_geometry(geometry, out, ri) || nb >= PASS_BLOCKS_MAX) return refuse(MIJPEG_ERR_NOT_AVAILABLE);
+  blocks = (uint32_t)nb;
+  const uint64_t per = ri ? (uint64_t)ri : mcus;
+  intervals = (uint32_t)((mcus + per - 1) / per);
+  return MIJPEG_OK;
+}
+
+// What a transcode pass reads of a picture beside its item: the decoded frame and where its planes lie in device memory
+struct RequantSource {
+  mijpeg_info info;
+  const int16_t *planes;
+};
 
 // ------------------------------------------------------------------------------------------------
 // argument blocks
@@ -364,13 +439,20 @@ struct EncodePassLayout {
   // pinned, behind the upload: what goes up later (first_chunk, own tables) and what comes back (histograms, gathered sums)
   size_t h_first_chunk, h_tables, h_hist, h_istart, h_ffstart, host_bytes;
   size_t hist_bytes;
+  // A pass's first stage is the forward work lists above or, in a transcode pass, the requant work list: `sources` set,
+  // no ForwardArgs are made and no forward list is filled (frames[i] then hold the shape and the restart interval, no pixels).
+  // Its regions are empty in an encode pass, whose offsets and sizes are what they were
+  const RequantSource *sources;           // the pass's first, or null
+  ForwardWorkList requant;                // items (picture * 4 + component) of requant_list_kernel
+  size_t rq_pics_at, rq_first_at, rq_item_at, rq_flags_at; // uploaded: a RequantPicture per picture, the work list, the zeroed range flags (n words)
+  size_t h_flags;                         // pinned: the flags read back
 
   // all_planes: one entry per picture of the list; a planar picture's frame holds plane 0 in `pixels` and the planes' pitch in
   // `row_stride`, its entry planes 1 and 2 (only 8-bit pictures of three components are planar here)
   EncodePassLayout(const mijpeg_encode_frame *all_frames, const mijpeg_encode_ragged_item *all_items, int p0, int p1, int optimize,
-                   const ForwardPlanes *all_planes = nullptr)
+                   const ForwardPlanes *all_planes = nullptr, const RequantSource *all_sources = nullptr)
       : frames(all_frames + p0), items(all_items + p0), n((uint32_t)(p1 - p0)), own_index(n, UINT32_MAX), fargs(n), hargs(n),
-        planes(all_planes ? all_planes + p0 : nullptr)
+        planes(all_planes ? all_planes + p0 : nullptr), sources(all_sources ? all_sources + p0 : nullptr)
   {
     const mijpeg_encode_ragged_item &last = items[n - 1];
     N = last.first_block + pad256(last.blocks);
@@ -378,7 +460,7 @@ struct EncodePassLayout {
     coef_total = last.coef_base + ((last.info.coef_count + 127) & ~(int64_t)127);
     route(optimize);
     Carver up;
-    fargs_at = up.take((size_t)n * sizeof(ForwardArgs));
+    fargs_at = up.take(sources ? 0 : (size_t)n * sizeof(ForwardArgs));
     hargs_at = up.take((size_t)n * sizeof(HencArgs));
     first_block_at = up.take(((size_t)n + 1) * 4);
     first_interval_at = up.take(((size_t)n + 1) * 4);
@@ -388,6 +470,10 @@ struct EncodePassLayout {
     }
     std_tables_at = up.take(sizeof(HencTables));
     planes_at = up.take(n_planar ? (size_t)n * sizeof(ForwardPlanes) : 0);
+    rq_pics_at = up.take(sources ? (size_t)n * sizeof(RequantPicture) : 0);
+    rq_first_at = up.take(requant.first.size() * 4);
+    rq_item_at = up.take(requant.item.size() * 4);
+    rq_flags_at = up.take(sources ? (size_t)n * 4 : 0);
     up_bytes = up.at;
     hist_bytes = (size_t)n_own * HENC_HIST_BYTES;
     coder = coder_layout(N, I);
@@ -405,6 +491,7 @@ struct EncodePassLayout {
     h_hist = hp.take(hist_bytes);
     h_istart = hp.take(((size_t)n + 1) * 8);
     h_ffstart = hp.take(((size_t)n + 1) * 8);
+    h_flags = hp.take(sources ? (size_t)n * 4 : 0);
     host_bytes = hp.at;
   }
   // per picture: tables of its own or not, its ForwardArgs and its items in the work lists, its coder geometry
@@ -413,6 +500,14 @@ struct EncodePassLayout {
     for (uint32_t p = 0; p < n; p++) {
       if (codes_with_own_tables(items[p].info, optimize)) own_index[p] = n_own++;
       const mijpeg_encode_frame &e = frames[p];
+      if (sources) { // a transcode pass: the picture's components in the requant work list, its coder geometry
+        for (int c = 0; c < items[p].info.components; c++)
+          if (!work_list_append(requant, p * 4u + (uint32_t)c, requant_workgroups(items[p].info, c)))
+            return refuse(MIJPEG_ERR_NOT_AVAILABLE, "pass too large for one requant launch");
+        memset(&hargs[p], 0, sizeof(HencArgs));
+        if (!henc_frame_geometry(hargs[p], items[p].info, e.restart_interval)) return refuse(MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU");
+        continue;
+      }
       mijpeg_forward_batch b;
       memset(&b, 0, sizeof(b));
       b.info = items[p].info;
@@ -444,6 +539,8 @@ struct EncodePassLayout {
 struct EncodePassArgs {
   ForwardRaggedPlan forward;
   HencBatchArgs coder; // (plain, ffcount, ffstart, out, total_chunks: once the output arena is there)
+  RequantArgs requant; // a transcode pass: its first stage, and its grid
+  uint32_t requant_grid;
 };
 
 // The uploaded part into `host` (up_bytes of it), with the addresses it will have at `dev`: a ForwardArgs and a HencArgs per
@@ -458,8 +555,13 @@ inline EncodePassArgs fill_upload(uint8_t *host, uint8_t *dev, const EncodePassL
   int16_t *coef = (int16_t *)(dev + L.coef_at);
   for (uint32_t p = 0; p < L.n; p++) {
     const mijpeg_encode_ragged_item &it = L.items[p];
-    hf[p] = L.fargs[p];
-    hf[p].coef = coef + it.coef_base;
+    if (L.sources) {
+      requant_picture_of(((RequantPicture *)(host + L.rq_pics_at))[p], L.sources[p].info, L.sources[p].planes, it.info, coef + it.coef_base);
+      ((uint32_t *)(host + L.rq_flags_at))[p] = 0;
+    } else {
+      hf[p] = L.fargs[p];
+      hf[p].coef = coef + it.coef_base;
+    }
     HencArgs &a = hh[p];
     a = L.hargs[p];
     a.coef = coef + it.coef_base;
@@ -489,6 +591,16 @@ inline EncodePassArgs fill_upload(uint8_t *host, uint8_t *dev, const EncodePassL
   if (L.n_planar) {
     memcpy(host + L.planes_at, L.planes, (size_t)L.n * sizeof(ForwardPlanes));
     a.forward.planes = (const ForwardPlanes *)(dev + L.planes_at);
+  }
+  if (L.sources) {
+    memcpy(host + L.rq_first_at, L.requant.first.data(), L.requant.first.size() * 4);
+    memcpy(host + L.rq_item_at, L.requant.item.data(), L.requant.item.size() * 4);
+    a.requant.pics = (const RequantPicture *)(dev + L.rq_pics_at);
+    a.requant.first_wg = (const uint32_t *)(dev + L.rq_first_at);
+    a.requant.item = (const uint32_t *)(dev + L.rq_item_at);
+    a.requant.items = (uint32_t)L.requant.item.size();
+    a.requant.flags = (uint32_t *)(dev + L.rq_flags_at);
+    a.requant_grid = L.requant.first.back();
   }
   a.coder.pics = (const HencArgs *)(dev + L.hargs_at);
   a.coder.first_block = (const uint32_t *)(dev + L.first_block_at);
