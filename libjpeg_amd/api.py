@@ -390,6 +390,40 @@ class Decoder:
             lib().mijpeg_last_error(self._h, C.byref(msg))
             raise MijpegError(rc, (msg.value or b"").decode())
 
+    def _stats(self, struct, getter, leave_out=()) -> dict:
+        """A statistics struct filled by its getter, as a dict of its integer fields without those in leave_out."""
+        st = struct()
+        self._check(getter(self._h, C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in struct._fields_ if k not in leave_out}
+
+    def _ragged_lengths(self, destinations, row_strides, rects=None) -> int:
+        """The list calls' length check: one destination and row stride (and crop) per image of the ragged batch -> that many."""
+        n, images = len(destinations), getattr(self, "ragged_images", -1)
+        if n != images or len(row_strides) != n or (rects is not None and len(rects) != n):
+            crops = f"{len(rects)} crops, " if rects is not None else ""
+            raise ValueError(f"{crops}{n} destinations and {len(row_strides)} row strides for the {max(images, 0)} images of the ragged batch")
+        return n
+
+    @staticmethod
+    def _pointer_table(ptrs, planar: bool):
+        """The flat c_void_p array of a list call: one pointer per picture, or -- planar -- its plane pointers padded to 4; 0 / None /
+        empty: skipped."""
+        if not planar:
+            return (C.c_void_p * len(ptrs))(*[p or None for p in ptrs])
+        flat = []
+        for p in ptrs:
+            p = list(p or [])
+            flat += [q or None for q in p] + [None] * (4 - len(p))
+        return (C.c_void_p * (4 * len(ptrs)))(*flat)
+
+    def _ragged_call(self, fn, rects, ptrs, planar: bool, row_strides, flags: int, sync: bool, wait_foreign: bool) -> None:
+        """A list reconstruction call of the library: fn(handle, [crops,] destinations, row strides, flags, sync)."""
+        n = self._ragged_lengths(ptrs, row_strides, rects)
+        if wait_foreign:
+            _foreign_work_done()
+        crops = () if rects is None else (rect_array(rects),)
+        self._check(fn(self._h, *crops, self._pointer_table(ptrs, planar), (C.c_int64 * n)(*row_strides), flags, 1 if sync else 0))
+
     def read_header(self, data: bytes) -> MijpegInfo:
         """Tables + frame header (JPEG::Read up to the first scan, then JPEG::GetInformation)."""
         self._data = data  # keep alive: the library borrows the bytes
@@ -544,9 +578,7 @@ class Decoder:
 
     def encode_planar_stats(self) -> dict:
         """What the object's last planar encode did (mijpeg_encode_planar_stats)."""
-        st = MijpegEncodePlanarStats()
-        self._check(lib().mijpeg_encode_planar_stats_get(self._h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in MijpegEncodePlanarStats._fields_ if k != "reserved"}
+        return self._stats(MijpegEncodePlanarStats, lib().mijpeg_encode_planar_stats_get, {"reserved"})
 
     def interleave_device(self, plane_ptrs, plane_row_stride: int, width: int, height: int, components: int, sample_bytes: int, dst_ptr: int,
                           dst_row_stride: int, sync: bool = True):
@@ -571,9 +603,7 @@ class Decoder:
         return self._encode_ragged(lib().mijpeg_encode_ragged16, frames, optimize, precision=[12 if im.itemsize == 2 else 8 for im in imgs])
 
     def encode_ragged_stats(self) -> dict:
-        st = MijpegEncodeRaggedStats()
-        self._check(lib().mijpeg_encode_ragged_get_stats(self._h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in MijpegEncodeRaggedStats._fields_ if k != "reserved"}
+        return self._stats(MijpegEncodeRaggedStats, lib().mijpeg_encode_ragged_get_stats, {"reserved"})
 
     def transcode_ragged_device(self, specs=None, optimize: bool = False):
         """mijpeg_transcode_ragged_device: the pictures of the last decode_ragged_device call coded again from their quantised planes in
@@ -597,9 +627,7 @@ class Decoder:
 
     def transcode_ragged_stats(self) -> dict:
         """What the object's last transcode call did (mijpeg_transcode_ragged_stats)."""
-        st = MijpegTranscodeRaggedStats()
-        self._check(lib().mijpeg_transcode_ragged_stats_get(self._h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in MijpegTranscodeRaggedStats._fields_}
+        return self._stats(MijpegTranscodeRaggedStats, lib().mijpeg_transcode_ragged_stats_get)
 
     def xt_params(self) -> MijpegXtParams:
         xt = MijpegXtParams()
@@ -834,19 +862,10 @@ class Decoder:
     def reconstruct_ragged_device(self, dst_ptrs, row_strides, flags: int = 0, sync: bool = True, wait_foreign: bool = True):
         """mijpeg_reconstruct_ragged_device: image i -> dst_ptrs[i] (0 / None: skipped) with row_strides[i] bytes per line; one entry
         per stream of the decode call (the library walks that many)."""
-        n = len(dst_ptrs)
-        if n != getattr(self, "ragged_images", -1) or len(row_strides) != n:
-            raise ValueError(f"{n} destinations and {len(row_strides)} row strides for the {getattr(self, 'ragged_images', 0)} images of the ragged batch")
-        if wait_foreign:
-            _foreign_work_done()
-        dst = (C.c_void_p * n)(*[p or None for p in dst_ptrs])
-        rows = (C.c_int64 * n)(*row_strides)
-        self._check(lib().mijpeg_reconstruct_ragged_device(self._h, dst, rows, flags, 1 if sync else 0))
+        self._ragged_call(lib().mijpeg_reconstruct_ragged_device, None, dst_ptrs, False, row_strides, flags, sync, wait_foreign)
 
     def ragged_stats(self) -> dict:
-        st = MijpegRaggedStats()
-        self._check(lib().mijpeg_ragged_get_stats(self._h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in MijpegRaggedStats._fields_}
+        return self._stats(MijpegRaggedStats, lib().mijpeg_ragged_get_stats)
 
     # ---- planar output: component planes instead of interleaved pixels (include/mijpeg.h)
     def reconstruct_planar_device(self, plane_ptrs, row_stride: int, flags: int = 0, sync: bool = True):
@@ -866,53 +885,22 @@ class Decoder:
     def reconstruct_ragged_planar_device(self, plane_ptrs, row_strides, flags: int = 0, sync: bool = True, wait_foreign: bool = True):
         """mijpeg_reconstruct_ragged_planar_device: plane_ptrs[i] = the plane addresses of image i (None / empty: skipped), one entry
         per stream of the decode call; row_strides[i] bytes per line of its planes."""
-        n = len(plane_ptrs)
-        if n != getattr(self, "ragged_images", -1) or len(row_strides) != n:
-            raise ValueError(f"{n} destinations and {len(row_strides)} row strides for the {getattr(self, 'ragged_images', 0)} images of the ragged batch")
-        if wait_foreign:
-            _foreign_work_done()
-        flat = []
-        for p in plane_ptrs:
-            p = list(p or [])
-            flat += [q or None for q in p] + [None] * (4 - len(p))
-        dst = (C.c_void_p * (4 * n))(*flat)
-        rows = (C.c_int64 * n)(*row_strides)
-        self._check(lib().mijpeg_reconstruct_ragged_planar_device(self._h, dst, rows, flags, 1 if sync else 0))
+        self._ragged_call(lib().mijpeg_reconstruct_ragged_planar_device, None, plane_ptrs, True, row_strides, flags, sync, wait_foreign)
 
     # ---- crop windows of a ragged batch (include/mijpeg.h)
     def reconstruct_ragged_rect_device(self, rects, dst_ptrs, row_strides, flags: int = 0, sync: bool = True, wait_foreign: bool = True):
         """mijpeg_reconstruct_ragged_rect_device: pixel (min_x, min_y) of image i -> dst_ptrs[i] (0 / None: skipped), row_strides[i] bytes
         per line of the crop.  rects[i]: (min_x, min_y, max_x, max_y), inclusive; max beyond the picture is clipped (RECT_TO_EDGE)."""
-        n = len(dst_ptrs)
-        if n != getattr(self, "ragged_images", -1) or len(row_strides) != n or len(rects) != n:
-            raise ValueError(f"{len(rects)} crops, {n} destinations and {len(row_strides)} row strides for the {getattr(self, 'ragged_images', 0)} images of the ragged batch")
-        if wait_foreign:
-            _foreign_work_done()
-        dst = (C.c_void_p * n)(*[p or None for p in dst_ptrs])
-        rows = (C.c_int64 * n)(*row_strides)
-        self._check(lib().mijpeg_reconstruct_ragged_rect_device(self._h, rect_array(rects), dst, rows, flags, 1 if sync else 0))
+        self._ragged_call(lib().mijpeg_reconstruct_ragged_rect_device, rects, dst_ptrs, False, row_strides, flags, sync, wait_foreign)
 
     def reconstruct_ragged_rect_planar_device(self, rects, plane_ptrs, row_strides, flags: int = 0, sync: bool = True, wait_foreign: bool = True):
         """mijpeg_reconstruct_ragged_rect_planar_device: sample (min_x, min_y) of component c of image i -> plane_ptrs[i][c] (None /
         empty: the image is skipped), row_strides[i] bytes per line of every plane of the crop."""
-        n = len(plane_ptrs)
-        if n != getattr(self, "ragged_images", -1) or len(row_strides) != n or len(rects) != n:
-            raise ValueError(f"{len(rects)} crops, {n} destinations and {len(row_strides)} row strides for the {getattr(self, 'ragged_images', 0)} images of the ragged batch")
-        if wait_foreign:
-            _foreign_work_done()
-        flat = []
-        for p in plane_ptrs:
-            p = list(p or [])
-            flat += [q or None for q in p] + [None] * (4 - len(p))
-        dst = (C.c_void_p * (4 * n))(*flat)
-        rows = (C.c_int64 * n)(*row_strides)
-        self._check(lib().mijpeg_reconstruct_ragged_rect_planar_device(self._h, rect_array(rects), dst, rows, flags, 1 if sync else 0))
+        self._ragged_call(lib().mijpeg_reconstruct_ragged_rect_planar_device, rects, plane_ptrs, True, row_strides, flags, sync, wait_foreign)
 
     def ragged_rect_stats(self) -> dict:
         """What the object's last crop call did (mijpeg_ragged_rect_stats)."""
-        st = MijpegRaggedRectStats()
-        self._check(lib().mijpeg_ragged_rect_stats_get(self._h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in MijpegRaggedRectStats._fields_}
+        return self._stats(MijpegRaggedRectStats, lib().mijpeg_ragged_rect_stats_get)
 
     # ---- crops resized into one batch tensor (include/mijpeg.h, DESIGN 4.1f)
     def reconstruct_ragged_resized_device(self, rects, out_width: int, out_height: int, channels: int, dst_ptr: int, image_stride: int, plane_stride: int,
@@ -932,9 +920,7 @@ class Decoder:
 
     def ragged_resized_stats(self) -> dict:
         """What the object's last resized call did (mijpeg_ragged_resized_stats)."""
-        st = MijpegRaggedResizedStats()
-        self._check(lib().mijpeg_ragged_resized_stats_get(self._h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in MijpegRaggedResizedStats._fields_ if k != "reserved"}
+        return self._stats(MijpegRaggedResizedStats, lib().mijpeg_ragged_resized_stats_get, {"reserved"})
 
     # ---- ... as a normalised float batch, mirrored per picture (include/mijpeg.h, DESIGN 4.1g)
     def reconstruct_ragged_normalized_device(self, rects, out_width: int, out_height: int, channels: int, sample: int, scale, bias, mirror, dst_ptr: int,
@@ -967,9 +953,7 @@ class Decoder:
 
     def ragged_normalized_stats(self) -> dict:
         """Sample type and mirrored pictures of the object's last resized or normalised call (mijpeg_ragged_normalized_stats)."""
-        st = MijpegRaggedNormalizedStats()
-        self._check(lib().mijpeg_ragged_normalized_stats_get(self._h, C.byref(st)))
-        return dict(sample=int(st.sample), mirrored=int(st.mirrored))
+        return self._stats(MijpegRaggedNormalizedStats, lib().mijpeg_ragged_normalized_stats_get, {"reserved"})
 
     def deinterleave_device(self, src_ptr: int, src_row_stride: int, width: int, height: int, components: int, sample_bytes: int, plane_ptrs,
                             row_stride: int):
@@ -980,9 +964,7 @@ class Decoder:
 
     def planar_stats(self) -> dict:
         """What the object's last planar call did (mijpeg_planar_stats)."""
-        st = MijpegPlanarStats()
-        self._check(lib().mijpeg_planar_stats_get(self._h, C.byref(st)))
-        return {k: int(getattr(st, k)) for k, _ in MijpegPlanarStats._fields_}
+        return self._stats(MijpegPlanarStats, lib().mijpeg_planar_stats_get)
 
     def reconstruct_unsampled(self, comp: int, flags: int = 0) -> np.ndarray:
         """JPGTAG_DECODER_UPSAMPLE = false: component `comp` on its own sample grid, no colour transformation

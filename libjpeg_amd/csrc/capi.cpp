@@ -1,7 +1,7 @@
 // capi.cpp -- the C ABI of include/mijpeg.h: decoder object (host entropy decoding + streaming upload +
 // GPU reconstruction of whole frames) and uniform batches.  The kernel selection and the launch are in
-// reconstruct_device.cpp, the rectangle service in rect_service.cpp, ragged batches in ragged_decode.cpp, the encoder direction
-// in encode_device.cpp.  Compiled with hipcc (host side only uses the HIP runtime API).  There is NO CPU fallback for the
+// reconstruct_device.cpp, the rectangle service in rect_service.cpp, ragged batches in ragged_decode.cpp and
+// ragged_reconstruct.cpp, the encoder direction in encode_device.cpp.  Compiled with hipcc (host side only uses the HIP runtime API).  There is NO CPU fallback for the
 // reconstruction: without a device the reconstruct calls fail with MIJPEG_ERR_DEVICE.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -272,13 +272,9 @@ try {
     if (d->stage_host) (void)hipHostFree(d->stage_host);
     if (d->walk_dev) (void)hipFree(d->walk_dev);
     if (d->xt_helper) mijpeg_destroy(d->xt_helper);
-    if (d->ragged_desc_dev) (void)hipFree(d->ragged_desc_dev);
-    if (d->ragged_desc_host) (void)hipHostFree(d->ragged_desc_host);
-    if (d->ragged_uploaded) (void)hipEventDestroy(d->ragged_uploaded);
+    pinned_upload_release(d->list_tables);
     if (d->resized_arena_dev) (void)hipFree(d->resized_arena_dev);
-    if (d->resized_desc_dev) (void)hipFree(d->resized_desc_dev);
-    if (d->resized_desc_host) (void)hipHostFree(d->resized_desc_host);
-    if (d->resized_uploaded) (void)hipEventDestroy(d->resized_uploaded);
+    pinned_upload_release(d->resample_tables);
     if (d->enc_dev) (void)hipFree(d->enc_dev);
     for (int k = 0; k < 2; k++) {
       if (d->henc_dev[k]) (void)hipFree(d->henc_dev[k]);
@@ -1168,7 +1164,8 @@ try {
       it.own_deltas_dev = d->batch_quant_dev + (size_t)i * 4 * 64;
     }
   }
-  const int rc = reconstruct_planar_items(d, items.data(), d->batch_frames, flags & PLANAR_FLAGS, nullptr);
+  RaggedFailures failures;
+  const int rc = reconstruct_planar_items(d, items.data(), d->batch_frames, flags & PLANAR_FLAGS, failures);
   if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? "planar reconstruction: a kernel launch failed" : "planar reconstruction not available for this batch");
   d->planar_stats.images = d->batch_frames;
   if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
@@ -1253,7 +1250,8 @@ try {
   for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) it.planes[c] = c < d->host.info.components ? planes[c] : nullptr;
   it.row_stride = row_stride;
   it.xt = d->host.is_xt() ? &d->host.xt : nullptr;
-  const int rc = reconstruct_planar_items(d, &it, 1, flags & PLANAR_FLAGS, nullptr);
+  RaggedFailures failures;
+  const int rc = reconstruct_planar_items(d, &it, 1, flags & PLANAR_FLAGS, failures);
   if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? "planar reconstruction: a kernel launch failed" : "planar reconstruction not available for this stream");
   d->planar_stats.images = 1;
   if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));

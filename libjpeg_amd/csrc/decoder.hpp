@@ -1,6 +1,6 @@
 // decoder.hpp -- the decoder object of the C ABI and what its translation units share: capi.cpp (the object, single images, uniform
-// batches), rect_service.cpp (rectangles), entropy_device.cpp, reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp and
-// encode_device.cpp.
+// batches), rect_service.cpp (rectangles), entropy_device.cpp, reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp,
+// ragged_reconstruct.cpp and encode_device.cpp.
 // Private to libmijpeg.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +16,15 @@
 #include "../../include/mijpeg.h"
 #include "host_decoder.hpp"
 #include "request_model.hpp"
+
+// Tables that travel to the device through a pinned copy, once per call, on the object's stream (pinned_upload_reserve / _send /
+// _release below): the device buffer, the pinned one, and the event behind the last upload, which frees the pinned copy for the next
+struct PinnedUpload {
+  uint8_t *dev = nullptr, *host = nullptr;
+  size_t dev_cap = 0, host_cap = 0;
+  hipEvent_t left = nullptr;
+  bool pending = false;
+};
 
 struct mijpeg_decoder {
   int device = -1;
@@ -132,29 +141,23 @@ struct mijpeg_decoder {
   std::vector<RaggedImage> ragged;
   std::vector<mijpeg_decoder *> ragged_children; // kept from call to call
   std::vector<uint8_t> own_input;                // a child's copy of its stream (the caller's bytes are only read during the call)
-  hipEvent_t ragged_uploaded = nullptr;          // behind the upload of the descriptor tables (the pinned copy is free again)
-  bool ragged_upload_pending = false;
   int ragged_n = 0;
   mijpeg_ragged_stats ragged_stats{};
-  // launch_fused_lists (reconstruct_device.cpp) alone writes these: the tables of a list call's launches, interleaved or planar
-  // (fused_list.hpp), and their pinned copy, which ragged_uploaded guards from one call to the next
-  uint8_t *ragged_desc_dev = nullptr, *ragged_desc_host = nullptr;
-  size_t ragged_desc_cap = 0, ragged_desc_host_cap = 0;
+  PinnedUpload list_tables; // launch_fused_lists (reconstruct_device.cpp) alone writes these: the tables of a list call's launches (fused_list.hpp)
   // planar calls (reconstruct_planar_items): the interleaved picture of the two-pass route; what the last call did
   uint8_t *planar_tmp_dev = nullptr;
   size_t planar_tmp_cap = 0;
   mijpeg_planar_stats planar_stats{};
-  // crop calls (mijpeg_reconstruct_ragged_rect_device and its planar twin, ragged_decode.cpp): the full picture of the copy route
+  // crop calls (mijpeg_reconstruct_ragged_rect_device and its planar twin, ragged_reconstruct.cpp): the full picture of the copy route
   // (a child's own: its reconstruction runs on the child's stream); what the last call did
   uint8_t *rect_tmp_dev = nullptr;
   size_t rect_tmp_cap = 0;
   mijpeg_ragged_rect_stats rect_stats{};
-  // resized call (mijpeg_reconstruct_ragged_resized_device, ragged_decode.cpp): the arena of the crops, the call's tables
-  // (resample_taps.hpp) and their pinned copy, which resized_uploaded guards from one call to the next; what the last call did
-  uint8_t *resized_arena_dev = nullptr, *resized_desc_dev = nullptr, *resized_desc_host = nullptr;
-  size_t resized_arena_cap = 0, resized_desc_cap = 0, resized_desc_host_cap = 0;
-  hipEvent_t resized_uploaded = nullptr;
-  bool resized_upload_pending = false;
+  // resized call (mijpeg_reconstruct_ragged_resized_device, ragged_reconstruct.cpp): the arena of the crops and the call's tables
+  // (resample_taps.hpp; of their own: a crop call inside the resized call fills list_tables while these wait); what the last call did
+  uint8_t *resized_arena_dev = nullptr;
+  size_t resized_arena_cap = 0;
+  PinnedUpload resample_tables;
   mijpeg_ragged_resized_stats resized_stats{};
   mijpeg_ragged_normalized_stats normalized_stats{}; // (the normalised call's sample type and mirrored pictures: set wherever resized_stats is)
   // ragged encode (encode_device.cpp): descriptors, coder arrays and coefficient store of a pass; plain stream and output arena;
@@ -227,6 +230,30 @@ inline int ensure_pinned(mijpeg_decoder *d, uint8_t **ptr, size_t *cap, size_t b
   HIP_TRY(d, hipHostMalloc((void **)ptr, bytes, hipHostMallocDefault));
   *cap = bytes;
   return MIJPEG_OK;
+}
+
+// `bytes` of u's pinned copy to fill, once the last call's upload has left it (the copy travels asynchronously); grows both buffers
+inline int pinned_upload_reserve(mijpeg_decoder *d, PinnedUpload &u, size_t bytes)
+{
+  if (const int rc = ensure_dev(d, (void **)&u.dev, &u.dev_cap, bytes)) return rc;
+  if (u.pending) HIP_TRY(d, hipEventSynchronize(u.left));
+  u.pending = false;
+  return ensure_pinned(d, &u.host, &u.host_cap, bytes);
+}
+// ... and on their way: u.host -> u.dev on the object's stream, the event behind it (nothing is waited for)
+inline int pinned_upload_send(mijpeg_decoder *d, PinnedUpload &u, size_t bytes)
+{
+  HIP_TRY(d, hipMemcpyAsync(u.dev, u.host, bytes, hipMemcpyHostToDevice, d->stream));
+  if (!u.left) HIP_TRY(d, hipEventCreateWithFlags(&u.left, hipEventDisableTiming));
+  HIP_TRY(d, hipEventRecord(u.left, d->stream));
+  u.pending = true;
+  return MIJPEG_OK;
+}
+inline void pinned_upload_release(PinnedUpload &u) // (mijpeg_destroy)
+{
+  if (u.dev) (void)hipFree(u.dev);
+  if (u.host) (void)hipHostFree(u.host);
+  if (u.left) (void)hipEventDestroy(u.left);
 }
 
 // MIJPEG_TRACE_SUBMIT (diagnostics): the host time of the steps of a device decode, since t0, on stderr

@@ -1,8 +1,9 @@
 // reconstruct.hpp -- what reconstruct_device.cpp (kernel selection, workspace and launch of the reconstruction) shares with the
-// decoder object's entry points in capi.cpp, rect_service.cpp and ragged_decode.cpp.  Private to libmijpeg.so.
+// decoder object's entry points in capi.cpp, rect_service.cpp, ragged_decode.cpp and ragged_reconstruct.cpp.  Private to libmijpeg.so.
 #pragma once
 #include "decoder.hpp"
 #include "kernels.hpp"
+#include "ragged_failures.hpp"
 #include "rect_request.hpp"
 
 // The range gates of the kernel selection (plan_reconstruct): a kernel or flavour is admitted where mijpeg_info::range_max
@@ -22,6 +23,8 @@ mij::Sampling sampling_of(const mijpeg_info &f);
 // Which kernel reconstructs a batch, and in which flavour; what it needs as workspace
 mij::ReconPlan plan_reconstruct(const mijpeg_batch *b);
 size_t workspace_need(const mijpeg_batch *b, const mij::ReconPlan &p);
+// ... of one frame as a member of a list launch, which brings per-frame tables
+mij::ReconPlan plan_list_member(const mijpeg_info &f, const int16_t *coef_dev, void *out_dev, int64_t row_stride, uint32_t flags);
 
 // A frame as the fused kernels address it, into g (Fused420Args, RaggedFrame, the planner's mijpeg_ragged_frame): its size, the
 // luma and chroma planes in blocks and where they start in the coefficient store, valid chroma samples, the grid of 128 x 128 tiles
@@ -57,7 +60,7 @@ int reconstruct_view(mijpeg_decoder *d, int comp, void *dst_device, int64_t row_
 // ---- lists of differently shaped frames in fused launches (fused_list.hpp: items, launches, table layout) ----
 struct FusedListItem;
 struct FusedListLaunch;
-// The launches on the object's stream (nothing is waited for): their tables into d->ragged_desc_host once the last call's upload
+// The launches on the object's stream (nothing is waited for): their tables into d->list_tables once the last call's upload
 // has left it, one upload, one launch_fused_list each.  -> the number of launches made, or the (negative) error, set on the object.
 // window: the launches run the items' crop windows (FusedListItem::window, every item has one); a planar window call's
 // one-component launches are their own plane and take the interleaved window flavour.
@@ -75,12 +78,19 @@ struct PlanarItem {
   const mijpeg_xt_params *xt = nullptr;
 };
 constexpr uint32_t PLANAR_FLAGS = MIJPEG_FLAG_FORCE_SAFE | MIJPEG_FLAG_FORCE_GENERIC | MIJPEG_FLAG_NO_COLOR_TRANSFORM; // what the planar calls take
-// bytes per sample of a frame's reconstruction
+// bytes per sample of a frame's reconstruction; of the whole picture, interleaved with tightly packed lines
 inline int sample_bytes_of(const mijpeg_info &f) { return f.xt ? (f.sample_bytes > 1 ? 2 : 1) : f.precision > 8 ? 2 : 1; }
+inline size_t picture_bytes(const mijpeg_info &f) { return (size_t)f.height * (size_t)f.width * (size_t)f.components * (size_t)sample_bytes_of(f); }
 // MIJPEG_ERR_INVALID_PARAMETER where a plane of a component the frame has is missing or row_stride is below a line of samples
 int planar_check(const mijpeg_info &f, void *const *planes, int64_t row_stride);
-// The items on the object's stream (nothing is waited for): those whose plan (plan_reconstruct, per-frame tables) has a planar twin
-// share one launch of it per kernel and flavour; the others are reconstructed interleaved into the object's staging buffer and
-// taken apart by deinterleave_kernel.  One-component frames are their own plane.  Adds to d->planar_stats.  An item that fails
-// does not stop the others: -> the first such code, *failed_item its index (a launch of a whole group that fails ends the call).
-int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, uint32_t flags, int *failed_item);
+// The staged second pass, on the object's stream: rectangle w (inclusive) of the full picture at `full` (interleaved, tightly packed
+// lines) to ptrs -- a strided device copy to ptrs[0], or (planar) deinterleave_kernel to a plane each ...
+int staged_rect_out(mijpeg_decoder *d, const uint8_t *full, const mijpeg_info &f, const mijpeg_rect &w, void *const *ptrs, int64_t row_stride, bool planar);
+// ... behind the first: the frame of b in full, as the existing kernels write it, into `staging` (b's destination is set here; the
+// stream orders one picture after the other), and its rectangle w to ptrs.  No message: the caller reports.
+int reconstruct_staged(mijpeg_decoder *d, mijpeg_batch &b, uint8_t *staging, const mijpeg_rect &w, void *const *ptrs, int64_t row_stride, bool planar);
+// The items on the object's stream (nothing is waited for): those whose plan (plan_list_member) has a planar twin share one launch
+// of it per kernel and flavour; the others take the staged second pass through planar_tmp_dev.  One-component frames are their own
+// plane.  Adds to d->planar_stats.  An item that fails does not stop the others: item i is noted in `failures` (empty on entry) as
+// image image_of[i] (i without a map).  -> what ends the call with nothing noted (a whole launch that fails), or the first noted code.
+int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, uint32_t flags, RaggedFailures &failures, const int *image_of = nullptr);

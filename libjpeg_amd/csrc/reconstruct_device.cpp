@@ -486,6 +486,14 @@ mijpeg_batch batch_of(const mijpeg_info &info, const int16_t *coef_dev, void *ou
   return b;
 }
 
+ReconPlan plan_list_member(const mijpeg_info &f, const int16_t *coef_dev, void *out_dev, int64_t row_stride, uint32_t flags)
+{
+  static const uint16_t per_frame_tables = 0; // (quant_dev is only tested by the planner: the list launches read their own tables)
+  mijpeg_batch b = batch_of(f, coef_dev, out_dev, row_stride, 0, 1, flags);
+  b.quant_dev = &per_frame_tables;
+  return plan_reconstruct(&b);
+}
+
 int reconstruct_on(mijpeg_decoder *d, mijpeg_batch &b, const RequestExtra *rx, const char *noun)
 {
   const size_t ws = workspace_need(&b, plan_reconstruct(&b));
@@ -529,38 +537,64 @@ int launch_fused_lists(mijpeg_decoder *d, const FusedListItem *items, const std:
   if (launches.empty()) return 0;
   const std::vector<FusedListTable> tables = fused_list_layout(launches, planar, window);
   const size_t bytes = tables.back().end;
-  int rc = ensure_dev(d, (void **)&d->ragged_desc_dev, &d->ragged_desc_cap, bytes);
-  if (rc) return rc;
-  if (d->ragged_upload_pending) { // (the pinned copy travels asynchronously: the last call's must have left)
-    HIP_TRY(d, hipEventSynchronize(d->ragged_uploaded));
-    d->ragged_upload_pending = false;
-  }
-  if ((rc = ensure_pinned(d, &d->ragged_desc_host, &d->ragged_desc_host_cap, bytes))) return rc;
-  for (size_t l = 0; l < launches.size(); l++) fused_list_fill(d->ragged_desc_host, tables[l], launches[l], items, planar, window);
-  HIP_TRY(d, hipMemcpyAsync(d->ragged_desc_dev, d->ragged_desc_host, bytes, hipMemcpyHostToDevice, d->stream));
-  if (!d->ragged_uploaded) HIP_TRY(d, hipEventCreateWithFlags(&d->ragged_uploaded, hipEventDisableTiming));
-  HIP_TRY(d, hipEventRecord(d->ragged_uploaded, d->stream));
-  d->ragged_upload_pending = true;
+  PinnedUpload &u = d->list_tables;
+  if (const int rc = pinned_upload_reserve(d, u, bytes)) return rc;
+  for (size_t l = 0; l < launches.size(); l++) fused_list_fill(u.host, tables[l], launches[l], items, planar, window);
+  if (const int rc = pinned_upload_send(d, u, bytes)) return rc;
   for (size_t l = 0; l < launches.size(); l++) {
     Fused420Args a;
     memset(&a, 0, sizeof(a));
     a.coef = d->coef_dev;
     a.frames = (int32_t)launches[l].members.size();
-    a.ragged = (const RaggedFrame *)(d->ragged_desc_dev + tables[l].frames);
-    a.ragged_first = (const uint32_t *)(d->ragged_desc_dev + tables[l].first);
-    a.qdev = (const int32_t *)(d->ragged_desc_dev + tables[l].deltas);
+    a.ragged = (const RaggedFrame *)(u.dev + tables[l].frames);
+    a.ragged_first = (const uint32_t *)(u.dev + tables[l].first);
+    a.qdev = (const int32_t *)(u.dev + tables[l].deltas);
     const bool planes = planar && !(window && launches[l].p.sampling == Sampling::GREY); // (a window call's grey launches: their own plane)
-    if (planes) a.out = d->ragged_desc_dev + tables[l].planes; // (the PlanarFrame table: kernels.hpp; a window launch finds its WindowFrame table behind it)
-    else if (window) a.out = d->ragged_desc_dev + tables[l].windows;
+    if (planes) a.out = u.dev + tables[l].planes; // (the PlanarFrame table: kernels.hpp; a window launch finds its WindowFrame table behind it)
+    else if (window) a.out = u.dev + tables[l].windows;
     if (launch_fused_list(launches[l].p, a, (unsigned)launches[l].grid, planes, d->stream, window))
       return set_error(d, MIJPEG_ERR_DEVICE, std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
   }
   return (int)launches.size();
 }
 
-int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, uint32_t flags, int *failed_item)
+// what deinterleave_kernel takes: an interleaved picture (or a rectangle of one: src at its first sample) -> a plane per component
+static DeinterleaveArgs deinterleave_args(const void *src, int64_t src_row, int components, int sample_bytes, int32_t width, int32_t height, void *const *planes,
+                                          int64_t row_stride)
 {
-  static const uint16_t per_frame_tables = 0; // (the planner only asks whether a batch brings per-frame tables: the planar launches do)
+  DeinterleaveArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = (const uint8_t *)src; a.src_row = src_row;
+  a.ncomp = components; a.sample_bytes = sample_bytes; a.width = width; a.height = height;
+  for (int c = 0; c < components; c++) a.dst[c] = (uint8_t *)planes[c];
+  a.dst_row = row_stride;
+  return a;
+}
+
+int staged_rect_out(mijpeg_decoder *d, const uint8_t *full, const mijpeg_info &f, const mijpeg_rect &w, void *const *ptrs, int64_t row_stride, bool planar)
+{
+  const int sb = sample_bytes_of(f);
+  const int64_t bpp = (int64_t)f.components * sb, line = (int64_t)f.width * bpp;
+  const int32_t cw = w.max_x - w.min_x + 1, ch = w.max_y - w.min_y + 1;
+  const uint8_t *src = full + (int64_t)w.min_y * line + (int64_t)w.min_x * bpp;
+  if (!planar) {
+    HIP_TRY(d, hipMemcpy2DAsync(ptrs[0], (size_t)row_stride, src, (size_t)line, (size_t)(cw * bpp), (size_t)ch, hipMemcpyDeviceToDevice, d->stream));
+    return MIJPEG_OK;
+  }
+  return launch_deinterleave(deinterleave_args(src, line, f.components, sb, cw, ch, ptrs, row_stride), d->stream) ? MIJPEG_ERR_DEVICE : MIJPEG_OK;
+}
+
+int reconstruct_staged(mijpeg_decoder *d, mijpeg_batch &b, uint8_t *staging, const mijpeg_rect &w, void *const *ptrs, int64_t row_stride, bool planar)
+{
+  b.out_dev = staging;
+  b.out_row_stride = (int64_t)b.info.width * b.info.components * sample_bytes_of(b.info);
+  b.out_frame_stride = b.out_row_stride * b.info.height;
+  const int rc = reconstruct_on(d, b, nullptr, nullptr);
+  return rc ? rc : staged_rect_out(d, staging, b.info, w, ptrs, row_stride, planar);
+}
+
+int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, uint32_t flags, RaggedFailures &failures, const int *image_of)
+{
   std::vector<FusedListItem> fused;
   std::vector<FusedListLaunch> launches;
   std::vector<int> two_pass;
@@ -568,14 +602,11 @@ int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, 
   for (int i = 0; i < n; i++) {
     const PlanarItem &it = items[i];
     const mijpeg_info &f = *it.info;
-    mijpeg_batch b = batch_of(f, it.coef_dev, it.planes[0], it.row_stride, 0, 1, flags);
-    b.xt = it.xt;
     if (f.components == 1) { two_pass.push_back(i); continue; } // (its own plane: the existing kernel, no second pass)
-    b.quant_dev = &per_frame_tables;
-    const ReconPlan p = plan_reconstruct(&b);
+    const ReconPlan p = plan_list_member(f, it.coef_dev, it.planes[0], it.row_stride, flags);
     if (f.components != 3 || f.precision != 8 || f.xt || !planar_twin(p) || fused_list_tiles(f) > 0x7fffffffull) {
       two_pass.push_back(i);
-      staging = std::max(staging, (size_t)f.height * (size_t)f.width * (size_t)f.components * (size_t)sample_bytes_of(f));
+      staging = std::max(staging, picture_bytes(f));
       continue;
     }
     fused_list_add(launches, p, (int)fused.size(), f);
@@ -585,43 +616,22 @@ int reconstruct_planar_items(mijpeg_decoder *d, const PlanarItem *items, int n, 
   if (made < 0) return made;
   d->planar_stats.fused_launches += made;
   d->planar_stats.fused += (int32_t)fused.size();
-  // the others: the picture as the existing kernels write it, into the staging buffer (one after the other: the stream orders
-  // them), and deinterleave_kernel behind each
-  if (staging) {
-    const int rc = ensure_dev(d, (void **)&d->planar_tmp_dev, &d->planar_tmp_cap, staging);
-    if (rc) return rc;
-  }
-  int failed = MIJPEG_OK;
+  // the others: the staged second pass with the whole picture as the rectangle
+  if (const int rc = ensure_dev(d, (void **)&d->planar_tmp_dev, &d->planar_tmp_cap, staging)) return rc; // (nobody staged: nothing to grow)
   for (int i : two_pass) {
     const PlanarItem &it = items[i];
     const mijpeg_info &f = *it.info;
-    const int sb = sample_bytes_of(f);
-    const bool own_plane = f.components == 1;
-    const int64_t line = (int64_t)f.width * f.components * sb;
-    mijpeg_batch b = own_plane ? batch_of(f, it.coef_dev, it.planes[0], it.row_stride, it.row_stride * f.height, 1, flags)
-                               : batch_of(f, it.coef_dev, d->planar_tmp_dev, line, line * f.height, 1, flags);
+    const bool own_plane = f.components == 1; // (one pass either way for a single component)
+    mijpeg_batch b = batch_of(f, it.coef_dev, it.planes[0], it.row_stride, it.row_stride * f.height, 1, flags);
     b.xt = it.xt;
     b.quant_dev = it.own_deltas_dev;
-    int rc = reconstruct_on(d, b, nullptr, nullptr);
-    if (!rc && !own_plane) {
-      DeinterleaveArgs a;
-      memset(&a, 0, sizeof(a));
-      a.src = d->planar_tmp_dev;
-      a.src_row = line;
-      a.ncomp = f.components; a.sample_bytes = sb;
-      a.width = f.width; a.height = f.height;
-      for (int c = 0; c < f.components; c++) a.dst[c] = (uint8_t *)it.planes[c];
-      a.dst_row = it.row_stride;
-      if (launch_deinterleave(a, d->stream)) rc = MIJPEG_ERR_DEVICE;
-      else d->planar_stats.two_pass_launches++;
-    }
-    if (!rc) (own_plane ? d->planar_stats.fused : d->planar_stats.two_pass)++; // (one pass either way for a single component)
-    else if (!failed) {
-      failed = rc;
-      if (failed_item) *failed_item = i;
-    }
+    const int rc = own_plane ? reconstruct_on(d, b, nullptr, nullptr)
+                             : reconstruct_staged(d, b, d->planar_tmp_dev, mijpeg_rect{0, 0, f.width - 1, f.height - 1}, it.planes, it.row_stride, true);
+    if (!rc) (own_plane ? d->planar_stats.fused : d->planar_stats.two_pass)++;
+    if (!rc && !own_plane) d->planar_stats.two_pass_launches++;
+    failures.note(image_of ? image_of[i] : i, rc);
   }
-  return failed;
+  return failures.code;
 }
 
 extern "C" {
@@ -643,15 +653,7 @@ try {
   if (row_stride < (int64_t)width * sample_bytes || src_row_stride < (int64_t)width * sample_bytes * components) return MIJPEG_ERR_INVALID_PARAMETER;
   if (d->device < 0) return set_error(d, MIJPEG_ERR_DEVICE, "decoder was created without a device");
   HIP_TRY(d, hipSetDevice(d->device));
-  DeinterleaveArgs a;
-  memset(&a, 0, sizeof(a));
-  a.src = (const uint8_t *)src_device;
-  a.src_row = src_row_stride;
-  a.ncomp = components; a.sample_bytes = sample_bytes;
-  a.width = width; a.height = height;
-  for (int c = 0; c < components; c++) a.dst[c] = (uint8_t *)planes[c];
-  a.dst_row = row_stride;
-  if (launch_deinterleave(a, d->stream)) return hip_fail(d, hipGetLastError(), "deinterleave_kernel launch");
+  if (launch_deinterleave(deinterleave_args(src_device, src_row_stride, components, sample_bytes, width, height, planes, row_stride), d->stream)) return hip_fail(d, hipGetLastError(), "deinterleave_kernel launch");
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(d, "mijpeg_deinterleave_device"); }
 

@@ -14,7 +14,7 @@ constexpr unsigned RESAMPLE_GROUP = 256;       // lanes of a workgroup: RESAMPLE
 constexpr int RESAMPLE_STRIP = 16;             // source lines a workgroup filters horizontally at a time (its LDS: STRIP x TILE_W words)
 constexpr int RESAMPLE_REG_TAPS = 8;           // horizontal taps per output up to which a lane keeps its weights in registers
 constexpr size_t RESAMPLE_ARENA_SPARE = 16;    // bytes behind the last crop: a three-component pixel is read as one word
-// what a launch stores per sample: the values of MIJPEG_SAMPLE_* (include/mijpeg.h; ragged_decode.cpp asserts that they agree)
+// what a launch stores per sample: the values of MIJPEG_SAMPLE_* (include/mijpeg.h; ragged_reconstruct.cpp asserts that they agree)
 constexpr int RESAMPLE_U8 = 0, RESAMPLE_F32 = 1, RESAMPLE_F16 = 2, RESAMPLE_BF16 = 3;
 inline unsigned resample_sample_bytes(int sample) { return sample == RESAMPLE_U8 ? 1u : sample == RESAMPLE_F32 ? 4u : 2u; }
 

@@ -1,5 +1,5 @@
 // resample_taps.hpp -- the host half of the resized crop call (include/mijpeg.h): the filter's taps for one axis, in
-// integers only, and the layout of the tables one call uploads.  resample.hip reads what stands in them; ragged_decode.cpp uploads and
+// integers only, and the layout of the tables one call uploads.  resample.hip reads what stands in them; ragged_reconstruct.cpp uploads and
 // launches.  Calls nothing of the HIP runtime and nothing of the library: a plain host compiler builds tests/cxx/resample_taps.cpp
 // around it.  Private to libmijpeg.so.
 //

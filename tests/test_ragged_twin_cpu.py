@@ -3,7 +3,8 @@ ragged flavour (ragged_twin, kernels.hip) and asks nothing about the group: that
 kernel of the ragged families only for frames of that family's layout and precision.  Pinned here, without a device, over every
 layout the planner tells apart, both precisions, the colour transformation on and off, both arithmetic flavours and every range
 gate from both sides.  tests/cxx/fused_list_tables.cpp: the tables of those launches (fused_list.hpp) under the sanitizers;
-tests/cxx/encode_list_tables.cpp: the other direction's device-free half, the passes of the ragged encode (encode_list.hpp)."""
+tests/cxx/encode_list_tables.cpp: the other direction's device-free half, the passes of the ragged encode (encode_list.hpp);
+tests/cxx/ragged_failures.cpp: which failing picture a list reconstruction call reports, and in which words (ragged_failures.hpp)."""
 import ctypes as C
 import itertools
 import os
@@ -73,3 +74,10 @@ def test_encode_list_tables_under_sanitizers(tmp_path):
     encode from the real planner, layout and fill -- arenas of exactly their sizes, every pointer, prefix table and work list read
     back, the plain buffer and every picture's piece of a fake output arena -- under AddressSanitizer and UBSan."""
     _run_under_sanitizers(tmp_path, "encode_list_tables", "encoder.cpp")
+
+
+def test_ragged_failures_under_sanitizers(tmp_path):
+    """tests/cxx/ragged_failures.cpp, a program of its own around ragged_failures.hpp: no failure is MIJPEG_OK, the first noted of
+    several failures gives code and message, and the message's two forms -- with a child object's text behind ": " (an empty text
+    leaves the ": "), without any -- byte for byte, under AddressSanitizer and UBSan."""
+    _run_under_sanitizers(tmp_path, "ragged_failures")
