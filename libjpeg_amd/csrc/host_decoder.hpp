@@ -306,6 +306,7 @@ private:
   bool parsing_hidden_ = false;
   int64_t plane_offset_[MIJPEG_MAX_COMPONENTS] = {0, 0, 0, 0}; // component planes inside this frame's own store
   int finish_xt(bool header_only);
+  struct XtFinish; // finish_xt's stages (xt_finish.cpp): what one call carries from stage to stage
   int spec_without_residual(const XtBox &spec);
   int spec_ltrafo_ = 255; // L transformation a merging specification WITHOUT a residual names (255: none; codestream/tables.cpp:1994-2021)
   int add_hidden_scans(uint32_t type, const std::vector<XtBox> &boxes, int hidden);

@@ -20,11 +20,12 @@ for f in capi rect_service reconstruct_device ragged_decode ragged_reconstruct e
   "$HIPCC" --offload-arch=gfx950 -O1 -std=c++17 -fPIC -w -Xarch_host "-fsanitize=address,undefined" -Xarch_host -fno-omit-frame-pointer -x hip -c "$SRC/$f.cpp" -o "$OUT/$f.o" &
 done
 "$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/host_decoder.cpp" -o "$OUT/host_decoder.o" &
+"$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/xt_finish.cpp" -o "$OUT/xt_finish.o" &
 "$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/encoder.cpp" -o "$OUT/encoder.o" &
 "$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/interface/jpeg.cpp" -o "$OUT/jpeg_class.o" &
 "$CXX" -O1 -std=c++17 -pthread $SAN -c "$ROOT/tools/cxx/prepare_batch_host_check.cpp" -o "$OUT/check.o" &
 wait
 "$HIPCC" --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize -o "$OUT/prepare_batch_host_check" "$OUT"/check.o "$OUT"/capi.o "$OUT"/rect_service.o "$OUT"/reconstruct_device.o \
-  "$OUT"/ragged_decode.o "$OUT"/ragged_reconstruct.o "$OUT"/entropy_device.o "$OUT"/encode_device.o "$OUT"/batch_pipeline.o "$OUT"/host_decoder.o "$OUT"/encoder.o "$OUT"/jpeg_class.o \
+  "$OUT"/ragged_decode.o "$OUT"/ragged_reconstruct.o "$OUT"/entropy_device.o "$OUT"/encode_device.o "$OUT"/batch_pipeline.o "$OUT"/host_decoder.o "$OUT"/xt_finish.o "$OUT"/encoder.o "$OUT"/jpeg_class.o \
   "$SRC"/build/kernels.o "$SRC"/build/forward.o "$SRC"/build/hencode.o "$SRC"/build/huffman.o "$SRC"/build/markers.o "$SRC"/build/resample.o "$SRC"/build/requant.o -pthread
 echo "$OUT/prepare_batch_host_check"

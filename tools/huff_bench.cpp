@@ -1,5 +1,5 @@
 // huff_bench.cpp -- host entropy decoder scaling: decode one JPEG repeatedly with 1..N pool workers.
-//   g++ -O3 -std=c++17 -pthread tools/huff_bench.cpp libjpeg_amd/csrc/host_decoder.cpp -o /tmp/huff_bench
+//   g++ -O3 -std=c++17 -pthread tools/huff_bench.cpp libjpeg_amd/csrc/host_decoder.cpp libjpeg_amd/csrc/xt_finish.cpp -o /tmp/huff_bench
 #include <chrono>
 #include <cstdio>
 #include <fstream>

@@ -1,5 +1,5 @@
 // tsan_host.cpp -- the multi-threaded host decoder under ThreadSanitizer ("race detection").
-//   g++ -O1 -g -std=c++17 -pthread -fsanitize=thread tools/tsan_host.cpp libjpeg_amd/csrc/host_decoder.cpp libjpeg_amd/csrc/encoder.cpp -o /tmp/tsan_host
+//   g++ -O1 -g -std=c++17 -pthread -fsanitize=thread tools/tsan_host.cpp libjpeg_amd/csrc/host_decoder.cpp libjpeg_amd/csrc/xt_finish.cpp libjpeg_amd/csrc/encoder.cpp -o /tmp/tsan_host
 //   /tmp/tsan_host tests/golden/*.jpg          (tools/tsan_host.sh does both)
 // What runs concurrently in the product and therefore here: the restart-interval-parallel decode and the speculative
 // (self-synchronising) decode of scans without restart markers on the library's worker pool (HostDecoder::decode with
