@@ -1,6 +1,6 @@
 // capi.cpp -- the C ABI of include/mijpeg.h: decoder object (host entropy decoding + streaming upload +
-// GPU reconstruction of whole frames) and uniform batches.  The kernel selection and the launch are in
-// reconstruct_device.cpp, the rectangle service in rect_service.cpp, ragged batches in ragged_decode.cpp and
+// GPU reconstruction of whole frames), its buffer cache and its queries.  Uniform batches are in batch_decode.cpp, the kernel
+// selection and the launch in reconstruct_device.cpp, the rectangle service in rect_service.cpp, ragged batches in ragged_decode.cpp and
 // ragged_reconstruct.cpp, the encoder direction in encode_device.cpp.  Compiled with hipcc (host side only uses the HIP runtime API).  There is NO CPU fallback for the
 // reconstruction: without a device the reconstruct calls fail with MIJPEG_ERR_DEVICE.
 #include <hip/hip_runtime.h>
@@ -395,6 +395,16 @@ static int decode_alpha_channel(mijpeg_decoder *d, int threads)
   return MIJPEG_OK;
 }
 
+// Block rows [y0, y1) of component c of a JPEG XT frame's residual planes (they sit behind the legacy planes in the same store)
+// on their way to the device, on the object's stream
+static hipError_t upload_residual_rows(mijpeg_decoder *d, int c, int y0, int y1)
+{
+  const mijpeg_xt_params &x = d->host.xt;
+  const size_t row = (size_t)x.residual.blocks_w[c] * 64 * (x.residual_wide ? 2 : 1); // int16 units per block row
+  const size_t off = (size_t)x.residual.coef_offset[c] + row * (size_t)y0;
+  return hipMemcpyAsync(d->coef_dev + off, d->coef_host + off, row * (size_t)(y1 - y0) * sizeof(int16_t), hipMemcpyHostToDevice, d->stream);
+}
+
 int mijpeg_decode_coefficients(mijpeg_decoder *d, int threads)
 try {
   if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
@@ -439,10 +449,7 @@ try {
   if (d->device >= 0 && d->host.residual()) {
     d->host.set_residual_rows_callback([&, d](int c, int y0, int y1) {
       (void)hipSetDevice(d->device);
-      const mijpeg_xt_params &x = d->host.xt;
-      const size_t row = (size_t)x.residual.blocks_w[c] * 64 * (x.residual_wide ? 2 : 1); // int16 units per block row
-      const size_t off = (size_t)x.residual.coef_offset[c] + row * (size_t)y0;
-      const hipError_t e = hipMemcpyAsync(d->coef_dev + off, d->coef_host + off, row * (size_t)(y1 - y0) * sizeof(int16_t), hipMemcpyHostToDevice, d->stream);
+      const hipError_t e = upload_residual_rows(d, c, y0, y1);
       if (e != hipSuccess) rcopy_err.store((int)e);
     });
   }
@@ -490,10 +497,7 @@ try {
     } else // (rows the decode has sent on their way already: the rest of each plane)
       for (int c = 0; c < x.residual.components && copy_err == hipSuccess; c++) {
         const int y0 = d->host.residual_rows_reported(c), y1 = x.residual.blocks_h[c];
-        if (y0 >= y1) continue;
-        const size_t row = (size_t)x.residual.blocks_w[c] * 64 * (x.residual_wide ? 2 : 1);
-        const size_t off = (size_t)x.residual.coef_offset[c] + row * (size_t)y0;
-        copy_err = hipMemcpyAsync(d->coef_dev + off, d->coef_host + off, row * (size_t)(y1 - y0) * sizeof(int16_t), hipMemcpyHostToDevice, d->stream);
+        if (y0 < y1) copy_err = upload_residual_rows(d, c, y0, y1);
       }
   }
   if (copy_err != hipSuccess) return hip_fail(d, copy_err, "hipMemcpyAsync(coefficients)");
@@ -588,27 +592,6 @@ const int16_t *mijpeg_coefficients(mijpeg_decoder *d, int component)
     d->host_planes_stale = false;
   }
   return d->coef_host + d->host.info.coef_offset[component];
-}
-
-// The marker route of a call (mijpeg_set_device_markers) is an attempt: it ends well, or the call runs the ordinary route as if
-// the option were off -- error state included (whatever the attempt reported is taken back).  Counts the images either way.
-static int with_device_markers(mijpeg_decoder *d, int images, const std::function<int(bool)> &attempt)
-{
-  if (d->device_markers == 1) {
-    const int keep_code = d->err_code;
-    const std::string keep_msg = d->err_msg;
-    d->markers_retry = false;
-    d->markers_staged.clear();
-    if (attempt(true) == MIJPEG_OK) {
-      d->markers_searched += images;
-      return MIJPEG_OK;
-    }
-    d->markers_staged.clear();
-    d->markers_declined += images;
-    d->err_code = keep_code;
-    d->err_msg = keep_msg;
-  }
-  return attempt(false);
 }
 
 static int decode_coefficients_device(mijpeg_decoder *d, int min_intervals, bool markers)
@@ -723,335 +706,6 @@ try {
   return with_device_markers(d, 1, [&](bool markers) { return decode_coefficients_device(d, min_intervals, markers); });
 } catch (...) { return boundary_catch(d, "mijpeg_decode_coefficients_device"); }
 
-// ------------------------------------------------------------------------------------------------
-// batches: n streams of one geometry -> n coefficient stores -> n frames, two kernel launches in all
-// ------------------------------------------------------------------------------------------------
-// Aggregation over the images of a decoded batch: what one reconstruction launch for all of them needs to know.
-static int finish_batch(mijpeg_decoder *d);
-
-// What the last finished batch of shared tables reported, for the speculative launch of the next one (MIJPEG_FLAG_SPECULATIVE):
-// frame geometry, tables, and the range check that selected its kernel.  Process-wide: the decoder objects of a pipeline work
-// on chunks of the same material.
-namespace {
-struct SpecHint {
-  std::mutex m;
-  bool valid = false;
-  mijpeg_info info{};
-};
-SpecHint *spec_hint()
-{
-  static SpecHint *h = new SpecHint;
-  return h;
-}
-// an assumed range just below the next gate selects the kernel the hint's batch ran on and holds for every batch that stays
-// below that gate
-int32_t next_gate_below(int32_t range)
-{
-  for (int32_t g : RANGE_GATES)
-    if (range < g) return g - 1;
-  return -1;
-}
-bool same_shape_and_tables(const mijpeg_info &a, const mijpeg_info &b)
-{
-  if (a.width != b.width || a.height != b.height || a.components != b.components || a.precision != b.precision || a.ycbcr != b.ycbcr || a.xt != b.xt ||
-      a.dnl != b.dnl || a.coef_count != b.coef_count)
-    return false;
-  for (int c = 0; c < a.components; c++) {
-    if (a.hsamp[c] != b.hsamp[c] || a.vsamp[c] != b.vsamp[c]) return false;
-    if (memcmp(a.quant[a.quant_index[c]], b.quant[b.quant_index[c]], sizeof(a.quant[0]))) return false;
-  }
-  return true;
-}
-} // namespace
-
-static int submit_batch(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals, bool defer, bool markers)
-{
-  if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device < 0) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "decoder was created without a device");
-  HIP_TRY(d, hipSetDevice(d->device));
-  using clk = std::chrono::steady_clock;
-  const auto t0 = clk::now();
-  if (d->spec_active) { // a speculative reconstruction nobody validated (mijpeg_finish_batch_device): its verdict comes first
-    const int src = settle_speculation(d);
-    if (src) return src;
-  }
-  if (const int prc = settle_pending(d)) return prc; // a submitted batch nobody waited for: its staging buffers are about to be reused
-  d->batch_frames = 0;
-  d->ragged_n = 0; // (a ragged batch's coefficient stores are about to be overwritten)
-  if (d->batch_hosts.size() < (size_t)n) d->batch_hosts.resize((size_t)n); // never shrinks: a pipeline's chunks differ in size, and
-  for (auto &h : d->batch_hosts)                                         // a parser that is thrown away takes its grown vectors along
-    if (!h) h.reset(new HostDecoder());
-  // headers and restart markers of all streams, one stream per worker -- which writes the device's copy of the entropy
-  // coded data (no byte stuffing, no markers) into the stream's slot of the pinned gathering area while it is at it
-  std::vector<int> rcs((size_t)n, 0);
-  {
-    std::vector<size_t> slot;
-    const size_t total = stream_slots(sizes, n, slot);
-    const int src = ensure_pinned(d, &d->stage_host, &d->stage_cap, total);
-    if (src) return src;
-    parallel_for(std::min(n, default_threads()), [&](int w) {
-      for (int i = w; i < n; i += std::min(n, default_threads())) {
-        // (a worker walks ~3 GB/s this way: good for the many small streams of a batch; a large stream is searched in
-        // parallel chunks and gathered in parallel pieces instead -- device_entropy_batch sees which it was)
-        if (markers) d->batch_hosts[(size_t)i]->set_skip_search(); // (headers only: the device searches the segments)
-        else if (sizes[i] <= ((size_t)2 << 20) || n >= default_threads()) d->batch_hosts[(size_t)i]->set_unstuff_sink(d->stage_host + slot[(size_t)i], sizes[i]);
-        rcs[(size_t)i] = d->batch_hosts[(size_t)i]->parse(streams[i], sizes[i], false);
-      }
-    });
-  }
-  for (int i = 0; i < n; i++)
-    if (rcs[(size_t)i]) return set_error(d, rcs[(size_t)i], d->batch_hosts[(size_t)i]->error.message);
-  const auto t_parsed = clk::now();
-  std::vector<HostDecoder *> hosts((size_t)n);
-  for (int i = 0; i < n; i++) hosts[(size_t)i] = d->batch_hosts[(size_t)i].get();
-  for (int i = 0; i < n; i++)
-    if (const char *why = markers ? device_markers_obstacle(*hosts[(size_t)i], sizes[i]) : device_entropy_obstacle(*hosts[(size_t)i], sizes[i]))
-      return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
-  const mijpeg_info &f0 = hosts[0]->info;
-  // one reconstruction launch serves the batch; images with tables of their own (motion JPEG under rate control) make it
-  // read per-frame tables from device memory instead of the kernel arguments
-  bool own_tables = false;
-  for (int i = 1; i < n && !own_tables; i++) {
-    const mijpeg_info &f = hosts[(size_t)i]->info;
-    for (int c = 0; c < f.components; c++)
-      if (memcmp(f.quant[f.quant_index[c]], f0.quant[f0.quant_index[c]], sizeof(f.quant[0]))) own_tables = true;
-  }
-  int rc = ensure_coef_store(d, (size_t)f0.coef_count * (size_t)n, false);
-  if (rc) return rc;
-  d->img_valid = d->model_valid = false;
-  d->uploaded = false;
-  d->decoded = false;
-  d->pend_n = 0;
-  EntropyBatchOptions opt;
-  opt.defer = defer;
-  opt.markers = markers;
-  rc = device_entropy_batch(d, hosts.data(), streams, sizes, n, min_intervals, d->coef_dev, f0.coef_count, opt);
-  if (!rc && markers) {
-    std::vector<size_t> slot;
-    stream_slots(sizes, n, slot);
-    for (int i = 0; i < n; i++) d->markers_staged.emplace_back(slot[(size_t)i], sizes[i] - hosts[(size_t)i]->scans[0].ecs_begin);
-  }
-  d->timing[0] = std::chrono::duration<double>(clk::now() - t0).count();
-  d->timing[1] = std::chrono::duration<double>(t_parsed - t0).count();
-  d->timing[2] = d->phase_prepare;
-  d->timing[3] = d->phase_device;
-  if (rc) { // (device_entropy_batch has waited for whatever it enqueued before the failure)
-    d->pend_n = 0;
-    return rc;
-  }
-  d->batch_own_tables = own_tables;
-  d->batch_frames = -n; // decoded (or on its way) but not aggregated yet
-  if (d->pend_n) return MIJPEG_OK; // deferred: finish_batch() waits
-  return finish_batch(d);
-}
-
-static int finish_batch(mijpeg_decoder *d)
-{
-  const int n = d->batch_frames < 0 ? -d->batch_frames : 0;
-  if (n == 0) return d->batch_frames > 0 ? MIJPEG_OK : set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no batch has been submitted");
-  d->batch_frames = 0;
-  std::vector<HostDecoder *> hosts((size_t)n);
-  for (int i = 0; i < n; i++) hosts[(size_t)i] = d->batch_hosts[(size_t)i].get();
-  if (d->pend_n) { // wait for the upload and the Huffman kernel of the submitted batch, then look at what it reported
-    const int pn = d->pend_n;
-    d->pend_n = 0;
-    // The pipeline's one wait on the device.  hipStreamSynchronize blocks on an interrupt after a short spin, and how long the wake-up
-    // takes is the host's business (idle states of the core that takes the interrupt): on some boxes 0.3 ms per wait for seconds
-    // on end -- sixteen chunks of a batch, five milliseconds (profiles/r05/batch4k_stall.txt).  A submitted batch is a
-    // millisecond from done when somebody asks for it: poll the stream for that long, block only beyond.
-    {
-      static const bool no_spin = getenv("MIJPEG_NO_SPIN_WAIT") != nullptr; // A-B measurements
-      const auto t_spin = std::chrono::steady_clock::now();
-      hipError_t q = hipSuccess;
-      while (!no_spin && (q = hipStreamQuery(d->stream)) == hipErrorNotReady) {
-        if (std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(4)) break;
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-      }
-      // hipErrorNotReady is not an error: drop it -- and only it; anything else the query saw (a failed launch of the work it waits
-      // for) is the batch's verdict
-      if (q == hipErrorNotReady) (void)hipGetLastError();
-      else if (q != hipSuccess) HIP_TRY(d, q);
-    }
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
-    d->phase_device += std::chrono::duration<double>(std::chrono::steady_clock::now() - d->pend_t0).count();
-    // the device searched the segments: is every search good?  (The bytes are gone: the caller's fallback takes over.)  Asked first:
-    // the walk of a stream without restart markers follows its search, and has walked nothing behind one that is not good
-    if (d->pend_markers) {
-      const uint32_t *results = d->pend_markers;
-      d->pend_markers = nullptr;
-      if (!device_markers_good(results, d->markers_want_term.data(), pn)) {
-        d->markers_searched -= pn;
-        d->markers_declined += pn;
-        d->pend_walk_round = 0;
-        return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "device marker search: a segment is not the plain case; the host searches such streams (mijpeg_decode_batch_device)");
-      }
-    }
-    if (d->pend_walk_round > 0) { // streams without restart markers: did the walk settle within the rounds it was given?
-      const int rounds = d->pend_walk_round;
-      d->pend_walk_round = 0;
-      if (d->pend_walk_flags[rounds]) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding did not settle in the rounds a submitted batch gets: decode it with mijpeg_decode_batch_device");
-      d->walk_rounds = walk_rounds_needed(d->pend_walk_flags, rounds);
-      if (d->pend_walk_status)
-        if (const int wrc = walk_verdict(d, d->pend_walk_status, pn)) return wrc;
-    }
-    const int rc = evaluate_entropy_status(d, hosts.data(), pn, d->pend_status);
-    if (rc) return rc;
-  }
-  const mijpeg_info &f0 = hosts[0]->info;
-  const bool own_tables = d->batch_own_tables;
-  int rc = MIJPEG_OK;
-  d->batch_info = f0;
-  d->batch_own_tables = own_tables;
-  if (own_tables) {
-    // the batch's info then carries, per COMPONENT, the largest delta any image has at each position: what the range
-    // gates of the kernel selection look at
-    d->batch_quant_host.assign((size_t)n * 4 * 64, 1);
-    mijpeg_info &bi = d->batch_info;
-    for (int c = 0; c < f0.components; c++) {
-      bi.quant_index[c] = (uint8_t)c;
-      for (int k = 0; k < 64; k++) bi.quant[c][k] = 0;
-    }
-    for (int i = 0; i < n; i++) {
-      const mijpeg_info &f = hosts[(size_t)i]->info;
-      for (int c = 0; c < f.components; c++)
-        for (int k = 0; k < 64; k++) {
-          const uint16_t q = f.quant[f.quant_index[c]][k];
-          d->batch_quant_host[((size_t)i * 4 + c) * 64 + k] = q;
-          bi.quant[c][k] = std::max(bi.quant[c][k], q);
-        }
-    }
-    const size_t bytes = d->batch_quant_host.size() * sizeof(uint16_t);
-    rc = ensure_dev(d, (void **)&d->batch_quant_dev, &d->batch_quant_cap, bytes);
-    if (rc) return rc;
-    HIP_TRY(d, hipMemcpyAsync(d->batch_quant_dev, d->batch_quant_host.data(), bytes, hipMemcpyHostToDevice, d->stream));
-  }
-  d->batch_info.fast_arith = 1;
-  for (int i = 0; i < n; i++) { // the batch is as fast as its most demanding image
-    const mijpeg_info &f = hosts[(size_t)i]->info;
-    if (!f.fast_arith) d->batch_info.fast_arith = 0;
-    for (int c = 0; c < f.components; c++) d->batch_info.range_max[c] = std::max(d->batch_info.range_max[c], f.range_max[c]);
-  }
-  d->batch_frames = n;
-  if (!own_tables && !d->batch_info.xt) { // the next batch of this shape may launch its reconstruction on this range check
-    SpecHint &h = *spec_hint();
-    std::lock_guard<std::mutex> lock(h.m);
-    h.info = d->batch_info;
-    h.valid = true;
-  }
-  return MIJPEG_OK;
-}
-
-// A speculative launch is validated: the batch is finished the ordinary way (wait, errors, range check), and where the range
-// check is not the one the launch assumed the reconstruction runs again with the kernel the real one selects.
-extern "C++" int settle_speculation(mijpeg_decoder *d) // (C++ linkage as decoder.hpp declares it: ragged_decode.cpp calls it too)
-{
-  if (!d->spec_active) return MIJPEG_OK;
-  d->spec_active = false;
-  d->spec_redone = false;
-  if (d->batch_frames == 0) return MIJPEG_OK; // (the batch was abandoned: another stream was set on the object)
-  if (d->batch_frames < 0) {
-    const int rc = finish_batch(d);
-    if (rc) return rc; // (the stream is damaged, the walk had not settled ...: nothing of the speculative pixels counts)
-  }
-  bool holds = d->batch_info.fast_arith != 0;
-  for (int c = 0; c < d->batch_info.components; c++) holds = holds && d->batch_info.range_max[c] <= d->spec_assumed[c];
-  if (holds) return MIJPEG_OK;
-  d->spec_redone = true;
-  d->spec_redone_count++;
-  return mijpeg_reconstruct_batch_device(d, d->spec_dst, d->spec_frame_stride, d->spec_row_stride, d->spec_flags & ~MIJPEG_FLAG_SPECULATIVE, 1);
-}
-
-int mijpeg_decode_batch_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals)
-try {
-  if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  return with_device_markers(d, n, [&](bool markers) { return submit_batch(d, streams, sizes, n, min_intervals, false, markers); });
-} catch (...) { return boundary_catch(d, "mijpeg_decode_batch_device"); }
-
-static int prepare_batch_host(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, bool markers)
-{
-  if (const int prc = settle_pending(d)) return prc;
-  d->batch_frames = 0;
-  if (d->batch_hosts.size() < (size_t)n) d->batch_hosts.resize((size_t)n); // never shrinks: a pipeline's chunks differ in size, and
-  for (auto &h : d->batch_hosts)                                         // a parser that is thrown away takes its grown vectors along
-    if (!h) h.reset(new HostDecoder());
-  std::vector<size_t> slot;
-  const size_t total = stream_slots(sizes, n, slot);
-  uint8_t *stage;
-  if (d->device >= 0) {
-    HIP_TRY(d, hipSetDevice(d->device));
-    if (const int src = ensure_pinned(d, &d->stage_host, &d->stage_cap, total)) return src;
-    stage = d->stage_host;
-  } else {
-    if (d->host_stage.size() < total) d->host_stage.resize(total);
-    stage = d->host_stage.data();
-  }
-  std::vector<int> rcs((size_t)n, 0);
-  const int workers = std::min(n, default_threads());
-  parallel_for(workers, [&](int w) {
-    for (int i = w; i < n; i += workers) {
-      HostDecoder &h = *d->batch_hosts[(size_t)i];
-      if (markers) h.set_skip_search(); // (the host half of the marker route: headers, and one memcpy of the raw segment)
-      else h.set_unstuff_sink(stage + slot[(size_t)i], sizes[i]);
-      rcs[(size_t)i] = h.parse(streams[i], sizes[i], false);
-      if (markers && !rcs[(size_t)i] && !h.scans.empty() && h.scans[0].search_skipped)
-        memcpy(stage + slot[(size_t)i], streams[i] + h.scans[0].ecs_begin, sizes[i] - h.scans[0].ecs_begin);
-    }
-  });
-  for (int i = 0; i < n; i++)
-    if (rcs[(size_t)i]) return set_error(d, rcs[(size_t)i], d->batch_hosts[(size_t)i]->error.message);
-  for (int i = 0; i < n && markers; i++)
-    if (const char *why = device_markers_obstacle(*d->batch_hosts[(size_t)i], sizes[i])) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
-  for (int i = 0; i < n && markers; i++) d->markers_staged.emplace_back(slot[(size_t)i], sizes[i] - d->batch_hosts[(size_t)i]->scans[0].ecs_begin);
-  return MIJPEG_OK;
-}
-
-int mijpeg_prepare_batch_host(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n)
-try {
-  if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  return with_device_markers(d, n, [&](bool markers) { return prepare_batch_host(d, streams, sizes, n, markers); });
-} catch (...) { return boundary_catch(d, "mijpeg_prepare_batch_host"); }
-
-int mijpeg_set_device_markers(mijpeg_decoder *d, int on)
-try {
-  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (on != 0 && on != 1) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "mijpeg_set_device_markers: on must be 0 or 1");
-  d->device_markers = on;
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_set_device_markers"); }
-
-int mijpeg_device_markers_stats(mijpeg_decoder *d, int64_t *searched, int64_t *declined)
-try {
-  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (searched) *searched = d->markers_searched;
-  if (declined) *declined = d->markers_declined;
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_device_markers_stats"); }
-
-const uint8_t *mijpeg_device_markers_staging(mijpeg_decoder *d, int image, size_t *bytes)
-{
-  if (!d || image < 0 || (size_t)image >= d->markers_staged.size()) return nullptr;
-  const uint8_t *stage = d->device >= 0 ? d->stage_host : d->host_stage.data();
-  if (!stage) return nullptr;
-  if (bytes) *bytes = d->markers_staged[(size_t)image].second;
-  return stage + d->markers_staged[(size_t)image].first;
-}
-
-int64_t mijpeg_device_marker_search(mijpeg_decoder *d, const uint8_t *segment, size_t size, int32_t expect, uint8_t *dst, size_t capacity,
-                                    uint32_t *begin, uint32_t *end, uint32_t *term, uint32_t *flags)
-try {
-  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (expect > (1 << 26)) return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "mijpeg_device_marker_search: expect");
-  return device_marker_search(d, segment, size, expect, dst, capacity, begin, end, term, flags);
-} catch (...) { return boundary_catch(d, "mijpeg_device_marker_search"); }
-
-int mijpeg_submit_batch_device(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, int min_intervals)
-try {
-  if (!d || !streams || !sizes || n < 1) return MIJPEG_ERR_INVALID_PARAMETER;
-  return with_device_markers(d, n, [&](bool markers) { return submit_batch(d, streams, sizes, n, min_intervals, true, markers); });
-} catch (...) { return boundary_catch(d, "mijpeg_submit_batch_device"); }
-
 int mijpeg_synchronize(mijpeg_decoder *d)
 try {
   if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
@@ -1072,105 +726,6 @@ try {
   HIP_TRY(d, hipStreamWaitEvent((hipStream_t)client_stream, d->chain_ev, 0));
   return MIJPEG_OK;
 } catch (...) { return boundary_catch(d, "mijpeg_stream_wait"); }
-
-int mijpeg_finish_batch_device(mijpeg_decoder *d)
-try {
-  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device >= 0) HIP_TRY(d, hipSetDevice(d->device));
-  if (d->spec_active) return settle_speculation(d);
-  return finish_batch(d);
-} catch (...) { return boundary_catch(d, "mijpeg_finish_batch_device"); }
-
-int mijpeg_batch_speculation(mijpeg_decoder *d, int64_t *launched, int64_t *redone)
-try {
-  if (!d) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (launched) *launched = d->spec_launched;
-  if (redone) *redone = d->spec_redone_count;
-  return d->spec_redone ? 1 : 0;
-} catch (...) { return boundary_catch(d, "mijpeg_batch_speculation"); }
-
-int mijpeg_reconstruct_batch_device(mijpeg_decoder *d, void *dst_device, int64_t frame_stride, int64_t row_stride, uint32_t flags, int sync)
-try {
-  if (!d || !dst_device) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device >= 0) HIP_TRY(d, hipSetDevice(d->device));
-  bool speculate = false;
-  mijpeg_info assumed;
-  if (d->batch_frames < 0 && (flags & MIJPEG_FLAG_SPECULATIVE) && !sync && d->pend_n && !d->pend_walk_round && !d->batch_own_tables && !d->spec_active) {
-    // A submitted batch whose Huffman kernel may still be running: launch the reconstruction behind it on the range check the
-    // last batch of this shape and these tables reported (rounded up to the selection's next gate) instead of waiting for this
-    // one's.  The pipeline's host thread never blocks on the device; mijpeg_finish_batch_device validates.
-    const mijpeg_info &f0 = d->batch_hosts[0]->info;
-    SpecHint &h = *spec_hint();
-    std::lock_guard<std::mutex> lock(h.m);
-    if (h.valid && h.info.fast_arith && same_shape_and_tables(h.info, f0)) {
-      assumed = f0;
-      assumed.fast_arith = 1;
-      speculate = true;
-      for (int c = 0; c < f0.components; c++) {
-        assumed.range_max[c] = next_gate_below(h.info.range_max[c]);
-        if (assumed.range_max[c] < 0) speculate = false;
-      }
-    }
-  }
-  if (d->batch_frames < 0 && !speculate) { // submitted with mijpeg_submit_batch_device: wait for it now
-    const int rc = d->spec_active ? settle_speculation(d) : finish_batch(d);
-    if (rc) return rc;
-  }
-  if (d->batch_frames < 1 && !speculate) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded batch: call mijpeg_decode_batch_device first");
-  mijpeg_batch b = batch_of(speculate ? assumed : d->batch_info, d->coef_dev, dst_device, row_stride, frame_stride, speculate ? -d->batch_frames : d->batch_frames,
-                            flags & ~(MIJPEG_FLAG_DEVICE_OUTPUT | MIJPEG_FLAG_NO_UPSAMPLING | MIJPEG_FLAG_SPECULATIVE));
-  b.quant_dev = d->batch_own_tables ? d->batch_quant_dev : nullptr;
-  if (const int rc = reconstruct_on(d, b, nullptr, "batch")) return rc;
-  if (speculate) {
-    d->spec_active = true;
-    d->spec_redone = false;
-    d->spec_dst = dst_device;
-    d->spec_frame_stride = frame_stride;
-    d->spec_row_stride = row_stride;
-    d->spec_flags = flags;
-    for (int c = 0; c < MIJPEG_MAX_COMPONENTS; c++) d->spec_assumed[c] = assumed.range_max[c];
-    d->spec_launched++;
-    return MIJPEG_OK;
-  }
-  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_batch_device"); }
-
-int mijpeg_reconstruct_batch_planar_device(mijpeg_decoder *d, void *dst_device, int64_t frame_stride, int64_t plane_stride, int64_t row_stride, uint32_t flags,
-                                           int sync)
-try {
-  if (!d || !dst_device) return MIJPEG_ERR_INVALID_PARAMETER;
-  if (d->device >= 0) HIP_TRY(d, hipSetDevice(d->device));
-  if (d->batch_frames < 0) { // submitted with mijpeg_submit_batch_device: wait for it now
-    const int rc = d->spec_active ? settle_speculation(d) : finish_batch(d);
-    if (rc) return rc;
-  }
-  if (d->batch_frames < 1) return set_error(d, MIJPEG_ERR_OBJECT_DOESNT_EXIST, "no decoded batch: call mijpeg_decode_batch_device first");
-  const mijpeg_info &f = d->batch_info;
-  void *first[MIJPEG_MAX_COMPONENTS] = {dst_device, dst_device, dst_device, dst_device};
-  if (planar_check(f, first, row_stride) || plane_stride < row_stride * f.height || frame_stride < plane_stride * f.components)
-    return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "planar destination: the strides do not hold a line, a plane or a frame");
-  d->planar_stats = mijpeg_planar_stats{};
-  std::vector<PlanarItem> items((size_t)d->batch_frames);
-  for (int i = 0; i < d->batch_frames; i++) {
-    PlanarItem &it = items[(size_t)i];
-    it.info = &d->batch_info;
-    it.coef_dev = d->coef_dev + (int64_t)i * f.coef_count;
-    for (int c = 0; c < f.components; c++) it.planes[c] = (uint8_t *)dst_device + i * frame_stride + c * plane_stride;
-    for (int c = f.components; c < MIJPEG_MAX_COMPONENTS; c++) it.planes[c] = nullptr;
-    it.row_stride = row_stride;
-    if (d->batch_own_tables) {
-      it.own_deltas = d->batch_quant_host.data() + (size_t)i * 4 * 64;
-      it.own_deltas_dev = d->batch_quant_dev + (size_t)i * 4 * 64;
-    }
-  }
-  RaggedFailures failures;
-  const int rc = reconstruct_planar_items(d, items.data(), d->batch_frames, flags & PLANAR_FLAGS, failures);
-  if (rc) return set_error(d, rc, rc == MIJPEG_ERR_DEVICE ? "planar reconstruction: a kernel launch failed" : "planar reconstruction not available for this batch");
-  d->planar_stats.images = d->batch_frames;
-  if (sync) HIP_TRY(d, hipStreamSynchronize(d->stream));
-  return MIJPEG_OK;
-} catch (...) { return boundary_catch(d, "mijpeg_reconstruct_batch_planar_device"); }
 
 const int16_t *mijpeg_device_coefficients(mijpeg_decoder *d) { return (d && d->uploaded) ? d->coef_dev : nullptr; }
 

@@ -1,6 +1,6 @@
-// decoder.hpp -- the decoder object of the C ABI and what its translation units share: capi.cpp (the object, single images, uniform
-// batches), rect_service.cpp (rectangles), entropy_device.cpp, reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp,
-// ragged_reconstruct.cpp and encode_device.cpp.
+// decoder.hpp -- the decoder object of the C ABI and what its translation units share: capi.cpp (the object, single images),
+// batch_decode.cpp (uniform batches, the header pass of a list, the marker route option), rect_service.cpp (rectangles),
+// entropy_device.cpp, reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp, ragged_reconstruct.cpp and encode_device.cpp.
 // Private to libmijpeg.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include <chrono>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -214,10 +215,26 @@ int ensure_dev(mijpeg_decoder *d, void **ptr, size_t *cap, size_t bytes);
 int ensure_cached(mijpeg_decoder *d, bool pinned, void **ptr, size_t *cap, size_t bytes);
 
 // capi.cpp: the coefficient store for `count` int16 (device mirror; pinned host planes where need_host); a batch that was submitted
-// and not waited for is settled before its staging buffers are rewritten; a speculative launch is validated
+// and not waited for is settled before its staging buffers are rewritten
 int ensure_coef_store(mijpeg_decoder *d, size_t count, bool need_host = true);
 int settle_pending(mijpeg_decoder *d);
+
+// ---- batch_decode.cpp: uniform batches ----
+// a speculative launch (MIJPEG_FLAG_SPECULATIVE) is validated
 int settle_speculation(mijpeg_decoder *d);
+// The marker route of a call over `images` images (mijpeg_set_device_markers): attempt(true) where the option is on, and
+// attempt(false) -- the ordinary route, as if it were off -- where that declines or the option is off
+int with_device_markers(mijpeg_decoder *d, int images, const std::function<int(bool)> &attempt);
+// The header pass of a list call: d->batch_hosts grows to n parsers (and never shrinks), stream i is parsed by batch_hosts[i] on
+// worker i mod min(n, default_threads()), its code goes to rcs[i].  The caller's steps, once per stream on that worker: arm(h, i)
+// before the parse (skip-search, the unstuff sink; a code other than 0 is the stream's, and it is not parsed), after(h, i, rc)
+// behind it (optional)
+using StreamArm = std::function<int(mij::HostDecoder &, int)>;
+using StreamAfter = std::function<void(mij::HostDecoder &, int, int)>;
+void parse_stream_headers(mijpeg_decoder *d, const uint8_t *const *streams, const size_t *sizes, int n, std::vector<int> &rcs, const StreamArm &arm,
+                          const StreamAfter &after = nullptr);
+// ... and the first n of those parsers as device_entropy_batch takes them
+std::vector<mij::HostDecoder *> batch_host_list(mijpeg_decoder *d, int n);
 
 // ... and ensure_dev's pinned counterpart, for staging buffers that are not handed to the buffer cache
 inline int ensure_pinned(mijpeg_decoder *d, uint8_t **ptr, size_t *cap, size_t bytes)

@@ -98,22 +98,16 @@ static int decode_ragged(mijpeg_decoder *d, const uint8_t *const *streams, const
   d->ragged_n = 0;
   d->img_valid = d->model_valid = d->uploaded = d->decoded = false;
   d->ragged_stats = mijpeg_ragged_stats{};
-  if (d->batch_hosts.size() < (size_t)n) d->batch_hosts.resize((size_t)n);
-  for (auto &h : d->batch_hosts)
-    if (!h) h.reset(new HostDecoder());
   d->ragged.assign((size_t)n, mijpeg_decoder::RaggedImage{});
   // headers and restart markers of all streams, one stream per worker.  mijpeg_set_device_markers: headers only where the parse
   // can leave the search to the device (HostDecoder::set_skip_search; Scan::search_skipped tells) -- such members are searched
   // inside their layout group's launch, beside members that were searched here
   const bool markers = d->device_markers == 1;
-  std::vector<int> rcs((size_t)n, 0);
-  const int workers = std::min(n, default_threads());
-  parallel_for(workers, [&](int w) {
-    for (int i = w; i < n; i += workers) {
-      if (!streams[i] || !sizes[i]) { rcs[(size_t)i] = MIJPEG_ERR_STREAM_EMPTY; continue; }
-      if (markers) d->batch_hosts[(size_t)i]->set_skip_search(); // (armed for the parse that follows)
-      rcs[(size_t)i] = d->batch_hosts[(size_t)i]->parse(streams[i], sizes[i], false);
-    }
+  std::vector<int> rcs;
+  parse_stream_headers(d, streams, sizes, n, rcs, [&](HostDecoder &h, int i) {
+    if (!streams[i] || !sizes[i]) return (int)MIJPEG_ERR_STREAM_EMPTY; // (nothing to parse)
+    if (markers) h.set_skip_search(); // (armed for the parse that follows)
+    return 0;
   });
   auto skipped = [&](int i) { return !rcs[(size_t)i] && !d->batch_hosts[(size_t)i]->scans.empty() && d->batch_hosts[(size_t)i]->scans[0].search_skipped; };
   int64_t searched = 0;

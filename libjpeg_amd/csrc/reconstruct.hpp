@@ -1,5 +1,6 @@
 // reconstruct.hpp -- what reconstruct_device.cpp (kernel selection, workspace and launch of the reconstruction) shares with the
-// decoder object's entry points in capi.cpp, rect_service.cpp, ragged_decode.cpp and ragged_reconstruct.cpp.  Private to libmijpeg.so.
+// decoder object's entry points in capi.cpp, batch_decode.cpp, rect_service.cpp, ragged_decode.cpp and ragged_reconstruct.cpp.
+// Private to libmijpeg.so.
 #pragma once
 #include "decoder.hpp"
 #include "kernels.hpp"
