@@ -979,7 +979,7 @@ int mijpeg_interleave_device(mijpeg_decoder *d, const void *const planes[MIJPEG_
  * The passes are those of the ragged encode with the requant launch in place of the forward launches: launches and host waits do
  * not grow with the list, MIJPEG_ENCODE_RAGGED_PASS_BLOCKS cuts them, 12-bit pictures always get Huffman tables of their own and
  * `optimize` speaks for the 8-bit ones.  The outputs carry the headers every encoder call here writes (DQT, SOF0 / SOF1, DHT, DRI,
- * SOS): APPn, COM and ICC segments of the source are NOT carried across.  Sampling and size never change; the output is never
+ * SOS): APPn, COM and ICC segments of the source are NOT carried across.  Sampling and size change only under a transform (below); the output is never
  * progressive or arithmetic coded (a progressive source comes out sequential).
  * Served: members of the layout groups, and pictures of the single-image route whose object holds int16 planes of a plain Huffman
  * frame of 8 or 12 bits with 1 or 3 components (progressive, SOF1, DNL, 4:4:0, 4:1:1, ...).  A one-component output has sampling
@@ -1028,6 +1028,52 @@ int mijpeg_transcode_plan(const mijpeg_info *source, const mijpeg_transcode_spec
  * q_old and target table q_new (no entry 0), clamped into the coding range of `precision` (8 or 12).  Returns the number of
  * coefficients that were clamped, or MIJPEG_ERR_INVALID_PARAMETER.  The kernel's host twin: one header states the rule for both. */
 int64_t mijpeg_requantize(const int16_t *src, int16_t *dst, int64_t n, const uint16_t q_old[64], const uint16_t q_new[64], int precision);
+
+/* ---- ragged transcode: lossless flips, transposes and rotations -------------------------------------------
+ * What jpegtran -flip / -transpose / -transverse / -rotate does, in the pass of the ragged transcode and on the planes in device
+ * memory: a permutation of blocks, a transposition inside each block, sign changes on odd frequencies -- no pixels, no DCT loss --
+ * by ONE launch per pass of transform_list_kernel for the pictures that have a transform; the others stay with
+ * requant_list_kernel, so a pass has at most two first-stage launches and a list without transforms exactly the launches, waits,
+ * bytes and statistics of mijpeg_transcode_ragged_device.  The codes are jpegtran's JXFORM_CODE; each is "transpose first (T), then
+ * mirror horizontally (MH) and / or vertically (MV)":
+ *   NONE -   FLIP_H MH   FLIP_V MV   TRANSPOSE T   TRANSVERSE T MH MV   ROT_90 T MH (clockwise)   ROT_180 MH MV   ROT_270 T MV
+ * T swaps width and height and every component's sampling factors (4:2:2 becomes 4:4:0) and transposes the quantiser tables; with a
+ * quality the (transposed) source entry at the destination position is the rule's a.  A mirrored axis must be a whole number of MCUs
+ * of the frame after T: otherwise the picture is refused with MIJPEG_ERR_NOT_AVAILABLE (jpegtran -perfect), or, with
+ * MIJPEG_TRANSFORM_TRIM OR-ed in, the partial MCU column or row at the source's far edge is dropped and width or height shrink to the
+ * multiple (a picture that would shrink to nothing is refused).  Axes that are not mirrored keep their partial MCUs.  A
+ * one-component output is 1 x 1 sampled: its MCU is one block. */
+#define MIJPEG_TRANSFORM_NONE 0
+#define MIJPEG_TRANSFORM_FLIP_H 1
+#define MIJPEG_TRANSFORM_FLIP_V 2
+#define MIJPEG_TRANSFORM_TRANSPOSE 3
+#define MIJPEG_TRANSFORM_TRANSVERSE 4
+#define MIJPEG_TRANSFORM_ROT_90 5    /* clockwise */
+#define MIJPEG_TRANSFORM_ROT_180 6
+#define MIJPEG_TRANSFORM_ROT_270 7
+#define MIJPEG_TRANSFORM_TRIM 0x100  /* OR-ed in: drop partial MCUs of a mirrored axis instead of refusing the picture */
+/* mijpeg_transcode_ragged_device with one transform per picture of the decoded batch (NULL: none, the existing call).  A code outside
+ * the eight (with or without TRIM) is MIJPEG_ERR_INVALID_PARAMETER, returned before a device is touched; everything else as there. */
+int mijpeg_transcode_ragged_transformed_device(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, const int32_t *transforms, int optimize,
+                                               uint32_t flags, uint8_t **streams, size_t *sizes, int32_t *status);
+/* mijpeg_transcode_plan under a transform: the output frame with its width, height, sampling and (kept: transposed) tables.  The
+ * refusals of mijpeg_transcode_plan come first; then the geometry's MIJPEG_ERR_NOT_AVAILABLE.  A bad code: INVALID_PARAMETER. */
+int mijpeg_transcode_plan_transformed(const mijpeg_info *source, const mijpeg_transcode_spec *spec, int32_t transform, mijpeg_info *out,
+                                      int32_t *restart_interval, int32_t *kept);
+/* The kernel's host twin over ONE component's plane in host memory (blocks of 64 coefficients, natural order): src, src_bw x src_bh
+ * blocks, under table q_old (in the SOURCE's order) -> dst (another buffer), dst_bw x dst_bh blocks, under q_new (the destination's
+ * order).  transform: one of the eight codes (TRIM is the plan's matter: it shows in dst_bw / dst_bh).  A destination block
+ * without a source block is zero.  Returns the number of clamped coefficients, or MIJPEG_ERR_INVALID_PARAMETER. */
+int64_t mijpeg_transform_blocks(const int16_t *src, int32_t src_bw, int32_t src_bh, int16_t *dst, int32_t dst_bw, int32_t dst_bh, int32_t transform,
+                                const uint16_t q_old[64], const uint16_t q_new[64], int precision);
+/* What the transforms of the object's last transcode call did (beside mijpeg_transcode_ragged_stats). */
+typedef struct mijpeg_transcode_transform_stats {
+  int32_t transformed;         /* served pictures with a transform other than NONE                       */
+  int32_t trimmed;             /* ... of them that lost a partial MCU column or row                      */
+  int32_t geometry_refusals;   /* pictures refused because a mirrored axis is no whole number of MCUs    */
+  int32_t transform_launches;  /* one per pass that holds a transformed picture                          */
+} mijpeg_transcode_transform_stats;
+int mijpeg_transcode_transform_stats_get(mijpeg_decoder *d, mijpeg_transcode_transform_stats *out);
 
 /* Worker threads mijpeg_decode_coefficients uses for threads <= 0 (MIJPEG_THREADS overrides; default min(cores, 64)). */
 int mijpeg_default_threads(void);

@@ -155,6 +155,16 @@ class MijpegTranscodeRaggedStats(C.Structure):
 TRANSCODE_KEEP, TRANSCODE_SKIP = 0, -1  # mijpeg_transcode_spec.quality: the source's tables; no stream for this picture
 
 
+class MijpegTranscodeTransformStats(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("transformed", "trimmed", "geometry_refusals", "transform_launches")]
+
+
+# MIJPEG_TRANSFORM_*: jpegtran's JXFORM_CODE, and the bit that trims partial MCUs of a mirrored axis
+(TRANSFORM_NONE, TRANSFORM_FLIP_H, TRANSFORM_FLIP_V, TRANSFORM_TRANSPOSE, TRANSFORM_TRANSVERSE, TRANSFORM_ROT_90, TRANSFORM_ROT_180,
+ TRANSFORM_ROT_270) = range(8)
+TRANSFORM_TRIM = 0x100
+
+
 # sampling factors (hsamp, vsamp) per component of the layouts the encoder takes by name
 ENCODE_LAYOUTS = {"444": ((1, 1, 1), (1, 1, 1)), "420": ((2, 1, 1), (2, 1, 1)), "422": ((2, 1, 1), (1, 1, 1)), "440": ((1, 1, 1), (2, 1, 1)),
                   "411": ((4, 1, 1), (1, 1, 1))}
@@ -264,6 +274,12 @@ def lib():
             L.mijpeg_transcode_plan.argtypes = [P(MijpegInfo), P(MijpegTranscodeSpec), P(MijpegInfo), P(C.c_int32), P(C.c_int32)]
             L.mijpeg_requantize.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int]
             L.mijpeg_requantize.restype = C.c_int64
+        if hasattr(L, "mijpeg_transcode_ragged_transformed_device"):  # (as above: a build from before the transforms fails by name)
+            L.mijpeg_transcode_ragged_transformed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.mijpeg_transcode_transform_stats_get.argtypes = [C.c_void_p, P(MijpegTranscodeTransformStats)]
+            L.mijpeg_transcode_plan_transformed.argtypes = [P(MijpegInfo), P(MijpegTranscodeSpec), C.c_int32, P(MijpegInfo), P(C.c_int32), P(C.c_int32)]
+            L.mijpeg_transform_blocks.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int]
+            L.mijpeg_transform_blocks.restype = C.c_int64
         L.mijpeg_free.argtypes = [C.c_void_p]
         L.mijpeg_free.restype = None
         L.mijpeg_set_device_markers.argtypes = [C.c_void_p, C.c_int]
@@ -605,20 +621,30 @@ class Decoder:
     def encode_ragged_stats(self) -> dict:
         return self._stats(MijpegEncodeRaggedStats, lib().mijpeg_encode_ragged_get_stats, {"reserved"})
 
-    def transcode_ragged_device(self, specs=None, optimize: bool = False):
+    def transcode_ragged_device(self, specs=None, optimize: bool = False, transforms=None):
         """mijpeg_transcode_ragged_device: the pictures of the last decode_ragged_device call coded again from their quantised planes in
         HBM.  specs: None (keep every picture's tables and restart interval) or one (quality, restart_interval) per
         picture -- quality 1..100, TRANSCODE_KEEP or TRANSCODE_SKIP; restart_interval 0..65535 or -1 for the source's.
+        transforms: None, or one TRANSFORM_* code per picture, TRANSFORM_TRIM OR-ed in where partial MCUs of a mirrored axis are to be
+        dropped (mijpeg_transcode_ragged_transformed_device).
         -> (streams, status): bytes or None per picture, and its status code (0 with None: skipped)."""
         n = getattr(self, "ragged_images", 0)
         arr = None
+        if transforms is not None:
+            transforms = [int(t) for t in transforms]
+            if len(transforms) != n:
+                raise ValueError(f"{len(transforms)} transforms for the {n} images of the ragged batch")
         if specs is not None:
             specs = list(specs)
             if len(specs) != n:
                 raise ValueError(f"{len(specs)} specs for the {n} images of the ragged batch")
             arr = (MijpegTranscodeSpec * max(n, 1))(*[MijpegTranscodeSpec(int(q), int(r)) for q, r in specs])
         ptrs, sizes, status = (C.c_void_p * max(n, 1))(), (C.c_size_t * max(n, 1))(), (C.c_int32 * max(n, 1))()
-        self._check(lib().mijpeg_transcode_ragged_device(self._h, arr, 1 if optimize else 0, 0, ptrs, sizes, status))
+        if transforms is None:
+            self._check(lib().mijpeg_transcode_ragged_device(self._h, arr, 1 if optimize else 0, 0, ptrs, sizes, status))
+        else:
+            codes = (C.c_int32 * max(n, 1))(*transforms)
+            self._check(lib().mijpeg_transcode_ragged_transformed_device(self._h, arr, codes, 1 if optimize else 0, 0, ptrs, sizes, status))
         out = []
         for i in range(n):
             out.append(C.string_at(ptrs[i], sizes[i]) if ptrs[i] else None)
@@ -628,6 +654,10 @@ class Decoder:
     def transcode_ragged_stats(self) -> dict:
         """What the object's last transcode call did (mijpeg_transcode_ragged_stats)."""
         return self._stats(MijpegTranscodeRaggedStats, lib().mijpeg_transcode_ragged_stats_get)
+
+    def transcode_transform_stats(self) -> dict:
+        """What the transforms of the object's last transcode call did (mijpeg_transcode_transform_stats)."""
+        return self._stats(MijpegTranscodeTransformStats, lib().mijpeg_transcode_transform_stats_get)
 
     def xt_params(self) -> MijpegXtParams:
         xt = MijpegXtParams()
@@ -1172,6 +1202,26 @@ def transcode_plan(source: MijpegInfo, quality: int = TRANSCODE_KEEP, restart_in
     spec, out, ri, kept = MijpegTranscodeSpec(int(quality), int(restart_interval)), MijpegInfo(), C.c_int32(), C.c_int32()
     rc = lib().mijpeg_transcode_plan(C.byref(source), C.byref(spec), C.byref(out), C.byref(ri), C.byref(kept))
     return rc, out, ri.value, bool(kept.value)
+
+
+def transcode_plan_transformed(source: MijpegInfo, quality: int = TRANSCODE_KEEP, restart_interval: int = -1, transform: int = TRANSFORM_NONE):
+    """mijpeg_transcode_plan_transformed (no device): transcode_plan under a TRANSFORM_* code (TRANSFORM_TRIM may be OR-ed in)."""
+    spec, out, ri, kept = MijpegTranscodeSpec(int(quality), int(restart_interval)), MijpegInfo(), C.c_int32(), C.c_int32()
+    rc = lib().mijpeg_transcode_plan_transformed(C.byref(source), C.byref(spec), int(transform), C.byref(out), C.byref(ri), C.byref(kept))
+    return rc, out, ri.value, bool(kept.value)
+
+
+def transform_blocks(plane: np.ndarray, dst_bh: int, dst_bw: int, transform: int, q_old, q_new, precision: int = 8):
+    """mijpeg_transform_blocks, the host twin of transform_list_kernel: one component's plane (blocks_h, blocks_w, 64) int16 under
+    table q_old (the source's order) -> ((dst_bh, dst_bw, 64) under q_new (the destination's order), how many values were clamped)."""
+    src = np.ascontiguousarray(plane, np.int16)
+    dst = np.empty((int(dst_bh), int(dst_bw), 64), np.int16)
+    a, b = np.ascontiguousarray(q_old, np.uint16).reshape(64), np.ascontiguousarray(q_new, np.uint16).reshape(64)
+    clamped = lib().mijpeg_transform_blocks(src.ctypes.data, src.shape[1], src.shape[0], dst.ctypes.data, int(dst_bw), int(dst_bh), int(transform), a.ctypes.data,
+                                            b.ctypes.data, int(precision))
+    if clamped < 0:
+        raise MijpegError(int(clamped), "mijpeg_transform_blocks failed")
+    return dst, int(clamped)
 
 
 def requantize(blocks: np.ndarray, q_old, q_new, precision: int = 8):

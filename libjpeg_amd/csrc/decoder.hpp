@@ -169,6 +169,7 @@ struct mijpeg_decoder {
   // planar input (mijpeg_encode_ragged_planar_device16): what the last call did; the interleaved pictures of its two-pass route
   // lie in enc_dev
   mijpeg_encode_planar_stats eplanar_stats{};
+  mijpeg_transcode_transform_stats transform_stats{}; // ... and what its transforms did
   mijpeg_transcode_ragged_stats transcode_stats{}; // ragged transcode (encode_device.cpp; its passes use the eragged_ buffers): what the last call did
   double eragged_forward_s = 0; // MIJPEG_ENCODE_RAGGED_TIME_FORWARD: device time of the last ragged encode's forward stages (0: not timed)
   hipStream_t stream = nullptr;

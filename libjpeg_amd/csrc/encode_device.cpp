@@ -22,6 +22,8 @@
 // The RAGGED TRANSCODE (mijpeg_transcode_ragged_device) is the same pass with another first stage: the pictures are those
 // of the object's decoded ragged batch, `forward` is ONE launch of requant_list_kernel (requant.hip) from the decode's stores into the
 // pass's coefficient store, its range flags come back with the plain sizes, and a flagged picture's piece is dropped at assembly.
+// Pictures that are flipped, transposed or rotated on the way (mijpeg_transcode_ragged_transformed_device) leave that launch
+// for ONE of transform_list_kernel (transform.hip) over the same descriptors and flags.
 #include <stdlib.h>
 #include <string.h>
 
@@ -288,11 +290,18 @@ struct EncodePass {
   }
 
   // a transcode pass's first stage: the planes of all its pictures requantised (or copied, where the tables are kept) into the
-  // pass's coefficient store, range-checked, ONE launch
+  // pass's coefficient store, range-checked, ONE launch -- and ONE more for the pictures that are flipped, transposed or rotated on
+  // the way; a list of them alone has no requant launch
   int requant()
   {
-    if (const int e = launch_requant_list(a.requant, a.requant_grid, stream)) return hip_fail(d, (hipError_t)e, "requant_list_kernel launch");
-    d->transcode_stats.requant_launches++;
+    if (a.requant_grid) {
+      if (const int e = launch_requant_list(a.requant, a.requant_grid, stream)) return hip_fail(d, (hipError_t)e, "requant_list_kernel launch");
+      d->transcode_stats.requant_launches++;
+    }
+    if (a.transform_grid) {
+      if (const int e = launch_transform_list(a.transform, a.transform_grid, stream)) return hip_fail(d, (hipError_t)e, "transform_list_kernel launch");
+      d->transform_stats.transform_launches++;
+    }
     return MIJPEG_OK;
   }
 
@@ -621,11 +630,15 @@ int child_planes(mijpeg_decoder *d, mijpeg_decoder *c, const mijpeg_info &f, con
   return MIJPEG_OK;
 }
 
-int transcode_entry(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes, int32_t *status)
+int transcode_entry(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, const int32_t *transforms, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes,
+                    int32_t *status)
 {
   if (!d || !streams || !sizes || !status || flags != 0) return MIJPEG_ERR_INVALID_PARAMETER;
   const int n = d->ragged_n;
   for (int i = 0; i < n; i++) { streams[i] = nullptr; sizes[i] = 0; status[i] = MIJPEG_OK; }
+  for (int i = 0; transforms && i < n; i++)
+    if (!transform_in_order(transforms[i]))
+      return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "transform " + std::to_string(i) + ": one of MIJPEG_TRANSFORM_NONE .. ROT_270, with or without MIJPEG_TRANSFORM_TRIM");
   for (int i = 0; specs && i < n; i++)
     if (!transcode_spec_in_order(specs[i]))
       return set_error(d, MIJPEG_ERR_INVALID_PARAMETER, "transcode spec " + std::to_string(i) + ": quality is 1 .. 100, KEEP or SKIP, restart_interval 0 .. 65535 or -1");
@@ -636,13 +649,15 @@ int transcode_entry(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int o
   mijpeg_transcode_ragged_stats &stats = d->transcode_stats;
   stats = mijpeg_transcode_ragged_stats{};
   stats.pictures = n;
+  mijpeg_transcode_transform_stats &tstats = d->transform_stats;
+  tstats = mijpeg_transcode_transform_stats{};
   // the plan: who is served, every served picture's output frame and its place in the passes
   const mijpeg_transcode_spec keep{MIJPEG_TRANSCODE_KEEP, -1};
   std::vector<int> picture; // of served slot k
   std::vector<mijpeg_encode_frame> frames;
   std::vector<mijpeg_encode_ragged_item> items;
   std::vector<RequantSource> sources;
-  std::vector<char> kept;
+  std::vector<char> kept, trimmed;
   mijpeg_encode_ragged_totals totals;
   memset(&totals, 0, sizeof(totals));
   const uint32_t pass_blocks = pass_blocks_setting();
@@ -658,8 +673,12 @@ int transcode_entry(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int o
     memset(&it, 0, sizeof(it));
     int ri = 0;
     bool keeps = false;
-    if ((status[i] = transcode_plan_one(r.info, spec, it.info, ri, keeps, it.blocks, it.intervals))) continue;
-    RequantSource src{r.info, d->coef_dev + r.coef_base};
+    TransformPlan how;
+    if ((status[i] = transcode_plan_one(r.info, spec, it.info, ri, keeps, it.blocks, it.intervals, transforms ? transforms[i] : MIJPEG_TRANSFORM_NONE, &how))) {
+      tstats.geometry_refusals += how.geometry;
+      continue;
+    }
+    RequantSource src{r.info, d->coef_dev + r.coef_base, how.bits};
     if (r.group < 0) {
       if ((rc = child_planes(d, r.child, r.info, &src.planes))) break;
       stats.children++;
@@ -676,6 +695,7 @@ int transcode_entry(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int o
     items.push_back(it);
     sources.push_back(src);
     kept.push_back(keeps);
+    trimmed.push_back(how.trimmed);
   }
   // the passes: an encode pass each, its first stage the requant launch (the counters of the last ragged encode stay that call's)
   const int m = (int)picture.size();
@@ -705,7 +725,12 @@ int transcode_entry(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int o
       streams[i] = out[(size_t)k];
       sizes[i] = out_size[(size_t)k];
       status[i] = out_status[(size_t)k];
-      if (streams[i]) { stats.served++; stats.kept += kept[(size_t)k]; }
+      if (streams[i]) {
+        stats.served++;
+        stats.kept += kept[(size_t)k];
+        tstats.transformed += sources[(size_t)k].transform != 0;
+        tstats.trimmed += trimmed[(size_t)k];
+      }
     }
     for (int i = 0; i < n; i++) stats.refused += status[i] != MIJPEG_OK;
   }
@@ -720,11 +745,56 @@ extern "C" {
 int mijpeg_transcode_ragged_device(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, int optimize, uint32_t flags, uint8_t **streams, size_t *sizes,
                                    int32_t *status)
 try {
-  return transcode_entry(d, specs, optimize, flags, streams, sizes, status);
+  return transcode_entry(d, specs, nullptr, optimize, flags, streams, sizes, status);
 } catch (...) {
   if (d) drop_streams(streams, sizes, d->ragged_n);
   return boundary_catch(d, "mijpeg_transcode_ragged_device");
 }
+
+int mijpeg_transcode_ragged_transformed_device(mijpeg_decoder *d, const mijpeg_transcode_spec *specs, const int32_t *transforms, int optimize, uint32_t flags,
+                                               uint8_t **streams, size_t *sizes, int32_t *status)
+try {
+  return transcode_entry(d, specs, transforms, optimize, flags, streams, sizes, status);
+} catch (...) {
+  if (d) drop_streams(streams, sizes, d->ragged_n);
+  return boundary_catch(d, "mijpeg_transcode_ragged_transformed_device");
+}
+
+int mijpeg_transcode_transform_stats_get(mijpeg_decoder *d, mijpeg_transcode_transform_stats *out)
+try {
+  if (!d || !out) return MIJPEG_ERR_INVALID_PARAMETER;
+  *out = d->transform_stats;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(d, "mijpeg_transcode_transform_stats_get"); }
+
+int mijpeg_transcode_plan_transformed(const mijpeg_info *source, const mijpeg_transcode_spec *spec, int32_t transform, mijpeg_info *out, int32_t *restart_interval,
+                                      int32_t *kept)
+try {
+  if (out) memset(out, 0, sizeof(*out));
+  if (restart_interval) *restart_interval = 0;
+  if (kept) *kept = 0;
+  if (!source || !spec || !out || !restart_interval || !kept || !transcode_spec_in_order(*spec) || !transform_in_order(transform)) return MIJPEG_ERR_INVALID_PARAMETER;
+  if (spec->quality == MIJPEG_TRANSCODE_SKIP) return MIJPEG_OK;
+  int ri = 0;
+  bool keeps = false;
+  uint32_t blocks = 0, intervals = 0;
+  const int rc = transcode_plan_one(*source, *spec, *out, ri, keeps, blocks, intervals, transform);
+  if (rc) return rc;
+  *restart_interval = ri;
+  *kept = keeps;
+  return MIJPEG_OK;
+} catch (...) { return boundary_catch(nullptr, "mijpeg_transcode_plan_transformed"); }
+
+int64_t mijpeg_transform_blocks(const int16_t *src, int32_t src_bw, int32_t src_bh, int16_t *dst, int32_t dst_bw, int32_t dst_bh, int32_t transform,
+                                const uint16_t q_old[64], const uint16_t q_new[64], int precision)
+try {
+  if (!src || !dst || src == dst || src_bw < 1 || src_bh < 1 || dst_bw < 1 || dst_bh < 1 || transform < 0 || transform > MIJPEG_TRANSFORM_ROT_270 || !q_old || !q_new ||
+      (precision != 8 && precision != 12))
+    return MIJPEG_ERR_INVALID_PARAMETER;
+  for (int k = 0; k < 64; k++)
+    if (!q_old[k] || !q_new[k]) return MIJPEG_ERR_INVALID_PARAMETER;
+  return transform_blocks(src, src_bw, src_bh, dst, dst_bw, dst_bh, transform_bits(transform), q_old, q_new, precision);
+} catch (...) { return boundary_catch(nullptr, "mijpeg_transform_blocks"); }
 
 int mijpeg_transcode_ragged_stats_get(mijpeg_decoder *d, mijpeg_transcode_ragged_stats *out)
 try {

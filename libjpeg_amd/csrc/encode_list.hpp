@@ -6,7 +6,9 @@
 // planes adds a plane table to the pass and a third set of work lists, through defaulted arguments; tests/cxx/
 // encode_list_planar_tables.cpp is their program.  A pass of the ragged transcode is the same pass with another first
 // stage: transcode_plan_one makes a decoded picture's output frame, and a layout built with `sources` carries the requant work list,
-// descriptors and range flags (requant.hpp) in place of the forward lists; tests/cxx/transcode_tables.cpp.  encode_device.cpp enqueues, waits
+// descriptors and range flags (requant.hpp) in place of the forward lists; tests/cxx/transcode_tables.cpp.  Pictures with a flip,
+// transpose or rotation (transform.hpp) get their output frame from the same planner and a second work list in the same
+// layout; tests/cxx/transform_tables.cpp.  encode_device.cpp enqueues, waits
 // and copies.  Calls nothing of the HIP runtime: a plain host compiler builds tests/cxx/encode_list_tables.cpp around it and
 // encoder.cpp.  Private to libmijpeg.so.
 #pragma once
@@ -20,6 +22,7 @@
 #include "forward.hpp"
 #include "hencode.hpp"
 #include "requant.hpp"
+#include "transform.hpp"
 
 namespace mij {
 
@@ -207,8 +210,22 @@ inline bool henc_frame_geometry(HencArgs &a, const mijpeg_info &info, int ri); /
 //   a quality   what picture_info_of completes for the source's shape, sampling and precision: every component on table 0
 //   kept        the same layout with the source's tables and quant_index, which enc_write_headers writes generally
 // A one-component scan is not interleaved, so its output has sampling factors 1 x 1: the coders walk info.mcus_x * mcus_y blocks.
-inline int transcode_plan_one(const mijpeg_info &src, const mijpeg_transcode_spec &spec, mijpeg_info &out, int &ri, bool &kept, uint32_t &blocks, uint32_t &intervals)
+// transform (a code of mijpeg.h in order): under T width and height and every component's sampling factors swap and kept
+// tables are transposed; a mirrored axis that is no whole number of the output's MCUs is trimmed to one (TRIM) or refuses the
+// picture -- after the refusals above, with MIJPEG_ERR_NOT_AVAILABLE.  how: what became of the transform.
+struct TransformPlan {
+  uint32_t bits = 0;     // T / MH / MV
+  bool trimmed = false;  // a partial MCU column or row was dropped
+  bool geometry = false; // refused: a mirrored axis is no whole number of MCUs, or nothing is left of it
+};
+inline int transcode_plan_one(const mijpeg_info &src, const mijpeg_transcode_spec &spec, mijpeg_info &out, int &ri, bool &kept, uint32_t &blocks, uint32_t &intervals,
+                              int32_t transform = MIJPEG_TRANSFORM_NONE, TransformPlan *how = nullptr)
 {
+  TransformPlan local;
+  TransformPlan &tp = how ? *how : local;
+  tp = TransformPlan{};
+  tp.bits = transform_bits(transform);
+  const bool T = tp.bits & TRANSFORM_T;
   auto refuse = [&](int code) { memset(&out, 0, sizeof(out)); return code; };
   kept = spec.quality == MIJPEG_TRANSCODE_KEEP;
   ri = spec.restart_interval < 0 ? src.restart_interval : spec.restart_interval;
@@ -219,12 +236,27 @@ inline int transcode_plan_one(const mijpeg_info &src, const mijpeg_transcode_spe
   if (src.components == 3) {
     per_mcu = 0;
     for (int c = 0; c < 3; c++) {
-      hs[c] = src.hsamp[c];
-      vs[c] = src.vsamp[c];
+      hs[c] = T ? src.vsamp[c] : src.hsamp[c];
+      vs[c] = T ? src.hsamp[c] : src.vsamp[c];
       per_mcu += hs[c] * vs[c];
     }
   }
-  if (picture_info_of(src.width, src.height, src.components, hs, vs, kept ? 50 : spec.quality, out, src.precision)) return refuse(MIJPEG_ERR_NOT_IMPLEMENTED);
+  // the frame after T, and its mirrored axes in whole MCUs (sampling factors out of order are picture_info_of's to refuse)
+  int32_t width = T ? src.height : src.width, height = T ? src.width : src.height;
+  auto mcu_of = [](const int32_t *s) { return 8 * std::min(4, std::max(1, std::max(s[0], std::max(s[1], s[2])))); }; // (1 .. 4 whatever the source says)
+  const int mcu_w = mcu_of(hs), mcu_h = mcu_of(vs);
+  auto whole = [&](uint32_t mirrored, int32_t &extent, int mcu) {
+    if (!(tp.bits & mirrored) || extent < 1 || extent % mcu == 0) return;
+    if ((transform & MIJPEG_TRANSFORM_TRIM) && extent > mcu) {
+      extent -= extent % mcu;
+      tp.trimmed = true;
+    } else {
+      tp.geometry = true;
+    }
+  };
+  whole(TRANSFORM_MH, width, mcu_w);
+  whole(TRANSFORM_MV, height, mcu_h);
+  if (picture_info_of(width, height, src.components, hs, vs, kept ? 50 : spec.quality, out, src.precision)) return refuse(MIJPEG_ERR_NOT_IMPLEMENTED);
   for (int c = 0; c < src.components; c++) {
     if ((unsigned)src.quant_index[c] >= 4 || src.blocks_w[c] < 1 || src.blocks_h[c] < 1) return refuse(MIJPEG_ERR_NOT_IMPLEMENTED);
     for (int k = 0; k < 64; k++) {
@@ -232,8 +264,9 @@ inline int transcode_plan_one(const mijpeg_info &src, const mijpeg_transcode_spe
       if (a == 0 || (kept && src.precision == 8 && a > 255)) return refuse(MIJPEG_ERR_NOT_IMPLEMENTED); // (no division by it; no baseline DQT holds it)
     }
   }
+  if (tp.geometry) return refuse(MIJPEG_ERR_NOT_AVAILABLE);
   if (kept) {
-    memcpy(out.quant, src.quant, sizeof(out.quant));
+    for (int t = 0; t < 4; t++) transform_table(tp.bits, src.quant[t], out.quant[t]);
     for (int c = 0; c < src.components; c++) out.quant_index[c] = src.quant_index[c];
   }
   HencArgs geometry;
@@ -250,6 +283,7 @@ inline int transcode_plan_one(const mijpeg_info &src, const mijpeg_transcode_spe
 struct RequantSource {
   mijpeg_info info;
   const int16_t *planes;
+  uint32_t transform = 0; // T / MH / MV (transform.hpp); not 0: the picture is transform_list_kernel's
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -446,6 +480,11 @@ struct EncodePassLayout {
   ForwardWorkList requant;                // items (picture * 4 + component) of requant_list_kernel
   size_t rq_pics_at, rq_first_at, rq_item_at, rq_flags_at; // uploaded: a RequantPicture per picture, the work list, the zeroed range flags (n words)
   size_t h_flags;                         // pinned: the flags read back
+  // The transformed pictures of a transcode pass have a work list of their own, transform_list_kernel's, over the same
+  // descriptors and flags, and the pass a word of T / MH / MV bits per picture.  Without such pictures the regions are empty and
+  // every offset and size is what it was
+  ForwardWorkList transform;
+  size_t tf_first_at, tf_item_at, tf_bits_at;
 
   // all_planes: one entry per picture of the list; a planar picture's frame holds plane 0 in `pixels` and the planes' pitch in
   // `row_stride`, its entry planes 1 and 2 (only 8-bit pictures of three components are planar here)
@@ -474,6 +513,9 @@ struct EncodePassLayout {
     rq_first_at = up.take(requant.first.size() * 4);
     rq_item_at = up.take(requant.item.size() * 4);
     rq_flags_at = up.take(sources ? (size_t)n * 4 : 0);
+    tf_first_at = up.take(transform.first.size() * 4);
+    tf_item_at = up.take(transform.item.size() * 4);
+    tf_bits_at = up.take(transform.item.empty() ? 0 : (size_t)n * 4);
     up_bytes = up.at;
     hist_bytes = (size_t)n_own * HENC_HIST_BYTES;
     coder = coder_layout(N, I);
@@ -502,7 +544,7 @@ struct EncodePassLayout {
       const mijpeg_encode_frame &e = frames[p];
       if (sources) { // a transcode pass: the picture's components in the requant work list, its coder geometry
         for (int c = 0; c < items[p].info.components; c++)
-          if (!work_list_append(requant, p * 4u + (uint32_t)c, requant_workgroups(items[p].info, c)))
+          if (!work_list_append(sources[p].transform ? transform : requant, p * 4u + (uint32_t)c, requant_workgroups(items[p].info, c)))
             return refuse(MIJPEG_ERR_NOT_AVAILABLE, "pass too large for one requant launch");
         memset(&hargs[p], 0, sizeof(HencArgs));
         if (!henc_frame_geometry(hargs[p], items[p].info, e.restart_interval)) return refuse(MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU");
@@ -541,6 +583,8 @@ struct EncodePassArgs {
   HencBatchArgs coder; // (plain, ffcount, ffstart, out, total_chunks: once the output arena is there)
   RequantArgs requant; // a transcode pass: its first stage, and its grid
   uint32_t requant_grid;
+  TransformArgs transform; // ... and the first stage of its transformed pictures
+  uint32_t transform_grid;
 };
 
 // The uploaded part into `host` (up_bytes of it), with the addresses it will have at `dev`: a ForwardArgs and a HencArgs per
@@ -556,7 +600,9 @@ inline EncodePassArgs fill_upload(uint8_t *host, uint8_t *dev, const EncodePassL
   for (uint32_t p = 0; p < L.n; p++) {
     const mijpeg_encode_ragged_item &it = L.items[p];
     if (L.sources) {
-      requant_picture_of(((RequantPicture *)(host + L.rq_pics_at))[p], L.sources[p].info, L.sources[p].planes, it.info, coef + it.coef_base);
+      if (L.sources[p].transform) transform_picture_of(((RequantPicture *)(host + L.rq_pics_at))[p], L.sources[p].info, L.sources[p].planes, it.info, coef + it.coef_base, L.sources[p].transform);
+      else requant_picture_of(((RequantPicture *)(host + L.rq_pics_at))[p], L.sources[p].info, L.sources[p].planes, it.info, coef + it.coef_base);
+      if (!L.transform.item.empty()) ((uint32_t *)(host + L.tf_bits_at))[p] = L.sources[p].transform;
       ((uint32_t *)(host + L.rq_flags_at))[p] = 0;
     } else {
       hf[p] = L.fargs[p];
@@ -593,14 +639,26 @@ inline EncodePassArgs fill_upload(uint8_t *host, uint8_t *dev, const EncodePassL
     a.forward.planes = (const ForwardPlanes *)(dev + L.planes_at);
   }
   if (L.sources) {
-    memcpy(host + L.rq_first_at, L.requant.first.data(), L.requant.first.size() * 4);
-    memcpy(host + L.rq_item_at, L.requant.item.data(), L.requant.item.size() * 4);
+    if (!L.requant.item.empty()) { // (every picture of the pass may be transformed)
+      memcpy(host + L.rq_first_at, L.requant.first.data(), L.requant.first.size() * 4);
+      memcpy(host + L.rq_item_at, L.requant.item.data(), L.requant.item.size() * 4);
+    }
     a.requant.pics = (const RequantPicture *)(dev + L.rq_pics_at);
     a.requant.first_wg = (const uint32_t *)(dev + L.rq_first_at);
     a.requant.item = (const uint32_t *)(dev + L.rq_item_at);
     a.requant.items = (uint32_t)L.requant.item.size();
     a.requant.flags = (uint32_t *)(dev + L.rq_flags_at);
-    a.requant_grid = L.requant.first.back();
+    a.requant_grid = L.requant.first.empty() ? 0 : L.requant.first.back();
+  }
+  if (!L.transform.item.empty()) {
+    memcpy(host + L.tf_first_at, L.transform.first.data(), L.transform.first.size() * 4);
+    memcpy(host + L.tf_item_at, L.transform.item.data(), L.transform.item.size() * 4);
+    a.transform.list = a.requant;
+    a.transform.list.first_wg = (const uint32_t *)(dev + L.tf_first_at);
+    a.transform.list.item = (const uint32_t *)(dev + L.tf_item_at);
+    a.transform.list.items = (uint32_t)L.transform.item.size();
+    a.transform.bits = (const uint32_t *)(dev + L.tf_bits_at);
+    a.transform_grid = L.transform.first.back();
   }
   a.coder.pics = (const HencArgs *)(dev + L.hargs_at);
   a.coder.first_block = (const uint32_t *)(dev + L.first_block_at);
