@@ -4,7 +4,7 @@
 //
 // Reference behaviour reproduced, damaged streams included (the state machine of JPEG::ReadInternal with its
 // warn-and-continue paths and the restart marker resynchronisation of codestream/entropyparser.cpp:117-201; see the
-// RefWalker class in host_decoder.cpp):
+// RefWalker class in codestream_walk.cpp):
 //   codestream/tables.cpp:1003-...      marker dispatch (DQT, DHT, DRI, APP14)
 //   marker/quantization.cpp:474-537     DQT, stored de-zigzagged
 //   coding/huffmantemplate.cpp:802-905  DHT -> decoder tables
@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/mijpeg.h"
+#include "worker_pool.hpp" // parallel_for, default_threads
 
 namespace mij {
 
@@ -133,7 +134,7 @@ public:
   int decode_wide(int32_t *coef, int threads);
   // The stream is damaged in a way the parallel decoders (host and device) must not touch: restart markers missing,
   // out of sequence or in excess, or a sequential scan with a point transform.  decode() then walks the stream
-  // sequentially the way the reference does (resynchronisation, grey intervals; RefWalker in host_decoder.cpp).
+  // sequentially the way the reference does (resynchronisation, grey intervals; RefWalker in codestream_walk.cpp).
   bool needs_sequential() const { return needs_sequential_; }
   // The scans a frame's SEQUENTIAL walk met (decode_sequential: damaged streams, DNL frames, the residual scan types of part 8):
   // where their entropy coded data begins and ends and their MCU grid -- what the stop loops of class JPEG walk for frames that
@@ -341,13 +342,8 @@ private:
   static bool defer_progressive_scans(); // (MIJPEG_NO_DEFERRED_SEARCH: A-B)
 };
 
-int default_threads();
-
 // diagnostics: scans decoded by the self-synchronising parallel path since the library was loaded, and their pieces
 extern std::atomic<int64_t> g_speculative_scans, g_speculative_pieces;
-
-// Run fn(i) for i in [0, n) on the entropy-decoder worker pool (used for large host-side pixel copies).
-void parallel_for(int n, const std::function<void(int)> &fn);
 
 // zig-zag position -> natural index (dct/dct.cpp:57-74), generated at start-up
 extern const uint8_t *scan_order();

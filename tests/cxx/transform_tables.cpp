@@ -17,7 +17,7 @@
 
 using namespace mij;
 
-// what encoder.cpp's coder and header writer ask of host_decoder.cpp; nothing here calls them
+// what encoder.cpp's coder and header writer ask of worker_pool.cpp and host_decoder.cpp; nothing here calls them
 namespace mij {
 int default_threads() { return 1; }
 void parallel_for(int n, const std::function<void(int)> &fn) { for (int i = 0; i < n; i++) fn(i); }

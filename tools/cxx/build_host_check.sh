@@ -15,17 +15,27 @@ HIPCC="${HIPCC:-/opt/rocm/bin/hipcc}"
 CXX="${HOSTCXX:-/opt/rocm/lib/llvm/bin/clang++}" # (the compiler hipcc drives: one sanitizer runtime for all objects)
 SAN="-fsanitize=address,undefined -fno-omit-frame-pointer -g"
 mkdir -p "$OUT"
-make -s -C "$SRC" build/kernels.o build/forward.o build/hencode.o build/huffman.o build/markers.o build/resample.o build/requant.o
-for f in capi batch_decode rect_service reconstruct_device ragged_decode ragged_reconstruct entropy_device encode_device batch_pipeline; do
-  "$HIPCC" --offload-arch=gfx950 -O1 -std=c++17 -fPIC -w -Xarch_host "-fsanitize=address,undefined" -Xarch_host -fno-omit-frame-pointer -x hip -c "$SRC/$f.cpp" -o "$OUT/$f.o" &
-done
-"$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/host_decoder.cpp" -o "$OUT/host_decoder.o" &
-"$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/xt_finish.cpp" -o "$OUT/xt_finish.o" &
-"$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/encoder.cpp" -o "$OUT/encoder.o" &
-"$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/interface/jpeg.cpp" -o "$OUT/jpeg_class.o" &
+# The translation units are the Makefile's own lists (libjpeg_amd/csrc/Makefile: `make -s print-objs`, `make -s print-host-srcs`): an
+# object with a .hip source is the ordinary build's, a unit of HOST_SRCS and class JPEG are plain C++, every other .cpp is compiled as HIP.
+HOST_SRCS=" $(make -s -C "$SRC" print-host-srcs) "
+LINK=("$OUT/check.o")
 "$CXX" -O1 -std=c++17 -pthread $SAN -c "$ROOT/tools/cxx/prepare_batch_host_check.cpp" -o "$OUT/check.o" &
+for obj in $(make -s -C "$SRC" print-objs); do
+  f="$(basename "$obj" .o)"
+  if [ -f "$SRC/$f.hip" ]; then
+    make -s -C "$SRC" "$obj"
+    LINK+=("$SRC/$obj")
+    continue
+  fi
+  LINK+=("$OUT/$f.o")
+  if [ "$f" = jpeg_class ]; then
+    "$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/interface/jpeg.cpp" -o "$OUT/$f.o" &
+  elif [[ "$HOST_SRCS" == *" $f.cpp "* ]]; then
+    "$CXX" -O1 -std=c++17 -fPIC -pthread $SAN -c "$SRC/$f.cpp" -o "$OUT/$f.o" &
+  else
+    "$HIPCC" --offload-arch=gfx950 -O1 -std=c++17 -fPIC -w -Xarch_host "-fsanitize=address,undefined" -Xarch_host -fno-omit-frame-pointer -x hip -c "$SRC/$f.cpp" -o "$OUT/$f.o" &
+  fi
+done
 wait
-"$HIPCC" --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize -o "$OUT/prepare_batch_host_check" "$OUT"/check.o "$OUT"/capi.o "$OUT"/batch_decode.o "$OUT"/rect_service.o "$OUT"/reconstruct_device.o \
-  "$OUT"/ragged_decode.o "$OUT"/ragged_reconstruct.o "$OUT"/entropy_device.o "$OUT"/encode_device.o "$OUT"/batch_pipeline.o "$OUT"/host_decoder.o "$OUT"/xt_finish.o "$OUT"/encoder.o "$OUT"/jpeg_class.o \
-  "$SRC"/build/kernels.o "$SRC"/build/forward.o "$SRC"/build/hencode.o "$SRC"/build/huffman.o "$SRC"/build/markers.o "$SRC"/build/resample.o "$SRC"/build/requant.o -pthread
+"$HIPCC" --offload-arch=gfx950 -fsanitize=address,undefined -fno-gpu-sanitize -o "$OUT/prepare_batch_host_check" "${LINK[@]}" -pthread
 echo "$OUT/prepare_batch_host_check"

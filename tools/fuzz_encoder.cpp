@@ -1,5 +1,6 @@
 // fuzz_encoder.cpp -- ASan/UBSan harness of the host entropy coder (tools only, not part of the library or the tests):
-//   g++ -O1 -g -fsanitize=address,undefined -std=c++17 -pthread -Ilibjpeg_amd/csrc tools/fuzz_encoder.cpp libjpeg_amd/csrc/encoder.cpp libjpeg_amd/csrc/host_decoder.cpp libjpeg_amd/csrc/xt_finish.cpp -o /tmp/enc_fuzz && MIJPEG_THREADS=8 /tmp/enc_fuzz
+//   (cd libjpeg_amd/csrc && g++ -O1 -g -fsanitize=address,undefined -std=c++17 -pthread -I. ../../tools/fuzz_encoder.cpp $(make -s print-host-srcs) -o /tmp/enc_fuzz) && MIJPEG_THREADS=8 /tmp/enc_fuzz
+//   (print-host-srcs: the Makefile's list of the library's plain-C++ units)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>

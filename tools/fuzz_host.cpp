@@ -1,5 +1,6 @@
 // fuzz_host.cpp -- mutation fuzzing of the host decoder under AddressSanitizer / UBSan.
-//   g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined tools/fuzz_host.cpp libjpeg_amd/csrc/host_decoder.cpp libjpeg_amd/csrc/xt_finish.cpp libjpeg_amd/csrc/encoder.cpp -o /tmp/fuzz_host
+//   (cd libjpeg_amd/csrc && g++ -O1 -g -std=c++17 -pthread -fsanitize=address,undefined ../../tools/fuzz_host.cpp $(make -s print-host-srcs) -o /tmp/fuzz_host)
+//   (print-host-srcs: the Makefile's list of the library's plain-C++ units)
 //   /tmp/fuzz_host tests/golden/*.jpg
 #include <cstdio>
 #include <cstdlib>

@@ -1,5 +1,6 @@
 // huff_bench.cpp -- host entropy decoder scaling: decode one JPEG repeatedly with 1..N pool workers.
-//   g++ -O3 -std=c++17 -pthread tools/huff_bench.cpp libjpeg_amd/csrc/host_decoder.cpp libjpeg_amd/csrc/xt_finish.cpp -o /tmp/huff_bench
+//   (cd libjpeg_amd/csrc && g++ -O3 -std=c++17 -pthread ../../tools/huff_bench.cpp $(make -s print-host-srcs) -o /tmp/huff_bench)
+//   (print-host-srcs: the Makefile's list of the library's plain-C++ units)
 #include <chrono>
 #include <cstdio>
 #include <fstream>

@@ -1,6 +1,6 @@
 // tsan_host.cpp -- the multi-threaded host decoder under ThreadSanitizer ("race detection").
-//   g++ -O1 -g -std=c++17 -pthread -fsanitize=thread tools/tsan_host.cpp libjpeg_amd/csrc/host_decoder.cpp libjpeg_amd/csrc/xt_finish.cpp libjpeg_amd/csrc/encoder.cpp -o /tmp/tsan_host
-//   /tmp/tsan_host tests/golden/*.jpg          (tools/tsan_host.sh does both)
+//   tools/tsan_host.sh builds it with the library's plain-C++ units (the Makefile's print-host-srcs) under -fsanitize=thread and
+//   runs it on streams that take every parallel path
 // What runs concurrently in the product and therefore here: the restart-interval-parallel decode and the speculative
 // (self-synchronising) decode of scans without restart markers on the library's worker pool (HostDecoder::decode with
 // 8 threads), several decoder objects decoding different streams at the same time from different caller threads (the pool is

@@ -5,7 +5,10 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 # a private scratch directory: fixed names under /tmp collide with another user's run of this script
 T="$(mktemp -d)"
 trap 'rm -rf "$T"' EXIT
-g++ -O1 -g -std=c++17 -pthread -fsanitize=thread -I"$ROOT/include" "$ROOT/tools/tsan_host.cpp" "$ROOT/libjpeg_amd/csrc/host_decoder.cpp" "$ROOT/libjpeg_amd/csrc/xt_finish.cpp" "$ROOT/libjpeg_amd/csrc/encoder.cpp" -o $T/tsan_host
+# the library's plain-C++ units: the Makefile's list (HOST_SRCS)
+SRCS=()
+for f in $(make -s -C "$ROOT/libjpeg_amd/csrc" print-host-srcs); do SRCS+=("$ROOT/libjpeg_amd/csrc/$f"); done
+g++ -O1 -g -std=c++17 -pthread -fsanitize=thread -I"$ROOT/include" "$ROOT/tools/tsan_host.cpp" "${SRCS[@]}" -o $T/tsan_host
 # big enough for the parallel paths: restart intervals, and a scan without restart markers for the speculative decoder
 python3 - <<PY
 import sys
