@@ -2,12 +2,16 @@
 // mij::window and mij::window::planar, where WINDOW_OUT is true: the crop windows of a list)
 // D2: the second pass of every transform on v_dot2 (idct_columns_dot2; admitted by the host where sum |c| q <= 1476 in all three
 // components: plan_reconstruct in capi.cpp)
+// The uniform flavours (one table set for the launch, !QDEV && !RAGGED) run the lean transforms: three-operand dot products and,
+// with D2, no shifts behind the first pass (dequant_idct16 in kernels.hip).  The per-frame-table and list flavours keep the
+// helpers every other kernel has.
 template <int MINW, bool QDEV, bool D2 = false, bool RAGGED = false>
 __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420Args a)
 {
   static_assert(!RAGGED || QDEV, "ragged launches: per-frame tables");
   static_assert(!PLANAR_OUT || RAGGED, "planar output: the ragged flavours");
   static_assert(!WINDOW_OUT || RAGGED, "crop windows: the ragged flavours");
+  constexpr bool LEAN = !QDEV && !RAGGED;
   __shared__ __attribute__((aligned(16))) unsigned cpair[F420_CROWS * F420_CPITCH];
   __shared__ __attribute__((aligned(16))) u32x4 stage_all[4][128];
 
@@ -51,10 +55,16 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
         // (per-frame tables: the index is formed here and held across the transform.  The build then allocates the 133 registers
         // this instantiation had before the ring was split off, the count tests/test_ragged_batch.py holds it to; 132 otherwise.
         // Three workgroups per CU either way.)
-        if (QDEV) asm volatile("" : "+v"(at));
+        // (the lean flavours: without the accumulator copies both come out at 126 registers, and
+        // tests/test_ragged_batch.py::test_ragged_flavours_cost_the_existing_kernels_nothing holds them to the 127 and -- D2 -- 128 of
+        // the build it was written against.  The index held across the transform is the 127th, its column part held apart the
+        // 128th.  Four waves per SIMD from 103 to 128 registers: nothing is lost.)
+        int at_col = 0;
+        if (LEAN && D2) { at_col = 8 * cbx + 4; at -= at_col; asm volatile("" : "+v"(at_col)); }
+        if (QDEV || LEAN) asm volatile("" : "+v"(at));
         int v[64];
-        dequant_idct_sparse<!QDEV, false, D2>(rows, q, v);
-        short *dst = cp + 2 * at; // one base per lane: the 64 stores take immediate offsets
+        dequant_idct_sparse<!QDEV, false, D2, LEAN>(rows, q, v);
+        short *dst = cp + 2 * (at + at_col); // one base per lane: the 64 stores take immediate offsets
 #pragma unroll
         for (int r = 0; r < 8; r++)
 #pragma unroll
@@ -174,7 +184,7 @@ __global__ __launch_bounds__(F420_THREADS, MINW) void fused420p_kernel(Fused420A
   const BlockOut o = WINDOW_OUT ? block_out_window<PLANAR_OUT ? 1 : 3>(a, t, wb, wc) : block_out<PLANAR_OUT ? 1 : 3>(a, t);
   if (o.outside) return; // no barrier below this point
   int yv[64];
-  dequant_idct_sparse<!QDEV, true, D2>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
+  dequant_idct_sparse<!QDEV, true, D2, LEAN>(rows, frame_deltas<QDEV>(a, frame, 0), yv, 0, LUMA_FOLD_R2);
 
   const int bx = o.bx, by = o.by, npx = o.npx, nln = o.nln;
   uint8_t *__restrict__ out_frame = o.out_frame;

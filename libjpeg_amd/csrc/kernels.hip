@@ -326,8 +326,8 @@ constexpr int LUMA_FOLD_R = 2048 + ((2048 + 8) << 12);
 // ... and with the second pass doubled (idct_1d X2) the outputs are 2 * (sum + LUMA_FOLD_R): luma13() of one is the y << 13 above
 constexpr int LUMA_FOLD_R2 = 2 * LUMA_FOLD_R;
 __device__ __forceinline__ int luma13(int doubled_sum) { return doubled_sum & (int)0xffffe000; }
-template <int NR, bool X2> __device__ __forceinline__ void idct_columns_dot2(int (&v)[64], const int R);
-template <bool FAST, int NR = 8, int NC = 8, bool X2 = false, bool D2 = false>
+template <int NR, bool X2, int LEAN = 0> __device__ __forceinline__ void idct_columns_dot2(int (&v)[64], const int R);
+template <bool FAST, int NR = 8, int NC = 8, bool X2 = false, bool D2 = false, bool LEAN = false>
 __device__ __forceinline__ void dequant_idct(const u32x4 (&rows)[8], const int *__restrict__ q, int (&v)[64], int dcoff, const int colr = 2048)
 {
 #pragma unroll
@@ -349,7 +349,7 @@ __device__ __forceinline__ void dequant_idct(const u32x4 (&rows)[8], const int *
   for (int r = 0; r < NR; r++)
     idct_1d<FAST, 9, NC>(v[r * 8 + 0], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5],
                          v[r * 8 + 6], v[r * 8 + 7]);
-  if constexpr (D2) { idct_columns_dot2<NR, X2>(v, colr); return; }
+  if constexpr (D2) { idct_columns_dot2<NR, X2, LEAN ? 1 : 0>(v, colr); return; }
 #pragma unroll
   for (int c = 0; c < 8; c++)
     idct_1d<FAST, 12, NR, X2>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c], colr);
@@ -382,6 +382,33 @@ __device__ __forceinline__ int sdot2(unsigned pk, int k, int c)
   typedef short s16x2 __attribute__((ext_vector_type(2)));
   return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, pk), __builtin_bit_cast(s16x2, k), c, false);
 }
+// The same inner product as the three-operand v_dot2_i32_i16 d, pk, k, c.  From the builtin the compiler emits the two-operand
+// v_dot2c_i32_i16, which takes the constant as a literal and OVERWRITES its accumulator: every accumulator that two chains share
+// (A, B, R, the rounding seed) and every zero start is copied first, eight v_mov_b32 per 1-D transform.  A VOP3P instruction takes
+// no literal, so the constant pair travels in an SGPR -- one per instruction, which is why a chain that starts from a constant
+// keeps that constant in a VGPR -- and a chain that starts from nothing names the inline 0.
+__device__ __forceinline__ int sdot2_sgpr(unsigned pk, int k, int c)
+{
+  int d;
+  asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(pk), "s"(k), "v"(c));
+  return d;
+}
+__device__ __forceinline__ int sdot2_sgpr0(unsigned pk, int k)
+{
+  int d;
+  asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(d) : "v"(pk), "s"(k));
+  return d;
+}
+// LEAN: the three-operand form (fused420p_kernel's uniform flavours); otherwise the builtin, as every other kernel has it
+template <int LEAN> __device__ __forceinline__ int dotk(unsigned pk, int k, int c) { return LEAN ? sdot2_sgpr(pk, k, c) : sdot2(pk, k, c); }
+template <int LEAN> __device__ __forceinline__ int dotk0(unsigned pk, int k) { return LEAN ? sdot2_sgpr0(pk, k) : sdot2(pk, k, 0); }
+// {bytes 1..2 of hi, bytes 1..2 of lo} -> one register: (hi >> 8, lo >> 8) as int16 halves without the shifts (volatile: as above)
+__device__ __forceinline__ unsigned pack_mid16_now(int hi, int lo)
+{
+  unsigned d;
+  asm volatile("v_perm_b32 %0, %1, %2, %3" : "=v"(d) : "v"(hi), "v"(lo), "s"(0x06050201u));
+  return d;
+}
 // The SECOND pass as v_dot2_i32_i16 inner products (D2 flavours; 8-bit FAST frames whose first-pass results fit 16 bits: the host
 // admits them by sum |c| q <= 1476 per block -- a first-pass output is (sum_x s_x M_xj + 16) >> 5 with |M_xj| <= 710, the largest
 // entry of the butterfly's integer matrix, and (710 * 1476 + 16) >> 5 = 32749; the level shift is not in it, dcoff = 0).  The pass
@@ -390,9 +417,13 @@ __device__ __forceinline__ int sdot2(unsigned pk, int k, int c)
 // one dot product that takes the previous one as its accumulator; 22 issue slots per column where the mad24 butterfly takes 36
 // (X2) / 44, plus four packings.  Exact: the ring Z / 2^32 is distributive, the operands are the same integers.
 // R, X2 as in idct_1d (the doubled pass: every constant twice, no final shift).
-template <int NR, bool X2>
+// LEAN = 1: the products in their three-operand form (dotk).  LEAN = 2: that, and v[] holds the first pass's sums times 8 with
+// the rounding seed 128 inside and NOT shifted (the lean dequant_idct16): the pass's input is bytes 1..2 of every sum, and the
+// packing that pairs the rows takes those bytes directly.
+template <int NR, bool X2, int LEAN>
 __device__ __forceinline__ void idct_columns_dot2(int (&v)[64], const int R)
 {
+  auto pack = [](int hi, int lo) { return LEAN == 2 ? pack_mid16_now(hi, lo) : pack_lo16_now(hi, lo); };
   constexpr int M = X2 ? 2 : 1, OSH = X2 ? 0 : 12;
   constexpr int C0541 = M * FIX9(0.541196100), C0765 = M * FIX9(0.765366865), C1847 = M * FIX9(1.847759065), C1175 = M * FIX9(1.175875602),
                 C1961 = M * FIX9(1.961570560), C0390 = M * FIX9(0.390180644), C0899 = M * FIX9(0.899976223), C0298 = M * FIX9(0.298631336),
@@ -402,27 +433,27 @@ __device__ __forceinline__ void idct_columns_dot2(int (&v)[64], const int R)
   for (int c = 0; c < 8; c++) {
     int t10, t11, t12, t13, o0, o1, o2, o3;
     if (NR == 8) {
-      const unsigned s04 = pack_lo16_now(v[32 + c], v[c]), s15 = pack_lo16_now(v[40 + c], v[8 + c]);
-      const unsigned s26 = pack_lo16_now(v[48 + c], v[16 + c]), s37 = pack_lo16_now(v[56 + c], v[24 + c]);
-      const int A = sdot2(s04, PK16(ONE, ONE), R), B = sdot2(s04, PK16(ONE, -ONE), R);
-      t10 = sdot2(s26, PK16(C0541 + C0765, C0541), A);
-      t13 = sdot2(s26, PK16(-(C0541 + C0765), -C0541), A);
-      t11 = sdot2(s26, PK16(C0541, C0541 - C1847), B);
-      t12 = sdot2(s26, PK16(-C0541, C1847 - C0541), B);
-      o0 = sdot2(s37, PK16(C1175 - C1961, -C0899 + C0298 + C1175 - C1961), sdot2(s15, PK16(-C0899 + C1175, C1175), 0));
-      o1 = sdot2(s37, PK16(-C2562 + C1175, C1175), sdot2(s15, PK16(C1175 - C0390, -C2562 + C2053 + C1175 - C0390), 0));
-      o2 = sdot2(s37, PK16(-C2562 + C3072 + C1175 - C1961, C1175 - C1961), sdot2(s15, PK16(C1175, -C2562 + C1175), 0));
-      o3 = sdot2(s37, PK16(C1175, -C0899 + C1175), sdot2(s15, PK16(-C0899 + C1501 + C1175 - C0390, C1175 - C0390), 0));
+      const unsigned s04 = pack(v[32 + c], v[c]), s15 = pack(v[40 + c], v[8 + c]);
+      const unsigned s26 = pack(v[48 + c], v[16 + c]), s37 = pack(v[56 + c], v[24 + c]);
+      const int A = dotk<LEAN>(s04, PK16(ONE, ONE), R), B = dotk<LEAN>(s04, PK16(ONE, -ONE), R);
+      t10 = dotk<LEAN>(s26, PK16(C0541 + C0765, C0541), A);
+      t13 = dotk<LEAN>(s26, PK16(-(C0541 + C0765), -C0541), A);
+      t11 = dotk<LEAN>(s26, PK16(C0541, C0541 - C1847), B);
+      t12 = dotk<LEAN>(s26, PK16(-C0541, C1847 - C0541), B);
+      o0 = dotk<LEAN>(s37, PK16(C1175 - C1961, -C0899 + C0298 + C1175 - C1961), dotk0<LEAN>(s15, PK16(-C0899 + C1175, C1175)));
+      o1 = dotk<LEAN>(s37, PK16(-C2562 + C1175, C1175), dotk0<LEAN>(s15, PK16(C1175 - C0390, -C2562 + C2053 + C1175 - C0390)));
+      o2 = dotk<LEAN>(s37, PK16(-C2562 + C3072 + C1175 - C1961, C1175 - C1961), dotk0<LEAN>(s15, PK16(C1175, -C2562 + C1175)));
+      o3 = dotk<LEAN>(s37, PK16(C1175, -C0899 + C1175), dotk0<LEAN>(s15, PK16(-C0899 + C1501 + C1175 - C0390, C1175 - C0390)));
     } else {
-      const unsigned s02 = pack_lo16_now(v[16 + c], v[c]), s13 = pack_lo16_now(v[24 + c], v[8 + c]);
-      t10 = sdot2(s02, PK16(ONE, C0541 + C0765), R);
-      t13 = sdot2(s02, PK16(ONE, -(C0541 + C0765)), R);
-      t11 = sdot2(s02, PK16(ONE, C0541), R);
-      t12 = sdot2(s02, PK16(ONE, -C0541), R);
-      o0 = sdot2(s13, PK16(-C0899 + C1175, C1175 - C1961), 0);
-      o1 = sdot2(s13, PK16(C1175 - C0390, -C2562 + C1175), 0);
-      o2 = sdot2(s13, PK16(C1175, -C2562 + C3072 + C1175 - C1961), 0);
-      o3 = sdot2(s13, PK16(-C0899 + C1501 + C1175 - C0390, C1175), 0);
+      const unsigned s02 = pack(v[16 + c], v[c]), s13 = pack(v[24 + c], v[8 + c]);
+      t10 = dotk<LEAN>(s02, PK16(ONE, C0541 + C0765), R);
+      t13 = dotk<LEAN>(s02, PK16(ONE, -(C0541 + C0765)), R);
+      t11 = dotk<LEAN>(s02, PK16(ONE, C0541), R);
+      t12 = dotk<LEAN>(s02, PK16(ONE, -C0541), R);
+      o0 = dotk0<LEAN>(s13, PK16(-C0899 + C1175, C1175 - C1961));
+      o1 = dotk0<LEAN>(s13, PK16(C1175 - C0390, -C2562 + C1175));
+      o2 = dotk0<LEAN>(s13, PK16(C1175, -C2562 + C3072 + C1175 - C1961));
+      o3 = dotk0<LEAN>(s13, PK16(-C0899 + C1501 + C1175 - C0390, C1175));
     }
     v[c] = (t10 + o3) >> OSH; v[56 + c] = (t10 - o3) >> OSH;
     v[8 + c] = (t11 + o2) >> OSH; v[48 + c] = (t11 - o2) >> OSH;
@@ -431,12 +462,20 @@ __device__ __forceinline__ void idct_columns_dot2(int (&v)[64], const int R)
   }
 }
 
-template <int NR, int NC, bool X2 = false, bool D2 = false>
+// LEAN: the products in their three-operand form (dotk).  LEAN with D2, where the second pass consumes packed 16-bit pairs: every
+// constant of this pass times 8 (|entry| <= 710, so 5680 fits 16 bits) and the rounding seed 128 for 16 -- in two's complement
+// (8 x + 128) >> 8 = (x + 16) >> 5, so the pass's result is bytes 1..2 of the sum and the second pass's packing picks them up
+// (idct_columns_dot2, LEAN = 2): the eight shifts per row are not issued.  The D2 gate (sum |c| q <= 1476) already holds
+// (x + 16) >> 5 within 16 bits; the first pass's own gate (sum |c| q < 16384) holds |8 x + 128| <= 8 * 710 * 16383 + 128 < 2^31.
+// Without D2 the second pass wants the 32-bit values: shift and constants stay.
+template <int NR, int NC, bool X2 = false, bool D2 = false, bool LEAN = false>
 __device__ __forceinline__ void dequant_idct16(const u32x4 (&rows)[8], const int *__restrict__ q, int (&v)[64], int dcoff, const int colr = 2048)
 {
-  constexpr int C0541 = FIX9(0.541196100), C0765 = FIX9(0.765366865), C1847 = FIX9(1.847759065), C1175 = FIX9(1.175875602),
-                C1961 = FIX9(1.961570560), C0390 = FIX9(0.390180644), C0899 = FIX9(0.899976223), C0298 = FIX9(0.298631336),
-                C2562 = FIX9(2.562915447), C2053 = FIX9(2.053119869), C3072 = FIX9(3.072711026), C1501 = FIX9(1.501321110);
+  constexpr bool BYTES = LEAN && D2;
+  constexpr int M = BYTES ? 8 : 1, OSH = BYTES ? 0 : 5, ONE = M * 512, SEED = M * 16;
+  constexpr int C0541 = M * FIX9(0.541196100), C0765 = M * FIX9(0.765366865), C1847 = M * FIX9(1.847759065), C1175 = M * FIX9(1.175875602),
+                C1961 = M * FIX9(1.961570560), C0390 = M * FIX9(0.390180644), C0899 = M * FIX9(0.899976223), C0298 = M * FIX9(0.298631336),
+                C2562 = M * FIX9(2.562915447), C2053 = M * FIX9(2.053119869), C3072 = M * FIX9(3.072711026), C1501 = M * FIX9(1.501321110);
   const unsigned *__restrict__ qp = reinterpret_cast<const unsigned *>(q + QROW_PACKED);
   const unsigned dc16 = (unsigned)(dcoff >> 4) & 0xffffu; // the level shift, added to the DC term (low half of the first pair of row 0)
 #pragma unroll
@@ -449,35 +488,35 @@ __device__ __forceinline__ void dequant_idct16(const u32x4 (&rows)[8], const int
       const unsigned s26 = pk_mul_lo16(__builtin_amdgcn_perm(rows[k].w, rows[k].y, 0x05040100u), qp[k * 4 + 2]);
       const unsigned s37 = pk_mul_lo16(__builtin_amdgcn_perm(rows[k].w, rows[k].y, 0x07060302u), qp[k * 4 + 3]);
       if (k == 0) s04 = pk_add16(s04, dc16);
-      const int A = sdot2(s04, PK16(512, 512), 16), B = sdot2(s04, PK16(512, -512), 16); // (s0 +- s4) << 9, rounding inside
-      t10 = sdot2(s26, PK16(C0541 + C0765, C0541), A);
-      t13 = sdot2(s26, PK16(-(C0541 + C0765), -C0541), A);
-      t11 = sdot2(s26, PK16(C0541, C0541 - C1847), B);
-      t12 = sdot2(s26, PK16(-C0541, C1847 - C0541), B);
-      o0 = sdot2(s37, PK16(C1175 - C1961, -C0899 + C0298 + C1175 - C1961), sdot2(s15, PK16(-C0899 + C1175, C1175), 0));
-      o1 = sdot2(s37, PK16(-C2562 + C1175, C1175), sdot2(s15, PK16(C1175 - C0390, -C2562 + C2053 + C1175 - C0390), 0));
-      o2 = sdot2(s37, PK16(-C2562 + C3072 + C1175 - C1961, C1175 - C1961), sdot2(s15, PK16(C1175, -C2562 + C1175), 0));
-      o3 = sdot2(s37, PK16(C1175, -C0899 + C1175), sdot2(s15, PK16(-C0899 + C1501 + C1175 - C0390, C1175 - C0390), 0));
+      const int A = dotk<LEAN>(s04, PK16(ONE, ONE), SEED), B = dotk<LEAN>(s04, PK16(ONE, -ONE), SEED); // (s0 +- s4) << 9, rounding inside
+      t10 = dotk<LEAN>(s26, PK16(C0541 + C0765, C0541), A);
+      t13 = dotk<LEAN>(s26, PK16(-(C0541 + C0765), -C0541), A);
+      t11 = dotk<LEAN>(s26, PK16(C0541, C0541 - C1847), B);
+      t12 = dotk<LEAN>(s26, PK16(-C0541, C1847 - C0541), B);
+      o0 = dotk<LEAN>(s37, PK16(C1175 - C1961, -C0899 + C0298 + C1175 - C1961), dotk0<LEAN>(s15, PK16(-C0899 + C1175, C1175)));
+      o1 = dotk<LEAN>(s37, PK16(-C2562 + C1175, C1175), dotk0<LEAN>(s15, PK16(C1175 - C0390, -C2562 + C2053 + C1175 - C0390)));
+      o2 = dotk<LEAN>(s37, PK16(-C2562 + C3072 + C1175 - C1961, C1175 - C1961), dotk0<LEAN>(s15, PK16(C1175, -C2562 + C1175)));
+      o3 = dotk<LEAN>(s37, PK16(C1175, -C0899 + C1175), dotk0<LEAN>(s15, PK16(-C0899 + C1501 + C1175 - C0390, C1175 - C0390)));
     } else {
       // columns 4..7 are zero: pairs (c0,c2) (c1,c3)
       unsigned s02 = pk_mul_lo16(__builtin_amdgcn_perm(rows[k].y, rows[k].x, 0x05040100u), qp[32 + k * 2 + 0]);
       const unsigned s13 = pk_mul_lo16(__builtin_amdgcn_perm(rows[k].y, rows[k].x, 0x07060302u), qp[32 + k * 2 + 1]);
       if (k == 0) s02 = pk_add16(s02, dc16);
-      t10 = sdot2(s02, PK16(512, C0541 + C0765), 16);
-      t13 = sdot2(s02, PK16(512, -(C0541 + C0765)), 16);
-      t11 = sdot2(s02, PK16(512, C0541), 16);
-      t12 = sdot2(s02, PK16(512, -C0541), 16);
-      o0 = sdot2(s13, PK16(-C0899 + C1175, C1175 - C1961), 0);
-      o1 = sdot2(s13, PK16(C1175 - C0390, -C2562 + C1175), 0);
-      o2 = sdot2(s13, PK16(C1175, -C2562 + C3072 + C1175 - C1961), 0);
-      o3 = sdot2(s13, PK16(-C0899 + C1501 + C1175 - C0390, C1175), 0);
+      t10 = dotk<LEAN>(s02, PK16(ONE, C0541 + C0765), SEED);
+      t13 = dotk<LEAN>(s02, PK16(ONE, -(C0541 + C0765)), SEED);
+      t11 = dotk<LEAN>(s02, PK16(ONE, C0541), SEED);
+      t12 = dotk<LEAN>(s02, PK16(ONE, -C0541), SEED);
+      o0 = dotk0<LEAN>(s13, PK16(-C0899 + C1175, C1175 - C1961));
+      o1 = dotk0<LEAN>(s13, PK16(C1175 - C0390, -C2562 + C1175));
+      o2 = dotk0<LEAN>(s13, PK16(C1175, -C2562 + C3072 + C1175 - C1961));
+      o3 = dotk0<LEAN>(s13, PK16(-C0899 + C1501 + C1175 - C0390, C1175));
     }
-    v[k * 8 + 0] = (t10 + o3) >> 5; v[k * 8 + 7] = (t10 - o3) >> 5;
-    v[k * 8 + 1] = (t11 + o2) >> 5; v[k * 8 + 6] = (t11 - o2) >> 5;
-    v[k * 8 + 2] = (t12 + o1) >> 5; v[k * 8 + 5] = (t12 - o1) >> 5;
-    v[k * 8 + 3] = (t13 + o0) >> 5; v[k * 8 + 4] = (t13 - o0) >> 5;
+    v[k * 8 + 0] = (t10 + o3) >> OSH; v[k * 8 + 7] = (t10 - o3) >> OSH;
+    v[k * 8 + 1] = (t11 + o2) >> OSH; v[k * 8 + 6] = (t11 - o2) >> OSH;
+    v[k * 8 + 2] = (t12 + o1) >> OSH; v[k * 8 + 5] = (t12 - o1) >> OSH;
+    v[k * 8 + 3] = (t13 + o0) >> OSH; v[k * 8 + 4] = (t13 - o0) >> OSH;
   }
-  if (D2) { idct_columns_dot2<NR, X2>(v, colr); return; }
+  if (D2) { idct_columns_dot2<NR, X2, LEAN ? 2 : 0>(v, colr); return; }
 #pragma unroll
   for (int c = 0; c < 8; c++)
     idct_1d<true, 12, NR, X2>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c], colr);
@@ -505,15 +544,17 @@ __device__ __forceinline__ bool cols_4_to_7_zero(const u32x4 (&rows)[8])
 // dequant_idct<true> with the pruned paths where the data allow it.  PK16ROW: q is a row of the kernel's argument block (the
 // packed deltas follow the 64) and the frame has 8-bit samples -- the first pass runs in 16 bits (dequant_idct16).
 // D2 (with PK16ROW): the second pass on v_dot2 as well (idct_columns_dot2: the host's gate, dcoff = 0).
-template <bool PK16ROW = false, bool X2 = false, bool D2 = false>
+// LEAN (with PK16ROW): the v_dot2 products without accumulator copies and, with D2, without the first pass's shifts (dequant_idct16).
+template <bool PK16ROW = false, bool X2 = false, bool D2 = false, bool LEAN = false>
 __device__ __forceinline__ void dequant_idct_sparse(const u32x4 (&rows)[8], const int *__restrict__ q, int (&v)[64], int dcoff = 0, const int colr = 2048)
 {
   static_assert(!D2 || PK16ROW, "the 16-bit second pass belongs to the 8-bit FAST flavours");
+  static_assert(!LEAN || PK16ROW, "the lean products belong to the 8-bit FAST flavours");
   if (PK16ROW) {
     if (rows_4_to_7_zero(rows)) {
-      if (cols_4_to_7_zero(rows)) dequant_idct<true, 4, 4, X2, D2>(rows, q, v, dcoff, colr); // (the pruned butterfly is as short as the products)
-      else dequant_idct16<4, 8, X2, D2>(rows, q, v, dcoff, colr);
-    } else dequant_idct16<8, 8, X2, D2>(rows, q, v, dcoff, colr);
+      if (cols_4_to_7_zero(rows)) dequant_idct<true, 4, 4, X2, D2, LEAN>(rows, q, v, dcoff, colr); // (the pruned butterfly is as short as the products)
+      else dequant_idct16<4, 8, X2, D2, LEAN>(rows, q, v, dcoff, colr);
+    } else dequant_idct16<8, 8, X2, D2, LEAN>(rows, q, v, dcoff, colr);
     return;
   }
   if (rows_4_to_7_zero(rows)) {
