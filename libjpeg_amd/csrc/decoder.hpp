@@ -1,6 +1,6 @@
 // decoder.hpp -- the decoder object of the C ABI and what its translation units share: capi.cpp (the object, single images),
 // batch_decode.cpp (uniform batches, the header pass of a list, the marker route option), rect_service.cpp (rectangles),
-// entropy_device.cpp, reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp, ragged_reconstruct.cpp and encode_device.cpp.
+// entropy_device.cpp (with entropy_plan.hpp), reconstruct_device.cpp (with reconstruct.hpp), ragged_decode.cpp, ragged_reconstruct.cpp and encode_device.cpp.
 // Private to libmijpeg.so.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -175,7 +175,7 @@ struct mijpeg_decoder {
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t chain_ev = nullptr; // mijpeg_stream_wait
-  hipEvent_t ms_ready = nullptr, ms_done = nullptr; // device_entropy_multiscan: the second frame's stream
+  hipEvent_t ms_ready = nullptr, ms_done = nullptr; // device_entropy_multiscan (MultiscanRun): the second frame's stream
   hipStream_t ms_stream = nullptr;
   int err_code = 0;
   std::string err_msg;

@@ -1,11 +1,13 @@
 // entropy_device.cpp -- entropy decoding on the device: which streams qualify, the upload of their entropy coded data and
 // tables, the launches of the Huffman kernels (huffman.hip) and what their status words say.  Host code only, compiled with
-// hipcc like capi.cpp, whose extern "C" bodies call it.
+// hipcc like capi.cpp, whose extern "C" bodies call it.  What needs no device -- the helpers the paths share, plan and staging of
+// the multiscan and walk paths -- is entropy_plan.hpp.
 #include <string.h>
 
 #include <algorithm>
 
 #include "decoder.hpp"
+#include "entropy_plan.hpp"
 #include "huffman_dev.hpp"
 #include "kernels.hpp"
 #include "markers.hpp"
@@ -146,34 +148,7 @@ bool device_markers_good(const uint32_t *results, const uint32_t *want_term, int
 
 namespace { // steps the sequential, progressive and walk paths share
 
-// Workgroups of the Huffman kernels hold four waves, one per SIMD: with two-wave workgroups (which round 1 chose for the LDS
-// they leave to others) the same eight waves per CU decode 37 % slower (0.60 against 0.38 ms per 32 4K frames; 3, 5, 6 waves:
-// 0.55, 0.58, 0.48) -- the waves of a workgroup go to the SIMDs in cyclic order, and only a multiple of four loads them evenly
-constexpr int WAVES_PER_GROUP = 4;
-
 const char DC_OVERFLOW[] = "on-device entropy decoding: a DC coefficient leaves the 16 bit coefficient store (damaged stream); the host decoder keeps 32-bit coefficients for it";
-
-// The regions of a packed buffer: offsets handed out in order, each region starting on a 16-byte boundary.
-struct Layout {
-  size_t end = 0;
-  size_t take(size_t bytes) { const size_t at = end; end = (at + bytes + 15) & ~(size_t)15; return at; }
-};
-
-// Decoding lanes per wave for a launch of `intervals` restart intervals: about a thousand waves (one per SIMD) are what a small
-// launch wants -- fewer lanes per wave mean more waves that each issue the same instructions for less, fuller waves mean longer
-// steps (the slowest lane's block).  Measured with the bit-addressed reader and four-wave workgroups on one 8K 4:2:0 frame with
-// 16200 intervals (tools/gpu_huff_lanes.sh): 1 lane 0.81 ms, 2: 0.52, 4: 0.33, 8: 0.26, 16: 0.26, 32: 0.27.
-// MIJPEG_HUFF_LANES (a power of two up to 64) overrides the choice.
-int lanes_for(int64_t intervals)
-{
-  int lanes = 64;
-  while (lanes > 1 && intervals / lanes < 768) lanes >>= 1;
-  if (const char *e = getenv("MIJPEG_HUFF_LANES")) {
-    const int l = atoi(e);
-    if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) lanes = l;
-  }
-  return lanes;
-}
 
 // The buffer of one device decode: on the device [streams][tables, intervals ...][status words][what only the device keeps:
 // `device_extra` bytes]; in pinned staging (ent_host) everything behind the streams up to the status words, at the same offsets
@@ -182,14 +157,6 @@ int ensure_entropy_buffers(mijpeg_decoder *d, size_t stream_bytes, size_t tail_b
 {
   const int rc = ensure_dev(d, (void **)&d->ent_dev, &d->ent_cap, stream_bytes + tail_bytes + device_extra);
   return rc ? rc : ensure_pinned(d, &d->ent_host, &d->ent_host_cap, tail_bytes);
-}
-
-// Blocks of scan component k in one MCU: an interleaved scan uses the frame's sampling factors, a single-component scan 1 x 1
-struct McuBlocks { int h, v; };
-McuBlocks mcu_blocks(const mijpeg_info &f, const Scan &s, int k)
-{
-  const int c = s.sc[k].comp;
-  return s.ncomp > 1 ? McuBlocks{f.hsamp[c], f.vsamp[c]} : McuBlocks{1, 1};
 }
 
 // One image of a marker search in staging: its descriptor, its chunks (at chunks[im.first_chunk]) and a fresh result
@@ -361,212 +328,196 @@ int walk_verdict(mijpeg_decoder *d, const uint32_t *walk_status, int n)
 // Images whose source is SearchedWalk (the marker route, `search` its argument block): everything here is sized from the raw
 // segment, an upper bound of the copy the search writes, and the fit step (launch_marker_fit) puts what the search found --
 // the copy's size, the subsequences it really has, the end of every virtual interval -- where the walk kernels read it.
+// Plan and staging are entropy_plan.hpp's (plan_walk, fill_walk); the stages here bring the plan to the device.
 struct DeviceIntervals { uint32_t *ibegin, *iend; uint8_t *iskip; int16_t *ipred; };
-static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, const BatchPlan &plan, const EntropyBatchOptions &opt, const HuffScanArgs &scan,
-                              const DeviceIntervals &intervals, const MarkerArgs &search)
+
+namespace {
+
+// What the walk's plan reads of the images of a launch
+std::vector<WalkImage> walk_images(HostDecoder *const *hosts, const BatchPlan &plan)
 {
-  const int n = plan.n();
-  const bool defer = opt.defer, per_image = opt.ragged != nullptr; // (images of different sizes: interval sizes and block counts image by image)
-  int *const walk_launches = opt.ragged ? opt.ragged->walk_launches : nullptr;
-  // MCUs per virtual interval of the images that are walked, 0 for the others
-  auto dwalk = [&](int i) { return plan.images[(size_t)i].device_walked() ? plan.images[(size_t)i].mcus_per_interval : 0; };
-  // (the device's copy: entropy coded data without the byte stuffing; SearchedWalk: the raw segment, which is no shorter)
-  auto usize = [&](int i) { return plan.images[(size_t)i].copy_bytes; };
-  const mijpeg_info &f0 = hosts[0]->info;
-  const Scan &s0 = hosts[0]->scans[0];
+  std::vector<WalkImage> images((size_t)plan.n());
+  for (int i = 0; i < plan.n(); i++) {
+    const ImagePlan &p = plan.images[(size_t)i];
+    const Scan &s = hosts[i]->scans[0];
+    images[(size_t)i] = WalkImage{p.device_walked(), p.source == IntervalSource::SearchedWalk, p.mcus_per_interval, p.copy_bytes,
+                                  p.first_interval, p.n_intervals, (int64_t)s.mcus_x * s.mcus_y};
+  }
+  return images;
+}
+
+// device_walk_images' stages: the plan's buffer on the device (walk_dev) and what the host fills of it in pinned staging
+// (walk_host), the argument block of the walk kernels, everything enqueued on the object's stream
+struct WalkRun {
+  mijpeg_decoder *d;
+  const WalkPlan &p;
+  int *walk_launches; // (a ragged launch counts them)
   HuffWalkArgs w;
-  memset(&w, 0, sizeof(w));
-  w.ncomp = s0.ncomp;
-  int B = 0;
-  for (int k = 0; k < s0.ncomp; k++) {
-    const McuBlocks b = mcu_blocks(f0, s0, k);
-    w.hs[k] = b.h;
-    w.vs[k] = b.v;
-    B += b.h * b.v;
-  }
-  if (B > 64) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too many blocks per MCU for the device walk");
-  w.nblk_mcu = B;
-  w.ntables = scan.ntables;
-  // subsequence size.  One image: the launch is latency-bound, its serial part is (distance the decoder needs to
-  // synchronise + two subsequences), so small ones.  Batches are throughput-bound and every round re-walks whole
-  // subsequences, so fewer rounds over larger ones (measured on 1, 4 and 16 8K frames: 128, 256, 512 bytes win).
-  size_t longest = 0, all_bytes = 0;
-  for (int i = 0; i < n; i++)
-    if (dwalk(i)) {
-      const size_t len = usize(i);
-      longest = std::max(longest, len);
-      all_bytes += len;
-    }
-  uint32_t sub_bytes = all_bytes <= ((size_t)8 << 20) ? 128 : all_bytes <= ((size_t)32 << 20) ? 256 : 512;
-  while (sub_bytes < 1024 && longest / sub_bytes > ((size_t)1 << 20)) sub_bytes <<= 1; // bounds the prefix-sum tiles
-  if (const char *e = getenv("MIJPEG_WALK_SUB")) sub_bytes = (uint32_t)std::max(32, std::min(4096, atoi(e))); // experiments
-  w.sub_bytes = sub_bytes;
-  // per image: its subsequences; per workgroup: image and first subsequence
-  std::vector<uint32_t> img_sub0((size_t)n, 0), img_nsub((size_t)n, 0), img_e0((size_t)n, 0), img_e1((size_t)n, 0), img_int0((size_t)n, 0);
-  uint32_t nsub_total = 0;
-  for (int i = 0; i < n; i++) {
-    img_e0[(size_t)i] = 0;
-    img_e1[(size_t)i] = (uint32_t)usize(i);
-    img_int0[(size_t)i] = (uint32_t)plan.images[(size_t)i].first_interval;
-    img_sub0[(size_t)i] = nsub_total;
-    if (dwalk(i)) {
-      img_nsub[(size_t)i] = (uint32_t)((usize(i) + sub_bytes - 1) / sub_bytes);
-      nsub_total += img_nsub[(size_t)i];
-    }
-  }
-  w.lanes = 64;
-  while (w.lanes > 1 && nsub_total / (uint32_t)w.lanes < 2048) w.lanes >>= 1;
-  w.waves_per_group = WAVES_PER_GROUP;
-  const uint32_t per_group = (uint32_t)(w.lanes * w.waves_per_group);
-  std::vector<uint32_t> sub_image, sub_first;
-  for (int i = 0; i < n; i++)
-    for (uint32_t k = 0; k < img_nsub[(size_t)i]; k += per_group) { sub_image.push_back((uint32_t)i); sub_first.push_back(k); }
-  w.n_groups = (int32_t)sub_image.size();
-  // one device buffer: [per group: image, first][per image: sub0, nsub, e0, e1, int0][per subsequence: state][per image, ragged
-  // launches: blocks per interval, blocks][per image, the fit step: virtual intervals] (the host fills these; nsub and e1 of a
-  // SearchedWalk image are bounds the fit step replaces) [changed flag per round, status per image][per subsequence: stamp]
-  // (start out as zero) [per subsequence: nblocks,
-  // dcsum, first_block, first_pred][prefix-sum tiles]
-  constexpr int MAX_ROUNDS = 48;
-  const size_t G = sub_image.size(), S = nsub_total;
-  Layout L;
-  const size_t o_simg = L.take(G * 4), o_sfirst = L.take(G * 4);
-  const size_t o_isub0 = L.take((size_t)n * 4), o_insub = L.take((size_t)n * 4), o_e0 = L.take((size_t)n * 4), o_e1 = L.take((size_t)n * 4);
-  const size_t o_int0 = L.take((size_t)n * 4), o_state = L.take(S * 8);
-  // images of different sizes (per_image): blocks per virtual interval and blocks in all, image by image
-  const size_t o_every = L.take(per_image ? (size_t)n * 4 : 0), o_blocks = L.take(per_image ? (size_t)n * 4 : 0);
-  // the fit step: virtual intervals of every image that is walked behind its search, 0 for the others
-  bool any_fit = false;
-  for (int i = 0; i < n; i++) any_fit |= plan.images[(size_t)i].source == IntervalSource::SearchedWalk;
-  const size_t o_fit = L.take(any_fit ? (size_t)n * 4 : 0);
-  const size_t o_up_end = L.end;
-  const size_t o_flags = L.take((size_t)(MAX_ROUNDS + 1) * 4 + (size_t)n * 4); // changed[], walk_status[]
-  const size_t o_stamp = L.take(S * 4);
-  const size_t o_zero_end = L.end;
-  const size_t o_nblk = L.take(S * 4), o_dcsum = L.take(S * 16), o_fblk = L.take(S * 4), o_fpred = L.take(S * 16);
-  uint32_t most = 0;
-  for (int i = 0; i < n; i++) most = std::max(most, img_nsub[(size_t)i]);
-  const int tiles = (int)((most + HUFF_WALK_TILE - 1) / HUFF_WALK_TILE);
-  if (tiles > HUFF_WALK_TILE) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "stream too long for the device walk");
-  const size_t o_tiles = L.take((size_t)n * tiles * HUFF_WALK_SUMS_BYTES);
-  int rc = ensure_dev(d, (void **)&d->walk_dev, &d->walk_cap, L.end);
-  if (rc) return rc;
+
+  uint32_t *flags_host() const { return (uint32_t *)(d->walk_host + p.o_up_end); }
+
   // pinned: what the host fills, then room for the flags (and the status words, read back to the start)
-  rc = ensure_pinned(d, &d->walk_host, &d->walk_host_cap, o_up_end + (o_stamp - o_flags));
-  if (rc) return rc;
-  uint8_t *wh = d->walk_host, *wd = d->walk_dev;
-  memcpy(wh + o_simg, sub_image.data(), G * 4);
-  memcpy(wh + o_sfirst, sub_first.data(), G * 4);
-  memcpy(wh + o_isub0, img_sub0.data(), (size_t)n * 4);
-  memcpy(wh + o_insub, img_nsub.data(), (size_t)n * 4);
-  memcpy(wh + o_e0, img_e0.data(), (size_t)n * 4);
-  memcpy(wh + o_e1, img_e1.data(), (size_t)n * 4);
-  memcpy(wh + o_int0, img_int0.data(), (size_t)n * 4);
-  if (per_image) {
-    uint32_t *every = (uint32_t *)(wh + o_every), *blocks = (uint32_t *)(wh + o_blocks);
-    for (int i = 0; i < n; i++) {
-      const Scan &s = hosts[i]->scans[0];
-      every[i] = (uint32_t)(std::max(1, dwalk(i)) * B);
-      blocks[i] = (uint32_t)((int64_t)s.mcus_x * s.mcus_y * B);
-    }
-    w.img_emit_every = (const uint32_t *)(d->walk_dev + o_every);
-    w.img_total_blocks = (const uint32_t *)(d->walk_dev + o_blocks);
-  }
-  // the initial guess: every subsequence starts at its boundary (behind a stuffed zero if it falls on one) with the
-  // first block of an MCU; for the first subsequence of an image that is no guess
+  int ensure()
   {
-    // (positions in the device's copy, which has no byte stuffing: nothing of the stream is looked at here)
-    uint64_t *st = (uint64_t *)(wh + o_state);
-    for (int i = 0; i < n; i++)
-      for (uint32_t k = 0; k < img_nsub[(size_t)i]; k++) st[img_sub0[(size_t)i] + k] = (uint64_t)k * sub_bytes;
+    const int rc = ensure_dev(d, (void **)&d->walk_dev, &d->walk_cap, p.end);
+    return rc ? rc : ensure_pinned(d, &d->walk_host, &d->walk_host_cap, p.o_up_end + p.flags_bytes());
   }
-  if (any_fit) {
-    uint32_t *fit = (uint32_t *)(wh + o_fit);
-    for (int i = 0; i < n; i++) fit[i] = plan.images[(size_t)i].source == IntervalSource::SearchedWalk ? (uint32_t)plan.images[(size_t)i].n_intervals : 0u;
+
+  int upload_and_clear()
+  {
+    HIP_TRY(d, hipMemcpyAsync(d->walk_dev, d->walk_host, p.o_up_end, hipMemcpyHostToDevice, d->stream));
+    HIP_TRY(d, hipMemsetAsync(d->walk_dev + p.o_flags, 0, p.o_zero_end - p.o_flags, d->stream));
+    return MIJPEG_OK;
   }
-  HIP_TRY(d, hipMemcpyAsync(wd, wh, o_up_end, hipMemcpyHostToDevice, d->stream));
-  HIP_TRY(d, hipMemsetAsync(wd + o_flags, 0, o_zero_end - o_flags, d->stream));
-  if (any_fit) { // (behind the search on this stream, behind the upload and the cleared status words, in front of the first round)
+
+  // (behind the search on this stream, behind the upload and the cleared status words, in front of the first round)
+  int fit_step(const MarkerArgs &search, const DeviceIntervals &intervals)
+  {
+    uint8_t *const wd = d->walk_dev;
     MarkerFitArgs fit;
     memset(&fit, 0, sizeof(fit));
     fit.images = search.images;
     fit.results = search.results;
-    fit.fit_intervals = (const uint32_t *)(wd + o_fit);
-    fit.img_e1 = (uint32_t *)(wd + o_e1);
-    fit.img_nsub = (uint32_t *)(wd + o_insub);
-    fit.walk_status = (uint32_t *)(wd + o_flags) + MAX_ROUNDS + 1;
+    fit.fit_intervals = (const uint32_t *)(wd + p.o_fit);
+    fit.img_e1 = (uint32_t *)(wd + p.o_e1);
+    fit.img_nsub = (uint32_t *)(wd + p.o_insub);
+    fit.walk_status = (uint32_t *)(wd + p.o_flags) + WALK_MAX_ROUNDS + 1;
     fit.iend = intervals.iend;
-    fit.sub_bytes = sub_bytes;
-    fit.n_images = (uint32_t)n;
+    fit.sub_bytes = p.sub_bytes;
+    fit.n_images = (uint32_t)p.n;
     if (launch_marker_fit(fit, d->stream)) return hip_fail(d, hipGetLastError(), "marker_fit_kernel launch");
+    return MIJPEG_OK;
   }
-  w.data = scan.data;
-  w.images = scan.images;
-  w.tables = scan.tables;
-  w.sub_image = (const uint32_t *)(wd + o_simg);
-  w.sub_first = (const uint32_t *)(wd + o_sfirst);
-  w.img_sub0 = (const uint32_t *)(wd + o_isub0);
-  w.img_nsub = (const uint32_t *)(wd + o_insub);
-  w.img_e0 = (const uint32_t *)(wd + o_e0);
-  w.img_e1 = (const uint32_t *)(wd + o_e1);
-  w.img_int0 = (const uint32_t *)(wd + o_int0);
-  w.state = (uint64_t *)(wd + o_state);
-  w.stamp = (uint32_t *)(wd + o_stamp);
-  w.changed = (uint32_t *)(wd + o_flags);
-  w.walk_status = w.changed + MAX_ROUNDS + 1;
-  w.nblocks = (uint32_t *)(wd + o_nblk);
-  w.dcsum = (int32_t *)(wd + o_dcsum);
-  w.first_block = (uint32_t *)(wd + o_fblk);
-  w.first_pred = (int32_t *)(wd + o_fpred);
-  w.tile_sums = (WalkSums *)(wd + o_tiles);
-  w.tiles_per_image = tiles;
-  w.ibegin = intervals.ibegin;
-  w.iskip = intervals.iskip;
-  w.ipred = intervals.ipred;
-  if (!per_image) {
-    // one interval size and one block count for the launch: the images share their geometry, hence their MCUs per virtual interval
-    int per = 0;
-    for (int i = 0; i < n; i++)
-      if (dwalk(i)) per = dwalk(i);
-    w.emit_every = (uint32_t)(per * B);
-    w.total_blocks = (uint32_t)((int64_t)s0.mcus_x * s0.mcus_y * B);
+
+  // `scan`: the argument block of the decode that follows (its data, images, tables and MCU are the walk's)
+  void arguments(const HuffScanArgs &scan, const DeviceIntervals &intervals, const WalkImage *images)
+  {
+    uint8_t *const wd = d->walk_dev;
+    memset(&w, 0, sizeof(w));
+    w.ncomp = scan.ncomp;
+    for (int k = 0; k < scan.ncomp; k++) {
+      w.hs[k] = scan.hs[k];
+      w.vs[k] = scan.vs[k];
+    }
+    w.nblk_mcu = p.nblk_mcu;
+    w.ntables = scan.ntables;
+    w.sub_bytes = p.sub_bytes;
+    w.lanes = p.lanes;
+    w.waves_per_group = WAVES_PER_GROUP;
+    w.n_groups = (int32_t)p.sub_image.size();
+    w.data = scan.data;
+    w.images = scan.images;
+    w.tables = scan.tables;
+    w.sub_image = (const uint32_t *)(wd + p.o_simg);
+    w.sub_first = (const uint32_t *)(wd + p.o_sfirst);
+    w.img_sub0 = (const uint32_t *)(wd + p.o_isub0);
+    w.img_nsub = (const uint32_t *)(wd + p.o_insub);
+    w.img_e0 = (const uint32_t *)(wd + p.o_e0);
+    w.img_e1 = (const uint32_t *)(wd + p.o_e1);
+    w.img_int0 = (const uint32_t *)(wd + p.o_int0);
+    w.state = (uint64_t *)(wd + p.o_state);
+    w.stamp = (uint32_t *)(wd + p.o_stamp);
+    w.changed = (uint32_t *)(wd + p.o_flags);
+    w.walk_status = w.changed + WALK_MAX_ROUNDS + 1;
+    w.nblocks = (uint32_t *)(wd + p.o_nblk);
+    w.dcsum = (int32_t *)(wd + p.o_dcsum);
+    w.first_block = (uint32_t *)(wd + p.o_fblk);
+    w.first_pred = (int32_t *)(wd + p.o_fpred);
+    w.tile_sums = (WalkSums *)(wd + p.o_tiles);
+    w.tiles_per_image = p.tiles;
+    w.ibegin = intervals.ibegin;
+    w.iskip = intervals.iskip;
+    w.ipred = intervals.ipred;
+    if (p.per_image) {
+      w.img_emit_every = (const uint32_t *)(wd + p.o_every);
+      w.img_total_blocks = (const uint32_t *)(wd + p.o_blocks);
+    } else {
+      // one interval size and one block count for the launch: the images share their geometry, hence their MCUs per virtual interval
+      int per = 0;
+      for (int i = 0; i < p.n; i++)
+        if (images[i].device_walked) per = images[i].mcus_per_interval;
+      w.emit_every = (uint32_t)(per * p.nblk_mcu);
+      w.total_blocks = (uint32_t)(images[0].total_mcus * p.nblk_mcu);
+    }
   }
+
+  int read_flags()
+  {
+    HIP_TRY(d, hipMemcpyAsync(flags_host(), d->walk_dev + p.o_flags, (size_t)(WALK_MAX_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, d->stream));
+    return MIJPEG_OK;
+  }
+
+  // mijpeg_submit_batch_device: nobody looks at the flags between the rounds.  Enough rounds for the states to settle are
+  // launched in one go -- a round in which no lane is dirty costs a few microseconds (its workgroups leave before they
+  // load their tables) -- and whoever waits for the batch checks that the last one changed nothing (finish_batch).
+  int rounds_in_one_go()
+  {
+    int round = 0;
+    while (round < p.defer_rounds) {
+      w.round = (uint32_t)++round;
+      if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+    }
+    if (const int rc = read_flags()) return rc;
+    d->pend_walk_round = round;
+    d->pend_walk_flags = flags_host();
+    d->walk_rounds = 1;
+    return MIJPEG_OK;
+  }
+
   // rounds, launched back to back in bunches; between bunches the host looks at the flags: a round that changed no
   // hand-over state means the states are the fixed point (and the counts of the lanes' last walks belong to it)
-  uint32_t *flags_host = (uint32_t *)(wh + o_up_end);
-  constexpr int FIRST_BUNCH = 8;
-  int round = 0;
-  if (defer) {
-    // mijpeg_submit_batch_device: nobody looks at the flags between the rounds.  Enough rounds for the states to settle are
-    // launched in one go -- a round in which no lane is dirty costs a few microseconds (its workgroups leave before they
-    // load their tables) -- and whoever waits for the batch checks that the last one changed nothing (finish_batch).
-    const int rounds = std::min(MAX_ROUNDS, sub_bytes >= 512 ? 16 : sub_bytes >= 256 ? 24 : 40);
-    while (round < rounds) {
-      w.round = (uint32_t)++round;
-      if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+  int rounds_until_settled()
+  {
+    constexpr int FIRST_BUNCH = 8;
+    int round = 0;
+    for (;;) {
+      const int upto = round == 0 ? FIRST_BUNCH : std::min(WALK_MAX_ROUNDS, round + 4);
+      while (round < upto) {
+        w.round = (uint32_t)++round;
+        if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+        if (walk_launches) ++*walk_launches;
+      }
+      if (const int rc = read_flags()) return rc;
+      HIP_TRY(d, hipStreamSynchronize(d->stream));
+      if (!flags_host()[round]) break;
+      if (round == WALK_MAX_ROUNDS) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding did not settle");
     }
-    HIP_TRY(d, hipMemcpyAsync(flags_host, wd + o_flags, (size_t)(MAX_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, d->stream));
-    d->pend_walk_round = round;
-    d->pend_walk_flags = flags_host;
+    d->walk_rounds = walk_rounds_needed(flags_host(), round);
+    return MIJPEG_OK;
   }
-  for (; !defer;) {
-    const int upto = round == 0 ? FIRST_BUNCH : std::min(MAX_ROUNDS, round + 4);
-    while (round < upto) {
-      w.round = (uint32_t)++round;
-      if (launch_huffman_walk(w, false, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
-      if (walk_launches) ++*walk_launches;
-    }
-    HIP_TRY(d, hipMemcpyAsync(flags_host, wd + o_flags, (size_t)(MAX_ROUNDS + 1) * 4, hipMemcpyDeviceToHost, d->stream));
-    HIP_TRY(d, hipStreamSynchronize(d->stream));
-    if (!flags_host[round]) break;
-    if (round == MAX_ROUNDS) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "speculative decoding did not settle");
+
+  // prefix sums over the subsequences, and the EMIT walk that writes the interval tables
+  int sums_and_emit()
+  {
+    if (launch_huffman_walk_scan(w, p.n, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_scan_kernel launch");
+    if (launch_huffman_walk(w, true, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
+    if (walk_launches) ++*walk_launches;
+    d->walk_status_dev = w.walk_status;
+    return MIJPEG_OK;
   }
-  d->walk_rounds = defer ? 1 : walk_rounds_needed(flags_host, round);
-  if (launch_huffman_walk_scan(w, n, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_scan_kernel launch");
-  if (launch_huffman_walk(w, true, d->stream)) return hip_fail(d, hipGetLastError(), "huffman_walk_kernel launch");
-  if (walk_launches) ++*walk_launches;
-  d->walk_status_dev = w.walk_status;
-  return MIJPEG_OK;
+};
+
+} // namespace
+
+static int device_walk_images(mijpeg_decoder *d, HostDecoder *const *hosts, const BatchPlan &plan, const EntropyBatchOptions &opt, const HuffScanArgs &scan,
+                              const DeviceIntervals &intervals, const MarkerArgs &search)
+{
+  // (the MCU of the decode that follows -- scan_args filled hs / vs with mcu_blocks of hosts[0]'s scan, and the walk must step through
+  // the same blocks: it reads them there instead of deriving them a second time)
+  int nblk_mcu = 0;
+  for (int k = 0; k < scan.ncomp; k++) nblk_mcu += scan.hs[k] * scan.vs[k];
+  const std::vector<WalkImage> images = walk_images(hosts, plan);
+  WalkPlan wp;
+  if (const char *why = plan_walk(images.data(), plan.n(), opt.ragged != nullptr, nblk_mcu, wp)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
+  WalkRun run{d, wp, opt.ragged ? opt.ragged->walk_launches : nullptr, HuffWalkArgs()};
+  int rc;
+  if ((rc = run.ensure())) return rc;
+  fill_walk(wp, images.data(), d->walk_host);
+  if ((rc = run.upload_and_clear())) return rc;
+  if (wp.any_fit && (rc = run.fit_step(search, intervals))) return rc;
+  run.arguments(scan, intervals, images.data());
+  if ((rc = opt.defer ? run.rounds_in_one_go() : run.rounds_until_settled())) return rc;
+  return run.sums_and_emit();
 }
 
 // What the Huffman kernel left in the status words of n images: errors, and per image the range check that selects the
@@ -589,51 +540,6 @@ int evaluate_entropy_status(mijpeg_decoder *d, HostDecoder *const *hosts, int n,
     if (f.precision != 8) f.fast_arith = 0; // (as HostDecoder::decode has it: the fast flavour is derived for 8-bit frames; 12-bit kernels gate on range_max)
   }
   return MIJPEG_OK;
-}
-
-// Second-level tables of a device Huffman table: every code longer than the direct table's ten bits, grouped by its first
-// ten bits, in a 64-entry table indexed by the six bits that follow (entries as in the direct table: huff_dev_entry).  Codes
-// whose prefix finds no table left keep the direct entry HUFF_DEV_SUB | HUFF_DEV_NO_SUB: the kernels walk the canonical arrays
-// for those.
-static void fill_second_level(HuffDevTable &dst, const HuffTable &h, int ac)
-{
-  int prefix_of[HUFF_DEV_SUBTABLES], used = 0;
-  int code = 0, k = 0;
-  for (int l = 1; l <= 16; l++) {
-    for (int i = 0; i < h.counts[l - 1]; i++, code++, k++) {
-      if (l <= HUFF_DEV_LOOKAHEAD || k >= 256) continue;
-      if (code >= (1 << l)) return; // over-subscribed lengths: the host refuses such tables anyway
-      const int prefix = code >> (l - HUFF_DEV_LOOKAHEAD), rest = l - HUFF_DEV_LOOKAHEAD; // 1..6 bits behind the prefix
-      int t = 0;
-      while (t < used && prefix_of[t] != prefix) t++;
-      if (t == used) {
-        if (used == HUFF_DEV_SUBTABLES) continue;
-        prefix_of[used++] = prefix;
-        dst.fast[prefix] = (uint16_t)(HUFF_DEV_SUB | t);
-      }
-      const uint16_t e = (uint16_t)huff_dev_entry(l, h.values[k], ac);
-      const int first = (code & ((1 << rest) - 1)) << (6 - rest);
-      for (int j = 0; j < (1 << (6 - rest)); j++) dst.sub[t][first + j] = e;
-    }
-    code <<= 1;
-  }
-}
-
-// The host's decoder table in the device's form (huffman_dev.hpp): direct entries, second-level tables, the canonical arrays.
-// mode: 0 DC, 1 AC of a sequential scan, 2 AC of a progressive / refinement scan (huff_dev_entry).
-static void build_dev_table(HuffDevTable &dst, const HuffTable &src, int mode)
-{
-  memset(&dst, 0, sizeof(dst));
-  // the host's direct table ((length << 8) | symbol, 0 = a longer code or none) in the device's entry format
-  for (int x = 0; x < (1 << HUFF_DEV_LOOKAHEAD); x++) {
-    const uint16_t he = src.fast[x];
-    dst.fast[x] = he ? (uint16_t)huff_dev_entry(he >> 8, he & 0xffu, mode) : (uint16_t)(HUFF_DEV_SUB | HUFF_DEV_NO_SUB);
-  }
-  static const bool no_sub = getenv("MIJPEG_HUFF_NO_SUBTABLES") != nullptr; // A-B measurements: long codes walk the canonical arrays
-  if (!no_sub) fill_second_level(dst, src, mode);
-  memcpy(dst.maxcode, src.maxcode, sizeof(dst.maxcode));
-  memcpy(dst.valoff, src.valoff, sizeof(dst.valoff));
-  memcpy(dst.values, src.values, sizeof(dst.values));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1333,254 +1239,176 @@ const char *multiscan_obstacle(const HostDecoder &h, bool xt_part, bool residual
   return nullptr;
 }
 
+namespace {
+
+// The range pass over one frame's finished planes
+CoefRangeArgs coef_range_args(const mijpeg_decoder *d, const MultiScanFrame &fr, uint32_t *status)
+{
+  const mijpeg_info &f = fr.h->info;
+  CoefRangeArgs r;
+  memset(&r, 0, sizeof(r));
+  r.coef = (const void *)(d->coef_dev + fr.base16);
+  r.wide = fr.wide ? 1 : 0;
+  r.ncomp = f.components;
+  for (int c = 0; c < f.components; c++) {
+    r.coef_off[c] = plane_offset(f, c);
+    r.nblocks[c] = (int64_t)f.blocks_w[c] * f.blocks_h[c];
+    memcpy(r.q[c], f.quant[f.quant_index[c]], sizeof(r.q[c]));
+  }
+  r.status = status;
+  return r;
+}
+
+// device_entropy_multiscan's stages behind plan and staging (entropy_plan.hpp).  The entropy coded data of every scan without its
+// stuffing is gathered by the pool in two goes: what the first launches read, then the rest -- while the copy engine brings up the
+// first part and the first launches run.  Uploads on the copy stream, one event per level; the frames' launches wait for their
+// level's event.
+struct MultiscanRun {
+  mijpeg_decoder *d;
+  const MultiScanFrame *frames;
+  int nframes;
+  const MultiscanPlan &p;
+  hipStream_t second; // the two frames of a JPEG XT file share nothing: the second one's launches go to a stream of their own
+  ProgArgs a;
+  Gather gather;
+
+  uint8_t *tail_dev() const { return d->ent_dev + p.stream_bytes; }
+  uint32_t *status_dev(int fi) const { return (uint32_t *)(tail_dev() + p.status) + 8 * fi; }
+  hipStream_t stream_of(int fi) const { return fi == 0 ? d->stream : second; }
+
+  int prepare_second_stream()
+  {
+    second = d->stream;
+    if (nframes > 1) {
+      if (!d->ms_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->ms_stream, hipStreamNonBlocking));
+      if (!d->ms_ready) HIP_TRY(d, hipEventCreateWithFlags(&d->ms_ready, hipEventDisableTiming));
+      if (!d->ms_done) HIP_TRY(d, hipEventCreateWithFlags(&d->ms_done, hipEventDisableTiming));
+      second = d->ms_stream;
+    }
+    return MIJPEG_OK;
+  }
+
+  // what every launch shares (launch_levels: its workgroups, lanes, frame)
+  void arguments()
+  {
+    uint8_t *const dp = tail_dev();
+    memset(&a, 0, sizeof(a));
+    a.data = d->ent_dev;
+    a.ibegin = (const uint32_t *)(dp + p.ibegin);
+    a.iend = (const uint32_t *)(dp + p.iend);
+    a.scans = (const ProgScanDev *)(dp + p.scans);
+    a.waves_per_group = WAVES_PER_GROUP;
+    a.max_tables = p.max_tables;
+    a.tables = dp + p.tables;
+  }
+
+  void gather_levels(int lv0, int lv1)
+  {
+    for (const MultiscanPlan::Item &it : p.items)
+      if (it.level >= lv0 && it.level < lv1) gather.add(frames[it.frame].h, it.scan, d->stage_host + it.stream_off);
+    gather.run();
+  }
+
+  // (tables, intervals, descriptors and groups travel in front of level 0's bytes)
+  int upload_levels(int lv0, int lv1)
+  {
+    for (int lv = lv0; lv < lv1; lv++) {
+      const size_t b0 = lv ? p.level_end[(size_t)lv - 1] : 0, b1 = p.level_end[(size_t)lv];
+      if (lv == 0) HIP_TRY(d, hipMemcpyAsync(tail_dev(), d->ent_host, p.status, hipMemcpyHostToDevice, d->copy_stream));
+      if (b1 > b0) HIP_TRY(d, hipMemcpyAsync(d->ent_dev + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
+      HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)lv], d->copy_stream));
+    }
+    return MIJPEG_OK;
+  }
+
+  int clear_status_and_planes()
+  {
+    HIP_TRY(d, hipMemsetAsync(tail_dev() + p.status, 0, p.status_bytes, d->stream));
+    if (nframes > 1) { // (behind whatever the object's stream still does with the planes, and the cleared status words)
+      HIP_TRY(d, hipEventRecord(d->ms_ready, d->stream));
+      HIP_TRY(d, hipStreamWaitEvent(second, d->ms_ready, 0));
+    }
+    // coefficients accumulate over the scans: the planes start out as zeros (coding/blockrow.cpp:77-87)
+    for (int fi = 0; fi < nframes; fi++) {
+      const mijpeg_info &f = frames[fi].h->info;
+      int64_t count = 0;
+      for (int c = 0; c < f.components; c++) count += (int64_t)f.blocks_w[c] * f.blocks_h[c] * 64;
+      HIP_TRY(d, hipMemsetAsync(d->coef_dev + frames[fi].base16, 0, (size_t)count * (frames[fi].wide ? 4 : 2), stream_of(fi)));
+    }
+    return MIJPEG_OK;
+  }
+
+  int launch_levels(int lv0, int lv1)
+  {
+    for (const MultiscanPlan::Launch &l : p.launches) {
+      const int fi = l.frame, lv = l.level;
+      if (lv < lv0 || lv >= lv1) continue;
+      HIP_TRY(d, hipStreamWaitEvent(stream_of(fi), d->copy_events[(size_t)lv], 0));
+      a.groups = (const ProgGroup *)(tail_dev() + p.groups) + l.g0;
+      a.n_groups = (int32_t)l.groups;
+      a.lanes = p.level_lanes[(size_t)fi][(size_t)lv];
+      a.wide = frames[fi].wide ? 1 : 0;
+      a.coef = (void *)(d->coef_dev + frames[fi].base16);
+      a.status = status_dev(fi);
+      if (launch_huffman_prog(a, stream_of(fi))) return hip_fail(d, hipGetLastError(), "huffman_prog_kernel launch");
+    }
+    return MIJPEG_OK;
+  }
+
+  int join_second_stream()
+  {
+    if (second == d->stream) return MIJPEG_OK;
+    HIP_TRY(d, hipEventRecord(d->ms_done, second));
+    HIP_TRY(d, hipStreamWaitEvent(d->stream, d->ms_done, 0));
+    return MIJPEG_OK;
+  }
+
+  int range_pass()
+  {
+    for (int fi = 0; fi < nframes; fi++)
+      if (launch_coef_range(coef_range_args(d, frames[fi], status_dev(fi)), d->stream)) return hip_fail(d, hipGetLastError(), "coef_range_kernel launch");
+    return MIJPEG_OK;
+  }
+};
+
+} // namespace
+
 // All scans of the given frames (one file: a progressive picture, or the two frames of a JPEG XT file): upload of the entropy
 // coded data without its stuffing, planes cleared, the scans launched level by level (scans that share a component one after
 // the other, the rest side by side), range pass.  MIJPEG_ERR_NOT_AVAILABLE: the host decoder's.
 int device_entropy_multiscan(mijpeg_decoder *d, const MultiScanFrame *frames, int nframes, int min_intervals)
 {
-  struct Item { int frame; size_t scan; int level; int64_t nint; size_t stream_off; size_t table_off; int ntab; int dc_tab[4], ac_tab[4]; int64_t first; };
-  std::vector<Item> items;
   const TraceMarks mark{"mijpeg multiscan"};
-  size_t table_bytes = 0;
-  int64_t total_intervals = 0;
-  int max_tables = 1;
-  std::vector<int> frame_levels((size_t)nframes, 0);
-  for (int fi = 0; fi < nframes; fi++) {
-    const HostDecoder &h = *frames[fi].h;
-    std::vector<int> level(h.scans.size(), 0);
-    for (size_t j = 0; j < h.scans.size(); j++) {
-      const Scan &b = h.scans[j];
-      // (a scan of the AC kind writes whole blocks back: two scans that share a component never run side by side)
-      for (size_t i = 0; i < j; i++) {
-        const Scan &a = h.scans[i];
-        bool common = false;
-        for (int ka = 0; ka < a.ncomp; ka++)
-          for (int kb = 0; kb < b.ncomp; kb++) common |= a.sc[ka].comp == b.sc[kb].comp;
-        if (common) level[j] = std::max(level[j], level[i] + 1);
-      }
-      Item it;
-      memset(&it, 0, sizeof(it));
-      it.frame = fi;
-      it.scan = j;
-      it.level = level[j];
-      const int64_t total_mcus = (int64_t)b.mcus_x * b.mcus_y;
-      it.nint = b.restart_interval > 0 ? (total_mcus + b.restart_interval - 1) / b.restart_interval : 1;
-      it.table_off = table_bytes;
-      for (int k = 0; k < b.ncomp; k++) {
-        it.dc_tab[k] = it.ac_tab[k] = 0;
-        if (b.ss == 0 && b.ah == 0) it.dc_tab[k] = it.ntab++;
-        if (b.se > 0) it.ac_tab[k] = it.ntab++;
-      }
-      table_bytes += (size_t)it.ntab * sizeof(HuffDevTable);
-      max_tables = std::max(max_tables, it.ntab);
-      it.first = total_intervals;
-      total_intervals += it.nint;
-      frame_levels[(size_t)fi] = std::max(frame_levels[(size_t)fi], level[j] + 1);
-      items.push_back(it);
-    }
-  }
-  // The entropy coded data lies in the upload level by level: what the first launches read goes up first, and the rest is
-  // gathered and uploaded while they run (level_end[l]: end of level l's bytes).
-  int n_levels = 0;
-  for (int fi = 0; fi < nframes; fi++) n_levels = std::max(n_levels, frame_levels[(size_t)fi]);
-  std::vector<size_t> level_end((size_t)n_levels, 0);
-  Layout streams;
-  for (int lv = 0; lv < n_levels; lv++) {
-    for (Item &it : items)
-      if (it.level == lv) it.stream_off = streams.take(frames[it.frame].h->scans[it.scan].unstuffed_size + HUFF_STREAM_PAD);
-    level_end[(size_t)lv] = streams.end;
-  }
-  const size_t stream_bytes = streams.end;
-  if (stream_bytes > 0xfffffff0ull || total_intervals > 0x7fffffff) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "file too large for one device decode");
-  // the largest launch decides whether the device is worth the trip ("auto"); every launch -- the scans of one level of one
-  // frame -- picks how many lanes of a wave decode by its own number of intervals: fewer lanes = more waves, less divergence
-  const int waves = WAVES_PER_GROUP;
-  int64_t widest = 0, n_groups = 0;
-  std::vector<std::vector<int>> level_lanes((size_t)nframes);
-  for (int fi = 0; fi < nframes; fi++)
-    for (int lv = 0; lv < frame_levels[(size_t)fi]; lv++) {
-      int64_t n = 0;
-      for (const Item &it : items)
-        if (it.frame == fi && it.level == lv) n += it.nint;
-      widest = std::max(widest, n);
-      const int lanes = lanes_for(n);
-      level_lanes[(size_t)fi].push_back(lanes);
-      for (const Item &it : items)
-        if (it.frame == fi && it.level == lv) n_groups += (it.nint + lanes * waves - 1) / (lanes * waves);
-    }
-  if (min_intervals <= 0) min_intervals = 2048;
-  if (widest < min_intervals) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, "too few restart intervals to occupy the device");
-  // device buffer: [streams][ibegin][iend][tables][scans][groups][status: 8 dwords per frame]; offsets behind the streams: in
-  // the device buffer at dp, in pinned staging at hp
-  Layout L;
-  const size_t off_ib = L.take((size_t)total_intervals * 4), off_ie = L.take((size_t)total_intervals * 4), off_tab = L.take(table_bytes);
-  const size_t off_scan = L.take(items.size() * sizeof(ProgScanDev)), off_grp = L.take((size_t)n_groups * sizeof(ProgGroup));
-  const size_t status_bytes = (size_t)nframes * 32, off_status = L.take(status_bytes);
-  int rc = ensure_entropy_buffers(d, stream_bytes, L.end);
-  if (rc) return rc;
-  rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, stream_bytes);
-  if (rc) return rc;
-  uint8_t *const hp = d->ent_host, *const dp = d->ent_dev + stream_bytes;
-  uint32_t *ib = (uint32_t *)(hp + off_ib), *ie = (uint32_t *)(hp + off_ie);
-  ProgScanDev *sd = (ProgScanDev *)(hp + off_scan);
-  ProgGroup *groups = (ProgGroup *)(hp + off_grp);
-  // groups in launch order: frame, level, scan
-  struct Launch { int frame, level; int64_t g0, groups; };
-  std::vector<Launch> launches;
-  int64_t g = 0;
-  for (int fi = 0; fi < nframes; fi++)
-    for (int lv = 0; lv < frame_levels[(size_t)fi]; lv++) {
-      const int64_t g0 = g;
-      const int per_group = level_lanes[(size_t)fi][(size_t)lv] * waves;
-      for (size_t ii = 0; ii < items.size(); ii++) {
-        const Item &it = items[ii];
-        if (it.frame != fi || it.level != lv) continue;
-        for (int64_t k = 0; k < it.nint; k += per_group) {
-          groups[g].scan = (uint32_t)ii;
-          groups[g].first_interval = (uint32_t)k;
-          g++;
-        }
-      }
-      if (g > g0) launches.push_back(Launch{fi, lv, g0, g - g0});
-    }
-  for (size_t ii = 0; ii < items.size(); ii++) {
-    const Item &it = items[ii];
-    const HostDecoder &h = *frames[it.frame].h;
-    const mijpeg_info &f = h.info;
-    const Scan &s = h.scans[it.scan];
-    ProgScanDev &o = sd[ii];
-    memset(&o, 0, sizeof(o));
-    o.stream_off = (uint32_t)it.stream_off;
-    o.first_interval = (uint32_t)it.first;
-    o.n_intervals = (int32_t)it.nint;
-    o.total_mcus = s.mcus_x * s.mcus_y;
-    o.restart_interval = s.restart_interval > 0 ? s.restart_interval : o.total_mcus;
-    o.mcus_x = s.mcus_x;
-    o.ncomp = s.ncomp;
-    o.ntables = it.ntab;
-    o.table_off = (uint32_t)it.table_off;
-    o.ss = s.ss; o.se = s.se; o.ah = s.ah; o.al = s.al;
-    o.runs_legal = s.progressive_run ? 1 : 0;
-    HuffDevTable *tabs = (HuffDevTable *)(hp + off_tab + it.table_off);
-    for (int k = 0; k < s.ncomp; k++) {
-      const int c = s.sc[k].comp;
-      o.comp[k] = c;
-      const McuBlocks b = mcu_blocks(f, s, k);
-      o.hs[k] = b.h;
-      o.vs[k] = b.v;
-      o.bw[k] = f.blocks_w[c];
-      o.coef_off[k] = f.coef_offset[c] / (f.coef_wide ? 2 : 1);
-      o.dc_tab[k] = it.dc_tab[k];
-      o.ac_tab[k] = it.ac_tab[k];
-      if (s.ss == 0 && s.ah == 0) build_dev_table(tabs[it.dc_tab[k]], s.dc[k], 0);
-      if (s.se > 0) build_dev_table(tabs[it.ac_tab[k]], s.ac[k], 2);
-    }
-    memcpy(ib + it.first, s.interval_ubegin.data(), (size_t)it.nint * sizeof(uint32_t)); // (multiscan_obstacle: both lists hold nint entries at least)
-    memcpy(ie + it.first, s.interval_uend.data(), (size_t)it.nint * sizeof(uint32_t));
-  }
+  std::vector<FrameScans> views;
+  for (int fi = 0; fi < nframes; fi++) views.push_back(FrameScans{&frames[fi].h->info, &frames[fi].h->scans});
+  MultiscanPlan plan;
+  if (const char *why = plan_multiscan(views.data(), nframes, min_intervals, plan)) return set_error(d, MIJPEG_ERR_NOT_AVAILABLE, why);
+  int rc;
+  if ((rc = ensure_entropy_buffers(d, plan.stream_bytes, plan.end))) return rc;
+  if ((rc = ensure_pinned(d, &d->stage_host, &d->stage_cap, plan.stream_bytes))) return rc;
+  fill_multiscan(plan, views.data(), d->ent_host);
   mark("tables + intervals");
-  // The entropy coded data of every scan without its stuffing, gathered by the pool in two goes: what the first launches read
-  // (level 0 of every frame), then the rest -- while the copy engine brings up the first part and the first launches run.
-  // Uploads on the copy stream, one event per level; the frames' launches wait for their level's event.
-  Gather gather;
-  auto gather_levels = [&](int lv0, int lv1) {
-    for (const Item &it : items)
-      if (it.level >= lv0 && it.level < lv1) gather.add(frames[it.frame].h, it.scan, d->stage_host + it.stream_off);
-    gather.run();
-  };
   QuiesceOnError guard{d};
   guard.armed = true;
-  if ((rc = prepare_copy_stream(d, (size_t)n_levels))) return rc;
-  auto upload_levels = [&](int lv0, int lv1) -> int {
-    for (int lv = lv0; lv < lv1; lv++) {
-      const size_t b0 = lv ? level_end[(size_t)lv - 1] : 0, b1 = level_end[(size_t)lv];
-      if (lv == 0) HIP_TRY(d, hipMemcpyAsync(dp, hp, off_status, hipMemcpyHostToDevice, d->copy_stream));
-      if (b1 > b0) HIP_TRY(d, hipMemcpyAsync(d->ent_dev + b0, d->stage_host + b0, b1 - b0, hipMemcpyHostToDevice, d->copy_stream));
-      HIP_TRY(d, hipEventRecord(d->copy_events[(size_t)lv], d->copy_stream));
-    }
-    return 0;
-  };
-  ProgArgs a;
-  memset(&a, 0, sizeof(a));
-  a.data = d->ent_dev;
-  a.ibegin = (const uint32_t *)(dp + off_ib);
-  a.iend = (const uint32_t *)(dp + off_ie);
-  a.scans = (const ProgScanDev *)(dp + off_scan);
-  a.waves_per_group = waves;
-  a.max_tables = max_tables;
-  a.tables = dp + off_tab;
-  // the two frames of a JPEG XT file share nothing: the second one's launches go to a stream of their own
-  hipStream_t second = d->stream;
-  if (nframes > 1) {
-    if (!d->ms_stream) HIP_TRY(d, hipStreamCreateWithFlags(&d->ms_stream, hipStreamNonBlocking));
-    if (!d->ms_ready) HIP_TRY(d, hipEventCreateWithFlags(&d->ms_ready, hipEventDisableTiming));
-    if (!d->ms_done) HIP_TRY(d, hipEventCreateWithFlags(&d->ms_done, hipEventDisableTiming));
-    second = d->ms_stream;
-  }
-  auto launch_levels = [&](int lv0, int lv1) -> int {
-    for (const Launch &l : launches) {
-      const int fi = l.frame, lv = l.level;
-      if (lv < lv0 || lv >= lv1) continue;
-      hipStream_t st = fi == 0 ? d->stream : second;
-      HIP_TRY(d, hipStreamWaitEvent(st, d->copy_events[(size_t)lv], 0));
-      a.groups = (const ProgGroup *)(dp + off_grp) + l.g0;
-      a.n_groups = (int32_t)l.groups;
-      a.lanes = level_lanes[(size_t)fi][(size_t)lv];
-      a.wide = frames[fi].wide ? 1 : 0;
-      a.coef = (void *)(d->coef_dev + frames[fi].base16);
-      a.status = (uint32_t *)(dp + off_status) + 8 * fi;
-      if (launch_huffman_prog(a, st)) return hip_fail(d, hipGetLastError(), "huffman_prog_kernel launch");
-    }
-    return 0;
-  };
-  // where to cut: behind the first level that brings a quarter of the bytes (a progressive frame's DC scan alone is over before
-  // anything could hide behind it); no cut when that is the last level
-  int cut = n_levels;
-  for (int lv = 0; lv + 1 < n_levels; lv++)
-    if (level_end[(size_t)lv] * 4 >= stream_bytes) { cut = lv + 1; break; }
-  gather_levels(0, cut);
+  if ((rc = prepare_copy_stream(d, (size_t)plan.levels()))) return rc;
+  MultiscanRun run{d, frames, nframes, plan, d->stream, ProgArgs(), Gather{}};
+  if ((rc = run.prepare_second_stream())) return rc;
+  run.arguments();
+  run.gather_levels(0, plan.cut);
   mark("first levels gathered");
-  if ((rc = upload_levels(0, cut))) return rc;
-  HIP_TRY(d, hipMemsetAsync(dp + off_status, 0, status_bytes, d->stream));
-  if (nframes > 1) { // (behind whatever the object's stream still does with the planes, and the cleared status words)
-    HIP_TRY(d, hipEventRecord(d->ms_ready, d->stream));
-    HIP_TRY(d, hipStreamWaitEvent(second, d->ms_ready, 0));
-  }
-  // coefficients accumulate over the scans: the planes start out as zeros (coding/blockrow.cpp:77-87)
-  for (int fi = 0; fi < nframes; fi++) {
-    const mijpeg_info &f = frames[fi].h->info;
-    int64_t count = 0;
-    for (int c = 0; c < f.components; c++) count += (int64_t)f.blocks_w[c] * f.blocks_h[c] * 64;
-    HIP_TRY(d, hipMemsetAsync(d->coef_dev + frames[fi].base16, 0, (size_t)count * (frames[fi].wide ? 4 : 2), fi == 0 ? d->stream : second));
-  }
-  if ((rc = launch_levels(0, cut))) return rc;
-  if (cut < n_levels) {
-    gather_levels(cut, n_levels);
+  if ((rc = run.upload_levels(0, plan.cut))) return rc;
+  if ((rc = run.clear_status_and_planes())) return rc;
+  if ((rc = run.launch_levels(0, plan.cut))) return rc;
+  if (plan.cut < plan.levels()) {
+    run.gather_levels(plan.cut, plan.levels());
     mark("other levels gathered");
-    if ((rc = upload_levels(cut, n_levels))) return rc;
-    if ((rc = launch_levels(cut, n_levels))) return rc;
+    if ((rc = run.upload_levels(plan.cut, plan.levels()))) return rc;
+    if ((rc = run.launch_levels(plan.cut, plan.levels()))) return rc;
   }
-  if (second != d->stream) {
-    HIP_TRY(d, hipEventRecord(d->ms_done, second));
-    HIP_TRY(d, hipStreamWaitEvent(d->stream, d->ms_done, 0));
-  }
-  for (int fi = 0; fi < nframes; fi++) {
-    const mijpeg_info &f = frames[fi].h->info;
-    CoefRangeArgs r;
-    memset(&r, 0, sizeof(r));
-    r.coef = (const void *)(d->coef_dev + frames[fi].base16);
-    r.wide = frames[fi].wide ? 1 : 0;
-    r.ncomp = f.components;
-    for (int c = 0; c < f.components; c++) {
-      r.coef_off[c] = f.coef_offset[c] / (f.coef_wide ? 2 : 1);
-      r.nblocks[c] = (int64_t)f.blocks_w[c] * f.blocks_h[c];
-      memcpy(r.q[c], f.quant[f.quant_index[c]], sizeof(r.q[c]));
-    }
-    r.status = (uint32_t *)(dp + off_status) + 8 * fi;
-    if (launch_coef_range(r, d->stream)) return hip_fail(d, hipGetLastError(), "coef_range_kernel launch");
-  }
-  uint32_t *status_host = (uint32_t *)(hp + off_status);
-  if ((rc = read_back_status(d, status_host, dp + off_status, status_bytes))) return rc;
+  if ((rc = run.join_second_stream())) return rc;
+  if ((rc = run.range_pass())) return rc;
+  uint32_t *status_host = (uint32_t *)(d->ent_host + plan.status);
+  if ((rc = read_back_status(d, status_host, run.tail_dev() + plan.status, plan.status_bytes))) return rc;
   mark("launches enqueued");
   HIP_TRY(d, hipStreamSynchronize(d->stream));
   guard.armed = false; // (the second frame's stream and the copy stream are behind it)

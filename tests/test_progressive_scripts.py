@@ -1,6 +1,7 @@
 """huffman_prog_kernel's refinement pass (prog_block_refine: two 32-bit history masks split at scan position 32, the list of
 free positions, correction bits taken in one piece from the 32-bit window or past it, their 64-bit string and the rank of a
-coefficient in the history, EOB runs that carry corrections only) and the level schedule of device_entropy_multiscan, on scan
+coefficient in the history, EOB runs that carry corrections only) and the level schedule of device_entropy_multiscan
+(plan_multiscan in entropy_plan.hpp, whose levels, slots and lanes tests/test_entropy_plan_cpu.py asserts directly), on scan
 scripts and coefficient histories made for them (huffcraft.scripts, huffcraft.history_content): bands that end and start at the
 split of the masks, one-coefficient bands, three refinement levels over 1..63, DC with Al = 3, DC scans of one component, scans of
 different components and kinds in one launch, frames that are not whole MCUs.

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round 6: device_entropy_multiscan with the uploads level by level on the copy stream (the first launches run while the rest of the
-# file is gathered and brought up) against the build before it (tools/ab/libmijpeg_oldms.so); streams from build/ms (multiscan_probe.py make)
+# file is gathered and brought up; today plan_multiscan's `cut` in entropy_plan.hpp and MultiscanRun in entropy_device.cpp) against the build before it (tools/ab/libmijpeg_oldms.so); streams from build/ms (multiscan_probe.py make)
 ROOT="${GRAFT_REPO_ROOT:-/root/repo}"
 cd "$ROOT"; mkdir -p gpurun_out/msov; export TMPDIR=/tmp
 O=gpurun_out/msov
